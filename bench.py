@@ -36,6 +36,9 @@ Extra objects in the line:
                 max |d| of the poses and |dMPJPE| per protocol (max over the T steps), with the count of (step, protocol) pairs inside
                 north_star's 1e-4 mm (BASELINE's metric is "hypotheses/sec ...; MPJPE mm"; consumer: main_h3wb.py:344-362).
 
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (dump_outputs), for comparing two builds on the
+same seeded inputs, weights and noise output for output.
+
 N > 1: `python bench.py --gpus N` started WITHOUT torch.distributed's environment starts the N ranks itself - a child
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, before this process touches the GPU - relays
 rank 0's line and exits with the children's status; started under torch.distributed.run it is one of the ranks.
@@ -142,6 +145,11 @@ def main():
     ap.add_argument("--dump-output", default=None, metavar="FILE",
                     help="rank 0 saves the last step's gathered predictions [B,T,P,F,J,3] (torch.save): the rehearsal tests "
                          "compare them with a single-process run of the same seed")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step returned as DIR/<name>.npy (float32): "
+                         "poses [B,T,P,F,J,3]; with --train the loss and the poses of the step.  At most 64 MiB in all (beyond "
+                         "that a fixed seeded sample, see dump_outputs); the same arguments give the same inputs, so two builds "
+                         "compare output for output")
     ap.add_argument("--train-dtype", choices=("f32", "bf16x3"), default="bf16x3",
                     help="--train: matrix products of the plain GEMMs (qkv, fc1, dX): split precision (default) or fp32 MFMA")
     ap.add_argument("--no-train-leg", action="store_true",
@@ -154,6 +162,8 @@ def main():
                     help="time training steps instead (SURVEY 8f n2: fwd + bwd + AdamW, DDP over RCCL for N > 1); "
                          "--batch is then clips per GPU (default 37 = 1024 // 27, main_h3wb.py:781)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)            # (does not return; nothing above has initialised the GPU)
 
@@ -305,6 +315,7 @@ def main():
     gather_ms = copy_ms = None
     if args.dump_output and rank == 0:
         torch.save(out.cpu(), args.dump_output)
+    dumped = dump_outputs(args.dump_outputs, {"poses": out}) if args.dump_outputs and rank == 0 else None
     if world > 1:
         local = out[:, :, lo:hi].contiguous()
         gather_hypotheses(local, P_total)                      # warm-up
@@ -361,6 +372,8 @@ def main():
         "allgather_ms": gather_ms, "allgather_ms_note": "collective + the one layout pass, max over ranks", "gather_copy_ms": copy_ms,
         "roofline_loop": loop_roofline(args.dtype, sec_per_step),
     }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
 
     # ---- dominant kernel family: the linear-layer GEMM launches of one flip-TTA denoiser pass, HIP-event timed ----
     if not args.no_roofline and rank == 0:
@@ -468,6 +481,35 @@ def main():
     if world > 1:
         dist.barrier()      # ranks > 0 wait here while rank 0 runs the roofline and CPU-baseline legs
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 * 2**20     # --dump-outputs: the most the files of one run may hold together
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every named tensor as DIR/<name>.npy, float32 (float64 stays float64).  When they would hold more than
+    `limit` bytes together, each keeps its share as a fixed sample (seed 0, sorted flat positions; the same for every run of the
+    same shapes) in DIR/<name>.npy, its flat positions beside it in DIR/<name>_index.npy (float64: exact below 2**53).
+    Returns {name: shape of the file} for the result line."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.detach().cpu() for k, v in arrays.items()}
+    arrays = {k: v.double() if v.dtype == torch.float64 else v.float() for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    shapes = {}
+    for name, v in arrays.items():
+        v = v.contiguous()
+        if total > limit:
+            share = limit * v.numel() * v.element_size() // total
+            keep = max(1, share // (v.element_size() + 8))
+            idx = torch.randint(v.numel(), (keep,), generator=torch.Generator().manual_seed(0)).unique()
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.double().numpy())
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), v.numpy())
+        shapes[name] = list(v.shape)
+    print(f"[bench] wrote {sorted(shapes)} to {dirname}", file=sys.stderr, flush=True)
+    return shapes
 
 
 def parity_object(orc, out, ref, gu, x2d, P, T):
@@ -600,7 +642,7 @@ def train_bench(args, rank, local_rank, world, dev):
         loss = torch.mean(torch.norm(pred - target, dim=-1))          # common/loss.py:27-34 (mpjpe)
         loss.backward()
         opt.step()
-        return loss
+        return loss, pred
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -609,14 +651,15 @@ def train_bench(args, rank, local_rank, world, dev):
         torch.cuda.synchronize(dev)
 
     for _ in range(max(args.warmup, 1)):
-        loss = step()
+        loss, pred = step()
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, pred = step()
     fence()
     elapsed = time.perf_counter() - t0
     assert bool(torch.isfinite(loss.detach()))
+    dumped = dump_outputs(args.dump_outputs, {"loss": loss, "poses": pred}) if args.dump_outputs and rank == 0 else None
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -660,7 +703,7 @@ def train_bench(args, rank, local_rank, world, dev):
                               "unit": "TFLOP/s", "frac": round(tflops / MODES[effective]["peak"], 4),
                               "frac_of_f32_peak": round(tflops / PEAK_F32_MFMA_TFLOPS, 4),
                               "note": "per GPU: B*3*69.3847 GFLOP (forward + 2x backward) / step time"},
-            "cpu_baseline": cpu}), flush=True)
+            "cpu_baseline": cpu, **({"dumped_outputs": dumped} if dumped is not None else {})}), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz by running the REAL reference (valeoai/PAFUSE, /root/reference) on CPU.
+"""Generate tests/golden/*.npz (and g20_config.yaml) by running the REAL reference (valeoai/PAFUSE, /root/reference) on CPU.
 
 Runs only in the build container (the reference never travels to the GPU box).  Nothing of the
 reference is copied: it is imported through three shims
@@ -656,14 +656,31 @@ def g8_default_init():
     save("g8_init.npz", sha=np.frombuffer(gu.sha256_of(m.state_dict()), dtype=np.uint8))
 
 
+# ------------------------------------------------------------------------------------------------- G20
+def g20_reference_config():
+    """The values the reference configuration (config/config.yaml) gives the keys this package reads
+    (pafuse_amd.config.DEFAULTS), as a YAML file of the same sections that pafuse_amd.config.load() reads back."""
+    import yaml
+    from pafuse_amd import config
+    with open(os.path.join(REF, "config", "config.yaml")) as f:
+        ref = yaml.safe_load(f)
+    tree = {section: {k: ref[section][k] for k in values} for section, values in config.DEFAULTS.items()}
+    path = os.path.join(HERE, "g20_config.yaml")
+    with open(path, "w") as f:
+        f.write("# generated by tests/golden/make_golden.py g20: the reference configuration's values of the keys pafuse_amd reads\n")
+        yaml.safe_dump(tree, f, sort_keys=True)
+    print(f"wrote g20_config.yaml: {os.path.getsize(path) / 1024:.1f} KiB")
+
+
 if __name__ == "__main__":
     install_shims()
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20"]
     table = dict(g1=g1_tiny_mixste, g2=g2_schedule, g3=g3_time_mlp, g4=g4_blocks, g5=g5_d3dp_loops,
                  g6=g6_index_ops, g7=g7_metrics, g8=g8_default_init, g9=g9_evaluate_accumulators,
                  g10=g10_clip_cutting, g11=g11_scale, g12=g12_train_tiny, g13=g13_d3dp_train,
                  g14=g14_h3wb_loader, g15=g15_camera_to_world,
-                 g16=g16_chunked_generator, g17=g17_single_model, g18=g18_mixste_options, g19=g19_metric_config_p20_t10)
+                 g16=g16_chunked_generator, g17=g17_single_model, g18=g18_mixste_options, g19=g19_metric_config_p20_t10,
+                 g20=g20_reference_config)
     for w in which:
         table[w]()

@@ -165,15 +165,19 @@ def test_config_tree_and_overrides():
     assert args.model.number_of_frames == 27 and args.data.num_kps == 134 and args.data.merge_hands is True
     with pytest.raises(ValueError):
         config.load(overrides=["nonsense"])
-    ref_yaml = "/root/reference/config/config.yaml"
-    if os.path.exists(ref_yaml):                                 # build container only: defaults = the reference's file
-        ref = config.load(ref_yaml)
-        for section, values in config.DEFAULTS.items():
-            for k, v in values.items():
-                assert getattr(getattr(ref, section), k) == v, (section, k)
-        # the module mirror constructs from the tree exactly like from the reference's args
-        from __graft_entry__ import make_model
-        assert make_model(1, 1, device="cpu")[0].frames == ref.model.number_of_frames
+    # defaults = the reference's configuration file (golden G20: its values of every key in DEFAULTS)
+    import yaml
+    g20 = os.path.join(ROOT, "tests", "golden", "g20_config.yaml")
+    with open(g20) as f:
+        assert {s: set(v) for s, v in yaml.safe_load(f).items()} == {s: set(v) for s, v in config.DEFAULTS.items()}
+    ref = config.load(g20)
+    for section, values in config.DEFAULTS.items():
+        for k, v in values.items():
+            got = getattr(getattr(ref, section), k)
+            assert got == v and type(got) is type(v), (section, k)
+    # the module mirror constructs from the tree exactly like from the reference's args
+    from __graft_entry__ import make_model
+    assert make_model(1, 1, device="cpu")[0].frames == ref.model.number_of_frames
 
 
 def test_torch_custom_ops_are_registered_for_the_hip_device_only():
@@ -356,3 +360,27 @@ def test_bench_parity_object_on_known_differences():
     moved = bench.parity_object(orc, out, ref, gu, x2d, 3, 2)
     assert abs(moved["max_abs_m"] - 1e-6) < 2e-7
     assert 0.0 < moved["dMPJPE_mm"]["P-Agg"] <= 1e-3 / 3 + 1e-9 and set(moved["dMPJPE_mm"]) == {"J-Best", "P-Best", "P-Agg", "J-Agg"}
+
+
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.py --dump-outputs: every output as <name>.npy in float32 (float64 kept); beyond the size limit a fixed seeded sample
+    of flat positions, the same on every call, with those positions beside it - and the files together within the limit."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(5)
+    poses, loss = torch.randn(2, 3, 4, 5, generator=g), torch.tensor(0.25, dtype=torch.float64)
+    shapes = bench.dump_outputs(str(tmp_path / "all"), {"poses": poses, "loss": loss})
+    assert shapes == {"poses": [2, 3, 4, 5], "loss": []}
+    got = np.load(tmp_path / "all" / "poses.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, poses.numpy())
+    assert np.load(tmp_path / "all" / "loss.npy").dtype == np.float64
+    limit = 400
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"poses": poses.half()}, limit=limit)
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == ["poses.npy", "poses_index.npy"]
+        assert sum(np.load(tmp_path / run / f).nbytes for f in files) <= limit
+    a, ia = np.load(tmp_path / "a" / "poses.npy"), np.load(tmp_path / "a" / "poses_index.npy")
+    assert a.dtype == np.float32 and ia.dtype == np.float64 and 0 < len(a) == len(ia) and np.all(np.diff(ia) > 0)
+    assert np.array_equal(a, poses.half().float().reshape(-1).numpy()[ia.astype(np.int64)])
+    assert np.array_equal(a, np.load(tmp_path / "b" / "poses.npy")) and np.array_equal(ia, np.load(tmp_path / "b" / "poses_index.npy"))
