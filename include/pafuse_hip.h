@@ -177,7 +177,7 @@ const char *pafuse_last_error(void);
 /* Layout version of the structs above (bumped whenever a field is added, moved or removed: this header has no size fields).
  * A caller built against another header gets shifted pointers, not an error - compare with PAFUSE_ABI_VERSION at load time
  * (pafuse_amd/_lib.py does; tests/cabi/linear_smoke.c shows the C side). */
-#define PAFUSE_ABI_VERSION 6
+#define PAFUSE_ABI_VERSION 7
 int pafuse_abi_version(void);
 
 /* out[M,N] = act(A[M,K] @ W[N,K]^T + bias), act: 0 none, 1 exact-erf GELU; +2: bf16 operands (see operand_bf16).
@@ -262,6 +262,57 @@ int pafuse_qkv_attention_image(int32_t scheme, const void *x_img, const float *s
  * out_xh may be xh itself (a workgroup owns its rows). */
 int pafuse_mlp_h(const void *xh, const float *stats_in, const void *W1h, const float *bias1, const void *W2hp, const float *bias2,
                  void *out_xh, float *stats_out, int64_t M, int32_t C, float eps, void *stream);
+
+/* The whole-row layers (attn.proj, mlp.fc2 with the residual add and the LayerNorm chain behind them, common/mixste.py:41,80,
+ * 114-115,243,250,257) as unit entry points: the kernels pafuse_mixste2_forward / pafuse_d3dp_sample launch for them, picked by
+ * the same dispatch.  Per row m of [M, N] (N = the channel width, the whole row):
+ *   y  = A[m] W^T + bias + resid[m]                  (training: y = resid[m] + rowscale[seq(m)] (A[m] W^T + bias), out_pre = y)
+ *   z  = post_w ? LN(y; post_w, post_b, post_eps) : y ;   z += pos[(m / posJ) % posF] if pos ;   out_x = z
+ *   next_w set:  ln_stats NULL: n = LN(z; next) -> out_n, and with head_w: out_head[m] = n head_w^T + head_b  (head_w [3,N])
+ *                ln_stats set (the LayerNorm folded into its consumer): ln_stats[m] = (mean(z), rstd(z)), out_x = z - mean(z)
+ *                (the stored mean: the row and its statistics agree), no out_n
+ * Every output pointer may be NULL (not written).  out_x may be resid itself (a workgroup owns its rows).
+ * operand_bf16 as pafuse_mixste2_weights.operand_bf16:
+ *   0, 1: W fp32.   2: Wsplit = the layout-1 image of W (pafuse_split_weights(W, N, K, 1, ..)).
+ *   3, 4 (inference): A_img = the H / X image of A; Wsplit = the PAFUSE_SPLIT_F16X2 / PAFUSE_SPLIT_X image of W; the residual is
+ *         fp32 `resid` or - resid_img - the (centred) image of it; out_x_img / out_n_img: the images of out_x / n (may alias
+ *         resid_img).  Widths 224 / 256 / 384.
+ *   training (EPI_ROWLN_TRAIN; modes 0 and 2, W always - shapes without a split tile run the fp32 kernels): rowscale [nseq] or
+ *         NULL (= 1), seq(m) = rs_temporal ? (m / rs_FJ) rs_J + m % rs_J : m / rs_J; out_pre [M,N] or NULL.
+ * Refused (PAFUSE_E_ARG): head without next, ln_stats without next or with the head, out_n with ln_stats, pos with posJ or
+ * posF <= 0, a missing operand or image, training in modes 1, 3, 4 or in a group, n outside 1 .. 4; (PAFUSE_E_SHAPE): a width
+ * without a whole-row kernel, K not a positive multiple of 32.  M == 0: nothing is launched.
+ * pafuse_linear_rowln_group: n independent layers; shared_grid != 0 runs them in ONE grid where the grouped kernel has variants
+ * for all of them (mode 2, widths 384 / 256 / 224 at M >= 4096 - the library's single-stream schedule), else one launch each. */
+typedef struct pafuse_rowln_args {
+    int64_t M;
+    int32_t N, K;
+    int32_t operand_bf16;
+    int32_t training;
+    const float *A;                 /* [M,K] (modes 0 - 2) */
+    const float *W;                 /* [N,K] (modes 0, 1, training) */
+    const void *Wsplit;             /* modes 2 - 4: the weight image */
+    const float *bias;              /* [N] */
+    const float *resid;             /* [M,N] */
+    float *out_x, *out_n;           /* [M,N] */
+    const float *post_w, *post_b;   /* [N] */
+    float post_eps;
+    const float *pos;               /* [posF, N] */
+    int32_t posJ, posF;
+    const float *next_w, *next_b;   /* [N] */
+    float next_eps;
+    const float *head_w, *head_b;   /* [3,N], [3] */
+    float *out_head;                /* [M,3] */
+    float *ln_stats;                /* [M,2] */
+    const void *A_img;              /* modes 3, 4: [M,K] image */
+    const void *resid_img;          /* modes 3, 4: [M,N] image of the (centred) residual, instead of resid */
+    void *out_x_img, *out_n_img;    /* modes 3, 4: [M,N] images */
+    const float *rowscale;          /* training */
+    int32_t rs_temporal, rs_J, rs_FJ;
+    float *out_pre;                 /* training: [M,N] */
+} pafuse_rowln_args;
+int pafuse_linear_rowln(const pafuse_rowln_args *a, void *stream);
+int pafuse_linear_rowln_group(const pafuse_rowln_args *a, int32_t n, int32_t shared_grid, void *stream);
 
 /* out[M,C] = LayerNorm(x[M,C]) * w + b  (biased variance, eps inside the sqrt). */
 int pafuse_layernorm(const float *x, const float *w, const float *b, float *out, int64_t M, int32_t C, float eps,

@@ -47,6 +47,17 @@ class D3DPConfig(C.Structure):
                 ("part_by_part_launches", C.c_int32)]
 
 
+class RowLNArgs(C.Structure):
+    """pafuse_rowln_args: one whole-row layer (attn.proj / mlp.fc2 + residual + LayerNorm chain) for pafuse_linear_rowln[_group]"""
+    _fields_ = ([("M", C.c_int64), ("N", C.c_int32), ("K", C.c_int32), ("operand_bf16", C.c_int32), ("training", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("A", "W", "Wsplit", "bias", "resid", "out_x", "out_n", "post_w", "post_b")] +
+                [("post_eps", C.c_float), ("pos", C.c_void_p), ("posJ", C.c_int32), ("posF", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("next_w", "next_b")] + [("next_eps", C.c_float)] +
+                [(n, C.c_void_p) for n in ("head_w", "head_b", "out_head", "ln_stats", "A_img", "resid_img", "out_x_img",
+                                           "out_n_img", "rowscale")] +
+                [(n, C.c_int32) for n in ("rs_temporal", "rs_J", "rs_FJ")] + [("out_pre", C.c_void_p)])
+
+
 class DDIMStep(C.Structure):
     _fields_ = [("time", C.c_int64), ("last", C.c_int32),
                 ("sqrt_recip_acp", C.c_double), ("sqrt_recipm1_acp", C.c_double),
@@ -65,6 +76,8 @@ SIGNATURES = {
     "pafuse_split_weights": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pafuse_linear_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_void_p]),
+    "pafuse_linear_rowln": (C.c_int, [C.POINTER(RowLNArgs), C.c_void_p]),
+    "pafuse_linear_rowln_group": (C.c_int, [C.POINTER(RowLNArgs), C.c_int32, C.c_int32, C.c_void_p]),
     "pafuse_hsplit_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "pafuse_xsplit_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "pafuse_linear_x": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
@@ -122,7 +135,7 @@ SIGNATURES = {
 
 _lib = None
 
-ABI_VERSION = 6      # include/pafuse_hip.h PAFUSE_ABI_VERSION: the struct layouts mirrored above
+ABI_VERSION = 7      # include/pafuse_hip.h PAFUSE_ABI_VERSION: the struct layouts mirrored above
 
 KERNEL_SOURCES = ("pafuse_amd/csrc/kernels.hpp", "pafuse_amd/csrc/hgemm.hpp", "pafuse_amd/csrc/xgemm.hpp", "pafuse_amd/csrc/sgemm.hpp", "pafuse_amd/csrc/train_kernels.hpp", "pafuse_amd/csrc/pafuse_hip.hip",
                   "pafuse_amd/csrc/train_host.inc", "include/pafuse_hip.h")

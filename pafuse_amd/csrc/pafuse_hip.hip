@@ -1171,6 +1171,81 @@ int pafuse_linear_split(const float* A, const void* Wsplit, const float* bias, f
     return gemm_bias(g, (hipStream_t)stream);
 }
 
+// the whole-row unit entries: check one argument set and turn it into the GemmParams run_blocks / the training forward build
+static int rowln_params(const pafuse_rowln_args* a, GemmParams& g) {
+    if (!a) return fail(PAFUSE_E_ARG, "linear_rowln: null arguments");
+    const int mode = a->operand_bf16;
+    if (mode < 0 || mode > 4) return fail(PAFUSE_E_ARG, "linear_rowln: matrix-product mode %d", mode);
+    if (a->M < 0) return fail(PAFUSE_E_ARG, "linear_rowln: negative M");
+    if (a->training && mode != 0 && mode != 2) return fail(PAFUSE_E_ARG, "linear_rowln: training runs modes 0 and 2 only, got %d", mode);
+    const bool img = mode >= 3;
+    if (img ? !hgemm_width(a->N) : !width_supported(a->N))
+        return fail(PAFUSE_E_SHAPE, "linear_rowln: no whole-row kernel for width %d in mode %d", a->N, mode);
+    if (a->K <= 0 || a->K % BK) return fail(PAFUSE_E_SHAPE, "linear_rowln: K=%d must be a positive multiple of 32", a->K);
+    if (!a->bias) return fail(PAFUSE_E_ARG, "linear_rowln: no bias");
+    if (img) {
+        if (!a->A_img || !a->Wsplit) return fail(PAFUSE_E_ARG, "linear_rowln: mode %d needs the images of A and W (A_img, Wsplit)", mode);
+        if (!a->resid == !a->resid_img) return fail(PAFUSE_E_ARG, "linear_rowln: mode %d takes exactly one residual (resid or resid_img)", mode);
+    } else {
+        if (!a->A || !a->resid) return fail(PAFUSE_E_ARG, "linear_rowln: no A or no residual");
+        if (a->A_img || a->resid_img || a->out_x_img || a->out_n_img) return fail(PAFUSE_E_ARG, "linear_rowln: images exist in modes 3 and 4 only");
+        if (mode == 2 && !a->Wsplit) return fail(PAFUSE_E_ARG, "linear_rowln: mode 2 needs the layout-1 image of W (Wsplit)");
+        if ((mode != 2 || a->training) && !a->W) return fail(PAFUSE_E_ARG, "linear_rowln: no fp32 weight W");
+    }
+    if (!a->post_w != !a->post_b) return fail(PAFUSE_E_ARG, "linear_rowln: post_w and post_b go together");
+    if (!a->next_w != !a->next_b) return fail(PAFUSE_E_ARG, "linear_rowln: next_w and next_b go together");
+    const bool head = a->head_w || a->head_b || a->out_head;
+    if (head && !(a->head_w && a->head_b && a->out_head)) return fail(PAFUSE_E_ARG, "linear_rowln: head needs head_w, head_b and out_head");
+    if (head && !a->next_w) return fail(PAFUSE_E_ARG, "linear_rowln: head without next LayerNorm");
+    if (a->ln_stats && !a->next_w) return fail(PAFUSE_E_ARG, "linear_rowln: ln_stats without next LayerNorm");
+    if (a->ln_stats && head) return fail(PAFUSE_E_ARG, "linear_rowln: ln_stats together with the head");
+    if ((a->out_n || a->out_n_img) && (!a->next_w || a->ln_stats)) return fail(PAFUSE_E_ARG, "linear_rowln: out_n needs next LayerNorm without ln_stats");
+    if (a->pos && (a->posJ <= 0 || a->posF <= 0)) return fail(PAFUSE_E_ARG, "linear_rowln: pos with posJ=%d, posF=%d", a->posJ, a->posF);
+    if (!a->training && (a->rowscale || a->out_pre)) return fail(PAFUSE_E_ARG, "linear_rowln: rowscale / out_pre without training");
+    if (a->rowscale && (a->rs_J <= 0 || (a->rs_temporal && a->rs_FJ <= 0)))
+        return fail(PAFUSE_E_ARG, "linear_rowln: rowscale with rs_J=%d, rs_FJ=%d", a->rs_J, a->rs_FJ);
+    g = GemmParams{};
+    g.A = a->A, g.W = a->W, g.bias = a->bias, g.M = a->M, g.N = a->N, g.K = a->K, g.bf16 = mode;
+    g.Wsplit = mode == 2 ? (const uint8_t*)a->Wsplit : nullptr;
+    g.resid = a->resid, g.out_x = a->out_x, g.out_n = a->out_n;
+    g.post_w = a->post_w, g.post_b = a->post_b, g.post_eps = a->post_eps;
+    g.pos = a->pos, g.posJ = a->posJ, g.posF = a->posF;
+    g.next_w = a->next_w, g.next_b = a->next_b, g.next_eps = a->next_eps;
+    g.head_w = a->head_w, g.head_b = a->head_b, g.out_head = a->out_head;
+    g.ln_stats = a->ln_stats;
+    if (img) {
+        g.Ah = (const uint8_t*)a->A_img, g.Wh = (const uint8_t*)a->Wsplit;
+        g.resid_h = (const uint8_t*)a->resid_img;
+        g.out_xh = (uint8_t*)a->out_x_img, g.out_nh = (uint8_t*)a->out_n_img;
+    }
+    g.rowscale = a->rowscale, g.rs_temporal = a->rs_temporal, g.rs_J = a->rs_J, g.rs_FJ = a->rs_FJ, g.out_pre = a->out_pre;
+    return PAFUSE_OK;
+}
+
+int pafuse_linear_rowln(const pafuse_rowln_args* a, void* stream) {
+    StreamDevice on_stream_device(stream);
+    GemmParams g;
+    const int rc = rowln_params(a, g);
+    if (rc) return rc;
+    if (g.M == 0) return PAFUSE_OK;
+    return a->training ? gemm_rowln_train(g, (hipStream_t)stream) : gemm_rowln(g, (hipStream_t)stream);
+}
+
+int pafuse_linear_rowln_group(const pafuse_rowln_args* a, int32_t n, int32_t shared_grid, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!a || n < 1 || n > GROUP_MAX) return fail(PAFUSE_E_ARG, "linear_rowln_group: %d layers (1 .. %d)", n, GROUP_MAX);
+    GemmParams g[GROUP_MAX];
+    int live = 0;
+    for (int i = 0; i < n; ++i) {
+        const int rc = rowln_params(&a[i], g[live]);
+        if (rc) return rc;
+        if (a[i].training) return fail(PAFUSE_E_ARG, "linear_rowln_group: training layers run one by one (pafuse_linear_rowln)");
+        if (g[live].M > 0) ++live;   // (an empty layer launches nothing, as in pafuse_linear_rowln)
+    }
+    if (!live) return PAFUSE_OK;
+    return gemm_group<true>(g, live, (hipStream_t)stream, shared_grid != 0);
+}
+
 int pafuse_hsplit_rows(const float* X, int64_t R, int32_t K, void* out, void* stream) {
     StreamDevice on_stream_device(stream);
     if (!X || !out || R < 0) return fail(PAFUSE_E_ARG, "hsplit_rows: null pointer or negative row count");

@@ -424,7 +424,8 @@ SPLIT_X = 8          # include/pafuse_hip.h PAFUSE_SPLIT_X: the X image of the b
 
 def split_image(weight, layout, f16=False, x=False):
     """The pre-split image of one linear weight [N,K] on its device (pafuse_split_weights): a uint8 tensor of 6 bytes per
-    element; `layout`: 0 mlp.fc1 / the unit op, 1 the whole-row layers (attn.proj, mlp.fc2), 2 attn.qkv (mode 2's three
+    element; `layout`: 0 the plain unit op (pafuse_linear_split without PAFUSE_LINEAR_QKV_IMAGE; no model layer since ABI 6),
+    1 the whole-row layers (attn.proj, mlp.fc2), 2 attn.qkv and - since ABI 6 - mlp.fc1 (mode 2's three
     geometries; the image pipelines have one each); `f16`: the f16x2 scheme's H image (two fp16 slices of the power-of-two-scaled
     weight, 4 bytes per element + a 256-byte tail); `x`: the X image of mode 4 (three bf16 slices, [N][K/32][3][32])."""
     lib = _lib.load()

@@ -333,10 +333,11 @@ def split_weights(weight, layout=0, scheme="bf16x3"):
     """Pre-split image of a [N,K] fp32 weight for the split-precision products (pafuse_split_weights);
     scheme 'bf16x3_images' (the X image of the image pipeline: three bf16 slices, one geometry for every layer), 'f16x2' (the H image:
     two fp16 slices of the power-of-two-scaled weight) or 'bf16x3' (the round-3 kernels' images; layout 0: the
-    32x32x16-MFMA plain kernel (mlp.fc1), 2: the 16x16x32-MFMA kernel of the qkv layers)."""
+    32x32x16-MFMA plain kernel (linear_split's layout 0; no layer of the model since ABI 6), 1: the whole-row layers attn.proj
+    and mlp.fc2 (linear_rowln), 2: the 16x16x32-MFMA kernels of attn.qkv and mlp.fc1)."""
     lib = _lib.load()
     _need(weight.dim() == 2 and weight.shape[1] % 32 == 0, "split_weights: weight must be [N, K] with K % 32 == 0")
-    _need(layout in (0, 2), "split_weights: layout 0 (fc1 kernel) or 2 (qkv kernel)")
+    _need(layout in (0, 1, 2), "split_weights: layout 0 (plain 32x32x16 kernel), 1 (whole-row layers) or 2 (qkv / fc1 kernels)")
     _need(scheme in SCHEME_FLAG, f"split_weights: scheme must be one of {sorted(SCHEME_FLAG)}")
     N, K = weight.shape
     img = torch.empty(lib.pafuse_split_image_bytes(N, K, layout | SCHEME_FLAG[scheme]), dtype=torch.uint8, device=weight.device)
@@ -351,12 +352,14 @@ def linear_split(x, weight, bias, act=None, image=None, layout=0, scheme="bf16x3
     as three bf16 slices each, six bf16 MFMA products per pair (on the image pipeline: both operands as X images; on the
     round-3 kernels: A split in registers); 'f16x2' - two fp16 slices of the activation, three of the scaled weight, three
     fp16 MFMA products.  ``image`` = split_weights(weight, layout, scheme) to reuse a cached image; ``layout`` picks the
-    round-3 kernel: 0 the 32x32x16-MFMA tiles (mlp.fc1), 2 the 16x16x32-MFMA tiles (attn.qkv).  ``out_image`` (image schemes):
+    round-3 kernel: 0 the 32x32x16-MFMA tiles (no model layer since ABI 6), 2 the 16x16x32-MFMA tiles (attn.qkv and mlp.fc1:
+    the persistent strip kernel).  (Layout 1 images belong to the whole-row layers: linear_rowln.)  ``out_image`` (image schemes):
     return the image of the output (what a producer hands its consumer) instead of fp32 rows."""
     lib = _lib.load()
     K = x.shape[-1]
     N = weight.shape[0]
     _need(tuple(weight.shape) == (N, K) and bias.numel() == N, f"linear: x [..,{K}] needs weight [N,{K}] and bias [N]")
+    _need(layout in (0, 2), "linear_split: layout 0 or 2 (layout-1 images are the whole-row layers': linear_rowln)")
     img = split_weights(weight, layout, scheme) if image is None else image
     _need(img.numel() == lib.pafuse_split_image_bytes(N, K, layout | SCHEME_FLAG[scheme]), "linear_split: image size does not match the weight")
     x2 = x.contiguous().view(-1, K)
@@ -385,3 +388,141 @@ def linear_split(x, weight, bias, act=None, image=None, layout=0, scheme="bf16x3
                                            x2.shape[0], N, K,
                                            (1 if act == "gelu" else 0) + (2 if layout == 2 else 0), _stream(x)))
     return out.view(*x.shape[:-1], N)
+
+
+IMAGE_BYTES = {3: 4, 4: 6}      # bytes per element of an activation image: f16x2 H image, bf16x3 X image
+
+
+def rowln_args(x, weight, bias, resid, precision="bf16x3", image=None, post=None, pos=None, next=None, head=None, fold=False,
+               in_place=False, resid_image=False, training=False, rowscale=None, rs_map=(0, 1, 1), out=None):
+    """One whole-row layer as a pafuse_rowln_args (include/pafuse_hip.h), with the images its mode reads made here.
+    Returns (args, keep, finish): ``keep`` holds every tensor the struct points at, ``finish()`` the outputs as a dict.
+
+    x [M,K], weight [N,K], bias [N], resid [M,N] fp32.  post / next: (weight, bias, eps) of a LayerNorm; pos: (table [F',N],
+    posJ, posF); head: (weight [3,N], bias [3]) behind `next`; fold: (mean, rstd) of the next LayerNorm to 'stats' and x stored
+    centred on that mean instead of the normalised row.  precision: a key of PRECISIONS; mode 2 uses the layout-1 image of
+    weight, modes 3 / 4 the H / X images of x and weight (``image``: a cached weight image).  resid_image (modes 3 / 4): the
+    residual goes in as its image and x comes out only as an image ('x' is decoded from it).  in_place: x is written over the
+    residual itself (resid, or its image).  training (modes 0 / 2): rowscale [nseq] or None, rs_map = (rs_temporal, rs_J,
+    rs_FJ); 'pre' = the pre-norm sum.  out: preallocated outputs by name ('x', 'n', 'head', 'stats', 'pre', 'x_img', 'n_img'),
+    at least as large as the layer needs (nothing past row M is written).
+    Outputs: 'x', 'n', 'head', 'stats', 'pre' fp32 (those the options produce); in modes 3 / 4 also 'x_img' / 'n_img', the
+    images joined back to fp32."""
+    lib = _lib.load()
+    _need(precision in PRECISIONS, f"precision must be one of {sorted(PRECISIONS)}")
+    mode = PRECISIONS[precision]
+    M, K = x.shape
+    N = weight.shape[0]
+    _need(tuple(weight.shape) == (N, K) and bias.numel() == N and tuple(resid.shape) == (M, N),
+          f"linear_rowln: x [M,K], weight [N,{K}], bias [N], resid [{M},{N}]")
+    _need(not resid_image or mode >= 3, "linear_rowln: resid_image needs an image mode (f16x2, bf16x3_images)")
+    out = dict(out or {})
+    a = _lib.RowLNArgs()
+    a.M, a.N, a.K, a.operand_bf16, a.training = M, N, K, mode, int(bool(training))
+    keep = [x, weight, bias, resid]
+    eb = IMAGE_BYTES.get(mode, 4)
+
+    def buf(name, shape, dtype=torch.float32):
+        t = out.get(name)
+        if t is None:
+            t = out[name] = torch.empty(shape, dtype=dtype, device=x.device)
+        _need(t.is_contiguous() and t.numel() >= (shape if isinstance(shape, int) else shape[0] * shape[1]),
+              f"linear_rowln: output '{name}' is too small")
+        keep.append(t)
+        return t.data_ptr()
+
+    split = (hsplit_rows if mode == 3 else xsplit_rows) if mode >= 3 else None
+    if mode >= 3:
+        ximg = split(x)
+        wimg = image if image is not None else split_image(weight, 1, mode == 3, mode == 4)
+        keep += [ximg, wimg]
+        a.A_img, a.Wsplit = ximg.data_ptr(), wimg.data_ptr()
+    else:
+        a.A = _ptr(x, "x")
+        a.W = _ptr(weight, "weight")
+        if mode == 2:
+            wimg = image if image is not None else split_image(weight, 1)
+            keep.append(wimg)
+            a.Wsplit = wimg.data_ptr()
+    a.bias = _ptr(bias, "bias")
+    rimg = None
+    if resid_image:
+        rimg = split(resid)
+        keep.append(rimg)
+        a.resid_img = rimg.data_ptr()
+        if in_place:
+            out["x_img"] = rimg
+        a.out_x_img = buf("x_img", M * N * eb, torch.uint8)
+    else:
+        a.resid = _ptr(resid, "resid")
+        if in_place:
+            out["x"] = resid
+        a.out_x = buf("x", (M, N))
+        if mode >= 3:
+            a.out_x_img = buf("x_img", M * N * eb, torch.uint8)
+    if post is not None:
+        a.post_w, a.post_b, a.post_eps = _ptr(post[0], "post_w"), _ptr(post[1], "post_b"), float(post[2])
+    if pos is not None:
+        a.pos, a.posJ, a.posF = _ptr(pos[0], "pos"), int(pos[1]), int(pos[2])
+    if next is not None:
+        a.next_w, a.next_b, a.next_eps = _ptr(next[0], "next_w"), _ptr(next[1], "next_b"), float(next[2])
+        if fold:
+            a.ln_stats = buf("stats", (M, 2))
+        else:
+            a.out_n = buf("n", (M, N))
+            if mode >= 3:
+                a.out_n_img = buf("n_img", M * N * eb, torch.uint8)
+    if head is not None:
+        a.head_w, a.head_b = _ptr(head[0], "head_w"), _ptr(head[1], "head_b")
+        a.out_head = buf("head", (M, 3))
+    if training:
+        if rowscale is not None:
+            a.rowscale = _ptr(rowscale, "rowscale")
+        a.rs_temporal, a.rs_J, a.rs_FJ = (int(v) for v in rs_map)
+        a.out_pre = buf("pre", (M, N))
+    keep += [post, pos, next, head, rowscale]
+
+    def finish():
+        join = hjoin_rows if mode == 3 else xjoin_rows
+        res = {}
+        for name in ("x", "n", "pre"):
+            if name in out and out[name] is not None and (name != "x" or not resid_image):
+                res[name] = out[name].reshape(-1)[:M * N].view(M, N)
+        for name, cols in (("head", 3), ("stats", 2)):
+            if name in out:
+                res[name] = out[name].reshape(-1)[:M * cols].view(M, cols)
+        for name in ("x_img", "n_img"):
+            if name in out:
+                res[name] = join(out[name].reshape(-1)[:M * N * eb], M, N)
+        if resid_image:
+            res["x"] = res["x_img"]
+        return res
+
+    return a, keep, finish
+
+
+def linear_rowln(x, weight, bias, resid, precision="bf16x3", **options):
+    """One whole-row layer - attn.proj / mlp.fc2 with the residual add and the LayerNorm chain in the epilogue
+    (pafuse_linear_rowln, the kernels the denoisers launch): y = x W^T + b + resid, then post-norm, pos, next-norm / its folded
+    statistics / the head.  Options and the returned dict of outputs: rowln_args."""
+    lib = _lib.load()
+    a, keep, finish = rowln_args(x, weight, bias, resid, precision, **options)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.pafuse_linear_rowln(C.byref(a), _stream(x)))
+    del keep      # (stream-ordered: the caching allocator reuses the blocks only for later work on this stream)
+    return finish()
+
+
+def linear_rowln_group(layers, shared_grid=True):
+    """Up to four independent whole-row layers in one call (pafuse_linear_rowln_group): ``layers`` is a list of dicts of
+    linear_rowln's arguments (x, weight, bias, resid, precision, options); shared_grid=True runs them in ONE grid where the
+    grouped kernel has variants for all of them (the single-stream schedule of the denoiser loop), else one launch each.
+    Returns the list of output dicts."""
+    lib = _lib.load()
+    _need(1 <= len(layers) <= _lib.MAX_PARTS, f"linear_rowln_group: 1 .. {_lib.MAX_PARTS} layers")
+    built = [rowln_args(**layer) for layer in layers]
+    arr = (_lib.RowLNArgs * len(built))(*[b[0] for b in built])
+    dev = layers[0]["x"].device
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_linear_rowln_group(arr, len(built), int(bool(shared_grid)), _stream(layers[0]["x"])))
+    return [b[2]() for b in built]

@@ -76,7 +76,7 @@ _IMAGE_CACHE_MAX = 2048  # ~ three models' worth of linear weights; the oldest e
 def cached_split_image(weight, layout, f16=False, x=False):
     """The pre-split image of a linear weight, made once per (storage, version, layout, scheme): the schema'd ops take plain
     parameter tensors, so they build and cache the images the split-precision kernels read (the modules keep theirs per
-    module).  layout: pafuse_split_weights' (0 fc1, 1 proj / fc2, 2 qkv).
+    module).  layout: pafuse_split_weights' (1 proj / fc2, 2 qkv / fc1; 0 is no model layer's since ABI 6).
     An entry keeps a reference to the tensor it was made from: while the entry lives that storage cannot be freed, so no
     other tensor can come to sit at its address with a matching version and shape and hit a stale image (a freed temporary
     such as `w.float()` or `w.detach().clone()` made per call would otherwise do exactly that)."""
@@ -339,8 +339,8 @@ def ddim_loop(x2d: torch.Tensor, x2d_flip: torch.Tensor, noise: torch.Tensor, we
     joint_part, joint_local = joint_part.to(dev), joint_local.to(dev)
     perm = flip_perm.to(device=dev, dtype=torch.int32).contiguous()
     cfg.joint_part, cfg.joint_local, cfg.flip_perm = joint_part.data_ptr(), joint_local.data_ptr(), perm.data_ptr()
-    # one stream, every layer part by part: the launches (and so the bits) of the modules' three-stream schedule - the shared grids
-    # of the library's own single-stream schedule keep another whole-row epilogue (same function, rounding-level differences)
+    # one stream, every layer part by part: the launches of the modules' three-stream schedule.  (The shared grids of the library's
+    # own single-stream schedule run another whole-row epilogue that gives the same bits: tests/test_hip_rowln.py.)
     cfg.part_by_part_launches = 1
     steps = (_lib.DDIMStep * T)()
     for k in range(T):

@@ -52,7 +52,7 @@ static void make_block(pafuse_block_weights* b, int mode) {
     b->fc2_w = dev_rand((size_t)2 * C * C, 0.05f, 0.0f), b->fc2_b = dev_rand(C, 0.02f, 0.0f);
     if (mode == 2) {
         b->qkv_ws = split_of(b->qkv_w, 3 * C, C, 2), b->proj_ws = split_of(b->proj_w, C, C, 1);
-        b->fc1_ws = split_of(b->fc1_w, 2 * C, C, 0), b->fc2_ws = split_of(b->fc2_w, C, 2 * C, 1);
+        b->fc1_ws = split_of(b->fc1_w, 2 * C, C, 2), b->fc2_ws = split_of(b->fc2_w, C, 2 * C, 1);
     }
 }
 
