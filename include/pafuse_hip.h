@@ -14,7 +14,8 @@
  *   pafuse_attention         Attention.forward between qkv and proj, common/mixste.py:65-79
  *   pafuse_block_forward     Block.forward, common/mixste.py:113-116
  *   pafuse_attention_backward, pafuse_linear_weight_grad   the backward of the two above as torch autograd derives it
- *                            (unit entries of the training step's kernels)
+ *                            (unit entries of the training step's kernels; with pafuse_layernorm_backward,
+ *                            pafuse_linear_input_grad, pafuse_linear_train, pafuse_gelu_backward)
  *   pafuse_time_embed        MixSTE2.time_mlp, common/mixste.py:127-139,179-184
  *   pafuse_mixste2_forward   MixSTE2.forward (is_train=False), common/mixste.py:278-298
  *   pafuse_d3dp_sample       D3DP.ddim_sample_flip / ddim_sample, common/diffusionpose.py:227-316
@@ -177,7 +178,7 @@ const char *pafuse_last_error(void);
 /* Layout version of the structs above (bumped whenever a field is added, moved or removed: this header has no size fields).
  * A caller built against another header gets shifted pointers, not an error - compare with PAFUSE_ABI_VERSION at load time
  * (pafuse_amd/_lib.py does; tests/cabi/linear_smoke.c shows the C side). */
-#define PAFUSE_ABI_VERSION 7
+#define PAFUSE_ABI_VERSION 8
 int pafuse_abi_version(void);
 
 /* out[M,N] = act(A[M,K] @ W[N,K]^T + bias), act: 0 none, 1 exact-erf GELU; +2: bf16 operands (see operand_bf16).
@@ -339,6 +340,44 @@ int pafuse_attention_backward(const float *qkv, const float *d_o, float *dqkv, i
 size_t pafuse_linear_weight_grad_bytes(void);
 int pafuse_linear_weight_grad(const float *dY, const float *X, float *dW, float *db, int64_t M, int32_t N, int32_t K,
                               int32_t operand_bf16, void *workspace, size_t workspace_bytes, void *stream);
+
+/* More unit entry points of the training step: each calls the host function the step calls (train_host.inc).
+ * pafuse_layernorm_backward (ln_backward): with xh = (x - mean) rstd, g = dy w:
+ *   dx = add + rstd (g - mean(g) - xh mean(g xh))  (add NULL: 0; add may be dx itself, as the step's norm1 call passes it),
+ *   out_scaled = drop[seq(m)] dx (drop NULL: 1; seq(m) = temporal ? (m / FJ) J + m % J : m / J),
+ *   dw += sum_m dy xh, db += sum_m dy, dbranch += sum_m out_scaled (NULL: not formed; needs out_scaled).
+ *   C % 4 == 0 and C <= 384: the half-wave kernel (16-byte accesses: dy, x, w, add, dx, out_scaled 16-byte aligned), else the
+ *   one-wave-per-row kernel (C <= 768).
+ * pafuse_linear_input_grad (input_grad): dX[M,K] = dY[M,N] W[N,K], times gelu'(dact_u[M,K]) when dact_u is given (the dX GEMM
+ *   of mlp.fc2).  operand_bf16 0: W transposed, fp32 products; 2: split products on the M16 image of W^T where the step runs
+ *   them (M >= 128), made by split_weights_transposed_kernel (image_source 0) or by the one-launch batch kernel the step uses
+ *   (image_source 1).  dact_u: K % 64 == 0 unless the split route is taken.
+ * pafuse_linear_train (plain_linear): u[M,N] = A[M,K] W[N,K]^T + bias, h = gelu(u) from the same epilogue (h NULL: not
+ *   formed; h: N % 64 == 0 unless the split route is taken) - mlp.fc1 of the training forward, and the time MLP (M < 128).
+ * pafuse_gelu_backward (gelu_bwd): du[M,N] = dh gelu'(u) (du may be dh), db[N] += column sums of du.  N % 4 == 0.
+ * workspace: pafuse_train_unit_bytes(M, N, K) bytes, 16-byte aligned (layernorm_backward: N = C, K = 0; gelu_backward: K = 0).
+ * Refused before any launch: a NULL operand, M < 0, a misaligned vector operand, a width outside the kernels' range, a mode
+ * other than 0 / 2, a too-small workspace, dbranch without out_scaled, drop with J or FJ <= 0.  M == 0: nothing is launched. */
+typedef struct pafuse_lnb_args {
+    const float *dy, *x, *w;  /* [M,C], [M,C], [C] */
+    float eps;
+    const float *add;         /* [M,C] or NULL; may be dx */
+    float *dx;                /* [M,C] */
+    const float *drop;        /* [nseq] or NULL */
+    int32_t temporal, J, FJ;  /* the sequence map of drop */
+    float *out_scaled;        /* [M,C] or NULL */
+    float *dw, *db, *dbranch; /* [C], added into; dbranch may be NULL */
+    int64_t M;
+    int32_t C;
+} pafuse_lnb_args;
+size_t pafuse_train_unit_bytes(int64_t M, int32_t N, int32_t K);
+int pafuse_layernorm_backward(const pafuse_lnb_args *a, void *workspace, size_t workspace_bytes, void *stream);
+int pafuse_linear_input_grad(const float *dY, const float *W, const float *dact_u, float *dX, int64_t M, int32_t N, int32_t K,
+                             int32_t operand_bf16, int32_t image_source, void *workspace, size_t workspace_bytes, void *stream);
+int pafuse_linear_train(const float *A, const float *W, const float *bias, float *u, float *h, int64_t M, int32_t N, int32_t K,
+                        int32_t operand_bf16, void *workspace, size_t workspace_bytes, void *stream);
+int pafuse_gelu_backward(const float *u, const float *dh, float *du, float *db, int64_t M, int32_t N, void *workspace,
+                         size_t workspace_bytes, void *stream);
 
 /* x[S*L,C] <- Block(x) in place for S contiguous sequences of L tokens (Block.forward, eps 1e-6).  operand_bf16: the
  * matrix-product mode of the four linear layers (as pafuse_mixste2_weights.operand_bf16; 2, 3 and 4 need the *_ws images of

@@ -58,6 +58,13 @@ class RowLNArgs(C.Structure):
                 [(n, C.c_int32) for n in ("rs_temporal", "rs_J", "rs_FJ")] + [("out_pre", C.c_void_p)])
 
 
+class LnbArgs(C.Structure):
+    """pafuse_lnb_args: one LayerNorm backward of the training step for pafuse_layernorm_backward"""
+    _fields_ = ([(n, C.c_void_p) for n in ("dy", "x", "w")] + [("eps", C.c_float)] +
+                [(n, C.c_void_p) for n in ("add", "dx", "drop")] + [(n, C.c_int32) for n in ("temporal", "J", "FJ")] +
+                [(n, C.c_void_p) for n in ("out_scaled", "dw", "db", "dbranch")] + [("M", C.c_int64), ("C", C.c_int32)])
+
+
 class DDIMStep(C.Structure):
     _fields_ = [("time", C.c_int64), ("last", C.c_int32),
                 ("sqrt_recip_acp", C.c_double), ("sqrt_recipm1_acp", C.c_double),
@@ -97,6 +104,14 @@ SIGNATURES = {
     "pafuse_linear_weight_grad_bytes": (C.c_size_t, []),
     "pafuse_linear_weight_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pafuse_train_unit_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "pafuse_layernorm_backward": (C.c_int, [C.POINTER(LnbArgs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pafuse_linear_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pafuse_linear_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pafuse_gelu_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
     "pafuse_block_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "pafuse_block_forward": (C.c_int, [C.POINTER(BlockWeights), C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -135,7 +150,7 @@ SIGNATURES = {
 
 _lib = None
 
-ABI_VERSION = 7      # include/pafuse_hip.h PAFUSE_ABI_VERSION: the struct layouts mirrored above
+ABI_VERSION = 8      # include/pafuse_hip.h PAFUSE_ABI_VERSION: the struct layouts mirrored above
 
 KERNEL_SOURCES = ("pafuse_amd/csrc/kernels.hpp", "pafuse_amd/csrc/hgemm.hpp", "pafuse_amd/csrc/xgemm.hpp", "pafuse_amd/csrc/sgemm.hpp", "pafuse_amd/csrc/train_kernels.hpp", "pafuse_amd/csrc/pafuse_hip.hip",
                   "pafuse_amd/csrc/train_host.inc", "include/pafuse_hip.h")

@@ -1799,6 +1799,107 @@ int pafuse_linear_weight_grad(const float* dY, const float* X, float* dW, float*
     return weight_grad(dY, X, dW, M, N, K, tb, (hipStream_t)stream, false, db);
 }
 
+// workspace of the unit entries below, carved in this order (tb null: only the size): the column-sum partials of ln_backward /
+// gelu_bwd (width max(N, K)), the transposed weight and the split image of a dX GEMM, its zero bias
+static size_t carve_unit(char* base, int64_t M, int N, int K, TrainBuffers* tb) {
+    const size_t W = (size_t)std::max(N, K);
+    const size_t parts = std::max((size_t)blocks_for(M, LNB_ROWS_PER_BLOCK) * 3 * W, (size_t)std::min<int64_t>(1024, (M + 31) / 32) * W);
+    const size_t part_b = align_up(parts * 4), wt_b = align_up((size_t)N * K * 4), img_b = align_up((size_t)N * K * 6);
+    if (tb) {
+        *tb = TrainBuffers{};
+        tb->partial = tb->partial_side = (float*)base, tb->partial_floats = parts;
+        tb->wt = (float*)(base + part_b), tb->wimg = (uint8_t*)(base + part_b + wt_b), tb->zeros = (float*)(base + part_b + wt_b + img_b);
+    }
+    return part_b + wt_b + img_b + align_up(W * 4);
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }   // (null: nothing is loaded)
+
+size_t pafuse_train_unit_bytes(int64_t M, int32_t N, int32_t K) {
+    return (M < 0 || N < 0 || K < 0) ? 0 : carve_unit(nullptr, M, N, K, nullptr);
+}
+
+int pafuse_layernorm_backward(const pafuse_lnb_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!a || !a->dy || !a->x || !a->w || !a->dx || !a->dw || !a->db || !workspace || a->M < 0)
+        return fail(PAFUSE_E_ARG, "layernorm_backward: null pointer or negative M");
+    if (a->C < 1 || a->C > LN_BACKWARD_MAX_C) return fail(PAFUSE_E_SHAPE, "layernorm_backward: C=%d outside 1 .. %d", a->C, LN_BACKWARD_MAX_C);
+    if (a->dbranch && !a->out_scaled) return fail(PAFUSE_E_ARG, "layernorm_backward: dbranch without out_scaled");
+    if (a->drop && (a->J <= 0 || (a->temporal && a->FJ <= 0)))
+        return fail(PAFUSE_E_ARG, "layernorm_backward: drop with J=%d, FJ=%d", a->J, a->FJ);
+    if (!aligned16(workspace) || (ln_backward_quad(a->C) && !(aligned16(a->dy) && aligned16(a->x) && aligned16(a->w) &&
+                                                              aligned16(a->add) && aligned16(a->dx) && aligned16(a->out_scaled))))
+        return fail(PAFUSE_E_ARG, "layernorm_backward: a tensor read with 16-byte accesses is not 16-byte aligned (C=%d)", a->C);
+    if (workspace_bytes < carve_unit(nullptr, a->M, a->C, 0, nullptr)) return fail(PAFUSE_E_WORKSPACE, "layernorm_backward: workspace too small");
+    if (a->M == 0) return PAFUSE_OK;
+    TrainBuffers tb;
+    carve_unit((char*)workspace, a->M, a->C, 0, &tb);
+    return ln_backward(a->dy, a->x, a->w, a->eps, a->add, a->dx, a->drop, SeqMap{a->temporal, a->J, a->FJ}, a->out_scaled,
+                       a->dw, a->db, a->dbranch, a->M, a->C, tb, (hipStream_t)stream);
+}
+
+int pafuse_linear_input_grad(const float* dY, const float* W, const float* dact_u, float* dX, int64_t M, int32_t N, int32_t K,
+                             int32_t operand_bf16, int32_t image_source, void* workspace, size_t workspace_bytes, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!dY || !W || !dX || !workspace || M < 0) return fail(PAFUSE_E_ARG, "linear_input_grad: null pointer or negative M");
+    if (operand_bf16 != 0 && operand_bf16 != 2) return fail(PAFUSE_E_ARG, "linear_input_grad: matrix-product mode %d (0 or 2)", operand_bf16);
+    if (image_source != 0 && image_source != 1) return fail(PAFUSE_E_ARG, "linear_input_grad: image source %d (0 or 1)", image_source);
+    if (N <= 0 || K <= 0 || N % 32 || K % 32) return fail(PAFUSE_E_SHAPE, "linear_input_grad: N=%d, K=%d must be positive multiples of 32", N, K);
+    const bool split = operand_bf16 == 2 && plain_splits(M, K, N);
+    if (dact_u && !split && K % 64) return fail(PAFUSE_E_SHAPE, "linear_input_grad: dact_u on fp32 products needs K %% 64 == 0, K=%d", K);
+    if (!aligned16(dY) || !aligned16(W) || !aligned16(dact_u) || !aligned16(dX) || !aligned16(workspace))
+        return fail(PAFUSE_E_ARG, "linear_input_grad: an operand is not 16-byte aligned");
+    if (workspace_bytes < carve_unit(nullptr, M, N, K, nullptr)) return fail(PAFUSE_E_WORKSPACE, "linear_input_grad: workspace too small");
+    if (M == 0) return PAFUSE_OK;
+    TrainBuffers tb;
+    carve_unit((char*)workspace, M, N, K, &tb);
+    tb.split = operand_bf16 == 2;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(tb.zeros, 0, (size_t)K * 4, s) != hipSuccess) return fail(PAFUSE_E_HIP, "memset failed");
+    const uint8_t* image = nullptr;
+    if (split && image_source == 1) {   // the image as the step makes it: one item of the batch kernel (prepare_images)
+        SplitBatchParams p{};
+        const int blocks = add_split_item(p, 0, W, tb.wimg, N, K, transposed_split_kind(K));
+        hipLaunchKernelGGL(split_weights_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
+        const int rc = check_launch("split_weights_batch_kernel");
+        if (rc) return rc;
+        image = tb.wimg;
+    }
+    return input_grad(dY, W, dX, M, N, K, tb, s, dact_u, image);
+}
+
+int pafuse_linear_train(const float* A, const float* W, const float* bias, float* u, float* h, int64_t M, int32_t N, int32_t K,
+                        int32_t operand_bf16, void* workspace, size_t workspace_bytes, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!A || !W || !bias || !u || !workspace || M < 0) return fail(PAFUSE_E_ARG, "linear_train: null pointer or negative M");
+    if (operand_bf16 != 0 && operand_bf16 != 2) return fail(PAFUSE_E_ARG, "linear_train: matrix-product mode %d (0 or 2)", operand_bf16);
+    if (N <= 0 || K <= 0 || N % 32 || K % 32) return fail(PAFUSE_E_SHAPE, "linear_train: N=%d, K=%d must be positive multiples of 32", N, K);
+    const bool split = operand_bf16 == 2 && plain_splits(M, N, K);
+    if (h && !split && N % 64) return fail(PAFUSE_E_SHAPE, "linear_train: h on fp32 products needs N %% 64 == 0, N=%d", N);
+    if (!aligned16(A) || !aligned16(W) || !aligned16(bias) || !aligned16(u) || !aligned16(h) || !aligned16(workspace))
+        return fail(PAFUSE_E_ARG, "linear_train: an operand is not 16-byte aligned");
+    if (workspace_bytes < carve_unit(nullptr, M, N, K, nullptr)) return fail(PAFUSE_E_WORKSPACE, "linear_train: workspace too small");
+    if (M == 0) return PAFUSE_OK;
+    TrainBuffers tb;
+    carve_unit((char*)workspace, M, N, K, &tb);
+    tb.split = operand_bf16 == 2;
+    return plain_linear(A, W, bias, u, M, N, K, (hipStream_t)stream, &tb, h);
+}
+
+int pafuse_gelu_backward(const float* u, const float* dh, float* du, float* db, int64_t M, int32_t N, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!u || !dh || !du || !db || !workspace || M < 0) return fail(PAFUSE_E_ARG, "gelu_backward: null pointer or negative M");
+    if (N <= 0 || N % 4) return fail(PAFUSE_E_SHAPE, "gelu_backward: N=%d must be a positive multiple of 4", N);
+    if (!aligned16(u) || !aligned16(dh) || !aligned16(du) || !aligned16(workspace))
+        return fail(PAFUSE_E_ARG, "gelu_backward: an operand is not 16-byte aligned");
+    if (workspace_bytes < carve_unit(nullptr, M, N, 0, nullptr)) return fail(PAFUSE_E_WORKSPACE, "gelu_backward: workspace too small");
+    if (M == 0) return PAFUSE_OK;
+    TrainBuffers tb;
+    carve_unit((char*)workspace, M, N, 0, &tb);
+    return gelu_bwd(u, dh, du, db, M, N, tb, (hipStream_t)stream);
+}
+
 size_t pafuse_mixste2_train_bytes(const pafuse_mixste2_weights* w, int32_t B) {
     if (!w || B <= 0 || check_weights(w, true)) return 0;
     return train_bytes(w, B);

@@ -243,6 +243,9 @@ int input_grad(const float* dY, const float* W, float* dX, int64_t M, int N, int
     return gemm_bias(g, s);
 }
 
+constexpr int LN_BACKWARD_MAX_C = 64 * LN_MAX_PER_LANE;
+inline bool ln_backward_quad(int C) { return C % 4 == 0 && C <= 128 * LNB_NV; }
+
 // dbranch (may be null): bias gradient of the Linear whose DropPath-scaled output joins the residual below this norm
 // = column sums of out_scaled, accumulated alongside dw/db instead of a separate pass over [M,C]
 int ln_backward(const float* dy, const float* x, const float* w, float eps, const float* add, float* dx,
@@ -251,9 +254,11 @@ int ln_backward(const float* dy, const float* x, const float* w, float eps, cons
     LnBackwardParams p{};
     p.dy = dy, p.x = x, p.w = w, p.eps = eps, p.add = add, p.dx = dx, p.drop = drop, p.map = map;
     p.out_scaled = out_scaled, p.partial = tb.partial, p.M = M, p.C = C;
+    // (ln_backward_kernel keeps a row in LN_MAX_PER_LANE registers per lane: wider rows would lose channels and read past its LDS)
+    if (C < 1 || C > LN_BACKWARD_MAX_C) return fail(PAFUSE_E_SHAPE, "ln_backward: C=%d outside 1 .. %d", C, LN_BACKWARD_MAX_C);
     const unsigned nb = blocks_for(M, LNB_ROWS_PER_BLOCK);
     if ((size_t)nb * 3 * C > tb.partial_floats) return fail(PAFUSE_E_WORKSPACE, "ln_backward: partial buffer");
-    if (C % 4 == 0 && C <= 128 * LNB_NV)   // the PAFUSE widths: half-wave per row, 16-byte accesses
+    if (ln_backward_quad(C))   // the PAFUSE widths: half-wave per row, 16-byte accesses
         hipLaunchKernelGGL(ln_backward_quad_kernel, dim3(nb), dim3(256), 0, s, p);
     else
         hipLaunchKernelGGL(ln_backward_kernel, dim3(nb), dim3(256), 0, s, p);
@@ -362,6 +367,16 @@ BlockGeometry block_geometry(const pafuse_mixste2_weights* w, int k, int64_t R) 
     return g;
 }
 
+// kind of the batch item that makes the image of W^T [K, N] for a dX GEMM: the dX GEMM's output columns are the weight's K
+inline int transposed_split_kind(int K) { return plain_layout(K, false) == 2 ? 4 : 2; }
+
+// appends weight W [N, K] (as it lies) to a split_weights_batch_kernel launch; returns the launch's workgroup count after it
+int add_split_item(SplitBatchParams& p, int blocks, const float* W, uint8_t* out, int N, int K, int kind) {
+    SplitBatchItem& it = p.item[p.count++];
+    it.W = W, it.out = out, it.N = N, it.K = K, it.kind = kind, it.first_block = blocks;
+    return blocks + (int)(((int64_t)N * (K / 8) + 255) / 256);
+}
+
 // the images of every block's four linear weights in one launch: of W for the forward (qkv, fc1 in the plain layout; proj, fc2
 // in the whole-row layout), of W^T for the backward's dX GEMMs.  Sets tb.img[k][0..3] (null where the GEMM runs fp32 products).
 int prepare_images(const pafuse_mixste2_weights* w, int B, bool transposed, TrainBuffers& tb, hipStream_t s) {
@@ -381,13 +396,9 @@ int prepare_images(const pafuse_mixste2_weights* w, int B, bool transposed, Trai
             const bool ok = transposed ? plain_splits(M, K[l], N[l]) : (whole_row ? rowln_splits(M, N[l], K[l]) : plain_splits(M, N[l], K[l]));
             tb.img[k][l] = nullptr;
             if (!ok || p.count == SPLIT_BATCH_MAX) continue;
-            SplitBatchItem& it = p.item[p.count++];
-            it.W = W[l], it.out = base + off[l], it.N = N[l], it.K = K[l];
-            if (transposed) it.kind = plain_layout(K[l], false) == 2 ? 4 : 2;     // the dX GEMM's output columns are the weight's K
-            else it.kind = whole_row ? 1 : (plain_layout(N[l], l == 0) == 2 ? 3 : 0);
-            it.first_block = blocks;
-            blocks += (int)(((int64_t)N[l] * (K[l] / 8) + 255) / 256);
-            tb.img[k][l] = it.out;
+            const int kind = transposed ? transposed_split_kind(K[l]) : (whole_row ? 1 : (plain_layout(N[l], l == 0) == 2 ? 3 : 0));
+            blocks = add_split_item(p, blocks, W[l], base + off[l], N[l], K[l], kind);
+            tb.img[k][l] = base + off[l];
         }
     }
     if (!p.count) return PAFUSE_OK;

@@ -109,6 +109,119 @@ def linear_weight_grad(d_y, x, precision="bf16x3", bias=True):
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x3": 2, "f16x2": 3, "bf16x3_images": 4}       # as pafuse_amd.D3DP.PRECISIONS
 
 
+def _out_buf(out, name, shape, dev, zero=False):
+    """a preallocated output from `out` (contiguous, at least as large: nothing past the used part is written) or a new one"""
+    n = shape[0] * shape[1] if len(shape) == 2 else shape[0]
+    t = out.get(name) if out else None
+    if t is None:
+        return (torch.zeros if zero else torch.empty)(shape, device=dev, dtype=torch.float32)
+    _need(t.is_contiguous() and t.dtype == torch.float32 and t.numel() >= n, f"output '{name}' must be contiguous fp32 of >= {n} elements")
+    return t
+
+
+def _unit_workspace(lib, M, N, K, dev):
+    nbytes = lib.pafuse_train_unit_bytes(M, N, K)
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
+
+
+def layer_norm_backward(dy, x, weight, eps, add=None, drop=None, seq_map=(0, 1, 1), scaled=False, branch=False, out=None):
+    """The training step's LayerNorm backward on its own (pafuse_layernorm_backward -> ln_backward): dx = add + LN'(x)^T dy,
+    out_scaled = drop[seq(m)] dx (scaled=True), and dw += sum dy xh, db += sum dy, dbranch += column sums of out_scaled
+    (branch=True).  dy, x, add [M,C]; drop [nseq] with seq_map = (temporal, J, FJ).  out: preallocated outputs by name ('dx',
+    'out_scaled', 'dw', 'db', 'dbranch'); the gradients are ADDED into the given dw / db / dbranch (new ones start at 0); 'dx'
+    may be `add` itself.  Returns a dict of the outputs ('dx', 'dw', 'db', and 'out_scaled' / 'dbranch' when asked for)."""
+    lib = _lib.load()
+    M, Cc = x.shape
+    _need(tuple(dy.shape) == (M, Cc) and weight.numel() == Cc and (add is None or tuple(add.shape) == (M, Cc)),
+          "layer_norm_backward: dy, x, add [M,C] and weight [C]")
+    _need(not branch or scaled, "layer_norm_backward: the branch's bias gradient is the column sums of out_scaled")
+    dev = x.device
+    res = {"dx": _out_buf(out, "dx", (M, Cc), dev), "dw": _out_buf(out, "dw", (Cc,), dev, True),
+           "db": _out_buf(out, "db", (Cc,), dev, True)}
+    if scaled:
+        res["out_scaled"] = _out_buf(out, "out_scaled", (M, Cc), dev)
+    if branch:
+        res["dbranch"] = _out_buf(out, "dbranch", (Cc,), dev, True)
+    a = _lib.LnbArgs()
+    a.dy, a.x, a.w, a.eps = _ptr(dy, "dy"), _ptr(x, "x"), _ptr(weight, "weight"), float(eps)
+    a.add = _ptr(add, "add") if add is not None else None
+    a.dx = res["dx"].data_ptr()
+    if drop is not None:
+        a.drop = _ptr(drop, "drop")
+    a.temporal, a.J, a.FJ = (int(v) for v in seq_map)
+    a.out_scaled = res["out_scaled"].data_ptr() if scaled else None
+    a.dw, a.db = res["dw"].data_ptr(), res["db"].data_ptr()
+    a.dbranch = res["dbranch"].data_ptr() if branch else None
+    a.M, a.C = M, Cc
+    ws, nbytes = _unit_workspace(lib, M, Cc, 0, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_layernorm_backward(C.byref(a), ws.data_ptr(), nbytes, _stream(x)))
+    for name in ("dx", "out_scaled"):
+        if name in res:
+            res[name] = res[name].reshape(-1)[:M * Cc].view(M, Cc)
+    for name in ("dw", "db", "dbranch"):
+        if name in res:
+            res[name] = res[name].reshape(-1)[:Cc]
+    return res
+
+
+def linear_input_grad(d_y, weight, dact_u=None, precision="bf16x3", image_source=0, out=None):
+    """The training step's dX GEMM on its own (pafuse_linear_input_grad -> input_grad): dX [M,K] = d_y [M,N] weight [N,K],
+    times gelu'(dact_u) [M,K] when given.  precision 'bf16x3' (split products on the M16 image of W^T where the step takes
+    them, M >= 128; image_source 0: split_weights_transposed_kernel, 1: the batch kernel the step uses) or 'f32'.
+    out: a preallocated [>= M*K] output."""
+    lib = _lib.load()
+    M, N = d_y.shape
+    K = weight.shape[1]
+    _need(tuple(weight.shape) == (N, K) and (dact_u is None or tuple(dact_u.shape) == (M, K)),
+          "linear_input_grad: d_y [M,N], weight [N,K], dact_u [M,K]")
+    dev = d_y.device
+    dx = _out_buf({"dx": out} if out is not None else None, "dx", (M, K), dev)
+    ws, nbytes = _unit_workspace(lib, M, N, K, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_linear_input_grad(_ptr(d_y, "d_y"), _ptr(weight, "weight"), _ptr(dact_u, "dact_u") if dact_u is not None else None,
+                                                dx.data_ptr(), M, N, K, PRECISIONS[precision], int(image_source), ws.data_ptr(), nbytes,
+                                                _stream(d_y)))
+    return dx.reshape(-1)[:M * K].view(M, K)
+
+
+def linear_train(x, weight, bias, gelu=True, precision="bf16x3", out=None):
+    """The training forward's plain linear layer on its own (pafuse_linear_train -> plain_linear): u = x W^T + b and, with
+    gelu=True, h = gelu(u) from the same epilogue (mlp.fc1; the time MLP at M < 128).  out: preallocated 'u' / 'h'.
+    Returns (u, h or None)."""
+    lib = _lib.load()
+    M, K = x.shape
+    N = weight.shape[0]
+    _need(tuple(weight.shape) == (N, K) and bias.numel() == N, "linear_train: x [M,K], weight [N,K], bias [N]")
+    dev = x.device
+    u = _out_buf(out, "u", (M, N), dev)
+    h = _out_buf(out, "h", (M, N), dev) if gelu else None
+    ws, nbytes = _unit_workspace(lib, M, N, K, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_linear_train(_ptr(x, "x"), _ptr(weight, "weight"), _ptr(bias, "bias"), u.data_ptr(),
+                                           h.data_ptr() if gelu else None, M, N, K, PRECISIONS[precision], ws.data_ptr(), nbytes,
+                                           _stream(x)))
+    view = lambda t: t.reshape(-1)[:M * N].view(M, N)
+    return view(u), (view(h) if gelu else None)
+
+
+def gelu_backward(u, dh, db=None, in_place=False):
+    """The training step's GELU backward on its own (pafuse_gelu_backward -> gelu_bwd): du = dh gelu'(u) (in_place: written
+    over dh) and db += column sums of du (db None: a new zero vector).  Returns (du, db)."""
+    lib = _lib.load()
+    M, N = u.shape
+    _need(tuple(dh.shape) == (M, N), "gelu_backward: u and dh [M,N]")
+    dev = u.device
+    du = dh if in_place else torch.empty(M, N, device=dev, dtype=torch.float32)
+    db = torch.zeros(N, device=dev, dtype=torch.float32) if db is None else db
+    _need(db.is_contiguous() and db.numel() == N, "gelu_backward: db [N]")
+    ws, nbytes = _unit_workspace(lib, M, N, 0, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_gelu_backward(_ptr(u, "u"), _ptr(dh, "dh"), _ptr(du, "du"), db.data_ptr(), M, N, ws.data_ptr(), nbytes,
+                                            _stream(u)))
+    return du, db
+
+
 def block_forward(block_params, x, heads=8, precision="f32"):
     """Block.forward (common/mixste.py:113-116) on [S,L,C]; ``block_params`` is a pafuse_amd.mixste2._BlockParams;
     ``precision`` the matrix-product mode of its four linear layers (the split modes make their weight images here;

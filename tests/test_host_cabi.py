@@ -51,19 +51,22 @@ def test_struct_layouts_match_header_sizes():
     """ctypes mirrors must have the C layout: check against sizes computed by the C compiler."""
     import ctypes, subprocess, tempfile
     from pafuse_amd import _lib
-    # pafuse_rowln_args is filled field by field from Python: every field's offset is checked, not only the size
+    # pafuse_rowln_args and pafuse_lnb_args are filled field by field from Python: every field's offset is checked, not only the size
     rowln = [f for f, _ in _lib.RowLNArgs._fields_]
-    src = '#include "pafuse_hip.h"\n#include <stddef.h>\n#include <stdio.h>\nint main(){printf("%zu %zu %zu %zu %zu",' \
+    lnb = [f for f, _ in _lib.LnbArgs._fields_]
+    src = '#include "pafuse_hip.h"\n#include <stddef.h>\n#include <stdio.h>\nint main(){printf("%zu %zu %zu %zu %zu %zu",' \
           'sizeof(pafuse_block_weights),sizeof(pafuse_mixste2_weights),sizeof(pafuse_d3dp_config),' \
-          'sizeof(pafuse_ddim_step),sizeof(pafuse_rowln_args));' + \
-          "".join(f'printf(" %zu",offsetof(pafuse_rowln_args,{f}));' for f in rowln) + 'printf("\\n");return 0;}'
+          'sizeof(pafuse_ddim_step),sizeof(pafuse_rowln_args),sizeof(pafuse_lnb_args));' + \
+          "".join(f'printf(" %zu",offsetof(pafuse_rowln_args,{f}));' for f in rowln) + \
+          "".join(f'printf(" %zu",offsetof(pafuse_lnb_args,{f}));' for f in lnb) + 'printf("\\n");return 0;}'
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
         sizes = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
-    assert sizes[:5] == [ctypes.sizeof(_lib.BlockWeights), ctypes.sizeof(_lib.MixSTE2Weights),
-                         ctypes.sizeof(_lib.D3DPConfig), ctypes.sizeof(_lib.DDIMStep), ctypes.sizeof(_lib.RowLNArgs)]
-    assert sizes[5:] == [getattr(_lib.RowLNArgs, f).offset for f in rowln]
+    assert sizes[:6] == [ctypes.sizeof(_lib.BlockWeights), ctypes.sizeof(_lib.MixSTE2Weights), ctypes.sizeof(_lib.D3DPConfig),
+                         ctypes.sizeof(_lib.DDIMStep), ctypes.sizeof(_lib.RowLNArgs), ctypes.sizeof(_lib.LnbArgs)]
+    assert sizes[6:6 + len(rowln)] == [getattr(_lib.RowLNArgs, f).offset for f in rowln]
+    assert sizes[6 + len(rowln):] == [getattr(_lib.LnbArgs, f).offset for f in lnb]
 
 
 def test_state_dict_layout_matches_reference():
