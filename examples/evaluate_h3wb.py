@@ -7,6 +7,7 @@ flip-TTA DDIM sampling on the HIP path -> J-Best / P-Best / P-Agg / J-Agg and th
            ft2d.num_proposals=20 ft2d.sampling_timesteps=10
     torchrun --standalone --nproc-per-node 8 examples/evaluate_h3wb.py ... ft2d.num_proposals=160   # hypothesis-sharded
 
+`ft2d.p2=True` adds Protocol #2 (P-MPJPE after similarity alignment) to the log, as in the reference.
 Trailing `a.b=c` arguments override the config tree like the reference's Hydra command line (pafuse_amd/config.py).
 Without `--data` the synthetic H3WB files of tests/golden/h3wb_synth are used (random weights: numbers are meaningless).
 """
@@ -58,7 +59,7 @@ def main():
     log = print if int(os.environ.get("RANK", "0")) == 0 else (lambda *x: None)
     log("Test time augmentation:", args.model.test_time_augmentation)
     h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
-                  batch_size=args.model.batch_size, log=log)
+                  batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2))
     if world > 1:
         dist.destroy_process_group()
 

@@ -25,6 +25,7 @@
  *   pafuse_ddim_finalize     the output stage of a DDIM step: part concat + un-flip + TTA mean + clamp
  *                            (common/diffusionpose.py:165-171,211-218), epsilon in fp64 (:157-161,222-223), update (:302-312)
  *   pafuse_hypothesis_errors the per-joint part of evaluate()'s aggregation, main_h3wb.py:327-362
+ *   pafuse_procrustes_errors the Protocol #2 part of it (ft2d.p2), main_h3wb.py:381-395, common/loss.py:251-458
  *   pafuse_mixste2_train_*   MixSTE2.forward (is_train=True) + autograd backward, common/mixste.py:215-225,260-298
  *   pafuse_d3dp_qsample      D3DP.prepare_diffusion_concat / q_sample, common/diffusionpose.py:319-326,358-374
  */
@@ -481,6 +482,18 @@ int pafuse_hypothesis_errors(const float *pred, const float *gt, const float *x2
                              const int32_t *conn, const int32_t *pbroot, int32_t B, int32_t T, int32_t P, int32_t F,
                              int32_t J, float *e3, float *epb, float *jbest, float *pagg, float *jagg, float *paggpb,
                              void *stream);
+
+/* Protocol #2 (P-MPJPE) on the same operands - common/loss.py:251-458 as main_h3wb.py:381-395 calls it: every
+ * whole-body hypothesis pose (and, per (b,t,f), the mean over h of them) aligned to its whole-body target by the
+ * reference's similarity transform (scale, rotation with the reflection fix, translation), in fp64.
+ * Outputs: jbest [B,T,F,J] per-joint minimum over h of the aligned error (NaN if any is NaN, like np.min);
+ * pbest_sums double [B,T,P,F] sum over j of the aligned errors of every pose; pagg [B,T,F,J] aligned error of the
+ * mean pose; jagg [B,T,F,J] aligned error of the hypothesis pafuse_hypothesis_errors picks for J-Agg (smallest 2-D
+ * reprojection error of the unaligned pose, first minimum wins; 0 where no reprojection error is finite);
+ * pick int32 [B,T,F,J] (may be NULL) that hypothesis (-1 where none).  J <= 256.  Deterministic, no atomics. */
+int pafuse_procrustes_errors(const float *pred, const float *gt, const float *x2d, const float *traj, const float *cam,
+                             const int32_t *conn, int32_t B, int32_t T, int32_t P, int32_t F, int32_t J, float *jbest,
+                             double *pbest_sums, float *pagg, float *jagg, int32_t *pick, void *stream);
 
 /* Replays the GEMM launches of one flip-TTA denoiser pass (all three parts) back to back on `stream`, for
  * bench.py's per-kernel roofline measurement: returns the number of launches, adds their algorithmic FLOPs to

@@ -2460,4 +2460,264 @@ __global__ void __launch_bounds__(256) metrics_kernel(const MetricsParams p) {
     p.paggpb[e] = sqrtf(n0 * n0 + n1 * n1 + n2 * n2);
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// Protocol #2 (P-MPJPE) behind the all-gather: common/loss.py:251-458 as main_h3wb.py:381-395 calls it on the
+// whole-body poses.  Every hypothesis pose Y is aligned to its target X by the similarity transform of the
+// reference (centre both, H = (X0/|X0|)^T (Y0/|Y0|), R = V U^T with the reflection fix, a = tr(S') |X0| / |Y0|) and
+// the per-joint errors |a Y0_j R - X0_j| are reduced like Protocol #1: running minimum over h (J-Best, NaN
+// propagating like np.min), per-pose sums over j (P-Best, finished by the caller), the hypothesis mean pose aligned
+// once (P-Agg), and the aligned error of the hypothesis whose UNALIGNED pose reprojects best (J-Agg, the pick of
+// metrics_kernel).  R and tr(S') come from Horn's quaternion form: the eigenvector of the largest eigenvalue of a
+// symmetric 4x4 built from H is the proper rotation maximising tr(R H), and that eigenvalue is s0 + s1 + sign(det H) s2
+// - the reference's trace after its reflection fix.  Fixed-count cyclic Jacobi sweeps (5 reach fp64 round-off on
+// 4x4; 8 are run), so no data-dependent loop exists: a degenerate pose (|Y0| = 0) gives NaN, never a hang.
+// One workgroup of P2_WAVES waves per (b, t, f); wave w aligns poses h = w, w + P2_WAVES, ..., P (h = P is the
+// mean pose); lane l holds joints l, l + 64, ... in fp64.  Reductions over joints are butterflies (the same bits in
+// every lane), the per-joint results of the waves are merged in wave order (min and first-minimum are order-free),
+// and the mean pose is summed over h = 0 .. P-1 in order by one thread per joint: results do not depend on P2_WAVES.
+// ----------------------------------------------------------------------------------------------------------------
+constexpr int P2_WAVES = 4;
+constexpr int P2_SLOTS = 4;                  // joints per lane
+constexpr int P2_MAX_J = 64 * P2_SLOTS;      // = the workgroup size: one thread per joint in the per-joint phases
+constexpr int P2_SWEEPS = 8;
+
+struct ProcrustesParams {
+    const float* pred;  // [B,T,P,F,J,3] part-centred predictions
+    const float* gt;    // [B,F,J,3] part-centred ground truth
+    const float* x2d;   // [B,F,J,2]
+    const float* traj;  // [B,F,3]
+    const float* cam;   // [9]
+    const int32_t* conn;   // [J] connection joint (wb_pose_from_parts)
+    float *jbest, *pagg, *jagg;  // [B,T,F,J]
+    double* pbest_sums;          // [B,T,P,F]: sum over j of the aligned errors of every pose
+    int32_t* pick;               // [B,T,F,J] or null: the J-Agg hypothesis (-1 when no reprojection error is finite)
+    int B, T, P, F, J;
+};
+
+__device__ __forceinline__ double p2_wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);   // a + b == b + a: every lane ends with the same bits
+    return v;
+}
+
+__device__ __forceinline__ double p2_min(double a, double e) { return (isnan(e) || e < a) ? e : a; }  // NaN sticks
+
+// The 2-D reprojection error of metrics_kernel (common/camera.py:30-60), restated with the same expressions in the
+// same order so that both kernels pick the same hypothesis.
+__device__ __forceinline__ float p2_reproj_error(const float (&w)[3], const float* tr, const float* cam, const float* x2) {
+    const float fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
+    const float k1 = cam[4], k2 = cam[5], k3 = cam[6], p1 = cam[7], p2 = cam[8];
+    const float X = w[0] + tr[0], Y = w[1] + tr[1], Z = w[2] + tr[2];
+    const float xx = fminf(fmaxf(X / Z, -1.f), 1.f), yy = fminf(fmaxf(Y / Z, -1.f), 1.f);
+    const float r2 = xx * xx + yy * yy;
+    const float radial = 1.f + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2));
+    const float tan = p1 * xx + p2 * yy;
+    const float u = fx * (xx * (radial + tan) + p1 * r2) + cx, v = fy * (yy * (radial + tan) + p2 * r2) + cy;
+    const float q0 = u - x2[0], q1 = v - x2[1];
+    return sqrtf(q0 * q0 + q1 * q1);
+}
+
+// H[a][b] = sum_j X0_ja Y0_jb / (|X0| |Y0|) -> M = a R^T, so that the aligned centred joint is M y0 (column vectors;
+// the reference's row-vector form is y0^T a R).  Wave-uniform: every lane runs the same arithmetic on the same bits.
+__device__ __forceinline__ void p2_similarity(const double (&H)[3][3], double nx_over_ny, double (&M)[3][3]) {
+    // S = H^T: S_ab = sum_j Y0_ja X0_jb (moving points first, Horn 1987)
+    const double Sxx = H[0][0], Sxy = H[1][0], Sxz = H[2][0], Syx = H[0][1], Syy = H[1][1], Syz = H[2][1],
+                 Szx = H[0][2], Szy = H[1][2], Szz = H[2][2];
+    double A[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
+                      {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
+                      {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
+                      {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
+    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+#pragma unroll 1
+    for (int sweep = 0; sweep < P2_SWEEPS; ++sweep) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+#pragma unroll
+            for (int q = p + 1; q < 4; ++q) {
+                const double apq = A[p][q];
+                if (apq != 0.0) {   // NaN goes in: NaN comes out
+                    const double th = (A[q][q] - A[p][p]) / (2.0 * apq);
+                    const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
+                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {   // A J
+                        const double akp = A[k][p], akq = A[k][q];
+                        A[k][p] = c * akp - s * akq, A[k][q] = s * akp + c * akq;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {   // J^T (A J)
+                        const double apk = A[p][k], aqk = A[q][k];
+                        A[p][k] = c * apk - s * aqk, A[q][k] = s * apk + c * aqk;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {   // V J
+                        const double vkp = V[k][p], vkq = V[k][q];
+                        V[k][p] = c * vkp - s * vkq, V[k][q] = s * vkp + c * vkq;
+                    }
+                }
+            }
+        }
+    }
+    double lam = A[0][0], qw = V[0][0], qx = V[1][0], qy = V[2][0], qz = V[3][0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+        if (A[k][k] > lam) lam = A[k][k], qw = V[0][k], qx = V[1][k], qy = V[2][k], qz = V[3][k];
+    const double a = lam * nx_over_ny / (qw * qw + qx * qx + qy * qy + qz * qz);   // scale over |q|^2 of the rotation
+    M[0][0] = a * (qw * qw + qx * qx - qy * qy - qz * qz), M[0][1] = a * 2.0 * (qx * qy - qw * qz), M[0][2] = a * 2.0 * (qx * qz + qw * qy);
+    M[1][0] = a * 2.0 * (qx * qy + qw * qz), M[1][1] = a * (qw * qw - qx * qx + qy * qy - qz * qz), M[1][2] = a * 2.0 * (qy * qz - qw * qx);
+    M[2][0] = a * 2.0 * (qx * qz - qw * qy), M[2][1] = a * 2.0 * (qy * qz + qw * qx), M[2][2] = a * (qw * qw - qx * qx - qy * qy + qz * qz);
+}
+
+__global__ void __launch_bounds__(64 * P2_WAVES) procrustes_kernel(const ProcrustesParams p) {
+    static_assert(64 * P2_WAVES == P2_MAX_J, "the per-joint phases run one thread per joint");
+    __shared__ double mean_pose[P2_MAX_J * 3];
+    __shared__ float w_min[P2_WAVES][P2_MAX_J], w_e2[P2_WAVES][P2_MAX_J], w_sel[P2_WAVES][P2_MAX_J];
+    __shared__ int32_t w_h[P2_WAVES][P2_MAX_J];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = (int)(blockIdx.x % p.F);
+    const int t = (int)((blockIdx.x / p.F) % p.T);
+    const int b = (int)(blockIdx.x / ((unsigned)p.F * p.T));
+    const int J = p.J;
+    const int64_t hstride = (int64_t)p.F * J * 3;
+    const float* pose0 = p.pred + ((((int64_t)b * p.T + t) * p.P) * p.F + f) * J * 3;   // pose h at pose0 + h * hstride
+
+    // mean pose over h in order (torch.mean(predicted, dim=2) of the whole-body poses), one thread per joint
+    if (tid < J) {
+        double s[3] = {0.0, 0.0, 0.0};
+        for (int h = 0; h < p.P; ++h) {
+            float w[3];
+            wb_joint(pose0 + h * hstride, p.conn, tid, w);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s[k] += (double)w[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) mean_pose[tid * 3 + k] = s[k] / (double)p.P;
+    }
+
+    // the target, centred, in every wave
+    const float* gpose = p.gt + ((int64_t)b * p.F + f) * J * 3;
+    double x0[P2_SLOTS][3];
+    double mx[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) {
+        const int j = lane + 64 * s;
+        float g[3] = {0.f, 0.f, 0.f};
+        if (j < J) wb_joint(gpose, p.conn, j, g);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) x0[s][k] = (double)g[k], mx[k] += x0[s][k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) mx[k] = p2_wave_sum(mx[k]) / (double)J;
+    double nx = 0.0;
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) {
+        const bool valid = lane + 64 * s < J;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) x0[s][k] = valid ? x0[s][k] - mx[k] : 0.0, nx += x0[s][k] * x0[s][k];
+    }
+    nx = sqrt(p2_wave_sum(nx));
+
+    const float* tr = p.traj + ((int64_t)b * p.F + f) * 3;
+    const float* x2 = p.x2d + ((int64_t)b * p.F + f) * J * 2;
+    double run_min[P2_SLOTS], sel[P2_SLOTS];
+    float best2[P2_SLOTS];
+    int32_t hsel[P2_SLOTS];
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) run_min[s] = INFINITY, sel[s] = 0.0, best2[s] = INFINITY, hsel[s] = -1;
+    __syncthreads();   // mean_pose
+
+    const int64_t btf = ((int64_t)b * p.T + t) * p.F + f;
+    for (int h = wave; h <= p.P; h += P2_WAVES) {   // h == P: the mean pose (wave-uniform branch)
+        const bool mean = h == p.P;
+        double y[P2_SLOTS][3];
+        float e2[P2_SLOTS];
+        double my[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < P2_SLOTS; ++s) {
+            const int j = lane + 64 * s;
+            e2[s] = INFINITY;
+            float w[3] = {0.f, 0.f, 0.f};
+            if (j < J) {
+                if (mean) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) y[s][k] = mean_pose[j * 3 + k];
+                } else {
+                    wb_joint(pose0 + h * hstride, p.conn, j, w);
+                    e2[s] = p2_reproj_error(w, tr, p.cam, x2 + j * 2);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) y[s][k] = (double)w[k];
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) y[s][k] = 0.0;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) my[k] += y[s][k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) my[k] = p2_wave_sum(my[k]) / (double)J;
+        double ny = 0.0, H[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll
+        for (int s = 0; s < P2_SLOTS; ++s) {
+            const bool valid = lane + 64 * s < J;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) y[s][k] = valid ? y[s][k] - my[k] : 0.0, ny += y[s][k] * y[s][k];
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) H[r][c] += x0[s][r] * y[s][c];
+        }
+        ny = sqrt(p2_wave_sum(ny));
+        const double inv = 1.0 / (nx * ny);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) H[r][c] = p2_wave_sum(H[r][c]) * inv;
+        double M[3][3];
+        p2_similarity(H, nx / ny, M);
+        double err[P2_SLOTS], esum = 0.0;
+#pragma unroll
+        for (int s = 0; s < P2_SLOTS; ++s) {
+            double d[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) d[r] = M[r][0] * y[s][0] + M[r][1] * y[s][1] + M[r][2] * y[s][2] - x0[s][r];
+            err[s] = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+            if (lane + 64 * s < J) esum += err[s];
+        }
+        if (mean) {
+#pragma unroll
+            for (int s = 0; s < P2_SLOTS; ++s)
+                if (lane + 64 * s < J) p.pagg[btf * J + lane + 64 * s] = (float)err[s];
+            continue;
+        }
+        esum = p2_wave_sum(esum);
+        if (lane == 0) p.pbest_sums[((((int64_t)b * p.T + t) * p.P) + h) * p.F + f] = esum;
+#pragma unroll
+        for (int s = 0; s < P2_SLOTS; ++s) {
+            run_min[s] = p2_min(run_min[s], err[s]);
+            if (e2[s] < best2[s]) best2[s] = e2[s], hsel[s] = h, sel[s] = err[s];   // first minimum of this wave's h
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) {
+        const int j = lane + 64 * s;
+        if (j < J) w_min[wave][j] = (float)run_min[s], w_e2[wave][j] = best2[s], w_sel[wave][j] = (float)sel[s], w_h[wave][j] = hsel[s];
+    }
+    __syncthreads();
+    if (tid < J) {
+        float m = w_min[0][tid], b2 = INFINITY, e = 0.f;
+        int32_t hb = -1;
+#pragma unroll
+        for (int w = 0; w < P2_WAVES; ++w) {
+            if (w > 0) m = (float)p2_min(m, w_min[w][tid]);
+            const int32_t hw = w_h[w][tid];
+            // the overall first minimum: the smallest e2, the lowest h among equal ones
+            if (hw >= 0 && (hb < 0 || w_e2[w][tid] < b2 || (w_e2[w][tid] == b2 && hw < hb))) b2 = w_e2[w][tid], hb = hw, e = w_sel[w][tid];
+        }
+        p.jbest[btf * J + tid] = m;
+        p.jagg[btf * J + tid] = e;
+        if (p.pick) p.pick[btf * J + tid] = hb;
+    }
+}
+
 }  // namespace pafuse

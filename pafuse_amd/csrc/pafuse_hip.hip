@@ -1730,6 +1730,24 @@ int pafuse_hypothesis_errors(const float* pred, const float* gt, const float* x2
     return check_launch("metrics_kernel");
 }
 
+int pafuse_procrustes_errors(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,
+                             const int32_t* conn, int32_t B, int32_t T, int32_t P, int32_t F, int32_t J, float* jbest,
+                             double* pbest_sums, float* pagg, float* jagg, int32_t* pick, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!pred || !gt || !x2d || !traj || !cam || !conn || !jbest || !pbest_sums || !pagg || !jagg)
+        return fail(PAFUSE_E_ARG, "procrustes_errors: null pointer");
+    if (B <= 0 || T <= 0 || P <= 0 || F <= 0 || J <= 0) return fail(PAFUSE_E_ARG, "procrustes_errors: bad size");
+    if (J > P2_MAX_J) return fail(PAFUSE_E_ARG, "procrustes_errors: J = %d above the supported %d", J, P2_MAX_J);
+    const int64_t n = (int64_t)B * T * F;
+    if (n > 0x7fffffff) return fail(PAFUSE_E_ARG, "procrustes_errors: B*T*F = %lld workgroups", (long long)n);
+    ProcrustesParams m{};
+    m.pred = pred, m.gt = gt, m.x2d = x2d, m.traj = traj, m.cam = cam, m.conn = conn;
+    m.jbest = jbest, m.pagg = pagg, m.jagg = jagg, m.pbest_sums = pbest_sums, m.pick = pick;
+    m.B = B, m.T = T, m.P = P, m.F = F, m.J = J;
+    hipLaunchKernelGGL(procrustes_kernel, dim3((unsigned)n), dim3(64 * P2_WAVES), 0, (hipStream_t)stream, m);
+    return check_launch("procrustes_kernel");
+}
+
 int pafuse_d3dp_replay_gemms(const pafuse_d3dp_config* cfg, int32_t B, int32_t P, void* workspace,
                              size_t workspace_bytes, void* stream, double* flops) {
     return pafuse_d3dp_replay_layers(cfg, B, P, workspace, workspace_bytes, stream, 15, flops);

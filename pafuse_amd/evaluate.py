@@ -3,7 +3,9 @@
 
 ``hypothesis_errors`` is one HIP kernel over the gathered predictions (whole-body poses from parts, 2-D
 reprojection, per-joint J-Best / P-Agg / J-Agg and the part-re-centred variants); the remaining means over
-(b, f, j) and the P-Best argmin are a handful of reductions over small tensors.
+(b, f, j) and the P-Best argmin are a handful of reductions over small tensors.  With ``p2=True`` a second kernel
+(``procrustes_errors``) adds Protocol #2, the same four numbers after the reference's similarity alignment
+(main_h3wb.py:381-395, common/loss.py:251-458).
 """
 import torch
 
@@ -21,10 +23,11 @@ def _tables(dataset, num_kps, device):
     return conn.to(device), pbroot.to(device)
 
 
-def evaluate_accumulators(pred_parts, gt_parts, inputs_2d, traj, cam, dataset):
+def evaluate_accumulators(pred_parts, gt_parts, inputs_2d, traj, cam, dataset, p2=False):
     """pred_parts [B,T,P,F,J,3], gt_parts [B,F,J,3] (part-centred, metres), inputs_2d [B,F,J,2], traj [B,F,1,3],
     cam [9] or [1,9] -> dict of the 14 per-step vectors [T] the reference accumulates per batch (same names as
-    oracle.d3dp_oracle.evaluate_accumulators; multiply by 1000 for mm)."""
+    oracle.d3dp_oracle.evaluate_accumulators; multiply by 1000 for mm).  ``p2=True`` (the reference's ``ft2d.p2``)
+    adds the four Protocol #2 vectors p2_j_best, p2_p_best, p2_p_agg, p2_j_agg; the 14 others are unchanged."""
     lib = _lib.load()
     if not pred_parts.is_cuda:
         raise _lib.PafuseError("evaluate_accumulators runs on the HIP device only (no CPU fallback)")
@@ -69,4 +72,21 @@ def evaluate_accumulators(pred_parts, gt_parts, inputs_2d, traj, cam, dataset):
         ph = eh[..., idx].reshape(T, P, -1).mean(dim=-1)
         out["p_best_pb_" + part] = ph.gather(1, best.view(-1, 1)).squeeze(1)
         out["p_agg_pb_" + part] = per_t(paggpb[..., idx])
+    if p2:
+        out.update(_protocol2(pred, gt, x2d, tr, cm, conn))
     return out
+
+
+def _protocol2(pred, gt, x2d, traj, cam, conn):
+    """The four Protocol #2 vectors [T] from the per-joint / per-pose aligned errors: means over (b, f, j) in fp64,
+    P-Best's minimum over h NaN-propagating like the reference's np.min; fp32 like the reference's accumulators."""
+    from .ops import procrustes_errors
+    B, T, P, F, J, _ = pred.shape
+    r = procrustes_errors(pred, gt, x2d, traj, cam, conn, pick=False)
+
+    def per_t(x):                                            # [B,T,F,J] -> [T]
+        return x.double().permute(1, 0, 2, 3).reshape(T, -1).mean(dim=-1).float()
+
+    per_h = r["pbest_sums"].permute(1, 2, 0, 3).reshape(T, P, -1).sum(dim=-1) / (B * F * J)
+    return {"p2_j_best": per_t(r["jbest"]), "p2_p_best": per_h.min(dim=1).values.float(), "p2_p_agg": per_t(r["pagg"]),
+            "p2_j_agg": per_t(r["jagg"])}

@@ -11,6 +11,7 @@ from .parallel import ShardedSampler
 ACCUMULATORS = ("j_best", "p_best", "p_agg", "j_agg", "p_best_pb", "p_best_pb_body", "p_best_pb_face",
                 "p_best_pb_left_hand", "p_best_pb_right_hand", "p_agg_pb", "p_agg_pb_body", "p_agg_pb_face",
                 "p_agg_pb_left_hand", "p_agg_pb_right_hand")
+ACCUMULATORS_P2 = ACCUMULATORS + ("p2_j_best", "p2_p_best", "p2_p_agg", "p2_j_agg")   # with ft2d.p2 (main_h3wb.py:225-228)
 
 
 def flip_2d(inputs_2d, kps_left, kps_right):
@@ -142,12 +143,13 @@ def load_checkpoint(model, checkpoint):
 
 
 @torch.no_grad()
-def evaluate_sequence(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, batch_size=1024, group=None):
+def evaluate_sequence(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, batch_size=1024, group=None, p2=False):
     """One (camera, sequence) item of evaluate()'s loop (main_h3wb.py:261-396).
 
     seq_2d [N,J,2] normalised 2-D input, seq_3d [N,J,3] camera-space ground truth (metres), cam [9] intrinsics.
     Returns ``(sums, n)``: the 14 accumulators [T] already multiplied by the batch multiplier (clips x frames), and
     the multiplier total - add them over sequences and report ``sums[k] / n * 1000`` mm, like :func:`report`.
+    ``p2=True`` adds the four Protocol #2 accumulators (ACCUMULATORS_P2, the reference's ``ft2d.p2``).
     With torch.distributed initialised the hypothesis axis is sharded and gathered (pafuse_amd.parallel)."""
     dev = next(model.parameters()).device
     seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
@@ -163,7 +165,7 @@ def evaluate_sequence(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, 
     for lo in range(0, x2d.shape[0], batch_size):
         hi = min(lo + batch_size, x2d.shape[0])
         pred = sampler(x2d[lo:hi], gt_parts[lo:hi], input_2d_flip=x2d_flip[lo:hi])      # [b,T,P,F,J,3]
-        acc = evaluate_accumulators(pred, gt_parts[lo:hi], x2d[lo:hi], traj[lo:hi], cam, dataset)
+        acc = evaluate_accumulators(pred, gt_parts[lo:hi], x2d[lo:hi], traj[lo:hi], cam, dataset, p2=p2)
         mult = (hi - lo) * model.frames                           # main_h3wb.py:333
         sums = {k: mult * v for k, v in acc.items()} if sums is None else {k: sums[k] + mult * acc[k] for k in acc}
         n += mult
@@ -178,7 +180,9 @@ def report(sums, n):
 def format_report(rep, test_time_augmentation=True, action=None):
     """The reference's evaluation log, line for line (main_h3wb.py:406-509): returns ``(printed, written)`` - the lines
     evaluate() prints and the lines it appends to ``h36m_test_log_H<P>_K<T>.txt`` (the reference prints P_Best but
-    does not write it, and writes each part-based header twice; both quirks are kept so files diff clean)."""
+    does not write it, and writes each part-based header twice; both quirks are kept so files diff clean).  When ``rep``
+holds the p2_* keys, each step ends with the four Protocol #2 lines (:511-519): printed as ``print(fmt % ii, value,
+'mm')`` prints them (``str`` of the value), written with ``%f``, P_Best written too."""
     printed, written = [], []
 
     def both(line):
@@ -206,5 +210,10 @@ def format_report(rep, test_time_augmentation=True, action=None):
             both("step %d : Protocol #1 Error (MPJPE) %s Part-Based HANDS: %f mm" % (ii, name, hands(key)))
             both("step %d : Protocol #1 Error (MPJPE) %s Part-Based LEFT HAND: %f mm" % (ii, name, rep[key + "_left_hand"][ii]))
             both("step %d : Protocol #1 Error (MPJPE) %s Part-Based RIGHT HAND: %f mm" % (ii, name, rep[key + "_right_hand"][ii]))
+        if "p2_j_best" in rep:
+            for key, name in (("p2_j_best", "J_Best"), ("p2_p_best", "P_Best"), ("p2_p_agg", "P_Agg"), ("p2_j_agg", "J_Agg")):
+                head = "step %d : Protocol #2 Error (MPJPE) %s:" % (ii, name)
+                printed.append(" ".join((head, str(rep[key][ii]), "mm")))
+                written.append("%s %f mm" % (head, rep[key][ii]))
     both("----------")
     return printed, written

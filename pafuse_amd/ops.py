@@ -639,3 +639,29 @@ def linear_rowln_group(layers, shared_grid=True):
     with torch.cuda.device(dev):
         _lib.check(lib.pafuse_linear_rowln_group(arr, len(built), int(bool(shared_grid)), _stream(layers[0]["x"])))
     return [b[2]() for b in built]
+
+
+def procrustes_errors(pred, gt, x2d, traj, cam, conn, pick=True):
+    """Protocol #2 per-joint / per-pose errors (pafuse_procrustes_errors): pred [B,T,P,F,J,3] and gt [B,F,J,3]
+    part-centred, x2d [B,F,J,2], traj [B,F,3] (or [B,F,1,3]), cam [9], conn int32 [J] (connection joint of every
+    joint) -> dict jbest, pagg, jagg [B,T,F,J] fp32, pbest_sums [B,T,P,F] fp64 and (pick=True) the J-Agg pick [B,T,F,J]
+    int32.  fp32 operands on one HIP device, contiguous."""
+    lib = _lib.load()
+    _need(pred.dim() == 6 and pred.shape[-1] == 3, f"procrustes_errors: pred must be [B,T,P,F,J,3], got {tuple(pred.shape)}")
+    B, T, P, F, J, _ = pred.shape
+    _need(tuple(gt.shape) == (B, F, J, 3) and tuple(x2d.shape) == (B, F, J, 2) and traj.numel() == B * F * 3
+          and cam.numel() == 9 and conn.numel() == J, "procrustes_errors: operands do not match pred")
+    ops = (pred, gt, x2d, traj, cam, conn)
+    _need(all(t.is_cuda and t.device == pred.device and t.is_contiguous() for t in ops), "procrustes_errors: contiguous "
+          "tensors on one HIP device (no CPU fallback)")
+    _need(all(t.dtype == torch.float32 for t in ops[:5]) and conn.dtype == torch.int32, "procrustes_errors: dtypes")
+    dev = pred.device
+    out = {k: torch.empty(B, T, F, J, device=dev) for k in ("jbest", "pagg", "jagg")}
+    out["pbest_sums"] = torch.empty(B, T, P, F, device=dev, dtype=torch.float64)
+    if pick:
+        out["pick"] = torch.empty(B, T, F, J, device=dev, dtype=torch.int32)
+    _lib.check(lib.pafuse_procrustes_errors(
+        pred.data_ptr(), gt.data_ptr(), x2d.data_ptr(), traj.data_ptr(), cam.data_ptr(), conn.data_ptr(), B, T, P, F, J,
+        out["jbest"].data_ptr(), out["pbest_sums"].data_ptr(), out["pagg"].data_ptr(), out["jagg"].data_ptr(),
+        out["pick"].data_ptr() if pick else None, _stream(pred)))
+    return out
