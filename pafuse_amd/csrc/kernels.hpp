@@ -1822,6 +1822,109 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnParams p) {
     }
 }
 
+// Long sequences (144 < L <= 256: 243-frame clips): attn_kernel's arithmetic carried to LP = 256.  One (sequence, head)
+// per workgroup of 16 waves, wave w = query tile w; K and V of the item in LDS (2 x 256 x (DP + 4) floats, 104 KB at DP =
+// 48: one workgroup per CU); all keys of a query in 16 x 4 accumulator registers.  Key tiles past the last one holding a
+// key are skipped (uniform branches), so L = 145 does not pay for 256.  S is accumulated key tile by key tile (kt outer)
+// so that only one tile's K fragments are live next to the 64 score registers.
+constexpr int ATTN_LONG_LP = 256;
+template <int DP>
+__global__ void __launch_bounds__(1024) attn_long_kernel(const AttnParams p) {
+    PAFUSE_XQ_GUARD();
+    constexpr int LP = ATTN_LONG_LP, T = LP / 16, SD = DP / 16, CT = DP / 16, LDV = DP + 4, C4 = DP / 4;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* Ks = smem;             // [LP][LDV]
+    float* Vs = smem + LP * LDV;  // [LP][LDV]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, g = lane >> 4;
+    int64_t seq;
+    int head;
+    attn_item<1>((int64_t)blockIdx.x, p.nseq, p.heads, seq, head);
+    const int64_t base = (seq / p.group) * p.group_stride + (seq % p.group) * p.seq_stride;
+    const int C3 = 3 * p.C, nt = (p.L + 15) / 16;
+    f32x4 qf[SD];
+    {
+        const int q = 16 * w + l15;
+#pragma unroll
+        for (int s = 0; s < SD; ++s) {
+            qf[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (q < p.L && 16 * s + 4 * g < p.d)
+                qf[s] = *reinterpret_cast<const f32x4*>(p.qkv + (base + (int64_t)q * p.tok_stride) * C3 + head * p.d + 16 * s + 4 * g);
+        }
+    }
+    for (int idx = tid; idx < nt * 16 * C4; idx += 1024) {   // the rows of the nt key tiles, zero past L
+        const int t = idx / C4, c4 = idx % C4;
+        f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+        if (t < p.L && c4 * 4 < p.d) {
+            const float* src = p.qkv + (base + (int64_t)t * p.tok_stride) * C3 + head * p.d + c4 * 4;
+            kv = *reinterpret_cast<const f32x4*>(src + p.C);
+            vv = *reinterpret_cast<const f32x4*>(src + 2 * p.C);
+        }
+        *reinterpret_cast<f32x4*>(Ks + t * LDV + c4 * 4) = kv;
+        *reinterpret_cast<f32x4*>(Vs + t * LDV + c4 * 4) = vv;
+    }
+    __syncthreads();
+    if (w >= nt) return;
+    f32x4 sc[T];
+#pragma unroll
+    for (int kt = 0; kt < T; ++kt) {
+        sc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (kt < nt) {
+#pragma unroll
+            for (int s = 0; s < SD; ++s) {
+                const f32x4 kf = *reinterpret_cast<const f32x4*>(Ks + (kt * 16 + l15) * LDV + 16 * s + 4 * g);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sc[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[j], qf[s][j], sc[kt], 0, 0, 0);
+            }
+        }
+    }
+    // sc[kt][reg] = <q, k> for query 16 w + l15 and key 16 kt + 4 g + reg; softmax as in attn_kernel
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < T; ++kt)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const float v = kt * 16 + 4 * g + reg < p.L ? sc[kt][reg] * p.scale : -INFINITY;
+            sc[kt][reg] = v;
+            mx = fmaxf(mx, v);
+        }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    float sum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < T; ++kt)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const float e = __builtin_amdgcn_exp2f((sc[kt][reg] - mx) * 1.44269504088896340736f);   // 0 for the masked keys
+            sc[kt][reg] = e;
+            sum += e;
+        }
+    sum += __shfl_xor(sum, 16);
+    sum += __shfl_xor(sum, 32);
+    const float inv = 1.0f / sum;
+    // O^T = V^T P^T as in attn_kernel (1 / sum applied to P first, as there)
+    f32x4 oc[CT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) oc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kt = 0; kt < T; ++kt)
+        if (kt < nt) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const float pr = sc[kt][reg] * inv;
+                const float* vrow = Vs + (kt * 16 + 4 * g + reg) * LDV + l15;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) oc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[ct * 16], pr, oc[ct], 0, 0, 0);
+            }
+        }
+    const int q = 16 * w + l15;
+    if (q < p.L) {
+        float* orow = p.o + (base + (int64_t)q * p.tok_stride) * p.C + head * p.d + 4 * g;
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+            if (ct * 16 + 4 * g < p.d) *reinterpret_cast<f32x4*>(orow + ct * 16) = oc[ct];
+    }
+}
+
 // ----------------------------------------------------------------------------------------------------------------
 // qkv projection + attention of one head in ONE kernel (round 3; split-precision inference):
 //   o[rows of the tile, head] = softmax(q k^T * scale) v,   (q | k | v) = A[rows] @ W'_head^T + b_head   (+ folded LayerNorm)

@@ -636,13 +636,31 @@ int launch_attn(const AttnParams& p, hipStream_t s) {
     return check_launch("attn_kernel");
 }
 
+template <int DP>
+int launch_attn_long(const AttnParams& p, hipStream_t s) {
+    constexpr size_t lds = (size_t)2 * ATTN_LONG_LP * (DP + 4) * sizeof(float);   // 104 KB at DP = 48
+    static_assert(lds <= 160 * 1024, "LDS");
+    const int64_t grid = p.nseq * p.heads;
+    if (grid > 0x7fffffff) return fail(PAFUSE_E_ARG, "attention grid out of range");
+    {
+        static DeviceOnce once;
+        if (once.first()) hipFuncSetAttribute((const void*)attn_long_kernel<DP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    }
+    hipLaunchKernelGGL(attn_long_kernel<DP>, dim3((unsigned)grid), dim3(1024), lds, s, p);
+    return check_launch("attn_long_kernel");
+}
+
 int attention(const AttnParams& p, hipStream_t s) {
     if (p.nseq <= 0) return PAFUSE_OK;
 #ifdef PAFUSE_ABL_NO_ATTENTION   // timing ablation (tools/): what the loop costs with every attention launch removed (results wrong)
     return PAFUSE_OK;
 #endif
-    if (p.d % 4 || p.d > 48 || p.L > 144 || p.L <= 0)
-        return fail(PAFUSE_E_SHAPE, "attention: head dim %d (need %%4, <=48) / length %d (need <=144)", p.d, p.L);
+    if (p.d % 4 || p.d > 48 || p.L > ATTN_LONG_LP || p.L <= 0)
+        return fail(PAFUSE_E_SHAPE, "attention: head dim %d (need %%4, <=48) / length %d (need <=%d)", p.d, p.L, ATTN_LONG_LP);
+    if (p.L > 144) {   // long temporal sequences (clips of 145 .. 256 frames): fp32 output rows only
+        if (p.o_h) return fail(PAFUSE_E_SHAPE, "attention: no f16x2 image output for sequences of %d > 144 tokens: use mode 2", p.L);
+        return p.d <= 32 ? launch_attn_long<32>(p, s) : launch_attn_long<48>(p, s);
+    }
     const int dp = p.d <= 32 ? 32 : 48;
     const int lp = p.L <= 32 ? 32 : (p.L <= 48 ? 48 : (p.L <= 80 ? 80 : 144));
     if (lp == 144)  // the single-model variant: one sequence of all 134 keypoints (common/diffusionpose.py:150-153)
@@ -721,8 +739,10 @@ int check_weights(const pafuse_mixste2_weights* w, bool training = false) {
     if (w->heads <= 0 || w->channels % w->heads) return fail(PAFUSE_E_SHAPE, "heads %d !| C %d", w->heads, w->channels);
     const int d = w->channels / w->heads;
     if (d % 4 || d > 48) return fail(PAFUSE_E_SHAPE, "head dim %d unsupported", d);
-    if (w->joints < 1 || w->joints > 144 || w->frames < 1 || w->frames > 144)
-        return fail(PAFUSE_E_SHAPE, "sequence lengths J=%d F=%d must be in 1..144", w->joints, w->frames);
+    if (w->joints < 1 || w->joints > 144 || w->frames < 1 || w->frames > ATTN_LONG_LP)
+        return fail(PAFUSE_E_SHAPE, "sequence lengths J=%d F=%d: J must be in 1..144, F in 1..%d", w->joints, w->frames, ATTN_LONG_LP);
+    if (w->operand_bf16 == 3 && w->frames > 144)   // (the long-sequence attention writes fp32 rows, not the f16x2 H image)
+        return fail(PAFUSE_E_SHAPE, "f16x2: no attention form for clips of %d > 144 frames: use mode 2", w->frames);
     if (w->operand_bf16 < 0 || w->operand_bf16 > 4) return fail(PAFUSE_E_ARG, "matrix-product mode %d", w->operand_bf16);
     if (w->operand_bf16 >= 3) {   // the image pipelines: the PAFUSE part widths; plain layers that tile by 128 or 224 columns
         const int hidden = w->mlp_hidden > 0 ? w->mlp_hidden : 2 * w->channels;
@@ -1102,7 +1122,8 @@ int pafuse_mode_supported(int32_t mode, int32_t C, int32_t hidden, int32_t heads
     if (mode < 0 || mode > 4 || heads <= 0 || C <= 0 || C % heads) return 0;
     if (hidden <= 0) hidden = 2 * C;
     const int d = C / heads;
-    if (!width_supported(C) || d % 4 || d > 48 || joints < 1 || joints > 144 || frames < 1 || frames > 144) return 0;
+    if (!width_supported(C) || d % 4 || d > 48 || joints < 1 || joints > 144 || frames < 1 || frames > ATTN_LONG_LP) return 0;
+    if (mode == 3 && frames > 144) return 0;
     if (mode >= 3 && (!hgemm_width(C) || !hgemm_plain_n(3 * C) || !hgemm_plain_n(hidden) || hidden % 32)) return 0;
     if (mode == 4 && (!xfqa_has(joints, d, heads) || !xfqa_has(frames, d, heads))) return 0;
     return 1;
@@ -1932,9 +1953,10 @@ int pafuse_mixste2_train_forward(const pafuse_mixste2_weights* w, const float* x
     if (!x2d || !x3d || !t || !out || !saved || B <= 0) return fail(PAFUSE_E_ARG, "mixste2_train_forward: bad argument");
     if ((w->mlp_hidden && w->mlp_hidden != 2 * w->channels) || w->qk_scale != 0.f)
         return fail(PAFUSE_E_SHAPE, "training implements the PAFUSE configuration only (mlp_ratio = 2, qk_scale = None)");
-    if (w->joints > 80 || w->frames > 80)  // attn_backward_kernel keeps one item in LDS (train_kernels.hpp)
-        return fail(PAFUSE_E_SHAPE, "training: sequence lengths J=%d F=%d must be <= 80 (the single-model variant is inference only)",
-                    w->joints, w->frames);
+    // (the spatial sequences stay within the short attention backward kernels; the temporal ones may use the long one)
+    if (w->joints > 80 || w->frames > ATTN_BWD_LONG_LP)
+        return fail(PAFUSE_E_SHAPE, "training: sequence lengths J=%d F=%d must be <= 80 / <= %d (the single-model variant is inference only)",
+                    w->joints, w->frames, ATTN_BWD_LONG_LP);
     if (saved_bytes < train_bytes(w, B)) return fail(PAFUSE_E_WORKSPACE, "mixste2_train_forward: buffer too small");
     TrainBuffers tb;
     carve_train((char*)saved, w, B, tb);

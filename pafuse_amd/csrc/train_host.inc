@@ -318,8 +318,23 @@ int launch_attn_backward_mfma(const AttnBackwardParams& ab, hipStream_t s) {
     return check_launch("attn_backward_mfma_kernel");
 }
 
+template <int DP>
+int launch_attn_backward_long(const AttnBackwardParams& ab, hipStream_t s) {
+    constexpr size_t lds = ((size_t)2 * ATTN_BWD_LONG_LP * (DP + 4) + 3 * ATTN_BWD_LONG_LP) * sizeof(float);   // 107 KB at DP = 48
+    static_assert(lds <= 160 * 1024, "LDS");
+    const int64_t grid = ab.nseq * ab.heads;
+    if (grid > 0x7fffffff) return fail(PAFUSE_E_ARG, "attention backward grid out of range");
+    auto k = attn_backward_long_kernel<DP, 4>;
+    {
+        static DeviceOnce once;
+        if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    }
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(1024), lds, s, ab);
+    return check_launch("attn_backward_long_kernel");
+}
+
 // dqkv from qkv and dO: on the fp32 matrix cores for the PAFUSE sequence lengths and head widths (L <= 80, d <= 48, d % 4 == 0),
-// the FMA kernel otherwise
+// the FMA kernel where its two L x L planes fit the LDS, the long-sequence MFMA kernel above that (L <= 256, d <= 48)
 int attention_backward(const AttnBackwardParams& ab, hipStream_t s) {
     if (ab.d % 4 == 0 && ab.d <= 48 && ab.L <= 80) {
         const int lp = ab.L <= 32 ? 32 : (ab.L <= 48 ? 48 : 80);
@@ -334,7 +349,11 @@ int attention_backward(const AttnBackwardParams& ab, hipStream_t s) {
     }
     const int L4 = (ab.L + 3) / 4 * 4;
     const size_t lds = ((size_t)4 * L4 * attn_bwd_pitch(ab.d) + (size_t)2 * ab.L * (L4 + 1)) * sizeof(float);
-    if (lds > 160 * 1024) return fail(PAFUSE_E_SHAPE, "attention backward: L=%d d=%d exceed LDS", ab.L, ab.d);
+    if (lds > 160 * 1024 && ab.d % 4 == 0 && ab.d <= 48 && ab.L <= ATTN_BWD_LONG_LP)   // long clips: no L x L plane
+        return ab.d <= 32 ? launch_attn_backward_long<32>(ab, s) : launch_attn_backward_long<48>(ab, s);
+    if (lds > 160 * 1024)
+        return fail(PAFUSE_E_SHAPE, "attention backward: L=%d d=%d exceed LDS (sequences of up to %d tokens at head dim <= 48)", ab.L, ab.d,
+                    ATTN_BWD_LONG_LP);
     {
         static DeviceOnce once;  // per device: a one-process multi-device caller (nn.DataParallel) reaches this on each
         if (once.first())

@@ -1099,6 +1099,220 @@ __global__ void __launch_bounds__((LP / 16) * 64) attn_backward_mfma_kernel(cons
     }
 }
 
+// Long sequences (80 < L <= 256 where the FMA kernel's two L x L planes do not fit the LDS): attn_backward_mfma_kernel's
+// two passes with the sequence cut into blocks of KB tiles, so that no L x L plane and no all-keys accumulator set is
+// ever live.  One (sequence, head) per workgroup of 16 waves; LDS holds two [256][DP + 4] operands (K and V in pass 1,
+// then Q and dO in pass 2) and the three row statistics: 107 KB at DP = 48.
+//   pass 1  wave w = query tile w.  Sweep A over the key blocks: S^T and dP^T, online row max / sum / sum(e dP) (the
+//           sums rescaled when the max grows).  Sweep B: S^T and dP^T again, P = exp(S - max) / sum exactly as the short
+//           kernel forms it, dS, dQ^T += K^T dS^T.  (max, 1 / sum, rowsum(P dP)) of every query go to LDS.
+//   pass 2  wave w = key tile w, its K / V fragments from global; Q and dO replace K and V in LDS.  Per query block:
+//           S and dP, P and dS from the statistics, dK^T += Q^T dS and dV^T += dO^T P.
+// Every output element is written once by one lane, no atomics: bit-identical from run to run.
+constexpr int ATTN_BWD_LONG_LP = 256;
+template <int DP, int KB>
+__global__ void __launch_bounds__(1024) attn_backward_long_kernel(const AttnBackwardParams p) {
+    constexpr int LP = ATTN_BWD_LONG_LP, T = LP / 16, NB = T / KB, CT = DP / 16, SD = DP / 16, LDV = DP + 4, C4 = DP / 4;
+    static_assert(T % KB == 0, "key blocks tile the sequence");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* As = smem;               // [LP][LDV]: K, then Q
+    float* Bs = As + LP * LDV;      // [LP][LDV]: V, then dO
+    float* St = Bs + LP * LDV;      // [3][LP]: row max, 1 / row sum, rowsum(P dP)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, g = lane >> 4;
+    int64_t seq;
+    int head;
+    attn_item<1>((int64_t)blockIdx.x, p.nseq, p.heads, seq, head);
+    const int64_t base = (seq / p.group) * p.group_stride + (seq % p.group) * p.seq_stride;
+    const int C3 = 3 * p.C, nt = (p.L + 15) / 16;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    constexpr float LOG2E = 1.44269504088896340736f;
+    // stage two of the four operands, all LP rows (zero past L: the last key / query block may reach past tile nt - 1);
+    // a = the qkv row at offset oa, b = the qkv row at offset ob or the dO row
+    auto stage = [&](int oa, int ob, bool b_is_do) {
+        for (int idx = tid; idx < LP * C4; idx += 1024) {
+            const int t = idx / C4, c4 = idx % C4;
+            f32x4 a = zero, b = zero;
+            if (t < p.L && 4 * c4 < p.d) {
+                const int64_t row = base + (int64_t)t * p.tok_stride;
+                const float* src = p.qkv + row * C3 + head * p.d + 4 * c4;
+                a = *reinterpret_cast<const f32x4*>(src + oa);
+                b = b_is_do ? *reinterpret_cast<const f32x4*>(p.d_o + row * p.C + head * p.d + 4 * c4)
+                            : *reinterpret_cast<const f32x4*>(src + ob);
+            }
+            *reinterpret_cast<f32x4*>(As + t * LDV + 4 * c4) = a;
+            *reinterpret_cast<f32x4*>(Bs + t * LDV + 4 * c4) = b;
+        }
+    };
+    // this lane's fragments of token 16 w + l15 (channels 16 s + 4 g .. + 3): x = qkv at offset o, or dO
+    auto frag = [&](f32x4* f, int o, bool is_do) {
+        const int t = 16 * w + l15;
+#pragma unroll
+        for (int s = 0; s < SD; ++s) {
+            f[s] = zero;
+            if (t < p.L && 16 * s + 4 * g < p.d) {
+                const int64_t row = base + (int64_t)t * p.tok_stride;
+                f[s] = is_do ? *reinterpret_cast<const f32x4*>(p.d_o + row * p.C + head * p.d + 16 * s + 4 * g)
+                             : *reinterpret_cast<const f32x4*>(p.qkv + row * C3 + o + head * p.d + 16 * s + 4 * g);
+            }
+        }
+    };
+    stage(p.C, 2 * p.C, false);   // K, V
+    __syncthreads();
+    // ------------------------------------------------------------------ pass 1: query 16 w + l15 on the lane
+    if (w < nt) {
+        f32x4 qf[SD], gf[SD];
+        frag(qf, 0, false);
+        frag(gf, 0, true);
+        // S^T and dP^T of key block kb: sc[kk][reg] = scale <q, k>, dc[kk][reg] = <dO, v> for key 16 (KB kb + kk) + 4 g + reg
+        auto scores = [&](int kb, f32x4* sc, f32x4* dc) {
+#pragma unroll
+            for (int kk = 0; kk < KB; ++kk) sc[kk] = zero, dc[kk] = zero;
+#pragma unroll
+            for (int s = 0; s < SD; ++s)
+#pragma unroll
+                for (int kk = 0; kk < KB; ++kk) {
+                    const int r = (16 * (KB * kb + kk) + l15) * LDV + 16 * s + 4 * g;
+                    const f32x4 kf = *reinterpret_cast<const f32x4*>(As + r), vf = *reinterpret_cast<const f32x4*>(Bs + r);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        sc[kk] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[j], qf[s][j], sc[kk], 0, 0, 0);
+                        dc[kk] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[j], gf[s][j], dc[kk], 0, 0, 0);
+                    }
+                }
+#pragma unroll
+            for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg)
+                    sc[kk][reg] = 16 * (KB * kb + kk) + 4 * g + reg < p.L ? sc[kk][reg] * p.scale : -INFINITY;
+        };
+        float mx = -INFINITY, sum = 0.f, edp = 0.f;   // sum / edp: this lane's keys, relative to mx
+        for (int kb = 0; kb < NB && KB * kb < nt; ++kb) {
+            f32x4 sc[KB], dc[KB];
+            scores(kb, sc, dc);
+            float bm = -INFINITY;
+#pragma unroll
+            for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) bm = fmaxf(bm, sc[kk][reg]);
+            bm = fmaxf(bm, __shfl_xor(bm, 16));
+            bm = fmaxf(bm, __shfl_xor(bm, 32));
+            const float mn = fmaxf(mx, bm);   // finite: the block's first key is < L
+            const float alpha = __builtin_amdgcn_exp2f((mx - mn) * LOG2E);   // 0 on the first block
+            sum *= alpha, edp *= alpha, mx = mn;
+#pragma unroll
+            for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const float e = __builtin_amdgcn_exp2f((sc[kk][reg] - mx) * LOG2E);   // 0 for the masked keys
+                    sum += e;
+                    edp += e * dc[kk][reg];
+                }
+        }
+        sum += __shfl_xor(sum, 16);
+        sum += __shfl_xor(sum, 32);
+        edp += __shfl_xor(edp, 16);
+        edp += __shfl_xor(edp, 32);
+        const float inv = 1.0f / sum, dot = edp * inv;
+        if (g == 0) St[16 * w + l15] = mx, St[LP + 16 * w + l15] = inv, St[2 * LP + 16 * w + l15] = dot;
+        f32x4 dq[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) dq[ct] = zero;
+        for (int kb = 0; kb < NB && KB * kb < nt; ++kb) {
+            f32x4 sc[KB], dc[KB];
+            scores(kb, sc, dc);
+#pragma unroll
+            for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const float pr = __builtin_amdgcn_exp2f((sc[kk][reg] - mx) * LOG2E) * inv;
+                    sc[kk][reg] = pr * (dc[kk][reg] - dot) * p.scale;   // dS (0 where P is 0)
+                }
+            // dQ^T += K^T dS^T: the K element is the A operand (row = channel), dS the B operand (column = query)
+#pragma unroll
+            for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const float* krow = As + (16 * (KB * kb + kk) + 4 * g + reg) * LDV + l15;
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct)
+                        dq[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(krow[16 * ct], sc[kk][reg], dq[ct], 0, 0, 0);
+                }
+        }
+        const int q1 = 16 * w + l15;
+        if (q1 < p.L) {
+            float* dst = p.dqkv + (base + (int64_t)q1 * p.tok_stride) * C3 + head * p.d + 4 * g;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+                if (16 * ct + 4 * g < p.d) *reinterpret_cast<f32x4*>(dst + 16 * ct) = dq[ct];
+        }
+    }
+    __syncthreads();   // K and V are no longer read
+    stage(0, 0, true);   // Q, dO
+    __syncthreads();
+    // ------------------------------------------------------------------ pass 2: key 16 w + l15 on the lane
+    if (w < nt) {
+        f32x4 kf[SD], vf[SD];
+        frag(kf, p.C, false);
+        frag(vf, 2 * p.C, false);
+        const int k1 = 16 * w + l15;
+        f32x4 dk[CT], dv[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) dk[ct] = zero, dv[ct] = zero;
+        for (int qb = 0; qb < NB && KB * qb < nt; ++qb) {
+            f32x4 s2[KB], d2[KB];
+#pragma unroll
+            for (int qq = 0; qq < KB; ++qq) s2[qq] = zero, d2[qq] = zero;
+#pragma unroll
+            for (int s = 0; s < SD; ++s)
+#pragma unroll
+                for (int qq = 0; qq < KB; ++qq) {
+                    const int r = (16 * (KB * qb + qq) + l15) * LDV + 16 * s + 4 * g;
+                    const f32x4 qf = *reinterpret_cast<const f32x4*>(As + r), gf = *reinterpret_cast<const f32x4*>(Bs + r);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        s2[qq] = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[j], kf[s][j], s2[qq], 0, 0, 0);
+                        d2[qq] = __builtin_amdgcn_mfma_f32_16x16x4f32(gf[j], vf[s][j], d2[qq], 0, 0, 0);
+                    }
+                }
+            // s2[qq][reg] = <q, k>, d2[qq][reg] = <dO, v> for query 16 (KB qb + qq) + 4 g + reg and key 16 w + l15
+#pragma unroll
+            for (int qq = 0; qq < KB; ++qq)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int q = 16 * (KB * qb + qq) + 4 * g + reg;
+                    float pr = 0.f, ds = 0.f;   // (the statistics of queries past L were never written)
+                    if (q < p.L && k1 < p.L) {
+                        pr = __builtin_amdgcn_exp2f((s2[qq][reg] * p.scale - St[q]) * LOG2E) * St[LP + q];
+                        ds = pr * (d2[qq][reg] - St[2 * LP + q]) * p.scale;
+                    }
+                    s2[qq][reg] = pr;   // P
+                    d2[qq][reg] = ds;   // dS
+                }
+            // dK^T += Q^T dS, dV^T += dO^T P: the Q / dO element is the A operand (row = channel), dS / P the B operand
+#pragma unroll
+            for (int qq = 0; qq < KB; ++qq)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int r = (16 * (KB * qb + qq) + 4 * g + reg) * LDV + l15;
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) {
+                        dk[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(As[r + 16 * ct], d2[qq][reg], dk[ct], 0, 0, 0);
+                        dv[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(Bs[r + 16 * ct], s2[qq][reg], dv[ct], 0, 0, 0);
+                    }
+                }
+        }
+        if (k1 < p.L) {
+            float* dst = p.dqkv + (base + (int64_t)k1 * p.tok_stride) * C3 + head * p.d + 4 * g;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+                if (16 * ct + 4 * g < p.d) {
+                    *reinterpret_cast<f32x4*>(dst + p.C + 16 * ct) = dk[ct];
+                    *reinterpret_cast<f32x4*>(dst + 2 * p.C + 16 * ct) = dv[ct];
+                }
+        }
+    }
+}
+
 // ----------------------------------------------------------------------------------------------------------------
 // Small reductions of the first / last layers
 // ----------------------------------------------------------------------------------------------------------------

@@ -143,9 +143,11 @@ class D3DP(nn.Module):
         #                                      (same bits; pafuse_d3dp_config.part_by_part_launches - tests and A/B timing)
         self.use_graph = False         # replay the whole loop as one hipGraph (captured per input shape).  Measured in round 4
         #                                (profiles/r04_sweep.json): not faster at any P, so off
-        self.max_rows_per_launch = 640  # nflip*B*P hypothesis passes per library call: larger batches are cut along
-        #                                 the clip axis (clips are independent, results are bit-identical); bounds the
-        #                                 workspace (0.9 GB per 40 rows) and keeps activations cache-resident
+        self.max_rows_per_launch = 640  # nflip*B*P hypothesis passes of 27-frame clips per library call: larger batches
+        #                                 are cut along the clip axis (clips are independent, results are bit-identical);
+        #                                 bounds the workspace (0.9 GB per 40 rows of 27 frames) and keeps activations
+        #                                 cache-resident.  Longer clips scale it by 27 / frames (clips_per_launch): the
+        #                                 workspace of a row grows with the frames (8.2 GB per 40 rows of 243 frames)
         self._graphs = {}
         # matrix-product mode: 'bf16x3' everywhere - split-precision products whose operands carry all 24 bits of the fp32
         # numbers they stand for (three bf16 slices each, six bf16 MFMA products, fp32 accumulation: fp32-equivalent, as close
@@ -217,6 +219,14 @@ class D3DP(nn.Module):
                 st.sqrt_alpha_next, st.c, st.sigma = float(alpha_next.sqrt()), float(c), float(sigma)
         return steps
 
+    def clips_per_launch(self, P, flip):
+        """How many clips one library call samples: max_rows_per_launch hypothesis passes of 27-frame clips, the same
+        number of token rows for longer clips (never more passes than max_rows_per_launch), at least one clip."""
+        rows = self.max_rows_per_launch
+        if self.frames > 27:
+            rows = rows * 27 // self.frames
+        return max(1, rows // ((2 if flip else 1) * P))
+
     def config_struct(self, flip):
         cfg = _lib.D3DPConfig()
         models = self.denoisers()
@@ -269,8 +279,7 @@ class D3DP(nn.Module):
         if B == 0:       # an empty batch: torch runs the reference on it and stacks T empty predictions (the draws above keep the
             #              generator where the reference's torch.randn calls of zero elements leave it)
             return torch.zeros((0, len(steps), P, self.frames, self.num_kps, 3), device=dev, dtype=torch.float32)
-        per_clip = (2 if flip else 1) * P
-        bc = max(1, self.max_rows_per_launch // per_clip)
+        bc = self.clips_per_launch(P, flip)
         if B > bc:                                      # cut along the (independent) clip axis
             outs = []
             for b0 in range(0, B, bc):

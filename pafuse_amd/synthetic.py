@@ -70,22 +70,22 @@ def sha256_of(sd: Dict[str, torch.Tensor]) -> bytes:
     return h.digest()
 
 
-def synthetic_inputs_2d(B: int, seed: int = 1234):
-    """inputs_2d ~ U(-1,1) [B,27,134,2] and its flipped copy (reference main_h3wb.py:268-270)."""
+def synthetic_inputs_2d(B: int, seed: int = 1234, frames: int = FRAMES):
+    """inputs_2d ~ U(-1,1) [B,frames,134,2] and its flipped copy (reference main_h3wb.py:268-270)."""
     g = torch.Generator().manual_seed(seed)
-    x = torch.rand(B, FRAMES, NUM_KPS, 2, generator=g) * 2 - 1
+    x = torch.rand(B, frames, NUM_KPS, 2, generator=g) * 2 - 1
     xf = x.clone()
     xf[:, :, :, 0] *= -1
     xf[:, :, SYN_JOINTS_LEFT + SYN_JOINTS_RIGHT, :] = xf[:, :, SYN_JOINTS_RIGHT + SYN_JOINTS_LEFT, :]
     return x, xf
 
 
-def synthetic_noises(B: int, P: int, n: int, seed: int = 1):
-    """n draws of [B,P,27,134,3]: the initial img and the randn_like of every DDIM update."""
+def synthetic_noises(B: int, P: int, n: int, seed: int = 1, frames: int = FRAMES):
+    """n draws of [B,P,frames,134,3]: the initial img and the randn_like of every DDIM update."""
     g = torch.Generator().manual_seed(seed)
-    return [torch.randn(B, P, FRAMES, NUM_KPS, 3, generator=g) for _ in range(n)]
+    return [torch.randn(B, P, frames, NUM_KPS, 3, generator=g) for _ in range(n)]
 
 
-def synthetic_target_3d(B: int, seed: int = 1235):
+def synthetic_target_3d(B: int, seed: int = 1235, frames: int = FRAMES):
     g = torch.Generator().manual_seed(seed)
-    return torch.randn(B, FRAMES, NUM_KPS, 3, generator=g) * 0.25
+    return torch.randn(B, frames, NUM_KPS, 3, generator=g) * 0.25
