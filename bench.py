@@ -12,11 +12,16 @@ sharded (weak scaling: P = 20*N, 20 per rank) and every step ends with the singl
 per-rank predictions.  Rank 0 prints ONE JSON line.
 
 `value` is the default product mode, 'bf16x3': every GEMM operand carries all 24 bits of the fp32 number it stands for (three
-bf16 slices, six bf16 MFMA products, fp32 accumulation).  The same run (N = 1) also times the opt-in `f16x2` mode and reports it
-as a named secondary object, never as `value`: `value_f16x2` (three fp16 MFMA products on 22 - 23-bit operands: faster, narrower
-than the reference's arithmetic).
+bf16 slices, six bf16 MFMA products, fp32 accumulation).
 
-Extra objects in the line:
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line.  Everything else the benchmark measures or checks runs only with `--full` (each leg can still be dropped from a --full run
+with its --no-* switch): the objects below, the all-gather timing of N > 1 (`allgather_ms`, `gather_copy_ms`) and the CPU
+baseline of --train.  With --full the same run (N = 1) also times the opt-in `f16x2` mode and reports it as a named secondary
+object, never as `value`: `value_f16x2` (three fp16 MFMA products on 22 - 23-bit operands: faster, narrower than the
+reference's arithmetic), and the training step as `train`.
+
+Extra objects in the line (`roofline_loop` in every line: it is the timed steps' own figure; the others with --full only):
   roofline      the dominant kernel family, the linear-layer launches of one flip-TTA denoiser pass - bf16x3: `sgemm2_kernel`
                 (qkv, fc1: the persistent strip kernel of round 6), `gemm_dma_kernel` (proj, fc2), or the shared grids of the single-stream schedule
                 with --streams 0; bf16x3_images: `xfqa_kernel` (qkv + attention), `xgemm_kernel`; f16x2: `hfqa_kernel`,
@@ -113,9 +118,13 @@ def main():
     ap.add_argument("--proposals", type=int, default=20, help="hypotheses per GPU")
     ap.add_argument("--timesteps", type=int, default=10)
     ap.add_argument("--batch", type=int, default=1, help="clips per forward")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the value_f16x2 leg of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the roofline replay, the value_f16x2 leg, the CPU baseline and "
+                         "parity, the train leg, the all-gather timing of N > 1 and the CPU baseline of --train (a plain run "
+                         "only times the steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline and parity legs")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline replay")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the value_f16x2 leg")
     ap.add_argument("--streams", type=int, default=2, help="aux HIP streams the three parts are spread over")
     ap.add_argument("--graph", action="store_true", help="replay the loop as one captured hipGraph")
     ap.add_argument("--fuse-qkv-attention", choices=("auto", "on", "off"), default="auto",
@@ -153,7 +162,7 @@ def main():
     ap.add_argument("--train-dtype", choices=("f32", "bf16x3"), default="bf16x3",
                     help="--train: matrix products of the plain GEMMs (qkv, fc1, dX): split precision (default) or fp32 MFMA")
     ap.add_argument("--no-train-leg", action="store_true",
-                    help="skip the `train` object of the inference line (a short B=37 training measurement, N = 1 only)")
+                    help="--full: skip the `train` object of the inference line (a short B=37 training measurement, N = 1 only)")
     ap.add_argument("--dump-grads", default=None, metavar="FILE",
                     help="--train rehearsal: ONE forward + backward (no optimiser step, DropPath off, per-sample draws a function of the "
                          "GLOBAL sample index), rank 0 saves {parameter name: gradient} (torch.save) - under DDP the gradients averaged "
@@ -316,7 +325,7 @@ def main():
     if args.dump_output and rank == 0:
         torch.save(out.cpu(), args.dump_output)
     dumped = dump_outputs(args.dump_outputs, {"poses": out}) if args.dump_outputs and rank == 0 else None
-    if world > 1:
+    if world > 1 and args.full:
         local = out[:, :, lo:hi].contiguous()
         gather_hypotheses(local, P_total)                      # warm-up
         fence()
@@ -376,7 +385,7 @@ def main():
         line["dumped_outputs"] = dumped
 
     # ---- dominant kernel family: the linear-layer GEMM launches of one flip-TTA denoiser pass, HIP-event timed ----
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         obj, launches, pass_ms = family_replay(model, args.dtype, lanes)
         n, ms = obj["launches"], obj["avg_launch_us"] * obj["launches"] / 1e3
         # HBM bytes per launch come from rocprofv3 PMC passes of this same command (rocprof cannot run inside the benchmark):
@@ -418,8 +427,8 @@ def main():
                                        "same peak; `frac` is this kernel family replayed alone")
         line["roofline"] = obj
 
-    # ---- the opt-in product modes, timed in the same run (N = 1, default invocation only): named objects, never `value` ----
-    if world == 1 and args.dtype == DEFAULT_DTYPE and not args.no_secondary:
+    # ---- the opt-in product modes, timed in the same run (N = 1, default mode only): named objects, never `value` ----
+    if args.full and world == 1 and args.dtype == DEFAULT_DTYPE and not args.no_secondary:
         del model
         for dtype in SECONDARY_DTYPES:
             m2, _ = make(dtype)
@@ -435,7 +444,7 @@ def main():
             del m2
 
     # ---- CPU baseline: the oracle on the host cores, on the metric's own configuration; parity of the HIP default on that very sample
-    if not args.no_cpu_baseline and rank == 0:
+    if args.full and not args.no_cpu_baseline and rank == 0:
         from oracle import d3dp_oracle as orc
         Pc, Tc = 20, T        # the metric's P and T (unscaled since round 6: ~ 50 s of host CPU at the best thread count)
         noises = gu.synthetic_noises(B=1, P=Pc, n=Tc, seed=9)
@@ -474,7 +483,7 @@ def main():
             line["parity"] = parity_object(orc, out, ref, gu, xc, Pc, Tc)
 
     # ---- BASELINE configs[4] beside the headline (N = 1): a short training measurement, so that the driver's record holds one
-    if world == 1 and not args.no_train_leg:
+    if args.full and world == 1 and not args.no_train_leg:
         line["train"] = train_leg(dev, args.streams)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -553,7 +562,7 @@ def parity_object(orc, out, ref, gu, x2d, P, T):
 
 def train_leg(dev, streams, B=37, steps=6):
     """The `train` object of the inference line: D3DP train step (fwd + bwd + AdamW) at B = 37 clips, one GPU, 'bf16x3' products
-    (the single-process default; `python bench.py --train` is the full training bench with its CPU baseline and DDP)."""
+    (the single-process default; `python bench.py --train` is the full training bench with DDP, and with --full its CPU baseline)."""
     import torch
     import __graft_entry__ as ge
     from pafuse_amd import synthetic as gu
@@ -667,7 +676,7 @@ def train_bench(args, rank, local_rank, world, dev):
     sec = elapsed / args.steps
     tflops = B * 3 * GFLOP_PER_HYP_PASS / 1e3 / sec                  # per GPU: forward + 2x backward
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         # the oracle's train step (torch CPU autograd over the functional restatement) on one clip
         from oracle import d3dp_oracle as orc
         model.train_draw_fn = None

@@ -456,10 +456,11 @@ def test_bench_two_rank_rehearsal_on_one_gpu(tmp_path):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     dump = str(tmp_path / "gathered.pt")
-    # the driver's own spelling: `python bench.py --gpus N ...` - bench.py starts its ranks itself (a child torch.distributed.run)
+    # the driver's own spelling: `python bench.py --gpus N ...` - bench.py starts its ranks itself (a child torch.distributed.run);
+    # --full for the all-gather timing
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
            "--single-device", "--steps", "1", "--warmup", "1", "--proposals", "2", "--timesteps", "2",
-           "--no-cpu-baseline", "--no-roofline", "--dump-output", dump]
+           "--full", "--no-cpu-baseline", "--no-roofline", "--dump-output", dump]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -478,3 +479,28 @@ def test_bench_two_rank_rehearsal_on_one_gpu(tmp_path):
     gathered = torch.load(dump)
     assert gathered.shape == single.shape == (1, 2, 4, 27, 134, 3)
     assert torch.equal(gathered, single.cpu())
+
+
+def test_bench_plain_run_does_only_the_headline(tmp_path):
+    """A plain `python bench.py` run sets up, warms up, times its steps, writes --dump-outputs and prints the line - nothing
+    else: none of the legs --full adds (roofline replay, value_f16x2, cpu_baseline, parity, train) runs or shows in the line."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    from tests.conftest import ROOT
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--proposals", "2",
+           "--timesteps", "2", "--dump-outputs", str(dump)]
+    res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    line = json.loads(lines[0])
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True and line["unit"] == "hypotheses/s"
+    assert line["steps"] == 1 and line["warmup"] == 1 and line["config"]["P_total"] == 2 and line["config"]["T"] == 2
+    assert not {"roofline", "value_f16x2", "cpu_baseline", "parity", "train"} & set(line), sorted(line)
+    assert line["dumped_outputs"] == {"poses": [1, 2, 2, 27, 134, 3]} and sorted(os.listdir(dump)) == ["poses.npy"]
+    poses = np.load(dump / "poses.npy")
+    assert poses.dtype == np.float32 and poses.shape == (1, 2, 2, 27, 134, 3) and np.isfinite(poses).all()

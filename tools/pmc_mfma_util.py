@@ -2,7 +2,7 @@
 """MFMA-pipe utilisation of the roofline leg's GEMM launches from a rocprofv3 PMC pass:
 
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d out -o m -- \
-        python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
+        python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
     python tools/pmc_mfma_util.py out/m_counter_collection.csv [N [SKIP]] > profiles/r02_pmc_mfma_util.json
 (N launches of the roofline replay, before the last SKIP GEMM launches = the by_layer legs)
 

@@ -2,8 +2,8 @@
 """HBM-side traffic per kernel family from two rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE cannot share a pass):
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT -o fetch -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT -o write -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT -o fetch -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT -o write -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
     python tools/pmc_traffic.py OUT/fetch_counter_collection.csv OUT/write_counter_collection.csv OUT/fetch_kernel_trace.csv \
         [--sha256 DIGEST] [--git GITSHA] [--dtype bf16x3] > profiles/r02_pmc_traffic.json
 
@@ -69,7 +69,7 @@ def main():
     g = families.get("gemm", {"launches": 0})
     doc = {
         "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes, each with --kernel-trace) over "
-                  "python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline (P=20, T=10); all dispatches of the process",
+                  "python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline (P=20, T=10); all dispatches of the process",
         "kernel_source_sha256": opts.get("--sha256"), "git_sha": opts.get("--git"), "dtype": opts.get("--dtype", "bf16x3"),
         "note": "FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 tallies 64 B per 128-B request on 16-B/lane streams); "
                 "WRITE_SIZE exact for dwordx4 stores; counters are fabric-side: Infinity-Cache hits are included",
