@@ -29,6 +29,10 @@ def main():
     ap.add_argument("--data", default=os.path.join(ROOT, "tests", "golden", "h3wb_synth", "train_h3wb.npz"))
     ap.add_argument("--checkpoint", default="")
     ap.add_argument("--config", default="", help="a reference config.yaml (optional)")
+    ap.add_argument("--gather", choices=("hypotheses", "partials"), default="hypotheses",
+                    help="what the ranks exchange before the aggregation: all hypotheses, or their partial reductions")
+    ap.add_argument("--hypothesis-chunk", type=int, default=None,
+                    help="with --gather partials: sample and reduce this many hypotheses at a time")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
     args = config.load(a.config or None, a.overrides)
@@ -59,7 +63,8 @@ def main():
     log = print if int(os.environ.get("RANK", "0")) == 0 else (lambda *x: None)
     log("Test time augmentation:", args.model.test_time_augmentation)
     h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
-                  batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2))
+                  batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),
+                  gather=a.gather, hypothesis_chunk=a.hypothesis_chunk)
     if world > 1:
         dist.destroy_process_group()
 

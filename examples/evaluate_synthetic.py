@@ -29,6 +29,10 @@ def main():
     ap.add_argument("--sequences", type=int, default=2)
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--checkpoint", default="", help="a reference pafuse_model.bin (optional)")
+    ap.add_argument("--gather", choices=("hypotheses", "partials"), default="hypotheses",
+                    help="what the ranks exchange before the aggregation: all hypotheses, or their partial reductions")
+    ap.add_argument("--hypothesis-chunk", type=int, default=None,
+                    help="with --gather partials: sample and reduce this many hypotheses at a time")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -50,7 +54,8 @@ def main():
     for _ in range(a.sequences):
         seq_2d = torch.rand(a.frames, 134, 2, generator=g) * 2 - 1
         seq_3d = torch.randn(a.frames, 134, 3, generator=g) * 0.25 + torch.tensor([0.0, 0.0, 4.0])
-        sums, cnt = harness.evaluate_sequence(model, ds, seq_2d, seq_3d, cam, gu.SYN_JOINTS_LEFT, gu.SYN_JOINTS_RIGHT)
+        sums, cnt = harness.evaluate_sequence(model, ds, seq_2d, seq_3d, cam, gu.SYN_JOINTS_LEFT, gu.SYN_JOINTS_RIGHT,
+                                              gather=a.gather, hypothesis_chunk=a.hypothesis_chunk)
         total = sums if total is None else {k: total[k] + v for k, v in sums.items()}
         n += cnt
     torch.cuda.synchronize()

@@ -25,6 +25,7 @@
  *   pafuse_ddim_finalize     the output stage of a DDIM step: part concat + un-flip + TTA mean + clamp
  *                            (common/diffusionpose.py:165-171,211-218), epsilon in fp64 (:157-161,222-223), update (:302-312)
  *   pafuse_hypothesis_errors the per-joint part of evaluate()'s aggregation, main_h3wb.py:327-362
+ *   pafuse_hypothesis_partials / _combine  the same from per-shard partial reductions (sharded or chunked P)
  *   pafuse_procrustes_errors the Protocol #2 part of it (ft2d.p2), main_h3wb.py:381-395, common/loss.py:251-458
  *   pafuse_mixste2_train_*   MixSTE2.forward (is_train=True) + autograd backward, common/mixste.py:215-225,260-298
  *   pafuse_d3dp_qsample      D3DP.prepare_diffusion_concat / q_sample, common/diffusionpose.py:319-326,358-374
@@ -482,6 +483,44 @@ int pafuse_hypothesis_errors(const float *pred, const float *gt, const float *x2
                              const int32_t *conn, const int32_t *pbroot, int32_t B, int32_t T, int32_t P, int32_t F,
                              int32_t J, float *e3, float *epb, float *jbest, float *pagg, float *jagg, float *paggpb,
                              void *stream);
+
+/* The same aggregation from per-shard partial reductions (Protocol #1 only): a shard holds hypotheses
+ * [h0, h0 + P_r) of the P - the hypotheses of one rank, or one chunk of them on a single device - and is reduced to a
+ * state whose size does not depend on P, so that evaluation never holds (or gathers) the whole [B,T,P,F,J,3] tensor.
+ * pred [B,T,P_r,F,J,3] is the LOCAL tensor; the other operands are those of pafuse_hypothesis_errors, plus
+ * part int32 [J], the part number 0 .. num_parts-1 of every joint.
+ * State, one flat 8-byte aligned buffer of pafuse_hypothesis_partials_bytes bytes, n = B*T*F*J:
+ *   double sum[n][3]    sum over the local h, in h order, of the whole-body joint (the P-Agg mean pose; a part root's sum
+ *                       is the sum of that joint of the same frame)
+ *   float  jbest[n]     minimum over the local h of e3                                   (+inf when P_r == 0)
+ *   float  e2[n], sel3[n]; int32 idx[n]   the J-Agg candidate: smallest reprojection error, its e3, its GLOBAL
+ *                       hypothesis index h0 + h; first minimum wins; (+inf, 0, -1) where no e2 of the shard is finite
+ *   double hsum[P_r][T][1 + num_parts]    per local hypothesis and step: sum over (b, f, j) of e3, then of epb over the
+ *                       joints of each part (their sum over the parts is the whole-pose epb sum), fp64, fixed order
+ * Everything that depends on P_r is at the end: a ragged shard is a prefix of a buffer sized for the largest one, so W
+ * ranks exchange their states with one all-gather of equal-sized buffers.  Two kernels, no atomics, bit-reproducible;
+ * the per-hypothesis sums are independent of how the P hypotheses are cut into shards.  workspace:
+ * pafuse_hypothesis_partials_workspace_bytes bytes of scratch, 8-byte aligned (the workgroups' shares of hsum).
+ * B == 0 or P_r == 0: no kernel runs, the state is the neutral one.  Refused: a null operand, negative sizes or h0
+ * (PAFUSE_E_ARG), num_parts outside 1 .. PAFUSE_MAX_PARTS (PAFUSE_E_SHAPE), a small workspace (PAFUSE_E_WORKSPACE). */
+size_t pafuse_hypothesis_partials_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t num_parts);
+size_t pafuse_hypothesis_partials_workspace_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J,
+                                                  int32_t num_parts);
+int pafuse_hypothesis_partials(const float *pred, const float *gt, const float *x2d, const float *traj, const float *cam,
+                               const int32_t *conn, const int32_t *pbroot, const int32_t *part, int32_t num_parts,
+                               int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t h0, void *state,
+                               size_t state_bytes, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Combines W such states, `stride_bytes` apart (rank-major, as an all-gather leaves them) and in ascending-h0 order.
+ * Only the first 40*n bytes of each are read (the per-hypothesis tail is not combined: concatenate it).  Writes
+ *   merged (may be NULL): the 40*n-byte head of the state of the union - sums added in shard order, minimum of the
+ *           minima, the candidate with the smallest e2 and, among equal ones, the lowest global index.  It may be
+ *           the first operand itself (a running state accumulating chunk after chunk), but then without the maps;
+ *   jbest, pagg, jagg, paggpb [B,T,F,J] (all four or none): what pafuse_hypothesis_errors writes.  jbest and jagg are
+ *           bit-equal to it; pagg / paggpb use the fp64 sums divided by P_total (that kernel sums in fp32). */
+int pafuse_hypothesis_combine(const void *states, int32_t W, size_t stride_bytes, const float *gt, const int32_t *conn,
+                              const int32_t *pbroot, int32_t B, int32_t T, int32_t F, int32_t J, int32_t P_total,
+                              void *merged, float *jbest, float *pagg, float *jagg, float *paggpb, void *stream);
 
 /* Protocol #2 (P-MPJPE) on the same operands - common/loss.py:251-458 as main_h3wb.py:381-395 calls it: every
  * whole-body hypothesis pose (and, per (b,t,f), the mean over h of them) aligned to its whole-body target by the

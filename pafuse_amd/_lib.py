@@ -134,6 +134,12 @@ SIGNATURES = {
     "pafuse_ddim_finalize": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32] + [C.c_void_p] * 6 +
                              [C.c_int32] * 7 + [C.c_double, C.POINTER(DDIMStep), C.c_void_p]),
     "pafuse_hypothesis_errors": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p] * 7),
+    "pafuse_hypothesis_partials_bytes": (C.c_size_t, [C.c_int32] * 6),
+    "pafuse_hypothesis_partials_workspace_bytes": (C.c_size_t, [C.c_int32] * 6),
+    "pafuse_hypothesis_partials": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                                                  C.c_void_p]),
+    "pafuse_hypothesis_combine": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t] + [C.c_void_p] * 3 + [C.c_int32] * 5 +
+                                  [C.c_void_p] * 6),
     "pafuse_procrustes_errors": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p] * 6),
     "pafuse_d3dp_replay_gemms": (C.c_int, [C.POINTER(D3DPConfig), C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.POINTER(C.c_double)]),

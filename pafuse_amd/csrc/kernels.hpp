@@ -2564,6 +2564,248 @@ __global__ void __launch_bounds__(256) metrics_kernel(const MetricsParams p) {
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// The same aggregation from per-shard partial reductions (evaluation-sized batches).  A shard
+// holds hypotheses [h0, h0 + P_r) of the P - one rank's, or one chunk on a single device - and reduces them to a
+// state whose size does not grow with P: per (b, t, f, j) the J-Best minimum, the J-Agg candidate (smallest e2, its
+// e3, its GLOBAL hypothesis index) and the fp64 sum over h of the whole-body joint (the part root's sum is the sum
+// of another joint of the same frame: gathered at combine time); per local (h, t) the fp64 sums over (b, f, j) of
+// e3 and of epb per part.  combine_kernel merges W such states in ascending-h0 order into one state and / or the
+// four [B,T,F,J] maps metrics_kernel writes.  Per-hypothesis expressions are those of metrics_kernel, verbatim.
+//
+// State, one flat buffer (n = B*T*F*J, nv = 1 + num_parts); everything that depends on P_r is at the end, so a
+// ragged shard padded to the largest one is a prefix of the padded buffer:
+//   double sum[n][3] | float jbest[n] | float e2[n] | float sel3[n] | int32 idx[n] | double hsum[P_r][T][nv]
+// hsum slots: 0 = sum of e3, 1 + i = sum of epb over the joints of part i.
+//
+// partials_kernel: one workgroup per (b, t, 256 consecutive (f, j)); every thread walks the local h once.  The
+// per-hypothesis sums never touch memory as [B,T,P,F,J]: the errors of PART_HC hypotheses are parked in LDS
+// (row stride PART_LD: rows of neighbouring h fall into different halves of the 32 banks), then 16 lanes per
+// hypothesis add them up in fp64 - lane s takes elements s, s + 16, ... in order, a butterfly over the 16 lanes
+// (a + b == b + a: the same bits in each) finishes the workgroup's share, written to [B,T,nblk,P_r,nv] scratch.
+// partials_hsum_kernel adds those shares over (b, blk) in a fixed order.  No atomics anywhere.
+// ----------------------------------------------------------------------------------------------------------------
+constexpr int PART_HC = 8;            // hypotheses per LDS round
+constexpr int PART_LD = 256 + 16;     // LDS row stride in floats
+constexpr int PART_NV = 1 + 4;        // most per-hypothesis sums (PAFUSE_MAX_PARTS parts)
+
+struct PartialsParams {
+    const float* pred;  // [B,T,P_r,F,J,3] this shard's part-centred predictions
+    const float* gt;    // [B,F,J,3]
+    const float* x2d;   // [B,F,J,2]
+    const float* traj;  // [B,F,3]
+    const float* cam;   // [9]
+    const int32_t *conn, *pbroot, *part;  // [J]: connection joint, part root, part number (0 .. num_parts-1)
+    double* sum;        // state (see above)
+    float *jbest, *e2, *sel3;
+    int32_t* idx;
+    double* share;      // scratch [B,T,nblk,P_r,nv]
+    int B, T, P, F, J, h0, nv, nblk;
+};
+
+__global__ void __launch_bounds__(256, 8) partials_kernel(const PartialsParams p) {
+    __shared__ float s_e3[PART_HC * PART_LD], s_epb[PART_HC * PART_LD];
+    __shared__ int s_part[256];
+    const int tid = threadIdx.x;
+    const int blk = (int)(blockIdx.x % p.nblk);
+    const int t = (int)((blockIdx.x / p.nblk) % p.T);
+    const int b = (int)(blockIdx.x / ((unsigned)p.nblk * p.T));
+    const int FJ = p.F * p.J;
+    const int fj = blk * 256 + tid;
+    const bool valid = fj < FJ;
+    const int f = valid ? fj / p.J : 0, j = valid ? fj % p.J : 0;
+    const int jr = p.pbroot[j];
+    s_part[tid] = valid ? p.part[j] : -1;
+    const float* gpose = p.gt + ((int64_t)b * p.F + f) * p.J * 3;
+    float g[3], gr[3];
+    wb_joint(gpose, p.conn, j, g);
+    wb_joint(gpose, p.conn, jr, gr);
+    const float gc[3] = {g[0] - gr[0], g[1] - gr[1], g[2] - gr[2]};
+    const float* tr = p.traj + ((int64_t)b * p.F + f) * 3;
+    const float* x2 = p.x2d + (((int64_t)b * p.F + f) * p.J + j) * 2;
+    const float fx = p.cam[0], fy = p.cam[1], cx = p.cam[2], cy = p.cam[3];
+    const float k1 = p.cam[4], k2 = p.cam[5], k3 = p.cam[6], p1 = p.cam[7], p2 = p.cam[8];
+    float best3 = INFINITY, best2 = INFINITY, sel3 = 0.f;
+    int32_t hsel = -1;
+    double sm[3] = {0.0, 0.0, 0.0};
+    // second phase of a round: 16 lanes per parked hypothesis (threads 0 .. 16*PART_HC-1)
+    const int rh = tid >> 4, rs = tid & 15;
+    double* share = p.share + (((int64_t)b * p.T + t) * p.nblk + blk) * p.P * p.nv;
+    for (int hb = 0; hb < p.P; hb += PART_HC) {
+        const int hn = min(PART_HC, p.P - hb);
+        for (int hh = 0; hh < hn; ++hh) {
+            const int h = hb + hh;
+            float e3 = 0.f, epb = 0.f;
+            if (valid) {
+                const float* pose = p.pred + ((((int64_t)b * p.T + t) * p.P + h) * p.F + f) * p.J * 3;
+                float w[3], wr[3];
+                wb_joint(pose, p.conn, j, w);
+                wb_joint(pose, p.conn, jr, wr);
+                const float d0 = w[0] - g[0], d1 = w[1] - g[1], d2 = w[2] - g[2];
+                e3 = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+                const float c0 = (w[0] - wr[0]) - gc[0], c1 = (w[1] - wr[1]) - gc[1], c2 = (w[2] - wr[2]) - gc[2];
+                epb = sqrtf(c0 * c0 + c1 * c1 + c2 * c2);
+                best3 = fminf(best3, e3);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) sm[k] += (double)w[k];
+                // 2-D reprojection of the absolute pose (common/camera.py:30-60)
+                const float X = w[0] + tr[0], Y = w[1] + tr[1], Z = w[2] + tr[2];
+                const float xx = fminf(fmaxf(X / Z, -1.f), 1.f), yy = fminf(fmaxf(Y / Z, -1.f), 1.f);
+                const float r2 = xx * xx + yy * yy;
+                const float radial = 1.f + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2));
+                const float tan = p1 * xx + p2 * yy;
+                const float u = fx * (xx * (radial + tan) + p1 * r2) + cx, v = fy * (yy * (radial + tan) + p2 * r2) + cy;
+                const float q0 = u - x2[0], q1 = v - x2[1];
+                const float e2 = sqrtf(q0 * q0 + q1 * q1);
+                if (e2 < best2) best2 = e2, sel3 = e3, hsel = p.h0 + h;  // first minimum wins inside the shard
+            }
+            s_e3[hh * PART_LD + tid] = e3;
+            s_epb[hh * PART_LD + tid] = epb;
+        }
+        __syncthreads();
+        if (rh < hn) {   // uniform per 16 lanes; the butterfly below stays inside them
+            double a3 = 0.0, ap[PART_NV - 1] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+            for (int i = 0; i < 16; ++i) {
+                const int el = rs + 16 * i;
+                const int part = s_part[el];
+                const double v3 = (double)s_e3[rh * PART_LD + el], vp = (double)s_epb[rh * PART_LD + el];
+                a3 += v3;      // an element past F*J parked 0
+#pragma unroll
+                for (int q = 0; q < PART_NV - 1; ++q) ap[q] += part == q ? vp : 0.0;
+            }
+#pragma unroll
+            for (int m = 8; m >= 1; m >>= 1) {
+                a3 += __shfl_xor(a3, m, 64);
+#pragma unroll
+                for (int q = 0; q < PART_NV - 1; ++q) ap[q] += __shfl_xor(ap[q], m, 64);
+            }
+            if (rs == 0) {
+                double* o = share + (int64_t)(hb + rh) * p.nv;
+                o[0] = a3;
+#pragma unroll
+                for (int q = 0; q < PART_NV - 1; ++q)
+                    if (1 + q < p.nv) o[1 + q] = ap[q];
+            }
+        }
+        __syncthreads();
+    }
+    if (valid) {
+        const int64_t e = ((int64_t)b * p.T + t) * FJ + fj;
+        p.sum[e * 3 + 0] = sm[0], p.sum[e * 3 + 1] = sm[1], p.sum[e * 3 + 2] = sm[2];
+        p.jbest[e] = best3;
+        p.e2[e] = best2;
+        p.sel3[e] = sel3;
+        p.idx[e] = hsel;
+    }
+}
+
+struct PartialsHsumParams {
+    const double* share;  // [B,T,nblk,P_r,nv]
+    double* hsum;         // [P_r,T,nv]
+    int B, T, P, nv, nblk;
+};
+
+// one workgroup of four waves per (h, t): thread i adds the shares of (b, blk) pairs i, i + 256, ... in order, a butterfly
+// finishes each wave and thread 0 adds the four waves in order
+__global__ void __launch_bounds__(256) partials_hsum_kernel(const PartialsHsumParams p) {
+    __shared__ double s_w[4][PART_NV];
+    const int tid = threadIdx.x;
+    const int t = (int)(blockIdx.x % p.T), h = (int)(blockIdx.x / p.T);
+    const int n = p.B * p.nblk;
+    double a[PART_NV] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = tid; i < n; i += 256) {
+        const int b = i / p.nblk, blk = i % p.nblk;
+        const double* s = p.share + ((((int64_t)b * p.T + t) * p.nblk + blk) * p.P + h) * p.nv;
+#pragma unroll
+        for (int q = 0; q < PART_NV; ++q)
+            if (q < p.nv) a[q] += s[q];
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+        for (int q = 0; q < PART_NV; ++q) a[q] += __shfl_xor(a[q], m, 64);
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < PART_NV; ++q) s_w[tid >> 6][q] = a[q];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double* o = p.hsum + ((int64_t)h * p.T + t) * p.nv;
+#pragma unroll
+        for (int q = 0; q < PART_NV; ++q)
+            if (q < p.nv) o[q] = ((s_w[0][q] + s_w[1][q]) + s_w[2][q]) + s_w[3][q];
+    }
+}
+
+struct CombineParams {
+    const char* states;   // W states, `stride` bytes apart, in ascending-h0 order
+    int64_t stride;
+    int W;
+    const float* gt;      // [B,F,J,3]
+    const int32_t *conn, *pbroot;
+    double* m_sum;        // merged state (null: not wanted)
+    float *m_jbest, *m_e2, *m_sel3;
+    int32_t* m_idx;
+    float *jbest, *pagg, *jagg, *paggpb;   // [B,T,F,J] (null: not wanted)
+    int B, T, F, J, P;    // P: the TOTAL hypothesis count the P-Agg mean divides by
+};
+
+__global__ void __launch_bounds__(256) combine_kernel(const CombineParams p) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = (int64_t)p.B * p.T * p.F * p.J;
+    if (e >= n) return;
+    const int j = (int)(e % p.J);
+    const int f = (int)((e / p.J) % p.F);
+    const int b = (int)(e / ((int64_t)p.J * p.F * p.T));
+    const int jr = p.pbroot[j];
+    const int64_t er = e - j + jr;          // the part root of the same (b, t, f)
+    float best3 = INFINITY, best2 = INFINITY, sel3 = 0.f;
+    int32_t hsel = -1;
+    double s[3] = {0.0, 0.0, 0.0}, sr[3] = {0.0, 0.0, 0.0};
+    for (int w = 0; w < p.W; ++w) {
+        const char* st = p.states + (int64_t)w * p.stride;
+        const double* sum = (const double*)st;
+        const float* jb = (const float*)(st + n * 24);
+        const float* e2 = jb + n;
+        const float* s3 = e2 + n;
+        const int32_t* ix = (const int32_t*)(s3 + n);
+        best3 = fminf(best3, jb[e]);
+        const int32_t hw = ix[e];
+        // the overall first minimum: the smallest e2, the lowest global index among equal ones
+        if (hw >= 0 && (hsel < 0 || e2[e] < best2 || (e2[e] == best2 && hw < hsel))) best2 = e2[e], hsel = hw, sel3 = s3[e];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s[k] += sum[e * 3 + k];
+        if (p.jbest) {   // (not read when only merging: a merge may write its result over the first state)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sr[k] += sum[er * 3 + k];
+        }
+    }
+    if (p.jbest) {
+        const float* gpose = p.gt + ((int64_t)b * p.F + f) * p.J * 3;
+        float g[3], gr[3];
+        wb_joint(gpose, p.conn, j, g);
+        wb_joint(gpose, p.conn, jr, gr);
+        const float gc[3] = {g[0] - gr[0], g[1] - gr[1], g[2] - gr[2]};
+        const double P = (double)p.P;
+        const float m0 = (float)(s[0] / P) - g[0], m1 = (float)(s[1] / P) - g[1], m2 = (float)(s[2] / P) - g[2];
+        const float n0 = (float)((s[0] - sr[0]) / P) - gc[0], n1 = (float)((s[1] - sr[1]) / P) - gc[1],
+                    n2 = (float)((s[2] - sr[2]) / P) - gc[2];
+        p.jbest[e] = best3;
+        p.jagg[e] = sel3;
+        p.pagg[e] = sqrtf(m0 * m0 + m1 * m1 + m2 * m2);
+        p.paggpb[e] = sqrtf(n0 * n0 + n1 * n1 + n2 * n2);
+    }
+    if (p.m_sum) {
+        p.m_sum[e * 3 + 0] = s[0], p.m_sum[e * 3 + 1] = s[1], p.m_sum[e * 3 + 2] = s[2];
+        p.m_jbest[e] = best3;
+        p.m_e2[e] = best2;
+        p.m_sel3[e] = sel3;
+        p.m_idx[e] = hsel;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // Protocol #2 (P-MPJPE) behind the all-gather: common/loss.py:251-458 as main_h3wb.py:381-395 calls it on the
 // whole-body poses.  Every hypothesis pose Y is aligned to its target X by the similarity transform of the
 // reference (centre both, H = (X0/|X0|)^T (Y0/|Y0|), R = V U^T with the reflection fix, a = tr(S') |X0| / |Y0|) and

@@ -1751,6 +1751,104 @@ int pafuse_hypothesis_errors(const float* pred, const float* gt, const float* x2
     return check_launch("metrics_kernel");
 }
 
+// state of pafuse_hypothesis_partials: double sum[n][3] | float jbest[n], e2[n], sel3[n] | int32 idx[n] | double hsum[P_r][T][1+num_parts]
+static bool partials_sizes_ok(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t num_parts) {
+    return B >= 0 && T > 0 && P_r >= 0 && F > 0 && J > 0 && num_parts >= 1 && num_parts <= PAFUSE_MAX_PARTS;
+}
+static int partials_nblk(int32_t F, int32_t J) { return (int)(((int64_t)F * J + 255) / 256); }
+
+size_t pafuse_hypothesis_partials_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t num_parts) {
+    if (!partials_sizes_ok(B, T, P_r, F, J, num_parts)) return 0;
+    return (size_t)B * T * F * J * 40 + (size_t)P_r * T * (1 + num_parts) * 8;
+}
+
+size_t pafuse_hypothesis_partials_workspace_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t num_parts) {
+    if (!partials_sizes_ok(B, T, P_r, F, J, num_parts)) return 0;
+    return (size_t)B * T * partials_nblk(F, J) * P_r * (1 + num_parts) * 8;
+}
+
+int pafuse_hypothesis_partials(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,
+                               const int32_t* conn, const int32_t* pbroot, const int32_t* part, int32_t num_parts, int32_t B,
+                               int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t h0, void* state, size_t state_bytes,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (num_parts < 1 || num_parts > PAFUSE_MAX_PARTS) return fail(PAFUSE_E_SHAPE, "hypothesis_partials: num_parts %d", num_parts);
+    if (B < 0 || T <= 0 || P_r < 0 || F <= 0 || J <= 0 || h0 < 0) return fail(PAFUSE_E_ARG, "hypothesis_partials: bad size");
+    const size_t need = pafuse_hypothesis_partials_bytes(B, T, P_r, F, J, num_parts);
+    if (need && (!state || state_bytes < need)) return fail(PAFUSE_E_ARG, "hypothesis_partials: the state needs %zu bytes", need);
+    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "hypothesis_partials: the state must be 8-byte aligned");
+    const int64_t n = (int64_t)B * T * F * J;
+    char* st = (char*)state;
+    double* sum = (double*)st;
+    float* jbest = (float*)(st + n * 24);
+    double* hsum = (double*)(st + n * 40);
+    hipStream_t s = (hipStream_t)stream;
+    if (B == 0 || P_r == 0) {   // the neutral state: +inf minima, no candidate, zero sums; no kernel runs
+        hipError_t e = hipSuccess;
+        if (n) {
+            e = hipMemsetAsync(sum, 0, (size_t)n * 24, s);
+            if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)jbest, 0x7f800000, (size_t)n * 2, s);
+            if (e == hipSuccess) e = hipMemsetAsync(jbest + 2 * n, 0, (size_t)n * 4, s);
+            if (e == hipSuccess) e = hipMemsetAsync(jbest + 3 * n, 0xff, (size_t)n * 4, s);
+        }
+        if (e == hipSuccess && P_r) e = hipMemsetAsync(hsum, 0, (size_t)P_r * T * (1 + num_parts) * 8, s);
+        if (e != hipSuccess) return fail(PAFUSE_E_HIP, "hypothesis_partials: %s", hipGetErrorString(e));
+        return PAFUSE_OK;
+    }
+    if (!pred || !gt || !x2d || !traj || !cam || !conn || !pbroot || !part)
+        return fail(PAFUSE_E_ARG, "hypothesis_partials: null pointer");
+    const size_t wneed = pafuse_hypothesis_partials_workspace_bytes(B, T, P_r, F, J, num_parts);
+    if (!workspace || workspace_bytes < wneed || (uintptr_t)workspace % 8)
+        return fail(PAFUSE_E_WORKSPACE, "hypothesis_partials: the workspace needs %zu bytes, 8-byte aligned", wneed);
+    PartialsParams m{};
+    m.pred = pred, m.gt = gt, m.x2d = x2d, m.traj = traj, m.cam = cam, m.conn = conn, m.pbroot = pbroot, m.part = part;
+    m.sum = sum, m.jbest = jbest, m.e2 = jbest + n, m.sel3 = jbest + 2 * n, m.idx = (int32_t*)(jbest + 3 * n);
+    m.share = (double*)workspace;
+    m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0, m.nv = 1 + num_parts, m.nblk = partials_nblk(F, J);
+    const int64_t blocks = (int64_t)B * T * m.nblk;
+    if (blocks > 0x7fffffff || (int64_t)P_r * T > 0x7fffffff || (int64_t)B * m.nblk > 0x7fffffff)
+        return fail(PAFUSE_E_ARG, "hypothesis_partials: grid out of range");
+    hipLaunchKernelGGL(partials_kernel, dim3((unsigned)blocks), dim3(256), 0, s, m);
+    int rc = check_launch("partials_kernel");
+    if (rc) return rc;
+    PartialsHsumParams r{};
+    r.share = m.share, r.hsum = hsum, r.B = B, r.T = T, r.P = P_r, r.nv = m.nv, r.nblk = m.nblk;
+    hipLaunchKernelGGL(partials_hsum_kernel, dim3((unsigned)((int64_t)P_r * T)), dim3(256), 0, s, r);
+    return check_launch("partials_hsum_kernel");
+}
+
+int pafuse_hypothesis_combine(const void* states, int32_t W, size_t stride_bytes, const float* gt, const int32_t* conn,
+                              const int32_t* pbroot, int32_t B, int32_t T, int32_t F, int32_t J, int32_t P_total, void* merged,
+                              float* jbest, float* pagg, float* jagg, float* paggpb, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (B < 0 || T <= 0 || F <= 0 || J <= 0 || W < 1) return fail(PAFUSE_E_ARG, "hypothesis_combine: bad size");
+    const bool maps = jbest || pagg || jagg || paggpb;
+    if (maps && !(jbest && pagg && jagg && paggpb)) return fail(PAFUSE_E_ARG, "hypothesis_combine: the four maps come together");
+    if (!maps && !merged) return fail(PAFUSE_E_ARG, "hypothesis_combine: nothing to write");
+    if (maps && P_total < 1) return fail(PAFUSE_E_ARG, "hypothesis_combine: P_total %d", P_total);
+    const int64_t n = (int64_t)B * T * F * J;
+    if (n == 0) return PAFUSE_OK;
+    if (!states || !gt || !conn || !pbroot) return fail(PAFUSE_E_ARG, "hypothesis_combine: null pointer");
+    if (stride_bytes < (size_t)n * 40 || stride_bytes % 8 || (uintptr_t)states % 8 || (uintptr_t)merged % 8)
+        return fail(PAFUSE_E_ARG, "hypothesis_combine: states are %lld bytes or more apart, 8-byte aligned", (long long)(n * 40));
+    const char* lo = (const char*)states;
+    const char* hi = lo + (size_t)W * stride_bytes;
+    if (maps && merged && (const char*)merged < hi && (const char*)merged + n * 40 > lo)
+        return fail(PAFUSE_E_ARG, "hypothesis_combine: a merge over its own operands cannot also write the maps");
+    if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "hypothesis_combine: grid out of range");
+    CombineParams c{};
+    c.states = lo, c.stride = (int64_t)stride_bytes, c.W = W, c.gt = gt, c.conn = conn, c.pbroot = pbroot;
+    if (merged) {
+        char* st = (char*)merged;
+        c.m_sum = (double*)st, c.m_jbest = (float*)(st + n * 24), c.m_e2 = c.m_jbest + n, c.m_sel3 = c.m_jbest + 2 * n;
+        c.m_idx = (int32_t*)(c.m_jbest + 3 * n);
+    }
+    c.jbest = jbest, c.pagg = pagg, c.jagg = jagg, c.paggpb = paggpb;
+    c.B = B, c.T = T, c.F = F, c.J = J, c.P = P_total;
+    hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c);
+    return check_launch("combine_kernel");
+}
+
 int pafuse_procrustes_errors(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,
                              const int32_t* conn, int32_t B, int32_t T, int32_t P, int32_t F, int32_t J, float* jbest,
                              double* pbest_sums, float* pagg, float* jagg, int32_t* pick, void* stream) {

@@ -6,8 +6,14 @@ reprojection, per-joint J-Best / P-Agg / J-Agg and the part-re-centred variants)
 (b, f, j) and the P-Best argmin are a handful of reductions over small tensors.  With ``p2=True`` a second kernel
 (``procrustes_errors``) adds Protocol #2, the same four numbers after the reference's similarity alignment
 (main_h3wb.py:381-395, common/loss.py:251-458).
+
+``evaluate_accumulators_sharded`` gives the same 14 vectors without ever holding all P hypotheses: every shard of the
+hypothesis axis (a rank's, or a chunk on one device) is reduced to a small state (``ops.hypothesis_partials``), states
+are merged (``ops.combine_partials``), and ranks exchange states - not hypotheses - in one all-gather.  Protocol #1
+only: Protocol #2 needs the full tensor and keeps the gather of ``pafuse_amd.parallel.gather_hypotheses``.
 """
 import torch
+import torch.distributed as dist
 
 from . import _lib
 
@@ -23,34 +29,39 @@ def _tables(dataset, num_kps, device):
     return conn.to(device), pbroot.to(device)
 
 
+def _operands(pred_parts, gt_parts, inputs_2d, traj, cam, dataset, who, name="pred_parts", axis="P"):
+    """The argument checks and conversions every evaluation entry point shares: -> contiguous fp32 pred, gt, x2d,
+    traj [B,F,3], cam [9] on the device of the predictions, and the conn / pbroot index tables."""
+    if not pred_parts.is_cuda:
+        raise _lib.PafuseError(f"{who} runs on the HIP device only (no CPU fallback)")
+    dev = pred_parts.device
+    if pred_parts.dim() != 6 or pred_parts.shape[-1] != 3:
+        raise ValueError(f"{name} must be [B,T,{axis},F,J,3], got {tuple(pred_parts.shape)}")
+    B, T, P, F, J, _ = pred_parts.shape
+    # the kernels index every operand by (B, F, J): check before launching
+    if (tuple(gt_parts.shape) != (B, F, J, 3) or tuple(inputs_2d.shape) != (B, F, J, 2) or traj.numel() != B * F * 3
+            or cam.numel() < 9):
+        raise ValueError(f"{who}: operands do not match pred {tuple(pred_parts.shape)}: gt "
+                         f"{tuple(gt_parts.shape)}, 2d {tuple(inputs_2d.shape)}, traj {tuple(traj.shape)}, cam {tuple(cam.shape)}")
+    if any(t.device != dev for t in (gt_parts, inputs_2d, traj)):
+        raise ValueError(f"{who}: all tensors must live on the device of {name}")
+    covered = sorted(j for idx in dataset.parts_joint_indices.values() for j in idx)
+    if covered != list(range(J)):
+        raise ValueError("dataset.parts_joint_indices must cover every joint exactly once")
+    conn, pbroot = _tables(dataset, J, dev)
+    return (pred_parts.contiguous().float(), gt_parts.contiguous().float(), inputs_2d.contiguous().float(),
+            traj.reshape(B, F, 3).contiguous().float(), cam.reshape(-1)[:9].contiguous().float().to(dev), conn, pbroot)
+
+
 def evaluate_accumulators(pred_parts, gt_parts, inputs_2d, traj, cam, dataset, p2=False):
     """pred_parts [B,T,P,F,J,3], gt_parts [B,F,J,3] (part-centred, metres), inputs_2d [B,F,J,2], traj [B,F,1,3],
     cam [9] or [1,9] -> dict of the 14 per-step vectors [T] the reference accumulates per batch (same names as
     oracle.d3dp_oracle.evaluate_accumulators; multiply by 1000 for mm).  ``p2=True`` (the reference's ``ft2d.p2``)
     adds the four Protocol #2 vectors p2_j_best, p2_p_best, p2_p_agg, p2_j_agg; the 14 others are unchanged."""
     lib = _lib.load()
-    if not pred_parts.is_cuda:
-        raise _lib.PafuseError("evaluate_accumulators runs on the HIP device only (no CPU fallback)")
-    dev = pred_parts.device
-    if pred_parts.dim() != 6 or pred_parts.shape[-1] != 3:
-        raise ValueError(f"pred_parts must be [B,T,P,F,J,3], got {tuple(pred_parts.shape)}")
-    B, T, P, F, J, _ = pred_parts.shape
-    # the kernel indexes every operand by (B, F, J): check before launching
-    if (tuple(gt_parts.shape) != (B, F, J, 3) or tuple(inputs_2d.shape) != (B, F, J, 2) or traj.numel() != B * F * 3
-            or cam.numel() < 9):
-        raise ValueError(f"evaluate_accumulators: operands do not match pred {tuple(pred_parts.shape)}: gt "
-                         f"{tuple(gt_parts.shape)}, 2d {tuple(inputs_2d.shape)}, traj {tuple(traj.shape)}, cam {tuple(cam.shape)}")
-    if any(t.device != dev for t in (gt_parts, inputs_2d, traj)):
-        raise ValueError("evaluate_accumulators: all tensors must live on the device of pred_parts")
-    covered = sorted(j for idx in dataset.parts_joint_indices.values() for j in idx)
-    if covered != list(range(J)):
-        raise ValueError("dataset.parts_joint_indices must cover every joint exactly once")
-    pred = pred_parts.contiguous().float()
-    gt = gt_parts.contiguous().float()
-    x2d = inputs_2d.contiguous().float()
-    tr = traj.reshape(B, F, 3).contiguous().float()
-    cm = cam.reshape(-1)[:9].contiguous().float().to(dev)
-    conn, pbroot = _tables(dataset, J, dev)
+    pred, gt, x2d, tr, cm, conn, pbroot = _operands(pred_parts, gt_parts, inputs_2d, traj, cam, dataset, "evaluate_accumulators")
+    dev = pred.device
+    B, T, P, F, J, _ = pred.shape
     e3 = torch.empty(B, T, P, F, J, device=dev)
     epb = torch.empty_like(e3)
     jbest, pagg, jagg, paggpb = (torch.empty(B, T, F, J, device=dev) for _ in range(4))
@@ -90,3 +101,141 @@ def _protocol2(pred, gt, x2d, traj, cam, conn):
     per_h = r["pbest_sums"].permute(1, 2, 0, 3).reshape(T, P, -1).sum(dim=-1) / (B * F * J)
     return {"p2_j_best": per_t(r["jbest"]), "p2_p_best": per_h.min(dim=1).values.float(), "p2_p_agg": per_t(r["pagg"]),
             "p2_j_agg": per_t(r["jagg"])}
+
+
+def protocol2_accumulators(pred_parts, gt_parts, inputs_2d, traj, cam, dataset):
+    """the four Protocol #2 vectors of evaluate_accumulators(p2=True) alone, from all P hypotheses"""
+    pred, gt, x2d, tr, cm, conn, _ = _operands(pred_parts, gt_parts, inputs_2d, traj, cam, dataset, "protocol2_accumulators")
+    return _protocol2(pred, gt, x2d, tr, cm, conn)
+
+
+def _part_table(dataset, num_kps, device):
+    """part number of every joint, parts numbered in the order of dataset.parts_joint_indices"""
+    part = torch.zeros(num_kps, dtype=torch.int32)
+    for i, idx in enumerate(dataset.parts_joint_indices.values()):
+        part[idx] = i
+    return part.to(device)
+
+
+class PartialState:
+    """The running reduction of the hypotheses one rank has seen so far: the merged head of the kernel's state (40 bytes
+    per (b,t,f,j), independent of how many hypotheses went in) and the per-hypothesis sums of every chunk."""
+
+    def __init__(self, shape, num_parts, device):
+        self.shape, self.num_parts, self.device = tuple(shape), num_parts, device    # shape = (B, T, F, J)
+        self.slots = None        # [2, L] float64: row 0 the running head, row 1 the newest chunk's state
+        self.hsums = []          # [(h0, hsum [P_c,T,1+num_parts] f64)] in ascending h0
+        self.h0, self.count = None, 0
+
+    @property
+    def head(self):
+        B, T, F, J = self.shape
+        return self.slots[0, :5 * B * T * F * J]
+
+
+def accumulate_partials(state, pred_local, h0, gt_parts, inputs_2d, traj, cam, dataset):
+    """Fold the hypotheses pred_local [B,T,P_c,F,J,3] = global [h0, h0 + P_c) into `state` (None: start one) and return
+    it.  Chunks come in ascending h0 and follow each other without a gap; memory: the chunk, two 40-byte-per-(b,t,f,j)
+    heads and [P_c,T,1+parts] doubles - never anything of size P."""
+    from . import ops
+    pred, gt, x2d, tr, cm, conn, pbroot = _operands(pred_local, gt_parts, inputs_2d, traj, cam, dataset, "accumulate_partials",
+                                                    name="pred_local", axis="P_c")
+    B, T, P_c, F, J, _ = pred.shape
+    np_ = len(dataset.parts_joint_indices)
+    if not 1 <= np_ <= _lib.MAX_PARTS:
+        raise ValueError(f"the partial reductions keep per-part sums for 1 .. {_lib.MAX_PARTS} parts")
+    part = _part_table(dataset, J, pred.device)
+    if state is None:
+        state = PartialState((B, T, F, J), np_, pred.device)
+    if state.shape != (B, T, F, J) or state.num_parts != np_ or state.device != pred.device:
+        raise ValueError(f"accumulate_partials: the state holds {state.shape}, the chunk is {(B, T, F, J)}")
+    if state.h0 is not None and int(h0) != state.h0 + state.count:
+        raise ValueError(f"accumulate_partials: chunk starts at hypothesis {h0}, the state ends at {state.h0 + state.count}")
+    n5 = 5 * B * T * F * J
+    L = n5 + P_c * T * (1 + np_)
+    first = state.slots is None
+    if first or state.slots.shape[1] < L:
+        slots = torch.empty(2, L, device=pred.device, dtype=torch.float64)
+        if not first:
+            slots[0, :n5] = state.slots[0, :n5]
+        state.slots = slots
+    row = state.slots[0 if first else 1]
+    ops.hypothesis_partials(pred, gt, x2d, tr, cm, conn, pbroot, part, np_, int(h0), out=row)
+    state.hsums.append((int(h0), ops.partials_views(row, B, T, P_c, F, J, np_)["hsum"].clone()))
+    if not first:     # running head <- running head (+) this chunk, in place (the combine kernel reads each element before it writes it)
+        ops.combine_partials(state.slots, gt, conn, pbroot, (B, T, F, J), 1, merged=state.slots[0], maps=False)
+    if state.h0 is None:
+        state.h0 = int(h0)
+    state.count += P_c
+    return state
+
+
+def _gather_states(state, num_proposals, group):
+    """[W, L] states of all ranks (ONE all-gather of equal-sized flat buffers; ragged shards are padded to the largest)
+    and the concatenated per-hypothesis sums [P,T,1+parts]."""
+    from .parallel import shard_counts, shard_range
+    B, T, F, J = state.shape
+    n5, nv = 5 * B * T * F * J, 1 + state.num_parts
+    hs = torch.cat([h for _, h in state.hsums]) if state.hsums else torch.zeros(0, T, nv, device=state.device, dtype=torch.float64)
+    world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
+    if world == 1:
+        if state.h0 != 0 or state.count != num_proposals:
+            raise ValueError(f"the state holds hypotheses [{state.h0}, {state.h0 + state.count}) of {num_proposals}")
+        return state.slots[:1], hs
+    rank = dist.get_rank(group)
+    lo, hi = shard_range(num_proposals, rank, world)
+    if (state.h0, state.count) != (lo, hi - lo):
+        raise ValueError(f"rank {rank} of {world} owns hypotheses [{lo}, {hi}) of {num_proposals}, its state holds "
+                         f"[{state.h0}, {state.h0 + state.count})")
+    counts = shard_counts(num_proposals, world)
+    pmax = max(counts)
+    send = torch.zeros(n5 + pmax * T * nv, device=state.device, dtype=torch.float64)
+    send[:n5] = state.head
+    send[n5:n5 + hs.numel()] = hs.reshape(-1)
+    via_host = dist.get_backend(group) == "gloo"          # rehearsal on a box with fewer GPUs than ranks
+    if via_host:
+        send = send.cpu()
+    recv = send.new_empty(world * send.numel())
+    dist.all_gather_into_tensor(recv, send, group=group)
+    recv = recv.view(world, -1).to(state.device)
+    tails = [recv[r, n5:].view(pmax, T, nv)[:counts[r]] for r in range(world)]
+    return recv, torch.cat(tails)
+
+
+def evaluate_accumulators_sharded(pred_local, h0, num_proposals, gt_parts, inputs_2d, traj, cam, dataset, group=None,
+                                  state=None):
+    """evaluate_accumulators from partial reductions: pred_local [B,T,P_r,F,J,3] holds hypotheses [h0, h0 + P_r) of
+    the `num_proposals` of the run - this rank's share (pafuse_amd.parallel.shard_range) or, with `state`, the last chunk
+    of it (`state`: what accumulate_partials returned for the chunks before; pred_local=None evaluates the state as it
+    is).  -> the same dict of 14 vectors [T].  With torch.distributed initialised the ranks exchange their states in
+    ONE all_gather_into_tensor (through the host on a gloo group): 40 bytes per (b,t,f,j) plus 8 * (1 + parts) * T bytes
+    per hypothesis of the largest shard, whatever P is.  j_best and j_agg are bit-equal to evaluate_accumulators;
+    p_agg*, p_best* sum in fp64 where that kernel sums in fp32 (last-bit differences, closer to exact) and do not
+    depend on how the hypotheses are cut.  Protocol #1 only."""
+    from . import ops
+    if pred_local is not None:
+        state = accumulate_partials(state, pred_local, h0, gt_parts, inputs_2d, traj, cam, dataset)
+    if state is None:
+        raise ValueError("evaluate_accumulators_sharded: neither hypotheses nor a state")
+    B, T, F, J = state.shape
+    dev = state.device
+    states, hs = _gather_states(state, int(num_proposals), group)
+    P = hs.shape[0]
+    conn, pbroot = _tables(dataset, J, dev)
+    m = ops.combine_partials(states.contiguous(), gt_parts.contiguous().float(), conn, pbroot, (B, T, F, J), P)
+    jbest, pagg, jagg, paggpb = m["jbest"], m["pagg"], m["jagg"], m["paggpb"]
+
+    def per_t(x):                                            # [B,T,F,J'] -> [T]
+        return x.permute(1, 0, 2, 3).reshape(T, -1).mean(dim=-1)
+
+    out = {"j_best": per_t(jbest), "p_agg": per_t(pagg), "j_agg": per_t(jagg), "p_agg_pb": per_t(paggpb)}
+    hs = hs.permute(1, 0, 2)                                 # [T,P,1+parts] sums over (b,f,j), fp64
+    out["p_best"] = (hs[..., 0] / (B * F * J)).float().min(dim=1).values
+    per_h = (hs[..., 1:].sum(dim=-1) / (B * F * J)).float()
+    best = per_h.argmin(dim=1)
+    out["p_best_pb"] = per_h.min(dim=1).values
+    for i, (part, idx) in enumerate(dataset.parts_joint_indices.items()):
+        ph = (hs[..., 1 + i] / (B * F * len(idx))).float()
+        out["p_best_pb_" + part] = ph.gather(1, best.view(-1, 1)).squeeze(1)
+        out["p_agg_pb_" + part] = per_t(paggpb[..., idx])
+    return out

@@ -5,7 +5,7 @@ or Hydra here; the caller hands in arrays).
 """
 import torch
 
-from .evaluate import evaluate_accumulators
+from .evaluate import accumulate_partials, evaluate_accumulators, evaluate_accumulators_sharded
 from .parallel import ShardedSampler
 
 ACCUMULATORS = ("j_best", "p_best", "p_agg", "j_agg", "p_best_pb", "p_best_pb_body", "p_best_pb_face",
@@ -143,14 +143,27 @@ def load_checkpoint(model, checkpoint):
 
 
 @torch.no_grad()
-def evaluate_sequence(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, batch_size=1024, group=None, p2=False):
+def evaluate_sequence(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, batch_size=1024, group=None, p2=False,
+                      gather="hypotheses", hypothesis_chunk=None):
     """One (camera, sequence) item of evaluate()'s loop (main_h3wb.py:261-396).
 
     seq_2d [N,J,2] normalised 2-D input, seq_3d [N,J,3] camera-space ground truth (metres), cam [9] intrinsics.
     Returns ``(sums, n)``: the 14 accumulators [T] already multiplied by the batch multiplier (clips x frames), and
     the multiplier total - add them over sequences and report ``sums[k] / n * 1000`` mm, like :func:`report`.
     ``p2=True`` adds the four Protocol #2 accumulators (ACCUMULATORS_P2, the reference's ``ft2d.p2``).
-    With torch.distributed initialised the hypothesis axis is sharded and gathered (pafuse_amd.parallel)."""
+    With torch.distributed initialised the hypothesis axis is sharded and gathered (pafuse_amd.parallel).
+
+    ``gather="hypotheses"`` (default): every rank receives all P hypotheses and evaluates them in one kernel.
+    ``gather="partials"``: every rank reduces its own hypotheses to partial reductions and the ranks exchange those
+    (evaluate.evaluate_accumulators_sharded): neither the [B,T,P,F,J,3] tensor nor per-hypothesis error maps exist
+    anywhere.  ``hypothesis_chunk=n`` (partials only) also samples and reduces the rank's hypotheses n at a time, so peak
+    memory follows n instead of P; the numbers do not depend on n.  Protocol #1 comes from the partials; ``p2=True``
+    still needs all hypotheses on every rank, so the chunks are kept and gathered for the Protocol #2 kernel (the four
+    p2_* vectors are those of gather="hypotheses") - the memory saving is then lost."""
+    if gather not in ("hypotheses", "partials"):
+        raise ValueError(f'gather must be "hypotheses" or "partials", got {gather!r}')
+    if hypothesis_chunk is not None and (gather != "partials" or int(hypothesis_chunk) < 1):
+        raise ValueError('hypothesis_chunk is a positive count and needs gather="partials"')
     dev = next(model.parameters()).device
     seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
     seq_3d = torch.as_tensor(seq_3d, dtype=torch.float32)
@@ -164,12 +177,33 @@ def evaluate_sequence(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, 
     sums, n = None, 0
     for lo in range(0, x2d.shape[0], batch_size):
         hi = min(lo + batch_size, x2d.shape[0])
-        pred = sampler(x2d[lo:hi], gt_parts[lo:hi], input_2d_flip=x2d_flip[lo:hi])      # [b,T,P,F,J,3]
-        acc = evaluate_accumulators(pred, gt_parts[lo:hi], x2d[lo:hi], traj[lo:hi], cam, dataset, p2=p2)
+        if gather == "partials":
+            acc = _accumulators_from_partials(sampler, dataset, x2d[lo:hi], x2d_flip[lo:hi], gt_parts[lo:hi], traj[lo:hi], cam,
+                                              hypothesis_chunk, p2)
+        else:
+            pred = sampler(x2d[lo:hi], gt_parts[lo:hi], input_2d_flip=x2d_flip[lo:hi])      # [b,T,P,F,J,3]
+            acc = evaluate_accumulators(pred, gt_parts[lo:hi], x2d[lo:hi], traj[lo:hi], cam, dataset, p2=p2)
         mult = (hi - lo) * model.frames                           # main_h3wb.py:333
         sums = {k: mult * v for k, v in acc.items()} if sums is None else {k: sums[k] + mult * acc[k] for k in acc}
         n += mult
     return sums, n
+
+
+def _accumulators_from_partials(sampler, dataset, x2d, x2d_flip, gt_parts, traj, cam, hypothesis_chunk, p2):
+    """One batch of clips through sample -> reduce, chunk by chunk, then one exchange of the states."""
+    from .evaluate import protocol2_accumulators
+    from .parallel import gather_hypotheses
+    state, kept = None, []
+    for pred, h0, _ in sampler.sample_chunks(x2d, gt_parts, input_2d_flip=x2d_flip, chunk=hypothesis_chunk):
+        state = accumulate_partials(state, pred, h0, gt_parts, x2d, traj, cam, dataset)
+        if p2:
+            kept.append(pred)
+    P = sampler.model.num_proposals
+    acc = evaluate_accumulators_sharded(None, None, P, gt_parts, x2d, traj, cam, dataset, group=sampler.group, state=state)
+    if p2:
+        full = gather_hypotheses(torch.cat(kept, dim=2) if len(kept) > 1 else kept[0], P, sampler.group)
+        acc.update(protocol2_accumulators(full, gt_parts, x2d, traj, cam, dataset))
+    return acc
 
 
 def report(sums, n):

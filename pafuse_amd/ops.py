@@ -665,3 +665,102 @@ def procrustes_errors(pred, gt, x2d, traj, cam, conn, pick=True):
         out["jbest"].data_ptr(), out["pbest_sums"].data_ptr(), out["pagg"].data_ptr(), out["jagg"].data_ptr(),
         out["pick"].data_ptr() if pick else None, _stream(pred)))
     return out
+
+
+# ------------------------------------------------------------------------------------ sharded hypothesis evaluation
+PARTIALS_HEAD_BYTES_PER_ELEMENT = 40   # double sum[3] + float jbest, e2, sel3 + int32 idx per (b, t, f, j)
+
+
+def partials_bytes(B, T, P_r, F, J, num_parts):
+    """Bytes of the state pafuse_hypothesis_partials writes for a shard of P_r hypotheses (the formula of
+    pafuse_hypothesis_partials_bytes, restated so that sizes can be planned without the library): the head, independent
+    of P_r, then 8 * (1 + num_parts) bytes per local hypothesis and step."""
+    return PARTIALS_HEAD_BYTES_PER_ELEMENT * B * T * F * J + 8 * P_r * T * (1 + num_parts)
+
+
+def partials_views(state, B, T, P_r, F, J, num_parts):
+    """Typed views of a flat state (1-D float64 tensor of partials_bytes / 8 elements, or longer: a padded one):
+    sum [B,T,F,J,3] f64, jbest / e2 / sel3 [B,T,F,J] f32, idx [B,T,F,J] i32, hsum [P_r,T,1+num_parts] f64."""
+    n = B * T * F * J
+    _need(state.dim() == 1 and state.dtype == torch.float64 and state.is_contiguous()
+          and state.numel() * 8 >= partials_bytes(B, T, P_r, F, J, num_parts), "partials_views: not a state of these sizes")
+    f32 = state[3 * n:5 * n].view(torch.float32)
+    return {"sum": state[:3 * n].view(B, T, F, J, 3), "jbest": f32[:n].view(B, T, F, J), "e2": f32[n:2 * n].view(B, T, F, J),
+            "sel3": f32[2 * n:3 * n].view(B, T, F, J), "idx": f32[3 * n:].view(torch.int32).view(B, T, F, J),
+            "hsum": state[5 * n:5 * n + P_r * T * (1 + num_parts)].view(P_r, T, 1 + num_parts)}
+
+
+def hypothesis_partials(pred, gt, x2d, traj, cam, conn, pbroot, part, num_parts, h0, out=None):
+    """One shard's partial reductions (pafuse_hypothesis_partials): pred [B,T,P_r,F,J,3] the LOCAL hypotheses
+    [h0, h0 + P_r) of the run, gt [B,F,J,3], x2d [B,F,J,2], traj [B,F,3] (or [B,F,1,3]), cam [9], conn / pbroot / part
+    int32 [J] (connection joint, part root, part number of every joint) -> the flat state, a 1-D float64 tensor
+    (partials_views names its pieces).  `out`: a float64 buffer at least that long to write into (a padded state for
+    the collective); the result is then `out` itself.  fp32 operands on one HIP device, contiguous."""
+    lib = _lib.load()
+    _need(pred.dim() == 6 and pred.shape[-1] == 3, f"hypothesis_partials: pred must be [B,T,P_r,F,J,3], got {tuple(pred.shape)}")
+    B, T, P_r, F, J, _ = pred.shape
+    _need(tuple(gt.shape) == (B, F, J, 3) and tuple(x2d.shape) == (B, F, J, 2) and traj.numel() == B * F * 3
+          and cam.numel() == 9 and conn.numel() == J and pbroot.numel() == J and part.numel() == J,
+          "hypothesis_partials: operands do not match pred")
+    _need(T > 0 and F > 0 and J > 0 and int(h0) >= 0, "hypothesis_partials: T, F, J > 0 and h0 >= 0")
+    _need(1 <= num_parts <= _lib.MAX_PARTS, f"hypothesis_partials: 1 .. {_lib.MAX_PARTS} parts")
+    ops = (pred, gt, x2d, traj, cam, conn, pbroot, part)
+    _need(all(t.is_cuda and t.device == pred.device and t.is_contiguous() for t in ops), "hypothesis_partials: contiguous "
+          "tensors on one HIP device (no CPU fallback)")
+    _need(all(t.dtype == torch.float32 for t in ops[:5]) and all(t.dtype == torch.int32 for t in ops[5:]),
+          "hypothesis_partials: dtypes")
+    dev = pred.device
+    need = int(lib.pafuse_hypothesis_partials_bytes(B, T, P_r, F, J, num_parts))
+    assert need == partials_bytes(B, T, P_r, F, J, num_parts)
+    if out is None:
+        out = torch.empty(need // 8, device=dev, dtype=torch.float64)
+    _need(out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous()
+          and out.numel() * 8 >= need, f"hypothesis_partials: out must be a float64 buffer of {need} bytes or more on {dev}")
+    wbytes = int(lib.pafuse_hypothesis_partials_workspace_bytes(B, T, P_r, F, J, num_parts))
+    work = torch.empty(max(wbytes // 8, 1), device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_hypothesis_partials(
+            _data(pred), _data(gt), _data(x2d), _data(traj), _data(cam), _data(conn), _data(pbroot), _data(part), num_parts,
+            B, T, P_r, F, J, int(h0), _data(out), out.numel() * 8, work.data_ptr(), work.numel() * 8, _stream(pred)))
+    return out
+
+
+def _data(t):
+    return t.data_ptr() if t.numel() else None   # an empty tensor has no storage to point the library at
+
+
+def combine_partials(states, gt, conn, pbroot, shape, num_proposals, merged=None, maps=True):
+    """pafuse_hypothesis_combine: `states` [W, L] float64 (W flat states of the same (B,T,F,J) = `shape`, one per row, in
+    ascending-h0 order; L * 8 >= the head bytes - rows may carry their per-hypothesis tail and padding, which is not
+    read).  maps=True -> dict jbest, pagg, jagg, paggpb [B,T,F,J] (what pafuse_hypothesis_errors gives; the P-Agg mean
+    divides by `num_proposals`, the TOTAL hypothesis count).  `merged`: a float64 buffer that receives the head of the
+    union's state (5*B*T*F*J elements); it may be states[0] itself when maps=False (a running state)."""
+    lib = _lib.load()
+    B, T, F, J = (int(v) for v in shape)
+    n = B * T * F * J
+    _need(states.dim() == 2 and states.dtype == torch.float64 and states.is_cuda and states.is_contiguous()
+          and states.shape[0] >= 1 and states.shape[1] >= 5 * n, "combine_partials: states must be [W, >= 5*B*T*F*J] float64")
+    _need(T > 0 and F > 0 and J > 0 and B >= 0, "combine_partials: bad shape")
+    _need(maps or merged is not None, "combine_partials: nothing to compute")
+    _need(not maps or int(num_proposals) >= 1, "combine_partials: num_proposals >= 1")
+    dev = states.device
+    ops = (gt, conn, pbroot)
+    _need(tuple(gt.shape) == (B, F, J, 3) and conn.numel() == J and pbroot.numel() == J
+          and all(t.is_cuda and t.device == dev and t.is_contiguous() for t in ops) and gt.dtype == torch.float32
+          and conn.dtype == torch.int32 and pbroot.dtype == torch.int32, "combine_partials: gt [B,F,J,3] f32, conn / pbroot "
+          "[J] int32, contiguous on the device of the states")
+    if merged is not None:
+        _need(merged.is_cuda and merged.device == dev and merged.dtype == torch.float64 and merged.is_contiguous()
+              and merged.numel() >= 5 * n, "combine_partials: merged must hold 5*B*T*F*J float64")
+        lo, hi = states.data_ptr(), states.data_ptr() + states.numel() * 8
+        _need(not (maps and merged.data_ptr() < hi and merged.data_ptr() + 40 * n > lo),
+              "combine_partials: a merge over its own operands cannot also write the maps")
+    out = {k: torch.empty(B, T, F, J, device=dev) for k in ("jbest", "pagg", "jagg", "paggpb")} if maps else {}
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_hypothesis_combine(
+            states.data_ptr(), states.shape[0], states.shape[1] * 8, gt.data_ptr(), conn.data_ptr(), pbroot.data_ptr(),
+            B, T, F, J, int(num_proposals), None if merged is None else merged.data_ptr(),
+            *((out[k].data_ptr() for k in ("jbest", "pagg", "jagg", "paggpb")) if maps else (None,) * 4), _stream(states)))
+    return out

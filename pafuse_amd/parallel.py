@@ -5,6 +5,10 @@ common/mixste.py reduces over P), so rank r owns hypotheses [lo, hi) for all cli
 replicated, and the only exchange is ONE all-gather of the per-rank predictions before the aggregation
 protocols (J-Agg & co.) - 8.7 MB per rank at P_local=20, T=10, B=1.  Every rank draws the full-P noise tensor
 from the same seed and keeps its slice, so the sharded run reproduces the single-GPU hypotheses.
+
+Evaluation does not need the hypotheses themselves on every rank: ``ShardedSampler.sample_local`` /
+``sample_chunks`` hand out the local ones, and ``pafuse_amd.evaluate.evaluate_accumulators_sharded`` exchanges their
+partial reductions instead (40 bytes per (b,t,f,j), whatever P is).
 """
 import torch
 import torch.distributed as dist
@@ -78,6 +82,51 @@ class ShardedSampler:
         self.model, self.group = model, group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+
+    def local_range(self):
+        """[lo, hi): the hypotheses of the run this rank samples"""
+        return shard_range(self.model.num_proposals, self.rank, self.world)
+
+    def sample_local(self, input_2d, input_3d, input_2d_flip=None, lo=None, hi=None):
+        """This rank's hypotheses WITHOUT the gather -> (pred_local [B,T,P_r,F,J,3], h0, P_r).  `lo`, `hi` (global
+        indices inside local_range()) narrow the call to a part of them.  The model draws the full-P noise and keeps
+        the slice, so the values are those of the unsharded run provided the generator stands where that run would
+        find it (sample_chunks sees to that between chunks)."""
+        m = self.model
+        a, b = self.local_range()
+        lo, hi = a if lo is None else int(lo), b if hi is None else int(hi)
+        if not a <= lo <= hi <= b:
+            raise ValueError(f"hypotheses [{lo}, {hi}) are not inside this rank's [{a}, {b})")
+        if hi == lo:      # nothing to sample (a rank beyond the P-th when P < world): no model call, an empty tensor of the right shape
+            T = len(m.ddim_steps())
+            return input_2d.new_zeros((input_2d.shape[0], T, 0, m.frames, m.num_kps, 3), dtype=torch.float32), lo, 0
+        m.proposal_shard = (lo, hi)
+        try:
+            local = m(input_2d, input_3d, input_2d_flip=input_2d_flip)
+        finally:
+            m.proposal_shard = None
+        return local, lo, hi - lo
+
+    def sample_chunks(self, input_2d, input_3d, input_2d_flip=None, chunk=None):
+        """Generator over this rank's hypotheses in chunks of at most `chunk` (None: all at once), ascending:
+        yields (pred_chunk, h0, P_c).  Every chunk's call starts from the same state of the device's random generator,
+        so each draws the full-P noise of the unsharded run and keeps its own slice; after the last chunk the generator
+        stands where one unsharded call leaves it.  Peak memory follows the chunk, not P."""
+        if chunk is not None and int(chunk) < 1:
+            raise ValueError(f"hypothesis chunk must be a positive count, got {chunk}")
+        a, b = self.local_range()
+        step = max(b - a, 1) if chunk is None else int(chunk)
+        dev = input_2d.device
+        rng = torch.cuda.get_rng_state(dev) if (input_2d.is_cuda and b - a > step) else None
+        lo = a
+        while True:
+            hi = min(b, lo + step)
+            if rng is not None and lo > a:
+                torch.cuda.set_rng_state(rng, dev)
+            yield self.sample_local(input_2d, input_3d, input_2d_flip, lo, hi)
+            lo = hi
+            if lo >= b:
+                return
 
     def __call__(self, input_2d, input_3d, input_2d_flip=None):
         m = self.model

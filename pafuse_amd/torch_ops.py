@@ -9,6 +9,8 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::block(x, weights[12], heads, precision)          Block.forward on [S,L,C]       common/mixste.py:113-116
   pafuse::mixste_eval(x2d, x3d, t, weights, depth, heads, precision)  MixSTE2.forward, eval  common/mixste.py:278-298
   pafuse::ddim_loop(..., precision)                        D3DP.ddim_sample[_flip]        common/diffusionpose.py:227-316
+  pafuse::hypothesis_partials(pred, gt, x2d, traj, cam, conn, pbroot, part, num_parts, h0)   one shard's partial reductions
+  pafuse::combine_partials(states, gt, conn, pbroot, T, num_proposals)   jbest, pagg, jagg, paggpb from W states   main_h3wb.py:327-362
 
 ``precision`` ('bf16x3' = the modules' default; 'bf16x3_images', 'f16x2', 'f32', 'bf16': pafuse_amd.D3DP.precision) is the
 matrix-product mode of the linear layers; in the split modes the ops build and cache the pre-split weight images themselves (cached_split_image).
@@ -365,6 +367,37 @@ def ddim_loop(x2d: torch.Tensor, x2d_flip: torch.Tensor, noise: torch.Tensor, we
 def _(x2d, x2d_flip, noise, weights, part_joints, flip_perm, depth, heads, times, sched, flip, scale, precision="bf16x3"):
     n_draws, B, P, F, J, _ = noise.shape
     return noise.new_empty(B, len(times), P, F, J, 3)
+
+
+# --------------------------------------------------------------------------------- sharded hypothesis evaluation
+@torch.library.custom_op("pafuse::hypothesis_partials", mutates_args=(), device_types="cuda")
+def hypothesis_partials(pred: torch.Tensor, gt: torch.Tensor, x2d: torch.Tensor, traj: torch.Tensor, cam: torch.Tensor,
+                        conn: torch.Tensor, pbroot: torch.Tensor, part: torch.Tensor, num_parts: int, h0: int) -> torch.Tensor:
+    """pafuse_amd.ops.hypothesis_partials: the flat float64 state of the local hypotheses [h0, h0 + P_r)."""
+    from . import ops
+    return ops.hypothesis_partials(pred, gt, x2d, traj, cam, conn, pbroot, part, num_parts, h0)
+
+
+@hypothesis_partials.register_fake
+def _(pred, gt, x2d, traj, cam, conn, pbroot, part, num_parts, h0):
+    B, T, P_r, F, J, _ = pred.shape
+    return pred.new_empty(5 * B * T * F * J + P_r * T * (1 + num_parts), dtype=torch.float64)
+
+
+@torch.library.custom_op("pafuse::combine_partials", mutates_args=(), device_types="cuda")
+def combine_partials(states: torch.Tensor, gt: torch.Tensor, conn: torch.Tensor, pbroot: torch.Tensor, T: int,
+                     num_proposals: int) -> List[torch.Tensor]:
+    """pafuse_amd.ops.combine_partials on states [W, L]: -> [jbest, pagg, jagg, paggpb], each [B,T,F,J]."""
+    from . import ops
+    B, F, J, _ = gt.shape
+    m = ops.combine_partials(states, gt, conn, pbroot, (B, T, F, J), num_proposals)
+    return [m["jbest"], m["pagg"], m["jagg"], m["paggpb"]]
+
+
+@combine_partials.register_fake
+def _(states, gt, conn, pbroot, T, num_proposals):
+    B, F, J, _ = gt.shape
+    return [gt.new_empty(B, T, F, J) for _ in range(4)]
 
 
 def ddim_loop_args(model):
