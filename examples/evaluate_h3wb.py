@@ -33,6 +33,10 @@ def main():
                     help="what the ranks exchange before the aggregation: all hypotheses, or their partial reductions")
     ap.add_argument("--hypothesis-chunk", type=int, default=None,
                     help="with --gather partials: sample and reduce this many hypotheses at a time")
+    ap.add_argument("--noise", choices=("torch", "device"), default="torch",
+                    help="where the loop's normals come from: torch.randn on the full tensor, or the library's counter-based "
+                         "stream drawn inside the kernels (no noise tensor; other hypotheses than torch.randn's)")
+    ap.add_argument("--seed", type=int, default=0, help="with --noise device: the seed of the stream, in [0, 2^32)")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
     args = config.load(a.config or None, a.overrides)
@@ -59,6 +63,8 @@ def main():
         print("This model was trained for {} epochs".format(ckpt.get("epoch", "?")))
         harness.load_checkpoint(model, ckpt)
     model = model.to(f"cuda:{local}").eval()
+    if a.noise == "device":
+        model.noise, model.noise_seed = "device", a.seed
     torch.manual_seed(0)            # every rank draws the same full-P noise and keeps its hypothesis slice
     log = print if int(os.environ.get("RANK", "0")) == 0 else (lambda *x: None)
     log("Test time augmentation:", args.model.test_time_augmentation)

@@ -4,6 +4,7 @@ sequences (the H3WB npz files and the released checkpoint are not available offl
 
     python examples/evaluate_synthetic.py --proposals 20 --timesteps 10 --sequences 2 --frames 120
     torchrun --standalone --nproc-per-node 8 examples/evaluate_synthetic.py --proposals 160     # hypothesis-sharded
+    python examples/evaluate_synthetic.py --proposals 160 --gather partials --hypothesis-chunk 20 --noise device --seed 7
 
 Prints the per-step protocol lines in the reference's log format (values are meaningless with random weights).
 """
@@ -33,6 +34,10 @@ def main():
                     help="what the ranks exchange before the aggregation: all hypotheses, or their partial reductions")
     ap.add_argument("--hypothesis-chunk", type=int, default=None,
                     help="with --gather partials: sample and reduce this many hypotheses at a time")
+    ap.add_argument("--noise", choices=("torch", "device"), default="torch",
+                    help="where the loop's normals come from: torch.randn on the full tensor, or the library's counter-based "
+                         "stream drawn inside the kernels (no noise tensor; other hypotheses than torch.randn's)")
+    ap.add_argument("--seed", type=int, default=0, help="with --noise device: the seed of the stream, in [0, 2^32)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -45,6 +50,8 @@ def main():
     if a.checkpoint:
         harness.load_checkpoint(model, harness.read_checkpoint(a.checkpoint))
         model = model.to(f"cuda:{local}").eval()
+    if a.noise == "device":
+        model.noise, model.noise_seed = "device", a.seed
     ds = SimpleNamespace(parts_joint_indices=gu.DATASET_PART_JOINTS, root_indices=gu.ROOT_INDICES,
                          parts_connection_indices=dict(gu.CONNECTION_INDICES))
     cam = torch.tensor([2.29, 2.287, 0.025, 0.029, -0.207, 0.247, -0.003, -0.0009, -0.001])   # normalised intrinsics
@@ -76,7 +83,7 @@ def main():
             print("step %d : Protocol #1 Error (MPJPE) P_Agg Part-Based: %f mm" % (i, mm["p_agg_pb"][i]))
         clips = n // 27
         print(f"{clips} clips x {a.proposals} hypotheses x {a.timesteps} steps in {time.time() - t0:.2f} s "
-              f"on {world} GPU(s)")
+              f"on {world} GPU(s), noise {a.noise}, peak device memory {torch.cuda.max_memory_allocated() / 1e6:.0f} MB")
 
 
 if __name__ == "__main__":

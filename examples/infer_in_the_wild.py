@@ -37,6 +37,10 @@ def main():
     ap.add_argument("--checkpoint", default="")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "in_the_wild"))
     ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--noise", choices=("torch", "device"), default="torch",
+                    help="where the loop's normals come from: torch.randn on the full tensor, or the library's counter-based "
+                         "stream drawn inside the kernels (no noise tensor; other hypotheses than torch.randn's)")
+    ap.add_argument("--seed", type=int, default=0, help="with --noise device: the seed of the stream, in [0, 2^32)")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
     args = config.load(None, a.overrides)
@@ -58,6 +62,8 @@ def main():
     if a.checkpoint:
         harness.load_checkpoint(model, harness.read_checkpoint(a.checkpoint))
     model = model.cuda().eval()
+    if a.noise == "device":
+        model.noise, model.noise_seed = "device", a.seed
 
     pixels = harness.load_pifpaf_keypoints(a.keypoints, args.data.num_kps)
     keypoints = h3wb.normalize_screen_coordinates(pixels[..., :2], w=a.width, h=a.height).astype(np.float32)

@@ -426,6 +426,27 @@ int pafuse_d3dp_sample(const pafuse_d3dp_config *cfg, const pafuse_ddim_step *st
                        int32_t P, float *out, void *workspace, size_t workspace_bytes, void *stream,
                        void *const *aux_streams, int32_t n_aux);
 
+/* pafuse_d3dp_sample with the loop's noise drawn inside its own kernels from "noise stream v1"  instead
+ * of read from a [n_draws,B,P,F,J,3] stack: draw k (0 = the initial img, k >= 1 = the update after step k - 1) of global clip b,
+ * global hypothesis p, frame f, joint j is
+ *   (r0..r3) = Philox4x32-10(counter (f*J + j, p, b, k), key (seed, call));   u(r) = (r + 0.5) * 2^-32
+ *   x = sqrt(-2 ln u(r0)) cos(2 pi u(r1)),  y = sqrt(-2 ln u(r0)) sin(2 pi u(r1)),  z = sqrt(-2 ln u(r2)) cos(2 pi u(r3))
+ * evaluated in fp64 and rounded once to fp32 (host statement: pafuse_amd/noise.py).  key4_dev: four uint32 IN DEVICE MEMORY,
+ * {seed, call, b0, p0}, read by the kernels when they run - b0 / p0 are the global indices of this call's first clip / first
+ * hypothesis, so a call on clips [b0, b0 + B) and hypotheses [p0, p0 + P) returns that slice of the full call, and a captured
+ * graph is replayed with other words after a 16-byte copy.  Everything else as pafuse_d3dp_sample (same workspace, same lanes);
+ * the arithmetic that consumes the normals is the same, so the result equals pafuse_d3dp_sample on the pafuse_noise_fill
+ * tensors of the same key, bit for bit. */
+int pafuse_d3dp_sample_seeded(const pafuse_d3dp_config *cfg, const pafuse_ddim_step *steps, int32_t nsteps,
+                              const float *x2d, const float *x2d_flip, const uint32_t *key4_dev, int32_t B, int32_t P,
+                              float *out, void *workspace, size_t workspace_bytes, void *stream,
+                              void *const *aux_streams, int32_t n_aux);
+
+/* Draw `draw` of noise stream v1 for B clips x P hypotheses of F frames x J joints as a tensor: out [B,P,F,J,3].
+ * key4_dev as above (device memory). */
+int pafuse_noise_fill(const uint32_t *key4_dev, int32_t draw, int32_t B, int32_t P, int32_t F, int32_t J, float *out,
+                      void *stream);
+
 /* Loud failure through the loop.  pafuse_d3dp_sample keeps one int32 in its workspace (byte offset pafuse_d3dp_range_flag_offset,
  * zeroed at the start of every call) that the output stage of every step sets when a denoiser prediction is not finite.  The
  * values themselves flow on as NaN - the clamps of the loop keep a NaN a NaN, exactly as torch.clamp does

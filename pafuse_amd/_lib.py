@@ -126,6 +126,10 @@ SIGNATURES = {
     "pafuse_d3dp_sample": (C.c_int, [C.POINTER(D3DPConfig), C.POINTER(DDIMStep), C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32]),
+    "pafuse_d3dp_sample_seeded": (C.c_int, [C.POINTER(D3DPConfig), C.POINTER(DDIMStep), C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32]),
+    "pafuse_noise_fill": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
     "pafuse_d3dp_lanes": (C.c_int, [C.POINTER(D3DPConfig), C.c_int32, C.c_int32, C.c_int32]),
     "pafuse_d3dp_range_flag_offset": (C.c_size_t, [C.POINTER(D3DPConfig), C.c_int32, C.c_int32]),
     "pafuse_d3dp_check_range": (C.c_int, [C.POINTER(D3DPConfig), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -2417,13 +2417,63 @@ struct FinalizeParams {
     float scale, lim;  // (float)scale and (float)(1.1 * scale) (fp64 product), see EmbedParams
     double sr, srm1, c;
     float an_f, c_f, sigma_f;
+    const uint32_t* key4;  // finalize_seeded_kernel: {seed, call, b0, p0} in device memory (noise stream v1) ...
+    int draw;              // ... and which draw of it this step consumes; `noise` is not read
     int32_t* range_flag;   // device word (or null): set to 1 when a denoiser output of this step is not finite - in 'f16x2' the loud
     //                        form of an activation beyond the fp16 range (|a| >= 65504 -> inf -> NaN); the values themselves flow on as
     //                        NaN, as the reference's would (no clamp hides them)
 };
 
-__global__ void __launch_bounds__(256) finalize_kernel(const FinalizeParams p) {
+// ----------------------------------------------------------------------------------------------------------------
+// Noise stream v1 (host statement: pafuse_amd/noise.py).  The three normals of joint (f, j) of
+// hypothesis p of clip b in draw k:  Philox4x32-10, counter (f*J + j, p, b, k), key (seed, call);  u(r) = (r + 0.5) 2^-32;
+//   x = sqrt(-2 ln u(r0)) cos(2 pi u(r1)),  y = the same radius * sin(2 pi u(r1)),  z = sqrt(-2 ln u(r2)) cos(2 pi u(r3))
+// in fp64 (correctly rounded sqrt and products, log and sincospi of the device library: no fast-math), rounded once to
+// fp32 - which is what lets a host reproduce the stream to the bit.  key4 = {seed, call, b0, p0} lives in device memory
+// so that a captured graph is replayed with other words after a 16-byte copy; b0 / p0 are the global indices of the
+// call's first clip / hypothesis (index arithmetic is modulo 2^32, like the counter).
+// ----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c[0]), l0 = 0xD2511F53u * c[0];
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c[2]), l1 = 0xCD9E8D57u * c[2];
+        c[0] = h1 ^ c[1] ^ k0, c[1] = l1, c[2] = h0 ^ c[3] ^ k1, c[3] = l0;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+}
+
+__device__ __forceinline__ double noise_uniform(uint32_t r) { return __dmul_rn(__dadd_rn((double)r, 0.5), 0x1p-32); }
+
+__device__ __forceinline__ void noise_normals(const uint32_t* __restrict__ key4, uint32_t draw, uint32_t b, uint32_t p, uint32_t fj,
+                                              float (&z)[3]) {
+    uint32_t c[4] = {fj, key4[3] + p, key4[2] + b, draw};
+    philox4x32_10(c, key4[0], key4[1]);
+    const double rad_xy = sqrt(__dmul_rn(-2.0, log(noise_uniform(c[0]))));
+    const double rad_z = sqrt(__dmul_rn(-2.0, log(noise_uniform(c[2]))));
+    double s1, c1, s3, c3;
+    sincospi(__dmul_rn(2.0, noise_uniform(c[1])), &s1, &c1);
+    sincospi(__dmul_rn(2.0, noise_uniform(c[3])), &s3, &c3);
+    z[0] = (float)__dmul_rn(rad_xy, c1), z[1] = (float)__dmul_rn(rad_xy, s1), z[2] = (float)__dmul_rn(rad_z, c3);
+}
+
+// draw `draw` of the stream as a tensor [B,P,F,J,3]: the initial img of the seeded loop, and pafuse_noise_fill
+__global__ void __launch_bounds__(256) noise_fill_kernel(const uint32_t* __restrict__ key4, int draw, int B, int P, int F, int J,
+                                                         float* __restrict__ out) {
     PAFUSE_XQ_GUARD();
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t FJ = (int64_t)F * J;
+    if (e >= (int64_t)B * P * FJ) return;
+    const int64_t bp = e / FJ;
+    float z[3];
+    noise_normals(key4, (uint32_t)draw, (uint32_t)(bp / P), (uint32_t)(bp % P), (uint32_t)(e % FJ), z);
+    float* o = out + e * 3;
+    o[0] = z[0], o[1] = z[1], o[2] = z[2];
+}
+
+// SEEDED: the step's normals come from the stream (p.key4, p.draw) instead of p.noise; everything that consumes them is the same
+template <bool SEEDED>
+__device__ __forceinline__ void finalize_body(const FinalizeParams& p) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t total = (int64_t)p.B * p.P * p.F * p.J;
     if (e >= total) return;
@@ -2459,7 +2509,10 @@ __global__ void __launch_bounds__(256) finalize_kernel(const FinalizeParams p) {
         for (int k = 0; k < 3; ++k) im[k] = x0[k];
         return;
     }
-    const float* nz = p.noise + e * 3;
+    float drawn[3];
+    const float* nz = drawn;
+    if constexpr (SEEDED) noise_normals(p.key4, (uint32_t)p.draw, (uint32_t)b, (uint32_t)pp, (uint32_t)(f * p.J + j), drawn);
+    else nz = p.noise + e * 3;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const double eps64 = __ddiv_rn(__dsub_rn(__dmul_rn(p.sr, (double)im[k]), (double)x0[k]), p.srm1);
@@ -2475,6 +2528,16 @@ __global__ void __launch_bounds__(256) finalize_kernel(const FinalizeParams p) {
             im[k] = (float)__dadd_rn(__dadd_rn(t1, t2), t3);
         }
     }
+}
+
+__global__ void __launch_bounds__(256) finalize_kernel(const FinalizeParams p) {
+    PAFUSE_XQ_GUARD();
+    finalize_body<false>(p);
+}
+
+__global__ void __launch_bounds__(256) finalize_seeded_kernel(const FinalizeParams p) {
+    PAFUSE_XQ_GUARD();
+    finalize_body<true>(p);
 }
 
 // ----------------------------------------------------------------------------------------------------------------

@@ -1519,17 +1519,20 @@ static int d3dp_check(const pafuse_d3dp_config* cfg, int B, int P) {
     return PAFUSE_OK;
 }
 
-int pafuse_d3dp_sample(const pafuse_d3dp_config* cfg, const pafuse_ddim_step* steps, int32_t nsteps, const float* x2d,
-                       const float* x2d_flip, const float* noise, int32_t n_draws, int32_t B, int32_t P, float* out,
-                       void* workspace, size_t workspace_bytes, void* stream, void* const* aux_streams, int32_t n_aux) {
+// The loop behind pafuse_d3dp_sample (key4 null: the draws are read from `noise`) and pafuse_d3dp_sample_seeded (key4 set: the
+// draws are generated where they are consumed, noise stream v1; `noise` is null).
+static int d3dp_sample_impl(const pafuse_d3dp_config* cfg, const pafuse_ddim_step* steps, int32_t nsteps, const float* x2d,
+                            const float* x2d_flip, const float* noise, int32_t n_draws, const uint32_t* key4, int32_t B, int32_t P,
+                            float* out, void* workspace, size_t workspace_bytes, void* stream, void* const* aux_streams,
+                            int32_t n_aux) {
     StreamDevice on_stream_device(stream);
     int rc = d3dp_check(cfg, B, P);
     if (rc) return rc;
-    if (!steps || nsteps <= 0 || !x2d || !noise || !out || !workspace || (cfg->flip && !x2d_flip) || n_draws < 1)
+    if (!steps || nsteps <= 0 || !x2d || !(noise || key4) || !out || !workspace || (cfg->flip && !x2d_flip) || (!key4 && n_draws < 1))
         return fail(PAFUSE_E_ARG, "d3dp_sample: bad argument");
     int need = 1;
     for (int k = 0; k < nsteps; ++k) need += steps[k].last ? 0 : 1;
-    if (n_draws < need) return fail(PAFUSE_E_ARG, "d3dp_sample: %d noise draws given, %d needed", n_draws, need);
+    if (!key4 && n_draws < need) return fail(PAFUSE_E_ARG, "d3dp_sample: %d noise draws given, %d needed", n_draws, need);
     if (workspace_bytes < pafuse_d3dp_workspace_bytes(cfg, B, P)) return fail(PAFUSE_E_WORKSPACE, "workspace too small");
 
     hipStream_t s0 = (hipStream_t)stream;
@@ -1563,8 +1566,13 @@ int pafuse_d3dp_sample(const pafuse_d3dp_config* cfg, const pafuse_ddim_step* st
     const bool multi = n_aux > 0 && lanes > 1;
     constexpr int MAX_LANES = 64;
     if (lanes > MAX_LANES) return fail(PAFUSE_E_ARG, "too many stream lanes (%d)", lanes);
-    hipLaunchKernelGGL(copy_kernel, dim3((unsigned)((img_elems + 255) / 256)), dim3(256), 0, s0, noise, img, img_elems);
-    if ((rc = check_launch("copy_kernel"))) return rc;
+    if (key4) {
+        hipLaunchKernelGGL(noise_fill_kernel, dim3((unsigned)((img_elems / 3 + 255) / 256)), dim3(256), 0, s0, key4, 0, B, P, F, J, img);
+        if ((rc = check_launch("noise_fill_kernel"))) return rc;
+    } else {
+        hipLaunchKernelGGL(copy_kernel, dim3((unsigned)((img_elems + 255) / 256)), dim3(256), 0, s0, noise, img, img_elems);
+        if ((rc = check_launch("copy_kernel"))) return rc;
+    }
     hipEvent_t ev_fork = nullptr, ev_join[MAX_LANES] = {};
     if (multi) {
         hipError_t e = hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming);
@@ -1645,13 +1653,15 @@ int pafuse_d3dp_sample(const pafuse_d3dp_config* cfg, const pafuse_ddim_step* st
         FinalizeParams f{};
         for (int i = 0; i < NP; ++i) f.pred[i] = pb[i].pred, f.Jp[i] = cfg->part[i].joints;
         f.joint_part = cfg->joint_part, f.joint_local = cfg->joint_local, f.perm = cfg->flip_perm;
-        f.img = img, f.noise = st.last ? nullptr : noise + (int64_t)draw * img_elems, f.out = out;
+        f.img = img, f.noise = (st.last || key4) ? nullptr : noise + (int64_t)draw * img_elems, f.out = out;
+        f.key4 = key4, f.draw = draw;
         f.B = B, f.P = P, f.F = F, f.J = J, f.T = nsteps, f.step = k, f.flip = cfg->flip, f.last = st.last;
         f.scale = (float)cfg->scale, f.lim = (float)(1.1 * cfg->scale), f.sr = st.sqrt_recip_acp, f.srm1 = st.sqrt_recipm1_acp, f.c = st.c;
         f.an_f = (float)st.sqrt_alpha_next, f.c_f = (float)st.c, f.sigma_f = (float)st.sigma;
         f.range_flag = range_flag;
         const int64_t n = (int64_t)B * P * F * J;
-        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s0, f);
+        if (key4) hipLaunchKernelGGL(finalize_seeded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s0, f);
+        else hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s0, f);
         rc = check_launch("finalize_kernel");
         if (!st.last) ++draw;
     }
@@ -1665,6 +1675,31 @@ int pafuse_d3dp_sample(const pafuse_d3dp_config* cfg, const pafuse_ddim_step* st
             rc = fail(PAFUSE_E_HIP, "d3dp_sample: stream join failed: %s", hipGetErrorString(sync_err));
     }
     return rc;
+}
+
+int pafuse_d3dp_sample(const pafuse_d3dp_config* cfg, const pafuse_ddim_step* steps, int32_t nsteps, const float* x2d,
+                       const float* x2d_flip, const float* noise, int32_t n_draws, int32_t B, int32_t P, float* out,
+                       void* workspace, size_t workspace_bytes, void* stream, void* const* aux_streams, int32_t n_aux) {
+    return d3dp_sample_impl(cfg, steps, nsteps, x2d, x2d_flip, noise, n_draws, nullptr, B, P, out, workspace, workspace_bytes, stream,
+                            aux_streams, n_aux);
+}
+
+int pafuse_d3dp_sample_seeded(const pafuse_d3dp_config* cfg, const pafuse_ddim_step* steps, int32_t nsteps, const float* x2d,
+                              const float* x2d_flip, const uint32_t* key4_dev, int32_t B, int32_t P, float* out, void* workspace,
+                              size_t workspace_bytes, void* stream, void* const* aux_streams, int32_t n_aux) {
+    if (!key4_dev) return fail(PAFUSE_E_ARG, "d3dp_sample_seeded: null key");
+    return d3dp_sample_impl(cfg, steps, nsteps, x2d, x2d_flip, nullptr, 0, key4_dev, B, P, out, workspace, workspace_bytes, stream,
+                            aux_streams, n_aux);
+}
+
+int pafuse_noise_fill(const uint32_t* key4_dev, int32_t draw, int32_t B, int32_t P, int32_t F, int32_t J, float* out, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!key4_dev || !out) return fail(PAFUSE_E_ARG, "noise_fill: null pointer");
+    if (draw < 0 || B <= 0 || P <= 0 || F <= 0 || J <= 0) return fail(PAFUSE_E_ARG, "noise_fill: bad size (draw=%d B=%d P=%d F=%d J=%d)", draw, B, P, F, J);
+    const int64_t n = (int64_t)B * P * F * J, blocks = (n + 255) / 256;
+    if ((int64_t)F * J > 0xffffffffLL || blocks > 0x7fffffff) return fail(PAFUSE_E_ARG, "noise_fill: size out of range");
+    hipLaunchKernelGGL(noise_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, key4_dev, draw, B, P, F, J, out);
+    return check_launch("noise_fill_kernel");
 }
 
 int pafuse_d3dp_lanes(const pafuse_d3dp_config* cfg, int32_t B, int32_t P, int32_t n_aux) {

@@ -133,6 +133,10 @@ class D3DP(nn.Module):
         self.register_buffer("_flip_perm", perm, persistent=False)
         # hooks that do not change the reference call signature
         self.noise_fn = None           # callable(k, shape, device) -> draw k (tests inject recorded noise)
+        self._noise = "torch"          # noise source of the eval loop, see the `noise` property
+        self._noise_seed = 0           # "device" source: key word 0 of the stream (the `noise_seed` property)
+        self.noise_call = 0            # "device" source: key word 1 - the public sampling calls since noise_seed was set
+        self._hold_noise_call = False  # several model calls that make up ONE logical call (pafuse_amd.parallel)
         self.train_draw_fn = None      # callable(sample) -> (t [1] int64, noise [F,J,3]) (tests, training path)
         self.proposal_shard = None     # (lo, hi): this rank's slice of the hypothesis axis (pafuse_amd.parallel)
         self.aux_streams = None        # explicit list of torch.cuda.Stream the parts are spread over; None = two
@@ -161,6 +165,58 @@ class D3DP(nn.Module):
         for m in self.denoisers().values():
             m.operand_bf16 = self.PRECISIONS["bf16x3"]
         self.allow_split_products_under_ddp = False
+
+    NOISE_SOURCES = ("torch", "device")
+
+    @property
+    def noise(self):
+        """Where the eval loop's normal draws come from:
+        'torch'  (the default) torch.randn - or noise_fn - on the whole [B,P,F,J,3] tensor, once per draw, stacked and handed to
+                 the library; a shard draws the full-P tensor and keeps its slice.  Parity with the reference is a property of
+                 this source and of injected noise;
+        'device' noise stream v1 (pafuse_amd/noise.py): the loop's own kernels generate each normal where it
+                 is consumed, from a counter-based generator keyed by (noise_seed, noise_call).  Hypothesis p of clip b is a
+                 pure function of (noise_seed, noise_call, b, p) whatever the sharding, the hypothesis chunk, the clip chunk or
+                 the launch schedule, and no noise tensor is allocated.  These are NOT the hypotheses torch.randn gives."""
+        return self._noise
+
+    @noise.setter
+    def noise(self, value):
+        if value not in self.NOISE_SOURCES:
+            raise ValueError(f"noise must be one of {list(self.NOISE_SOURCES)}, got {value!r}")
+        if value == "device" and self.noise_fn is not None:
+            raise ValueError("noise = 'device' draws inside the kernels: it cannot be combined with noise_fn")
+        self._noise = value
+
+    @property
+    def noise_fn(self):
+        return self._noise_fn
+
+    @noise_fn.setter
+    def noise_fn(self, fn):
+        if fn is not None and getattr(self, "_noise", "torch") == "device":
+            raise ValueError("noise_fn injects draws into the 'torch' noise source: it cannot be combined with noise = 'device'")
+        self._noise_fn = fn
+
+    @property
+    def noise_seed(self):
+        """'device' noise source: the seed of the stream, a value in [0, 2^32).  Setting it restarts noise_call at 0, so a run
+        that sets the seed and makes the same calls sees the same hypotheses."""
+        return self._noise_seed
+
+    @noise_seed.setter
+    def noise_seed(self, value):
+        if isinstance(value, bool) or int(value) != value or not 0 <= int(value) < 2 ** 32:
+            raise ValueError(f"noise_seed must be an integer in [0, 2^32), got {value!r}")
+        self._noise_seed, self.noise_call = int(value), 0
+
+    def advance_noise_call(self):
+        """One public sampling call is over ('device' noise source): the next one draws under the next `call` word.  The calls
+        that make up one logical call (the hypothesis chunks of ShardedSampler.sample_chunks) hold it in between."""
+        if self._noise == "device" and not self._hold_noise_call:
+            if self.noise_call + 1 >= 2 ** 32:
+                raise _lib.PafuseError("noise_call ran out of its 32 bits: set a new noise_seed")
+            self.noise_call += 1
 
     PRECISIONS = {"f32": 0, "bf16": 1, "bf16x3": 2, "f16x2": 3, "bf16x3_images": 4}
 
@@ -269,8 +325,10 @@ class D3DP(nn.Module):
                              f"{tuple(inputs_2d.shape)}" + (f" / {tuple(input_2d_flip.shape)}" if flip else ""))
         if flip and input_2d_flip.device != dev:
             raise ValueError("input_2d_flip must live on the device of inputs_2d")
-        shape = (B, self.num_proposals, self.frames, self.num_kps, 3)
         steps = self.ddim_steps()
+        if self._noise == "device":
+            return self._ddim_sample_seeded(lib, inputs_2d, input_2d_flip, steps, flip)
+        shape = (B, self.num_proposals, self.frames, self.num_kps, 3)
         n_draws = 1 + sum(1 for s in steps if not s.last)
         noise = self._draws(n_draws, shape, dev)       # full batch, in the reference's draw order
         P = noise.shape[2]
@@ -288,6 +346,28 @@ class D3DP(nn.Module):
                                                noise[:, b0:b1].contiguous(), steps, n_draws, flip))
             return torch.cat(outs, dim=0)
         return self._sample_chunk(lib, inputs_2d, input_2d_flip, noise, steps, n_draws, flip)
+
+    def _ddim_sample_seeded(self, lib, inputs_2d, input_2d_flip, steps, flip):
+        """ddim_sample with noise = 'device': no noise tensor exists; every library call gets the 16 bytes {noise_seed,
+        noise_call, b0, p0} that place its clips and hypotheses in the stream."""
+        from .ops import noise_key
+        if self.noise_fn is not None:
+            raise ValueError("noise = 'device' draws inside the kernels: it cannot be combined with noise_fn")
+        dev, B = inputs_2d.device, inputs_2d.shape[0]
+        lo, hi = self.proposal_shard if self.proposal_shard is not None else (0, self.num_proposals)
+        P, call = hi - lo, self.noise_call
+        if not (0 <= lo < hi <= self.num_proposals):
+            raise ValueError(f"proposal_shard {(lo, hi)} is not a non-empty range of the {self.num_proposals} hypotheses")
+        if B == 0:
+            out = torch.zeros((0, len(steps), P, self.frames, self.num_kps, 3), device=dev, dtype=torch.float32)
+        else:
+            bc = self.clips_per_launch(P, flip)
+            outs = [self._sample_chunk(lib, inputs_2d[b0:b0 + bc], input_2d_flip[b0:b0 + bc] if flip else None, None, steps, 0,
+                                       flip, key4=noise_key(self._noise_seed, call, b0, lo, dev), P=P)
+                    for b0 in range(0, B, bc)]
+            out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        self.advance_noise_call()
+        return out
 
     def _aux_for(self, dev):
         """Side streams on `dev` (replicas made by nn.DataParallel share this module's attributes, so never hand a
@@ -307,9 +387,17 @@ class D3DP(nn.Module):
             self._aux_by_device[dev.index] = have[:self.n_aux_streams]
         return self._aux_by_device[dev.index]
 
-    def _sample_chunk(self, lib, inputs_2d, input_2d_flip, noise, steps, n_draws, flip):
+    def _sample_chunk(self, lib, inputs_2d, input_2d_flip, noise, steps, n_draws, flip, key4=None, P=None):
+        """One library call.  Either `noise` [n_draws,B,P,F,J,3] (pafuse_d3dp_sample) or, for the 'device' noise source, `key4`
+        (ops.noise_key: int32[4] on the device) and P (pafuse_d3dp_sample_seeded).  The key takes the place of the noise stack in
+        everything below: the buffer the launch reads and, under use_graph, the static buffer refreshed before a replay."""
         dev = inputs_2d.device
-        B, P = inputs_2d.shape[0], noise.shape[2]
+        seeded = key4 is not None
+        if seeded:
+            noise = key4
+        else:
+            P = noise.shape[2]
+        B = inputs_2d.shape[0]
         x2d = inputs_2d.contiguous().float()
         x2f = input_2d_flip.contiguous().float() if flip else x2d
         cfg = self.config_struct(flip)
@@ -325,6 +413,11 @@ class D3DP(nn.Module):
                 s.wait_stream(stream_)
             aux_arr = (C.c_void_p * max(1, len(aux)))(*[s.cuda_stream for s in aux])
             with torch.cuda.device(dev):
+                if seeded:               # noise_ is the 16-byte key
+                    _lib.check(lib.pafuse_d3dp_sample_seeded(C.byref(cfg), steps, len(steps), x2d_.data_ptr(), x2f_.data_ptr(),
+                                                             noise_.data_ptr(), B, P, out_.data_ptr(), ws_.data_ptr(),
+                                                             nbytes, stream_.cuda_stream, aux_arr, len(aux)))
+                    return
                 _lib.check(lib.pafuse_d3dp_sample(C.byref(cfg), steps, len(steps), x2d_.data_ptr(), x2f_.data_ptr(),
                                                   noise_.data_ptr(), n_draws, B, P, out_.data_ptr(), ws_.data_ptr(),
                                                   nbytes, stream_.cuda_stream, aux_arr, len(aux)))
@@ -339,8 +432,8 @@ class D3DP(nn.Module):
             weights_key = (tuple(cfg.part[i].patch_w for i in range(cfg.num_parts)),
                            tuple((cfg.part[i].operand_bf16, m.split_generation.get(dev.index, 0))
                                  for i, m in enumerate(self.denoisers().values())))
-            key = shape_key + weights_key
-            for k in [k for k in self._graphs if k[:6] == shape_key and k != key]:
+            key = shape_key + weights_key + ("device" if seeded else "torch",)      # (a seeded capture holds other launches)
+            for k in [k for k in self._graphs if k[:6] == shape_key and k[-1] == key[-1] and k != key]:
                 del self._graphs[k]
             g = self._graphs.get(key)
             if g is None:

@@ -65,7 +65,7 @@ def wb_pose_from_parts(pose, dataset):
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
-    Returns a CPU tensor [clips, T, P, F, J, 3]."""
+    Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``)."""
     dev = next(model.parameters()).device
     seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
     x2d = cut_clips(seq_2d, model.frames).to(dev)
@@ -152,6 +152,8 @@ def evaluate_sequence(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, 
     the multiplier total - add them over sequences and report ``sums[k] / n * 1000`` mm, like :func:`report`.
     ``p2=True`` adds the four Protocol #2 accumulators (ACCUMULATORS_P2, the reference's ``ft2d.p2``).
     With torch.distributed initialised the hypothesis axis is sharded and gathered (pafuse_amd.parallel).
+    The model is taken as it is configured: with ``model.noise = "device"`` (and a ``noise_seed``) the hypotheses come from the
+    library's counter-based stream, the same for every world size, batch size and hypothesis chunk, and no noise is allocated.
 
     ``gather="hypotheses"`` (default): every rank receives all P hypotheses and evaluates them in one kernel.
     ``gather="partials"``: every rank reduces its own hypotheses to partial reductions and the ranks exchange those

@@ -667,6 +667,37 @@ def procrustes_errors(pred, gt, x2d, traj, cam, conn, pick=True):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ noise stream v1
+def noise_key(seed, call, b0=0, p0=0, device="cuda"):
+    """The 16-byte device buffer {seed, call, b0, p0} the seeded kernels read (four uint32 behind an int32 tensor: torch
+    has no arithmetic on uint32 and none is needed).  seed and call in [0, 2^32); b0 / p0: global index of the first
+    clip / first hypothesis of the call."""
+    import numpy as np
+    for name, v in (("seed", seed), ("call", call), ("b0", b0), ("p0", p0)):
+        _need(0 <= int(v) < 2 ** 32, f"noise_key: {name} = {v} is not in [0, 2^32)")
+    words = np.array([int(seed), int(call), int(b0), int(p0)], dtype=np.uint32).view(np.int32)
+    return torch.from_numpy(words).to(device)
+
+
+def noise_fill(key, draw, B, P, F, J, out=None):
+    """Draw `draw` of noise stream v1 (pafuse_noise_fill; DESIGN.md section 6, host statement pafuse_amd.noise.reference_draw)
+    for clips [b0, b0 + B) and hypotheses [p0, p0 + P): key = noise_key(seed, call, b0, p0) -> float32 [B,P,F,J,3] on the
+    key's device."""
+    lib = _lib.load()
+    _need(torch.is_tensor(key) and key.is_cuda and key.dtype == torch.int32 and key.numel() == 4 and key.is_contiguous(),
+          "noise_fill: key must be the int32[4] device tensor of noise_key (no CPU fallback)")
+    draw, B, P, F, J = (int(v) for v in (draw, B, P, F, J))
+    _need(draw >= 0 and min(B, P, F, J) > 0 and F * J < 2 ** 32 and B * P * F * J < 2 ** 31 * 256,
+          f"noise_fill: bad size (draw={draw} B={B} P={P} F={F} J={J})")
+    if out is None:
+        out = torch.empty(B, P, F, J, 3, device=key.device, dtype=torch.float32)
+    _need(out.is_cuda and out.device == key.device and out.dtype == torch.float32 and out.is_contiguous()
+          and tuple(out.shape) == (B, P, F, J, 3), "noise_fill: out must be a contiguous float32 [B,P,F,J,3] on the key's device")
+    with torch.cuda.device(key.device):
+        _lib.check(lib.pafuse_noise_fill(key.data_ptr(), draw, B, P, F, J, out.data_ptr(), _stream(key)))
+    return out
+
+
 # ------------------------------------------------------------------------------------ sharded hypothesis evaluation
 PARTIALS_HEAD_BYTES_PER_ELEMENT = 40   # double sum[3] + float jbest, e2, sel3 + int32 idx per (b, t, f, j)
 

@@ -3,8 +3,11 @@
 DDIM trajectories are independent per hypothesis (nothing in common/diffusionpose.py:192-316 or
 common/mixste.py reduces over P), so rank r owns hypotheses [lo, hi) for all clips and all steps, weights are
 replicated, and the only exchange is ONE all-gather of the per-rank predictions before the aggregation
-protocols (J-Agg & co.) - 8.7 MB per rank at P_local=20, T=10, B=1.  Every rank draws the full-P noise tensor
-from the same seed and keeps its slice, so the sharded run reproduces the single-GPU hypotheses.
+protocols (J-Agg & co.) - 8.7 MB per rank at P_local=20, T=10, B=1.  With the model's default noise source
+('torch') every rank draws the full-P noise tensor from the same seed and keeps its slice, so the sharded run reproduces
+the single-GPU hypotheses - at the price of the full-P noise on every rank.  With ``model.noise = "device"`` a rank's
+kernels generate exactly its own hypotheses of the stream (pafuse_amd/noise.py): nothing is drawn and thrown away, and
+the hypotheses of a (noise_seed, noise_call) are the same for every world size and every chunking.
 
 Evaluation does not need the hypotheses themselves on every rank: ``ShardedSampler.sample_local`` /
 ``sample_chunks`` hand out the local ones, and ``pafuse_amd.evaluate.evaluate_accumulators_sharded`` exchanges their
@@ -89,9 +92,11 @@ class ShardedSampler:
 
     def sample_local(self, input_2d, input_3d, input_2d_flip=None, lo=None, hi=None):
         """This rank's hypotheses WITHOUT the gather -> (pred_local [B,T,P_r,F,J,3], h0, P_r).  `lo`, `hi` (global
-        indices inside local_range()) narrow the call to a part of them.  The model draws the full-P noise and keeps
-        the slice, so the values are those of the unsharded run provided the generator stands where that run would
-        find it (sample_chunks sees to that between chunks)."""
+        indices inside local_range()) narrow the call to a part of them.  Noise source 'torch': the model draws the
+        full-P noise and keeps the slice, so the values are those of the unsharded run provided the generator stands
+        where that run would find it (sample_chunks sees to that between chunks).  Noise source 'device': the values are
+        those of the unsharded run of the same (noise_seed, noise_call); a call of its own advances noise_call once, on
+        every rank, the ranks without a hypothesis included."""
         m = self.model
         a, b = self.local_range()
         lo, hi = a if lo is None else int(lo), b if hi is None else int(hi)
@@ -99,6 +104,8 @@ class ShardedSampler:
             raise ValueError(f"hypotheses [{lo}, {hi}) are not inside this rank's [{a}, {b})")
         if hi == lo:      # nothing to sample (a rank beyond the P-th when P < world): no model call, an empty tensor of the right shape
             T = len(m.ddim_steps())
+            if getattr(m, "noise", "torch") == "device":
+                m.advance_noise_call()
             return input_2d.new_zeros((input_2d.shape[0], T, 0, m.frames, m.num_kps, 3), dtype=torch.float32), lo, 0
         m.proposal_shard = (lo, hi)
         try:
@@ -111,22 +118,42 @@ class ShardedSampler:
         """Generator over this rank's hypotheses in chunks of at most `chunk` (None: all at once), ascending:
         yields (pred_chunk, h0, P_c).  Every chunk's call starts from the same state of the device's random generator,
         so each draws the full-P noise of the unsharded run and keeps its own slice; after the last chunk the generator
-        stands where one unsharded call leaves it.  Peak memory follows the chunk, not P."""
+        stands where one unsharded call leaves it.  The workspace and the predictions follow the chunk, not P; the noise
+        does not: every chunk draws and stacks the full-P tensor of every draw.
+        With ``model.noise = "device"`` there is no generator to rewind and no noise tensor: all chunks run under one
+        noise_call, which advances once after the last chunk (identically on every rank, whatever its share), and peak
+        memory does follow the chunk."""
         if chunk is not None and int(chunk) < 1:
             raise ValueError(f"hypothesis chunk must be a positive count, got {chunk}")
         a, b = self.local_range()
         step = max(b - a, 1) if chunk is None else int(chunk)
         dev = input_2d.device
-        rng = torch.cuda.get_rng_state(dev) if (input_2d.is_cuda and b - a > step) else None
+        m = self.model
+        seeded = getattr(m, "noise", "torch") == "device"
+        rng = torch.cuda.get_rng_state(dev) if (input_2d.is_cuda and b - a > step and not seeded) else None
+        if seeded:
+            held, call = m._hold_noise_call, m.noise_call        # the chunks are ONE logical call: one noise_call for all
         lo = a
-        while True:
-            hi = min(b, lo + step)
-            if rng is not None and lo > a:
-                torch.cuda.set_rng_state(rng, dev)
-            yield self.sample_local(input_2d, input_3d, input_2d_flip, lo, hi)
-            lo = hi
-            if lo >= b:
-                return
+        try:
+            while True:
+                hi = min(b, lo + step)
+                if rng is not None and lo > a:
+                    torch.cuda.set_rng_state(rng, dev)
+                if seeded:
+                    m._hold_noise_call, m.noise_call = True, call
+                try:
+                    item = self.sample_local(input_2d, input_3d, input_2d_flip, lo, hi)
+                finally:
+                    if seeded:
+                        m._hold_noise_call = held                # (not while the consumer runs between two chunks)
+                yield item
+                lo = hi
+                if lo >= b:
+                    return
+        finally:
+            if seeded:
+                m._hold_noise_call, m.noise_call = held, call
+                m.advance_noise_call()
 
     def __call__(self, input_2d, input_3d, input_2d_flip=None):
         m = self.model

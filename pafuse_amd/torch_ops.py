@@ -11,6 +11,7 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::ddim_loop(..., precision)                        D3DP.ddim_sample[_flip]        common/diffusionpose.py:227-316
   pafuse::hypothesis_partials(pred, gt, x2d, traj, cam, conn, pbroot, part, num_parts, h0)   one shard's partial reductions
   pafuse::combine_partials(states, gt, conn, pbroot, T, num_proposals)   jbest, pagg, jagg, paggpb from W states   main_h3wb.py:327-362
+  pafuse::noise_fill(key, draw, B, P, F, J)               one draw of noise stream v1 as a tensor (DESIGN.md section 6)
 
 ``precision`` ('bf16x3' = the modules' default; 'bf16x3_images', 'f16x2', 'f32', 'bf16': pafuse_amd.D3DP.precision) is the
 matrix-product mode of the linear layers; in the split modes the ops build and cache the pre-split weight images themselves (cached_split_image).
@@ -398,6 +399,19 @@ def combine_partials(states: torch.Tensor, gt: torch.Tensor, conn: torch.Tensor,
 def _(states, gt, conn, pbroot, T, num_proposals):
     B, F, J, _ = gt.shape
     return [gt.new_empty(B, T, F, J) for _ in range(4)]
+
+
+# ----------------------------------------------------------------------------------------------- noise stream v1
+@torch.library.custom_op("pafuse::noise_fill", mutates_args=(), device_types="cuda")
+def noise_fill(key: torch.Tensor, draw: int, B: int, P: int, F: int, J: int) -> torch.Tensor:
+    """pafuse_amd.ops.noise_fill: draw `draw` of noise stream v1 under key = ops.noise_key(seed, call, b0, p0) -> [B,P,F,J,3]."""
+    from . import ops
+    return ops.noise_fill(key, draw, B, P, F, J)
+
+
+@noise_fill.register_fake
+def _(key, draw, B, P, F, J):
+    return key.new_empty((B, P, F, J, 3), dtype=torch.float32)
 
 
 def ddim_loop_args(model):
