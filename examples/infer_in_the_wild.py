@@ -8,7 +8,9 @@ sampling on the HIP path with ``input_3d=None`` -> whole-body poses stitched bac
            ft2d.num_proposals=20 ft2d.sampling_timesteps=10
 
 Writes <out>/test_3d_output.npy [T,P,frames,134,3] (camera space) and <out>/test_3d_output_postprocess.npy (rotated
-with the reference's fixed camera orientation, lowest point at height 0).  Without --keypoints a synthetic detection
+with the reference's fixed camera orientation, lowest point at height 0).  With --aggregate mean the hypotheses are
+averaged on the device (P-Agg, the mean whole-body pose; --hypothesis-chunk n samples and reduces them n at a time, so
+peak memory follows n instead of P) and both files hold [T,frames,134,3]: one pose per frame.  Without --keypoints a synthetic detection
 file is generated (random weights unless --checkpoint: numbers are meaningless).
 """
 import argparse
@@ -41,8 +43,15 @@ def main():
                     help="where the loop's normals come from: torch.randn on the full tensor, or the library's counter-based "
                          "stream drawn inside the kernels (no noise tensor; other hypotheses than torch.randn's)")
     ap.add_argument("--seed", type=int, default=0, help="with --noise device: the seed of the stream, in [0, 2^32)")
+    ap.add_argument("--aggregate", choices=("none", "mean"), default="none",
+                    help="none: write all P hypotheses; mean: one pose per frame, the mean over the hypotheses, reduced on the "
+                         "device (only the aggregate is copied to the host)")
+    ap.add_argument("--hypothesis-chunk", type=int, default=None,
+                    help="with --aggregate mean: sample and reduce the hypotheses this many at a time")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.hypothesis_chunk is not None and a.aggregate == "none":
+        ap.error("--hypothesis-chunk needs --aggregate mean")
     args = config.load(None, a.overrides)
     os.makedirs(a.out, exist_ok=True)
     ge.build()
@@ -67,8 +76,13 @@ def main():
 
     pixels = harness.load_pifpaf_keypoints(a.keypoints, args.data.num_kps)
     keypoints = h3wb.normalize_screen_coordinates(pixels[..., :2], w=a.width, h=a.height).astype(np.float32)
-    pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch)
-    poses = harness.stitch_clips(pred, keypoints.shape[0], model.frames)            # [T,P,frames,134,3]
+    if a.aggregate == "mean":
+        pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
+                                      hypothesis_chunk=a.hypothesis_chunk)
+        poses = harness.stitch_poses(pred, keypoints.shape[0], model.frames)        # [T,frames,134,3]
+    else:
+        pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch)
+        poses = harness.stitch_clips(pred, keypoints.shape[0], model.frames)        # [T,P,frames,134,3]
     np.save(os.path.join(a.out, "test_3d_output.npy"), poses.numpy(), allow_pickle=True)
     world = harness.camera_to_world(poses, CAMERA_ROTATION)
     world[..., 2] -= world[..., 2].min()                                            # no trajectory: rebase the height

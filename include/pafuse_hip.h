@@ -26,6 +26,7 @@
  *                            (common/diffusionpose.py:165-171,211-218), epsilon in fp64 (:157-161,222-223), update (:302-312)
  *   pafuse_hypothesis_errors the per-joint part of evaluate()'s aggregation, main_h3wb.py:327-362
  *   pafuse_hypothesis_partials / _combine  the same from per-shard partial reductions (sharded or chunked P)
+ *   pafuse_pose_partials / _combine  the P-Agg / J-Agg aggregates as poses, from shards or chunks of P (no ground truth)
  *   pafuse_procrustes_errors the Protocol #2 part of it (ft2d.p2), main_h3wb.py:381-395, common/loss.py:251-458
  *   pafuse_mixste2_train_*   MixSTE2.forward (is_train=True) + autograd backward, common/mixste.py:215-225,260-298
  *   pafuse_d3dp_qsample      D3DP.prepare_diffusion_concat / q_sample, common/diffusionpose.py:319-326,358-374
@@ -542,6 +543,35 @@ int pafuse_hypothesis_partials(const float *pred, const float *gt, const float *
 int pafuse_hypothesis_combine(const void *states, int32_t W, size_t stride_bytes, const float *gt, const int32_t *conn,
                               const int32_t *pbroot, int32_t B, int32_t T, int32_t F, int32_t J, int32_t P_total,
                               void *merged, float *jbest, float *pagg, float *jagg, float *paggpb, void *stream);
+
+/* The aggregates as poses, from the same shards: P-Agg (the mean over the hypotheses of the whole-body pose) and J-Agg
+ * (per joint, the whole-body joint of the hypothesis whose 2-D reprojection is closest to the input).  No ground truth.
+ * pred [B,T,P_r,F,J,3] holds the part-centred hypotheses [h0, h0 + P_r) of the run; x2d [B,F,J,2], traj [B,F,3], cam [9],
+ * conn int32 [J] as above.  x2d, traj and cam all NULL: mean-only (in the wild there is no camera and no trajectory) -
+ * the reprojection is skipped and every candidate stays neutral.
+ * State, one flat 8-byte aligned buffer of pafuse_pose_partials_bytes = 44*n rounded up to 8 bytes, n = B*T*F*J:
+ *   double sum[n][3]    sum over the local h, in h order, of the whole-body joint (one fp32 add of the connection joint,
+ *                       joint 0 pinned at 0)
+ *   float  e2[n]; int32 idx[n]; float sel[n][3]   the J-Agg candidate: smallest reprojection error (the fp32 expression of
+ *                       pafuse_hypothesis_errors, so the index is the one every evaluation entry picks), its GLOBAL
+ *                       hypothesis index h0 + h, its whole-body joint; first minimum wins; (+inf, -1, NaN NaN NaN) where
+ *                       no e2 of the shard is finite
+ * Nothing depends on P_r: W ranks exchange their states with one all-gather.  One kernel, no workspace, no atomics,
+ * bit-reproducible.  B == 0 or P_r == 0: no kernel runs, the state is the neutral one (zero sums, no candidate).
+ * Refused (PAFUSE_E_ARG): a null operand, negative sizes or h0, some but not all of x2d / traj / cam, a short state. */
+size_t pafuse_pose_partials_bytes(int32_t B, int32_t T, int32_t F, int32_t J);
+int pafuse_pose_partials(const float *pred, const float *x2d, const float *traj, const float *cam, const int32_t *conn,
+                         int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t h0, void *state,
+                         size_t state_bytes, void *stream);
+
+/* Combines W such states, `stride_bytes` apart and in ascending-h0 order: sums added in shard order, the candidate with
+ * the smallest e2 and, among equal ones, the lowest global index.  Writes any of (NULL: not wanted, at least one):
+ *   merged    the state of the union; of the operands it may only lie over the FIRST (a running state over chunks)
+ *   mean      [B,T,F,J,3] fp32 = sum / P_total, divided in fp64 and rounded once
+ *   pick      [B,T,F,J,3] fp32 the J-Agg pose (NaN where no state holds a candidate)
+ *   pick_idx  [B,T,F,J] int32 its hypothesis (-1 where none) */
+int pafuse_pose_combine(const void *states, int32_t W, size_t stride_bytes, int32_t B, int32_t T, int32_t F, int32_t J,
+                        int32_t P_total, void *merged, float *mean, float *pick, int32_t *pick_idx, void *stream);
 
 /* Protocol #2 (P-MPJPE) on the same operands - common/loss.py:251-458 as main_h3wb.py:381-395 calls it: every
  * whole-body hypothesis pose (and, per (b,t,f), the mean over h of them) aligned to its whole-body target by the

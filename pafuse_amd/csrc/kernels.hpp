@@ -2869,6 +2869,140 @@ __global__ void __launch_bounds__(256) combine_kernel(const CombineParams p) {
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// The aggregates as POSES (no ground truth anywhere): P-Agg, the mean over h of the whole-body pose, and J-Agg, per
+// joint the whole-body joint of the hypothesis whose 2-D reprojection is closest to the input.  Same shard / chunk
+// scheme as above: pose_partials_kernel reduces hypotheses [h0, h0 + P_r) to a state whose size does not depend on P,
+// pose_combine_kernel merges W states in ascending-h0 order and / or writes the poses.
+//
+// State, one flat buffer (n = B*T*F*J), 44*n bytes rounded up to a multiple of 8:
+//   double sum[n][3] | float e2[n] | int32 idx[n] | float sel[n][3]
+// sum: fp64 sum over the local h, in h order, of wb_joint; (e2, idx, sel): smallest reprojection error, its GLOBAL
+// hypothesis index, its whole-body joint - the first minimum wins; (+inf, -1, NaN NaN NaN) where no e2 is finite.
+// e2 is metrics_kernel's expression (same operations, same order), so the index is the one partials_kernel and
+// procrustes_kernel pick.  x2d == null (then traj and cam are null too): mean-only, every candidate stays neutral.
+//
+// pose_partials_kernel: one thread per (b, t, f, j) walks the local h; consecutive lanes read consecutive 12-byte
+// joints of one pose (every byte of a fetched line is used; the connection joint is a line of the same pose).  No
+// LDS, no atomics, no scratch.
+// ----------------------------------------------------------------------------------------------------------------
+struct PosePartialsParams {
+    const float* pred;  // [B,T,P_r,F,J,3] this shard's part-centred predictions
+    const float* x2d;   // [B,F,J,2] or null (mean-only)
+    const float* traj;  // [B,F,3]   or null
+    const float* cam;   // [9]       or null
+    const int32_t* conn;  // [J]
+    double* sum;        // state (see above)
+    float* e2;
+    int32_t* idx;
+    float* sel;
+    int B, T, P, F, J, h0;
+};
+
+__global__ void __launch_bounds__(256, 8) pose_partials_kernel(const PosePartialsParams p) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t total = (int64_t)p.B * p.T * p.F * p.J;
+    if (e >= total) return;
+    const int j = (int)(e % p.J);
+    const int f = (int)((e / p.J) % p.F);
+    const int t = (int)((e / ((int64_t)p.J * p.F)) % p.T);
+    const int b = (int)(e / ((int64_t)p.J * p.F * p.T));
+    const float* pose0 = p.pred + ((((int64_t)b * p.T + t) * p.P) * p.F + f) * p.J * 3;
+    const int64_t hstride = (int64_t)p.F * p.J * 3;
+    const float qnan = __builtin_nanf("");
+    float best2 = INFINITY, sel[3] = {qnan, qnan, qnan};
+    int32_t hsel = -1;
+    double sm[3] = {0.0, 0.0, 0.0};
+    if (p.x2d) {
+        const float* tr = p.traj + ((int64_t)b * p.F + f) * 3;
+        const float* x2 = p.x2d + (((int64_t)b * p.F + f) * p.J + j) * 2;
+        const float fx = p.cam[0], fy = p.cam[1], cx = p.cam[2], cy = p.cam[3];
+        const float k1 = p.cam[4], k2 = p.cam[5], k3 = p.cam[6], p1 = p.cam[7], p2 = p.cam[8];
+#pragma unroll 4
+        for (int h = 0; h < p.P; ++h) {
+            float w[3];
+            wb_joint(pose0 + h * hstride, p.conn, j, w);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sm[k] += (double)w[k];
+            // 2-D reprojection of the absolute pose (common/camera.py:30-60), as metrics_kernel states it
+            const float X = w[0] + tr[0], Y = w[1] + tr[1], Z = w[2] + tr[2];
+            const float xx = fminf(fmaxf(X / Z, -1.f), 1.f), yy = fminf(fmaxf(Y / Z, -1.f), 1.f);
+            const float r2 = xx * xx + yy * yy;
+            const float radial = 1.f + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2));
+            const float tan = p1 * xx + p2 * yy;
+            const float u = fx * (xx * (radial + tan) + p1 * r2) + cx, v = fy * (yy * (radial + tan) + p2 * r2) + cy;
+            const float q0 = u - x2[0], q1 = v - x2[1];
+            const float e2 = sqrtf(q0 * q0 + q1 * q1);
+            if (e2 < best2) best2 = e2, hsel = p.h0 + h, sel[0] = w[0], sel[1] = w[1], sel[2] = w[2];  // first minimum wins
+        }
+    } else {
+#pragma unroll 4
+        for (int h = 0; h < p.P; ++h) {
+            float w[3];
+            wb_joint(pose0 + h * hstride, p.conn, j, w);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sm[k] += (double)w[k];
+        }
+    }
+    p.sum[e * 3 + 0] = sm[0], p.sum[e * 3 + 1] = sm[1], p.sum[e * 3 + 2] = sm[2];
+    p.e2[e] = best2;
+    p.idx[e] = hsel;
+    p.sel[e * 3 + 0] = sel[0], p.sel[e * 3 + 1] = sel[1], p.sel[e * 3 + 2] = sel[2];
+}
+
+struct PoseCombineParams {
+    const char* states;   // W states, `stride` bytes apart, in ascending-h0 order
+    int64_t stride;
+    int W;
+    double* m_sum;        // merged state (null: not wanted); may be the first operand
+    float* m_e2;
+    int32_t* m_idx;
+    float* m_sel;
+    float* mean;          // [B,T,F,J,3] (null: not wanted)
+    float* pick;          // [B,T,F,J,3] (null: not wanted)
+    int32_t* pick_idx;    // [B,T,F,J]   (null: not wanted)
+    int64_t n;            // B*T*F*J
+    int P;                // the TOTAL hypothesis count the mean divides by
+};
+
+// one thread per (b, t, f, j): it reads its own element of every state before it writes anything, so the merged state
+// may lie over the first operand
+__global__ void __launch_bounds__(256) pose_combine_kernel(const PoseCombineParams p) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = p.n;
+    if (e >= n) return;
+    const float qnan = __builtin_nanf("");
+    float best2 = INFINITY, sel[3] = {qnan, qnan, qnan};
+    int32_t hsel = -1;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int w = 0; w < p.W; ++w) {
+        const char* st = p.states + (int64_t)w * p.stride;
+        const double* sum = (const double*)st;
+        const float* e2 = (const float*)(st + n * 24);
+        const int32_t* ix = (const int32_t*)(e2 + n);
+        const float* sl = (const float*)(ix + n);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s[k] += sum[e * 3 + k];
+        const int32_t hw = ix[e];
+        const float ew = e2[e];
+        // the overall first minimum: the smallest e2, the lowest global index among equal ones
+        if (hw >= 0 && (hsel < 0 || ew < best2 || (ew == best2 && hw < hsel)))
+            best2 = ew, hsel = hw, sel[0] = sl[e * 3 + 0], sel[1] = sl[e * 3 + 1], sel[2] = sl[e * 3 + 2];
+    }
+    if (p.m_sum) {
+        p.m_sum[e * 3 + 0] = s[0], p.m_sum[e * 3 + 1] = s[1], p.m_sum[e * 3 + 2] = s[2];
+        p.m_e2[e] = best2;
+        p.m_idx[e] = hsel;
+        p.m_sel[e * 3 + 0] = sel[0], p.m_sel[e * 3 + 1] = sel[1], p.m_sel[e * 3 + 2] = sel[2];
+    }
+    if (p.mean) {
+        const double P = (double)p.P;   // divided in fp64, rounded once
+        p.mean[e * 3 + 0] = (float)(s[0] / P), p.mean[e * 3 + 1] = (float)(s[1] / P), p.mean[e * 3 + 2] = (float)(s[2] / P);
+    }
+    if (p.pick) p.pick[e * 3 + 0] = sel[0], p.pick[e * 3 + 1] = sel[1], p.pick[e * 3 + 2] = sel[2];
+    if (p.pick_idx) p.pick_idx[e] = hsel;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // Protocol #2 (P-MPJPE) behind the all-gather: common/loss.py:251-458 as main_h3wb.py:381-395 calls it on the
 // whole-body poses.  Every hypothesis pose Y is aligned to its target X by the similarity transform of the
 // reference (centre both, H = (X0/|X0|)^T (Y0/|Y0|), R = V U^T with the reflection fix, a = tr(S') |X0| / |Y0|) and

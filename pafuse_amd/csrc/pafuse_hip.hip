@@ -1884,6 +1884,78 @@ int pafuse_hypothesis_combine(const void* states, int32_t W, size_t stride_bytes
     return check_launch("combine_kernel");
 }
 
+// state of pafuse_pose_partials: double sum[n][3] | float e2[n] | int32 idx[n] | float sel[n][3], rounded up to 8 bytes
+size_t pafuse_pose_partials_bytes(int32_t B, int32_t T, int32_t F, int32_t J) {
+    if (B < 0 || T <= 0 || F <= 0 || J <= 0) return 0;
+    return ((size_t)B * T * F * J * 44 + 7) / 8 * 8;
+}
+
+int pafuse_pose_partials(const float* pred, const float* x2d, const float* traj, const float* cam, const int32_t* conn,
+                         int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t h0, void* state, size_t state_bytes,
+                         void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (B < 0 || T <= 0 || P_r < 0 || F <= 0 || J <= 0 || h0 < 0) return fail(PAFUSE_E_ARG, "pose_partials: bad size");
+    const int given = (x2d ? 1 : 0) + (traj ? 1 : 0) + (cam ? 1 : 0);
+    if (given != 0 && given != 3)
+        return fail(PAFUSE_E_ARG, "pose_partials: x2d, traj and cam come together (all null: mean-only)");
+    const size_t need = pafuse_pose_partials_bytes(B, T, F, J);
+    if (need && (!state || state_bytes < need)) return fail(PAFUSE_E_ARG, "pose_partials: the state needs %zu bytes", need);
+    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "pose_partials: the state must be 8-byte aligned");
+    const int64_t n = (int64_t)B * T * F * J;
+    char* st = (char*)state;
+    double* sum = (double*)st;
+    float* e2 = (float*)(st + n * 24);
+    int32_t* idx = (int32_t*)(e2 + n);
+    float* sel = (float*)(idx + n);
+    hipStream_t s = (hipStream_t)stream;
+    if (B == 0 || P_r == 0) {   // the neutral state: zero sums, no candidate (+inf, -1, NaN NaN NaN); no kernel runs
+        hipError_t e = hipSuccess;
+        if (n) {
+            e = hipMemsetAsync(sum, 0, (size_t)n * 24, s);
+            if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)e2, 0x7f800000, (size_t)n, s);
+            if (e == hipSuccess) e = hipMemsetAsync(idx, 0xff, (size_t)n * 4, s);
+            if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)sel, 0x7fc00000, (size_t)n * 3, s);
+        }
+        if (e != hipSuccess) return fail(PAFUSE_E_HIP, "pose_partials: %s", hipGetErrorString(e));
+        return PAFUSE_OK;
+    }
+    if (!pred || !conn) return fail(PAFUSE_E_ARG, "pose_partials: null pointer");
+    if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "pose_partials: grid out of range");
+    PosePartialsParams m{};
+    m.pred = pred, m.x2d = x2d, m.traj = traj, m.cam = cam, m.conn = conn;
+    m.sum = sum, m.e2 = e2, m.idx = idx, m.sel = sel;
+    m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0;
+    hipLaunchKernelGGL(pose_partials_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m);
+    return check_launch("pose_partials_kernel");
+}
+
+int pafuse_pose_combine(const void* states, int32_t W, size_t stride_bytes, int32_t B, int32_t T, int32_t F, int32_t J,
+                        int32_t P_total, void* merged, float* mean, float* pick, int32_t* pick_idx, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (B < 0 || T <= 0 || F <= 0 || J <= 0 || W < 1) return fail(PAFUSE_E_ARG, "pose_combine: bad size");
+    if (!merged && !mean && !pick && !pick_idx) return fail(PAFUSE_E_ARG, "pose_combine: nothing to write");
+    if (mean && P_total < 1) return fail(PAFUSE_E_ARG, "pose_combine: P_total %d", P_total);
+    const int64_t n = (int64_t)B * T * F * J;
+    if (n == 0) return PAFUSE_OK;
+    if (!states) return fail(PAFUSE_E_ARG, "pose_combine: null pointer");
+    if (stride_bytes < (size_t)n * 44 || stride_bytes % 8 || (uintptr_t)states % 8 || (uintptr_t)merged % 8)
+        return fail(PAFUSE_E_ARG, "pose_combine: states are %lld bytes or more apart, 8-byte aligned", (long long)(n * 44));
+    const char* lo = (const char*)states;
+    const char* hi = lo + (size_t)(W - 1) * stride_bytes + n * 44;
+    if (merged && merged != states && (const char*)merged < hi && (const char*)merged + n * 44 > lo)
+        return fail(PAFUSE_E_ARG, "pose_combine: of its operands the merged state may only lie over the first");
+    if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "pose_combine: grid out of range");
+    PoseCombineParams c{};
+    c.states = lo, c.stride = (int64_t)stride_bytes, c.W = W;
+    if (merged) {
+        char* st = (char*)merged;
+        c.m_sum = (double*)st, c.m_e2 = (float*)(st + n * 24), c.m_idx = (int32_t*)(c.m_e2 + n), c.m_sel = (float*)(c.m_idx + n);
+    }
+    c.mean = mean, c.pick = pick, c.pick_idx = pick_idx, c.n = n, c.P = P_total;
+    hipLaunchKernelGGL(pose_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c);
+    return check_launch("pose_combine_kernel");
+}
+
 int pafuse_procrustes_errors(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,
                              const int32_t* conn, int32_t B, int32_t T, int32_t P, int32_t F, int32_t J, float* jbest,
                              double* pbest_sums, float* pagg, float* jagg, int32_t* pick, void* stream) {

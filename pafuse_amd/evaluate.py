@@ -11,6 +11,9 @@ reprojection, per-joint J-Best / P-Agg / J-Agg and the part-re-centred variants)
 hypothesis axis (a rank's, or a chunk on one device) is reduced to a small state (``ops.hypothesis_partials``), states
 are merged (``ops.combine_partials``), and ranks exchange states - not hypotheses - in one all-gather.  Protocol #1
 only: Protocol #2 needs the full tensor and keeps the gather of ``pafuse_amd.parallel.gather_hypotheses``.
+
+``accumulate_poses`` / ``aggregate_poses_sharded`` return the aggregates themselves - the P-Agg mean pose and the J-Agg
+pose with its hypothesis index - by the same scheme and without a ground truth (``ops.pose_partials``, ``ops.combine_poses``).
 """
 import torch
 import torch.distributed as dist
@@ -239,3 +242,111 @@ def evaluate_accumulators_sharded(pred_local, h0, num_proposals, gt_parts, input
         out["p_best_pb_" + part] = ph.gather(1, best.view(-1, 1)).squeeze(1)
         out["p_agg_pb_" + part] = per_t(paggpb[..., idx])
     return out
+
+
+# ------------------------------------------------------------------------------------------- aggregates as poses
+class PoseState:
+    """The running pose reduction of the hypotheses one rank has seen so far: 44 bytes per (b,t,f,j) (ops.pose_views),
+    independent of how many hypotheses went in.  `reproj`: the chunks came with 2-D input, trajectory and camera, so the
+    state holds J-Agg candidates; a mean-only state has none."""
+
+    def __init__(self, shape, device, reproj):
+        self.shape, self.device, self.reproj = tuple(shape), device, bool(reproj)    # shape = (B, T, F, J)
+        self.slots = None        # [2, L] float64: row 0 the running state, row 1 the newest chunk's
+        self.h0, self.count = None, 0
+
+    @property
+    def head(self):
+        return self.slots[0]
+
+
+def accumulate_poses(state, pred_local, h0, dataset, inputs_2d=None, traj=None, cam=None):
+    """Fold the part-centred hypotheses pred_local [B,T,P_c,F,J,3] = global [h0, h0 + P_c) into the pose state `state`
+    (None: start one) and return it.  inputs_2d [B,F,J,2], traj [B,F,3] (or [B,F,1,3]) and cam [9] together keep the J-Agg
+    candidate; none of them: mean-only.  Chunks come in ascending h0 without a gap.  Memory: the chunk and two 44-byte
+    per-(b,t,f,j) states - never anything of size P."""
+    from . import ops
+    if not pred_local.is_cuda:
+        raise _lib.PafuseError("accumulate_poses runs on the HIP device only (no CPU fallback)")
+    if pred_local.dim() != 6 or pred_local.shape[-1] != 3:
+        raise ValueError(f"pred_local must be [B,T,P_c,F,J,3], got {tuple(pred_local.shape)}")
+    dev = pred_local.device
+    B, T, P_c, F, J, _ = pred_local.shape
+    given = [t is not None for t in (inputs_2d, traj, cam)]
+    if any(given) and not all(given):
+        raise ValueError("accumulate_poses: inputs_2d, traj and cam come together (none of them: mean-only)")
+    reproj = all(given)
+    covered = sorted(j for idx in dataset.parts_joint_indices.values() for j in idx)
+    if covered != list(range(J)):
+        raise ValueError("dataset.parts_joint_indices must cover every joint exactly once")
+    conn, _ = _tables(dataset, J, dev)
+    x2d = tr = cm = None
+    if reproj:
+        if tuple(inputs_2d.shape) != (B, F, J, 2) or traj.numel() != B * F * 3 or cam.numel() < 9:
+            raise ValueError(f"accumulate_poses: operands do not match pred {tuple(pred_local.shape)}: 2d "
+                             f"{tuple(inputs_2d.shape)}, traj {tuple(traj.shape)}, cam {tuple(cam.shape)}")
+        if inputs_2d.device != dev or traj.device != dev:
+            raise ValueError("accumulate_poses: all tensors must live on the device of pred_local")
+        x2d, tr = inputs_2d.contiguous().float(), traj.reshape(B, F, 3).contiguous().float()
+        cm = cam.reshape(-1)[:9].contiguous().float().to(dev)
+    if state is None:
+        state = PoseState((B, T, F, J), dev, reproj)
+    if state.shape != (B, T, F, J) or state.device != dev:
+        raise ValueError(f"accumulate_poses: the state holds {state.shape}, the chunk is {(B, T, F, J)}")
+    if state.reproj != reproj:
+        raise ValueError("accumulate_poses: a state is either mean-only or keeps candidates, for all of its chunks")
+    if state.h0 is not None and int(h0) != state.h0 + state.count:
+        raise ValueError(f"accumulate_poses: chunk starts at hypothesis {h0}, the state ends at {state.h0 + state.count}")
+    first = state.slots is None
+    if first:
+        state.slots = torch.empty(2, ops.pose_partials_bytes(B, T, F, J) // 8, device=dev, dtype=torch.float64)
+    ops.pose_partials(pred_local.contiguous().float(), conn, int(h0), x2d, tr, cm, out=state.slots[0 if first else 1])
+    if not first:     # running state <- running state (+) this chunk, in place (every thread reads its element before it writes it)
+        ops.combine_poses(state.slots, (B, T, F, J), 1, merged=state.slots[0], want=())
+    if state.h0 is None:
+        state.h0 = int(h0)
+    state.count += P_c
+    return state
+
+
+def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=None, traj=None, cam=None, group=None,
+                            state=None, want=None):
+    """The aggregates as poses without ever holding all P hypotheses: pred_local [B,T,P_r,F,J,3] holds the part-centred
+    hypotheses [h0, h0 + P_r) of the `num_proposals` of the run - this rank's share (pafuse_amd.parallel.shard_range) or,
+    with `state`, the last chunk of it (`state`: what accumulate_poses returned for the chunks before; pred_local=None
+    aggregates the state as it is).  -> dict "mean" [B,T,F,J,3] (P-Agg, the mean whole-body pose) and, when the state
+    keeps candidates, "pick" [B,T,F,J,3] and "idx" [B,T,F,J] int32 (J-Agg: per joint the hypothesis whose reprojection is
+    closest to the 2-D input - the hypothesis the evaluation kernels pick).  `want`: a subset of those names.  With
+    torch.distributed initialised the ranks exchange their states in ONE all_gather_into_tensor (through the host on a
+    gloo group): 44 bytes per (b,t,f,j), whatever P is.  pick and idx do not depend on how the hypotheses are cut; the
+    mean adds the shards' fp64 sums in shard order."""
+    from . import ops
+    from .parallel import shard_range
+    if pred_local is not None:
+        state = accumulate_poses(state, pred_local, h0, dataset, inputs_2d, traj, cam)
+    if state is None:
+        raise ValueError("aggregate_poses_sharded: neither hypotheses nor a state")
+    if want is None:
+        want = ("mean", "pick", "idx") if state.reproj else ("mean",)
+    want = tuple(want)
+    if not state.reproj and ("pick" in want or "idx" in want):
+        raise ValueError("aggregate_poses_sharded: a mean-only state has no pick (give inputs_2d, traj and cam)")
+    P = int(num_proposals)
+    world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
+    if world == 1:
+        if state.h0 != 0 or state.count != P:
+            raise ValueError(f"the state holds hypotheses [{state.h0}, {state.h0 + state.count}) of {P}")
+        states = state.slots[:1]
+    else:
+        rank = dist.get_rank(group)
+        lo, hi = shard_range(P, rank, world)
+        if (state.h0, state.count) != (lo, hi - lo):
+            raise ValueError(f"rank {rank} of {world} owns hypotheses [{lo}, {hi}) of {P}, its state holds "
+                             f"[{state.h0}, {state.h0 + state.count})")
+        send = state.head
+        if dist.get_backend(group) == "gloo":             # rehearsal on a box with fewer GPUs than ranks
+            send = send.cpu()
+        recv = send.new_empty(world * send.numel())
+        dist.all_gather_into_tensor(recv, send.contiguous(), group=group)
+        states = recv.view(world, -1).to(state.device)
+    return ops.combine_poses(states.contiguous(), state.shape, P, want=want)

@@ -5,7 +5,8 @@ or Hydra here; the caller hands in arrays).
 """
 import torch
 
-from .evaluate import accumulate_partials, evaluate_accumulators, evaluate_accumulators_sharded
+from .evaluate import (accumulate_partials, accumulate_poses, aggregate_poses_sharded, evaluate_accumulators,
+                       evaluate_accumulators_sharded)
 from .parallel import ShardedSampler
 
 ACCUMULATORS = ("j_best", "p_best", "p_agg", "j_agg", "p_best_pb", "p_best_pb_body", "p_best_pb_face",
@@ -62,20 +63,57 @@ def wb_pose_from_parts(pose, dataset):
 
 
 @torch.no_grad()
-def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None):
+def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
+                   hypothesis_chunk=None):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
-    Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``)."""
+    Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
+
+    ``aggregate`` asks for ONE pose per frame instead of all P hypotheses, reduced on the device (evaluate.accumulate_poses /
+    aggregate_poses_sharded): every rank samples its hypotheses, ``hypothesis_chunk`` at a time when given, folds each chunk
+    into a 44-byte-per-(clip,t,f,j) state and drops it; the ranks exchange states, and only the aggregate crosses to the host.
+    ``"mean"`` (P-Agg): a CPU tensor [clips, T, F, J, 3], the mean whole-body pose.  ``"reproj"`` (J-Agg):
+    ``(pose [clips,T,F,J,3], idx [clips,T,F,J])``, per joint the hypothesis whose 2-D reprojection is closest to the input
+    and its index (NaN / -1 where no reprojection error is finite); it needs ``cam`` [9] intrinsics and ``traj`` [N,3], the
+    root position of every frame (cut into clips like the 2-D input)."""
+    if aggregate not in (None, "mean", "reproj"):
+        raise ValueError(f'aggregate must be None, "mean" or "reproj", got {aggregate!r}')
+    if hypothesis_chunk is not None and (aggregate is None or int(hypothesis_chunk) < 1):
+        raise ValueError("hypothesis_chunk is a positive count and needs an aggregate")
+    if aggregate == "reproj" and (cam is None or traj is None):
+        raise ValueError('aggregate="reproj" needs cam [9] and traj [N,3]')
     dev = next(model.parameters()).device
     seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
     x2d = cut_clips(seq_2d, model.frames).to(dev)
     x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), model.frames).to(dev)
     sampler = ShardedSampler(model, group)
-    outs = []
+    if aggregate is None:
+        outs = []
+        for lo in range(0, x2d.shape[0], batch_size):
+            pred = sampler(x2d[lo:lo + batch_size], None, input_2d_flip=x2d_flip[lo:lo + batch_size])
+            outs.append(wb_pose_from_parts(pred, dataset).cpu())
+        return torch.cat(outs)
+    reproj = aggregate == "reproj"
+    if reproj:
+        traj = torch.as_tensor(traj, dtype=torch.float32)
+        if traj.dim() != 2 or tuple(traj.shape) != (seq_2d.shape[-3], 3):
+            raise ValueError(f"traj must be [N,3] with N = {seq_2d.shape[-3]} frames, got {tuple(traj.shape)}")
+        traj = cut_clips(traj.unsqueeze(1), model.frames).squeeze(2).to(dev)          # [clips,F,3]
+        cam = torch.as_tensor(cam, dtype=torch.float32).to(dev)
+    poses, picks = [], []
     for lo in range(0, x2d.shape[0], batch_size):
-        pred = sampler(x2d[lo:lo + batch_size], None, input_2d_flip=x2d_flip[lo:lo + batch_size])
-        outs.append(wb_pose_from_parts(pred, dataset).cpu())
-    return torch.cat(outs)
+        hi = min(lo + batch_size, x2d.shape[0])
+        operands = (x2d[lo:hi], traj[lo:hi], cam) if reproj else ()
+        state = None
+        for pred, h0, _ in sampler.sample_chunks(x2d[lo:hi], None, input_2d_flip=x2d_flip[lo:hi], chunk=hypothesis_chunk):
+            state = accumulate_poses(state, pred, h0, dataset, *operands)
+            del pred
+        out = aggregate_poses_sharded(None, None, model.num_proposals, dataset, group=group, state=state,
+                                      want=("pick", "idx") if reproj else ("mean",))
+        poses.append(out["pick" if reproj else "mean"].cpu())
+        if reproj:
+            picks.append(out["idx"].cpu())
+    return (torch.cat(poses), torch.cat(picks)) if reproj else torch.cat(poses)
 
 
 def load_pifpaf_keypoints(path, num_kps=134):
@@ -111,6 +149,12 @@ def stitch_clips(prediction, total_frames, frames=27):
     left = total_frames - (clips - 1) * frames
     out[:, :, -left:] = prediction[-1, :, :, -left:]
     return out
+
+
+def stitch_poses(poses, total_frames, frames=27):
+    """[clips, T, frames, J, 3] aggregated poses (clips cut by :func:`cut_clips`) -> [T, total_frames, J, 3], by the rule of
+    :func:`stitch_clips`: consecutive clips end to end, the last one contributing only its final frames."""
+    return stitch_clips(poses.unsqueeze(2), total_frames, frames).squeeze(1)
 
 
 def camera_to_world(X, R, t=0.0):

@@ -795,3 +795,105 @@ def combine_partials(states, gt, conn, pbroot, shape, num_proposals, merged=None
             B, T, F, J, int(num_proposals), None if merged is None else merged.data_ptr(),
             *((out[k].data_ptr() for k in ("jbest", "pagg", "jagg", "paggpb")) if maps else (None,) * 4), _stream(states)))
     return out
+
+
+# --------------------------------------------------------------------------------------- aggregates as poses
+POSE_STATE_BYTES_PER_ELEMENT = 44   # double sum[3] + float e2 + int32 idx + float sel[3] per (b, t, f, j)
+
+
+def pose_partials_bytes(B, T, F, J):
+    """Bytes of the state pafuse_pose_partials writes (the formula of pafuse_pose_partials_bytes, restated so that sizes
+    can be planned without the library): 44 bytes per (b,t,f,j), rounded up to a multiple of 8.  No P in it."""
+    return (POSE_STATE_BYTES_PER_ELEMENT * B * T * F * J + 7) // 8 * 8
+
+
+def pose_views(state, B, T, F, J):
+    """Typed views of a flat pose state (1-D float64 tensor of pose_partials_bytes / 8 elements, or longer):
+    sum [B,T,F,J,3] f64, e2 [B,T,F,J] f32, idx [B,T,F,J] i32, sel [B,T,F,J,3] f32."""
+    n = B * T * F * J
+    _need(state.dim() == 1 and state.dtype == torch.float64 and state.is_contiguous()
+          and state.numel() * 8 >= pose_partials_bytes(B, T, F, J), "pose_views: not a state of these sizes")
+    f32 = state[3 * n:].view(torch.float32)
+    return {"sum": state[:3 * n].view(B, T, F, J, 3), "e2": f32[:n].view(B, T, F, J),
+            "idx": f32[n:2 * n].view(torch.int32).view(B, T, F, J), "sel": f32[2 * n:5 * n].view(B, T, F, J, 3)}
+
+
+def pose_partials(pred, conn, h0, x2d=None, traj=None, cam=None, out=None):
+    """One shard's pose state (pafuse_pose_partials): pred [B,T,P_r,F,J,3] the LOCAL part-centred hypotheses
+    [h0, h0 + P_r) of the run, conn int32 [J]; x2d [B,F,J,2], traj [B,F,3] (or [B,F,1,3]) and cam [9] together, or none of
+    them (mean-only: no candidate is kept) -> the flat state, a 1-D float64 tensor (pose_views names its pieces).
+    `out`: a float64 buffer at least that long to write into; the result is then `out` itself."""
+    lib = _lib.load()
+    _need(pred.dim() == 6 and pred.shape[-1] == 3, f"pose_partials: pred must be [B,T,P_r,F,J,3], got {tuple(pred.shape)}")
+    B, T, P_r, F, J, _ = pred.shape
+    _need(T > 0 and F > 0 and J > 0 and int(h0) >= 0, "pose_partials: T, F, J > 0 and h0 >= 0")
+    _need(conn.numel() == J and conn.dtype == torch.int32, "pose_partials: conn must be int32 [J]")
+    given = [t for t in (x2d, traj, cam) if t is not None]   # some but not all of them: the library refuses (PafuseError)
+    _need((x2d is None or tuple(x2d.shape) == (B, F, J, 2)) and (traj is None or traj.numel() == B * F * 3)
+          and (cam is None or cam.numel() == 9), "pose_partials: operands do not match pred")
+    ops = [pred, conn] + given
+    _need(all(t.is_cuda and t.device == pred.device and t.is_contiguous() for t in ops), "pose_partials: contiguous "
+          "tensors on one HIP device (no CPU fallback)")
+    _need(all(t.dtype == torch.float32 for t in [pred] + given), "pose_partials: dtypes")
+    dev = pred.device
+    need = int(lib.pafuse_pose_partials_bytes(B, T, F, J))
+    assert need == pose_partials_bytes(B, T, F, J)
+    if out is None:
+        out = torch.empty(need // 8, device=dev, dtype=torch.float64)
+    _need(out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous()
+          and out.numel() * 8 >= need, f"pose_partials: out must be a float64 buffer of {need} bytes or more on {dev}")
+    ptrs = [None if t is None else t.data_ptr() for t in (x2d, traj, cam)]
+    if B == 0 and len(given) == 3:
+        ptrs = [None] * 3                    # empty tensors have no storage to point the library at
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_pose_partials(
+            _data(pred), *ptrs, _data(conn), B, T, P_r, F, J, int(h0),
+            _data(out), out.numel() * 8, _stream(pred)))
+    return out
+
+
+def combine_poses(states, shape, num_proposals, merged=None, want=("mean", "pick", "idx")):
+    """pafuse_pose_combine: `states` [W, L] float64 (W flat pose states of the same (B,T,F,J) = `shape`, one per row, in
+    ascending-h0 order; rows may be padded) -> dict with the entries named in `want`: "mean" [B,T,F,J,3] (the sums
+    divided by `num_proposals`, the TOTAL hypothesis count), "pick" [B,T,F,J,3], "idx" [B,T,F,J] int32.  `merged`: a
+    float64 buffer that receives the state of the union; of the operands it may only be states[0] (a running state).
+    Asking for "pick" or "idx" when no state holds a single candidate (mean-only states) raises - after the launch, at
+    the price of one synchronisation."""
+    lib = _lib.load()
+    B, T, F, J = (int(v) for v in shape)
+    n = B * T * F * J
+    L = pose_partials_bytes(B, T, F, J) // 8
+    want = tuple(want)
+    _need(all(k in ("mean", "pick", "idx") for k in want), f"combine_poses: want holds mean, pick, idx - got {want}")
+    _need(states.dim() == 2 and states.dtype == torch.float64 and states.is_cuda and states.is_contiguous()
+          and states.shape[0] >= 1 and states.shape[1] >= L, f"combine_poses: states must be [W, >= {L}] float64")
+    _need(T > 0 and F > 0 and J > 0 and B >= 0, "combine_poses: bad shape")
+    _need(want or merged is not None, "combine_poses: nothing to compute")
+    _need("mean" not in want or int(num_proposals) >= 1, "combine_poses: num_proposals >= 1")
+    dev = states.device
+    if merged is not None:
+        _need(merged.is_cuda and merged.device == dev and merged.dtype == torch.float64 and merged.is_contiguous()
+              and merged.numel() >= L, f"combine_poses: merged must hold {L} float64")
+        lo, hi = states.data_ptr(), states.data_ptr() + states.numel() * 8
+        _need(merged.data_ptr() == lo or not (merged.data_ptr() < hi and merged.data_ptr() + 8 * L > lo),
+              "combine_poses: of its operands the merged state may only lie over the first")
+    out = {}
+    if "mean" in want:
+        out["mean"] = torch.empty(B, T, F, J, 3, device=dev)
+    if "pick" in want:
+        out["pick"] = torch.empty(B, T, F, J, 3, device=dev)
+    if "idx" in want or "pick" in want:
+        idx = torch.empty(B, T, F, J, device=dev, dtype=torch.int32)
+        if "idx" in want:
+            out["idx"] = idx
+    if n == 0:
+        return out
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_pose_combine(
+            states.data_ptr(), states.shape[0], states.shape[1] * 8, B, T, F, J, int(num_proposals),
+            None if merged is None else merged.data_ptr(), ptr("mean"), ptr("pick"),
+            idx.data_ptr() if ("idx" in want or "pick" in want) else None, _stream(states)))
+    if ("idx" in want or "pick" in want) and not bool((idx >= 0).any()):
+        raise _lib.PafuseError("combine_poses: no state holds a J-Agg candidate (mean-only states have no pick)")
+    return out

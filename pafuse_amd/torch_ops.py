@@ -11,6 +11,7 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::ddim_loop(..., precision)                        D3DP.ddim_sample[_flip]        common/diffusionpose.py:227-316
   pafuse::hypothesis_partials(pred, gt, x2d, traj, cam, conn, pbroot, part, num_parts, h0)   one shard's partial reductions
   pafuse::combine_partials(states, gt, conn, pbroot, T, num_proposals)   jbest, pagg, jagg, paggpb from W states   main_h3wb.py:327-362
+  pafuse::aggregate_poses(pred, conn, x2d?, traj?, cam?)  P-Agg mean pose, J-Agg pose and its hypothesis index, one shard
   pafuse::noise_fill(key, draw, B, P, F, J)               one draw of noise stream v1 as a tensor (DESIGN.md section 6)
 
 ``precision`` ('bf16x3' = the modules' default; 'bf16x3_images', 'f16x2', 'f32', 'bf16': pafuse_amd.D3DP.precision) is the
@@ -22,7 +23,7 @@ are the same entry points for callers that want schema'd operators instead of nn
 """
 import ctypes as C
 from functools import lru_cache
-from typing import List
+from typing import List, Optional
 
 import torch
 
@@ -399,6 +400,29 @@ def combine_partials(states: torch.Tensor, gt: torch.Tensor, conn: torch.Tensor,
 def _(states, gt, conn, pbroot, T, num_proposals):
     B, F, J, _ = gt.shape
     return [gt.new_empty(B, T, F, J) for _ in range(4)]
+
+
+# ------------------------------------------------------------------------------------------ aggregates as poses
+@torch.library.custom_op("pafuse::aggregate_poses", mutates_args=(), device_types="cuda")
+def aggregate_poses(pred: torch.Tensor, conn: torch.Tensor, x2d: Optional[torch.Tensor] = None,
+                    traj: Optional[torch.Tensor] = None, cam: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+    """The one-shard convenience of pafuse_amd.ops.pose_partials + combine_poses: pred [B,T,P,F,J,3] part-centred ->
+    [mean [B,T,F,J,3], pick [B,T,F,J,3], idx [B,T,F,J] int32].  Without x2d / traj / cam (mean-only) there is no pick: it
+    comes back as NaN with idx -1, the library's "no candidate"."""
+    from . import ops
+    B, T, P, F, J, _ = pred.shape
+    state = ops.pose_partials(pred, conn, 0, x2d, traj, cam)
+    if x2d is None:
+        mean = ops.combine_poses(state.view(1, -1), (B, T, F, J), P, want=("mean",))["mean"]
+        return [mean, torch.full_like(mean, float("nan")), torch.full((B, T, F, J), -1, device=pred.device, dtype=torch.int32)]
+    m = ops.combine_poses(state.view(1, -1), (B, T, F, J), P)
+    return [m["mean"], m["pick"], m["idx"]]
+
+
+@aggregate_poses.register_fake
+def _(pred, conn, x2d=None, traj=None, cam=None):
+    B, T, P, F, J, _ = pred.shape
+    return [pred.new_empty(B, T, F, J, 3), pred.new_empty(B, T, F, J, 3), pred.new_empty((B, T, F, J), dtype=torch.int32)]
 
 
 # ----------------------------------------------------------------------------------------------- noise stream v1
