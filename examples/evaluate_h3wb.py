@@ -33,6 +33,9 @@ def main():
                     help="what the ranks exchange before the aggregation: all hypotheses, or their partial reductions")
     ap.add_argument("--hypothesis-chunk", type=int, default=None,
                     help="with --gather partials: sample and reduce this many hypotheses at a time")
+    ap.add_argument("--p2-gather", choices=("hypotheses", "partials"), default="hypotheses",
+                    help="with ft2d.p2=True and --gather partials: Protocol #2 from all gathered hypotheses (the default's numbers "
+                         "bit for bit), or from per-shard partial states in the same exchange (no hypothesis is kept)")
     ap.add_argument("--noise", choices=("torch", "device"), default="torch",
                     help="where the loop's normals come from: torch.randn on the full tensor, or the library's counter-based "
                          "stream drawn inside the kernels (no noise tensor; other hypotheses than torch.randn's)")
@@ -70,7 +73,7 @@ def main():
     log("Test time augmentation:", args.model.test_time_augmentation)
     h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
                   batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),
-                  gather=a.gather, hypothesis_chunk=a.hypothesis_chunk)
+                  gather=a.gather, hypothesis_chunk=a.hypothesis_chunk, p2_gather=a.p2_gather)
     if world > 1:
         dist.destroy_process_group()
 

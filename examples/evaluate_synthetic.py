@@ -5,6 +5,7 @@ sequences (the H3WB npz files and the released checkpoint are not available offl
     python examples/evaluate_synthetic.py --proposals 20 --timesteps 10 --sequences 2 --frames 120
     torchrun --standalone --nproc-per-node 8 examples/evaluate_synthetic.py --proposals 160     # hypothesis-sharded
     python examples/evaluate_synthetic.py --proposals 160 --gather partials --hypothesis-chunk 20 --noise device --seed 7
+    python examples/evaluate_synthetic.py --proposals 160 --gather partials --hypothesis-chunk 20 --p2 --p2-gather partials
 
 Prints the per-step protocol lines in the reference's log format (values are meaningless with random weights).
 """
@@ -34,6 +35,10 @@ def main():
                     help="what the ranks exchange before the aggregation: all hypotheses, or their partial reductions")
     ap.add_argument("--hypothesis-chunk", type=int, default=None,
                     help="with --gather partials: sample and reduce this many hypotheses at a time")
+    ap.add_argument("--p2", action="store_true", help="add Protocol #2 (P-MPJPE after similarity alignment)")
+    ap.add_argument("--p2-gather", choices=("hypotheses", "partials"), default="hypotheses",
+                    help="with --p2 and --gather partials: Protocol #2 from all gathered hypotheses (the default's numbers bit "
+                         "for bit), or from per-shard partial states in the same exchange (no hypothesis is kept)")
     ap.add_argument("--noise", choices=("torch", "device"), default="torch",
                     help="where the loop's normals come from: torch.randn on the full tensor, or the library's counter-based "
                          "stream drawn inside the kernels (no noise tensor; other hypotheses than torch.randn's)")
@@ -62,7 +67,8 @@ def main():
         seq_2d = torch.rand(a.frames, 134, 2, generator=g) * 2 - 1
         seq_3d = torch.randn(a.frames, 134, 3, generator=g) * 0.25 + torch.tensor([0.0, 0.0, 4.0])
         sums, cnt = harness.evaluate_sequence(model, ds, seq_2d, seq_3d, cam, gu.SYN_JOINTS_LEFT, gu.SYN_JOINTS_RIGHT,
-                                              gather=a.gather, hypothesis_chunk=a.hypothesis_chunk)
+                                              gather=a.gather, hypothesis_chunk=a.hypothesis_chunk, p2=a.p2,
+                                              p2_gather=a.p2_gather)
         total = sums if total is None else {k: total[k] + v for k, v in sums.items()}
         n += cnt
     torch.cuda.synchronize()
@@ -81,6 +87,9 @@ def main():
             print("step %d : Protocol #1 Error (MPJPE) P_Best Part-Based HANDS: %f mm"
                   % (i, (mm["p_best_pb_right_hand"][i] + mm["p_best_pb_left_hand"][i]) / 2.0))
             print("step %d : Protocol #1 Error (MPJPE) P_Agg Part-Based: %f mm" % (i, mm["p_agg_pb"][i]))
+            if a.p2:
+                for key, name in (("p2_j_best", "J_Best"), ("p2_p_best", "P_Best"), ("p2_p_agg", "P_Agg"), ("p2_j_agg", "J_Agg")):
+                    print("step %d : Protocol #2 Error (MPJPE) %s: %f mm" % (i, name, mm[key][i]))
         clips = n // 27
         print(f"{clips} clips x {a.proposals} hypotheses x {a.timesteps} steps in {time.time() - t0:.2f} s "
               f"on {world} GPU(s), noise {a.noise}, peak device memory {torch.cuda.max_memory_allocated() / 1e6:.0f} MB")

@@ -28,6 +28,7 @@
  *   pafuse_hypothesis_partials / _combine  the same from per-shard partial reductions (sharded or chunked P)
  *   pafuse_pose_partials / _combine  the P-Agg / J-Agg aggregates as poses, from shards or chunks of P (no ground truth)
  *   pafuse_procrustes_errors the Protocol #2 part of it (ft2d.p2), main_h3wb.py:381-395, common/loss.py:251-458
+ *   pafuse_procrustes_partials / _combine  Protocol #2 from per-shard partial states (sharded or chunked P)
  *   pafuse_mixste2_train_*   MixSTE2.forward (is_train=True) + autograd backward, common/mixste.py:215-225,260-298
  *   pafuse_d3dp_qsample      D3DP.prepare_diffusion_concat / q_sample, common/diffusionpose.py:319-326,358-374
  */
@@ -584,6 +585,45 @@ int pafuse_pose_combine(const void *states, int32_t W, size_t stride_bytes, int3
 int pafuse_procrustes_errors(const float *pred, const float *gt, const float *x2d, const float *traj, const float *cam,
                              const int32_t *conn, int32_t B, int32_t T, int32_t P, int32_t F, int32_t J, float *jbest,
                              double *pbest_sums, float *pagg, float *jagg, int32_t *pick, void *stream);
+
+/* Protocol #2 from per-shard partial states (opt-in: harness.evaluate_sequence(p2_gather="partials")).  Per (b,t,f) every
+ * hypothesis is aligned on its own, so a shard [h0, h0 + P_r) reduces to a state whose head does not depend on P.
+ * pred [B,T,P_r,F,J,3] is the LOCAL tensor; the other operands are those of pafuse_procrustes_errors.  J <= 256.
+ * State, one flat 8-byte aligned buffer of pafuse_procrustes_partials_bytes = 16*n + 8*T*P_r bytes, n = B*T*F*J:
+ *   float  jbest[n]     minimum over the local h of the aligned per-joint error, NaN-sticky (+inf when P_r == 0)
+ *   float  e2[n], sel[n]; int32 idx[n]   the J-Agg candidate: smallest reprojection error (the fp32 expression of
+ *                       pafuse_hypothesis_errors), that hypothesis's aligned error, its GLOBAL index h0 + h; first minimum
+ *                       wins; (+inf, 0, -1) where no e2 of the shard is finite
+ *   double psum[P_r][T] per local hypothesis and step: sum over (b, f) of the per-pose sums over j of the aligned errors
+ *                       (pbest_sums of pafuse_procrustes_errors reduced in one fixed order: the same bits however P is cut)
+ * The tail is at the end: a ragged shard is a prefix of a buffer sized for the largest one.  The state holds no sums for
+ * the P-Agg mean pose - pafuse_procrustes_combine borrows them.  workspace: pafuse_procrustes_partials_workspace_bytes bytes,
+ * 8-byte aligned (the per-pose sums [B,T,P_r,F]).  Two kernels, no atomics, bit-reproducible.  B == 0 or P_r == 0: no
+ * kernel runs, the state is the neutral one.  Refused: a null operand, negative sizes or h0, a short state (PAFUSE_E_ARG),
+ * J > 256 (PAFUSE_E_SHAPE), a small workspace (PAFUSE_E_WORKSPACE). */
+size_t pafuse_procrustes_partials_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J);
+size_t pafuse_procrustes_partials_workspace_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J);
+int pafuse_procrustes_partials(const float *pred, const float *gt, const float *x2d, const float *traj, const float *cam,
+                               const int32_t *conn, int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t h0,
+                               void *state, size_t state_bytes, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Combines W such states, `stride_bytes` apart and in ascending-h0 order; only the first 16*n bytes of each are read
+ * (concatenate the psum tails).  Per joint: the NaN-sticky minimum of the minima; the candidate with the smallest e2 and,
+ * among equal ones, the lowest global index.  sums (NULL unless pagg is wanted): W arrays double[n][3], `sums_stride_bytes`
+ * apart - the heads of the Protocol #1 states (pafuse_hypothesis_partials) or pose states (pafuse_pose_partials) of the
+ * same shards, which both begin with the fp64 sum over h of the whole-body joint.  They are added in shard order, divided
+ * by P_total in fp64, and that mean pose is aligned once against the target gt [B,F,J,3] (conn int32 [J]).
+ * Writes any of (NULL: not wanted, at least one):
+ *   merged  the 16*n-byte head of the union's state; of the operands it may only lie over the FIRST state
+ *   jbest, pagg, jagg [B,T,F,J] fp32, pick [B,T,F,J] int32: what pafuse_procrustes_errors writes for all hypotheses.
+ *           jbest, jagg and pick are bit-equal to it; pagg sums the mean pose per shard first (fp64 roundings apart).
+ *           jagg is 0 and pick is -1 where no state holds a candidate.
+ * Refused: null operands, negative sizes, W < 1, P_total < 1, pagg without sums, close or misaligned states
+ * (PAFUSE_E_ARG), J > 256 (PAFUSE_E_SHAPE). */
+int pafuse_procrustes_combine(const void *states, int32_t W, size_t stride_bytes, const void *sums,
+                              size_t sums_stride_bytes, const float *gt, const int32_t *conn, int32_t B, int32_t T,
+                              int32_t F, int32_t J, int32_t P_total, void *merged, float *jbest, float *pagg, float *jagg,
+                              int32_t *pick, void *stream);
 
 /* Replays the GEMM launches of one flip-TTA denoiser pass (all three parts) back to back on `stream`, for
  * bench.py's per-kernel roofline measurement: returns the number of launches, adds their algorithmic FLOPs to

@@ -148,6 +148,12 @@ SIGNATURES = {
     "pafuse_pose_partials": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "pafuse_pose_combine": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t] + [C.c_int32] * 5 + [C.c_void_p] * 5),
     "pafuse_procrustes_errors": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p] * 6),
+    "pafuse_procrustes_partials_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "pafuse_procrustes_partials_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "pafuse_procrustes_partials": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                                                   C.c_void_p]),
+    "pafuse_procrustes_combine": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+                                  + [C.c_int32] * 5 + [C.c_void_p] * 6),
     "pafuse_d3dp_replay_gemms": (C.c_int, [C.POINTER(D3DPConfig), C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.POINTER(C.c_double)]),
     "pafuse_d3dp_replay_layers": (C.c_int, [C.POINTER(D3DPConfig), C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,

@@ -3017,6 +3017,7 @@ __global__ void __launch_bounds__(256) pose_combine_kernel(const PoseCombinePara
 // mean pose); lane l holds joints l, l + 64, ... in fp64.  Reductions over joints are butterflies (the same bits in
 // every lane), the per-joint results of the waves are merged in wave order (min and first-minimum are order-free),
 // and the mean pose is summed over h = 0 .. P-1 in order by one thread per joint: results do not depend on P2_WAVES.
+// The per-pose body (p2_centre_target, p2_align_pose) is shared with the partial-state kernels further down.
 // ----------------------------------------------------------------------------------------------------------------
 constexpr int P2_WAVES = 4;
 constexpr int P2_SLOTS = 4;                  // joints per lane
@@ -3110,6 +3111,74 @@ __device__ __forceinline__ void p2_similarity(const double (&H)[3][3], double nx
     M[2][0] = a * 2.0 * (qx * qz - qw * qy), M[2][1] = a * 2.0 * (qy * qz + qw * qx), M[2][2] = a * (qw * qw - qx * qx - qy * qy + qz * qz);
 }
 
+// The target pose of one (b, f), whole-body and centred, lane l holding joints l, l + 64, ... (0 past J); returns |X0|.
+// Wave-uniform result: every lane ends with the same bits.
+__device__ __forceinline__ double p2_centre_target(const float* gpose, const int32_t* conn, int J, int lane,
+                                                   double (&x0)[P2_SLOTS][3]) {
+    double mx[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) {
+        const int j = lane + 64 * s;
+        float g[3] = {0.f, 0.f, 0.f};
+        if (j < J) wb_joint(gpose, conn, j, g);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) x0[s][k] = (double)g[k], mx[k] += x0[s][k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) mx[k] = p2_wave_sum(mx[k]) / (double)J;
+    double nx = 0.0;
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) {
+        const bool valid = lane + 64 * s < J;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) x0[s][k] = valid ? x0[s][k] - mx[k] : 0.0, nx += x0[s][k] * x0[s][k];
+    }
+    return sqrt(p2_wave_sum(nx));
+}
+
+// One pose y (whole-body joints of this lane's slots, 0 past J) aligned to the centred target x0: centres y in place,
+// H, the similarity, the per-joint aligned errors err[]; returns this lane's share of their sum over j (not yet reduced
+// over the wave).  The one body every Protocol #2 kernel aligns a pose with.
+__device__ __forceinline__ double p2_align_pose(double (&y)[P2_SLOTS][3], const double (&x0)[P2_SLOTS][3], double nx, int J,
+                                                int lane, double (&err)[P2_SLOTS]) {
+    double my[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) my[k] += y[s][k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) my[k] = p2_wave_sum(my[k]) / (double)J;
+    double ny = 0.0, H[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) {
+        const bool valid = lane + 64 * s < J;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) y[s][k] = valid ? y[s][k] - my[k] : 0.0, ny += y[s][k] * y[s][k];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) H[r][c] += x0[s][r] * y[s][c];
+    }
+    ny = sqrt(p2_wave_sum(ny));
+    const double inv = 1.0 / (nx * ny);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) H[r][c] = p2_wave_sum(H[r][c]) * inv;
+    double M[3][3];
+    p2_similarity(H, nx / ny, M);
+    double esum = 0.0;
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) {
+        double d[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) d[r] = M[r][0] * y[s][0] + M[r][1] * y[s][1] + M[r][2] * y[s][2] - x0[s][r];
+        err[s] = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        if (lane + 64 * s < J) esum += err[s];
+    }
+    return esum;
+}
+
 __global__ void __launch_bounds__(64 * P2_WAVES) procrustes_kernel(const ProcrustesParams p) {
     static_assert(64 * P2_WAVES == P2_MAX_J, "the per-joint phases run one thread per joint");
     __shared__ double mean_pose[P2_MAX_J * 3];
@@ -3139,25 +3208,7 @@ __global__ void __launch_bounds__(64 * P2_WAVES) procrustes_kernel(const Procrus
     // the target, centred, in every wave
     const float* gpose = p.gt + ((int64_t)b * p.F + f) * J * 3;
     double x0[P2_SLOTS][3];
-    double mx[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < P2_SLOTS; ++s) {
-        const int j = lane + 64 * s;
-        float g[3] = {0.f, 0.f, 0.f};
-        if (j < J) wb_joint(gpose, p.conn, j, g);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x0[s][k] = (double)g[k], mx[k] += x0[s][k];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) mx[k] = p2_wave_sum(mx[k]) / (double)J;
-    double nx = 0.0;
-#pragma unroll
-    for (int s = 0; s < P2_SLOTS; ++s) {
-        const bool valid = lane + 64 * s < J;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x0[s][k] = valid ? x0[s][k] - mx[k] : 0.0, nx += x0[s][k] * x0[s][k];
-    }
-    nx = sqrt(p2_wave_sum(nx));
+    const double nx = p2_centre_target(gpose, p.conn, J, lane, x0);
 
     const float* tr = p.traj + ((int64_t)b * p.F + f) * 3;
     const float* x2 = p.x2d + ((int64_t)b * p.F + f) * J * 2;
@@ -3173,7 +3224,6 @@ __global__ void __launch_bounds__(64 * P2_WAVES) procrustes_kernel(const Procrus
         const bool mean = h == p.P;
         double y[P2_SLOTS][3];
         float e2[P2_SLOTS];
-        double my[3] = {0.0, 0.0, 0.0};
 #pragma unroll
         for (int s = 0; s < P2_SLOTS; ++s) {
             const int j = lane + 64 * s;
@@ -3193,39 +3243,9 @@ __global__ void __launch_bounds__(64 * P2_WAVES) procrustes_kernel(const Procrus
 #pragma unroll
                 for (int k = 0; k < 3; ++k) y[s][k] = 0.0;
             }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) my[k] += y[s][k];
         }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) my[k] = p2_wave_sum(my[k]) / (double)J;
-        double ny = 0.0, H[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-#pragma unroll
-        for (int s = 0; s < P2_SLOTS; ++s) {
-            const bool valid = lane + 64 * s < J;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) y[s][k] = valid ? y[s][k] - my[k] : 0.0, ny += y[s][k] * y[s][k];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) H[r][c] += x0[s][r] * y[s][c];
-        }
-        ny = sqrt(p2_wave_sum(ny));
-        const double inv = 1.0 / (nx * ny);
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) H[r][c] = p2_wave_sum(H[r][c]) * inv;
-        double M[3][3];
-        p2_similarity(H, nx / ny, M);
-        double err[P2_SLOTS], esum = 0.0;
-#pragma unroll
-        for (int s = 0; s < P2_SLOTS; ++s) {
-            double d[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) d[r] = M[r][0] * y[s][0] + M[r][1] * y[s][1] + M[r][2] * y[s][2] - x0[s][r];
-            err[s] = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            if (lane + 64 * s < J) esum += err[s];
-        }
+        double err[P2_SLOTS];
+        double esum = p2_align_pose(y, x0, nx, J, lane, err);
         if (mean) {
 #pragma unroll
             for (int s = 0; s < P2_SLOTS; ++s)
@@ -3259,6 +3279,220 @@ __global__ void __launch_bounds__(64 * P2_WAVES) procrustes_kernel(const Procrus
         p.jbest[btf * J + tid] = m;
         p.jagg[btf * J + tid] = e;
         if (p.pick) p.pick[btf * J + tid] = hb;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// Protocol #2 from per-shard partial states.  Per (b, t, f) procrustes_kernel aligns every
+// hypothesis on its own, so J-Best (a NaN-sticky minimum over h), J-Agg (the aligned error of the picked hypothesis
+// under ITS OWN alignment) and the per-pose sums of P-Best reduce over shards exactly like Protocol #1; only P-Agg
+// needs work at combine time: one alignment of the mean pose, whose fp64 sums over h head every Protocol #1 state and
+// every pose state (double sum[n][3]) and are borrowed from there.
+//
+// State of a shard [h0, h0 + P_r), one flat 8-byte aligned buffer of 16*n + 8*T*P_r bytes, n = B*T*F*J:
+//   float jbest[n] | float e2[n] | float sel[n] | int32 idx[n] | double psum[P_r][T]
+// jbest: NaN-sticky minimum over the local h of the aligned error; (e2, idx, sel): smallest reprojection error
+// (p2_reproj_error), its GLOBAL index h0 + h, that hypothesis's aligned error, first minimum wins, (+inf, -1, 0) where
+// none is finite; psum[h][t]: fp64 sum over (b, f) of the per-pose sums over j, in one fixed order - the same bits
+// however P is cut.
+//
+// procrustes_partials_kernel is procrustes_kernel without the mean pose (same workgroup shape, same per-pose body
+// p2_align_pose); procrustes_psum_kernel reduces its [B,T,P_r,F] per-pose sums by partials_hsum_kernel's scheme;
+// procrustes_combine_kernel merges W states in ascending-h0 order, one wave per (b, t, f), and aligns the mean pose.
+// No atomics, no data-dependent loops.
+// ----------------------------------------------------------------------------------------------------------------
+struct ProcrustesPartialsParams {
+    const float* pred;  // [B,T,P_r,F,J,3] this shard's part-centred predictions
+    const float* gt;    // [B,F,J,3]
+    const float* x2d;   // [B,F,J,2]
+    const float* traj;  // [B,F,3]
+    const float* cam;   // [9]
+    const int32_t* conn;   // [J]
+    float *jbest, *e2, *sel;   // state head (see above)
+    int32_t* idx;
+    double* pose_sums;  // workspace [B,T,P_r,F]: sum over j of the aligned errors of every local pose
+    int B, T, P, F, J, h0;
+};
+
+__global__ void __launch_bounds__(64 * P2_WAVES) procrustes_partials_kernel(const ProcrustesPartialsParams p) {
+    __shared__ float w_min[P2_WAVES][P2_MAX_J], w_e2[P2_WAVES][P2_MAX_J], w_sel[P2_WAVES][P2_MAX_J];
+    __shared__ int32_t w_h[P2_WAVES][P2_MAX_J];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = (int)(blockIdx.x % p.F);
+    const int t = (int)((blockIdx.x / p.F) % p.T);
+    const int b = (int)(blockIdx.x / ((unsigned)p.F * p.T));
+    const int J = p.J;
+    const int64_t hstride = (int64_t)p.F * J * 3;
+    const float* pose0 = p.pred + ((((int64_t)b * p.T + t) * p.P) * p.F + f) * J * 3;   // local pose h at pose0 + h * hstride
+
+    const float* gpose = p.gt + ((int64_t)b * p.F + f) * J * 3;
+    double x0[P2_SLOTS][3];
+    const double nx = p2_centre_target(gpose, p.conn, J, lane, x0);
+
+    const float* tr = p.traj + ((int64_t)b * p.F + f) * 3;
+    const float* x2 = p.x2d + ((int64_t)b * p.F + f) * J * 2;
+    double run_min[P2_SLOTS], sel[P2_SLOTS];
+    float best2[P2_SLOTS];
+    int32_t hsel[P2_SLOTS];
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) run_min[s] = INFINITY, sel[s] = 0.0, best2[s] = INFINITY, hsel[s] = -1;
+
+    const int64_t btf = ((int64_t)b * p.T + t) * p.F + f;
+    for (int h = wave; h < p.P; h += P2_WAVES) {
+        double y[P2_SLOTS][3];
+        float e2[P2_SLOTS];
+#pragma unroll
+        for (int s = 0; s < P2_SLOTS; ++s) {
+            const int j = lane + 64 * s;
+            e2[s] = INFINITY;
+            float w[3] = {0.f, 0.f, 0.f};
+            if (j < J) {
+                wb_joint(pose0 + h * hstride, p.conn, j, w);
+                e2[s] = p2_reproj_error(w, tr, p.cam, x2 + j * 2);
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) y[s][k] = (double)w[k];
+        }
+        double err[P2_SLOTS];
+        const double esum = p2_wave_sum(p2_align_pose(y, x0, nx, J, lane, err));
+        if (lane == 0) p.pose_sums[((((int64_t)b * p.T + t) * p.P) + h) * p.F + f] = esum;
+#pragma unroll
+        for (int s = 0; s < P2_SLOTS; ++s) {
+            run_min[s] = p2_min(run_min[s], err[s]);
+            if (e2[s] < best2[s]) best2[s] = e2[s], hsel[s] = p.h0 + h, sel[s] = err[s];   // first minimum of this wave's h
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) {
+        const int j = lane + 64 * s;
+        if (j < J) w_min[wave][j] = (float)run_min[s], w_e2[wave][j] = best2[s], w_sel[wave][j] = (float)sel[s], w_h[wave][j] = hsel[s];
+    }
+    __syncthreads();
+    if (tid < J) {
+        float m = w_min[0][tid], b2 = INFINITY, e = 0.f;
+        int32_t hb = -1;
+#pragma unroll
+        for (int w = 0; w < P2_WAVES; ++w) {
+            if (w > 0) m = (float)p2_min(m, w_min[w][tid]);
+            const int32_t hw = w_h[w][tid];
+            // the shard's first minimum: the smallest e2, the lowest h among equal ones
+            if (hw >= 0 && (hb < 0 || w_e2[w][tid] < b2 || (w_e2[w][tid] == b2 && hw < hb))) b2 = w_e2[w][tid], hb = hw, e = w_sel[w][tid];
+        }
+        p.jbest[btf * J + tid] = m;
+        p.e2[btf * J + tid] = b2;
+        p.sel[btf * J + tid] = e;
+        p.idx[btf * J + tid] = hb;
+    }
+}
+
+struct ProcrustesPsumParams {
+    const double* pose_sums;  // [B,T,P_r,F]
+    double* psum;             // [P_r,T]
+    int B, T, P, F;
+};
+
+// one workgroup of four waves per (h, t): thread i adds the (b, f) pairs i, i + 256, ... (b-major) in order, a butterfly
+// finishes each wave and thread 0 adds the four waves in order - nothing in that order depends on P_r or h0
+__global__ void __launch_bounds__(256) procrustes_psum_kernel(const ProcrustesPsumParams p) {
+    __shared__ double s_w[4];
+    const int tid = threadIdx.x;
+    const int t = (int)(blockIdx.x % p.T), h = (int)(blockIdx.x / p.T);
+    const int n = p.B * p.F;
+    double a = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        const int b = i / p.F, f = i % p.F;
+        a += p.pose_sums[((((int64_t)b * p.T + t) * p.P) + h) * p.F + f];
+    }
+    a = p2_wave_sum(a);
+    if ((tid & 63) == 0) s_w[tid >> 6] = a;
+    __syncthreads();
+    if (tid == 0) p.psum[(int64_t)h * p.T + t] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+
+struct ProcrustesCombineParams {
+    const char* states;   // W states, `stride` bytes apart, in ascending-h0 order
+    int64_t stride;
+    const char* sums;     // W arrays double[n][3], `sums_stride` bytes apart (null: no P-Agg)
+    int64_t sums_stride;
+    int W;
+    const float* gt;      // [B,F,J,3]  (read for pagg only)
+    const int32_t* conn;  // [J]
+    float *m_jbest, *m_e2, *m_sel;   // merged head (null: not wanted); may be the first operand
+    int32_t* m_idx;
+    float *jbest, *pagg, *jagg;      // [B,T,F,J] (null: not wanted)
+    int32_t* pick;                   // [B,T,F,J] (null: not wanted)
+    int B, T, F, J, P;    // P: the TOTAL hypothesis count the mean pose divides by
+};
+
+constexpr int P2C_WAVES = 4;   // (b, t, f) triples per workgroup of procrustes_combine_kernel, one wave each
+
+// Every thread reads its own elements of every state before it writes anything, so the merged head may lie over the first
+// operand.  No LDS and no barrier: waves past the last (b, t, f) leave at once.
+__global__ void __launch_bounds__(64 * P2C_WAVES) procrustes_combine_kernel(const ProcrustesCombineParams p) {
+    const int lane = threadIdx.x & 63;
+    const int64_t btf = (int64_t)blockIdx.x * P2C_WAVES + (threadIdx.x >> 6);
+    const int64_t nbtf = (int64_t)p.B * p.T * p.F;
+    if (btf >= nbtf) return;   // wave-uniform
+    const int J = p.J;
+    const int64_t n = nbtf * J;
+    const int f = (int)(btf % p.F);
+    const int b = (int)(btf / ((int64_t)p.F * p.T));
+    float m[P2_SLOTS], best2[P2_SLOTS], sel[P2_SLOTS];
+    int32_t hsel[P2_SLOTS];
+    double y[P2_SLOTS][3];
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) {
+        m[s] = INFINITY, best2[s] = INFINITY, sel[s] = 0.f, hsel[s] = -1;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) y[s][k] = 0.0;
+    }
+    for (int w = 0; w < p.W; ++w) {
+        const float* jb = (const float*)(p.states + (int64_t)w * p.stride);
+        const float* e2 = jb + n;
+        const float* sl = e2 + n;
+        const int32_t* ix = (const int32_t*)(sl + n);
+        const double* sum = p.pagg ? (const double*)(p.sums + (int64_t)w * p.sums_stride) : nullptr;
+#pragma unroll
+        for (int s = 0; s < P2_SLOTS; ++s) {
+            const int j = lane + 64 * s;
+            if (j < J) {
+                const int64_t e = btf * J + j;
+                m[s] = (float)p2_min(m[s], jb[e]);
+                const int32_t hw = ix[e];
+                const float ew = e2[e];
+                // the overall first minimum: the smallest e2, the lowest global index among equal ones
+                if (hw >= 0 && (hsel[s] < 0 || ew < best2[s] || (ew == best2[s] && hw < hsel[s])))
+                    best2[s] = ew, hsel[s] = hw, sel[s] = sl[e];
+                if (sum) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) y[s][k] += sum[e * 3 + k];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < P2_SLOTS; ++s) {
+        const int j = lane + 64 * s;
+        if (j < J) {
+            const int64_t e = btf * J + j;
+            if (p.m_jbest) p.m_jbest[e] = m[s], p.m_e2[e] = best2[s], p.m_sel[e] = sel[s], p.m_idx[e] = hsel[s];
+            if (p.jbest) p.jbest[e] = m[s];
+            if (p.jagg) p.jagg[e] = sel[s];
+            if (p.pick) p.pick[e] = hsel[s];
+        }
+    }
+    if (p.pagg) {   // wave-uniform: the mean pose, aligned once
+        const double P = (double)p.P;
+#pragma unroll
+        for (int s = 0; s < P2_SLOTS; ++s)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) y[s][k] = y[s][k] / P;
+        double x0[P2_SLOTS][3], err[P2_SLOTS];
+        const double nx = p2_centre_target(p.gt + ((int64_t)b * p.F + f) * J * 3, p.conn, J, lane, x0);
+        p2_align_pose(y, x0, nx, J, lane, err);
+#pragma unroll
+        for (int s = 0; s < P2_SLOTS; ++s)
+            if (lane + 64 * s < J) p.pagg[btf * J + lane + 64 * s] = (float)err[s];
     }
 }
 

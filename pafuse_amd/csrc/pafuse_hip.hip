@@ -1974,6 +1974,109 @@ int pafuse_procrustes_errors(const float* pred, const float* gt, const float* x2
     return check_launch("procrustes_kernel");
 }
 
+// state of pafuse_procrustes_partials: float jbest[n], e2[n], sel[n] | int32 idx[n] | double psum[P_r][T]
+static bool p2_partials_sizes_ok(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J) {
+    return B >= 0 && T > 0 && P_r >= 0 && F > 0 && J > 0;
+}
+
+size_t pafuse_procrustes_partials_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J) {
+    if (!p2_partials_sizes_ok(B, T, P_r, F, J)) return 0;
+    return (size_t)B * T * F * J * 16 + (size_t)P_r * T * 8;
+}
+
+size_t pafuse_procrustes_partials_workspace_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J) {
+    if (!p2_partials_sizes_ok(B, T, P_r, F, J)) return 0;
+    return (size_t)B * T * P_r * F * 8;
+}
+
+int pafuse_procrustes_partials(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,
+                               const int32_t* conn, int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t h0,
+                               void* state, size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (B < 0 || T <= 0 || P_r < 0 || F <= 0 || J <= 0 || h0 < 0) return fail(PAFUSE_E_ARG, "procrustes_partials: bad size");
+    if (J > P2_MAX_J) return fail(PAFUSE_E_SHAPE, "procrustes_partials: J = %d above the supported %d", J, P2_MAX_J);
+    const size_t need = pafuse_procrustes_partials_bytes(B, T, P_r, F, J);
+    if (need && (!state || state_bytes < need)) return fail(PAFUSE_E_ARG, "procrustes_partials: the state needs %zu bytes", need);
+    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "procrustes_partials: the state must be 8-byte aligned");
+    const int64_t n = (int64_t)B * T * F * J;
+    char* st = (char*)state;
+    float* jbest = (float*)st;
+    double* psum = (double*)(st + n * 16);
+    hipStream_t s = (hipStream_t)stream;
+    if (B == 0 || P_r == 0) {   // the neutral state: +inf minima, no candidate (+inf, -1, 0), zero sums; no kernel runs
+        hipError_t e = hipSuccess;
+        if (n) {
+            e = hipMemsetD32Async((hipDeviceptr_t)jbest, 0x7f800000, (size_t)n * 2, s);
+            if (e == hipSuccess) e = hipMemsetAsync(jbest + 2 * n, 0, (size_t)n * 4, s);
+            if (e == hipSuccess) e = hipMemsetAsync(jbest + 3 * n, 0xff, (size_t)n * 4, s);
+        }
+        if (e == hipSuccess && P_r) e = hipMemsetAsync(psum, 0, (size_t)P_r * T * 8, s);
+        if (e != hipSuccess) return fail(PAFUSE_E_HIP, "procrustes_partials: %s", hipGetErrorString(e));
+        return PAFUSE_OK;
+    }
+    if (!pred || !gt || !x2d || !traj || !cam || !conn) return fail(PAFUSE_E_ARG, "procrustes_partials: null pointer");
+    const size_t wneed = pafuse_procrustes_partials_workspace_bytes(B, T, P_r, F, J);
+    if (!workspace || workspace_bytes < wneed || (uintptr_t)workspace % 8)
+        return fail(PAFUSE_E_WORKSPACE, "procrustes_partials: the workspace needs %zu bytes, 8-byte aligned", wneed);
+    const int64_t blocks = (int64_t)B * T * F;
+    if (blocks > 0x7fffffff || (int64_t)P_r * T > 0x7fffffff || (int64_t)B * F > 0x7fffffff)
+        return fail(PAFUSE_E_ARG, "procrustes_partials: grid out of range");
+    ProcrustesPartialsParams m{};
+    m.pred = pred, m.gt = gt, m.x2d = x2d, m.traj = traj, m.cam = cam, m.conn = conn;
+    m.jbest = jbest, m.e2 = jbest + n, m.sel = jbest + 2 * n, m.idx = (int32_t*)(jbest + 3 * n);
+    m.pose_sums = (double*)workspace;
+    m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0;
+    hipLaunchKernelGGL(procrustes_partials_kernel, dim3((unsigned)blocks), dim3(64 * P2_WAVES), 0, s, m);
+    int rc = check_launch("procrustes_partials_kernel");
+    if (rc) return rc;
+    ProcrustesPsumParams r{};
+    r.pose_sums = m.pose_sums, r.psum = psum, r.B = B, r.T = T, r.P = P_r, r.F = F;
+    hipLaunchKernelGGL(procrustes_psum_kernel, dim3((unsigned)((int64_t)P_r * T)), dim3(256), 0, s, r);
+    return check_launch("procrustes_psum_kernel");
+}
+
+int pafuse_procrustes_combine(const void* states, int32_t W, size_t stride_bytes, const void* sums, size_t sums_stride_bytes,
+                              const float* gt, const int32_t* conn, int32_t B, int32_t T, int32_t F, int32_t J,
+                              int32_t P_total, void* merged, float* jbest, float* pagg, float* jagg, int32_t* pick,
+                              void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (B < 0 || T <= 0 || F <= 0 || J <= 0 || W < 1) return fail(PAFUSE_E_ARG, "procrustes_combine: bad size");
+    if (P_total < 1) return fail(PAFUSE_E_ARG, "procrustes_combine: P_total %d", P_total);
+    if (J > P2_MAX_J) return fail(PAFUSE_E_SHAPE, "procrustes_combine: J = %d above the supported %d", J, P2_MAX_J);
+    if (!merged && !jbest && !pagg && !jagg && !pick) return fail(PAFUSE_E_ARG, "procrustes_combine: nothing to write");
+    if (pagg && !sums) return fail(PAFUSE_E_ARG, "procrustes_combine: pagg needs the sums of the mean pose");
+    const int64_t n = (int64_t)B * T * F * J;
+    if (n == 0) return PAFUSE_OK;
+    if (!states || (pagg && (!gt || !conn))) return fail(PAFUSE_E_ARG, "procrustes_combine: null pointer");
+    if (stride_bytes < (size_t)n * 16 || stride_bytes % 8 || (uintptr_t)states % 8 || (uintptr_t)merged % 8)
+        return fail(PAFUSE_E_ARG, "procrustes_combine: states are %lld bytes or more apart, 8-byte aligned", (long long)(n * 16));
+    if (pagg && (sums_stride_bytes < (size_t)n * 24 || sums_stride_bytes % 8 || (uintptr_t)sums % 8))
+        return fail(PAFUSE_E_ARG, "procrustes_combine: sums are %lld bytes or more apart, 8-byte aligned", (long long)(n * 24));
+    const char* lo = (const char*)states;
+    const char* hi = lo + (size_t)(W - 1) * stride_bytes + n * 16;
+    const char* mg = (const char*)merged;
+    if (merged && merged != states && mg < hi && mg + n * 16 > lo)
+        return fail(PAFUSE_E_ARG, "procrustes_combine: of its operands the merged state may only lie over the first");
+    if (merged && pagg) {
+        const char* slo = (const char*)sums;
+        const char* shi = slo + (size_t)(W - 1) * sums_stride_bytes + n * 24;
+        if (mg < shi && mg + n * 16 > slo) return fail(PAFUSE_E_ARG, "procrustes_combine: the merged state lies over the sums");
+    }
+    const int64_t nbtf = (int64_t)B * T * F;
+    const int64_t blocks = (nbtf + P2C_WAVES - 1) / P2C_WAVES;
+    if (blocks > 0x7fffffff) return fail(PAFUSE_E_ARG, "procrustes_combine: grid out of range");
+    ProcrustesCombineParams c{};
+    c.states = lo, c.stride = (int64_t)stride_bytes, c.W = W, c.gt = gt, c.conn = conn;
+    c.sums = pagg ? (const char*)sums : nullptr, c.sums_stride = (int64_t)sums_stride_bytes;
+    if (merged) {
+        c.m_jbest = (float*)merged, c.m_e2 = c.m_jbest + n, c.m_sel = c.m_jbest + 2 * n, c.m_idx = (int32_t*)(c.m_jbest + 3 * n);
+    }
+    c.jbest = jbest, c.pagg = pagg, c.jagg = jagg, c.pick = pick;
+    c.B = B, c.T = T, c.F = F, c.J = J, c.P = P_total;
+    hipLaunchKernelGGL(procrustes_combine_kernel, dim3((unsigned)blocks), dim3(64 * P2C_WAVES), 0, (hipStream_t)stream, c);
+    return check_launch("procrustes_combine_kernel");
+}
+
 int pafuse_d3dp_replay_gemms(const pafuse_d3dp_config* cfg, int32_t B, int32_t P, void* workspace,
                              size_t workspace_bytes, void* stream, double* flops) {
     return pafuse_d3dp_replay_layers(cfg, B, P, workspace, workspace_bytes, stream, 15, flops);

@@ -9,8 +9,11 @@ reprojection, per-joint J-Best / P-Agg / J-Agg and the part-re-centred variants)
 
 ``evaluate_accumulators_sharded`` gives the same 14 vectors without ever holding all P hypotheses: every shard of the
 hypothesis axis (a rank's, or a chunk on one device) is reduced to a small state (``ops.hypothesis_partials``), states
-are merged (``ops.combine_partials``), and ranks exchange states - not hypotheses - in one all-gather.  Protocol #1
-only: Protocol #2 needs the full tensor and keeps the gather of ``pafuse_amd.parallel.gather_hypotheses``.
+are merged (``ops.combine_partials``), and ranks exchange states - not hypotheses - in one all-gather.  Protocol #2 has
+two modes: by default it keeps the gather of ``pafuse_amd.parallel.gather_hypotheses`` and runs ``procrustes_errors`` on
+all P hypotheses; opt-in (``accumulate_procrustes`` / ``protocol2_accumulators_sharded``) every shard is reduced to a
+16-byte-per-(b,t,f,j) state (``ops.procrustes_partials``) that travels in the same all-gather, and only the mean pose of
+P-Agg is aligned at combine time (``ops.combine_procrustes``), from the fp64 sums the Protocol #1 states already hold.
 
 ``accumulate_poses`` / ``aggregate_poses_sharded`` return the aggregates themselves - the P-Agg mean pose and the J-Agg
 pose with its hypothesis index - by the same scheme and without a ground truth (``ops.pose_partials``, ``ops.combine_poses``).
@@ -173,18 +176,38 @@ def accumulate_partials(state, pred_local, h0, gt_parts, inputs_2d, traj, cam, d
     return state
 
 
-def _gather_states(state, num_proposals, group):
-    """[W, L] states of all ranks (ONE all-gather of equal-sized flat buffers; ragged shards are padded to the largest)
-    and the concatenated per-hypothesis sums [P,T,1+parts]."""
+class GatheredStates:
+    """What one exchange leaves on every rank: `states` [W, L] the ranks' Protocol #1 states in rank (= ascending-h0) order
+    and `hsums` [P,T,1+parts] their concatenated per-hypothesis sums; with Protocol #2 states in the same exchange also
+    `p2_states` [W, L2] (a column slice of the same buffer) and `psum` [P,T]."""
+
+    def __init__(self, shape, num_parts, device, states, hsums, p2_states=None, psum=None):
+        self.shape, self.num_parts, self.device = tuple(shape), num_parts, device
+        self.states, self.hsums, self.p2_states, self.psum = states, hsums, p2_states, psum
+
+
+def gather_partial_states(state, num_proposals, group=None, p2_state=None):
+    """ONE all-gather of equal-sized flat buffers (ragged shards are padded to the largest; through the host on a gloo
+    group): per rank the Protocol #1 state and, when `p2_state` (a Procrustes2State over the same hypotheses) is given,
+    the Protocol #2 state right behind it.  -> GatheredStates."""
     from .parallel import shard_counts, shard_range
     B, T, F, J = state.shape
-    n5, nv = 5 * B * T * F * J, 1 + state.num_parts
-    hs = torch.cat([h for _, h in state.hsums]) if state.hsums else torch.zeros(0, T, nv, device=state.device, dtype=torch.float64)
+    n = B * T * F * J
+    n5, nv = 5 * n, 1 + state.num_parts
+    dev = state.device
+    hs = torch.cat([h for _, h in state.hsums]) if state.hsums else torch.zeros(0, T, nv, device=dev, dtype=torch.float64)
+    ps = None
+    if p2_state is not None:
+        if p2_state.shape != state.shape or p2_state.device != dev or (p2_state.h0, p2_state.count) != (state.h0, state.count):
+            raise ValueError(f"the Protocol #2 state holds [{p2_state.h0}, +{p2_state.count}) of {p2_state.shape}, the "
+                             f"Protocol #1 state [{state.h0}, +{state.count}) of {state.shape}")
+        ps = torch.cat([q for _, q in p2_state.psums]) if p2_state.psums else torch.zeros(0, T, device=dev, dtype=torch.float64)
     world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
     if world == 1:
         if state.h0 != 0 or state.count != num_proposals:
             raise ValueError(f"the state holds hypotheses [{state.h0}, {state.h0 + state.count}) of {num_proposals}")
-        return state.slots[:1], hs
+        return GatheredStates(state.shape, state.num_parts, dev, state.slots[:1], hs,
+                              None if p2_state is None else p2_state.slots[:1], ps)
     rank = dist.get_rank(group)
     lo, hi = shard_range(num_proposals, rank, world)
     if (state.h0, state.count) != (lo, hi - lo):
@@ -192,17 +215,26 @@ def _gather_states(state, num_proposals, group):
                          f"[{state.h0}, {state.h0 + state.count})")
     counts = shard_counts(num_proposals, world)
     pmax = max(counts)
-    send = torch.zeros(n5 + pmax * T * nv, device=state.device, dtype=torch.float64)
+    L1 = n5 + pmax * T * nv
+    L2 = 0 if p2_state is None else 2 * n + pmax * T
+    send = torch.zeros(L1 + L2, device=dev, dtype=torch.float64)
     send[:n5] = state.head
     send[n5:n5 + hs.numel()] = hs.reshape(-1)
+    if p2_state is not None:
+        send[L1:L1 + 2 * n] = p2_state.head
+        send[L1 + 2 * n:L1 + 2 * n + ps.numel()] = ps.reshape(-1)
     via_host = dist.get_backend(group) == "gloo"          # rehearsal on a box with fewer GPUs than ranks
     if via_host:
         send = send.cpu()
     recv = send.new_empty(world * send.numel())
     dist.all_gather_into_tensor(recv, send, group=group)
-    recv = recv.view(world, -1).to(state.device)
-    tails = [recv[r, n5:].view(pmax, T, nv)[:counts[r]] for r in range(world)]
-    return recv, torch.cat(tails)
+    recv = recv.view(world, -1).to(dev)
+    tails = [recv[r, n5:L1].view(pmax, T, nv)[:counts[r]] for r in range(world)]
+    out = GatheredStates(state.shape, state.num_parts, dev, recv[:, :L1], torch.cat(tails))
+    if p2_state is not None:
+        out.p2_states = recv[:, L1:]
+        out.psum = torch.cat([recv[r, L1 + 2 * n:].view(pmax, T)[:counts[r]] for r in range(world)])
+    return out
 
 
 def evaluate_accumulators_sharded(pred_local, h0, num_proposals, gt_parts, inputs_2d, traj, cam, dataset, group=None,
@@ -214,7 +246,8 @@ def evaluate_accumulators_sharded(pred_local, h0, num_proposals, gt_parts, input
     ONE all_gather_into_tensor (through the host on a gloo group): 40 bytes per (b,t,f,j) plus 8 * (1 + parts) * T bytes
     per hypothesis of the largest shard, whatever P is.  j_best and j_agg are bit-equal to evaluate_accumulators;
     p_agg*, p_best* sum in fp64 where that kernel sums in fp32 (last-bit differences, closer to exact) and do not
-    depend on how the hypotheses are cut.  Protocol #1 only."""
+    depend on how the hypotheses are cut.  Protocol #1 only.  `state` may also be the GatheredStates of an exchange that
+    has already happened (gather_partial_states: the one all-gather can carry the Protocol #2 states too)."""
     from . import ops
     if pred_local is not None:
         state = accumulate_partials(state, pred_local, h0, gt_parts, inputs_2d, traj, cam, dataset)
@@ -222,8 +255,11 @@ def evaluate_accumulators_sharded(pred_local, h0, num_proposals, gt_parts, input
         raise ValueError("evaluate_accumulators_sharded: neither hypotheses nor a state")
     B, T, F, J = state.shape
     dev = state.device
-    states, hs = _gather_states(state, int(num_proposals), group)
+    gathered = state if isinstance(state, GatheredStates) else gather_partial_states(state, int(num_proposals), group)
+    states, hs = gathered.states, gathered.hsums
     P = hs.shape[0]
+    if P != int(num_proposals):
+        raise ValueError(f"the gathered states hold {P} hypotheses of {num_proposals}")
     conn, pbroot = _tables(dataset, J, dev)
     m = ops.combine_partials(states.contiguous(), gt_parts.contiguous().float(), conn, pbroot, (B, T, F, J), P)
     jbest, pagg, jagg, paggpb = m["jbest"], m["pagg"], m["jagg"], m["paggpb"]
@@ -242,6 +278,92 @@ def evaluate_accumulators_sharded(pred_local, h0, num_proposals, gt_parts, input
         out["p_best_pb_" + part] = ph.gather(1, best.view(-1, 1)).squeeze(1)
         out["p_agg_pb_" + part] = per_t(paggpb[..., idx])
     return out
+
+
+# ------------------------------------------------------------------------------- Protocol #2 from partial states
+class Procrustes2State:
+    """The running Protocol #2 reduction of the hypotheses one rank has seen so far: the merged head of the kernel's state
+    (16 bytes per (b,t,f,j), ops.procrustes_partial_views) and the per-hypothesis sums psum [P_c,T] of every chunk."""
+
+    def __init__(self, shape, device):
+        self.shape, self.device = tuple(shape), device    # shape = (B, T, F, J)
+        self.slots = None        # [2, L] float64: row 0 the running head, row 1 the newest chunk's state
+        self.psums = []          # [(h0, psum [P_c,T] f64)] in ascending h0
+        self.h0, self.count = None, 0
+
+    @property
+    def head(self):
+        B, T, F, J = self.shape
+        return self.slots[0, :2 * B * T * F * J]
+
+
+def accumulate_procrustes(state, pred_local, h0, gt_parts, inputs_2d, traj, cam, dataset):
+    """Fold the hypotheses pred_local [B,T,P_c,F,J,3] = global [h0, h0 + P_c) into the Protocol #2 state `state` (None:
+    start one) and return it.  Chunks come in ascending h0 and follow each other without a gap; memory: the chunk, two
+    16-byte-per-(b,t,f,j) heads, [B,T,P_c,F] doubles of workspace and [P_c,T] doubles - never anything of size P."""
+    from . import ops
+    pred, gt, x2d, tr, cm, conn, _ = _operands(pred_local, gt_parts, inputs_2d, traj, cam, dataset, "accumulate_procrustes",
+                                               name="pred_local", axis="P_c")
+    B, T, P_c, F, J, _ = pred.shape
+    if state is None:
+        state = Procrustes2State((B, T, F, J), pred.device)
+    if state.shape != (B, T, F, J) or state.device != pred.device:
+        raise ValueError(f"accumulate_procrustes: the state holds {state.shape}, the chunk is {(B, T, F, J)}")
+    if state.h0 is not None and int(h0) != state.h0 + state.count:
+        raise ValueError(f"accumulate_procrustes: chunk starts at hypothesis {h0}, the state ends at {state.h0 + state.count}")
+    n2 = 2 * B * T * F * J
+    L = n2 + P_c * T
+    first = state.slots is None
+    if first or state.slots.shape[1] < L:
+        slots = torch.empty(2, L, device=pred.device, dtype=torch.float64)
+        if not first:
+            slots[0, :n2] = state.slots[0, :n2]
+        state.slots = slots
+    row = state.slots[0 if first else 1]
+    ops.procrustes_partials(pred, gt, x2d, tr, cm, conn, int(h0), out=row)
+    state.psums.append((int(h0), ops.procrustes_partial_views(row, B, T, P_c, F, J)["psum"].clone()))
+    if not first:     # running head <- running head (+) this chunk, in place (every thread reads its elements before it writes them)
+        ops.combine_procrustes(state.slots, (B, T, F, J), 1, merged=state.slots[0], want=())
+    if state.h0 is None:
+        state.h0 = int(h0)
+    state.count += P_c
+    return state
+
+
+def protocol2_accumulators_sharded(state, p1, num_proposals, gt_parts, dataset, group=None):
+    """The four Protocol #2 vectors [T] (p2_j_best, p2_p_best, p2_p_agg, p2_j_agg) without ever holding all P hypotheses.
+    `state`: this rank's Procrustes2State (accumulate_procrustes over its hypotheses).  `p1`: this rank's PartialState
+    over the same hypotheses - the two flat buffers are concatenated and travel in ONE all_gather_into_tensor (through the
+    host on a gloo group), 56 bytes per (b,t,f,j) plus the per-hypothesis tails per rank - or the GatheredStates of that
+    exchange (gather_partial_states(p1, P, group, p2_state=state)) when the Protocol #1 evaluation has made it already;
+    `state` may then be None.  The mean pose of P-Agg comes from the fp64 sums heading the Protocol #1 states, added in rank
+    order.  p2_j_best and p2_j_agg are bit-equal to protocol2_accumulators on all hypotheses; p2_p_agg (sums per shard
+    first) and p2_p_best (per-hypothesis sums reduced in one fixed order) differ from it by fp64 roundings, and only
+    p2_p_agg depends on how the hypotheses are cut."""
+    from . import ops
+    if p1 is None or (state is None and not isinstance(p1, GatheredStates)):
+        raise ValueError("protocol2_accumulators_sharded: needs the Protocol #2 state and the Protocol #1 state of this rank, "
+                         "or the GatheredStates of their exchange")
+    gathered = p1 if isinstance(p1, GatheredStates) else gather_partial_states(p1, int(num_proposals), group, p2_state=state)
+    if gathered.p2_states is None:
+        raise ValueError("protocol2_accumulators_sharded: the gathered states carry no Protocol #2 states")
+    B, T, F, J = gathered.shape
+    dev = gathered.device
+    P = int(num_proposals)
+    if gathered.psum.shape[0] != P:
+        raise ValueError(f"the gathered states hold {gathered.psum.shape[0]} hypotheses of {P}")
+    if tuple(gt_parts.shape) != (B, F, J, 3) or gt_parts.device != dev:
+        raise ValueError(f"protocol2_accumulators_sharded: gt_parts must be {(B, F, J, 3)} on {dev}")
+    conn, _ = _tables(dataset, J, dev)
+    m = ops.combine_procrustes(gathered.p2_states, (B, T, F, J), P, sums=gathered.states, gt=gt_parts.contiguous().float(),
+                               conn=conn, want=("jbest", "pagg", "jagg"))
+
+    def per_t(x):                                            # [B,T,F,J] -> [T]
+        return x.double().permute(1, 0, 2, 3).reshape(T, -1).mean(dim=-1).float()
+
+    per_h = (gathered.psum.permute(1, 0) / (B * F * J)).float()          # [T,P]
+    return {"p2_j_best": per_t(m["jbest"]), "p2_p_best": per_h.min(dim=1).values, "p2_p_agg": per_t(m["pagg"]),
+            "p2_j_agg": per_t(m["jagg"])}
 
 
 # ------------------------------------------------------------------------------------------- aggregates as poses

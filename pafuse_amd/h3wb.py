@@ -218,7 +218,7 @@ def iter_sequences(cams, poses_3d, poses_2d):
 
 
 def evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, batch_size=1024, group=None, log=print,
-             action=None, log_dir=None, p2=False, gather="hypotheses", hypothesis_chunk=None):
+             action=None, log_dir=None, p2=False, gather="hypotheses", hypothesis_chunk=None, p2_gather="hypotheses"):
     """evaluate() of main_h3wb.py:194-531 for an already loaded eval model: every video through
     harness.evaluate_sequence (flip-TTA, 27-frame clips, sharded sampling, device-side aggregation), frame-weighted
     means in millimetres per protocol and sampling step, printed in the reference's log format (:406-509) and, with
@@ -226,13 +226,15 @@ def evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, batc
     the per-action header of the reference's run_evaluation loop (:1117-1362): call once per action's sequences.
     ``p2=True`` (``ft2d.p2``) adds Protocol #2 (P-MPJPE after similarity alignment) to the numbers and the log.
     ``gather`` / ``hypothesis_chunk``: harness.evaluate_sequence's - "partials" evaluates Protocol #1 from per-shard
-    partial reductions (optionally sampling the hypotheses a chunk at a time) instead of gathering all P hypotheses."""
+    partial reductions (optionally sampling the hypotheses a chunk at a time) instead of gathering all P hypotheses.
+    ``p2_gather``: harness.evaluate_sequence's - "partials" (with p2=True and gather="partials") takes Protocol #2 from
+    per-shard partial states too, so that no rank ever holds all hypotheses."""
     from . import harness
     total, n = None, 0
     for cam, seq_3d, seq_2d in iter_sequences(cams, poses_3d, poses_2d):
         sums, cnt = harness.evaluate_sequence(model, dataset, seq_2d[0].astype("float32"), seq_3d[0].astype("float32"),
                                               cam[0].astype("float32"), kps_left, kps_right, batch_size, group, p2=p2,
-                                              gather=gather, hypothesis_chunk=hypothesis_chunk)
+                                              gather=gather, hypothesis_chunk=hypothesis_chunk, p2_gather=p2_gather)
         total = sums if total is None else {k: total[k] + sums[k] for k in sums}
         n += cnt
     rep = harness.report(total, n)

@@ -188,7 +188,7 @@ def load_checkpoint(model, checkpoint):
 
 @torch.no_grad()
 def evaluate_sequence(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, batch_size=1024, group=None, p2=False,
-                      gather="hypotheses", hypothesis_chunk=None):
+                      gather="hypotheses", hypothesis_chunk=None, p2_gather="hypotheses"):
     """One (camera, sequence) item of evaluate()'s loop (main_h3wb.py:261-396).
 
     seq_2d [N,J,2] normalised 2-D input, seq_3d [N,J,3] camera-space ground truth (metres), cam [9] intrinsics.
@@ -203,13 +203,25 @@ def evaluate_sequence(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, 
     ``gather="partials"``: every rank reduces its own hypotheses to partial reductions and the ranks exchange those
     (evaluate.evaluate_accumulators_sharded): neither the [B,T,P,F,J,3] tensor nor per-hypothesis error maps exist
     anywhere.  ``hypothesis_chunk=n`` (partials only) also samples and reduces the rank's hypotheses n at a time, so peak
-    memory follows n instead of P; the numbers do not depend on n.  Protocol #1 comes from the partials; ``p2=True``
-    still needs all hypotheses on every rank, so the chunks are kept and gathered for the Protocol #2 kernel (the four
-    p2_* vectors are those of gather="hypotheses") - the memory saving is then lost."""
+    memory follows n instead of P; the numbers do not depend on n.  Protocol #1 comes from the partials.
+
+    ``p2_gather`` says where ``p2=True`` takes Protocol #2 from when ``gather="partials"``.  ``"hypotheses"`` (default): the
+    chunks are kept and gathered, and the Protocol #2 kernel runs on all P hypotheses of every rank - the four p2_* vectors
+    are those of gather="hypotheses" bit for bit, and the memory saving is lost.  ``"partials"`` (needs ``p2=True`` and
+    ``gather="partials"``): every chunk is also folded into a 16-byte-per-(clip,t,f,j) Protocol #2 state
+    (evaluate.accumulate_procrustes) and dropped; the states travel in the same all-gather as the Protocol #1 states (56
+    bytes per (clip,t,f,j) plus the per-hypothesis tails per rank) and no rank ever holds all hypotheses.  p2_j_best and
+    p2_j_agg are then still bit-equal to the default; p2_p_best and p2_p_agg differ from it by fp64 roundings (their sums
+    are taken in another order), and of the four only p2_p_agg depends on how the hypotheses are cut into ranks and chunks,
+    in the last bit."""
     if gather not in ("hypotheses", "partials"):
         raise ValueError(f'gather must be "hypotheses" or "partials", got {gather!r}')
     if hypothesis_chunk is not None and (gather != "partials" or int(hypothesis_chunk) < 1):
         raise ValueError('hypothesis_chunk is a positive count and needs gather="partials"')
+    if p2_gather not in ("hypotheses", "partials"):
+        raise ValueError(f'p2_gather must be "hypotheses" or "partials", got {p2_gather!r}')
+    if p2_gather == "partials" and not (p2 and gather == "partials"):
+        raise ValueError('p2_gather="partials" needs p2=True and gather="partials"')
     dev = next(model.parameters()).device
     seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
     seq_3d = torch.as_tensor(seq_3d, dtype=torch.float32)
@@ -225,7 +237,7 @@ def evaluate_sequence(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, 
         hi = min(lo + batch_size, x2d.shape[0])
         if gather == "partials":
             acc = _accumulators_from_partials(sampler, dataset, x2d[lo:hi], x2d_flip[lo:hi], gt_parts[lo:hi], traj[lo:hi], cam,
-                                              hypothesis_chunk, p2)
+                                              hypothesis_chunk, p2, p2_gather)
         else:
             pred = sampler(x2d[lo:hi], gt_parts[lo:hi], input_2d_flip=x2d_flip[lo:hi])      # [b,T,P,F,J,3]
             acc = evaluate_accumulators(pred, gt_parts[lo:hi], x2d[lo:hi], traj[lo:hi], cam, dataset, p2=p2)
@@ -235,16 +247,26 @@ def evaluate_sequence(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, 
     return sums, n
 
 
-def _accumulators_from_partials(sampler, dataset, x2d, x2d_flip, gt_parts, traj, cam, hypothesis_chunk, p2):
+def _accumulators_from_partials(sampler, dataset, x2d, x2d_flip, gt_parts, traj, cam, hypothesis_chunk, p2, p2_gather="hypotheses"):
     """One batch of clips through sample -> reduce, chunk by chunk, then one exchange of the states."""
-    from .evaluate import protocol2_accumulators
+    from .evaluate import (accumulate_procrustes, gather_partial_states, protocol2_accumulators,
+                           protocol2_accumulators_sharded)
     from .parallel import gather_hypotheses
-    state, kept = None, []
+    p2_partials = p2 and p2_gather == "partials"
+    state, p2_state, kept = None, None, []
     for pred, h0, _ in sampler.sample_chunks(x2d, gt_parts, input_2d_flip=x2d_flip, chunk=hypothesis_chunk):
         state = accumulate_partials(state, pred, h0, gt_parts, x2d, traj, cam, dataset)
-        if p2:
+        if p2_partials:
+            p2_state = accumulate_procrustes(p2_state, pred, h0, gt_parts, x2d, traj, cam, dataset)
+        elif p2:
             kept.append(pred)
+        del pred
     P = sampler.model.num_proposals
+    if p2_partials:       # both states of every rank in ONE all-gather; no hypothesis is kept or exchanged
+        gathered = gather_partial_states(state, P, sampler.group, p2_state=p2_state)
+        acc = evaluate_accumulators_sharded(None, None, P, gt_parts, x2d, traj, cam, dataset, state=gathered)
+        acc.update(protocol2_accumulators_sharded(None, gathered, P, gt_parts, dataset))
+        return acc
     acc = evaluate_accumulators_sharded(None, None, P, gt_parts, x2d, traj, cam, dataset, group=sampler.group, state=state)
     if p2:
         full = gather_hypotheses(torch.cat(kept, dim=2) if len(kept) > 1 else kept[0], P, sampler.group)

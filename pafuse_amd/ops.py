@@ -897,3 +897,108 @@ def combine_poses(states, shape, num_proposals, merged=None, want=("mean", "pick
     if ("idx" in want or "pick" in want) and not bool((idx >= 0).any()):
         raise _lib.PafuseError("combine_poses: no state holds a J-Agg candidate (mean-only states have no pick)")
     return out
+
+
+# ------------------------------------------------------------------------------ Protocol #2 from partial states
+PROCRUSTES_HEAD_BYTES_PER_ELEMENT = 16   # float jbest, e2, sel + int32 idx per (b, t, f, j)
+
+
+def procrustes_partials_bytes(B, T, P_r, F, J):
+    """Bytes of the state pafuse_procrustes_partials writes for a shard of P_r hypotheses (the formula of
+    pafuse_procrustes_partials_bytes, restated so that sizes can be planned without the library): the head, independent
+    of P_r, then 8 bytes per local hypothesis and step."""
+    return PROCRUSTES_HEAD_BYTES_PER_ELEMENT * B * T * F * J + 8 * P_r * T
+
+
+def procrustes_partial_views(state, B, T, P_r, F, J):
+    """Typed views of a flat Protocol #2 state (1-D float64 tensor of procrustes_partials_bytes / 8 elements, or longer: a
+    padded one): jbest / e2 / sel [B,T,F,J] f32, idx [B,T,F,J] i32, psum [P_r,T] f64."""
+    n = B * T * F * J
+    _need(state.dim() == 1 and state.dtype == torch.float64 and state.is_contiguous()
+          and state.numel() * 8 >= procrustes_partials_bytes(B, T, P_r, F, J), "procrustes_partial_views: not a state of these sizes")
+    f32 = state[:2 * n].view(torch.float32)
+    return {"jbest": f32[:n].view(B, T, F, J), "e2": f32[n:2 * n].view(B, T, F, J), "sel": f32[2 * n:3 * n].view(B, T, F, J),
+            "idx": f32[3 * n:].view(torch.int32).view(B, T, F, J), "psum": state[2 * n:2 * n + P_r * T].view(P_r, T)}
+
+
+def procrustes_partials(pred, gt, x2d, traj, cam, conn, h0, out=None):
+    """One shard's Protocol #2 state (pafuse_procrustes_partials): pred [B,T,P_r,F,J,3] the LOCAL hypotheses
+    [h0, h0 + P_r) of the run, gt [B,F,J,3], x2d [B,F,J,2], traj [B,F,3] (or [B,F,1,3]), cam [9], conn int32 [J] -> the flat
+    state, a 1-D float64 tensor (procrustes_partial_views names its pieces).  `out`: a float64 buffer at least that long
+    to write into; the result is then `out` itself.  fp32 operands on one HIP device, contiguous.  J <= 256."""
+    lib = _lib.load()
+    _need(pred.dim() == 6 and pred.shape[-1] == 3, f"procrustes_partials: pred must be [B,T,P_r,F,J,3], got {tuple(pred.shape)}")
+    B, T, P_r, F, J, _ = pred.shape
+    _need(tuple(gt.shape) == (B, F, J, 3) and tuple(x2d.shape) == (B, F, J, 2) and traj.numel() == B * F * 3
+          and cam.numel() == 9 and conn.numel() == J, "procrustes_partials: operands do not match pred")
+    _need(T > 0 and F > 0 and J > 0 and int(h0) >= 0, "procrustes_partials: T, F, J > 0 and h0 >= 0")
+    ops = (pred, gt, x2d, traj, cam, conn)
+    _need(all(t.is_cuda and t.device == pred.device and t.is_contiguous() for t in ops), "procrustes_partials: contiguous "
+          "tensors on one HIP device (no CPU fallback)")
+    _need(all(t.dtype == torch.float32 for t in ops[:5]) and conn.dtype == torch.int32, "procrustes_partials: dtypes")
+    dev = pred.device
+    need = procrustes_partials_bytes(B, T, P_r, F, J)
+    if out is None:
+        out = torch.empty(need // 8, device=dev, dtype=torch.float64)
+    _need(out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous()
+          and out.numel() * 8 >= need, f"procrustes_partials: out must be a float64 buffer of {need} bytes or more on {dev}")
+    wbytes = int(lib.pafuse_procrustes_partials_workspace_bytes(B, T, P_r, F, J))
+    work = torch.empty(max(wbytes // 8, 1), device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_procrustes_partials(
+            _data(pred), _data(gt), _data(x2d), _data(traj), _data(cam), _data(conn), B, T, P_r, F, J, int(h0),
+            _data(out), out.numel() * 8, work.data_ptr(), work.numel() * 8, _stream(pred)))
+    return out
+
+
+def combine_procrustes(states, shape, num_proposals, sums=None, gt=None, conn=None, merged=None,
+                       want=("jbest", "pagg", "jagg", "pick")):
+    """pafuse_procrustes_combine: `states` [W, L] float64 (W flat Protocol #2 states of the same (B,T,F,J) = `shape`, one per
+    row, in ascending-h0 order; rows may carry their psum tail and padding, which is not read) -> dict with the entries
+    named in `want`: "jbest", "pagg", "jagg" [B,T,F,J] fp32 and "pick" [B,T,F,J] int32 (what procrustes_errors gives for all
+    hypotheses).  "pagg" aligns the mean pose and needs `sums` [W, >= 3*B*T*F*J] float64 - rows that BEGIN with the
+    double sum[n][3] of the same shards, i.e. the Protocol #1 states (hypothesis_partials) or pose states (pose_partials) as
+    they are - plus gt [B,F,J,3] and conn int32 [J]; the sums are added in row order and divided by `num_proposals`, the
+    TOTAL hypothesis count.  `merged`: a float64 buffer that receives the head of the union's state (2*B*T*F*J
+    elements); of the operands it may only be states[0] (a running state)."""
+    lib = _lib.load()
+    B, T, F, J = (int(v) for v in shape)
+    n = B * T * F * J
+    want = tuple(want)
+    _need(all(k in ("jbest", "pagg", "jagg", "pick") for k in want), f"combine_procrustes: want holds jbest, pagg, jagg, pick - got {want}")
+    _need(states.dim() == 2 and states.dtype == torch.float64 and states.is_cuda and states.stride(1) == 1
+          and states.shape[0] >= 1 and states.shape[1] >= 2 * n and (states.shape[0] == 1 or states.stride(0) >= 2 * n),
+          "combine_procrustes: states must be [W, >= 2*B*T*F*J] float64 rows (a column slice of a wider buffer is fine)")
+    _need(T > 0 and F > 0 and 0 < J <= 256 and B >= 0, "combine_procrustes: bad shape (J <= 256)")
+    _need(want or merged is not None, "combine_procrustes: nothing to compute")
+    _need(int(num_proposals) >= 1, "combine_procrustes: num_proposals >= 1")
+    dev = states.device
+    W = states.shape[0]
+    row = lambda t: t.stride(0) if W > 1 else t.shape[1]   # elements between rows
+    if "pagg" in want:
+        _need(sums is not None and gt is not None and conn is not None, "combine_procrustes: pagg needs sums, gt and conn")
+        _need(sums.dim() == 2 and sums.dtype == torch.float64 and sums.is_cuda and sums.device == dev and sums.stride(1) == 1
+              and sums.shape[0] == W and sums.shape[1] >= 3 * n and (W == 1 or sums.stride(0) >= 3 * n),
+              "combine_procrustes: sums must be [W, >= 3*B*T*F*J] float64 rows on the device of the states")
+        _need(tuple(gt.shape) == (B, F, J, 3) and conn.numel() == J and all(t.is_cuda and t.device == dev and t.is_contiguous()
+              for t in (gt, conn)) and gt.dtype == torch.float32 and conn.dtype == torch.int32,
+              "combine_procrustes: gt [B,F,J,3] f32, conn [J] int32, contiguous on the device of the states")
+    if merged is not None:
+        _need(merged.is_cuda and merged.device == dev and merged.dtype == torch.float64 and merged.is_contiguous()
+              and merged.numel() >= 2 * n, "combine_procrustes: merged must hold 2*B*T*F*J float64")
+        lo = states.data_ptr()
+        hi = lo + ((W - 1) * row(states) + 2 * n) * 8
+        _need(merged.data_ptr() == lo or not (merged.data_ptr() < hi and merged.data_ptr() + 16 * n > lo),
+              "combine_procrustes: of its operands the merged state may only lie over the first")
+    out = {k: torch.empty(B, T, F, J, device=dev, dtype=torch.int32 if k == "pick" else torch.float32) for k in want}
+    if n == 0:
+        return out
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    pagg = "pagg" in want
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_procrustes_combine(
+            states.data_ptr(), W, row(states) * 8, sums.data_ptr() if pagg else None,
+            row(sums) * 8 if pagg else 0, gt.data_ptr() if pagg else None,
+            conn.data_ptr() if pagg else None, B, T, F, J, int(num_proposals),
+            None if merged is None else merged.data_ptr(), ptr("jbest"), ptr("pagg"), ptr("jagg"), ptr("pick"), _stream(states)))
+    return out

@@ -11,6 +11,8 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::ddim_loop(..., precision)                        D3DP.ddim_sample[_flip]        common/diffusionpose.py:227-316
   pafuse::hypothesis_partials(pred, gt, x2d, traj, cam, conn, pbroot, part, num_parts, h0)   one shard's partial reductions
   pafuse::combine_partials(states, gt, conn, pbroot, T, num_proposals)   jbest, pagg, jagg, paggpb from W states   main_h3wb.py:327-362
+  pafuse::procrustes_partials(pred, gt, x2d, traj, cam, conn, h0)   one shard's Protocol #2 state
+  pafuse::procrustes_combine(states, sums, gt, conn, T, num_proposals)   jbest, pagg, jagg, pick from W states   main_h3wb.py:381-395
   pafuse::aggregate_poses(pred, conn, x2d?, traj?, cam?)  P-Agg mean pose, J-Agg pose and its hypothesis index, one shard
   pafuse::noise_fill(key, draw, B, P, F, J)               one draw of noise stream v1 as a tensor (DESIGN.md section 6)
 
@@ -400,6 +402,38 @@ def combine_partials(states: torch.Tensor, gt: torch.Tensor, conn: torch.Tensor,
 def _(states, gt, conn, pbroot, T, num_proposals):
     B, F, J, _ = gt.shape
     return [gt.new_empty(B, T, F, J) for _ in range(4)]
+
+
+# ---------------------------------------------------------------------------- Protocol #2 from partial states
+@torch.library.custom_op("pafuse::procrustes_partials", mutates_args=(), device_types="cuda")
+def procrustes_partials(pred: torch.Tensor, gt: torch.Tensor, x2d: torch.Tensor, traj: torch.Tensor, cam: torch.Tensor,
+                        conn: torch.Tensor, h0: int) -> torch.Tensor:
+    """pafuse_amd.ops.procrustes_partials: the flat float64 Protocol #2 state of the local hypotheses [h0, h0 + P_r)."""
+    from . import ops
+    return ops.procrustes_partials(pred, gt, x2d, traj, cam, conn, h0)
+
+
+@procrustes_partials.register_fake
+def _(pred, gt, x2d, traj, cam, conn, h0):
+    B, T, P_r, F, J, _ = pred.shape
+    return pred.new_empty(2 * B * T * F * J + P_r * T, dtype=torch.float64)
+
+
+@torch.library.custom_op("pafuse::procrustes_combine", mutates_args=(), device_types="cuda")
+def procrustes_combine(states: torch.Tensor, sums: torch.Tensor, gt: torch.Tensor, conn: torch.Tensor, T: int,
+                       num_proposals: int) -> List[torch.Tensor]:
+    """pafuse_amd.ops.combine_procrustes on states [W, L] and sums [W, >= 3*B*T*F*J] (rows beginning with the fp64 sums of
+    the same shards): -> [jbest, pagg, jagg [B,T,F,J] fp32, pick [B,T,F,J] int32]."""
+    from . import ops
+    B, F, J, _ = gt.shape
+    m = ops.combine_procrustes(states, (B, T, F, J), num_proposals, sums=sums, gt=gt, conn=conn)
+    return [m["jbest"], m["pagg"], m["jagg"], m["pick"]]
+
+
+@procrustes_combine.register_fake
+def _(states, sums, gt, conn, T, num_proposals):
+    B, F, J, _ = gt.shape
+    return [gt.new_empty(B, T, F, J) for _ in range(3)] + [gt.new_empty((B, T, F, J), dtype=torch.int32)]
 
 
 # ------------------------------------------------------------------------------------------ aggregates as poses
