@@ -1665,10 +1665,13 @@ struct AttnParams {
 
 // Item -> (sequence, head).  The 8 heads of a sequence read interleaved 112..192-byte slices of the same qkv rows;
 // workgroups b and b+8 share an XCD (round-robin dispatch), so the heads of one sequence are given to workgroups of
-// one XCD and the partially used cache lines are L2 hits for 7 of them (speed only; plain order when nseq % 8 != 0).
+// one XCD and the partially used cache lines are L2 hits for 7 of them (speed only).  That order walks, for each of the 8
+// residues lo = seq % 8, the (nseq / 8) * heads pairs u in runs of ITEMS: it is a bijection onto (seq, head) only when
+// nseq % 8 == 0 AND ITEMS divides (nseq / 8) * heads - otherwise the last run of every residue would reach past the last
+// pair (odd heads at nseq = 8 mod 16 under the two-item forms: sequences nseq .. nseq + 3).  Plain order in every other case.
 template <int ITEMS>
 __device__ __forceinline__ void attn_item(int64_t i, int64_t nseq, int heads, int64_t& seq, int& head) {
-    if (nseq % 8 == 0) {
+    if (nseq % 8 == 0 && ((nseq / 8) * heads) % ITEMS == 0) {
         const int64_t blk = i / ITEMS;
         const int lo = (int)(blk % 8);
         const int64_t u = (blk / 8) * ITEMS + (i % ITEMS);

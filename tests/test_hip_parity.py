@@ -1303,7 +1303,8 @@ def test_c_abi_from_plain_c():
 
 def test_unit_ops_on_a_seeded_sweep_of_shapes():
     """40 seeded random shapes inside the documented limits (M tails, every N % 32 class, K up to 1152; sequence
-    lengths 1..80, head dims 4..48, contiguous and strided sequences; LayerNorm widths up to 768): each against an
+    lengths 1..80, head dims 4..48, 1..8 heads odd counts included, contiguous and strided sequences, every fourth
+    case a multiple of 8 sequences, guard rows behind the last sequence; LayerNorm widths up to 768): each against an
     fp64 evaluation of the same op."""
     import random
     from pafuse_amd import ops
@@ -1317,23 +1318,29 @@ def test_unit_ops_on_a_seeded_sweep_of_shapes():
         out = ops.linear(x.to(DEV), w.to(DEV), b.to(DEV), act).cpu().double()
         assert torch.allclose(out, ref, rtol=0, atol=2.5e-7 * K ** 0.5 + 1e-6), ("linear", M, N, K, act)
     for case in range(16):
-        heads = rng.choice([1, 2, 4, 8])
+        heads = rng.choice([1, 2, 3, 4, 5, 7, 8])
         d = 4 * rng.randint(1, 12)
         L, S = rng.randint(1, 80), rng.randint(1, 9)
+        if case % 4 == 0:                              # a sequence count that takes the XCD-friendly item order (nseq % 8 == 0)
+            S = rng.choice([8, 16, 24])
         C = heads * d
         temporal = rng.random() < 0.5
+        # guard rows: room for 8 more sequences of the same addressing behind the last one, random in qkv, to stay 0 in the output
         if temporal:                                   # S groups of J interleaved sequences, tokens J rows apart
             J = rng.randint(1, 7)
-            qkv = _seeded((S * L * J, 3 * C), 400 + case)
+            own = S * L * J
+            qkv = _seeded(((S + -(-8 // J)) * L * J, 3 * C), 400 + case)
             out = ops.attention(qkv.to(DEV), heads, S * J, L, group=J, group_stride=L * J, seq_stride=1, tok_stride=J).cpu()
-            q = qkv.view(S, L, J, 3, heads, d).permute(3, 0, 2, 4, 1, 5).double()          # 3, S, J, h, L, d
+            q = qkv[:own].view(S, L, J, 3, heads, d).permute(3, 0, 2, 4, 1, 5).double()    # 3, S, J, h, L, d
             o = torch.softmax(q[0] @ q[1].transpose(-1, -2) * d ** -0.5, -1) @ q[2]         # S, J, h, L, d
-            ref = o.permute(0, 3, 1, 2, 4).reshape(S * L * J, C)
+            ref = o.permute(0, 3, 1, 2, 4).reshape(own, C)
         else:
-            qkv = _seeded((S * L, 3 * C), 400 + case)
+            own = S * L
+            qkv = _seeded(((S + 8) * L, 3 * C), 400 + case)
             out = ops.attention(qkv.to(DEV), heads, S, L).cpu()
-            ref = _attn_ref(qkv.double(), S, L, heads)
-        assert torch.allclose(out.double(), ref, rtol=0, atol=3e-6), ("attention", heads, d, L, S, temporal)
+            ref = _attn_ref(qkv[:own].double(), S, L, heads)
+        assert torch.allclose(out[:own].double(), ref, rtol=0, atol=3e-6), ("attention", heads, d, L, S, temporal)
+        assert not bool((out[own:] != 0).any()), ("attention wrote rows no sequence owns", heads, d, L, S, temporal)
     for case in range(8):
         M, C = rng.randint(1, 300), rng.randint(1, 768)
         x, g, b = _seeded((M, C), 500 + case), _seeded((C,), 600 + case), _seeded((C,), 700 + case)
