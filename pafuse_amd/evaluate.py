@@ -17,6 +17,11 @@ P-Agg is aligned at combine time (``ops.combine_procrustes``), from the fp64 sum
 
 ``accumulate_poses`` / ``aggregate_poses_sharded`` return the aggregates themselves - the P-Agg mean pose and the J-Agg
 pose with its hypothesis index - by the same scheme and without a ground truth (``ops.pose_partials``, ``ops.combine_poses``).
+
+The three families share their host code: ``_operands`` checks and converts the arguments of every entry point,
+``_RunningState.fold`` is the one running reduction (``PartialState``, ``Procrustes2State`` and ``PoseState`` only declare
+what each family keeps; every ``accumulate_*`` hands ``fold`` its partials op and its combine op), and ``_exchange`` is the
+one collective (``gather_partial_states`` and ``aggregate_poses_sharded`` give it their pieces).
 """
 import torch
 import torch.distributed as dist
@@ -37,26 +42,47 @@ def _tables(dataset, num_kps, device):
 
 def _operands(pred_parts, gt_parts, inputs_2d, traj, cam, dataset, who, name="pred_parts", axis="P"):
     """The argument checks and conversions every evaluation entry point shares: -> contiguous fp32 pred, gt, x2d,
-    traj [B,F,3], cam [9] on the device of the predictions, and the conn / pbroot index tables."""
+    traj [B,F,3], cam [9] on the device of the predictions, and the conn / pbroot index tables.  gt_parts=None (the pose
+    aggregation has no ground truth): inputs_2d, traj and cam may then be absent too, all three; what is absent comes
+    back as None."""
     if not pred_parts.is_cuda:
         raise _lib.PafuseError(f"{who} runs on the HIP device only (no CPU fallback)")
     dev = pred_parts.device
     if pred_parts.dim() != 6 or pred_parts.shape[-1] != 3:
         raise ValueError(f"{name} must be [B,T,{axis},F,J,3], got {tuple(pred_parts.shape)}")
     B, T, P, F, J, _ = pred_parts.shape
+    given = [t is not None for t in (inputs_2d, traj, cam)]
+    if gt_parts is None and any(given) and not all(given):
+        raise ValueError(f"{who}: inputs_2d, traj and cam come together (none of them: mean-only)")
+    reproj = gt_parts is not None or all(given)
     # the kernels index every operand by (B, F, J): check before launching
-    if (tuple(gt_parts.shape) != (B, F, J, 3) or tuple(inputs_2d.shape) != (B, F, J, 2) or traj.numel() != B * F * 3
-            or cam.numel() < 9):
-        raise ValueError(f"{who}: operands do not match pred {tuple(pred_parts.shape)}: gt "
-                         f"{tuple(gt_parts.shape)}, 2d {tuple(inputs_2d.shape)}, traj {tuple(traj.shape)}, cam {tuple(cam.shape)}")
-    if any(t.device != dev for t in (gt_parts, inputs_2d, traj)):
+    if ((gt_parts is not None and tuple(gt_parts.shape) != (B, F, J, 3))
+            or (reproj and (tuple(inputs_2d.shape) != (B, F, J, 2) or traj.numel() != B * F * 3 or cam.numel() < 9))):
+        seen = (("gt", gt_parts), ("2d", inputs_2d), ("traj", traj), ("cam", cam))
+        raise ValueError(f"{who}: operands do not match pred {tuple(pred_parts.shape)}: "
+                         + ", ".join(f"{k} {tuple(t.shape)}" for k, t in seen if t is not None))
+    if any(t is not None and t.device != dev for t in (gt_parts, inputs_2d, traj)):
         raise ValueError(f"{who}: all tensors must live on the device of {name}")
     covered = sorted(j for idx in dataset.parts_joint_indices.values() for j in idx)
     if covered != list(range(J)):
         raise ValueError("dataset.parts_joint_indices must cover every joint exactly once")
     conn, pbroot = _tables(dataset, J, dev)
-    return (pred_parts.contiguous().float(), gt_parts.contiguous().float(), inputs_2d.contiguous().float(),
-            traj.reshape(B, F, 3).contiguous().float(), cam.reshape(-1)[:9].contiguous().float().to(dev), conn, pbroot)
+    x2d = tr = cm = None
+    if reproj:
+        x2d, tr = inputs_2d.contiguous().float(), traj.reshape(B, F, 3).contiguous().float()
+        cm = cam.reshape(-1)[:9].contiguous().float().to(dev)
+    return (pred_parts.contiguous().float(), None if gt_parts is None else gt_parts.contiguous().float(), x2d, tr, cm,
+            conn, pbroot)
+
+
+def _per_t(x):
+    """[B,T,F,J'] fp32 -> [T]: the mean over (b, f, j) in fp32"""
+    return x.permute(1, 0, 2, 3).reshape(x.shape[1], -1).mean(dim=-1)
+
+
+def _per_t64(x):
+    """[B,T,F,J] fp32 -> [T]: the mean over (b, f, j) in fp64, rounded to fp32 once (Protocol #2, like the reference)"""
+    return x.double().permute(1, 0, 2, 3).reshape(x.shape[1], -1).mean(dim=-1).float()
 
 
 def evaluate_accumulators(pred_parts, gt_parts, inputs_2d, traj, cam, dataset, p2=False):
@@ -76,10 +102,7 @@ def evaluate_accumulators(pred_parts, gt_parts, inputs_2d, traj, cam, dataset, p
         pbroot.data_ptr(), B, T, P, F, J, e3.data_ptr(), epb.data_ptr(), jbest.data_ptr(), pagg.data_ptr(),
         jagg.data_ptr(), paggpb.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
 
-    def per_t(x):                                            # [B,T,F,J'] -> [T]
-        return x.permute(1, 0, 2, 3).reshape(T, -1).mean(dim=-1)
-
-    out = {"j_best": per_t(jbest), "p_agg": per_t(pagg), "j_agg": per_t(jagg), "p_agg_pb": per_t(paggpb)}
+    out = {"j_best": _per_t(jbest), "p_agg": _per_t(pagg), "j_agg": _per_t(jagg), "p_agg_pb": _per_t(paggpb)}
     out["p_best"] = e3.permute(1, 2, 0, 3, 4).reshape(T, P, -1).mean(dim=-1).min(dim=1).values
     eh = epb.permute(1, 2, 0, 3, 4)                          # t h b f n
     per_h = eh.reshape(T, P, -1).mean(dim=-1)
@@ -88,7 +111,7 @@ def evaluate_accumulators(pred_parts, gt_parts, inputs_2d, traj, cam, dataset, p
     for part, idx in dataset.parts_joint_indices.items():
         ph = eh[..., idx].reshape(T, P, -1).mean(dim=-1)
         out["p_best_pb_" + part] = ph.gather(1, best.view(-1, 1)).squeeze(1)
-        out["p_agg_pb_" + part] = per_t(paggpb[..., idx])
+        out["p_agg_pb_" + part] = _per_t(paggpb[..., idx])
     if p2:
         out.update(_protocol2(pred, gt, x2d, tr, cm, conn))
     return out
@@ -101,12 +124,9 @@ def _protocol2(pred, gt, x2d, traj, cam, conn):
     B, T, P, F, J, _ = pred.shape
     r = procrustes_errors(pred, gt, x2d, traj, cam, conn, pick=False)
 
-    def per_t(x):                                            # [B,T,F,J] -> [T]
-        return x.double().permute(1, 0, 2, 3).reshape(T, -1).mean(dim=-1).float()
-
     per_h = r["pbest_sums"].permute(1, 2, 0, 3).reshape(T, P, -1).sum(dim=-1) / (B * F * J)
-    return {"p2_j_best": per_t(r["jbest"]), "p2_p_best": per_h.min(dim=1).values.float(), "p2_p_agg": per_t(r["pagg"]),
-            "p2_j_agg": per_t(r["jagg"])}
+    return {"p2_j_best": _per_t64(r["jbest"]), "p2_p_best": per_h.min(dim=1).values.float(), "p2_p_agg": _per_t64(r["pagg"]),
+            "p2_j_agg": _per_t64(r["jagg"])}
 
 
 def protocol2_accumulators(pred_parts, gt_parts, inputs_2d, traj, cam, dataset):
@@ -123,20 +143,65 @@ def _part_table(dataset, num_kps, device):
     return part.to(device)
 
 
-class PartialState:
+class _RunningState:
+    """The running reduction of the hypotheses one rank has seen so far, for any family of partial states: `slots` [2, L]
+    float64 with the merged head in row 0 and the newest chunk's state in row 1, `tails` the per-hypothesis rows of every
+    chunk [(h0, [P_c, ...] f64)] in ascending h0 (a family without a tail keeps none), `h0` / `count` the hypotheses
+    [h0, h0 + count) folded so far."""
+
+    def __init__(self, shape, device):
+        self.shape, self.device = tuple(shape), device    # shape = (B, T, F, J)
+        self.slots, self.tails = None, []
+        self.h0, self.count, self.head_len = None, 0, None
+
+    @property
+    def head(self):
+        return self.slots[0, :self.head_len]
+
+    def tail(self):
+        """the tails of all chunks so far as one [count, ...] tensor (None: nothing kept)"""
+        return torch.cat([t for _, t in self.tails]) if self.tails else None
+
+    def expect(self, who, shape, device, same=True):
+        if self.shape != shape or self.device != device or not same:
+            raise ValueError(f"{who}: the state holds {self.shape}, the chunk is {shape}")
+
+    def fold(self, who, count, h0, head, tail, write, merge):
+        """Fold the chunk of `count` hypotheses from `h0` on and return self.  `head`: float64 elements of the family's
+        head; `tail`: shape of its per-hypothesis row behind the head (None: no tail); `write(row)` writes the chunk's
+        state into the flat buffer `row`; `merge(slots)` merges slots[1] into slots[0] in place."""
+        h0 = int(h0)
+        if self.h0 is not None and h0 != self.h0 + self.count:
+            raise ValueError(f"{who}: chunk starts at hypothesis {h0}, the state ends at {self.h0 + self.count}")
+        L = head + (count * torch.Size(tail).numel() if tail is not None else 0)
+        first = self.slots is None
+        if first or self.slots.shape[1] < L:
+            slots = torch.empty(2, L, device=self.device, dtype=torch.float64)
+            if not first:
+                slots[0, :head] = self.slots[0, :head]
+            self.slots = slots
+        row = self.slots[0 if first else 1]
+        write(row)
+        if tail is not None:
+            self.tails.append((h0, row[head:L].view(count, *tail).clone()))
+        if not first:     # running head <- running head (+) this chunk, in place (the combine kernels read each element before they write it)
+            merge(self.slots)
+        if self.h0 is None:
+            self.h0 = h0
+        self.count += count
+        self.head_len = head
+        return self
+
+
+class PartialState(_RunningState):
     """The running reduction of the hypotheses one rank has seen so far: the merged head of the kernel's state (40 bytes
     per (b,t,f,j), independent of how many hypotheses went in) and the per-hypothesis sums of every chunk."""
 
     def __init__(self, shape, num_parts, device):
-        self.shape, self.num_parts, self.device = tuple(shape), num_parts, device    # shape = (B, T, F, J)
-        self.slots = None        # [2, L] float64: row 0 the running head, row 1 the newest chunk's state
-        self.hsums = []          # [(h0, hsum [P_c,T,1+num_parts] f64)] in ascending h0
-        self.h0, self.count = None, 0
+        super().__init__(shape, device)
+        self.num_parts = num_parts
 
-    @property
-    def head(self):
-        B, T, F, J = self.shape
-        return self.slots[0, :5 * B * T * F * J]
+    hsums = property(lambda self: self.tails)             # [(h0, hsum [P_c,T,1+num_parts] f64)] in ascending h0
 
 
 def accumulate_partials(state, pred_local, h0, gt_parts, inputs_2d, traj, cam, dataset):
@@ -144,36 +209,22 @@ def accumulate_partials(state, pred_local, h0, gt_parts, inputs_2d, traj, cam, d
     it.  Chunks come in ascending h0 and follow each other without a gap; memory: the chunk, two 40-byte-per-(b,t,f,j)
     heads and [P_c,T,1+parts] doubles - never anything of size P."""
     from . import ops
-    pred, gt, x2d, tr, cm, conn, pbroot = _operands(pred_local, gt_parts, inputs_2d, traj, cam, dataset, "accumulate_partials",
-                                                    name="pred_local", axis="P_c")
+    who = "accumulate_partials"
+    pred, gt, x2d, tr, cm, conn, pbroot = _operands(pred_local, gt_parts, inputs_2d, traj, cam, dataset, who, name="pred_local",
+                                                    axis="P_c")
     B, T, P_c, F, J, _ = pred.shape
+    shape = (B, T, F, J)
     np_ = len(dataset.parts_joint_indices)
     if not 1 <= np_ <= _lib.MAX_PARTS:
         raise ValueError(f"the partial reductions keep per-part sums for 1 .. {_lib.MAX_PARTS} parts")
     part = _part_table(dataset, J, pred.device)
     if state is None:
-        state = PartialState((B, T, F, J), np_, pred.device)
-    if state.shape != (B, T, F, J) or state.num_parts != np_ or state.device != pred.device:
-        raise ValueError(f"accumulate_partials: the state holds {state.shape}, the chunk is {(B, T, F, J)}")
-    if state.h0 is not None and int(h0) != state.h0 + state.count:
-        raise ValueError(f"accumulate_partials: chunk starts at hypothesis {h0}, the state ends at {state.h0 + state.count}")
-    n5 = 5 * B * T * F * J
-    L = n5 + P_c * T * (1 + np_)
-    first = state.slots is None
-    if first or state.slots.shape[1] < L:
-        slots = torch.empty(2, L, device=pred.device, dtype=torch.float64)
-        if not first:
-            slots[0, :n5] = state.slots[0, :n5]
-        state.slots = slots
-    row = state.slots[0 if first else 1]
-    ops.hypothesis_partials(pred, gt, x2d, tr, cm, conn, pbroot, part, np_, int(h0), out=row)
-    state.hsums.append((int(h0), ops.partials_views(row, B, T, P_c, F, J, np_)["hsum"].clone()))
-    if not first:     # running head <- running head (+) this chunk, in place (the combine kernel reads each element before it writes it)
-        ops.combine_partials(state.slots, gt, conn, pbroot, (B, T, F, J), 1, merged=state.slots[0], maps=False)
-    if state.h0 is None:
-        state.h0 = int(h0)
-    state.count += P_c
-    return state
+        state = PartialState(shape, np_, pred.device)
+    state.expect(who, shape, pred.device, state.num_parts == np_)
+    return state.fold(
+        who, P_c, h0, 5 * B * T * F * J, (T, 1 + np_),
+        lambda row: ops.hypothesis_partials(pred, gt, x2d, tr, cm, conn, pbroot, part, np_, int(h0), out=row),
+        lambda slots: ops.combine_partials(slots, gt, conn, pbroot, shape, 1, merged=slots[0], maps=False))
 
 
 class GatheredStates:
@@ -186,55 +237,62 @@ class GatheredStates:
         self.states, self.hsums, self.p2_states, self.psum = states, hsums, p2_states, psum
 
 
+def _exchange(pieces, h0, count, num_proposals, group, device):
+    """The one collective of an evaluation.  `pieces`: [(head, tail)], reductions of the SAME hypotheses [h0, h0 + count)
+    of this rank - head a flat float64 tensor, tail [count, ...] float64 per-hypothesis rows or None.  On the wire every
+    rank sends one flat buffer: piece after piece, each its head and then its tail padded to the largest shard
+    (parallel.shard_counts); ONE all_gather_into_tensor (through the host on a gloo group).  -> per piece (rows, tail):
+    rows [W, >= head] the ranks' rows in rank (= ascending-h0) order - column slices of the one received buffer - and
+    tail [P, ...] the un-padded tails concatenated in that order.  Without torch.distributed: the pieces as they are."""
+    from .parallel import shard_counts, shard_range
+    world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
+    if world == 1:
+        if h0 != 0 or count != num_proposals:
+            raise ValueError(f"the state holds hypotheses [{h0}, {h0 + count}) of {num_proposals}")
+        return [(head.view(1, -1), tail) for head, tail in pieces]
+    rank = dist.get_rank(group)
+    lo, hi = shard_range(num_proposals, rank, world)
+    if (h0, count) != (lo, hi - lo):
+        raise ValueError(f"rank {rank} of {world} owns hypotheses [{lo}, {hi}) of {num_proposals}, its state holds "
+                         f"[{h0}, {h0 + count})")
+    counts = shard_counts(num_proposals, world)
+    pmax = max(counts)
+    spans, off = [], 0                                     # per piece: where its head begins, its tail begins, the piece ends
+    for head, tail in pieces:
+        end = off + head.numel() + (0 if tail is None else pmax * tail.shape[1:].numel())
+        spans.append((off, off + head.numel(), end))
+        off = end
+    send = torch.zeros(off, device=device, dtype=torch.float64)
+    for (head, tail), (a, b, _) in zip(pieces, spans):
+        send[a:b] = head
+        if tail is not None:
+            send[b:b + tail.numel()] = tail.reshape(-1)
+    if dist.get_backend(group) == "gloo":                  # rehearsal on a box with fewer GPUs than ranks
+        send = send.cpu()
+    recv = send.new_empty(world * send.numel())
+    dist.all_gather_into_tensor(recv, send, group=group)
+    recv = recv.view(world, -1).to(device)
+    out = []
+    for (_, tail), (a, b, end) in zip(pieces, spans):
+        if tail is not None:
+            tail = torch.cat([recv[r, b:end].view(pmax, *tail.shape[1:])[:counts[r]] for r in range(world)])
+        out.append((recv[:, a:end], tail))
+    return out
+
+
 def gather_partial_states(state, num_proposals, group=None, p2_state=None):
     """ONE all-gather of equal-sized flat buffers (ragged shards are padded to the largest; through the host on a gloo
     group): per rank the Protocol #1 state and, when `p2_state` (a Procrustes2State over the same hypotheses) is given,
     the Protocol #2 state right behind it.  -> GatheredStates."""
-    from .parallel import shard_counts, shard_range
-    B, T, F, J = state.shape
-    n = B * T * F * J
-    n5, nv = 5 * n, 1 + state.num_parts
-    dev = state.device
-    hs = torch.cat([h for _, h in state.hsums]) if state.hsums else torch.zeros(0, T, nv, device=dev, dtype=torch.float64)
-    ps = None
+    pieces = [(state.head, state.tail())]
     if p2_state is not None:
-        if p2_state.shape != state.shape or p2_state.device != dev or (p2_state.h0, p2_state.count) != (state.h0, state.count):
+        if (p2_state.shape != state.shape or p2_state.device != state.device
+                or (p2_state.h0, p2_state.count) != (state.h0, state.count)):
             raise ValueError(f"the Protocol #2 state holds [{p2_state.h0}, +{p2_state.count}) of {p2_state.shape}, the "
                              f"Protocol #1 state [{state.h0}, +{state.count}) of {state.shape}")
-        ps = torch.cat([q for _, q in p2_state.psums]) if p2_state.psums else torch.zeros(0, T, device=dev, dtype=torch.float64)
-    world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
-    if world == 1:
-        if state.h0 != 0 or state.count != num_proposals:
-            raise ValueError(f"the state holds hypotheses [{state.h0}, {state.h0 + state.count}) of {num_proposals}")
-        return GatheredStates(state.shape, state.num_parts, dev, state.slots[:1], hs,
-                              None if p2_state is None else p2_state.slots[:1], ps)
-    rank = dist.get_rank(group)
-    lo, hi = shard_range(num_proposals, rank, world)
-    if (state.h0, state.count) != (lo, hi - lo):
-        raise ValueError(f"rank {rank} of {world} owns hypotheses [{lo}, {hi}) of {num_proposals}, its state holds "
-                         f"[{state.h0}, {state.h0 + state.count})")
-    counts = shard_counts(num_proposals, world)
-    pmax = max(counts)
-    L1 = n5 + pmax * T * nv
-    L2 = 0 if p2_state is None else 2 * n + pmax * T
-    send = torch.zeros(L1 + L2, device=dev, dtype=torch.float64)
-    send[:n5] = state.head
-    send[n5:n5 + hs.numel()] = hs.reshape(-1)
-    if p2_state is not None:
-        send[L1:L1 + 2 * n] = p2_state.head
-        send[L1 + 2 * n:L1 + 2 * n + ps.numel()] = ps.reshape(-1)
-    via_host = dist.get_backend(group) == "gloo"          # rehearsal on a box with fewer GPUs than ranks
-    if via_host:
-        send = send.cpu()
-    recv = send.new_empty(world * send.numel())
-    dist.all_gather_into_tensor(recv, send, group=group)
-    recv = recv.view(world, -1).to(dev)
-    tails = [recv[r, n5:L1].view(pmax, T, nv)[:counts[r]] for r in range(world)]
-    out = GatheredStates(state.shape, state.num_parts, dev, recv[:, :L1], torch.cat(tails))
-    if p2_state is not None:
-        out.p2_states = recv[:, L1:]
-        out.psum = torch.cat([recv[r, L1 + 2 * n:].view(pmax, T)[:counts[r]] for r in range(world)])
-    return out
+        pieces.append((p2_state.head, p2_state.tail()))
+    got = _exchange(pieces, state.h0, state.count, num_proposals, group, state.device)
+    return GatheredStates(state.shape, state.num_parts, state.device, *(x for piece in got for x in piece))
 
 
 def evaluate_accumulators_sharded(pred_local, h0, num_proposals, gt_parts, inputs_2d, traj, cam, dataset, group=None,
@@ -263,11 +321,7 @@ def evaluate_accumulators_sharded(pred_local, h0, num_proposals, gt_parts, input
     conn, pbroot = _tables(dataset, J, dev)
     m = ops.combine_partials(states.contiguous(), gt_parts.contiguous().float(), conn, pbroot, (B, T, F, J), P)
     jbest, pagg, jagg, paggpb = m["jbest"], m["pagg"], m["jagg"], m["paggpb"]
-
-    def per_t(x):                                            # [B,T,F,J'] -> [T]
-        return x.permute(1, 0, 2, 3).reshape(T, -1).mean(dim=-1)
-
-    out = {"j_best": per_t(jbest), "p_agg": per_t(pagg), "j_agg": per_t(jagg), "p_agg_pb": per_t(paggpb)}
+    out = {"j_best": _per_t(jbest), "p_agg": _per_t(pagg), "j_agg": _per_t(jagg), "p_agg_pb": _per_t(paggpb)}
     hs = hs.permute(1, 0, 2)                                 # [T,P,1+parts] sums over (b,f,j), fp64
     out["p_best"] = (hs[..., 0] / (B * F * J)).float().min(dim=1).values
     per_h = (hs[..., 1:].sum(dim=-1) / (B * F * J)).float()
@@ -276,25 +330,16 @@ def evaluate_accumulators_sharded(pred_local, h0, num_proposals, gt_parts, input
     for i, (part, idx) in enumerate(dataset.parts_joint_indices.items()):
         ph = (hs[..., 1 + i] / (B * F * len(idx))).float()
         out["p_best_pb_" + part] = ph.gather(1, best.view(-1, 1)).squeeze(1)
-        out["p_agg_pb_" + part] = per_t(paggpb[..., idx])
+        out["p_agg_pb_" + part] = _per_t(paggpb[..., idx])
     return out
 
 
 # ------------------------------------------------------------------------------- Protocol #2 from partial states
-class Procrustes2State:
+class Procrustes2State(_RunningState):
     """The running Protocol #2 reduction of the hypotheses one rank has seen so far: the merged head of the kernel's state
     (16 bytes per (b,t,f,j), ops.procrustes_partial_views) and the per-hypothesis sums psum [P_c,T] of every chunk."""
 
-    def __init__(self, shape, device):
-        self.shape, self.device = tuple(shape), device    # shape = (B, T, F, J)
-        self.slots = None        # [2, L] float64: row 0 the running head, row 1 the newest chunk's state
-        self.psums = []          # [(h0, psum [P_c,T] f64)] in ascending h0
-        self.h0, self.count = None, 0
-
-    @property
-    def head(self):
-        B, T, F, J = self.shape
-        return self.slots[0, :2 * B * T * F * J]
+    psums = property(lambda self: self.tails)             # [(h0, psum [P_c,T] f64)] in ascending h0
 
 
 def accumulate_procrustes(state, pred_local, h0, gt_parts, inputs_2d, traj, cam, dataset):
@@ -302,32 +347,17 @@ def accumulate_procrustes(state, pred_local, h0, gt_parts, inputs_2d, traj, cam,
     start one) and return it.  Chunks come in ascending h0 and follow each other without a gap; memory: the chunk, two
     16-byte-per-(b,t,f,j) heads, [B,T,P_c,F] doubles of workspace and [P_c,T] doubles - never anything of size P."""
     from . import ops
-    pred, gt, x2d, tr, cm, conn, _ = _operands(pred_local, gt_parts, inputs_2d, traj, cam, dataset, "accumulate_procrustes",
-                                               name="pred_local", axis="P_c")
+    who = "accumulate_procrustes"
+    pred, gt, x2d, tr, cm, conn, _ = _operands(pred_local, gt_parts, inputs_2d, traj, cam, dataset, who, name="pred_local",
+                                               axis="P_c")
     B, T, P_c, F, J, _ = pred.shape
+    shape = (B, T, F, J)
     if state is None:
-        state = Procrustes2State((B, T, F, J), pred.device)
-    if state.shape != (B, T, F, J) or state.device != pred.device:
-        raise ValueError(f"accumulate_procrustes: the state holds {state.shape}, the chunk is {(B, T, F, J)}")
-    if state.h0 is not None and int(h0) != state.h0 + state.count:
-        raise ValueError(f"accumulate_procrustes: chunk starts at hypothesis {h0}, the state ends at {state.h0 + state.count}")
-    n2 = 2 * B * T * F * J
-    L = n2 + P_c * T
-    first = state.slots is None
-    if first or state.slots.shape[1] < L:
-        slots = torch.empty(2, L, device=pred.device, dtype=torch.float64)
-        if not first:
-            slots[0, :n2] = state.slots[0, :n2]
-        state.slots = slots
-    row = state.slots[0 if first else 1]
-    ops.procrustes_partials(pred, gt, x2d, tr, cm, conn, int(h0), out=row)
-    state.psums.append((int(h0), ops.procrustes_partial_views(row, B, T, P_c, F, J)["psum"].clone()))
-    if not first:     # running head <- running head (+) this chunk, in place (every thread reads its elements before it writes them)
-        ops.combine_procrustes(state.slots, (B, T, F, J), 1, merged=state.slots[0], want=())
-    if state.h0 is None:
-        state.h0 = int(h0)
-    state.count += P_c
-    return state
+        state = Procrustes2State(shape, pred.device)
+    state.expect(who, shape, pred.device)
+    return state.fold(who, P_c, h0, 2 * B * T * F * J, (T,),
+                      lambda row: ops.procrustes_partials(pred, gt, x2d, tr, cm, conn, int(h0), out=row),
+                      lambda slots: ops.combine_procrustes(slots, shape, 1, merged=slots[0], want=()))
 
 
 def protocol2_accumulators_sharded(state, p1, num_proposals, gt_parts, dataset, group=None):
@@ -357,29 +387,20 @@ def protocol2_accumulators_sharded(state, p1, num_proposals, gt_parts, dataset, 
     conn, _ = _tables(dataset, J, dev)
     m = ops.combine_procrustes(gathered.p2_states, (B, T, F, J), P, sums=gathered.states, gt=gt_parts.contiguous().float(),
                                conn=conn, want=("jbest", "pagg", "jagg"))
-
-    def per_t(x):                                            # [B,T,F,J] -> [T]
-        return x.double().permute(1, 0, 2, 3).reshape(T, -1).mean(dim=-1).float()
-
     per_h = (gathered.psum.permute(1, 0) / (B * F * J)).float()          # [T,P]
-    return {"p2_j_best": per_t(m["jbest"]), "p2_p_best": per_h.min(dim=1).values, "p2_p_agg": per_t(m["pagg"]),
-            "p2_j_agg": per_t(m["jagg"])}
+    return {"p2_j_best": _per_t64(m["jbest"]), "p2_p_best": per_h.min(dim=1).values, "p2_p_agg": _per_t64(m["pagg"]),
+            "p2_j_agg": _per_t64(m["jagg"])}
 
 
 # ------------------------------------------------------------------------------------------- aggregates as poses
-class PoseState:
+class PoseState(_RunningState):
     """The running pose reduction of the hypotheses one rank has seen so far: 44 bytes per (b,t,f,j) (ops.pose_views),
     independent of how many hypotheses went in.  `reproj`: the chunks came with 2-D input, trajectory and camera, so the
     state holds J-Agg candidates; a mean-only state has none."""
 
     def __init__(self, shape, device, reproj):
-        self.shape, self.device, self.reproj = tuple(shape), device, bool(reproj)    # shape = (B, T, F, J)
-        self.slots = None        # [2, L] float64: row 0 the running state, row 1 the newest chunk's
-        self.h0, self.count = None, 0
-
-    @property
-    def head(self):
-        return self.slots[0]
+        super().__init__(shape, device)
+        self.reproj = bool(reproj)
 
 
 def accumulate_poses(state, pred_local, h0, dataset, inputs_2d=None, traj=None, cam=None):
@@ -388,47 +409,19 @@ def accumulate_poses(state, pred_local, h0, dataset, inputs_2d=None, traj=None, 
     candidate; none of them: mean-only.  Chunks come in ascending h0 without a gap.  Memory: the chunk and two 44-byte
     per-(b,t,f,j) states - never anything of size P."""
     from . import ops
-    if not pred_local.is_cuda:
-        raise _lib.PafuseError("accumulate_poses runs on the HIP device only (no CPU fallback)")
-    if pred_local.dim() != 6 or pred_local.shape[-1] != 3:
-        raise ValueError(f"pred_local must be [B,T,P_c,F,J,3], got {tuple(pred_local.shape)}")
-    dev = pred_local.device
-    B, T, P_c, F, J, _ = pred_local.shape
-    given = [t is not None for t in (inputs_2d, traj, cam)]
-    if any(given) and not all(given):
-        raise ValueError("accumulate_poses: inputs_2d, traj and cam come together (none of them: mean-only)")
-    reproj = all(given)
-    covered = sorted(j for idx in dataset.parts_joint_indices.values() for j in idx)
-    if covered != list(range(J)):
-        raise ValueError("dataset.parts_joint_indices must cover every joint exactly once")
-    conn, _ = _tables(dataset, J, dev)
-    x2d = tr = cm = None
-    if reproj:
-        if tuple(inputs_2d.shape) != (B, F, J, 2) or traj.numel() != B * F * 3 or cam.numel() < 9:
-            raise ValueError(f"accumulate_poses: operands do not match pred {tuple(pred_local.shape)}: 2d "
-                             f"{tuple(inputs_2d.shape)}, traj {tuple(traj.shape)}, cam {tuple(cam.shape)}")
-        if inputs_2d.device != dev or traj.device != dev:
-            raise ValueError("accumulate_poses: all tensors must live on the device of pred_local")
-        x2d, tr = inputs_2d.contiguous().float(), traj.reshape(B, F, 3).contiguous().float()
-        cm = cam.reshape(-1)[:9].contiguous().float().to(dev)
+    who = "accumulate_poses"
+    pred, _, x2d, tr, cm, conn, _ = _operands(pred_local, None, inputs_2d, traj, cam, dataset, who, name="pred_local", axis="P_c")
+    B, T, P_c, F, J, _ = pred.shape
+    shape = (B, T, F, J)
+    reproj = x2d is not None
     if state is None:
-        state = PoseState((B, T, F, J), dev, reproj)
-    if state.shape != (B, T, F, J) or state.device != dev:
-        raise ValueError(f"accumulate_poses: the state holds {state.shape}, the chunk is {(B, T, F, J)}")
+        state = PoseState(shape, pred.device, reproj)
+    state.expect(who, shape, pred.device)
     if state.reproj != reproj:
         raise ValueError("accumulate_poses: a state is either mean-only or keeps candidates, for all of its chunks")
-    if state.h0 is not None and int(h0) != state.h0 + state.count:
-        raise ValueError(f"accumulate_poses: chunk starts at hypothesis {h0}, the state ends at {state.h0 + state.count}")
-    first = state.slots is None
-    if first:
-        state.slots = torch.empty(2, ops.pose_partials_bytes(B, T, F, J) // 8, device=dev, dtype=torch.float64)
-    ops.pose_partials(pred_local.contiguous().float(), conn, int(h0), x2d, tr, cm, out=state.slots[0 if first else 1])
-    if not first:     # running state <- running state (+) this chunk, in place (every thread reads its element before it writes it)
-        ops.combine_poses(state.slots, (B, T, F, J), 1, merged=state.slots[0], want=())
-    if state.h0 is None:
-        state.h0 = int(h0)
-    state.count += P_c
-    return state
+    return state.fold(who, P_c, h0, ops.pose_partials_bytes(B, T, F, J) // 8, None,
+                      lambda row: ops.pose_partials(pred, conn, int(h0), x2d, tr, cm, out=row),
+                      lambda slots: ops.combine_poses(slots, shape, 1, merged=slots[0], want=()))
 
 
 def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=None, traj=None, cam=None, group=None,
@@ -443,7 +436,6 @@ def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=No
     gloo group): 44 bytes per (b,t,f,j), whatever P is.  pick and idx do not depend on how the hypotheses are cut; the
     mean adds the shards' fp64 sums in shard order."""
     from . import ops
-    from .parallel import shard_range
     if pred_local is not None:
         state = accumulate_poses(state, pred_local, h0, dataset, inputs_2d, traj, cam)
     if state is None:
@@ -454,21 +446,5 @@ def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=No
     if not state.reproj and ("pick" in want or "idx" in want):
         raise ValueError("aggregate_poses_sharded: a mean-only state has no pick (give inputs_2d, traj and cam)")
     P = int(num_proposals)
-    world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
-    if world == 1:
-        if state.h0 != 0 or state.count != P:
-            raise ValueError(f"the state holds hypotheses [{state.h0}, {state.h0 + state.count}) of {P}")
-        states = state.slots[:1]
-    else:
-        rank = dist.get_rank(group)
-        lo, hi = shard_range(P, rank, world)
-        if (state.h0, state.count) != (lo, hi - lo):
-            raise ValueError(f"rank {rank} of {world} owns hypotheses [{lo}, {hi}) of {P}, its state holds "
-                             f"[{state.h0}, {state.h0 + state.count})")
-        send = state.head
-        if dist.get_backend(group) == "gloo":             # rehearsal on a box with fewer GPUs than ranks
-            send = send.cpu()
-        recv = send.new_empty(world * send.numel())
-        dist.all_gather_into_tensor(recv, send.contiguous(), group=group)
-        states = recv.view(world, -1).to(state.device)
+    (states, _), = _exchange([(state.head, None)], state.h0, state.count, P, group, state.device)
     return ops.combine_poses(states.contiguous(), state.shape, P, want=want)

@@ -19,6 +19,52 @@ def _need(cond, msg):
         raise ValueError(msg)
 
 
+def _data(t):
+    return t.data_ptr() if t.numel() else None   # an empty tensor has no storage to point the library at
+
+
+def _need_pred(who, pred, axis="P_r"):
+    _need(pred.dim() == 6 and pred.shape[-1] == 3, f"{who}: pred must be [B,T,{axis},F,J,3], got {tuple(pred.shape)}")
+    return pred.shape[:5]
+
+
+def _need_tensors(who, f32, i32):
+    """the fp32 operands `f32` and the int32 tables `i32`: contiguous, all on the HIP device of the first"""
+    _need(all(t.is_cuda and t.device == f32[0].device and t.is_contiguous() for t in (*f32, *i32)),
+          f"{who}: contiguous tensors on one HIP device (no CPU fallback)")
+    _need(all(t.dtype == torch.float32 for t in f32) and all(t.dtype == torch.int32 for t in i32), f"{who}: dtypes")
+
+
+def _state_out(who, out, need, dev):
+    """the flat float64 buffer a partials op writes its `need` bytes of state into: `out`, or a new one"""
+    if out is None:
+        out = torch.empty(need // 8, device=dev, dtype=torch.float64)
+    _need(out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous()
+          and out.numel() * 8 >= need, f"{who}: out must be a float64 buffer of {need} bytes or more on {dev}")
+    return out
+
+
+def _need_rows(t, head, msg, strided=False, like=None):
+    """operand rows of a combine op: [W >= 1, >= head] float64 on a HIP device, contiguous or (strided) a column slice of
+    a wider buffer with rows `head` or more apart; `like`: on its device and with as many rows"""
+    ok = t.dim() == 2 and t.dtype == torch.float64 and t.is_cuda and t.shape[0] >= 1 and t.shape[1] >= head
+    ok = ok and (like is None or (t.device == like.device and t.shape[0] == like.shape[0]))
+    _need(ok and ((t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) >= head)) if strided else t.is_contiguous()), msg)
+
+
+def _need_merged(who, merged, states, head, size, span, over):
+    """the buffer a combine op merges into: `head` (in words: `size`) float64 or more on the device of `states`.  `over`:
+    what it may lie over of the `span` elements read from there - "first": states[0] alone, "none", None: not checked"""
+    _need(merged.is_cuda and merged.device == states.device and merged.dtype == torch.float64 and merged.is_contiguous()
+          and merged.numel() >= head, f"{who}: merged must hold {size} float64")
+    lo, at = states.data_ptr(), merged.data_ptr()
+    overlap = at < lo + 8 * span and at + 8 * head > lo
+    if over == "first":
+        _need(at == lo or not overlap, f"{who}: of its operands the merged state may only lie over the first")
+    elif over == "none":
+        _need(not overlap, f"{who}: a merge over its own operands cannot also write the maps")
+
+
 def linear(x, weight, bias, act=None, bf16=False):
     """nn.Linear (+ exact GELU when act == 'gelu') on the last dim of a contiguous fp32 tensor; bf16=True rounds both
     operands to bf16 in registers (fp32 accumulate)."""
@@ -651,10 +697,7 @@ def procrustes_errors(pred, gt, x2d, traj, cam, conn, pick=True):
     B, T, P, F, J, _ = pred.shape
     _need(tuple(gt.shape) == (B, F, J, 3) and tuple(x2d.shape) == (B, F, J, 2) and traj.numel() == B * F * 3
           and cam.numel() == 9 and conn.numel() == J, "procrustes_errors: operands do not match pred")
-    ops = (pred, gt, x2d, traj, cam, conn)
-    _need(all(t.is_cuda and t.device == pred.device and t.is_contiguous() for t in ops), "procrustes_errors: contiguous "
-          "tensors on one HIP device (no CPU fallback)")
-    _need(all(t.dtype == torch.float32 for t in ops[:5]) and conn.dtype == torch.int32, "procrustes_errors: dtypes")
+    _need_tensors("procrustes_errors", (pred, gt, x2d, traj, cam), (conn,))
     dev = pred.device
     out = {k: torch.empty(B, T, F, J, device=dev) for k in ("jbest", "pagg", "jagg")}
     out["pbest_sums"] = torch.empty(B, T, P, F, device=dev, dtype=torch.float64)
@@ -728,25 +771,17 @@ def hypothesis_partials(pred, gt, x2d, traj, cam, conn, pbroot, part, num_parts,
     (partials_views names its pieces).  `out`: a float64 buffer at least that long to write into (a padded state for
     the collective); the result is then `out` itself.  fp32 operands on one HIP device, contiguous."""
     lib = _lib.load()
-    _need(pred.dim() == 6 and pred.shape[-1] == 3, f"hypothesis_partials: pred must be [B,T,P_r,F,J,3], got {tuple(pred.shape)}")
-    B, T, P_r, F, J, _ = pred.shape
+    B, T, P_r, F, J = _need_pred("hypothesis_partials", pred)
     _need(tuple(gt.shape) == (B, F, J, 3) and tuple(x2d.shape) == (B, F, J, 2) and traj.numel() == B * F * 3
           and cam.numel() == 9 and conn.numel() == J and pbroot.numel() == J and part.numel() == J,
           "hypothesis_partials: operands do not match pred")
     _need(T > 0 and F > 0 and J > 0 and int(h0) >= 0, "hypothesis_partials: T, F, J > 0 and h0 >= 0")
     _need(1 <= num_parts <= _lib.MAX_PARTS, f"hypothesis_partials: 1 .. {_lib.MAX_PARTS} parts")
-    ops = (pred, gt, x2d, traj, cam, conn, pbroot, part)
-    _need(all(t.is_cuda and t.device == pred.device and t.is_contiguous() for t in ops), "hypothesis_partials: contiguous "
-          "tensors on one HIP device (no CPU fallback)")
-    _need(all(t.dtype == torch.float32 for t in ops[:5]) and all(t.dtype == torch.int32 for t in ops[5:]),
-          "hypothesis_partials: dtypes")
+    _need_tensors("hypothesis_partials", (pred, gt, x2d, traj, cam), (conn, pbroot, part))
     dev = pred.device
     need = int(lib.pafuse_hypothesis_partials_bytes(B, T, P_r, F, J, num_parts))
     assert need == partials_bytes(B, T, P_r, F, J, num_parts)
-    if out is None:
-        out = torch.empty(need // 8, device=dev, dtype=torch.float64)
-    _need(out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous()
-          and out.numel() * 8 >= need, f"hypothesis_partials: out must be a float64 buffer of {need} bytes or more on {dev}")
+    out = _state_out("hypothesis_partials", out, need, dev)
     wbytes = int(lib.pafuse_hypothesis_partials_workspace_bytes(B, T, P_r, F, J, num_parts))
     work = torch.empty(max(wbytes // 8, 1), device=dev, dtype=torch.float64)
     with torch.cuda.device(dev):
@@ -754,10 +789,6 @@ def hypothesis_partials(pred, gt, x2d, traj, cam, conn, pbroot, part, num_parts,
             _data(pred), _data(gt), _data(x2d), _data(traj), _data(cam), _data(conn), _data(pbroot), _data(part), num_parts,
             B, T, P_r, F, J, int(h0), _data(out), out.numel() * 8, work.data_ptr(), work.numel() * 8, _stream(pred)))
     return out
-
-
-def _data(t):
-    return t.data_ptr() if t.numel() else None   # an empty tensor has no storage to point the library at
 
 
 def combine_partials(states, gt, conn, pbroot, shape, num_proposals, merged=None, maps=True):
@@ -769,8 +800,7 @@ def combine_partials(states, gt, conn, pbroot, shape, num_proposals, merged=None
     lib = _lib.load()
     B, T, F, J = (int(v) for v in shape)
     n = B * T * F * J
-    _need(states.dim() == 2 and states.dtype == torch.float64 and states.is_cuda and states.is_contiguous()
-          and states.shape[0] >= 1 and states.shape[1] >= 5 * n, "combine_partials: states must be [W, >= 5*B*T*F*J] float64")
+    _need_rows(states, 5 * n, "combine_partials: states must be [W, >= 5*B*T*F*J] float64")
     _need(T > 0 and F > 0 and J > 0 and B >= 0, "combine_partials: bad shape")
     _need(maps or merged is not None, "combine_partials: nothing to compute")
     _need(not maps or int(num_proposals) >= 1, "combine_partials: num_proposals >= 1")
@@ -781,11 +811,7 @@ def combine_partials(states, gt, conn, pbroot, shape, num_proposals, merged=None
           and conn.dtype == torch.int32 and pbroot.dtype == torch.int32, "combine_partials: gt [B,F,J,3] f32, conn / pbroot "
           "[J] int32, contiguous on the device of the states")
     if merged is not None:
-        _need(merged.is_cuda and merged.device == dev and merged.dtype == torch.float64 and merged.is_contiguous()
-              and merged.numel() >= 5 * n, "combine_partials: merged must hold 5*B*T*F*J float64")
-        lo, hi = states.data_ptr(), states.data_ptr() + states.numel() * 8
-        _need(not (maps and merged.data_ptr() < hi and merged.data_ptr() + 40 * n > lo),
-              "combine_partials: a merge over its own operands cannot also write the maps")
+        _need_merged("combine_partials", merged, states, 5 * n, "5*B*T*F*J", states.numel(), "none" if maps else None)
     out = {k: torch.empty(B, T, F, J, device=dev) for k in ("jbest", "pagg", "jagg", "paggpb")} if maps else {}
     if n == 0:
         return out
@@ -824,24 +850,17 @@ def pose_partials(pred, conn, h0, x2d=None, traj=None, cam=None, out=None):
     them (mean-only: no candidate is kept) -> the flat state, a 1-D float64 tensor (pose_views names its pieces).
     `out`: a float64 buffer at least that long to write into; the result is then `out` itself."""
     lib = _lib.load()
-    _need(pred.dim() == 6 and pred.shape[-1] == 3, f"pose_partials: pred must be [B,T,P_r,F,J,3], got {tuple(pred.shape)}")
-    B, T, P_r, F, J, _ = pred.shape
+    B, T, P_r, F, J = _need_pred("pose_partials", pred)
     _need(T > 0 and F > 0 and J > 0 and int(h0) >= 0, "pose_partials: T, F, J > 0 and h0 >= 0")
     _need(conn.numel() == J and conn.dtype == torch.int32, "pose_partials: conn must be int32 [J]")
     given = [t for t in (x2d, traj, cam) if t is not None]   # some but not all of them: the library refuses (PafuseError)
     _need((x2d is None or tuple(x2d.shape) == (B, F, J, 2)) and (traj is None or traj.numel() == B * F * 3)
           and (cam is None or cam.numel() == 9), "pose_partials: operands do not match pred")
-    ops = [pred, conn] + given
-    _need(all(t.is_cuda and t.device == pred.device and t.is_contiguous() for t in ops), "pose_partials: contiguous "
-          "tensors on one HIP device (no CPU fallback)")
-    _need(all(t.dtype == torch.float32 for t in [pred] + given), "pose_partials: dtypes")
+    _need_tensors("pose_partials", [pred] + given, (conn,))
     dev = pred.device
     need = int(lib.pafuse_pose_partials_bytes(B, T, F, J))
     assert need == pose_partials_bytes(B, T, F, J)
-    if out is None:
-        out = torch.empty(need // 8, device=dev, dtype=torch.float64)
-    _need(out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous()
-          and out.numel() * 8 >= need, f"pose_partials: out must be a float64 buffer of {need} bytes or more on {dev}")
+    out = _state_out("pose_partials", out, need, dev)
     ptrs = [None if t is None else t.data_ptr() for t in (x2d, traj, cam)]
     if B == 0 and len(given) == 3:
         ptrs = [None] * 3                    # empty tensors have no storage to point the library at
@@ -865,18 +884,13 @@ def combine_poses(states, shape, num_proposals, merged=None, want=("mean", "pick
     L = pose_partials_bytes(B, T, F, J) // 8
     want = tuple(want)
     _need(all(k in ("mean", "pick", "idx") for k in want), f"combine_poses: want holds mean, pick, idx - got {want}")
-    _need(states.dim() == 2 and states.dtype == torch.float64 and states.is_cuda and states.is_contiguous()
-          and states.shape[0] >= 1 and states.shape[1] >= L, f"combine_poses: states must be [W, >= {L}] float64")
+    _need_rows(states, L, f"combine_poses: states must be [W, >= {L}] float64")
     _need(T > 0 and F > 0 and J > 0 and B >= 0, "combine_poses: bad shape")
     _need(want or merged is not None, "combine_poses: nothing to compute")
     _need("mean" not in want or int(num_proposals) >= 1, "combine_poses: num_proposals >= 1")
     dev = states.device
     if merged is not None:
-        _need(merged.is_cuda and merged.device == dev and merged.dtype == torch.float64 and merged.is_contiguous()
-              and merged.numel() >= L, f"combine_poses: merged must hold {L} float64")
-        lo, hi = states.data_ptr(), states.data_ptr() + states.numel() * 8
-        _need(merged.data_ptr() == lo or not (merged.data_ptr() < hi and merged.data_ptr() + 8 * L > lo),
-              "combine_poses: of its operands the merged state may only lie over the first")
+        _need_merged("combine_poses", merged, states, L, L, states.numel(), "first")
     out = {}
     if "mean" in want:
         out["mean"] = torch.empty(B, T, F, J, 3, device=dev)
@@ -927,21 +941,13 @@ def procrustes_partials(pred, gt, x2d, traj, cam, conn, h0, out=None):
     state, a 1-D float64 tensor (procrustes_partial_views names its pieces).  `out`: a float64 buffer at least that long
     to write into; the result is then `out` itself.  fp32 operands on one HIP device, contiguous.  J <= 256."""
     lib = _lib.load()
-    _need(pred.dim() == 6 and pred.shape[-1] == 3, f"procrustes_partials: pred must be [B,T,P_r,F,J,3], got {tuple(pred.shape)}")
-    B, T, P_r, F, J, _ = pred.shape
+    B, T, P_r, F, J = _need_pred("procrustes_partials", pred)
     _need(tuple(gt.shape) == (B, F, J, 3) and tuple(x2d.shape) == (B, F, J, 2) and traj.numel() == B * F * 3
           and cam.numel() == 9 and conn.numel() == J, "procrustes_partials: operands do not match pred")
     _need(T > 0 and F > 0 and J > 0 and int(h0) >= 0, "procrustes_partials: T, F, J > 0 and h0 >= 0")
-    ops = (pred, gt, x2d, traj, cam, conn)
-    _need(all(t.is_cuda and t.device == pred.device and t.is_contiguous() for t in ops), "procrustes_partials: contiguous "
-          "tensors on one HIP device (no CPU fallback)")
-    _need(all(t.dtype == torch.float32 for t in ops[:5]) and conn.dtype == torch.int32, "procrustes_partials: dtypes")
+    _need_tensors("procrustes_partials", (pred, gt, x2d, traj, cam), (conn,))
     dev = pred.device
-    need = procrustes_partials_bytes(B, T, P_r, F, J)
-    if out is None:
-        out = torch.empty(need // 8, device=dev, dtype=torch.float64)
-    _need(out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous()
-          and out.numel() * 8 >= need, f"procrustes_partials: out must be a float64 buffer of {need} bytes or more on {dev}")
+    out = _state_out("procrustes_partials", out, procrustes_partials_bytes(B, T, P_r, F, J), dev)
     wbytes = int(lib.pafuse_procrustes_partials_workspace_bytes(B, T, P_r, F, J))
     work = torch.empty(max(wbytes // 8, 1), device=dev, dtype=torch.float64)
     with torch.cuda.device(dev):
@@ -966,9 +972,8 @@ def combine_procrustes(states, shape, num_proposals, sums=None, gt=None, conn=No
     n = B * T * F * J
     want = tuple(want)
     _need(all(k in ("jbest", "pagg", "jagg", "pick") for k in want), f"combine_procrustes: want holds jbest, pagg, jagg, pick - got {want}")
-    _need(states.dim() == 2 and states.dtype == torch.float64 and states.is_cuda and states.stride(1) == 1
-          and states.shape[0] >= 1 and states.shape[1] >= 2 * n and (states.shape[0] == 1 or states.stride(0) >= 2 * n),
-          "combine_procrustes: states must be [W, >= 2*B*T*F*J] float64 rows (a column slice of a wider buffer is fine)")
+    _need_rows(states, 2 * n, "combine_procrustes: states must be [W, >= 2*B*T*F*J] float64 rows (a column slice of a wider "
+               "buffer is fine)", strided=True)
     _need(T > 0 and F > 0 and 0 < J <= 256 and B >= 0, "combine_procrustes: bad shape (J <= 256)")
     _need(want or merged is not None, "combine_procrustes: nothing to compute")
     _need(int(num_proposals) >= 1, "combine_procrustes: num_proposals >= 1")
@@ -977,19 +982,13 @@ def combine_procrustes(states, shape, num_proposals, sums=None, gt=None, conn=No
     row = lambda t: t.stride(0) if W > 1 else t.shape[1]   # elements between rows
     if "pagg" in want:
         _need(sums is not None and gt is not None and conn is not None, "combine_procrustes: pagg needs sums, gt and conn")
-        _need(sums.dim() == 2 and sums.dtype == torch.float64 and sums.is_cuda and sums.device == dev and sums.stride(1) == 1
-              and sums.shape[0] == W and sums.shape[1] >= 3 * n and (W == 1 or sums.stride(0) >= 3 * n),
-              "combine_procrustes: sums must be [W, >= 3*B*T*F*J] float64 rows on the device of the states")
+        _need_rows(sums, 3 * n, "combine_procrustes: sums must be [W, >= 3*B*T*F*J] float64 rows on the device of the states",
+                   strided=True, like=states)
         _need(tuple(gt.shape) == (B, F, J, 3) and conn.numel() == J and all(t.is_cuda and t.device == dev and t.is_contiguous()
               for t in (gt, conn)) and gt.dtype == torch.float32 and conn.dtype == torch.int32,
               "combine_procrustes: gt [B,F,J,3] f32, conn [J] int32, contiguous on the device of the states")
     if merged is not None:
-        _need(merged.is_cuda and merged.device == dev and merged.dtype == torch.float64 and merged.is_contiguous()
-              and merged.numel() >= 2 * n, "combine_procrustes: merged must hold 2*B*T*F*J float64")
-        lo = states.data_ptr()
-        hi = lo + ((W - 1) * row(states) + 2 * n) * 8
-        _need(merged.data_ptr() == lo or not (merged.data_ptr() < hi and merged.data_ptr() + 16 * n > lo),
-              "combine_procrustes: of its operands the merged state may only lie over the first")
+        _need_merged("combine_procrustes", merged, states, 2 * n, "2*B*T*F*J", (W - 1) * row(states) + 2 * n, "first")
     out = {k: torch.empty(B, T, F, J, device=dev, dtype=torch.int32 if k == "pick" else torch.float32) for k in want}
     if n == 0:
         return out
