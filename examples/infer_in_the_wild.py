@@ -10,7 +10,10 @@ sampling on the HIP path with ``input_3d=None`` -> whole-body poses stitched bac
 Writes <out>/test_3d_output.npy [T,P,frames,134,3] (camera space) and <out>/test_3d_output_postprocess.npy (rotated
 with the reference's fixed camera orientation, lowest point at height 0).  With --aggregate mean the hypotheses are
 averaged on the device (P-Agg, the mean whole-body pose; --hypothesis-chunk n samples and reduces them n at a time, so
-peak memory follows n instead of P) and both files hold [T,frames,134,3]: one pose per frame.  Without --keypoints a synthetic detection
+peak memory follows n instead of P) and both files hold [T,frames,134,3]: one pose per frame.  --spread std (with
+--aggregate mean) also writes test_3d_output_std.npy [T,frames,134], per joint the RMS distance in metres of the P
+hypotheses from that mean - the confidence of the joint; --spread cov writes test_3d_output_cov.npy [T,frames,134,6] as
+well, their population covariance (xx, xy, xz, yy, yz, zz), camera space.  Without --keypoints a synthetic detection
 file is generated (random weights unless --checkpoint: numbers are meaningless).
 """
 import argparse
@@ -48,8 +51,13 @@ def main():
                          "device (only the aggregate is copied to the host)")
     ap.add_argument("--hypothesis-chunk", type=int, default=None,
                     help="with --aggregate mean: sample and reduce the hypotheses this many at a time")
+    ap.add_argument("--spread", choices=("std", "cov"), default=None,
+                    help="with --aggregate mean: also write the per-joint spread of the hypotheses about the mean pose, reduced "
+                         "on the device: std [T,frames,134] (metres), and for cov the covariance [T,frames,134,6] as well")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.spread is not None and a.aggregate == "none":
+        ap.error("--spread needs --aggregate mean")
     if a.hypothesis_chunk is not None and a.aggregate == "none":
         ap.error("--hypothesis-chunk needs --aggregate mean")
     args = config.load(None, a.overrides)
@@ -78,7 +86,12 @@ def main():
     keypoints = h3wb.normalize_screen_coordinates(pixels[..., :2], w=a.width, h=a.height).astype(np.float32)
     if a.aggregate == "mean":
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
-                                      hypothesis_chunk=a.hypothesis_chunk)
+                                      hypothesis_chunk=a.hypothesis_chunk, spread=a.spread)
+        if a.spread is not None:
+            for k in ("std", "cov")[:1 if a.spread == "std" else 2]:
+                np.save(os.path.join(a.out, f"test_3d_output_{k}.npy"),
+                        harness.stitch_spread(pred[k], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
+            pred = pred["pose"]
         poses = harness.stitch_poses(pred, keypoints.shape[0], model.frames)        # [T,frames,134,3]
     else:
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch)

@@ -27,6 +27,7 @@
  *   pafuse_hypothesis_errors the per-joint part of evaluate()'s aggregation, main_h3wb.py:327-362
  *   pafuse_hypothesis_partials / _combine  the same from per-shard partial reductions (sharded or chunked P)
  *   pafuse_pose_partials / _combine  the P-Agg / J-Agg aggregates as poses, from shards or chunks of P (no ground truth)
+ *   pafuse_spread_partials / _combine  the spread of the hypotheses beside the P-Agg mean: per-joint covariance and std
  *   pafuse_procrustes_errors the Protocol #2 part of it (ft2d.p2), main_h3wb.py:381-395, common/loss.py:251-458
  *   pafuse_procrustes_partials / _combine  Protocol #2 from per-shard partial states (sharded or chunked P)
  *   pafuse_mixste2_train_*   MixSTE2.forward (is_train=True) + autograd backward, common/mixste.py:215-225,260-298
@@ -573,6 +574,36 @@ int pafuse_pose_partials(const float *pred, const float *x2d, const float *traj,
  *   pick_idx  [B,T,F,J] int32 its hypothesis (-1 where none) */
 int pafuse_pose_combine(const void *states, int32_t W, size_t stride_bytes, int32_t B, int32_t T, int32_t F, int32_t J,
                         int32_t P_total, void *merged, float *mean, float *pick, int32_t *pick_idx, void *stream);
+
+/* The spread of the hypotheses beside the mean pose, from the same shards: first and second moments of the whole-body
+ * joint per (b,t,f,j).  pred [B,T,P_r,F,J,3] holds the part-centred hypotheses [h0, h0 + P_r) of the run, conn int32 [J].
+ * State, one flat 8-byte aligned buffer of pafuse_spread_partials_bytes = (9*n + 1)*8 bytes, n = B*T*F*J, all doubles:
+ *   double sum[n][3]   sum over the local h, in h order, of the whole-body joint: the sum of a pose state, bit for bit
+ *   double m2[n][6]    centred second moments sum_h (w_h - mean)(w_h - mean)^T in the order xx, xy, xz, yy, yz, zz, updated
+ *                      per hypothesis by Welford's rule (d = w - sum_prev/k_prev; sum += w; m2 += d (x) (w - sum/k))
+ *   double count       P_r
+ * All state arithmetic is fp64, floating-point contraction off.  Nothing depends on P_r: W ranks exchange their states
+ * with one all-gather of double rows.  One kernel, no workspace, no atomics, bit-reproducible.  B == 0: the state is
+ * empty (0 bytes).  P_r == 0: no kernel runs, the state is the neutral one (all zeros, count 0).  h0 is checked only.
+ * Refused (PAFUSE_E_ARG): a null pred or conn with work to do, negative sizes or h0, a short or misaligned state, a grid
+ * out of range. */
+size_t pafuse_spread_partials_bytes(int32_t B, int32_t T, int32_t F, int32_t J);
+int pafuse_spread_partials(const float *pred, const int32_t *conn, int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J,
+                           int32_t h0, void *state, size_t state_bytes, void *stream);
+
+/* Combines W such states, `stride_bytes` apart and in ascending-h0 order, by Chan's pairwise rule in fp64, left to right:
+ * delta = sum_B/n_B - sum_A/n_A, m2 = m2_A + m2_B + delta (x) delta * n_A n_B / (n_A + n_B), sum = sum_A + sum_B; a state
+ * with count 0 is skipped.  Writes any of (NULL: not wanted, at least one):
+ *   merged   the state of the union; of the operands it may only lie over the FIRST (a running state over chunks)
+ *   mean     [B,T,F,J,3] fp32 = sum / count
+ *   cov      [B,T,F,J,6] fp32 = m2 / count, the POPULATION covariance (one hypothesis: 0, not NaN), order as m2
+ *   std_dev  [B,T,F,J]   fp32 = sqrt((m2_xx + m2_yy + m2_zz) / count): the RMS distance of the hypotheses from the mean joint
+ * each divided in fp64 and rounded once.  Total count 0: NaN.  A non-finite hypothesis makes the three outputs of its
+ * element NaN and touches no other element.
+ * Refused (PAFUSE_E_ARG): null states, negative sizes, W < 1, a stride smaller than the state, misalignment, a merged
+ * state over an operand other than the first, no output, a grid out of range. */
+int pafuse_spread_combine(const void *states, int32_t W, size_t stride_bytes, int32_t B, int32_t T, int32_t F, int32_t J,
+                          void *merged, float *mean, float *cov, float *std_dev, void *stream);
 
 /* Protocol #2 (P-MPJPE) on the same operands - common/loss.py:251-458 as main_h3wb.py:381-395 calls it: every
  * whole-body hypothesis pose (and, per (b,t,f), the mean over h of them) aligned to its whole-body target by the

@@ -3006,6 +3006,153 @@ __global__ void __launch_bounds__(256) pose_combine_kernel(const PoseCombinePara
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// The SPREAD of the hypotheses beside the mean pose: first and second moments of the whole-body joint per (b, t, f, j),
+// by the same shard / chunk scheme.  spread_partials_kernel reduces hypotheses [h0, h0 + P_r) to a state whose size does
+// not depend on P, spread_combine_kernel merges W states in ascending-h0 order and / or writes mean, covariance and std.
+//
+// State, one flat buffer of doubles (n = B*T*F*J), (9*n + 1)*8 bytes:
+//   double sum[n][3] | double m2[n][6] | double count
+// sum: the fp64 sum over the local h, in h order, of wb_joint - value for value, add for add the sum of a pose state.
+// m2: the CENTRED second moments  sum_h (w_h - mean)(w_h - mean)^T  in the order xx, xy, xz, yy, yz, zz, updated per
+// hypothesis by Welford's rule (d = w - sum_prev/k_prev; sum += w; m2 += d (x) (w - sum/k); the first hypothesis adds
+// nothing) and merged by Chan's pairwise rule.  Raw sums of squares would be cheaper and cannot give an exact 0 for
+// identical hypotheses; here d is exactly 0 for them (k copies of an fp32 value sum and divide exactly in fp64).
+// count: the number of hypotheses in the state, as a double, so that a state is one row of doubles for the collective.
+// All state arithmetic is fp64 with floating-point contraction pinned OFF in both kernels: every product is rounded
+// before it is added, so the host statement of the same operations (torch, fp64) gives the same bits.
+// One thread per (b, t, f, j); no LDS, no atomics, no scratch.  The fp64 divides (three per hypothesis: the running mean
+// is kept and reused as the next sum_prev/k_prev) are what keeps sum/k exact; a reciprocal multiply would not.
+// ----------------------------------------------------------------------------------------------------------------
+struct SpreadPartialsParams {
+    const float* pred;    // [B,T,P_r,F,J,3] this shard's part-centred predictions
+    const int32_t* conn;  // [J]
+    double* sum;          // state (see above)
+    double* m2;
+    double* count;
+    int B, T, P, F, J;
+};
+
+__global__ void __launch_bounds__(256) spread_partials_kernel(const SpreadPartialsParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t total = (int64_t)p.B * p.T * p.F * p.J;
+    if (e >= total) return;
+    if (e == 0) *p.count = (double)p.P;
+    const int j = (int)(e % p.J);
+    const int f = (int)((e / p.J) % p.F);
+    const int t = (int)((e / ((int64_t)p.J * p.F)) % p.T);
+    const int b = (int)(e / ((int64_t)p.J * p.F * p.T));
+    const float* pose0 = p.pred + ((((int64_t)b * p.T + t) * p.P) * p.F + f) * p.J * 3;
+    const int64_t hstride = (int64_t)p.F * p.J * 3;
+    double sm[3] = {0.0, 0.0, 0.0}, mu[3], m2[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    {   // the first hypothesis: sums only (0.0 + w, as the pose state adds it); its mean is itself
+        float w[3];
+        wb_joint(pose0, p.conn, j, w);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sm[k] += (double)w[k], mu[k] = sm[k];
+    }
+#pragma unroll 4
+    for (int h = 1; h < p.P; ++h) {
+        float w[3];
+        wb_joint(pose0 + h * hstride, p.conn, j, w);
+        const double cnt = (double)(h + 1);
+        double x[3], d[3], r[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            x[k] = (double)w[k];
+            d[k] = x[k] - mu[k];          // mu = sum_prev / k_prev
+            sm[k] += x[k];
+            mu[k] = sm[k] / cnt;
+            r[k] = x[k] - mu[k];
+        }
+        m2[0] += d[0] * r[0], m2[1] += d[0] * r[1], m2[2] += d[0] * r[2];
+        m2[3] += d[1] * r[1], m2[4] += d[1] * r[2], m2[5] += d[2] * r[2];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p.sum[e * 3 + k] = sm[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) p.m2[e * 6 + k] = m2[k];
+}
+
+struct SpreadCombineParams {
+    const char* states;   // W states, `stride` bytes apart, in ascending-h0 order
+    int64_t stride;
+    int W;
+    double* merged;       // merged state (null: not wanted); may be the first operand
+    float* mean;          // [B,T,F,J,3] (null: not wanted)
+    float* cov;           // [B,T,F,J,6] (null: not wanted)
+    float* sd;            // [B,T,F,J]   (null: not wanted)
+    int64_t n;            // B*T*F*J
+};
+
+// one thread per (b, t, f, j): it reads its own element of every state before it writes anything, so the merged state
+// may lie over the first operand.  The counts are the one thing every thread reads: the merged count is therefore NOT
+// written here but by spread_count_kernel, launched behind this kernel on the same stream.
+__global__ void __launch_bounds__(256) spread_combine_kernel(const SpreadCombineParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = p.n;
+    if (e >= n) return;
+    double na = 0.0, s[3] = {0.0, 0.0, 0.0}, m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int w = 0; w < p.W; ++w) {
+        const double* st = (const double*)(p.states + (int64_t)w * p.stride);
+        const double nb = st[9 * n];
+        if (nb == 0.0) continue;          // an empty shard: nothing to merge and no 0/0
+        const double* sb = st + e * 3;
+        const double* mb = st + 3 * n + e * 6;
+        if (na == 0.0) {                  // the first non-empty state goes through as it is
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s[k] = sb[k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) m[k] = mb[k];
+            na = nb;
+            continue;
+        }
+        const double fac = na * nb / (na + nb);
+        double dl[3], b3[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) b3[k] = sb[k], dl[k] = b3[k] / nb - s[k] / na;
+        m[0] = (m[0] + mb[0]) + dl[0] * dl[0] * fac, m[1] = (m[1] + mb[1]) + dl[0] * dl[1] * fac;
+        m[2] = (m[2] + mb[2]) + dl[0] * dl[2] * fac, m[3] = (m[3] + mb[3]) + dl[1] * dl[1] * fac;
+        m[4] = (m[4] + mb[4]) + dl[1] * dl[2] * fac, m[5] = (m[5] + mb[5]) + dl[2] * dl[2] * fac;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s[k] += b3[k];
+        na += nb;
+    }
+    if (p.merged) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p.merged[e * 3 + k] = s[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) p.merged[3 * n + e * 6 + k] = m[k];
+    }
+    // no hypothesis at all, or a non-finite one in this element (its sums or moments are then inf or NaN): NaN outputs
+    bool fine = na > 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) fine = fine && isfinite(s[k]);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) fine = fine && isfinite(m[k]);
+    const float qnan = __builtin_nanf("");
+    if (p.mean) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p.mean[e * 3 + k] = fine ? (float)(s[k] / na) : qnan;   // divided in fp64, rounded once
+    }
+    if (p.cov) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) p.cov[e * 6 + k] = fine ? (float)(m[k] / na) : qnan;    // population covariance: divisor P
+    }
+    if (p.sd) p.sd[e] = fine ? (float)sqrt(((m[0] + m[3]) + m[5]) / na) : qnan;
+}
+
+// the count of the merged state: the counts of the W operands added in order, by one thread, after every thread of
+// spread_combine_kernel has read them (stream order)
+__global__ void __launch_bounds__(64) spread_count_kernel(const char* states, int64_t stride, int W, int64_t n, double* merged) {
+    if (blockIdx.x || threadIdx.x) return;
+    double c = 0.0;
+    for (int w = 0; w < W; ++w) c += ((const double*)(states + (int64_t)w * stride))[9 * n];
+    merged[9 * n] = c;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // Protocol #2 (P-MPJPE) behind the all-gather: common/loss.py:251-458 as main_h3wb.py:381-395 calls it on the
 // whole-body poses.  Every hypothesis pose Y is aligned to its target X by the similarity transform of the
 // reference (centre both, H = (X0/|X0|)^T (Y0/|Y0|), R = V U^T with the reflection fix, a = tr(S') |X0| / |Y0|) and

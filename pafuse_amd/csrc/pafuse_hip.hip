@@ -1956,6 +1956,65 @@ int pafuse_pose_combine(const void* states, int32_t W, size_t stride_bytes, int3
     return check_launch("pose_combine_kernel");
 }
 
+// state of pafuse_spread_partials: double sum[n][3] | double m2[n][6] | double count
+size_t pafuse_spread_partials_bytes(int32_t B, int32_t T, int32_t F, int32_t J) {
+    if (B <= 0 || T <= 0 || F <= 0 || J <= 0) return 0;
+    return ((size_t)B * T * F * J * 9 + 1) * 8;
+}
+
+int pafuse_spread_partials(const float* pred, const int32_t* conn, int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J,
+                           int32_t h0, void* state, size_t state_bytes, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (B < 0 || T <= 0 || P_r < 0 || F <= 0 || J <= 0 || h0 < 0) return fail(PAFUSE_E_ARG, "spread_partials: bad size");
+    const size_t need = pafuse_spread_partials_bytes(B, T, F, J);
+    if (need && (!state || state_bytes < need)) return fail(PAFUSE_E_ARG, "spread_partials: the state needs %zu bytes", need);
+    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "spread_partials: the state must be 8-byte aligned");
+    const int64_t n = (int64_t)B * T * F * J;
+    if (n == 0) return PAFUSE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (P_r == 0) {   // the neutral state: zero sums, zero moments, count 0; no kernel runs
+        hipError_t e = hipMemsetAsync(state, 0, need, s);
+        if (e != hipSuccess) return fail(PAFUSE_E_HIP, "spread_partials: %s", hipGetErrorString(e));
+        return PAFUSE_OK;
+    }
+    if (!pred || !conn) return fail(PAFUSE_E_ARG, "spread_partials: null pointer");
+    if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "spread_partials: grid out of range");
+    SpreadPartialsParams m{};
+    m.pred = pred, m.conn = conn;
+    m.sum = (double*)state, m.m2 = m.sum + 3 * n, m.count = m.sum + 9 * n;
+    m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J;
+    hipLaunchKernelGGL(spread_partials_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m);
+    return check_launch("spread_partials_kernel");
+}
+
+int pafuse_spread_combine(const void* states, int32_t W, size_t stride_bytes, int32_t B, int32_t T, int32_t F, int32_t J,
+                          void* merged, float* mean, float* cov, float* std_dev, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (B < 0 || T <= 0 || F <= 0 || J <= 0 || W < 1) return fail(PAFUSE_E_ARG, "spread_combine: bad size");
+    if (!merged && !mean && !cov && !std_dev) return fail(PAFUSE_E_ARG, "spread_combine: nothing to write");
+    const int64_t n = (int64_t)B * T * F * J;
+    if (n == 0) return PAFUSE_OK;
+    if (!states) return fail(PAFUSE_E_ARG, "spread_combine: null pointer");
+    const size_t need = pafuse_spread_partials_bytes(B, T, F, J);
+    if (stride_bytes < need || stride_bytes % 8 || (uintptr_t)states % 8 || (uintptr_t)merged % 8)
+        return fail(PAFUSE_E_ARG, "spread_combine: states are %zu bytes or more apart, 8-byte aligned", need);
+    const char* lo = (const char*)states;
+    const char* hi = lo + (size_t)(W - 1) * stride_bytes + need;
+    if (merged && merged != states && (const char*)merged < hi && (const char*)merged + need > lo)
+        return fail(PAFUSE_E_ARG, "spread_combine: of its operands the merged state may only lie over the first");
+    if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "spread_combine: grid out of range");
+    SpreadCombineParams c{};
+    c.states = lo, c.stride = (int64_t)stride_bytes, c.W = W, c.merged = (double*)merged;
+    c.mean = mean, c.cov = cov, c.sd = std_dev, c.n = n;
+    hipLaunchKernelGGL(spread_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c);
+    if (int rc = check_launch("spread_combine_kernel")) return rc;
+    if (!merged) return PAFUSE_OK;
+    // the merged count, behind the kernel whose every thread reads the operands' counts (the merged state may lie over the first)
+    hipLaunchKernelGGL(spread_count_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, lo, (int64_t)stride_bytes, W, n,
+                       (double*)merged);
+    return check_launch("spread_count_kernel");
+}
+
 int pafuse_procrustes_errors(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,
                              const int32_t* conn, int32_t B, int32_t T, int32_t P, int32_t F, int32_t J, float* jbest,
                              double* pbest_sums, float* pagg, float* jagg, int32_t* pick, void* stream) {

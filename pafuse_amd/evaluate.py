@@ -18,8 +18,12 @@ P-Agg is aligned at combine time (``ops.combine_procrustes``), from the fp64 sum
 ``accumulate_poses`` / ``aggregate_poses_sharded`` return the aggregates themselves - the P-Agg mean pose and the J-Agg
 pose with its hypothesis index - by the same scheme and without a ground truth (``ops.pose_partials``, ``ops.combine_poses``).
 
-The three families share their host code: ``_operands`` checks and converts the arguments of every entry point,
-``_RunningState.fold`` is the one running reduction (``PartialState``, ``Procrustes2State`` and ``PoseState`` only declare
+``accumulate_spread`` keeps, by the same scheme again, the first and second moments of the whole-body hypotheses
+(``ops.spread_partials``, ``ops.combine_spread``); ``aggregate_poses_sharded(spread_state=...)`` returns their per-joint
+covariance and std beside the pose.
+
+The four families share their host code: ``_operands`` checks and converts the arguments of every entry point,
+``_RunningState.fold`` is the one running reduction (``PartialState``, ``Procrustes2State``, ``PoseState`` and ``SpreadState`` only declare
 what each family keeps; every ``accumulate_*`` hands ``fold`` its partials op and its combine op), and ``_exchange`` is the
 one collective (``gather_partial_states`` and ``aggregate_poses_sharded`` give it their pieces).
 """
@@ -425,7 +429,7 @@ def accumulate_poses(state, pred_local, h0, dataset, inputs_2d=None, traj=None, 
 
 
 def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=None, traj=None, cam=None, group=None,
-                            state=None, want=None):
+                            state=None, want=None, spread_state=None):
     """The aggregates as poses without ever holding all P hypotheses: pred_local [B,T,P_r,F,J,3] holds the part-centred
     hypotheses [h0, h0 + P_r) of the `num_proposals` of the run - this rank's share (pafuse_amd.parallel.shard_range) or,
     with `state`, the last chunk of it (`state`: what accumulate_poses returned for the chunks before; pred_local=None
@@ -434,17 +438,67 @@ def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=No
     closest to the 2-D input - the hypothesis the evaluation kernels pick).  `want`: a subset of those names.  With
     torch.distributed initialised the ranks exchange their states in ONE all_gather_into_tensor (through the host on a
     gloo group): 44 bytes per (b,t,f,j), whatever P is.  pick and idx do not depend on how the hypotheses are cut; the
-    mean adds the shards' fp64 sums in shard order."""
+    mean adds the shards' fp64 sums in shard order.
+
+    `spread_state` (what accumulate_spread returned for the same hypotheses; a last chunk pred_local is folded into it
+    too) adds the names "cov" [B,T,F,J,6] and "std" [B,T,F,J] (ops.combine_spread); its 72 bytes per (b,t,f,j) ride in
+    the same all-gather behind the pose state.  `state` may then be None: the spread state holds the sums, so "mean" comes
+    from it - the same bits, there is no pick.  Without a spread state nothing changes, and "cov" / "std" are refused."""
     from . import ops
     if pred_local is not None:
-        state = accumulate_poses(state, pred_local, h0, dataset, inputs_2d, traj, cam)
-    if state is None:
+        if state is not None or spread_state is None or inputs_2d is not None:
+            state = accumulate_poses(state, pred_local, h0, dataset, inputs_2d, traj, cam)
+        if spread_state is not None:
+            spread_state = accumulate_spread(spread_state, pred_local, h0, dataset)
+    if state is None and spread_state is None:
         raise ValueError("aggregate_poses_sharded: neither hypotheses nor a state")
+    reproj = state is not None and state.reproj
     if want is None:
-        want = ("mean", "pick", "idx") if state.reproj else ("mean",)
+        want = (("mean", "pick", "idx") if reproj else ("mean",)) + (("cov", "std") if spread_state is not None else ())
     want = tuple(want)
-    if not state.reproj and ("pick" in want or "idx" in want):
+    if not reproj and ("pick" in want or "idx" in want):
         raise ValueError("aggregate_poses_sharded: a mean-only state has no pick (give inputs_2d, traj and cam)")
+    if spread_state is None and ("cov" in want or "std" in want):
+        raise ValueError('aggregate_poses_sharded: "cov" and "std" need a spread state (accumulate_spread)')
     P = int(num_proposals)
-    (states, _), = _exchange([(state.head, None)], state.h0, state.count, P, group, state.device)
-    return ops.combine_poses(states.contiguous(), state.shape, P, want=want)
+    if spread_state is None:
+        (states, _), = _exchange([(state.head, None)], state.h0, state.count, P, group, state.device)
+        return ops.combine_poses(states.contiguous(), state.shape, P, want=want)
+    first = spread_state if state is None else state
+    if state is not None and (state.shape != spread_state.shape or state.device != spread_state.device
+                              or (state.h0, state.count) != (spread_state.h0, spread_state.count)):
+        raise ValueError(f"the spread state holds [{spread_state.h0}, +{spread_state.count}) of {spread_state.shape}, the "
+                         f"pose state [{state.h0}, +{state.count}) of {state.shape}")
+    pieces = ([] if state is None else [(state.head, None)]) + [(spread_state.head, None)]
+    got = _exchange(pieces, first.h0, first.count, P, group, first.device)      # one all-gather for both families
+    from_pose = tuple(k for k in want if k in ("pick", "idx") or (k == "mean" and state is not None))
+    from_spread = tuple(k for k in want if k not in from_pose)
+    out = {}
+    if from_pose:
+        out.update(ops.combine_poses(got[0][0].contiguous(), first.shape, P, want=from_pose))
+    if from_spread:
+        out.update(ops.combine_spread(got[-1][0].contiguous(), first.shape, want=from_spread))
+    return out
+
+
+# ------------------------------------------------------------------------------------- spread of the hypotheses
+class SpreadState(_RunningState):
+    """The running first and second moments of the hypotheses one rank has seen so far: 72 bytes per (b,t,f,j) and a
+    count (ops.spread_views), independent of how many hypotheses went in."""
+
+
+def accumulate_spread(state, pred_local, h0, dataset):
+    """Fold the part-centred hypotheses pred_local [B,T,P_c,F,J,3] = global [h0, h0 + P_c) into the spread state `state`
+    (None: start one) and return it.  Chunks come in ascending h0 without a gap.  Memory: the chunk and two
+    72-byte-per-(b,t,f,j) states - never anything of size P."""
+    from . import ops
+    who = "accumulate_spread"
+    pred, _, _, _, _, conn, _ = _operands(pred_local, None, None, None, None, dataset, who, name="pred_local", axis="P_c")
+    B, T, P_c, F, J, _ = pred.shape
+    shape = (B, T, F, J)
+    if state is None:
+        state = SpreadState(shape, pred.device)
+    state.expect(who, shape, pred.device)
+    return state.fold(who, P_c, h0, ops.spread_partials_bytes(B, T, F, J) // 8, None,
+                      lambda row: ops.spread_partials(pred, conn, int(h0), out=row),
+                      lambda slots: ops.combine_spread(slots, shape, merged=slots[0], want=()))

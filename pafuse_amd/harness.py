@@ -5,8 +5,8 @@ or Hydra here; the caller hands in arrays).
 """
 import torch
 
-from .evaluate import (accumulate_partials, accumulate_poses, aggregate_poses_sharded, evaluate_accumulators,
-                       evaluate_accumulators_sharded)
+from .evaluate import (accumulate_partials, accumulate_poses, accumulate_spread, aggregate_poses_sharded,
+                       evaluate_accumulators, evaluate_accumulators_sharded)
 from .parallel import ShardedSampler
 
 ACCUMULATORS = ("j_best", "p_best", "p_agg", "j_agg", "p_best_pb", "p_best_pb_body", "p_best_pb_face",
@@ -64,7 +64,7 @@ def wb_pose_from_parts(pose, dataset):
 
 @torch.no_grad()
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
-                   hypothesis_chunk=None):
+                   hypothesis_chunk=None, spread=None):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -75,9 +75,20 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     ``"mean"`` (P-Agg): a CPU tensor [clips, T, F, J, 3], the mean whole-body pose.  ``"reproj"`` (J-Agg):
     ``(pose [clips,T,F,J,3], idx [clips,T,F,J])``, per joint the hypothesis whose 2-D reprojection is closest to the input
     and its index (NaN / -1 where no reprojection error is finite); it needs ``cam`` [9] intrinsics and ``traj`` [N,3], the
-    root position of every frame (cut into clips like the 2-D input)."""
+    root position of every frame (cut into clips like the 2-D input).
+
+    ``spread`` (with an ``aggregate``) also returns how much the hypotheses disagree per joint, reduced on the device by the
+    same scheme (evaluate.accumulate_spread, 72 bytes per (clip,t,f,j)).  The return value is then a dict of CPU tensors:
+    ``"pose"`` as above, ``"idx"`` for "reproj", ``"std"`` [clips,T,F,J] - the RMS distance in metres of the P whole-body
+    hypotheses from their mean joint - and, for ``spread="cov"``, ``"cov"`` [clips,T,F,J,6], their population covariance
+    (xx, xy, xz, yy, yz, zz).  With "mean" only the spread state is kept (it holds the sums: the pose is the same, bit
+    for bit); with "reproj" every chunk is folded into both states.  Both are taken about the MEAN pose."""
     if aggregate not in (None, "mean", "reproj"):
         raise ValueError(f'aggregate must be None, "mean" or "reproj", got {aggregate!r}')
+    if spread not in (None, "std", "cov"):
+        raise ValueError(f'spread must be None, "std" or "cov", got {spread!r}')
+    if spread is not None and aggregate is None:
+        raise ValueError('spread needs aggregate="mean" or "reproj" (it is reduced on the device beside the pose)')
     if hypothesis_chunk is not None and (aggregate is None or int(hypothesis_chunk) < 1):
         raise ValueError("hypothesis_chunk is a positive count and needs an aggregate")
     if aggregate == "reproj" and (cam is None or traj is None):
@@ -100,20 +111,27 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
             raise ValueError(f"traj must be [N,3] with N = {seq_2d.shape[-3]} frames, got {tuple(traj.shape)}")
         traj = cut_clips(traj.unsqueeze(1), model.frames).squeeze(2).to(dev)          # [clips,F,3]
         cam = torch.as_tensor(cam, dtype=torch.float32).to(dev)
-    poses, picks = [], []
+    pose_name = "pick" if reproj else "mean"
+    names = (pose_name,) + (("idx",) if reproj else ()) + (() if spread is None else ("std",) if spread == "std" else ("std", "cov"))
+    kept = {k: [] for k in names}
     for lo in range(0, x2d.shape[0], batch_size):
         hi = min(lo + batch_size, x2d.shape[0])
         operands = (x2d[lo:hi], traj[lo:hi], cam) if reproj else ()
-        state = None
+        state = moments = None
         for pred, h0, _ in sampler.sample_chunks(x2d[lo:hi], None, input_2d_flip=x2d_flip[lo:hi], chunk=hypothesis_chunk):
-            state = accumulate_poses(state, pred, h0, dataset, *operands)
+            if reproj or spread is None:
+                state = accumulate_poses(state, pred, h0, dataset, *operands)
+            if spread is not None:
+                moments = accumulate_spread(moments, pred, h0, dataset)
             del pred
-        out = aggregate_poses_sharded(None, None, model.num_proposals, dataset, group=group, state=state,
-                                      want=("pick", "idx") if reproj else ("mean",))
-        poses.append(out["pick" if reproj else "mean"].cpu())
-        if reproj:
-            picks.append(out["idx"].cpu())
-    return (torch.cat(poses), torch.cat(picks)) if reproj else torch.cat(poses)
+        out = aggregate_poses_sharded(None, None, model.num_proposals, dataset, group=group, state=state, want=names,
+                                      spread_state=moments)
+        for k in names:
+            kept[k].append(out[k].cpu())
+    kept = {k: torch.cat(v) for k, v in kept.items()}
+    if spread is not None:
+        return {("pose" if k == pose_name else k): v for k, v in kept.items()}
+    return (kept["pick"], kept["idx"]) if reproj else kept["mean"]
 
 
 def load_pifpaf_keypoints(path, num_kps=134):
@@ -155,6 +173,14 @@ def stitch_poses(poses, total_frames, frames=27):
     """[clips, T, frames, J, 3] aggregated poses (clips cut by :func:`cut_clips`) -> [T, total_frames, J, 3], by the rule of
     :func:`stitch_clips`: consecutive clips end to end, the last one contributing only its final frames."""
     return stitch_clips(poses.unsqueeze(2), total_frames, frames).squeeze(1)
+
+
+def stitch_spread(spread, total_frames, frames=27):
+    """[clips, T, frames, J] per-joint std or [clips, T, frames, J, 6] covariance (clips cut by :func:`cut_clips`) ->
+    [T, total_frames, J] / [T, total_frames, J, 6], by the rule of :func:`stitch_poses`."""
+    if spread.dim() == 4:
+        return stitch_clips(spread[:, :, None, :, :, None], total_frames, frames)[:, 0, :, :, 0]
+    return stitch_clips(spread.unsqueeze(2), total_frames, frames).squeeze(1)
 
 
 def camera_to_world(X, R, t=0.0):

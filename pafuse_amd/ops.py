@@ -913,6 +913,76 @@ def combine_poses(states, shape, num_proposals, merged=None, want=("mean", "pick
     return out
 
 
+# ------------------------------------------------------------------------------------- spread of the hypotheses
+SPREAD_STATE_DOUBLES_PER_ELEMENT = 9   # double sum[3] + double m2[6] per (b, t, f, j); one more double, the count, ends the state
+SPREAD_OUTPUTS = {"mean": (3,), "cov": (6,), "std": ()}   # trailing shape of every output of combine_spread behind [B,T,F,J]
+
+
+def spread_partials_bytes(B, T, F, J):
+    """Bytes of the state pafuse_spread_partials writes (the formula of pafuse_spread_partials_bytes, restated so that sizes
+    can be planned without the library): 72 bytes per (b,t,f,j) and 8 for the count, all float64; 0 for an empty shape.
+    No P in it."""
+    n = B * T * F * J
+    return (SPREAD_STATE_DOUBLES_PER_ELEMENT * n + 1) * 8 if min(B, T, F, J) > 0 else 0
+
+
+def spread_views(state, B, T, F, J):
+    """Typed views of a flat spread state (1-D float64 tensor of spread_partials_bytes / 8 elements, or longer):
+    sum [B,T,F,J,3], m2 [B,T,F,J,6] (xx, xy, xz, yy, yz, zz), count [1], all f64."""
+    n = B * T * F * J
+    _need(state.dim() == 1 and state.dtype == torch.float64 and state.is_contiguous() and n > 0
+          and state.numel() * 8 >= spread_partials_bytes(B, T, F, J), "spread_views: not a state of these sizes")
+    return {"sum": state[:3 * n].view(B, T, F, J, 3), "m2": state[3 * n:9 * n].view(B, T, F, J, 6), "count": state[9 * n:9 * n + 1]}
+
+
+def spread_partials(pred, conn, h0, out=None):
+    """One shard's spread state (pafuse_spread_partials): pred [B,T,P_r,F,J,3] the LOCAL part-centred hypotheses
+    [h0, h0 + P_r) of the run, conn int32 [J] -> the flat state, a 1-D float64 tensor (spread_views names its pieces).
+    `out`: a float64 buffer at least that long to write into; the result is then `out` itself."""
+    lib = _lib.load()
+    B, T, P_r, F, J = _need_pred("spread_partials", pred)
+    _need(T > 0 and F > 0 and J > 0 and int(h0) >= 0, "spread_partials: T, F, J > 0 and h0 >= 0")
+    _need(conn.numel() == J and conn.dtype == torch.int32, "spread_partials: conn must be int32 [J]")
+    _need_tensors("spread_partials", (pred,), (conn,))
+    dev = pred.device
+    need = int(lib.pafuse_spread_partials_bytes(B, T, F, J))
+    assert need == spread_partials_bytes(B, T, F, J)
+    out = _state_out("spread_partials", out, need, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_spread_partials(_data(pred), _data(conn), B, T, P_r, F, J, int(h0), _data(out), out.numel() * 8,
+                                              _stream(pred)))
+    return out
+
+
+def combine_spread(states, shape, merged=None, want=("mean", "cov", "std")):
+    """pafuse_spread_combine: `states` [W, L] float64 (W flat spread states of the same (B,T,F,J) = `shape`, one per row, in
+    ascending-h0 order; rows may be padded) -> dict with the entries named in `want`: "mean" [B,T,F,J,3] (the sums divided
+    by the states' total count), "cov" [B,T,F,J,6] (population covariance: xx, xy, xz, yy, yz, zz) and "std" [B,T,F,J] (RMS
+    distance from the mean joint), fp32.  `merged`: a float64 buffer that receives the state of the union; of the
+    operands it may only be states[0] (a running state)."""
+    lib = _lib.load()
+    B, T, F, J = (int(v) for v in shape)
+    n = B * T * F * J
+    L = spread_partials_bytes(B, T, F, J) // 8
+    want = tuple(want)
+    _need(all(k in SPREAD_OUTPUTS for k in want), f"combine_spread: want holds mean, cov, std - got {want}")
+    _need_rows(states, L, f"combine_spread: states must be [W, >= {L}] float64")
+    _need(T > 0 and F > 0 and J > 0 and B >= 0, "combine_spread: bad shape")
+    _need(want or merged is not None, "combine_spread: nothing to compute")
+    dev = states.device
+    if merged is not None:
+        _need_merged("combine_spread", merged, states, L, L, states.numel(), "first")
+    out = {k: torch.empty(B, T, F, J, *SPREAD_OUTPUTS[k], device=dev) for k in want}
+    if n == 0:
+        return out
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_spread_combine(
+            states.data_ptr(), states.shape[0], states.shape[1] * 8, B, T, F, J,
+            None if merged is None else merged.data_ptr(), ptr("mean"), ptr("cov"), ptr("std"), _stream(states)))
+    return out
+
+
 # ------------------------------------------------------------------------------ Protocol #2 from partial states
 PROCRUSTES_HEAD_BYTES_PER_ELEMENT = 16   # float jbest, e2, sel + int32 idx per (b, t, f, j)
 

@@ -459,6 +459,23 @@ def _(pred, conn, x2d=None, traj=None, cam=None):
     return [pred.new_empty(B, T, F, J, 3), pred.new_empty(B, T, F, J, 3), pred.new_empty((B, T, F, J), dtype=torch.int32)]
 
 
+# ----------------------------------------------------------------------------------- spread of the hypotheses
+@torch.library.custom_op("pafuse::hypothesis_spread", mutates_args=(), device_types="cuda")
+def hypothesis_spread(pred: torch.Tensor, conn: torch.Tensor) -> List[torch.Tensor]:
+    """The one-shard convenience of pafuse_amd.ops.spread_partials + combine_spread: pred [B,T,P,F,J,3] part-centred ->
+    [mean [B,T,F,J,3], cov [B,T,F,J,6] (population covariance: xx, xy, xz, yy, yz, zz), std [B,T,F,J]], fp32."""
+    from . import ops
+    B, T, P, F, J, _ = pred.shape
+    m = ops.combine_spread(ops.spread_partials(pred, conn, 0).view(1, -1), (B, T, F, J))
+    return [m["mean"], m["cov"], m["std"]]
+
+
+@hypothesis_spread.register_fake
+def _(pred, conn):
+    B, T, P, F, J, _ = pred.shape
+    return [pred.new_empty(B, T, F, J, 3), pred.new_empty(B, T, F, J, 6), pred.new_empty(B, T, F, J)]
+
+
 # ----------------------------------------------------------------------------------------------- noise stream v1
 @torch.library.custom_op("pafuse::noise_fill", mutates_args=(), device_types="cuda")
 def noise_fill(key: torch.Tensor, draw: int, B: int, P: int, F: int, J: int) -> torch.Tensor:
