@@ -171,6 +171,10 @@ SIGNATURES = {
                                       C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
 }
 
+# matrix-product modes (include/pafuse_hip.h: pafuse_mixste2_weights.operand_bf16) and the precision names they go by: the one table
+MODE_F32, MODE_BF16, MODE_BF16X3, MODE_F16X2, MODE_BF16X3_IMAGES = range(5)
+PRECISIONS = {"f32": MODE_F32, "bf16": MODE_BF16, "bf16x3": MODE_BF16X3, "f16x2": MODE_F16X2, "bf16x3_images": MODE_BF16X3_IMAGES}
+
 _lib = None
 
 ABI_VERSION = 8      # include/pafuse_hip.h PAFUSE_ABI_VERSION: the struct layouts mirrored above

@@ -2,7 +2,7 @@
 //
 // Everything in memory, LayerNorm, softmax, attention and the DDIM arithmetic are fp32 (the parity contract is 1e-4 mm
 // MPJPE, SURVEY.md section 7 "Hard parts" 1), with the reference's fp64 islands kept in fp64.  The linear layers'
-// products have three modes (GemmParams::bf16): the inference default splits every fp32 operand into three bf16 slices and
+// products have three modes (GemmParams::mode): the inference default splits every fp32 operand into three bf16 slices and
 // keeps the six products above 2^-24 relative on the bf16 matrix cores with fp32 accumulation (v_mfma_f32_32x32x16_bf16;
 // the qkv layers v_mfma_f32_16x16x32_bf16) - fp32-equivalent results; training and the 'f32' mode run the f32-input
 // matrix cores (v_mfma_f32_32x32x2_f32), attention v_mfma_f32_16x16x4_f32 in every mode.
@@ -346,6 +346,15 @@ __device__ __forceinline__ float wave_sum(float v) {
 // ----------------------------------------------------------------------------------------------------------------
 enum { EPI_BIAS = 0, EPI_ROWLN = 1, EPI_ROWLN_TRAIN = 2 };  // _TRAIN: + DropPath row factor, + pre-norm sum output
 
+// host-side names of the matrix-product modes (GemmParams::mode, pafuse_mixste2_weights::operand_bf16: include/pafuse_hip.h)
+enum { MODE_F32 = 0, MODE_BF16 = 1, MODE_BF16X3 = 2, MODE_F16X2 = 3, MODE_BF16X3_IMAGES = 4 };
+constexpr bool mode_valid(int m) { return m >= MODE_F32 && m <= MODE_BF16X3_IMAGES; }
+constexpr bool mode_split(int m) { return m >= MODE_BF16X3; }      // fp32-equivalent products from operand slices (needs weight images)
+constexpr bool mode_images(int m) { return m >= MODE_F16X2; }      // both operands arrive as images: the H and X pipelines
+constexpr int image_elem_bytes(int m) { return m == MODE_BF16X3_IMAGES ? 6 : 4; }   // of an activation image (H: 4, X: 6)
+// ... and of the layouts of a pre-split weight image (GemmParams::wlayout, pafuse_split_weights)
+enum { WLAYOUT_PLAIN = 0, WLAYOUT_ROWLN = 1, WLAYOUT_M16 = 2 };   // 32x32x16 kernels' | whole-row layers' | gemm16_tile / strip kernels'
+
 struct GemmParams {
     const float* A;     // [M,K]
     const float* W;     // [N,K]  (torch nn.Linear.weight)
@@ -353,9 +362,9 @@ struct GemmParams {
     float* out;         // EPI_BIAS: [M,N]
     int64_t M;
     int N, K;
-    int bf16;  // host-side only: matrix-product mode - 0 fp32 MFMA, 1 bf16-rounded operands, 2 split bf16x3 (needs Wsplit)
-    const uint8_t* Wsplit;  // mode 2: the pre-split image of W (split_weights_kernel), wsplit_bytes(N, K) bytes
-    int wlayout;            // host-side only: 0 = the 32x32x16 kernels' image, 2 = the gemm16_tile (qkv) image
+    int mode;  // host-side only: matrix-product mode, MODE_* above (MODE_BF16X3 needs Wsplit)
+    const uint8_t* Wsplit;  // MODE_BF16X3: the pre-split image of W (split_weights_kernel), wsplit_bytes(N, K) bytes
+    int wlayout;            // host-side only: WLAYOUT_PLAIN or WLAYOUT_M16
     int act;   // EPI_BIAS: 0 none, 1 GELU
     // training, EPI_BIAS through the coalesced (slab) epilogue of gemm_tile or gemm16_tile's (gemm_bias checks): with out_act, `out` receives the
     // pre-activation u and out_act gelu(u) (fc1 forward: the backward needs both); with dact_u, out = (acc + bias) * gelu'(dact_u)

@@ -53,6 +53,26 @@ struct DeviceOnce {
     }
 };
 
+// The one launch stanza.  The kernel is a template argument, so its latch below exists once per kernel instantiation.
+// A launch with more than 64 KB of dynamic LDS needs the kernel's ceiling raised first, once per device (one-process
+// multi-device callers: nn.DataParallel); `lds_attr` is that ceiling where it is not the launch's own size.
+template <auto Kernel> DeviceOnce g_lds_raised;
+
+template <auto Kernel, class... Args>
+int launch_lds(const char* name, dim3 grid, unsigned threads, size_t lds, size_t lds_attr, hipStream_t s, const Args&... args) {
+    if (lds_attr > 64 * 1024 && g_lds_raised<Kernel>.first()) {
+        const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_attr);
+        if (e != hipSuccess) return fail(PAFUSE_E_HIP, "%s: %s", name, hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, s, args...);
+    return check_launch(name);
+}
+template <auto Kernel, class... Args>
+int launch(const char* name, dim3 grid, unsigned threads, size_t lds, hipStream_t s, const Args&... args) {
+    return launch_lds<Kernel>(name, grid, threads, lds, lds, s, args...);
+}
+inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+
 // Makes the device of the caller's stream current for the duration of an entry point (kernel launches, events and
 // function attributes go to the CURRENT device): a caller whose tensors live on cuda:1 while cuda:0 is current
 // would otherwise record events on the wrong device.  The legacy null stream belongs to the current device.
@@ -81,24 +101,20 @@ int launch_gemm(const GemmParams& p, hipStream_t s) {
     if (BF16 == 2 && !p.Wsplit) return fail(PAFUSE_E_ARG, "split-precision GEMM without a pre-split weight image");
     static_assert(EPI == EPI_BIAS || 7 * T::BM * WN <= NSTAGE * T::STAGE_FLOATS, "cross-wave reduction scratch must fit");
     static_assert(stage_bytes <= 160 * 1024, "LDS budget");
-    size_t lds = stage_bytes;
-    auto k = gemm_kernel<WM, WN, NT, EPI, NSTAGE, MINW, TR, BF16>;
-#ifdef PAFUSE_DIAG
-    static const int dbg_pad = [] { const char* e = getenv("PAFUSE_DEBUG_LDS_PAD"); return e ? atoi(e) : 0; }();
-    if (dbg_pad && BF16 == 2 && EPI == EPI_BIAS) {  // diagnostic: keep other kernels off this workgroup's CU
-        lds = std::max(lds, (size_t)dbg_pad);
-        hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    } else
-#endif
-    if (lds > 64 * 1024) {
-        static DeviceOnce once;  // the attribute is per device (one-process multi-device callers: nn.DataParallel)
-        if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    constexpr auto k = gemm_kernel<WM, WN, NT, EPI, NSTAGE, MINW, TR, BF16>;
     const int64_t tiles_m = (p.M + T::BM - 1) / T::BM;
     const int64_t tiles = tiles_m * (p.N / T::BN);
     if (tiles <= 0 || tiles > 0x7fffffff) return fail(PAFUSE_E_ARG, "gemm grid out of range");
-    hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(T::NTHR), lds, s, p);
-    return check_launch("gemm_kernel");
+#ifdef PAFUSE_DIAG
+    static const int dbg_pad = [] { const char* e = getenv("PAFUSE_DEBUG_LDS_PAD"); return e ? atoi(e) : 0; }();
+    if (dbg_pad && BF16 == 2 && EPI == EPI_BIAS) {  // diagnostic: keep other kernels off this workgroup's CU (set on every call, as before)
+        const size_t lds = std::max(stage_bytes, (size_t)dbg_pad);
+        hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(T::NTHR), lds, s, p);
+        return check_launch("gemm_kernel");
+    }
+#endif
+    return launch<k>("gemm_kernel", (unsigned)tiles, T::NTHR, stage_bytes, s, p);
 }
 
 // qkv projection + attention of one head per workgroup (kernels.hpp fqa_kernel)
@@ -106,28 +122,22 @@ template <int LP, int DP>
 int launch_fqa(const FqaParams& f, hipStream_t s) {
     using FT = FqaTile<LP, DP>;
     static_assert(FT::LDS_BYTES <= 80 * 1024, "two workgroups per CU");
-    auto k = fqa_kernel<LP, DP>;
-    if (FT::LDS_BYTES > 64 * 1024) {
-        static DeviceOnce once;
-        if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FT::LDS_BYTES);
-    }
     const int64_t ntiles = (f.nseq + f.nseq_tile - 1) / f.nseq_tile;
     const int64_t blocks = (ntiles + 7) / 8 * 8 * f.heads;
     if (blocks <= 0 || blocks > 0x7fffffff) return fail(PAFUSE_E_ARG, "fused qkv-attention grid out of range");
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), FT::LDS_BYTES, s, f);
-    return check_launch("fqa_kernel");
+    return launch<fqa_kernel<LP, DP>>("fqa_kernel", (unsigned)blocks, 256, FT::LDS_BYTES, s, f);
 }
 
 // padded sizes of the fused kernel for a sequence length / head dim, 0 = no fused form (the caller keeps qkv GEMM + attention)
-// (mode 3, f16x2, also has an 80-token form on five waves - 160-row tiles - for head dim <= 32: the face's 68 joints)
-static int fqa_lp(int L, int bf16 = 2) { return L <= 32 ? 32 : (L <= 48 ? 48 : (bf16 >= 3 && L <= 80 ? 80 : 0)); }
+// (the image modes also have an 80-token form on five waves - 160-row tiles - for head dim <= 32: the face's 68 joints)
+static int fqa_lp(int L, int mode) { return L <= 32 ? 32 : (L <= 48 ? 48 : (mode_images(mode) && L <= 80 ? 80 : 0)); }
 static int fqa_dp(int d) { return (d % 4 || d > 48) ? 0 : (d <= 32 ? 32 : 48); }
-static bool fqa_has(int L, int d, int bf16 = 2) {   // (48, 48) would need 80.4 KB of LDS: one workgroup per CU, not built
-    const int lp = fqa_lp(L, bf16), dp = fqa_dp(d);
+static bool fqa_has(int L, int d, int mode) {   // (48, 48) would need 80.4 KB of LDS: one workgroup per CU, not built
+    const int lp = fqa_lp(L, mode), dp = fqa_dp(d);
     return lp && dp && !(lp >= 48 && dp == 48);
 }
 // mode 4 (xgemm.hpp xfqa_kernel): the workgroup's columns come in whole 32-column blocks - two heads at head dim 33 .. 48
-static bool xfqa_has(int L, int d, int heads) { return fqa_has(L, d, 4) && (fqa_dp(d) == 32 || heads % 2 == 0); }
+static bool xfqa_has(int L, int d, int heads) { return fqa_has(L, d, MODE_BF16X3_IMAGES) && (fqa_dp(d) == 32 || heads % 2 == 0); }
 // rows of the fused kernel's q | k | v tiles, and whole sequences per tile (the last one's LP-row key tile inside the buffer)
 static int fqa_rows(int lp) { return lp == 80 ? 160 : 128 + (lp == 48 ? 4 : 0); }
 static int fqa_tile_rows(int lp) { return lp == 80 ? 160 : 128; }
@@ -139,18 +149,12 @@ int launch_hfqa(const FqaParams& f, hipStream_t s) {
     using FT = HfqaTile<LP, DP, HPW>;
     static_assert(FT::LDS_BYTES <= 80 * 1024, "two workgroups per CU");
     if (f.heads % HPW) return fail(PAFUSE_E_SHAPE, "fused qkv-attention: %d heads do not split into groups of %d", f.heads, HPW);
-    auto k = hfqa_kernel<LP, DP, HPW>;
-    if (FT::LDS_BYTES > 64 * 1024) {
-        static DeviceOnce once;
-        if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FT::LDS_BYTES);
-    }
     if (!f.g.Ah || !f.g.Wh) return fail(PAFUSE_E_ARG, "fused qkv-attention (f16x2) without the H images of its operands");
     if (f.g.M >= (int64_t)1 << 31 || f.nseq >= (int64_t)1 << 31) return fail(PAFUSE_E_ARG, "fused qkv-attention: more than 2^31 tokens");
     const int64_t ntiles = (f.nseq + f.nseq_tile - 1) / f.nseq_tile;
     const int64_t blocks = (ntiles + 7) / 8 * 8 * (f.heads / HPW);
     if (blocks <= 0 || blocks > 0x7fffffff) return fail(PAFUSE_E_ARG, "fused qkv-attention grid out of range");
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(FT::NTHR), FT::LDS_BYTES, s, f);
-    return check_launch("hfqa_kernel");
+    return launch<hfqa_kernel<LP, DP, HPW>>("hfqa_kernel", (unsigned)blocks, FT::NTHR, FT::LDS_BYTES, s, f);
 }
 
 // ... and in the bf16x3 X pipeline (xgemm.hpp xfqa_kernel): A and the head-major weight as X images, o as X image
@@ -159,32 +163,26 @@ int launch_xfqa(const FqaParams& f, hipStream_t s) {
     using FT = XfqaTile<LP, DP, HPW>;
     static_assert(2 * FT::LDS_BYTES <= 160 * 1024, "two workgroups per CU");
     if (f.heads % HPW) return fail(PAFUSE_E_SHAPE, "fused qkv-attention: %d heads do not split into groups of %d", f.heads, HPW);
-    auto k = xfqa_kernel<LP, DP, HPW>;
-    if (FT::LDS_BYTES > 64 * 1024) {
-        static DeviceOnce once;
-        if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FT::LDS_BYTES);
-    }
     if (!f.g.Ah || !f.g.Wh) return fail(PAFUSE_E_ARG, "fused qkv-attention (bf16x3 images) without the X images of its operands");
     if (f.g.K % 32 || f.g.K <= 0) return fail(PAFUSE_E_SHAPE, "fused qkv-attention: K=%d must be a positive multiple of 32", f.g.K);
     if (f.g.M >= (int64_t)1 << 31 || f.nseq >= (int64_t)1 << 31) return fail(PAFUSE_E_ARG, "fused qkv-attention: more than 2^31 tokens");
     const int64_t ntiles = (f.nseq + f.nseq_tile - 1) / f.nseq_tile;
     const int64_t blocks = (ntiles + 7) / 8 * 8 * (f.heads / HPW);
     if (blocks <= 0 || blocks > 0x7fffffff) return fail(PAFUSE_E_ARG, "fused qkv-attention grid out of range");
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(FT::NTHR), FT::LDS_BYTES, s, f);
-    return check_launch("xfqa_kernel");
+    return launch<xfqa_kernel<LP, DP, HPW>>("xfqa_kernel", (unsigned)blocks, FT::NTHR, FT::LDS_BYTES, s, f);
 }
 
 int fused_qkv_attention(const FqaParams& f, hipStream_t s) {
     if (f.nseq <= 0) return PAFUSE_OK;
-    const int lp = fqa_lp(f.L, f.g.bf16), dp = fqa_dp(f.d);
-    if (f.g.bf16 == 4) {
+    const int lp = fqa_lp(f.L, f.g.mode), dp = fqa_dp(f.d);
+    if (f.g.mode == MODE_BF16X3_IMAGES) {
         if (lp == 80 && dp == 32) return launch_xfqa<80, 32, 1>(f, s);
         if (lp == 32 && dp == 48) return launch_xfqa<32, 48, 2>(f, s);
         if (lp == 32 && dp == 32) return f.heads % 2 ? launch_xfqa<32, 32, 1>(f, s) : launch_xfqa<32, 32, 2>(f, s);
         if (lp == 48 && dp == 32) return f.heads % 2 ? launch_xfqa<48, 32, 1>(f, s) : launch_xfqa<48, 32, 2>(f, s);
         return fail(PAFUSE_E_SHAPE, "fused qkv-attention: no kernel for L=%d, d=%d", f.L, f.d);
     }
-    if (f.g.bf16 == 3) {
+    if (f.g.mode == MODE_F16X2) {
         if (lp == 80 && dp == 32) return launch_hfqa<80, 32, 1>(f, s);
         // head dim <= 32: two heads per workgroup share the A stream (the ring grows to the 80 KB two workgroups per CU allow)
         if (lp == 32 && dp == 48) return launch_hfqa<32, 48, 1>(f, s);
@@ -204,15 +202,9 @@ template <int NT2, int MINW>
 int launch_hmlp(const MlpParams& m, hipStream_t s) {
     using T = MlpTile<NT2>;
     static_assert(T::LDS_BYTES <= (MINW == 2 ? 80 : 160) * 1024, "LDS budget");
-    auto k = hmlp_kernel<NT2, MINW>;
-    {
-        static DeviceOnce once;
-        if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES);
-    }
     const int64_t tiles = (m.g.M + 127) / 128;
     if (tiles <= 0 || tiles > 0x7fffffff) return fail(PAFUSE_E_ARG, "fused MLP grid out of range");
-    hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(256), T::LDS_BYTES, s, m);
-    return check_launch("hmlp_kernel");
+    return launch<hmlp_kernel<NT2, MINW>>("hmlp_kernel", (unsigned)tiles, 256, T::LDS_BYTES, s, m);   // 74 - 75 KB
 }
 int fused_mlp(const MlpParams& m, hipStream_t s) {
     if (m.g.M <= 0) return PAFUSE_OK;
@@ -234,8 +226,7 @@ int launch_gemm16(const GemmParams& p, hipStream_t s) {
     if (!p.Wsplit) return fail(PAFUSE_E_ARG, "split-precision GEMM without a pre-split weight image");
     const int64_t tiles = ((p.M + T::BM - 1) / T::BM) * (p.N / T::BN);
     if (tiles <= 0 || tiles > 0x7fffffff) return fail(PAFUSE_E_ARG, "gemm grid out of range");
-    hipLaunchKernelGGL((gemm16_kernel<NB, MINW>), dim3((unsigned)tiles), dim3(T::NTHR), T::STAGE_BYTES, s, p);
-    return check_launch("gemm16_kernel");
+    return launch<gemm16_kernel<NB, MINW>>("gemm16_kernel", (unsigned)tiles, T::NTHR, T::STAGE_BYTES, s, p);
 }
 
 // ---- the strip GEMM (sgemm.hpp, round 6): the plain split-precision layers (qkv, fc1) on the software-pipelined persistent kernel.
@@ -262,21 +253,17 @@ int launch_strip2(const GemmParams& p, hipStream_t s) {
     using T = StripTile<NB, RG, NW, 2>;
     static_assert(T::LDS_BYTES <= 80 * 1024, "two workgroups per CU");
     if (!p.Wsplit) return fail(PAFUSE_E_ARG, "split-precision GEMM without a pre-split weight image");
-    auto k = sgemm2_kernel<NB, RG, NW, SEPI_BIAS, 2, FLAGS>;
-    static DeviceOnce once;
-    if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::LDS_BYTES);
     const int64_t tiles = ((p.M + T::BM - 1) / T::BM) * (p.N / T::BN);
     if (tiles <= 0 || tiles > 0x7fffffff) return fail(PAFUSE_E_ARG, "gemm grid out of range");
     int64_t grid = (int64_t)device_cus() * PAFUSE_STRIP_WGS_PER_CU / 8 * 8;   // a multiple of 8: virtual workgroup v = b + j grid keeps b's XCD
     if (grid >= tiles || grid <= 0) grid = tiles;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(T::NTHR), T::LDS_BYTES, s, p);
-    return check_launch("sgemm2_kernel");
+    return launch<sgemm2_kernel<NB, RG, NW, SEPI_BIAS, 2, FLAGS>>("sgemm2_kernel", (unsigned)grid, T::NTHR, T::LDS_BYTES, s, p);
 }
 // which plain layers the strip kernel takes: an M16 image, at most one training epilogue option (alone), at least four 32-deep chunks (the deferred
 // stores of a tile go out inside the first four chunks of the next one), a column count one of its tiles divides
 bool strip2_ok(const GemmParams& p) {
     if ((p.out_act || p.dact_u) && (p.ln_in || p.act || (p.out_act && p.dact_u))) return false;   // training options: alone, on a plain product
-    return p.bf16 == 2 && p.wlayout == 2 && p.K % 32 == 0 && p.K >= 128 && p.M > 0 &&
+    return p.mode == MODE_BF16X3 && p.wlayout == WLAYOUT_M16 && p.K % 32 == 0 && p.K >= 128 && p.M > 0 &&
            p.M * (int64_t)p.N < (int64_t)1 << 31 && p.M * (int64_t)p.K < (int64_t)1 << 31 &&   // (32-bit float offsets of its rows)
            (p.N % 128 == 0 || p.N % 112 == 0 || p.N % 96 == 0);
 }
@@ -313,15 +300,9 @@ int launch_gemm_dma(const GemmParams& p, hipStream_t s) {
     static_assert(EPI == EPI_BIAS || (size_t)7 * T::BM * WN * sizeof(float) <= lds, "cross-wave reduction scratch must fit");
     if (!p.Wsplit) return fail(PAFUSE_E_ARG, "split-precision GEMM without a pre-split weight image");
     if (p.K % BKC) return fail(PAFUSE_E_SHAPE, "split GEMM: K=%d is not a multiple of %d", p.K, BKC);
-    auto k = gemm_dma_kernel<WM, WN, NT, EPI, NSTAGE, MINW, 0, BKC>;
-    if (lds > 64 * 1024) {
-        static DeviceOnce once;
-        if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
     const int64_t tiles = (p.M + T::BM - 1) / T::BM * (p.N / T::BN);
     if (tiles <= 0 || tiles > 0x7fffffff) return fail(PAFUSE_E_ARG, "gemm grid out of range");
-    hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(T::NTHR), lds, s, p);
-    return check_launch("gemm_dma_kernel");
+    return launch<gemm_dma_kernel<WM, WN, NT, EPI, NSTAGE, MINW, 0, BKC>>("gemm_dma_kernel", (unsigned)tiles, T::NTHR, lds, s, p);
 }
 
 // ---- f16x2 "H pipeline" (hgemm.hpp): both operands arrive as H images; one workgroup of WM x WN waves per CU
@@ -334,15 +315,9 @@ int launch_hgemm(const GemmParams& p, hipStream_t s) {
     if (!p.Ah || !p.Wh) return fail(PAFUSE_E_ARG, "f16x2 GEMM without the H images of its operands");
     if (p.K % BKC || p.K <= 0 || p.N % T::BN) return fail(PAFUSE_E_SHAPE, "f16x2 GEMM: N=%d, K=%d do not fit the %d-column tile", p.N, p.K, T::BN);
     if (HRES && !p.resid_h) return fail(PAFUSE_E_ARG, "f16x2 whole-row GEMM: no H-image residual");
-    auto k = hgemm_kernel<WM, WN, NT, EPI, NSTAGE, BKC, MINW, HRES>;
-    if (lds > 64 * 1024) {
-        static DeviceOnce once;
-        if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
     const int64_t tiles = (p.M + T::BM - 1) / T::BM * (p.N / T::BN);
     if (tiles <= 0 || tiles > 0x7fffffff) return fail(PAFUSE_E_ARG, "gemm grid out of range");
-    hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(T::NTHR), lds, s, p);
-    return check_launch("hgemm_kernel");
+    return launch<hgemm_kernel<WM, WN, NT, EPI, NSTAGE, BKC, MINW, HRES>>("hgemm_kernel", (unsigned)tiles, T::NTHR, lds, s, p);
 }
 
 // widths the f16x2 kernels serve: the PAFUSE parts' (whole-row layers), and every plain-layer width that tiles by 128 or 224
@@ -386,15 +361,9 @@ int launch_xgemm(const GemmParams& p, hipStream_t s) {
     if (!p.Ah || !p.Wh) return fail(PAFUSE_E_ARG, "bf16x3 image GEMM without the X images of its operands");
     if (p.K % 32 || p.K <= 0 || p.N % T::BN) return fail(PAFUSE_E_SHAPE, "bf16x3 image GEMM: N=%d, K=%d do not fit the %d-column tile", p.N, p.K, T::BN);
     if (HRES && !p.resid_h) return fail(PAFUSE_E_ARG, "bf16x3 whole-row GEMM: no X-image residual");
-    auto k = xgemm_kernel<WM, WN, NT, EPI, NSTAGE, BKC, MINW, HRES>;
-    if (lds > 64 * 1024) {
-        static DeviceOnce once;
-        if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
     const int64_t tiles = (p.M + T::BM - 1) / T::BM * (p.N / T::BN);
     if (tiles <= 0 || tiles > 0x7fffffff) return fail(PAFUSE_E_ARG, "gemm grid out of range");
-    hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(T::NTHR), lds, s, p);
-    return check_launch("xgemm_kernel");
+    return launch<xgemm_kernel<WM, WN, NT, EPI, NSTAGE, BKC, MINW, HRES>>("xgemm_kernel", (unsigned)tiles, T::NTHR, lds, s, p);
 }
 
 // tile choice per shape: tools/xgemm_bench.hip (profiles/r05_xgemm_bench.log).  With six products per k the K loops of these
@@ -450,37 +419,37 @@ constexpr int debug_f32_mask() { return 0; }
 #endif
 int gemm_bias(const GemmParams& p0, hipStream_t s) {
     GemmParams p = p0;
-    if (p.bf16 == 2 && (debug_f32_mask() & 1)) p.bf16 = 0;
-    if (p.bf16 == 2 && (debug_f32_mask() & 4) && !p.act) p.bf16 = 0;   // qkv only
-    if (p.bf16 == 2 && (debug_f32_mask() & 8) && p.act) p.bf16 = 0;    // fc1 only
-    if (p.bf16 == 2 && (debug_f32_mask() & 16)) {                        // split arithmetic, small 128x64 tiles only
+    if (p.mode == MODE_BF16X3 && (debug_f32_mask() & 1)) p.mode = MODE_F32;
+    if (p.mode == MODE_BF16X3 && (debug_f32_mask() & 4) && !p.act) p.mode = MODE_F32;   // qkv only
+    if (p.mode == MODE_BF16X3 && (debug_f32_mask() & 8) && p.act) p.mode = MODE_F32;    // fc1 only
+    if (p.mode == MODE_BF16X3 && (debug_f32_mask() & 16)) {                        // split arithmetic, small 128x64 tiles only
         if (p.N % 64 == 0) return launch_gemm<4, 1, 2, EPI_BIAS, 1, 4, 0, 2>(p, s);
     }
     if (p.M <= 0) return PAFUSE_OK;
     if (p.K % BK || p.N % 32 || p.K <= 0 || p.N <= 0)
         return fail(PAFUSE_E_SHAPE, "linear: N=%d K=%d must be positive multiples of 32", p.N, p.K);
     // the training epilogue options live in the slab epilogue of gemm_tile (every N % 64 == 0 route below ends there) and in gemm16_tile's
-    if ((p.out_act || p.dact_u) && ((p.N % 64 && !(p.bf16 == 2 && p.wlayout == 2)) || p.bf16 > 2 || p.ln_in || p.act))
+    if ((p.out_act || p.dact_u) && ((p.N % 64 && !(p.mode == MODE_BF16X3 && p.wlayout == WLAYOUT_M16)) || mode_images(p.mode) || p.ln_in || p.act))
         return fail(PAFUSE_E_ARG, "linear: out_act / dact_u need N %% 64 == 0 and a plain fp32 or bf16x3 product");
-    if (p.bf16 == 3) return hgemm_bias(p, s);   // f16x2: the H pipeline
-    if (p.bf16 == 4) return xgemm_bias(p, s);   // bf16x3 on images: the X pipeline
+    if (p.mode == MODE_F16X2) return hgemm_bias(p, s);   // f16x2: the H pipeline
+    if (p.mode == MODE_BF16X3_IMAGES) return xgemm_bias(p, s);   // bf16x3 on images: the X pipeline
     // small accumulators + single LDS stage = 4-5 independent workgroups per CU, which hides the per-tile
     // prologue/epilogue (measured with tools/gemm_bench.hip: 128x64 tiles reach 72-74 % of the f32 MFMA peak at the
     // qkv shape, 128x96/double-buffered 65-67 %, 128x128 58-60 %)
 #ifdef PAFUSE_QKV_32X32   // A/B build (tools/): the qkv layers on the 32x32x16 tiles, their images in layout 0
-    p.wlayout = 0;
+    p.wlayout = WLAYOUT_PLAIN;
 #endif
 #ifndef PAFUSE_NO_STRIP
     if (strip2_ok(p)) return strip2_bias(p, s);   // qkv, fc1 (+ GELU): the pipelined persistent strip kernel (sgemm.hpp; same bits as gemm16_tile)
 #endif
-    if (p.bf16 == 2 && p.wlayout == 2) {  // 16x16x32 MFMAs on the M16 image (kernels.hpp gemm16_tile): training's epilogue options, short K
+    if (p.mode == MODE_BF16X3 && p.wlayout == WLAYOUT_M16) {  // 16x16x32 MFMAs on the M16 image (kernels.hpp gemm16_tile): training's epilogue options, short K
         if (p.N % 128 == 0) return launch_gemm16<8, 3>(p, s);    // body 1152, hands 768: 128 x 128 tiles, 3 workgroups per CU
         if (p.N % 96 == 0) return launch_gemm16<6, 3>(p, s);     // face 672, single-model 864: 128 x 96
         if (p.N % 112 == 0) return launch_gemm16<7, 3>(p, s);    // face 224, 448 (training: every plain GEMM of the face): 128 x 112
         if (p.N % 64 == 0) return launch_gemm16<4, 4>(p, s);
         return launch_gemm16<2, 4>(p, s);
     }
-    if (p.bf16 == 2) {  // split precision (bf16x3): fp32-equivalent products on the bf16 matrix cores
+    if (p.mode == MODE_BF16X3) {  // split precision (bf16x3): fp32-equivalent products on the bf16 matrix cores
         // measured per shape with tools/gemm_bench.hip (profiles/r02_gemm_bench_split_v1.log): 128x128 tiles at two
         // workgroups per CU where N allows (159 TFLOP/s at the body qkv shape), 128x64 at four otherwise (148)
         if (p.N % 128 == 0 && p.M >= 4096) return launch_gemm<4, 1, 4, EPI_BIAS, 1, PAFUSE_FC1_MINW, 0, 2>(p, s);
@@ -488,7 +457,7 @@ int gemm_bias(const GemmParams& p0, hipStream_t s) {
         if (p.N % 96 == 0) return launch_gemm<4, 1, 3, EPI_BIAS, 1, 1, 1, 2>(p, s);
         return launch_gemm<4, 1, 1, EPI_BIAS, 1, 1, 0, 2>(p, s);
     }
-    if (p.bf16) {  // opt-in bf16-operand mode: same tiles, bf16 MFMA
+    if (p.mode != MODE_F32) {  // opt-in bf16-operand mode: same tiles, bf16 MFMA
         if (p.N % 64 == 0) return launch_gemm<4, 1, 2, EPI_BIAS, 1, 5, 0, 1>(p, s);
         if (p.N % 96 == 0) return launch_gemm<4, 1, 3, EPI_BIAS, 1, 1, 1, 1>(p, s);
         return launch_gemm<4, 1, 1, EPI_BIAS, 1, 1, 0, 1>(p, s);
@@ -501,26 +470,26 @@ int gemm_bias(const GemmParams& p0, hipStream_t s) {
 template <int EPI>
 int gemm_rowln_as(const GemmParams& p0, hipStream_t s) {
     GemmParams p = p0;
-    if (p.bf16 == 2 && (debug_f32_mask() & 2)) p.bf16 = 0;
+    if (p.mode == MODE_BF16X3 && (debug_f32_mask() & 2)) p.mode = MODE_F32;
     if (p.M <= 0) return PAFUSE_OK;
     if (p.K % BK || p.K <= 0) return fail(PAFUSE_E_SHAPE, "rowln: K=%d must be a positive multiple of 32", p.K);
-    if (p.bf16 == 3 || p.bf16 == 4) {   // f16x2: the H pipeline; bf16x3 on images: the X pipeline (inference only)
-        if constexpr (EPI == EPI_ROWLN) return p.bf16 == 3 ? hgemm_rowln(p, s) : xgemm_rowln(p, s);
+    if (p.mode == MODE_F16X2 || p.mode == MODE_BF16X3_IMAGES) {   // f16x2: the H pipeline; bf16x3 on images: the X pipeline (inference only)
+        if constexpr (EPI == EPI_ROWLN) return p.mode == MODE_F16X2 ? hgemm_rowln(p, s) : xgemm_rowln(p, s);
         else return fail(PAFUSE_E_ARG, "training has no image-pipeline kernels");
     }
     if constexpr (EPI == EPI_ROWLN_TRAIN) {   // training forward with split products: the three PAFUSE widths (train_host.inc)
-        if (p.bf16 == 2) {
+        if (p.mode == MODE_BF16X3) {
             switch (p.N) {
                 case 384: return launch_gemm_dma<2, 2, 6, EPI, 2, 2, 16>(p, s);
                 case 256: return launch_gemm_dma<2, 2, 4, EPI, 2, 2, 16>(p, s);
                 case 224: if (p.M >= 4096) return launch_gemm_dma<4, 1, 7, EPI, 2, 2, 16>(p, s); break;
                 default: break;
             }
-            p.bf16 = 0;   // no split whole-row tile for this shape: the fp32 kernels below
+            p.mode = MODE_F32;   // no split whole-row tile for this shape: the fp32 kernels below
         }
     }
     if constexpr (EPI == EPI_ROWLN) {
-        if (p.bf16 == 2) {
+        if (p.mode == MODE_BF16X3) {
             switch (p.N) {
                 // picked per width with tools/gemm_bench.hip (profiles/r02_gemm_bench_*.log): the LDS-DMA kernel on 16-deep
                 // chunks, four waves, a two-stage ring and TWO workgroups per CU - the LayerNorm epilogue of one tile
@@ -537,7 +506,7 @@ int gemm_rowln_as(const GemmParams& p0, hipStream_t s) {
                 case 64: return launch_gemm<1, 2, 1, EPI, 1, 1, 1, 2>(p, s);
                 default: break;
             }
-        } else if (p.bf16) {
+        } else if (p.mode != MODE_F32) {
             switch (p.N) {
                 case 384: return launch_gemm<1, 4, 3, EPI, 1, 1, 1, 1>(p, s);
                 case 288: return launch_gemm<1, 3, 3, EPI, 1, 1, 1, 1>(p, s);
@@ -570,7 +539,7 @@ int gemm_rowln_train(const GemmParams& p, hipStream_t s) { return gemm_rowln_as<
 // Only the split-precision mode has them (the fp32 mode overlaps parts on streams instead); anything a grouped kernel
 // has no variant for goes part by part through the dispatch above - same tiles, same arithmetic, same results.
 bool group_ok_rowln(const GemmParams& p) {
-    return p.bf16 == 2 && p.Wsplit && (p.N == 384 || p.N == 256 || (p.N == 224 && p.M >= 4096)) && p.K % 16 == 0 && p.K > 0 &&
+    return p.mode == MODE_BF16X3 && p.Wsplit && (p.N == 384 || p.N == 256 || (p.N == 224 && p.M >= 4096)) && p.K % 16 == 0 && p.K > 0 &&
            !(debug_f32_mask() & 2);
 }
 // (the plain layers - qkv, fc1 - have no shared grid since round 6: the persistent strip kernel fills the chip from one part's tiles;
@@ -615,11 +584,7 @@ int gemm_group(const GemmParams* ps, int n, hipStream_t s, bool shared_grids) {
     for (int k = n + 1; k <= GROUP_MAX; ++k) g.first[k] = (int)first;
     constexpr size_t lds = 2 * DmaTile<2, 2, 6, 16>::STAGE_BYTES;  // the widest variant's ring
     static_assert(lds >= 2 * DmaTile<2, 2, 4, 16>::STAGE_BYTES && lds >= 2 * DmaTile<4, 1, 7, 16>::STAGE_BYTES && lds <= 80 * 1024, "LDS");
-    auto k = grouped_rowln_kernel<EPI_ROWLN>;
-    static DeviceOnce once;
-    if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)first), dim3(256), lds, s, g);
-    return check_launch("grouped_rowln_kernel");
+    return launch<grouped_rowln_kernel<EPI_ROWLN>>("grouped_rowln_kernel", (unsigned)first, 256, lds, s, g);
 }
 
 bool width_supported(int C) { return C == 384 || C == 288 || C == 256 || C == 224 || C == 128 || C == 64; }
@@ -632,8 +597,7 @@ int launch_attn(const AttnParams& p, hipStream_t s) {
     const int64_t nitems = p.nseq * p.heads;
     const int64_t grid = (nitems + ITEMS - 1) / ITEMS;
     if (grid > 0x7fffffff) return fail(PAFUSE_E_ARG, "attention grid out of range");
-    hipLaunchKernelGGL((attn_kernel<LP, DP, NW>), dim3((unsigned)grid), dim3(NW * 64), lds, s, p);
-    return check_launch("attn_kernel");
+    return launch<attn_kernel<LP, DP, NW>>("attn_kernel", (unsigned)grid, NW * 64, lds, s, p);
 }
 
 template <int DP>
@@ -642,12 +606,7 @@ int launch_attn_long(const AttnParams& p, hipStream_t s) {
     static_assert(lds <= 160 * 1024, "LDS");
     const int64_t grid = p.nseq * p.heads;
     if (grid > 0x7fffffff) return fail(PAFUSE_E_ARG, "attention grid out of range");
-    {
-        static DeviceOnce once;
-        if (once.first()) hipFuncSetAttribute((const void*)attn_long_kernel<DP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    hipLaunchKernelGGL(attn_long_kernel<DP>, dim3((unsigned)grid), dim3(1024), lds, s, p);
-    return check_launch("attn_long_kernel");
+    return launch<attn_long_kernel<DP>>("attn_long_kernel", (unsigned)grid, 1024, lds, s, p);
 }
 
 int attention(const AttnParams& p, hipStream_t s) {
@@ -689,7 +648,6 @@ struct PartBuffers {
     float* stats;              // [M,2] (mean, rstd) of a row when the LayerNorm is folded into the consumer GEMM
 };
 
-static int image_elem_bytes(int operand_mode) { return operand_mode == 4 ? 6 : 4; }
 size_t part_buffer_bytes(int64_t M, int C, int B, int eb = 4) {
     return align_up((size_t)M * C * 4) + 2 * align_up((size_t)M * C * eb) + align_up((size_t)M * 3 * C * 4) + align_up((size_t)B * C * 4) +
            align_up((size_t)M * 3 * 4) + align_up((size_t)M * 2 * 4);
@@ -727,7 +685,7 @@ PartBuffers offset_rows(const PartBuffers& pb, int64_t row0, int C) {
 
 static bool ln_folded(const pafuse_mixste2_weights* w) { return w->ste[0].qkv_lt != nullptr; }   // (qkv_ls / fc1_ls: round 3's uncentred form, not read)
 // f16x2 with the LayerNorm folded: the residual stream between the blocks lives in memory as its H image only
-static bool h_residual_only(const pafuse_mixste2_weights* w) { return w->operand_bf16 >= 3 && ln_folded(w) && !w->keep_f32_residual; }
+static bool h_residual_only(const pafuse_mixste2_weights* w) { return mode_images(w->operand_bf16) && ln_folded(w) && !w->keep_f32_residual; }
 
 // `training`: the training entry points make the images of the weights they multiply themselves (weights change every step)
 int check_weights(const pafuse_mixste2_weights* w, bool training = false) {
@@ -741,16 +699,16 @@ int check_weights(const pafuse_mixste2_weights* w, bool training = false) {
     if (d % 4 || d > 48) return fail(PAFUSE_E_SHAPE, "head dim %d unsupported", d);
     if (w->joints < 1 || w->joints > 144 || w->frames < 1 || w->frames > ATTN_LONG_LP)
         return fail(PAFUSE_E_SHAPE, "sequence lengths J=%d F=%d: J must be in 1..144, F in 1..%d", w->joints, w->frames, ATTN_LONG_LP);
-    if (w->operand_bf16 == 3 && w->frames > 144)   // (the long-sequence attention writes fp32 rows, not the f16x2 H image)
+    if (w->operand_bf16 == MODE_F16X2 && w->frames > 144)   // (the long-sequence attention writes fp32 rows, not the f16x2 H image)
         return fail(PAFUSE_E_SHAPE, "f16x2: no attention form for clips of %d > 144 frames: use mode 2", w->frames);
-    if (w->operand_bf16 < 0 || w->operand_bf16 > 4) return fail(PAFUSE_E_ARG, "matrix-product mode %d", w->operand_bf16);
-    if (w->operand_bf16 >= 3) {   // the image pipelines: the PAFUSE part widths; plain layers that tile by 128 or 224 columns
+    if (!mode_valid(w->operand_bf16)) return fail(PAFUSE_E_ARG, "matrix-product mode %d", w->operand_bf16);
+    if (mode_images(w->operand_bf16)) {   // the image pipelines: the PAFUSE part widths; plain layers that tile by 128 or 224 columns
         const int hidden = w->mlp_hidden > 0 ? w->mlp_hidden : 2 * w->channels;
         if (!hgemm_width(w->channels) || !hgemm_plain_n(3 * w->channels) || !hgemm_plain_n(hidden) || hidden % 32)
             return fail(PAFUSE_E_SHAPE, "the image pipelines (f16x2, bf16x3 on images) serve the widths 224 / 256 / 384 with an MLP hidden "
                                         "width that is a multiple of 128 or 224 (got C = %d, hidden = %d): use mode 2", w->channels, hidden);
     }
-    if (w->operand_bf16 == 4 && !training) {   // bf16x3 on images: qkv + attention fused in every block (no unfused attention on X images)
+    if (w->operand_bf16 == MODE_BF16X3_IMAGES && !training) {   // bf16x3 on images: qkv + attention fused in every block (no unfused attention on X images)
         for (int i = 0; i < w->depth; ++i)
             for (const pafuse_block_weights* b : {&w->ste[i], &w->tte[i]})
                 if (!b->qkv_hs || !b->qkv_hb) return fail(PAFUSE_E_ARG, "bf16x3 on images needs the head-major qkv image of every block (qkv_hs, qkv_hb)");
@@ -761,12 +719,12 @@ int check_weights(const pafuse_mixste2_weights* w, bool training = false) {
     if (w->mlp_hidden < 0 || (w->mlp_hidden > 0 && (w->mlp_hidden % 32 || w->mlp_hidden > 3 * w->channels)))
         return fail(PAFUSE_E_SHAPE, "mlp hidden width %d must be a multiple of 32 and at most 3C = %d", w->mlp_hidden, 3 * w->channels);
     if (!(w->qk_scale >= 0.f)) return fail(PAFUSE_E_ARG, "qk_scale must be positive (0 = head_dim^-0.5)");
-    if (training && (w->operand_bf16 == 1 || w->operand_bf16 >= 3))
+    if (training && (w->operand_bf16 == MODE_BF16 || mode_images(w->operand_bf16)))
         return fail(PAFUSE_E_ARG, "training runs fp32 ('f32') or split-precision ('bf16x3') products");
-    if (w->operand_bf16 >= 2 && !training)
+    if (mode_split(w->operand_bf16) && !training)
         for (int i = 0; i < w->depth; ++i)
             for (const pafuse_block_weights* b : {&w->ste[i], &w->tte[i]})
-                if ((!b->qkv_ws && w->operand_bf16 != 4) || !b->proj_ws || !b->fc1_ws || !b->fc2_ws)   // (mode 4 multiplies qkv_hs only)
+                if ((!b->qkv_ws && w->operand_bf16 != MODE_BF16X3_IMAGES) || !b->proj_ws || !b->fc1_ws || !b->fc2_ws)   // (mode 4 multiplies qkv_hs only)
                     return fail(PAFUSE_E_ARG, "split-precision mode needs the pre-split image of every linear weight "
                                               "(pafuse_split_weights)");
     // a folded LayerNorm (pafuse_block_weights.qkv_lt, fc1_lt) is a property of the whole denoiser: the producer of a block's
@@ -777,7 +735,7 @@ int check_weights(const pafuse_mixste2_weights* w, bool training = false) {
             const int set = (b->qkv_lt != nullptr) + (b->fc1_lt != nullptr);
             if (set != (fold ? 2 : 0)) return fail(PAFUSE_E_ARG, "folded-LayerNorm vectors (qkv_lt, fc1_lt) must be set in every block or in none");
         }
-    if (fold && w->operand_bf16 < 2) return fail(PAFUSE_E_ARG, "the folded LayerNorm exists in the split-precision modes only");
+    if (fold && !mode_split(w->operand_bf16)) return fail(PAFUSE_E_ARG, "the folded LayerNorm exists in the split-precision modes only");
     return PAFUSE_OK;
 }
 
@@ -805,21 +763,21 @@ struct BlockLaunch {
 
 BlockLaunch make_block(const pafuse_block_weights& bw, const PartBuffers& pb, int64_t M, int C, int heads, int64_t nseq, int L,
                        int64_t group, int64_t group_stride, int64_t seq_stride, int64_t tok_stride, const BlockTail& tail,
-                       int bf16, int hidden = 0, float qk_scale = 0.f, bool fold = false, bool keep_f32_residual = false) {
+                       int mode, int hidden = 0, float qk_scale = 0.f, bool fold = false, bool keep_f32_residual = false) {
     if (hidden <= 0) hidden = 2 * C;  // mlp_ratio = 2, the PAFUSE configuration
     BlockLaunch b{};
     // fold: the LayerNorm in front of qkv / fc1 is applied inside those GEMMs (GemmParams::ln_in); the producer of a row
     // leaves its (mean, rstd) in the part's stats buffer
     float* const stats = pb.stats;
-    // f16x2 (bf16 == 3): every GEMM operand is an H image - xn (of x with the fold, else of LN(x)), o, and the MLP hidden in
+    // f16x2: every GEMM operand is an H image - xn (of x with the fold, else of LN(x)), o, and the MLP hidden in
     // `wide` are written in that form by their producers (hgemm.hpp); the *_ws pointers are the weights' H images
-    const bool hp = bf16 >= 3;   // (mode 4, bf16x3 on images: the same flow on X images - 6 bytes per element, exact)
+    const bool hp = mode_images(mode);   // (mode 4, bf16x3 on images: the same flow on X images - 6 bytes per element, exact)
     uint8_t* const xn_h = reinterpret_cast<uint8_t*>(pb.xn);
     const bool h_residual = hp && fold && !keep_f32_residual;
     // qkv = LN1(x) Wqkv^T + b        (xn already holds LN1(x))                         mixste.py:65
     GemmParams& g = b.qkv;
     g.A = pb.xn, g.W = bw.qkv_w, g.bias = bw.qkv_b, g.out = pb.wide, g.M = M, g.N = 3 * C, g.K = C, g.act = 0;
-    g.bf16 = bf16, g.Wsplit = (const uint8_t*)bw.qkv_ws, g.wlayout = 2;   // qkv images are in the M16 layout (include/pafuse_hip.h)
+    g.mode = mode, g.Wsplit = (const uint8_t*)bw.qkv_ws, g.wlayout = WLAYOUT_M16;   // qkv images are in the M16 layout (include/pafuse_hip.h)
     if (fold) g.A = pb.x, g.ln_in = stats, g.bias = bw.qkv_lt;
     if (hp) g.Ah = xn_h, g.Wh = (const uint8_t*)bw.qkv_ws;
     if (fold) g.ln_s = nullptr;   // x (its image; mode 2: its fp32 rows) is stored centred on the row mean: rstd acc + lt, no mean term
@@ -830,8 +788,8 @@ BlockLaunch make_block(const pafuse_block_weights& bw, const PartBuffers& pb, in
     if (hp) a.o_h = reinterpret_cast<uint8_t*>(pb.o);
     // the two in one kernel where a head-major image was supplied and the shape has a fused form
     b.fused = false;
-    if (bf16 >= 2 && bw.qkv_hs && bw.qkv_hb && (bf16 == 4 ? xfqa_has(L, C / heads, heads) : fqa_has(L, C / heads, bf16))) {   // (qkv_hl, round 3's uncentred term, is not read: not required)
-        const int lp = fqa_lp(L, bf16), dp = fqa_dp(C / heads);
+    if (mode_split(mode) && bw.qkv_hs && bw.qkv_hb && (mode == MODE_BF16X3_IMAGES ? xfqa_has(L, C / heads, heads) : fqa_has(L, C / heads, mode))) {   // (qkv_hl, round 3's uncentred term, is not read: not required)
+        const int lp = fqa_lp(L, mode), dp = fqa_dp(C / heads);
         FqaParams& f = b.fqa;
         f.g = g;
         f.g.Wsplit = (const uint8_t*)bw.qkv_hs, f.g.bias = bw.qkv_hb, f.g.ln_s = nullptr;
@@ -848,7 +806,7 @@ BlockLaunch make_block(const pafuse_block_weights& bw, const PartBuffers& pb, in
     pj.A = pb.o, pj.W = bw.proj_w, pj.bias = bw.proj_b, pj.M = M, pj.N = C, pj.K = C;
     pj.resid = pb.x, pj.out_x = pb.x, pj.out_n = pb.xn;
     pj.next_w = bw.norm2_w, pj.next_b = bw.norm2_b, pj.next_eps = 1e-6f;
-    pj.bf16 = bf16, pj.Wsplit = (const uint8_t*)bw.proj_ws;
+    pj.mode = mode, pj.Wsplit = (const uint8_t*)bw.proj_ws;
     if (fold) pj.out_n = nullptr, pj.ln_stats = stats;
     if (hp) {
         pj.Ah = reinterpret_cast<const uint8_t*>(pb.o), pj.Wh = (const uint8_t*)bw.proj_ws;
@@ -861,7 +819,7 @@ BlockLaunch make_block(const pafuse_block_weights& bw, const PartBuffers& pb, in
     // h = GELU(xn W1^T + b1)                                                            mixste.py:38-39
     GemmParams& f1 = b.fc1;
     f1.A = pb.xn, f1.W = bw.fc1_w, f1.bias = bw.fc1_b, f1.out = pb.wide, f1.M = M, f1.N = hidden, f1.K = C, f1.act = 1;
-    f1.bf16 = bf16, f1.Wsplit = (const uint8_t*)bw.fc1_ws, f1.wlayout = 2;   // (round 6: fc1 images are in the M16 layout too)
+    f1.mode = mode, f1.Wsplit = (const uint8_t*)bw.fc1_ws, f1.wlayout = WLAYOUT_M16;   // (round 6: fc1 images are in the M16 layout too)
     if (fold) f1.A = pb.x, f1.ln_in = stats, f1.bias = bw.fc1_lt;
     if (hp) f1.Ah = xn_h, f1.Wh = (const uint8_t*)bw.fc1_ws, f1.out_h = reinterpret_cast<uint8_t*>(pb.wide);
     if (fold) f1.ln_s = nullptr;
@@ -875,7 +833,7 @@ BlockLaunch make_block(const pafuse_block_weights& bw, const PartBuffers& pb, in
     f2.head_w = tail.head_w, f2.head_b = tail.head_b, f2.out_head = tail.out_head;
     if (!tail.next_w) f2.out_n = nullptr;
     if (fold && tail.next_w && !tail.out_head) f2.out_n = nullptr, f2.ln_stats = stats;   // the head keeps its own LayerNorm
-    f2.bf16 = bf16, f2.Wsplit = (const uint8_t*)bw.fc2_ws;
+    f2.mode = mode, f2.Wsplit = (const uint8_t*)bw.fc2_ws;
     if (hp) {
         f2.Ah = reinterpret_cast<const uint8_t*>(pb.wide), f2.Wh = (const uint8_t*)bw.fc2_ws;
         if (f2.ln_stats) f2.out_xh = xn_h;                       // folded: the next block's qkv reads the H image of x
@@ -888,7 +846,7 @@ BlockLaunch make_block(const pafuse_block_weights& bw, const PartBuffers& pb, in
     // the two MLP launches as one kernel: the hidden activations stay in registers (hgemm.hpp hmlp_kernel); fc2_hp is the H
     // image of fc2.weight with the columns of each group of 16 in the order the kernel's accumulators hand them over
     b.mlp_fused = false;
-    if (h_residual && bf16 == 3 && bw.fc2_hp && hmlp_has(C, hidden)) {
+    if (h_residual && mode == MODE_F16X2 && bw.fc2_hp && hmlp_has(C, hidden)) {
         MlpParams& m = b.mlp;
         m.g = f2;
         m.g.Ah = xn_h, m.g.Wh = (const uint8_t*)bw.fc2_hp;
@@ -966,7 +924,7 @@ int run_blocks(const BlockLaunch* bl, int n, hipStream_t s, bool gemms_only = fa
             PAFUSE_TRACE(bl[i].attn.o, (size_t)g[i].M * bl[i].attn.C * 4, s);
             continue;
         }
-        if (g[i].bf16 == 4) return fail(PAFUSE_E_SHAPE, "bf16x3 on images: this block has no fused qkv + attention form");
+        if (g[i].mode == MODE_BF16X3_IMAGES) return fail(PAFUSE_E_SHAPE, "bf16x3 on images: this block has no fused qkv + attention form");
         if ((layer_mask & 1) && (rc = gemm_bias(g[i], s))) return rc;
         PAFUSE_TRACE(g[i].out, (size_t)g[i].M * g[i].N * 4, s);
         if (!gemms_only && (rc = attention(bl[i].attn, s))) return rc;
@@ -995,8 +953,8 @@ int run_blocks(const BlockLaunch* bl, int n, hipStream_t s, bool gemms_only = fa
 
 int run_block(const pafuse_block_weights& bw, const PartBuffers& pb, int64_t M, int C, int heads, int64_t nseq, int L,
               int64_t group, int64_t group_stride, int64_t seq_stride, int64_t tok_stride, const BlockTail& tail,
-              hipStream_t s, bool gemms_only = false, double* flops = nullptr, int* launches = nullptr, int bf16 = 0) {
-    const BlockLaunch b = make_block(bw, pb, M, C, heads, nseq, L, group, group_stride, seq_stride, tok_stride, tail, bf16);
+              hipStream_t s, bool gemms_only = false, double* flops = nullptr, int* launches = nullptr, int mode = MODE_F32) {
+    const BlockLaunch b = make_block(bw, pb, M, C, heads, nseq, L, group, group_stride, seq_stride, tok_stride, tail, mode);
     return run_blocks(&b, 1, s, gemms_only, flops, launches);
 }
 
@@ -1054,7 +1012,7 @@ int run_mixste_layers(const pafuse_mixste2_weights* w, const PartBuffers& pb, in
 bool parts_groupable(const pafuse_d3dp_config* cfg) {
     if (cfg->part_by_part_launches || cfg->num_parts < 2 || cfg->num_parts > GROUP_MAX) return false;
     for (int i = 0; i < cfg->num_parts; ++i)
-        if (cfg->part[i].operand_bf16 != 2 || cfg->part[i].depth != cfg->part[0].depth) return false;
+        if (cfg->part[i].operand_bf16 != MODE_BF16X3 || cfg->part[i].depth != cfg->part[0].depth) return false;
     return true;
 }
 
@@ -1064,9 +1022,8 @@ int launch_time_embed(const pafuse_mixste2_weights* w, const int64_t* t, int64_t
     const int C = w->channels;
     p.t = t, p.t_scalar = t_scalar, p.freqs = w->freqs;
     p.w1 = w->tm1_w, p.b1 = w->tm1_b, p.w3 = w->tm3_w, p.b3 = w->tm3_b, p.hid = hid_scratch, p.out = out, p.C = C;
-    hipLaunchKernelGGL(time_embed_kernel<0>, dim3((2 * C + 7) / 8, B), dim3(512), (size_t)C * sizeof(float), s, p);
-    hipLaunchKernelGGL(time_embed_kernel<1>, dim3((C + 7) / 8, B), dim3(512), (size_t)2 * C * sizeof(float), s, p);
-    return check_launch("time_embed_kernel");
+    if (int rc = launch<time_embed_kernel<0>>("time_embed_kernel", dim3((2 * C + 7) / 8, B), 512, (size_t)C * sizeof(float), s, p)) return rc;
+    return launch<time_embed_kernel<1>>("time_embed_kernel", dim3((C + 7) / 8, B), 512, (size_t)2 * C * sizeof(float), s, p);
 }
 
 __global__ void copy_kernel(const float* src, float* dst, int64_t n) {
@@ -1108,7 +1065,7 @@ int pafuse_linear(const float* A, const float* W, const float* bias, float* out,
     StreamDevice on_stream_device(stream);
     if (!A || !W || !bias || !out || M < 0) return fail(PAFUSE_E_ARG, "linear: null pointer or negative M");
     GemmParams g{};
-    g.A = A, g.W = W, g.bias = bias, g.out = out, g.M = M, g.N = N, g.K = K, g.act = act & 1, g.bf16 = (act >> 1) & 1;
+    g.A = A, g.W = W, g.bias = bias, g.out = out, g.M = M, g.N = N, g.K = K, g.act = act & 1, g.mode = (act >> 1) & 1;
     return gemm_bias(g, (hipStream_t)stream);
 }
 
@@ -1119,13 +1076,13 @@ size_t pafuse_split_image_bytes(int64_t N, int64_t K, int32_t layout) {
 }
 
 int pafuse_mode_supported(int32_t mode, int32_t C, int32_t hidden, int32_t heads, int32_t joints, int32_t frames) {
-    if (mode < 0 || mode > 4 || heads <= 0 || C <= 0 || C % heads) return 0;
+    if (!mode_valid(mode) || heads <= 0 || C <= 0 || C % heads) return 0;
     if (hidden <= 0) hidden = 2 * C;
     const int d = C / heads;
     if (!width_supported(C) || d % 4 || d > 48 || joints < 1 || joints > 144 || frames < 1 || frames > ATTN_LONG_LP) return 0;
-    if (mode == 3 && frames > 144) return 0;
-    if (mode >= 3 && (!hgemm_width(C) || !hgemm_plain_n(3 * C) || !hgemm_plain_n(hidden) || hidden % 32)) return 0;
-    if (mode == 4 && (!xfqa_has(joints, d, heads) || !xfqa_has(frames, d, heads))) return 0;
+    if (mode == MODE_F16X2 && frames > 144) return 0;
+    if (mode_images(mode) && (!hgemm_width(C) || !hgemm_plain_n(3 * C) || !hgemm_plain_n(hidden) || hidden % 32)) return 0;
+    if (mode == MODE_BF16X3_IMAGES && (!xfqa_has(joints, d, heads) || !xfqa_has(frames, d, heads))) return 0;
     return 1;
 }
 
@@ -1139,8 +1096,8 @@ int pafuse_mixste2_fused_blocks(const pafuse_mixste2_weights* w) {
         const pafuse_block_weights* pair[2] = {&w->ste[i], &w->tte[i]};
         const int len[2] = {w->joints, w->frames};
         for (int k = 0; k < 2; ++k)   // the condition of make_block, plus the tile-capacity check it makes
-            if (w->operand_bf16 >= 2 && pair[k]->qkv_hs && pair[k]->qkv_hb &&
-                (w->operand_bf16 == 4 ? xfqa_has(len[k], d, w->heads) : fqa_has(len[k], d, w->operand_bf16)) &&
+            if (mode_split(w->operand_bf16) && pair[k]->qkv_hs && pair[k]->qkv_hb &&
+                (w->operand_bf16 == MODE_BF16X3_IMAGES ? xfqa_has(len[k], d, w->heads) : fqa_has(len[k], d, w->operand_bf16)) &&
                 true) {   // (no qkv_hl requirement: nothing reads it since the centred fold of round 5)
                 const int lp = fqa_lp(len[k], w->operand_bf16);
                 n += (fqa_nseq_tile(len[k], lp) * len[k] <= fqa_tile_rows(lp)) ? 1 : 0;
@@ -1156,30 +1113,27 @@ int pafuse_split_weights(const float* W, int32_t N, int32_t K, int32_t layout, v
     const int64_t n = (int64_t)N * (K / 8);
     const dim3 grid((unsigned)((n + 255) / 256));
     if (layout & PAFUSE_SPLIT_X) {   // the X image (bf16x3 on the LDS-DMA pipeline): one geometry for every layer, no scaling, no tail
-        hipLaunchKernelGGL(xsplit_weights_kernel, grid, dim3(256), 0, (hipStream_t)stream, W, (uint8_t*)out, N, K);
-        return check_launch("xsplit_weights_kernel");
+        return launch<xsplit_weights_kernel>("xsplit_weights_kernel", grid, 256, 0, (hipStream_t)stream, W, (uint8_t*)out, N, K);
     }
     if (layout & PAFUSE_SPLIT_F16X2) {   // the f16x2 H image (one geometry for every layer): largest |W| first, then the slices
         hipStream_t st = (hipStream_t)stream;
         uint8_t* const tail = (uint8_t*)out + (size_t)N * K * 4;
         if (hipMemsetAsync(tail, 0, HSPLIT_TAIL_BYTES, st) != hipSuccess) return fail(PAFUSE_E_HIP, "split_weights: memset failed");
         const int64_t elems = (int64_t)N * K;
-        hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)std::min<int64_t>((elems + 255) / 256, 1024)), dim3(256), 0, st, W, elems,
-                           reinterpret_cast<uint32_t*>(tail) + 1);
-        hipLaunchKernelGGL(hsplit_weights_kernel, grid, dim3(256), 0, st, W, (uint8_t*)out, N, K);
-        return check_launch("hsplit_weights_kernel");
+        if (int rc = launch<absmax_kernel>("hsplit_weights_kernel", (unsigned)std::min<int64_t>((elems + 255) / 256, 1024), 256, 0, st, W, elems,
+                                           reinterpret_cast<uint32_t*>(tail) + 1))
+            return rc;
+        return launch<hsplit_weights_kernel>("hsplit_weights_kernel", grid, 256, 0, st, W, (uint8_t*)out, N, K);
     }
-    if (layout < 0 || layout > 2) return fail(PAFUSE_E_ARG, "split_weights: layout %d (0 plain, 1 whole-row, 2 qkv; or PAFUSE_SPLIT_F16X2)", layout);
+    if (layout < WLAYOUT_PLAIN || layout > WLAYOUT_M16) return fail(PAFUSE_E_ARG, "split_weights: layout %d (0 plain, 1 whole-row, 2 qkv; or PAFUSE_SPLIT_F16X2)", layout);
 #ifdef PAFUSE_QKV_32X32
-    if (layout == 2) layout = 0;
+    if (layout == WLAYOUT_M16) layout = WLAYOUT_PLAIN;
 #endif
-    if (layout == 2)
-        hipLaunchKernelGGL((split_weights_kernel<32, 1>), grid, dim3(256), 0, (hipStream_t)stream, W, (uint8_t*)out, N, K);
-    else if (wsplit_chunk(N, layout == 1) == 16)
-        hipLaunchKernelGGL(split_weights_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, W, (uint8_t*)out, N, K);
-    else
-        hipLaunchKernelGGL(split_weights_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, W, (uint8_t*)out, N, K);
-    return check_launch("split_weights_kernel");
+    if (layout == WLAYOUT_M16)
+        return launch<split_weights_kernel<32, 1>>("split_weights_kernel", grid, 256, 0, (hipStream_t)stream, W, (uint8_t*)out, N, K);
+    if (wsplit_chunk(N, layout == WLAYOUT_ROWLN) == 16)
+        return launch<split_weights_kernel<16>>("split_weights_kernel", grid, 256, 0, (hipStream_t)stream, W, (uint8_t*)out, N, K);
+    return launch<split_weights_kernel<32>>("split_weights_kernel", grid, 256, 0, (hipStream_t)stream, W, (uint8_t*)out, N, K);
 }
 
 int pafuse_linear_split(const float* A, const void* Wsplit, const float* bias, float* out, int64_t M, int32_t N, int32_t K,
@@ -1188,7 +1142,7 @@ int pafuse_linear_split(const float* A, const void* Wsplit, const float* bias, f
     if (!A || !Wsplit || !bias || !out || M < 0) return fail(PAFUSE_E_ARG, "linear_split: null pointer or negative M");
     GemmParams g{};
     g.A = A, g.Wsplit = (const uint8_t*)Wsplit, g.bias = bias, g.out = out, g.M = M, g.N = N, g.K = K, g.act = act & 1;
-    g.bf16 = 2, g.wlayout = (act & 2) ? 2 : 0;
+    g.mode = MODE_BF16X3, g.wlayout = (act & 2) ? WLAYOUT_M16 : WLAYOUT_PLAIN;
     return gemm_bias(g, (hipStream_t)stream);
 }
 
@@ -1196,10 +1150,10 @@ int pafuse_linear_split(const float* A, const void* Wsplit, const float* bias, f
 static int rowln_params(const pafuse_rowln_args* a, GemmParams& g) {
     if (!a) return fail(PAFUSE_E_ARG, "linear_rowln: null arguments");
     const int mode = a->operand_bf16;
-    if (mode < 0 || mode > 4) return fail(PAFUSE_E_ARG, "linear_rowln: matrix-product mode %d", mode);
+    if (!mode_valid(mode)) return fail(PAFUSE_E_ARG, "linear_rowln: matrix-product mode %d", mode);
     if (a->M < 0) return fail(PAFUSE_E_ARG, "linear_rowln: negative M");
-    if (a->training && mode != 0 && mode != 2) return fail(PAFUSE_E_ARG, "linear_rowln: training runs modes 0 and 2 only, got %d", mode);
-    const bool img = mode >= 3;
+    if (a->training && mode != MODE_F32 && mode != MODE_BF16X3) return fail(PAFUSE_E_ARG, "linear_rowln: training runs modes 0 and 2 only, got %d", mode);
+    const bool img = mode_images(mode);
     if (img ? !hgemm_width(a->N) : !width_supported(a->N))
         return fail(PAFUSE_E_SHAPE, "linear_rowln: no whole-row kernel for width %d in mode %d", a->N, mode);
     if (a->K <= 0 || a->K % BK) return fail(PAFUSE_E_SHAPE, "linear_rowln: K=%d must be a positive multiple of 32", a->K);
@@ -1210,8 +1164,8 @@ static int rowln_params(const pafuse_rowln_args* a, GemmParams& g) {
     } else {
         if (!a->A || !a->resid) return fail(PAFUSE_E_ARG, "linear_rowln: no A or no residual");
         if (a->A_img || a->resid_img || a->out_x_img || a->out_n_img) return fail(PAFUSE_E_ARG, "linear_rowln: images exist in modes 3 and 4 only");
-        if (mode == 2 && !a->Wsplit) return fail(PAFUSE_E_ARG, "linear_rowln: mode 2 needs the layout-1 image of W (Wsplit)");
-        if ((mode != 2 || a->training) && !a->W) return fail(PAFUSE_E_ARG, "linear_rowln: no fp32 weight W");
+        if (mode == MODE_BF16X3 && !a->Wsplit) return fail(PAFUSE_E_ARG, "linear_rowln: mode 2 needs the layout-1 image of W (Wsplit)");
+        if ((mode != MODE_BF16X3 || a->training) && !a->W) return fail(PAFUSE_E_ARG, "linear_rowln: no fp32 weight W");
     }
     if (!a->post_w != !a->post_b) return fail(PAFUSE_E_ARG, "linear_rowln: post_w and post_b go together");
     if (!a->next_w != !a->next_b) return fail(PAFUSE_E_ARG, "linear_rowln: next_w and next_b go together");
@@ -1226,8 +1180,8 @@ static int rowln_params(const pafuse_rowln_args* a, GemmParams& g) {
     if (a->rowscale && (a->rs_J <= 0 || (a->rs_temporal && a->rs_FJ <= 0)))
         return fail(PAFUSE_E_ARG, "linear_rowln: rowscale with rs_J=%d, rs_FJ=%d", a->rs_J, a->rs_FJ);
     g = GemmParams{};
-    g.A = a->A, g.W = a->W, g.bias = a->bias, g.M = a->M, g.N = a->N, g.K = a->K, g.bf16 = mode;
-    g.Wsplit = mode == 2 ? (const uint8_t*)a->Wsplit : nullptr;
+    g.A = a->A, g.W = a->W, g.bias = a->bias, g.M = a->M, g.N = a->N, g.K = a->K, g.mode = mode;
+    g.Wsplit = mode == MODE_BF16X3 ? (const uint8_t*)a->Wsplit : nullptr;
     g.resid = a->resid, g.out_x = a->out_x, g.out_n = a->out_n;
     g.post_w = a->post_w, g.post_b = a->post_b, g.post_eps = a->post_eps;
     g.pos = a->pos, g.posJ = a->posJ, g.posF = a->posF;
@@ -1274,8 +1228,7 @@ int pafuse_hsplit_rows(const float* X, int64_t R, int32_t K, void* out, void* st
     if (R == 0) return PAFUSE_OK;
     const int64_t n = R * (K / 8);
     if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "hsplit_rows: grid out of range");
-    hipLaunchKernelGGL(hsplit_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, (uint8_t*)out, R, K);
-    return check_launch("hsplit_rows_kernel");
+    return launch<hsplit_rows_kernel>("hsplit_rows_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, X, (uint8_t*)out, R, K);
 }
 
 int pafuse_xsplit_rows(const float* X, int64_t R, int32_t K, void* out, void* stream) {
@@ -1285,8 +1238,7 @@ int pafuse_xsplit_rows(const float* X, int64_t R, int32_t K, void* out, void* st
     if (R == 0) return PAFUSE_OK;
     const int64_t n = R * (K / 8);
     if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "xsplit_rows: grid out of range");
-    hipLaunchKernelGGL(xsplit_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, (uint8_t*)out, R, K);
-    return check_launch("xsplit_rows_kernel");
+    return launch<xsplit_rows_kernel>("xsplit_rows_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, X, (uint8_t*)out, R, K);
 }
 
 int pafuse_linear_x(const void* Ax, const void* Wx, const float* bias, float* out, void* out_x, int64_t M, int32_t N, int32_t K,
@@ -1295,7 +1247,7 @@ int pafuse_linear_x(const void* Ax, const void* Wx, const float* bias, float* ou
     if (!Ax || !Wx || !bias || (!out && !out_x) || M < 0) return fail(PAFUSE_E_ARG, "linear_x: null pointer or negative M");
     GemmParams g{};
     g.Ah = (const uint8_t*)Ax, g.Wh = (const uint8_t*)Wx, g.bias = bias, g.out = out, g.out_h = (uint8_t*)out_x;
-    g.M = M, g.N = N, g.K = K, g.act = act & 1, g.bf16 = 4;
+    g.M = M, g.N = N, g.K = K, g.act = act & 1, g.mode = MODE_BF16X3_IMAGES;
     return gemm_bias(g, (hipStream_t)stream);
 }
 
@@ -1305,7 +1257,7 @@ int pafuse_linear_h(const void* Ah, const void* Wh, const float* bias, float* ou
     if (!Ah || !Wh || !bias || (!out && !out_h) || M < 0) return fail(PAFUSE_E_ARG, "linear_h: null pointer or negative M");
     GemmParams g{};
     g.Ah = (const uint8_t*)Ah, g.Wh = (const uint8_t*)Wh, g.bias = bias, g.out = out, g.out_h = (uint8_t*)out_h;
-    g.M = M, g.N = N, g.K = K, g.act = act & 1, g.bf16 = 3;
+    g.M = M, g.N = N, g.K = K, g.act = act & 1, g.mode = MODE_F16X2;
     return gemm_bias(g, (hipStream_t)stream);
 }
 
@@ -1316,14 +1268,14 @@ int pafuse_qkv_attention_image(int32_t scheme, const void* x_img, const float* s
     if (!x_img || !qkv_hs || !qkv_hb || !o_img || M < 0 || nseq < 0 || group <= 0) return fail(PAFUSE_E_ARG, "qkv_attention_image: bad argument");
     if (scheme != PAFUSE_SPLIT_F16X2 && scheme != PAFUSE_SPLIT_X) return fail(PAFUSE_E_ARG, "qkv_attention_image: scheme must be PAFUSE_SPLIT_F16X2 or PAFUSE_SPLIT_X");
     if (heads <= 0 || C <= 0 || C % heads || C % 32) return fail(PAFUSE_E_SHAPE, "qkv_attention_image: C=%d, heads=%d", C, heads);
-    const int mode = scheme == PAFUSE_SPLIT_X ? 4 : 3, d = C / heads;
-    if (L <= 0 || !(mode == 4 ? xfqa_has(L, d, heads) : fqa_has(L, d, 3)))
+    const int mode = scheme == PAFUSE_SPLIT_X ? MODE_BF16X3_IMAGES : MODE_F16X2, d = C / heads;
+    if (L <= 0 || !(mode == MODE_BF16X3_IMAGES ? xfqa_has(L, d, heads) : fqa_has(L, d, MODE_F16X2)))
         return fail(PAFUSE_E_SHAPE, "qkv_attention_image: no fused form for sequences of %d tokens at head dim %d", L, d);
     if (nseq == 0) return PAFUSE_OK;
     const int lp = fqa_lp(L, mode), dp = fqa_dp(d);
     FqaParams f{};
     f.g.Ah = (const uint8_t*)x_img, f.g.Wh = (const uint8_t*)qkv_hs, f.g.bias = qkv_hb, f.g.ln_in = stats;
-    f.g.M = M, f.g.N = heads * 3 * dp, f.g.K = C, f.g.bf16 = mode;
+    f.g.M = M, f.g.N = heads * 3 * dp, f.g.K = C, f.g.mode = mode;
     f.o = (float*)o_img, f.nseq = nseq, f.L = L, f.C = C, f.heads = heads, f.d = d;
     f.nseq_tile = fqa_nseq_tile(L, lp);
     if (f.nseq_tile * L > fqa_tile_rows(lp)) return fail(PAFUSE_E_SHAPE, "qkv_attention_image: %d sequences of %d tokens do not fit a tile", f.nseq_tile, L);
@@ -1340,7 +1292,7 @@ int pafuse_mlp_h(const void* xh, const float* stats_in, const void* W1h, const f
     MlpParams m{};
     m.g.Ah = (const uint8_t*)xh, m.g.Wh = (const uint8_t*)W2hp, m.g.bias = bias2, m.g.resid_h = (const uint8_t*)xh;
     m.g.out_xh = (uint8_t*)out_xh, m.g.ln_stats = stats_out, m.g.next_w = bias2, m.g.next_b = bias2, m.g.next_eps = eps;   // (folded: next_* only say "a LayerNorm follows")
-    m.g.M = M, m.g.N = C, m.g.K = 2 * C, m.g.bf16 = 3;
+    m.g.M = M, m.g.N = C, m.g.K = 2 * C, m.g.mode = MODE_F16X2;
     m.W1h = (const uint8_t*)W1h, m.bias1 = bias1, m.ln_in = stats_in;
     return fused_mlp(m, (hipStream_t)stream);
 }
@@ -1351,9 +1303,7 @@ int pafuse_layernorm(const float* x, const float* w, const float* b, float* out,
     if (!x || !w || !b || !out || M < 0) return fail(PAFUSE_E_ARG, "layernorm: null pointer or negative M");
     if (C <= 0 || C > 64 * LN_MAX_PER_LANE) return fail(PAFUSE_E_SHAPE, "layernorm: C=%d out of range", C);
     if (M == 0) return PAFUSE_OK;
-    hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, w, b, out,
-                       M, C, eps);
-    return check_launch("layernorm_kernel");
+    return launch<layernorm_kernel>("layernorm_kernel", (unsigned)((M + 3) / 4), 256, 0, (hipStream_t)stream, x, w, b, out, M, C, eps);
 }
 
 int pafuse_attention(const float* qkv, float* o, int64_t nseq, int32_t L, int32_t C, int32_t heads, int64_t group,
@@ -1374,12 +1324,12 @@ int pafuse_block_forward(const pafuse_block_weights* w, float* x, int64_t S, int
                          int32_t operand_bf16, void* workspace, size_t workspace_bytes, void* stream) {
     StreamDevice on_stream_device(stream);
     if (!w || !x || !workspace || S < 0) return fail(PAFUSE_E_ARG, "block_forward: bad argument");
-    if (operand_bf16 < 0 || operand_bf16 > 4) return fail(PAFUSE_E_ARG, "block_forward: matrix-product mode %d", operand_bf16);
-    if (operand_bf16 >= 3 && !hgemm_width(C)) return fail(PAFUSE_E_SHAPE, "block_forward: the image pipelines serve the widths 224 / 256 / 384");
-    if (operand_bf16 == 4 && (heads <= 0 || C % heads || !w->qkv_hs || !w->qkv_hb || !xfqa_has(L, C / heads, heads)))
+    if (!mode_valid(operand_bf16)) return fail(PAFUSE_E_ARG, "block_forward: matrix-product mode %d", operand_bf16);
+    if (mode_images(operand_bf16) && !hgemm_width(C)) return fail(PAFUSE_E_SHAPE, "block_forward: the image pipelines serve the widths 224 / 256 / 384");
+    if (operand_bf16 == MODE_BF16X3_IMAGES && (heads <= 0 || C % heads || !w->qkv_hs || !w->qkv_hb || !xfqa_has(L, C / heads, heads)))
         return fail(PAFUSE_E_ARG, "block_forward: bf16x3 on images needs the head-major qkv image (qkv_hs, qkv_hb) and a sequence length / head "
                                   "dim with a fused qkv + attention form");
-    if (operand_bf16 >= 2 && ((!w->qkv_ws && operand_bf16 != 4) || !w->proj_ws || !w->fc1_ws || !w->fc2_ws))
+    if (mode_split(operand_bf16) && ((!w->qkv_ws && operand_bf16 != MODE_BF16X3_IMAGES) || !w->proj_ws || !w->fc1_ws || !w->fc2_ws))
         return fail(PAFUSE_E_ARG, "block_forward: split-precision mode needs the pre-split image of every linear weight");
     if (!width_supported(C)) return fail(PAFUSE_E_SHAPE, "channel width %d has no kernel", C);
     if (heads <= 0 || C % heads) return fail(PAFUSE_E_SHAPE, "block_forward: heads %d must divide C %d", heads, C);
@@ -1392,10 +1342,10 @@ int pafuse_block_forward(const pafuse_block_weights* w, float* x, int64_t S, int
     carve_part((char*)workspace, M, C, 1, pb, 6);
     pb.x = x;
     // image pipelines: the qkv GEMM reads the image of LN1(x) - the fp32 rows pass through `wide` (free until qkv writes it)
-    int rc = pafuse_layernorm(x, w->norm1_w, w->norm1_b, operand_bf16 >= 3 ? pb.wide : pb.xn, M, C, 1e-6f, stream);
+    int rc = pafuse_layernorm(x, w->norm1_w, w->norm1_b, mode_images(operand_bf16) ? pb.wide : pb.xn, M, C, 1e-6f, stream);
     if (rc) return rc;
-    if (operand_bf16 == 3 && (rc = pafuse_hsplit_rows(pb.wide, M, C, pb.xn, stream))) return rc;
-    if (operand_bf16 == 4 && (rc = pafuse_xsplit_rows(pb.wide, M, C, pb.xn, stream))) return rc;
+    if (operand_bf16 == MODE_F16X2 && (rc = pafuse_hsplit_rows(pb.wide, M, C, pb.xn, stream))) return rc;
+    if (operand_bf16 == MODE_BF16X3_IMAGES && (rc = pafuse_xsplit_rows(pb.wide, M, C, pb.xn, stream))) return rc;
     BlockTail t{};  // plain Block.forward: no post norm, nothing after
     return run_block(*w, pb, M, C, heads, S, L, 1, L, 0, 1, t, s, false, nullptr, nullptr, operand_bf16);
 }
@@ -1435,14 +1385,13 @@ int pafuse_mixste2_forward(const pafuse_mixste2_weights* w, const float* x2d, co
     e.pw = w->patch_w, e.pb = w->patch_b, e.pos = w->pos_spatial, e.temb = pb.temb;
     e.n_w = w->ste[0].norm1_w, e.n_b = w->ste[0].norm1_b, e.n_eps = 1e-6f;
     e.x = pb.x, e.xn = pb.xn, e.stats = ln_folded(w) ? pb.stats : nullptr;
-    e.xh = w->operand_bf16 >= 3 ? reinterpret_cast<uint8_t*>(pb.xn) : nullptr;
-    e.x_image = w->operand_bf16 == 4;
-    e.centre_x = w->operand_bf16 == 2 && ln_folded(w);
+    e.xh = mode_images(w->operand_bf16) ? reinterpret_cast<uint8_t*>(pb.xn) : nullptr;
+    e.x_image = w->operand_bf16 == MODE_BF16X3_IMAGES;
+    e.centre_x = w->operand_bf16 == MODE_BF16X3 && ln_folded(w);
     if (h_residual_only(w)) e.x = nullptr;
     e.B = B, e.P = P, e.F = w->frames, e.J = w->joints, e.J3 = w->joints, e.C = w->channels, e.nflip = 1;
     e.do_clamp = 0, e.scale = 1.f, e.lim = 1.1f, e.row0 = 0, e.nrows = M;
-    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)((M + EMBED_ROWS_PER_BLOCK - 1) / EMBED_ROWS_PER_BLOCK)), dim3(256), 0, s, e);
-    if ((rc = check_launch("embed_kernel"))) return rc;
+    if ((rc = launch<embed_kernel>("embed_kernel", (unsigned)((M + EMBED_ROWS_PER_BLOCK - 1) / EMBED_ROWS_PER_BLOCK), 256, 0, s, e))) return rc;
     PAFUSE_TRACE(pb.temb, (size_t)B * w->channels * 4, s);
     PAFUSE_TRACE(pb.x, (size_t)M * w->channels * 4, s);
     PAFUSE_TRACE(pb.xn, (size_t)M * w->channels * 4, s);
@@ -1450,8 +1399,7 @@ int pafuse_mixste2_forward(const pafuse_mixste2_weights* w, const float* x2d, co
     if (g_snap) (void)hipMemcpyAsync(g_snap, pb.x, (size_t)M * w->channels * 4, hipMemcpyDeviceToDevice, s);
 #endif
     if ((rc = run_mixste_layers(w, pb, R, s, (debug_f32_mask() & 32) != 0))) return rc;
-    hipLaunchKernelGGL(copy_kernel, dim3((unsigned)((M * 3 + 255) / 256)), dim3(256), 0, s, pb.pred, out, M * 3);
-    return check_launch("copy_kernel");
+    return launch<copy_kernel>("copy_kernel", blocks_for(M * 3), 256, 0, s, pb.pred, out, M * 3);
 }
 
 size_t pafuse_d3dp_workspace_bytes(const pafuse_d3dp_config* cfg, int32_t B, int32_t P) {
@@ -1497,7 +1445,7 @@ static bool lanes_allowed(const pafuse_d3dp_config* cfg) {
     return true;
 #else
     for (int i = 0; i < cfg->num_parts; ++i)
-        if (cfg->part[i].operand_bf16 != 0) return false;
+        if (cfg->part[i].operand_bf16 != MODE_F32) return false;
     return true;
 #endif
 }
@@ -1567,11 +1515,9 @@ static int d3dp_sample_impl(const pafuse_d3dp_config* cfg, const pafuse_ddim_ste
     constexpr int MAX_LANES = 64;
     if (lanes > MAX_LANES) return fail(PAFUSE_E_ARG, "too many stream lanes (%d)", lanes);
     if (key4) {
-        hipLaunchKernelGGL(noise_fill_kernel, dim3((unsigned)((img_elems / 3 + 255) / 256)), dim3(256), 0, s0, key4, 0, B, P, F, J, img);
-        if ((rc = check_launch("noise_fill_kernel"))) return rc;
+        if ((rc = launch<noise_fill_kernel>("noise_fill_kernel", blocks_for(img_elems / 3), 256, 0, s0, key4, 0, B, P, F, J, img))) return rc;
     } else {
-        hipLaunchKernelGGL(copy_kernel, dim3((unsigned)((img_elems + 255) / 256)), dim3(256), 0, s0, noise, img, img_elems);
-        if ((rc = check_launch("copy_kernel"))) return rc;
+        if ((rc = launch<copy_kernel>("copy_kernel", blocks_for(img_elems), 256, 0, s0, noise, img, img_elems))) return rc;
     }
     hipEvent_t ev_fork = nullptr, ev_join[MAX_LANES] = {};
     if (multi) {
@@ -1625,15 +1571,13 @@ static int d3dp_sample_impl(const pafuse_d3dp_config* cfg, const pafuse_ddim_ste
             e.n_w = w->ste[0].norm1_w, e.n_b = w->ste[0].norm1_b, e.n_eps = 1e-6f;
             e.x = pb[i].x, e.xn = pb[i].xn;
             e.stats = ln_folded(w) ? pb[i].stats + row0 * 2 : nullptr;   // where offset_rows puts this group's statistics
-            e.xh = w->operand_bf16 >= 3 ? reinterpret_cast<uint8_t*>(pb[i].xn) : nullptr;   // (indexed by the absolute row)
-            e.x_image = w->operand_bf16 == 4;
-            e.centre_x = w->operand_bf16 == 2 && ln_folded(w);
+            e.xh = mode_images(w->operand_bf16) ? reinterpret_cast<uint8_t*>(pb[i].xn) : nullptr;   // (indexed by the absolute row)
+            e.x_image = w->operand_bf16 == MODE_BF16X3_IMAGES;
+            e.centre_x = w->operand_bf16 == MODE_BF16X3 && ln_folded(w);
             if (h_residual_only(w)) e.x = nullptr;
             e.B = B, e.P = P, e.F = F, e.J = w->joints, e.J3 = J, e.C = w->channels, e.nflip = nflip;
             e.do_clamp = 1, e.scale = (float)cfg->scale, e.lim = (float)(1.1 * cfg->scale), e.row0 = row0, e.nrows = nrows;
-            hipLaunchKernelGGL(embed_kernel, dim3((unsigned)((nrows + EMBED_ROWS_PER_BLOCK - 1) / EMBED_ROWS_PER_BLOCK)),
-                               dim3(256), 0, ls, e);
-            if ((rc = check_launch("embed_kernel"))) break;
+            if ((rc = launch<embed_kernel>("embed_kernel", (unsigned)((nrows + EMBED_ROWS_PER_BLOCK - 1) / EMBED_ROWS_PER_BLOCK), 256, 0, ls, e))) break;
             if (!together) rc = run_mixste_layers(w, offset_rows(pb[i], row0, w->channels), r1 - r0, ls);
         }
         if (rc) break;
@@ -1660,9 +1604,8 @@ static int d3dp_sample_impl(const pafuse_d3dp_config* cfg, const pafuse_ddim_ste
         f.an_f = (float)st.sqrt_alpha_next, f.c_f = (float)st.c, f.sigma_f = (float)st.sigma;
         f.range_flag = range_flag;
         const int64_t n = (int64_t)B * P * F * J;
-        if (key4) hipLaunchKernelGGL(finalize_seeded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s0, f);
-        else hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s0, f);
-        rc = check_launch("finalize_kernel");
+        rc = key4 ? launch<finalize_seeded_kernel>("finalize_kernel", blocks_for(n), 256, 0, s0, f)
+                  : launch<finalize_kernel>("finalize_kernel", blocks_for(n), 256, 0, s0, f);
         if (!st.last) ++draw;
     }
     if (multi) {
@@ -1698,8 +1641,7 @@ int pafuse_noise_fill(const uint32_t* key4_dev, int32_t draw, int32_t B, int32_t
     if (draw < 0 || B <= 0 || P <= 0 || F <= 0 || J <= 0) return fail(PAFUSE_E_ARG, "noise_fill: bad size (draw=%d B=%d P=%d F=%d J=%d)", draw, B, P, F, J);
     const int64_t n = (int64_t)B * P * F * J, blocks = (n + 255) / 256;
     if ((int64_t)F * J > 0xffffffffLL || blocks > 0x7fffffff) return fail(PAFUSE_E_ARG, "noise_fill: size out of range");
-    hipLaunchKernelGGL(noise_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, key4_dev, draw, B, P, F, J, out);
-    return check_launch("noise_fill_kernel");
+    return launch<noise_fill_kernel>("noise_fill_kernel", (unsigned)blocks, 256, 0, (hipStream_t)stream, key4_dev, draw, B, P, F, J, out);
 }
 
 int pafuse_d3dp_lanes(const pafuse_d3dp_config* cfg, int32_t B, int32_t P, int32_t n_aux) {
@@ -1736,8 +1678,7 @@ int pafuse_embed(const float* x3d, const float* x2d, const float* x2d_flip, cons
     e.row0 = 0, e.nrows = (int64_t)nflip * B * P * F * J;
     const int64_t blocks = (e.nrows + EMBED_ROWS_PER_BLOCK - 1) / EMBED_ROWS_PER_BLOCK;
     if (blocks > 0x7fffffff) return fail(PAFUSE_E_ARG, "embed: grid out of range");
-    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, e);
-    return check_launch("embed_kernel");
+    return launch<embed_kernel>("embed_kernel", (unsigned)blocks, 256, 0, (hipStream_t)stream, e);
 }
 
 int pafuse_ddim_finalize(const float* const* pred, const int32_t* part_joints, int32_t num_parts, const int32_t* joint_part,
@@ -1765,8 +1706,7 @@ int pafuse_ddim_finalize(const float* const* pred, const int32_t* part_joints, i
     f.scale = (float)scale, f.lim = (float)(1.1 * scale), f.sr = st->sqrt_recip_acp, f.srm1 = st->sqrt_recipm1_acp, f.c = st->c;
     f.an_f = (float)st->sqrt_alpha_next, f.c_f = (float)st->c, f.sigma_f = (float)st->sigma;
     const int64_t n = (int64_t)B * P * F * J;
-    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f);
-    return check_launch("finalize_kernel");
+    return launch<finalize_kernel>("finalize_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, f);
 }
 
 int pafuse_hypothesis_errors(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,
@@ -1782,8 +1722,7 @@ int pafuse_hypothesis_errors(const float* pred, const float* gt, const float* x2
     m.e3 = e3, m.epb = epb, m.jbest = jbest, m.pagg = pagg, m.jagg = jagg, m.paggpb = paggpb;
     m.B = B, m.T = T, m.P = P, m.F = F, m.J = J;
     const int64_t n = (int64_t)B * T * F * J;
-    hipLaunchKernelGGL(metrics_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m);
-    return check_launch("metrics_kernel");
+    return launch<metrics_kernel>("metrics_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, m);
 }
 
 // state of pafuse_hypothesis_partials: double sum[n][3] | float jbest[n], e2[n], sel3[n] | int32 idx[n] | double hsum[P_r][T][1+num_parts]
@@ -1843,13 +1782,11 @@ int pafuse_hypothesis_partials(const float* pred, const float* gt, const float* 
     const int64_t blocks = (int64_t)B * T * m.nblk;
     if (blocks > 0x7fffffff || (int64_t)P_r * T > 0x7fffffff || (int64_t)B * m.nblk > 0x7fffffff)
         return fail(PAFUSE_E_ARG, "hypothesis_partials: grid out of range");
-    hipLaunchKernelGGL(partials_kernel, dim3((unsigned)blocks), dim3(256), 0, s, m);
-    int rc = check_launch("partials_kernel");
+    int rc = launch<partials_kernel>("partials_kernel", (unsigned)blocks, 256, 0, s, m);
     if (rc) return rc;
     PartialsHsumParams r{};
     r.share = m.share, r.hsum = hsum, r.B = B, r.T = T, r.P = P_r, r.nv = m.nv, r.nblk = m.nblk;
-    hipLaunchKernelGGL(partials_hsum_kernel, dim3((unsigned)((int64_t)P_r * T)), dim3(256), 0, s, r);
-    return check_launch("partials_hsum_kernel");
+    return launch<partials_hsum_kernel>("partials_hsum_kernel", (unsigned)((int64_t)P_r * T), 256, 0, s, r);
 }
 
 int pafuse_hypothesis_combine(const void* states, int32_t W, size_t stride_bytes, const float* gt, const int32_t* conn,
@@ -1880,8 +1817,7 @@ int pafuse_hypothesis_combine(const void* states, int32_t W, size_t stride_bytes
     }
     c.jbest = jbest, c.pagg = pagg, c.jagg = jagg, c.paggpb = paggpb;
     c.B = B, c.T = T, c.F = F, c.J = J, c.P = P_total;
-    hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c);
-    return check_launch("combine_kernel");
+    return launch<combine_kernel>("combine_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, c);
 }
 
 // state of pafuse_pose_partials: double sum[n][3] | float e2[n] | int32 idx[n] | float sel[n][3], rounded up to 8 bytes
@@ -1925,8 +1861,7 @@ int pafuse_pose_partials(const float* pred, const float* x2d, const float* traj,
     m.pred = pred, m.x2d = x2d, m.traj = traj, m.cam = cam, m.conn = conn;
     m.sum = sum, m.e2 = e2, m.idx = idx, m.sel = sel;
     m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0;
-    hipLaunchKernelGGL(pose_partials_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m);
-    return check_launch("pose_partials_kernel");
+    return launch<pose_partials_kernel>("pose_partials_kernel", blocks_for(n), 256, 0, s, m);
 }
 
 int pafuse_pose_combine(const void* states, int32_t W, size_t stride_bytes, int32_t B, int32_t T, int32_t F, int32_t J,
@@ -1952,8 +1887,7 @@ int pafuse_pose_combine(const void* states, int32_t W, size_t stride_bytes, int3
         c.m_sum = (double*)st, c.m_e2 = (float*)(st + n * 24), c.m_idx = (int32_t*)(c.m_e2 + n), c.m_sel = (float*)(c.m_idx + n);
     }
     c.mean = mean, c.pick = pick, c.pick_idx = pick_idx, c.n = n, c.P = P_total;
-    hipLaunchKernelGGL(pose_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c);
-    return check_launch("pose_combine_kernel");
+    return launch<pose_combine_kernel>("pose_combine_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, c);
 }
 
 // state of pafuse_spread_partials: double sum[n][3] | double m2[n][6] | double count
@@ -1983,8 +1917,7 @@ int pafuse_spread_partials(const float* pred, const int32_t* conn, int32_t B, in
     m.pred = pred, m.conn = conn;
     m.sum = (double*)state, m.m2 = m.sum + 3 * n, m.count = m.sum + 9 * n;
     m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J;
-    hipLaunchKernelGGL(spread_partials_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m);
-    return check_launch("spread_partials_kernel");
+    return launch<spread_partials_kernel>("spread_partials_kernel", blocks_for(n), 256, 0, s, m);
 }
 
 int pafuse_spread_combine(const void* states, int32_t W, size_t stride_bytes, int32_t B, int32_t T, int32_t F, int32_t J,
@@ -2006,13 +1939,10 @@ int pafuse_spread_combine(const void* states, int32_t W, size_t stride_bytes, in
     SpreadCombineParams c{};
     c.states = lo, c.stride = (int64_t)stride_bytes, c.W = W, c.merged = (double*)merged;
     c.mean = mean, c.cov = cov, c.sd = std_dev, c.n = n;
-    hipLaunchKernelGGL(spread_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c);
-    if (int rc = check_launch("spread_combine_kernel")) return rc;
+    if (int rc = launch<spread_combine_kernel>("spread_combine_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, c)) return rc;
     if (!merged) return PAFUSE_OK;
     // the merged count, behind the kernel whose every thread reads the operands' counts (the merged state may lie over the first)
-    hipLaunchKernelGGL(spread_count_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, lo, (int64_t)stride_bytes, W, n,
-                       (double*)merged);
-    return check_launch("spread_count_kernel");
+    return launch<spread_count_kernel>("spread_count_kernel", 1, 64, 0, (hipStream_t)stream, lo, (int64_t)stride_bytes, W, n, (double*)merged);
 }
 
 int pafuse_procrustes_errors(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,
@@ -2029,8 +1959,7 @@ int pafuse_procrustes_errors(const float* pred, const float* gt, const float* x2
     m.pred = pred, m.gt = gt, m.x2d = x2d, m.traj = traj, m.cam = cam, m.conn = conn;
     m.jbest = jbest, m.pagg = pagg, m.jagg = jagg, m.pbest_sums = pbest_sums, m.pick = pick;
     m.B = B, m.T = T, m.P = P, m.F = F, m.J = J;
-    hipLaunchKernelGGL(procrustes_kernel, dim3((unsigned)n), dim3(64 * P2_WAVES), 0, (hipStream_t)stream, m);
-    return check_launch("procrustes_kernel");
+    return launch<procrustes_kernel>("procrustes_kernel", (unsigned)n, 64 * P2_WAVES, 0, (hipStream_t)stream, m);
 }
 
 // state of pafuse_procrustes_partials: float jbest[n], e2[n], sel[n] | int32 idx[n] | double psum[P_r][T]
@@ -2085,13 +2014,11 @@ int pafuse_procrustes_partials(const float* pred, const float* gt, const float* 
     m.jbest = jbest, m.e2 = jbest + n, m.sel = jbest + 2 * n, m.idx = (int32_t*)(jbest + 3 * n);
     m.pose_sums = (double*)workspace;
     m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0;
-    hipLaunchKernelGGL(procrustes_partials_kernel, dim3((unsigned)blocks), dim3(64 * P2_WAVES), 0, s, m);
-    int rc = check_launch("procrustes_partials_kernel");
+    int rc = launch<procrustes_partials_kernel>("procrustes_partials_kernel", (unsigned)blocks, 64 * P2_WAVES, 0, s, m);
     if (rc) return rc;
     ProcrustesPsumParams r{};
     r.pose_sums = m.pose_sums, r.psum = psum, r.B = B, r.T = T, r.P = P_r, r.F = F;
-    hipLaunchKernelGGL(procrustes_psum_kernel, dim3((unsigned)((int64_t)P_r * T)), dim3(256), 0, s, r);
-    return check_launch("procrustes_psum_kernel");
+    return launch<procrustes_psum_kernel>("procrustes_psum_kernel", (unsigned)((int64_t)P_r * T), 256, 0, s, r);
 }
 
 int pafuse_procrustes_combine(const void* states, int32_t W, size_t stride_bytes, const void* sums, size_t sums_stride_bytes,
@@ -2132,8 +2059,7 @@ int pafuse_procrustes_combine(const void* states, int32_t W, size_t stride_bytes
     }
     c.jbest = jbest, c.pagg = pagg, c.jagg = jagg, c.pick = pick;
     c.B = B, c.T = T, c.F = F, c.J = J, c.P = P_total;
-    hipLaunchKernelGGL(procrustes_combine_kernel, dim3((unsigned)blocks), dim3(64 * P2C_WAVES), 0, (hipStream_t)stream, c);
-    return check_launch("procrustes_combine_kernel");
+    return launch<procrustes_combine_kernel>("procrustes_combine_kernel", (unsigned)blocks, 64 * P2C_WAVES, 0, (hipStream_t)stream, c);
 }
 
 int pafuse_d3dp_replay_gemms(const pafuse_d3dp_config* cfg, int32_t B, int32_t P, void* workspace,
@@ -2194,12 +2120,12 @@ int pafuse_linear_weight_grad(const float* dY, const float* X, float* dW, float*
                               int32_t operand_bf16, void* workspace, size_t workspace_bytes, void* stream) {
     StreamDevice on_stream_device(stream);
     if (!dY || !X || !dW || !workspace || M < 0 || N <= 0 || K <= 0) return fail(PAFUSE_E_ARG, "linear_weight_grad: bad argument");
-    if (operand_bf16 != 0 && operand_bf16 != 2) return fail(PAFUSE_E_ARG, "linear_weight_grad: matrix-product mode %d (0 or 2)", operand_bf16);
+    if (operand_bf16 != MODE_F32 && operand_bf16 != MODE_BF16X3) return fail(PAFUSE_E_ARG, "linear_weight_grad: matrix-product mode %d (0 or 2)", operand_bf16);
     if (N % 4 || K % 4) return fail(PAFUSE_E_SHAPE, "linear_weight_grad: N=%d K=%d must be multiples of 4", N, K);
     if (workspace_bytes < pafuse_linear_weight_grad_bytes()) return fail(PAFUSE_E_WORKSPACE, "workspace too small");
     if (M == 0) return PAFUSE_OK;
     TrainBuffers tb{};
-    tb.split = operand_bf16 == 2;
+    tb.split = operand_bf16 == MODE_BF16X3;
     tb.partial = tb.partial_side = (float*)workspace;
     tb.partial_floats = TRAIN_PARTIAL_FLOATS;
     return weight_grad(dY, X, dW, M, N, K, tb, (hipStream_t)stream, false, db);
@@ -2248,10 +2174,10 @@ int pafuse_linear_input_grad(const float* dY, const float* W, const float* dact_
                              int32_t operand_bf16, int32_t image_source, void* workspace, size_t workspace_bytes, void* stream) {
     StreamDevice on_stream_device(stream);
     if (!dY || !W || !dX || !workspace || M < 0) return fail(PAFUSE_E_ARG, "linear_input_grad: null pointer or negative M");
-    if (operand_bf16 != 0 && operand_bf16 != 2) return fail(PAFUSE_E_ARG, "linear_input_grad: matrix-product mode %d (0 or 2)", operand_bf16);
+    if (operand_bf16 != MODE_F32 && operand_bf16 != MODE_BF16X3) return fail(PAFUSE_E_ARG, "linear_input_grad: matrix-product mode %d (0 or 2)", operand_bf16);
     if (image_source != 0 && image_source != 1) return fail(PAFUSE_E_ARG, "linear_input_grad: image source %d (0 or 1)", image_source);
     if (N <= 0 || K <= 0 || N % 32 || K % 32) return fail(PAFUSE_E_SHAPE, "linear_input_grad: N=%d, K=%d must be positive multiples of 32", N, K);
-    const bool split = operand_bf16 == 2 && plain_splits(M, K, N);
+    const bool split = operand_bf16 == MODE_BF16X3 && plain_splits(M, K, N);
     if (dact_u && !split && K % 64) return fail(PAFUSE_E_SHAPE, "linear_input_grad: dact_u on fp32 products needs K %% 64 == 0, K=%d", K);
     if (!aligned16(dY) || !aligned16(W) || !aligned16(dact_u) || !aligned16(dX) || !aligned16(workspace))
         return fail(PAFUSE_E_ARG, "linear_input_grad: an operand is not 16-byte aligned");
@@ -2259,15 +2185,14 @@ int pafuse_linear_input_grad(const float* dY, const float* W, const float* dact_
     if (M == 0) return PAFUSE_OK;
     TrainBuffers tb;
     carve_unit((char*)workspace, M, N, K, &tb);
-    tb.split = operand_bf16 == 2;
+    tb.split = operand_bf16 == MODE_BF16X3;
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(tb.zeros, 0, (size_t)K * 4, s) != hipSuccess) return fail(PAFUSE_E_HIP, "memset failed");
     const uint8_t* image = nullptr;
     if (split && image_source == 1) {   // the image as the step makes it: one item of the batch kernel (prepare_images)
         SplitBatchParams p{};
         const int blocks = add_split_item(p, 0, W, tb.wimg, N, K, transposed_split_kind(K));
-        hipLaunchKernelGGL(split_weights_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
-        const int rc = check_launch("split_weights_batch_kernel");
+        const int rc = launch<split_weights_batch_kernel>("split_weights_batch_kernel", (unsigned)blocks, 256, 0, s, p);
         if (rc) return rc;
         image = tb.wimg;
     }
@@ -2278,9 +2203,9 @@ int pafuse_linear_train(const float* A, const float* W, const float* bias, float
                         int32_t operand_bf16, void* workspace, size_t workspace_bytes, void* stream) {
     StreamDevice on_stream_device(stream);
     if (!A || !W || !bias || !u || !workspace || M < 0) return fail(PAFUSE_E_ARG, "linear_train: null pointer or negative M");
-    if (operand_bf16 != 0 && operand_bf16 != 2) return fail(PAFUSE_E_ARG, "linear_train: matrix-product mode %d (0 or 2)", operand_bf16);
+    if (operand_bf16 != MODE_F32 && operand_bf16 != MODE_BF16X3) return fail(PAFUSE_E_ARG, "linear_train: matrix-product mode %d (0 or 2)", operand_bf16);
     if (N <= 0 || K <= 0 || N % 32 || K % 32) return fail(PAFUSE_E_SHAPE, "linear_train: N=%d, K=%d must be positive multiples of 32", N, K);
-    const bool split = operand_bf16 == 2 && plain_splits(M, N, K);
+    const bool split = operand_bf16 == MODE_BF16X3 && plain_splits(M, N, K);
     if (h && !split && N % 64) return fail(PAFUSE_E_SHAPE, "linear_train: h on fp32 products needs N %% 64 == 0, N=%d", N);
     if (!aligned16(A) || !aligned16(W) || !aligned16(bias) || !aligned16(u) || !aligned16(h) || !aligned16(workspace))
         return fail(PAFUSE_E_ARG, "linear_train: an operand is not 16-byte aligned");
@@ -2288,7 +2213,7 @@ int pafuse_linear_train(const float* A, const float* W, const float* bias, float
     if (M == 0) return PAFUSE_OK;
     TrainBuffers tb;
     carve_unit((char*)workspace, M, N, K, &tb);
-    tb.split = operand_bf16 == 2;
+    tb.split = operand_bf16 == MODE_BF16X3;
     return plain_linear(A, W, bias, u, M, N, K, (hipStream_t)stream, &tb, h);
 }
 
@@ -2350,9 +2275,7 @@ int pafuse_d3dp_qsample(const float* x0, const float* noise, const int64_t* t, c
     if (!x0 || !noise || !t || !sqrt_alphas_cumprod || !sqrt_one_minus_alphas_cumprod || !out || B <= 0 || per_sample <= 0)
         return fail(PAFUSE_E_ARG, "d3dp_qsample: bad argument");
     const int64_t n = (int64_t)B * per_sample;
-    hipLaunchKernelGGL(qsample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x0, noise, t,
-                       sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, scale, out, per_sample, n);
-    return check_launch("qsample_kernel");
+    return launch<qsample_kernel>("qsample_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, x0, noise, t, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, scale, out, per_sample, n);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // train_host.inc - host side of the training entry points (included by pafuse_hip.hip inside its anonymous namespace,
-// after the inference helpers it reuses: gemm_bias, attention, check_weights, align_up, fail, check_launch).
+// after the inference helpers it reuses: gemm_bias, attention, check_weights, align_up, fail, launch).
 //
 // Train-mode MixSTE2 (common/mixste.py:215-225,260-298) is the inference network at P = 1 plus DropPath on both
 // residual branches of every block; the forward runs the inference kernels (whole-row epilogues in their
@@ -21,7 +21,7 @@ struct TrainBuffers {
     uint8_t *wimg;                     // [18 C*C bytes] split-precision image of a weight outside the blocks (made in front of its GEMM)
     uint8_t *wimg_blocks;              // [2 depth][48 C*C bytes] the images of the blocks' four linear weights, one launch per pass
     const uint8_t* img[2 * PAFUSE_MAX_DEPTH][4];   // qkv, proj, fc1, fc2 of block k in wimg_blocks (null: no image - fp32 products)
-    bool split;                        // operand_bf16 == 2: the plain GEMMs (qkv, fc1, every dX) run bf16x3 products
+    bool split;                        // MODE_BF16X3: the plain GEMMs (qkv, fc1, every dX) run bf16x3 products
     float *zeros;                      // [3C] zero bias of the dX GEMMs
     float *small;                      // [max(B,8) * 2C] tiny results (d temb, d hid, [5][C] sums)
     float *partial, *partial_side;     // two-stage reduction partials (main stream / weight-gradient side stream)
@@ -68,12 +68,10 @@ void carve_train(char* base, const pafuse_mixste2_weights* w, int B, TrainBuffer
     tb.wimg = (uint8_t*)take((18 * C * C + 3) / 4);
     tb.wimg_blocks = (uint8_t*)take((size_t)2 * w->depth * 12 * C * C);
     for (int k = 0; k < 2 * PAFUSE_MAX_DEPTH; ++k) tb.img[k][0] = tb.img[k][1] = tb.img[k][2] = tb.img[k][3] = nullptr;
-    tb.split = w->operand_bf16 == 2;
+    tb.split = w->operand_bf16 == MODE_BF16X3;
     tb.partial = take(TRAIN_PARTIAL_FLOATS), tb.partial_side = take(TRAIN_PARTIAL_FLOATS);
     tb.partial_floats = TRAIN_PARTIAL_FLOATS;
 }
-
-inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // which GEMMs of the training step run split-precision (their weight needs an image)
 inline bool plain_splits(int64_t M, int N, int K) { return M >= 128 && K % 32 == 0 && N % 32 == 0; }
@@ -82,9 +80,9 @@ inline bool plain_splits(int64_t M, int N, int K) { return M >= 128 && K % 32 ==
 // two options: fc1 forward's out_act, fc2-dX's dact_u).  No kernel of the forward / dX GEMMs issues
 // v_mfma_f32_32x32x16_bf16 any more except the whole-row forward tiles.  (-DPAFUSE_TRAIN_PLAIN_LAYOUT0: the old rule, for the A/B.)
 #ifdef PAFUSE_TRAIN_PLAIN_LAYOUT0
-inline int plain_layout(int N, bool qkv_forward) { return (qkv_forward || N % 224 == 0) ? 2 : 0; }
+inline int plain_layout(int N, bool qkv_forward) { return (qkv_forward || N % 224 == 0) ? WLAYOUT_M16 : WLAYOUT_PLAIN; }
 #else
-inline int plain_layout(int, bool) { return 2; }
+inline int plain_layout(int, bool) { return WLAYOUT_M16; }
 #endif
 inline bool rowln_splits(int64_t M, int N, int K) { return M >= 4096 && (N == 384 || N == 256 || N == 224) && K % 32 == 0; }
 
@@ -94,12 +92,11 @@ int rowln_train(GemmParams q, TrainBuffers& tb, hipStream_t s, const uint8_t* im
     if (tb.split && rowln_splits(q.M, q.N, q.K)) {
         if (!image) {
             const int64_t n = (int64_t)q.N * (q.K / 8);
-            hipLaunchKernelGGL((split_weights_kernel<16, 0>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q.W, tb.wimg, q.N, q.K);
-            int rc = check_launch("split_weights_kernel");
+            int rc = launch<split_weights_kernel<16, 0>>("split_weights_kernel", blocks_for(n), 256, 0, s, q.W, tb.wimg, q.N, q.K);
             if (rc) return rc;
             image = tb.wimg;
         }
-        q.bf16 = 2, q.Wsplit = image;
+        q.mode = MODE_BF16X3, q.Wsplit = image;
     }
     return gemm_rowln_train(q, s);
 }
@@ -115,15 +112,12 @@ int plain_linear(const float* A, const float* W, const float* bias, float* out, 
         const int wl = plain_layout(N, qkv_forward);
         if (!image) {
             const int64_t n = (int64_t)N * (K / 8);
-            if (wl == 2)
-                hipLaunchKernelGGL((split_weights_kernel<32, 1>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, tb->wimg, N, K);
-            else
-                hipLaunchKernelGGL((split_weights_kernel<32, 0>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, tb->wimg, N, K);
-            int rc = check_launch("split_weights_kernel");
+            const int rc = wl == WLAYOUT_M16 ? launch<split_weights_kernel<32, 1>>("split_weights_kernel", blocks_for(n), 256, 0, s, W, tb->wimg, N, K)
+                                             : launch<split_weights_kernel<32, 0>>("split_weights_kernel", blocks_for(n), 256, 0, s, W, tb->wimg, N, K);
             if (rc) return rc;
             image = tb->wimg;
         }
-        g.bf16 = 2, g.Wsplit = image, g.wlayout = wl;
+        g.mode = MODE_BF16X3, g.Wsplit = image, g.wlayout = wl;
     }
     return gemm_bias(g, s);
 }
@@ -132,12 +126,10 @@ int reduce_into(const float* partial, float* out, int n, int nparts, int64_t str
                 float* out2 = nullptr, int split = -1, float* out3 = nullptr, int split2 = 0) {
     if (split < 0) split = n;
     if (n >= 16384 || nparts < 32)
-        hipLaunchKernelGGL(reduce_partials_kernel<1>, dim3(blocks_for(n, 256)), dim3(256), 0, s, partial, out, out2, split,
-                           n, nparts, stride, accumulate, out3, split2);
-    else
-        hipLaunchKernelGGL(reduce_partials_kernel<16>, dim3(blocks_for(n, 16)), dim3(256), 0, s, partial, out, out2, split,
-                           n, nparts, stride, accumulate, out3, split2);
-    return check_launch("reduce_partials_kernel");
+        return launch<reduce_partials_kernel<1>>("reduce_partials_kernel", blocks_for(n), 256, 0, s, partial, out, out2, split, n, nparts, stride,
+                                                 accumulate, out3, split2);
+    return launch<reduce_partials_kernel<16>>("reduce_partials_kernel", blocks_for(n, 16), 256, 0, s, partial, out, out2, split, n, nparts, stride,
+                                              accumulate, out3, split2);
 }
 
 int bias_grad(const float* dY, float* db, int64_t M, int N, TrainBuffers& tb, hipStream_t s, bool side = false);
@@ -146,12 +138,8 @@ constexpr int TN_BIG_TARGET_WORKGROUPS = 256;  // one large-tile workgroup per C
 
 template <int NB, int KB, int WN, int WK>
 int launch_tn_big(const TnSplitParams& p, int tiles, int splits, hipStream_t s) {
-    auto k = tn_split_big_kernel<NB, KB, WN, WK>;
-    constexpr int lds = 2 * 3072 * (NB + KB);
-    static DeviceOnce once;  // per device, per tile shape
-    if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)tiles, (unsigned)splits), dim3(64 * WN * WK), lds, s, p);
-    return check_launch("tn_split_big_kernel");
+    constexpr int lds = 2 * 3072 * (NB + KB);   // 72 - 96 KB
+    return launch<tn_split_big_kernel<NB, KB, WN, WK>>("tn_split_big_kernel", dim3((unsigned)tiles, (unsigned)splits), 64 * WN * WK, lds, s, p);
 }
 
 // dW[N,K] += dY[M,N]^T X[M,K]; with db given also db[N] += column sums of dY (the bias gradient of the same Linear: with
@@ -192,15 +180,13 @@ int weight_grad(const float* dY, const float* X, float* dW, int64_t M, int N, in
         TnSplitParams p{};
         p.Y = dY, p.X = X, p.partial = partial, p.M = M, p.rows_per_split = rows, p.N = N, p.K = K;
         p.colsum = db ? partial + (size_t)splits * N * K : nullptr;
-        hipLaunchKernelGGL(tn_split_gemm_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, s, p);
-        if ((rc = check_launch("tn_split_gemm_kernel"))) return rc;
+        if ((rc = launch<tn_split_gemm_kernel>("tn_split_gemm_kernel", dim3((unsigned)tiles, (unsigned)splits), 256, 0, s, p))) return rc;
         if ((rc = reduce_into(partial, dW, N * K, splits, (int64_t)N * K, s))) return rc;
         return db ? reduce_into(p.colsum, db, N, splits, N, s) : PAFUSE_OK;
     }
     TnParams p{};
     p.Y = dY, p.X = X, p.partial = partial, p.M = M, p.rows_per_split = rows, p.N = N, p.K = K;
-    hipLaunchKernelGGL(tn_gemm_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, s, p);   // fp32 products
-    if ((rc = check_launch("tn_gemm_kernel"))) return rc;
+    if ((rc = launch<tn_gemm_kernel>("tn_gemm_kernel", dim3((unsigned)tiles, (unsigned)splits), 256, 0, s, p))) return rc;   // fp32 products
     if ((rc = reduce_into(partial, dW, N * K, splits, (int64_t)N * K, s))) return rc;
     return db ? bias_grad(dY, db, M, N, tb, s, side) : PAFUSE_OK;
 }
@@ -211,8 +197,7 @@ int bias_grad(const float* dY, float* db, int64_t M, int N, TrainBuffers& tb, hi
     int chunks = (int)std::min<int64_t>(256, (M + 63) / 64);
     const int64_t rows = (M + chunks - 1) / chunks;
     chunks = (int)((M + rows - 1) / rows);
-    hipLaunchKernelGGL(colsum_kernel, dim3(blocks_for(N, 256), (unsigned)chunks), dim3(256), 0, s, dY, partial, M, N, rows);
-    int rc = check_launch("colsum_kernel");
+    int rc = launch<colsum_kernel>("colsum_kernel", dim3(blocks_for(N), (unsigned)chunks), 256, 0, s, dY, partial, M, N, rows);
     if (rc) return rc;
     return reduce_into(partial, db, N, chunks, N, s);
 }
@@ -228,17 +213,14 @@ int input_grad(const float* dY, const float* W, float* dX, int64_t M, int N, int
         const int wl = plain_layout(K, false);
         if (!image) {
             const int64_t n = (int64_t)K * (N / 8);
-            if (wl == 2)
-                hipLaunchKernelGGL((split_weights_transposed_kernel<32, 1>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, tb.wimg, K, N);
-            else
-                hipLaunchKernelGGL((split_weights_transposed_kernel<32, 0>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, tb.wimg, K, N);
-            if ((rc = check_launch("split_weights_transposed_kernel"))) return rc;
+            rc = wl == WLAYOUT_M16 ? launch<split_weights_transposed_kernel<32, 1>>("split_weights_transposed_kernel", blocks_for(n), 256, 0, s, W, tb.wimg, K, N)
+                                   : launch<split_weights_transposed_kernel<32, 0>>("split_weights_transposed_kernel", blocks_for(n), 256, 0, s, W, tb.wimg, K, N);
+            if (rc) return rc;
             image = tb.wimg;
         }
-        g.bf16 = 2, g.Wsplit = image, g.wlayout = wl;
+        g.mode = MODE_BF16X3, g.Wsplit = image, g.wlayout = wl;
     } else {
-        hipLaunchKernelGGL(transpose_kernel, dim3(blocks_for(K, 32), blocks_for(N, 32)), dim3(256), 0, s, W, tb.wt, N, K);
-        if ((rc = check_launch("transpose_kernel"))) return rc;
+        if ((rc = launch<transpose_kernel>("transpose_kernel", dim3(blocks_for(K, 32), blocks_for(N, 32)), 256, 0, s, W, tb.wt, N, K))) return rc;
     }
     return gemm_bias(g, s);
 }
@@ -258,11 +240,8 @@ int ln_backward(const float* dy, const float* x, const float* w, float eps, cons
     if (C < 1 || C > LN_BACKWARD_MAX_C) return fail(PAFUSE_E_SHAPE, "ln_backward: C=%d outside 1 .. %d", C, LN_BACKWARD_MAX_C);
     const unsigned nb = blocks_for(M, LNB_ROWS_PER_BLOCK);
     if ((size_t)nb * 3 * C > tb.partial_floats) return fail(PAFUSE_E_WORKSPACE, "ln_backward: partial buffer");
-    if (ln_backward_quad(C))   // the PAFUSE widths: half-wave per row, 16-byte accesses
-        hipLaunchKernelGGL(ln_backward_quad_kernel, dim3(nb), dim3(256), 0, s, p);
-    else
-        hipLaunchKernelGGL(ln_backward_kernel, dim3(nb), dim3(256), 0, s, p);
-    int rc = check_launch("ln_backward_kernel");
+    const int rc = ln_backward_quad(C) ? launch<ln_backward_quad_kernel>("ln_backward_kernel", nb, 256, 0, s, p)   // the PAFUSE widths: half-wave per row, 16-byte accesses
+                                       : launch<ln_backward_kernel>("ln_backward_kernel", nb, 256, 0, s, p);
     if (rc) return rc;
     if (dbranch && out_scaled)   // dw, db and the branch's bias gradient in one pass over the partials
         return reduce_into(tb.partial, dw, 3 * C, (int)nb, 3 * (int64_t)C, s, 1, db, C, dbranch, 2 * C);
@@ -270,8 +249,7 @@ int ln_backward(const float* dy, const float* x, const float* w, float eps, cons
 }
 
 int gelu_fwd(const float* u, float* h, int64_t n, hipStream_t s) {
-    hipLaunchKernelGGL(gelu_forward_kernel, dim3(blocks_for(n / 4, 256)), dim3(256), 0, s, u, h, n / 4);
-    return check_launch("gelu_forward_kernel");
+    return launch<gelu_forward_kernel>("gelu_forward_kernel", blocks_for(n / 4), 256, 0, s, u, h, n / 4);
 }
 
 // du[M,N] = dh * gelu'(u) (in place allowed) and db[N] += column sums of du
@@ -279,8 +257,7 @@ int gelu_bwd(const float* u, const float* dh, float* du, float* db, int64_t M, i
     int chunks = (int)std::min<int64_t>(1024, (M + 31) / 32);
     const int64_t rows = (M + chunks - 1) / chunks;
     chunks = (int)((M + rows - 1) / rows);
-    hipLaunchKernelGGL(gelu_backward_kernel, dim3((unsigned)chunks), dim3(256), 0, s, u, dh, du, tb.partial, M, N, rows);
-    int rc = check_launch("gelu_backward_kernel");
+    int rc = launch<gelu_backward_kernel>("gelu_backward_kernel", (unsigned)chunks, 256, 0, s, u, dh, du, tb.partial, M, N, rows);
     if (rc) return rc;
     return reduce_into(tb.partial, db, N, chunks, N, s);
 }
@@ -292,9 +269,7 @@ int group_sum(const float* x, float* out, int mode, int B, int F, int J, int C, 
     int chunks = std::min(32, (count + 15) / 16);
     const int per = (count + chunks - 1) / chunks;
     chunks = (count + per - 1) / per;
-    hipLaunchKernelGGL(group_sum_kernel, dim3((unsigned)G, (unsigned)chunks), dim3(256), 0, s, x, tb.partial, mode, B, F, J, C,
-                       G, per);
-    int rc = check_launch("group_sum_kernel");
+    int rc = launch<group_sum_kernel>("group_sum_kernel", dim3((unsigned)G, (unsigned)chunks), 256, 0, s, x, tb.partial, mode, B, F, J, C, G, per);
     if (rc) return rc;
     return reduce_into(tb.partial, out, G * C, chunks, (int64_t)G * C, s, accumulate);
 }
@@ -305,8 +280,7 @@ int outer_sum(const float* sv, const float* x, float* out, int64_t M, int NI, in
     int chunks = (int)std::min<int64_t>(256, (M + 63) / 64);
     const int64_t rows = (M + chunks - 1) / chunks;
     chunks = (int)((M + rows - 1) / rows);
-    hipLaunchKernelGGL(outer_sum_kernel, dim3((unsigned)chunks), dim3(256), 0, s, sv, x, tb.partial, M, NI, C, rows);
-    int rc = check_launch("outer_sum_kernel");
+    int rc = launch<outer_sum_kernel>("outer_sum_kernel", (unsigned)chunks, 256, 0, s, sv, x, tb.partial, M, NI, C, rows);
     if (rc) return rc;
     return reduce_into(tb.partial, out, NI * C, chunks, (int64_t)NI * C, s, accumulate);
 }
@@ -314,8 +288,7 @@ int outer_sum(const float* sv, const float* x, float* out, int64_t M, int NI, in
 template <int LP, int DP>
 int launch_attn_backward_mfma(const AttnBackwardParams& ab, hipStream_t s) {
     constexpr size_t lds = ((size_t)4 * LP * (DP + 4) + 3 * LP) * sizeof(float);   // <= 47 KB
-    hipLaunchKernelGGL((attn_backward_mfma_kernel<LP, DP>), dim3((unsigned)(ab.nseq * ab.heads)), dim3((LP / 16) * 64), lds, s, ab);
-    return check_launch("attn_backward_mfma_kernel");
+    return launch<attn_backward_mfma_kernel<LP, DP>>("attn_backward_mfma_kernel", (unsigned)(ab.nseq * ab.heads), (LP / 16) * 64, lds, s, ab);
 }
 
 template <int DP>
@@ -324,13 +297,7 @@ int launch_attn_backward_long(const AttnBackwardParams& ab, hipStream_t s) {
     static_assert(lds <= 160 * 1024, "LDS");
     const int64_t grid = ab.nseq * ab.heads;
     if (grid > 0x7fffffff) return fail(PAFUSE_E_ARG, "attention backward grid out of range");
-    auto k = attn_backward_long_kernel<DP, 4>;
-    {
-        static DeviceOnce once;
-        if (once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(1024), lds, s, ab);
-    return check_launch("attn_backward_long_kernel");
+    return launch<attn_backward_long_kernel<DP, 4>>("attn_backward_long_kernel", (unsigned)grid, 1024, lds, s, ab);
 }
 
 // dqkv from qkv and dO: on the fp32 matrix cores for the PAFUSE sequence lengths and head widths (L <= 80, d <= 48, d % 4 == 0),
@@ -354,13 +321,8 @@ int attention_backward(const AttnBackwardParams& ab, hipStream_t s) {
     if (lds > 160 * 1024)
         return fail(PAFUSE_E_SHAPE, "attention backward: L=%d d=%d exceed LDS (sequences of up to %d tokens at head dim <= 48)", ab.L, ab.d,
                     ATTN_BWD_LONG_LP);
-    {
-        static DeviceOnce once;  // per device: a one-process multi-device caller (nn.DataParallel) reaches this on each
-        if (once.first())
-            hipFuncSetAttribute((const void*)attn_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-    hipLaunchKernelGGL(attn_backward_kernel, dim3((unsigned)(ab.nseq * ab.heads)), dim3(256), lds, s, ab);
-    return check_launch("attn_backward_kernel");
+    // (the ceiling is raised to the whole 160 KB once, whatever this launch's L needs)
+    return launch_lds<attn_backward_kernel>("attn_backward_kernel", (unsigned)(ab.nseq * ab.heads), 256, lds, 160 * 1024, s, ab);
 }
 
 struct BlockGeometry {
@@ -387,7 +349,7 @@ BlockGeometry block_geometry(const pafuse_mixste2_weights* w, int k, int64_t R) 
 }
 
 // kind of the batch item that makes the image of W^T [K, N] for a dX GEMM: the dX GEMM's output columns are the weight's K
-inline int transposed_split_kind(int K) { return plain_layout(K, false) == 2 ? 4 : 2; }
+inline int transposed_split_kind(int K) { return plain_layout(K, false) == WLAYOUT_M16 ? 4 : 2; }
 
 // appends weight W [N, K] (as it lies) to a split_weights_batch_kernel launch; returns the launch's workgroup count after it
 int add_split_item(SplitBatchParams& p, int blocks, const float* W, uint8_t* out, int N, int K, int kind) {
@@ -415,14 +377,13 @@ int prepare_images(const pafuse_mixste2_weights* w, int B, bool transposed, Trai
             const bool ok = transposed ? plain_splits(M, K[l], N[l]) : (whole_row ? rowln_splits(M, N[l], K[l]) : plain_splits(M, N[l], K[l]));
             tb.img[k][l] = nullptr;
             if (!ok || p.count == SPLIT_BATCH_MAX) continue;
-            const int kind = transposed ? transposed_split_kind(K[l]) : (whole_row ? 1 : (plain_layout(N[l], l == 0) == 2 ? 3 : 0));
+            const int kind = transposed ? transposed_split_kind(K[l]) : (whole_row ? 1 : (plain_layout(N[l], l == 0) == WLAYOUT_M16 ? 3 : 0));
             blocks = add_split_item(p, blocks, W[l], base + off[l], N[l], K[l], kind);
             tb.img[k][l] = base + off[l];
         }
     }
     if (!p.count) return PAFUSE_OK;
-    hipLaunchKernelGGL(split_weights_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    return check_launch("split_weights_batch_kernel");
+    return launch<split_weights_batch_kernel>("split_weights_batch_kernel", (unsigned)blocks, 256, 0, s, p);
 }
 
 int train_forward(const pafuse_mixste2_weights* w, const float* x2d, const float* x3d, const int64_t* t, int B,
@@ -431,20 +392,17 @@ int train_forward(const pafuse_mixste2_weights* w, const float* x2d, const float
     const int64_t M = (int64_t)B * F * J, smax = (int64_t)B * std::max(F, J);
     int rc;
     // time MLP, unfused so that its intermediates are kept                          mixste.py:179-184,228-230
-    hipLaunchKernelGGL(sinusoid_kernel, dim3(blocks_for((int64_t)B * C / 2, 256)), dim3(256), 0, s, t, w->freqs, tb.sincos, B, C);
-    if ((rc = check_launch("sinusoid_kernel"))) return rc;
+    if ((rc = launch<sinusoid_kernel>("sinusoid_kernel", blocks_for((int64_t)B * C / 2), 256, 0, s, t, w->freqs, tb.sincos, B, C))) return rc;
     if ((rc = plain_linear(tb.sincos, w->tm1_w, w->tm1_b, tb.uh, B, 2 * C, C, s))) return rc;
     if ((rc = gelu_fwd(tb.uh, tb.hid, (int64_t)B * 2 * C, s))) return rc;
     if ((rc = plain_linear(tb.hid, w->tm3_w, w->tm3_b, tb.temb, B, C, 2 * C, s))) return rc;
-    hipLaunchKernelGGL(concat_inputs_kernel, dim3(blocks_for(M, 256)), dim3(256), 0, s, x2d, x3d, tb.in5, M);
-    if ((rc = check_launch("concat_inputs_kernel"))) return rc;
+    if ((rc = launch<concat_inputs_kernel>("concat_inputs_kernel", blocks_for(M), 256, 0, s, x2d, x3d, tb.in5, M))) return rc;
     EmbedParams e{};
     e.x3d = x3d, e.x2d = x2d, e.pw = w->patch_w, e.pb = w->patch_b, e.pos = w->pos_spatial, e.temb = tb.temb;
     e.n_w = w->ste[0].norm1_w, e.n_b = w->ste[0].norm1_b, e.n_eps = 1e-6f;
     e.x = tb.blk[0].x_in, e.xn = tb.blk[0].xn1;
     e.B = B, e.P = 1, e.F = F, e.J = J, e.J3 = J, e.C = C, e.nflip = 1, e.do_clamp = 0, e.scale = 1.f, e.row0 = 0, e.nrows = M;
-    hipLaunchKernelGGL(embed_kernel, dim3(blocks_for(M, EMBED_ROWS_PER_BLOCK)), dim3(256), 0, s, e);
-    if ((rc = check_launch("embed_kernel"))) return rc;
+    if ((rc = launch<embed_kernel>("embed_kernel", blocks_for(M, EMBED_ROWS_PER_BLOCK), 256, 0, s, e))) return rc;
     if ((rc = prepare_images(w, B, false, tb, s))) return rc;
     for (int k = 0; k < nblk; ++k) {
         const BlockGeometry g = block_geometry(w, k, B);
@@ -545,8 +503,7 @@ int train_backward(const pafuse_mixste2_weights* w, const pafuse_mixste2_weights
     // head: out = LN_h(y) Wh^T + bh                                                  mixste.py:208-211,291
     if ((rc = outer_sum(dout, tb.hn, G(gr->head_w), M, 3, C, tb, s, 1))) return rc;
     if ((rc = bias_grad(dout, G(gr->head_b), M, 3, tb, s))) return rc;
-    hipLaunchKernelGGL(head_backward_kernel, dim3(blocks_for(M * C, 256)), dim3(256), 0, s, dout, w->head_w, tb.g2, M, C);
-    if ((rc = check_launch("head_backward_kernel"))) return rc;
+    if ((rc = launch<head_backward_kernel>("head_backward_kernel", blocks_for(M * C), 256, 0, s, dout, w->head_w, tb.g2, M, C))) return rc;
     if ((rc = ln_backward(tb.g2, tb.y_last, w->hnorm_w, 1e-5f, nullptr, tb.g, nullptr, SeqMap{}, nullptr, G(gr->hnorm_w),
                           G(gr->hnorm_b), nullptr, M, C, tb, s)))
         return rc;
@@ -561,8 +518,7 @@ int train_backward(const pafuse_mixste2_weights* w, const pafuse_mixste2_weights
     if (rc) return rc;
     // x0 = in5 Wpatch^T + b + pos_s[j] + temb[b]                                     mixste.py:222-227
     if ((rc = outer_sum(tb.in5, tb.g, tb.small, M, 5, C, tb, s, 0))) return rc;
-    hipLaunchKernelGGL(transpose_small_kernel, dim3(blocks_for(5 * C, 256)), dim3(256), 0, s, tb.small, G(gr->patch_w), 5, C);
-    if ((rc = check_launch("transpose_small_kernel"))) return rc;
+    if ((rc = launch<transpose_small_kernel>("transpose_small_kernel", blocks_for(5 * C), 256, 0, s, tb.small, G(gr->patch_w), 5, C))) return rc;
     if ((rc = bias_grad(tb.g, G(gr->patch_b), M, C, tb, s))) return rc;
     if ((rc = group_sum(tb.g, G(gr->pos_spatial), 0, B, F, J, C, tb, s))) return rc;
     if ((rc = group_sum(tb.g, tb.small, 2, B, F, J, C, tb, s, 0))) return rc;  // d temb [B,C]

@@ -218,7 +218,7 @@ class D3DP(nn.Module):
                 raise _lib.PafuseError("noise_call ran out of its 32 bits: set a new noise_seed")
             self.noise_call += 1
 
-    PRECISIONS = {"f32": 0, "bf16": 1, "bf16x3": 2, "f16x2": 3, "bf16x3_images": 4}
+    PRECISIONS = _lib.PRECISIONS
 
     def denoisers(self):
         """{name: MixSTE2} in the order of the library's part table: the per-part models, or {'all': the single model}."""

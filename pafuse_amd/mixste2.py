@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import MODE_BF16, MODE_BF16X3, MODE_BF16X3_IMAGES, MODE_F16X2, MODE_F32
 
 
 class _AttentionParams(nn.Module):
@@ -104,7 +105,7 @@ class MixSTE2(nn.Module):
         self.split_generation = {}     # device index -> how many times the split images were (re)made (graph caches key on it)
         self._param_names = tuple(n for n, _ in self.named_parameters())
         self.drop_fn = None            # tests: callable(block, branch, nseq, rate) -> DropPath factors [nseq] or None
-        self.operand_bf16 = 0          # matrix-product mode of the linear layers (include/pafuse_hip.h): 0 fp32 MFMA, 2 split precision
+        self.operand_bf16 = MODE_F32   # matrix-product mode of the linear layers (include/pafuse_hip.h): 0 fp32 MFMA, 2 split precision
         #                                "bf16x3" (the D3DP default), 4 the same products on the image pipeline ('bf16x3_images',
         #                                inference; where its kernels do not exist - training, the single-model variant -
         #                                effective_mode() runs mode 2), 3 split precision "f16x2" (inference only), 1 opt-in bf16 operands
@@ -138,7 +139,7 @@ class MixSTE2(nn.Module):
         falls back to the same products on the round-3 kernels (2) where the image pipeline has no kernels - training and
         shapes outside its set (pafuse_mode_supported)."""
         mode = int(self.operand_bf16)
-        if mode == 4 and (training or not _lib.load().pafuse_mode_supported(4, self.embed_dim, self.mlp_hidden, self.num_heads,
+        if mode == MODE_BF16X3_IMAGES and (training or not _lib.load().pafuse_mode_supported(mode, self.embed_dim, self.mlp_hidden, self.num_heads,
                                                                            self.num_joints, self.num_frame)):
             return 2
         return mode
@@ -166,12 +167,12 @@ class MixSTE2(nn.Module):
             w.qk_scale = 0.0 if self.qk_scale is None else self.qk_scale
             self._wcache_by_device[("train", self._freqs.device.index)] = (key, w)
             return w
-        split = mode in (2, 3, 4)
+        split = mode >= MODE_BF16X3
         fold = split and (True if self.fold_layernorm is None else bool(self.fold_layernorm))
         if split:           # the split images are values, not views: an in-place update of a weight must remake them
             key += tuple(get(n)._version for n in self._param_names if n.endswith(SPLIT_SUFFIXES))
         # (mode 4 has no unfused attention: qkv + attention is one kernel in every block)
-        fuse = split and (mode == 4 or (mode == 3 if self.fuse_qkv_attention is None else bool(self.fuse_qkv_attention)))
+        fuse = split and (mode == MODE_BF16X3_IMAGES or (mode == MODE_F16X2 if self.fuse_qkv_attention is None else bool(self.fuse_qkv_attention)))
         if fold or fuse:    # ... and so are the folded / head-major images and vectors: they also hold LayerNorm and bias values
             key += ("fold", fold, fuse) + tuple(get(n)._version for n in self._param_names if n.endswith(FOLD_SUFFIXES))
         dev = self._freqs.device
@@ -191,10 +192,10 @@ class MixSTE2(nn.Module):
         w = _lib.MixSTE2Weights()
         images, event, stream = None, None, None
         if split:
-            fuse_mlp = (mode == 3 and fold and not self.keep_f32_residual and self.mlp_hidden == 2 * self.embed_dim
+            fuse_mlp = (mode == MODE_F16X2 and fold and not self.keep_f32_residual and self.mlp_hidden == 2 * self.embed_dim
                         and self.embed_dim in FUSED_MLP_WIDTHS
                         and (self.embed_dim in FUSED_MLP_DEFAULT_WIDTHS if self.fuse_mlp is None else bool(self.fuse_mlp)))
-            images = self._split_images(get, fold, fuse, f16=(mode == 3), fuse_mlp=fuse_mlp, x=(mode == 4))
+            images = self._split_images(get, fold, fuse, f16=(mode == MODE_F16X2), fuse_mlp=fuse_mlp, x=(mode == MODE_BF16X3_IMAGES))
             stream = torch.cuda.current_stream(dev)
             event = torch.cuda.Event()
             event.record(stream)
@@ -244,7 +245,7 @@ class MixSTE2(nn.Module):
                     or self.attn_drop_rate):
                 raise NotImplementedError("training implements the PAFUSE configuration: qkv_bias=True, qk_scale=None, "
                                           "mlp_ratio=2, no dropout (common/diffusionpose.py:144-147)")
-            if self.operand_bf16 in (1, 3):
+            if self.operand_bf16 in (MODE_BF16, MODE_F16X2):
                 raise NotImplementedError("rounded-bf16 and f16x2 products are inference options; training runs fp32 ('f32') "
                                           "or split-precision ('bf16x3') products")
             return self._forward_train(x_2d, x_3d, t)

@@ -6,6 +6,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._lib import MODE_BF16X3, MODE_BF16X3_IMAGES, MODE_F16X2, PRECISIONS      # (PRECISIONS: as pafuse_amd.D3DP.PRECISIONS)
 from .mixste2 import _ptr, fill_block_struct, split_image
 
 
@@ -152,7 +153,6 @@ def linear_weight_grad(d_y, x, precision="bf16x3", bias=True):
     return dw, db
 
 
-PRECISIONS = {"f32": 0, "bf16": 1, "bf16x3": 2, "f16x2": 3, "bf16x3_images": 4}       # as pafuse_amd.D3DP.PRECISIONS
 
 
 def _out_buf(out, name, shape, dev, zero=False):
@@ -281,16 +281,16 @@ def block_forward(block_params, x, heads=8, precision="f32"):
     fill_block_struct(w, block_params)
     images = []
     mode = PRECISIONS[precision]
-    if mode == 4 and not lib.pafuse_mode_supported(4, Cc, 0, heads, L, L):
+    if mode == MODE_BF16X3_IMAGES and not lib.pafuse_mode_supported(mode, Cc, 0, heads, L, L):
         mode = 2
-    if mode >= 2:
+    if mode >= MODE_BF16X3:
         for field, lin, layout in (("qkv_ws", block_params.attn.qkv, 2), ("proj_ws", block_params.attn.proj, 1),
                                    ("fc1_ws", block_params.mlp.fc1, 2), ("fc2_ws", block_params.mlp.fc2, 1)):
-            if mode == 4 and field == "qkv_ws":
+            if mode == MODE_BF16X3_IMAGES and field == "qkv_ws":
                 continue
-            images.append(split_image(lin.weight, layout, mode == 3, mode == 4))
+            images.append(split_image(lin.weight, layout, mode == MODE_F16X2, mode == MODE_BF16X3_IMAGES))
             setattr(w, field, images[-1].data_ptr())
-    if mode == 4:       # qkv + attention is one kernel there: the head-major image (LayerNorm not folded: Block.forward normalises)
+    if mode == MODE_BF16X3_IMAGES:       # qkv + attention is one kernel there: the head-major image (LayerNorm not folded: Block.forward normalises)
         from .mixste2 import head_major_qkv
         table = {"b.0.attn.qkv.weight": block_params.attn.qkv.weight, "b.0.attn.qkv.bias": block_params.attn.qkv.bias}
         hs, hb, _ = head_major_qkv(table.__getitem__, "b.0.attn.qkv.weight", heads, False, False, True)
@@ -549,7 +549,7 @@ def linear_split(x, weight, bias, act=None, image=None, layout=0, scheme="bf16x3
     return out.view(*x.shape[:-1], N)
 
 
-IMAGE_BYTES = {3: 4, 4: 6}      # bytes per element of an activation image: f16x2 H image, bf16x3 X image
+IMAGE_BYTES = {MODE_F16X2: 4, MODE_BF16X3_IMAGES: 6}      # bytes per element of an activation image: f16x2 H image, bf16x3 X image
 
 
 def rowln_args(x, weight, bias, resid, precision="bf16x3", image=None, post=None, pos=None, next=None, head=None, fold=False,
@@ -574,7 +574,7 @@ def rowln_args(x, weight, bias, resid, precision="bf16x3", image=None, post=None
     N = weight.shape[0]
     _need(tuple(weight.shape) == (N, K) and bias.numel() == N and tuple(resid.shape) == (M, N),
           f"linear_rowln: x [M,K], weight [N,{K}], bias [N], resid [{M},{N}]")
-    _need(not resid_image or mode >= 3, "linear_rowln: resid_image needs an image mode (f16x2, bf16x3_images)")
+    _need(not resid_image or mode >= MODE_F16X2, "linear_rowln: resid_image needs an image mode (f16x2, bf16x3_images)")
     out = dict(out or {})
     a = _lib.RowLNArgs()
     a.M, a.N, a.K, a.operand_bf16, a.training = M, N, K, mode, int(bool(training))
@@ -590,16 +590,16 @@ def rowln_args(x, weight, bias, resid, precision="bf16x3", image=None, post=None
         keep.append(t)
         return t.data_ptr()
 
-    split = (hsplit_rows if mode == 3 else xsplit_rows) if mode >= 3 else None
-    if mode >= 3:
+    split = (hsplit_rows if mode == MODE_F16X2 else xsplit_rows) if mode >= MODE_F16X2 else None
+    if mode >= MODE_F16X2:
         ximg = split(x)
-        wimg = image if image is not None else split_image(weight, 1, mode == 3, mode == 4)
+        wimg = image if image is not None else split_image(weight, 1, mode == MODE_F16X2, mode == MODE_BF16X3_IMAGES)
         keep += [ximg, wimg]
         a.A_img, a.Wsplit = ximg.data_ptr(), wimg.data_ptr()
     else:
         a.A = _ptr(x, "x")
         a.W = _ptr(weight, "weight")
-        if mode == 2:
+        if mode == MODE_BF16X3:
             wimg = image if image is not None else split_image(weight, 1)
             keep.append(wimg)
             a.Wsplit = wimg.data_ptr()
@@ -617,7 +617,7 @@ def rowln_args(x, weight, bias, resid, precision="bf16x3", image=None, post=None
         if in_place:
             out["x"] = resid
         a.out_x = buf("x", (M, N))
-        if mode >= 3:
+        if mode >= MODE_F16X2:
             a.out_x_img = buf("x_img", M * N * eb, torch.uint8)
     if post is not None:
         a.post_w, a.post_b, a.post_eps = _ptr(post[0], "post_w"), _ptr(post[1], "post_b"), float(post[2])
@@ -629,7 +629,7 @@ def rowln_args(x, weight, bias, resid, precision="bf16x3", image=None, post=None
             a.ln_stats = buf("stats", (M, 2))
         else:
             a.out_n = buf("n", (M, N))
-            if mode >= 3:
+            if mode >= MODE_F16X2:
                 a.out_n_img = buf("n_img", M * N * eb, torch.uint8)
     if head is not None:
         a.head_w, a.head_b = _ptr(head[0], "head_w"), _ptr(head[1], "head_b")
@@ -642,7 +642,7 @@ def rowln_args(x, weight, bias, resid, precision="bf16x3", image=None, post=None
     keep += [post, pos, next, head, rowscale]
 
     def finish():
-        join = hjoin_rows if mode == 3 else xjoin_rows
+        join = hjoin_rows if mode == MODE_F16X2 else xjoin_rows
         res = {}
         for name in ("x", "n", "pre"):
             if name in out and out[name] is not None and (name != "x" or not resid_image):

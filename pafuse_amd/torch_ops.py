@@ -30,21 +30,13 @@ from typing import List, Optional
 import torch
 
 from . import _lib
+from ._lib import MODE_BF16X3, MODE_BF16X3_IMAGES, MODE_F16X2, PRECISIONS      # (PRECISIONS: as pafuse_amd.D3DP.PRECISIONS)
+from .ops import _need, _stream
 from .mixste2 import (FOLDED_LINEAR, FUSED_MLP_DEFAULT_WIDTHS, MixSTE2, SPLIT_SUFFIXES, _ptr, fill_weights_struct, folded_linear,
                       fused_mlp_fc2_image, head_major_qkv, image_layout, sinusoid_frequencies, split_image)
 
 BLOCK_KEYS = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
               "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _need(cond, msg):
-    """host-side operand check: a kernel launched on mismatched shapes faults on the device"""
-    if not cond:
-        raise ValueError(msg)
 
 
 @lru_cache(maxsize=None)
@@ -74,7 +66,6 @@ def _freqs(channels, device):
     return _freq_cache[key]
 
 
-PRECISIONS = {"f32": 0, "bf16": 1, "bf16x3": 2, "f16x2": 3, "bf16x3_images": 4}     # as pafuse_amd.D3DP.PRECISIONS
 _image_cache = {}        # (data_ptr, _version, device, layout, shape, scheme) of a linear weight -> (its split image, the weight)
 _IMAGE_CACHE_MAX = 2048  # ~ three models' worth of linear weights; the oldest entries go first
 
@@ -146,7 +137,7 @@ def mixste_struct(weights, frames, joints, depth, heads, precision="f32"):
     """pafuse_mixste2_weights from a flat parameter list; returns (struct, keep-alive)."""
     mode = _mode(precision)
     channels = weights[0].shape[-1]                           # Spatial_pos_embed [1,J,C] comes first
-    if mode == 4 and not _lib.load().pafuse_mode_supported(4, channels, 0, heads, joints, frames):
+    if mode == MODE_BF16X3_IMAGES and not _lib.load().pafuse_mode_supported(mode, channels, 0, heads, joints, frames):
         mode = 2                                              # as MixSTE2.effective_mode: the same products on the round-3 kernels
     names = mixste_param_names(frames, joints, channels, depth, heads)
     if len(weights) != len(names):
@@ -158,9 +149,9 @@ def mixste_struct(weights, frames, joints, depth, heads, precision="f32"):
     fr = _freqs(channels, weights[0].device)
     w = _lib.MixSTE2Weights()
     images = None
-    if mode in (2, 3, 4):
+    if mode >= MODE_BF16X3:
         images = {}
-        f16, x = mode == 3, mode == 4
+        f16, x = mode == MODE_F16X2, mode == MODE_BF16X3_IMAGES
         for n, t in table.items():
             plain = not (x and n.endswith("attn.qkv.weight"))      # mode 4 multiplies the head-major qkv image only
             if n.endswith(tuple(FOLDED_LINEAR)):    # the modules' default in every split mode: LayerNorm folded into qkv / fc1
@@ -169,10 +160,10 @@ def mixste_struct(weights, frames, joints, depth, heads, precision="f32"):
                     del images[n]
             elif n.endswith(SPLIT_SUFFIXES):
                 images[n] = cached_split_image(t, image_layout(n), f16, x)
-            if mode >= 3 and n.endswith("attn.qkv.weight"):     # the modules' default there: qkv + attention in one kernel
+            if mode >= MODE_F16X2 and n.endswith("attn.qkv.weight"):     # the modules' default there: qkv + attention in one kernel
                 stem = n[:-len("weight")]
                 images[stem + "hs"], images[stem + "hb"], images[stem + "hl"] = cached_head_major_qkv(table, n, heads, f16, x)
-            if mode == 3 and n.endswith("mlp.fc2.weight") and channels in FUSED_MLP_DEFAULT_WIDTHS and t.shape[1] == 2 * channels:
+            if mode == MODE_F16X2 and n.endswith("mlp.fc2.weight") and channels in FUSED_MLP_DEFAULT_WIDTHS and t.shape[1] == 2 * channels:
                 images[n[:-len("weight")] + "hp"] = cached_fused_mlp_fc2(t)    # ... and the MLP in one kernel where the modules do
     fill_weights_struct(w, table.__getitem__, fr, frames, joints, channels, depth, heads, 5, mode, images)
     return w, (table, fr, images)
@@ -256,15 +247,15 @@ def block(x: torch.Tensor, weights: List[torch.Tensor], heads: int, precision: s
     for field, t, name in zip(_lib.BLOCK_FIELDS, weights, BLOCK_KEYS):
         setattr(w, field, _ptr(t, name))
     images = []
-    if mode == 4 and not lib.pafuse_mode_supported(4, Cc, 0, heads, L, L):
+    if mode == MODE_BF16X3_IMAGES and not lib.pafuse_mode_supported(mode, Cc, 0, heads, L, L):
         mode = 2
-    if mode in (2, 3, 4):
+    if mode >= MODE_BF16X3:
         for field, idx, layout in (("qkv_ws", 2, 2), ("proj_ws", 4, 1), ("fc1_ws", 8, 2), ("fc2_ws", 10, 1)):
-            if mode == 4 and field == "qkv_ws":
+            if mode == MODE_BF16X3_IMAGES and field == "qkv_ws":
                 continue
-            images.append(cached_split_image(weights[idx], layout, mode == 3, mode == 4))
+            images.append(cached_split_image(weights[idx], layout, mode == MODE_F16X2, mode == MODE_BF16X3_IMAGES))
             setattr(w, field, images[-1].data_ptr())
-    if mode == 4:       # qkv + attention is one kernel there: the head-major image (LayerNorm not folded: Block.forward normalises)
+    if mode == MODE_BF16X3_IMAGES:       # qkv + attention is one kernel there: the head-major image (LayerNorm not folded: Block.forward normalises)
         table = {"b.0.attn.qkv.weight": weights[2], "b.0.attn.qkv.bias": weights[3]}
         hs, hb, _ = head_major_qkv(table.__getitem__, "b.0.attn.qkv.weight", heads, False, False, True)
         images += [hs, hb]

@@ -15,7 +15,7 @@ template <int WM, int WN, int NT, int EPI, int NSTAGE, int MINW = 1, int TR = 0,
 void life(const char* tag, GemmParams p) {
     using T = GemmTile<WM, WN, NT>;
     size_t lds = (size_t)NSTAGE * (MODE == 2 ? T::STAGE_FLOATS_SPLIT : T::STAGE_FLOATS) * 4;
-    p.bf16 = MODE;
+    p.mode = MODE;
     if (MODE == 2) {  // split-precision products: the pre-split image of W
         uint8_t* ws; CK(hipMalloc(&ws, (size_t)p.N * p.K * 6));
         hipLaunchKernelGGL(split_weights_kernel<32>, dim3((unsigned)(((int64_t)p.N * (p.K / 8) + 255) / 256)), dim3(256), 0, 0, p.W, ws, p.N, p.K);
@@ -56,7 +56,7 @@ template <int WM, int WN, int NT, int EPI, int NSTAGE, int MINW, int BKC>
 void life_dma(const char* tag, GemmParams p) {
     using T = DmaTile<WM, WN, NT, BKC>;
     const size_t lds = (size_t)NSTAGE * T::STAGE_BYTES;
-    p.bf16 = 2;
+    p.mode = 2;
     uint8_t* ws; CK(hipMalloc(&ws, (size_t)p.N * p.K * 6));
     hipLaunchKernelGGL(split_weights_kernel<BKC>, dim3((unsigned)(((int64_t)p.N * (p.K / 8) + 255) / 256)), dim3(256), 0, 0, p.W, ws, p.N, p.K);
     p.Wsplit = ws;

@@ -221,7 +221,7 @@ int main() {
             const int N = layer == 0 ? 3 * C : 2 * C;
             images(N, C);
             GemmParams p{};
-            p.Ah = Ah, p.Wh = Wh, p.bias = vec, p.ln_in = stats, p.ln_s = vec + 1500, p.M = pt.M, p.N = N, p.K = C, p.bf16 = 3;
+            p.Ah = Ah, p.Wh = Wh, p.bias = vec, p.ln_in = stats, p.ln_s = vec + 1500, p.M = pt.M, p.N = N, p.K = C, p.mode = 3;
             if (layer == 0) p.out = out; else p.out_h = outh, p.act = 1;
             snprintf(shape, sizeof shape, "%s %s", pt.name, layer == 0 ? "qkv" : "fc1");
             if (C != 224) {
@@ -247,7 +247,7 @@ int main() {
             for (int temporal = 0; temporal < 2; ++temporal) {
                 const int L = temporal ? 27 : J, lp = L <= 32 ? 32 : (L <= 48 ? 48 : 80);
                 FqaParams f{};
-                f.g.Ah = Ah, f.g.Wh = Wh, f.g.bias = vec, f.g.ln_in = stats, f.g.M = pt.M, f.g.N = heads * 3 * dp, f.g.K = C, f.g.bf16 = 3;
+                f.g.Ah = Ah, f.g.Wh = Wh, f.g.bias = vec, f.g.ln_in = stats, f.g.M = pt.M, f.g.N = heads * 3 * dp, f.g.K = C, f.g.mode = 3;
                 f.o = reinterpret_cast<float*>(outh), f.L = L, f.C = C, f.heads = heads, f.d = d;
                 f.nseq = temporal ? 40 * J : 40 * 27;
                 f.nseq_tile = ((lp == 80 ? 160 : 128 + (lp == 48 ? 4 : 0)) - lp) / L + 1;
@@ -271,7 +271,7 @@ int main() {
             MlpParams m{};
             m.g.Ah = xh, m.g.Wh = W2h, m.g.bias = vec, m.g.resid_h = xh, m.g.out_xh = xh, m.g.ln_stats = stats;
             m.g.post_w = vec + 400, m.g.post_b = vec + 800, m.g.post_eps = 1e-6f, m.g.next_w = vec + 1200, m.g.next_b = vec + 1600, m.g.next_eps = 1e-6f;
-            m.g.M = pt.M, m.g.N = C, m.g.K = 2 * C, m.g.bf16 = 3;
+            m.g.M = pt.M, m.g.N = C, m.g.K = 2 * C, m.g.mode = 3;
             m.W1h = Wh, m.bias1 = vec + 2000, m.ln_in = stats;
             if (C == 224) { run_mlp<7, 2>(pt.name, m); }
             if (C == 256) { run_mlp<8, 2>(pt.name, m); }
@@ -286,7 +286,7 @@ int main() {
             GemmParams q{};
             q.Ah = Ah, q.Wh = Wh, q.bias = vec, q.resid_h = xh, q.out_xh = xh, q.ln_stats = stats;   // the production form: H-image residual in place
             q.post_w = layer ? vec + 400 : nullptr, q.post_b = vec + 800, q.post_eps = 1e-6f, q.next_w = vec + 1200, q.next_b = vec + 1600, q.next_eps = 1e-6f;
-            q.M = pt.M, q.N = C, q.K = K, q.bf16 = 3;
+            q.M = pt.M, q.N = C, q.K = K, q.mode = 3;
             snprintf(shape, sizeof shape, "%s %s", pt.name, layer == 0 ? "proj" : "fc2");
             if (C == 384 && getenv("HB_ABLATE")) {   // where the whole-row epilogue's cycles go (results wrong by design)
                 char sh2[96];

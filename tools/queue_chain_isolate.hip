@@ -31,7 +31,7 @@ struct Chain {
 template <int MODE>   // 2: split-precision products (v_mfma_f32_32x32x16_bf16), 0: fp32 matrix cores
 static void launch(const float* A, const float* W, const uint8_t* Ws, const float* b, float* out, int64_t M, int N, int K, hipStream_t s) {
     GemmParams p{};
-    p.A = A, p.W = W, p.Wsplit = Ws, p.bias = b, p.out = out, p.M = M, p.N = N, p.K = K, p.bf16 = MODE;
+    p.A = A, p.W = W, p.Wsplit = Ws, p.bias = b, p.out = out, p.M = M, p.N = N, p.K = K, p.mode = MODE;
     if (MODE == 2) {
         using T = GemmTile<4, 1, 4>;
         hipLaunchKernelGGL((gemm_kernel<4, 1, 4, EPI_BIAS, 1, 2, 0, 2>), dim3((unsigned)((M + 127) / 128 * (N / 128))), dim3(256),

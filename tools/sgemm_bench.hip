@@ -298,7 +298,7 @@ int main() {
                 hipLaunchKernelGGL((split_weights_kernel<16, 0>), dim3((unsigned)(((int64_t)N * (K / 8) + 255) / 256)), dim3(256), 0, 0, W, Wi1, N, K);
                 hipLaunchKernelGGL((split_weights_kernel<32, 1>), dim3((unsigned)(((int64_t)N * (K / 8) + 255) / 256)), dim3(256), 0, 0, W, Wi, N, K);
                 GemmParams p{};
-                p.A = X, p.bias = vec, p.M = pt.M, p.N = N, p.K = K, p.bf16 = 2;
+                p.A = X, p.bias = vec, p.M = pt.M, p.N = N, p.K = K, p.mode = 2;
                 p.next_w = vec, p.next_b = vec, p.next_eps = 1e-6f;
                 if (layer == 1) p.post_w = postv, p.post_b = vec + 512, p.post_eps = 1e-6f;
                 char shape[64];
@@ -324,7 +324,7 @@ int main() {
             const int N = layer == 0 ? 3 * C : 2 * C, K = C;
             hipLaunchKernelGGL((split_weights_kernel<32, 1>), dim3((unsigned)(((int64_t)N * (K / 8) + 255) / 256)), dim3(256), 0, 0, W, Wi, N, K);
             GemmParams p{};
-            p.A = X, p.Wsplit = Wi, p.bias = vec, p.ln_in = stats, p.out = out, p.M = pt.M, p.N = N, p.K = K, p.bf16 = 2, p.wlayout = 2;
+            p.A = X, p.Wsplit = Wi, p.bias = vec, p.ln_in = stats, p.out = out, p.M = pt.M, p.N = N, p.K = K, p.mode = 2, p.wlayout = 2;
             p.act = layer;
             char shape[64];
             snprintf(shape, sizeof shape, "%s %s", pt.name, layer == 0 ? "qkv" : "fc1");

@@ -130,7 +130,7 @@ int main() {
             const int N = 2 * C;
             images(N, C);
             GemmParams p{};
-            p.Ah = Ax, p.Wh = Wx, p.bias = vec, p.ln_in = stats, p.M = pt.M, p.N = N, p.K = C, p.bf16 = 4, p.out_h = outx, p.act = 1;
+            p.Ah = Ax, p.Wh = Wx, p.bias = vec, p.ln_in = stats, p.M = pt.M, p.N = N, p.K = C, p.mode = 4, p.out_h = outx, p.act = 1;
             snprintf(shape, sizeof shape, "%s fc1", pt.name);
             if (C != 224) {
                 run<4, 2, 2, EPI_BIAS, 3, 16, 2>(shape, p);
@@ -163,7 +163,7 @@ int main() {
             for (int temporal = 0; temporal < 2; ++temporal) {
                 const int L = temporal ? 27 : J, lp = L <= 32 ? 32 : (L <= 48 ? 48 : 80);
                 FqaParams f{};
-                f.g.Ah = Ax, f.g.Wh = Wx, f.g.bias = vec, f.g.ln_in = stats, f.g.M = pt.M, f.g.N = heads * 3 * dp, f.g.K = C, f.g.bf16 = 4;
+                f.g.Ah = Ax, f.g.Wh = Wx, f.g.bias = vec, f.g.ln_in = stats, f.g.M = pt.M, f.g.N = heads * 3 * dp, f.g.K = C, f.g.mode = 4;
                 f.o = reinterpret_cast<float*>(outx), f.L = L, f.C = C, f.heads = heads, f.d = d;
                 f.nseq = temporal ? 40 * J : 40 * 27;
                 f.nseq_tile = ((lp == 80 ? 160 : 128 + (lp == 48 ? 4 : 0)) - lp) / L + 1;
@@ -184,7 +184,7 @@ int main() {
             GemmParams q{};
             q.Ah = Ax, q.Wh = Wx, q.bias = vec, q.resid_h = xx, q.out_xh = xx, q.ln_stats = stats;   // the production form: image residual in place
             q.post_w = layer ? vec + 400 : nullptr, q.post_b = vec + 800, q.post_eps = 1e-6f, q.next_w = vec + 1200, q.next_b = vec + 1600, q.next_eps = 1e-6f;
-            q.M = pt.M, q.N = C, q.K = K, q.bf16 = 4;
+            q.M = pt.M, q.N = C, q.K = K, q.mode = 4;
             snprintf(shape, sizeof shape, "%s %s", pt.name, layer == 0 ? "proj" : "fc2");
             if (getenv("XB_ABLATE")) {   // where the whole-row epilogue's cycles go (results wrong by design)
                 char sh2[96];
