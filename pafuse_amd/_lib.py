@@ -174,6 +174,10 @@ SIGNATURES = {
 # matrix-product modes (include/pafuse_hip.h: pafuse_mixste2_weights.operand_bf16) and the precision names they go by: the one table
 MODE_F32, MODE_BF16, MODE_BF16X3, MODE_F16X2, MODE_BF16X3_IMAGES = range(5)
 PRECISIONS = {"f32": MODE_F32, "bf16": MODE_BF16, "bf16x3": MODE_BF16X3, "f16x2": MODE_F16X2, "bf16x3_images": MODE_BF16X3_IMAGES}
+# ... per split mode, the scheme flag pafuse_split_weights adds to the layout (include/pafuse_hip.h PAFUSE_SPLIT_F16X2, PAFUSE_SPLIT_X),
+# and per image mode the bytes per element of an activation image (f16x2 H image, bf16x3 X image)
+SPLIT_FLAG = {MODE_BF16X3: 0, MODE_F16X2: 4, MODE_BF16X3_IMAGES: 8}
+IMAGE_BYTES = {MODE_F16X2: 4, MODE_BF16X3_IMAGES: 6}
 
 _lib = None
 

@@ -15,7 +15,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import MODE_BF16, MODE_BF16X3, MODE_BF16X3_IMAGES, MODE_F16X2, MODE_F32
+from ._lib import MODE_BF16, MODE_BF16X3, MODE_F16X2, MODE_F32
+from .images import (FOLD_SUFFIXES, SPLIT_SUFFIXES, _ptr, effective_mode, fill_block_struct, make_images,  # noqa: F401  (_ptr: imported from here too)
+                     plan_images, resolve_options)
 
 
 class _AttentionParams(nn.Module):
@@ -52,13 +54,6 @@ def sinusoid_frequencies(dim):
     half = dim // 2
     step = math.log(10000) / (half - 1)
     return torch.exp(torch.arange(half) * -step)
-
-
-def _ptr(t, what):
-    if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
-        raise _lib.PafuseError(f"{what}: expected a contiguous fp32 tensor on the HIP device, got "
-                               f"{t.dtype} contiguous={t.is_contiguous()} device={t.device}")
-    return t.data_ptr()
 
 
 class MixSTE2(nn.Module):
@@ -105,10 +100,11 @@ class MixSTE2(nn.Module):
         self.split_generation = {}     # device index -> how many times the split images were (re)made (graph caches key on it)
         self._param_names = tuple(n for n, _ in self.named_parameters())
         self.drop_fn = None            # tests: callable(block, branch, nseq, rate) -> DropPath factors [nseq] or None
-        self.operand_bf16 = MODE_F32   # matrix-product mode of the linear layers (include/pafuse_hip.h): 0 fp32 MFMA, 2 split precision
-        #                                "bf16x3" (the D3DP default), 4 the same products on the image pipeline ('bf16x3_images',
-        #                                inference; where its kernels do not exist - training, the single-model variant -
-        #                                effective_mode() runs mode 2), 3 split precision "f16x2" (inference only), 1 opt-in bf16 operands
+        self.operand_bf16 = MODE_F32   # matrix-product mode of the linear layers (_lib.PRECISIONS, include/pafuse_hip.h): 'f32' fp32 MFMA,
+        #                                'bf16x3' split precision (the D3DP default), 'bf16x3_images' the same products on the image
+        #                                pipeline (inference; where its kernels do not exist - training, the single-model variant -
+        #                                images.effective_mode runs 'bf16x3'), 'f16x2' split precision (inference only), 'bf16' opt-in bf16
+        #                                operands.  Which weight images a mode needs and how they are made: images.py
         self.fold_layernorm = None     # split-precision inference: norm1 / norm2 applied inside the qkv / fc1 GEMMs
         #                                (pafuse_block_weights.qkv_lt ...: g-scaled weight images + a vector per layer) - the producing
         #                                whole-row kernel stores the residual stream CENTRED on its row means and emits (mean, rstd), the
@@ -118,7 +114,7 @@ class MixSTE2(nn.Module):
         self.fuse_qkv_attention = None   # split-precision inference: qkv projection + attention of a block in ONE kernel where the
         #                                sequence length has a fused form (include/pafuse_hip.h pafuse_block_weights.qkv_hs): q, k, v
         #                                never reach memory.  None = on in 'f16x2' (+7 % on the loop), always on in 'bf16x3_images' (its
-        #                                only form), off in 'bf16x3' (mode 2: equal in time)
+        #                                only form), off in 'bf16x3' (equal in time)
         self.fuse_mlp = None           # 'f16x2' with the LayerNorm folded and the residual stream as its image only: fc1 -> GELU -> fc2
         #                                of a block in ONE kernel, the hidden activations [M, 2C] stay in registers (include/pafuse_hip.h
         #                                pafuse_block_weights.fc2_hp).  None = on at the widths where it wins in the loop (224 and 256: the face and
@@ -134,16 +130,6 @@ class MixSTE2(nn.Module):
         self._side_by_device = {}
 
     # ------------------------------------------------------------------------------------------- C structs
-    def effective_mode(self, training=False):
-        """The matrix-product mode the library is handed: the requested one, except that 'bf16x3_images' on the image pipeline (4)
-        falls back to the same products on the round-3 kernels (2) where the image pipeline has no kernels - training and
-        shapes outside its set (pafuse_mode_supported)."""
-        mode = int(self.operand_bf16)
-        if mode == MODE_BF16X3_IMAGES and (training or not _lib.load().pafuse_mode_supported(mode, self.embed_dim, self.mlp_hidden, self.num_heads,
-                                                                           self.num_joints, self.num_frame)):
-            return 2
-        return mode
-
     def weights_struct(self, images=True):
         """pafuse_mixste2_weights pointing at the live parameter storage (cached until a pointer changes).
         images=False (training): no pre-split / folded images - the training entry points split the weight a GEMM is
@@ -153,7 +139,8 @@ class MixSTE2(nn.Module):
             if name.endswith("attn.qkv.bias") and not self.qkv_bias:
                 return self._zero_qkv_bias
             return attrgetter(name)(self)
-        mode = self.effective_mode(training=not images)
+        mode = effective_mode(int(self.operand_bf16), self.embed_dim, self.mlp_hidden, self.num_heads, self.num_joints, self.num_frame,
+                              training=not images)
         key = tuple(get(n).data_ptr() for n in self._param_names) + (self._freqs.data_ptr(), mode, bool(images),
                                                                      bool(self.keep_f32_residual), self.fuse_mlp)
         if not images:
@@ -168,11 +155,10 @@ class MixSTE2(nn.Module):
             self._wcache_by_device[("train", self._freqs.device.index)] = (key, w)
             return w
         split = mode >= MODE_BF16X3
-        fold = split and (True if self.fold_layernorm is None else bool(self.fold_layernorm))
+        fold, fuse, fuse_mlp = resolve_options(mode, self.embed_dim, self.mlp_hidden, self.fold_layernorm, self.fuse_qkv_attention,
+                                               self.fuse_mlp, self.keep_f32_residual)
         if split:           # the split images are values, not views: an in-place update of a weight must remake them
             key += tuple(get(n)._version for n in self._param_names if n.endswith(SPLIT_SUFFIXES))
-        # (mode 4 has no unfused attention: qkv + attention is one kernel in every block)
-        fuse = split and (mode == MODE_BF16X3_IMAGES or (mode == MODE_F16X2 if self.fuse_qkv_attention is None else bool(self.fuse_qkv_attention)))
         if fold or fuse:    # ... and so are the folded / head-major images and vectors: they also hold LayerNorm and bias values
             key += ("fold", fold, fuse) + tuple(get(n)._version for n in self._param_names if n.endswith(FOLD_SUFFIXES))
         dev = self._freqs.device
@@ -192,10 +178,8 @@ class MixSTE2(nn.Module):
         w = _lib.MixSTE2Weights()
         images, event, stream = None, None, None
         if split:
-            fuse_mlp = (mode == MODE_F16X2 and fold and not self.keep_f32_residual and self.mlp_hidden == 2 * self.embed_dim
-                        and self.embed_dim in FUSED_MLP_WIDTHS
-                        and (self.embed_dim in FUSED_MLP_DEFAULT_WIDTHS if self.fuse_mlp is None else bool(self.fuse_mlp)))
-            images = self._split_images(get, fold, fuse, f16=(mode == MODE_F16X2), fuse_mlp=fuse_mlp, x=(mode == MODE_BF16X3_IMAGES))
+            # one uint8 tensor per image, made on the device and kept until a weight changes (the cache key above)
+            images = make_images(plan_images(self._param_names, mode, (fold, fuse, fuse_mlp)), get, mode, self.num_heads)
             stream = torch.cuda.current_stream(dev)
             event = torch.cuda.Event()
             event.record(stream)
@@ -210,28 +194,6 @@ class MixSTE2(nn.Module):
         else:
             self._wcache_by_device[dev.index] = (key, w, images, event, stream)   # (images: keeps the storage the struct points into alive)
         return w
-
-    def _split_images(self, get, fold=False, fuse=False, f16=False, fuse_mlp=False, x=False):
-        """Pre-split images (bf16x3; f16x2 with `f16`; X images - bf16x3 on the image pipeline - with `x`) of every linear weight,
-        made on the device by pafuse_split_weights: one uint8 tensor per weight, kept until a weight changes (the cache key of
-        weights_struct).  `fold`: qkv / fc1 get the image of W (.) g and the two vectors of the folded LayerNorm (norm1 / norm2
-        of their block, include/pafuse_hip.h pafuse_block_weights.qkv_ls): ls = W g, lt = W beta + b, formed in fp64."""
-        images = {}
-        for name in self._param_names:
-            if not name.endswith(SPLIT_SUFFIXES):
-                continue
-            stem = name[:-len("weight")]
-            # mode 4 multiplies the head-major qkv image only (qkv + attention fused in every block): no plain qkv image
-            plain = not (x and name.endswith("attn.qkv.weight"))
-            if fold and name.endswith(tuple(FOLDED_LINEAR)):
-                images[name], images[stem + "ls"], images[stem + "lt"] = folded_linear(get, name, f16, x, image=plain)
-            elif plain:
-                images[name] = split_image(get(name), image_layout(name), f16, x)
-            if fuse and name.endswith("attn.qkv.weight"):
-                images[stem + "hs"], images[stem + "hb"], images[stem + "hl"] = head_major_qkv(get, name, self.num_heads, fold, f16, x)
-            if fuse_mlp and name.endswith("mlp.fc2.weight"):
-                images[stem + "hp"] = fused_mlp_fc2_image(get(name))
-        return images
 
     # ---------------------------------------------------------------------------------------------- forward
     def forward(self, x_2d, x_3d, t):
@@ -369,18 +331,6 @@ class _TrainFunction(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(grads[n] for n in module._param_names)
 
 
-SPLIT_SUFFIXES = ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight")
-# the LayerNorm folded into a linear layer: linear weight suffix -> the norm of the same block in front of it
-FOLDED_LINEAR = {"attn.qkv.weight": "norm1", "mlp.fc1.weight": "norm2"}
-FOLD_SUFFIXES = ("norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias", "attn.qkv.bias", "mlp.fc1.bias")
-BLOCK_FOLD = (("qkv_ls", "attn.qkv.ls"), ("qkv_lt", "attn.qkv.lt"), ("fc1_ls", "mlp.fc1.ls"), ("fc1_lt", "mlp.fc1.lt"),
-              ("qkv_hs", "attn.qkv.hs"), ("qkv_hb", "attn.qkv.hb"), ("qkv_hl", "attn.qkv.hl"), ("fc2_hp", "mlp.fc2.hp"))
-BLOCK_SPLIT = (("qkv_ws", "attn.qkv.weight"), ("proj_ws", "attn.proj.weight"), ("fc1_ws", "mlp.fc1.weight"),
-               ("fc2_ws", "mlp.fc2.weight"))
-BLOCK_PARAMS = (("norm1_w", "norm1.weight"), ("norm1_b", "norm1.bias"), ("qkv_w", "attn.qkv.weight"),
-                ("qkv_b", "attn.qkv.bias"), ("proj_w", "attn.proj.weight"), ("proj_b", "attn.proj.bias"),
-                ("norm2_w", "norm2.weight"), ("norm2_b", "norm2.bias"), ("fc1_w", "mlp.fc1.weight"),
-                ("fc1_b", "mlp.fc1.bias"), ("fc2_w", "mlp.fc2.weight"), ("fc2_b", "mlp.fc2.bias"))
 MODEL_PARAMS = (("patch_w", "Spatial_patch_to_embedding.weight"), ("patch_b", "Spatial_patch_to_embedding.bias"),
                 ("pos_spatial", "Spatial_pos_embed"), ("pos_temporal", "Temporal_pos_embed"),
                 ("tm1_w", "time_mlp.1.weight"), ("tm1_b", "time_mlp.1.bias"), ("tm3_w", "time_mlp.3.weight"),
@@ -390,8 +340,8 @@ MODEL_PARAMS = (("patch_w", "Spatial_patch_to_embedding.weight"), ("patch_b", "S
 
 
 def fill_weights_struct(w, get, freqs, frames, joints, channels, depth, heads, in_chans, operand_bf16=0, split=None):
-    """Fill a pafuse_mixste2_weights from ``get(state-dict key) -> tensor`` (keys as in common/mixste.py); ``split``
-    maps the names of the linear weights to their pre-split images (mode 2 only)."""
+    """Fill a pafuse_mixste2_weights from ``get(state-dict key) -> tensor`` (keys as in common/mixste.py); ``split`` is the
+    image dict of the split modes (images.make_images)."""
     if depth > _lib.MAX_DEPTH:
         raise _lib.PafuseError(f"depth {depth} > {_lib.MAX_DEPTH}")
     w.frames, w.joints, w.channels, w.depth, w.heads, w.in_chans = frames, joints, channels, depth, heads, in_chans
@@ -401,108 +351,4 @@ def fill_weights_struct(w, get, freqs, frames, joints, channels, depth, heads, i
     w.freqs = _ptr(freqs, "freqs")
     for dst, prefix in ((w.ste, "STEblocks"), (w.tte, "TTEblocks")):
         for i in range(depth):
-            for field, key in BLOCK_PARAMS:
-                setattr(dst[i], field, _ptr(get(f"{prefix}.{i}.{key}"), f"{prefix}.{i}.{key}"))
-            for field, key in BLOCK_SPLIT:       # (mode 4 has no plain qkv image: qkv_hs is what it multiplies)
-                img = split.get(f"{prefix}.{i}.{key}") if split is not None else None
-                setattr(dst[i], field, img.data_ptr() if img is not None else None)
-            for field, key in BLOCK_FOLD:       # present only when the images were made with the LayerNorm folded in
-                vec = split.get(f"{prefix}.{i}.{key}") if split is not None else None
-                setattr(dst[i], field, vec.data_ptr() if vec is not None else None)
-
-
-LAYOUT_OF = {"attn.qkv.weight": 2, "attn.proj.weight": 1, "mlp.fc2.weight": 1, "mlp.fc1.weight": 2}     # (round 6: fc1 runs the 16x16x32 kernels, its image is the M16 one like qkv's)
-
-
-def image_layout(name):
-    """pafuse_split_weights' layout argument for a state-dict key of a linear weight (include/pafuse_hip.h)."""
-    return LAYOUT_OF[name.split(".", 2)[2] if name.count(".") >= 3 else name]
-
-
-SPLIT_F16X2 = 4      # include/pafuse_hip.h PAFUSE_SPLIT_F16X2: added to the layout, the image is for the f16x2 scheme
-SPLIT_X = 8          # include/pafuse_hip.h PAFUSE_SPLIT_X: the X image of the bf16x3 image pipeline (mode 4)
-
-
-def split_image(weight, layout, f16=False, x=False):
-    """The pre-split image of one linear weight [N,K] on its device (pafuse_split_weights): a uint8 tensor of 6 bytes per
-    element; `layout`: 0 the plain unit op (pafuse_linear_split without PAFUSE_LINEAR_QKV_IMAGE; no model layer since ABI 6),
-    1 the whole-row layers (attn.proj, mlp.fc2), 2 attn.qkv and - since ABI 6 - mlp.fc1 (mode 2's three
-    geometries; the image pipelines have one each); `f16`: the f16x2 scheme's H image (two fp16 slices of the power-of-two-scaled
-    weight, 4 bytes per element + a 256-byte tail); `x`: the X image of mode 4 (three bf16 slices, [N][K/32][3][32])."""
-    lib = _lib.load()
-    N, K = weight.shape
-    flags = int(layout) | (SPLIT_F16X2 if f16 else 0) | (SPLIT_X if x else 0)
-    img = torch.empty(lib.pafuse_split_image_bytes(N, K, flags), dtype=torch.uint8, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _lib.check(lib.pafuse_split_weights(_ptr(weight.detach(), "weight"), N, K, flags, img.data_ptr(),
-                                            torch.cuda.current_stream(weight.device).cuda_stream))
-    return img
-
-
-FUSED_MLP_WIDTHS = (224, 256, 384)     # channel widths hmlp_kernel is built for (csrc/pafuse_hip.hip fused_mlp)
-FUSED_MLP_DEFAULT_WIDTHS = (224, 256)  # ... and where MixSTE2.fuse_mlp = None turns it on
-
-
-def fused_mlp_column_order(hidden, device=None):
-    """Column order of fc2.weight in the fused MLP kernel's image (include/pafuse_hip.h pafuse_block_weights.fc2_hp): column
-    16 b + 8 h + i of the image is column 16 b + 8 (i >> 2) + 4 h + (i & 3) of the weight - inside every group of 16 hidden
-    units, the order in which fc1's accumulators hold them."""
-    c = torch.arange(hidden, device=device)
-    b, h, i = c // 16, (c // 8) % 2, c % 8
-    return 16 * b + 8 * (i // 4) + 4 * h + (i % 4)
-
-
-def fused_mlp_fc2_image(weight):
-    """The f16x2 image of fc2.weight [C, 2C] for the fused MLP kernel: the image of W[:, fused_mlp_column_order]."""
-    w = weight.detach()
-    return split_image(w[:, fused_mlp_column_order(w.shape[1], w.device)].contiguous(), LAYOUT_OF["mlp.fc2.weight"], True)
-
-
-def folded_linear(get, name, f16=False, x=False, image=True):
-    """(image, ls, lt) of the linear layer `name` (a state-dict key ending in attn.qkv.weight / mlp.fc1.weight) with the
-    LayerNorm in front of it folded in (include/pafuse_hip.h, pafuse_block_weights.qkv_ls): the split image of W (.) g
-    (one fp32 rounding per element, then split exactly), lt = W beta + b formed in fp64, rounded once; ls is None (the
-    centred fold of round 5 has no mean term)."""
-    block, norm = name.rsplit(".", 3)[0], FOLDED_LINEAR[name.split(".", 2)[2]]
-    weight = get(name).detach()
-    g, beta = get(f"{block}.{norm}.weight").detach(), get(f"{block}.{norm}.bias").detach()
-    bias = get(name[:-len("weight")] + "bias").detach()
-    lt = (weight.double() @ beta.double() + bias.double()).float().contiguous()
-    # (ls = W g, the mean term of round 3's uncentred fold, is not read by any kernel since round 5 and no longer formed: None)
-    return (split_image((weight * g[None, :]).contiguous(), image_layout(name), f16, x) if image else None), None, lt
-
-
-def head_major_qkv(get, name, heads, fold, f16=False, x=False):
-    """(image, hb, hl) for the fused qkv + attention kernel (include/pafuse_hip.h pafuse_block_weights.qkv_hs): the qkv weight
-    [3C, C] re-ordered head by head - q_h, k_h, v_h, each zero-padded from d to DP rows (DP = 32 for d <= 32, else 48) - as
-    a layout-2 image; hb = the bias in that order; with the LayerNorm folded the image is that of W (.) g and hb = W beta + b
-    (folded_linear's vector, re-ordered); hl is None (not read by any kernel since the centred fold of round 5)."""
-    weight = get(name).detach()
-    C3, C = weight.shape
-    d = C3 // 3 // heads
-    dp = 32 if d <= 32 else 48
-    stem = name[:-len("weight")]
-    bias = get(stem + "bias").detach()
-    hl = None
-    if fold:
-        block, norm = name.rsplit(".", 3)[0], FOLDED_LINEAR[name.split(".", 2)[2]]
-        g, beta = get(f"{block}.{norm}.weight").detach(), get(f"{block}.{norm}.bias").detach()
-        bias = (weight.double() @ beta.double() + bias.double()).float()     # (hl = W g: not read since round 5, not formed)
-        weight = weight * g[None, :]
-
-    def reorder(t):                     # [3C, ...] -> [heads * 3 * dp, ...]
-        t = t.reshape(3, heads, d, *t.shape[1:])
-        out = t.new_zeros((heads, 3, dp) + tuple(t.shape[3:]))
-        out[:, :, :d] = t.transpose(0, 1)
-        return out.reshape(heads * 3 * dp, *t.shape[3:]).contiguous()
-    image = split_image(reorder(weight), 2, f16, x)
-    return image, reorder(bias), (reorder(hl) if hl is not None else None)
-
-
-def fill_block_struct(dst, blk):
-    dst.norm1_w, dst.norm1_b = _ptr(blk.norm1.weight, "norm1"), _ptr(blk.norm1.bias, "norm1")
-    dst.qkv_w, dst.qkv_b = _ptr(blk.attn.qkv.weight, "qkv"), _ptr(blk.attn.qkv.bias, "qkv")
-    dst.proj_w, dst.proj_b = _ptr(blk.attn.proj.weight, "proj"), _ptr(blk.attn.proj.bias, "proj")
-    dst.norm2_w, dst.norm2_b = _ptr(blk.norm2.weight, "norm2"), _ptr(blk.norm2.bias, "norm2")
-    dst.fc1_w, dst.fc1_b = _ptr(blk.mlp.fc1.weight, "fc1"), _ptr(blk.mlp.fc1.bias, "fc1")
-    dst.fc2_w, dst.fc2_b = _ptr(blk.mlp.fc2.weight, "fc2"), _ptr(blk.mlp.fc2.bias, "fc2")
+            fill_block_struct(dst[i], get, f"{prefix}.{i}.", split)

@@ -2,12 +2,13 @@
 
 Every wrapper checks operand shapes on the host and launches with the operands' device current."""
 import ctypes as C
+from operator import attrgetter
 
 import torch
 
 from . import _lib
-from ._lib import MODE_BF16X3, MODE_BF16X3_IMAGES, MODE_F16X2, PRECISIONS      # (PRECISIONS: as pafuse_amd.D3DP.PRECISIONS)
-from .mixste2 import _ptr, fill_block_struct, split_image
+from ._lib import IMAGE_BYTES, MODE_BF16X3, MODE_F16X2, PRECISIONS, SPLIT_FLAG      # (PRECISIONS: as pafuse_amd.D3DP.PRECISIONS)
+from .images import _ptr, block_images, effective_mode, fill_block_struct, fused_mlp_fc2_image, head_major_qkv, split_image
 
 
 def _stream(t):
@@ -271,31 +272,17 @@ def gelu_backward(u, dh, db=None, in_place=False):
 def block_forward(block_params, x, heads=8, precision="f32"):
     """Block.forward (common/mixste.py:113-116) on [S,L,C]; ``block_params`` is a pafuse_amd.mixste2._BlockParams;
     ``precision`` the matrix-product mode of its four linear layers (the split modes make their weight images here;
-    'bf16x3_images' runs the image pipeline where it has kernels for the shape, else the round-3 kernels)."""
+    'bf16x3_images' runs the image pipeline where it has kernels for the shape, else the 'bf16x3' kernels)."""
     lib = _lib.load()
     S, L, Cc = x.shape
     _need(block_params.norm1.weight.numel() == Cc and Cc % heads == 0, f"block: parameters are not for width {Cc}")
     _need(precision in PRECISIONS, f"precision must be one of {sorted(PRECISIONS)}")
     y = x.contiguous().clone()
     w = _lib.BlockWeights()
-    fill_block_struct(w, block_params)
-    images = []
-    mode = PRECISIONS[precision]
-    if mode == MODE_BF16X3_IMAGES and not lib.pafuse_mode_supported(mode, Cc, 0, heads, L, L):
-        mode = 2
-    if mode >= MODE_BF16X3:
-        for field, lin, layout in (("qkv_ws", block_params.attn.qkv, 2), ("proj_ws", block_params.attn.proj, 1),
-                                   ("fc1_ws", block_params.mlp.fc1, 2), ("fc2_ws", block_params.mlp.fc2, 1)):
-            if mode == MODE_BF16X3_IMAGES and field == "qkv_ws":
-                continue
-            images.append(split_image(lin.weight, layout, mode == MODE_F16X2, mode == MODE_BF16X3_IMAGES))
-            setattr(w, field, images[-1].data_ptr())
-    if mode == MODE_BF16X3_IMAGES:       # qkv + attention is one kernel there: the head-major image (LayerNorm not folded: Block.forward normalises)
-        from .mixste2 import head_major_qkv
-        table = {"b.0.attn.qkv.weight": block_params.attn.qkv.weight, "b.0.attn.qkv.bias": block_params.attn.qkv.bias}
-        hs, hb, _ = head_major_qkv(table.__getitem__, "b.0.attn.qkv.weight", heads, False, False, True)
-        images += [hs, hb]
-        w.qkv_hs, w.qkv_hb = hs.data_ptr(), hb.data_ptr()
+    mode = effective_mode(PRECISIONS[precision], Cc, 0, heads, L, L)
+    get = lambda key: attrgetter(key)(block_params)      # noqa: E731
+    images = block_images(get, mode, heads)
+    fill_block_struct(w, get, images=images, what=lambda key: key.split(".")[-2])
     nbytes = lib.pafuse_block_workspace_bytes(S * L, Cc)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
@@ -437,7 +424,6 @@ def qkv_attention_fused(x, qkv_weight, qkv_bias, heads, nseq, L, scheme="bf16x3_
     a folded LayerNorm) -> o [M,C] fp32 decoded from the image the kernel writes; q | k | v = rstd (x W^T) + b per head, then
     softmax(q k^T d^-1/2) v per (sequence, head).  scheme 'f16x2' (hfqa_kernel, H images) or 'bf16x3_images' (xfqa_kernel, X
     images).  Sequence map as `attention`."""
-    from .mixste2 import head_major_qkv
     lib = _lib.load()
     M, Cw = x.shape
     _need(scheme in ("f16x2", "bf16x3_images"), "qkv_attention_fused: scheme 'f16x2' or 'bf16x3_images'")
@@ -446,17 +432,17 @@ def qkv_attention_fused(x, qkv_weight, qkv_bias, heads, nseq, L, scheme="bf16x3_
     if nseq:   # the last row any sequence touches must exist
         last = ((nseq - 1) // group) * gs + ((nseq - 1) % group) * seq_stride + (L - 1) * tok_stride
         _need(0 <= last < M and min(gs, seq_stride, tok_stride) >= 0, f"qkv_attention_fused: sequences reach row {last} of {M}")
-    f16 = scheme == "f16x2"
-    table = {"b.0.attn.qkv.weight": qkv_weight.contiguous(), "b.0.attn.qkv.bias": qkv_bias.contiguous()}
-    hs, hb, _ = head_major_qkv(table.__getitem__, "b.0.attn.qkv.weight", heads, False, f16, not f16)
+    mode = PRECISIONS[scheme]
+    f16 = mode == MODE_F16X2
+    table = {"attn.qkv.weight": qkv_weight.contiguous(), "attn.qkv.bias": qkv_bias.contiguous()}
+    hs, hb = head_major_qkv(table.__getitem__, "attn.qkv.weight", heads, False, mode)
     xi = hsplit_rows(x.contiguous()) if f16 else xsplit_rows(x.contiguous())
     stats = None
     if rstd is not None:
         stats = torch.stack([torch.zeros_like(rstd), rstd], dim=1).contiguous()
-    eb = 4 if f16 else 6
-    oi = torch.zeros(M * Cw * eb, dtype=torch.uint8, device=x.device)
+    oi = torch.zeros(M * Cw * IMAGE_BYTES[mode], dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(lib.pafuse_qkv_attention_image(4 if f16 else 8, xi.data_ptr(), stats.data_ptr() if stats is not None else None,
+        _lib.check(lib.pafuse_qkv_attention_image(SPLIT_FLAG[mode], xi.data_ptr(), stats.data_ptr() if stats is not None else None,
                                                   hs.data_ptr(), _ptr(hb, "qkv_hb"), oi.data_ptr(), M, nseq, L, Cw, heads, group, gs,
                                                   seq_stride, tok_stride, 0.0, _stream(x)))
     return hjoin_rows(oi, M, Cw) if f16 else xjoin_rows(oi, M, Cw)
@@ -466,7 +452,6 @@ def mlp_fused(xc, rstd, fc1_weight, fc1_bias, fc2_weight, fc2_bias, eps=1e-6, in
     """The fused MLP kernel on its own (pafuse_mlp_h): xc [M,C] = rows of the residual stream centred on their means, rstd [M] or
     None -> (y - mean(y) as fp32 [M,C] decoded from the H image the kernel writes, stats [M,2] = (mean(y), rstd(y))) with
     y = xc + GELU(rstd (xc W1^T) + b1) W2^T + b2."""
-    from .mixste2 import fused_mlp_fc2_image, split_image
     lib = _lib.load()
     M, Cw = xc.shape
     _need(tuple(fc1_weight.shape) == (2 * Cw, Cw) and tuple(fc2_weight.shape) == (Cw, 2 * Cw), "mlp_fused: weights must be [2C,C] and [C,2C]")
@@ -474,7 +459,7 @@ def mlp_fused(xc, rstd, fc1_weight, fc1_bias, fc2_weight, fc2_bias, eps=1e-6, in
     stats_in = None
     if rstd is not None:
         stats_in = torch.stack([torch.zeros_like(rstd), rstd], dim=1).contiguous()
-    w1h = split_image(fc1_weight.contiguous(), 0, True)
+    w1h = split_image(fc1_weight.contiguous(), 0, MODE_F16X2)
     w2hp = fused_mlp_fc2_image(fc2_weight)
     out = xh if in_place else torch.empty(M * Cw * 4, dtype=torch.uint8, device=xc.device)
     stats = stats_in if in_place and stats_in is not None else torch.empty(M, 2, device=xc.device, dtype=torch.float32)
@@ -485,7 +470,7 @@ def mlp_fused(xc, rstd, fc1_weight, fc1_bias, fc2_weight, fc2_bias, eps=1e-6, in
     return hjoin_rows(out, M, Cw), stats
 
 
-SCHEME_FLAG = {"bf16x3": 0, "f16x2": 4, "bf16x3_images": 8}      # include/pafuse_hip.h: PAFUSE_SPLIT_F16X2, PAFUSE_SPLIT_X
+SCHEMES = {name: mode for name, mode in PRECISIONS.items() if mode in SPLIT_FLAG}      # the split modes by name
 
 
 def split_weights(weight, layout=0, scheme="bf16x3"):
@@ -494,16 +479,10 @@ def split_weights(weight, layout=0, scheme="bf16x3"):
     two fp16 slices of the power-of-two-scaled weight) or 'bf16x3' (the round-3 kernels' images; layout 0: the
     32x32x16-MFMA plain kernel (linear_split's layout 0; no layer of the model since ABI 6), 1: the whole-row layers attn.proj
     and mlp.fc2 (linear_rowln), 2: the 16x16x32-MFMA kernels of attn.qkv and mlp.fc1)."""
-    lib = _lib.load()
     _need(weight.dim() == 2 and weight.shape[1] % 32 == 0, "split_weights: weight must be [N, K] with K % 32 == 0")
     _need(layout in (0, 1, 2), "split_weights: layout 0 (plain 32x32x16 kernel), 1 (whole-row layers) or 2 (qkv / fc1 kernels)")
-    _need(scheme in SCHEME_FLAG, f"split_weights: scheme must be one of {sorted(SCHEME_FLAG)}")
-    N, K = weight.shape
-    img = torch.empty(lib.pafuse_split_image_bytes(N, K, layout | SCHEME_FLAG[scheme]), dtype=torch.uint8, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _lib.check(lib.pafuse_split_weights(_ptr(weight, "weight"), N, K, layout | SCHEME_FLAG[scheme], img.data_ptr(),
-                                            _stream(weight)))
-    return img
+    _need(scheme in SCHEMES, f"split_weights: scheme must be one of {sorted(SCHEMES)}")
+    return split_image(weight, layout, SCHEMES[scheme])
 
 
 def linear_split(x, weight, bias, act=None, image=None, layout=0, scheme="bf16x3", out_image=False):
@@ -520,7 +499,7 @@ def linear_split(x, weight, bias, act=None, image=None, layout=0, scheme="bf16x3
     _need(tuple(weight.shape) == (N, K) and bias.numel() == N, f"linear: x [..,{K}] needs weight [N,{K}] and bias [N]")
     _need(layout in (0, 2), "linear_split: layout 0 or 2 (layout-1 images are the whole-row layers': linear_rowln)")
     img = split_weights(weight, layout, scheme) if image is None else image
-    _need(img.numel() == lib.pafuse_split_image_bytes(N, K, layout | SCHEME_FLAG[scheme]), "linear_split: image size does not match the weight")
+    _need(img.numel() == lib.pafuse_split_image_bytes(N, K, layout | SPLIT_FLAG[SCHEMES[scheme]]), "linear_split: image size does not match the weight")
     x2 = x.contiguous().view(-1, K)
     out = torch.empty(x2.shape[0], N, device=x.device, dtype=torch.float32)
     if scheme == "f16x2":      # both operands as H images (pafuse_linear_h)
@@ -549,9 +528,6 @@ def linear_split(x, weight, bias, act=None, image=None, layout=0, scheme="bf16x3
     return out.view(*x.shape[:-1], N)
 
 
-IMAGE_BYTES = {MODE_F16X2: 4, MODE_BF16X3_IMAGES: 6}      # bytes per element of an activation image: f16x2 H image, bf16x3 X image
-
-
 def rowln_args(x, weight, bias, resid, precision="bf16x3", image=None, post=None, pos=None, next=None, head=None, fold=False,
                in_place=False, resid_image=False, training=False, rowscale=None, rs_map=(0, 1, 1), out=None):
     """One whole-row layer as a pafuse_rowln_args (include/pafuse_hip.h), with the images its mode reads made here.
@@ -559,13 +535,13 @@ def rowln_args(x, weight, bias, resid, precision="bf16x3", image=None, post=None
 
     x [M,K], weight [N,K], bias [N], resid [M,N] fp32.  post / next: (weight, bias, eps) of a LayerNorm; pos: (table [F',N],
     posJ, posF); head: (weight [3,N], bias [3]) behind `next`; fold: (mean, rstd) of the next LayerNorm to 'stats' and x stored
-    centred on that mean instead of the normalised row.  precision: a key of PRECISIONS; mode 2 uses the layout-1 image of
-    weight, modes 3 / 4 the H / X images of x and weight (``image``: a cached weight image).  resid_image (modes 3 / 4): the
+    centred on that mean instead of the normalised row.  precision: a key of PRECISIONS; 'bf16x3' uses the layout-1 image of
+    weight, 'f16x2' / 'bf16x3_images' the H / X images of x and weight (``image``: a cached weight image).  resid_image (image modes): the
     residual goes in as its image and x comes out only as an image ('x' is decoded from it).  in_place: x is written over the
     residual itself (resid, or its image).  training (modes 0 / 2): rowscale [nseq] or None, rs_map = (rs_temporal, rs_J,
     rs_FJ); 'pre' = the pre-norm sum.  out: preallocated outputs by name ('x', 'n', 'head', 'stats', 'pre', 'x_img', 'n_img'),
     at least as large as the layer needs (nothing past row M is written).
-    Outputs: 'x', 'n', 'head', 'stats', 'pre' fp32 (those the options produce); in modes 3 / 4 also 'x_img' / 'n_img', the
+    Outputs: 'x', 'n', 'head', 'stats', 'pre' fp32 (those the options produce); in the image modes also 'x_img' / 'n_img', the
     images joined back to fp32."""
     lib = _lib.load()
     _need(precision in PRECISIONS, f"precision must be one of {sorted(PRECISIONS)}")
@@ -593,7 +569,7 @@ def rowln_args(x, weight, bias, resid, precision="bf16x3", image=None, post=None
     split = (hsplit_rows if mode == MODE_F16X2 else xsplit_rows) if mode >= MODE_F16X2 else None
     if mode >= MODE_F16X2:
         ximg = split(x)
-        wimg = image if image is not None else split_image(weight, 1, mode == MODE_F16X2, mode == MODE_BF16X3_IMAGES)
+        wimg = image if image is not None else split_image(weight, 1, mode)
         keep += [ximg, wimg]
         a.A_img, a.Wsplit = ximg.data_ptr(), wimg.data_ptr()
     else:

@@ -17,7 +17,8 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::noise_fill(key, draw, B, P, F, J)               one draw of noise stream v1 as a tensor (DESIGN.md section 6)
 
 ``precision`` ('bf16x3' = the modules' default; 'bf16x3_images', 'f16x2', 'f32', 'bf16': pafuse_amd.D3DP.precision) is the
-matrix-product mode of the linear layers; in the split modes the ops build and cache the pre-split weight images themselves (cached_split_image).
+matrix-product mode of the linear layers; in the split modes the ops build and cache the pre-split weight images themselves: the
+modules' plan with the modules' default options (images.py: plan_images, make_images, cached), so the ops return the modules' bits.
 
 ``weights`` lists are in ``named_parameters()`` order of the corresponding module (= the reference's state-dict
 order), so ``list(model.parameters())`` is the argument.  The modules in pafuse_amd call the C ABI directly; these ops
@@ -30,13 +31,13 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from ._lib import MODE_BF16X3, MODE_BF16X3_IMAGES, MODE_F16X2, PRECISIONS      # (PRECISIONS: as pafuse_amd.D3DP.PRECISIONS)
+from ._lib import PRECISIONS      # (as pafuse_amd.D3DP.PRECISIONS)
+from .images import (BLOCK_PARAMS, _IMAGE_CACHE_MAX, _image_cache, _ptr, block_images, cached, cached_split_image,  # noqa: F401
+                     effective_mode, fill_block_struct, make_images, plan_images, resolve_options)   # (the cache: importable from here)
 from .ops import _need, _stream
-from .mixste2 import (FOLDED_LINEAR, FUSED_MLP_DEFAULT_WIDTHS, MixSTE2, SPLIT_SUFFIXES, _ptr, fill_weights_struct, folded_linear,
-                      fused_mlp_fc2_image, head_major_qkv, image_layout, sinusoid_frequencies, split_image)
+from .mixste2 import MixSTE2, fill_weights_struct, sinusoid_frequencies
 
-BLOCK_KEYS = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
-              "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
+BLOCK_KEYS = tuple(key for _, key in BLOCK_PARAMS)
 
 
 @lru_cache(maxsize=None)
@@ -66,67 +67,6 @@ def _freqs(channels, device):
     return _freq_cache[key]
 
 
-_image_cache = {}        # (data_ptr, _version, device, layout, shape, scheme) of a linear weight -> (its split image, the weight)
-_IMAGE_CACHE_MAX = 2048  # ~ three models' worth of linear weights; the oldest entries go first
-
-
-def cached_split_image(weight, layout, f16=False, x=False):
-    """The pre-split image of a linear weight, made once per (storage, version, layout, scheme): the schema'd ops take plain
-    parameter tensors, so they build and cache the images the split-precision kernels read (the modules keep theirs per
-    module).  layout: pafuse_split_weights' (1 proj / fc2, 2 qkv / fc1; 0 is no model layer's since ABI 6).
-    An entry keeps a reference to the tensor it was made from: while the entry lives that storage cannot be freed, so no
-    other tensor can come to sit at its address with a matching version and shape and hit a stale image (a freed temporary
-    such as `w.float()` or `w.detach().clone()` made per call would otherwise do exactly that)."""
-    key = (weight.data_ptr(), weight._version, weight.device, int(layout), tuple(weight.shape), bool(f16), bool(x))
-    hit = _image_cache.get(key)
-    if hit is None:
-        while len(_image_cache) >= _IMAGE_CACHE_MAX:
-            _image_cache.pop(next(iter(_image_cache)))
-        hit = _image_cache[key] = (split_image(weight, layout, f16, x), weight)
-    return hit[0]
-
-
-def cached_folded_linear(table, name, f16=False, x=False, image=True):
-    """(image, ls, lt) of a qkv / fc1 layer with its LayerNorm folded in (mixste2.folded_linear), made once per version of
-    the four tensors it is built from - the modules' own default in the split modes, so the ops return the modules' bits.
-    The entry pins its four source tensors (see cached_split_image)."""
-    block, norm = name.rsplit(".", 3)[0], FOLDED_LINEAR[name.split(".", 2)[2]]
-    parts = (table[name], table[f"{block}.{norm}.weight"], table[f"{block}.{norm}.bias"], table[name[:-len("weight")] + "bias"])
-    key = ("fold", bool(f16), bool(x), bool(image)) + tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in parts) + (parts[0].device,)
-    hit = _image_cache.get(key)
-    if hit is None:
-        while len(_image_cache) >= _IMAGE_CACHE_MAX:
-            _image_cache.pop(next(iter(_image_cache)))
-        hit = _image_cache[key] = (folded_linear(table.__getitem__, name, f16, x, image), parts)
-    return hit[0]
-
-
-def cached_head_major_qkv(table, name, heads, f16=False, x=False):
-    """(image, hb, hl) of a qkv layer for the fused qkv + attention kernel (mixste2.head_major_qkv, LayerNorm folded), made once
-    per version of the four tensors it is built from; the entry pins them (see cached_split_image)."""
-    block, norm = name.rsplit(".", 3)[0], FOLDED_LINEAR[name.split(".", 2)[2]]
-    parts = (table[name], table[f"{block}.{norm}.weight"], table[f"{block}.{norm}.bias"], table[name[:-len("weight")] + "bias"])
-    key = ("head-major", bool(f16), bool(x), int(heads)) + tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in parts) + (parts[0].device,)
-    hit = _image_cache.get(key)
-    if hit is None:
-        while len(_image_cache) >= _IMAGE_CACHE_MAX:
-            _image_cache.pop(next(iter(_image_cache)))
-        hit = _image_cache[key] = (head_major_qkv(table.__getitem__, name, heads, True, f16, x), parts)
-    return hit[0]
-
-
-def cached_fused_mlp_fc2(weight):
-    """The fused MLP kernel's image of an fc2 weight (mixste2.fused_mlp_fc2_image), made once per (storage, version); the entry
-    pins the tensor (see cached_split_image)."""
-    key = ("fused-mlp", weight.data_ptr(), weight._version, weight.device, tuple(weight.shape))
-    hit = _image_cache.get(key)
-    if hit is None:
-        while len(_image_cache) >= _IMAGE_CACHE_MAX:
-            _image_cache.pop(next(iter(_image_cache)))
-        hit = _image_cache[key] = (fused_mlp_fc2_image(weight), weight)
-    return hit[0]
-
-
 def _mode(precision):
     if precision not in PRECISIONS:
         raise _lib.PafuseError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
@@ -135,10 +75,8 @@ def _mode(precision):
 
 def mixste_struct(weights, frames, joints, depth, heads, precision="f32"):
     """pafuse_mixste2_weights from a flat parameter list; returns (struct, keep-alive)."""
-    mode = _mode(precision)
     channels = weights[0].shape[-1]                           # Spatial_pos_embed [1,J,C] comes first
-    if mode == MODE_BF16X3_IMAGES and not _lib.load().pafuse_mode_supported(mode, channels, 0, heads, joints, frames):
-        mode = 2                                              # as MixSTE2.effective_mode: the same products on the round-3 kernels
+    mode = effective_mode(_mode(precision), channels, 0, heads, joints, frames)
     names = mixste_param_names(frames, joints, channels, depth, heads)
     if len(weights) != len(names):
         raise _lib.PafuseError(f"expected {len(names)} weight tensors (named_parameters() order), got {len(weights)}")
@@ -148,23 +86,9 @@ def mixste_struct(weights, frames, joints, depth, heads, precision="f32"):
         _ptr(t, n)
     fr = _freqs(channels, weights[0].device)
     w = _lib.MixSTE2Weights()
-    images = None
-    if mode >= MODE_BF16X3:
-        images = {}
-        f16, x = mode == MODE_F16X2, mode == MODE_BF16X3_IMAGES
-        for n, t in table.items():
-            plain = not (x and n.endswith("attn.qkv.weight"))      # mode 4 multiplies the head-major qkv image only
-            if n.endswith(tuple(FOLDED_LINEAR)):    # the modules' default in every split mode: LayerNorm folded into qkv / fc1
-                images[n], images[n[:-len("weight")] + "ls"], images[n[:-len("weight")] + "lt"] = cached_folded_linear(table, n, f16, x, plain)
-                if not plain:
-                    del images[n]
-            elif n.endswith(SPLIT_SUFFIXES):
-                images[n] = cached_split_image(t, image_layout(n), f16, x)
-            if mode >= MODE_F16X2 and n.endswith("attn.qkv.weight"):     # the modules' default there: qkv + attention in one kernel
-                stem = n[:-len("weight")]
-                images[stem + "hs"], images[stem + "hb"], images[stem + "hl"] = cached_head_major_qkv(table, n, heads, f16, x)
-            if mode == MODE_F16X2 and n.endswith("mlp.fc2.weight") and channels in FUSED_MLP_DEFAULT_WIDTHS and t.shape[1] == 2 * channels:
-                images[n[:-len("weight")] + "hp"] = cached_fused_mlp_fc2(t)    # ... and the MLP in one kernel where the modules do
+    # the modules' default options (the shapes checked above are those of mlp_ratio 2)
+    plan = plan_images(names, mode, resolve_options(mode, channels, 2 * channels))
+    images = make_images(plan, table.__getitem__, mode, heads, cache=cached) if plan else None
     fill_weights_struct(w, table.__getitem__, fr, frames, joints, channels, depth, heads, 5, mode, images)
     return w, (table, fr, images)
 
@@ -244,22 +168,10 @@ def block(x: torch.Tensor, weights: List[torch.Tensor], heads: int, precision: s
     _need(heads > 0 and Cc % heads == 0, "block: heads must divide the width")
     y = x.contiguous().clone()
     w = _lib.BlockWeights()
-    for field, t, name in zip(_lib.BLOCK_FIELDS, weights, BLOCK_KEYS):
-        setattr(w, field, _ptr(t, name))
-    images = []
-    if mode == MODE_BF16X3_IMAGES and not lib.pafuse_mode_supported(mode, Cc, 0, heads, L, L):
-        mode = 2
-    if mode >= MODE_BF16X3:
-        for field, idx, layout in (("qkv_ws", 2, 2), ("proj_ws", 4, 1), ("fc1_ws", 8, 2), ("fc2_ws", 10, 1)):
-            if mode == MODE_BF16X3_IMAGES and field == "qkv_ws":
-                continue
-            images.append(cached_split_image(weights[idx], layout, mode == MODE_F16X2, mode == MODE_BF16X3_IMAGES))
-            setattr(w, field, images[-1].data_ptr())
-    if mode == MODE_BF16X3_IMAGES:       # qkv + attention is one kernel there: the head-major image (LayerNorm not folded: Block.forward normalises)
-        table = {"b.0.attn.qkv.weight": weights[2], "b.0.attn.qkv.bias": weights[3]}
-        hs, hb, _ = head_major_qkv(table.__getitem__, "b.0.attn.qkv.weight", heads, False, False, True)
-        images += [hs, hb]
-        w.qkv_hs, w.qkv_hb = hs.data_ptr(), hb.data_ptr()
+    mode = effective_mode(mode, Cc, 0, heads, L, L)
+    get = dict(zip(BLOCK_KEYS, weights)).__getitem__
+    images = block_images(get, mode, heads, cache=cached)
+    fill_block_struct(w, get, images=images)
     nbytes = lib.pafuse_block_workspace_bytes(S * L, Cc)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     _lib.check(lib.pafuse_block_forward(C.byref(w), _ptr(y, "x"), S, L, Cc, heads, mode, ws.data_ptr(), nbytes, _stream(x)))
