@@ -15,7 +15,9 @@
  *   pafuse_block_forward     Block.forward, common/mixste.py:113-116
  *   pafuse_attention_backward, pafuse_linear_weight_grad   the backward of the two above as torch autograd derives it
  *                            (unit entries of the training step's kernels; with pafuse_layernorm_backward,
- *                            pafuse_linear_input_grad, pafuse_linear_train, pafuse_gelu_backward)
+ *                            pafuse_linear_input_grad, pafuse_linear_train, pafuse_gelu_backward; the first and last
+ *                            layers: pafuse_train_head_grad, pafuse_train_patch_grad, pafuse_train_group_sum,
+ *                            pafuse_train_sinusoid)
  *   pafuse_time_embed        MixSTE2.time_mlp, common/mixste.py:127-139,179-184
  *   pafuse_mixste2_forward   MixSTE2.forward (is_train=False), common/mixste.py:278-298
  *   pafuse_d3dp_sample       D3DP.ddim_sample_flip / ddim_sample, common/diffusionpose.py:227-316
@@ -384,6 +386,33 @@ int pafuse_linear_train(const float *A, const float *W, const float *bias, float
 int pafuse_gelu_backward(const float *u, const float *dh, float *du, float *db, int64_t M, int32_t N, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* Unit entry points of the gradients at the rim of the training step - the output head, the patch embedding, the position and
+ * time embeddings - and of the sinusoid in front of the time MLP: each calls the host function the step calls (train_host.inc).
+ * Gradient outputs are ADDED INTO (as the step accumulates into its gradient struct), except dhn and dtemb, which are OVERWRITTEN.
+ * pafuse_train_head_grad (head_grad): out = hn head_w^T + head_b with dout [M,3], hn [M,C], head_w [3,C]:
+ *   d_head_w [3,C] += dout^T hn,  d_head_b [3] += column sums of dout,  dhn [M,C] = dout head_w.
+ * pafuse_train_patch_grad (concat_inputs, patch_grad): x0 = (x2d | x3d) patch_w^T + patch_b + pos_spatial[j] + temb[b] with
+ *   x2d [B,F,J,2], x3d [B,F,J,3], g = d x0 [B,F,J,C]:  d_patch_w [C,5] += g^T (x2d | x3d),  d_patch_b [C] += column sums of g,
+ *   d_pos_spatial [J,C] += sums of g over (b, f),  dtemb [B,C] = sums of g over (f, j).
+ * pafuse_train_group_sum (group_sum): out [G,C] = (accumulate 1: out +) sums of x [B,F,J,C] over the rows of each group -
+ *   mode 0: per joint (G = J, Spatial_pos_embed), 1: per frame (G = F, Temporal_pos_embed), 2: per sample (G = B, time embedding).
+ * pafuse_train_sinusoid (sinusoid): out [B,C] = [sin(a) | cos(a)], a = (float)t[b] * freqs[k] in fp32, freqs [C/2]
+ *   (common/mixste.py:132-138); C even.
+ * workspace: the entry's own ..._bytes query (0 for arguments the entry refuses).  Partial sums are joined in a fixed order
+ * (bit-reproducible).  Refused before any launch: a NULL operand, a negative size, a mode outside 0 .. 2, an accumulate flag
+ * other than 0 / 1, C < 1 (sinusoid: odd C), a too-small workspace.  No rows (M, or one of B, F, J, = 0): nothing is launched. */
+size_t pafuse_train_head_grad_bytes(int64_t M, int32_t C);
+int pafuse_train_head_grad(const float *dout, const float *hn, const float *head_w, float *d_head_w, float *d_head_b, float *dhn,
+                           int64_t M, int32_t C, void *workspace, size_t workspace_bytes, void *stream);
+size_t pafuse_train_patch_grad_bytes(int32_t B, int32_t F, int32_t J, int32_t C);
+int pafuse_train_patch_grad(const float *x2d, const float *x3d, const float *g, float *d_patch_w, float *d_patch_b,
+                            float *d_pos_spatial, float *dtemb, int32_t B, int32_t F, int32_t J, int32_t C, void *workspace,
+                            size_t workspace_bytes, void *stream);
+size_t pafuse_train_group_sum_bytes(int32_t mode, int32_t B, int32_t F, int32_t J, int32_t C);
+int pafuse_train_group_sum(const float *x, float *out, int32_t mode, int32_t accumulate, int32_t B, int32_t F, int32_t J, int32_t C,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int pafuse_train_sinusoid(const int64_t *t, const float *freqs, float *out, int32_t B, int32_t C, void *stream);
+
 /* x[S*L,C] <- Block(x) in place for S contiguous sequences of L tokens (Block.forward, eps 1e-6).  operand_bf16: the
  * matrix-product mode of the four linear layers (as pafuse_mixste2_weights.operand_bf16; 2, 3 and 4 need the *_ws images of
  * their scheme, 4 also qkv_hs / qkv_hb). */
@@ -679,7 +708,9 @@ int pafuse_d3dp_replay_layers(const pafuse_d3dp_config *cfg, int32_t B, int32_t 
  * in a fixed order: bit-reproducible, no atomics.  `side_stream` (may be NULL): a second HIP stream the weight-gradient
  * GEMMs run on next to the input-gradient chain (forked and joined with events inside the call; results identical).
  * w->operand_bf16: 0 = every GEMM on the fp32 matrix cores; 2 = split-precision products in the GEMMs of the step
- * (qkv, fc1, the whole-row proj / fc2, every dX and dW; fp32-equivalent, gradients within the same bounds); 1 is refused. */
+ * (qkv, fc1, the whole-row proj / fc2, every dX and dW; fp32-equivalent, gradients within the same bounds); 1 is refused.
+ * B is bounded by the reduction partials of the time embedding's gradient, 32 B C floats of 18.9 M: B <= 1536 at C = 384
+ * (PAFUSE_E_SHAPE above that, from both calls, before any launch). */
 size_t pafuse_mixste2_train_bytes(const pafuse_mixste2_weights *w, int32_t B);
 int pafuse_mixste2_train_forward(const pafuse_mixste2_weights *w, const float *x2d, const float *x3d, const int64_t *t,
                                  int32_t B, const float *drop_path, float *out, void *saved, size_t saved_bytes,

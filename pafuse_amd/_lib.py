@@ -112,6 +112,13 @@ SIGNATURES = {
                                       C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pafuse_gelu_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                        C.c_size_t, C.c_void_p]),
+    "pafuse_train_head_grad_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "pafuse_train_head_grad": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pafuse_train_patch_grad_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "pafuse_train_patch_grad": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pafuse_train_group_sum_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "pafuse_train_group_sum": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pafuse_train_sinusoid": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p]),
     "pafuse_block_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "pafuse_block_forward": (C.c_int, [C.POINTER(BlockWeights), C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -2231,6 +2231,104 @@ int pafuse_gelu_backward(const float* u, const float* dh, float* du, float* db, 
     return gelu_bwd(u, dh, du, db, M, N, tb, (hipStream_t)stream);
 }
 
+// Unit entries of the first- and last-layer gradients.  Their workspaces hold exactly what the host helpers write: the partials
+// (row_chunks / group_chunks parts), and for the patch embedding the [M,5] input and the [5,C] sums in front of them.
+static size_t head_grad_partials(int64_t M, int C) {
+    int64_t rows;
+    return M > 0 ? (size_t)row_chunks(M, rows) * 3 * C : 0;
+}
+
+static size_t group_sum_partials(int mode, int B, int F, int J, int C) {
+    int per;
+    const int count = group_sum_count(mode, B, F, J);
+    return count > 0 ? (size_t)group_chunks(count, per) * group_sum_groups(mode, B, F, J) * C : 0;
+}
+
+static size_t patch_grad_partials(int B, int F, int J, int C) {
+    const int64_t M = (int64_t)B * F * J;
+    int64_t rows;
+    if (M <= 0) return 0;
+    return std::max((size_t)row_chunks(M, rows) * 5 * C, std::max(group_sum_partials(0, B, F, J, C), group_sum_partials(2, B, F, J, C)));
+}
+
+// B, F, J >= 0 and C >= 1 with B F J rows that the kernels' int row counts hold
+static bool rim_dims_ok(int B, int F, int J, int C) { return B >= 0 && F >= 0 && J >= 0 && C >= 1; }
+static bool rim_rows_fit(int B, int F, int J) {   // (a zero size leaves the other two's product in a group's int row count)
+    const int64_t lim = 0x7fffffff;
+    return (int64_t)B * F * J <= lim && (int64_t)B * F <= lim && (int64_t)B * J <= lim && (int64_t)F * J <= lim;
+}
+
+size_t pafuse_train_head_grad_bytes(int64_t M, int32_t C) {
+    return (M < 0 || C < 1 || M > (int64_t)0xffffffff / C) ? 0 : align_up(head_grad_partials(M, C) * 4);
+}
+
+int pafuse_train_head_grad(const float* dout, const float* hn, const float* head_w, float* d_head_w, float* d_head_b, float* dhn,
+                           int64_t M, int32_t C, void* workspace, size_t workspace_bytes, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!dout || !hn || !head_w || !d_head_w || !d_head_b || !dhn || !workspace || M < 0)
+        return fail(PAFUSE_E_ARG, "train_head_grad: null pointer or negative M");
+    // (head_backward_kernel: one thread per element of dhn, M C / 256 workgroups in one grid dimension)
+    if (C < 1 || M > (int64_t)0xffffffff / C) return fail(PAFUSE_E_SHAPE, "train_head_grad: M=%lld, C=%d out of range", (long long)M, C);
+    if (workspace_bytes < pafuse_train_head_grad_bytes(M, C)) return fail(PAFUSE_E_WORKSPACE, "train_head_grad: workspace too small");
+    if (M == 0) return PAFUSE_OK;
+    TrainBuffers tb{};
+    tb.partial = tb.partial_side = (float*)workspace, tb.partial_floats = head_grad_partials(M, C);
+    return head_grad(dout, hn, head_w, d_head_w, d_head_b, dhn, M, C, tb, (hipStream_t)stream);
+}
+
+size_t pafuse_train_patch_grad_bytes(int32_t B, int32_t F, int32_t J, int32_t C) {
+    if (!rim_dims_ok(B, F, J, C) || !rim_rows_fit(B, F, J)) return 0;
+    return align_up((size_t)B * F * J * 5 * 4) + align_up((size_t)5 * C * 4) + align_up(patch_grad_partials(B, F, J, C) * 4);
+}
+
+int pafuse_train_patch_grad(const float* x2d, const float* x3d, const float* g, float* d_patch_w, float* d_patch_b,
+                            float* d_pos_spatial, float* dtemb, int32_t B, int32_t F, int32_t J, int32_t C, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!x2d || !x3d || !g || !d_patch_w || !d_patch_b || !d_pos_spatial || !dtemb || !workspace || B < 0 || F < 0 || J < 0)
+        return fail(PAFUSE_E_ARG, "train_patch_grad: null pointer or negative size");
+    if (C < 1 || !rim_rows_fit(B, F, J)) return fail(PAFUSE_E_SHAPE, "train_patch_grad: B=%d F=%d J=%d C=%d out of range", B, F, J, C);
+    if (workspace_bytes < pafuse_train_patch_grad_bytes(B, F, J, C)) return fail(PAFUSE_E_WORKSPACE, "train_patch_grad: workspace too small");
+    const int64_t M = (int64_t)B * F * J;
+    if (M == 0) return PAFUSE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    TrainBuffers tb{};
+    char* base = (char*)workspace;
+    tb.in5 = (float*)base, base += align_up((size_t)M * 5 * 4);
+    tb.small = (float*)base, base += align_up((size_t)5 * C * 4);
+    tb.partial = tb.partial_side = (float*)base, tb.partial_floats = patch_grad_partials(B, F, J, C);
+    const int rc = concat_inputs(x2d, x3d, tb.in5, M, s);
+    if (rc) return rc;
+    return patch_grad(tb.in5, g, d_patch_w, d_patch_b, d_pos_spatial, dtemb, B, F, J, C, tb, s);
+}
+
+size_t pafuse_train_group_sum_bytes(int32_t mode, int32_t B, int32_t F, int32_t J, int32_t C) {
+    if (mode < 0 || mode > 2 || !rim_dims_ok(B, F, J, C) || !rim_rows_fit(B, F, J)) return 0;
+    return align_up(group_sum_partials(mode, B, F, J, C) * 4);
+}
+
+int pafuse_train_group_sum(const float* x, float* out, int32_t mode, int32_t accumulate, int32_t B, int32_t F, int32_t J, int32_t C,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!x || !out || !workspace || B < 0 || F < 0 || J < 0) return fail(PAFUSE_E_ARG, "train_group_sum: null pointer or negative size");
+    if (mode < 0 || mode > 2) return fail(PAFUSE_E_ARG, "train_group_sum: mode %d (0, 1 or 2)", mode);
+    if (accumulate != 0 && accumulate != 1) return fail(PAFUSE_E_ARG, "train_group_sum: accumulate %d (0 or 1)", accumulate);
+    if (C < 1 || !rim_rows_fit(B, F, J)) return fail(PAFUSE_E_SHAPE, "train_group_sum: B=%d F=%d J=%d C=%d out of range", B, F, J, C);
+    if (workspace_bytes < pafuse_train_group_sum_bytes(mode, B, F, J, C)) return fail(PAFUSE_E_WORKSPACE, "train_group_sum: workspace too small");
+    if ((int64_t)B * F * J == 0) return PAFUSE_OK;
+    TrainBuffers tb{};
+    tb.partial = tb.partial_side = (float*)workspace, tb.partial_floats = group_sum_partials(mode, B, F, J, C);
+    return group_sum(x, out, mode, B, F, J, C, tb, (hipStream_t)stream, accumulate);
+}
+
+int pafuse_train_sinusoid(const int64_t* t, const float* freqs, float* out, int32_t B, int32_t C, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!t || !freqs || !out || B < 0) return fail(PAFUSE_E_ARG, "train_sinusoid: null pointer or negative B");
+    if (C < 2 || C % 2 || (int64_t)B * C > 0x7fffffff) return fail(PAFUSE_E_SHAPE, "train_sinusoid: C=%d must be even and positive (B=%d)", C, B);
+    if (B == 0) return PAFUSE_OK;
+    return sinusoid(t, freqs, out, B, C, (hipStream_t)stream);
+}
+
 size_t pafuse_mixste2_train_bytes(const pafuse_mixste2_weights* w, int32_t B) {
     if (!w || B <= 0 || check_weights(w, true)) return 0;
     return train_bytes(w, B);
@@ -2249,6 +2347,7 @@ int pafuse_mixste2_train_forward(const pafuse_mixste2_weights* w, const float* x
     if (w->joints > 80 || w->frames > ATTN_BWD_LONG_LP)
         return fail(PAFUSE_E_SHAPE, "training: sequence lengths J=%d F=%d must be <= 80 / <= %d (the single-model variant is inference only)",
                     w->joints, w->frames, ATTN_BWD_LONG_LP);
+    if (!train_partials_fit(w, B)) return fail(PAFUSE_E_SHAPE, "training: B=%d exceeds the %d samples per call at width %d", B, train_max_batch(w), w->channels);
     if (saved_bytes < train_bytes(w, B)) return fail(PAFUSE_E_WORKSPACE, "mixste2_train_forward: buffer too small");
     TrainBuffers tb;
     carve_train((char*)saved, w, B, tb);
@@ -2262,6 +2361,7 @@ int pafuse_mixste2_train_backward(const pafuse_mixste2_weights* w, const pafuse_
     int rc = check_weights(w, true);
     if (rc) return rc;
     if (!grads || !dout || !saved || B <= 0) return fail(PAFUSE_E_ARG, "mixste2_train_backward: bad argument");
+    if (!train_partials_fit(w, B)) return fail(PAFUSE_E_SHAPE, "training: B=%d exceeds the %d samples per call at width %d", B, train_max_batch(w), w->channels);
     if (saved_bytes < train_bytes(w, B)) return fail(PAFUSE_E_WORKSPACE, "mixste2_train_backward: buffer too small");
     TrainBuffers tb;
     carve_train((char*)saved, w, B, tb);

@@ -32,6 +32,12 @@ constexpr int TN_TARGET_WORKGROUPS = 512;  // ~2 per CU: more splits only add pa
 // room for one large-tile workgroup per CU (256 x 256 outputs each) plus the column-sum partials: the partial tiles of a
 // weight gradient are written once and read once - 67 MB per launch at 256 workgroups, beside the 170 - 340 MB its operands take
 constexpr size_t TRAIN_PARTIAL_FLOATS = (size_t)(256 + 32) * 256 * 256;
+// The small reductions of the first and last layers share it: the largest, group_sum, writes 32 chunks x max(B, F, J) groups x C
+// floats - 6.3 M at F = 256, C = 768, whatever J <= 80.  Its per-sample mode bounds B: 32 B C floats, B <= 1536 at C = 384.
+inline int train_max_batch(const pafuse_mixste2_weights* w) { return (int)(TRAIN_PARTIAL_FLOATS / ((size_t)32 * w->channels)); }
+inline bool train_partials_fit(const pafuse_mixste2_weights* w, int B) {
+    return (size_t)32 * std::max(B, std::max(w->frames, w->joints)) * w->channels <= TRAIN_PARTIAL_FLOATS;
+}
 
 size_t train_bytes(const pafuse_mixste2_weights* w, int B) {
     const size_t M = (size_t)B * w->frames * w->joints, C = w->channels;
@@ -134,6 +140,21 @@ int reduce_into(const float* partial, float* out, int n, int nparts, int64_t str
 
 int bias_grad(const float* dY, float* db, int64_t M, int N, TrainBuffers& tb, hipStream_t s, bool side = false);
 
+// the row split of the small reductions (bias_grad, outer_sum): chunks of `rows` rows, at most 256, none empty
+inline int row_chunks(int64_t M, int64_t& rows) {
+    const int chunks = (int)std::min<int64_t>(256, (M + 63) / 64);
+    rows = (M + chunks - 1) / chunks;
+    return (int)((M + rows - 1) / rows);
+}
+// the split of group_sum: chunks of `per` of a group's `count` rows, at most 32, none empty
+inline int group_chunks(int count, int& per) {
+    const int chunks = std::min(32, (count + 15) / 16);
+    per = (count + chunks - 1) / chunks;
+    return (count + per - 1) / per;
+}
+inline int group_sum_groups(int mode, int B, int F, int J) { return mode == 0 ? J : (mode == 1 ? F : B); }
+inline int group_sum_count(int mode, int B, int F, int J) { return mode == 0 ? B * F : (mode == 1 ? B * J : F * J); }
+
 constexpr int TN_BIG_TARGET_WORKGROUPS = 256;  // one large-tile workgroup per CU
 
 template <int NB, int KB, int WN, int WK>
@@ -194,9 +215,9 @@ int weight_grad(const float* dY, const float* X, float* dW, int64_t M, int N, in
 // db[N] += column sums of dY[M,N]
 int bias_grad(const float* dY, float* db, int64_t M, int N, TrainBuffers& tb, hipStream_t s, bool side) {
     float* partial = side ? tb.partial_side : tb.partial;
-    int chunks = (int)std::min<int64_t>(256, (M + 63) / 64);
-    const int64_t rows = (M + chunks - 1) / chunks;
-    chunks = (int)((M + rows - 1) / rows);
+    int64_t rows;
+    const int chunks = row_chunks(M, rows);
+    if ((size_t)chunks * N > tb.partial_floats) return fail(PAFUSE_E_WORKSPACE, "bias_grad: partial buffer");
     int rc = launch<colsum_kernel>("colsum_kernel", dim3(blocks_for(N), (unsigned)chunks), 256, 0, s, dY, partial, M, N, rows);
     if (rc) return rc;
     return reduce_into(partial, db, N, chunks, N, s);
@@ -262,13 +283,13 @@ int gelu_bwd(const float* u, const float* dh, float* du, float* db, int64_t M, i
     return reduce_into(tb.partial, db, N, chunks, N, s);
 }
 
+// out[G][C] (+)= sums of x[B*F*J][C] over the rows of each group: mode 0 per joint, 1 per frame, 2 per sample (group_sum_kernel)
 int group_sum(const float* x, float* out, int mode, int B, int F, int J, int C, TrainBuffers& tb, hipStream_t s,
               int accumulate = 1) {
-    const int G = mode == 0 ? J : (mode == 1 ? F : B);
-    const int count = mode == 0 ? B * F : (mode == 1 ? B * J : F * J);
-    int chunks = std::min(32, (count + 15) / 16);
-    const int per = (count + chunks - 1) / chunks;
-    chunks = (count + per - 1) / per;
+    const int G = group_sum_groups(mode, B, F, J);
+    int per;
+    const int chunks = group_chunks(group_sum_count(mode, B, F, J), per);
+    if ((size_t)chunks * G * C > tb.partial_floats) return fail(PAFUSE_E_WORKSPACE, "group_sum: partial buffer");
     int rc = launch<group_sum_kernel>("group_sum_kernel", dim3((unsigned)G, (unsigned)chunks), 256, 0, s, x, tb.partial, mode, B, F, J, C, G, per);
     if (rc) return rc;
     return reduce_into(tb.partial, out, G * C, chunks, (int64_t)G * C, s, accumulate);
@@ -277,12 +298,36 @@ int group_sum(const float* x, float* out, int mode, int B, int F, int J, int C, 
 // out[NI][C] (+)= sum_rows s[row][i] x[row][c]
 int outer_sum(const float* sv, const float* x, float* out, int64_t M, int NI, int C, TrainBuffers& tb, hipStream_t s,
               int accumulate) {
-    int chunks = (int)std::min<int64_t>(256, (M + 63) / 64);
-    const int64_t rows = (M + chunks - 1) / chunks;
-    chunks = (int)((M + rows - 1) / rows);
+    int64_t rows;
+    const int chunks = row_chunks(M, rows);
+    if ((size_t)chunks * NI * C > tb.partial_floats) return fail(PAFUSE_E_WORKSPACE, "outer_sum: partial buffer");
     int rc = launch<outer_sum_kernel>("outer_sum_kernel", (unsigned)chunks, 256, 0, s, sv, x, tb.partial, M, NI, C, rows);
     if (rc) return rc;
     return reduce_into(tb.partial, out, NI * C, chunks, (int64_t)NI * C, s, accumulate);
+}
+
+// head: out = hn Wh^T + bh (mixste.py:208-211,291).  d head_w [3,C] += dout^T hn, d head_b [3] += column sums of dout,
+// dhn [M,C] = dout Wh (overwritten)
+int head_grad(const float* dout, const float* hn, const float* head_w, float* d_head_w, float* d_head_b, float* dhn, int64_t M,
+              int C, TrainBuffers& tb, hipStream_t s) {
+    int rc;
+    if ((rc = outer_sum(dout, hn, d_head_w, M, 3, C, tb, s, 1))) return rc;
+    if ((rc = bias_grad(dout, d_head_b, M, 3, tb, s))) return rc;
+    return launch<head_backward_kernel>("head_backward_kernel", blocks_for(M * C), 256, 0, s, dout, head_w, dhn, M, C);
+}
+
+// first layer: x0 = in5 Wpatch^T + b + pos_s[j] + temb[b] (mixste.py:222-227), g = d x0 [B*F*J,C].  d patch_w [C,5] += g^T in5
+// (through the [5,C] sums in tb.small), d patch_b [C] += column sums of g, d pos_spatial [J,C] += sums per joint,
+// dtemb [B,C] = sums per sample (overwritten; may be tb.small: the [5,C] sums have been read by then)
+int patch_grad(const float* in5, const float* g, float* d_patch_w, float* d_patch_b, float* d_pos_spatial, float* dtemb, int B,
+               int F, int J, int C, TrainBuffers& tb, hipStream_t s) {
+    const int64_t M = (int64_t)B * F * J;
+    int rc;
+    if ((rc = outer_sum(in5, g, tb.small, M, 5, C, tb, s, 0))) return rc;
+    if ((rc = launch<transpose_small_kernel>("transpose_small_kernel", blocks_for(5 * C), 256, 0, s, tb.small, d_patch_w, 5, C))) return rc;
+    if ((rc = bias_grad(g, d_patch_b, M, C, tb, s))) return rc;
+    if ((rc = group_sum(g, d_pos_spatial, 0, B, F, J, C, tb, s))) return rc;
+    return group_sum(g, dtemb, 2, B, F, J, C, tb, s, 0);
 }
 
 template <int LP, int DP>
@@ -386,17 +431,27 @@ int prepare_images(const pafuse_mixste2_weights* w, int B, bool transposed, Trai
     return launch<split_weights_batch_kernel>("split_weights_batch_kernel", (unsigned)blocks, 256, 0, s, p);
 }
 
+// out[B,C] = [sin(t_b freqs) | cos(t_b freqs)], freqs [C/2]: the time MLP's input
+int sinusoid(const int64_t* t, const float* freqs, float* out, int B, int C, hipStream_t s) {
+    return launch<sinusoid_kernel>("sinusoid_kernel", blocks_for((int64_t)B * C / 2), 256, 0, s, t, freqs, out, B, C);
+}
+
+// in5[M,5] = (x2d[M,2] | x3d[M,3]): the patch embedding's input, kept for its weight gradient
+int concat_inputs(const float* x2d, const float* x3d, float* in5, int64_t M, hipStream_t s) {
+    return launch<concat_inputs_kernel>("concat_inputs_kernel", blocks_for(M), 256, 0, s, x2d, x3d, in5, M);
+}
+
 int train_forward(const pafuse_mixste2_weights* w, const float* x2d, const float* x3d, const int64_t* t, int B,
                   const float* drop, float* out, TrainBuffers& tb, hipStream_t s) {
     const int F = w->frames, J = w->joints, C = w->channels, nblk = 2 * w->depth;
     const int64_t M = (int64_t)B * F * J, smax = (int64_t)B * std::max(F, J);
     int rc;
     // time MLP, unfused so that its intermediates are kept                          mixste.py:179-184,228-230
-    if ((rc = launch<sinusoid_kernel>("sinusoid_kernel", blocks_for((int64_t)B * C / 2), 256, 0, s, t, w->freqs, tb.sincos, B, C))) return rc;
+    if ((rc = sinusoid(t, w->freqs, tb.sincos, B, C, s))) return rc;
     if ((rc = plain_linear(tb.sincos, w->tm1_w, w->tm1_b, tb.uh, B, 2 * C, C, s))) return rc;
     if ((rc = gelu_fwd(tb.uh, tb.hid, (int64_t)B * 2 * C, s))) return rc;
     if ((rc = plain_linear(tb.hid, w->tm3_w, w->tm3_b, tb.temb, B, C, 2 * C, s))) return rc;
-    if ((rc = launch<concat_inputs_kernel>("concat_inputs_kernel", blocks_for(M), 256, 0, s, x2d, x3d, tb.in5, M))) return rc;
+    if ((rc = concat_inputs(x2d, x3d, tb.in5, M, s))) return rc;
     EmbedParams e{};
     e.x3d = x3d, e.x2d = x2d, e.pw = w->patch_w, e.pb = w->patch_b, e.pos = w->pos_spatial, e.temb = tb.temb;
     e.n_w = w->ste[0].norm1_w, e.n_b = w->ste[0].norm1_b, e.n_eps = 1e-6f;
@@ -501,9 +556,7 @@ int train_backward(const pafuse_mixste2_weights* w, const pafuse_mixste2_weights
     int rc;
     if (hipMemsetAsync(tb.zeros, 0, (size_t)3 * C * 4, s) != hipSuccess) return fail(PAFUSE_E_HIP, "memset failed");
     // head: out = LN_h(y) Wh^T + bh                                                  mixste.py:208-211,291
-    if ((rc = outer_sum(dout, tb.hn, G(gr->head_w), M, 3, C, tb, s, 1))) return rc;
-    if ((rc = bias_grad(dout, G(gr->head_b), M, 3, tb, s))) return rc;
-    if ((rc = launch<head_backward_kernel>("head_backward_kernel", blocks_for(M * C), 256, 0, s, dout, w->head_w, tb.g2, M, C))) return rc;
+    if ((rc = head_grad(dout, tb.hn, w->head_w, G(gr->head_w), G(gr->head_b), tb.g2, M, C, tb, s))) return rc;
     if ((rc = ln_backward(tb.g2, tb.y_last, w->hnorm_w, 1e-5f, nullptr, tb.g, nullptr, SeqMap{}, nullptr, G(gr->hnorm_w),
                           G(gr->hnorm_b), nullptr, M, C, tb, s)))
         return rc;
@@ -517,13 +570,9 @@ int train_backward(const pafuse_mixste2_weights* w, const pafuse_mixste2_weights
     lane.close();  // joins the side stream on every path
     if (rc) return rc;
     // x0 = in5 Wpatch^T + b + pos_s[j] + temb[b]                                     mixste.py:222-227
-    if ((rc = outer_sum(tb.in5, tb.g, tb.small, M, 5, C, tb, s, 0))) return rc;
-    if ((rc = launch<transpose_small_kernel>("transpose_small_kernel", blocks_for(5 * C), 256, 0, s, tb.small, G(gr->patch_w), 5, C))) return rc;
-    if ((rc = bias_grad(tb.g, G(gr->patch_b), M, C, tb, s))) return rc;
-    if ((rc = group_sum(tb.g, G(gr->pos_spatial), 0, B, F, J, C, tb, s))) return rc;
-    if ((rc = group_sum(tb.g, tb.small, 2, B, F, J, C, tb, s, 0))) return rc;  // d temb [B,C]
+    float* dtemb = tb.small;  // [B,C]
+    if ((rc = patch_grad(tb.in5, tb.g, G(gr->patch_w), G(gr->patch_b), G(gr->pos_spatial), dtemb, B, F, J, C, tb, s))) return rc;
     // temb = gelu(sincos W1^T + b1) W3^T + b3
-    float* dtemb = tb.small;
     float* dhid = tb.big2;  // [B,2C]
     if ((rc = weight_grad(dtemb, tb.hid, G(gr->tm3_w), B, C, 2 * C, tb, s))) return rc;
     if ((rc = bias_grad(dtemb, G(gr->tm3_b), B, C, tb, s))) return rc;

@@ -2,6 +2,7 @@
 
 Every wrapper checks operand shapes on the host and launches with the operands' device current."""
 import ctypes as C
+import math
 from operator import attrgetter
 
 import torch
@@ -267,6 +268,84 @@ def gelu_backward(u, dh, db=None, in_place=False):
         _lib.check(lib.pafuse_gelu_backward(_ptr(u, "u"), _ptr(dh, "dh"), _ptr(du, "du"), db.data_ptr(), M, N, ws.data_ptr(), nbytes,
                                             _stream(u)))
     return du, db
+
+
+def _rim_workspace(nbytes, dev):
+    """the workspace of a first- / last-layer unit entry, every float a NaN: a partial sum a kernel fails to write shows in the result"""
+    return torch.full((max(nbytes, 1),), 0xFF, dtype=torch.uint8, device=dev)
+
+
+def train_head_grad(dout, hn, head_w, out=None):
+    """The training step's output-head backward on its own (pafuse_train_head_grad -> head_grad): for out = hn head_w^T + b with
+    dout [M,3], hn [M,C], head_w [3,C]: d_head_w [3,C] += dout^T hn, d_head_b [3] += column sums of dout, dhn [M,C] = dout head_w.
+    out: preallocated outputs by name; the gradients are ADDED into a given 'd_head_w' / 'd_head_b' (new ones start at 0), 'dhn'
+    is overwritten.  Returns a dict of the three."""
+    lib = _lib.load()
+    M, Cc = hn.shape
+    _need(tuple(dout.shape) == (M, 3) and tuple(head_w.shape) == (3, Cc), "train_head_grad: dout [M,3], hn [M,C], head_w [3,C]")
+    dev = hn.device
+    res = {"d_head_w": _out_buf(out, "d_head_w", (3, Cc), dev, True), "d_head_b": _out_buf(out, "d_head_b", (3,), dev, True),
+           "dhn": _out_buf(out, "dhn", (M, Cc), dev)}
+    nbytes = lib.pafuse_train_head_grad_bytes(M, Cc)
+    ws = _rim_workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_train_head_grad(_ptr(dout, "dout"), _ptr(hn, "hn"), _ptr(head_w, "head_w"), res["d_head_w"].data_ptr(),
+                                              res["d_head_b"].data_ptr(), res["dhn"].data_ptr(), M, Cc, ws.data_ptr(), nbytes,
+                                              _stream(hn)))
+    return {"d_head_w": res["d_head_w"].reshape(-1)[:3 * Cc].view(3, Cc), "d_head_b": res["d_head_b"].reshape(-1)[:3],
+            "dhn": res["dhn"].reshape(-1)[:M * Cc].view(M, Cc)}
+
+
+def train_patch_grad(x2d, x3d, g, out=None):
+    """The training step's first-layer backward on its own (pafuse_train_patch_grad -> concat_inputs, patch_grad): for
+    x0 = (x2d | x3d) patch_w^T + patch_b + pos_spatial[j] + temb[b] with x2d [B,F,J,2], x3d [B,F,J,3], g = d x0 [B,F,J,C]:
+    d_patch_w [C,5] += g^T (x2d | x3d), d_patch_b [C] += column sums of g, d_pos_spatial [J,C] += sums over (b, f),
+    dtemb [B,C] = sums over (f, j).  out: preallocated outputs by name; the three gradients are ADDED into given ones (new ones
+    start at 0), 'dtemb' is overwritten.  Returns a dict of the four."""
+    lib = _lib.load()
+    B, F, J, Cc = g.shape
+    _need(tuple(x2d.shape) == (B, F, J, 2) and tuple(x3d.shape) == (B, F, J, 3), "train_patch_grad: x2d [B,F,J,2], x3d [B,F,J,3], g [B,F,J,C]")
+    dev = g.device
+    shapes = {"d_patch_w": (Cc, 5), "d_patch_b": (Cc,), "d_pos_spatial": (J, Cc), "dtemb": (B, Cc)}
+    res = {k: _out_buf(out, k, s, dev, k != "dtemb") for k, s in shapes.items()}
+    nbytes = lib.pafuse_train_patch_grad_bytes(B, F, J, Cc)
+    ws = _rim_workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_train_patch_grad(_ptr(x2d, "x2d"), _ptr(x3d, "x3d"), _ptr(g, "g"), res["d_patch_w"].data_ptr(),
+                                               res["d_patch_b"].data_ptr(), res["d_pos_spatial"].data_ptr(), res["dtemb"].data_ptr(),
+                                               B, F, J, Cc, ws.data_ptr(), nbytes, _stream(g)))
+    return {k: res[k].reshape(-1)[:math.prod(s)].view(s) for k, s in shapes.items()}
+
+
+def train_group_sum(x, mode, out=None, accumulate=True):
+    """The training step's embedding-gradient sums on their own (pafuse_train_group_sum -> group_sum): x [B,F,J,C] summed over the
+    rows of each group - mode 0: per joint -> [J,C], 1: per frame -> [F,C], 2: per sample -> [B,C].  accumulate: ADDED into `out`
+    (None: a new zero tensor), else `out` is overwritten."""
+    lib = _lib.load()
+    B, F, J, Cc = x.shape
+    _need(mode in (0, 1, 2), "train_group_sum: mode 0, 1 or 2")
+    G = (J, F, B)[mode]
+    dev = x.device
+    res = _out_buf({"out": out} if out is not None else None, "out", (G, Cc), dev, True)
+    nbytes = lib.pafuse_train_group_sum_bytes(mode, B, F, J, Cc)
+    ws = _rim_workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_train_group_sum(_ptr(x, "x"), res.data_ptr(), mode, 1 if accumulate else 0, B, F, J, Cc, ws.data_ptr(),
+                                              nbytes, _stream(x)))
+    return res.reshape(-1)[:G * Cc].view(G, Cc)
+
+
+def train_sinusoid(t, freqs, out=None):
+    """The time MLP's input as the training forward forms it (pafuse_train_sinusoid -> sinusoid): t int64 [B], freqs [C/2] ->
+    [B,C] = [sin(t freqs) | cos(t freqs)], the argument one fp32 product.  out: a preallocated [>= B*C] output."""
+    lib = _lib.load()
+    _need(t.dim() == 1 and t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and freqs.dim() == 1, "train_sinusoid: t int64 [B], freqs [C/2]")
+    B, Cc = t.shape[0], 2 * freqs.shape[0]
+    dev = t.device
+    res = _out_buf({"out": out} if out is not None else None, "out", (B, Cc), dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_train_sinusoid(_data(t), _ptr(freqs, "freqs"), res.data_ptr(), B, Cc, _stream(t)))
+    return res.reshape(-1)[:B * Cc].view(B, Cc)
 
 
 def block_forward(block_params, x, heads=8, precision="f32"):

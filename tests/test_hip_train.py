@@ -434,7 +434,8 @@ def test_attention_backward_kernel_against_fp64(L, d, temporal):
 # (N, K): one shape per tile form of the split kernel - 256 x 256 (hands), 384 x 128 (body), 224 x 224 (face), 192 x 192 (a width
 # that only that tile divides), the 128 x 128 fallback with ragged edges - at a contraction that is not a multiple of anything
 @pytest.mark.parametrize("N,K,M", [(768, 256, 4696), (1152, 384, 4696), (672, 224, 4696), (192, 576, 4696), (200, 72, 4696),
-                                   (768, 256, 389)])          # (below 4096 rows: the 128 x 128 kernel whatever the width)
+                                   (768, 256, 389),           # (below 4096 rows: the 128 x 128 kernel whatever the width)
+                                   (224, 448, 1), (768, 384, 3), (256, 512, 37)])      # the time MLP's: M = B rows, fewer than the 32-row minimum split
 @pytest.mark.parametrize("precision", ["bf16x3", "f32"])
 def test_weight_gradient_kernels_exact_on_integers_and_against_fp64(N, K, M, precision):
     from pafuse_amd import ops
