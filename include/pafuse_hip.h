@@ -726,6 +726,35 @@ int pafuse_d3dp_qsample(const float *x0, const float *noise, const int64_t *t, c
                         const double *sqrt_one_minus_alphas_cumprod, double scale, float *out, int32_t B,
                         int64_t per_sample, void *stream);
 
+/* Training draws of noise stream v1 (host statement: pafuse_amd/noise.py reference_train_draws and
+ * reference_droppath).  Philox4x32-10 under the key (seed, call), call = the model's training forward passes; g = the GLOBAL
+ * index of a clip; counter word 3 takes three values reserved at the top of its range (the sampling loop's word 3 is its
+ * draw number, an int32 counted up from 0: at most 2^31 - 1):
+ *   noise of (f, j)    counter (f*J + j, 0, g, 0xFFFFFFFF)   the three normals of the stream, as pafuse_noise_fill draws them
+ *   timestep of g      counter (0, 0, g, 0xFFFFFFFE)         t = (uint64(r0) * num_timesteps) >> 32
+ *   DropPath           counter (s, (denoiser << 16) | (k << 1) | branch, g, 0xFFFFFFFD)   keep iff (r0 + 0.5) 2^-32 < keep[k]
+ * key4_dev: four uint32 IN DEVICE MEMORY, {seed, call, first, stride}: local clip i of the call is global clip
+ * g = first + i * stride.  The library reads the words on the device and never synchronises, so it cannot check them: the
+ * CALLER must make sure that stride >= 1 and first + (B - 1) * stride < 2^32 (pafuse_amd.ops.train_key does).
+ *
+ * pafuse_d3dp_qsample_seeded: pafuse_d3dp_qsample on B clips of F x J joints with (t, noise) drawn inside the kernel; the
+ * arithmetic that consumes them is the same, so `out` equals pafuse_d3dp_qsample fed t_out and noise_out, bit for bit.
+ * sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod: num_timesteps doubles each.  t_out [B] int64; noise_out [B,F,J,3]
+ * or NULL (the normals are then never stored). */
+int pafuse_d3dp_qsample_seeded(const float *x0, const uint32_t *key4_dev, const double *sqrt_alphas_cumprod,
+                               const double *sqrt_one_minus_alphas_cumprod, double scale, int32_t num_timesteps,
+                               float *out, int64_t *t_out, float *noise_out, int32_t B, int32_t F, int32_t J,
+                               void *stream);
+
+/* The drop_path table of pafuse_mixste2_train_forward for one denoiser, float [2*depth][2][B*max(F,J)], in one launch.  Block k
+ * in execution order (even: spatial, sequences (b, f), L_k = F; odd: temporal, sequences (b, j), L_k = J), branch 0 attention /
+ * 1 MLP: column i * L_k + s holds factor[k] if the draw of sequence s of local clip i keeps the branch, else 0; the columns
+ * beyond B * L_k hold 1.  keep [2*depth] doubles (1 - rate of block k) and factor [2*depth] floats (1 / keep as the caller's
+ * framework rounds it) in device memory: the kernel compares and selects.  denoiser < 2^16 (the part's index: the parts draw
+ * independently), depth <= 2^14, out_floats = the floats `out` holds (PAFUSE_E_ARG if fewer than the table's). */
+int pafuse_train_droppath_fill(const uint32_t *key4_dev, int32_t denoiser, int32_t depth, int32_t F, int32_t J, int32_t B,
+                               const double *keep, const float *factor, float *out, int64_t out_floats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,9 @@ SIGNATURES = {
                                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pafuse_d3dp_qsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                       C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "pafuse_d3dp_qsample_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "pafuse_train_droppath_fill": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
 }
 
 # matrix-product modes (include/pafuse_hip.h: pafuse_mixste2_weights.operand_bf16) and the precision names they go by: the one table

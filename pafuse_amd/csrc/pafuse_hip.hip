@@ -2374,8 +2374,40 @@ int pafuse_d3dp_qsample(const float* x0, const float* noise, const int64_t* t, c
     StreamDevice on_stream_device(stream);
     if (!x0 || !noise || !t || !sqrt_alphas_cumprod || !sqrt_one_minus_alphas_cumprod || !out || B <= 0 || per_sample <= 0)
         return fail(PAFUSE_E_ARG, "d3dp_qsample: bad argument");
-    const int64_t n = (int64_t)B * per_sample;
-    return launch<qsample_kernel>("qsample_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, x0, noise, t, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, scale, out, per_sample, n);
+    QsampleParams q{};
+    q.x0 = x0, q.noise = noise, q.t = t, q.sqrt_acp = sqrt_alphas_cumprod, q.sqrt_1m_acp = sqrt_one_minus_alphas_cumprod;
+    q.scale = scale, q.out = out, q.per_sample = per_sample, q.n = (int64_t)B * per_sample;
+    return launch<qsample_kernel>("qsample_kernel", blocks_for(q.n), 256, 0, (hipStream_t)stream, q);
+}
+
+int pafuse_d3dp_qsample_seeded(const float* x0, const uint32_t* key4_dev, const double* sqrt_alphas_cumprod,
+                               const double* sqrt_one_minus_alphas_cumprod, double scale, int32_t num_timesteps, float* out,
+                               int64_t* t_out, float* noise_out, int32_t B, int32_t F, int32_t J, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!x0 || !key4_dev || !sqrt_alphas_cumprod || !sqrt_one_minus_alphas_cumprod || !out || !t_out)
+        return fail(PAFUSE_E_ARG, "d3dp_qsample_seeded: null pointer");
+    if (num_timesteps <= 0 || B <= 0 || F <= 0 || J <= 0)
+        return fail(PAFUSE_E_ARG, "d3dp_qsample_seeded: bad size (num_timesteps=%d B=%d F=%d J=%d)", num_timesteps, B, F, J);
+    const int64_t threads = (int64_t)B * F * J;
+    if ((int64_t)F * J > 0xffffffffLL || (threads + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "d3dp_qsample_seeded: size out of range");
+    QsampleParams q{};
+    q.x0 = x0, q.key4 = key4_dev, q.num_timesteps = (uint32_t)num_timesteps, q.t_out = t_out, q.noise_out = noise_out;
+    q.sqrt_acp = sqrt_alphas_cumprod, q.sqrt_1m_acp = sqrt_one_minus_alphas_cumprod;
+    q.scale = scale, q.out = out, q.per_sample = (int64_t)F * J * 3, q.n = threads * 3;
+    return launch<qsample_seeded_kernel>("qsample_seeded_kernel", blocks_for(threads), 256, 0, (hipStream_t)stream, q);
+}
+
+int pafuse_train_droppath_fill(const uint32_t* key4_dev, int32_t denoiser, int32_t depth, int32_t F, int32_t J, int32_t B,
+                               const double* keep, const float* factor, float* out, int64_t out_floats, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!key4_dev || !keep || !factor || !out) return fail(PAFUSE_E_ARG, "train_droppath_fill: null pointer");
+    if (denoiser < 0 || denoiser >= (1 << 16) || depth <= 0 || depth > (1 << 14) || B <= 0 || F <= 0 || J <= 0)
+        return fail(PAFUSE_E_ARG, "train_droppath_fill: bad argument (denoiser=%d depth=%d B=%d F=%d J=%d)", denoiser, depth, B, F, J);
+    const int64_t n = 4 * (int64_t)depth * B * (F > J ? F : J);
+    if ((int64_t)F * J > 0xffffffffLL || (n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "train_droppath_fill: size out of range");
+    if (out_floats < n) return fail(PAFUSE_E_ARG, "train_droppath_fill: out holds %lld floats, the table has %lld", (long long)out_floats, (long long)n);
+    return launch<droppath_fill_kernel>("droppath_fill_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, key4_dev, (uint32_t)denoiser, depth, F, J, B,
+                                        keep, factor, out);
 }
 
 }  // extern "C"

@@ -1392,17 +1392,91 @@ __global__ void __launch_bounds__(256) transpose_small_kernel(const float* in, f
 
 // D3DP.prepare_diffusion_concat + q_sample (common/diffusionpose.py:319-326,358-374): per sample b
 //   x = clamp(sqrt_acp[t_b] * (x0 * scale) + sqrt_1m_acp[t_b] * noise, +-1.1 scale) / scale, fp64 buffers, cast to fp32
-__global__ void __launch_bounds__(256) qsample_kernel(const float* x0, const float* noise, const int64_t* t,
-                                                      const double* sqrt_acp, const double* sqrt_1m_acp, double scale,
-                                                      float* out, int64_t per_sample, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int64_t tb = t[i / per_sample];
-    const float xs = __fmul_rn(x0[i], (float)scale);  // fp32 tensor * python scalar stays fp32
-    double v = __dadd_rn(__dmul_rn(sqrt_acp[tb], (double)xs), __dmul_rn(sqrt_1m_acp[tb], (double)noise[i]));
-    const double lim = 1.1 * scale;
-    v = v < -lim ? -lim : (v > lim ? lim : v);
-    out[i] = (float)(v / scale);
+//
+// Training draws of noise stream v1 (host statement: pafuse_amd/noise.py reference_train_draws /
+// reference_droppath).  Key (seed, call) with call = the model's training forward passes; g = the clip's GLOBAL index.  Counter
+// word 3 takes three values reserved at the top of its range - the sampling loop's word 3 is its draw number, an int32 that
+// pafuse_d3dp_sample_seeded counts up from 0 to at most nsteps <= 2^31 - 1, so the two families cannot meet:
+//   0xFFFFFFFF  noise of (f, j):   counter (f*J + j, 0, g, .)  -> the three normals of noise_normals
+//   0xFFFFFFFE  timestep of clip:  counter (0, 0, g, .)        -> t = (uint64(r0) * num_timesteps) >> 32
+//   0xFFFFFFFD  DropPath:          counter (s, (denoiser << 16) | (k << 1) | branch, g, .) -> keep iff u(r0) < keep_k
+// key4 = {seed, call, first, stride} in device memory (ops.train_key): local clip i of the call is global clip first + i*stride
+// (modulo 2^32 like the counter; the Python layer refuses a map that would wrap).
+constexpr uint32_t TRAIN_K_NOISE = 0xFFFFFFFFu, TRAIN_K_TIMESTEP = 0xFFFFFFFEu, TRAIN_K_DROPPATH = 0xFFFFFFFDu;
+
+struct QsampleParams {
+    const float* x0;
+    const float* noise;    // [B, per_sample]                                   (qsample_kernel)
+    const int64_t* t;      // [B]                                               (qsample_kernel)
+    const uint32_t* key4;  // {seed, call, first, stride}                       (qsample_seeded_kernel) ...
+    uint32_t num_timesteps;
+    int64_t* t_out;        // ... [B]: the timestep it drew for every clip
+    float* noise_out;      // ... [B, per_sample] or null: the normals it drew
+    const double *sqrt_acp, *sqrt_1m_acp;
+    double scale;
+    float* out;
+    int64_t per_sample, n;  // floats per clip (F*J*3 when seeded), floats in all
+};
+
+// SEEDED: one thread per (clip, f, j) draws the clip's timestep and its own three normals from the stream instead of reading
+// p.t / p.noise; everything that consumes them is the same
+template <bool SEEDED>
+__device__ __forceinline__ void qsample_body(const QsampleParams& p) {
+    constexpr int W = SEEDED ? 3 : 1;  // values per thread
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * W;
+    if (i >= p.n) return;
+    const int64_t b = i / p.per_sample;
+    int64_t tb;
+    float drawn[3];
+    const float* nz = drawn;
+    if constexpr (SEEDED) {
+        const uint32_t g = p.key4[2] + (uint32_t)b * p.key4[3];
+        uint32_t c[4] = {0u, 0u, g, TRAIN_K_TIMESTEP};
+        philox4x32_10(c, p.key4[0], p.key4[1]);
+        tb = (int64_t)(((uint64_t)c[0] * (uint64_t)p.num_timesteps) >> 32);
+        const uint32_t at[4] = {p.key4[0], p.key4[1], g, 0u};  // noise_normals adds its (b, p) to words 2, 3: the clip sits in word 2
+        noise_normals(at, TRAIN_K_NOISE, 0u, 0u, (uint32_t)((i - b * p.per_sample) / 3), drawn);
+        if (i == b * p.per_sample) p.t_out[b] = tb;
+        if (p.noise_out) p.noise_out[i] = drawn[0], p.noise_out[i + 1] = drawn[1], p.noise_out[i + 2] = drawn[2];
+    } else {
+        tb = p.t[b];
+        nz = p.noise + i;
+    }
+    const double lim = 1.1 * p.scale;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const float xs = __fmul_rn(p.x0[i + k], (float)p.scale);  // fp32 tensor * python scalar stays fp32
+        double v = __dadd_rn(__dmul_rn(p.sqrt_acp[tb], (double)xs), __dmul_rn(p.sqrt_1m_acp[tb], (double)nz[k]));
+        v = v < -lim ? -lim : (v > lim ? lim : v);
+        p.out[i + k] = (float)(v / p.scale);
+    }
+}
+
+__global__ void __launch_bounds__(256) qsample_kernel(const QsampleParams p) { qsample_body<false>(p); }
+
+__global__ void __launch_bounds__(256) qsample_seeded_kernel(const QsampleParams p) { qsample_body<true>(p); }
+
+// One denoiser's DropPath table [2*depth][2][smax], smax = B * max(F, J), in one launch: one thread per element.  Row (k, br),
+// column c: sequence s = c % L_k of local clip c / L_k with L_k = F (k even: spatial, rows (b f)) or J (k odd: temporal, rows
+// (b n)); columns beyond B * L_k are 1 (what torch.ones leaves there).  keep [2*depth] doubles and factor [2*depth] floats come
+// from the host: the kernel compares and selects, nothing else.
+__global__ void __launch_bounds__(256) droppath_fill_kernel(const uint32_t* __restrict__ key4, uint32_t denoiser, int depth, int F, int J, int B,
+                                                            const double* __restrict__ keep, const float* __restrict__ factor,
+                                                            float* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t smax = (int64_t)B * (F > J ? F : J);
+    if (e >= 4 * (int64_t)depth * smax) return;
+    const int64_t c = e % smax;
+    const uint32_t row = (uint32_t)(e / smax), k = row >> 1;  // row = (k << 1) | branch
+    const int L = (k & 1u) ? J : F;
+    float v = 1.0f;
+    if (c < (int64_t)B * L) {
+        const uint32_t g = key4[2] + (uint32_t)(c / L) * key4[3];
+        uint32_t w[4] = {(uint32_t)(c % L), (denoiser << 16) | row, g, TRAIN_K_DROPPATH};
+        philox4x32_10(w, key4[0], key4[1]);
+        v = noise_uniform(w[0]) < keep[k] ? factor[k] : 0.0f;
+    }
+    out[e] = v;
 }
 
 }  // namespace pafuse

@@ -137,6 +137,10 @@ class D3DP(nn.Module):
         self._noise_seed = 0           # "device" source: key word 0 of the stream (the `noise_seed` property)
         self.noise_call = 0            # "device" source: key word 1 - the public sampling calls since noise_seed was set
         self._hold_noise_call = False  # several model calls that make up ONE logical call (pafuse_amd.parallel)
+        self._train_draws = "torch"    # where a training forward's (t, noise, DropPath) come from, see the `train_draws` property
+        self.train_call = 0            # "device" training draws: key word 1 - the training forwards since noise_seed was set
+        self.train_clips = (0, 1)      # "device" training draws: (first, stride) - local clip i is clip first + i * stride of the
+        #                                GLOBAL batch (h3wb.train_epoch sets (rank, world) from the generator's shard)
         self.train_draw_fn = None      # callable(sample) -> (t [1] int64, noise [F,J,3]) (tests, training path)
         self.proposal_shard = None     # (lo, hi): this rank's slice of the hypothesis axis (pafuse_amd.parallel)
         self.aux_streams = None        # explicit list of torch.cuda.Stream the parts are spread over; None = two
@@ -199,16 +203,47 @@ class D3DP(nn.Module):
         self._noise_fn = fn
 
     @property
+    def train_draws(self):
+        """Where the random numbers of a TRAINING forward come from (deliberately not `noise`, which stays the eval loop's):
+        'torch'  (the default) per clip one torch.randint and one torch.randn - or train_draw_fn -, per block and branch one
+                 bernoulli_ - or drop_fn: the reference's draws, in an order that follows the layout of the batch;
+        'device' noise stream v1 (pafuse_amd/noise.py): ONE kernel draws every clip's timestep and noise
+                 and applies q_sample (no noise tensor is kept unless a caller of prepare_targets asks for it), ONE kernel per
+                 denoiser fills its DropPath table.  The draws of a clip are a pure function of (noise_seed, train_call, its
+                 index in the global batch - see train_clips), whatever the number of ranks.  NOT the values torch draws."""
+        return self._train_draws
+
+    @train_draws.setter
+    def train_draws(self, value):
+        if value not in self.NOISE_SOURCES:
+            raise ValueError(f"train_draws must be one of {list(self.NOISE_SOURCES)}, got {value!r}")
+        if value == "device" and self.train_draw_fn is not None:
+            raise ValueError("train_draws = 'device' draws inside the kernels: it cannot be combined with train_draw_fn")
+        self._train_draws = value
+
+    @property
+    def train_draw_fn(self):
+        return self._train_draw_fn
+
+    @train_draw_fn.setter
+    def train_draw_fn(self, fn):
+        if fn is not None and getattr(self, "_train_draws", "torch") == "device":
+            raise ValueError("train_draw_fn injects draws into the 'torch' training draws: it cannot be combined with "
+                             "train_draws = 'device'")
+        self._train_draw_fn = fn
+
+    @property
     def noise_seed(self):
-        """'device' noise source: the seed of the stream, a value in [0, 2^32).  Setting it restarts noise_call at 0, so a run
-        that sets the seed and makes the same calls sees the same hypotheses."""
+        """The seed of noise stream v1 - of the 'device' noise source and of the 'device' training draws -, a value in
+        [0, 2^32).  Setting it restarts noise_call and train_call at 0, so a run that sets the seed and makes the same calls
+        sees the same hypotheses / the same training draws."""
         return self._noise_seed
 
     @noise_seed.setter
     def noise_seed(self, value):
         if isinstance(value, bool) or int(value) != value or not 0 <= int(value) < 2 ** 32:
             raise ValueError(f"noise_seed must be an integer in [0, 2^32), got {value!r}")
-        self._noise_seed, self.noise_call = int(value), 0
+        self._noise_seed, self.noise_call, self.train_call = int(value), 0, 0
 
     def advance_noise_call(self):
         """One public sampling call is over ('device' noise source): the next one draws under the next `call` word.  The calls
@@ -485,8 +520,40 @@ class D3DP(nn.Module):
         if not self.is_train:
             return self.ddim_sample(input_2d, input_3d, input_2d_flip=input_2d_flip, flip=self.flip)
         self._training_precision()
+        if self._train_draws == "device":
+            return self._forward_train_seeded(input_2d, input_3d)
         x_poses, _noises, t = self.prepare_targets(input_3d)
         return self.pred_parts(input_2d, x_poses, t.squeeze(-1))
+
+    def _train_key(self, B, dev):
+        """the 16 bytes {noise_seed, train_call, first, stride} of the running training forward (ops.train_key checks the map)"""
+        from .ops import train_key
+        if self.train_draw_fn is not None:
+            raise ValueError("train_draws = 'device' draws inside the kernels: it cannot be combined with train_draw_fn")
+        first, stride = self.train_clips
+        return train_key(self._noise_seed, self.train_call, first, stride, dev, clips=B)
+
+    def _forward_train_seeded(self, input_2d, input_3d):
+        """forward in train mode with train_draws = 'device': one key for the step - q_sample draws under it, every denoiser
+        fills its DropPath table under it and its own index -, then the next forward draws under train_call + 1."""
+        self._check_targets(input_3d)
+        key4 = self._train_key(input_3d.shape[0], input_3d.device)
+        x_poses, _, t = self._prepare_targets_seeded(input_3d, key4, want_noise=False)
+        models = list(self.denoisers().values())
+        for d, m in enumerate(models):
+            m.drop_key = (key4, d)
+        try:
+            out = self.pred_parts(input_2d, x_poses, t.squeeze(-1))
+        finally:
+            for m in models:
+                m.drop_key = None
+        if self.part_based and key4.is_cuda:     # the parts read the key on their side streams
+            for s in self._aux_for(input_3d.device):
+                key4.record_stream(s)
+        if self.train_call + 1 >= 2 ** 32:
+            raise _lib.PafuseError("train_call ran out of its 32 bits: set a new noise_seed")
+        self.train_call += 1
+        return out
 
     # ------------------------------------------------------------------------------------------------ training
     def prepare_for_ddp(self):
@@ -527,11 +594,9 @@ class D3DP(nn.Module):
     def prepare_targets(self, targets):
         """common/diffusionpose.py:358-388: per sample one timestep and one noise draw (in that order, on the
         device), then q_sample + clamp in the fp64 of the schedule buffers (pafuse_d3dp_qsample), cast to fp32."""
-        if not targets.is_cuda:
-            raise _lib.PafuseError("D3DP runs on the HIP device only (no CPU fallback)")
-        if tuple(targets.shape[1:]) != (self.frames, self.num_kps, 3):
-            raise ValueError(f"D3DP expects 3-D targets of shape [B, {self.frames}, {self.num_kps}, 3], got "
-                             f"{tuple(targets.shape)}")
+        self._check_targets(targets)
+        if self._train_draws == "device":       # the draws of the NEXT training forward (train_call advances in forward only)
+            return self._prepare_targets_seeded(targets, self._train_key(targets.shape[0], targets.device), want_noise=True)
         lib = _lib.load()
         dev, B = targets.device, targets.shape[0]
         ts, noises = [], []
@@ -551,6 +616,23 @@ class D3DP(nn.Module):
                                            self.sqrt_one_minus_alphas_cumprod.data_ptr(), float(self.scale),
                                            out.data_ptr(), B, x0[0].numel(), torch.cuda.current_stream(dev).cuda_stream))
         return out, noise, t
+
+    def _check_targets(self, targets):
+        if not targets.is_cuda:
+            raise _lib.PafuseError("D3DP runs on the HIP device only (no CPU fallback)")
+        if tuple(targets.shape[1:]) != (self.frames, self.num_kps, 3):
+            raise ValueError(f"D3DP expects 3-D targets of shape [B, {self.frames}, {self.num_kps}, 3], got "
+                             f"{tuple(targets.shape)}")
+
+    def _prepare_targets_seeded(self, targets, key4, want_noise):
+        """prepare_targets with train_draws = 'device': ONE launch draws every clip's (t, noise) from the stream and applies
+        q_sample; -> (x_t, noise or None, t [B,1])."""
+        from .ops import qsample_seeded
+        if targets.shape[0] == 0:
+            raise ValueError("train_draws = 'device' needs at least one clip")
+        x_t, t, noise = qsample_seeded(targets.contiguous().float(), key4, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod,
+                                       float(self.scale), self.num_timesteps, want_noise=want_noise)
+        return x_t, noise, t.unsqueeze(-1)
 
     def split_data(self, input_2d, x_poses):
         """common/diffusionpose.py:328-335"""

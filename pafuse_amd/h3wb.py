@@ -368,6 +368,10 @@ def train_epoch(model, optimizer, generator, dataset, device, wb_loss=False, log
     if weighted_loss:
         J = dataset.skeleton().num_joints() if hasattr(dataset, "skeleton") else 134
         weights = torch.tensor(list(WEIGHTED_LOSS_HEAD) + [1.0] * (J - len(WEIGHTED_LOSS_HEAD)), device=device)
+    module = model.module if hasattr(model, "module") else model
+    if getattr(module, "train_draws", "torch") == "device":
+        # the rank's clips are clips rank, rank + world, ... of the global batch: their draws follow the GLOBAL index
+        module.train_clips = tuple(getattr(generator, "shard", None) or (0, 1))
     for it, (_, batch_3d, batch_2d) in enumerate(generator.next_epoch()):
         inputs_3d = torch.from_numpy(batch_3d.astype("float32")).to(device)
         inputs_2d = torch.from_numpy(batch_2d.astype("float32")).to(device)
@@ -400,7 +404,10 @@ def save_state(model, optimizer, epoch_no, lr, foldername, random_state=None, ta
     'model_pos' keys carry a ``module.`` prefix and its loaders expect one (:252 strict, :713-714).  With
     ``reference_layout`` (default) the file written here has exactly those keys whether or not `model` is wrapped
     (DataParallel / DistributedDataParallel), so checkpoints are interchangeable with the reference in both directions
-    (``harness.load_checkpoint`` strips the prefix); ``reference_layout=False`` writes bare keys."""
+    (``harness.load_checkpoint`` strips the prefix); ``reference_layout=False`` writes bare keys.
+
+    A model that draws on the device (``train_draws = "device"``) adds ``train_stream: {"seed", "call"}``, from which
+    ``harness.load_checkpoint`` lets a resumed run continue the sequence; the file of a default run keeps its exact key set."""
     import torch
     module = model.module if hasattr(model, "module") else model
     sd = module.state_dict()
@@ -409,6 +416,8 @@ def save_state(model, optimizer, epoch_no, lr, foldername, random_state=None, ta
     params = {"optimizer": optimizer.state_dict(), "epoch": epoch_no, "lr": lr, "model_pos": sd}
     if random_state is not None:
         params["random_state"] = random_state
+    if getattr(module, "train_draws", "torch") == "device":
+        params["train_stream"] = {"seed": int(module.noise_seed), "call": int(module.train_call)}
     fname = f"{foldername}/{tag or f'epoch_{epoch_no}'}.bin"
     torch.save(params, fname)
     return fname

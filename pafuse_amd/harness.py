@@ -204,9 +204,15 @@ def read_checkpoint(path):
 
 def load_checkpoint(model, checkpoint):
     """Accept what the reference saves (common/logging.py:83-115): a dict with 'model_pos', DataParallel
-    ``module.``-prefixed keys, or a bare state dict - or the path of such a file (:func:`read_checkpoint`)."""
+    ``module.``-prefixed keys, or a bare state dict - or the path of such a file (:func:`read_checkpoint`).
+    A ``train_stream`` entry (written by :func:`pafuse_amd.h3wb.save_state` for ``train_draws = "device"``) puts a training
+    model back where the saved run stood in noise stream v1: the next forward draws what the uninterrupted run would have."""
     if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, "__fspath__"):
         checkpoint = read_checkpoint(checkpoint)
+    stream = checkpoint.get("train_stream") if isinstance(checkpoint, dict) else None
+    if stream is not None and getattr(model, "is_train", False) and hasattr(model, "train_call"):
+        model.noise_seed = int(stream["seed"])
+        model.train_call = int(stream["call"])
     sd = checkpoint.get("model_pos", checkpoint) if isinstance(checkpoint, dict) else checkpoint
     sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
     return model.load_state_dict(sd)

@@ -100,6 +100,9 @@ class MixSTE2(nn.Module):
         self.split_generation = {}     # device index -> how many times the split images were (re)made (graph caches key on it)
         self._param_names = tuple(n for n, _ in self.named_parameters())
         self.drop_fn = None            # tests: callable(block, branch, nseq, rate) -> DropPath factors [nseq] or None
+        self.drop_key = None           # (key4, denoiser index) of the running training forward, set by a D3DP with train_draws =
+        #                                "device": the DropPath table comes from noise stream v1 in ONE launch (ops.droppath_fill)
+        self._drop_tables = {}         # device index -> (drop_path_rate, depth, keep float64 [2 depth], factor float32 [2 depth])
         self.operand_bf16 = MODE_F32   # matrix-product mode of the linear layers (_lib.PRECISIONS, include/pafuse_hip.h): 'f32' fp32 MFMA,
         #                                'bf16x3' split precision (the D3DP default), 'bf16x3_images' the same products on the image
         #                                pipeline (inference; where its kernels do not exist - training, the single-model variant -
@@ -251,6 +254,8 @@ class MixSTE2(nn.Module):
         blocks draw them: execution order STE0 (attn, mlp), TTE0, STE1, ...; one Bernoulli(keep) per sequence of the
         block's batch axis ((b f) spatial, (b n) temporal); rate 0 is nn.Identity and draws nothing
         (common/mixste.py:100,113-116,187; timm.layers.drop_path with scale_by_keep=True)."""
+        if self.drop_key is not None:
+            return self._drop_path_factors_seeded(B, device)
         rates = [x.item() for x in torch.linspace(0, self.drop_path_rate, self.block_depth)]
         if not self.training or all(r <= 0.0 for r in rates):
             return None
@@ -271,6 +276,34 @@ class MixSTE2(nn.Module):
                     if m is not None:
                         out[k, branch, :nseq] = m.reshape(nseq).to(device=device, dtype=torch.float32)
         return out
+
+    def drop_path_tables(self, device):
+        """(rates, keep float64 [2 depth], factor float32 [2 depth]) of the seeded DropPath draws, made on the host as the torch
+        path makes them - rate = linspace(0, drop_path_rate, depth)[i].item(), keep = 1.0 - rate in double, factor =
+        torch.ones(()).div_(keep) - once per module and device; block k of the execution order belongs to layer k // 2."""
+        device = torch.device(device)
+        hit = self._drop_tables.get(device.index)
+        if hit is None or hit[0] != (self.drop_path_rate, self.block_depth):
+            rates = [x.item() for x in torch.linspace(0, self.drop_path_rate, self.block_depth)]
+            keep = [1.0 - r if r > 0.0 else 1.0 for r in rates]
+            factor = [float(torch.ones(()).div_(k)) if k > 0.0 else 1.0 for k in keep]       # keep = 0: nothing is ever kept
+            keep2 = torch.tensor([k for k in keep for _ in range(2)], dtype=torch.float64)
+            factor2 = torch.tensor([f for f in factor for _ in range(2)], dtype=torch.float32)
+            hit = self._drop_tables[device.index] = ((self.drop_path_rate, self.block_depth), rates, keep2.to(device), factor2.to(device))
+        return hit[1:]
+
+    def _drop_path_factors_seeded(self, B, device):
+        """drop_path_factors from noise stream v1: the same table, in one launch, a pure function of
+        (seed, call, denoiser, global clip index)."""
+        from . import ops
+        if self.drop_fn is not None:
+            raise ValueError("drop_fn injects DropPath factors into the torch draws: it cannot be combined with a stream key "
+                             "(D3DP.train_draws = 'device')")
+        key4, denoiser = self.drop_key
+        rates, keep, factor = self.drop_path_tables(device)
+        if not self.training or all(r <= 0.0 for r in rates):
+            return None
+        return ops.droppath_fill(key4, denoiser, self.block_depth, self.num_frame, self.num_joints, B, keep, factor)
 
     def _forward_train(self, x_2d, x_3d, t):
         B, _, F, J = self._check_inputs(x_2d, x_3d, t, 4)

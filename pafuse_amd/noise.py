@@ -13,13 +13,36 @@ frame f and joint j:
 evaluated in fp64 and rounded once to fp32.  A value is a pure function of (seed, call, k, b, p, f, j): the sharding, the
 hypothesis chunk, the clip chunk and the launch schedule cannot change it.
 
+The training draws (``train_draws = "device"`` of pafuse_amd.D3DP, qsample_seeded_kernel and
+droppath_fill_kernel in csrc/train_kernels.hpp) extend the stream without changing it.  The key is (seed, call) with call = the
+model's training forward passes (D3DP.train_call, a counter of its own); g is the GLOBAL index of a clip - its position in the
+global batch, not in a rank's slice.  Counter word 3 takes three values reserved at the top of its range; the sampling loop's
+word 3 is its draw number k, which pafuse_d3dp_sample_seeded counts in an int32 from 0 to at most its number of steps
+(<= 2^31 - 1, and <= num_timesteps from pafuse_amd.D3DP), so the two families never share a counter:
+
+  noise of (f, j)    counter (f*J + j, 0, g, K_NOISE = 0xFFFFFFFF)     the three normals above: reference_draw with k = K_NOISE,
+                                                                       b = g, p = 0
+  timestep of g      counter (0, 0, g, K_TIMESTEP = 0xFFFFFFFE)        t = (uint64(r0) * num_timesteps) >> 32: integer arithmetic,
+                                                                       0 <= t < num_timesteps, each value's probability within
+                                                                       2^-32 of 1 / num_timesteps
+  DropPath           counter (s, (d << 16) | (k << 1) | br, g, K_DROPPATH = 0xFFFFFFFD)
+                                                                       keep iff u(r0) < keep_k in fp64; the factor is factor_k
+                                                                       if kept, else 0
+for block k in [0, 2 depth) in execution order (STE0, TTE0, STE1, ...), branch br (0 attention, 1 MLP), denoiser d (its index
+in D3DP.denoisers(); d < 2^16, depth <= 2^14) and sequence s of the block's batch axis: the frame f for even k (spatial, rows
+(b f)), the joint j for odd k (temporal, rows (b n)).  keep_k = 1.0 - rate as a double with rate =
+torch.linspace(0, drop_path_rate, depth)[k // 2].item(), factor_k = the fp32 value torch.ones(()).div_(keep_k) gives: both are
+made on the host and handed to the kernel, which compares and selects.
+
 This module is test infrastructure and the documentation of the stream.  The product path never calls it.
 """
 import numpy as np
 
-__all__ = ["philox4x32_10", "uniform", "sincos_turns", "reference_draw", "STREAM_VERSION"]
+__all__ = ["philox4x32_10", "uniform", "sincos_turns", "reference_draw", "reference_train_draws", "reference_droppath",
+           "K_NOISE", "K_TIMESTEP", "K_DROPPATH", "STREAM_VERSION"]
 
 STREAM_VERSION = 1
+K_NOISE, K_TIMESTEP, K_DROPPATH = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD     # reserved values of counter word 3 (training draws)
 PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57      # round multipliers
 PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85      # Weyl increments of the key
 
@@ -70,10 +93,56 @@ def reference_draw(seed, call, k, b0, p0, B, P, F, J):
     fj = np.arange(F * J, dtype=np.uint32).reshape(1, 1, F * J)
     p = (p0 + np.arange(P, dtype=np.uint32)).reshape(1, P, 1)
     b = (b0 + np.arange(B, dtype=np.uint32)).reshape(B, 1, 1)
-    r0, r1, r2, r3 = philox4x32_10((fj, p, b, np.uint32(k)), (np.uint32(seed), np.uint32(call)))
+    out = _normals(philox4x32_10((fj, p, b, np.uint32(k)), (np.uint32(seed), np.uint32(call))))
+    return out.reshape(B, P, F, J, 3)
+
+
+def _normals(words):
+    """the three normals of four Philox words (arrays of one shape) -> float32 [..., 3]"""
+    r0, r1, r2, r3 = words
     rad_xy = np.sqrt(-2.0 * np.log(uniform(r0)))
     rad_z = np.sqrt(-2.0 * np.log(uniform(r2)))
     s1, c1 = sincos_turns(r1)
     _, c3 = sincos_turns(r3)
-    out = np.stack([rad_xy * c1, rad_xy * s1, rad_z * c3], axis=-1).astype(np.float32)
-    return out.reshape(B, P, F, J, 3)
+    return np.stack([rad_xy * c1, rad_xy * s1, rad_z * c3], axis=-1).astype(np.float32)
+
+
+def _clip_indices(seed, call, clips, **more):
+    clips = [int(g) for g in clips]
+    for name, v in [("seed", seed), ("call", call)] + [("clip", g) for g in clips] + list(more.items()):
+        if not 0 <= int(v) < 2 ** 32:
+            raise ValueError(f"noise stream v1: {name} = {v} is not a uint32")
+    return np.array(clips, dtype=np.uint32)
+
+
+def reference_train_draws(seed, call, clips, F, J, num_timesteps):
+    """The (t, noise) draws of one training forward for the clips with the global indices `clips` (an explicit list: a
+    rank's clips are strided) -> (t int64 [n], noise float32 [n, F, J, 3]).  1 <= num_timesteps <= 2^32."""
+    g = _clip_indices(seed, call, clips, **{"F * J": F * J, "num_timesteps - 1": num_timesteps - 1})
+    key = (np.uint32(seed), np.uint32(call))
+    r0 = philox4x32_10((np.uint32(0), np.uint32(0), g, np.uint32(K_TIMESTEP)), key)[0]
+    t = ((r0.astype(np.uint64) * np.uint64(num_timesteps)) >> np.uint64(32)).astype(np.int64)     # < 2^64: no overflow
+    fj = np.arange(F * J, dtype=np.uint32).reshape(1, F * J)
+    noise = _normals(philox4x32_10((fj, np.uint32(0), g.reshape(-1, 1), np.uint32(K_NOISE)), key))
+    return t, noise.reshape(len(g), F, J, 3)
+
+
+def reference_droppath(seed, call, clips, d, F, J, keep, factor):
+    """The DropPath table of denoiser d for one training forward on the clips `clips` -> float32 [2 depth, 2, n max(F, J)]:
+    row (k, br), column i * L_k + s = sequence s of the i-th clip (L_k = F for even k, J for odd k); the columns beyond
+    n * L_k hold 1.  keep: 2 depth doubles, factor: 2 depth float32 values (see the module text)."""
+    g = _clip_indices(seed, call, clips, **{"F * J": F * J})
+    keep, factor = np.asarray(keep, dtype=np.float64), np.asarray(factor, dtype=np.float32)
+    rows = len(keep)
+    if rows % 2 or rows != len(factor) or not 0 <= int(d) < 2 ** 16 or rows > 2 ** 15:
+        raise ValueError("noise stream v1: keep / factor hold 2 * depth <= 2^15 values each, d < 2^16")
+    n = len(g)
+    out = np.ones((rows, 2, n * max(F, J)), dtype=np.float32)
+    for k in range(rows):
+        L = J if k % 2 else F
+        s = np.arange(L, dtype=np.uint32).reshape(1, L)
+        for br in range(2):
+            word1 = np.uint32((int(d) << 16) | (k << 1) | br)
+            r0 = philox4x32_10((s, word1, g.reshape(-1, 1), np.uint32(K_DROPPATH)), (np.uint32(seed), np.uint32(call)))[0]
+            out[k, br, :n * L] = np.where(uniform(r0) < keep[k], factor[k], np.float32(0)).reshape(-1)
+    return out

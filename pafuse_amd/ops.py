@@ -796,6 +796,74 @@ def noise_fill(key, draw, B, P, F, J, out=None):
     return out
 
 
+# --------------------------------------------------------------------- training draws of noise stream v1
+def train_key(seed, call, first=0, stride=1, device="cuda", clips=None):
+    """The 16-byte device buffer {seed, call, first, stride} the training-draw kernels read: noise_key's layout with the last
+    two words saying where the call's clips sit in the GLOBAL batch - local clip i is global clip first + i * stride.  The
+    library reads the words on the device and cannot check them, so the checks live here: stride >= 1 and, with `clips`
+    (the number of clips of the call), first + (clips - 1) * stride < 2^32.  On a HIP device the words travel through pinned
+    memory without a synchronisation (the training step makes one key per forward)."""
+    import numpy as np
+    for name, v in (("seed", seed), ("call", call), ("first", first), ("stride", stride)):
+        _need(not isinstance(v, bool) and int(v) == v and 0 <= int(v) < 2 ** 32, f"train_key: {name} = {v!r} is not an integer in [0, 2^32)")
+    _need(int(stride) >= 1, "train_key: stride = 0 would give every clip of the call the same draws")
+    if clips is not None:
+        _need(int(clips) >= 1 and int(first) + (int(clips) - 1) * int(stride) < 2 ** 32,
+              f"train_key: clips {first} + i * {stride}, i < {clips}, leave the 32 bits of the global clip index")
+    words = torch.from_numpy(np.array([int(seed), int(call), int(first), int(stride)], dtype=np.uint32).view(np.int32))
+    if torch.device(device).type == "cuda":
+        return words.pin_memory().to(device, non_blocking=True)
+    return words.to(device)
+
+
+def _need_key(who, key):
+    _need(torch.is_tensor(key) and key.is_cuda and key.dtype == torch.int32 and key.numel() == 4 and key.is_contiguous(),
+          f"{who}: key must be the int32[4] device tensor of train_key (no CPU fallback)")
+
+
+def qsample_seeded(x0, key4, sqrt_ac, sqrt_1mac, scale, num_timesteps, want_noise=False):
+    """pafuse_d3dp_qsample_seeded: draw (t, noise) for the clips of x0 [B,F,J,3] from the stream (key4 = train_key(...)) and
+    apply q_sample + clamp + / scale in the fp64 of the schedule tables -> (x_t float32 [B,F,J,3], t int64 [B], noise
+    float32 [B,F,J,3] or None).  Without want_noise the normals are never stored."""
+    lib = _lib.load()
+    _need_key("qsample_seeded", key4)
+    _need(x0.dim() == 4 and x0.shape[-1] == 3 and x0.shape[0] > 0 and x0.is_cuda and x0.device == key4.device and x0.dtype == torch.float32
+          and x0.is_contiguous(), f"qsample_seeded: x0 must be a contiguous float32 [B,F,J,3] on the key's device, got {tuple(x0.shape)}")
+    B, F, J, _ = x0.shape
+    num_timesteps = int(num_timesteps)
+    _need(0 < num_timesteps < 2 ** 31 and F * J < 2 ** 32, f"qsample_seeded: bad size (num_timesteps={num_timesteps} F={F} J={J})")
+    for name, tab in (("sqrt_ac", sqrt_ac), ("sqrt_1mac", sqrt_1mac)):
+        _need(tab.is_cuda and tab.device == x0.device and tab.dtype == torch.float64 and tab.is_contiguous() and tab.numel() >= num_timesteps,
+              f"qsample_seeded: {name} must hold num_timesteps float64 on the device of x0")
+    out = torch.empty_like(x0)
+    t = torch.empty(B, device=x0.device, dtype=torch.int64)
+    noise = torch.empty_like(x0) if want_noise else None
+    with torch.cuda.device(x0.device):
+        _lib.check(lib.pafuse_d3dp_qsample_seeded(x0.data_ptr(), key4.data_ptr(), sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(), float(scale),
+                                                  num_timesteps, out.data_ptr(), t.data_ptr(), noise.data_ptr() if want_noise else None,
+                                                  B, F, J, _stream(x0)))
+    return out, t, noise
+
+
+def droppath_fill(key4, denoiser, depth, F, J, B, keep, factor):
+    """pafuse_train_droppath_fill: one denoiser's DropPath table of one training forward, float32 [2*depth, 2, B*max(F,J)]
+    (the drop_path operand of pafuse_mixste2_train_forward), from the stream.  keep: float64 [2*depth], factor: float32
+    [2*depth], both on the key's device (MixSTE2.drop_path_tables makes them)."""
+    lib = _lib.load()
+    _need_key("droppath_fill", key4)
+    denoiser, depth, F, J, B = (int(v) for v in (denoiser, depth, F, J, B))
+    _need(0 <= denoiser < 2 ** 16 and 0 < depth <= 2 ** 14 and min(F, J, B) > 0 and F * J < 2 ** 32,
+          f"droppath_fill: bad argument (denoiser={denoiser} depth={depth} F={F} J={J} B={B})")
+    for name, tab, dtype in (("keep", keep, torch.float64), ("factor", factor, torch.float32)):
+        _need(torch.is_tensor(tab) and tab.is_cuda and tab.device == key4.device and tab.dtype == dtype and tab.is_contiguous()
+              and tab.numel() == 2 * depth, f"droppath_fill: {name} must hold 2 * depth {dtype} on the key's device")
+    out = torch.empty(2 * depth, 2, B * max(F, J), device=key4.device, dtype=torch.float32)
+    with torch.cuda.device(key4.device):
+        _lib.check(lib.pafuse_train_droppath_fill(key4.data_ptr(), denoiser, depth, F, J, B, keep.data_ptr(), factor.data_ptr(),
+                                                  out.data_ptr(), out.numel(), _stream(key4)))
+    return out
+
+
 # ------------------------------------------------------------------------------------ sharded hypothesis evaluation
 PARTIALS_HEAD_BYTES_PER_ELEMENT = 40   # double sum[3] + float jbest, e2, sel3 + int32 idx per (b, t, f, j)
 
