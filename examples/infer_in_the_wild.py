@@ -15,6 +15,13 @@ peak memory follows n instead of P) and both files hold [T,frames,134,3]: one po
 hypotheses from that mean - the confidence of the joint; --spread cov writes test_3d_output_cov.npy [T,frames,134,6] as
 well, their population covariance (xx, xy, xz, yy, yz, zz), camera space.  Without --keypoints a synthetic detection
 file is generated (random weights unless --checkpoint: numbers are meaningless).
+
+--reproj-fit FOCAL_PX adds J-Agg, the aggregate the method is known for, without a trajectory: per joint the hypothesis whose
+2-D reprojection is closest to the detection, with the root position of every (hypothesis, frame) fitted on the device from
+the detections, their confidences and a pinhole camera of that focal length in pixels (principal point at the image centre;
+a per-frame fit, no smoothing over time).  It writes test_3d_output_pick.npy [T,frames,134,3] and test_3d_output_pick_idx.npy
+[T,frames,134] (the hypothesis of every joint; -1: the detector did not find the joint and the pose holds the mean there)
+next to what --aggregate asks for (the hypotheses are sampled again for that); --hypothesis-chunk and --spread (test_3d_output_pick_std.npy / _pick_cov.npy) go with it.
 """
 import argparse
 import json
@@ -54,11 +61,17 @@ def main():
     ap.add_argument("--spread", choices=("std", "cov"), default=None,
                     help="with --aggregate mean: also write the per-joint spread of the hypotheses about the mean pose, reduced "
                          "on the device: std [T,frames,134] (metres), and for cov the covariance [T,frames,134,6] as well")
+    ap.add_argument("--reproj-fit", type=float, default=None, metavar="FOCAL_PX",
+                    help="also write J-Agg (test_3d_output_pick.npy, _pick_idx.npy): per joint the hypothesis whose reprojection is "
+                         "closest to the detection, the root of every hypothesis fitted on the device from the detections, their "
+                         "confidences and this focal length in pixels; --hypothesis-chunk and --spread go with it")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
-    if a.spread is not None and a.aggregate == "none":
+    if a.reproj_fit is not None and not a.reproj_fit > 0:
+        ap.error("--reproj-fit takes a positive focal length in pixels")
+    if a.spread is not None and a.aggregate == "none" and a.reproj_fit is None:
         ap.error("--spread needs --aggregate mean")
-    if a.hypothesis_chunk is not None and a.aggregate == "none":
+    if a.hypothesis_chunk is not None and a.aggregate == "none" and a.reproj_fit is None:
         ap.error("--hypothesis-chunk needs --aggregate mean")
     args = config.load(None, a.overrides)
     os.makedirs(a.out, exist_ok=True)
@@ -82,8 +95,24 @@ def main():
     if a.noise == "device":
         model.noise, model.noise_seed = "device", a.seed
 
-    pixels = harness.load_pifpaf_keypoints(a.keypoints, args.data.num_kps)
+    pixels, conf = harness.load_pifpaf_keypoints(a.keypoints, args.data.num_kps, with_conf=True)
     keypoints = h3wb.normalize_screen_coordinates(pixels[..., :2], w=a.width, h=a.height).astype(np.float32)
+    if a.reproj_fit is not None:
+        # screen-normalised coordinates: x in [-1, 1] over the width, the image centre at (0, 0), one scale for both axes
+        cam = np.array([2 * a.reproj_fit / a.width, 2 * a.reproj_fit / a.width, 0, 0, 0, 0, 0, 0, 0], dtype=np.float32)
+        pick = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="reproj_fit",
+                                      cam=cam, conf=conf, hypothesis_chunk=a.hypothesis_chunk, spread=a.spread)
+        if a.spread is not None:
+            for k in ("std", "cov")[:1 if a.spread == "std" else 2]:
+                np.save(os.path.join(a.out, f"test_3d_output_pick_{k}.npy"),
+                        harness.stitch_spread(pick[k], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
+            pick = (pick["pose"], pick["idx"])
+        np.save(os.path.join(a.out, "test_3d_output_pick.npy"),
+                harness.stitch_poses(pick[0], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
+        np.save(os.path.join(a.out, "test_3d_output_pick_idx.npy"),
+                harness.stitch_spread(pick[1], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
+        if a.aggregate == "none":        # the chunk and the spread belonged to the pick
+            a.hypothesis_chunk = a.spread = None
     if a.aggregate == "mean":
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
                                       hypothesis_chunk=a.hypothesis_chunk, spread=a.spread)

@@ -29,6 +29,7 @@
  *   pafuse_hypothesis_errors the per-joint part of evaluate()'s aggregation, main_h3wb.py:327-362
  *   pafuse_hypothesis_partials / _combine  the same from per-shard partial reductions (sharded or chunked P)
  *   pafuse_pose_partials / _combine  the P-Agg / J-Agg aggregates as poses, from shards or chunks of P (no ground truth)
+ *   pafuse_pose_partials_fit the same state without a trajectory: the root of every hypothesis fitted from the detections
  *   pafuse_spread_partials / _combine  the spread of the hypotheses beside the P-Agg mean: per-joint covariance and std
  *   pafuse_procrustes_errors the Protocol #2 part of it (ft2d.p2), main_h3wb.py:381-395, common/loss.py:251-458
  *   pafuse_procrustes_partials / _combine  Protocol #2 from per-shard partial states (sharded or chunked P)
@@ -594,6 +595,27 @@ size_t pafuse_pose_partials_bytes(int32_t B, int32_t T, int32_t F, int32_t J);
 int pafuse_pose_partials(const float *pred, const float *x2d, const float *traj, const float *cam, const int32_t *conn,
                          int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t h0, void *state,
                          size_t state_bytes, void *stream);
+
+/* The same state WITHOUT a trajectory (J-Agg in the wild): the root position t of every (hypothesis, frame) is fitted
+ * on the device from the detections and the intrinsics, and takes the place of traj in the reprojection error.
+ * x2d [B,F,J,2] screen-normalised detections, conf [B,F,J] their weights (NULL: every weight 1), cam [9].
+ * The fit, fp64 per (b,t,h,f) over the whole-body joints w_j (fx, fy, cx, cy = cam[0:4]; the distortion terms cam[4:9]
+ * take no part in it - they do in the error):
+ *   a = (u - cx)/fx, b = (v - cy)/fy, rx = a*wz - wx, ry = b*wz - wy
+ *   W, Sa, Sb, Sq = sum c*(1, a, b, a^2 + b^2);  Srx, Sry, Sm = sum c*(rx, ry, a*rx + b*ry)
+ *   den = Sq - (Sa^2 + Sb^2)/W;  tz = (-Sm + (Sa*Srx + Sb*Sry)/W)/den;  tx = (Srx + Sa*tz)/W;  ty = (Sry + Sb*tz)/W
+ * A weight that is not > 0 (0, negative, NaN) takes its joint out of every sum and out of the pick: its candidate
+ * stays (+inf, -1, NaN NaN NaN) whatever its coordinates hold.  No fit - fewer than two weighted joints, den not finite
+ * and > 0, t not finite in fp32 - offers no candidate; the sums still take the hypothesis.  The order of every sum over
+ * j is fixed (pafuse_amd/rootfit.py states it and the same operations in numpy), so the result is bit-reproducible and
+ * does not depend on how P is cut.  A per-frame fit with a KNOWN focal length: no temporal smoothing, no focal estimate.
+ * tfit (NULL: not wanted) [B,T,P_r,F,3] fp32: the fitted root of every local hypothesis, NaN where there is no fit.
+ * One kernel, no workspace, no atomics.  B == 0 or P_r == 0: no kernel runs, the state is the neutral one.
+ * Refused (PAFUSE_E_ARG): a null pred / x2d / cam / conn, negative sizes or h0, a short or misaligned state. */
+int pafuse_pose_partials_fit(const float *pred, const float *x2d, const float *conf /* [B,F,J] or NULL = all 1 */,
+                             const float *cam, const int32_t *conn, int32_t B, int32_t T, int32_t P_r, int32_t F,
+                             int32_t J, int32_t h0, void *state, size_t state_bytes,
+                             float *tfit /* [B,T,P_r,F,3] or NULL */, void *stream);
 
 /* Combines W such states, `stride_bytes` apart and in ascending-h0 order: sums added in shard order, the candidate with
  * the smallest e2 and, among equal ones, the lowest global index.  Writes any of (NULL: not wanted, at least one):

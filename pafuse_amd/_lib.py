@@ -153,6 +153,7 @@ SIGNATURES = {
                                   [C.c_void_p] * 6),
     "pafuse_pose_partials_bytes": (C.c_size_t, [C.c_int32] * 4),
     "pafuse_pose_partials": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pafuse_pose_partials_fit": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pafuse_pose_combine": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t] + [C.c_int32] * 5 + [C.c_void_p] * 5),
     "pafuse_spread_partials_bytes": (C.c_size_t, [C.c_int32] * 4),
     "pafuse_spread_partials": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),

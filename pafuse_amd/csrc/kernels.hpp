@@ -3015,6 +3015,181 @@ __global__ void __launch_bounds__(256) pose_combine_kernel(const PoseCombinePara
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// J-Agg WITHOUT a trajectory: pose_fit_partials_kernel fits the root position t of every (hypothesis, frame) from the
+// 2-D detections and the intrinsics, and then makes pose_partials_kernel's pick with t in the place of traj.  It writes
+// the pose state above (same layout, same neutral element), so pose_combine_kernel merges and finishes it unchanged.
+//
+// The fit (statement: pafuse_amd/rootfit.py; fp64, contraction pinned OFF, every product rounded before it is added):
+// with a = (u - cx)/fx, b = (v - cy)/fy the pinhole residual of joint j is linear in t,
+//   rx = a*wz - wx, ry = b*wz - wy;  tx - a*tz = rx, ty - b*tz = ry  in the least-squares sense with weights c_j,
+// whose normal equations close to
+//   den = Sq - (Sa^2 + Sb^2)/W,  tz = (-Sm + (Sa*Srx + Sb*Sry)/W)/den,  tx = (Srx + Sa*tz)/W,  ty = (Sry + Sb*tz)/W
+// with W, Sa, Sb, Sq = sum c*(1, a, b, a^2 + b^2) (no hypothesis in them: once per wave) and Srx, Sry, Sm =
+// sum c*(rx, ry, a*rx + b*ry) per hypothesis.  A weight that is not > 0 (0, negative, NaN) takes its joint out of every
+// sum, whatever its coordinates hold.  No fit - fewer than two weighted joints, den not finite and > 0, t (rounded to
+// fp32) not finite - is NaN in tfit and offers no candidate.
+// Order of every sum over j: lane l adds its joints l, l + 64, l + 128, ... in ascending order from 0.0, then
+// v += shfl_xor(v, o) for o = 32, 16, 8, 4, 2, 1 - after which every lane holds the same bits (a + b == b + a).
+//
+// One wave per (b, t, f), four per workgroup; the local hypotheses go in chunks of 64.  Per chunk, A: for every h the
+// lanes walk the joints (the rounds loop is wave-uniform: a lane without a joint in a round adds nothing and still feeds
+// its 0.0 to the butterfly), three fp64 butterflies, the solve in every lane, and lane h - c0 keeps t_h.  B: every lane
+// takes its joints round by round and walks the chunk's h serially (t_h by a shuffle from its keeper, the joint re-read:
+// a cache hit), adding to sum and keeping the first minimum of e2 - pose_partials_kernel's expression, compiled with the
+// same contraction setting as there.  The running element of a joint lives in registers within a chunk and in the state
+// itself between chunks (only P_r > 64 ever re-reads it; the same thread wrote it).  No LDS, no atomics, no scratch.
+// ----------------------------------------------------------------------------------------------------------------
+struct PoseFitParams {
+    const float* pred;    // [B,T,P_r,F,J,3] this shard's part-centred predictions
+    const float* x2d;     // [B,F,J,2]
+    const float* conf;    // [B,F,J] or null (every weight 1)
+    const float* cam;     // [9]
+    const int32_t* conn;  // [J]
+    double* sum;          // the pose state
+    float* e2;
+    int32_t* idx;
+    float* sel;
+    float* tfit;          // [B,T,P_r,F,3] or null
+    int B, T, P, F, J, h0;
+};
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// the weight and the normalised image point of joint j; false: the joint takes no part
+__device__ __forceinline__ bool fit_joint(const float* x2, const float* cf, int j, double fx, double fy, double cx, double cy,
+                                          double& a, double& b, double& c) {
+    const float cw = cf ? cf[j] : 1.f;
+    if (!(cw > 0.f)) return false;
+    c = (double)cw;
+    a = ((double)x2[2 * j] - cx) / fx;
+    b = ((double)x2[2 * j + 1] - cy) / fy;
+    return true;
+}
+
+// pose_partials_kernel's reprojection error of the whole-body joint w under the root tr (the same text)
+__device__ __forceinline__ float reproj_e2(const float (&w)[3], float tr0, float tr1, float tr2, float x20, float x21,
+                                           const float* cam) {
+    const float fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
+    const float k1 = cam[4], k2 = cam[5], k3 = cam[6], p1 = cam[7], p2 = cam[8];
+    const float X = w[0] + tr0, Y = w[1] + tr1, Z = w[2] + tr2;
+    const float xx = fminf(fmaxf(X / Z, -1.f), 1.f), yy = fminf(fmaxf(Y / Z, -1.f), 1.f);
+    const float r2 = xx * xx + yy * yy;
+    const float radial = 1.f + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2));
+    const float tan = p1 * xx + p2 * yy;
+    const float u = fx * (xx * (radial + tan) + p1 * r2) + cx, v = fy * (yy * (radial + tan) + p2 * r2) + cy;
+    const float q0 = u - x20, q1 = v - x21;
+    return sqrtf(q0 * q0 + q1 * q1);
+}
+
+__global__ void __launch_bounds__(256) pose_fit_partials_kernel(const PoseFitParams p) {
+    const int lane = threadIdx.x & 63;
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (int64_t)p.B * p.T * p.F) return;   // wave-uniform: all 64 lanes of a wave share `item`
+    const int f = (int)(item % p.F);
+    const int t = (int)((item / p.F) % p.T);
+    const int b = (int)(item / ((int64_t)p.F * p.T));
+    const int J = p.J, rounds = (J + 63) / 64;
+    const float* pose0 = p.pred + ((((int64_t)b * p.T + t) * p.P) * p.F + f) * J * 3;
+    const int64_t hstride = (int64_t)p.F * J * 3;
+    const float* x2 = p.x2d + ((int64_t)b * p.F + f) * J * 2;
+    const float* cf = p.conf ? p.conf + ((int64_t)b * p.F + f) * J : nullptr;
+    const float qnan = __builtin_nanf("");
+    const double fx = (double)p.cam[0], fy = (double)p.cam[1], cx = (double)p.cam[2], cy = (double)p.cam[3];
+    double W, Sa, Sb, den;
+    bool can;
+    {   // the sums without a hypothesis in them
+#pragma clang fp contract(off)
+        double w0 = 0.0, sa = 0.0, sb = 0.0, sq = 0.0;
+        int cnt = 0;
+        for (int r = 0; r < rounds; ++r) {
+            const int j = r * 64 + lane;
+            double a, bb, c;
+            if (j < J && fit_joint(x2, cf, j, fx, fy, cx, cy, a, bb, c))
+                w0 += c, sa += c * a, sb += c * bb, sq += c * (a * a + bb * bb), ++cnt;
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+        W = wave_sum_f64(w0), Sa = wave_sum_f64(sa), Sb = wave_sum_f64(sb);
+        const double Sq = wave_sum_f64(sq);
+        den = Sq - (Sa * Sa + Sb * Sb) / W;
+        can = cnt >= 2 && isfinite(den) && den > 0.0;
+    }
+    for (int c0 = 0; c0 < p.P; c0 += 64) {
+        const int nh = min(64, p.P - c0);
+        float myt[3] = {qnan, qnan, qnan};
+        int myok = 0;
+        for (int hh = 0; hh < nh; ++hh) {   // A: the root of every hypothesis of the chunk
+#pragma clang fp contract(off)
+            float tf[3] = {qnan, qnan, qnan};
+            int ok = 0;
+            if (can) {
+                const float* pose = pose0 + (c0 + hh) * hstride;
+                double srx = 0.0, sry = 0.0, sm = 0.0;
+                for (int r = 0; r < rounds; ++r) {
+                    const int j = r * 64 + lane;
+                    double a, bb, c;
+                    if (j < J && fit_joint(x2, cf, j, fx, fy, cx, cy, a, bb, c)) {
+                        float w[3];
+                        wb_joint(pose, p.conn, j, w);
+                        const double rx = a * (double)w[2] - (double)w[0], ry = bb * (double)w[2] - (double)w[1];
+                        srx += c * rx, sry += c * ry, sm += c * (a * rx + bb * ry);
+                    }
+                }
+                const double Srx = wave_sum_f64(srx), Sry = wave_sum_f64(sry), Sm = wave_sum_f64(sm);
+                const double tz = (-Sm + (Sa * Srx + Sb * Sry) / W) / den;
+                const double tx = (Srx + Sa * tz) / W, ty = (Sry + Sb * tz) / W;
+                const float t0 = (float)tx, t1 = (float)ty, t2 = (float)tz;
+                if (isfinite(t0) && isfinite(t1) && isfinite(t2)) tf[0] = t0, tf[1] = t1, tf[2] = t2, ok = 1;
+            }
+            if (lane == hh) myt[0] = tf[0], myt[1] = tf[1], myt[2] = tf[2], myok = ok;
+            if (p.tfit && lane < 3)
+                p.tfit[((((int64_t)b * p.T + t) * p.P + c0 + hh) * p.F + f) * 3 + lane] = lane == 0 ? tf[0] : lane == 1 ? tf[1] : tf[2];
+        }
+        for (int r = 0; r < rounds; ++r) {   // B: sum and pick of every joint over the chunk
+            const int j = r * 64 + lane;
+            const bool have = j < J;
+            const int64_t e = item * J + j;
+            const bool weighted = have && (cf ? cf[j] > 0.f : true);
+            float best2 = INFINITY, sel[3] = {qnan, qnan, qnan}, x20 = 0.f, x21 = 0.f;
+            int32_t hsel = -1;
+            double sm[3] = {0.0, 0.0, 0.0};
+            if (have) {
+                x20 = x2[2 * j], x21 = x2[2 * j + 1];
+                if (c0) {
+                    sm[0] = p.sum[e * 3 + 0], sm[1] = p.sum[e * 3 + 1], sm[2] = p.sum[e * 3 + 2];
+                    best2 = p.e2[e], hsel = p.idx[e];
+                    sel[0] = p.sel[e * 3 + 0], sel[1] = p.sel[e * 3 + 1], sel[2] = p.sel[e * 3 + 2];
+                }
+            }
+            for (int hh = 0; hh < nh; ++hh) {
+                const float t0 = __shfl(myt[0], hh), t1 = __shfl(myt[1], hh), t2 = __shfl(myt[2], hh);
+                const int ok = __shfl(myok, hh);
+                if (have) {
+                    float w[3];
+                    wb_joint(pose0 + (c0 + hh) * hstride, p.conn, j, w);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) sm[k] += (double)w[k];
+                    if (ok && weighted) {
+                        const float e2 = reproj_e2(w, t0, t1, t2, x20, x21, p.cam);
+                        if (e2 < best2) best2 = e2, hsel = p.h0 + c0 + hh, sel[0] = w[0], sel[1] = w[1], sel[2] = w[2];  // first minimum wins
+                    }
+                }
+            }
+            if (have) {
+                p.sum[e * 3 + 0] = sm[0], p.sum[e * 3 + 1] = sm[1], p.sum[e * 3 + 2] = sm[2];
+                p.e2[e] = best2;
+                p.idx[e] = hsel;
+                p.sel[e * 3 + 0] = sel[0], p.sel[e * 3 + 1] = sel[1], p.sel[e * 3 + 2] = sel[2];
+            }
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // The SPREAD of the hypotheses beside the mean pose: first and second moments of the whole-body joint per (b, t, f, j),
 // by the same shard / chunk scheme.  spread_partials_kernel reduces hypotheses [h0, h0 + P_r) to a state whose size does
 // not depend on P, spread_combine_kernel merges W states in ascending-h0 order and / or writes mean, covariance and std.

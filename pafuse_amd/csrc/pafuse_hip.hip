@@ -1826,6 +1826,19 @@ size_t pafuse_pose_partials_bytes(int32_t B, int32_t T, int32_t F, int32_t J) {
     return ((size_t)B * T * F * J * 44 + 7) / 8 * 8;
 }
 
+// the neutral pose state: zero sums, no candidate (+inf, -1, NaN NaN NaN)
+static int pose_neutral_state(const char* who, double* sum, float* e2, int32_t* idx, float* sel, int64_t n, hipStream_t s) {
+    hipError_t e = hipSuccess;
+    if (n) {
+        e = hipMemsetAsync(sum, 0, (size_t)n * 24, s);
+        if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)e2, 0x7f800000, (size_t)n, s);
+        if (e == hipSuccess) e = hipMemsetAsync(idx, 0xff, (size_t)n * 4, s);
+        if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)sel, 0x7fc00000, (size_t)n * 3, s);
+    }
+    if (e != hipSuccess) return fail(PAFUSE_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    return PAFUSE_OK;
+}
+
 int pafuse_pose_partials(const float* pred, const float* x2d, const float* traj, const float* cam, const int32_t* conn,
                          int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t h0, void* state, size_t state_bytes,
                          void* stream) {
@@ -1844,17 +1857,7 @@ int pafuse_pose_partials(const float* pred, const float* x2d, const float* traj,
     int32_t* idx = (int32_t*)(e2 + n);
     float* sel = (float*)(idx + n);
     hipStream_t s = (hipStream_t)stream;
-    if (B == 0 || P_r == 0) {   // the neutral state: zero sums, no candidate (+inf, -1, NaN NaN NaN); no kernel runs
-        hipError_t e = hipSuccess;
-        if (n) {
-            e = hipMemsetAsync(sum, 0, (size_t)n * 24, s);
-            if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)e2, 0x7f800000, (size_t)n, s);
-            if (e == hipSuccess) e = hipMemsetAsync(idx, 0xff, (size_t)n * 4, s);
-            if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)sel, 0x7fc00000, (size_t)n * 3, s);
-        }
-        if (e != hipSuccess) return fail(PAFUSE_E_HIP, "pose_partials: %s", hipGetErrorString(e));
-        return PAFUSE_OK;
-    }
+    if (B == 0 || P_r == 0) return pose_neutral_state("pose_partials", sum, e2, idx, sel, n, s);   // no kernel runs
     if (!pred || !conn) return fail(PAFUSE_E_ARG, "pose_partials: null pointer");
     if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "pose_partials: grid out of range");
     PosePartialsParams m{};
@@ -1862,6 +1865,35 @@ int pafuse_pose_partials(const float* pred, const float* x2d, const float* traj,
     m.sum = sum, m.e2 = e2, m.idx = idx, m.sel = sel;
     m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0;
     return launch<pose_partials_kernel>("pose_partials_kernel", blocks_for(n), 256, 0, s, m);
+}
+
+// pafuse_pose_partials without a trajectory: the root of every (hypothesis, frame) is fitted from x2d, conf and the
+// intrinsics (pose_fit_partials_kernel); the state is the one above
+int pafuse_pose_partials_fit(const float* pred, const float* x2d, const float* conf, const float* cam, const int32_t* conn,
+                             int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t h0, void* state,
+                             size_t state_bytes, float* tfit, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (B < 0 || T <= 0 || P_r < 0 || F <= 0 || J <= 0 || h0 < 0) return fail(PAFUSE_E_ARG, "pose_partials_fit: bad size");
+    if (!x2d || !cam) return fail(PAFUSE_E_ARG, "pose_partials_fit: x2d and cam are needed (conf may be null: every weight 1)");
+    const size_t need = pafuse_pose_partials_bytes(B, T, F, J);
+    if (need && (!state || state_bytes < need)) return fail(PAFUSE_E_ARG, "pose_partials_fit: the state needs %zu bytes", need);
+    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "pose_partials_fit: the state must be 8-byte aligned");
+    const int64_t n = (int64_t)B * T * F * J;
+    char* st = (char*)state;
+    double* sum = (double*)st;
+    float* e2 = (float*)(st + n * 24);
+    int32_t* idx = (int32_t*)(e2 + n);
+    float* sel = (float*)(idx + n);
+    hipStream_t s = (hipStream_t)stream;
+    if (B == 0 || P_r == 0) return pose_neutral_state("pose_partials_fit", sum, e2, idx, sel, n, s);   // no kernel runs, tfit is empty
+    if (!pred || !conn) return fail(PAFUSE_E_ARG, "pose_partials_fit: null pointer");
+    const int64_t waves = (int64_t)B * T * F;   // one wave per (b, t, f), four per workgroup
+    if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "pose_partials_fit: grid out of range");
+    PoseFitParams m{};
+    m.pred = pred, m.x2d = x2d, m.conf = conf, m.cam = cam, m.conn = conn;
+    m.sum = sum, m.e2 = e2, m.idx = idx, m.sel = sel, m.tfit = tfit;
+    m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0;
+    return launch<pose_fit_partials_kernel>("pose_fit_partials_kernel", blocks_for(waves, 4), 256, 0, s, m);
 }
 
 int pafuse_pose_combine(const void* states, int32_t W, size_t stride_bytes, int32_t B, int32_t T, int32_t F, int32_t J,

@@ -402,18 +402,28 @@ class PoseState(_RunningState):
     independent of how many hypotheses went in.  `reproj`: the chunks came with 2-D input, trajectory and camera, so the
     state holds J-Agg candidates; a mean-only state has none."""
 
-    def __init__(self, shape, device, reproj):
+    def __init__(self, shape, device, reproj, fit=False):
         super().__init__(shape, device)
         self.reproj = bool(reproj)
+        self.fit = bool(fit)      # the roots were fitted (accumulate_poses(fit=True)): a state without any pick is legitimate
 
 
-def accumulate_poses(state, pred_local, h0, dataset, inputs_2d=None, traj=None, cam=None):
+def accumulate_poses(state, pred_local, h0, dataset, inputs_2d=None, traj=None, cam=None, *, fit=False, conf=None, tfit=None):
     """Fold the part-centred hypotheses pred_local [B,T,P_c,F,J,3] = global [h0, h0 + P_c) into the pose state `state`
     (None: start one) and return it.  inputs_2d [B,F,J,2], traj [B,F,3] (or [B,F,1,3]) and cam [9] together keep the J-Agg
     candidate; none of them: mean-only.  Chunks come in ascending h0 without a gap.  Memory: the chunk and two 44-byte
-    per-(b,t,f,j) states - never anything of size P."""
+    per-(b,t,f,j) states - never anything of size P.
+
+    fit=True: J-Agg WITHOUT a trajectory - inputs_2d and cam, no traj; the root of every (hypothesis, frame) is fitted on
+    the device (ops.pose_partials_fit, pafuse_amd.rootfit) with the weights conf [B,F,J] (None: all 1; not > 0: the joint
+    takes no part and gets no pick).  tfit: a contiguous fp32 [B,T,P_c,F,3] device tensor that receives this chunk's roots
+    (NaN: no fit).  The state is a PoseState(reproj=True) and combines like any other."""
     from . import ops
     who = "accumulate_poses"
+    if fit:
+        return _accumulate_poses_fit(state, pred_local, h0, dataset, inputs_2d, traj, cam, conf, tfit)
+    if conf is not None or tfit is not None:
+        raise ValueError("accumulate_poses: conf and tfit belong to fit=True")
     pred, _, x2d, tr, cm, conn, _ = _operands(pred_local, None, inputs_2d, traj, cam, dataset, who, name="pred_local", axis="P_c")
     B, T, P_c, F, J, _ = pred.shape
     shape = (B, T, F, J)
@@ -423,8 +433,39 @@ def accumulate_poses(state, pred_local, h0, dataset, inputs_2d=None, traj=None, 
     state.expect(who, shape, pred.device)
     if state.reproj != reproj:
         raise ValueError("accumulate_poses: a state is either mean-only or keeps candidates, for all of its chunks")
+    if state.fit:
+        raise ValueError("accumulate_poses: a state is fitted for all of its chunks or for none")
     return state.fold(who, P_c, h0, ops.pose_partials_bytes(B, T, F, J) // 8, None,
                       lambda row: ops.pose_partials(pred, conn, int(h0), x2d, tr, cm, out=row),
+                      lambda slots: ops.combine_poses(slots, shape, 1, merged=slots[0], want=()))
+
+
+def _accumulate_poses_fit(state, pred_local, h0, dataset, inputs_2d, traj, cam, conf, tfit):
+    from . import ops
+    who = "accumulate_poses"
+    if inputs_2d is None or cam is None or traj is not None:
+        raise ValueError("accumulate_poses: fit=True takes inputs_2d and cam and no traj (the root is what it fits)")
+    pred, _, _, _, _, conn, _ = _operands(pred_local, None, None, None, None, dataset, who, name="pred_local", axis="P_c")
+    B, T, P_c, F, J, _ = pred.shape
+    shape = (B, T, F, J)
+    dev = pred.device
+    if (tuple(inputs_2d.shape) != (B, F, J, 2) or cam.numel() < 9 or (conf is not None and tuple(conf.shape) != (B, F, J))
+            or (tfit is not None and tuple(tfit.shape) != (B, T, P_c, F, 3))):
+        raise ValueError(f"{who}: operands do not match pred {tuple(pred.shape)}: 2d {tuple(inputs_2d.shape)}, cam "
+                         f"{tuple(cam.shape)}" + ("" if conf is None else f", conf {tuple(conf.shape)}")
+                         + ("" if tfit is None else f", tfit {tuple(tfit.shape)}"))
+    if inputs_2d.device != dev or (conf is not None and conf.device != dev) or (tfit is not None and tfit.device != dev):
+        raise ValueError(f"{who}: all tensors must live on the device of pred_local")
+    x2d = inputs_2d.contiguous().float()
+    cm = cam.reshape(-1)[:9].contiguous().float().to(dev)
+    cf = None if conf is None else conf.contiguous().float()
+    if state is None:
+        state = PoseState(shape, dev, True, fit=True)
+    state.expect(who, shape, dev)
+    if not (state.reproj and state.fit):
+        raise ValueError("accumulate_poses: a state is fitted for all of its chunks or for none")
+    return state.fold(who, P_c, h0, ops.pose_partials_bytes(B, T, F, J) // 8, None,
+                      lambda row: ops.pose_partials_fit(pred, conn, int(h0), x2d, cm, conf=cf, out=row, tfit=tfit),
                       lambda slots: ops.combine_poses(slots, shape, 1, merged=slots[0], want=()))
 
 
@@ -463,7 +504,7 @@ def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=No
     P = int(num_proposals)
     if spread_state is None:
         (states, _), = _exchange([(state.head, None)], state.h0, state.count, P, group, state.device)
-        return ops.combine_poses(states.contiguous(), state.shape, P, want=want)
+        return ops.combine_poses(states.contiguous(), state.shape, P, want=want, no_pick_ok=state.fit)
     first = spread_state if state is None else state
     if state is not None and (state.shape != spread_state.shape or state.device != spread_state.device
                               or (state.h0, state.count) != (spread_state.h0, spread_state.count)):
@@ -475,7 +516,8 @@ def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=No
     from_spread = tuple(k for k in want if k not in from_pose)
     out = {}
     if from_pose:
-        out.update(ops.combine_poses(got[0][0].contiguous(), first.shape, P, want=from_pose))
+        out.update(ops.combine_poses(got[0][0].contiguous(), first.shape, P, want=from_pose,
+                                     no_pick_ok=state is not None and state.fit))
     if from_spread:
         out.update(ops.combine_spread(got[-1][0].contiguous(), first.shape, want=from_spread))
     return out

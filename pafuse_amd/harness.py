@@ -64,7 +64,7 @@ def wb_pose_from_parts(pose, dataset):
 
 @torch.no_grad()
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
-                   hypothesis_chunk=None, spread=None):
+                   hypothesis_chunk=None, spread=None, conf=None):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -77,24 +77,42 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     and its index (NaN / -1 where no reprojection error is finite); it needs ``cam`` [9] intrinsics and ``traj`` [N,3], the
     root position of every frame (cut into clips like the 2-D input).
 
+    ``"reproj_fit"`` is J-Agg WITHOUT a trajectory, for videos of one's own: it needs ``cam`` [9] and refuses a ``traj`` - the
+    root of every (hypothesis, frame) is fitted on the device from the un-flipped 2-D input and the intrinsics
+    (pafuse_amd.rootfit: a per-frame linear fit with a known focal length, no smoothing over time).  ``conf`` [N,J] weighs
+    the detections (None: all 1; a weight that is not > 0 - OpenPifPaf's "not found" - takes the joint out of the fit and
+    out of the pick); it is cut into clips like the 2-D input.  It returns ``(pose, idx)`` as "reproj" does, except that a
+    joint without a pick (idx -1: no weight, or no hypothesis of its frame could be fitted) holds the MEAN of the
+    hypotheses instead of NaN.  The fitted roots themselves are not returned (evaluate.accumulate_poses(tfit=...) has them).
+
     ``spread`` (with an ``aggregate``) also returns how much the hypotheses disagree per joint, reduced on the device by the
     same scheme (evaluate.accumulate_spread, 72 bytes per (clip,t,f,j)).  The return value is then a dict of CPU tensors:
     ``"pose"`` as above, ``"idx"`` for "reproj", ``"std"`` [clips,T,F,J] - the RMS distance in metres of the P whole-body
     hypotheses from their mean joint - and, for ``spread="cov"``, ``"cov"`` [clips,T,F,J,6], their population covariance
     (xx, xy, xz, yy, yz, zz).  With "mean" only the spread state is kept (it holds the sums: the pose is the same, bit
     for bit); with "reproj" every chunk is folded into both states.  Both are taken about the MEAN pose."""
-    if aggregate not in (None, "mean", "reproj"):
-        raise ValueError(f'aggregate must be None, "mean" or "reproj", got {aggregate!r}')
+    if aggregate not in (None, "mean", "reproj", "reproj_fit"):
+        raise ValueError(f'aggregate must be None, "mean", "reproj" or "reproj_fit", got {aggregate!r}')
     if spread not in (None, "std", "cov"):
         raise ValueError(f'spread must be None, "std" or "cov", got {spread!r}')
     if spread is not None and aggregate is None:
-        raise ValueError('spread needs aggregate="mean" or "reproj" (it is reduced on the device beside the pose)')
+        raise ValueError('spread needs aggregate="mean", "reproj" or "reproj_fit" (it is reduced on the device beside the pose)')
     if hypothesis_chunk is not None and (aggregate is None or int(hypothesis_chunk) < 1):
         raise ValueError("hypothesis_chunk is a positive count and needs an aggregate")
     if aggregate == "reproj" and (cam is None or traj is None):
         raise ValueError('aggregate="reproj" needs cam [9] and traj [N,3]')
-    dev = next(model.parameters()).device
+    fit = aggregate == "reproj_fit"
     seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
+    if fit:
+        if cam is None or traj is not None:
+            raise ValueError('aggregate="reproj_fit" needs cam [9] and takes no traj (the root is what it fits)')
+        if conf is not None:
+            conf = torch.as_tensor(conf, dtype=torch.float32)
+            if tuple(conf.shape) != tuple(seq_2d.shape[-3:-1]):
+                raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[-3:-1])}, got {tuple(conf.shape)}")
+    elif conf is not None:
+        raise ValueError('conf belongs to aggregate="reproj_fit"')
+    dev = next(model.parameters()).device
     x2d = cut_clips(seq_2d, model.frames).to(dev)
     x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), model.frames).to(dev)
     sampler = ShardedSampler(model, group)
@@ -104,29 +122,39 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
             pred = sampler(x2d[lo:lo + batch_size], None, input_2d_flip=x2d_flip[lo:lo + batch_size])
             outs.append(wb_pose_from_parts(pred, dataset).cpu())
         return torch.cat(outs)
-    reproj = aggregate == "reproj"
-    if reproj:
+    reproj = aggregate in ("reproj", "reproj_fit")
+    if fit:
+        cam = torch.as_tensor(cam, dtype=torch.float32).to(dev)
+        if conf is not None:
+            conf = cut_clips(conf.unsqueeze(-1), model.frames).squeeze(-1).to(dev)  # [clips,F,J]
+    elif reproj:
         traj = torch.as_tensor(traj, dtype=torch.float32)
         if traj.dim() != 2 or tuple(traj.shape) != (seq_2d.shape[-3], 3):
             raise ValueError(f"traj must be [N,3] with N = {seq_2d.shape[-3]} frames, got {tuple(traj.shape)}")
         traj = cut_clips(traj.unsqueeze(1), model.frames).squeeze(2).to(dev)          # [clips,F,3]
         cam = torch.as_tensor(cam, dtype=torch.float32).to(dev)
     pose_name = "pick" if reproj else "mean"
-    names = (pose_name,) + (("idx",) if reproj else ()) + (() if spread is None else ("std",) if spread == "std" else ("std", "cov"))
-    kept = {k: [] for k in names}
+    names = ((pose_name,) + (("idx",) if reproj else ()) + (("mean",) if fit else ())
+             + (() if spread is None else ("std",) if spread == "std" else ("std", "cov")))
+    kept = {k: [] for k in names if not (fit and k == "mean")}     # with the fit the mean only fills joints without a pick
     for lo in range(0, x2d.shape[0], batch_size):
         hi = min(lo + batch_size, x2d.shape[0])
-        operands = (x2d[lo:hi], traj[lo:hi], cam) if reproj else ()
+        operands = (x2d[lo:hi], traj[lo:hi], cam) if reproj and not fit else ()
         state = moments = None
         for pred, h0, _ in sampler.sample_chunks(x2d[lo:hi], None, input_2d_flip=x2d_flip[lo:hi], chunk=hypothesis_chunk):
-            if reproj or spread is None:
+            if fit:
+                state = accumulate_poses(state, pred, h0, dataset, x2d[lo:hi], None, cam, fit=True,
+                                         conf=None if conf is None else conf[lo:hi])
+            elif reproj or spread is None:
                 state = accumulate_poses(state, pred, h0, dataset, *operands)
             if spread is not None:
                 moments = accumulate_spread(moments, pred, h0, dataset)
             del pred
         out = aggregate_poses_sharded(None, None, model.num_proposals, dataset, group=group, state=state, want=names,
                                       spread_state=moments)
-        for k in names:
+        if fit:     # a joint without a pick carries the mean (the one combine call wrote both)
+            out["pick"] = torch.where((out["idx"] < 0).unsqueeze(-1), out["mean"], out["pick"])
+        for k in kept:
             kept[k].append(out[k].cpu())
     kept = {k: torch.cat(v) for k, v in kept.items()}
     if spread is not None:
@@ -134,10 +162,12 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     return (kept["pick"], kept["idx"]) if reproj else kept["mean"]
 
 
-def load_pifpaf_keypoints(path, num_kps=134):
+def load_pifpaf_keypoints(path, num_kps=134, with_conf=False):
     """OpenPifPaf whole-body detections, one JSON object per line and frame, first person of each frame
     (in_the_wild/h3wb_diffusion.py:57-70): -> float32 [frames, num_kps, 2] in pixels with the root joint (midpoint of
-    the shifted hip joints 12 and 13) inserted at index 0.  Confidences are dropped, as in the reference."""
+    the shifted hip joints 12 and 13) inserted at index 0.  Confidences are dropped, as in the reference - unless
+    with_conf=True: then -> (kps, conf [frames, num_kps] float32), the detector's confidence of every keypoint (0 where it
+    found none: OpenPifPaf writes (0, 0, 0) there), the inserted root taking the smaller of its two hips'."""
     import json
     import numpy as np
     frames = []
@@ -146,12 +176,15 @@ def load_pifpaf_keypoints(path, num_kps=134):
             if line.strip():
                 frames.append(json.loads(line))
     kps = np.zeros((len(frames), num_kps, 2), dtype=np.float32)
+    conf = np.zeros((len(frames), num_kps), dtype=np.float32)
     for i, frame in enumerate(frames):
         flat = frame["predictions"][0]["keypoints"]
         kps[i, 1:, 0] = flat[::3]
         kps[i, 1:, 1] = flat[1::3]
         kps[i, :1, :] = (kps[i, 12:13, :] + kps[i, 13:14, :]) / 2.
-    return kps
+        conf[i, 1:] = flat[2::3]
+        conf[i, 0] = min(conf[i, 12], conf[i, 13])
+    return (kps, conf) if with_conf else kps
 
 
 def stitch_clips(prediction, total_frames, frames=27):

@@ -994,13 +994,42 @@ def pose_partials(pred, conn, h0, x2d=None, traj=None, cam=None, out=None):
     return out
 
 
-def combine_poses(states, shape, num_proposals, merged=None, want=("mean", "pick", "idx")):
+def pose_partials_fit(pred, conn, h0, x2d, cam, conf=None, out=None, tfit=None):
+    """One shard's pose state WITHOUT a trajectory (pafuse_pose_partials_fit): pred [B,T,P_r,F,J,3] the LOCAL part-centred
+    hypotheses [h0, h0 + P_r), conn int32 [J], x2d [B,F,J,2] screen-normalised detections, cam [9], conf [B,F,J] their
+    weights (None: every weight 1; not > 0: the joint takes no part and gets no pick).  The root of every (hypothesis,
+    frame) is fitted on the device (pafuse_amd.rootfit states the arithmetic) and stands in for traj -> the flat state of
+    pose_partials.  `out`: as there.  `tfit`: a contiguous fp32 [B,T,P_r,F,3] tensor that receives the fitted roots, NaN
+    where there is no fit."""
+    lib = _lib.load()
+    B, T, P_r, F, J = _need_pred("pose_partials_fit", pred)
+    _need(T > 0 and F > 0 and J > 0 and int(h0) >= 0, "pose_partials_fit: T, F, J > 0 and h0 >= 0")
+    _need(conn.numel() == J and conn.dtype == torch.int32, "pose_partials_fit: conn must be int32 [J]")
+    _need(x2d is not None and cam is not None, "pose_partials_fit: x2d and cam are needed")
+    _need(tuple(x2d.shape) == (B, F, J, 2) and cam.numel() == 9 and (conf is None or tuple(conf.shape) == (B, F, J))
+          and (tfit is None or tuple(tfit.shape) == (B, T, P_r, F, 3)), "pose_partials_fit: operands do not match pred")
+    _need_tensors("pose_partials_fit", [pred, x2d, cam] + [t for t in (conf, tfit) if t is not None], (conn,))
+    dev = pred.device
+    need = int(lib.pafuse_pose_partials_bytes(B, T, F, J))
+    assert need == pose_partials_bytes(B, T, F, J)
+    out = _state_out("pose_partials_fit", out, need, dev)
+    x2d_ptr = x2d.data_ptr() if B else cam.data_ptr()   # B == 0: no storage to point at, and the library reads none of it
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_pose_partials_fit(
+            _data(pred), x2d_ptr, None if conf is None else _data(conf), cam.data_ptr(),
+            _data(conn), B, T, P_r, F, J, int(h0), _data(out), out.numel() * 8, None if tfit is None else _data(tfit),
+            _stream(pred)))
+    return out
+
+
+def combine_poses(states, shape, num_proposals, merged=None, want=("mean", "pick", "idx"), no_pick_ok=False):
     """pafuse_pose_combine: `states` [W, L] float64 (W flat pose states of the same (B,T,F,J) = `shape`, one per row, in
     ascending-h0 order; rows may be padded) -> dict with the entries named in `want`: "mean" [B,T,F,J,3] (the sums
     divided by `num_proposals`, the TOTAL hypothesis count), "pick" [B,T,F,J,3], "idx" [B,T,F,J] int32.  `merged`: a
     float64 buffer that receives the state of the union; of the operands it may only be states[0] (a running state).
     Asking for "pick" or "idx" when no state holds a single candidate (mean-only states) raises - after the launch, at
-    the price of one synchronisation."""
+    the price of one synchronisation.  no_pick_ok=True (states of pose_partials_fit, where a batch without one weighted
+    detection is legitimate) skips that check: the pick is then NaN and idx -1 throughout."""
     lib = _lib.load()
     B, T, F, J = (int(v) for v in shape)
     n = B * T * F * J
@@ -1031,7 +1060,7 @@ def combine_poses(states, shape, num_proposals, merged=None, want=("mean", "pick
             states.data_ptr(), states.shape[0], states.shape[1] * 8, B, T, F, J, int(num_proposals),
             None if merged is None else merged.data_ptr(), ptr("mean"), ptr("pick"),
             idx.data_ptr() if ("idx" in want or "pick" in want) else None, _stream(states)))
-    if ("idx" in want or "pick" in want) and not bool((idx >= 0).any()):
+    if ("idx" in want or "pick" in want) and not no_pick_ok and not bool((idx >= 0).any()):
         raise _lib.PafuseError("combine_poses: no state holds a J-Agg candidate (mean-only states have no pick)")
     return out
 

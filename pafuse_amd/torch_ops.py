@@ -14,6 +14,7 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::procrustes_partials(pred, gt, x2d, traj, cam, conn, h0)   one shard's Protocol #2 state
   pafuse::procrustes_combine(states, sums, gt, conn, T, num_proposals)   jbest, pagg, jagg, pick from W states   main_h3wb.py:381-395
   pafuse::aggregate_poses(pred, conn, x2d?, traj?, cam?)  P-Agg mean pose, J-Agg pose and its hypothesis index, one shard
+  pafuse::aggregate_poses_fit(pred, conn, x2d, cam, conf?)  the same without a trajectory: roots fitted on the device; + tfit
   pafuse::noise_fill(key, draw, B, P, F, J)               one draw of noise stream v1 as a tensor (DESIGN.md section 6)
 
 ``precision`` ('bf16x3' = the modules' default; 'bf16x3_images', 'f16x2', 'f32', 'bf16': pafuse_amd.D3DP.precision) is the
@@ -360,6 +361,28 @@ def aggregate_poses(pred: torch.Tensor, conn: torch.Tensor, x2d: Optional[torch.
 def _(pred, conn, x2d=None, traj=None, cam=None):
     B, T, P, F, J, _ = pred.shape
     return [pred.new_empty(B, T, F, J, 3), pred.new_empty(B, T, F, J, 3), pred.new_empty((B, T, F, J), dtype=torch.int32)]
+
+
+@torch.library.custom_op("pafuse::aggregate_poses_fit", mutates_args=(), device_types="cuda")
+def aggregate_poses_fit(pred: torch.Tensor, conn: torch.Tensor, x2d: torch.Tensor, cam: torch.Tensor,
+                        conf: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+    """The one-shard convenience of pafuse_amd.ops.pose_partials_fit + combine_poses (J-Agg without a trajectory): pred
+    [B,T,P,F,J,3] part-centred, x2d [B,F,J,2], cam [9], conf [B,F,J] or None -> [mean [B,T,F,J,3], pick [B,T,F,J,3], idx
+    [B,T,F,J] int32, tfit [B,T,P,F,3]].  Where no hypothesis has a fit, or a joint no positive weight, pick is NaN and
+    idx -1; tfit is NaN where there is no fit."""
+    from . import ops
+    B, T, P, F, J, _ = pred.shape
+    tfit = pred.new_empty(B, T, P, F, 3)
+    state = ops.pose_partials_fit(pred, conn, 0, x2d, cam, conf=conf, tfit=tfit)
+    m = ops.combine_poses(state.view(1, -1), (B, T, F, J), P, no_pick_ok=True)
+    return [m["mean"], m["pick"], m["idx"], tfit]
+
+
+@aggregate_poses_fit.register_fake
+def _(pred, conn, x2d, cam, conf=None):
+    B, T, P, F, J, _ = pred.shape
+    return [pred.new_empty(B, T, F, J, 3), pred.new_empty(B, T, F, J, 3), pred.new_empty((B, T, F, J), dtype=torch.int32),
+            pred.new_empty(B, T, P, F, 3)]
 
 
 # ----------------------------------------------------------------------------------- spread of the hypotheses
