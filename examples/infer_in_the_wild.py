@@ -22,6 +22,11 @@ the detections, their confidences and a pinhole camera of that focal length in p
 a per-frame fit, no smoothing over time).  It writes test_3d_output_pick.npy [T,frames,134,3] and test_3d_output_pick_idx.npy
 [T,frames,134] (the hypothesis of every joint; -1: the detector did not find the joint and the pose holds the mean there)
 next to what --aggregate asks for (the hypotheses are sampled again for that); --hypothesis-chunk and --spread (test_3d_output_pick_std.npy / _pick_cov.npy) go with it.
+
+--stride S (1 .. the clip length; with --aggregate mean and / or --reproj-fit) slides the window over the video with that stride
+instead of cutting consecutive clips, and pools on the device all windows that cover a frame: the same files, the per-frame arrays
+written directly (no stitching), each frame aggregated over (windows covering it) x P hypotheses, plus test_3d_output_count.npy
+[frames] and, with --reproj-fit, test_3d_output_pick_window.npy [T,frames,134].  Sampling costs about clip length / S times as much.
 """
 import argparse
 import json
@@ -65,8 +70,13 @@ def main():
                     help="also write J-Agg (test_3d_output_pick.npy, _pick_idx.npy): per joint the hypothesis whose reprojection is "
                          "closest to the detection, the root of every hypothesis fitted on the device from the detections, their "
                          "confidences and this focal length in pixels; --hypothesis-chunk and --spread go with it")
+    ap.add_argument("--stride", type=int, default=None, metavar="S",
+                    help="with --aggregate mean or --reproj-fit: slide the window over the video with this stride (1 .. clip length) "
+                         "and pool the windows covering a frame on the device: one pose per video frame, no seam at the clip borders")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.stride is not None and a.aggregate == "none" and a.reproj_fit is None:
+        ap.error("--stride needs --aggregate mean or --reproj-fit")
     if a.reproj_fit is not None and not a.reproj_fit > 0:
         ap.error("--reproj-fit takes a positive focal length in pixels")
     if a.spread is not None and a.aggregate == "none" and a.reproj_fit is None:
@@ -97,23 +107,37 @@ def main():
 
     pixels, conf = harness.load_pifpaf_keypoints(a.keypoints, args.data.num_kps, with_conf=True)
     keypoints = h3wb.normalize_screen_coordinates(pixels[..., :2], w=a.width, h=a.height).astype(np.float32)
+    save = lambda name, t: np.save(os.path.join(a.out, name), t.numpy(), allow_pickle=True)
     if a.reproj_fit is not None:
         # screen-normalised coordinates: x in [-1, 1] over the width, the image centre at (0, 0), one scale for both axes
         cam = np.array([2 * a.reproj_fit / a.width, 2 * a.reproj_fit / a.width, 0, 0, 0, 0, 0, 0, 0], dtype=np.float32)
         pick = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="reproj_fit",
-                                      cam=cam, conf=conf, hypothesis_chunk=a.hypothesis_chunk, spread=a.spread)
-        if a.spread is not None:
+                                      cam=cam, conf=conf, hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride)
+        if a.stride is not None:         # per-frame arrays already
+            for k, name in (("pose", "pick"), ("idx", "pick_idx"), ("window", "pick_window"), ("std", "pick_std"), ("cov", "pick_cov")):
+                if k in pick:
+                    save(f"test_3d_output_{name}.npy", pick[k])
+            save("test_3d_output_count.npy", pick["count"])
+        elif a.spread is not None:
             for k in ("std", "cov")[:1 if a.spread == "std" else 2]:
                 np.save(os.path.join(a.out, f"test_3d_output_pick_{k}.npy"),
                         harness.stitch_spread(pick[k], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
             pick = (pick["pose"], pick["idx"])
-        np.save(os.path.join(a.out, "test_3d_output_pick.npy"),
-                harness.stitch_poses(pick[0], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
-        np.save(os.path.join(a.out, "test_3d_output_pick_idx.npy"),
-                harness.stitch_spread(pick[1], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
+        if a.stride is None:
+            np.save(os.path.join(a.out, "test_3d_output_pick.npy"),
+                    harness.stitch_poses(pick[0], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
+            np.save(os.path.join(a.out, "test_3d_output_pick_idx.npy"),
+                    harness.stitch_spread(pick[1], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
         if a.aggregate == "none":        # the chunk and the spread belonged to the pick
             a.hypothesis_chunk = a.spread = None
-    if a.aggregate == "mean":
+    if a.aggregate == "mean" and a.stride is not None:
+        pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
+                                      hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride)
+        for k in ("std", "cov", "count"):
+            if k in pred:
+                save(f"test_3d_output_{k}.npy", pred[k])
+        poses = pred["pose"]                                                        # [T,frames,134,3]
+    elif a.aggregate == "mean":
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
                                       hypothesis_chunk=a.hypothesis_chunk, spread=a.spread)
         if a.spread is not None:

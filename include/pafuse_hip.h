@@ -31,6 +31,8 @@
  *   pafuse_pose_partials / _combine  the P-Agg / J-Agg aggregates as poses, from shards or chunks of P (no ground truth)
  *   pafuse_pose_partials_fit the same state without a trajectory: the root of every hypothesis fitted from the detections
  *   pafuse_spread_partials / _combine  the spread of the hypotheses beside the P-Agg mean: per-joint covariance and std
+ *   pafuse_pose_windows_fold / pafuse_spread_windows_fold / pafuse_frames_finish  those states of overlapping windows
+ *                            pooled into one pose (and spread) per video frame
  *   pafuse_procrustes_errors the Protocol #2 part of it (ft2d.p2), main_h3wb.py:381-395, common/loss.py:251-458
  *   pafuse_procrustes_partials / _combine  Protocol #2 from per-shard partial states (sharded or chunked P)
  *   pafuse_mixste2_train_*   MixSTE2.forward (is_train=True) + autograd backward, common/mixste.py:215-225,260-298
@@ -655,6 +657,59 @@ int pafuse_spread_partials(const float *pred, const int32_t *conn, int32_t B, in
  * state over an operand other than the first, no output, a grid out of range. */
 int pafuse_spread_combine(const void *states, int32_t W, size_t stride_bytes, int32_t B, int32_t T, int32_t F, int32_t J,
                           void *merged, float *mean, float *cov, float *std_dev, void *stream);
+
+/* Overlapping windows pooled into one state per video FRAME.  A video of N frames is cut into windows of F frames; window
+ * b of a batch starts at frame starts[b] and its first valid[b] frames are real (a video shorter than F is one padded
+ * window; the padding is never folded).  The batch's hypotheses have been reduced to ONE pose state [B,T,F,J] - what
+ * pafuse_pose_partials, pafuse_pose_partials_fit or the `merged` output of pafuse_pose_combine writes for the union of
+ * P_total hypotheses - and / or one spread state; the folds below merge row (b,t,f,j) into frame row (t, starts[b] + f, j).
+ * Frame pose state, one flat 8-byte aligned buffer of pafuse_frame_pose_state_bytes = 48*r + 4*N rounded up to 8 bytes,
+ * r = T*N*J rows in (t,n,j) order:
+ *   double sum[r][3]; float e2[r]; int32 idx[r]; int32 win[r]; float sel[r][3]   as in a pose state; win: the GLOBAL window
+ *                       index of the candidate
+ *   int32 count[N]      the hypotheses folded into frame n
+ * Frame spread state, pafuse_frame_spread_state_bytes = (9*r + N)*8 bytes:  double sum[r][3]; double m2[r][6]; double count[N].
+ * The *_init entries write the neutral states: zero sums and counts, candidate (+inf, -1, -1, NaN NaN NaN); zero moments. */
+size_t pafuse_frame_pose_state_bytes(int32_t N, int32_t T, int32_t J);
+size_t pafuse_frame_spread_state_bytes(int32_t N, int32_t T, int32_t J);
+int pafuse_frame_pose_state_init(void *frame_state, size_t frame_bytes, int32_t N, int32_t T, int32_t J, void *stream);
+int pafuse_frame_spread_state_init(void *frame_state, size_t frame_bytes, int32_t N, int32_t T, int32_t J, void *stream);
+
+/* Folds the pose state of B windows into the frame state.  For every (n,t,j) the windows of the batch that cover frame n
+ * are visited in ascending order: sum += state.sum (one fp64 add per component and window), count[n] += P_total, and the
+ * candidate is replaced only if state.e2 < e2 (strict: among equal errors the lowest window keeps it, and within it the
+ * lowest hypothesis); idx takes the state's global hypothesis index, win takes w0 + b (w0: the global index of the
+ * batch's first window).  A gather - one thread per (n,t,j) of the frame range the batch touches; no atomics, no
+ * workspace; frames outside that range (and frames in a gap between two windows) are not touched.  A frame's windows
+ * arrive in ascending order whether they come in one batch or in several, so the result does not depend on the batching,
+ * provided the batches come in ascending window order.
+ * starts / valid are passed TWICE: device int32 [B], which the kernel reads, and host int32 [B] with the same values, which
+ * this entry checks (the call neither copies nor synchronises, so it can be captured).  Should the two differ, the kernel
+ * still reads inside the batch state and writes inside the frames the host copy names.
+ * Refused (PAFUSE_E_ARG): a null operand, N, T, F, J < 1 or B, w0, P_total < 0, a window reaching past N or starting below
+ * 0, valid outside 1 .. F, starts not strictly ascending, a short or misaligned state.  B == 0 launches nothing. */
+int pafuse_pose_windows_fold(void *frame_state, size_t frame_bytes, int32_t N, const void *state, size_t state_bytes,
+                             int32_t B, int32_t T, int32_t F, int32_t J, const int32_t *starts, const int32_t *valid,
+                             const int32_t *starts_host, const int32_t *valid_host, int32_t w0, int32_t P_total,
+                             void *stream);
+
+/* The same fold for a spread state (pafuse_spread_partials, or the `merged` output of pafuse_spread_combine): every
+ * covering window is merged into the frame by Chan's rule, the operations of pafuse_spread_combine in its order, fp64,
+ * contraction off; count[n] += the state's count per window.  A state with count 0 folds nothing.  Two kernels (the
+ * counts are written behind the fold, whose every thread reads them).  Operands and refusals as above. */
+int pafuse_spread_windows_fold(void *frame_state, size_t frame_bytes, int32_t N, const void *state, size_t state_bytes,
+                               int32_t B, int32_t T, int32_t F, int32_t J, const int32_t *starts, const int32_t *valid,
+                               const int32_t *starts_host, const int32_t *valid_host, void *stream);
+
+/* Writes any of (NULL: not wanted, at least one), from a frame pose state (frame_state; NULL when nothing of it is asked):
+ *   mean      [T,N,J,3] fp32 = sum / count[n], divided in fp64 and rounded once (count 0: NaN)
+ *   pick      [T,N,J,3] fp32, pick_idx [T,N,J] int32, pick_win [T,N,J] int32   the J-Agg pose, its hypothesis and its window
+ *                       (NaN, -1, -1 where no window offered a candidate)
+ * and from a frame spread state (frame_spread; NULL when nothing of it is asked), by the arithmetic of pafuse_spread_combine:
+ *   std_dev   [T,N,J] fp32,  cov [T,N,J,6] fp32   (count 0 or a non-finite hypothesis: NaN)
+ * Refused (PAFUSE_E_ARG): negative sizes, no output, an output without its state, misalignment, a grid out of range. */
+int pafuse_frames_finish(const void *frame_state, const void *frame_spread, int32_t N, int32_t T, int32_t J, float *mean,
+                         float *pick, int32_t *pick_idx, int32_t *pick_win, float *std_dev, float *cov, void *stream);
 
 /* Protocol #2 (P-MPJPE) on the same operands - common/loss.py:251-458 as main_h3wb.py:381-395 calls it: every
  * whole-body hypothesis pose (and, per (b,t,f), the mean over h of them) aligned to its whole-body target by the

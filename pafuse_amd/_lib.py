@@ -158,6 +158,15 @@ SIGNATURES = {
     "pafuse_spread_partials_bytes": (C.c_size_t, [C.c_int32] * 4),
     "pafuse_spread_partials": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "pafuse_spread_combine": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t] + [C.c_int32] * 4 + [C.c_void_p] * 5),
+    "pafuse_frame_pose_state_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "pafuse_frame_spread_state_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "pafuse_frame_pose_state_init": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_int32] * 3 + [C.c_void_p]),
+    "pafuse_frame_spread_state_init": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_int32] * 3 + [C.c_void_p]),
+    "pafuse_pose_windows_fold": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_size_t] + [C.c_int32] * 4 +
+                                 [C.c_void_p] * 4 + [C.c_int32] * 2 + [C.c_void_p]),
+    "pafuse_spread_windows_fold": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_size_t] + [C.c_int32] * 4 +
+                                   [C.c_void_p] * 5),
+    "pafuse_frames_finish": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p] * 7),
     "pafuse_procrustes_errors": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p] * 6),
     "pafuse_procrustes_partials_bytes": (C.c_size_t, [C.c_int32] * 5),
     "pafuse_procrustes_partials_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),

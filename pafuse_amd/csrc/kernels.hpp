@@ -3337,6 +3337,222 @@ __global__ void __launch_bounds__(64) spread_count_kernel(const char* states, in
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// Overlapping WINDOWS pooled into one state per video FRAME.  A video of N frames is cut into windows of F frames that
+// start at starts[b] (strictly ascending) and of which the first valid[b] frames are real (a video shorter than a window
+// is padded; the padding is never folded).  A batch of B windows has been reduced over its hypotheses to one pose state
+// [B,T,F,J] (and / or one spread state); the fold below maps (window, local frame) to the global frame n = start + f and
+// merges the row into the FRAME state, whose rows are (t, n, j) - the order of the outputs [T,N,J,..].
+//
+// Frame pose state, one flat buffer (r = T*N*J rows), 48*r + 4*N bytes rounded up to a multiple of 8:
+//   double sum[r][3] | float e2[r] | int32 idx[r] | int32 win[r] | float sel[r][3] | int32 count[N]
+// Frame spread state, (9*r + N)*8 bytes:  double sum[r][3] | double m2[r][6] | double count[N]
+// count[n]: the hypotheses folded into frame n (windows covering it x hypotheses per window).
+//
+// The fold is a GATHER: one thread per (t, n, j) of the frame range [n_lo, n_hi) the batch touches visits the windows of
+// the batch that cover n in ascending order (a binary search for the first start above n - F, then a walk while start <=
+// n), so a row is read and written by one thread only: no atomics, no workspace, no LDS.  Consecutive lanes are
+// consecutive j of one (window, t, f) row of the batch state and of one (t, n) row of the frame state.  Whatever the
+// device copies of starts / valid hold, a read stays inside the batch state (0 <= f < min(valid, F), b < B) and a write
+// inside the rows of [n_lo, n_hi), which the host checked against N.
+// ----------------------------------------------------------------------------------------------------------------
+// the first window of the batch that can cover frame n: the lowest b with starts[b] > n - F
+__device__ __forceinline__ int first_window_over(const int32_t* starts, int B, int n, int F) {
+    int lo = 0, hi = B;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (starts[mid] > n - F) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+struct PoseWindowsFoldParams {
+    double* f_sum;        // frame state (see above)
+    float* f_e2;
+    int32_t* f_idx;
+    int32_t* f_win;
+    float* f_sel;
+    int32_t* f_count;
+    const double* s_sum;  // the batch's pose state [B,T,F,J]
+    const float* s_e2;
+    const int32_t* s_idx;
+    const float* s_sel;
+    const int32_t* starts;  // [B] device
+    const int32_t* valid;   // [B] device
+    int N, B, T, F, J, w0, P, n_lo, n_hi;
+};
+
+__global__ void __launch_bounds__(256) pose_windows_fold_kernel(const PoseWindowsFoldParams p) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int span = p.n_hi - p.n_lo;
+    if (e >= (int64_t)p.T * span * p.J) return;
+    const int j = (int)(e % p.J);
+    const int n = p.n_lo + (int)((e / p.J) % span);
+    const int t = (int)(e / ((int64_t)p.J * span));
+    const int64_t row = ((int64_t)t * p.N + n) * p.J + j;
+    double s[3] = {p.f_sum[row * 3 + 0], p.f_sum[row * 3 + 1], p.f_sum[row * 3 + 2]};
+    float best2 = p.f_e2[row], sel[3] = {p.f_sel[row * 3 + 0], p.f_sel[row * 3 + 1], p.f_sel[row * 3 + 2]};
+    int32_t hsel = p.f_idx[row], wsel = p.f_win[row];
+    int covered = 0;
+    for (int b = first_window_over(p.starts, p.B, n, p.F); b < p.B && p.starts[b] <= n; ++b) {
+        const int f = n - p.starts[b];
+        if (f < 0 || f >= min(p.valid[b], p.F)) continue;   // a padded frame, or device tables that are not the host's
+        const int64_t se = (((int64_t)b * p.T + t) * p.F + f) * p.J + j;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s[k] += p.s_sum[se * 3 + k];
+        const float ew = p.s_e2[se];
+        if (ew < best2)   // strict: among equal errors the lowest window stays, and within it the lowest hypothesis
+            best2 = ew, hsel = p.s_idx[se], wsel = p.w0 + b, sel[0] = p.s_sel[se * 3 + 0], sel[1] = p.s_sel[se * 3 + 1],
+            sel[2] = p.s_sel[se * 3 + 2];
+        ++covered;
+    }
+    if (!covered) return;   // a gap between the windows of the batch: the frame is not touched
+    p.f_sum[row * 3 + 0] = s[0], p.f_sum[row * 3 + 1] = s[1], p.f_sum[row * 3 + 2] = s[2];
+    p.f_e2[row] = best2;
+    p.f_idx[row] = hsel;
+    p.f_win[row] = wsel;
+    p.f_sel[row * 3 + 0] = sel[0], p.f_sel[row * 3 + 1] = sel[1], p.f_sel[row * 3 + 2] = sel[2];
+    if (t == 0 && j == 0) {   // one thread per frame: count += P_total, once per window
+        int32_t c = p.f_count[n];
+        for (int k = 0; k < covered; ++k) c += p.P;
+        p.f_count[n] = c;
+    }
+}
+
+struct SpreadWindowsFoldParams {
+    double* frame;          // frame spread state (see above)
+    const double* state;    // the batch's spread state [B,T,F,J] and its count
+    const int32_t* starts;  // [B] device
+    const int32_t* valid;   // [B] device
+    int N, B, T, F, J, n_lo, n_hi;
+};
+
+// Chan's rule per covering window, the operations of spread_combine_kernel in its order.  Every thread of a frame reads
+// count[n]: it is therefore NOT written here but by spread_windows_count_kernel, launched behind this kernel.
+__global__ void __launch_bounds__(256) spread_windows_fold_kernel(const SpreadWindowsFoldParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int span = p.n_hi - p.n_lo;
+    if (e >= (int64_t)p.T * span * p.J) return;
+    const int j = (int)(e % p.J);
+    const int n = p.n_lo + (int)((e / p.J) % span);
+    const int t = (int)(e / ((int64_t)p.J * span));
+    const int64_t rows = (int64_t)p.T * p.N * p.J, srows = (int64_t)p.B * p.T * p.F * p.J;
+    const int64_t row = ((int64_t)t * p.N + n) * p.J + j;
+    const double nb = p.state[9 * srows];
+    if (nb == 0.0) return;            // an empty batch state: nothing to merge and no 0/0
+    double* fs = p.frame + row * 3;
+    double* fm = p.frame + 3 * rows + row * 6;
+    double na = p.frame[9 * rows + n], s[3], m[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] = fs[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) m[k] = fm[k];
+    int covered = 0;
+    for (int b = first_window_over(p.starts, p.B, n, p.F); b < p.B && p.starts[b] <= n; ++b) {
+        const int f = n - p.starts[b];
+        if (f < 0 || f >= min(p.valid[b], p.F)) continue;
+        const int64_t se = (((int64_t)b * p.T + t) * p.F + f) * p.J + j;
+        const double* sb = p.state + se * 3;
+        const double* mb = p.state + 3 * srows + se * 6;
+        ++covered;
+        if (na == 0.0) {              // the first window of a frame goes through as it is
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s[k] = sb[k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) m[k] = mb[k];
+            na = nb;
+            continue;
+        }
+        const double fac = na * nb / (na + nb);
+        double dl[3], b3[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) b3[k] = sb[k], dl[k] = b3[k] / nb - s[k] / na;
+        m[0] = (m[0] + mb[0]) + dl[0] * dl[0] * fac, m[1] = (m[1] + mb[1]) + dl[0] * dl[1] * fac;
+        m[2] = (m[2] + mb[2]) + dl[0] * dl[2] * fac, m[3] = (m[3] + mb[3]) + dl[1] * dl[1] * fac;
+        m[4] = (m[4] + mb[4]) + dl[1] * dl[2] * fac, m[5] = (m[5] + mb[5]) + dl[2] * dl[2] * fac;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s[k] += b3[k];
+        na += nb;
+    }
+    if (!covered) return;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) fs[k] = s[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) fm[k] = m[k];
+}
+
+// the counts of the frames the batch touches: count[n] += the batch state's count, once per covering window, by one
+// thread per frame, after every thread of spread_windows_fold_kernel has read them (stream order)
+__global__ void __launch_bounds__(256) spread_windows_count_kernel(const SpreadWindowsFoldParams p) {
+    const int n = p.n_lo + (int)(blockIdx.x * 256 + threadIdx.x);
+    if (n >= p.n_hi) return;
+    const int64_t rows = (int64_t)p.T * p.N * p.J, srows = (int64_t)p.B * p.T * p.F * p.J;
+    const double nb = p.state[9 * srows];
+    double c = p.frame[9 * rows + n];
+    int covered = 0;
+    for (int b = first_window_over(p.starts, p.B, n, p.F); b < p.B && p.starts[b] <= n; ++b) {
+        const int f = n - p.starts[b];
+        if (f < 0 || f >= min(p.valid[b], p.F)) continue;
+        c += nb;
+        ++covered;
+    }
+    if (covered) p.frame[9 * rows + n] = c;
+}
+
+struct FramesFinishParams {
+    const double* f_sum;     // frame pose state (null: none)
+    const int32_t* f_idx;
+    const int32_t* f_win;
+    const float* f_sel;
+    const int32_t* f_count;
+    const double* spread;    // frame spread state (null: none)
+    float* mean;             // [T,N,J,3] (null: not wanted)
+    float* pick;             // [T,N,J,3]
+    int32_t* pick_idx;       // [T,N,J]
+    int32_t* pick_win;       // [T,N,J]
+    float* sd;               // [T,N,J]
+    float* cov;              // [T,N,J,6]
+    int N, T, J;
+};
+
+// one thread per (t, n, j): the mean is sum / count[n] in fp64, rounded once (count 0: NaN); std and cov by the arithmetic
+// of spread_combine_kernel
+__global__ void __launch_bounds__(256) frames_finish_kernel(const FramesFinishParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t rows = (int64_t)p.T * p.N * p.J;
+    if (e >= rows) return;
+    const int n = (int)((e / p.J) % p.N);
+    if (p.mean) {
+        const double P = (double)p.f_count[n];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p.mean[e * 3 + k] = (float)(p.f_sum[e * 3 + k] / P);
+    }
+    if (p.pick) p.pick[e * 3 + 0] = p.f_sel[e * 3 + 0], p.pick[e * 3 + 1] = p.f_sel[e * 3 + 1], p.pick[e * 3 + 2] = p.f_sel[e * 3 + 2];
+    if (p.pick_idx) p.pick_idx[e] = p.f_idx[e];
+    if (p.pick_win) p.pick_win[e] = p.f_win[e];
+    if (p.sd || p.cov) {
+        const double na = p.spread[9 * rows + n];
+        double s[3], m[6];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s[k] = p.spread[e * 3 + k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) m[k] = p.spread[3 * rows + e * 6 + k];
+        bool fine = na > 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fine = fine && isfinite(s[k]);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) fine = fine && isfinite(m[k]);
+        const float qnan = __builtin_nanf("");
+        if (p.cov) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) p.cov[e * 6 + k] = fine ? (float)(m[k] / na) : qnan;
+        }
+        if (p.sd) p.sd[e] = fine ? (float)sqrt(((m[0] + m[3]) + m[5]) / na) : qnan;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // Protocol #2 (P-MPJPE) behind the all-gather: common/loss.py:251-458 as main_h3wb.py:381-395 calls it on the
 // whole-body poses.  Every hypothesis pose Y is aligned to its target X by the similarity transform of the
 // reference (centre both, H = (X0/|X0|)^T (Y0/|Y0|), R = V U^T with the reflection fix, a = tr(S') |X0| / |Y0|) and

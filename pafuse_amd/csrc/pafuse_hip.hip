@@ -1977,6 +1977,145 @@ int pafuse_spread_combine(const void* states, int32_t W, size_t stride_bytes, in
     return launch<spread_count_kernel>("spread_count_kernel", 1, 64, 0, (hipStream_t)stream, lo, (int64_t)stride_bytes, W, n, (double*)merged);
 }
 
+// frame pose state: double sum[r][3] | float e2[r] | int32 idx[r] | int32 win[r] | float sel[r][3] | int32 count[N], r = T*N*J
+size_t pafuse_frame_pose_state_bytes(int32_t N, int32_t T, int32_t J) {
+    if (N <= 0 || T <= 0 || J <= 0) return 0;
+    return ((size_t)N * T * J * 48 + (size_t)N * 4 + 7) / 8 * 8;
+}
+
+// frame spread state: double sum[r][3] | double m2[r][6] | double count[N]
+size_t pafuse_frame_spread_state_bytes(int32_t N, int32_t T, int32_t J) {
+    if (N <= 0 || T <= 0 || J <= 0) return 0;
+    return ((size_t)N * T * J * 9 + (size_t)N) * 8;
+}
+
+namespace {
+struct FramePoseViews {
+    double* sum; float* e2; int32_t* idx; int32_t* win; float* sel; int32_t* count;
+    FramePoseViews(void* state, int64_t rows) {
+        char* st = (char*)state;
+        sum = (double*)st, e2 = (float*)(st + rows * 24), idx = (int32_t*)(e2 + rows), win = idx + rows;
+        sel = (float*)(win + rows), count = (int32_t*)(sel + 3 * rows);
+    }
+};
+
+// what both folds check of their window tables (the HOST copies) before anything is launched; -> the frame range touched
+int check_windows(const char* who, const int32_t* starts, const int32_t* valid, int32_t B, int32_t F, int32_t N, int* n_lo, int* n_hi) {
+    int hi = 0;
+    for (int b = 0; b < B; ++b) {
+        if (valid[b] < 1 || valid[b] > F) return fail(PAFUSE_E_ARG, "%s: valid[%d] = %d outside 1 .. %d", who, b, valid[b], F);
+        if (starts[b] < 0 || (int64_t)starts[b] + valid[b] > N)
+            return fail(PAFUSE_E_ARG, "%s: window %d covers frames [%d, %lld) of %d", who, b, starts[b], (long long)starts[b] + valid[b], N);
+        if (b && starts[b] <= starts[b - 1]) return fail(PAFUSE_E_ARG, "%s: starts must ascend strictly (window %d)", who, b);
+        hi = starts[b] + valid[b] > hi ? starts[b] + valid[b] : hi;
+    }
+    *n_lo = starts[0], *n_hi = hi;
+    return PAFUSE_OK;
+}
+}  // namespace
+
+int pafuse_frame_pose_state_init(void* frame_state, size_t frame_bytes, int32_t N, int32_t T, int32_t J, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (N < 0 || T <= 0 || J <= 0) return fail(PAFUSE_E_ARG, "frame_pose_state_init: bad size");
+    const size_t need = pafuse_frame_pose_state_bytes(N, T, J);
+    if (need == 0) return PAFUSE_OK;
+    if (!frame_state || frame_bytes < need) return fail(PAFUSE_E_ARG, "frame_pose_state_init: the state needs %zu bytes", need);
+    if ((uintptr_t)frame_state % 8) return fail(PAFUSE_E_ARG, "frame_pose_state_init: the state must be 8-byte aligned");
+    const int64_t rows = (int64_t)N * T * J;
+    FramePoseViews v(frame_state, rows);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = pose_neutral_state("frame_pose_state_init", v.sum, v.e2, v.idx, v.sel, rows, s)) return rc;
+    hipError_t e = hipMemsetAsync(v.win, 0xff, (size_t)rows * 4, s);
+    if (e == hipSuccess) e = hipMemsetAsync(v.count, 0, (size_t)N * 4, s);
+    if (e != hipSuccess) return fail(PAFUSE_E_HIP, "frame_pose_state_init: %s", hipGetErrorString(e));
+    return PAFUSE_OK;
+}
+
+int pafuse_frame_spread_state_init(void* frame_state, size_t frame_bytes, int32_t N, int32_t T, int32_t J, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (N < 0 || T <= 0 || J <= 0) return fail(PAFUSE_E_ARG, "frame_spread_state_init: bad size");
+    const size_t need = pafuse_frame_spread_state_bytes(N, T, J);
+    if (need == 0) return PAFUSE_OK;
+    if (!frame_state || frame_bytes < need) return fail(PAFUSE_E_ARG, "frame_spread_state_init: the state needs %zu bytes", need);
+    if ((uintptr_t)frame_state % 8) return fail(PAFUSE_E_ARG, "frame_spread_state_init: the state must be 8-byte aligned");
+    hipError_t e = hipMemsetAsync(frame_state, 0, need, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PAFUSE_E_HIP, "frame_spread_state_init: %s", hipGetErrorString(e));
+    return PAFUSE_OK;
+}
+
+int pafuse_pose_windows_fold(void* frame_state, size_t frame_bytes, int32_t N, const void* state, size_t state_bytes, int32_t B,
+                             int32_t T, int32_t F, int32_t J, const int32_t* starts, const int32_t* valid,
+                             const int32_t* starts_host, const int32_t* valid_host, int32_t w0, int32_t P_total, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (N <= 0 || B < 0 || T <= 0 || F <= 0 || J <= 0 || w0 < 0 || P_total < 0) return fail(PAFUSE_E_ARG, "pose_windows_fold: bad size");
+    const size_t fneed = pafuse_frame_pose_state_bytes(N, T, J);
+    if (!frame_state || frame_bytes < fneed) return fail(PAFUSE_E_ARG, "pose_windows_fold: the frame state needs %zu bytes", fneed);
+    if (B == 0) return PAFUSE_OK;   // nothing to fold, nothing is launched
+    if (!state || !starts || !valid || !starts_host || !valid_host) return fail(PAFUSE_E_ARG, "pose_windows_fold: null pointer");
+    const size_t need = pafuse_pose_partials_bytes(B, T, F, J);
+    if (state_bytes < need) return fail(PAFUSE_E_ARG, "pose_windows_fold: the batch state needs %zu bytes", need);
+    if ((uintptr_t)frame_state % 8 || (uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "pose_windows_fold: states must be 8-byte aligned");
+    int n_lo = 0, n_hi = 0;
+    if (int rc = check_windows("pose_windows_fold", starts_host, valid_host, B, F, N, &n_lo, &n_hi)) return rc;
+    const int64_t rows = (int64_t)N * T * J, sn = (int64_t)B * T * F * J, work = (int64_t)T * (n_hi - n_lo) * J;
+    if ((work + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "pose_windows_fold: grid out of range");
+    FramePoseViews v(frame_state, rows);
+    PoseWindowsFoldParams m{};
+    m.f_sum = v.sum, m.f_e2 = v.e2, m.f_idx = v.idx, m.f_win = v.win, m.f_sel = v.sel, m.f_count = v.count;
+    const char* st = (const char*)state;
+    m.s_sum = (const double*)st, m.s_e2 = (const float*)(st + sn * 24), m.s_idx = (const int32_t*)(m.s_e2 + sn);
+    m.s_sel = (const float*)(m.s_idx + sn);
+    m.starts = starts, m.valid = valid;
+    m.N = N, m.B = B, m.T = T, m.F = F, m.J = J, m.w0 = w0, m.P = P_total, m.n_lo = n_lo, m.n_hi = n_hi;
+    return launch<pose_windows_fold_kernel>("pose_windows_fold_kernel", blocks_for(work), 256, 0, (hipStream_t)stream, m);
+}
+
+int pafuse_spread_windows_fold(void* frame_state, size_t frame_bytes, int32_t N, const void* state, size_t state_bytes, int32_t B,
+                               int32_t T, int32_t F, int32_t J, const int32_t* starts, const int32_t* valid,
+                               const int32_t* starts_host, const int32_t* valid_host, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (N <= 0 || B < 0 || T <= 0 || F <= 0 || J <= 0) return fail(PAFUSE_E_ARG, "spread_windows_fold: bad size");
+    const size_t fneed = pafuse_frame_spread_state_bytes(N, T, J);
+    if (!frame_state || frame_bytes < fneed) return fail(PAFUSE_E_ARG, "spread_windows_fold: the frame state needs %zu bytes", fneed);
+    if (B == 0) return PAFUSE_OK;   // nothing to fold, nothing is launched
+    if (!state || !starts || !valid || !starts_host || !valid_host) return fail(PAFUSE_E_ARG, "spread_windows_fold: null pointer");
+    const size_t need = pafuse_spread_partials_bytes(B, T, F, J);
+    if (state_bytes < need) return fail(PAFUSE_E_ARG, "spread_windows_fold: the batch state needs %zu bytes", need);
+    if ((uintptr_t)frame_state % 8 || (uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "spread_windows_fold: states must be 8-byte aligned");
+    int n_lo = 0, n_hi = 0;
+    if (int rc = check_windows("spread_windows_fold", starts_host, valid_host, B, F, N, &n_lo, &n_hi)) return rc;
+    const int64_t work = (int64_t)T * (n_hi - n_lo) * J;
+    if ((work + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "spread_windows_fold: grid out of range");
+    SpreadWindowsFoldParams m{};
+    m.frame = (double*)frame_state, m.state = (const double*)state, m.starts = starts, m.valid = valid;
+    m.N = N, m.B = B, m.T = T, m.F = F, m.J = J, m.n_lo = n_lo, m.n_hi = n_hi;
+    if (int rc = launch<spread_windows_fold_kernel>("spread_windows_fold_kernel", blocks_for(work), 256, 0, (hipStream_t)stream, m)) return rc;
+    // the counts, behind the kernel whose every thread reads them
+    return launch<spread_windows_count_kernel>("spread_windows_count_kernel", blocks_for(n_hi - n_lo), 256, 0, (hipStream_t)stream, m);
+}
+
+int pafuse_frames_finish(const void* frame_state, const void* frame_spread, int32_t N, int32_t T, int32_t J, float* mean,
+                         float* pick, int32_t* pick_idx, int32_t* pick_win, float* std_dev, float* cov, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (N < 0 || T <= 0 || J <= 0) return fail(PAFUSE_E_ARG, "frames_finish: bad size");
+    const bool pose = mean || pick || pick_idx || pick_win, spread = std_dev || cov;
+    if (!pose && !spread) return fail(PAFUSE_E_ARG, "frames_finish: nothing to write");
+    if (N == 0) return PAFUSE_OK;
+    if ((pose && !frame_state) || (spread && !frame_spread)) return fail(PAFUSE_E_ARG, "frames_finish: null pointer");
+    if ((uintptr_t)frame_state % 8 || (uintptr_t)frame_spread % 8) return fail(PAFUSE_E_ARG, "frames_finish: states must be 8-byte aligned");
+    const int64_t rows = (int64_t)N * T * J;
+    if ((rows + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "frames_finish: grid out of range");
+    FramesFinishParams m{};
+    if (pose) {
+        FramePoseViews v((void*)frame_state, rows);
+        m.f_sum = v.sum, m.f_idx = v.idx, m.f_win = v.win, m.f_sel = v.sel, m.f_count = v.count;
+    }
+    m.spread = spread ? (const double*)frame_spread : nullptr;
+    m.mean = mean, m.pick = pick, m.pick_idx = pick_idx, m.pick_win = pick_win, m.sd = std_dev, m.cov = cov;
+    m.N = N, m.T = T, m.J = J;
+    return launch<frames_finish_kernel>("frames_finish_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
+}
+
 int pafuse_procrustes_errors(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,
                              const int32_t* conn, int32_t B, int32_t T, int32_t P, int32_t F, int32_t J, float* jbest,
                              double* pbest_sums, float* pagg, float* jagg, int32_t* pick, void* stream) {

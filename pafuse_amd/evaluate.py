@@ -470,7 +470,7 @@ def _accumulate_poses_fit(state, pred_local, h0, dataset, inputs_2d, traj, cam, 
 
 
 def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=None, traj=None, cam=None, group=None,
-                            state=None, want=None, spread_state=None):
+                            state=None, want=None, spread_state=None, merged=False):
     """The aggregates as poses without ever holding all P hypotheses: pred_local [B,T,P_r,F,J,3] holds the part-centred
     hypotheses [h0, h0 + P_r) of the `num_proposals` of the run - this rank's share (pafuse_amd.parallel.shard_range) or,
     with `state`, the last chunk of it (`state`: what accumulate_poses returned for the chunks before; pred_local=None
@@ -484,7 +484,12 @@ def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=No
     `spread_state` (what accumulate_spread returned for the same hypotheses; a last chunk pred_local is folded into it
     too) adds the names "cov" [B,T,F,J,6] and "std" [B,T,F,J] (ops.combine_spread); its 72 bytes per (b,t,f,j) ride in
     the same all-gather behind the pose state.  `state` may then be None: the spread state holds the sums, so "mean" comes
-    from it - the same bits, there is no pick.  Without a spread state nothing changes, and "cov" / "std" are refused."""
+    from it - the same bits, there is no pick.  Without a spread state nothing changes, and "cov" / "std" are refused.
+
+    merged=True also hands back the state of the UNION across ranks and chunks, as the same combine call writes it: "state"
+    (the flat pose state, ops.pose_views; absent without a pose state), "spread_state" (ops.spread_views; with a spread
+    state) and "shape" = (B,T,F,J) - what accumulate_frames folds into per-frame states.  `want` may then be empty.  Every
+    rank holds the same merged states."""
     from . import ops
     if pred_local is not None:
         if state is not None or spread_state is None or inputs_2d is not None:
@@ -502,9 +507,15 @@ def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=No
     if spread_state is None and ("cov" in want or "std" in want):
         raise ValueError('aggregate_poses_sharded: "cov" and "std" need a spread state (accumulate_spread)')
     P = int(num_proposals)
+    union = lambda like: torch.empty(like.shape[1], device=like.device, dtype=torch.float64) if merged else None
     if spread_state is None:
         (states, _), = _exchange([(state.head, None)], state.h0, state.count, P, group, state.device)
-        return ops.combine_poses(states.contiguous(), state.shape, P, want=want, no_pick_ok=state.fit)
+        states = states.contiguous()
+        into = union(states)
+        out = ops.combine_poses(states, state.shape, P, merged=into, want=want, no_pick_ok=state.fit)
+        if merged:
+            out.update(state=into, shape=state.shape)
+        return out
     first = spread_state if state is None else state
     if state is not None and (state.shape != spread_state.shape or state.device != spread_state.device
                               or (state.h0, state.count) != (spread_state.h0, spread_state.count)):
@@ -515,11 +526,19 @@ def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=No
     from_pose = tuple(k for k in want if k in ("pick", "idx") or (k == "mean" and state is not None))
     from_spread = tuple(k for k in want if k not in from_pose)
     out = {}
-    if from_pose:
-        out.update(ops.combine_poses(got[0][0].contiguous(), first.shape, P, want=from_pose,
+    if from_pose or (merged and state is not None):
+        states = got[0][0].contiguous()
+        into = union(states)
+        out.update(ops.combine_poses(states, first.shape, P, merged=into, want=from_pose,
                                      no_pick_ok=state is not None and state.fit))
-    if from_spread:
-        out.update(ops.combine_spread(got[-1][0].contiguous(), first.shape, want=from_spread))
+        if merged:
+            out["state"] = into
+    if from_spread or merged:
+        states = got[-1][0].contiguous()
+        into = union(states)
+        out.update(ops.combine_spread(states, first.shape, merged=into, want=from_spread))
+        if merged:
+            out.update(spread_state=into, shape=first.shape)
     return out
 
 
@@ -544,3 +563,45 @@ def accumulate_spread(state, pred_local, h0, dataset):
     return state.fold(who, P_c, h0, ops.spread_partials_bytes(B, T, F, J) // 8, None,
                       lambda row: ops.spread_partials(pred, conn, int(h0), out=row),
                       lambda slots: ops.combine_spread(slots, shape, merged=slots[0], want=()))
+
+
+# ----------------------------------------------------------------- overlapping windows pooled into one pose per frame
+class FrameState:
+    """The running per-frame reduction of the windows folded so far (ops.frame_views): `pose` the frame pose state - 48
+    bytes per (t,n,j) and a count per frame - or None, `spread` the frame spread state (72 bytes) or None, `windows` the
+    number of windows folded (the global index of the next batch's first window)."""
+
+    def __init__(self, N, T, J, device):
+        self.N, self.T, self.J, self.device = int(N), int(T), int(J), device
+        self.pose = self.spread = None
+        self.windows = 0
+
+
+def accumulate_frames(frames, merged, starts, valid, N, num_proposals):
+    """Fold one batch of windows into the per-frame state `frames` (None: start one over N video frames) and return it.
+    `merged`: what aggregate_poses_sharded(..., merged=True) returned for the batch - the pose and / or spread state of
+    the union of the `num_proposals` hypotheses across ranks and chunks, so the fold happens behind the cross-rank combine,
+    every rank holds the same frame state and no collective is added.  starts, valid: the batch's rows of
+    pafuse_amd.windows.window_starts (host integers); batches come in ascending window order.  Memory: the frame states
+    and the batch's merged states - nothing grows with the number of windows.  ops.finish_frames writes the result."""
+    from . import ops
+    if "shape" not in merged or not ("state" in merged or "spread_state" in merged):
+        raise ValueError("accumulate_frames: needs the merged states of aggregate_poses_sharded(..., merged=True)")
+    B, T, F, J = merged["shape"]
+    first = merged["state"] if "state" in merged else merged["spread_state"]
+    if frames is None:
+        frames = FrameState(N, T, J, first.device)
+        if "state" in merged:
+            frames.pose = ops.frame_state(N, T, J, first.device)
+        if "spread_state" in merged:
+            frames.spread = ops.frame_state(N, T, J, first.device, spread=True)
+    if (frames.N, frames.T, frames.J, frames.device) != (int(N), T, J, first.device):
+        raise ValueError(f"accumulate_frames: the frame state holds {(frames.N, frames.T, frames.J)}, the batch {(int(N), T, J)}")
+    if (frames.pose is None) != ("state" not in merged) or (frames.spread is None) != ("spread_state" not in merged):
+        raise ValueError("accumulate_frames: every batch brings the states the first one brought")
+    if frames.pose is not None:
+        ops.fold_windows(frames.pose, N, merged["state"], (B, T, F, J), starts, valid, frames.windows, num_proposals)
+    if frames.spread is not None:
+        ops.fold_spread_windows(frames.spread, N, merged["spread_state"], (B, T, F, J), starts, valid)
+    frames.windows += B
+    return frames

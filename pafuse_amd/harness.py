@@ -5,7 +5,7 @@ or Hydra here; the caller hands in arrays).
 """
 import torch
 
-from .evaluate import (accumulate_partials, accumulate_poses, accumulate_spread, aggregate_poses_sharded,
+from .evaluate import (accumulate_frames, accumulate_partials, accumulate_poses, accumulate_spread, aggregate_poses_sharded,
                        evaluate_accumulators, evaluate_accumulators_sharded)
 from .parallel import ShardedSampler
 
@@ -64,7 +64,7 @@ def wb_pose_from_parts(pose, dataset):
 
 @torch.no_grad()
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
-                   hypothesis_chunk=None, spread=None, conf=None):
+                   hypothesis_chunk=None, spread=None, conf=None, stride=None):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -90,7 +90,23 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     ``"pose"`` as above, ``"idx"`` for "reproj", ``"std"`` [clips,T,F,J] - the RMS distance in metres of the P whole-body
     hypotheses from their mean joint - and, for ``spread="cov"``, ``"cov"`` [clips,T,F,J,6], their population covariance
     (xx, xy, xz, yy, yz, zz).  With "mean" only the spread state is kept (it holds the sums: the pose is the same, bit
-    for bit); with "reproj" every chunk is folded into both states.  Both are taken about the MEAN pose."""
+    for bit); with "reproj" every chunk is folded into both states.  Both are taken about the MEAN pose.
+
+    ``stride`` (with an ``aggregate``; None: everything above, unchanged) slides the F-frame window over the video with that
+    stride, 1 .. F (pafuse_amd.windows.window_starts: starts 0, s, 2s, ... and a last window at N - F), and pools the windows
+    on the device into ONE pose per video frame: a frame covered by m windows is aggregated over its m x P hypotheses - the
+    mean over all of them, the J-Agg pick the first minimum in (window, hypothesis) order, the spread about the pooled mean
+    (evaluate.accumulate_frames, behind the cross-rank combine; 48 + 72 bytes per (t,frame,j) stay on the device however many
+    windows there are).  Sampling costs about F / stride times as much.  The return value is a dict of CPU tensors:
+    ``"pose"`` [T,N,J,3], ``"count"`` [N] (the hypotheses pooled per frame), for the reprojection aggregates ``"idx"`` and
+    ``"window"`` [T,N,J] (the pick's hypothesis and its window; -1 without one), with ``spread`` ``"std"`` [T,N,J] and
+    ``"cov"`` [T,N,J,6].  traj and conf are cut per window; with "reproj_fit" a joint without a pick carries the pooled mean.
+    stride = F visits exactly the clips of cut_clips."""
+    if stride is not None:
+        if isinstance(stride, bool) or int(stride) != stride or not 1 <= int(stride) <= model.frames:
+            raise ValueError(f"stride must be an integer in 1 .. {model.frames} (the window length), got {stride!r}")
+        if aggregate is None:
+            raise ValueError('stride needs aggregate="mean", "reproj" or "reproj_fit": the hypotheses per frame would be ragged')
     if aggregate not in (None, "mean", "reproj", "reproj_fit"):
         raise ValueError(f'aggregate must be None, "mean", "reproj" or "reproj_fit", got {aggregate!r}')
     if spread not in (None, "std", "cov"):
@@ -113,6 +129,9 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     elif conf is not None:
         raise ValueError('conf belongs to aggregate="reproj_fit"')
     dev = next(model.parameters()).device
+    if stride is not None:
+        return _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
+                             spread, conf, int(stride), dev)
     x2d = cut_clips(seq_2d, model.frames).to(dev)
     x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), model.frames).to(dev)
     sampler = ShardedSampler(model, group)
@@ -160,6 +179,65 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     if spread is not None:
         return {("pose" if k == pose_name else k): v for k, v in kept.items()}
     return (kept["pick"], kept["idx"]) if reproj else kept["mean"]
+
+
+def cut_windows(seq, starts, frames=27):
+    """[N, ...] -> [len(starts), frames, ...]: the windows that begin at `starts` (pafuse_amd.windows.window_starts); a
+    sequence shorter than a window is padded by repeating its final frame, as cut_clips pads it."""
+    n = seq.shape[0]
+    if n < frames:
+        seq = torch.cat([seq, seq[-1:].expand(frames - n, *seq.shape[1:])], dim=0)
+    return torch.stack([seq[int(s):int(s) + frames] for s in starts])
+
+
+def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
+                  conf, stride, dev):
+    """infer_sequence(stride=...): sliding windows pooled into one pose per video frame (arguments already checked)"""
+    from . import ops
+    from .windows import window_starts
+    if seq_2d.dim() == 4:
+        seq_2d = seq_2d.squeeze(0)
+    N, F = seq_2d.shape[0], model.frames
+    starts, valid = window_starts(N, F, stride)
+    fit, reproj = aggregate == "reproj_fit", aggregate in ("reproj", "reproj_fit")
+    x2d = cut_windows(seq_2d, starts, F).to(dev)
+    x2d_flip = cut_windows(flip_2d(seq_2d, kps_left, kps_right), starts, F).to(dev)
+    if reproj:
+        cam = torch.as_tensor(cam, dtype=torch.float32).to(dev)
+    if fit and conf is not None:
+        conf = cut_windows(conf, starts, F).to(dev)                                    # [windows,F,J]
+    elif reproj and not fit:
+        traj = torch.as_tensor(traj, dtype=torch.float32)
+        if traj.dim() != 2 or tuple(traj.shape) != (N, 3):
+            raise ValueError(f"traj must be [N,3] with N = {N} frames, got {tuple(traj.shape)}")
+        traj = cut_windows(traj, starts, F).to(dev)                                    # [windows,F,3]
+    sampler = ShardedSampler(model, group)
+    frames = None
+    for lo in range(0, x2d.shape[0], batch_size):
+        hi = min(lo + batch_size, x2d.shape[0])
+        state = moments = None
+        for pred, h0, _ in sampler.sample_chunks(x2d[lo:hi], None, input_2d_flip=x2d_flip[lo:hi], chunk=hypothesis_chunk):
+            if fit:
+                state = accumulate_poses(state, pred, h0, dataset, x2d[lo:hi], None, cam, fit=True,
+                                         conf=None if conf is None else conf[lo:hi])
+            elif reproj:
+                state = accumulate_poses(state, pred, h0, dataset, x2d[lo:hi], traj[lo:hi], cam)
+            else:
+                state = accumulate_poses(state, pred, h0, dataset)
+            if spread is not None:
+                moments = accumulate_spread(moments, pred, h0, dataset)
+            del pred
+        merged = aggregate_poses_sharded(None, None, model.num_proposals, dataset, group=group, state=state, want=(),
+                                         spread_state=moments, merged=True)
+        frames = accumulate_frames(frames, merged, starts[lo:hi], valid[lo:hi], N, model.num_proposals)
+    want = (("mean", "count") + (("pick", "idx", "window") if reproj else ())
+            + (() if spread is None else ("std",) if spread == "std" else ("std", "cov")))
+    out = ops.finish_frames(N, frames.T, frames.J, frame=frames.pose, spread=frames.spread, want=want)
+    if fit:         # a joint without a pick carries the pooled mean
+        out["pick"] = torch.where((out["idx"] < 0).unsqueeze(-1), out["mean"], out["pick"])
+    out["pose"] = out.pop("pick") if reproj else out["mean"]
+    out.pop("mean", None)
+    return {k: v.cpu() for k, v in out.items()}
 
 
 def load_pifpaf_keypoints(path, num_kps=134, with_conf=False):

@@ -1135,6 +1135,146 @@ def combine_spread(states, shape, merged=None, want=("mean", "cov", "std")):
     return out
 
 
+# ----------------------------------------------------------------- overlapping windows pooled into one pose per frame
+FRAME_POSE_BYTES_PER_ROW = 48   # double sum[3] + float e2 + int32 idx + int32 win + float sel[3] per (t, n, j); + int32 count per frame
+FRAME_OUTPUTS = {"mean": ((3,), torch.float32), "pick": ((3,), torch.float32), "idx": ((), torch.int32), "window": ((), torch.int32),
+                 "std": ((), torch.float32), "cov": ((6,), torch.float32)}      # trailing shape and dtype behind [T,N,J]
+
+
+def frame_state_bytes(N, T, J, spread=False):
+    """Bytes of a frame state over N video frames (the formulas of pafuse_frame_pose_state_bytes / _spread_state_bytes):
+    pose 48 per (t,n,j) + 4 per frame, rounded up to 8; spread 72 per (t,n,j) + 8 per frame."""
+    if min(N, T, J) <= 0:
+        return 0
+    return (9 * N * T * J + N) * 8 if spread else (FRAME_POSE_BYTES_PER_ROW * N * T * J + 4 * N + 7) // 8 * 8
+
+
+def frame_state(N, T, J, device="cuda", spread=False, out=None):
+    """The NEUTRAL frame state of N video frames as a flat float64 tensor (pafuse_frame_pose_state_init /
+    pafuse_frame_spread_state_init): zero sums and counts and no candidate (+inf, -1, -1, NaN NaN NaN); spread=True: the
+    frame spread state, all zeros.  `out`: a float64 buffer at least that long to write into."""
+    lib = _lib.load()
+    N, T, J = int(N), int(T), int(J)
+    _need(N > 0 and T > 0 and J > 0, "frame_state: N, T, J > 0")
+    dev = out.device if out is not None else torch.empty(0, device=device).device
+    _need(dev.type == "cuda", "frame_state: a HIP device (no CPU fallback)")
+    need = int((lib.pafuse_frame_spread_state_bytes if spread else lib.pafuse_frame_pose_state_bytes)(N, T, J))
+    assert need == frame_state_bytes(N, T, J, spread)
+    out = _state_out("frame_state", out, need, dev)
+    init = lib.pafuse_frame_spread_state_init if spread else lib.pafuse_frame_pose_state_init
+    with torch.cuda.device(out.device):
+        _lib.check(init(out.data_ptr(), out.numel() * 8, N, T, J, _stream(out)))
+    return out
+
+
+def frame_views(state, N, T, J, spread=False):
+    """Typed views of a flat frame state: pose - sum [T,N,J,3] f64, e2 [T,N,J] f32, idx, win [T,N,J] i32, sel [T,N,J,3] f32,
+    count [N] i32; spread=True - sum [T,N,J,3], m2 [T,N,J,6], count [N], all f64."""
+    r = N * T * J
+    _need(state.dim() == 1 and state.dtype == torch.float64 and state.is_contiguous() and r > 0
+          and state.numel() * 8 >= frame_state_bytes(N, T, J, spread), "frame_views: not a frame state of these sizes")
+    if spread:
+        return {"sum": state[:3 * r].view(T, N, J, 3), "m2": state[3 * r:9 * r].view(T, N, J, 6), "count": state[9 * r:9 * r + N]}
+    f32 = state[3 * r:].view(torch.float32)
+    i32 = f32.view(torch.int32)
+    return {"sum": state[:3 * r].view(T, N, J, 3), "e2": f32[:r].view(T, N, J), "idx": i32[r:2 * r].view(T, N, J),
+            "win": i32[2 * r:3 * r].view(T, N, J), "sel": f32[3 * r:6 * r].view(T, N, J, 3), "count": i32[6 * r:6 * r + N]}
+
+
+def _fold_operands(who, frame, N, state, shape, starts, valid, spread):
+    import numpy as np
+    B, T, F, J = (int(v) for v in shape)
+    N = int(N)
+    _need(B >= 0 and T > 0 and F > 0 and J > 0 and N > 0, f"{who}: bad shape")
+    for name, t in (("frame", frame), ("state", state)):
+        _need(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 1 and t.is_contiguous(),
+              f"{who}: {name} must be a flat float64 tensor on a HIP device (no CPU fallback)")
+    _need(state.device == frame.device, f"{who}: frame and state on one device")
+    _need(frame.numel() * 8 >= frame_state_bytes(N, T, J, spread), f"{who}: the frame state needs {frame_state_bytes(N, T, J, spread)} bytes")
+    need = spread_partials_bytes(B, T, F, J) if spread else pose_partials_bytes(B, T, F, J)
+    _need(state.numel() * 8 >= need, f"{who}: the batch state needs {need} bytes")
+    hs = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1))
+    hv = np.ascontiguousarray(np.asarray(valid, dtype=np.int32).reshape(-1))
+    _need(hs.shape[0] == B and hv.shape[0] == B, f"{who}: starts and valid must hold B = {B} windows")
+    _need(bool(((hv >= 1) & (hv <= F)).all()), f"{who}: valid must lie in 1 .. F = {F}")
+    _need(bool((hs >= 0).all() and (hs.astype(np.int64) + hv <= N).all()), f"{who}: a window reaches past the N = {N} frames")
+    _need(bool((np.diff(hs) > 0).all()), f"{who}: starts must ascend strictly")
+    tables = torch.from_numpy(np.stack([hs, hv])).to(frame.device) if B else None     # the device copies the kernels read
+    return B, T, F, J, N, hs, hv, tables
+
+
+def fold_windows(frame, N, state, shape, starts, valid, w0, num_proposals):
+    """pafuse_pose_windows_fold: fold `state`, the flat pose state of B windows (`shape` = (B,T,F,J); what pose_partials,
+    pose_partials_fit or combine_poses(merged=) wrote for the union of `num_proposals` hypotheses), into the frame pose
+    state `frame` of N video frames, in place -> frame.  starts, valid: B host integers each (pafuse_amd.windows.window_starts),
+    strictly ascending starts; window b covers frames [starts[b], starts[b] + valid[b]).  w0: the global index of the
+    batch's first window (it is what "window" of finish_frames reports).  Batches come in ascending window order; the
+    result does not depend on how the windows are cut into batches."""
+    lib = _lib.load()
+    B, T, F, J, N, hs, hv, tables = _fold_operands("fold_windows", frame, N, state, shape, starts, valid, False)
+    _need(int(w0) >= 0 and int(num_proposals) >= 0, "fold_windows: w0 and num_proposals >= 0")
+    if B == 0:
+        return frame
+    dev = frame.device
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_pose_windows_fold(
+            frame.data_ptr(), frame.numel() * 8, N, state.data_ptr(), state.numel() * 8, B, T, F, J,
+            tables[0].data_ptr(), tables[1].data_ptr(), hs.ctypes.data, hv.ctypes.data, int(w0), int(num_proposals), _stream(frame)))
+    return frame
+
+
+def fold_spread_windows(frame, N, state, shape, starts, valid):
+    """pafuse_spread_windows_fold: fold `state`, the flat spread state of B windows (spread_partials, or
+    combine_spread(merged=)), into the frame spread state `frame` (frame_state(spread=True)) in place -> frame.  Operands
+    as fold_windows; every covering window is merged by Chan's rule and adds its count to the frame's."""
+    lib = _lib.load()
+    B, T, F, J, N, hs, hv, tables = _fold_operands("fold_spread_windows", frame, N, state, shape, starts, valid, True)
+    if B == 0:
+        return frame
+    dev = frame.device
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_spread_windows_fold(
+            frame.data_ptr(), frame.numel() * 8, N, state.data_ptr(), state.numel() * 8, B, T, F, J,
+            tables[0].data_ptr(), tables[1].data_ptr(), hs.ctypes.data, hv.ctypes.data, _stream(frame)))
+    return frame
+
+
+def finish_frames(N, T, J, frame=None, spread=None, want=None):
+    """pafuse_frames_finish -> dict with the entries named in `want`: from the frame pose state `frame` "mean" [T,N,J,3]
+    (sum / count[n]), "pick" [T,N,J,3], "idx" and "window" [T,N,J] int32 (the J-Agg pose, its hypothesis and its window;
+    NaN / -1 / -1 without a candidate); from the frame spread state `spread` "std" [T,N,J] and "cov" [T,N,J,6].  Also
+    "count" [N]: the hypotheses folded into every frame (int64; from `frame`, else from `spread`).  want=None: everything
+    the given states hold except "count"."""
+    lib = _lib.load()
+    N, T, J = int(N), int(T), int(J)
+    _need(N > 0 and T > 0 and J > 0, "finish_frames: N, T, J > 0")
+    _need(frame is not None or spread is not None, "finish_frames: no state")
+    if want is None:
+        want = (("mean", "pick", "idx", "window") if frame is not None else ()) + (("std", "cov") if spread is not None else ())
+    want = tuple(want)
+    _need(all(k in FRAME_OUTPUTS or k == "count" for k in want), f"finish_frames: want holds {sorted(FRAME_OUTPUTS)} and count - got {want}")
+    _need(frame is not None or not any(k in want for k in ("mean", "pick", "idx", "window")), "finish_frames: mean, pick, idx and window need the frame pose state")
+    _need(spread is not None or not any(k in want for k in ("std", "cov")), 'finish_frames: "std" and "cov" need the frame spread state')
+    for name, t, sp in (("frame", frame, False), ("spread", spread, True)):
+        _need(t is None or (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 1
+                            and t.is_contiguous() and t.numel() * 8 >= frame_state_bytes(N, T, J, sp)),
+              f"finish_frames: {name} must be a flat float64 frame state of {frame_state_bytes(N, T, J, sp)} bytes on a HIP device")
+    first = frame if frame is not None else spread
+    _need(frame is None or spread is None or frame.device == spread.device, "finish_frames: both states on one device")
+    dev = first.device
+    out = {k: torch.empty(T, N, J, *FRAME_OUTPUTS[k][0], device=dev, dtype=FRAME_OUTPUTS[k][1]) for k in want if k != "count"}
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    if out:
+        with torch.cuda.device(dev):
+            _lib.check(lib.pafuse_frames_finish(
+                None if frame is None else frame.data_ptr(), None if spread is None else spread.data_ptr(), N, T, J,
+                ptr("mean"), ptr("pick"), ptr("idx"), ptr("window"), ptr("std"), ptr("cov"), _stream(first)))
+    if "count" in want:
+        out["count"] = (frame_views(frame, N, T, J)["count"] if frame is not None
+                        else frame_views(spread, N, T, J, spread=True)["count"]).to(torch.int64)
+    return out
+
+
 # ------------------------------------------------------------------------------ Protocol #2 from partial states
 PROCRUSTES_HEAD_BYTES_PER_ELEMENT = 16   # float jbest, e2, sel + int32 idx per (b, t, f, j)
 

@@ -15,6 +15,8 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::procrustes_combine(states, sums, gt, conn, T, num_proposals)   jbest, pagg, jagg, pick from W states   main_h3wb.py:381-395
   pafuse::aggregate_poses(pred, conn, x2d?, traj?, cam?)  P-Agg mean pose, J-Agg pose and its hypothesis index, one shard
   pafuse::aggregate_poses_fit(pred, conn, x2d, cam, conf?)  the same without a trajectory: roots fitted on the device; + tfit
+  pafuse::fold_windows(frame!, N, state, shape, starts, valid, w0, num_proposals)   a batch of overlapping windows into the frame state
+  pafuse::finish_frames(frame, N, T, J, spread?)          one pose per video frame: mean, pick, idx, window (+ std, cov)
   pafuse::noise_fill(key, draw, B, P, F, J)               one draw of noise stream v1 as a tensor (DESIGN.md section 6)
 
 ``precision`` ('bf16x3' = the modules' default; 'bf16x3_images', 'f16x2', 'f32', 'bf16': pafuse_amd.D3DP.precision) is the
@@ -400,6 +402,37 @@ def hypothesis_spread(pred: torch.Tensor, conn: torch.Tensor) -> List[torch.Tens
 def _(pred, conn):
     B, T, P, F, J, _ = pred.shape
     return [pred.new_empty(B, T, F, J, 3), pred.new_empty(B, T, F, J, 6), pred.new_empty(B, T, F, J)]
+
+
+# ----------------------------------------------------------------- overlapping windows pooled into one pose per frame
+@torch.library.custom_op("pafuse::fold_windows", mutates_args=("frame",), device_types="cuda")
+def fold_windows(frame: torch.Tensor, N: int, state: torch.Tensor, shape: List[int], starts: List[int], valid: List[int],
+                 w0: int, num_proposals: int) -> None:
+    """pafuse_amd.ops.fold_windows: the flat pose state of B windows (shape = [B,T,F,J]) folded IN PLACE into the frame pose
+    state `frame` (ops.frame_state) of N video frames; window b covers frames [starts[b], starts[b] + valid[b])."""
+    from . import ops
+    ops.fold_windows(frame, N, state, shape, starts, valid, w0, num_proposals)
+
+
+@fold_windows.register_fake
+def _(frame, N, state, shape, starts, valid, w0, num_proposals):
+    return None
+
+
+@torch.library.custom_op("pafuse::finish_frames", mutates_args=(), device_types="cuda")
+def finish_frames(frame: torch.Tensor, N: int, T: int, J: int, spread: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+    """pafuse_amd.ops.finish_frames: the frame pose state -> [mean [T,N,J,3], pick [T,N,J,3], idx [T,N,J] int32, window
+    [T,N,J] int32]; with the frame spread state `spread` also [std [T,N,J], cov [T,N,J,6]]."""
+    from . import ops
+    m = ops.finish_frames(N, T, J, frame=frame, spread=spread)
+    return [m[k] for k in ("mean", "pick", "idx", "window") + (("std", "cov") if spread is not None else ())]
+
+
+@finish_frames.register_fake
+def _(frame, N, T, J, spread=None):
+    f32 = lambda *tail: frame.new_empty((T, N, J, *tail), dtype=torch.float32)
+    i32 = lambda: frame.new_empty((T, N, J), dtype=torch.int32)
+    return [f32(3), f32(3), i32(), i32()] + ([f32(), f32(6)] if spread is not None else [])
 
 
 # ----------------------------------------------------------------------------------------------- noise stream v1
