@@ -27,6 +27,15 @@ next to what --aggregate asks for (the hypotheses are sampled again for that); -
 instead of cutting consecutive clips, and pools on the device all windows that cover a frame: the same files, the per-frame arrays
 written directly (no stitching), each frame aggregated over (windows covering it) x P hypotheses, plus test_3d_output_count.npy
 [frames] and, with --reproj-fit, test_3d_output_pick_window.npy [T,frames,134].  Sampling costs about clip length / S times as much.
+
+--trajectory FOCAL_PX (with --aggregate mean) puts the poses, which are root-relative, into camera space: the root of every (step,
+frame) is fitted on the device on the mean pose from the detections, their confidences and a pinhole camera of that focal length
+(the camera of --reproj-fit; a per-frame fit with a KNOWN focal length).  It writes test_3d_output_traj.npy [T,frames,3] (metres;
+NaN where a frame has no fit) and test_3d_output_traj_resid.npy [T,frames] (the weighted residual of the fit in metres: large
+values say the focal length is wrong), and test_3d_output_postprocess.npy is then built from poses + trajectory instead of a
+rebased height.  --smooth-trajectory R (1 .. 64) also runs a confidence-weighted local-linear filter of radius R frames over the
+trajectory (frames without a fit are filled from their neighbours): _traj.npy then holds the filtered roots and _traj_raw.npy
+the per-frame fit.  With --stride the fit runs inside infer_sequence; without, on the stitched poses (harness.fit_trajectory).
 """
 import argparse
 import json
@@ -73,8 +82,19 @@ def main():
     ap.add_argument("--stride", type=int, default=None, metavar="S",
                     help="with --aggregate mean or --reproj-fit: slide the window over the video with this stride (1 .. clip length) "
                          "and pool the windows covering a frame on the device: one pose per video frame, no seam at the clip borders")
+    ap.add_argument("--trajectory", type=float, default=None, metavar="FOCAL_PX",
+                    help="with --aggregate mean: fit the camera-space root of every frame's pose on the device from the detections, "
+                         "their confidences and this focal length in pixels; writes test_3d_output_traj.npy and _traj_resid.npy, "
+                         "and the post-processed poses move with it")
+    ap.add_argument("--smooth-trajectory", type=int, default=None, metavar="R",
+                    help="with --trajectory: a confidence-weighted local-linear filter of radius R frames (1 .. 64) over the fitted "
+                         "roots; the per-frame fit goes to test_3d_output_traj_raw.npy")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.trajectory is not None and (a.aggregate != "mean" or not a.trajectory > 0):
+        ap.error("--trajectory takes a positive focal length in pixels and needs --aggregate mean (one pose per frame)")
+    if a.smooth_trajectory is not None and (a.trajectory is None or not 1 <= a.smooth_trajectory <= 64):
+        ap.error("--smooth-trajectory takes a radius in 1 .. 64 and needs --trajectory")
     if a.stride is not None and a.aggregate == "none" and a.reproj_fit is None:
         ap.error("--stride needs --aggregate mean or --reproj-fit")
     if a.reproj_fit is not None and not a.reproj_fit > 0:
@@ -108,9 +128,11 @@ def main():
     pixels, conf = harness.load_pifpaf_keypoints(a.keypoints, args.data.num_kps, with_conf=True)
     keypoints = h3wb.normalize_screen_coordinates(pixels[..., :2], w=a.width, h=a.height).astype(np.float32)
     save = lambda name, t: np.save(os.path.join(a.out, name), t.numpy(), allow_pickle=True)
+    # screen-normalised coordinates: x in [-1, 1] over the width, the image centre at (0, 0), one scale for both axes
+    pinhole = lambda focal: np.array([2 * focal / a.width, 2 * focal / a.width, 0, 0, 0, 0, 0, 0, 0], dtype=np.float32)
+    traj = None
     if a.reproj_fit is not None:
-        # screen-normalised coordinates: x in [-1, 1] over the width, the image centre at (0, 0), one scale for both axes
-        cam = np.array([2 * a.reproj_fit / a.width, 2 * a.reproj_fit / a.width, 0, 0, 0, 0, 0, 0, 0], dtype=np.float32)
+        cam = pinhole(a.reproj_fit)
         pick = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="reproj_fit",
                                       cam=cam, conf=conf, hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride)
         if a.stride is not None:         # per-frame arrays already
@@ -131,12 +153,15 @@ def main():
         if a.aggregate == "none":        # the chunk and the spread belonged to the pick
             a.hypothesis_chunk = a.spread = None
     if a.aggregate == "mean" and a.stride is not None:
+        wanted = {} if a.trajectory is None else dict(cam=pinhole(a.trajectory), conf=conf,
+                                                      trajectory=True if a.smooth_trajectory is None else a.smooth_trajectory)
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
-                                      hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride)
+                                      hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride, **wanted)
         for k in ("std", "cov", "count"):
             if k in pred:
                 save(f"test_3d_output_{k}.npy", pred[k])
         poses = pred["pose"]                                                        # [T,frames,134,3]
+        traj = pred if a.trajectory is not None else None
     elif a.aggregate == "mean":
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
                                       hypothesis_chunk=a.hypothesis_chunk, spread=a.spread)
@@ -146,12 +171,20 @@ def main():
                         harness.stitch_spread(pred[k], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
             pred = pred["pose"]
         poses = harness.stitch_poses(pred, keypoints.shape[0], model.frames)        # [T,frames,134,3]
+        if a.trajectory is not None:     # consecutive clips: the fit runs on the stitched per-frame array
+            traj = harness.fit_trajectory(poses, keypoints, pinhole(a.trajectory), conf=conf, smooth=a.smooth_trajectory)
     else:
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch)
         poses = harness.stitch_clips(pred, keypoints.shape[0], model.frames)        # [T,P,frames,134,3]
     np.save(os.path.join(a.out, "test_3d_output.npy"), poses.numpy(), allow_pickle=True)
-    world = harness.camera_to_world(poses, CAMERA_ROTATION)
-    world[..., 2] -= world[..., 2].min()                                            # no trajectory: rebase the height
+    if traj is not None:
+        for k in ("traj", "traj_raw", "traj_resid"):
+            if k in traj:
+                save(f"test_3d_output_{k}.npy", traj[k])
+        world = harness.camera_to_world(poses + traj["traj"][:, :, None], CAMERA_ROTATION)   # a broadcast add: camera-space poses
+    else:
+        world = harness.camera_to_world(poses, CAMERA_ROTATION)
+        world[..., 2] -= world[..., 2].min()                                        # no trajectory: rebase the height
     np.save(os.path.join(a.out, "test_3d_output_postprocess.npy"), world.numpy(), allow_pickle=True)
     print(f"{keypoints.shape[0]} frames -> poses {tuple(poses.shape)} in {a.out}")
 

@@ -33,6 +33,8 @@
  *   pafuse_spread_partials / _combine  the spread of the hypotheses beside the P-Agg mean: per-joint covariance and std
  *   pafuse_pose_windows_fold / pafuse_spread_windows_fold / pafuse_frames_finish  those states of overlapping windows
  *                            pooled into one pose (and spread) per video frame
+ *   pafuse_frames_root_fit / pafuse_trajectory_smooth  the camera-space root of that per-frame pose, fitted from the
+ *                            detections, and a confidence-weighted local-linear filter along the frames
  *   pafuse_procrustes_errors the Protocol #2 part of it (ft2d.p2), main_h3wb.py:381-395, common/loss.py:251-458
  *   pafuse_procrustes_partials / _combine  Protocol #2 from per-shard partial states (sharded or chunked P)
  *   pafuse_mixste2_train_*   MixSTE2.forward (is_train=True) + autograd backward, common/mixste.py:215-225,260-298
@@ -710,6 +712,40 @@ int pafuse_spread_windows_fold(void *frame_state, size_t frame_bytes, int32_t N,
  * Refused (PAFUSE_E_ARG): negative sizes, no output, an output without its state, misalignment, a grid out of range. */
 int pafuse_frames_finish(const void *frame_state, const void *frame_spread, int32_t N, int32_t T, int32_t J, float *mean,
                          float *pick, int32_t *pick_idx, int32_t *pick_win, float *std_dev, float *cov, void *stream);
+
+/* The camera-space root of the finished per-frame pose: one fit per (t, frame) on the pose that is returned (the pooled
+ * mean or the pick of pafuse_frames_finish, or any [T,N,J,3] array), by the algebra of pafuse_pose_partials_fit, operation
+ * for operation (fp64, contraction off, the same fixed order of every sum over j; pafuse_amd/trajectory.py states it).
+ * x2d [N,J,2] screen-normalised detections and conf [N,J] their weights are shared by the T steps; cam[0:4] = fx fy cx cy.
+ * Besides a weight that is not > 0, a joint any component of whose pose is not finite drops out of every sum (a frame no
+ * window covered, a pick without a candidate), so W, Sa, Sb, Sq are per (t, n).  No fit - fewer than two joints in the
+ * sums, den not finite and > 0, t not finite in fp32 - is NaN in traj.
+ *   traj  [T,N,3]  the root, metres, camera space; camera-space pose = pose + traj (broadcast over j)
+ *   wsum  [T,N]    (NULL: not wanted) W rounded to fp32: the weight the frame's fit rests on; 0 where there is no fit
+ *   resid [T,N]    (NULL: not wanted) sqrt(R / W), R = sum c*(ex^2 + ey^2), ex = (tx - a*tz) - rx, ey = (ty - b*tz) - ry with
+ *                  t before its rounding: the weighted algebraic residual in metres (a wrong focal length shows here);
+ *                  NaN where there is no fit
+ * One kernel, one wave per (t, n), no workspace, no atomics, bit-reproducible.
+ * Refused (PAFUSE_E_ARG) before any HIP call: a null pose / x2d / cam / traj, T, N or J < 1. */
+int pafuse_frames_root_fit(const float *pose /* [T,N,J,3] whole-body, root-relative */,
+                           const float *x2d /* [N,J,2] */, const float *conf /* [N,J] or NULL = all 1 */,
+                           const float *cam /* [>=4]: fx fy cx cy */, int32_t T, int32_t N, int32_t J,
+                           float *traj /* [T,N,3], NaN = no fit */, float *wsum /* [T,N] or NULL */,
+                           float *resid /* [T,N] or NULL */, void *stream);
+
+/* A confidence-weighted local-linear filter along the frames of a trajectory.  For every (t, n) the frames
+ * m = max(0, n - r) .. min(N - 1, n + r) are walked in ascending order, d = m - n, all in fp64 with contraction off:
+ *   g = (1 - d*d/(r+1)^2)^2 (the biweight taper), omega = g * weight[t,m]; a frame takes part only if its weight is > 0
+ *   (NULL: 1) and the three components of traj[t,m] are finite
+ *   S0, S1, S2 = sum omega*(1, d, d*d);  per component Q0, Q1 = sum omega*(y, d*y);  D = S0*S2 - S1*S1
+ *   two frames or more and D finite and > 0:  (S2*Q0 - S1*Q1)/D, the local line's value at d = 0
+ *   else S0 > 0:  Q0/S0;   else NaN
+ * rounded once to fp32.  A line, not a mean: constant velocity comes through without lag or end-shrinkage; a frame
+ * without a fit is filled from its neighbours.  A fixed-radius linear smoother, not a tracker.
+ * One kernel, one thread per (t, n).  Refused (PAFUSE_E_ARG) before any HIP call: a null traj or out, T or N < 1, radius
+ * outside 1 .. 64, out == traj. */
+int pafuse_trajectory_smooth(const float *traj /* [T,N,3] */, const float *weight /* [T,N] or NULL */, int32_t T, int32_t N,
+                             int32_t radius /* 1..64 */, float *out /* [T,N,3], may not alias traj */, void *stream);
 
 /* Protocol #2 (P-MPJPE) on the same operands - common/loss.py:251-458 as main_h3wb.py:381-395 calls it: every
  * whole-body hypothesis pose (and, per (b,t,f), the mean over h of them) aligned to its whole-body target by the

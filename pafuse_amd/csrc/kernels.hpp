@@ -3553,6 +3553,160 @@ __global__ void __launch_bounds__(256) frames_finish_kernel(const FramesFinishPa
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// The camera-space root of the per-frame pose (statement: pafuse_amd/trajectory.py).
+// frames_root_fit_kernel fits the root t of the FINISHED pose [T,N,J,3] - the pooled mean or the pick, one per (t, n) - by
+// the algebra of pose_fit_partials_kernel above, operation for operation (fp64, contraction off, every sum over j in the
+// lane-then-butterfly order).  One addition to the weight rule: a joint any component of whose pose is not finite (a frame
+// no window covered, a pick without a candidate) drops out of every sum like a joint without a weight, so W, Sa, Sb, Sq
+// are per (t, n) here.  No fit (fewer than two joints in the sums, den not finite and > 0, t not finite in fp32): NaN in
+// traj, 0 in wsum, NaN in resid.  resid = sqrt(R / W), R = sum c*(ex^2 + ey^2) in the same order with
+// ex = (tx - a*tz) - rx, ey = (ty - b*tz) - ry and t before its rounding: the weighted algebraic residual in metres.
+//
+// One wave per (t, n), four per workgroup.  SLOTS >= 1: a lane loads pose, detection and weight of all its <= SLOTS
+// joints (J <= 64*SLOTS) before the first butterfly and keeps a, b, c, rx, ry of each in registers; the seven sums go
+// through seven independent butterfly chains, interleaved round by round; R is an eighth sum behind the solve.  Every
+// lane runs every round, a lane (or slot) without a joint feeds 0.0.  SLOTS == 0 is the same arithmetic for any J: the
+// joints are walked round by round and read again for R.  No LDS, no atomics, no scratch.
+// ----------------------------------------------------------------------------------------------------------------
+struct FramesRootFitParams {
+    const float* pose;    // [T,N,J,3] whole-body, root-relative
+    const float* x2d;     // [N,J,2]
+    const float* conf;    // [N,J] or null (every weight 1)
+    const float* cam;     // [>= 4]: fx fy cx cy
+    float* traj;          // [T,N,3]
+    float* wsum;          // [T,N] or null
+    float* resid;         // [T,N] or null
+    int T, N, J;
+};
+
+struct RootFitJoint {
+    double a, b, c, rx, ry;   // all 0.0 where the joint takes no part
+    int on;
+};
+
+__device__ __forceinline__ RootFitJoint root_fit_joint(const float* pose, const float* x2, const float* cf, int j, int J,
+                                                       double fx, double fy, double cx, double cy) {
+#pragma clang fp contract(off)
+    RootFitJoint q{0.0, 0.0, 0.0, 0.0, 0.0, 0};
+    if (j < J) {
+        const float cw = cf ? cf[j] : 1.f;
+        const float u = x2[2 * j], v = x2[2 * j + 1];
+        const float wx = pose[3 * j], wy = pose[3 * j + 1], wz = pose[3 * j + 2];
+        if (cw > 0.f && isfinite(wx) && isfinite(wy) && isfinite(wz)) {
+            q.c = (double)cw;
+            q.a = ((double)u - cx) / fx;
+            q.b = ((double)v - cy) / fy;
+            q.rx = q.a * (double)wz - (double)wx;
+            q.ry = q.b * (double)wz - (double)wy;
+            q.on = 1;
+        }
+    }
+    return q;
+}
+
+template <int SLOTS>
+__global__ void __launch_bounds__(256) frames_root_fit_kernel(const FramesRootFitParams p) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (int64_t)p.T * p.N) return;   // wave-uniform
+    const int n = (int)(item % p.N);
+    const int J = p.J;
+    const float* pose = p.pose + item * J * 3;
+    const float* x2 = p.x2d + (int64_t)n * J * 2;
+    const float* cf = p.conf ? p.conf + (int64_t)n * J : nullptr;
+    const double fx = (double)p.cam[0], fy = (double)p.cam[1], cx = (double)p.cam[2], cy = (double)p.cam[3];
+    constexpr int KEPT = SLOTS > 0 ? SLOTS : 1;
+    const int rounds = SLOTS > 0 ? SLOTS : (J + 63) / 64;
+    RootFitJoint q[KEPT];
+    auto joint = [&](int r) -> RootFitJoint {
+        if constexpr (SLOTS > 0) return q[r];
+        else return root_fit_joint(pose, x2, cf, r * 64 + lane, J, fx, fy, cx, cy);
+    };
+#pragma unroll
+    for (int r = 0; r < KEPT; ++r) q[r] = root_fit_joint(pose, x2, cf, SLOTS > 0 ? r * 64 + lane : J, J, fx, fy, cx, cy);   // SLOTS == 0: unused
+    double w = 0.0, sa = 0.0, sb = 0.0, sq = 0.0, srx = 0.0, sry = 0.0, sm = 0.0;
+    int cnt = 0;
+#pragma unroll KEPT
+    for (int r = 0; r < rounds; ++r) {
+        const RootFitJoint g = joint(r);
+        w += g.c, sa += g.c * g.a, sb += g.c * g.b, sq += g.c * (g.a * g.a + g.b * g.b);
+        srx += g.c * g.rx, sry += g.c * g.ry, sm += g.c * (g.a * g.rx + g.b * g.ry);
+        cnt += g.on;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {   // seven independent chains, interleaved
+        const double w2 = __shfl_xor(w, o), sa2 = __shfl_xor(sa, o), sb2 = __shfl_xor(sb, o), sq2 = __shfl_xor(sq, o);
+        const double srx2 = __shfl_xor(srx, o), sry2 = __shfl_xor(sry, o), sm2 = __shfl_xor(sm, o);
+        cnt += __shfl_xor(cnt, o);
+        w += w2, sa += sa2, sb += sb2, sq += sq2, srx += srx2, sry += sry2, sm += sm2;
+    }
+    const double den = sq - (sa * sa + sb * sb) / w;
+    const double tz = (-sm + (sa * srx + sb * sry) / w) / den;
+    const double tx = (srx + sa * tz) / w, ty = (sry + sb * tz) / w;
+    const float t0 = (float)tx, t1 = (float)ty, t2 = (float)tz;
+    const bool ok = cnt >= 2 && isfinite(den) && den > 0.0 && isfinite(t0) && isfinite(t1) && isfinite(t2);
+    const float qnan = __builtin_nanf("");
+    if (lane < 3) p.traj[item * 3 + lane] = !ok ? qnan : lane == 0 ? t0 : lane == 1 ? t1 : t2;
+    if (p.wsum && lane == 3) p.wsum[item] = ok ? (float)w : 0.f;
+    if (p.resid) {
+        double rs = 0.0;
+#pragma unroll KEPT
+        for (int r = 0; r < rounds; ++r) {
+            const RootFitJoint g = joint(r);
+            const double ex = (tx - g.a * tz) - g.rx, ey = (ty - g.b * tz) - g.ry;
+            const double term = g.c * (ex * ex + ey * ey);
+            rs += g.on ? term : 0.0;           // a joint that takes no part feeds 0.0 whatever t holds
+        }
+        rs = wave_sum_f64(rs);
+        if (lane == 4) p.resid[item] = ok ? (float)sqrt(rs / w) : qnan;
+    }
+}
+
+// trajectory_smooth_kernel: the confidence-weighted local-linear filter along the frames (statement:
+// pafuse_amd/trajectory.py smooth).  One thread per (t, n) walks m = max(0, n - r) .. min(N - 1, n + r) in ascending
+// order, d = m - n; taper g = (1 - d*d/(r+1)^2)^2 (the biweight: no transcendental), omega = g * weight[t,m]; a frame
+// takes part if its weight is > 0 (null: 1) and its three components are finite.  S0, S1, S2 = sum omega*(1, d, d*d),
+// Q0, Q1 = sum omega*(y, d*y) per component, D = S0*S2 - S1*S1.  Two frames or more and D finite and > 0: the local
+// line's value at d = 0, (S2*Q0 - S1*Q1)/D; else S0 > 0: Q0/S0; else NaN.  fp64, contraction off, rounded once.
+struct TrajectorySmoothParams {
+    const float* traj;    // [T,N,3]
+    const float* weight;  // [T,N] or null
+    float* out;           // [T,N,3]
+    int T, N, radius;
+};
+
+__global__ void __launch_bounds__(256) trajectory_smooth_kernel(const TrajectorySmoothParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)p.T * p.N) return;
+    const int n = (int)(e % p.N), r = p.radius;
+    const int64_t row0 = e - n;   // (t, 0)
+    const double span = (double)((r + 1) * (r + 1));
+    double S0 = 0.0, S1 = 0.0, S2 = 0.0, Q0[3] = {0.0, 0.0, 0.0}, Q1[3] = {0.0, 0.0, 0.0};
+    int cnt = 0;
+    const int lo = max(0, n - r), hi = min(p.N - 1, n + r);
+    for (int m = lo; m <= hi; ++m) {
+        const float wt = p.weight ? p.weight[row0 + m] : 1.f;
+        const float y0 = p.traj[(row0 + m) * 3 + 0], y1 = p.traj[(row0 + m) * 3 + 1], y2 = p.traj[(row0 + m) * 3 + 2];
+        if (!(wt > 0.f && isfinite(y0) && isfinite(y1) && isfinite(y2))) continue;
+        const int d = m - n;
+        const double dd = (double)d;
+        const double q = (double)(d * d) / span, h = 1.0 - q, g = h * h;
+        const double om = g * (double)wt, omd = om * dd;
+        S0 += om, S1 += omd, S2 += omd * dd;
+        Q0[0] += om * (double)y0, Q0[1] += om * (double)y1, Q0[2] += om * (double)y2;
+        Q1[0] += omd * (double)y0, Q1[1] += omd * (double)y1, Q1[2] += omd * (double)y2;
+        ++cnt;
+    }
+    const double D = S0 * S2 - S1 * S1;
+    const bool line = cnt >= 2 && isfinite(D) && D > 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        p.out[e * 3 + k] = line ? (float)((S2 * Q0[k] - S1 * Q1[k]) / D) : S0 > 0.0 ? (float)(Q0[k] / S0) : __builtin_nanf("");
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // Protocol #2 (P-MPJPE) behind the all-gather: common/loss.py:251-458 as main_h3wb.py:381-395 calls it on the
 // whole-body poses.  Every hypothesis pose Y is aligned to its target X by the similarity transform of the
 // reference (centre both, H = (X0/|X0|)^T (Y0/|Y0|), R = V U^T with the reflection fix, a = tr(S') |X0| / |Y0|) and

@@ -2116,6 +2116,44 @@ int pafuse_frames_finish(const void* frame_state, const void* frame_spread, int3
     return launch<frames_finish_kernel>("frames_finish_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
 }
 
+// the camera-space root of every (t, frame) of the finished pose (frames_root_fit_kernel): the argument checks come before
+// the first HIP call
+int pafuse_frames_root_fit(const float* pose, const float* x2d, const float* conf, const float* cam, int32_t T, int32_t N,
+                           int32_t J, float* traj, float* wsum, float* resid, void* stream) {
+    if (!pose || !x2d || !cam || !traj) return fail(PAFUSE_E_ARG, "frames_root_fit: pose, x2d, cam and traj are needed (conf, wsum, resid may be null)");
+    if (T < 1 || N < 1 || J < 1) return fail(PAFUSE_E_ARG, "frames_root_fit: bad size (T=%d N=%d J=%d)", T, N, J);
+    const int64_t waves = (int64_t)T * N;   // one wave per (t, n), four per workgroup
+    if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "frames_root_fit: grid out of range");
+    StreamDevice on_stream_device(stream);
+    FramesRootFitParams m{};
+    m.pose = pose, m.x2d = x2d, m.conf = conf, m.cam = cam, m.traj = traj, m.wsum = wsum, m.resid = resid;
+    m.T = T, m.N = N, m.J = J;
+    const unsigned grid = blocks_for(waves, 4);
+    hipStream_t s = (hipStream_t)stream;
+    switch ((J + 63) / 64) {   // the joints of a lane in registers up to J = 256; beyond, the same arithmetic round by round
+        case 1: return launch<frames_root_fit_kernel<1>>("frames_root_fit_kernel", grid, 256, 0, s, m);
+        case 2: return launch<frames_root_fit_kernel<2>>("frames_root_fit_kernel", grid, 256, 0, s, m);
+        case 3: return launch<frames_root_fit_kernel<3>>("frames_root_fit_kernel", grid, 256, 0, s, m);
+        case 4: return launch<frames_root_fit_kernel<4>>("frames_root_fit_kernel", grid, 256, 0, s, m);
+        default: return launch<frames_root_fit_kernel<0>>("frames_root_fit_kernel", grid, 256, 0, s, m);
+    }
+}
+
+// the confidence-weighted local-linear filter along the frames (trajectory_smooth_kernel)
+int pafuse_trajectory_smooth(const float* traj, const float* weight, int32_t T, int32_t N, int32_t radius, float* out,
+                             void* stream) {
+    if (!traj || !out) return fail(PAFUSE_E_ARG, "trajectory_smooth: traj and out are needed (weight may be null: every weight 1)");
+    if (T < 1 || N < 1) return fail(PAFUSE_E_ARG, "trajectory_smooth: bad size (T=%d N=%d)", T, N);
+    if (radius < 1 || radius > 64) return fail(PAFUSE_E_ARG, "trajectory_smooth: radius %d outside 1 .. 64", radius);
+    if (out == traj) return fail(PAFUSE_E_ARG, "trajectory_smooth: out may not alias traj (every thread reads its neighbours' frames)");
+    const int64_t rows = (int64_t)T * N;
+    if ((rows + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "trajectory_smooth: grid out of range");
+    StreamDevice on_stream_device(stream);
+    TrajectorySmoothParams m{};
+    m.traj = traj, m.weight = weight, m.out = out, m.T = T, m.N = N, m.radius = radius;
+    return launch<trajectory_smooth_kernel>("trajectory_smooth_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
+}
+
 int pafuse_procrustes_errors(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,
                              const int32_t* conn, int32_t B, int32_t T, int32_t P, int32_t F, int32_t J, float* jbest,
                              double* pbest_sums, float* pagg, float* jagg, int32_t* pick, void* stream) {

@@ -64,7 +64,7 @@ def wb_pose_from_parts(pose, dataset):
 
 @torch.no_grad()
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
-                   hypothesis_chunk=None, spread=None, conf=None, stride=None):
+                   hypothesis_chunk=None, spread=None, conf=None, stride=None, trajectory=None):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -101,7 +101,25 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     ``"pose"`` [T,N,J,3], ``"count"`` [N] (the hypotheses pooled per frame), for the reprojection aggregates ``"idx"`` and
     ``"window"`` [T,N,J] (the pick's hypothesis and its window; -1 without one), with ``spread`` ``"std"`` [T,N,J] and
     ``"cov"`` [T,N,J,6].  traj and conf are cut per window; with "reproj_fit" a joint without a pick carries the pooled mean.
-    stride = F visits exactly the clips of cut_clips."""
+    stride = F visits exactly the clips of cut_clips.
+
+    ``trajectory`` (with ``stride``; None: everything above, unchanged) also returns the camera-space ROOT of the pose that is
+    returned - every pose above is root-relative.  It needs ``cam`` (fx, fy, cx, cy first) and takes ``conf`` [N,J] with any
+    aggregate.  The root of every (t, frame) is fitted on the device on the finished pose (the pooled mean, or the pick with the
+    mean already filled in where idx == -1) from the detections and the intrinsics - pafuse_amd.trajectory: the per-frame linear
+    fit of "reproj_fit" with a KNOWN focal length; a joint without a weight or with a NaN pose takes no part.  ``True``: the
+    per-frame fit as it is.  An integer r in 1 .. 64: also a confidence-weighted local-linear filter of radius r along the
+    frames (weights: the fit's summed weights), which fills frames without a fit from their neighbours.  Added keys:
+    ``"traj"`` [T,N,3] (smoothed when r is given; NaN where there is no fit and nothing to fill from), ``"traj_raw"`` [T,N,3]
+    when smoothed, ``"traj_weight"`` [T,N] (0: no fit) and ``"traj_resid"`` [T,N], the weighted residual of the fit in metres
+    (it is what a wrong focal length shows in).  Camera-space poses are ``pose + traj[:, :, None]``.  Every rank holds the same
+    frame state and runs the same fit.  Without ``stride`` use :func:`fit_trajectory` on the stitched poses."""
+    smooth = _trajectory_radius(trajectory)
+    if trajectory is not None:
+        if stride is None:
+            raise ValueError("trajectory needs stride (one pose per video frame); for stitched clips call harness.fit_trajectory")
+        if cam is None:
+            raise ValueError("trajectory needs cam (fx, fy, cx, cy first): the fit takes the intrinsics as known")
     if stride is not None:
         if isinstance(stride, bool) or int(stride) != stride or not 1 <= int(stride) <= model.frames:
             raise ValueError(f"stride must be an integer in 1 .. {model.frames} (the window length), got {stride!r}")
@@ -126,12 +144,16 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
             conf = torch.as_tensor(conf, dtype=torch.float32)
             if tuple(conf.shape) != tuple(seq_2d.shape[-3:-1]):
                 raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[-3:-1])}, got {tuple(conf.shape)}")
-    elif conf is not None:
+    elif conf is not None and trajectory is None:
         raise ValueError('conf belongs to aggregate="reproj_fit"')
+    elif conf is not None:
+        conf = torch.as_tensor(conf, dtype=torch.float32)
+        if tuple(conf.shape) != tuple(seq_2d.shape[-3:-1]):
+            raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[-3:-1])}, got {tuple(conf.shape)}")
     dev = next(model.parameters()).device
     if stride is not None:
         return _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                             spread, conf, int(stride), dev)
+                             spread, conf, int(stride), dev, trajectory is not None, smooth)
     x2d = cut_clips(seq_2d, model.frames).to(dev)
     x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), model.frames).to(dev)
     sampler = ShardedSampler(model, group)
@@ -191,7 +213,7 @@ def cut_windows(seq, starts, frames=27):
 
 
 def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                  conf, stride, dev):
+                  conf, stride, dev, trajectory=False, smooth=None):
     """infer_sequence(stride=...): sliding windows pooled into one pose per video frame (arguments already checked)"""
     from . import ops
     from .windows import window_starts
@@ -200,9 +222,10 @@ def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group
     N, F = seq_2d.shape[0], model.frames
     starts, valid = window_starts(N, F, stride)
     fit, reproj = aggregate == "reproj_fit", aggregate in ("reproj", "reproj_fit")
+    frame_conf = conf
     x2d = cut_windows(seq_2d, starts, F).to(dev)
     x2d_flip = cut_windows(flip_2d(seq_2d, kps_left, kps_right), starts, F).to(dev)
-    if reproj:
+    if reproj or trajectory:
         cam = torch.as_tensor(cam, dtype=torch.float32).to(dev)
     if fit and conf is not None:
         conf = cut_windows(conf, starts, F).to(dev)                                    # [windows,F,J]
@@ -237,6 +260,56 @@ def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group
         out["pick"] = torch.where((out["idx"] < 0).unsqueeze(-1), out["mean"], out["pick"])
     out["pose"] = out.pop("pick") if reproj else out["mean"]
     out.pop("mean", None)
+    if trajectory:  # the root of the pose that is returned, on the device before anything crosses to the host
+        out.update(_fit_trajectory(out["pose"], seq_2d.to(dev), cam, None if frame_conf is None else frame_conf.to(dev), smooth))
+    return {k: v.cpu() for k, v in out.items()}
+
+
+def _trajectory_radius(trajectory, name="trajectory"):
+    """infer_sequence's `trajectory`: None / True -> None (no smoothing), an integer r in 1 .. 64 -> r"""
+    if trajectory is None or trajectory is True:
+        return None
+    if isinstance(trajectory, bool) or not isinstance(trajectory, int) or not 1 <= trajectory <= 64:
+        raise ValueError(f"{name} must be None, True (the per-frame fit) or a smoothing radius in 1 .. 64, got {trajectory!r}")
+    return trajectory
+
+
+def _fit_trajectory(pose, x2d, cam, conf, smooth):
+    """device tensors -> the trajectory keys of infer_sequence / fit_trajectory, on the device"""
+    from . import ops
+    m = ops.fit_trajectory(pose.contiguous(), x2d.contiguous(), cam.contiguous(), conf=None if conf is None else conf.contiguous())
+    out = {"traj": m["traj"], "traj_weight": m["wsum"], "traj_resid": m["resid"]}
+    if smooth is not None:
+        out["traj_raw"] = m["traj"]
+        out["traj"] = ops.smooth_trajectory(m["traj"], m["wsum"], smooth)
+    return out
+
+
+@torch.no_grad()
+def fit_trajectory(poses, seq_2d, cam, conf=None, smooth=None, device="cuda"):
+    """The camera-space root trajectory of per-frame poses: ``poses`` [T,N,J,3] whole-body and root-relative - an
+    ``infer_sequence(stride=...)["pose"]`` or the result of :func:`stitch_poses` - ``seq_2d`` [N,J,2] the screen-normalised
+    detections they were lifted from, ``cam`` the intrinsics (fx, fy, cx, cy first), ``conf`` [N,J] the detections' weights
+    (None: all 1).  Fitted on the device per (t, frame) (pafuse_amd.trajectory; ops.fit_trajectory); ``smooth=r`` (1 .. 64)
+    also runs the local-linear filter of that radius along the frames (ops.smooth_trajectory).  Returns a dict of CPU tensors:
+    ``"traj"`` [T,N,3] (smoothed when ``smooth`` is given), ``"traj_raw"`` when smoothed, ``"traj_weight"`` [T,N] and
+    ``"traj_resid"`` [T,N] - the keys ``infer_sequence(trajectory=...)`` adds.  Camera-space poses: ``poses + traj[:, :, None]``."""
+    if smooth is True:
+        raise ValueError("smooth must be None or a smoothing radius in 1 .. 64")
+    smooth = _trajectory_radius(smooth, "smooth")
+    poses = torch.as_tensor(poses, dtype=torch.float32)
+    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
+    if cam is None:
+        raise ValueError("fit_trajectory needs cam (fx, fy, cx, cy first)")
+    if poses.dim() != 4 or poses.shape[-1] != 3 or tuple(seq_2d.shape) != (*poses.shape[1:3], 2):
+        raise ValueError(f"poses must be [T,N,J,3] and seq_2d [N,J,2], got {tuple(poses.shape)} and {tuple(seq_2d.shape)}")
+    if conf is not None:
+        conf = torch.as_tensor(conf, dtype=torch.float32)
+        if tuple(conf.shape) != tuple(seq_2d.shape[:2]):
+            raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[:2])}, got {tuple(conf.shape)}")
+    dev = poses.device if poses.is_cuda else torch.device(device)
+    cam = torch.as_tensor(cam, dtype=torch.float32).reshape(-1).to(dev)
+    out = _fit_trajectory(poses.to(dev), seq_2d.to(dev), cam, None if conf is None else conf.to(dev), smooth)
     return {k: v.cpu() for k, v in out.items()}
 
 

@@ -1275,6 +1275,61 @@ def finish_frames(N, T, J, frame=None, spread=None, want=None):
     return out
 
 
+# ------------------------------------------------------------------ the camera-space root of the per-frame pose
+TRAJECTORY_OUTPUTS = ("traj", "wsum", "resid")
+
+
+def fit_trajectory(pose, x2d, cam, conf=None, want=TRAJECTORY_OUTPUTS):
+    """pafuse_frames_root_fit: pose [T,N,J,3] the finished whole-body, root-relative pose of every (t, frame) (finish_frames'
+    "mean" or "pick", or stitched clips), x2d [N,J,2] screen-normalised detections, cam [>= 4] (fx fy cx cy first), conf
+    [N,J] their weights (None: every weight 1) -> dict with the entries named in `want`: "traj" [T,N,3] the fitted root
+    (NaN where there is no fit), "wsum" [T,N] the weight the fit rests on (0 where none), "resid" [T,N] the weighted
+    algebraic residual in metres (NaN where none).  A joint without a positive weight or with a non-finite pose takes no
+    part (pafuse_amd.trajectory states the arithmetic).  Camera-space poses are pose + traj[:, :, None]."""
+    lib = _lib.load()
+    want = tuple(want)
+    _need(all(k in TRAJECTORY_OUTPUTS for k in want) and "traj" in want, f'fit_trajectory: want holds "traj" and any of wsum, resid - got {want}')
+    _need(isinstance(pose, torch.Tensor) and pose.dim() == 4 and pose.shape[-1] == 3, "fit_trajectory: pose must be [T,N,J,3]")
+    T, N, J = (int(v) for v in pose.shape[:3])
+    _need(T > 0 and N > 0 and J > 0, "fit_trajectory: T, N, J > 0")
+    _need(x2d is not None and cam is not None, "fit_trajectory: x2d and cam are needed")
+    _need(tuple(x2d.shape) == (N, J, 2) and cam.dim() == 1 and cam.numel() >= 4 and (conf is None or tuple(conf.shape) == (N, J)),
+          "fit_trajectory: x2d [N,J,2], cam [>= 4] and conf [N,J] must match pose [T,N,J,3]")
+    _need_tensors("fit_trajectory", [pose, x2d, cam] + ([] if conf is None else [conf]), ())
+    dev = pose.device
+    out = {k: torch.empty((T, N, 3) if k == "traj" else (T, N), device=dev, dtype=torch.float32) for k in want}
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_frames_root_fit(pose.data_ptr(), x2d.data_ptr(), None if conf is None else conf.data_ptr(),
+                                              cam.data_ptr(), T, N, J, ptr("traj"), ptr("wsum"), ptr("resid"), _stream(pose)))
+    return out
+
+
+def smooth_trajectory(traj, weight, radius, out=None):
+    """pafuse_trajectory_smooth: traj [T,N,3] (NaN: no fit), weight [T,N] or None (every weight 1), radius 1 .. 64 ->
+    [T,N,3]: the confidence-weighted local-linear filter along the frames (pafuse_amd.trajectory.smooth states it); a frame
+    takes part if its weight is > 0 and its root finite, a frame without a fit is filled from its neighbours, and a frame
+    with nothing within `radius` stays NaN.  `out`: a [T,N,3] tensor to write into that shares no memory with traj."""
+    lib = _lib.load()
+    _need(isinstance(traj, torch.Tensor) and traj.dim() == 3 and traj.shape[-1] == 3, "smooth_trajectory: traj must be [T,N,3]")
+    T, N = int(traj.shape[0]), int(traj.shape[1])
+    _need(T > 0 and N > 0, "smooth_trajectory: T, N > 0")
+    _need(not isinstance(radius, bool) and int(radius) == radius and 1 <= int(radius) <= 64,
+          f"smooth_trajectory: radius must be an integer in 1 .. 64, got {radius!r}")
+    _need(weight is None or tuple(weight.shape) == (T, N), "smooth_trajectory: weight must be [T,N]")
+    if out is None:
+        out = torch.empty_like(traj)
+    _need(tuple(out.shape) == (T, N, 3), "smooth_trajectory: out must be [T,N,3]")
+    lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
+    _need(hi <= traj.data_ptr() or lo >= traj.data_ptr() + traj.numel() * 4,
+          "smooth_trajectory: out may not alias traj (every frame is read by its neighbours)")
+    _need_tensors("smooth_trajectory", [traj, out] + ([] if weight is None else [weight]), ())
+    with torch.cuda.device(traj.device):
+        _lib.check(lib.pafuse_trajectory_smooth(traj.data_ptr(), None if weight is None else weight.data_ptr(), T, N, int(radius),
+                                                out.data_ptr(), _stream(traj)))
+    return out
+
+
 # ------------------------------------------------------------------------------ Protocol #2 from partial states
 PROCRUSTES_HEAD_BYTES_PER_ELEMENT = 16   # float jbest, e2, sel + int32 idx per (b, t, f, j)
 

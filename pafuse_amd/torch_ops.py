@@ -17,6 +17,8 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::aggregate_poses_fit(pred, conn, x2d, cam, conf?)  the same without a trajectory: roots fitted on the device; + tfit
   pafuse::fold_windows(frame!, N, state, shape, starts, valid, w0, num_proposals)   a batch of overlapping windows into the frame state
   pafuse::finish_frames(frame, N, T, J, spread?)          one pose per video frame: mean, pick, idx, window (+ std, cov)
+  pafuse::fit_trajectory(pose, x2d, cam, conf?)           the camera-space root of that pose: traj, wsum, resid per (t, frame)
+  pafuse::smooth_trajectory(traj, weight?, radius)        a confidence-weighted local-linear filter along the frames
   pafuse::noise_fill(key, draw, B, P, F, J)               one draw of noise stream v1 as a tensor (DESIGN.md section 6)
 
 ``precision`` ('bf16x3' = the modules' default; 'bf16x3_images', 'f16x2', 'f32', 'bf16': pafuse_amd.D3DP.precision) is the
@@ -433,6 +435,35 @@ def _(frame, N, T, J, spread=None):
     f32 = lambda *tail: frame.new_empty((T, N, J, *tail), dtype=torch.float32)
     i32 = lambda: frame.new_empty((T, N, J), dtype=torch.int32)
     return [f32(3), f32(3), i32(), i32()] + ([f32(), f32(6)] if spread is not None else [])
+
+
+# ------------------------------------------------------------------ the camera-space root of the per-frame pose
+@torch.library.custom_op("pafuse::fit_trajectory", mutates_args=(), device_types="cuda")
+def fit_trajectory(pose: torch.Tensor, x2d: torch.Tensor, cam: torch.Tensor, conf: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+    """pafuse_amd.ops.fit_trajectory: pose [T,N,J,3] root-relative, x2d [N,J,2], cam [>= 4], conf [N,J] or None -> [traj [T,N,3]
+    (NaN where there is no fit), wsum [T,N], resid [T,N]]."""
+    from . import ops
+    m = ops.fit_trajectory(pose, x2d, cam, conf=conf)
+    return [m["traj"], m["wsum"], m["resid"]]
+
+
+@fit_trajectory.register_fake
+def _(pose, x2d, cam, conf=None):
+    T, N = pose.shape[0], pose.shape[1]
+    return [pose.new_empty((T, N, 3), dtype=torch.float32), pose.new_empty((T, N), dtype=torch.float32),
+            pose.new_empty((T, N), dtype=torch.float32)]
+
+
+@torch.library.custom_op("pafuse::smooth_trajectory", mutates_args=(), device_types="cuda")
+def smooth_trajectory(traj: torch.Tensor, weight: Optional[torch.Tensor], radius: int) -> torch.Tensor:
+    """pafuse_amd.ops.smooth_trajectory: traj [T,N,3], weight [T,N] or None, radius 1 .. 64 -> the filtered trajectory [T,N,3]."""
+    from . import ops
+    return ops.smooth_trajectory(traj, weight, radius)
+
+
+@smooth_trajectory.register_fake
+def _(traj, weight, radius):
+    return torch.empty_like(traj)
 
 
 # ----------------------------------------------------------------------------------------------- noise stream v1

@@ -1,0 +1,123 @@
+"""The camera-space root trajectory of the per-frame pose - the host statement, in numpy, of what
+frames_root_fit_kernel and trajectory_smooth_kernel (csrc/kernels.hpp; pafuse_frames_root_fit, pafuse_trajectory_smooth)
+compute.
+
+The fit.  The pose the in-the-wild flow returns - the pooled mean or the J-Agg pick, one per (t, frame) - is root-relative.
+With the intrinsics known its root t is the weighted linear least-squares problem of pafuse_amd.rootfit, solved by the same
+operations in the same order (fp64, no fused multiply-add, every sum over j in rootfit.SUM_ORDER), with one addition to
+the weight rule: a joint any component of whose pose is not finite takes no part either (a frame no window covered and
+a "reproj" pick without a candidate are NaN).  So the sums W, Sa, Sb, Sq are per (t, frame), and fit_frames is
+rootfit._fit with B = T, P = 1, F = N and the detections broadcast over t.  No fit (fewer than two joints in the sums,
+den not finite and > 0, t not finite in fp32): NaN in traj, 0 in wsum, NaN in resid.
+
+  wsum  = W rounded to fp32
+  resid = sqrt(R / W) rounded to fp32,  R = sum c*(ex*ex + ey*ey) in SUM_ORDER,  ex = (tx - a*tz) - rx,  ey = (ty - b*tz) - ry
+          with t BEFORE its rounding: the weighted algebraic residual in metres (a wrong focal length shows here)
+
+The smoother.  A confidence-weighted local-linear filter along the frames with a fixed radius r in 1 .. 64.  For frame n
+the frames m = max(0, n - r) .. min(N - 1, n + r) are walked in ascending order, d = m - n, everything in fp64:
+
+  q = double(d*d) / double((r+1)*(r+1));  h = 1.0 - q;  g = h*h          the biweight taper: no transcendental
+  omega = g * weight[t,m]         a frame takes part only if its weight is > 0 (None: 1) and its three components are finite
+  S0 = sum omega;  S1 = sum omega*d;  S2 = sum (omega*d)*d;  per component  Q0 = sum omega*y;  Q1 = sum (omega*d)*y
+  D = S0*S2 - S1*S1
+  two frames or more and D finite and > 0:   (S2*Q0 - S1*Q1)/D     the local line's value at d = 0
+  else S0 > 0:                               Q0/S0
+  else:                                      NaN
+
+rounded once to fp32.  A local line, not a local mean: a root moving at constant velocity comes through without lag and
+without shrinking at the ends, and a frame without a fit is filled from its neighbours.
+
+This module is test infrastructure and the documentation of the arithmetic.  The product path never calls it.
+"""
+import numpy as np
+
+from . import rootfit
+
+
+def _operands(pose, x2d, conf):
+    pose = np.asarray(pose, dtype=np.float32)
+    x2d = np.asarray(x2d, dtype=np.float32)
+    T, N, J, _ = pose.shape
+    assert pose.shape == (T, N, J, 3) and x2d.shape == (N, J, 2)
+    c = np.ones((N, J), dtype=np.float32) if conf is None else np.asarray(conf, dtype=np.float32)
+    assert c.shape == (N, J)
+    c = np.where(np.isfinite(pose).all(axis=-1), c[None], np.float32(0))          # [T,N,J]: the one addition to the rule
+    return pose, np.ascontiguousarray(np.broadcast_to(x2d, (T, N, J, 2))), c
+
+
+def fit_frames_f64(pose, x2d, conf, cam):
+    """-> (t [T,N,3] fp64, the fit BEFORE its rounding; fit [T,N] bool, where there is one)"""
+    pose, x2, c = _operands(pose, x2d, conf)
+    t, fit = rootfit._fit(pose[:, None, None], x2, c, cam)
+    return t[:, 0, 0], fit[:, 0, 0]
+
+
+def fit_frames(pose, x2d, conf, cam):
+    """pose [T,N,J,3] fp32 whole-body, root-relative; x2d [N,J,2] fp32 screen-normalised; conf [N,J] fp32 or None; cam [>=4]
+    -> (traj [T,N,3], wsum [T,N], resid [T,N]) fp32: what pafuse_frames_root_fit writes."""
+    pose, x2, c32 = _operands(pose, x2d, conf)
+    t, fit = rootfit._fit(pose[:, None, None], x2, c32, cam)
+    t, fit = t[:, 0, 0], fit[:, 0, 0]                                  # [T,N,3], [T,N]
+    cam = np.asarray(cam, dtype=np.float32).reshape(-1)
+    fx, fy, cx, cy = (np.float64(v) for v in cam[:4])
+    with np.errstate(all="ignore"):
+        on = c32 > 0
+        c = c32.astype(np.float64)
+        a = (x2[..., 0].astype(np.float64) - cx) / fx
+        b = (x2[..., 1].astype(np.float64) - cy) / fy
+        w = pose.astype(np.float64)
+        rx = a * w[..., 2] - w[..., 0]
+        ry = b * w[..., 2] - w[..., 1]
+        tx, ty, tz = (t[..., k][..., None] for k in range(3))
+        ex = (tx - a * tz) - rx
+        ey = (ty - b * tz) - ry
+        R = rootfit.lane_sum(np.where(on, c * (ex * ex + ey * ey), 0.0))
+        W = rootfit.lane_sum(np.where(on, c, 0.0))
+        traj = np.where(fit[..., None], t.astype(np.float32), np.float32(np.nan))
+        wsum = np.where(fit, W.astype(np.float32), np.float32(0))
+        resid = np.where(fit, np.sqrt(R / W).astype(np.float32), np.float32(np.nan))
+    return traj, wsum, resid
+
+
+def smooth(traj, weight, radius):
+    """traj [T,N,3] fp32, weight [T,N] fp32 or None, radius 1 .. 64 -> [T,N,3] fp32: what pafuse_trajectory_smooth writes,
+    one rounded operation after the other."""
+    traj = np.asarray(traj, dtype=np.float32)
+    T, N, _ = traj.shape
+    r = int(radius)
+    if not 1 <= r <= 64:
+        raise ValueError(f"smooth: radius must lie in 1 .. 64, got {radius!r}")
+    wt = np.ones((T, N), dtype=np.float32) if weight is None else np.asarray(weight, dtype=np.float32)
+    assert traj.shape == (T, N, 3) and wt.shape == (T, N)
+    with np.errstate(all="ignore"):
+        part = (wt > 0) & np.isfinite(traj).all(axis=-1)              # [T,N]; False for a NaN weight
+        y = traj.astype(np.float64)
+        w64 = wt.astype(np.float64)
+        S0, S1, S2 = np.zeros((T, N)), np.zeros((T, N)), np.zeros((T, N))
+        Q0, Q1 = np.zeros((T, N, 3)), np.zeros((T, N, 3))
+        cnt = np.zeros((T, N), dtype=np.int64)
+        n = np.arange(N)
+        span = np.float64((r + 1) * (r + 1))
+        for d in range(-r, r + 1):                                    # ascending m = n + d
+            m = n + d
+            inside = (m >= 0) & (m < N)
+            mc = np.clip(m, 0, N - 1)
+            take = part[:, mc] & inside[None]
+            q = np.float64(d * d) / span
+            h = 1.0 - q
+            g = h * h
+            om = g * w64[:, mc]
+            omd = om * np.float64(d)
+            S0 = S0 + np.where(take, om, 0.0)
+            S1 = S1 + np.where(take, omd, 0.0)
+            S2 = S2 + np.where(take, omd * np.float64(d), 0.0)
+            Q0 = Q0 + np.where(take[..., None], om[..., None] * y[:, mc], 0.0)
+            Q1 = Q1 + np.where(take[..., None], omd[..., None] * y[:, mc], 0.0)
+            cnt = cnt + take
+        D = S0 * S2 - S1 * S1
+        line = (cnt >= 2) & np.isfinite(D) & (D > 0)
+        val_line = ((S2[..., None] * Q0 - S1[..., None] * Q1) / D[..., None]).astype(np.float32)
+        val_mean = (Q0 / S0[..., None]).astype(np.float32)
+        out = np.where(line[..., None], val_line, np.where((S0 > 0)[..., None], val_mean, np.float32(np.nan)))
+    return out.astype(np.float32)
