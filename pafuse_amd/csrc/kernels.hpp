@@ -2582,14 +2582,117 @@ __device__ __forceinline__ void wb_joint(const float* pose /*[J,3]*/, const int3
     o[0] = a[0] + c[0], o[1] = a[1] + c[1], o[2] = a[2] + c[2];
 }
 
+// The 2-D reprojection error of the whole-body joint w under the root tr against the detection x2 (common/camera.py:30-60;
+// cam: f(2) c(2) k(3) p(2)).  THE statement of e2: every kernel that forms the J-Agg index calls it, so they all round alike.
+__device__ __forceinline__ float reproj_error(const float (&w)[3], float tr0, float tr1, float tr2, float x20, float x21,
+                                              const float* cam) {
+    const float fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
+    const float k1 = cam[4], k2 = cam[5], k3 = cam[6], p1 = cam[7], p2 = cam[8];
+    const float X = w[0] + tr0, Y = w[1] + tr1, Z = w[2] + tr2;
+    const float xx = fminf(fmaxf(X / Z, -1.f), 1.f), yy = fminf(fmaxf(Y / Z, -1.f), 1.f);
+    const float r2 = xx * xx + yy * yy;
+    const float radial = 1.f + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2));
+    const float tan = p1 * xx + p2 * yy;
+    const float u = fx * (xx * (radial + tan) + p1 * r2) + cx, v = fy * (yy * (radial + tan) + p2 * r2) + cy;
+    const float q0 = u - x20, q1 = v - x21;
+    return sqrtf(q0 * q0 + q1 * q1);
+}
+
+// The merge rule for the first minimum across states (or waves): the offered candidate (ew, hw) replaces the held one
+// (best2, hsel) if its e2 is smaller, or equal with the lower global index; a state without a candidate (hw < 0) never wins.
+__device__ __forceinline__ bool candidate_wins(float ew, int32_t hw, float best2, int32_t hsel) {
+    return hw >= 0 && (hsel < 0 || ew < best2 || (ew == best2 && hw < hsel));
+}
+
+// (b, t, f, j) of the flat element index e of a [B,T,F,J] map
+struct BTFJ {
+    int b, t, f, j;
+};
+__device__ __forceinline__ BTFJ decode_btfj(int64_t e, int T, int F, int J) {
+    BTFJ o;
+    o.j = (int)(e % J);
+    o.f = (int)((e / J) % F);
+    o.t = (int)((e / ((int64_t)J * F)) % T);
+    o.b = (int)(e / ((int64_t)J * F * T));
+    return o;
+}
+
+// a + b == b + a: after the butterfly every lane of the wave holds the same bits
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// The flat states of the partial-state kernels below, each carved in ONE place: a views struct built from (base pointer,
+// n = B*T*F*J) on the host for the launch parameters and on the device for state w of a combine (states + w * stride).
+// What the fields hold is described at the kernels that write them.
+// ----------------------------------------------------------------------------------------------------------------
+// Protocol #1: double sum[n][3] | float jbest[n] | float e2[n] | float sel3[n] | int32 idx[n] | double hsum[P_r][T][nv]
+struct PartialsStateViews {
+    double* sum = nullptr;
+    float *jbest = nullptr, *e2 = nullptr, *sel3 = nullptr;
+    int32_t* idx = nullptr;
+    double* hsum = nullptr;
+    PartialsStateViews() = default;
+    __host__ __device__ PartialsStateViews(const void* state, int64_t n) {
+        char* st = (char*)state;
+        sum = (double*)st, jbest = (float*)(st + n * 24), e2 = jbest + n, sel3 = e2 + n, idx = (int32_t*)(sel3 + n);
+        hsum = (double*)(st + head_bytes(n));
+    }
+    __host__ __device__ static size_t head_bytes(int64_t n) { return (size_t)n * 40; }   // what a combine reads of a state
+};
+
+// pose: double sum[n][3] | float e2[n] | int32 idx[n] | float sel[n][3], rounded up to a multiple of 8 bytes
+struct PoseStateViews {
+    double* sum = nullptr;
+    float* e2 = nullptr;
+    int32_t* idx = nullptr;
+    float* sel = nullptr;
+    PoseStateViews() = default;
+    __host__ __device__ PoseStateViews(const void* state, int64_t n) {
+        char* st = (char*)state;
+        sum = (double*)st, e2 = (float*)(st + n * 24), idx = (int32_t*)(e2 + n), sel = (float*)(idx + n);
+    }
+    __host__ __device__ static size_t head_bytes(int64_t n) { return (size_t)n * 44; }
+    __host__ __device__ static size_t bytes(int64_t n) { return (head_bytes(n) + 7) / 8 * 8; }
+};
+
+// Protocol #2: float jbest[n] | float e2[n] | float sel[n] | int32 idx[n] | double psum[P_r][T]
+struct P2StateViews {
+    float *jbest = nullptr, *e2 = nullptr, *sel = nullptr;
+    int32_t* idx = nullptr;
+    double* psum = nullptr;
+    P2StateViews() = default;
+    __host__ __device__ P2StateViews(const void* state, int64_t n) {
+        jbest = (float*)state, e2 = jbest + n, sel = e2 + n, idx = (int32_t*)(sel + n);
+        psum = (double*)((char*)state + head_bytes(n));
+    }
+    __host__ __device__ static size_t head_bytes(int64_t n) { return (size_t)n * 16; }
+};
+
+// frame pose (r = T*N*J rows): double sum[r][3] | float e2[r] | int32 idx[r] | int32 win[r] | float sel[r][3] | int32 count[N]
+struct FramePoseViews {
+    double* sum = nullptr;
+    float* e2 = nullptr;
+    int32_t *idx = nullptr, *win = nullptr;
+    float* sel = nullptr;
+    int32_t* count = nullptr;
+    FramePoseViews() = default;
+    __host__ __device__ FramePoseViews(const void* state, int64_t rows) {
+        char* st = (char*)state;
+        sum = (double*)st, e2 = (float*)(st + rows * 24), idx = (int32_t*)(e2 + rows), win = idx + rows;
+        sel = (float*)(win + rows), count = (int32_t*)(sel + 3 * rows);
+    }
+    __host__ __device__ static size_t bytes(int64_t rows, int64_t N) { return ((size_t)rows * 48 + (size_t)N * 4 + 7) / 8 * 8; }
+};
+
 __global__ void __launch_bounds__(256) metrics_kernel(const MetricsParams p) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t total = (int64_t)p.B * p.T * p.F * p.J;
     if (e >= total) return;
-    const int j = (int)(e % p.J);
-    const int f = (int)((e / p.J) % p.F);
-    const int t = (int)((e / ((int64_t)p.J * p.F)) % p.T);
-    const int b = (int)(e / ((int64_t)p.J * p.F * p.T));
+    const auto [b, t, f, j] = decode_btfj(e, p.T, p.F, p.J);
     const int jr = p.pbroot[j];
     const float* gpose = p.gt + ((int64_t)b * p.F + f) * p.J * 3;
     float g[3], gr[3];
@@ -2598,8 +2701,9 @@ __global__ void __launch_bounds__(256) metrics_kernel(const MetricsParams p) {
     const float gc[3] = {g[0] - gr[0], g[1] - gr[1], g[2] - gr[2]};
     const float* tr = p.traj + ((int64_t)b * p.F + f) * 3;
     const float* x2 = p.x2d + (((int64_t)b * p.F + f) * p.J + j) * 2;
-    const float fx = p.cam[0], fy = p.cam[1], cx = p.cam[2], cy = p.cam[3];
-    const float k1 = p.cam[4], k2 = p.cam[5], k3 = p.cam[6], p1 = p.cam[7], p2 = p.cam[8];
+    float cam[9];   // read once, ahead of the loop: its stores could alias p.cam
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cam[k] = p.cam[k];
     float best3 = INFINITY, best2 = INFINITY, sel3 = 0.f;
     float sm[3] = {0.f, 0.f, 0.f}, smr[3] = {0.f, 0.f, 0.f};
     for (int h = 0; h < p.P; ++h) {
@@ -2617,15 +2721,7 @@ __global__ void __launch_bounds__(256) metrics_kernel(const MetricsParams p) {
         best3 = fminf(best3, e3);
 #pragma unroll
         for (int k = 0; k < 3; ++k) sm[k] += w[k], smr[k] += wr[k];
-        // 2-D reprojection of the absolute pose (common/camera.py:30-60)
-        const float X = w[0] + tr[0], Y = w[1] + tr[1], Z = w[2] + tr[2];
-        const float xx = fminf(fmaxf(X / Z, -1.f), 1.f), yy = fminf(fmaxf(Y / Z, -1.f), 1.f);
-        const float r2 = xx * xx + yy * yy;
-        const float radial = 1.f + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2));
-        const float tan = p1 * xx + p2 * yy;
-        const float u = fx * (xx * (radial + tan) + p1 * r2) + cx, v = fy * (yy * (radial + tan) + p2 * r2) + cy;
-        const float q0 = u - x2[0], q1 = v - x2[1];
-        const float e2 = sqrtf(q0 * q0 + q1 * q1);
+        const float e2 = reproj_error(w, tr[0], tr[1], tr[2], x2[0], x2[1], cam);   // of the absolute pose
         if (e2 < best2) best2 = e2, sel3 = e3;  // first minimum wins, like torch.min(...).indices
     }
     const float invP = 1.0f / (float)p.P;
@@ -2645,10 +2741,10 @@ __global__ void __launch_bounds__(256) metrics_kernel(const MetricsParams p) {
 // e3, its GLOBAL hypothesis index) and the fp64 sum over h of the whole-body joint (the part root's sum is the sum
 // of another joint of the same frame: gathered at combine time); per local (h, t) the fp64 sums over (b, f, j) of
 // e3 and of epb per part.  combine_kernel merges W such states in ascending-h0 order into one state and / or the
-// four [B,T,F,J] maps metrics_kernel writes.  Per-hypothesis expressions are those of metrics_kernel, verbatim.
+// four [B,T,F,J] maps metrics_kernel writes.  Per-hypothesis expressions are those of metrics_kernel; e2 is reproj_error.
 //
-// State, one flat buffer (n = B*T*F*J, nv = 1 + num_parts); everything that depends on P_r is at the end, so a
-// ragged shard padded to the largest one is a prefix of the padded buffer:
+// State, one flat buffer (PartialsStateViews; n = B*T*F*J, nv = 1 + num_parts); everything that depends on P_r is at the
+// end, so a ragged shard padded to the largest one is a prefix of the padded buffer:
 //   double sum[n][3] | float jbest[n] | float e2[n] | float sel3[n] | int32 idx[n] | double hsum[P_r][T][nv]
 // hsum slots: 0 = sum of e3, 1 + i = sum of epb over the joints of part i.
 //
@@ -2670,9 +2766,7 @@ struct PartialsParams {
     const float* traj;  // [B,F,3]
     const float* cam;   // [9]
     const int32_t *conn, *pbroot, *part;  // [J]: connection joint, part root, part number (0 .. num_parts-1)
-    double* sum;        // state (see above)
-    float *jbest, *e2, *sel3;
-    int32_t* idx;
+    PartialsStateViews st;   // state (see above)
     double* share;      // scratch [B,T,nblk,P_r,nv]
     int B, T, P, F, J, h0, nv, nblk;
 };
@@ -2697,8 +2791,9 @@ __global__ void __launch_bounds__(256, 8) partials_kernel(const PartialsParams p
     const float gc[3] = {g[0] - gr[0], g[1] - gr[1], g[2] - gr[2]};
     const float* tr = p.traj + ((int64_t)b * p.F + f) * 3;
     const float* x2 = p.x2d + (((int64_t)b * p.F + f) * p.J + j) * 2;
-    const float fx = p.cam[0], fy = p.cam[1], cx = p.cam[2], cy = p.cam[3];
-    const float k1 = p.cam[4], k2 = p.cam[5], k3 = p.cam[6], p1 = p.cam[7], p2 = p.cam[8];
+    float cam[9];   // read once, ahead of the loop: its stores could alias p.cam
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cam[k] = p.cam[k];
     float best3 = INFINITY, best2 = INFINITY, sel3 = 0.f;
     int32_t hsel = -1;
     double sm[3] = {0.0, 0.0, 0.0};
@@ -2722,15 +2817,7 @@ __global__ void __launch_bounds__(256, 8) partials_kernel(const PartialsParams p
                 best3 = fminf(best3, e3);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) sm[k] += (double)w[k];
-                // 2-D reprojection of the absolute pose (common/camera.py:30-60)
-                const float X = w[0] + tr[0], Y = w[1] + tr[1], Z = w[2] + tr[2];
-                const float xx = fminf(fmaxf(X / Z, -1.f), 1.f), yy = fminf(fmaxf(Y / Z, -1.f), 1.f);
-                const float r2 = xx * xx + yy * yy;
-                const float radial = 1.f + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2));
-                const float tan = p1 * xx + p2 * yy;
-                const float u = fx * (xx * (radial + tan) + p1 * r2) + cx, v = fy * (yy * (radial + tan) + p2 * r2) + cy;
-                const float q0 = u - x2[0], q1 = v - x2[1];
-                const float e2 = sqrtf(q0 * q0 + q1 * q1);
+                const float e2 = reproj_error(w, tr[0], tr[1], tr[2], x2[0], x2[1], cam);   // of the absolute pose
                 if (e2 < best2) best2 = e2, sel3 = e3, hsel = p.h0 + h;  // first minimum wins inside the shard
             }
             s_e3[hh * PART_LD + tid] = e3;
@@ -2766,11 +2853,11 @@ __global__ void __launch_bounds__(256, 8) partials_kernel(const PartialsParams p
     }
     if (valid) {
         const int64_t e = ((int64_t)b * p.T + t) * FJ + fj;
-        p.sum[e * 3 + 0] = sm[0], p.sum[e * 3 + 1] = sm[1], p.sum[e * 3 + 2] = sm[2];
-        p.jbest[e] = best3;
-        p.e2[e] = best2;
-        p.sel3[e] = sel3;
-        p.idx[e] = hsel;
+        p.st.sum[e * 3 + 0] = sm[0], p.st.sum[e * 3 + 1] = sm[1], p.st.sum[e * 3 + 2] = sm[2];
+        p.st.jbest[e] = best3;
+        p.st.e2[e] = best2;
+        p.st.sel3[e] = sel3;
+        p.st.idx[e] = hsel;
     }
 }
 
@@ -2819,9 +2906,7 @@ struct CombineParams {
     int W;
     const float* gt;      // [B,F,J,3]
     const int32_t *conn, *pbroot;
-    double* m_sum;        // merged state (null: not wanted)
-    float *m_jbest, *m_e2, *m_sel3;
-    int32_t* m_idx;
+    PartialsStateViews merged;   // head of the merged state (sum null: not wanted)
     float *jbest, *pagg, *jagg, *paggpb;   // [B,T,F,J] (null: not wanted)
     int B, T, F, J, P;    // P: the TOTAL hypothesis count the P-Agg mean divides by
 };
@@ -2830,30 +2915,23 @@ __global__ void __launch_bounds__(256) combine_kernel(const CombineParams p) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t n = (int64_t)p.B * p.T * p.F * p.J;
     if (e >= n) return;
-    const int j = (int)(e % p.J);
-    const int f = (int)((e / p.J) % p.F);
-    const int b = (int)(e / ((int64_t)p.J * p.F * p.T));
+    const BTFJ at = decode_btfj(e, p.T, p.F, p.J);
+    const int b = at.b, f = at.f, j = at.j;
     const int jr = p.pbroot[j];
     const int64_t er = e - j + jr;          // the part root of the same (b, t, f)
     float best3 = INFINITY, best2 = INFINITY, sel3 = 0.f;
     int32_t hsel = -1;
     double s[3] = {0.0, 0.0, 0.0}, sr[3] = {0.0, 0.0, 0.0};
     for (int w = 0; w < p.W; ++w) {
-        const char* st = p.states + (int64_t)w * p.stride;
-        const double* sum = (const double*)st;
-        const float* jb = (const float*)(st + n * 24);
-        const float* e2 = jb + n;
-        const float* s3 = e2 + n;
-        const int32_t* ix = (const int32_t*)(s3 + n);
-        best3 = fminf(best3, jb[e]);
-        const int32_t hw = ix[e];
-        // the overall first minimum: the smallest e2, the lowest global index among equal ones
-        if (hw >= 0 && (hsel < 0 || e2[e] < best2 || (e2[e] == best2 && hw < hsel))) best2 = e2[e], hsel = hw, sel3 = s3[e];
+        const PartialsStateViews st(p.states + (int64_t)w * p.stride, n);
+        best3 = fminf(best3, st.jbest[e]);
+        const int32_t hw = st.idx[e];
+        if (candidate_wins(st.e2[e], hw, best2, hsel)) best2 = st.e2[e], hsel = hw, sel3 = st.sel3[e];   // the overall first minimum
 #pragma unroll
-        for (int k = 0; k < 3; ++k) s[k] += sum[e * 3 + k];
+        for (int k = 0; k < 3; ++k) s[k] += st.sum[e * 3 + k];
         if (p.jbest) {   // (not read when only merging: a merge may write its result over the first state)
 #pragma unroll
-            for (int k = 0; k < 3; ++k) sr[k] += sum[er * 3 + k];
+            for (int k = 0; k < 3; ++k) sr[k] += st.sum[er * 3 + k];
         }
     }
     if (p.jbest) {
@@ -2871,12 +2949,12 @@ __global__ void __launch_bounds__(256) combine_kernel(const CombineParams p) {
         p.pagg[e] = sqrtf(m0 * m0 + m1 * m1 + m2 * m2);
         p.paggpb[e] = sqrtf(n0 * n0 + n1 * n1 + n2 * n2);
     }
-    if (p.m_sum) {
-        p.m_sum[e * 3 + 0] = s[0], p.m_sum[e * 3 + 1] = s[1], p.m_sum[e * 3 + 2] = s[2];
-        p.m_jbest[e] = best3;
-        p.m_e2[e] = best2;
-        p.m_sel3[e] = sel3;
-        p.m_idx[e] = hsel;
+    if (p.merged.sum) {
+        p.merged.sum[e * 3 + 0] = s[0], p.merged.sum[e * 3 + 1] = s[1], p.merged.sum[e * 3 + 2] = s[2];
+        p.merged.jbest[e] = best3;
+        p.merged.e2[e] = best2;
+        p.merged.sel3[e] = sel3;
+        p.merged.idx[e] = hsel;
     }
 }
 
@@ -2886,12 +2964,12 @@ __global__ void __launch_bounds__(256) combine_kernel(const CombineParams p) {
 // scheme as above: pose_partials_kernel reduces hypotheses [h0, h0 + P_r) to a state whose size does not depend on P,
 // pose_combine_kernel merges W states in ascending-h0 order and / or writes the poses.
 //
-// State, one flat buffer (n = B*T*F*J), 44*n bytes rounded up to a multiple of 8:
+// State, one flat buffer (PoseStateViews; n = B*T*F*J), 44*n bytes rounded up to a multiple of 8:
 //   double sum[n][3] | float e2[n] | int32 idx[n] | float sel[n][3]
 // sum: fp64 sum over the local h, in h order, of wb_joint; (e2, idx, sel): smallest reprojection error, its GLOBAL
 // hypothesis index, its whole-body joint - the first minimum wins; (+inf, -1, NaN NaN NaN) where no e2 is finite.
-// e2 is metrics_kernel's expression (same operations, same order), so the index is the one partials_kernel and
-// procrustes_kernel pick.  x2d == null (then traj and cam are null too): mean-only, every candidate stays neutral.
+// e2 is reproj_error, as in metrics_kernel, so the index is the one partials_kernel and procrustes_kernel pick.
+// x2d == null (then traj and cam are null too): mean-only, every candidate stays neutral.
 //
 // pose_partials_kernel: one thread per (b, t, f, j) walks the local h; consecutive lanes read consecutive 12-byte
 // joints of one pose (every byte of a fetched line is used; the connection joint is a line of the same pose).  No
@@ -2903,10 +2981,7 @@ struct PosePartialsParams {
     const float* traj;  // [B,F,3]   or null
     const float* cam;   // [9]       or null
     const int32_t* conn;  // [J]
-    double* sum;        // state (see above)
-    float* e2;
-    int32_t* idx;
-    float* sel;
+    PoseStateViews st;    // state (see above)
     int B, T, P, F, J, h0;
 };
 
@@ -2914,10 +2989,7 @@ __global__ void __launch_bounds__(256, 8) pose_partials_kernel(const PosePartial
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t total = (int64_t)p.B * p.T * p.F * p.J;
     if (e >= total) return;
-    const int j = (int)(e % p.J);
-    const int f = (int)((e / p.J) % p.F);
-    const int t = (int)((e / ((int64_t)p.J * p.F)) % p.T);
-    const int b = (int)(e / ((int64_t)p.J * p.F * p.T));
+    const auto [b, t, f, j] = decode_btfj(e, p.T, p.F, p.J);
     const float* pose0 = p.pred + ((((int64_t)b * p.T + t) * p.P) * p.F + f) * p.J * 3;
     const int64_t hstride = (int64_t)p.F * p.J * 3;
     const float qnan = __builtin_nanf("");
@@ -2927,23 +2999,16 @@ __global__ void __launch_bounds__(256, 8) pose_partials_kernel(const PosePartial
     if (p.x2d) {
         const float* tr = p.traj + ((int64_t)b * p.F + f) * 3;
         const float* x2 = p.x2d + (((int64_t)b * p.F + f) * p.J + j) * 2;
-        const float fx = p.cam[0], fy = p.cam[1], cx = p.cam[2], cy = p.cam[3];
-        const float k1 = p.cam[4], k2 = p.cam[5], k3 = p.cam[6], p1 = p.cam[7], p2 = p.cam[8];
+        float cam[9];   // read once, ahead of the loop
+#pragma unroll
+        for (int k = 0; k < 9; ++k) cam[k] = p.cam[k];
 #pragma unroll 4
         for (int h = 0; h < p.P; ++h) {
             float w[3];
             wb_joint(pose0 + h * hstride, p.conn, j, w);
 #pragma unroll
             for (int k = 0; k < 3; ++k) sm[k] += (double)w[k];
-            // 2-D reprojection of the absolute pose (common/camera.py:30-60), as metrics_kernel states it
-            const float X = w[0] + tr[0], Y = w[1] + tr[1], Z = w[2] + tr[2];
-            const float xx = fminf(fmaxf(X / Z, -1.f), 1.f), yy = fminf(fmaxf(Y / Z, -1.f), 1.f);
-            const float r2 = xx * xx + yy * yy;
-            const float radial = 1.f + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2));
-            const float tan = p1 * xx + p2 * yy;
-            const float u = fx * (xx * (radial + tan) + p1 * r2) + cx, v = fy * (yy * (radial + tan) + p2 * r2) + cy;
-            const float q0 = u - x2[0], q1 = v - x2[1];
-            const float e2 = sqrtf(q0 * q0 + q1 * q1);
+            const float e2 = reproj_error(w, tr[0], tr[1], tr[2], x2[0], x2[1], cam);   // of the absolute pose
             if (e2 < best2) best2 = e2, hsel = p.h0 + h, sel[0] = w[0], sel[1] = w[1], sel[2] = w[2];  // first minimum wins
         }
     } else {
@@ -2955,21 +3020,18 @@ __global__ void __launch_bounds__(256, 8) pose_partials_kernel(const PosePartial
             for (int k = 0; k < 3; ++k) sm[k] += (double)w[k];
         }
     }
-    p.sum[e * 3 + 0] = sm[0], p.sum[e * 3 + 1] = sm[1], p.sum[e * 3 + 2] = sm[2];
-    p.e2[e] = best2;
-    p.idx[e] = hsel;
-    p.sel[e * 3 + 0] = sel[0], p.sel[e * 3 + 1] = sel[1], p.sel[e * 3 + 2] = sel[2];
+    p.st.sum[e * 3 + 0] = sm[0], p.st.sum[e * 3 + 1] = sm[1], p.st.sum[e * 3 + 2] = sm[2];
+    p.st.e2[e] = best2;
+    p.st.idx[e] = hsel;
+    p.st.sel[e * 3 + 0] = sel[0], p.st.sel[e * 3 + 1] = sel[1], p.st.sel[e * 3 + 2] = sel[2];
 }
 
 struct PoseCombineParams {
     const char* states;   // W states, `stride` bytes apart, in ascending-h0 order
     int64_t stride;
     int W;
-    double* m_sum;        // merged state (null: not wanted); may be the first operand
-    float* m_e2;
-    int32_t* m_idx;
-    float* m_sel;
-    float* mean;          // [B,T,F,J,3] (null: not wanted)
+    PoseStateViews merged;   // merged state (sum null: not wanted); may be the first operand
+    float* mean;         // [B,T,F,J,3] (null: not wanted)
     float* pick;          // [B,T,F,J,3] (null: not wanted)
     int32_t* pick_idx;    // [B,T,F,J]   (null: not wanted)
     int64_t n;            // B*T*F*J
@@ -2987,24 +3049,19 @@ __global__ void __launch_bounds__(256) pose_combine_kernel(const PoseCombinePara
     int32_t hsel = -1;
     double s[3] = {0.0, 0.0, 0.0};
     for (int w = 0; w < p.W; ++w) {
-        const char* st = p.states + (int64_t)w * p.stride;
-        const double* sum = (const double*)st;
-        const float* e2 = (const float*)(st + n * 24);
-        const int32_t* ix = (const int32_t*)(e2 + n);
-        const float* sl = (const float*)(ix + n);
+        const PoseStateViews st(p.states + (int64_t)w * p.stride, n);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) s[k] += sum[e * 3 + k];
-        const int32_t hw = ix[e];
-        const float ew = e2[e];
-        // the overall first minimum: the smallest e2, the lowest global index among equal ones
-        if (hw >= 0 && (hsel < 0 || ew < best2 || (ew == best2 && hw < hsel)))
-            best2 = ew, hsel = hw, sel[0] = sl[e * 3 + 0], sel[1] = sl[e * 3 + 1], sel[2] = sl[e * 3 + 2];
+        for (int k = 0; k < 3; ++k) s[k] += st.sum[e * 3 + k];
+        const int32_t hw = st.idx[e];
+        const float ew = st.e2[e];
+        if (candidate_wins(ew, hw, best2, hsel))   // the overall first minimum
+            best2 = ew, hsel = hw, sel[0] = st.sel[e * 3 + 0], sel[1] = st.sel[e * 3 + 1], sel[2] = st.sel[e * 3 + 2];
     }
-    if (p.m_sum) {
-        p.m_sum[e * 3 + 0] = s[0], p.m_sum[e * 3 + 1] = s[1], p.m_sum[e * 3 + 2] = s[2];
-        p.m_e2[e] = best2;
-        p.m_idx[e] = hsel;
-        p.m_sel[e * 3 + 0] = sel[0], p.m_sel[e * 3 + 1] = sel[1], p.m_sel[e * 3 + 2] = sel[2];
+    if (p.merged.sum) {
+        p.merged.sum[e * 3 + 0] = s[0], p.merged.sum[e * 3 + 1] = s[1], p.merged.sum[e * 3 + 2] = s[2];
+        p.merged.e2[e] = best2;
+        p.merged.idx[e] = hsel;
+        p.merged.sel[e * 3 + 0] = sel[0], p.merged.sel[e * 3 + 1] = sel[1], p.merged.sel[e * 3 + 2] = sel[2];
     }
     if (p.mean) {
         const double P = (double)p.P;   // divided in fp64, rounded once
@@ -3035,8 +3092,8 @@ __global__ void __launch_bounds__(256) pose_combine_kernel(const PoseCombinePara
 // lanes walk the joints (the rounds loop is wave-uniform: a lane without a joint in a round adds nothing and still feeds
 // its 0.0 to the butterfly), three fp64 butterflies, the solve in every lane, and lane h - c0 keeps t_h.  B: every lane
 // takes its joints round by round and walks the chunk's h serially (t_h by a shuffle from its keeper, the joint re-read:
-// a cache hit), adding to sum and keeping the first minimum of e2 - pose_partials_kernel's expression, compiled with the
-// same contraction setting as there.  The running element of a joint lives in registers within a chunk and in the state
+// a cache hit), adding to sum and keeping the first minimum of e2 - reproj_error, compiled with the same contraction
+// setting as in pose_partials_kernel.  The running element of a joint lives in registers within a chunk and in the state
 // itself between chunks (only P_r > 64 ever re-reads it; the same thread wrote it).  No LDS, no atomics, no scratch.
 // ----------------------------------------------------------------------------------------------------------------
 struct PoseFitParams {
@@ -3045,44 +3102,67 @@ struct PoseFitParams {
     const float* conf;    // [B,F,J] or null (every weight 1)
     const float* cam;     // [9]
     const int32_t* conn;  // [J]
-    double* sum;          // the pose state
-    float* e2;
-    int32_t* idx;
-    float* sel;
+    PoseStateViews st;    // the pose state
     float* tfit;          // [B,T,P_r,F,3] or null
     int B, T, P, F, J, h0;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
+// Joint j of a root fit: its weight c and normalised image point (a, b) and, where its whole-body position w is given,
+// the residual terms rx, ry.  A joint past J, without a weight > 0 or (ROOT_FINITE_POSE) with a w that is not finite
+// takes no part: on = 0 and everything 0.0.  THE statement of the weight rule, for both fit kernels.  The caller
+// has read w (three floats of its own); weight and detection are read here before the first test, so that the loads of
+// a caller's several joints overlap.
+struct RootJoint {
+    double a, b, c, rx, ry;
+    int on;
+};
+enum RootPose { ROOT_NO_POSE, ROOT_POSE, ROOT_FINITE_POSE };   // w: not given (null) / given / given, and it must be finite
+
+__device__ __forceinline__ RootJoint root_joint(const float* x2, const float* cf, int j, int J, double fx, double fy,
+                                                       double cx, double cy, RootPose pose, const float* w) {
+#pragma clang fp contract(off)
+    RootJoint q{0.0, 0.0, 0.0, 0.0, 0.0, 0};
+    if (j < J) {
+        const bool posed = pose != ROOT_NO_POSE;
+        const float cw = cf ? cf[j] : 1.f;
+        const float u = x2[2 * j], v = x2[2 * j + 1];
+        const float wx = posed ? w[0] : 0.f, wy = posed ? w[1] : 0.f, wz = posed ? w[2] : 0.f;
+        if (cw > 0.f && (pose != ROOT_FINITE_POSE || (isfinite(wx) && isfinite(wy) && isfinite(wz)))) {
+            q.c = (double)cw;
+            q.a = ((double)u - cx) / fx;
+            q.b = ((double)v - cy) / fy;
+            if (posed) {
+                q.rx = q.a * (double)wz - (double)wx;
+                q.ry = q.b * (double)wz - (double)wy;
+            }
+            q.on = 1;
+        }
+    }
+    return q;
 }
 
-// the weight and the normalised image point of joint j; false: the joint takes no part
-__device__ __forceinline__ bool fit_joint(const float* x2, const float* cf, int j, double fx, double fy, double cx, double cy,
-                                          double& a, double& b, double& c) {
-    const float cw = cf ? cf[j] : 1.f;
-    if (!(cw > 0.f)) return false;
-    c = (double)cw;
-    a = ((double)x2[2 * j] - cx) / fx;
-    b = ((double)x2[2 * j + 1] - cy) / fy;
-    return true;
+// the closed form behind the seven sums (see above): its denominator, whether the sums admit a fit at all, and the root
+__device__ __forceinline__ double root_den(double W, double Sa, double Sb, double Sq) {
+#pragma clang fp contract(off)
+    return Sq - (Sa * Sa + Sb * Sb) / W;
 }
 
-// pose_partials_kernel's reprojection error of the whole-body joint w under the root tr (the same text)
-__device__ __forceinline__ float reproj_e2(const float (&w)[3], float tr0, float tr1, float tr2, float x20, float x21,
-                                           const float* cam) {
-    const float fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
-    const float k1 = cam[4], k2 = cam[5], k3 = cam[6], p1 = cam[7], p2 = cam[8];
-    const float X = w[0] + tr0, Y = w[1] + tr1, Z = w[2] + tr2;
-    const float xx = fminf(fmaxf(X / Z, -1.f), 1.f), yy = fminf(fmaxf(Y / Z, -1.f), 1.f);
-    const float r2 = xx * xx + yy * yy;
-    const float radial = 1.f + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2));
-    const float tan = p1 * xx + p2 * yy;
-    const float u = fx * (xx * (radial + tan) + p1 * r2) + cx, v = fy * (yy * (radial + tan) + p2 * r2) + cy;
-    const float q0 = u - x20, q1 = v - x21;
-    return sqrtf(q0 * q0 + q1 * q1);
+__device__ __forceinline__ bool root_fittable(int cnt, double den) { return cnt >= 2 && isfinite(den) && den > 0.0; }
+
+struct RootSolution {
+    double tx, ty, tz;   // before the rounding (the residual is formed from these)
+    float t0, t1, t2;
+    bool ok;             // the rounded root is finite
+};
+
+__device__ __forceinline__ RootSolution root_solve(double W, double Sa, double Sb, double den, double Srx, double Sry, double Sm) {
+#pragma clang fp contract(off)
+    RootSolution r;
+    r.tz = (-Sm + (Sa * Srx + Sb * Sry) / W) / den;
+    r.tx = (Srx + Sa * r.tz) / W, r.ty = (Sry + Sb * r.tz) / W;
+    r.t0 = (float)r.tx, r.t1 = (float)r.ty, r.t2 = (float)r.tz;
+    r.ok = isfinite(r.t0) && isfinite(r.t1) && isfinite(r.t2);
+    return r;
 }
 
 __global__ void __launch_bounds__(256) pose_fit_partials_kernel(const PoseFitParams p) {
@@ -3106,17 +3186,14 @@ __global__ void __launch_bounds__(256) pose_fit_partials_kernel(const PoseFitPar
         double w0 = 0.0, sa = 0.0, sb = 0.0, sq = 0.0;
         int cnt = 0;
         for (int r = 0; r < rounds; ++r) {
-            const int j = r * 64 + lane;
-            double a, bb, c;
-            if (j < J && fit_joint(x2, cf, j, fx, fy, cx, cy, a, bb, c))
-                w0 += c, sa += c * a, sb += c * bb, sq += c * (a * a + bb * bb), ++cnt;
+            const RootJoint q = root_joint(x2, cf, r * 64 + lane, J, fx, fy, cx, cy, ROOT_NO_POSE, nullptr);
+            if (q.on) w0 += q.c, sa += q.c * q.a, sb += q.c * q.b, sq += q.c * (q.a * q.a + q.b * q.b), ++cnt;
         }
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
         W = wave_sum_f64(w0), Sa = wave_sum_f64(sa), Sb = wave_sum_f64(sb);
-        const double Sq = wave_sum_f64(sq);
-        den = Sq - (Sa * Sa + Sb * Sb) / W;
-        can = cnt >= 2 && isfinite(den) && den > 0.0;
+        den = root_den(W, Sa, Sb, wave_sum_f64(sq));
+        can = root_fittable(cnt, den);
     }
     for (int c0 = 0; c0 < p.P; c0 += 64) {
         const int nh = min(64, p.P - c0);
@@ -3131,19 +3208,13 @@ __global__ void __launch_bounds__(256) pose_fit_partials_kernel(const PoseFitPar
                 double srx = 0.0, sry = 0.0, sm = 0.0;
                 for (int r = 0; r < rounds; ++r) {
                     const int j = r * 64 + lane;
-                    double a, bb, c;
-                    if (j < J && fit_joint(x2, cf, j, fx, fy, cx, cy, a, bb, c)) {
-                        float w[3];
-                        wb_joint(pose, p.conn, j, w);
-                        const double rx = a * (double)w[2] - (double)w[0], ry = bb * (double)w[2] - (double)w[1];
-                        srx += c * rx, sry += c * ry, sm += c * (a * rx + bb * ry);
-                    }
+                    float w[3] = {0.f, 0.f, 0.f};
+                    if (j < J) wb_joint(pose, p.conn, j, w);
+                    const RootJoint q = root_joint(x2, cf, j, J, fx, fy, cx, cy, ROOT_POSE, w);   // a w that is not finite spoils the fit
+                    if (q.on) srx += q.c * q.rx, sry += q.c * q.ry, sm += q.c * (q.a * q.rx + q.b * q.ry);
                 }
-                const double Srx = wave_sum_f64(srx), Sry = wave_sum_f64(sry), Sm = wave_sum_f64(sm);
-                const double tz = (-Sm + (Sa * Srx + Sb * Sry) / W) / den;
-                const double tx = (Srx + Sa * tz) / W, ty = (Sry + Sb * tz) / W;
-                const float t0 = (float)tx, t1 = (float)ty, t2 = (float)tz;
-                if (isfinite(t0) && isfinite(t1) && isfinite(t2)) tf[0] = t0, tf[1] = t1, tf[2] = t2, ok = 1;
+                const RootSolution s = root_solve(W, Sa, Sb, den, wave_sum_f64(srx), wave_sum_f64(sry), wave_sum_f64(sm));
+                if (s.ok) tf[0] = s.t0, tf[1] = s.t1, tf[2] = s.t2, ok = 1;
             }
             if (lane == hh) myt[0] = tf[0], myt[1] = tf[1], myt[2] = tf[2], myok = ok;
             if (p.tfit && lane < 3)
@@ -3160,9 +3231,9 @@ __global__ void __launch_bounds__(256) pose_fit_partials_kernel(const PoseFitPar
             if (have) {
                 x20 = x2[2 * j], x21 = x2[2 * j + 1];
                 if (c0) {
-                    sm[0] = p.sum[e * 3 + 0], sm[1] = p.sum[e * 3 + 1], sm[2] = p.sum[e * 3 + 2];
-                    best2 = p.e2[e], hsel = p.idx[e];
-                    sel[0] = p.sel[e * 3 + 0], sel[1] = p.sel[e * 3 + 1], sel[2] = p.sel[e * 3 + 2];
+                    sm[0] = p.st.sum[e * 3 + 0], sm[1] = p.st.sum[e * 3 + 1], sm[2] = p.st.sum[e * 3 + 2];
+                    best2 = p.st.e2[e], hsel = p.st.idx[e];
+                    sel[0] = p.st.sel[e * 3 + 0], sel[1] = p.st.sel[e * 3 + 1], sel[2] = p.st.sel[e * 3 + 2];
                 }
             }
             for (int hh = 0; hh < nh; ++hh) {
@@ -3174,16 +3245,16 @@ __global__ void __launch_bounds__(256) pose_fit_partials_kernel(const PoseFitPar
 #pragma unroll
                     for (int k = 0; k < 3; ++k) sm[k] += (double)w[k];
                     if (ok && weighted) {
-                        const float e2 = reproj_e2(w, t0, t1, t2, x20, x21, p.cam);
+                        const float e2 = reproj_error(w, t0, t1, t2, x20, x21, p.cam);
                         if (e2 < best2) best2 = e2, hsel = p.h0 + c0 + hh, sel[0] = w[0], sel[1] = w[1], sel[2] = w[2];  // first minimum wins
                     }
                 }
             }
             if (have) {
-                p.sum[e * 3 + 0] = sm[0], p.sum[e * 3 + 1] = sm[1], p.sum[e * 3 + 2] = sm[2];
-                p.e2[e] = best2;
-                p.idx[e] = hsel;
-                p.sel[e * 3 + 0] = sel[0], p.sel[e * 3 + 1] = sel[1], p.sel[e * 3 + 2] = sel[2];
+                p.st.sum[e * 3 + 0] = sm[0], p.st.sum[e * 3 + 1] = sm[1], p.st.sum[e * 3 + 2] = sm[2];
+                p.st.e2[e] = best2;
+                p.st.idx[e] = hsel;
+                p.st.sel[e * 3 + 0] = sel[0], p.st.sel[e * 3 + 1] = sel[1], p.st.sel[e * 3 + 2] = sel[2];
             }
         }
     }
@@ -3343,7 +3414,7 @@ __global__ void __launch_bounds__(64) spread_count_kernel(const char* states, in
 // [B,T,F,J] (and / or one spread state); the fold below maps (window, local frame) to the global frame n = start + f and
 // merges the row into the FRAME state, whose rows are (t, n, j) - the order of the outputs [T,N,J,..].
 //
-// Frame pose state, one flat buffer (r = T*N*J rows), 48*r + 4*N bytes rounded up to a multiple of 8:
+// Frame pose state, one flat buffer (FramePoseViews; r = T*N*J rows), 48*r + 4*N bytes rounded up to a multiple of 8:
 //   double sum[r][3] | float e2[r] | int32 idx[r] | int32 win[r] | float sel[r][3] | int32 count[N]
 // Frame spread state, (9*r + N)*8 bytes:  double sum[r][3] | double m2[r][6] | double count[N]
 // count[n]: the hypotheses folded into frame n (windows covering it x hypotheses per window).
@@ -3366,16 +3437,8 @@ __device__ __forceinline__ int first_window_over(const int32_t* starts, int B, i
 }
 
 struct PoseWindowsFoldParams {
-    double* f_sum;        // frame state (see above)
-    float* f_e2;
-    int32_t* f_idx;
-    int32_t* f_win;
-    float* f_sel;
-    int32_t* f_count;
-    const double* s_sum;  // the batch's pose state [B,T,F,J]
-    const float* s_e2;
-    const int32_t* s_idx;
-    const float* s_sel;
+    FramePoseViews frame;   // frame state (see above)
+    PoseStateViews state;   // the batch's pose state [B,T,F,J], read only
     const int32_t* starts;  // [B] device
     const int32_t* valid;   // [B] device
     int N, B, T, F, J, w0, P, n_lo, n_hi;
@@ -3389,32 +3452,36 @@ __global__ void __launch_bounds__(256) pose_windows_fold_kernel(const PoseWindow
     const int n = p.n_lo + (int)((e / p.J) % span);
     const int t = (int)(e / ((int64_t)p.J * span));
     const int64_t row = ((int64_t)t * p.N + n) * p.J + j;
-    double s[3] = {p.f_sum[row * 3 + 0], p.f_sum[row * 3 + 1], p.f_sum[row * 3 + 2]};
-    float best2 = p.f_e2[row], sel[3] = {p.f_sel[row * 3 + 0], p.f_sel[row * 3 + 1], p.f_sel[row * 3 + 2]};
-    int32_t hsel = p.f_idx[row], wsel = p.f_win[row];
+    const FramePoseViews& fr = p.frame;
+    const PoseStateViews& st = p.state;
+    double s[3] = {fr.sum[row * 3 + 0], fr.sum[row * 3 + 1], fr.sum[row * 3 + 2]};
+    float best2 = fr.e2[row], sel[3] = {fr.sel[row * 3 + 0], fr.sel[row * 3 + 1], fr.sel[row * 3 + 2]};
+    int32_t hsel = fr.idx[row], wsel = fr.win[row];
     int covered = 0;
     for (int b = first_window_over(p.starts, p.B, n, p.F); b < p.B && p.starts[b] <= n; ++b) {
         const int f = n - p.starts[b];
         if (f < 0 || f >= min(p.valid[b], p.F)) continue;   // a padded frame, or device tables that are not the host's
         const int64_t se = (((int64_t)b * p.T + t) * p.F + f) * p.J + j;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) s[k] += p.s_sum[se * 3 + k];
-        const float ew = p.s_e2[se];
-        if (ew < best2)   // strict: among equal errors the lowest window stays, and within it the lowest hypothesis
-            best2 = ew, hsel = p.s_idx[se], wsel = p.w0 + b, sel[0] = p.s_sel[se * 3 + 0], sel[1] = p.s_sel[se * 3 + 1],
-            sel[2] = p.s_sel[se * 3 + 2];
+        for (int k = 0; k < 3; ++k) s[k] += st.sum[se * 3 + k];
+        const float ew = st.e2[se];
+        const int32_t hw = st.idx[se];
+        // the index the rule orders equal errors by is the WINDOW (windows come in ascending order: the lowest window stays),
+        // and within a window the state already holds its lowest hypothesis
+        if (candidate_wins(ew, hw >= 0 ? p.w0 + b : -1, best2, wsel))
+            best2 = ew, hsel = hw, wsel = p.w0 + b, sel[0] = st.sel[se * 3 + 0], sel[1] = st.sel[se * 3 + 1], sel[2] = st.sel[se * 3 + 2];
         ++covered;
     }
     if (!covered) return;   // a gap between the windows of the batch: the frame is not touched
-    p.f_sum[row * 3 + 0] = s[0], p.f_sum[row * 3 + 1] = s[1], p.f_sum[row * 3 + 2] = s[2];
-    p.f_e2[row] = best2;
-    p.f_idx[row] = hsel;
-    p.f_win[row] = wsel;
-    p.f_sel[row * 3 + 0] = sel[0], p.f_sel[row * 3 + 1] = sel[1], p.f_sel[row * 3 + 2] = sel[2];
+    fr.sum[row * 3 + 0] = s[0], fr.sum[row * 3 + 1] = s[1], fr.sum[row * 3 + 2] = s[2];
+    fr.e2[row] = best2;
+    fr.idx[row] = hsel;
+    fr.win[row] = wsel;
+    fr.sel[row * 3 + 0] = sel[0], fr.sel[row * 3 + 1] = sel[1], fr.sel[row * 3 + 2] = sel[2];
     if (t == 0 && j == 0) {   // one thread per frame: count += P_total, once per window
-        int32_t c = p.f_count[n];
+        int32_t c = fr.count[n];
         for (int k = 0; k < covered; ++k) c += p.P;
-        p.f_count[n] = c;
+        fr.count[n] = c;
     }
 }
 
@@ -3500,11 +3567,7 @@ __global__ void __launch_bounds__(256) spread_windows_count_kernel(const SpreadW
 }
 
 struct FramesFinishParams {
-    const double* f_sum;     // frame pose state (null: none)
-    const int32_t* f_idx;
-    const int32_t* f_win;
-    const float* f_sel;
-    const int32_t* f_count;
+    FramePoseViews frame;    // frame pose state, read only (sum null: none)
     const double* spread;    // frame spread state (null: none)
     float* mean;             // [T,N,J,3] (null: not wanted)
     float* pick;             // [T,N,J,3]
@@ -3524,13 +3587,13 @@ __global__ void __launch_bounds__(256) frames_finish_kernel(const FramesFinishPa
     if (e >= rows) return;
     const int n = (int)((e / p.J) % p.N);
     if (p.mean) {
-        const double P = (double)p.f_count[n];
+        const double P = (double)p.frame.count[n];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) p.mean[e * 3 + k] = (float)(p.f_sum[e * 3 + k] / P);
+        for (int k = 0; k < 3; ++k) p.mean[e * 3 + k] = (float)(p.frame.sum[e * 3 + k] / P);
     }
-    if (p.pick) p.pick[e * 3 + 0] = p.f_sel[e * 3 + 0], p.pick[e * 3 + 1] = p.f_sel[e * 3 + 1], p.pick[e * 3 + 2] = p.f_sel[e * 3 + 2];
-    if (p.pick_idx) p.pick_idx[e] = p.f_idx[e];
-    if (p.pick_win) p.pick_win[e] = p.f_win[e];
+    if (p.pick) p.pick[e * 3 + 0] = p.frame.sel[e * 3 + 0], p.pick[e * 3 + 1] = p.frame.sel[e * 3 + 1], p.pick[e * 3 + 2] = p.frame.sel[e * 3 + 2];
+    if (p.pick_idx) p.pick_idx[e] = p.frame.idx[e];
+    if (p.pick_win) p.pick_win[e] = p.frame.win[e];
     if (p.sd || p.cov) {
         const double na = p.spread[9 * rows + n];
         double s[3], m[6];
@@ -3555,8 +3618,8 @@ __global__ void __launch_bounds__(256) frames_finish_kernel(const FramesFinishPa
 // ----------------------------------------------------------------------------------------------------------------
 // The camera-space root of the per-frame pose (statement: pafuse_amd/trajectory.py).
 // frames_root_fit_kernel fits the root t of the FINISHED pose [T,N,J,3] - the pooled mean or the pick, one per (t, n) - by
-// the algebra of pose_fit_partials_kernel above, operation for operation (fp64, contraction off, every sum over j in the
-// lane-then-butterfly order).  One addition to the weight rule: a joint any component of whose pose is not finite (a frame
+// the algebra of pose_fit_partials_kernel above - the same root_joint, root_den, root_fittable and root_solve (fp64,
+// contraction off, every sum over j in the lane-then-butterfly order).  One addition to the weight rule: a joint any component of whose pose is not finite (a frame
 // no window covered, a pick without a candidate) drops out of every sum like a joint without a weight, so W, Sa, Sb, Sq
 // are per (t, n) here.  No fit (fewer than two joints in the sums, den not finite and > 0, t not finite in fp32): NaN in
 // traj, 0 in wsum, NaN in resid.  resid = sqrt(R / W), R = sum c*(ex^2 + ey^2) in the same order with
@@ -3579,31 +3642,6 @@ struct FramesRootFitParams {
     int T, N, J;
 };
 
-struct RootFitJoint {
-    double a, b, c, rx, ry;   // all 0.0 where the joint takes no part
-    int on;
-};
-
-__device__ __forceinline__ RootFitJoint root_fit_joint(const float* pose, const float* x2, const float* cf, int j, int J,
-                                                       double fx, double fy, double cx, double cy) {
-#pragma clang fp contract(off)
-    RootFitJoint q{0.0, 0.0, 0.0, 0.0, 0.0, 0};
-    if (j < J) {
-        const float cw = cf ? cf[j] : 1.f;
-        const float u = x2[2 * j], v = x2[2 * j + 1];
-        const float wx = pose[3 * j], wy = pose[3 * j + 1], wz = pose[3 * j + 2];
-        if (cw > 0.f && isfinite(wx) && isfinite(wy) && isfinite(wz)) {
-            q.c = (double)cw;
-            q.a = ((double)u - cx) / fx;
-            q.b = ((double)v - cy) / fy;
-            q.rx = q.a * (double)wz - (double)wx;
-            q.ry = q.b * (double)wz - (double)wy;
-            q.on = 1;
-        }
-    }
-    return q;
-}
-
 template <int SLOTS>
 __global__ void __launch_bounds__(256) frames_root_fit_kernel(const FramesRootFitParams p) {
 #pragma clang fp contract(off)
@@ -3618,18 +3656,23 @@ __global__ void __launch_bounds__(256) frames_root_fit_kernel(const FramesRootFi
     const double fx = (double)p.cam[0], fy = (double)p.cam[1], cx = (double)p.cam[2], cy = (double)p.cam[3];
     constexpr int KEPT = SLOTS > 0 ? SLOTS : 1;
     const int rounds = SLOTS > 0 ? SLOTS : (J + 63) / 64;
-    RootFitJoint q[KEPT];
-    auto joint = [&](int r) -> RootFitJoint {
+    RootJoint q[KEPT];
+    auto load = [&](int j) -> RootJoint {
+        float w[3] = {0.f, 0.f, 0.f};
+        if (j < J) w[0] = pose[3 * j], w[1] = pose[3 * j + 1], w[2] = pose[3 * j + 2];
+        return root_joint(x2, cf, j, J, fx, fy, cx, cy, ROOT_FINITE_POSE, w);
+    };
+    auto joint = [&](int r) -> RootJoint {
         if constexpr (SLOTS > 0) return q[r];
-        else return root_fit_joint(pose, x2, cf, r * 64 + lane, J, fx, fy, cx, cy);
+        else return load(r * 64 + lane);
     };
 #pragma unroll
-    for (int r = 0; r < KEPT; ++r) q[r] = root_fit_joint(pose, x2, cf, SLOTS > 0 ? r * 64 + lane : J, J, fx, fy, cx, cy);   // SLOTS == 0: unused
+    for (int r = 0; r < KEPT; ++r) q[r] = load(SLOTS > 0 ? r * 64 + lane : J);   // SLOTS == 0: unused
     double w = 0.0, sa = 0.0, sb = 0.0, sq = 0.0, srx = 0.0, sry = 0.0, sm = 0.0;
     int cnt = 0;
 #pragma unroll KEPT
     for (int r = 0; r < rounds; ++r) {
-        const RootFitJoint g = joint(r);
+        const RootJoint g = joint(r);
         w += g.c, sa += g.c * g.a, sb += g.c * g.b, sq += g.c * (g.a * g.a + g.b * g.b);
         srx += g.c * g.rx, sry += g.c * g.ry, sm += g.c * (g.a * g.rx + g.b * g.ry);
         cnt += g.on;
@@ -3641,19 +3684,18 @@ __global__ void __launch_bounds__(256) frames_root_fit_kernel(const FramesRootFi
         cnt += __shfl_xor(cnt, o);
         w += w2, sa += sa2, sb += sb2, sq += sq2, srx += srx2, sry += sry2, sm += sm2;
     }
-    const double den = sq - (sa * sa + sb * sb) / w;
-    const double tz = (-sm + (sa * srx + sb * sry) / w) / den;
-    const double tx = (srx + sa * tz) / w, ty = (sry + sb * tz) / w;
-    const float t0 = (float)tx, t1 = (float)ty, t2 = (float)tz;
-    const bool ok = cnt >= 2 && isfinite(den) && den > 0.0 && isfinite(t0) && isfinite(t1) && isfinite(t2);
+    const double den = root_den(w, sa, sb, sq);
+    const RootSolution sol = root_solve(w, sa, sb, den, srx, sry, sm);
+    const bool ok = root_fittable(cnt, den) && sol.ok;
+    const double tx = sol.tx, ty = sol.ty, tz = sol.tz;
     const float qnan = __builtin_nanf("");
-    if (lane < 3) p.traj[item * 3 + lane] = !ok ? qnan : lane == 0 ? t0 : lane == 1 ? t1 : t2;
+    if (lane < 3) p.traj[item * 3 + lane] = !ok ? qnan : lane == 0 ? sol.t0 : lane == 1 ? sol.t1 : sol.t2;
     if (p.wsum && lane == 3) p.wsum[item] = ok ? (float)w : 0.f;
     if (p.resid) {
         double rs = 0.0;
 #pragma unroll KEPT
         for (int r = 0; r < rounds; ++r) {
-            const RootFitJoint g = joint(r);
+            const RootJoint g = joint(r);
             const double ex = (tx - g.a * tz) - g.rx, ey = (ty - g.b * tz) - g.ry;
             const double term = g.c * (ex * ex + ey * ey);
             rs += g.on ? term : 0.0;           // a joint that takes no part feeds 0.0 whatever t holds
@@ -3741,28 +3783,7 @@ struct ProcrustesParams {
     int B, T, P, F, J;
 };
 
-__device__ __forceinline__ double p2_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);   // a + b == b + a: every lane ends with the same bits
-    return v;
-}
-
 __device__ __forceinline__ double p2_min(double a, double e) { return (isnan(e) || e < a) ? e : a; }  // NaN sticks
-
-// The 2-D reprojection error of metrics_kernel (common/camera.py:30-60), restated with the same expressions in the
-// same order so that both kernels pick the same hypothesis.
-__device__ __forceinline__ float p2_reproj_error(const float (&w)[3], const float* tr, const float* cam, const float* x2) {
-    const float fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
-    const float k1 = cam[4], k2 = cam[5], k3 = cam[6], p1 = cam[7], p2 = cam[8];
-    const float X = w[0] + tr[0], Y = w[1] + tr[1], Z = w[2] + tr[2];
-    const float xx = fminf(fmaxf(X / Z, -1.f), 1.f), yy = fminf(fmaxf(Y / Z, -1.f), 1.f);
-    const float r2 = xx * xx + yy * yy;
-    const float radial = 1.f + (k1 * r2 + k2 * (r2 * r2) + k3 * (r2 * r2 * r2));
-    const float tan = p1 * xx + p2 * yy;
-    const float u = fx * (xx * (radial + tan) + p1 * r2) + cx, v = fy * (yy * (radial + tan) + p2 * r2) + cy;
-    const float q0 = u - x2[0], q1 = v - x2[1];
-    return sqrtf(q0 * q0 + q1 * q1);
-}
 
 // H[a][b] = sum_j X0_ja Y0_jb / (|X0| |Y0|) -> M = a R^T, so that the aligned centred joint is M y0 (column vectors;
 // the reference's row-vector form is y0^T a R).  Wave-uniform: every lane runs the same arithmetic on the same bits.
@@ -3829,7 +3850,7 @@ __device__ __forceinline__ double p2_centre_target(const float* gpose, const int
         for (int k = 0; k < 3; ++k) x0[s][k] = (double)g[k], mx[k] += x0[s][k];
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) mx[k] = p2_wave_sum(mx[k]) / (double)J;
+    for (int k = 0; k < 3; ++k) mx[k] = wave_sum_f64(mx[k]) / (double)J;
     double nx = 0.0;
 #pragma unroll
     for (int s = 0; s < P2_SLOTS; ++s) {
@@ -3837,7 +3858,7 @@ __device__ __forceinline__ double p2_centre_target(const float* gpose, const int
 #pragma unroll
         for (int k = 0; k < 3; ++k) x0[s][k] = valid ? x0[s][k] - mx[k] : 0.0, nx += x0[s][k] * x0[s][k];
     }
-    return sqrt(p2_wave_sum(nx));
+    return sqrt(wave_sum_f64(nx));
 }
 
 // One pose y (whole-body joints of this lane's slots, 0 past J) aligned to the centred target x0: centres y in place,
@@ -3851,7 +3872,7 @@ __device__ __forceinline__ double p2_align_pose(double (&y)[P2_SLOTS][3], const 
 #pragma unroll
         for (int k = 0; k < 3; ++k) my[k] += y[s][k];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) my[k] = p2_wave_sum(my[k]) / (double)J;
+    for (int k = 0; k < 3; ++k) my[k] = wave_sum_f64(my[k]) / (double)J;
     double ny = 0.0, H[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
 #pragma unroll
     for (int s = 0; s < P2_SLOTS; ++s) {
@@ -3863,12 +3884,12 @@ __device__ __forceinline__ double p2_align_pose(double (&y)[P2_SLOTS][3], const 
 #pragma unroll
             for (int c = 0; c < 3; ++c) H[r][c] += x0[s][r] * y[s][c];
     }
-    ny = sqrt(p2_wave_sum(ny));
+    ny = sqrt(wave_sum_f64(ny));
     const double inv = 1.0 / (nx * ny);
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) H[r][c] = p2_wave_sum(H[r][c]) * inv;
+        for (int c = 0; c < 3; ++c) H[r][c] = wave_sum_f64(H[r][c]) * inv;
     double M[3][3];
     p2_similarity(H, nx / ny, M);
     double esum = 0.0;
@@ -3939,7 +3960,7 @@ __global__ void __launch_bounds__(64 * P2_WAVES) procrustes_kernel(const Procrus
                     for (int k = 0; k < 3; ++k) y[s][k] = mean_pose[j * 3 + k];
                 } else {
                     wb_joint(pose0 + h * hstride, p.conn, j, w);
-                    e2[s] = p2_reproj_error(w, tr, p.cam, x2 + j * 2);
+                    e2[s] = reproj_error(w, tr[0], tr[1], tr[2], x2[j * 2], x2[j * 2 + 1], p.cam);
 #pragma unroll
                     for (int k = 0; k < 3; ++k) y[s][k] = (double)w[k];
                 }
@@ -3956,7 +3977,7 @@ __global__ void __launch_bounds__(64 * P2_WAVES) procrustes_kernel(const Procrus
                 if (lane + 64 * s < J) p.pagg[btf * J + lane + 64 * s] = (float)err[s];
             continue;
         }
-        esum = p2_wave_sum(esum);
+        esum = wave_sum_f64(esum);
         if (lane == 0) p.pbest_sums[((((int64_t)b * p.T + t) * p.P) + h) * p.F + f] = esum;
 #pragma unroll
         for (int s = 0; s < P2_SLOTS; ++s) {
@@ -3977,8 +3998,7 @@ __global__ void __launch_bounds__(64 * P2_WAVES) procrustes_kernel(const Procrus
         for (int w = 0; w < P2_WAVES; ++w) {
             if (w > 0) m = (float)p2_min(m, w_min[w][tid]);
             const int32_t hw = w_h[w][tid];
-            // the overall first minimum: the smallest e2, the lowest h among equal ones
-            if (hw >= 0 && (hb < 0 || w_e2[w][tid] < b2 || (w_e2[w][tid] == b2 && hw < hb))) b2 = w_e2[w][tid], hb = hw, e = w_sel[w][tid];
+            if (candidate_wins(w_e2[w][tid], hw, b2, hb)) b2 = w_e2[w][tid], hb = hw, e = w_sel[w][tid];   // the overall first minimum
         }
         p.jbest[btf * J + tid] = m;
         p.jagg[btf * J + tid] = e;
@@ -3993,10 +4013,10 @@ __global__ void __launch_bounds__(64 * P2_WAVES) procrustes_kernel(const Procrus
 // needs work at combine time: one alignment of the mean pose, whose fp64 sums over h head every Protocol #1 state and
 // every pose state (double sum[n][3]) and are borrowed from there.
 //
-// State of a shard [h0, h0 + P_r), one flat 8-byte aligned buffer of 16*n + 8*T*P_r bytes, n = B*T*F*J:
+// State of a shard [h0, h0 + P_r), one flat 8-byte aligned buffer (P2StateViews) of 16*n + 8*T*P_r bytes, n = B*T*F*J:
 //   float jbest[n] | float e2[n] | float sel[n] | int32 idx[n] | double psum[P_r][T]
 // jbest: NaN-sticky minimum over the local h of the aligned error; (e2, idx, sel): smallest reprojection error
-// (p2_reproj_error), its GLOBAL index h0 + h, that hypothesis's aligned error, first minimum wins, (+inf, -1, 0) where
+// (reproj_error), its GLOBAL index h0 + h, that hypothesis's aligned error, first minimum wins, (+inf, -1, 0) where
 // none is finite; psum[h][t]: fp64 sum over (b, f) of the per-pose sums over j, in one fixed order - the same bits
 // however P is cut.
 //
@@ -4012,8 +4032,7 @@ struct ProcrustesPartialsParams {
     const float* traj;  // [B,F,3]
     const float* cam;   // [9]
     const int32_t* conn;   // [J]
-    float *jbest, *e2, *sel;   // state head (see above)
-    int32_t* idx;
+    P2StateViews st;    // state (see above); the kernel writes its head
     double* pose_sums;  // workspace [B,T,P_r,F]: sum over j of the aligned errors of every local pose
     int B, T, P, F, J, h0;
 };
@@ -4052,13 +4071,13 @@ __global__ void __launch_bounds__(64 * P2_WAVES) procrustes_partials_kernel(cons
             float w[3] = {0.f, 0.f, 0.f};
             if (j < J) {
                 wb_joint(pose0 + h * hstride, p.conn, j, w);
-                e2[s] = p2_reproj_error(w, tr, p.cam, x2 + j * 2);
+                e2[s] = reproj_error(w, tr[0], tr[1], tr[2], x2[j * 2], x2[j * 2 + 1], p.cam);
             }
 #pragma unroll
             for (int k = 0; k < 3; ++k) y[s][k] = (double)w[k];
         }
         double err[P2_SLOTS];
-        const double esum = p2_wave_sum(p2_align_pose(y, x0, nx, J, lane, err));
+        const double esum = wave_sum_f64(p2_align_pose(y, x0, nx, J, lane, err));
         if (lane == 0) p.pose_sums[((((int64_t)b * p.T + t) * p.P) + h) * p.F + f] = esum;
 #pragma unroll
         for (int s = 0; s < P2_SLOTS; ++s) {
@@ -4079,13 +4098,12 @@ __global__ void __launch_bounds__(64 * P2_WAVES) procrustes_partials_kernel(cons
         for (int w = 0; w < P2_WAVES; ++w) {
             if (w > 0) m = (float)p2_min(m, w_min[w][tid]);
             const int32_t hw = w_h[w][tid];
-            // the shard's first minimum: the smallest e2, the lowest h among equal ones
-            if (hw >= 0 && (hb < 0 || w_e2[w][tid] < b2 || (w_e2[w][tid] == b2 && hw < hb))) b2 = w_e2[w][tid], hb = hw, e = w_sel[w][tid];
+            if (candidate_wins(w_e2[w][tid], hw, b2, hb)) b2 = w_e2[w][tid], hb = hw, e = w_sel[w][tid];   // the shard's first minimum
         }
-        p.jbest[btf * J + tid] = m;
-        p.e2[btf * J + tid] = b2;
-        p.sel[btf * J + tid] = e;
-        p.idx[btf * J + tid] = hb;
+        p.st.jbest[btf * J + tid] = m;
+        p.st.e2[btf * J + tid] = b2;
+        p.st.sel[btf * J + tid] = e;
+        p.st.idx[btf * J + tid] = hb;
     }
 }
 
@@ -4107,7 +4125,7 @@ __global__ void __launch_bounds__(256) procrustes_psum_kernel(const ProcrustesPs
         const int b = i / p.F, f = i % p.F;
         a += p.pose_sums[((((int64_t)b * p.T + t) * p.P) + h) * p.F + f];
     }
-    a = p2_wave_sum(a);
+    a = wave_sum_f64(a);
     if ((tid & 63) == 0) s_w[tid >> 6] = a;
     __syncthreads();
     if (tid == 0) p.psum[(int64_t)h * p.T + t] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
@@ -4121,8 +4139,7 @@ struct ProcrustesCombineParams {
     int W;
     const float* gt;      // [B,F,J,3]  (read for pagg only)
     const int32_t* conn;  // [J]
-    float *m_jbest, *m_e2, *m_sel;   // merged head (null: not wanted); may be the first operand
-    int32_t* m_idx;
+    P2StateViews merged;             // merged head (jbest null: not wanted); may be the first operand
     float *jbest, *pagg, *jagg;      // [B,T,F,J] (null: not wanted)
     int32_t* pick;                   // [B,T,F,J] (null: not wanted)
     int B, T, F, J, P;    // P: the TOTAL hypothesis count the mean pose divides by
@@ -4151,22 +4168,17 @@ __global__ void __launch_bounds__(64 * P2C_WAVES) procrustes_combine_kernel(cons
         for (int k = 0; k < 3; ++k) y[s][k] = 0.0;
     }
     for (int w = 0; w < p.W; ++w) {
-        const float* jb = (const float*)(p.states + (int64_t)w * p.stride);
-        const float* e2 = jb + n;
-        const float* sl = e2 + n;
-        const int32_t* ix = (const int32_t*)(sl + n);
+        const P2StateViews st(p.states + (int64_t)w * p.stride, n);
         const double* sum = p.pagg ? (const double*)(p.sums + (int64_t)w * p.sums_stride) : nullptr;
 #pragma unroll
         for (int s = 0; s < P2_SLOTS; ++s) {
             const int j = lane + 64 * s;
             if (j < J) {
                 const int64_t e = btf * J + j;
-                m[s] = (float)p2_min(m[s], jb[e]);
-                const int32_t hw = ix[e];
-                const float ew = e2[e];
-                // the overall first minimum: the smallest e2, the lowest global index among equal ones
-                if (hw >= 0 && (hsel[s] < 0 || ew < best2[s] || (ew == best2[s] && hw < hsel[s])))
-                    best2[s] = ew, hsel[s] = hw, sel[s] = sl[e];
+                m[s] = (float)p2_min(m[s], st.jbest[e]);
+                const int32_t hw = st.idx[e];
+                const float ew = st.e2[e];
+                if (candidate_wins(ew, hw, best2[s], hsel[s])) best2[s] = ew, hsel[s] = hw, sel[s] = st.sel[e];   // the overall first minimum
                 if (sum) {
 #pragma unroll
                     for (int k = 0; k < 3; ++k) y[s][k] += sum[e * 3 + k];
@@ -4179,7 +4191,7 @@ __global__ void __launch_bounds__(64 * P2C_WAVES) procrustes_combine_kernel(cons
         const int j = lane + 64 * s;
         if (j < J) {
             const int64_t e = btf * J + j;
-            if (p.m_jbest) p.m_jbest[e] = m[s], p.m_e2[e] = best2[s], p.m_sel[e] = sel[s], p.m_idx[e] = hsel[s];
+            if (p.merged.jbest) p.merged.jbest[e] = m[s], p.merged.e2[e] = best2[s], p.merged.sel[e] = sel[s], p.merged.idx[e] = hsel[s];
             if (p.jbest) p.jbest[e] = m[s];
             if (p.jagg) p.jagg[e] = sel[s];
             if (p.pick) p.pick[e] = hsel[s];

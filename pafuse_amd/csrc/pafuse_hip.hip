@@ -1725,7 +1725,75 @@ int pafuse_hypothesis_errors(const float* pred, const float* gt, const float* x2
     return launch<metrics_kernel>("metrics_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, m);
 }
 
-// state of pafuse_hypothesis_partials: double sum[n][3] | float jbest[n], e2[n], sel3[n] | int32 idx[n] | double hsum[P_r][T][1+num_parts]
+// ---- what the partial-state entries below share (their layouts: the views structs of kernels.hpp) ----
+// the prologue of a partials entry: the state buffer holds the `need` bytes the entry writes, 8-byte aligned
+static int check_state(const char* who, const void* state, size_t state_bytes, size_t need) {
+    if (need && (!state || state_bytes < need)) return fail(PAFUSE_E_ARG, "%s: the state needs %zu bytes", who, need);
+    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "%s: the state must be 8-byte aligned", who);
+    return PAFUSE_OK;
+}
+
+// what of its operands the merged state of a combine may lie over
+enum class MergeOver { Unchecked, Nothing, First };
+
+// the prologue of a combine entry: W states of `head` bytes, `stride` bytes apart, every pointer 8-byte aligned; where the
+// merged state may lie; the grid
+static int check_combine(const char* who, const void* states, int32_t W, size_t stride, size_t head, const void* merged,
+                         MergeOver over, int64_t blocks) {
+    if (stride < head || stride % 8 || (uintptr_t)states % 8 || (uintptr_t)merged % 8)
+        return fail(PAFUSE_E_ARG, "%s: states are %zu bytes or more apart, 8-byte aligned", who, head);
+    const char *lo = (const char*)states, *mg = (const char*)merged;
+    if (merged && over == MergeOver::Nothing && mg < lo + (size_t)W * stride && mg + head > lo)
+        return fail(PAFUSE_E_ARG, "%s: a merge over its own operands cannot also write the maps", who);
+    if (merged && over == MergeOver::First && mg != lo && mg < lo + (size_t)(W - 1) * stride + head && mg + head > lo)
+        return fail(PAFUSE_E_ARG, "%s: of its operands the merged state may only lie over the first", who);
+    if (blocks > 0x7fffffff) return fail(PAFUSE_E_ARG, "%s: grid out of range", who);
+    return PAFUSE_OK;
+}
+
+// the neutral states (what an empty shard writes; no kernel runs): zero sums, +inf minima, no candidate
+static int neutral_state(const char* who, const PartialsStateViews& v, int64_t n, size_t hsum_bytes, hipStream_t s) {
+    hipError_t e = hipSuccess;
+    if (n) {
+        e = hipMemsetAsync(v.sum, 0, (size_t)n * 3 * sizeof(double), s);
+        if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)v.jbest, 0x7f800000, (size_t)n, s);
+        if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)v.e2, 0x7f800000, (size_t)n, s);
+        if (e == hipSuccess) e = hipMemsetAsync(v.sel3, 0, (size_t)n * 4, s);
+        if (e == hipSuccess) e = hipMemsetAsync(v.idx, 0xff, (size_t)n * 4, s);
+    }
+    if (e == hipSuccess && hsum_bytes) e = hipMemsetAsync(v.hsum, 0, hsum_bytes, s);
+    if (e != hipSuccess) return fail(PAFUSE_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    return PAFUSE_OK;
+}
+
+// (+inf, -1, NaN NaN NaN); Views: PoseStateViews or FramePoseViews, which name these four fields alike
+extern "C++" template <class Views>
+static int neutral_state(const char* who, const Views& v, int64_t n, hipStream_t s) {
+    hipError_t e = hipSuccess;
+    if (n) {
+        e = hipMemsetAsync(v.sum, 0, (size_t)n * 3 * sizeof(double), s);
+        if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)v.e2, 0x7f800000, (size_t)n, s);
+        if (e == hipSuccess) e = hipMemsetAsync(v.idx, 0xff, (size_t)n * 4, s);
+        if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)v.sel, 0x7fc00000, (size_t)n * 3, s);
+    }
+    if (e != hipSuccess) return fail(PAFUSE_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    return PAFUSE_OK;
+}
+
+// (+inf, -1, 0)
+static int neutral_state(const char* who, const P2StateViews& v, int64_t n, size_t psum_bytes, hipStream_t s) {
+    hipError_t e = hipSuccess;
+    if (n) {
+        e = hipMemsetD32Async((hipDeviceptr_t)v.jbest, 0x7f800000, (size_t)n, s);
+        if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)v.e2, 0x7f800000, (size_t)n, s);
+        if (e == hipSuccess) e = hipMemsetAsync(v.sel, 0, (size_t)n * 4, s);
+        if (e == hipSuccess) e = hipMemsetAsync(v.idx, 0xff, (size_t)n * 4, s);
+    }
+    if (e == hipSuccess && psum_bytes) e = hipMemsetAsync(v.psum, 0, psum_bytes, s);
+    if (e != hipSuccess) return fail(PAFUSE_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    return PAFUSE_OK;
+}
+
 static bool partials_sizes_ok(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t num_parts) {
     return B >= 0 && T > 0 && P_r >= 0 && F > 0 && J > 0 && num_parts >= 1 && num_parts <= PAFUSE_MAX_PARTS;
 }
@@ -1733,7 +1801,7 @@ static int partials_nblk(int32_t F, int32_t J) { return (int)(((int64_t)F * J + 
 
 size_t pafuse_hypothesis_partials_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t num_parts) {
     if (!partials_sizes_ok(B, T, P_r, F, J, num_parts)) return 0;
-    return (size_t)B * T * F * J * 40 + (size_t)P_r * T * (1 + num_parts) * 8;
+    return PartialsStateViews::head_bytes((int64_t)B * T * F * J) + (size_t)P_r * T * (1 + num_parts) * 8;
 }
 
 size_t pafuse_hypothesis_partials_workspace_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J, int32_t num_parts) {
@@ -1748,27 +1816,11 @@ int pafuse_hypothesis_partials(const float* pred, const float* gt, const float* 
     StreamDevice on_stream_device(stream);
     if (num_parts < 1 || num_parts > PAFUSE_MAX_PARTS) return fail(PAFUSE_E_SHAPE, "hypothesis_partials: num_parts %d", num_parts);
     if (B < 0 || T <= 0 || P_r < 0 || F <= 0 || J <= 0 || h0 < 0) return fail(PAFUSE_E_ARG, "hypothesis_partials: bad size");
-    const size_t need = pafuse_hypothesis_partials_bytes(B, T, P_r, F, J, num_parts);
-    if (need && (!state || state_bytes < need)) return fail(PAFUSE_E_ARG, "hypothesis_partials: the state needs %zu bytes", need);
-    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "hypothesis_partials: the state must be 8-byte aligned");
+    if (int rc = check_state("hypothesis_partials", state, state_bytes, pafuse_hypothesis_partials_bytes(B, T, P_r, F, J, num_parts))) return rc;
     const int64_t n = (int64_t)B * T * F * J;
-    char* st = (char*)state;
-    double* sum = (double*)st;
-    float* jbest = (float*)(st + n * 24);
-    double* hsum = (double*)(st + n * 40);
+    const PartialsStateViews v(state, n);
     hipStream_t s = (hipStream_t)stream;
-    if (B == 0 || P_r == 0) {   // the neutral state: +inf minima, no candidate, zero sums; no kernel runs
-        hipError_t e = hipSuccess;
-        if (n) {
-            e = hipMemsetAsync(sum, 0, (size_t)n * 24, s);
-            if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)jbest, 0x7f800000, (size_t)n * 2, s);
-            if (e == hipSuccess) e = hipMemsetAsync(jbest + 2 * n, 0, (size_t)n * 4, s);
-            if (e == hipSuccess) e = hipMemsetAsync(jbest + 3 * n, 0xff, (size_t)n * 4, s);
-        }
-        if (e == hipSuccess && P_r) e = hipMemsetAsync(hsum, 0, (size_t)P_r * T * (1 + num_parts) * 8, s);
-        if (e != hipSuccess) return fail(PAFUSE_E_HIP, "hypothesis_partials: %s", hipGetErrorString(e));
-        return PAFUSE_OK;
-    }
+    if (B == 0 || P_r == 0) return neutral_state("hypothesis_partials", v, n, (size_t)P_r * T * (1 + num_parts) * 8, s);
     if (!pred || !gt || !x2d || !traj || !cam || !conn || !pbroot || !part)
         return fail(PAFUSE_E_ARG, "hypothesis_partials: null pointer");
     const size_t wneed = pafuse_hypothesis_partials_workspace_bytes(B, T, P_r, F, J, num_parts);
@@ -1776,8 +1828,7 @@ int pafuse_hypothesis_partials(const float* pred, const float* gt, const float* 
         return fail(PAFUSE_E_WORKSPACE, "hypothesis_partials: the workspace needs %zu bytes, 8-byte aligned", wneed);
     PartialsParams m{};
     m.pred = pred, m.gt = gt, m.x2d = x2d, m.traj = traj, m.cam = cam, m.conn = conn, m.pbroot = pbroot, m.part = part;
-    m.sum = sum, m.jbest = jbest, m.e2 = jbest + n, m.sel3 = jbest + 2 * n, m.idx = (int32_t*)(jbest + 3 * n);
-    m.share = (double*)workspace;
+    m.st = v, m.share = (double*)workspace;
     m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0, m.nv = 1 + num_parts, m.nblk = partials_nblk(F, J);
     const int64_t blocks = (int64_t)B * T * m.nblk;
     if (blocks > 0x7fffffff || (int64_t)P_r * T > 0x7fffffff || (int64_t)B * m.nblk > 0x7fffffff)
@@ -1785,7 +1836,7 @@ int pafuse_hypothesis_partials(const float* pred, const float* gt, const float* 
     int rc = launch<partials_kernel>("partials_kernel", (unsigned)blocks, 256, 0, s, m);
     if (rc) return rc;
     PartialsHsumParams r{};
-    r.share = m.share, r.hsum = hsum, r.B = B, r.T = T, r.P = P_r, r.nv = m.nv, r.nblk = m.nblk;
+    r.share = m.share, r.hsum = v.hsum, r.B = B, r.T = T, r.P = P_r, r.nv = m.nv, r.nblk = m.nblk;
     return launch<partials_hsum_kernel>("partials_hsum_kernel", (unsigned)((int64_t)P_r * T), 256, 0, s, r);
 }
 
@@ -1801,20 +1852,11 @@ int pafuse_hypothesis_combine(const void* states, int32_t W, size_t stride_bytes
     const int64_t n = (int64_t)B * T * F * J;
     if (n == 0) return PAFUSE_OK;
     if (!states || !gt || !conn || !pbroot) return fail(PAFUSE_E_ARG, "hypothesis_combine: null pointer");
-    if (stride_bytes < (size_t)n * 40 || stride_bytes % 8 || (uintptr_t)states % 8 || (uintptr_t)merged % 8)
-        return fail(PAFUSE_E_ARG, "hypothesis_combine: states are %lld bytes or more apart, 8-byte aligned", (long long)(n * 40));
-    const char* lo = (const char*)states;
-    const char* hi = lo + (size_t)W * stride_bytes;
-    if (maps && merged && (const char*)merged < hi && (const char*)merged + n * 40 > lo)
-        return fail(PAFUSE_E_ARG, "hypothesis_combine: a merge over its own operands cannot also write the maps");
-    if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "hypothesis_combine: grid out of range");
+    if (int rc = check_combine("hypothesis_combine", states, W, stride_bytes, PartialsStateViews::head_bytes(n), merged,
+                               maps ? MergeOver::Nothing : MergeOver::Unchecked, (n + 255) / 256)) return rc;
     CombineParams c{};
-    c.states = lo, c.stride = (int64_t)stride_bytes, c.W = W, c.gt = gt, c.conn = conn, c.pbroot = pbroot;
-    if (merged) {
-        char* st = (char*)merged;
-        c.m_sum = (double*)st, c.m_jbest = (float*)(st + n * 24), c.m_e2 = c.m_jbest + n, c.m_sel3 = c.m_jbest + 2 * n;
-        c.m_idx = (int32_t*)(c.m_jbest + 3 * n);
-    }
+    c.states = (const char*)states, c.stride = (int64_t)stride_bytes, c.W = W, c.gt = gt, c.conn = conn, c.pbroot = pbroot;
+    if (merged) c.merged = PartialsStateViews(merged, n);
     c.jbest = jbest, c.pagg = pagg, c.jagg = jagg, c.paggpb = paggpb;
     c.B = B, c.T = T, c.F = F, c.J = J, c.P = P_total;
     return launch<combine_kernel>("combine_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, c);
@@ -1823,20 +1865,7 @@ int pafuse_hypothesis_combine(const void* states, int32_t W, size_t stride_bytes
 // state of pafuse_pose_partials: double sum[n][3] | float e2[n] | int32 idx[n] | float sel[n][3], rounded up to 8 bytes
 size_t pafuse_pose_partials_bytes(int32_t B, int32_t T, int32_t F, int32_t J) {
     if (B < 0 || T <= 0 || F <= 0 || J <= 0) return 0;
-    return ((size_t)B * T * F * J * 44 + 7) / 8 * 8;
-}
-
-// the neutral pose state: zero sums, no candidate (+inf, -1, NaN NaN NaN)
-static int pose_neutral_state(const char* who, double* sum, float* e2, int32_t* idx, float* sel, int64_t n, hipStream_t s) {
-    hipError_t e = hipSuccess;
-    if (n) {
-        e = hipMemsetAsync(sum, 0, (size_t)n * 24, s);
-        if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)e2, 0x7f800000, (size_t)n, s);
-        if (e == hipSuccess) e = hipMemsetAsync(idx, 0xff, (size_t)n * 4, s);
-        if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)sel, 0x7fc00000, (size_t)n * 3, s);
-    }
-    if (e != hipSuccess) return fail(PAFUSE_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    return PAFUSE_OK;
+    return PoseStateViews::bytes((int64_t)B * T * F * J);
 }
 
 int pafuse_pose_partials(const float* pred, const float* x2d, const float* traj, const float* cam, const int32_t* conn,
@@ -1847,22 +1876,15 @@ int pafuse_pose_partials(const float* pred, const float* x2d, const float* traj,
     const int given = (x2d ? 1 : 0) + (traj ? 1 : 0) + (cam ? 1 : 0);
     if (given != 0 && given != 3)
         return fail(PAFUSE_E_ARG, "pose_partials: x2d, traj and cam come together (all null: mean-only)");
-    const size_t need = pafuse_pose_partials_bytes(B, T, F, J);
-    if (need && (!state || state_bytes < need)) return fail(PAFUSE_E_ARG, "pose_partials: the state needs %zu bytes", need);
-    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "pose_partials: the state must be 8-byte aligned");
+    if (int rc = check_state("pose_partials", state, state_bytes, pafuse_pose_partials_bytes(B, T, F, J))) return rc;
     const int64_t n = (int64_t)B * T * F * J;
-    char* st = (char*)state;
-    double* sum = (double*)st;
-    float* e2 = (float*)(st + n * 24);
-    int32_t* idx = (int32_t*)(e2 + n);
-    float* sel = (float*)(idx + n);
+    const PoseStateViews v(state, n);
     hipStream_t s = (hipStream_t)stream;
-    if (B == 0 || P_r == 0) return pose_neutral_state("pose_partials", sum, e2, idx, sel, n, s);   // no kernel runs
+    if (B == 0 || P_r == 0) return neutral_state("pose_partials", v, n, s);   // no kernel runs
     if (!pred || !conn) return fail(PAFUSE_E_ARG, "pose_partials: null pointer");
     if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "pose_partials: grid out of range");
     PosePartialsParams m{};
-    m.pred = pred, m.x2d = x2d, m.traj = traj, m.cam = cam, m.conn = conn;
-    m.sum = sum, m.e2 = e2, m.idx = idx, m.sel = sel;
+    m.pred = pred, m.x2d = x2d, m.traj = traj, m.cam = cam, m.conn = conn, m.st = v;
     m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0;
     return launch<pose_partials_kernel>("pose_partials_kernel", blocks_for(n), 256, 0, s, m);
 }
@@ -1875,23 +1897,16 @@ int pafuse_pose_partials_fit(const float* pred, const float* x2d, const float* c
     StreamDevice on_stream_device(stream);
     if (B < 0 || T <= 0 || P_r < 0 || F <= 0 || J <= 0 || h0 < 0) return fail(PAFUSE_E_ARG, "pose_partials_fit: bad size");
     if (!x2d || !cam) return fail(PAFUSE_E_ARG, "pose_partials_fit: x2d and cam are needed (conf may be null: every weight 1)");
-    const size_t need = pafuse_pose_partials_bytes(B, T, F, J);
-    if (need && (!state || state_bytes < need)) return fail(PAFUSE_E_ARG, "pose_partials_fit: the state needs %zu bytes", need);
-    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "pose_partials_fit: the state must be 8-byte aligned");
+    if (int rc = check_state("pose_partials_fit", state, state_bytes, pafuse_pose_partials_bytes(B, T, F, J))) return rc;
     const int64_t n = (int64_t)B * T * F * J;
-    char* st = (char*)state;
-    double* sum = (double*)st;
-    float* e2 = (float*)(st + n * 24);
-    int32_t* idx = (int32_t*)(e2 + n);
-    float* sel = (float*)(idx + n);
+    const PoseStateViews v(state, n);
     hipStream_t s = (hipStream_t)stream;
-    if (B == 0 || P_r == 0) return pose_neutral_state("pose_partials_fit", sum, e2, idx, sel, n, s);   // no kernel runs, tfit is empty
+    if (B == 0 || P_r == 0) return neutral_state("pose_partials_fit", v, n, s);   // no kernel runs, tfit is empty
     if (!pred || !conn) return fail(PAFUSE_E_ARG, "pose_partials_fit: null pointer");
     const int64_t waves = (int64_t)B * T * F;   // one wave per (b, t, f), four per workgroup
     if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "pose_partials_fit: grid out of range");
     PoseFitParams m{};
-    m.pred = pred, m.x2d = x2d, m.conf = conf, m.cam = cam, m.conn = conn;
-    m.sum = sum, m.e2 = e2, m.idx = idx, m.sel = sel, m.tfit = tfit;
+    m.pred = pred, m.x2d = x2d, m.conf = conf, m.cam = cam, m.conn = conn, m.st = v, m.tfit = tfit;
     m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0;
     return launch<pose_fit_partials_kernel>("pose_fit_partials_kernel", blocks_for(waves, 4), 256, 0, s, m);
 }
@@ -1905,19 +1920,11 @@ int pafuse_pose_combine(const void* states, int32_t W, size_t stride_bytes, int3
     const int64_t n = (int64_t)B * T * F * J;
     if (n == 0) return PAFUSE_OK;
     if (!states) return fail(PAFUSE_E_ARG, "pose_combine: null pointer");
-    if (stride_bytes < (size_t)n * 44 || stride_bytes % 8 || (uintptr_t)states % 8 || (uintptr_t)merged % 8)
-        return fail(PAFUSE_E_ARG, "pose_combine: states are %lld bytes or more apart, 8-byte aligned", (long long)(n * 44));
-    const char* lo = (const char*)states;
-    const char* hi = lo + (size_t)(W - 1) * stride_bytes + n * 44;
-    if (merged && merged != states && (const char*)merged < hi && (const char*)merged + n * 44 > lo)
-        return fail(PAFUSE_E_ARG, "pose_combine: of its operands the merged state may only lie over the first");
-    if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "pose_combine: grid out of range");
+    if (int rc = check_combine("pose_combine", states, W, stride_bytes, PoseStateViews::head_bytes(n), merged, MergeOver::First,
+                               (n + 255) / 256)) return rc;
     PoseCombineParams c{};
-    c.states = lo, c.stride = (int64_t)stride_bytes, c.W = W;
-    if (merged) {
-        char* st = (char*)merged;
-        c.m_sum = (double*)st, c.m_e2 = (float*)(st + n * 24), c.m_idx = (int32_t*)(c.m_e2 + n), c.m_sel = (float*)(c.m_idx + n);
-    }
+    c.states = (const char*)states, c.stride = (int64_t)stride_bytes, c.W = W;
+    if (merged) c.merged = PoseStateViews(merged, n);
     c.mean = mean, c.pick = pick, c.pick_idx = pick_idx, c.n = n, c.P = P_total;
     return launch<pose_combine_kernel>("pose_combine_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, c);
 }
@@ -1933,8 +1940,7 @@ int pafuse_spread_partials(const float* pred, const int32_t* conn, int32_t B, in
     StreamDevice on_stream_device(stream);
     if (B < 0 || T <= 0 || P_r < 0 || F <= 0 || J <= 0 || h0 < 0) return fail(PAFUSE_E_ARG, "spread_partials: bad size");
     const size_t need = pafuse_spread_partials_bytes(B, T, F, J);
-    if (need && (!state || state_bytes < need)) return fail(PAFUSE_E_ARG, "spread_partials: the state needs %zu bytes", need);
-    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "spread_partials: the state must be 8-byte aligned");
+    if (int rc = check_state("spread_partials", state, state_bytes, need)) return rc;
     const int64_t n = (int64_t)B * T * F * J;
     if (n == 0) return PAFUSE_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -1961,13 +1967,8 @@ int pafuse_spread_combine(const void* states, int32_t W, size_t stride_bytes, in
     if (n == 0) return PAFUSE_OK;
     if (!states) return fail(PAFUSE_E_ARG, "spread_combine: null pointer");
     const size_t need = pafuse_spread_partials_bytes(B, T, F, J);
-    if (stride_bytes < need || stride_bytes % 8 || (uintptr_t)states % 8 || (uintptr_t)merged % 8)
-        return fail(PAFUSE_E_ARG, "spread_combine: states are %zu bytes or more apart, 8-byte aligned", need);
+    if (int rc = check_combine("spread_combine", states, W, stride_bytes, need, merged, MergeOver::First, (n + 255) / 256)) return rc;
     const char* lo = (const char*)states;
-    const char* hi = lo + (size_t)(W - 1) * stride_bytes + need;
-    if (merged && merged != states && (const char*)merged < hi && (const char*)merged + need > lo)
-        return fail(PAFUSE_E_ARG, "spread_combine: of its operands the merged state may only lie over the first");
-    if ((n + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "spread_combine: grid out of range");
     SpreadCombineParams c{};
     c.states = lo, c.stride = (int64_t)stride_bytes, c.W = W, c.merged = (double*)merged;
     c.mean = mean, c.cov = cov, c.sd = std_dev, c.n = n;
@@ -1980,7 +1981,7 @@ int pafuse_spread_combine(const void* states, int32_t W, size_t stride_bytes, in
 // frame pose state: double sum[r][3] | float e2[r] | int32 idx[r] | int32 win[r] | float sel[r][3] | int32 count[N], r = T*N*J
 size_t pafuse_frame_pose_state_bytes(int32_t N, int32_t T, int32_t J) {
     if (N <= 0 || T <= 0 || J <= 0) return 0;
-    return ((size_t)N * T * J * 48 + (size_t)N * 4 + 7) / 8 * 8;
+    return FramePoseViews::bytes((int64_t)N * T * J, N);
 }
 
 // frame spread state: double sum[r][3] | double m2[r][6] | double count[N]
@@ -1990,15 +1991,6 @@ size_t pafuse_frame_spread_state_bytes(int32_t N, int32_t T, int32_t J) {
 }
 
 namespace {
-struct FramePoseViews {
-    double* sum; float* e2; int32_t* idx; int32_t* win; float* sel; int32_t* count;
-    FramePoseViews(void* state, int64_t rows) {
-        char* st = (char*)state;
-        sum = (double*)st, e2 = (float*)(st + rows * 24), idx = (int32_t*)(e2 + rows), win = idx + rows;
-        sel = (float*)(win + rows), count = (int32_t*)(sel + 3 * rows);
-    }
-};
-
 // what both folds check of their window tables (the HOST copies) before anything is launched; -> the frame range touched
 int check_windows(const char* who, const int32_t* starts, const int32_t* valid, int32_t B, int32_t F, int32_t N, int* n_lo, int* n_hi) {
     int hi = 0;
@@ -2019,12 +2011,11 @@ int pafuse_frame_pose_state_init(void* frame_state, size_t frame_bytes, int32_t 
     if (N < 0 || T <= 0 || J <= 0) return fail(PAFUSE_E_ARG, "frame_pose_state_init: bad size");
     const size_t need = pafuse_frame_pose_state_bytes(N, T, J);
     if (need == 0) return PAFUSE_OK;
-    if (!frame_state || frame_bytes < need) return fail(PAFUSE_E_ARG, "frame_pose_state_init: the state needs %zu bytes", need);
-    if ((uintptr_t)frame_state % 8) return fail(PAFUSE_E_ARG, "frame_pose_state_init: the state must be 8-byte aligned");
+    if (int rc = check_state("frame_pose_state_init", frame_state, frame_bytes, need)) return rc;
     const int64_t rows = (int64_t)N * T * J;
     FramePoseViews v(frame_state, rows);
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = pose_neutral_state("frame_pose_state_init", v.sum, v.e2, v.idx, v.sel, rows, s)) return rc;
+    if (int rc = neutral_state("frame_pose_state_init", v, rows, s)) return rc;
     hipError_t e = hipMemsetAsync(v.win, 0xff, (size_t)rows * 4, s);
     if (e == hipSuccess) e = hipMemsetAsync(v.count, 0, (size_t)N * 4, s);
     if (e != hipSuccess) return fail(PAFUSE_E_HIP, "frame_pose_state_init: %s", hipGetErrorString(e));
@@ -2036,8 +2027,7 @@ int pafuse_frame_spread_state_init(void* frame_state, size_t frame_bytes, int32_
     if (N < 0 || T <= 0 || J <= 0) return fail(PAFUSE_E_ARG, "frame_spread_state_init: bad size");
     const size_t need = pafuse_frame_spread_state_bytes(N, T, J);
     if (need == 0) return PAFUSE_OK;
-    if (!frame_state || frame_bytes < need) return fail(PAFUSE_E_ARG, "frame_spread_state_init: the state needs %zu bytes", need);
-    if ((uintptr_t)frame_state % 8) return fail(PAFUSE_E_ARG, "frame_spread_state_init: the state must be 8-byte aligned");
+    if (int rc = check_state("frame_spread_state_init", frame_state, frame_bytes, need)) return rc;
     hipError_t e = hipMemsetAsync(frame_state, 0, need, (hipStream_t)stream);
     if (e != hipSuccess) return fail(PAFUSE_E_HIP, "frame_spread_state_init: %s", hipGetErrorString(e));
     return PAFUSE_OK;
@@ -2059,12 +2049,8 @@ int pafuse_pose_windows_fold(void* frame_state, size_t frame_bytes, int32_t N, c
     if (int rc = check_windows("pose_windows_fold", starts_host, valid_host, B, F, N, &n_lo, &n_hi)) return rc;
     const int64_t rows = (int64_t)N * T * J, sn = (int64_t)B * T * F * J, work = (int64_t)T * (n_hi - n_lo) * J;
     if ((work + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "pose_windows_fold: grid out of range");
-    FramePoseViews v(frame_state, rows);
     PoseWindowsFoldParams m{};
-    m.f_sum = v.sum, m.f_e2 = v.e2, m.f_idx = v.idx, m.f_win = v.win, m.f_sel = v.sel, m.f_count = v.count;
-    const char* st = (const char*)state;
-    m.s_sum = (const double*)st, m.s_e2 = (const float*)(st + sn * 24), m.s_idx = (const int32_t*)(m.s_e2 + sn);
-    m.s_sel = (const float*)(m.s_idx + sn);
+    m.frame = FramePoseViews(frame_state, rows), m.state = PoseStateViews(state, sn);
     m.starts = starts, m.valid = valid;
     m.N = N, m.B = B, m.T = T, m.F = F, m.J = J, m.w0 = w0, m.P = P_total, m.n_lo = n_lo, m.n_hi = n_hi;
     return launch<pose_windows_fold_kernel>("pose_windows_fold_kernel", blocks_for(work), 256, 0, (hipStream_t)stream, m);
@@ -2106,10 +2092,7 @@ int pafuse_frames_finish(const void* frame_state, const void* frame_spread, int3
     const int64_t rows = (int64_t)N * T * J;
     if ((rows + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "frames_finish: grid out of range");
     FramesFinishParams m{};
-    if (pose) {
-        FramePoseViews v((void*)frame_state, rows);
-        m.f_sum = v.sum, m.f_idx = v.idx, m.f_win = v.win, m.f_sel = v.sel, m.f_count = v.count;
-    }
+    if (pose) m.frame = FramePoseViews(frame_state, rows);
     m.spread = spread ? (const double*)frame_spread : nullptr;
     m.mean = mean, m.pick = pick, m.pick_idx = pick_idx, m.pick_win = pick_win, m.sd = std_dev, m.cov = cov;
     m.N = N, m.T = T, m.J = J;
@@ -2178,7 +2161,7 @@ static bool p2_partials_sizes_ok(int32_t B, int32_t T, int32_t P_r, int32_t F, i
 
 size_t pafuse_procrustes_partials_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J) {
     if (!p2_partials_sizes_ok(B, T, P_r, F, J)) return 0;
-    return (size_t)B * T * F * J * 16 + (size_t)P_r * T * 8;
+    return P2StateViews::head_bytes((int64_t)B * T * F * J) + (size_t)P_r * T * 8;
 }
 
 size_t pafuse_procrustes_partials_workspace_bytes(int32_t B, int32_t T, int32_t P_r, int32_t F, int32_t J) {
@@ -2192,25 +2175,11 @@ int pafuse_procrustes_partials(const float* pred, const float* gt, const float* 
     StreamDevice on_stream_device(stream);
     if (B < 0 || T <= 0 || P_r < 0 || F <= 0 || J <= 0 || h0 < 0) return fail(PAFUSE_E_ARG, "procrustes_partials: bad size");
     if (J > P2_MAX_J) return fail(PAFUSE_E_SHAPE, "procrustes_partials: J = %d above the supported %d", J, P2_MAX_J);
-    const size_t need = pafuse_procrustes_partials_bytes(B, T, P_r, F, J);
-    if (need && (!state || state_bytes < need)) return fail(PAFUSE_E_ARG, "procrustes_partials: the state needs %zu bytes", need);
-    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "procrustes_partials: the state must be 8-byte aligned");
+    if (int rc = check_state("procrustes_partials", state, state_bytes, pafuse_procrustes_partials_bytes(B, T, P_r, F, J))) return rc;
     const int64_t n = (int64_t)B * T * F * J;
-    char* st = (char*)state;
-    float* jbest = (float*)st;
-    double* psum = (double*)(st + n * 16);
+    const P2StateViews v(state, n);
     hipStream_t s = (hipStream_t)stream;
-    if (B == 0 || P_r == 0) {   // the neutral state: +inf minima, no candidate (+inf, -1, 0), zero sums; no kernel runs
-        hipError_t e = hipSuccess;
-        if (n) {
-            e = hipMemsetD32Async((hipDeviceptr_t)jbest, 0x7f800000, (size_t)n * 2, s);
-            if (e == hipSuccess) e = hipMemsetAsync(jbest + 2 * n, 0, (size_t)n * 4, s);
-            if (e == hipSuccess) e = hipMemsetAsync(jbest + 3 * n, 0xff, (size_t)n * 4, s);
-        }
-        if (e == hipSuccess && P_r) e = hipMemsetAsync(psum, 0, (size_t)P_r * T * 8, s);
-        if (e != hipSuccess) return fail(PAFUSE_E_HIP, "procrustes_partials: %s", hipGetErrorString(e));
-        return PAFUSE_OK;
-    }
+    if (B == 0 || P_r == 0) return neutral_state("procrustes_partials", v, n, (size_t)P_r * T * 8, s);   // no kernel runs
     if (!pred || !gt || !x2d || !traj || !cam || !conn) return fail(PAFUSE_E_ARG, "procrustes_partials: null pointer");
     const size_t wneed = pafuse_procrustes_partials_workspace_bytes(B, T, P_r, F, J);
     if (!workspace || workspace_bytes < wneed || (uintptr_t)workspace % 8)
@@ -2220,13 +2189,12 @@ int pafuse_procrustes_partials(const float* pred, const float* gt, const float* 
         return fail(PAFUSE_E_ARG, "procrustes_partials: grid out of range");
     ProcrustesPartialsParams m{};
     m.pred = pred, m.gt = gt, m.x2d = x2d, m.traj = traj, m.cam = cam, m.conn = conn;
-    m.jbest = jbest, m.e2 = jbest + n, m.sel = jbest + 2 * n, m.idx = (int32_t*)(jbest + 3 * n);
-    m.pose_sums = (double*)workspace;
+    m.st = v, m.pose_sums = (double*)workspace;
     m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0;
     int rc = launch<procrustes_partials_kernel>("procrustes_partials_kernel", (unsigned)blocks, 64 * P2_WAVES, 0, s, m);
     if (rc) return rc;
     ProcrustesPsumParams r{};
-    r.pose_sums = m.pose_sums, r.psum = psum, r.B = B, r.T = T, r.P = P_r, r.F = F;
+    r.pose_sums = m.pose_sums, r.psum = v.psum, r.B = B, r.T = T, r.P = P_r, r.F = F;
     return launch<procrustes_psum_kernel>("procrustes_psum_kernel", (unsigned)((int64_t)P_r * T), 256, 0, s, r);
 }
 
@@ -2243,29 +2211,20 @@ int pafuse_procrustes_combine(const void* states, int32_t W, size_t stride_bytes
     const int64_t n = (int64_t)B * T * F * J;
     if (n == 0) return PAFUSE_OK;
     if (!states || (pagg && (!gt || !conn))) return fail(PAFUSE_E_ARG, "procrustes_combine: null pointer");
-    if (stride_bytes < (size_t)n * 16 || stride_bytes % 8 || (uintptr_t)states % 8 || (uintptr_t)merged % 8)
-        return fail(PAFUSE_E_ARG, "procrustes_combine: states are %lld bytes or more apart, 8-byte aligned", (long long)(n * 16));
-    if (pagg && (sums_stride_bytes < (size_t)n * 24 || sums_stride_bytes % 8 || (uintptr_t)sums % 8))
-        return fail(PAFUSE_E_ARG, "procrustes_combine: sums are %lld bytes or more apart, 8-byte aligned", (long long)(n * 24));
-    const char* lo = (const char*)states;
-    const char* hi = lo + (size_t)(W - 1) * stride_bytes + n * 16;
-    const char* mg = (const char*)merged;
-    if (merged && merged != states && mg < hi && mg + n * 16 > lo)
-        return fail(PAFUSE_E_ARG, "procrustes_combine: of its operands the merged state may only lie over the first");
+    const int64_t blocks = ((int64_t)B * T * F + P2C_WAVES - 1) / P2C_WAVES;
+    const size_t head = P2StateViews::head_bytes(n), sums_bytes = (size_t)n * 3 * sizeof(double);   // double sum[n][3] heads every row of sums
+    if (int rc = check_combine("procrustes_combine", states, W, stride_bytes, head, merged, MergeOver::First, blocks)) return rc;
+    if (pagg && (sums_stride_bytes < sums_bytes || sums_stride_bytes % 8 || (uintptr_t)sums % 8))
+        return fail(PAFUSE_E_ARG, "procrustes_combine: sums are %zu bytes or more apart, 8-byte aligned", sums_bytes);
     if (merged && pagg) {
-        const char* slo = (const char*)sums;
-        const char* shi = slo + (size_t)(W - 1) * sums_stride_bytes + n * 24;
-        if (mg < shi && mg + n * 16 > slo) return fail(PAFUSE_E_ARG, "procrustes_combine: the merged state lies over the sums");
+        const char *mg = (const char*)merged, *slo = (const char*)sums;
+        const char* shi = slo + (size_t)(W - 1) * sums_stride_bytes + sums_bytes;
+        if (mg < shi && mg + head > slo) return fail(PAFUSE_E_ARG, "procrustes_combine: the merged state lies over the sums");
     }
-    const int64_t nbtf = (int64_t)B * T * F;
-    const int64_t blocks = (nbtf + P2C_WAVES - 1) / P2C_WAVES;
-    if (blocks > 0x7fffffff) return fail(PAFUSE_E_ARG, "procrustes_combine: grid out of range");
     ProcrustesCombineParams c{};
-    c.states = lo, c.stride = (int64_t)stride_bytes, c.W = W, c.gt = gt, c.conn = conn;
+    c.states = (const char*)states, c.stride = (int64_t)stride_bytes, c.W = W, c.gt = gt, c.conn = conn;
     c.sums = pagg ? (const char*)sums : nullptr, c.sums_stride = (int64_t)sums_stride_bytes;
-    if (merged) {
-        c.m_jbest = (float*)merged, c.m_e2 = c.m_jbest + n, c.m_sel = c.m_jbest + 2 * n, c.m_idx = (int32_t*)(c.m_jbest + 3 * n);
-    }
+    if (merged) c.merged = P2StateViews(merged, n);
     c.jbest = jbest, c.pagg = pagg, c.jagg = jagg, c.pick = pick;
     c.B = B, c.T = T, c.F = F, c.J = J, c.P = P_total;
     return launch<procrustes_combine_kernel>("procrustes_combine_kernel", (unsigned)blocks, 64 * P2C_WAVES, 0, (hipStream_t)stream, c);

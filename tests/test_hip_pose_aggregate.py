@@ -247,6 +247,62 @@ def test_torch_op_is_the_ops_pair(big):
     assert "Tensor? x2d=None, Tensor? traj=None, Tensor? cam=None" in s and s.endswith("-> Tensor[]")
 
 
+def test_every_picking_kernel_agrees_on_one_hostile_input():
+    """One input (tools/eval_bits.hostile_inputs: an exact tie across the shard border, Z = 0, a projection that clamps in
+    every hypothesis, a NaN detection) through the six paths that form the J-Agg index; they all call reproj_error and
+    candidate_wins, so the indices are torch.equal.  B=1, T=2, P=6 cut 4+2, F=2, J=134: F*J = 268 > 256 (partials_kernel runs
+    two blocks per (b, t)), 128 < J <= 256 (three rounds in the wave kernels, within Protocol #2's limit)."""
+    from pafuse_amd import ops
+    from tests.test_hip_partials import unsharded
+    from tools.eval_bits import HOSTILE, hostile_inputs
+    z = hostile_inputs(DEV)
+    pred, gt, x2d, traj, cam = (z[k] for k in ("pred", "gt", "x2d", "traj", "cam"))
+    (B, T, P, F), sizes = HOSTILE["shape"], HOSTILE["cut"]
+    shape, cuts = (B, T, F, J), cuts_of(P, sizes)
+    conn, pbroot, part = tables()
+    shard = lambda lo, hi: pred[:, :, lo:hi].contiguous()
+    picks = {"procrustes_errors": ops.procrustes_errors(pred, gt, x2d, traj, cam, conn, pick=True)["pick"],
+             "pose_partials": aggregate(z, sizes, want=("idx",))["idx"]}
+    p1 = torch.zeros(len(cuts), ops.partials_bytes(B, T, max(sizes), F, J, 4) // 8, device=DEV, dtype=torch.float64)
+    p2 = torch.zeros(len(cuts), ops.procrustes_partials_bytes(B, T, max(sizes), F, J) // 8, device=DEV, dtype=torch.float64)
+    fit = torch.zeros(len(cuts), ops.pose_partials_bytes(B, T, F, J) // 8, device=DEV, dtype=torch.float64)
+    ones, tfit = torch.ones(B, F, J, device=DEV), []
+    for r, (lo, hi) in enumerate(cuts):
+        ops.hypothesis_partials(shard(lo, hi), gt, x2d, traj, cam, conn, pbroot, part, 4, lo, out=p1[r])
+        ops.procrustes_partials(shard(lo, hi), gt, x2d, traj, cam, conn, lo, out=p2[r])
+        tfit.append(torch.full((B, T, hi - lo, F, 3), 7.0, device=DEV))
+        ops.pose_partials_fit(shard(lo, hi), conn, lo, x2d, cam, conf=ones, out=fit[r], tfit=tfit[-1])
+    merged = torch.empty(5 * B * T * F * J, device=DEV, dtype=torch.float64)
+    ops.combine_partials(p1, gt, conn, pbroot, shape, P, merged=merged, maps=False)
+    picks["hypothesis_partials"] = ops.partials_views(merged, B, T, 0, F, J, 4)["idx"]
+    picks["procrustes_partials"] = ops.combine_procrustes(p2, shape, P, want=("pick",))["pick"]
+    want = picks["procrustes_errors"]
+    for k, got in picks.items():
+        assert got.dtype == torch.int32 and torch.equal(got, want), k
+    # what was planted is there: the tie goes to the lower hypothesis, equal clamped errors to the first, NaN to nobody
+    (lo, hi), (f, j) = HOSTILE["tie"], HOSTILE["nan"]
+    assert (want == lo).any() and not (want == hi).any() and (want[..., HOSTILE["clamped"]] == 0).all()
+    assert (want[:, :, f, j] == -1).all() and int((want < 0).sum()) == B * T
+    # pafuse_hypothesis_errors keeps no index: its jagg is its e3 at that pick (0 where there is none)
+    old, valid = unsharded(pred, gt, x2d, traj, cam), want >= 0
+    at_pick = old["e3"].gather(2, want.clamp(min=0).long().unsqueeze(2)).squeeze(2)
+    assert torch.equal(at_pick[valid], old["jagg"][valid]) and (old["jagg"][~valid] == 0).all()
+    # pose_partials_fit: the pick of pose_partials_kernel on the roots it fitted, one hypothesis at a time
+    tfit = torch.cat(tfit, dim=2)
+    got = ops.combine_poses(fit, shape, P, want=("idx",), no_pick_ok=True)["idx"]
+    x2d_bt = x2d[:, None].expand(B, T, F, J, 2).reshape(B * T, F, J, 2).contiguous()
+    best = torch.full(shape, float("inf"), device=DEV)
+    idx = torch.full(shape, -1, device=DEV, dtype=torch.int32)
+    for h in range(P):
+        one = pred[:, :, h].reshape(B * T, 1, 1, F, J, 3).contiguous()
+        s = ops.pose_views(ops.pose_partials(one, conn, h, x2d_bt, tfit[:, :, h].reshape(B * T, F, 3).contiguous(), cam), B * T, 1, F, J)
+        fitted = ~torch.isnan(tfit[:, :, h]).any(dim=-1)
+        better = (s["e2"].view(shape) < best) & fitted[..., None]       # strict: the first minimum wins
+        best, idx = torch.where(better, s["e2"].view(shape), best), torch.where(better, s["idx"].view(shape), idx)
+    assert torch.equal(got, idx)
+    assert (got[:, :, 1 - f] >= 0).all() and (got[:, :, f] == -1).all() and not (got == hi).any()    # the NaN detection leaves frame f without a fit
+
+
 # ---------------------------------------------------------------------------------------------------- end to end
 SEED, FRAMES = 3, 30
 
