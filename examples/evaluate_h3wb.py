@@ -9,6 +9,8 @@ flip-TTA DDIM sampling on the HIP path -> J-Best / P-Best / P-Agg / J-Agg and th
 
 `ft2d.p2=True` adds Protocol #2 (P-MPJPE after similarity alignment) to the log, as in the reference.
 Trailing `a.b=c` arguments override the config tree like the reference's Hydra command line (pafuse_amd/config.py).
+`--frames` scores one pose per video frame instead (`--aggregate`, `--stride`, `--trajectory [R]`, `--seam-profile`): position,
+velocity, acceleration, root and part-based errors of the per-frame output (harness.evaluate_frames).
 Without `--data` the synthetic H3WB files of tests/golden/h3wb_synth are used (random weights: numbers are meaningless).
 """
 import argparse
@@ -40,6 +42,15 @@ def main():
                     help="where the loop's normals come from: torch.randn on the full tensor, or the library's counter-based "
                          "stream drawn inside the kernels (no noise tensor; other hypotheses than torch.randn's)")
     ap.add_argument("--seed", type=int, default=0, help="with --noise device: the seed of the stream, in [0, 2^32)")
+    ap.add_argument("--frames", action="store_true",
+                    help="score at the level of video frames instead: one pose per frame (--aggregate, --stride) against the ground "
+                         "truth - position, velocity, acceleration and part-based errors (harness.evaluate_frames)")
+    ap.add_argument("--aggregate", choices=("mean", "reproj", "reproj_fit"), default="mean", help="with --frames: the pose of a frame")
+    ap.add_argument("--stride", type=int, default=None,
+                    help="with --frames: slide the window with this stride and pool overlapping windows (default: clips end to end)")
+    ap.add_argument("--trajectory", nargs="?", type=int, const=0, default=None, metavar="R",
+                    help="with --frames: also fit the camera-space root and score it; R (1 .. 64) smooths it along the frames")
+    ap.add_argument("--seam-profile", action="store_true", help="with --frames: the position error by the frame's position in the clip")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
     args = config.load(a.config or None, a.overrides)
@@ -71,9 +82,14 @@ def main():
     torch.manual_seed(0)            # every rank draws the same full-P noise and keeps its hypothesis slice
     log = print if int(os.environ.get("RANK", "0")) == 0 else (lambda *x: None)
     log("Test time augmentation:", args.model.test_time_augmentation)
-    h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
-                  batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),
-                  gather=a.gather, hypothesis_chunk=a.hypothesis_chunk, p2_gather=a.p2_gather)
+    if a.frames:
+        h3wb.evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, aggregate=a.aggregate, stride=a.stride,
+                             trajectory=None if a.trajectory is None else (a.trajectory or True), log=log,
+                             hypothesis_chunk=a.hypothesis_chunk, p2=bool(args.ft2d.p2), seam_profile=a.seam_profile)
+    else:
+        h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
+                      batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),
+                      gather=a.gather, hypothesis_chunk=a.hypothesis_chunk, p2_gather=a.p2_gather)
     if world > 1:
         dist.destroy_process_group()
 

@@ -35,6 +35,8 @@
  *                            pooled into one pose (and spread) per video frame
  *   pafuse_frames_root_fit / pafuse_trajectory_smooth  the camera-space root of that per-frame pose, fitted from the
  *                            detections, and a confidence-weighted local-linear filter along the frames
+ *   pafuse_frame_errors / pafuse_frame_errors_reduce  that per-frame pose and root scored against ground truth: position,
+ *                            velocity (mean_velocity_error, common/loss.py:488-497), acceleration, root and part-based errors
  *   pafuse_procrustes_errors the Protocol #2 part of it (ft2d.p2), main_h3wb.py:381-395, common/loss.py:251-458
  *   pafuse_procrustes_partials / _combine  Protocol #2 from per-shard partial states (sharded or chunked P)
  *   pafuse_mixste2_train_*   MixSTE2.forward (is_train=True) + autograd backward, common/mixste.py:215-225,260-298
@@ -746,6 +748,41 @@ int pafuse_frames_root_fit(const float *pose /* [T,N,J,3] whole-body, root-relat
  * outside 1 .. 64, out == traj. */
 int pafuse_trajectory_smooth(const float *traj /* [T,N,3] */, const float *weight /* [T,N] or NULL */, int32_t T, int32_t N,
                              int32_t radius /* 1..64 */, float *out /* [T,N,3], may not alias traj */, void *stream);
+
+/* Frame-level errors of the per-frame pose against ground truth (pafuse_amd/framemetrics.py states the arithmetic):
+ * pose [T,N,J,3] and gt [N,J,3] whole-body and root-relative, traj [T,N,3] / gt_root [N,3] the camera-space root (both or
+ * neither).  Every fp32 input is converted to double once; everything after that is fp64 with contraction off:
+ * d[n,j] = pose[t,n,j] - gt[n,j], r[n] = traj[t,n] - gt_root[n], |v| = sqrt((v0*v0 + v1*v1) + v2*v2).  A joint takes part in
+ * a frame only if the three components of its pose and of its gt are finite.  K = 6 + num_parts slots per (t, n), each
+ * the sum of a term over the joints that take part, and their number:
+ *   0 mpjpe      |d[n,j]|
+ *   1 mpjve      |d[n,j] - d[n-1,j]|                            n >= 1, the joint in both frames (mean_velocity_error, common/loss.py:488)
+ *   2 accel      |(d[n+1,j] - d[n,j]) - (d[n,j] - d[n-1,j])|    1 <= n <= N-2, the joint in all three frames
+ *   3 root       |r[n]|              one term, count 1          traj given; traj[t,n] and gt_root[n] finite
+ *   4 root_vel   |r[n] - r[n-1]|     one term                   traj given, n >= 1, both frames
+ *   5 abs_mpjpe  |d[n,j] + r[n]|                                traj given: the camera-space error
+ *   6+i          |d[n,j] - d[n,pbroot[j]]| over the joints with part[j] == i whose part root takes part too (the part
+ *                re-centred error of pafuse_hypothesis_errors)
+ * A slot that is not defined for a frame or has no participant holds 0.0 and 0.  Every sum over j in the fixed order of
+ * pafuse_frames_root_fit.  A metric is sum of sums / sum of counts (metres, metres/frame, metres/frame^2).
+ *   err double [T,N,K], cnt int32 [T,N,K]
+ * One kernel, one wave per (t, n), no workspace, no atomics, bit-reproducible.
+ * Refused before any HIP call: a null pose / gt / pbroot / part / err / cnt, traj without gt_root or the reverse, T, N or
+ * J < 1 (PAFUSE_E_ARG); num_parts outside 1 .. PAFUSE_MAX_PARTS (PAFUSE_E_SHAPE). */
+int pafuse_frame_errors(const float *pose /* [T,N,J,3] */, const float *gt /* [N,J,3] */,
+                        const float *traj /* [T,N,3] or NULL */, const float *gt_root /* [N,3]; NULL iff traj is */,
+                        const int32_t *pbroot /* [J] root joint of every joint's part */,
+                        const int32_t *part /* [J] part of every joint, 0 .. num_parts-1 */, int32_t num_parts, int32_t T,
+                        int32_t N, int32_t J, double *err /* [T,N,6+num_parts] */, int32_t *cnt /* [T,N,6+num_parts] */,
+                        void *stream);
+
+/* The sums of those maps over the frames: sums double [T,K] and counts int64 [T,K] from err [T,N,K] and cnt [T,N,K].
+ * One wave per (t, k): lane l adds frames l, l + 64, ... in ascending order, then v += v[lane ^ o] for o = 32 .. 1.
+ * Bit-reproducible, independent of any launch shape.
+ * Refused before any HIP call: a null pointer, T or N < 1 (PAFUSE_E_ARG); K outside 7 .. 6 + PAFUSE_MAX_PARTS
+ * (PAFUSE_E_SHAPE). */
+int pafuse_frame_errors_reduce(const double *err, const int32_t *cnt, int32_t T, int32_t N, int32_t K, double *sums,
+                               int64_t *counts, void *stream);
 
 /* Protocol #2 (P-MPJPE) on the same operands - common/loss.py:251-458 as main_h3wb.py:381-395 calls it: every
  * whole-body hypothesis pose (and, per (b,t,f), the mean over h of them) aligned to its whole-body target by the

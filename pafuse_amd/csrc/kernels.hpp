@@ -3749,6 +3749,183 @@ __global__ void __launch_bounds__(256) trajectory_smooth_kernel(const Trajectory
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// Frame-level errors of the per-frame pose against ground truth (statement:
+// pafuse_amd/framemetrics.py).  pose [T,N,J,3] and gt [N,J,3] are whole-body and root-relative, traj [T,N,3] / gt_root
+// [N,3] the camera-space root (both or neither).  Every fp32 input is converted to double once, everything after that is
+// fp64 with contraction off: d[n,j] = pose[t,n,j] - gt[n,j], r[n] = traj[t,n] - gt_root[n], |v| = sqrt((v0*v0 + v1*v1) +
+// v2*v2).  A joint takes part in a frame only if the three components of its pose and of its gt are finite.  K = 6 +
+// num_parts slots per (t, n), each a sum over the joints that take part and their number:
+//   0 mpjpe      |d[n,j]|
+//   1 mpjve      |d[n,j] - d[n-1,j]|                              n >= 1, the joint in both frames
+//   2 accel      |(d[n+1,j] - d[n,j]) - (d[n,j] - d[n-1,j])|      1 <= n <= N-2, the joint in all three
+//   3 root       |r[n]|                 one term, count 1         traj given and finite, gt_root finite
+//   4 root_vel   |r[n] - r[n-1]|        one term                  n >= 1, both frames
+//   5 abs_mpjpe  |d[n,j] + r[n]|                                  the camera-space error
+//   6+i          |d[n,j] - d[n,pbroot[j]]| over the joints of part i whose part root takes part too (metrics_kernel's epb)
+// A slot that is not defined for a frame or has no participant holds 0.0 and 0.
+//
+// frame_errors_kernel: one wave per (t, n), four per workgroup; lane l owns joints l, l + 64, ... in ascending order.  The
+// rows of frames n-1 and n+1 are read again by the neighbouring waves (up to 3x the bytes of a row; L2 is expected to
+// serve them).  SLOTS >= 1: a lane loads all its <= SLOTS joints (J <= 64*SLOTS) before it adds the first term;
+// SLOTS == 0 is the same arithmetic for any J, round by round.  The per-lane sums of slots 0, 1, 2, 5 and the <= 4 parts
+// go through eight independent butterfly chains (xor 32 .. 1, as wave_sum_f64), interleaved, beside their int counts;
+// slots 3 and 4 hold one term.  A lane (or slot) without a joint feeds 0.0.  No LDS, no atomics, no scratch.
+// frame_errors_reduce_kernel: one wave per (t, k); lane l adds frames l, l + 64, ... in ascending order, then the same
+// butterfly: sums double [T,K], counts int64 [T,K], the same bits for every launch shape.
+// ----------------------------------------------------------------------------------------------------------------
+constexpr int FRAME_MAX_PARTS = 4;   // PAFUSE_MAX_PARTS: the part slots a lane keeps in registers
+
+struct FrameErrorsParams {
+    const float* pose;      // [T,N,J,3] whole-body, root-relative
+    const float* gt;        // [N,J,3]
+    const float* traj;      // [T,N,3] or null
+    const float* gt_root;   // [N,3], null iff traj is
+    const int32_t* pbroot;  // [J] the root joint of every joint's part
+    const int32_t* part;    // [J] the part of every joint
+    double* err;            // [T,N,K]
+    int32_t* cnt;           // [T,N,K]
+    int T, N, J, K;
+};
+
+// joint j in the frames n-1, n, n+1 (d[0], d[1], d[2]) and its part root in frame n (b); on*: whether it takes part there
+struct FrameJoint {
+    double d[3][3], b[3];
+    int part;
+    bool on[3], onb;
+};
+
+// x - y per component of one fp32 triple each, in fp64; -> whether all six are finite (false: d holds anything)
+__device__ __forceinline__ bool frame_diff(const float* x, const float* y, double (&d)[3]) {
+#pragma clang fp contract(off)
+    const float x0 = x[0], x1 = x[1], x2 = x[2], y0 = y[0], y1 = y[1], y2 = y[2];
+    d[0] = (double)x0 - (double)y0, d[1] = (double)x1 - (double)y1, d[2] = (double)x2 - (double)y2;
+    return isfinite(x0) && isfinite(x1) && isfinite(x2) && isfinite(y0) && isfinite(y1) && isfinite(y2);
+}
+
+__device__ __forceinline__ double frame_norm(double v0, double v1, double v2) {
+#pragma clang fp contract(off)
+    return sqrt((v0 * v0 + v1 * v1) + v2 * v2);
+}
+
+template <int SLOTS>
+__global__ void __launch_bounds__(256) frame_errors_kernel(const FrameErrorsParams p) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (int64_t)p.T * p.N) return;   // wave-uniform
+    const int n = (int)(item % p.N);
+    const int J = p.J, N = p.N;
+    const float* pose = p.pose + item * J * 3;          // row (t, n); its neighbours lie J*3 floats before and behind
+    const float* gt = p.gt + (int64_t)n * J * 3;
+    const bool rooted = p.traj != nullptr;
+    // the root error of frames n-1 and n, the same bits in every lane
+    double r0[3] = {0.0, 0.0, 0.0}, r1[3] = {0.0, 0.0, 0.0};
+    bool ron0 = false, ron1 = false;
+    if (rooted) {
+        ron1 = frame_diff(p.traj + item * 3, p.gt_root + (int64_t)n * 3, r1);
+        if (n >= 1) ron0 = frame_diff(p.traj + (item - 1) * 3, p.gt_root + (int64_t)(n - 1) * 3, r0);
+    }
+    constexpr int KEPT = SLOTS > 0 ? SLOTS : 1;
+    const int rounds = SLOTS > 0 ? SLOTS : (J + 63) / 64;
+    FrameJoint q[KEPT];
+    auto load = [&](int j) -> FrameJoint {
+        FrameJoint g;
+#pragma unroll
+        for (int m = 0; m < 3; ++m) g.on[m] = false, g.d[m][0] = g.d[m][1] = g.d[m][2] = 0.0;
+        g.onb = false, g.part = -1, g.b[0] = g.b[1] = g.b[2] = 0.0;
+        if (j < J) {
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+                const int nn = n - 1 + m;
+                if (nn >= 0 && nn < N) g.on[m] = frame_diff(pose + ((int64_t)(m - 1) * J + j) * 3, gt + ((int64_t)(m - 1) * J + j) * 3, g.d[m]);
+            }
+            const int jb = p.pbroot[j];
+            g.part = p.part[j];
+            if (jb >= 0 && jb < J) g.onb = frame_diff(pose + (int64_t)jb * 3, gt + (int64_t)jb * 3, g.b);
+        }
+        return g;
+    };
+    auto joint = [&](int r) -> FrameJoint {
+        if constexpr (SLOTS > 0) return q[r];
+        else return load(r * 64 + lane);
+    };
+#pragma unroll
+    for (int r = 0; r < KEPT; ++r) q[r] = load(SLOTS > 0 ? r * 64 + lane : J);   // SLOTS == 0: unused
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s5 = 0.0, sp[FRAME_MAX_PARTS];
+    int c0 = 0, c1 = 0, c2 = 0, c5 = 0, cp[FRAME_MAX_PARTS];
+#pragma unroll
+    for (int i = 0; i < FRAME_MAX_PARTS; ++i) sp[i] = 0.0, cp[i] = 0;
+#pragma unroll KEPT
+    for (int r = 0; r < rounds; ++r) {
+        const FrameJoint g = joint(r);
+        const double(&a)[3] = g.d[0];
+        const double(&d)[3] = g.d[1];
+        const double(&z)[3] = g.d[2];
+        const bool in01 = g.on[0] && g.on[1], in012 = in01 && g.on[2], in5 = g.on[1] && ron1, inb = g.on[1] && g.onb;
+        const double e0 = frame_norm(d[0], d[1], d[2]);
+        const double e1 = frame_norm(d[0] - a[0], d[1] - a[1], d[2] - a[2]);
+        const double e2 = frame_norm((z[0] - d[0]) - (d[0] - a[0]), (z[1] - d[1]) - (d[1] - a[1]), (z[2] - d[2]) - (d[2] - a[2]));
+        const double e5 = frame_norm(d[0] + r1[0], d[1] + r1[1], d[2] + r1[2]);
+        const double eb = frame_norm(d[0] - g.b[0], d[1] - g.b[1], d[2] - g.b[2]);
+        s0 += g.on[1] ? e0 : 0.0, c0 += g.on[1];      // a joint that takes no part feeds 0.0 whatever it holds
+        s1 += in01 ? e1 : 0.0, c1 += in01;
+        s2 += in012 ? e2 : 0.0, c2 += in012;
+        s5 += in5 ? e5 : 0.0, c5 += in5;
+#pragma unroll
+        for (int i = 0; i < FRAME_MAX_PARTS; ++i) {
+            const bool mine = inb && g.part == i;
+            sp[i] += mine ? eb : 0.0, cp[i] += mine;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {   // eight independent chains and their counts, interleaved
+        const double t0 = __shfl_xor(s0, o), t1 = __shfl_xor(s1, o), t2 = __shfl_xor(s2, o), t5 = __shfl_xor(s5, o);
+        double tp[FRAME_MAX_PARTS];
+#pragma unroll
+        for (int i = 0; i < FRAME_MAX_PARTS; ++i) tp[i] = __shfl_xor(sp[i], o);
+        c0 += __shfl_xor(c0, o), c1 += __shfl_xor(c1, o), c2 += __shfl_xor(c2, o), c5 += __shfl_xor(c5, o);
+#pragma unroll
+        for (int i = 0; i < FRAME_MAX_PARTS; ++i) cp[i] += __shfl_xor(cp[i], o);
+        s0 += t0, s1 += t1, s2 += t2, s5 += t5;
+#pragma unroll
+        for (int i = 0; i < FRAME_MAX_PARTS; ++i) sp[i] += tp[i];
+    }
+    const bool in4 = ron0 && ron1;
+    const double e3 = ron1 ? frame_norm(r1[0], r1[1], r1[2]) : 0.0;
+    const double e4 = in4 ? frame_norm(r1[0] - r0[0], r1[1] - r0[1], r1[2] - r0[2]) : 0.0;
+    // lane k writes slot k
+    const double v = lane == 0 ? s0 : lane == 1 ? s1 : lane == 2 ? s2 : lane == 3 ? e3 : lane == 4 ? e4 : lane == 5 ? s5
+                   : lane == 6 ? sp[0] : lane == 7 ? sp[1] : lane == 8 ? sp[2] : sp[3];
+    const int c = lane == 0 ? c0 : lane == 1 ? c1 : lane == 2 ? c2 : lane == 3 ? (int)ron1 : lane == 4 ? (int)in4 : lane == 5 ? c5
+                : lane == 6 ? cp[0] : lane == 7 ? cp[1] : lane == 8 ? cp[2] : cp[3];
+    if (lane < p.K) p.err[item * p.K + lane] = v, p.cnt[item * p.K + lane] = c;
+}
+
+struct FrameErrorsReduceParams {
+    const double* err;    // [T,N,K]
+    const int32_t* cnt;   // [T,N,K]
+    double* sums;         // [T,K]
+    int64_t* counts;      // [T,K]
+    int T, N, K;
+};
+
+__global__ void __launch_bounds__(256) frame_errors_reduce_kernel(const FrameErrorsReduceParams p) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // (t, k)
+    if (item >= (int64_t)p.T * p.K) return;   // wave-uniform
+    const int k = (int)(item % p.K);
+    const int64_t row0 = (item / p.K) * p.N;   // (t, 0)
+    double s = 0.0;
+    long long c = 0;
+    for (int n = lane; n < p.N; n += 64) s += p.err[(row0 + n) * p.K + k], c += p.cnt[(row0 + n) * p.K + k];
+    s = wave_sum_f64(s);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o);
+    if (lane == 0) p.sums[item] = s, p.counts[item] = (int64_t)c;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // Protocol #2 (P-MPJPE) behind the all-gather: common/loss.py:251-458 as main_h3wb.py:381-395 calls it on the
 // whole-body poses.  Every hypothesis pose Y is aligned to its target X by the similarity transform of the
 // reference (centre both, H = (X0/|X0|)^T (Y0/|Y0|), R = V U^T with the reflection fix, a = tr(S') |X0| / |Y0|) and

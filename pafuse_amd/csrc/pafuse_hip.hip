@@ -2137,6 +2137,47 @@ int pafuse_trajectory_smooth(const float* traj, const float* weight, int32_t T, 
     return launch<trajectory_smooth_kernel>("trajectory_smooth_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
 }
 
+// the frame-level errors of the per-frame pose against ground truth (frame_errors_kernel) and their sums over the frames
+// (frame_errors_reduce_kernel): the argument checks come before the first HIP call
+static_assert(FRAME_MAX_PARTS == PAFUSE_MAX_PARTS, "frame_errors_kernel keeps one register slot per part");
+
+int pafuse_frame_errors(const float* pose, const float* gt, const float* traj, const float* gt_root, const int32_t* pbroot,
+                        const int32_t* part, int32_t num_parts, int32_t T, int32_t N, int32_t J, double* err, int32_t* cnt,
+                        void* stream) {
+    if (!pose || !gt || !pbroot || !part || !err || !cnt) return fail(PAFUSE_E_ARG, "frame_errors: pose, gt, pbroot, part, err and cnt are needed");
+    if ((traj == nullptr) != (gt_root == nullptr)) return fail(PAFUSE_E_ARG, "frame_errors: traj and gt_root come together (or neither)");
+    if (T < 1 || N < 1 || J < 1) return fail(PAFUSE_E_ARG, "frame_errors: bad size (T=%d N=%d J=%d)", T, N, J);
+    if (num_parts < 1 || num_parts > PAFUSE_MAX_PARTS) return fail(PAFUSE_E_SHAPE, "frame_errors: num_parts %d outside 1 .. %d", num_parts, PAFUSE_MAX_PARTS);
+    const int64_t waves = (int64_t)T * N;   // one wave per (t, n), four per workgroup
+    if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "frame_errors: grid out of range");
+    StreamDevice on_stream_device(stream);
+    FrameErrorsParams m{};
+    m.pose = pose, m.gt = gt, m.traj = traj, m.gt_root = gt_root, m.pbroot = pbroot, m.part = part, m.err = err, m.cnt = cnt;
+    m.T = T, m.N = N, m.J = J, m.K = 6 + num_parts;
+    const unsigned grid = blocks_for(waves, 4);
+    hipStream_t s = (hipStream_t)stream;
+    switch ((J + 63) / 64) {   // the joints of a lane in registers up to J = 256; beyond, the same arithmetic round by round
+        case 1: return launch<frame_errors_kernel<1>>("frame_errors_kernel", grid, 256, 0, s, m);
+        case 2: return launch<frame_errors_kernel<2>>("frame_errors_kernel", grid, 256, 0, s, m);
+        case 3: return launch<frame_errors_kernel<3>>("frame_errors_kernel", grid, 256, 0, s, m);
+        case 4: return launch<frame_errors_kernel<4>>("frame_errors_kernel", grid, 256, 0, s, m);
+        default: return launch<frame_errors_kernel<0>>("frame_errors_kernel", grid, 256, 0, s, m);
+    }
+}
+
+int pafuse_frame_errors_reduce(const double* err, const int32_t* cnt, int32_t T, int32_t N, int32_t K, double* sums,
+                               int64_t* counts, void* stream) {
+    if (!err || !cnt || !sums || !counts) return fail(PAFUSE_E_ARG, "frame_errors_reduce: null pointer");
+    if (T < 1 || N < 1) return fail(PAFUSE_E_ARG, "frame_errors_reduce: bad size (T=%d N=%d)", T, N);
+    if (K < 7 || K > 6 + PAFUSE_MAX_PARTS) return fail(PAFUSE_E_SHAPE, "frame_errors_reduce: K = %d outside 7 .. %d (6 + num_parts)", K, 6 + PAFUSE_MAX_PARTS);
+    const int64_t waves = (int64_t)T * K;   // one wave per (t, k), four per workgroup
+    if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "frame_errors_reduce: grid out of range");
+    StreamDevice on_stream_device(stream);
+    FrameErrorsReduceParams m{};
+    m.err = err, m.cnt = cnt, m.sums = sums, m.counts = counts, m.T = T, m.N = N, m.K = K;
+    return launch<frame_errors_reduce_kernel>("frame_errors_reduce_kernel", blocks_for(waves, 4), 256, 0, (hipStream_t)stream, m);
+}
+
 int pafuse_procrustes_errors(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,
                              const int32_t* conn, int32_t B, int32_t T, int32_t P, int32_t F, int32_t J, float* jbest,
                              double* pbest_sums, float* pagg, float* jagg, int32_t* pick, void* stream) {

@@ -22,6 +22,9 @@ pose with its hypothesis index - by the same scheme and without a ground truth (
 (``ops.spread_partials``, ``ops.combine_spread``); ``aggregate_poses_sharded(spread_state=...)`` returns their per-joint
 covariance and std beside the pose.
 
+``frame_metrics`` scores a per-frame pose (and its camera-space root) against ground truth at the level of frames - position,
+velocity, acceleration, root and part-based errors (``ops.frame_errors``; ``pafuse_amd.framemetrics`` states the arithmetic).
+
 The four families share their host code: ``_operands`` checks and converts the arguments of every entry point,
 ``_RunningState.fold`` is the one running reduction (``PartialState``, ``Procrustes2State``, ``PoseState`` and ``SpreadState`` only declare
 what each family keeps; every ``accumulate_*`` hands ``fold`` its partials op and its combine op), and ``_exchange`` is the
@@ -605,3 +608,65 @@ def accumulate_frames(frames, merged, starts, valid, N, num_proposals):
         ops.fold_spread_windows(frames.spread, N, merged["spread_state"], (B, T, F, J), starts, valid)
     frames.windows += B
     return frames
+
+
+# ----------------------------------------------------------------- the per-frame pose scored against ground truth
+FRAME_METRICS = ("mpjpe", "mpjve", "accel", "root", "root_vel", "abs_mpjpe")   # ops.FRAME_ERROR_SLOTS; then one slot per part
+
+
+def frame_metric_names(dataset):
+    """the slots of ops.frame_errors by name: FRAME_METRICS, then "mpjpe_pb_<part>" in the order of dataset.parts_joint_indices"""
+    return FRAME_METRICS + tuple("mpjpe_pb_" + part for part in dataset.parts_joint_indices)
+
+
+def frame_metrics(pose, gt_wb, dataset, traj=None, gt_root=None, p2=False, per_frame=False):
+    """The per-frame output scored against ground truth on the device (ops.frame_errors; pafuse_amd.framemetrics states the
+    arithmetic): pose [T,N,J,3] whole-body and root-relative - infer_sequence(stride=)["pose"] or stitch_poses, NaN where there
+    is no pose - gt_wb [N,J,3] likewise (joint 0 at 0), traj [T,N,3] the fitted or smoothed root with gt_root [N,3] (both or
+    neither).  Returns a dict of ``(sum [T] float64, count [T] int64)`` on the device, a metric being sum / count in metres:
+
+      mpjpe       the position error per joint             mpjve   its first difference along the frames (m/frame)
+      accel       its second difference (m/frame^2)        mpjpe_pb_<part>, mpjpe_pb   the part re-centred error, per part and all
+      root, root_vel, abs_mpjpe   (with traj) the root error, its first difference, and the camera-space error per joint
+
+    A joint takes part in a frame only where its pose and its gt are finite; the counts say how many did.  ``p2=True`` adds
+    ``p_mpjpe``: the error after the reference's similarity alignment of every frame's pose to its gt - the existing
+    ops.procrustes_errors on the pose as a single hypothesis (its P-Agg of one hypothesis is the aligned error of the pose
+    itself) - summed as the mean over the joints of every frame in which all joints are finite; its count is the number of
+    frames scored.  It needs joint 0 at the origin in both (wb_joint pins it there) and J <= 256.  ``per_frame=True`` adds
+    ``"err"`` [T,N,K] float64 and ``"cnt"`` [T,N,K] int32, the maps per frame in the order of frame_metric_names."""
+    from . import ops
+    if not (isinstance(pose, torch.Tensor) and pose.is_cuda):
+        raise _lib.PafuseError("frame_metrics runs on the HIP device only (no CPU fallback)")
+    if pose.dim() != 4 or pose.shape[-1] != 3:
+        raise ValueError(f"pose must be [T,N,J,3], got {tuple(pose.shape)}")
+    T, N, J, _ = pose.shape
+    if tuple(gt_wb.shape) != (N, J, 3):
+        raise ValueError(f"gt_wb must be [N,J,3] = {(N, J, 3)}, got {tuple(gt_wb.shape)}")
+    if (traj is None) != (gt_root is None):
+        raise ValueError("traj and gt_root come together (or neither)")
+    covered = sorted(j for idx in dataset.parts_joint_indices.values() for j in idx)
+    if covered != list(range(J)):
+        raise ValueError("dataset.parts_joint_indices must cover every joint exactly once")
+    dev = pose.device
+    _, pbroot = _tables(dataset, J, dev)
+    part = _part_table(dataset, J, dev)
+    names = frame_metric_names(dataset)
+    num_parts = len(names) - len(FRAME_METRICS)
+    pose, gt = pose.contiguous().float(), gt_wb.to(dev).contiguous().float()
+    if traj is not None:
+        traj, gt_root = traj.to(dev).contiguous().float(), gt_root.to(dev).reshape(N, 3).contiguous().float()
+    m = ops.frame_errors(pose, gt, pbroot, part, num_parts, traj=traj, gt_root=gt_root, per_frame=per_frame)
+    out = {k: (m["sums"][:, i], m["counts"][:, i]) for i, k in enumerate(names) if traj is not None or k not in ("root", "root_vel", "abs_mpjpe")}
+    out["mpjpe_pb"] = (m["sums"][:, 6:].sum(dim=1), m["counts"][:, 6:].sum(dim=1))
+    if p2:
+        scored = (torch.isfinite(pose).all(dim=-1) & torch.isfinite(gt).all(dim=-1)[None]).all(dim=-1)     # [T,N]
+        cam = torch.tensor([1.0, 1.0, 0, 0, 0, 0, 0, 0, 0], device=dev)
+        root = torch.tensor([0.0, 0.0, 1.0], device=dev).expand(1, N, 3).contiguous()   # x2d, traj, cam: only outputs ignored here see them
+        r = ops.procrustes_errors(pose.view(1, T, 1, N, J, 3), gt.view(1, N, J, 3), torch.zeros(1, N, J, 2, device=dev), root, cam,
+                                  torch.zeros(J, dtype=torch.int32, device=dev), pick=False)
+        per_frame_mean = r["pagg"][0].double().sum(dim=-1) / J                                                # [T,N]
+        out["p_mpjpe"] = (torch.where(scored, per_frame_mean, torch.zeros_like(per_frame_mean)).sum(dim=1), scored.sum(dim=1))
+    if per_frame:
+        out["err"], out["cnt"] = m["err"], m["cnt"]
+    return out

@@ -249,6 +249,38 @@ def evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, batc
     return rep
 
 
+def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
+                    batch_size=2, group=None, log=print, action=None, hypothesis_chunk=None, p2=False, seam_profile=False):
+    """The frame-level evaluation of every video, looped like :func:`evaluate`: harness.evaluate_frames per (camera, sequence) -
+    one pose per video frame (``aggregate``, ``stride``; None: un-strided clips laid end to end), optionally its fitted
+    camera-space root (``trajectory``: True or a smoothing radius) - scored on the device; the sums and counts added over the
+    videos; millimetres per metric and sampling step (harness.frame_report) printed through `log` in the lines of
+    harness.format_frame_report.  ``seam_profile=True`` also keeps the per-frame maps and logs the position error binned by the
+    frame's position in the clip (harness.seam_profile, summed over the videos); the return value is then ``(rep, profile)``,
+    profile float64 [T, model.frames] in mm.  On synthetic weights the numbers mean nothing."""
+    from . import harness
+    sums = counts = prof_s = prof_c = None
+    for cam, seq_3d, seq_2d in iter_sequences(cams, poses_3d, poses_2d):
+        got = harness.evaluate_frames(model, dataset, seq_2d[0].astype("float32"), seq_3d[0].astype("float32"),
+                                      cam[0].astype("float32"), kps_left, kps_right, aggregate=aggregate, stride=stride,
+                                      trajectory=trajectory, batch_size=batch_size, group=group,
+                                      hypothesis_chunk=hypothesis_chunk, p2=p2, per_frame=seam_profile)
+        sums = got[0] if sums is None else {k: sums[k] + got[0][k] for k in sums}
+        counts = got[1] if counts is None else {k: counts[k] + got[1][k] for k in counts}
+        if seam_profile:       # the sums and the counts of the bins add over videos; the quotient is formed once
+            s, c = harness.seam_bins(got[2]["err"], got[2]["cnt"], model.frames)
+            prof_s, prof_c = (s, c) if prof_s is None else (prof_s + s, prof_c + c)
+    rep = harness.frame_report(sums, counts)
+    for line in harness.format_frame_report(rep, action):
+        log(line)
+    if not seam_profile:
+        return rep
+    profile = prof_s / prof_c * 1000.0
+    for t in range(profile.shape[0]):
+        log("step %d : MPJPE by position in the clip (mm): %s" % (t, " ".join("%.3f" % v for v in profile[t].tolist())))
+    return rep, profile
+
+
 class ChunkedClips:
     """Training batches: every video cut into `chunk_length`-frame clips centred on the video (the overhang split
     between both ends and filled by repeating the edge frame), each clip optionally a second time mirrored (x negated,

@@ -215,6 +215,14 @@ def cut_windows(seq, starts, frames=27):
 def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
                   conf, stride, dev, trajectory=False, smooth=None):
     """infer_sequence(stride=...): sliding windows pooled into one pose per video frame (arguments already checked)"""
+    out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
+                               spread, conf, stride, dev, trajectory, smooth)
+    return {k: v.cpu() for k, v in out.items()}
+
+
+def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
+                         conf, stride, dev, trajectory=False, smooth=None):
+    """_infer_frames with its result left on the device (evaluate_frames scores it there)"""
     from . import ops
     from .windows import window_starts
     if seq_2d.dim() == 4:
@@ -262,7 +270,7 @@ def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group
     out.pop("mean", None)
     if trajectory:  # the root of the pose that is returned, on the device before anything crosses to the host
         out.update(_fit_trajectory(out["pose"], seq_2d.to(dev), cam, None if frame_conf is None else frame_conf.to(dev), smooth))
-    return {k: v.cpu() for k, v in out.items()}
+    return out
 
 
 def _trajectory_radius(trajectory, name="trajectory"):
@@ -535,3 +543,104 @@ holds the p2_* keys, each step ends with the four Protocol #2 lines (:511-519): 
                 written.append("%s %f mm" % (head, rep[key][ii]))
     both("----------")
     return printed, written
+
+
+# ----------------------------------------------------------------- the per-frame output scored against ground truth
+@torch.no_grad()
+def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
+                    conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False):
+    """One video scored at the level of frames: the frames path of :func:`infer_sequence` - ONE pose per video frame, pooled
+    over the windows that cover it - against the ground truth, on the device before anything crosses to the host
+    (evaluate.frame_metrics; pafuse_amd.framemetrics states the arithmetic).
+
+    seq_2d [N,J,2] normalised 2-D input, seq_3d [N,J,3] camera-space ground truth (metres), cam [9] intrinsics.  ``aggregate``:
+    "mean", "reproj" or "reproj_fit" as in infer_sequence; "reproj" takes its trajectory from the ground truth root, as the
+    reference's J-Agg does; "reproj_fit" and ``trajectory`` use ``cam`` only.  ``stride``: 1 .. model.frames; None means
+    model.frames - un-strided clips laid end to end.  ``trajectory`` (True, or a smoothing radius 1 .. 64) also fits the
+    camera-space root and scores it: root, root_vel, abs_mpjpe.  ``conf`` [N,J] with "reproj_fit" or a trajectory.
+
+    Returns ``(sums, counts)``: dicts of CPU tensors [T], float64 and int64, keyed by evaluate.frame_metric_names plus
+    "mpjpe_pb" (and "p_mpjpe" with ``p2=True``) - add them over videos and hand them to :func:`frame_report`.
+    ``per_frame=True`` returns ``(sums, counts, maps)``, maps = {"err" [T,N,K] float64, "cnt" [T,N,K] int32, "names"}: the
+    same per frame, what :func:`seam_profile` bins.  On synthetic weights the numbers mean nothing."""
+    if aggregate not in ("mean", "reproj", "reproj_fit"):
+        raise ValueError(f'aggregate must be "mean", "reproj" or "reproj_fit", got {aggregate!r}')
+    frames = getattr(model, "frames", None)
+    if stride is None:
+        stride = frames
+    if isinstance(stride, bool) or not isinstance(stride, int) or not 1 <= stride <= frames:
+        raise ValueError(f"stride must be None or an integer in 1 .. {frames} (the window length), got {stride!r}")
+    smooth = _trajectory_radius(trajectory)
+    if cam is None:
+        raise ValueError("evaluate_frames needs cam [9] (the intrinsics)")
+    if hypothesis_chunk is not None and int(hypothesis_chunk) < 1:
+        raise ValueError("hypothesis_chunk is a positive count")
+    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
+    seq_3d = torch.as_tensor(seq_3d, dtype=torch.float32)
+    if seq_2d.dim() != 3 or seq_2d.shape[-1] != 2 or tuple(seq_3d.shape) != (*seq_2d.shape[:2], 3):
+        raise ValueError(f"seq_2d must be [N,J,2] and seq_3d [N,J,3], got {tuple(seq_2d.shape)} and {tuple(seq_3d.shape)}")
+    if conf is not None:
+        if aggregate != "reproj_fit" and trajectory is None:
+            raise ValueError('conf belongs to aggregate="reproj_fit" or a trajectory')
+        conf = torch.as_tensor(conf, dtype=torch.float32)
+        if tuple(conf.shape) != tuple(seq_2d.shape[:2]):
+            raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[:2])}, got {tuple(conf.shape)}")
+    from .evaluate import frame_metrics
+    dev = next(model.parameters()).device
+    gt_root = seq_3d[:, 0].contiguous()                             # [N,3]
+    gt_wb = (seq_3d - seq_3d[:, :1]).to(dev)                        # joint 0 at 0, exactly
+    out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam,
+                               gt_root if aggregate == "reproj" else None, hypothesis_chunk, None, conf, stride, dev,
+                               trajectory is not None, smooth)
+    m = frame_metrics(out["pose"], gt_wb, dataset, traj=out.get("traj"), gt_root=gt_root.to(dev) if "traj" in out else None,
+                      p2=p2, per_frame=per_frame)
+    maps = {k: m.pop(k).cpu() for k in ("err", "cnt") if k in m}
+    sums, counts = {k: v[0].cpu() for k, v in m.items()}, {k: v[1].cpu() for k, v in m.items()}
+    if per_frame:
+        from .evaluate import frame_metric_names
+        maps["names"] = frame_metric_names(dataset)
+        return sums, counts, maps
+    return sums, counts
+
+
+FRAME_UNITS = {"mpjve": "mm/frame", "root_vel": "mm/frame", "accel": "mm/frame^2"}     # every other metric: mm
+
+
+def frame_report(sums, counts):
+    """mm per metric and step from the sums and counts of :func:`evaluate_frames` (added over the videos): sum / count * 1000;
+    mm/frame for mpjve and root_vel, mm/frame^2 for accel (FRAME_UNITS); NaN where nothing was counted."""
+    return {k: (sums[k].double() / counts[k].double() * 1000.0).tolist() for k in sums}
+
+
+def format_frame_report(rep, action=None):
+    """The lines of a frame-level report, step by step, in the style of :func:`format_report`."""
+    lines = ["----------" if action is None else "----" + action + "----"]
+    for ii in range(len(rep["mpjpe"])):
+        for k in rep:
+            lines.append("step %d : Frame Error (%s): %f %s" % (ii, k.upper(), rep[k][ii], FRAME_UNITS.get(k, "mm")))
+    lines.append("----------")
+    return lines
+
+
+def seam_bins(err, cnt, frames, slot=0):
+    """-> (sums, counts) float64 [T, frames]: err[t, n, slot] and cnt[t, n, slot] added over n = i mod frames; what
+    :func:`seam_profile` divides, kept apart so that several videos can be added first"""
+    err = torch.as_tensor(err, dtype=torch.float64).cpu()
+    cnt = torch.as_tensor(cnt).cpu()
+    frames = int(frames)
+    if err.dim() != 3 or tuple(cnt.shape) != tuple(err.shape) or not 0 <= int(slot) < err.shape[2] or frames < 1:
+        raise ValueError("seam_profile: err and cnt are [T,N,K] maps, slot one of the K, frames >= 1")
+    T, N, _ = err.shape
+    bins = (torch.arange(N) % frames).expand(T, N)
+    s = torch.zeros(T, frames, dtype=torch.float64).scatter_add_(1, bins, err[:, :, slot])
+    c = torch.zeros(T, frames, dtype=torch.float64).scatter_add_(1, bins, cnt[:, :, slot].double())
+    return s, c
+
+
+def seam_profile(err, cnt, frames, slot=0):
+    """The per-frame maps of evaluate_frames(per_frame=True) binned by the position in the clip: err, cnt [T,N,K] ->
+    float64 [T, frames], entry (t, i) = sum of err[t, n, slot] over n = i mod frames / the sum of cnt there (NaN where nothing
+    was counted), in the maps' unit (metres).  With stride = frames the ends of the profile are the clip seams - a border frame
+    has temporal context on one side only; compare with a stride < frames.  Host-side."""
+    s, c = seam_bins(err, cnt, frames, slot)
+    return s / c

@@ -1330,6 +1330,41 @@ def smooth_trajectory(traj, weight, radius, out=None):
     return out
 
 
+# ------------------------------------------------------------------ the per-frame pose scored against ground truth
+FRAME_ERROR_SLOTS = ("mpjpe", "mpjve", "accel", "root", "root_vel", "abs_mpjpe")   # then one slot per part (pafuse_amd.framemetrics)
+
+
+def frame_errors(pose, gt, pbroot, part, num_parts, traj=None, gt_root=None, per_frame=False):
+    """pafuse_frame_errors + pafuse_frame_errors_reduce: pose [T,N,J,3] the per-frame whole-body, root-relative pose (NaN: no
+    pose), gt [N,J,3] likewise, pbroot / part int32 [J] (the root joint of every joint's part, the part's number), num_parts
+    1 .. 4, traj [T,N,3] with gt_root [N,3] (the camera-space root; both or neither) -> {"sums": [T,K] float64, "counts": [T,K]
+    int64}, K = 6 + num_parts in the order of FRAME_ERROR_SLOTS then the parts: the sums over the frames of the position,
+    velocity, acceleration, root, root-velocity, camera-space and part-based errors and of the joints (frames) that took part.
+    A metric is sums / counts, in metres.  per_frame=True: also "err" [T,N,K] float64 and "cnt" [T,N,K] int32, the same per
+    frame.  pafuse_amd.framemetrics states the arithmetic (fp64)."""
+    lib = _lib.load()
+    _need(isinstance(pose, torch.Tensor) and pose.dim() == 4 and pose.shape[-1] == 3, "frame_errors: pose must be [T,N,J,3]")
+    T, N, J = (int(v) for v in pose.shape[:3])
+    _need(T > 0 and N > 0 and J > 0, "frame_errors: T, N, J > 0")
+    _need(not isinstance(num_parts, bool) and int(num_parts) == num_parts and 1 <= int(num_parts) <= _lib.MAX_PARTS,
+          f"frame_errors: num_parts must be an integer in 1 .. {_lib.MAX_PARTS}, got {num_parts!r}")
+    _need((traj is None) == (gt_root is None), "frame_errors: traj and gt_root come together (or neither)")
+    _need(isinstance(gt, torch.Tensor) and tuple(gt.shape) == (N, J, 3) and tuple(pbroot.shape) == (J,) and tuple(part.shape) == (J,)
+          and (traj is None or (tuple(traj.shape) == (T, N, 3) and tuple(gt_root.shape) == (N, 3))),
+          "frame_errors: gt [N,J,3], pbroot [J], part [J], traj [T,N,3] and gt_root [N,3] must match pose [T,N,J,3]")
+    _need_tensors("frame_errors", [pose, gt] + ([] if traj is None else [traj, gt_root]), (pbroot, part))
+    dev, K = pose.device, 6 + int(num_parts)
+    out = {"err": torch.empty(T, N, K, device=dev, dtype=torch.float64), "cnt": torch.empty(T, N, K, device=dev, dtype=torch.int32),
+           "sums": torch.empty(T, K, device=dev, dtype=torch.float64), "counts": torch.empty(T, K, device=dev, dtype=torch.int64)}
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_frame_errors(pose.data_ptr(), gt.data_ptr(), None if traj is None else traj.data_ptr(),
+                                           None if traj is None else gt_root.data_ptr(), pbroot.data_ptr(), part.data_ptr(),
+                                           int(num_parts), T, N, J, out["err"].data_ptr(), out["cnt"].data_ptr(), _stream(pose)))
+        _lib.check(lib.pafuse_frame_errors_reduce(out["err"].data_ptr(), out["cnt"].data_ptr(), T, N, K, out["sums"].data_ptr(),
+                                                  out["counts"].data_ptr(), _stream(pose)))
+    return out if per_frame else {k: out[k] for k in ("sums", "counts")}
+
+
 # ------------------------------------------------------------------------------ Protocol #2 from partial states
 PROCRUSTES_HEAD_BYTES_PER_ELEMENT = 16   # float jbest, e2, sel + int32 idx per (b, t, f, j)
 

@@ -19,6 +19,7 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::finish_frames(frame, N, T, J, spread?)          one pose per video frame: mean, pick, idx, window (+ std, cov)
   pafuse::fit_trajectory(pose, x2d, cam, conf?)           the camera-space root of that pose: traj, wsum, resid per (t, frame)
   pafuse::smooth_trajectory(traj, weight?, radius)        a confidence-weighted local-linear filter along the frames
+  pafuse::frame_errors(pose, gt, pbroot, part, num_parts, traj?, gt_root?)   that pose (and root) scored against ground truth
   pafuse::noise_fill(key, draw, B, P, F, J)               one draw of noise stream v1 as a tensor (DESIGN.md section 6)
 
 ``precision`` ('bf16x3' = the modules' default; 'bf16x3_images', 'f16x2', 'f32', 'bf16': pafuse_amd.D3DP.precision) is the
@@ -464,6 +465,24 @@ def smooth_trajectory(traj: torch.Tensor, weight: Optional[torch.Tensor], radius
 @smooth_trajectory.register_fake
 def _(traj, weight, radius):
     return torch.empty_like(traj)
+
+
+# ------------------------------------------------------------------ the per-frame pose scored against ground truth
+@torch.library.custom_op("pafuse::frame_errors", mutates_args=(), device_types="cuda")
+def frame_errors(pose: torch.Tensor, gt: torch.Tensor, pbroot: torch.Tensor, part: torch.Tensor, num_parts: int,
+                 traj: Optional[torch.Tensor] = None, gt_root: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+    """pafuse_amd.ops.frame_errors(per_frame=True): pose [T,N,J,3], gt [N,J,3], pbroot / part int32 [J], num_parts, traj [T,N,3]
+    with gt_root [N,3] or neither -> [sums [T,K] float64, counts [T,K] int64, err [T,N,K] float64, cnt [T,N,K] int32], K = 6 + num_parts."""
+    from . import ops
+    m = ops.frame_errors(pose, gt, pbroot, part, num_parts, traj=traj, gt_root=gt_root, per_frame=True)
+    return [m["sums"], m["counts"], m["err"], m["cnt"]]
+
+
+@frame_errors.register_fake
+def _(pose, gt, pbroot, part, num_parts, traj=None, gt_root=None):
+    T, N, K = pose.shape[0], pose.shape[1], 6 + num_parts
+    return [pose.new_empty((T, K), dtype=torch.float64), pose.new_empty((T, K), dtype=torch.int64),
+            pose.new_empty((T, N, K), dtype=torch.float64), pose.new_empty((T, N, K), dtype=torch.int32)]
 
 
 # ----------------------------------------------------------------------------------------------- noise stream v1
