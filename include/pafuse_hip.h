@@ -24,6 +24,7 @@
  *                            (with model_predictions[_fliping] :174-225, pred_parts/split_data :163-172,328-335)
  *   pafuse_embed             the input stage of model_predictions_fliping + split_data + the first lines of
  *                            MixSTE2.STE_forward: common/diffusionpose.py:193-198,328-335, common/mixste.py:227-235
+ *   pafuse_embed_unit        the same stage in each output form the loop launches (folded LayerNorm, images, row windows)
  *   pafuse_ddim_finalize     the output stage of a DDIM step: part concat + un-flip + TTA mean + clamp
  *                            (common/diffusionpose.py:165-171,211-218), epsilon in fp64 (:157-161,222-223), update (:302-312)
  *   pafuse_hypothesis_errors the per-joint part of evaluate()'s aggregation, main_h3wb.py:327-362
@@ -518,6 +519,33 @@ int pafuse_embed(const float *x3d, const float *x2d, const float *x2d_flip, cons
                  const float *patch_w, const float *patch_b, const float *pos_spatial, const float *temb,
                  const float *norm_w, const float *norm_b, float norm_eps, int32_t B, int32_t P, int32_t F, int32_t J,
                  int32_t J3, int32_t C, int32_t nflip, int32_t do_clamp, double scale, float *x, float *xn, void *stream);
+
+/* pafuse_embed_unit: the same stage in every output form the sampling loop launches it in, for the rows [row0, row0 + nrows)
+ * of the token matrix - through the one host function that maps (product mode, folded LayerNorm, H-residual-only) to the
+ * kernel's outputs for pafuse_d3dp_sample, pafuse_mixste2_forward and pafuse_embed alike.  Operands as pafuse_embed; further:
+ *   operand_bf16     as pafuse_mixste2_weights.operand_bf16.  3 / 4: the normalised (or centred) row is written as its H / X
+ *                    image into `image` ([M,C] rows of 4 C / 6 C bytes) and xn is not written
+ *   ln_folded        (modes 2 - 4) the LayerNorm is left to the qkv GEMM: stats[2 i] = (mean, rstd) of row row0 + i, no xn;
+ *                    mode 2: x holds the CENTRED rows x - mean; modes 3 / 4: the image is that of the centred row, x stays plain
+ *   h_residual_only  (modes 3 / 4, folded) the fp32 rows are not kept: x is not written (and may be NULL)
+ * x, xn and image are indexed by the ABSOLUTE row (buffers of all M = nflip B P F J rows), stats by the LOCAL row (nrows pairs).
+ * Refused before any launch: PAFUSE_E_ARG for what pafuse_embed refuses, a mode outside 0 .. 4, ln_folded in modes 0 / 1,
+ * h_residual_only outside (modes 3 / 4, folded), a window that is empty or not inside [0, M), an output the form writes that
+ * is NULL; PAFUSE_E_SHAPE for an H image at C % 8 != 0 or an X image at C % 32 != 0. */
+typedef struct pafuse_embed_args {
+    const float *x3d, *x2d, *x2d_flip;
+    const int32_t *joints, *perm;
+    const float *patch_w, *patch_b, *pos_spatial, *temb, *norm_w, *norm_b;
+    float norm_eps;
+    int32_t B, P, F, J, J3, C, nflip, do_clamp;
+    double scale;
+    int32_t operand_bf16, ln_folded, h_residual_only;
+    float *x, *xn;                  /* [M,C] */
+    void *image;                    /* modes 3, 4: [M,C] image */
+    float *stats;                   /* ln_folded: [nrows,2] */
+    int64_t row0, nrows;
+} pafuse_embed_args;
+int pafuse_embed_unit(const pafuse_embed_args *a, void *stream);
 
 /* pafuse_ddim_finalize: output stage of DDIM step `step` of T.  pred[i] = part i's denoiser output
  * [nflip*B*P*F*part_joints[i], 3] (host array of `num_parts` device pointers; flipped half second).  Per (b,p,f,j):

@@ -65,6 +65,15 @@ class LnbArgs(C.Structure):
                 [(n, C.c_void_p) for n in ("out_scaled", "dw", "db", "dbranch")] + [("M", C.c_int64), ("C", C.c_int32)])
 
 
+class EmbedArgs(C.Structure):
+    """pafuse_embed_args: one embed launch in any of the sampling loop's output forms, for pafuse_embed_unit"""
+    _fields_ = ([(n, C.c_void_p) for n in ("x3d", "x2d", "x2d_flip", "joints", "perm", "patch_w", "patch_b", "pos_spatial", "temb",
+                                           "norm_w", "norm_b")] + [("norm_eps", C.c_float)] +
+                [(n, C.c_int32) for n in ("B", "P", "F", "J", "J3", "C", "nflip", "do_clamp")] + [("scale", C.c_double)] +
+                [(n, C.c_int32) for n in ("operand_bf16", "ln_folded", "h_residual_only")] +
+                [(n, C.c_void_p) for n in ("x", "xn", "image", "stats")] + [("row0", C.c_int64), ("nrows", C.c_int64)])
+
+
 class DDIMStep(C.Structure):
     _fields_ = [("time", C.c_int64), ("last", C.c_int32),
                 ("sqrt_recip_acp", C.c_double), ("sqrt_recipm1_acp", C.c_double),
@@ -142,6 +151,7 @@ SIGNATURES = {
     "pafuse_d3dp_check_range": (C.c_int, [C.POINTER(D3DPConfig), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pafuse_embed": (C.c_int, [C.c_void_p] * 11 + [C.c_float] + [C.c_int32] * 8 + [C.c_double, C.c_void_p, C.c_void_p,
                                                                                     C.c_void_p]),
+    "pafuse_embed_unit": (C.c_int, [C.POINTER(EmbedArgs), C.c_void_p]),
     "pafuse_ddim_finalize": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32] + [C.c_void_p] * 6 +
                              [C.c_int32] * 7 + [C.c_double, C.POINTER(DDIMStep), C.c_void_p]),
     "pafuse_hypothesis_errors": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p] * 7),

@@ -2415,8 +2415,12 @@ __global__ void __launch_bounds__(256) embed_kernel(const EmbedParams p) {
 // ----------------------------------------------------------------------------------------------------------------
 // End of a DDIM step (common/diffusionpose.py:211-223 and :298-312): part concat, un-flip, TTA average, scale,
 // clamp -> x_start (written into preds_all[:, step]); epsilon in fp64; img update with the step's noise draw.
-// One thread per (b, p, f, joint).  Every fp32 op is individually rounded (no FMA contraction) like the
-// reference's separate ATen ops.
+// One thread per (b, p, f, joint).  Every fp32 and fp64 op is individually rounded (no FMA contraction) like the
+// reference's separate ATen ops: finalize_body is compiled with contraction off and spells its products and sums with the
+// plain operators that switch governs - HIP's __fmul_rn / __fadd_rn / __dmul_rn are plain operators inside inline functions
+// of a header, which the compiler's default (contract = fast) fuses after inlining: the flip update ran as one multiply and
+// two fused multiply-adds, epsilon as fma(sr, img, -x0), the no-flip update as fma(c, eps, x0 an), each a last-bit departure
+// from the reference (tests/test_hip_loop_rim.py holds the chain to the oracle with torch.equal).
 // ----------------------------------------------------------------------------------------------------------------
 struct FinalizeParams {
     const float* pred[4];  // per part [nflip*B*P*F*Jp, 3]
@@ -2486,6 +2490,7 @@ __global__ void __launch_bounds__(256) noise_fill_kernel(const uint32_t* __restr
 // SEEDED: the step's normals come from the stream (p.key4, p.draw) instead of p.noise; everything that consumes them is the same
 template <bool SEEDED>
 __device__ __forceinline__ void finalize_body(const FinalizeParams& p) {
+#pragma clang fp contract(off)
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t total = (int64_t)p.B * p.P * p.F * p.J;
     if (e >= total) return;
@@ -2503,16 +2508,16 @@ __device__ __forceinline__ void finalize_body(const FinalizeParams& p) {
         const int part2 = p.joint_part[js], lj2 = p.joint_local[js];
         const float* u = p.pred[part2] + ((((int64_t)p.B * p.P + bp) * p.F + f) * p.Jp[part2] + lj2) * 3;
         finite = finite && isfinite(u[0]) && isfinite(u[1]) && isfinite(u[2]);
-        x0[0] = __fdiv_rn(__fadd_rn(x0[0], -u[0]), 2.0f);
-        x0[1] = __fdiv_rn(__fadd_rn(x0[1], u[1]), 2.0f);
-        x0[2] = __fdiv_rn(__fadd_rn(x0[2], u[2]), 2.0f);
+        x0[0] = (x0[0] + -u[0]) / 2.0f;
+        x0[1] = (x0[1] + u[1]) / 2.0f;
+        x0[2] = (x0[2] + u[2]) / 2.0f;
     }
     if (!finite && p.range_flag) *p.range_flag = 1;   // (every writer stores the same word: no atomic needed)
     const float lim = p.lim;
     float* o = p.out + ((((int64_t)b * p.T + p.step) * p.P + pp) * p.F + f) * p.J * 3 + j * 3;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        x0[k] = clamp_keep_nan(__fmul_rn(x0[k], p.scale), lim);
+        x0[k] = clamp_keep_nan(x0[k] * p.scale, lim);
         o[k] = x0[k];
     }
     float* im = p.img + e * 3;
@@ -2527,17 +2532,17 @@ __device__ __forceinline__ void finalize_body(const FinalizeParams& p) {
     else nz = p.noise + e * 3;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const double eps64 = __ddiv_rn(__dsub_rn(__dmul_rn(p.sr, (double)im[k]), (double)x0[k]), p.srm1);
+        const double eps64 = (p.sr * (double)im[k] - (double)x0[k]) / p.srm1;
         if (p.flip) {
             // pred_noise.float(); then fp32 tensor ops with fp64 0-dim scalars demoted to fp32
             const float eps = (float)eps64;
-            im[k] = __fadd_rn(__fadd_rn(__fmul_rn(x0[k], p.an_f), __fmul_rn(p.c_f, eps)), __fmul_rn(p.sigma_f, nz[k]));
+            im[k] = (x0[k] * p.an_f + p.c_f * eps) + p.sigma_f * nz[k];
         } else {
             // ddim_sample keeps eps in fp64 and casts img at the end (common/diffusionpose.py:264-267)
-            const double t1 = (double)__fmul_rn(x0[k], p.an_f);
-            const double t2 = __dmul_rn(p.c, eps64);
-            const double t3 = (double)__fmul_rn(p.sigma_f, nz[k]);
-            im[k] = (float)__dadd_rn(__dadd_rn(t1, t2), t3);
+            const double t1 = (double)(x0[k] * p.an_f);
+            const double t2 = p.c * eps64;
+            const double t3 = (double)(p.sigma_f * nz[k]);
+            im[k] = (float)((t1 + t2) + t3);
         }
     }
 }

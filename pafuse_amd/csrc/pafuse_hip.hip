@@ -687,6 +687,21 @@ static bool ln_folded(const pafuse_mixste2_weights* w) { return w->ste[0].qkv_lt
 // f16x2 with the LayerNorm folded: the residual stream between the blocks lives in memory as its H image only
 static bool h_residual_only(const pafuse_mixste2_weights* w) { return mode_images(w->operand_bf16) && ln_folded(w) && !w->keep_f32_residual; }
 
+// The output side of an embed launch, in ONE place (the loop, pafuse_mixste2_forward, pafuse_embed and pafuse_embed_unit): which
+// of fp32 rows / normalised rows / image / statistics embed_kernel writes for a product mode, with the first LayerNorm folded
+// into the qkv GEMM or not, for the rows [row0, row0 + nrows) of the part's token matrix.  `x`, `xn` and `image` are indexed by
+// the ABSOLUTE row; `stats` points at the pair of row row0 (the kernel indexes it by the local row).  In the image pipelines the
+// image takes the place of xn (callers that carve one buffer for both pass it twice).
+static void embed_outputs(EmbedParams& e, int mode, bool folded, bool h_only, float* x, float* xn, void* image, float* stats,
+                          int64_t row0, int64_t nrows) {
+    e.x = h_only ? nullptr : x, e.xn = xn;
+    e.stats = folded ? stats : nullptr;
+    e.xh = mode_images(mode) ? reinterpret_cast<uint8_t*>(image) : nullptr;
+    e.x_image = mode == MODE_BF16X3_IMAGES;
+    e.centre_x = mode == MODE_BF16X3 && folded;
+    e.row0 = row0, e.nrows = nrows;
+}
+
 // `training`: the training entry points make the images of the weights they multiply themselves (weights change every step)
 int check_weights(const pafuse_mixste2_weights* w, bool training = false) {
     if (!w) return fail(PAFUSE_E_ARG, "null weights");
@@ -1384,13 +1399,9 @@ int pafuse_mixste2_forward(const pafuse_mixste2_weights* w, const float* x2d, co
     e.x3d = x3d, e.x2d = x2d, e.x2d_flip = nullptr, e.joints = nullptr, e.perm = nullptr;
     e.pw = w->patch_w, e.pb = w->patch_b, e.pos = w->pos_spatial, e.temb = pb.temb;
     e.n_w = w->ste[0].norm1_w, e.n_b = w->ste[0].norm1_b, e.n_eps = 1e-6f;
-    e.x = pb.x, e.xn = pb.xn, e.stats = ln_folded(w) ? pb.stats : nullptr;
-    e.xh = mode_images(w->operand_bf16) ? reinterpret_cast<uint8_t*>(pb.xn) : nullptr;
-    e.x_image = w->operand_bf16 == MODE_BF16X3_IMAGES;
-    e.centre_x = w->operand_bf16 == MODE_BF16X3 && ln_folded(w);
-    if (h_residual_only(w)) e.x = nullptr;
+    embed_outputs(e, w->operand_bf16, ln_folded(w), h_residual_only(w), pb.x, pb.xn, pb.xn, pb.stats, 0, M);
     e.B = B, e.P = P, e.F = w->frames, e.J = w->joints, e.J3 = w->joints, e.C = w->channels, e.nflip = 1;
-    e.do_clamp = 0, e.scale = 1.f, e.lim = 1.1f, e.row0 = 0, e.nrows = M;
+    e.do_clamp = 0, e.scale = 1.f, e.lim = 1.1f;
     if ((rc = launch<embed_kernel>("embed_kernel", (unsigned)((M + EMBED_ROWS_PER_BLOCK - 1) / EMBED_ROWS_PER_BLOCK), 256, 0, s, e))) return rc;
     PAFUSE_TRACE(pb.temb, (size_t)B * w->channels * 4, s);
     PAFUSE_TRACE(pb.x, (size_t)M * w->channels * 4, s);
@@ -1569,14 +1580,11 @@ static int d3dp_sample_impl(const pafuse_d3dp_config* cfg, const pafuse_ddim_ste
             e.x3d = img, e.x2d = x2d, e.x2d_flip = x2d_flip, e.joints = cfg->part_joints[i], e.perm = cfg->flip_perm;
             e.pw = w->patch_w, e.pb = w->patch_b, e.pos = w->pos_spatial, e.temb = pb[i].temb;
             e.n_w = w->ste[0].norm1_w, e.n_b = w->ste[0].norm1_b, e.n_eps = 1e-6f;
-            e.x = pb[i].x, e.xn = pb[i].xn;
-            e.stats = ln_folded(w) ? pb[i].stats + row0 * 2 : nullptr;   // where offset_rows puts this group's statistics
-            e.xh = mode_images(w->operand_bf16) ? reinterpret_cast<uint8_t*>(pb[i].xn) : nullptr;   // (indexed by the absolute row)
-            e.x_image = w->operand_bf16 == MODE_BF16X3_IMAGES;
-            e.centre_x = w->operand_bf16 == MODE_BF16X3 && ln_folded(w);
-            if (h_residual_only(w)) e.x = nullptr;
+            // (the statistics go where offset_rows puts this group's; rows and image are indexed by the absolute row)
+            embed_outputs(e, w->operand_bf16, ln_folded(w), h_residual_only(w), pb[i].x, pb[i].xn, pb[i].xn,
+                          ln_folded(w) ? pb[i].stats + row0 * 2 : nullptr, row0, nrows);
             e.B = B, e.P = P, e.F = F, e.J = w->joints, e.J3 = J, e.C = w->channels, e.nflip = nflip;
-            e.do_clamp = 1, e.scale = (float)cfg->scale, e.lim = (float)(1.1 * cfg->scale), e.row0 = row0, e.nrows = nrows;
+            e.do_clamp = 1, e.scale = (float)cfg->scale, e.lim = (float)(1.1 * cfg->scale);
             if ((rc = launch<embed_kernel>("embed_kernel", (unsigned)((nrows + EMBED_ROWS_PER_BLOCK - 1) / EMBED_ROWS_PER_BLOCK), 256, 0, ls, e))) break;
             if (!together) rc = run_mixste_layers(w, offset_rows(pb[i], row0, w->channels), r1 - r0, ls);
         }
@@ -1656,12 +1664,12 @@ int pafuse_d3dp_lanes(const pafuse_d3dp_config* cfg, int32_t B, int32_t P, int32
     return lanes < 1 + n_aux ? lanes : 1 + n_aux;  // distinct streams in use (lane 0 = the caller's stream)
 }
 
-int pafuse_embed(const float* x3d, const float* x2d, const float* x2d_flip, const int32_t* joints, const int32_t* perm,
-                 const float* patch_w, const float* patch_b, const float* pos_spatial, const float* temb,
-                 const float* norm_w, const float* norm_b, float norm_eps, int32_t B, int32_t P, int32_t F, int32_t J,
-                 int32_t J3, int32_t C, int32_t nflip, int32_t do_clamp, double scale, float* x, float* xn, void* stream) {
-    StreamDevice on_stream_device(stream);
-    if (!x3d || !x2d || !patch_w || !patch_b || !pos_spatial || !temb || !norm_w || !norm_b || !x || !xn)
+// operands shared by pafuse_embed and pafuse_embed_unit, checked before anything is launched; fills the input side of `e`
+static int embed_inputs(EmbedParams& e, const float* x3d, const float* x2d, const float* x2d_flip, const int32_t* joints,
+                        const int32_t* perm, const float* patch_w, const float* patch_b, const float* pos_spatial, const float* temb,
+                        const float* norm_w, const float* norm_b, float norm_eps, int B, int P, int F, int J, int J3, int C, int nflip,
+                        int do_clamp, double scale) {
+    if (!x3d || !x2d || !patch_w || !patch_b || !pos_spatial || !temb || !norm_w || !norm_b)
         return fail(PAFUSE_E_ARG, "embed: null pointer");
     if (B <= 0 || P <= 0 || F <= 0 || J <= 0 || J3 < J || (nflip != 1 && nflip != 2))
         return fail(PAFUSE_E_ARG, "embed: bad size (B=%d P=%d F=%d J=%d J3=%d nflip=%d)", B, P, F, J, J3, nflip);
@@ -1669,16 +1677,59 @@ int pafuse_embed(const float* x3d, const float* x2d, const float* x2d_flip, cons
     if (J3 != J && !joints) return fail(PAFUSE_E_ARG, "embed: a part of %d joints out of %d needs its joint list", J, J3);
     if (C % 4 || C <= 0 || C > EMBED_NV * 128) return fail(PAFUSE_E_SHAPE, "embed: C=%d (need %%4, <= %d)", C, EMBED_NV * 128);
     if (do_clamp && !(scale > 0.0)) return fail(PAFUSE_E_ARG, "embed: scale must be positive");
-    EmbedParams e{};
     e.x3d = x3d, e.x2d = x2d, e.x2d_flip = x2d_flip, e.joints = joints, e.perm = perm;
     e.pw = patch_w, e.pb = patch_b, e.pos = pos_spatial, e.temb = temb;
-    e.n_w = norm_w, e.n_b = norm_b, e.n_eps = norm_eps, e.x = x, e.xn = xn;
+    e.n_w = norm_w, e.n_b = norm_b, e.n_eps = norm_eps;
     e.B = B, e.P = P, e.F = F, e.J = J, e.J3 = J3, e.C = C, e.nflip = nflip, e.do_clamp = do_clamp;
     e.scale = (float)scale, e.lim = (float)(1.1 * scale);
-    e.row0 = 0, e.nrows = (int64_t)nflip * B * P * F * J;
+    return PAFUSE_OK;
+}
+
+static int launch_embed(const EmbedParams& e, hipStream_t s) {
     const int64_t blocks = (e.nrows + EMBED_ROWS_PER_BLOCK - 1) / EMBED_ROWS_PER_BLOCK;
     if (blocks > 0x7fffffff) return fail(PAFUSE_E_ARG, "embed: grid out of range");
-    return launch<embed_kernel>("embed_kernel", (unsigned)blocks, 256, 0, (hipStream_t)stream, e);
+    return launch<embed_kernel>("embed_kernel", (unsigned)blocks, 256, 0, s, e);
+}
+
+int pafuse_embed(const float* x3d, const float* x2d, const float* x2d_flip, const int32_t* joints, const int32_t* perm,
+                 const float* patch_w, const float* patch_b, const float* pos_spatial, const float* temb,
+                 const float* norm_w, const float* norm_b, float norm_eps, int32_t B, int32_t P, int32_t F, int32_t J,
+                 int32_t J3, int32_t C, int32_t nflip, int32_t do_clamp, double scale, float* x, float* xn, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!x || !xn) return fail(PAFUSE_E_ARG, "embed: null pointer");
+    EmbedParams e{};
+    if (int rc = embed_inputs(e, x3d, x2d, x2d_flip, joints, perm, patch_w, patch_b, pos_spatial, temb, norm_w, norm_b, norm_eps, B, P,
+                              F, J, J3, C, nflip, do_clamp, scale))
+        return rc;
+    embed_outputs(e, MODE_F32, false, false, x, xn, nullptr, nullptr, 0, (int64_t)nflip * B * P * F * J);
+    return launch_embed(e, (hipStream_t)stream);
+}
+
+int pafuse_embed_unit(const pafuse_embed_args* a, void* stream) {
+    StreamDevice on_stream_device(stream);
+    if (!a) return fail(PAFUSE_E_ARG, "embed_unit: null arguments");
+    EmbedParams e{};
+    if (int rc = embed_inputs(e, a->x3d, a->x2d, a->x2d_flip, a->joints, a->perm, a->patch_w, a->patch_b, a->pos_spatial, a->temb,
+                              a->norm_w, a->norm_b, a->norm_eps, a->B, a->P, a->F, a->J, a->J3, a->C, a->nflip, a->do_clamp, a->scale))
+        return rc;
+    const int mode = a->operand_bf16;
+    if (!mode_valid(mode)) return fail(PAFUSE_E_ARG, "embed_unit: matrix-product mode %d", mode);
+    const bool folded = a->ln_folded != 0, h_only = a->h_residual_only != 0, img = mode_images(mode);
+    if (folded && !mode_split(mode)) return fail(PAFUSE_E_ARG, "embed_unit: the folded LayerNorm exists in the split-precision modes only");
+    if (h_only && !(img && folded)) return fail(PAFUSE_E_ARG, "embed_unit: the H-residual-only form is an image pipeline with the LayerNorm folded");
+    const int64_t M = (int64_t)a->nflip * a->B * a->P * a->F * a->J;
+    if (a->row0 < 0 || a->nrows < 1 || a->row0 > M - a->nrows)
+        return fail(PAFUSE_E_ARG, "embed_unit: rows [%lld, %lld + %lld) outside the %lld rows of the token matrix", (long long)a->row0,
+                    (long long)a->row0, (long long)a->nrows, (long long)M);
+    if (img && a->C % (mode == MODE_BF16X3_IMAGES ? 32 : 8))
+        return fail(PAFUSE_E_SHAPE, "embed_unit: C=%d: an %s image has rows of whole %d-element blocks", a->C,
+                    mode == MODE_BF16X3_IMAGES ? "X" : "H", mode == MODE_BF16X3_IMAGES ? 32 : 8);
+    if (!h_only && !a->x) return fail(PAFUSE_E_ARG, "embed_unit: no x");
+    if (img && !a->image) return fail(PAFUSE_E_ARG, "embed_unit: mode %d writes an image: no image", mode);
+    if (!img && !folded && !a->xn) return fail(PAFUSE_E_ARG, "embed_unit: no xn");
+    if (folded && !a->stats) return fail(PAFUSE_E_ARG, "embed_unit: the folded LayerNorm writes statistics: no stats");
+    embed_outputs(e, mode, folded, h_only, a->x, a->xn, a->image, a->stats, a->row0, a->nrows);
+    return launch_embed(e, (hipStream_t)stream);
 }
 
 int pafuse_ddim_finalize(const float* const* pred, const int32_t* part_joints, int32_t num_parts, const int32_t* joint_part,

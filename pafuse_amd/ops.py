@@ -371,28 +371,24 @@ def block_forward(block_params, x, heads=8, precision="f32"):
     return y
 
 
-def time_embed(model, t):
-    """MixSTE2.time_mlp(t) for a pafuse_amd.MixSTE2."""
+def time_embed(model, t, out=None):
+    """MixSTE2.time_mlp(t) for a pafuse_amd.MixSTE2 (into `out` [B,C] when given)."""
     lib = _lib.load()
     w = model.weights_struct()
     _need(t.dim() == 1, "time_embed: t must be [B]")
     t = t.contiguous().long()
-    out = torch.empty(t.shape[0], model.embed_dim, device=t.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(t.shape[0], model.embed_dim, device=t.device, dtype=torch.float32)
+    _need(out.is_cuda and out.device == t.device and out.dtype == torch.float32 and out.is_contiguous() and
+          tuple(out.shape) == (t.shape[0], model.embed_dim), "time_embed: out must be a contiguous fp32 [B,C] on the device of t")
     hid = torch.empty(t.shape[0], 2 * model.embed_dim, device=t.device, dtype=torch.float32)
     with torch.cuda.device(t.device):
         _lib.check(lib.pafuse_time_embed(C.byref(w), t.data_ptr(), t.shape[0], out.data_ptr(), hid.data_ptr(), _stream(t)))
     return out
 
 
-def embed(x3d, x2d, patch_w, patch_b, pos_spatial, temb, norm_w, norm_b, norm_eps=1e-6, joints=None, perm=None,
-          x2d_flip=None, do_clamp=False, scale=1.0):
-    """Input stage of one body part (pafuse_embed, include/pafuse_hip.h): clamp / scale / flip / part gather of the
-    noised 3-D pose, 2-D broadcast over P, Linear(5->C) + pos-embed + time-embed -> x, and LayerNorm(x) -> xn.
-
-    x3d [B,P,F,J3,3], x2d [B,F,J3,2]; ``joints`` = this part's indices into the J3 axis (None: all joints);
-    ``x2d_flip`` + ``perm`` switch on the flipped half (rows of the second half).  Returns (x, xn) as
-    [nflip, B, P, F, J, C]."""
-    lib = _lib.load()
+def _embed_operands(x3d, x2d, patch_w, patch_b, pos_spatial, temb, norm_w, norm_b, joints, perm, x2d_flip):
+    """host checks shared by embed and embed_unit -> (B, P, F, J, J3, C, nflip, {name: pointer of an index table})"""
     B, P, F, J3, _ = x3d.shape
     Cc = patch_w.shape[0]
     nflip = 2 if x2d_flip is not None else 1
@@ -408,6 +404,20 @@ def embed(x3d, x2d, patch_w, patch_b, pos_spatial, temb, norm_w, norm_b, norm_ep
             idx[name] = t.data_ptr()
     if nflip == 2:
         _need(perm is not None and tuple(x2d_flip.shape) == (B, F, J3, 2), "embed: the flipped half needs perm and x2d_flip")
+    return B, P, F, J, J3, Cc, nflip, idx
+
+
+def embed(x3d, x2d, patch_w, patch_b, pos_spatial, temb, norm_w, norm_b, norm_eps=1e-6, joints=None, perm=None,
+          x2d_flip=None, do_clamp=False, scale=1.0):
+    """Input stage of one body part (pafuse_embed, include/pafuse_hip.h): clamp / scale / flip / part gather of the
+    noised 3-D pose, 2-D broadcast over P, Linear(5->C) + pos-embed + time-embed -> x, and LayerNorm(x) -> xn.
+
+    x3d [B,P,F,J3,3], x2d [B,F,J3,2]; ``joints`` = this part's indices into the J3 axis (None: all joints);
+    ``x2d_flip`` + ``perm`` switch on the flipped half (rows of the second half).  Returns (x, xn) as
+    [nflip, B, P, F, J, C]."""
+    lib = _lib.load()
+    B, P, F, J, J3, Cc, nflip, idx = _embed_operands(x3d, x2d, patch_w, patch_b, pos_spatial, temb, norm_w, norm_b, joints, perm,
+                                                     x2d_flip)
     x = torch.empty(nflip, B, P, F, J, Cc, device=x3d.device, dtype=torch.float32)
     xn = torch.empty_like(x)
     with torch.cuda.device(x3d.device):
@@ -417,6 +427,60 @@ def embed(x3d, x2d, patch_w, patch_b, pos_spatial, temb, norm_w, norm_b, norm_ep
                                     _ptr(norm_b, "norm_b"), float(norm_eps), B, P, F, J, J3, Cc, nflip, int(do_clamp),
                                     float(scale), x.data_ptr(), xn.data_ptr(), _stream(x3d)))
     return x, xn
+
+
+def embed_unit(x3d, x2d, patch_w, patch_b, pos_spatial, temb, norm_w, norm_b, norm_eps=1e-6, joints=None, perm=None,
+               x2d_flip=None, do_clamp=False, scale=1.0, precision="f32", folded=False, h_residual_only=False, window=None,
+               out=None):
+    """The embed stage in the output form the sampling loop launches for (precision, folded, h_residual_only), over the rows
+    ``window`` = (row0, nrows) of the token matrix (None: all M = nflip B P F J rows) - pafuse_embed_unit, which maps the
+    three to the kernel's outputs through the loop's own host function.  Operands as :func:`embed`.
+
+    Returns a dict of what the form writes: ``x`` [M,C] (the centred rows in folded 'bf16x3'; absent with h_residual_only),
+    ``xn`` [M,C] (unfolded 'f32' / 'bf16' / 'bf16x3'), ``image`` (uint8: the H image in 'f16x2', 4 M C bytes, the X image in
+    'bf16x3_images', 6 M C bytes, of the normalised row - folded: of the centred row), ``stats`` [nrows,2] (folded: mean, rstd).
+    x, xn and image cover ALL M rows and only the window's rows are written; ``out`` may supply any of the buffers (name ->
+    tensor; an ``x`` given with h_residual_only is handed to the library, which must leave it alone)."""
+    lib = _lib.load()
+    B, P, F, J, J3, Cc, nflip, idx = _embed_operands(x3d, x2d, patch_w, patch_b, pos_spatial, temb, norm_w, norm_b, joints, perm,
+                                                     x2d_flip)
+    _need(precision in PRECISIONS, f"embed_unit: precision must be one of {sorted(PRECISIONS)}")
+    mode = PRECISIONS[precision]
+    M = nflip * B * P * F * J
+    row0, nrows = (0, M) if window is None else (int(window[0]), int(window[1]))
+    _need(0 <= row0 and 1 <= nrows and row0 + nrows <= M, f"embed_unit: window ({row0}, {nrows}) outside the {M} rows")
+    images = mode in IMAGE_BYTES
+    _need(not folded or mode >= MODE_BF16X3, "embed_unit: the folded LayerNorm exists in 'bf16x3', 'f16x2' and 'bf16x3_images' only")
+    _need(not h_residual_only or (images and folded), "embed_unit: h_residual_only is a folded image pipeline's form")
+    _need(not images or Cc % (8 if mode == MODE_F16X2 else 32) == 0, f"embed_unit: no {precision} image at C = {Cc}")
+    given = dict(out or {})
+    _need(set(given) <= {"x", "xn", "image", "stats"}, "embed_unit: out holds x / xn / image / stats")
+    dev = x3d.device
+    want = {"x": not h_residual_only, "xn": not images and not folded, "image": images, "stats": bool(folded)}
+    shapes = {"x": ((M, Cc), torch.float32), "xn": ((M, Cc), torch.float32),
+              "image": ((M * Cc * IMAGE_BYTES.get(mode, 0),), torch.uint8), "stats": ((nrows, 2), torch.float32)}
+    bufs = {}
+    for name, (shape, dtype) in shapes.items():
+        t = given.get(name)
+        if t is None and want[name]:
+            t = torch.empty(shape, device=dev, dtype=dtype)
+        if t is not None:
+            _need(t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape,
+                  f"embed_unit: {name} must be a contiguous {dtype} tensor {shape} on {dev}")
+            bufs[name] = t
+    a = _lib.EmbedArgs()
+    a.x3d, a.x2d, a.x2d_flip = _ptr(x3d, "x3d"), _ptr(x2d, "x2d"), _ptr(x2d_flip, "x2d_flip") if nflip == 2 else None
+    a.joints, a.perm = idx.get("joints"), idx.get("perm")
+    a.patch_w, a.patch_b, a.pos_spatial, a.temb = _ptr(patch_w, "patch_w"), _ptr(patch_b, "patch_b"), _ptr(pos_spatial, "pos"), _ptr(temb, "temb")
+    a.norm_w, a.norm_b, a.norm_eps = _ptr(norm_w, "norm_w"), _ptr(norm_b, "norm_b"), float(norm_eps)
+    a.B, a.P, a.F, a.J, a.J3, a.C, a.nflip, a.do_clamp, a.scale = B, P, F, J, J3, Cc, nflip, int(do_clamp), float(scale)
+    a.operand_bf16, a.ln_folded, a.h_residual_only = mode, int(bool(folded)), int(bool(h_residual_only))
+    for name, t in bufs.items():
+        setattr(a, name, t.data_ptr())
+    a.row0, a.nrows = row0, nrows
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_embed_unit(C.byref(a), _stream(x3d)))
+    return {name: t for name, t in bufs.items() if want[name]}
 
 
 def ddim_finalize(preds, joint_part, joint_local, img, step_scalars, noise=None, flip_perm=None, scale=1.0, T=1, step=0,

@@ -54,11 +54,14 @@ def test_struct_layouts_match_header_sizes():
     # pafuse_rowln_args and pafuse_lnb_args are filled field by field from Python: every field's offset is checked, not only the size
     rowln = [f for f, _ in _lib.RowLNArgs._fields_]
     lnb = [f for f, _ in _lib.LnbArgs._fields_]
+    emb = [f for f, _ in _lib.EmbedArgs._fields_]
     src = '#include "pafuse_hip.h"\n#include <stddef.h>\n#include <stdio.h>\nint main(){printf("%zu %zu %zu %zu %zu %zu",' \
           'sizeof(pafuse_block_weights),sizeof(pafuse_mixste2_weights),sizeof(pafuse_d3dp_config),' \
           'sizeof(pafuse_ddim_step),sizeof(pafuse_rowln_args),sizeof(pafuse_lnb_args));' + \
           "".join(f'printf(" %zu",offsetof(pafuse_rowln_args,{f}));' for f in rowln) + \
-          "".join(f'printf(" %zu",offsetof(pafuse_lnb_args,{f}));' for f in lnb) + 'printf("\\n");return 0;}'
+          "".join(f'printf(" %zu",offsetof(pafuse_lnb_args,{f}));' for f in lnb) + \
+          'printf(" %zu",sizeof(pafuse_embed_args));' + \
+          "".join(f'printf(" %zu",offsetof(pafuse_embed_args,{f}));' for f in emb) + 'printf("\\n");return 0;}'
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
@@ -66,7 +69,9 @@ def test_struct_layouts_match_header_sizes():
     assert sizes[:6] == [ctypes.sizeof(_lib.BlockWeights), ctypes.sizeof(_lib.MixSTE2Weights), ctypes.sizeof(_lib.D3DPConfig),
                          ctypes.sizeof(_lib.DDIMStep), ctypes.sizeof(_lib.RowLNArgs), ctypes.sizeof(_lib.LnbArgs)]
     assert sizes[6:6 + len(rowln)] == [getattr(_lib.RowLNArgs, f).offset for f in rowln]
-    assert sizes[6 + len(rowln):] == [getattr(_lib.LnbArgs, f).offset for f in lnb]
+    at = 6 + len(rowln) + len(lnb)
+    assert sizes[6 + len(rowln):at] == [getattr(_lib.LnbArgs, f).offset for f in lnb]
+    assert sizes[at] == ctypes.sizeof(_lib.EmbedArgs) and sizes[at + 1:] == [getattr(_lib.EmbedArgs, f).offset for f in emb]
 
 
 def test_state_dict_layout_matches_reference():
