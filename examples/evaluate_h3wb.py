@@ -10,7 +10,9 @@ flip-TTA DDIM sampling on the HIP path -> J-Best / P-Best / P-Agg / J-Agg and th
 `ft2d.p2=True` adds Protocol #2 (P-MPJPE after similarity alignment) to the log, as in the reference.
 Trailing `a.b=c` arguments override the config tree like the reference's Hydra command line (pafuse_amd/config.py).
 `--frames` scores one pose per video frame instead (`--aggregate`, `--stride`, `--trajectory [R]`, `--seam-profile`): position,
-velocity, acceleration, root and part-based errors of the per-frame output (harness.evaluate_frames).
+velocity, acceleration, root and part-based errors of the per-frame output (harness.evaluate_frames).  `--estimate-focal` (with
+`--frames --trajectory`) fits and scores the root with the focal length estimated from each video and prints the estimate against
+the true one per video (H3WB knows its intrinsics: this is how the estimator can be measured).
 Without `--data` the synthetic H3WB files of tests/golden/h3wb_synth are used (random weights: numbers are meaningless).
 """
 import argparse
@@ -50,9 +52,14 @@ def main():
                     help="with --frames: slide the window with this stride and pool overlapping windows (default: clips end to end)")
     ap.add_argument("--trajectory", nargs="?", type=int, const=0, default=None, metavar="R",
                     help="with --frames: also fit the camera-space root and score it; R (1 .. 64) smooths it along the frames")
+    ap.add_argument("--estimate-focal", action="store_true",
+                    help="with --frames --trajectory: fit and score the root with the focal length estimated from each video, and "
+                         "print the estimate against the true one per video")
     ap.add_argument("--seam-profile", action="store_true", help="with --frames: the position error by the frame's position in the clip")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.estimate_focal and not (a.frames and a.trajectory is not None):
+        ap.error("--estimate-focal needs --frames --trajectory")
     args = config.load(a.config or None, a.overrides)
     world, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
@@ -85,7 +92,8 @@ def main():
     if a.frames:
         h3wb.evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, aggregate=a.aggregate, stride=a.stride,
                              trajectory=None if a.trajectory is None else (a.trajectory or True), log=log,
-                             hypothesis_chunk=a.hypothesis_chunk, p2=bool(args.ft2d.p2), seam_profile=a.seam_profile)
+                             hypothesis_chunk=a.hypothesis_chunk, p2=bool(args.ft2d.p2), seam_profile=a.seam_profile,
+                             focal="estimate" if a.estimate_focal else None)
     else:
         h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
                       batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),

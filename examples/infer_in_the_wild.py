@@ -36,6 +36,14 @@ values say the focal length is wrong), and test_3d_output_postprocess.npy is the
 rebased height.  --smooth-trajectory R (1 .. 64) also runs a confidence-weighted local-linear filter of radius R frames over the
 trajectory (frames without a fit are filled from their neighbours): _traj.npy then holds the filtered roots and _traj_raw.npy
 the per-frame fit.  With --stride the fit runs inside infer_sequence; without, on the stitched poses (harness.fit_trajectory).
+
+--estimate-focal (with --aggregate mean) estimates the focal length from the video itself: one value for the whole video from the
+mean poses and the detections (harness.estimate_focal; square pixels and the principal point at the image centre are assumed).  It
+writes test_3d_output_focal.json: per step the focal length in pixels (f * width / 2), r2 - the fraction of the perspective signal
+the estimate explains - and the number of frames it rests on.  --trajectory then needs no number: the root is fitted with the
+estimate of the last step (a number given all the same is not read).  The estimate inherits a depth-scale error of the lifted pose
+one for one, and a single frame or a distant person carries little signal - look at r2 and frames.  null in the file: no estimate,
+and then the trajectory is NaN.
 """
 import argparse
 import json
@@ -82,17 +90,23 @@ def main():
     ap.add_argument("--stride", type=int, default=None, metavar="S",
                     help="with --aggregate mean or --reproj-fit: slide the window over the video with this stride (1 .. clip length) "
                          "and pool the windows covering a frame on the device: one pose per video frame, no seam at the clip borders")
-    ap.add_argument("--trajectory", type=float, default=None, metavar="FOCAL_PX",
+    ap.add_argument("--trajectory", type=float, default=None, nargs="?", const=0.0, metavar="FOCAL_PX",
                     help="with --aggregate mean: fit the camera-space root of every frame's pose on the device from the detections, "
                          "their confidences and this focal length in pixels; writes test_3d_output_traj.npy and _traj_resid.npy, "
-                         "and the post-processed poses move with it")
+                         "and the post-processed poses move with it (with --estimate-focal the number may be left out)")
     ap.add_argument("--smooth-trajectory", type=int, default=None, metavar="R",
                     help="with --trajectory: a confidence-weighted local-linear filter of radius R frames (1 .. 64) over the fitted "
                          "roots; the per-frame fit goes to test_3d_output_traj_raw.npy")
+    ap.add_argument("--estimate-focal", action="store_true",
+                    help="with --aggregate mean: estimate the focal length from the mean poses and the detections on the device and "
+                         "write it, in pixels, with r2 and the frame count to test_3d_output_focal.json; --trajectory then fits "
+                         "the root with the estimate and needs no number")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
-    if a.trajectory is not None and (a.aggregate != "mean" or not a.trajectory > 0):
-        ap.error("--trajectory takes a positive focal length in pixels and needs --aggregate mean (one pose per frame)")
+    if a.estimate_focal and a.aggregate != "mean":
+        ap.error("--estimate-focal needs --aggregate mean (one pose per frame)")
+    if a.trajectory is not None and (a.aggregate != "mean" or not (a.trajectory > 0 or a.estimate_focal)):
+        ap.error("--trajectory takes a positive focal length in pixels (or --estimate-focal) and needs --aggregate mean (one pose per frame)")
     if a.smooth_trajectory is not None and (a.trajectory is None or not 1 <= a.smooth_trajectory <= 64):
         ap.error("--smooth-trajectory takes a radius in 1 .. 64 and needs --trajectory")
     if a.stride is not None and a.aggregate == "none" and a.reproj_fit is None:
@@ -130,7 +144,9 @@ def main():
     save = lambda name, t: np.save(os.path.join(a.out, name), t.numpy(), allow_pickle=True)
     # screen-normalised coordinates: x in [-1, 1] over the width, the image centre at (0, 0), one scale for both axes
     pinhole = lambda focal: np.array([2 * focal / a.width, 2 * focal / a.width, 0, 0, 0, 0, 0, 0, 0], dtype=np.float32)
-    traj = None
+    traj = focal = None
+    # the camera of the trajectory: the given focal length, or (cam=None) the estimate with square pixels and a centred principal point
+    camera = dict(focal="estimate") if a.estimate_focal else dict(cam=None if a.trajectory is None else pinhole(a.trajectory))
     if a.reproj_fit is not None:
         cam = pinhole(a.reproj_fit)
         pick = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="reproj_fit",
@@ -153,8 +169,8 @@ def main():
         if a.aggregate == "none":        # the chunk and the spread belonged to the pick
             a.hypothesis_chunk = a.spread = None
     if a.aggregate == "mean" and a.stride is not None:
-        wanted = {} if a.trajectory is None else dict(cam=pinhole(a.trajectory), conf=conf,
-                                                      trajectory=True if a.smooth_trajectory is None else a.smooth_trajectory)
+        wanted = {} if a.trajectory is None else dict(conf=conf, trajectory=True if a.smooth_trajectory is None else a.smooth_trajectory,
+                                                      **camera)
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
                                       hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride, **wanted)
         for k in ("std", "cov", "count"):
@@ -172,11 +188,20 @@ def main():
             pred = pred["pose"]
         poses = harness.stitch_poses(pred, keypoints.shape[0], model.frames)        # [T,frames,134,3]
         if a.trajectory is not None:     # consecutive clips: the fit runs on the stitched per-frame array
-            traj = harness.fit_trajectory(poses, keypoints, pinhole(a.trajectory), conf=conf, smooth=a.smooth_trajectory)
+            traj = harness.fit_trajectory(poses, keypoints, conf=conf, smooth=a.smooth_trajectory, **camera)
     else:
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch)
         poses = harness.stitch_clips(pred, keypoints.shape[0], model.frames)        # [T,P,frames,134,3]
     np.save(os.path.join(a.out, "test_3d_output.npy"), poses.numpy(), allow_pickle=True)
+    if a.estimate_focal:                 # from the fit where there was one, else on the per-frame poses alone
+        focal = traj if traj is not None else harness.estimate_focal(poses, keypoints, conf=conf)
+        number = lambda v: None if v != v else v                                    # NaN (no estimate) -> null
+        with open(os.path.join(a.out, "test_3d_output_focal.json"), "w") as f:
+            json.dump({"width": a.width, "height": a.height,
+                       "focal_px": [number(float(v) * a.width / 2) for v in focal["focal"]],
+                       "r2": [number(float(v)) for v in focal["focal_r2"]],
+                       "frames": [int(v) for v in focal["focal_frames"]]}, f, indent=1)
+        print("estimated focal length per step, pixels:", [None if v != v else round(float(v) * a.width / 2, 1) for v in focal["focal"]])
     if traj is not None:
         for k in ("traj", "traj_raw", "traj_resid"):
             if k in traj:

@@ -36,6 +36,8 @@
  *                            pooled into one pose (and spread) per video frame
  *   pafuse_frames_root_fit / pafuse_trajectory_smooth  the camera-space root of that per-frame pose, fitted from the
  *                            detections, and a confidence-weighted local-linear filter along the frames
+ *   pafuse_frames_focal_sums / pafuse_focal_solve  the focal length that fit needs, estimated from the same pose and
+ *                            detections: one value per video, with the fraction of the signal it explains
  *   pafuse_frame_errors / pafuse_frame_errors_reduce  that per-frame pose and root scored against ground truth: position,
  *                            velocity (mean_velocity_error, common/loss.py:488-497), acceleration, root and part-based errors
  *   pafuse_procrustes_errors the Protocol #2 part of it (ft2d.p2), main_h3wb.py:381-395, common/loss.py:251-458
@@ -776,6 +778,45 @@ int pafuse_frames_root_fit(const float *pose /* [T,N,J,3] whole-body, root-relat
  * outside 1 .. 64, out == traj. */
 int pafuse_trajectory_smooth(const float *traj /* [T,N,3] */, const float *weight /* [T,N] or NULL */, int32_t T, int32_t N,
                              int32_t radius /* 1..64 */, float *out /* [T,N,3], may not alias traj */, void *stream);
+
+/* The focal length of the video's camera from the finished per-frame pose and its detections, part one: the sums per
+ * (t, frame) (pafuse_amd/focal.py states the arithmetic).  Operands as pafuse_frames_root_fit, except
+ * that of cam only cx, cy = cam[2:4] and the pixel aspect rho = cam[1]/cam[0] are read: cam and cam with fx, fy doubled give
+ * the same bits.  With p = u - cx, q = (v - cy)/rho, hx = p*Z, hy = q*Z the pinhole is linear in (1/f; tx, ty, tz/f):
+ * X + tx = hx/f + (tz/f)*p, Y + ty = hy/f + (tz/f)*q.  The per-frame directions e_x, e_y and (p, q) are projected out of
+ * g = (X, Y) and h = (hx, hy) with the weights c, from thirteen sums over the joints that take part (weight > 0 and a finite
+ * pose), fp64, contraction off, every sum in the fixed order of pafuse_frames_root_fit:
+ *   K = <h_perp,h_perp>   H = <h_perp,g_perp>   G = <g_perp,g_perp>
+ * A frame takes part if at least 4 joints are in the sums, den = Spp - (Sp*Sp + Sq*Sq)/W is finite and > 0 and K, H, G are
+ * finite.
+ *   state double [T,N,4]   (K, H, G, 1.0) per (t, n); (0, 0, 0, 0) for a frame that takes no part.  States of several videos
+ *                          of one camera concatenate along N.
+ * One kernel, one wave per (t, n), no workspace, no atomics, bit-reproducible.
+ * Refused (PAFUSE_E_ARG) before any HIP call: a null pose / x2d / cam / state, T, N or J < 1, a state that is not 8-byte
+ * aligned. */
+int pafuse_frames_focal_sums(const float *pose /* [T,N,J,3] whole-body, root-relative */,
+                             const float *x2d /* [N,J,2] */, const float *conf /* [N,J] or NULL = all 1 */,
+                             const float *cam /* [>=4]: fx fy cx cy */, int32_t T, int32_t N, int32_t J,
+                             double *state /* [T,N,4] */, void *stream);
+
+/* Part two: the estimate per t.  K, H, G and the frame count are summed over n as pafuse_frame_errors_reduce sums (lane l
+ * adds frames l, l + 64, ... in ascending order, then v += v[lane ^ o] for o = 32 .. 1).  There is an estimate if the count
+ * is >= 1, K > 0 and H > 0 - h regressed ON g, the direction that survives pose noise:
+ *   focal   [T] fp32   K/H rounded once, in the units of the detections (screen-normalised: pixels = focal * width / 2); NaN
+ *                      without an estimate
+ *   r2      [T] fp32   (NULL: not wanted) (H*H)/(G*K) rounded once: the fraction of the perspective signal the line explains;
+ *                      NaN without an estimate
+ *   frames  [T] int32  (NULL: not wanted) the frames that took part
+ *   cam_out [T,cam_len] fp32  (NULL: not wanted) (focal, rho*(K/H) in fp64 rounded once, cam[2], ..., cam[cam_len-1]): the
+ *                      intrinsics to hand to pafuse_frames_root_fit.  NaN in the first two slots without an estimate, so
+ *                      that a video without one gives a NaN trajectory and not a guessed one.
+ * The estimate inherits a depth-scale error of the pose one for one, and a single frame or a distant person carries little
+ * signal: r2 and frames are what tells.  One kernel, one wave per t, bit-reproducible.
+ * Refused (PAFUSE_E_ARG) before any HIP call: a null state / cam / focal, T or N < 1, cam_len outside 4 .. 9, a state that is
+ * not 8-byte aligned. */
+int pafuse_focal_solve(const double *state /* [T,N,4] */, int32_t T, int32_t N, const float *cam /* [cam_len] */,
+                       int32_t cam_len /* 4..9 */, float *focal /* [T] */, float *r2 /* [T] or NULL */,
+                       int32_t *frames /* [T] or NULL */, float *cam_out /* [T,cam_len] or NULL */, void *stream);
 
 /* Frame-level errors of the per-frame pose against ground truth (pafuse_amd/framemetrics.py states the arithmetic):
  * pose [T,N,J,3] and gt [N,J,3] whole-body and root-relative, traj [T,N,3] / gt_root [N,3] the camera-space root (both or

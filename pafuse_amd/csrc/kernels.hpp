@@ -3754,6 +3754,149 @@ __global__ void __launch_bounds__(256) trajectory_smooth_kernel(const Trajectory
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// The focal length of the video's camera from the per-frame pose and its detections (statement:
+// pafuse_amd/focal.py).  With p = u - cx, q = (v - cy)/rho, rho = cam[1]/cam[0], hx = p*Z, hy = q*Z the pinhole is linear
+// in (1/f; tx, ty, tz/f): X + tx = hx/f + (tz/f)*p, Y + ty = hy/f + (tz/f)*q.  frames_focal_sums_kernel projects the
+// per-frame nuisance directions e_x, e_y, (p, q) out of g = (X, Y) and h = (hx, hy) with the weights c and writes
+// K = <h_perp,h_perp>, H = <h_perp,g_perp>, G = <g_perp,g_perp> per (t, n); focal_solve_kernel sums them over the frames
+// and gives f = K/H (h regressed ON g: the direction that survives pose noise) and r2 = H*H/(G*K).
+//
+// frames_focal_sums_kernel has the structure of frames_root_fit_kernel: one wave per (t, n), four per workgroup; SLOTS >= 1:
+// a lane loads pose, detection and weight of all its <= SLOTS joints (J <= 64*SLOTS) before the first butterfly and
+// keeps c, p, q, X, Y, Z of each in registers; the thirteen sums and the int count go through independent butterfly
+// chains, interleaved step by step.  A joint takes part if its weight is > 0 and its pose finite (the rule of the root
+// fit); a lane or slot without such a joint feeds 0.0 by a select.  SLOTS == 0 is the same arithmetic for any J, round by
+// round.  fp64, contraction off, every product rounded before it is added.  No LDS, no atomics, no scratch.
+// A frame takes part if >= 4 joints are in the sums, den is finite and > 0 and K, H, G are finite: its row is
+// (K, H, G, 1.0), otherwise (0, 0, 0, 0).
+// focal_solve_kernel: one wave per t; lane l adds frames l, l + 64, ... in ascending order, then the butterfly (the order
+// of frame_errors_reduce_kernel), four chains interleaved.
+// ----------------------------------------------------------------------------------------------------------------
+struct FramesFocalSumsParams {
+    const float* pose;    // [T,N,J,3] whole-body, root-relative
+    const float* x2d;     // [N,J,2]
+    const float* conf;    // [N,J] or null (every weight 1)
+    const float* cam;     // [>= 4]: fx fy cx cy (of fx, fy only the ratio is read)
+    double* state;        // [T,N,4]
+    int T, N, J;
+};
+
+struct FocalJoint {
+    double c, p, q, X, Y, Z;
+    int on;
+};
+constexpr int FOCAL_MIN_JOINTS = 4;
+
+template <int SLOTS>
+__global__ void __launch_bounds__(256) frames_focal_sums_kernel(const FramesFocalSumsParams p) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (int64_t)p.T * p.N) return;   // wave-uniform
+    const int n = (int)(item % p.N);
+    const int J = p.J;
+    const float* pose = p.pose + item * J * 3;
+    const float* x2 = p.x2d + (int64_t)n * J * 2;
+    const float* cf = p.conf ? p.conf + (int64_t)n * J : nullptr;
+    const double rho = (double)p.cam[1] / (double)p.cam[0], cx = (double)p.cam[2], cy = (double)p.cam[3];
+    constexpr int KEPT = SLOTS > 0 ? SLOTS : 1;
+    const int rounds = SLOTS > 0 ? SLOTS : (J + 63) / 64;
+    FocalJoint kept[KEPT];
+    auto load = [&](int j) -> FocalJoint {
+        const bool in = j < J;
+        const int jj = in ? j : 0;               // J >= 1: a lane past the end reads joint 0 and selects 0.0
+        const float cw = cf ? cf[jj] : 1.f;
+        const float u = x2[2 * jj], v = x2[2 * jj + 1];
+        const float wx = pose[3 * jj], wy = pose[3 * jj + 1], wz = pose[3 * jj + 2];
+        const bool on = in && cw > 0.f && isfinite(wx) && isfinite(wy) && isfinite(wz);
+        FocalJoint g;
+        g.c = on ? (double)cw : 0.0;
+        g.p = on ? (double)u - cx : 0.0;
+        g.q = on ? ((double)v - cy) / rho : 0.0;
+        g.X = on ? (double)wx : 0.0, g.Y = on ? (double)wy : 0.0, g.Z = on ? (double)wz : 0.0;
+        g.on = on;
+        return g;
+    };
+    auto joint = [&](int r) -> FocalJoint {
+        if constexpr (SLOTS > 0) return kept[r];
+        else return load(r * 64 + lane);
+    };
+#pragma unroll
+    for (int r = 0; r < KEPT; ++r) kept[r] = load(SLOTS > 0 ? r * 64 + lane : J);   // SLOTS == 0: unused
+    double w = 0.0, sp = 0.0, sq = 0.0, spp = 0.0, gx = 0.0, gy = 0.0, gp = 0.0, gg = 0.0;
+    double hxs = 0.0, hys = 0.0, hp = 0.0, hh = 0.0, hg = 0.0;
+    int cnt = 0;
+#pragma unroll KEPT
+    for (int r = 0; r < rounds; ++r) {
+        const FocalJoint g = joint(r);
+        const double hx = g.p * g.Z, hy = g.q * g.Z;
+        w += g.c, sp += g.c * g.p, sq += g.c * g.q, spp += g.c * (g.p * g.p + g.q * g.q);
+        gx += g.c * g.X, gy += g.c * g.Y, gp += g.c * (g.p * g.X + g.q * g.Y), gg += g.c * (g.X * g.X + g.Y * g.Y);
+        hxs += g.c * hx, hys += g.c * hy, hp += g.c * (g.p * hx + g.q * hy);
+        hh += g.c * (hx * hx + hy * hy), hg += g.c * (hx * g.X + hy * g.Y);
+        cnt += g.on;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {   // thirteen independent chains and the count, interleaved
+        const double w2 = __shfl_xor(w, o), sp2 = __shfl_xor(sp, o), sq2 = __shfl_xor(sq, o), spp2 = __shfl_xor(spp, o);
+        const double gx2 = __shfl_xor(gx, o), gy2 = __shfl_xor(gy, o), gp2 = __shfl_xor(gp, o), gg2 = __shfl_xor(gg, o);
+        const double hxs2 = __shfl_xor(hxs, o), hys2 = __shfl_xor(hys, o), hp2 = __shfl_xor(hp, o);
+        const double hh2 = __shfl_xor(hh, o), hg2 = __shfl_xor(hg, o);
+        cnt += __shfl_xor(cnt, o);
+        w += w2, sp += sp2, sq += sq2, spp += spp2, gx += gx2, gy += gy2, gp += gp2, gg += gg2;
+        hxs += hxs2, hys += hys2, hp += hp2, hh += hh2, hg += hg2;
+    }
+    const double den = spp - (sp * sp + sq * sq) / w;
+    const double rg = gp - (sp * gx + sq * gy) / w;
+    const double rh = hp - (sp * hxs + sq * hys) / w;
+    const double K = (hh - (hxs * hxs + hys * hys) / w) - (rh * rh) / den;
+    const double H = (hg - (hxs * gx + hys * gy) / w) - (rh * rg) / den;
+    const double G = (gg - (gx * gx + gy * gy) / w) - (rg * rg) / den;
+    const bool part = cnt >= FOCAL_MIN_JOINTS && isfinite(den) && den > 0.0 && isfinite(K) && isfinite(H) && isfinite(G);
+    const double v = lane == 0 ? K : lane == 1 ? H : lane == 2 ? G : 1.0;   // lane k writes slot k
+    if (lane < 4) p.state[item * 4 + lane] = part ? v : 0.0;
+}
+
+struct FocalSolveParams {
+    const double* state;  // [T,N,4]
+    const float* cam;     // [cam_len]
+    float* focal;         // [T]
+    float* r2;            // [T] or null
+    int32_t* frames;      // [T] or null
+    float* cam_out;       // [T,cam_len] or null
+    int T, N, cam_len;
+};
+
+__global__ void __launch_bounds__(256) focal_solve_kernel(const FocalSolveParams p) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= p.T) return;   // wave-uniform
+    const double* row = p.state + t * p.N * 4;
+    double K = 0.0, H = 0.0, G = 0.0, C = 0.0;
+    for (int n = lane; n < p.N; n += 64) {
+        const double* s = row + (int64_t)n * 4;
+        K += s[0], H += s[1], G += s[2], C += s[3];
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const double k2 = __shfl_xor(K, o), h2 = __shfl_xor(H, o), g2 = __shfl_xor(G, o), c2 = __shfl_xor(C, o);
+        K += k2, H += h2, G += g2, C += c2;
+    }
+    const bool ok = C >= 1.0 && K > 0.0 && H > 0.0;
+    const float qnan = __builtin_nanf("");
+    const double f = K / H;
+    if (lane == 0) p.focal[t] = ok ? (float)f : qnan;
+    if (p.r2 && lane == 1) p.r2[t] = ok ? (float)((H * H) / (G * K)) : qnan;
+    if (p.frames && lane == 2) p.frames[t] = (int32_t)C;   // a sum of 0.0 and 1.0: exact
+    if (p.cam_out && lane < p.cam_len) {
+        const double rho = (double)p.cam[1] / (double)p.cam[0];
+        const float fy = (float)(rho * f);
+        p.cam_out[t * p.cam_len + lane] = lane == 0 ? (ok ? (float)f : qnan) : lane == 1 ? (ok ? fy : qnan) : p.cam[lane];
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // Frame-level errors of the per-frame pose against ground truth (statement:
 // pafuse_amd/framemetrics.py).  pose [T,N,J,3] and gt [N,J,3] are whole-body and root-relative, traj [T,N,3] / gt_root
 // [N,3] the camera-space root (both or neither).  Every fp32 input is converted to double once, everything after that is

@@ -2188,6 +2188,43 @@ int pafuse_trajectory_smooth(const float* traj, const float* weight, int32_t T, 
     return launch<trajectory_smooth_kernel>("trajectory_smooth_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
 }
 
+// the focal-length sums of every (t, frame) of the finished pose (frames_focal_sums_kernel) and the estimate from them
+// (focal_solve_kernel): the argument checks come before the first HIP call
+int pafuse_frames_focal_sums(const float* pose, const float* x2d, const float* conf, const float* cam, int32_t T, int32_t N,
+                             int32_t J, double* state, void* stream) {
+    if (!pose || !x2d || !cam || !state) return fail(PAFUSE_E_ARG, "frames_focal_sums: pose, x2d, cam and state are needed (conf may be null)");
+    if (T < 1 || N < 1 || J < 1) return fail(PAFUSE_E_ARG, "frames_focal_sums: bad size (T=%d N=%d J=%d)", T, N, J);
+    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "frames_focal_sums: state must be 8-byte aligned");
+    const int64_t waves = (int64_t)T * N;   // one wave per (t, n), four per workgroup
+    if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "frames_focal_sums: grid out of range");
+    StreamDevice on_stream_device(stream);
+    FramesFocalSumsParams m{};
+    m.pose = pose, m.x2d = x2d, m.conf = conf, m.cam = cam, m.state = state;
+    m.T = T, m.N = N, m.J = J;
+    const unsigned grid = blocks_for(waves, 4);
+    hipStream_t s = (hipStream_t)stream;
+    switch ((J + 63) / 64) {   // the joints of a lane in registers up to J = 256; beyond, the same arithmetic round by round
+        case 1: return launch<frames_focal_sums_kernel<1>>("frames_focal_sums_kernel", grid, 256, 0, s, m);
+        case 2: return launch<frames_focal_sums_kernel<2>>("frames_focal_sums_kernel", grid, 256, 0, s, m);
+        case 3: return launch<frames_focal_sums_kernel<3>>("frames_focal_sums_kernel", grid, 256, 0, s, m);
+        case 4: return launch<frames_focal_sums_kernel<4>>("frames_focal_sums_kernel", grid, 256, 0, s, m);
+        default: return launch<frames_focal_sums_kernel<0>>("frames_focal_sums_kernel", grid, 256, 0, s, m);
+    }
+}
+
+int pafuse_focal_solve(const double* state, int32_t T, int32_t N, const float* cam, int32_t cam_len, float* focal, float* r2,
+                       int32_t* frames, float* cam_out, void* stream) {
+    if (!state || !cam || !focal) return fail(PAFUSE_E_ARG, "focal_solve: state, cam and focal are needed (r2, frames, cam_out may be null)");
+    if (T < 1 || N < 1) return fail(PAFUSE_E_ARG, "focal_solve: bad size (T=%d N=%d)", T, N);
+    if (cam_len < 4 || cam_len > 9) return fail(PAFUSE_E_ARG, "focal_solve: cam_len %d outside 4 .. 9", cam_len);
+    if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "focal_solve: state must be 8-byte aligned");
+    StreamDevice on_stream_device(stream);
+    FocalSolveParams m{};
+    m.state = state, m.cam = cam, m.focal = focal, m.r2 = r2, m.frames = frames, m.cam_out = cam_out;
+    m.T = T, m.N = N, m.cam_len = cam_len;
+    return launch<focal_solve_kernel>("focal_solve_kernel", blocks_for((int64_t)T, 4), 256, 0, (hipStream_t)stream, m);   // one wave per t
+}
+
 // the frame-level errors of the per-frame pose against ground truth (frame_errors_kernel) and their sums over the frames
 // (frame_errors_reduce_kernel): the argument checks come before the first HIP call
 static_assert(FRAME_MAX_PARTS == PAFUSE_MAX_PARTS, "frame_errors_kernel keeps one register slot per part");

@@ -250,21 +250,29 @@ def evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, batc
 
 
 def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
-                    batch_size=2, group=None, log=print, action=None, hypothesis_chunk=None, p2=False, seam_profile=False):
+                    batch_size=2, group=None, log=print, action=None, hypothesis_chunk=None, p2=False, seam_profile=False, focal=None):
     """The frame-level evaluation of every video, looped like :func:`evaluate`: harness.evaluate_frames per (camera, sequence) -
     one pose per video frame (``aggregate``, ``stride``; None: un-strided clips laid end to end), optionally its fitted
     camera-space root (``trajectory``: True or a smoothing radius) - scored on the device; the sums and counts added over the
     videos; millimetres per metric and sampling step (harness.frame_report) printed through `log` in the lines of
     harness.format_frame_report.  ``seam_profile=True`` also keeps the per-frame maps and logs the position error binned by the
     frame's position in the clip (harness.seam_profile, summed over the videos); the return value is then ``(rep, profile)``,
-    profile float64 [T, model.frames] in mm.  On synthetic weights the numbers mean nothing."""
+    profile float64 [T, model.frames] in mm.  ``focal="estimate"`` (with ``trajectory``) fits and scores the root with the focal
+    length estimated from each video (harness.estimate_focal) and logs, per video, the estimate of every step beside the true
+    cam[0], with r2 and the frames it rests on.  On synthetic weights the numbers mean nothing."""
     from . import harness
     sums = counts = prof_s = prof_c = None
-    for cam, seq_3d, seq_2d in iter_sequences(cams, poses_3d, poses_2d):
+    for video, (cam, seq_3d, seq_2d) in enumerate(iter_sequences(cams, poses_3d, poses_2d)):
         got = harness.evaluate_frames(model, dataset, seq_2d[0].astype("float32"), seq_3d[0].astype("float32"),
                                       cam[0].astype("float32"), kps_left, kps_right, aggregate=aggregate, stride=stride,
                                       trajectory=trajectory, batch_size=batch_size, group=group,
-                                      hypothesis_chunk=hypothesis_chunk, p2=p2, per_frame=seam_profile)
+                                      hypothesis_chunk=hypothesis_chunk, p2=p2, per_frame=seam_profile, focal=focal)
+        if focal is not None:
+            est = got[-1]
+            for t in range(est["focal"].shape[0]):
+                log("video %d step %d : estimated focal length %f (true %f, ratio %f), r2 %f over %d frames"
+                    % (video, t, float(est["focal"][t]), float(cam[0][0]), float(est["focal"][t]) / float(cam[0][0]),
+                       float(est["focal_r2"][t]), int(est["focal_frames"][t])))
         sums = got[0] if sums is None else {k: sums[k] + got[0][k] for k in sums}
         counts = got[1] if counts is None else {k: counts[k] + got[1][k] for k in counts}
         if seam_profile:       # the sums and the counts of the bins add over videos; the quotient is formed once

@@ -64,7 +64,7 @@ def wb_pose_from_parts(pose, dataset):
 
 @torch.no_grad()
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
-                   hypothesis_chunk=None, spread=None, conf=None, stride=None, trajectory=None):
+                   hypothesis_chunk=None, spread=None, conf=None, stride=None, trajectory=None, focal=None):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -113,13 +113,23 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     ``"traj"`` [T,N,3] (smoothed when r is given; NaN where there is no fit and nothing to fill from), ``"traj_raw"`` [T,N,3]
     when smoothed, ``"traj_weight"`` [T,N] (0: no fit) and ``"traj_resid"`` [T,N], the weighted residual of the fit in metres
     (it is what a wrong focal length shows in).  Camera-space poses are ``pose + traj[:, :, None]``.  Every rank holds the same
-    frame state and runs the same fit.  Without ``stride`` use :func:`fit_trajectory` on the stitched poses."""
+    frame state and runs the same fit.  Without ``stride`` use :func:`fit_trajectory` on the stitched poses.
+
+    ``focal="estimate"`` (with ``trajectory``; None: everything above, unchanged) estimates the focal length the fit needs from
+    the video itself - :func:`estimate_focal` on the pose that is returned - and fits the root with it: ``cam`` becomes optional
+    (None: square pixels, the principal point at the image centre; given: its principal point, aspect and distortion terms are
+    kept and its focal length is not read).  The fit runs with the estimate of the last, fully denoised step, ``"cam"[T-1]``,
+    read on the device.  Added keys: ``"focal"`` [T], ``"focal_r2"`` [T], ``"focal_frames"`` [T] and ``"cam"`` [T,9].  A video
+    without an estimate (NaN) has a NaN trajectory, not a guessed one."""
     smooth = _trajectory_radius(trajectory)
+    _focal_mode(focal)
+    if focal is not None and trajectory is None:
+        raise ValueError('focal="estimate" belongs to a trajectory (harness.estimate_focal gives the estimate alone)')
     if trajectory is not None:
         if stride is None:
             raise ValueError("trajectory needs stride (one pose per video frame); for stitched clips call harness.fit_trajectory")
-        if cam is None:
-            raise ValueError("trajectory needs cam (fx, fy, cx, cy first): the fit takes the intrinsics as known")
+        if cam is None and focal is None:
+            raise ValueError('trajectory needs cam (fx, fy, cx, cy first): the fit takes the intrinsics as known (or focal="estimate")')
     if stride is not None:
         if isinstance(stride, bool) or int(stride) != stride or not 1 <= int(stride) <= model.frames:
             raise ValueError(f"stride must be an integer in 1 .. {model.frames} (the window length), got {stride!r}")
@@ -153,7 +163,7 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     dev = next(model.parameters()).device
     if stride is not None:
         return _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                             spread, conf, int(stride), dev, trajectory is not None, smooth)
+                             spread, conf, int(stride), dev, trajectory is not None, smooth, focal)
     x2d = cut_clips(seq_2d, model.frames).to(dev)
     x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), model.frames).to(dev)
     sampler = ShardedSampler(model, group)
@@ -213,15 +223,15 @@ def cut_windows(seq, starts, frames=27):
 
 
 def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                  conf, stride, dev, trajectory=False, smooth=None):
+                  conf, stride, dev, trajectory=False, smooth=None, focal=None):
     """infer_sequence(stride=...): sliding windows pooled into one pose per video frame (arguments already checked)"""
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, dev, trajectory, smooth)
+                               spread, conf, stride, dev, trajectory, smooth, focal)
     return {k: v.cpu() for k, v in out.items()}
 
 
 def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                         conf, stride, dev, trajectory=False, smooth=None):
+                         conf, stride, dev, trajectory=False, smooth=None, focal=None):
     """_infer_frames with its result left on the device (evaluate_frames scores it there)"""
     from . import ops
     from .windows import window_starts
@@ -234,7 +244,7 @@ def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size
     x2d = cut_windows(seq_2d, starts, F).to(dev)
     x2d_flip = cut_windows(flip_2d(seq_2d, kps_left, kps_right), starts, F).to(dev)
     if reproj or trajectory:
-        cam = torch.as_tensor(cam, dtype=torch.float32).to(dev)
+        cam = _default_cam(dev) if cam is None else torch.as_tensor(cam, dtype=torch.float32).to(dev)
     if fit and conf is not None:
         conf = cut_windows(conf, starts, F).to(dev)                                    # [windows,F,J]
     elif reproj and not fit:
@@ -269,7 +279,7 @@ def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size
     out["pose"] = out.pop("pick") if reproj else out["mean"]
     out.pop("mean", None)
     if trajectory:  # the root of the pose that is returned, on the device before anything crosses to the host
-        out.update(_fit_trajectory(out["pose"], seq_2d.to(dev), cam, None if frame_conf is None else frame_conf.to(dev), smooth))
+        out.update(_fit_trajectory(out["pose"], seq_2d.to(dev), cam, None if frame_conf is None else frame_conf.to(dev), smooth, focal))
     return out
 
 
@@ -282,11 +292,43 @@ def _trajectory_radius(trajectory, name="trajectory"):
     return trajectory
 
 
-def _fit_trajectory(pose, x2d, cam, conf, smooth):
+def _focal_mode(focal):
+    if focal not in (None, "estimate"):
+        raise ValueError(f'focal must be None (cam holds it) or "estimate", got {focal!r}')
+
+
+def _default_cam(dev):
+    """the intrinsics of a camera nothing is known of, for screen-normalised detections: square pixels, the principal point at the
+    image centre, no distortion (the focal slots are placeholders: estimate_focal reads only their ratio)"""
+    return torch.tensor([1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+
+
+def _cam9(cam, dev):
+    """cam (None, or 4 .. 9 values, fx fy cx cy first) -> [9] fp32 on the device, the missing distortion terms 0"""
+    if cam is None:
+        return _default_cam(dev)
+    cam = torch.as_tensor(cam, dtype=torch.float32).reshape(-1)
+    if not 4 <= cam.numel() <= 9:
+        raise ValueError(f"cam holds 4 .. 9 values (fx fy cx cy, then the distortion terms), got {cam.numel()}")
+    return torch.cat([cam, cam.new_zeros(9 - cam.numel())]).to(dev)
+
+
+def _estimate_focal(pose, x2d, cam, conf):
+    """device tensors -> the focal keys of infer_sequence / fit_trajectory / estimate_focal, on the device"""
+    from . import ops
+    m = ops.estimate_focal(pose.contiguous(), x2d.contiguous(), cam.contiguous(), conf=None if conf is None else conf.contiguous())
+    return {"focal": m["focal"], "focal_r2": m["r2"], "focal_frames": m["frames"], "cam": m["cam"]}
+
+
+def _fit_trajectory(pose, x2d, cam, conf, smooth, focal=None):
     """device tensors -> the trajectory keys of infer_sequence / fit_trajectory, on the device"""
     from . import ops
+    est = {}
+    if focal is not None:       # the estimate of the last, fully denoised step: a row of the device tensor, no host round trip
+        est = _estimate_focal(pose, x2d, _cam9(cam, pose.device), conf)
+        cam = est["cam"][est["cam"].shape[0] - 1]
     m = ops.fit_trajectory(pose.contiguous(), x2d.contiguous(), cam.contiguous(), conf=None if conf is None else conf.contiguous())
-    out = {"traj": m["traj"], "traj_weight": m["wsum"], "traj_resid": m["resid"]}
+    out = {"traj": m["traj"], "traj_weight": m["wsum"], "traj_resid": m["resid"], **est}
     if smooth is not None:
         out["traj_raw"] = m["traj"]
         out["traj"] = ops.smooth_trajectory(m["traj"], m["wsum"], smooth)
@@ -294,21 +336,25 @@ def _fit_trajectory(pose, x2d, cam, conf, smooth):
 
 
 @torch.no_grad()
-def fit_trajectory(poses, seq_2d, cam, conf=None, smooth=None, device="cuda"):
+def fit_trajectory(poses, seq_2d, cam=None, conf=None, smooth=None, device="cuda", focal=None):
     """The camera-space root trajectory of per-frame poses: ``poses`` [T,N,J,3] whole-body and root-relative - an
     ``infer_sequence(stride=...)["pose"]`` or the result of :func:`stitch_poses` - ``seq_2d`` [N,J,2] the screen-normalised
     detections they were lifted from, ``cam`` the intrinsics (fx, fy, cx, cy first), ``conf`` [N,J] the detections' weights
     (None: all 1).  Fitted on the device per (t, frame) (pafuse_amd.trajectory; ops.fit_trajectory); ``smooth=r`` (1 .. 64)
     also runs the local-linear filter of that radius along the frames (ops.smooth_trajectory).  Returns a dict of CPU tensors:
     ``"traj"`` [T,N,3] (smoothed when ``smooth`` is given), ``"traj_raw"`` when smoothed, ``"traj_weight"`` [T,N] and
-    ``"traj_resid"`` [T,N] - the keys ``infer_sequence(trajectory=...)`` adds.  Camera-space poses: ``poses + traj[:, :, None]``."""
+    ``"traj_resid"`` [T,N] - the keys ``infer_sequence(trajectory=...)`` adds.  Camera-space poses: ``poses + traj[:, :, None]``.
+    ``focal="estimate"``: the focal length is estimated from the poses and detections (:func:`estimate_focal`) and the fit runs
+    with the estimate of the last step; ``cam`` is then optional, and ``"focal"``, ``"focal_r2"``, ``"focal_frames"`` [T] and
+    ``"cam"`` [T,9] are added."""
+    _focal_mode(focal)
     if smooth is True:
         raise ValueError("smooth must be None or a smoothing radius in 1 .. 64")
     smooth = _trajectory_radius(smooth, "smooth")
     poses = torch.as_tensor(poses, dtype=torch.float32)
     seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
-    if cam is None:
-        raise ValueError("fit_trajectory needs cam (fx, fy, cx, cy first)")
+    if cam is None and focal is None:
+        raise ValueError('fit_trajectory needs cam (fx, fy, cx, cy first), or focal="estimate"')
     if poses.dim() != 4 or poses.shape[-1] != 3 or tuple(seq_2d.shape) != (*poses.shape[1:3], 2):
         raise ValueError(f"poses must be [T,N,J,3] and seq_2d [N,J,2], got {tuple(poses.shape)} and {tuple(seq_2d.shape)}")
     if conf is not None:
@@ -316,8 +362,34 @@ def fit_trajectory(poses, seq_2d, cam, conf=None, smooth=None, device="cuda"):
         if tuple(conf.shape) != tuple(seq_2d.shape[:2]):
             raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[:2])}, got {tuple(conf.shape)}")
     dev = poses.device if poses.is_cuda else torch.device(device)
-    cam = torch.as_tensor(cam, dtype=torch.float32).reshape(-1).to(dev)
-    out = _fit_trajectory(poses.to(dev), seq_2d.to(dev), cam, None if conf is None else conf.to(dev), smooth)
+    cam = _cam9(cam, dev) if focal is not None else torch.as_tensor(cam, dtype=torch.float32).reshape(-1).to(dev)
+    out = _fit_trajectory(poses.to(dev), seq_2d.to(dev), cam, None if conf is None else conf.to(dev), smooth, focal)
+    return {k: v.cpu() for k, v in out.items()}
+
+
+@torch.no_grad()
+def estimate_focal(poses, seq_2d, cam=None, conf=None, device="cuda"):
+    """The focal length of the camera of a video, estimated from per-frame poses and the detections they were lifted from:
+    ``poses`` [T,N,J,3] whole-body and root-relative, ``seq_2d`` [N,J,2] screen-normalised, ``conf`` [N,J] (None: all 1), as
+    :func:`fit_trajectory` takes them.  ``cam`` (4 .. 9 values): its principal point, pixel aspect cam[1]/cam[0] and distortion
+    terms are kept, its focal length is not read; None means square pixels and the principal point at the image centre.
+    One focal length per step t for the whole video, on the device (pafuse_amd.focal; ops.estimate_focal).  Returns a dict of
+    CPU tensors: ``"focal"`` [T] in screen-normalised units (pixels: focal * width / 2; NaN: no estimate), ``"focal_r2"`` [T]
+    the fraction of the perspective signal the estimate explains, ``"focal_frames"`` [T] the frames it rests on, and ``"cam"``
+    [T,9] the intrinsics with the estimate in place - what ``fit_trajectory(..., cam=out["cam"][-1])`` takes.  The estimate
+    inherits a depth-scale error of the poses one for one; a single frame or a distant person carries little signal, which
+    focal_r2 and focal_frames show."""
+    poses = torch.as_tensor(poses, dtype=torch.float32)
+    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
+    if poses.dim() != 4 or poses.shape[-1] != 3 or tuple(seq_2d.shape) != (*poses.shape[1:3], 2):
+        raise ValueError(f"poses must be [T,N,J,3] and seq_2d [N,J,2], got {tuple(poses.shape)} and {tuple(seq_2d.shape)}")
+    if conf is not None:
+        conf = torch.as_tensor(conf, dtype=torch.float32)
+        if tuple(conf.shape) != tuple(seq_2d.shape[:2]):
+            raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[:2])}, got {tuple(conf.shape)}")
+    cam = _cam9(cam, "cpu")                                          # refused here, before anything touches the device
+    dev = poses.device if poses.is_cuda else torch.device(device)
+    out = _estimate_focal(poses.to(dev), seq_2d.to(dev), cam.to(dev), None if conf is None else conf.to(dev))
     return {k: v.cpu() for k, v in out.items()}
 
 
@@ -548,7 +620,7 @@ holds the p2_* keys, each step ends with the four Protocol #2 lines (:511-519): 
 # ----------------------------------------------------------------- the per-frame output scored against ground truth
 @torch.no_grad()
 def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
-                    conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False):
+                    conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False, focal=None):
     """One video scored at the level of frames: the frames path of :func:`infer_sequence` - ONE pose per video frame, pooled
     over the windows that cover it - against the ground truth, on the device before anything crosses to the host
     (evaluate.frame_metrics; pafuse_amd.framemetrics states the arithmetic).
@@ -562,7 +634,14 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     Returns ``(sums, counts)``: dicts of CPU tensors [T], float64 and int64, keyed by evaluate.frame_metric_names plus
     "mpjpe_pb" (and "p_mpjpe" with ``p2=True``) - add them over videos and hand them to :func:`frame_report`.
     ``per_frame=True`` returns ``(sums, counts, maps)``, maps = {"err" [T,N,K] float64, "cnt" [T,N,K] int32, "names"}: the
-    same per frame, what :func:`seam_profile` bins.  On synthetic weights the numbers mean nothing."""
+    same per frame, what :func:`seam_profile` bins.  On synthetic weights the numbers mean nothing.
+
+    ``focal="estimate"`` (with ``trajectory``): the root is fitted and scored with the ESTIMATED focal length (``cam`` gives the
+    principal point, aspect and distortion terms), and the estimate is returned as one more, last element: a dict of CPU
+    tensors ``"focal"``, ``"focal_r2"``, ``"focal_frames"`` [T] and ``"cam"`` [T,9], to be compared with cam[0]."""
+    _focal_mode(focal)
+    if focal is not None and trajectory is None:
+        raise ValueError('focal="estimate" belongs to a trajectory')
     if aggregate not in ("mean", "reproj", "reproj_fit"):
         raise ValueError(f'aggregate must be "mean", "reproj" or "reproj_fit", got {aggregate!r}')
     frames = getattr(model, "frames", None)
@@ -591,7 +670,8 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     gt_wb = (seq_3d - seq_3d[:, :1]).to(dev)                        # joint 0 at 0, exactly
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam,
                                gt_root if aggregate == "reproj" else None, hypothesis_chunk, None, conf, stride, dev,
-                               trajectory is not None, smooth)
+                               trajectory is not None, smooth, focal)
+    estimate = {k: out[k].cpu() for k in ("focal", "focal_r2", "focal_frames", "cam")} if focal is not None else None
     m = frame_metrics(out["pose"], gt_wb, dataset, traj=out.get("traj"), gt_root=gt_root.to(dev) if "traj" in out else None,
                       p2=p2, per_frame=per_frame)
     maps = {k: m.pop(k).cpu() for k in ("err", "cnt") if k in m}
@@ -599,8 +679,8 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     if per_frame:
         from .evaluate import frame_metric_names
         maps["names"] = frame_metric_names(dataset)
-        return sums, counts, maps
-    return sums, counts
+        return (sums, counts, maps) if estimate is None else (sums, counts, maps, estimate)
+    return (sums, counts) if estimate is None else (sums, counts, estimate)
 
 
 FRAME_UNITS = {"mpjve": "mm/frame", "root_vel": "mm/frame", "accel": "mm/frame^2"}     # every other metric: mm

@@ -1394,6 +1394,60 @@ def smooth_trajectory(traj, weight, radius, out=None):
     return out
 
 
+# ------------------------------------------------------------------ the focal length, estimated from pose and detections
+FOCAL_OUTPUTS = ("focal", "r2", "frames", "cam")
+
+
+def focal_sums(pose, x2d, cam, conf=None):
+    """pafuse_frames_focal_sums: pose [T,N,J,3], x2d [N,J,2], cam [>= 4] and conf [N,J] (None: every weight 1) as fit_trajectory
+    takes them - of cam only cx, cy and the ratio cam[1]/cam[0] are read -> state [T,N,4] float64: (K, H, G, 1.0) per (t, frame),
+    zeros for a frame that takes no part (pafuse_amd.focal states the arithmetic).  States of several videos of one camera
+    concatenate along N."""
+    lib = _lib.load()
+    _need(isinstance(pose, torch.Tensor) and pose.dim() == 4 and pose.shape[-1] == 3, "focal_sums: pose must be [T,N,J,3]")
+    T, N, J = (int(v) for v in pose.shape[:3])
+    _need(T > 0 and N > 0 and J > 0, "focal_sums: T, N, J > 0")
+    _need(x2d is not None and cam is not None, "focal_sums: x2d and cam are needed")
+    _need(tuple(x2d.shape) == (N, J, 2) and cam.dim() == 1 and cam.numel() >= 4 and (conf is None or tuple(conf.shape) == (N, J)),
+          "focal_sums: x2d [N,J,2], cam [>= 4] and conf [N,J] must match pose [T,N,J,3]")
+    _need_tensors("focal_sums", [pose, x2d, cam] + ([] if conf is None else [conf]), ())
+    out = torch.empty(T, N, 4, device=pose.device, dtype=torch.float64)
+    with torch.cuda.device(pose.device):
+        _lib.check(lib.pafuse_frames_focal_sums(pose.data_ptr(), x2d.data_ptr(), None if conf is None else conf.data_ptr(),
+                                                cam.data_ptr(), T, N, J, out.data_ptr(), _stream(pose)))
+    return out
+
+
+def focal_solve(state, cam, want=FOCAL_OUTPUTS):
+    """pafuse_focal_solve: state [T,N,4] float64 (focal_sums; several concatenated along N), cam [4 .. 9] the intrinsics whose
+    principal point, aspect and distortion terms are kept -> dict with the entries named in `want`: "focal" [T] (screen-normalised
+    units, NaN without an estimate), "r2" [T] the fraction of the perspective signal the estimate explains, "frames" [T] int32
+    the frames it rests on, "cam" [T,len(cam)] the intrinsics with the estimate in the place of fx, fy (NaN without one)."""
+    lib = _lib.load()
+    want = tuple(want)
+    _need(all(k in FOCAL_OUTPUTS for k in want) and "focal" in want, f'focal_solve: want holds "focal" and any of r2, frames, cam - got {want}')
+    _need(isinstance(state, torch.Tensor) and state.dim() == 3 and state.shape[-1] == 4 and state.dtype == torch.float64
+          and state.is_cuda and state.is_contiguous(), "focal_solve: state must be a contiguous float64 [T,N,4] tensor on a HIP device")
+    T, N = int(state.shape[0]), int(state.shape[1])
+    _need(T > 0 and N > 0, "focal_solve: T, N > 0")
+    _need(cam is not None and cam.dim() == 1 and 4 <= cam.numel() <= 9, "focal_solve: cam must be [4 .. 9]")
+    _need_tensors("focal_solve", [cam], ())
+    _need(cam.device == state.device, "focal_solve: cam on the device of the state")
+    dev, L = state.device, int(cam.numel())
+    shapes = {"focal": ((T,), torch.float32), "r2": ((T,), torch.float32), "frames": ((T,), torch.int32), "cam": ((T, L), torch.float32)}
+    out = {k: torch.empty(shapes[k][0], device=dev, dtype=shapes[k][1]) for k in want}
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_focal_solve(state.data_ptr(), T, N, cam.data_ptr(), L, ptr("focal"), ptr("r2"), ptr("frames"),
+                                          ptr("cam"), _stream(state)))
+    return out
+
+
+def estimate_focal(pose, x2d, cam, conf=None, want=FOCAL_OUTPUTS):
+    """focal_sums and focal_solve in one call, for one video: -> the dict of focal_solve."""
+    return focal_solve(focal_sums(pose, x2d, cam, conf=conf), cam, want=want)
+
+
 # ------------------------------------------------------------------ the per-frame pose scored against ground truth
 FRAME_ERROR_SLOTS = ("mpjpe", "mpjve", "accel", "root", "root_vel", "abs_mpjpe")   # then one slot per part (pafuse_amd.framemetrics)
 

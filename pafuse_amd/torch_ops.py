@@ -19,6 +19,8 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::finish_frames(frame, N, T, J, spread?)          one pose per video frame: mean, pick, idx, window (+ std, cov)
   pafuse::fit_trajectory(pose, x2d, cam, conf?)           the camera-space root of that pose: traj, wsum, resid per (t, frame)
   pafuse::smooth_trajectory(traj, weight?, radius)        a confidence-weighted local-linear filter along the frames
+  pafuse::focal_sums(pose, x2d, cam, conf?)               the focal-length sums of that pose: (K, H, G, 1) per (t, frame)
+  pafuse::focal_solve(state, cam)                         the focal length from them: focal, r2, frames, cam per t
   pafuse::frame_errors(pose, gt, pbroot, part, num_parts, traj?, gt_root?)   that pose (and root) scored against ground truth
   pafuse::noise_fill(key, draw, B, P, F, J)               one draw of noise stream v1 as a tensor (DESIGN.md section 6)
 
@@ -465,6 +467,34 @@ def smooth_trajectory(traj: torch.Tensor, weight: Optional[torch.Tensor], radius
 @smooth_trajectory.register_fake
 def _(traj, weight, radius):
     return torch.empty_like(traj)
+
+
+# ------------------------------------------------------------------ the focal length, estimated from pose and detections
+@torch.library.custom_op("pafuse::focal_sums", mutates_args=(), device_types="cuda")
+def focal_sums(pose: torch.Tensor, x2d: torch.Tensor, cam: torch.Tensor, conf: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pafuse_amd.ops.focal_sums: pose [T,N,J,3] root-relative, x2d [N,J,2], cam [>= 4], conf [N,J] or None -> state [T,N,4] float64."""
+    from . import ops
+    return ops.focal_sums(pose, x2d, cam, conf=conf)
+
+
+@focal_sums.register_fake
+def _(pose, x2d, cam, conf=None):
+    return pose.new_empty((pose.shape[0], pose.shape[1], 4), dtype=torch.float64)
+
+
+@torch.library.custom_op("pafuse::focal_solve", mutates_args=(), device_types="cuda")
+def focal_solve(state: torch.Tensor, cam: torch.Tensor) -> List[torch.Tensor]:
+    """pafuse_amd.ops.focal_solve: state [T,N,4] float64, cam [4 .. 9] -> [focal [T], r2 [T], frames [T] int32, cam [T,len(cam)]]."""
+    from . import ops
+    m = ops.focal_solve(state, cam)
+    return [m["focal"], m["r2"], m["frames"], m["cam"]]
+
+
+@focal_solve.register_fake
+def _(state, cam):
+    T = state.shape[0]
+    return [state.new_empty((T,), dtype=torch.float32), state.new_empty((T,), dtype=torch.float32),
+            state.new_empty((T,), dtype=torch.int32), state.new_empty((T, cam.shape[0]), dtype=torch.float32)]
 
 
 # ------------------------------------------------------------------ the per-frame pose scored against ground truth
