@@ -13,6 +13,10 @@ Trailing `a.b=c` arguments override the config tree like the reference's Hydra c
 velocity, acceleration, root and part-based errors of the per-frame output (harness.evaluate_frames).  `--estimate-focal` (with
 `--frames --trajectory`) fits and scores the root with the focal length estimated from each video and prints the estimate against
 the true one per video (H3WB knows its intrinsics: this is how the estimator can be measured).
+`--drop-detections RATE:RUN[:SEED]` (with `--frames`) loses ground-truth 2-D detections on purpose - runs of RUN frames, a share of
+about RATE of the joints, detections.plant_dropouts - and `--repair [R]` repairs them on the device before the model sees them
+(harness.repair_detections; R in 1 .. 64, default 13); per video the joints per status and detections.repair_error are logged.
+Ground-truth 2-D has no dropouts: without the planting nobody can measure whether the repair helps on H3WB.
 Without `--data` the synthetic H3WB files of tests/golden/h3wb_synth are used (random weights: numbers are meaningless).
 """
 import argparse
@@ -56,8 +60,26 @@ def main():
                     help="with --frames --trajectory: fit and score the root with the focal length estimated from each video, and "
                          "print the estimate against the true one per video")
     ap.add_argument("--seam-profile", action="store_true", help="with --frames: the position error by the frame's position in the clip")
+    ap.add_argument("--drop-detections", default=None, metavar="RATE:RUN[:SEED]",
+                    help="with --frames: lose detections on purpose before the model sees them - runs of RUN frames, about a share RATE "
+                         "of the joints (at (-1, -1) with confidence 0), seeded per video with SEED (default 0) + the video's number")
+    ap.add_argument("--repair", type=int, default=None, nargs="?", const=13, metavar="R",
+                    help="with --frames --drop-detections: repair the lost detections on the device along the frames within R "
+                         "(1 .. 64, default 13) and log the repair error per video")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    drop = None
+    if a.drop_detections is not None:
+        try:
+            fields = a.drop_detections.split(":")
+            drop = (float(fields[0]), int(fields[1]), int(fields[2]) if len(fields) > 2 else 0)
+            assert len(fields) <= 3 and 0.0 <= drop[0] <= 1.0 and drop[1] >= 1
+        except (ValueError, IndexError, AssertionError):
+            ap.error("--drop-detections takes RATE:RUN[:SEED], RATE in 0 .. 1 and RUN >= 1 frames")
+    if (drop is not None or a.repair is not None) and not a.frames:
+        ap.error("--drop-detections and --repair need --frames")
+    if a.repair is not None and (drop is None or not 1 <= a.repair <= 64):
+        ap.error("--repair takes a radius in 1 .. 64 and needs --drop-detections (ground-truth 2-D has nothing to repair)")
     if a.estimate_focal and not (a.frames and a.trajectory is not None):
         ap.error("--estimate-focal needs --frames --trajectory")
     args = config.load(a.config or None, a.overrides)
@@ -93,7 +115,7 @@ def main():
         h3wb.evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, aggregate=a.aggregate, stride=a.stride,
                              trajectory=None if a.trajectory is None else (a.trajectory or True), log=log,
                              hypothesis_chunk=a.hypothesis_chunk, p2=bool(args.ft2d.p2), seam_profile=a.seam_profile,
-                             focal="estimate" if a.estimate_focal else None)
+                             focal="estimate" if a.estimate_focal else None, repair=a.repair, drop=drop)
     else:
         h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
                       batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),

@@ -44,6 +44,12 @@ the estimate explains - and the number of frames it rests on.  --trajectory then
 estimate of the last step (a number given all the same is not read).  The estimate inherits a depth-scale error of the lifted pose
 one for one, and a single frame or a distant person carries little signal - look at r2 and frames.  null in the file: no estimate,
 and then the trajectory is NaN.
+
+--repair [R] (default 13 frames; --repair-threshold C) repairs the detections on the device before anything else sees them
+(harness.repair_detections): a keypoint the detector did not find - OpenPifPaf writes (0, 0, 0), which would enter the model as the
+image corner - is filled along the frames from the frames within R in which it was found, a face keypoint relative to the nose and
+a hand keypoint relative to its wrist; found keypoints are not touched, and a filled one keeps confidence 0, so the fits above go on
+ignoring it.  It writes test_3d_output_repaired.npy [frames,134] (0 observed, 1 filled, 2 held, 3 unfilled) and prints the counts.
 """
 import argparse
 import json
@@ -101,8 +107,19 @@ def main():
                     help="with --aggregate mean: estimate the focal length from the mean poses and the detections on the device and "
                          "write it, in pixels, with r2 and the frame count to test_3d_output_focal.json; --trajectory then fits "
                          "the root with the estimate and needs no number")
+    ap.add_argument("--repair", type=int, default=None, nargs="?", const=13, metavar="R",
+                    help="repair the detections on the device before lifting: a keypoint the detector did not find is filled along "
+                         "the frames from the frames within R (1 .. 64, default 13) in which it was found, a face or hand keypoint "
+                         "relative to the nose or its wrist; writes test_3d_output_repaired.npy [frames,134] (0 observed, 1 filled, "
+                         "2 held, 3 unfilled) and prints the four counts")
+    ap.add_argument("--repair-threshold", type=float, default=0.0, metavar="C",
+                    help="with --repair: a keypoint counts as found if its confidence is above C (default 0)")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.repair is not None and not 1 <= a.repair <= 64:
+        ap.error("--repair takes a radius in 1 .. 64 frames")
+    if not 0.0 <= a.repair_threshold < float("inf"):
+        ap.error("--repair-threshold takes a finite confidence >= 0")
     if a.estimate_focal and a.aggregate != "mean":
         ap.error("--estimate-focal needs --aggregate mean (one pose per frame)")
     if a.trajectory is not None and (a.aggregate != "mean" or not (a.trajectory > 0 or a.estimate_focal)):
@@ -142,6 +159,11 @@ def main():
     pixels, conf = harness.load_pifpaf_keypoints(a.keypoints, args.data.num_kps, with_conf=True)
     keypoints = h3wb.normalize_screen_coordinates(pixels[..., :2], w=a.width, h=a.height).astype(np.float32)
     save = lambda name, t: np.save(os.path.join(a.out, name), t.numpy(), allow_pickle=True)
+    if a.repair is not None:             # once, up front: every call below sees the repaired pair, as infer_sequence(repair=...) would
+        fixed = harness.repair_detections(keypoints, conf, dataset=dataset, radius=a.repair, threshold=a.repair_threshold)
+        keypoints, conf = fixed["x2d"].numpy(), fixed["conf"].numpy()
+        save("test_3d_output_repaired.npy", fixed["status"])
+        print("detections observed %d, filled %d, held %d, unfilled %d (unfilled ones enter the model as they are)" % tuple(fixed["counts"].tolist()))
     # screen-normalised coordinates: x in [-1, 1] over the width, the image centre at (0, 0), one scale for both axes
     pinhole = lambda focal: np.array([2 * focal / a.width, 2 * focal / a.width, 0, 0, 0, 0, 0, 0, 0], dtype=np.float32)
     traj = focal = None

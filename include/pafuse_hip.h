@@ -36,6 +36,8 @@
  *                            pooled into one pose (and spread) per video frame
  *   pafuse_frames_root_fit / pafuse_trajectory_smooth  the camera-space root of that per-frame pose, fitted from the
  *                            detections, and a confidence-weighted local-linear filter along the frames
+ *   pafuse_detections_repair missing 2-D detections filled along the frames by that filter, per joint, a hand or face joint
+ *                            relative to the joint it hangs on - the input side, before lifting
  *   pafuse_frames_focal_sums / pafuse_focal_solve  the focal length that fit needs, estimated from the same pose and
  *                            detections: one value per video, with the fraction of the signal it explains
  *   pafuse_frame_errors / pafuse_frame_errors_reduce  that per-frame pose and root scored against ground truth: position,
@@ -778,6 +780,33 @@ int pafuse_frames_root_fit(const float *pose /* [T,N,J,3] whole-body, root-relat
  * outside 1 .. 64, out == traj. */
 int pafuse_trajectory_smooth(const float *traj /* [T,N,3] */, const float *weight /* [T,N] or NULL */, int32_t T, int32_t N,
                              int32_t radius /* 1..64 */, float *out /* [T,N,3], may not alias traj */, void *stream);
+
+/* Missing 2-D detections repaired along the frames before lifting, per joint (pafuse_amd/detections.py states the arithmetic;
+ * DESIGN.md section 6j).  observed(n, j): conf[n,j] > threshold and both coordinates of x2d[n,j] finite (a NaN confidence is
+ * not observed).  An observed joint is copied: the same bits, status 0.  A missing one is filled by the filter of
+ * pafuse_trajectory_smooth over the frames m = max(0, n - r) .. min(N - 1, n + r) in which joint j is observed, omega =
+ * g * conf[m,j]: the local line's value at d = 0 (two frames or more, D finite and > 0: status 1, filled), else Q0/S0 (S0 > 0:
+ * status 2, held), else status 3, unfilled.  The value is rounded once to fp32; one that is not finite in fp32 is status 3.
+ * Status 3 keeps the input's bits: no input gets worse and no NaN is created.
+ * The level rule.  anchor [J] names the joint a joint hangs on (a finger on its wrist), < 0 for none.  Joint j is LEVEL 1 iff
+ * 0 <= anchor[j] < J and anchor[anchor[j]] < 0; every other joint is LEVEL 0 - anchor[j] < 0, out of range, anchored on
+ * itself or on an anchored joint, and every joint of a NULL table.  anchor[anchor[j]] is read only for an in-range anchor[j],
+ * so no table causes a read out of bounds; this entry does NOT refuse a table the rule demotes (the Python layers do).
+ * Level 0 filters y = x2d[m,j].  Level 1, a = anchor[j], filters y = x2d[m,j] - out[m,a] over the frames in which also
+ * status[m,a] != 3 and writes out[n,a] + line, and only if status[n,a] != 3 (otherwise status 3): a hand lost for a few
+ * frames moves with its wrist.
+ *   out      [N,J,2]  the repaired detections
+ *   conf_out [N,J]    (NULL: not wanted) conf where status is 0, 0 elsewhere: a filled joint carries no measurement
+ *   status   [N,J]    0 observed, 1 filled, 2 held, 3 unfilled
+ * Two launches of one kernel on the stream (level 0, then level 1; one with a NULL table), one thread per (n, j); level 1
+ * reads out / status of level-0 joints and writes level-1 joints, which is why out may not alias x2d and status is required.
+ * No workspace, no atomics, no host synchronisation, bit-reproducible.
+ * Refused (PAFUSE_E_ARG) before any HIP call: a null x2d / conf / out / status, N or J < 1, radius outside 1 .. 64, a threshold
+ * that is not finite or < 0, out == x2d, conf_out == conf, a grid out of range. */
+int pafuse_detections_repair(const float *x2d /* [N,J,2] */, const float *conf /* [N,J] */,
+                             const int32_t *anchor /* [J] device, or NULL */, int32_t N, int32_t J, int32_t radius /* 1..64 */,
+                             float threshold /* >= 0 */, float *out /* [N,J,2], may not alias x2d */,
+                             float *conf_out /* [N,J] or NULL, may not alias conf */, uint8_t *status /* [N,J] */, void *stream);
 
 /* The focal length of the video's camera from the finished per-frame pose and its detections, part one: the sums per
  * (t, frame) (pafuse_amd/focal.py states the arithmetic).  Operands as pafuse_frames_root_fit, except

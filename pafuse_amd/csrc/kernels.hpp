@@ -3753,6 +3753,89 @@ __global__ void __launch_bounds__(256) trajectory_smooth_kernel(const Trajectory
         p.out[e * 3 + k] = line ? (float)((S2 * Q0[k] - S1 * Q1[k]) / D) : S0 > 0.0 ? (float)(Q0[k] / S0) : __builtin_nanf("");
 }
 
+// detections_repair_kernel: the smoother's filter brought to the 2-D detections, per joint, filling only what is missing
+// (statement: pafuse_amd/detections.py repair).  observed(n, j): conf[n,j] > threshold and both
+// coordinates finite.  One thread per (n, j), e = n*J + j with j fastest: the lanes of a wave read neighbouring addresses of
+// one frame at every step of the walk.  Joint j is level 1 iff 0 <= anchor[j] < J and anchor[anchor[j]] < 0 (anchor[anchor[j]]
+// is read only for an in-range anchor[j]); every other joint - and every joint of a null table - is level 0.  A thread whose
+// joint is not of p.level returns without writing.  An observed joint is copied (status 0).  A missing one walks
+// m = max(0, n - r) .. min(N - 1, n + r) with the taper, sums and the line-else-mean rule of trajectory_smooth_kernel over the
+// frames where (m, j) is observed: level 0 on y = x2d[m,j], level 1 - a = anchor[j] - on y = x2d[m,j] - out[m,a] over the frames
+// where also status[m,a] != 3, the value out[n,a] + line, and only if status[n,a] != 3.  Line: status 1; mean: status 2;
+// neither, or a value that is not finite in fp32: status 3, which keeps the input's bits.  conf_out (may be null) is conf at
+// status 0 and 0 elsewhere.  Level 1 reads out / status of level-0 joints only and writes level-1 joints only: the host
+// launches level 0, then level 1, on one stream, and no element is read and written within one launch.
+// fp64, contraction off, rounded once.  No LDS, no atomics, no scratch.
+struct DetectionsRepairParams {
+    const float* x2d;       // [N,J,2]
+    const float* conf;      // [N,J]
+    const int32_t* anchor;  // [J] or null
+    float* out;             // [N,J,2]
+    float* conf_out;        // [N,J] or null
+    uint8_t* status;        // [N,J]
+    int N, J, radius, level;
+    float threshold;
+};
+
+__global__ void __launch_bounds__(256) detections_repair_kernel(const DetectionsRepairParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)p.N * p.J) return;
+    const int J = p.J, j = (int)(e % J), n = (int)(e / J), r = p.radius;
+    int a = p.anchor ? p.anchor[j] : -1;
+    const bool hangs = a >= 0 && a < J && p.anchor[a] < 0;
+    if ((hangs ? 1 : 0) != p.level) return;
+    const float thr = p.threshold;
+    const float c = p.conf[e], x = p.x2d[e * 2], y = p.x2d[e * 2 + 1];
+    if (c > thr && isfinite(x) && isfinite(y)) {
+        p.out[e * 2] = x, p.out[e * 2 + 1] = y, p.status[e] = 0;
+        if (p.conf_out) p.conf_out[e] = c;
+        return;
+    }
+    float vx = x, vy = y;
+    int st = 3;
+    const bool able = !hangs || p.status[(int64_t)n * J + a] != 3;
+    if (able) {
+        const double span = (double)((r + 1) * (r + 1));
+        double S0 = 0.0, S1 = 0.0, S2 = 0.0, Q0x = 0.0, Q0y = 0.0, Q1x = 0.0, Q1y = 0.0;
+        int cnt = 0;
+        const int lo = max(0, n - r), hi = min(p.N - 1, n + r);
+        for (int m = lo; m <= hi; ++m) {
+            const int64_t em = (int64_t)m * J + j;
+            const float cm = p.conf[em], xm = p.x2d[em * 2], ym = p.x2d[em * 2 + 1];
+            if (!(cm > thr && isfinite(xm) && isfinite(ym))) continue;
+            double y0 = (double)xm, y1 = (double)ym;
+            if (hangs) {
+                const int64_t ea = (int64_t)m * J + a;
+                if (p.status[ea] == 3) continue;
+                y0 = y0 - (double)p.out[ea * 2], y1 = y1 - (double)p.out[ea * 2 + 1];
+            }
+            const int d = m - n;
+            const double dd = (double)d;
+            const double q = (double)(d * d) / span, h = 1.0 - q, g = h * h;
+            const double om = g * (double)cm, omd = om * dd;
+            S0 += om, S1 += omd, S2 += omd * dd;
+            Q0x += om * y0, Q0y += om * y1;
+            Q1x += omd * y0, Q1y += omd * y1;
+            ++cnt;
+        }
+        const double D = S0 * S2 - S1 * S1;
+        const bool line = cnt >= 2 && isfinite(D) && D > 0.0;
+        if (line || S0 > 0.0) {
+            double fx = line ? (S2 * Q0x - S1 * Q1x) / D : Q0x / S0;
+            double fy = line ? (S2 * Q0y - S1 * Q1y) / D : Q0y / S0;
+            if (hangs) {
+                const int64_t ea = (int64_t)n * J + a;
+                fx = (double)p.out[ea * 2] + fx, fy = (double)p.out[ea * 2 + 1] + fy;
+            }
+            const float gx = (float)fx, gy = (float)fy;
+            if (isfinite(gx) && isfinite(gy)) vx = gx, vy = gy, st = line ? 1 : 2;
+        }
+    }
+    p.out[e * 2] = vx, p.out[e * 2 + 1] = vy, p.status[e] = (uint8_t)st;
+    if (p.conf_out) p.conf_out[e] = 0.f;
+}
+
 // ----------------------------------------------------------------------------------------------------------------
 // The focal length of the video's camera from the per-frame pose and its detections (statement:
 // pafuse_amd/focal.py).  With p = u - cx, q = (v - cy)/rho, rho = cam[1]/cam[0], hx = p*Z, hy = q*Z the pinhole is linear

@@ -2188,6 +2188,30 @@ int pafuse_trajectory_smooth(const float* traj, const float* weight, int32_t T, 
     return launch<trajectory_smooth_kernel>("trajectory_smooth_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
 }
 
+// missing 2-D detections filled along the frames, per joint (detections_repair_kernel): level 0, then - with a table - level 1
+// on the same stream; the argument checks come before the first HIP call
+int pafuse_detections_repair(const float* x2d, const float* conf, const int32_t* anchor, int32_t N, int32_t J, int32_t radius,
+                             float threshold, float* out, float* conf_out, uint8_t* status, void* stream) {
+    if (!x2d || !conf || !out || !status) return fail(PAFUSE_E_ARG, "detections_repair: x2d, conf, out and status are needed (anchor, conf_out may be null)");
+    if (N < 1 || J < 1) return fail(PAFUSE_E_ARG, "detections_repair: bad size (N=%d J=%d)", N, J);
+    if (radius < 1 || radius > 64) return fail(PAFUSE_E_ARG, "detections_repair: radius %d outside 1 .. 64", radius);
+    if (!std::isfinite(threshold) || threshold < 0.f) return fail(PAFUSE_E_ARG, "detections_repair: threshold %g is not finite and >= 0", (double)threshold);
+    if (out == x2d) return fail(PAFUSE_E_ARG, "detections_repair: out may not alias x2d (every thread reads its neighbours' frames)");
+    if (conf_out && conf_out == conf) return fail(PAFUSE_E_ARG, "detections_repair: conf_out may not alias conf (the walk reads the confidences)");
+    const int64_t rows = (int64_t)N * J;
+    if ((rows + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "detections_repair: grid out of range");
+    StreamDevice on_stream_device(stream);
+    DetectionsRepairParams m{};
+    m.x2d = x2d, m.conf = conf, m.anchor = anchor, m.out = out, m.conf_out = conf_out, m.status = status;
+    m.N = N, m.J = J, m.radius = radius, m.threshold = threshold;
+    for (int level = 0; level < (anchor ? 2 : 1); ++level) {
+        m.level = level;
+        const int rc = launch<detections_repair_kernel>("detections_repair_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
+        if (rc != PAFUSE_OK) return rc;
+    }
+    return PAFUSE_OK;
+}
+
 // the focal-length sums of every (t, frame) of the finished pose (frames_focal_sums_kernel) and the estimate from them
 // (focal_solve_kernel): the argument checks come before the first HIP call
 int pafuse_frames_focal_sums(const float* pose, const float* x2d, const float* conf, const float* cam, int32_t T, int32_t N,

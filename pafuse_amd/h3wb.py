@@ -250,7 +250,8 @@ def evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, batc
 
 
 def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
-                    batch_size=2, group=None, log=print, action=None, hypothesis_chunk=None, p2=False, seam_profile=False, focal=None):
+                    batch_size=2, group=None, log=print, action=None, hypothesis_chunk=None, p2=False, seam_profile=False, focal=None,
+                    repair=None, drop=None, repair_threshold=0.0):
     """The frame-level evaluation of every video, looped like :func:`evaluate`: harness.evaluate_frames per (camera, sequence) -
     one pose per video frame (``aggregate``, ``stride``; None: un-strided clips laid end to end), optionally its fitted
     camera-space root (``trajectory``: True or a smoothing radius) - scored on the device; the sums and counts added over the
@@ -259,14 +260,34 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
     frame's position in the clip (harness.seam_profile, summed over the videos); the return value is then ``(rep, profile)``,
     profile float64 [T, model.frames] in mm.  ``focal="estimate"`` (with ``trajectory``) fits and scores the root with the focal
     length estimated from each video (harness.estimate_focal) and logs, per video, the estimate of every step beside the true
-    cam[0], with r2 and the frames it rests on.  On synthetic weights the numbers mean nothing."""
-    from . import harness
+    cam[0], with r2 and the frames it rests on.  ``drop=(rate, run, seed)`` loses detections of the ground-truth 2-D on purpose
+    (detections.plant_dropouts with seed + the video's number; DROPPED_XY, confidence 0, else 1) and ``repair`` (a radius
+    1 .. 64, with ``drop``) repairs them on the device before the model sees them (harness.evaluate_frames); per video the
+    joints per status are logged and, with both, detections.repair_error: the RMS 2-D distance of the filled and of the
+    unfilled joints from the detections that were dropped, overall and per part.  On synthetic weights the numbers mean nothing."""
+    from . import detections, harness
+    if drop is not None and (not isinstance(drop, (tuple, list)) or len(drop) != 3):
+        raise ValueError(f"drop must be (rate, run, seed), got {drop!r}")
     sums = counts = prof_s = prof_c = None
     for video, (cam, seq_3d, seq_2d) in enumerate(iter_sequences(cams, poses_3d, poses_2d)):
         got = harness.evaluate_frames(model, dataset, seq_2d[0].astype("float32"), seq_3d[0].astype("float32"),
                                       cam[0].astype("float32"), kps_left, kps_right, aggregate=aggregate, stride=stride,
                                       trajectory=trajectory, batch_size=batch_size, group=group,
-                                      hypothesis_chunk=hypothesis_chunk, p2=p2, per_frame=seam_profile, focal=focal)
+                                      hypothesis_chunk=hypothesis_chunk, p2=p2, per_frame=seam_profile, focal=focal, repair=repair,
+                                      drop=None if drop is None else (drop[0], drop[1], int(drop[2]) + video),
+                                      repair_threshold=repair_threshold)
+        if repair is not None or drop is not None:
+            seen, got = got[-1], got[:-1]
+            if "status" in seen:
+                log("video %d : detections observed %d, filled %d, held %d, unfilled %d" % ((video,) + tuple(detections.counts(seen["status"].numpy()))))
+            if "status" in seen and "lost" in seen:
+                err = detections.repair_error(seq_2d[0].astype("float32"), seen["x2d"].numpy(), seen["lost"].numpy(), seen["status"].numpy(),
+                                              parts=dataset.parts_joint_indices)
+                for name, e in [("all", err)] + list(err["parts"].items()):
+                    log("video %d : repair error %s: filled %f over %d joints, unfilled %f over %d (RMS, screen-normalised units)"
+                        % (video, name, e["filled"], e["n_filled"], e["unfilled"], e["n_unfilled"]))
+            elif "lost" in seen:
+                log("video %d : %d detections dropped, none repaired" % (video, int(seen["lost"].sum())))
         if focal is not None:
             est = got[-1]
             for t in range(est["focal"].shape[0]):

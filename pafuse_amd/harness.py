@@ -62,9 +62,55 @@ def wb_pose_from_parts(pose, dataset):
     return out
 
 
+def _repair_radius(repair, threshold=0.0, name="repair"):
+    """infer_sequence's `repair` and `repair_threshold`: None -> None, an integer r in 1 .. 64 -> r; the threshold finite and >= 0"""
+    if repair is None:
+        return None
+    if isinstance(repair, bool) or not isinstance(repair, int) or not 1 <= repair <= 64:
+        raise ValueError(f"{name} must be None or a radius in 1 .. 64 (frames), got {repair!r}")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 <= float(threshold) < float("inf"):
+        raise ValueError(f"{name}_threshold must be a finite confidence >= 0, got {threshold!r}")
+    return repair
+
+
+def _repair_detections(seq_2d, conf, anchor, radius, threshold, dev):
+    """CPU or device tensors seq_2d [N,J,2], conf [N,J] -> ops.repair_detections' dict on the device"""
+    from . import ops
+    return ops.repair_detections(seq_2d.to(dev).contiguous(), conf.to(dev).contiguous(), anchor=anchor, radius=radius, threshold=threshold)
+
+
+@torch.no_grad()
+def repair_detections(seq_2d, conf, dataset=None, anchor=None, radius=13, threshold=0.0, device="cuda"):
+    """Missing 2-D detections repaired on the device before lifting (pafuse_amd.detections; ops.repair_detections): ``seq_2d``
+    [N,J,2] screen-normalised detections, ``conf`` [N,J] their confidences (:func:`load_pifpaf_keypoints` with
+    ``with_conf=True``).  A joint whose confidence is not > ``threshold`` (OpenPifPaf's "not found" writes (0, 0, 0)), or whose
+    coordinates are not finite, is filled along the frames from the frames within ``radius`` in which it was seen, by the
+    confidence-weighted local-linear filter of :func:`fit_trajectory`'s smoother; seen joints keep their bits.  ``dataset``
+    gives the anchor table detections.repair_anchors(dataset): a face joint is filled relative to the nose and a hand joint
+    relative to its wrist, so a hand lost for a few frames moves with the arm.  ``anchor`` [J] overrides it; with both None no
+    joint hangs on another.  Returns a dict of CPU tensors: ``"x2d"`` [N,J,2], ``"conf"`` [N,J] (0 at every joint that was
+    not seen: a filled joint carries no measurement), ``"status"`` [N,J] uint8 (0 observed, 1 filled, 2 held from a single
+    neighbour, 3 unfilled: nothing within the radius, the input as it was) and ``"counts"`` [4] int64, the joints per status."""
+    from .detections import repair_anchors
+    radius = _repair_radius(radius, threshold, "radius")
+    if radius is None:
+        raise ValueError("radius must be a radius in 1 .. 64 (frames), got None")
+    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
+    conf = torch.as_tensor(conf, dtype=torch.float32)
+    if seq_2d.dim() != 3 or seq_2d.shape[-1] != 2 or tuple(conf.shape) != tuple(seq_2d.shape[:2]):
+        raise ValueError(f"seq_2d must be [N,J,2] and conf [N,J], got {tuple(seq_2d.shape)} and {tuple(conf.shape)}")
+    if anchor is None and dataset is not None:
+        anchor = repair_anchors(dataset)
+    dev = seq_2d.device if seq_2d.is_cuda else torch.device(device)
+    out = {k: v.cpu() for k, v in _repair_detections(seq_2d, conf, anchor, radius, float(threshold), dev).items()}
+    out["counts"] = torch.bincount(out["status"].reshape(-1).long(), minlength=4)
+    return out
+
+
 @torch.no_grad()
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
-                   hypothesis_chunk=None, spread=None, conf=None, stride=None, trajectory=None, focal=None):
+                   hypothesis_chunk=None, spread=None, conf=None, stride=None, trajectory=None, focal=None, repair=None,
+                   repair_threshold=0.0):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -120,9 +166,20 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     (None: square pixels, the principal point at the image centre; given: its principal point, aspect and distortion terms are
     kept and its focal length is not read).  The fit runs with the estimate of the last, fully denoised step, ``"cam"[T-1]``,
     read on the device.  Added keys: ``"focal"`` [T], ``"focal_r2"`` [T], ``"focal_frames"`` [T] and ``"cam"`` [T,9].  A video
-    without an estimate (NaN) has a NaN trajectory, not a guessed one."""
+    without an estimate (NaN) has a NaN trajectory, not a guessed one.
+
+    ``repair`` (None: everything above, unchanged, bit for bit) repairs the detections on the device BEFORE anything else sees
+    them - :func:`repair_detections` with the anchors of ``dataset``, that radius (1 .. 64 frames) and ``repair_threshold``.  It
+    needs ``conf`` [N,J], which is then accepted with every ``aggregate``, None included.  ``seq_2d`` and ``conf`` are replaced by
+    the repaired pair before the flip copy and the cutting: the denoisers, the flip copy, the root fits, the focal estimate and
+    the pick all see the same filled detections, and the zeroed confidences keep the filled joints out of every fit.  Results
+    that are dicts gain ``"repaired"`` [N,J] uint8, the status of every joint (0 observed, 1 filled, 2 held, 3 unfilled);
+    tensor and tuple results keep their type."""
     smooth = _trajectory_radius(trajectory)
     _focal_mode(focal)
+    repair = _repair_radius(repair, repair_threshold)
+    if repair is not None and conf is None:
+        raise ValueError("repair needs conf [N,J]: a missing detection is one whose confidence is not above repair_threshold")
     if focal is not None and trajectory is None:
         raise ValueError('focal="estimate" belongs to a trajectory (harness.estimate_focal gives the estimate alone)')
     if trajectory is not None:
@@ -154,13 +211,31 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
             conf = torch.as_tensor(conf, dtype=torch.float32)
             if tuple(conf.shape) != tuple(seq_2d.shape[-3:-1]):
                 raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[-3:-1])}, got {tuple(conf.shape)}")
-    elif conf is not None and trajectory is None:
+    elif conf is not None and trajectory is None and repair is None:
         raise ValueError('conf belongs to aggregate="reproj_fit"')
     elif conf is not None:
         conf = torch.as_tensor(conf, dtype=torch.float32)
         if tuple(conf.shape) != tuple(seq_2d.shape[-3:-1]):
             raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[-3:-1])}, got {tuple(conf.shape)}")
     dev = next(model.parameters()).device
+    if repair is None:
+        return _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
+                               spread, conf, stride, trajectory, smooth, focal, dev)
+    from .detections import repair_anchors
+    fixed = _repair_detections(seq_2d.squeeze(0) if seq_2d.dim() == 4 else seq_2d, conf, repair_anchors(dataset), repair,
+                               float(repair_threshold), dev)
+    # the callees cut and flip on the host: the repaired pair takes the place of the input, whole, before either
+    out = _infer_sequence(model, dataset, fixed["x2d"].cpu(), kps_left, kps_right, batch_size, group, aggregate, cam, traj,
+                          hypothesis_chunk, spread, fixed["conf"].cpu(), stride, trajectory, smooth, focal, dev)
+    if isinstance(out, dict):
+        out["repaired"] = fixed["status"].cpu()
+    return out
+
+
+def _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
+                    conf, stride, trajectory, smooth, focal, dev):
+    """infer_sequence behind its argument checks (and behind the repair of the detections, when one was asked for)"""
+    fit = aggregate == "reproj_fit"
     if stride is not None:
         return _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
                              spread, conf, int(stride), dev, trajectory is not None, smooth, focal)
@@ -620,7 +695,8 @@ holds the p2_* keys, each step ends with the four Protocol #2 lines (:511-519): 
 # ----------------------------------------------------------------- the per-frame output scored against ground truth
 @torch.no_grad()
 def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
-                    conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False, focal=None):
+                    conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False, focal=None, repair=None,
+                    drop=None, repair_threshold=0.0):
     """One video scored at the level of frames: the frames path of :func:`infer_sequence` - ONE pose per video frame, pooled
     over the windows that cover it - against the ground truth, on the device before anything crosses to the host
     (evaluate.frame_metrics; pafuse_amd.framemetrics states the arithmetic).
@@ -638,8 +714,23 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
 
     ``focal="estimate"`` (with ``trajectory``): the root is fitted and scored with the ESTIMATED focal length (``cam`` gives the
     principal point, aspect and distortion terms), and the estimate is returned as one more, last element: a dict of CPU
-    tensors ``"focal"``, ``"focal_r2"``, ``"focal_frames"`` [T] and ``"cam"`` [T,9], to be compared with cam[0]."""
+    tensors ``"focal"``, ``"focal_r2"``, ``"focal_frames"`` [T] and ``"cam"`` [T,9], to be compared with cam[0].
+
+    ``drop=(rate, run, seed)`` (None: everything above, unchanged) loses detections on purpose - ground-truth 2-D has no
+    dropouts, so without it nobody can measure what a repair is worth: detections.plant_dropouts(N, J, rate, run, seed) marks
+    the lost (frame, joint)s, which get detections.DROPPED_XY and confidence 0; every other joint keeps ``conf`` (None: 1).
+    ``repair`` (a radius 1 .. 64; needs ``conf`` or ``drop``) then repairs the detections as infer_sequence(repair=...) does,
+    before the model sees them.  With either, one more, last element is returned: a dict of CPU tensors ``"x2d"`` [N,J,2] and
+    ``"conf"`` [N,J] as the model and the fits saw them, ``"lost"`` [N,J] bool with ``drop`` and ``"status"`` [N,J] uint8 with
+    ``repair`` - what detections.repair_error takes."""
     _focal_mode(focal)
+    repair = _repair_radius(repair, repair_threshold)
+    if drop is not None:
+        if (not isinstance(drop, (tuple, list)) or len(drop) != 3 or not 0.0 <= float(drop[0]) <= 1.0
+                or isinstance(drop[1], bool) or int(drop[1]) != drop[1] or int(drop[1]) < 1):
+            raise ValueError(f"drop must be (rate in 0 .. 1, run >= 1 frames, seed), got {drop!r}")
+    if repair is not None and conf is None and drop is None:
+        raise ValueError("repair needs conf [N,J] or drop: a missing detection is one whose confidence is not above repair_threshold")
     if focal is not None and trajectory is None:
         raise ValueError('focal="estimate" belongs to a trajectory')
     if aggregate not in ("mean", "reproj", "reproj_fit"):
@@ -659,13 +750,27 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     if seq_2d.dim() != 3 or seq_2d.shape[-1] != 2 or tuple(seq_3d.shape) != (*seq_2d.shape[:2], 3):
         raise ValueError(f"seq_2d must be [N,J,2] and seq_3d [N,J,3], got {tuple(seq_2d.shape)} and {tuple(seq_3d.shape)}")
     if conf is not None:
-        if aggregate != "reproj_fit" and trajectory is None:
+        if aggregate != "reproj_fit" and trajectory is None and repair is None and drop is None:
             raise ValueError('conf belongs to aggregate="reproj_fit" or a trajectory')
         conf = torch.as_tensor(conf, dtype=torch.float32)
         if tuple(conf.shape) != tuple(seq_2d.shape[:2]):
             raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[:2])}, got {tuple(conf.shape)}")
     from .evaluate import frame_metrics
     dev = next(model.parameters()).device
+    seen = None
+    if drop is not None:
+        from .detections import DROPPED_XY, plant_dropouts
+        lost = torch.from_numpy(plant_dropouts(seq_2d.shape[0], seq_2d.shape[1], float(drop[0]), int(drop[1]), drop[2]))
+        seq_2d = torch.where(lost.unsqueeze(-1), torch.tensor(DROPPED_XY, dtype=torch.float32), seq_2d)
+        conf = torch.where(lost, torch.zeros(()), torch.ones(lost.shape) if conf is None else conf)
+        seen = {"lost": lost}
+    if repair is not None:
+        from .detections import repair_anchors
+        fixed = _repair_detections(seq_2d, conf, repair_anchors(dataset), repair, float(repair_threshold), dev)
+        seq_2d, conf = fixed["x2d"].cpu(), fixed["conf"].cpu()
+        seen = {**(seen or {}), "status": fixed["status"].cpu()}
+    if seen is not None:
+        seen.update(x2d=seq_2d, conf=conf)
     gt_root = seq_3d[:, 0].contiguous()                             # [N,3]
     gt_wb = (seq_3d - seq_3d[:, :1]).to(dev)                        # joint 0 at 0, exactly
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam,
@@ -676,11 +781,12 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
                       p2=p2, per_frame=per_frame)
     maps = {k: m.pop(k).cpu() for k in ("err", "cnt") if k in m}
     sums, counts = {k: v[0].cpu() for k, v in m.items()}, {k: v[1].cpu() for k, v in m.items()}
+    tail = (() if estimate is None else (estimate,)) + (() if seen is None else (seen,))
     if per_frame:
         from .evaluate import frame_metric_names
         maps["names"] = frame_metric_names(dataset)
-        return (sums, counts, maps) if estimate is None else (sums, counts, maps, estimate)
-    return (sums, counts) if estimate is None else (sums, counts, estimate)
+        return (sums, counts, maps) + tail
+    return (sums, counts) + tail
 
 
 FRAME_UNITS = {"mpjve": "mm/frame", "root_vel": "mm/frame", "accel": "mm/frame^2"}     # every other metric: mm

@@ -1394,8 +1394,70 @@ def smooth_trajectory(traj, weight, radius, out=None):
     return out
 
 
+# ------------------------------------------------------------------ missing 2-D detections, repaired before lifting
+REPAIR_OUTPUTS = {"x2d": ((2,), torch.float32), "conf": ((), torch.float32), "status": ((), torch.uint8)}
+_ANCHOR_CACHE_MAX = 16
+_anchor_cache = {}    # (the table's bytes, device) -> its int32 device copy
+
+
+def repair_anchor_table(anchor, J, device=None):
+    """The anchor table of repair_detections, validated on the host: an integer sequence, numpy array or tensor [J], every
+    entry negative (the joint hangs on nothing) or the index of a joint whose own entry is negative.  An entry the level rule
+    of pafuse_detections_repair would demote silently - out of range, the joint itself, an anchored joint - is a ValueError
+    (pafuse_amd.detections.check_anchor).  -> int32 numpy [J]; with `device` its cached int32 copy there."""
+    from .detections import check_anchor
+    import numpy as np
+    if isinstance(anchor, torch.Tensor):
+        _need(not anchor.dtype.is_floating_point and anchor.dtype != torch.bool, "repair_detections: anchor must be an integer table")
+        anchor = anchor.detach().cpu().numpy()
+    table = check_anchor(np.asarray(anchor), int(J))
+    if device is None:
+        return table
+    key = (table.tobytes(), str(device))
+    hit = _anchor_cache.get(key)
+    if hit is None:
+        if len(_anchor_cache) >= _ANCHOR_CACHE_MAX:
+            _anchor_cache.pop(next(iter(_anchor_cache)))
+        hit = _anchor_cache[key] = torch.from_numpy(table).to(device)
+    return hit
+
+
+def repair_detections(x2d, conf, anchor=None, radius=13, threshold=0.0, want=("x2d", "conf", "status")):
+    """pafuse_detections_repair: x2d [N,J,2] screen-normalised detections, conf [N,J] their confidences, anchor [J] (host
+    integers; None: no joint hangs on another), radius 1 .. 64, threshold >= 0 -> dict with the entries named in `want`:
+    "x2d" [N,J,2] the detections with every joint that is not observed (conf <= threshold, or not finite) filled along the
+    frames from its observed neighbours within `radius` - a joint with an anchor relative to that joint's repaired track -
+    "conf" [N,J] the confidences with 0 at every joint that is not observed, "status" [N,J] uint8: 0 observed (the same
+    bits), 1 filled (local line), 2 held (one neighbour), 3 unfilled (the input's bits).  pafuse_amd.detections states the
+    arithmetic."""
+    lib = _lib.load()
+    want = tuple(want)
+    _need(all(k in REPAIR_OUTPUTS for k in want), f"repair_detections: want holds any of {sorted(REPAIR_OUTPUTS)} - got {want}")
+    _need(isinstance(x2d, torch.Tensor) and x2d.dim() == 3 and x2d.shape[-1] == 2, "repair_detections: x2d must be [N,J,2]")
+    N, J = int(x2d.shape[0]), int(x2d.shape[1])
+    _need(N > 0 and J > 0, "repair_detections: N, J > 0")
+    _need(isinstance(conf, torch.Tensor) and tuple(conf.shape) == (N, J), "repair_detections: conf must be [N,J]")
+    _need(not isinstance(radius, bool) and int(radius) == radius and 1 <= int(radius) <= 64,
+          f"repair_detections: radius must be an integer in 1 .. 64, got {radius!r}")
+    threshold = float(threshold)
+    _need(threshold == threshold and 0.0 <= threshold < float("inf"), f"repair_detections: threshold must be finite and >= 0, got {threshold!r}")
+    table = None if anchor is None else repair_anchor_table(anchor, J)      # refused here, before anything touches the device
+    _need_tensors("repair_detections", [x2d, conf], ())
+    dev = x2d.device
+    if table is not None:
+        table = repair_anchor_table(table, J, dev)
+    made = ("x2d", "status") + (("conf",) if "conf" in want else ())     # the kernel needs out and status whatever is wanted
+    out = {k: torch.empty((N, J, *REPAIR_OUTPUTS[k][0]), device=dev, dtype=REPAIR_OUTPUTS[k][1]) for k in made}
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_detections_repair(x2d.data_ptr(), conf.data_ptr(), None if table is None else table.data_ptr(), N, J,
+                                                int(radius), threshold, out["x2d"].data_ptr(),
+                                                out["conf"].data_ptr() if "conf" in out else None, out["status"].data_ptr(),
+                                                _stream(x2d)))
+    return {k: out[k] for k in want}
+
+
 # ------------------------------------------------------------------ the focal length, estimated from pose and detections
-FOCAL_OUTPUTS = ("focal", "r2", "frames", "cam")
+FOCAL_OUTPUTS =("focal", "r2", "frames", "cam")
 
 
 def focal_sums(pose, x2d, cam, conf=None):

@@ -19,6 +19,7 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::finish_frames(frame, N, T, J, spread?)          one pose per video frame: mean, pick, idx, window (+ std, cov)
   pafuse::fit_trajectory(pose, x2d, cam, conf?)           the camera-space root of that pose: traj, wsum, resid per (t, frame)
   pafuse::smooth_trajectory(traj, weight?, radius)        a confidence-weighted local-linear filter along the frames
+  pafuse::repair_detections(x2d, conf, anchor?, radius, threshold)   missing 2-D detections filled along the frames, per joint
   pafuse::focal_sums(pose, x2d, cam, conf?)               the focal-length sums of that pose: (K, H, G, 1) per (t, frame)
   pafuse::focal_solve(state, cam)                         the focal length from them: focal, r2, frames, cam per t
   pafuse::frame_errors(pose, gt, pbroot, part, num_parts, traj?, gt_root?)   that pose (and root) scored against ground truth
@@ -467,6 +468,22 @@ def smooth_trajectory(traj: torch.Tensor, weight: Optional[torch.Tensor], radius
 @smooth_trajectory.register_fake
 def _(traj, weight, radius):
     return torch.empty_like(traj)
+
+
+# ------------------------------------------------------------------ missing 2-D detections, repaired before lifting
+@torch.library.custom_op("pafuse::repair_detections", mutates_args=(), device_types="cuda")
+def repair_detections(x2d: torch.Tensor, conf: torch.Tensor, anchor: Optional[List[int]] = None, radius: int = 13,
+                      threshold: float = 0.0) -> List[torch.Tensor]:
+    """pafuse_amd.ops.repair_detections: x2d [N,J,2], conf [N,J], anchor J host integers or None, radius 1 .. 64, threshold >= 0
+    -> [x2d [N,J,2] repaired, conf [N,J] (0 where not observed), status [N,J] uint8]."""
+    from . import ops
+    m = ops.repair_detections(x2d, conf, anchor=anchor, radius=radius, threshold=threshold)
+    return [m["x2d"], m["conf"], m["status"]]
+
+
+@repair_detections.register_fake
+def _(x2d, conf, anchor=None, radius=13, threshold=0.0):
+    return [torch.empty_like(x2d), torch.empty_like(conf), conf.new_empty(conf.shape, dtype=torch.uint8)]
 
 
 # ------------------------------------------------------------------ the focal length, estimated from pose and detections
