@@ -2629,6 +2629,63 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
+// The same butterfly over a small array of sums (double, int or long long), per chain exactly v += __shfl_xor(v, o), with
+// the independent chains interleaved: per step all the shuffles, then all the adds.  The second form carries M counts.
+template <class V, int N>
+__device__ __forceinline__ void wave_sums(V (&v)[N]) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        V t[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) t[i] = __shfl_xor(v[i], o);
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] += t[i];
+    }
+}
+template <int N, class C, int M>
+__device__ __forceinline__ void wave_sums(double (&v)[N], C (&c)[M]) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        double t[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) t[i] = __shfl_xor(v[i], o);
+#pragma unroll
+        for (int i = 0; i < M; ++i) c[i] += __shfl_xor(c[i], o);
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] += t[i];
+    }
+}
+
+// One wave per item, four per workgroup (256 threads): the launch shape of the per-frame kernels below; `item` is
+// wave-uniform.  LaneJoints is what a lane keeps of the J joints of its wave's item: lane l owns joints l, l + 64, ... in
+// ascending order.  `load(j)` -> Joint is the kernel's own loader; for j >= J it gives a joint that takes no part and feeds
+// 0.0.  SLOTS >= 1 (J <= 64*SLOTS): the constructor loads all SLOTS joints of the lane into registers - every load is issued
+// before the first butterfly, which is what the latency of these kernels rests on - and for_each walks the registers.
+// SLOTS == 0 is the same arithmetic for any J: every for_each loads round by round.  Every lane runs every round.  No LDS,
+// no atomics, no scratch.
+__device__ __forceinline__ int wave_lane() { return threadIdx.x & 63; }
+__device__ __forceinline__ int64_t wave_item() { return (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); }
+
+template <int SLOTS, class Load>
+struct LaneJoints {
+    using Joint = decltype(std::declval<const Load&>()(0));
+    static constexpr int KEPT = SLOTS > 0 ? SLOTS : 1;
+    const Load& load;
+    const int lane, rounds;
+    Joint kept[KEPT];   // SLOTS == 0: unused
+    __device__ __forceinline__ LaneJoints(int J, const Load& ld) : load(ld), lane(wave_lane()), rounds(SLOTS > 0 ? SLOTS : (J + 63) / 64) {
+#pragma unroll
+        for (int r = 0; r < SLOTS; ++r) kept[r] = load(r * 64 + lane);
+    }
+    template <class F> __device__ __forceinline__ void for_each(F&& f) const {
+#pragma unroll KEPT
+        for (int r = 0; r < rounds; ++r) {
+            if constexpr (SLOTS > 0) f(kept[r]);
+            else f(load(r * 64 + lane));
+        }
+    }
+};
+
 // ----------------------------------------------------------------------------------------------------------------
 // The flat states of the partial-state kernels below, each carved in ONE place: a views struct built from (base pointer,
 // n = B*T*F*J) on the host for the launch parameters and on the device for state w of a combine (states + w * stride).
@@ -3171,8 +3228,8 @@ __device__ __forceinline__ RootSolution root_solve(double W, double Sa, double S
 }
 
 __global__ void __launch_bounds__(256) pose_fit_partials_kernel(const PoseFitParams p) {
-    const int lane = threadIdx.x & 63;
-    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane();
+    const int64_t item = wave_item();
     if (item >= (int64_t)p.B * p.T * p.F) return;   // wave-uniform: all 64 lanes of a wave share `item`
     const int f = (int)(item % p.F);
     const int t = (int)((item / p.F) % p.T);
@@ -3189,16 +3246,15 @@ __global__ void __launch_bounds__(256) pose_fit_partials_kernel(const PoseFitPar
     {   // the sums without a hypothesis in them
 #pragma clang fp contract(off)
         double w0 = 0.0, sa = 0.0, sb = 0.0, sq = 0.0;
-        int cnt = 0;
+        int cnt[1] = {0};
         for (int r = 0; r < rounds; ++r) {
             const RootJoint q = root_joint(x2, cf, r * 64 + lane, J, fx, fy, cx, cy, ROOT_NO_POSE, nullptr);
-            if (q.on) w0 += q.c, sa += q.c * q.a, sb += q.c * q.b, sq += q.c * (q.a * q.a + q.b * q.b), ++cnt;
+            if (q.on) w0 += q.c, sa += q.c * q.a, sb += q.c * q.b, sq += q.c * (q.a * q.a + q.b * q.b), ++cnt[0];
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+        wave_sums(cnt);
         W = wave_sum_f64(w0), Sa = wave_sum_f64(sa), Sb = wave_sum_f64(sb);
         den = root_den(W, Sa, Sb, wave_sum_f64(sq));
-        can = root_fittable(cnt, den);
+        can = root_fittable(cnt[0], den);
     }
     for (int c0 = 0; c0 < p.P; c0 += 64) {
         const int nh = min(64, p.P - c0);
@@ -3630,11 +3686,8 @@ __global__ void __launch_bounds__(256) frames_finish_kernel(const FramesFinishPa
 // traj, 0 in wsum, NaN in resid.  resid = sqrt(R / W), R = sum c*(ex^2 + ey^2) in the same order with
 // ex = (tx - a*tz) - rx, ey = (ty - b*tz) - ry and t before its rounding: the weighted algebraic residual in metres.
 //
-// One wave per (t, n), four per workgroup.  SLOTS >= 1: a lane loads pose, detection and weight of all its <= SLOTS
-// joints (J <= 64*SLOTS) before the first butterfly and keeps a, b, c, rx, ry of each in registers; the seven sums go
-// through seven independent butterfly chains, interleaved round by round; R is an eighth sum behind the solve.  Every
-// lane runs every round, a lane (or slot) without a joint feeds 0.0.  SLOTS == 0 is the same arithmetic for any J: the
-// joints are walked round by round and read again for R.  No LDS, no atomics, no scratch.
+// One wave per (t, n) on LaneJoints<SLOTS> (a, b, c, rx, ry per joint); the seven sums go through wave_sums, R is an
+// eighth sum behind the solve, over a second walk of the joints.
 // ----------------------------------------------------------------------------------------------------------------
 struct FramesRootFitParams {
     const float* pose;    // [T,N,J,3] whole-body, root-relative
@@ -3650,8 +3703,8 @@ struct FramesRootFitParams {
 template <int SLOTS>
 __global__ void __launch_bounds__(256) frames_root_fit_kernel(const FramesRootFitParams p) {
 #pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane();
+    const int64_t item = wave_item();
     if (item >= (int64_t)p.T * p.N) return;   // wave-uniform
     const int n = (int)(item % p.N);
     const int J = p.J;
@@ -3659,63 +3712,83 @@ __global__ void __launch_bounds__(256) frames_root_fit_kernel(const FramesRootFi
     const float* x2 = p.x2d + (int64_t)n * J * 2;
     const float* cf = p.conf ? p.conf + (int64_t)n * J : nullptr;
     const double fx = (double)p.cam[0], fy = (double)p.cam[1], cx = (double)p.cam[2], cy = (double)p.cam[3];
-    constexpr int KEPT = SLOTS > 0 ? SLOTS : 1;
-    const int rounds = SLOTS > 0 ? SLOTS : (J + 63) / 64;
-    RootJoint q[KEPT];
-    auto load = [&](int j) -> RootJoint {
+    const auto load = [&](int j) -> RootJoint {
         float w[3] = {0.f, 0.f, 0.f};
         if (j < J) w[0] = pose[3 * j], w[1] = pose[3 * j + 1], w[2] = pose[3 * j + 2];
         return root_joint(x2, cf, j, J, fx, fy, cx, cy, ROOT_FINITE_POSE, w);
     };
-    auto joint = [&](int r) -> RootJoint {
-        if constexpr (SLOTS > 0) return q[r];
-        else return load(r * 64 + lane);
-    };
-#pragma unroll
-    for (int r = 0; r < KEPT; ++r) q[r] = load(SLOTS > 0 ? r * 64 + lane : J);   // SLOTS == 0: unused
-    double w = 0.0, sa = 0.0, sb = 0.0, sq = 0.0, srx = 0.0, sry = 0.0, sm = 0.0;
-    int cnt = 0;
-#pragma unroll KEPT
-    for (int r = 0; r < rounds; ++r) {
-        const RootJoint g = joint(r);
-        w += g.c, sa += g.c * g.a, sb += g.c * g.b, sq += g.c * (g.a * g.a + g.b * g.b);
-        srx += g.c * g.rx, sry += g.c * g.ry, sm += g.c * (g.a * g.rx + g.b * g.ry);
-        cnt += g.on;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {   // seven independent chains, interleaved
-        const double w2 = __shfl_xor(w, o), sa2 = __shfl_xor(sa, o), sb2 = __shfl_xor(sb, o), sq2 = __shfl_xor(sq, o);
-        const double srx2 = __shfl_xor(srx, o), sry2 = __shfl_xor(sry, o), sm2 = __shfl_xor(sm, o);
-        cnt += __shfl_xor(cnt, o);
-        w += w2, sa += sa2, sb += sb2, sq += sq2, srx += srx2, sry += sry2, sm += sm2;
-    }
-    const double den = root_den(w, sa, sb, sq);
-    const RootSolution sol = root_solve(w, sa, sb, den, srx, sry, sm);
-    const bool ok = root_fittable(cnt, den) && sol.ok;
+    const LaneJoints<SLOTS, decltype(load)> joints(J, load);
+    enum { W, SA, SB, SQ, SRX, SRY, SM, SUMS };
+    double s[SUMS] = {};
+    int cnt[1] = {0};
+    joints.for_each([&](const RootJoint& g) {
+        s[W] += g.c, s[SA] += g.c * g.a, s[SB] += g.c * g.b, s[SQ] += g.c * (g.a * g.a + g.b * g.b);
+        s[SRX] += g.c * g.rx, s[SRY] += g.c * g.ry, s[SM] += g.c * (g.a * g.rx + g.b * g.ry);
+        cnt[0] += g.on;
+    });
+    wave_sums(s, cnt);
+    const double den = root_den(s[W], s[SA], s[SB], s[SQ]);
+    const RootSolution sol = root_solve(s[W], s[SA], s[SB], den, s[SRX], s[SRY], s[SM]);
+    const bool ok = root_fittable(cnt[0], den) && sol.ok;
     const double tx = sol.tx, ty = sol.ty, tz = sol.tz;
     const float qnan = __builtin_nanf("");
     if (lane < 3) p.traj[item * 3 + lane] = !ok ? qnan : lane == 0 ? sol.t0 : lane == 1 ? sol.t1 : sol.t2;
-    if (p.wsum && lane == 3) p.wsum[item] = ok ? (float)w : 0.f;
+    if (p.wsum && lane == 3) p.wsum[item] = ok ? (float)s[W] : 0.f;
     if (p.resid) {
         double rs = 0.0;
-#pragma unroll KEPT
-        for (int r = 0; r < rounds; ++r) {
-            const RootJoint g = joint(r);
+        joints.for_each([&](const RootJoint& g) {
             const double ex = (tx - g.a * tz) - g.rx, ey = (ty - g.b * tz) - g.ry;
             const double term = g.c * (ex * ex + ey * ey);
             rs += g.on ? term : 0.0;           // a joint that takes no part feeds 0.0 whatever t holds
-        }
+        });
         rs = wave_sum_f64(rs);
-        if (lane == 4) p.resid[item] = ok ? (float)sqrt(rs / w) : qnan;
+        if (lane == 4) p.resid[item] = ok ? (float)sqrt(rs / s[W]) : qnan;
     }
 }
 
-// trajectory_smooth_kernel: the confidence-weighted local-linear filter along the frames (statement:
-// pafuse_amd/trajectory.py smooth).  One thread per (t, n) walks m = max(0, n - r) .. min(N - 1, n + r) in ascending
-// order, d = m - n; taper g = (1 - d*d/(r+1)^2)^2 (the biweight: no transcendental), omega = g * weight[t,m]; a frame
-// takes part if its weight is > 0 (null: 1) and its three components are finite.  S0, S1, S2 = sum omega*(1, d, d*d),
-// Q0, Q1 = sum omega*(y, d*y) per component, D = S0*S2 - S1*S1.  Two frames or more and D finite and > 0: the local
-// line's value at d = 0, (S2*Q0 - S1*Q1)/D; else S0 > 0: Q0/S0; else NaN.  fp64, contraction off, rounded once.
+// The confidence-weighted local-linear filter along the frames on C components (statement: pafuse_amd/trajectory.py
+// local_line), the one filter of trajectory_smooth_kernel (C = 3) and detections_repair_kernel (C = 2).  A thread adds the
+// frames m around its frame n that take part (the caller's test), in ascending order, d = m - n: taper g = (1 - d*d/(r+1)^2)^2
+// (the biweight: no transcendental), omega = g * weight; S0, S1, S2 = sum omega*(1, d, d*d), Q0, Q1 = sum omega*(y, d*y) per
+// component, D = S0*S2 - S1*S1.  Two frames or more and D finite and > 0: LINE_FIT, the local line's value at d = 0,
+// (S2*Q0 - S1*Q1)/D; else S0 > 0: LINE_MEAN, Q0/S0; else LINE_NONE.  fp64, contraction off in every member; the caller
+// rounds once.  The kinds are the status codes 1, 2, 3 of the repair.
+enum LineKind { LINE_FIT = 1, LINE_MEAN = 2, LINE_NONE = 3 };
+
+template <int C>
+struct LineFilter {
+    const double span;
+    double S0 = 0.0, S1 = 0.0, S2 = 0.0, Q0[C] = {}, Q1[C] = {};
+    int cnt = 0;
+
+    __device__ __forceinline__ explicit LineFilter(int radius) : span((double)((radius + 1) * (radius + 1))) {}
+    __device__ __forceinline__ void add(int d, double weight, const double (&y)[C]) {
+#pragma clang fp contract(off)
+        const double dd = (double)d;
+        const double q = (double)(d * d) / span, h = 1.0 - q, g = h * h;
+        const double om = g * weight, omd = om * dd;
+        S0 += om, S1 += omd, S2 += omd * dd;
+#pragma unroll
+        for (int k = 0; k < C; ++k) Q0[k] += om * y[k];
+#pragma unroll
+        for (int k = 0; k < C; ++k) Q1[k] += omd * y[k];
+        ++cnt;
+    }
+    __device__ __forceinline__ LineKind kind() const {
+#pragma clang fp contract(off)
+        const double D = S0 * S2 - S1 * S1;
+        return cnt >= 2 && isfinite(D) && D > 0.0 ? LINE_FIT : S0 > 0.0 ? LINE_MEAN : LINE_NONE;
+    }
+    __device__ __forceinline__ double value(int k) const {   // kind() != LINE_NONE
+#pragma clang fp contract(off)
+        const double D = S0 * S2 - S1 * S1;
+        return kind() == LINE_FIT ? (S2 * Q0[k] - S1 * Q1[k]) / D : Q0[k] / S0;
+    }
+};
+
+// trajectory_smooth_kernel: LineFilter<3> on the roots (statement: pafuse_amd/trajectory.py smooth).  One thread per (t, n)
+// walks m = max(0, n - r) .. min(N - 1, n + r); a frame takes part if its weight is > 0 (null: 1) and its three components
+// are finite.  No line and no mean: NaN.
 struct TrajectorySmoothParams {
     const float* traj;    // [T,N,3]
     const float* weight;  // [T,N] or null
@@ -3729,28 +3802,17 @@ __global__ void __launch_bounds__(256) trajectory_smooth_kernel(const Trajectory
     if (e >= (int64_t)p.T * p.N) return;
     const int n = (int)(e % p.N), r = p.radius;
     const int64_t row0 = e - n;   // (t, 0)
-    const double span = (double)((r + 1) * (r + 1));
-    double S0 = 0.0, S1 = 0.0, S2 = 0.0, Q0[3] = {0.0, 0.0, 0.0}, Q1[3] = {0.0, 0.0, 0.0};
-    int cnt = 0;
+    LineFilter<3> f(r);
     const int lo = max(0, n - r), hi = min(p.N - 1, n + r);
     for (int m = lo; m <= hi; ++m) {
         const float wt = p.weight ? p.weight[row0 + m] : 1.f;
         const float y0 = p.traj[(row0 + m) * 3 + 0], y1 = p.traj[(row0 + m) * 3 + 1], y2 = p.traj[(row0 + m) * 3 + 2];
         if (!(wt > 0.f && isfinite(y0) && isfinite(y1) && isfinite(y2))) continue;
-        const int d = m - n;
-        const double dd = (double)d;
-        const double q = (double)(d * d) / span, h = 1.0 - q, g = h * h;
-        const double om = g * (double)wt, omd = om * dd;
-        S0 += om, S1 += omd, S2 += omd * dd;
-        Q0[0] += om * (double)y0, Q0[1] += om * (double)y1, Q0[2] += om * (double)y2;
-        Q1[0] += omd * (double)y0, Q1[1] += omd * (double)y1, Q1[2] += omd * (double)y2;
-        ++cnt;
+        const double y[3] = {(double)y0, (double)y1, (double)y2};
+        f.add(m - n, (double)wt, y);
     }
-    const double D = S0 * S2 - S1 * S1;
-    const bool line = cnt >= 2 && isfinite(D) && D > 0.0;
 #pragma unroll
-    for (int k = 0; k < 3; ++k)
-        p.out[e * 3 + k] = line ? (float)((S2 * Q0[k] - S1 * Q1[k]) / D) : S0 > 0.0 ? (float)(Q0[k] / S0) : __builtin_nanf("");
+    for (int k = 0; k < 3; ++k) p.out[e * 3 + k] = f.kind() == LINE_NONE ? __builtin_nanf("") : (float)f.value(k);
 }
 
 // detections_repair_kernel: the smoother's filter brought to the 2-D detections, per joint, filling only what is missing
@@ -3759,7 +3821,7 @@ __global__ void __launch_bounds__(256) trajectory_smooth_kernel(const Trajectory
 // one frame at every step of the walk.  Joint j is level 1 iff 0 <= anchor[j] < J and anchor[anchor[j]] < 0 (anchor[anchor[j]]
 // is read only for an in-range anchor[j]); every other joint - and every joint of a null table - is level 0.  A thread whose
 // joint is not of p.level returns without writing.  An observed joint is copied (status 0).  A missing one walks
-// m = max(0, n - r) .. min(N - 1, n + r) with the taper, sums and the line-else-mean rule of trajectory_smooth_kernel over the
+// m = max(0, n - r) .. min(N - 1, n + r) and feeds LineFilter<2> (above: the smoother's own filter) with the
 // frames where (m, j) is observed: level 0 on y = x2d[m,j], level 1 - a = anchor[j] - on y = x2d[m,j] - out[m,a] over the frames
 // where also status[m,a] != 3, the value out[n,a] + line, and only if status[n,a] != 3.  Line: status 1; mean: status 2;
 // neither, or a value that is not finite in fp32: status 3, which keeps the input's bits.  conf_out (may be null) is conf at
@@ -3796,40 +3858,29 @@ __global__ void __launch_bounds__(256) detections_repair_kernel(const Detections
     int st = 3;
     const bool able = !hangs || p.status[(int64_t)n * J + a] != 3;
     if (able) {
-        const double span = (double)((r + 1) * (r + 1));
-        double S0 = 0.0, S1 = 0.0, S2 = 0.0, Q0x = 0.0, Q0y = 0.0, Q1x = 0.0, Q1y = 0.0;
-        int cnt = 0;
+        LineFilter<2> f(r);
         const int lo = max(0, n - r), hi = min(p.N - 1, n + r);
         for (int m = lo; m <= hi; ++m) {
             const int64_t em = (int64_t)m * J + j;
             const float cm = p.conf[em], xm = p.x2d[em * 2], ym = p.x2d[em * 2 + 1];
             if (!(cm > thr && isfinite(xm) && isfinite(ym))) continue;
-            double y0 = (double)xm, y1 = (double)ym;
+            double ys[2] = {(double)xm, (double)ym};
             if (hangs) {
                 const int64_t ea = (int64_t)m * J + a;
                 if (p.status[ea] == 3) continue;
-                y0 = y0 - (double)p.out[ea * 2], y1 = y1 - (double)p.out[ea * 2 + 1];
+                ys[0] = ys[0] - (double)p.out[ea * 2], ys[1] = ys[1] - (double)p.out[ea * 2 + 1];
             }
-            const int d = m - n;
-            const double dd = (double)d;
-            const double q = (double)(d * d) / span, h = 1.0 - q, g = h * h;
-            const double om = g * (double)cm, omd = om * dd;
-            S0 += om, S1 += omd, S2 += omd * dd;
-            Q0x += om * y0, Q0y += om * y1;
-            Q1x += omd * y0, Q1y += omd * y1;
-            ++cnt;
+            f.add(m - n, (double)cm, ys);
         }
-        const double D = S0 * S2 - S1 * S1;
-        const bool line = cnt >= 2 && isfinite(D) && D > 0.0;
-        if (line || S0 > 0.0) {
-            double fx = line ? (S2 * Q0x - S1 * Q1x) / D : Q0x / S0;
-            double fy = line ? (S2 * Q0y - S1 * Q1y) / D : Q0y / S0;
+        const LineKind kind = f.kind();
+        if (kind != LINE_NONE) {
+            double fx = f.value(0), fy = f.value(1);
             if (hangs) {
                 const int64_t ea = (int64_t)n * J + a;
                 fx = (double)p.out[ea * 2] + fx, fy = (double)p.out[ea * 2 + 1] + fy;
             }
             const float gx = (float)fx, gy = (float)fy;
-            if (isfinite(gx) && isfinite(gy)) vx = gx, vy = gy, st = line ? 1 : 2;
+            if (isfinite(gx) && isfinite(gy)) vx = gx, vy = gy, st = kind;   // 1: line, 2: mean
         }
     }
     p.out[e * 2] = vx, p.out[e * 2 + 1] = vy, p.status[e] = (uint8_t)st;
@@ -3844,16 +3895,13 @@ __global__ void __launch_bounds__(256) detections_repair_kernel(const Detections
 // K = <h_perp,h_perp>, H = <h_perp,g_perp>, G = <g_perp,g_perp> per (t, n); focal_solve_kernel sums them over the frames
 // and gives f = K/H (h regressed ON g: the direction that survives pose noise) and r2 = H*H/(G*K).
 //
-// frames_focal_sums_kernel has the structure of frames_root_fit_kernel: one wave per (t, n), four per workgroup; SLOTS >= 1:
-// a lane loads pose, detection and weight of all its <= SLOTS joints (J <= 64*SLOTS) before the first butterfly and
-// keeps c, p, q, X, Y, Z of each in registers; the thirteen sums and the int count go through independent butterfly
-// chains, interleaved step by step.  A joint takes part if its weight is > 0 and its pose finite (the rule of the root
-// fit); a lane or slot without such a joint feeds 0.0 by a select.  SLOTS == 0 is the same arithmetic for any J, round by
-// round.  fp64, contraction off, every product rounded before it is added.  No LDS, no atomics, no scratch.
-// A frame takes part if >= 4 joints are in the sums, den is finite and > 0 and K, H, G are finite: its row is
+// frames_focal_sums_kernel: one wave per (t, n) on LaneJoints<SLOTS> (c, p, q, X, Y, Z per joint); the thirteen sums and
+// the count go through wave_sums.  A joint takes part if its weight is > 0 and its pose finite (the rule of the root
+// fit); a lane or slot without such a joint feeds 0.0 by a select.  fp64, contraction off, every product rounded before
+// it is added.  A frame takes part if >= 4 joints are in the sums, den is finite and > 0 and K, H, G are finite: its row is
 // (K, H, G, 1.0), otherwise (0, 0, 0, 0).
 // focal_solve_kernel: one wave per t; lane l adds frames l, l + 64, ... in ascending order, then the butterfly (the order
-// of frame_errors_reduce_kernel), four chains interleaved.
+// of frame_errors_reduce_kernel), the four slots through wave_sums.
 // ----------------------------------------------------------------------------------------------------------------
 struct FramesFocalSumsParams {
     const float* pose;    // [T,N,J,3] whole-body, root-relative
@@ -3873,8 +3921,8 @@ constexpr int FOCAL_MIN_JOINTS = 4;
 template <int SLOTS>
 __global__ void __launch_bounds__(256) frames_focal_sums_kernel(const FramesFocalSumsParams p) {
 #pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane();
+    const int64_t item = wave_item();
     if (item >= (int64_t)p.T * p.N) return;   // wave-uniform
     const int n = (int)(item % p.N);
     const int J = p.J;
@@ -3882,10 +3930,7 @@ __global__ void __launch_bounds__(256) frames_focal_sums_kernel(const FramesFoca
     const float* x2 = p.x2d + (int64_t)n * J * 2;
     const float* cf = p.conf ? p.conf + (int64_t)n * J : nullptr;
     const double rho = (double)p.cam[1] / (double)p.cam[0], cx = (double)p.cam[2], cy = (double)p.cam[3];
-    constexpr int KEPT = SLOTS > 0 ? SLOTS : 1;
-    const int rounds = SLOTS > 0 ? SLOTS : (J + 63) / 64;
-    FocalJoint kept[KEPT];
-    auto load = [&](int j) -> FocalJoint {
+    const auto load = [&](int j) -> FocalJoint {
         const bool in = j < J;
         const int jj = in ? j : 0;               // J >= 1: a lane past the end reads joint 0 and selects 0.0
         const float cw = cf ? cf[jj] : 1.f;
@@ -3900,42 +3945,27 @@ __global__ void __launch_bounds__(256) frames_focal_sums_kernel(const FramesFoca
         g.on = on;
         return g;
     };
-    auto joint = [&](int r) -> FocalJoint {
-        if constexpr (SLOTS > 0) return kept[r];
-        else return load(r * 64 + lane);
-    };
-#pragma unroll
-    for (int r = 0; r < KEPT; ++r) kept[r] = load(SLOTS > 0 ? r * 64 + lane : J);   // SLOTS == 0: unused
-    double w = 0.0, sp = 0.0, sq = 0.0, spp = 0.0, gx = 0.0, gy = 0.0, gp = 0.0, gg = 0.0;
-    double hxs = 0.0, hys = 0.0, hp = 0.0, hh = 0.0, hg = 0.0;
-    int cnt = 0;
-#pragma unroll KEPT
-    for (int r = 0; r < rounds; ++r) {
-        const FocalJoint g = joint(r);
+    const LaneJoints<SLOTS, decltype(load)> joints(J, load);
+    enum { W, SP, SQ, SPP, GX, GY, GP, GG, HX, HY, HP, HH, HG, SUMS };
+    double s[SUMS] = {};
+    int cnt[1] = {0};
+    joints.for_each([&](const FocalJoint& g) {
         const double hx = g.p * g.Z, hy = g.q * g.Z;
-        w += g.c, sp += g.c * g.p, sq += g.c * g.q, spp += g.c * (g.p * g.p + g.q * g.q);
-        gx += g.c * g.X, gy += g.c * g.Y, gp += g.c * (g.p * g.X + g.q * g.Y), gg += g.c * (g.X * g.X + g.Y * g.Y);
-        hxs += g.c * hx, hys += g.c * hy, hp += g.c * (g.p * hx + g.q * hy);
-        hh += g.c * (hx * hx + hy * hy), hg += g.c * (hx * g.X + hy * g.Y);
-        cnt += g.on;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {   // thirteen independent chains and the count, interleaved
-        const double w2 = __shfl_xor(w, o), sp2 = __shfl_xor(sp, o), sq2 = __shfl_xor(sq, o), spp2 = __shfl_xor(spp, o);
-        const double gx2 = __shfl_xor(gx, o), gy2 = __shfl_xor(gy, o), gp2 = __shfl_xor(gp, o), gg2 = __shfl_xor(gg, o);
-        const double hxs2 = __shfl_xor(hxs, o), hys2 = __shfl_xor(hys, o), hp2 = __shfl_xor(hp, o);
-        const double hh2 = __shfl_xor(hh, o), hg2 = __shfl_xor(hg, o);
-        cnt += __shfl_xor(cnt, o);
-        w += w2, sp += sp2, sq += sq2, spp += spp2, gx += gx2, gy += gy2, gp += gp2, gg += gg2;
-        hxs += hxs2, hys += hys2, hp += hp2, hh += hh2, hg += hg2;
-    }
+        s[W] += g.c, s[SP] += g.c * g.p, s[SQ] += g.c * g.q, s[SPP] += g.c * (g.p * g.p + g.q * g.q);
+        s[GX] += g.c * g.X, s[GY] += g.c * g.Y, s[GP] += g.c * (g.p * g.X + g.q * g.Y), s[GG] += g.c * (g.X * g.X + g.Y * g.Y);
+        s[HX] += g.c * hx, s[HY] += g.c * hy, s[HP] += g.c * (g.p * hx + g.q * hy);
+        s[HH] += g.c * (hx * hx + hy * hy), s[HG] += g.c * (hx * g.X + hy * g.Y);
+        cnt[0] += g.on;
+    });
+    wave_sums(s, cnt);
+    const auto& [w, sp, sq, spp, gx, gy, gp, gg, hxs, hys, hp, hh, hg] = s;   // in the order of the enum
     const double den = spp - (sp * sp + sq * sq) / w;
     const double rg = gp - (sp * gx + sq * gy) / w;
     const double rh = hp - (sp * hxs + sq * hys) / w;
     const double K = (hh - (hxs * hxs + hys * hys) / w) - (rh * rh) / den;
     const double H = (hg - (hxs * gx + hys * gy) / w) - (rh * rg) / den;
     const double G = (gg - (gx * gx + gy * gy) / w) - (rg * rg) / den;
-    const bool part = cnt >= FOCAL_MIN_JOINTS && isfinite(den) && den > 0.0 && isfinite(K) && isfinite(H) && isfinite(G);
+    const bool part = cnt[0] >= FOCAL_MIN_JOINTS && isfinite(den) && den > 0.0 && isfinite(K) && isfinite(H) && isfinite(G);
     const double v = lane == 0 ? K : lane == 1 ? H : lane == 2 ? G : 1.0;   // lane k writes slot k
     if (lane < 4) p.state[item * 4 + lane] = part ? v : 0.0;
 }
@@ -3952,20 +3982,17 @@ struct FocalSolveParams {
 
 __global__ void __launch_bounds__(256) focal_solve_kernel(const FocalSolveParams p) {
 #pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane();
+    const int64_t t = wave_item();
     if (t >= p.T) return;   // wave-uniform
     const double* row = p.state + t * p.N * 4;
-    double K = 0.0, H = 0.0, G = 0.0, C = 0.0;
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};   // the slots of a state row: K, H, G and the frames that take part
     for (int n = lane; n < p.N; n += 64) {
         const double* s = row + (int64_t)n * 4;
-        K += s[0], H += s[1], G += s[2], C += s[3];
+        sum[0] += s[0], sum[1] += s[1], sum[2] += s[2], sum[3] += s[3];
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const double k2 = __shfl_xor(K, o), h2 = __shfl_xor(H, o), g2 = __shfl_xor(G, o), c2 = __shfl_xor(C, o);
-        K += k2, H += h2, G += g2, C += c2;
-    }
+    wave_sums(sum);
+    const auto& [K, H, G, C] = sum;
     const bool ok = C >= 1.0 && K > 0.0 && H > 0.0;
     const float qnan = __builtin_nanf("");
     const double f = K / H;
@@ -3995,12 +4022,9 @@ __global__ void __launch_bounds__(256) focal_solve_kernel(const FocalSolveParams
 //   6+i          |d[n,j] - d[n,pbroot[j]]| over the joints of part i whose part root takes part too (metrics_kernel's epb)
 // A slot that is not defined for a frame or has no participant holds 0.0 and 0.
 //
-// frame_errors_kernel: one wave per (t, n), four per workgroup; lane l owns joints l, l + 64, ... in ascending order.  The
-// rows of frames n-1 and n+1 are read again by the neighbouring waves (up to 3x the bytes of a row; L2 is expected to
-// serve them).  SLOTS >= 1: a lane loads all its <= SLOTS joints (J <= 64*SLOTS) before it adds the first term;
-// SLOTS == 0 is the same arithmetic for any J, round by round.  The per-lane sums of slots 0, 1, 2, 5 and the <= 4 parts
-// go through eight independent butterfly chains (xor 32 .. 1, as wave_sum_f64), interleaved, beside their int counts;
-// slots 3 and 4 hold one term.  A lane (or slot) without a joint feeds 0.0.  No LDS, no atomics, no scratch.
+// frame_errors_kernel: one wave per (t, n) on LaneJoints<SLOTS>.  The rows of frames n-1 and n+1 are read again by the
+// neighbouring waves (up to 3x the bytes of a row; L2 is expected to serve them).  The per-lane sums of slots 0, 1, 2, 5
+// and the <= 4 parts go through wave_sums beside their int counts; slots 3 and 4 hold one term.
 // frame_errors_reduce_kernel: one wave per (t, k); lane l adds frames l, l + 64, ... in ascending order, then the same
 // butterfly: sums double [T,K], counts int64 [T,K], the same bits for every launch shape.
 // ----------------------------------------------------------------------------------------------------------------
@@ -4041,8 +4065,8 @@ __device__ __forceinline__ double frame_norm(double v0, double v1, double v2) {
 template <int SLOTS>
 __global__ void __launch_bounds__(256) frame_errors_kernel(const FrameErrorsParams p) {
 #pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = wave_lane();
+    const int64_t item = wave_item();
     if (item >= (int64_t)p.T * p.N) return;   // wave-uniform
     const int n = (int)(item % p.N);
     const int J = p.J, N = p.N;
@@ -4056,10 +4080,7 @@ __global__ void __launch_bounds__(256) frame_errors_kernel(const FrameErrorsPara
         ron1 = frame_diff(p.traj + item * 3, p.gt_root + (int64_t)n * 3, r1);
         if (n >= 1) ron0 = frame_diff(p.traj + (item - 1) * 3, p.gt_root + (int64_t)(n - 1) * 3, r0);
     }
-    constexpr int KEPT = SLOTS > 0 ? SLOTS : 1;
-    const int rounds = SLOTS > 0 ? SLOTS : (J + 63) / 64;
-    FrameJoint q[KEPT];
-    auto load = [&](int j) -> FrameJoint {
+    const auto load = [&](int j) -> FrameJoint {
         FrameJoint g;
 #pragma unroll
         for (int m = 0; m < 3; ++m) g.on[m] = false, g.d[m][0] = g.d[m][1] = g.d[m][2] = 0.0;
@@ -4076,19 +4097,11 @@ __global__ void __launch_bounds__(256) frame_errors_kernel(const FrameErrorsPara
         }
         return g;
     };
-    auto joint = [&](int r) -> FrameJoint {
-        if constexpr (SLOTS > 0) return q[r];
-        else return load(r * 64 + lane);
-    };
-#pragma unroll
-    for (int r = 0; r < KEPT; ++r) q[r] = load(SLOTS > 0 ? r * 64 + lane : J);   // SLOTS == 0: unused
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s5 = 0.0, sp[FRAME_MAX_PARTS];
-    int c0 = 0, c1 = 0, c2 = 0, c5 = 0, cp[FRAME_MAX_PARTS];
-#pragma unroll
-    for (int i = 0; i < FRAME_MAX_PARTS; ++i) sp[i] = 0.0, cp[i] = 0;
-#pragma unroll KEPT
-    for (int r = 0; r < rounds; ++r) {
-        const FrameJoint g = joint(r);
+    const LaneJoints<SLOTS, decltype(load)> joints(J, load);
+    enum { MPJPE, MPJVE, ACCEL, ABS, PART, SUMS = PART + FRAME_MAX_PARTS };   // the slots that are sums over the joints
+    double s[SUMS] = {};
+    int c[SUMS] = {};
+    joints.for_each([&](const FrameJoint& g) {
         const double(&a)[3] = g.d[0];
         const double(&d)[3] = g.d[1];
         const double(&z)[3] = g.d[2];
@@ -4098,38 +4111,26 @@ __global__ void __launch_bounds__(256) frame_errors_kernel(const FrameErrorsPara
         const double e2 = frame_norm((z[0] - d[0]) - (d[0] - a[0]), (z[1] - d[1]) - (d[1] - a[1]), (z[2] - d[2]) - (d[2] - a[2]));
         const double e5 = frame_norm(d[0] + r1[0], d[1] + r1[1], d[2] + r1[2]);
         const double eb = frame_norm(d[0] - g.b[0], d[1] - g.b[1], d[2] - g.b[2]);
-        s0 += g.on[1] ? e0 : 0.0, c0 += g.on[1];      // a joint that takes no part feeds 0.0 whatever it holds
-        s1 += in01 ? e1 : 0.0, c1 += in01;
-        s2 += in012 ? e2 : 0.0, c2 += in012;
-        s5 += in5 ? e5 : 0.0, c5 += in5;
+        s[MPJPE] += g.on[1] ? e0 : 0.0, c[MPJPE] += g.on[1];      // a joint that takes no part feeds 0.0 whatever it holds
+        s[MPJVE] += in01 ? e1 : 0.0, c[MPJVE] += in01;
+        s[ACCEL] += in012 ? e2 : 0.0, c[ACCEL] += in012;
+        s[ABS] += in5 ? e5 : 0.0, c[ABS] += in5;
 #pragma unroll
         for (int i = 0; i < FRAME_MAX_PARTS; ++i) {
             const bool mine = inb && g.part == i;
-            sp[i] += mine ? eb : 0.0, cp[i] += mine;
+            s[PART + i] += mine ? eb : 0.0, c[PART + i] += mine;
         }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {   // eight independent chains and their counts, interleaved
-        const double t0 = __shfl_xor(s0, o), t1 = __shfl_xor(s1, o), t2 = __shfl_xor(s2, o), t5 = __shfl_xor(s5, o);
-        double tp[FRAME_MAX_PARTS];
-#pragma unroll
-        for (int i = 0; i < FRAME_MAX_PARTS; ++i) tp[i] = __shfl_xor(sp[i], o);
-        c0 += __shfl_xor(c0, o), c1 += __shfl_xor(c1, o), c2 += __shfl_xor(c2, o), c5 += __shfl_xor(c5, o);
-#pragma unroll
-        for (int i = 0; i < FRAME_MAX_PARTS; ++i) cp[i] += __shfl_xor(cp[i], o);
-        s0 += t0, s1 += t1, s2 += t2, s5 += t5;
-#pragma unroll
-        for (int i = 0; i < FRAME_MAX_PARTS; ++i) sp[i] += tp[i];
-    }
+    });
+    wave_sums(s, c);
     const bool in4 = ron0 && ron1;
     const double e3 = ron1 ? frame_norm(r1[0], r1[1], r1[2]) : 0.0;
     const double e4 = in4 ? frame_norm(r1[0] - r0[0], r1[1] - r0[1], r1[2] - r0[2]) : 0.0;
     // lane k writes slot k
-    const double v = lane == 0 ? s0 : lane == 1 ? s1 : lane == 2 ? s2 : lane == 3 ? e3 : lane == 4 ? e4 : lane == 5 ? s5
-                   : lane == 6 ? sp[0] : lane == 7 ? sp[1] : lane == 8 ? sp[2] : sp[3];
-    const int c = lane == 0 ? c0 : lane == 1 ? c1 : lane == 2 ? c2 : lane == 3 ? (int)ron1 : lane == 4 ? (int)in4 : lane == 5 ? c5
-                : lane == 6 ? cp[0] : lane == 7 ? cp[1] : lane == 8 ? cp[2] : cp[3];
-    if (lane < p.K) p.err[item * p.K + lane] = v, p.cnt[item * p.K + lane] = c;
+    const double v = lane == 0 ? s[MPJPE] : lane == 1 ? s[MPJVE] : lane == 2 ? s[ACCEL] : lane == 3 ? e3 : lane == 4 ? e4 : lane == 5 ? s[ABS]
+                   : lane == 6 ? s[PART] : lane == 7 ? s[PART + 1] : lane == 8 ? s[PART + 2] : s[PART + 3];
+    const int k = lane == 0 ? c[MPJPE] : lane == 1 ? c[MPJVE] : lane == 2 ? c[ACCEL] : lane == 3 ? (int)ron1 : lane == 4 ? (int)in4 : lane == 5 ? c[ABS]
+                : lane == 6 ? c[PART] : lane == 7 ? c[PART + 1] : lane == 8 ? c[PART + 2] : c[PART + 3];
+    if (lane < p.K) p.err[item * p.K + lane] = v, p.cnt[item * p.K + lane] = k;
 }
 
 struct FrameErrorsReduceParams {
@@ -4142,18 +4143,16 @@ struct FrameErrorsReduceParams {
 
 __global__ void __launch_bounds__(256) frame_errors_reduce_kernel(const FrameErrorsReduceParams p) {
 #pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // (t, k)
+    const int lane = wave_lane();
+    const int64_t item = wave_item();   // (t, k)
     if (item >= (int64_t)p.T * p.K) return;   // wave-uniform
     const int k = (int)(item % p.K);
     const int64_t row0 = (item / p.K) * p.N;   // (t, 0)
-    double s = 0.0;
-    long long c = 0;
-    for (int n = lane; n < p.N; n += 64) s += p.err[(row0 + n) * p.K + k], c += p.cnt[(row0 + n) * p.K + k];
-    s = wave_sum_f64(s);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o);
-    if (lane == 0) p.sums[item] = s, p.counts[item] = (int64_t)c;
+    double s[1] = {0.0};
+    long long c[1] = {0};
+    for (int n = lane; n < p.N; n += 64) s[0] += p.err[(row0 + n) * p.K + k], c[0] += p.cnt[(row0 + n) * p.K + k];
+    wave_sums(s, c);
+    if (lane == 0) p.sums[item] = s[0], p.counts[item] = (int64_t)c[0];
 }
 
 // ----------------------------------------------------------------------------------------------------------------

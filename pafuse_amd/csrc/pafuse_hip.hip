@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "kernels.hpp"
 #include "hgemm.hpp"
@@ -72,6 +73,26 @@ int launch(const char* name, dim3 grid, unsigned threads, size_t lds, hipStream_
     return launch_lds<Kernel>(name, grid, threads, lds, lds, s, args...);
 }
 inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+
+// the grid of a kernel that runs one wave per item, four per workgroup (kernels.hpp wave_item), refused if out of range
+int wave_grid(const char* who, int64_t waves, unsigned& grid) {
+    if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "%s: grid out of range", who);
+    grid = blocks_for(waves, 4);
+    return PAFUSE_OK;
+}
+
+// f(std::integral_constant<int, SLOTS>) for the LaneJoints form that holds J joints: a lane's joints in registers up to
+// J = 256 (SLOTS 1 .. 4); beyond, the same arithmetic round by round (SLOTS 0)
+template <class F>
+int by_joint_slots(int J, F&& f) {
+    switch ((J + 63) / 64) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        default: return f(std::integral_constant<int, 0>{});
+    }
+}
 
 // Makes the device of the caller's stream current for the duration of an entry point (kernel launches, events and
 // function attributes go to the CURRENT device): a caller whose tensors live on cuda:1 while cuda:0 is current
@@ -1954,12 +1975,12 @@ int pafuse_pose_partials_fit(const float* pred, const float* x2d, const float* c
     hipStream_t s = (hipStream_t)stream;
     if (B == 0 || P_r == 0) return neutral_state("pose_partials_fit", v, n, s);   // no kernel runs, tfit is empty
     if (!pred || !conn) return fail(PAFUSE_E_ARG, "pose_partials_fit: null pointer");
-    const int64_t waves = (int64_t)B * T * F;   // one wave per (b, t, f), four per workgroup
-    if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "pose_partials_fit: grid out of range");
+    unsigned grid;
+    if (int rc = wave_grid("pose_partials_fit", (int64_t)B * T * F, grid)) return rc;   // one wave per (b, t, f)
     PoseFitParams m{};
     m.pred = pred, m.x2d = x2d, m.conf = conf, m.cam = cam, m.conn = conn, m.st = v, m.tfit = tfit;
     m.B = B, m.T = T, m.P = P_r, m.F = F, m.J = J, m.h0 = h0;
-    return launch<pose_fit_partials_kernel>("pose_fit_partials_kernel", blocks_for(waves, 4), 256, 0, s, m);
+    return launch<pose_fit_partials_kernel>("pose_fit_partials_kernel", grid, 256, 0, s, m);
 }
 
 int pafuse_pose_combine(const void* states, int32_t W, size_t stride_bytes, int32_t B, int32_t T, int32_t F, int32_t J,
@@ -2156,21 +2177,13 @@ int pafuse_frames_root_fit(const float* pose, const float* x2d, const float* con
                            int32_t J, float* traj, float* wsum, float* resid, void* stream) {
     if (!pose || !x2d || !cam || !traj) return fail(PAFUSE_E_ARG, "frames_root_fit: pose, x2d, cam and traj are needed (conf, wsum, resid may be null)");
     if (T < 1 || N < 1 || J < 1) return fail(PAFUSE_E_ARG, "frames_root_fit: bad size (T=%d N=%d J=%d)", T, N, J);
-    const int64_t waves = (int64_t)T * N;   // one wave per (t, n), four per workgroup
-    if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "frames_root_fit: grid out of range");
+    unsigned grid;
+    if (int rc = wave_grid("frames_root_fit", (int64_t)T * N, grid)) return rc;   // one wave per (t, n)
     StreamDevice on_stream_device(stream);
     FramesRootFitParams m{};
     m.pose = pose, m.x2d = x2d, m.conf = conf, m.cam = cam, m.traj = traj, m.wsum = wsum, m.resid = resid;
     m.T = T, m.N = N, m.J = J;
-    const unsigned grid = blocks_for(waves, 4);
-    hipStream_t s = (hipStream_t)stream;
-    switch ((J + 63) / 64) {   // the joints of a lane in registers up to J = 256; beyond, the same arithmetic round by round
-        case 1: return launch<frames_root_fit_kernel<1>>("frames_root_fit_kernel", grid, 256, 0, s, m);
-        case 2: return launch<frames_root_fit_kernel<2>>("frames_root_fit_kernel", grid, 256, 0, s, m);
-        case 3: return launch<frames_root_fit_kernel<3>>("frames_root_fit_kernel", grid, 256, 0, s, m);
-        case 4: return launch<frames_root_fit_kernel<4>>("frames_root_fit_kernel", grid, 256, 0, s, m);
-        default: return launch<frames_root_fit_kernel<0>>("frames_root_fit_kernel", grid, 256, 0, s, m);
-    }
+    return by_joint_slots(J, [&](auto slots) { return launch<frames_root_fit_kernel<decltype(slots)::value>>("frames_root_fit_kernel", grid, 256, 0, (hipStream_t)stream, m); });
 }
 
 // the confidence-weighted local-linear filter along the frames (trajectory_smooth_kernel)
@@ -2219,21 +2232,13 @@ int pafuse_frames_focal_sums(const float* pose, const float* x2d, const float* c
     if (!pose || !x2d || !cam || !state) return fail(PAFUSE_E_ARG, "frames_focal_sums: pose, x2d, cam and state are needed (conf may be null)");
     if (T < 1 || N < 1 || J < 1) return fail(PAFUSE_E_ARG, "frames_focal_sums: bad size (T=%d N=%d J=%d)", T, N, J);
     if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "frames_focal_sums: state must be 8-byte aligned");
-    const int64_t waves = (int64_t)T * N;   // one wave per (t, n), four per workgroup
-    if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "frames_focal_sums: grid out of range");
+    unsigned grid;
+    if (int rc = wave_grid("frames_focal_sums", (int64_t)T * N, grid)) return rc;   // one wave per (t, n)
     StreamDevice on_stream_device(stream);
     FramesFocalSumsParams m{};
     m.pose = pose, m.x2d = x2d, m.conf = conf, m.cam = cam, m.state = state;
     m.T = T, m.N = N, m.J = J;
-    const unsigned grid = blocks_for(waves, 4);
-    hipStream_t s = (hipStream_t)stream;
-    switch ((J + 63) / 64) {   // the joints of a lane in registers up to J = 256; beyond, the same arithmetic round by round
-        case 1: return launch<frames_focal_sums_kernel<1>>("frames_focal_sums_kernel", grid, 256, 0, s, m);
-        case 2: return launch<frames_focal_sums_kernel<2>>("frames_focal_sums_kernel", grid, 256, 0, s, m);
-        case 3: return launch<frames_focal_sums_kernel<3>>("frames_focal_sums_kernel", grid, 256, 0, s, m);
-        case 4: return launch<frames_focal_sums_kernel<4>>("frames_focal_sums_kernel", grid, 256, 0, s, m);
-        default: return launch<frames_focal_sums_kernel<0>>("frames_focal_sums_kernel", grid, 256, 0, s, m);
-    }
+    return by_joint_slots(J, [&](auto slots) { return launch<frames_focal_sums_kernel<decltype(slots)::value>>("frames_focal_sums_kernel", grid, 256, 0, (hipStream_t)stream, m); });
 }
 
 int pafuse_focal_solve(const double* state, int32_t T, int32_t N, const float* cam, int32_t cam_len, float* focal, float* r2,
@@ -2242,11 +2247,13 @@ int pafuse_focal_solve(const double* state, int32_t T, int32_t N, const float* c
     if (T < 1 || N < 1) return fail(PAFUSE_E_ARG, "focal_solve: bad size (T=%d N=%d)", T, N);
     if (cam_len < 4 || cam_len > 9) return fail(PAFUSE_E_ARG, "focal_solve: cam_len %d outside 4 .. 9", cam_len);
     if ((uintptr_t)state % 8) return fail(PAFUSE_E_ARG, "focal_solve: state must be 8-byte aligned");
+    unsigned grid;
+    if (int rc = wave_grid("focal_solve", (int64_t)T, grid)) return rc;   // one wave per t
     StreamDevice on_stream_device(stream);
     FocalSolveParams m{};
     m.state = state, m.cam = cam, m.focal = focal, m.r2 = r2, m.frames = frames, m.cam_out = cam_out;
     m.T = T, m.N = N, m.cam_len = cam_len;
-    return launch<focal_solve_kernel>("focal_solve_kernel", blocks_for((int64_t)T, 4), 256, 0, (hipStream_t)stream, m);   // one wave per t
+    return launch<focal_solve_kernel>("focal_solve_kernel", grid, 256, 0, (hipStream_t)stream, m);
 }
 
 // the frame-level errors of the per-frame pose against ground truth (frame_errors_kernel) and their sums over the frames
@@ -2260,21 +2267,13 @@ int pafuse_frame_errors(const float* pose, const float* gt, const float* traj, c
     if ((traj == nullptr) != (gt_root == nullptr)) return fail(PAFUSE_E_ARG, "frame_errors: traj and gt_root come together (or neither)");
     if (T < 1 || N < 1 || J < 1) return fail(PAFUSE_E_ARG, "frame_errors: bad size (T=%d N=%d J=%d)", T, N, J);
     if (num_parts < 1 || num_parts > PAFUSE_MAX_PARTS) return fail(PAFUSE_E_SHAPE, "frame_errors: num_parts %d outside 1 .. %d", num_parts, PAFUSE_MAX_PARTS);
-    const int64_t waves = (int64_t)T * N;   // one wave per (t, n), four per workgroup
-    if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "frame_errors: grid out of range");
+    unsigned grid;
+    if (int rc = wave_grid("frame_errors", (int64_t)T * N, grid)) return rc;   // one wave per (t, n)
     StreamDevice on_stream_device(stream);
     FrameErrorsParams m{};
     m.pose = pose, m.gt = gt, m.traj = traj, m.gt_root = gt_root, m.pbroot = pbroot, m.part = part, m.err = err, m.cnt = cnt;
     m.T = T, m.N = N, m.J = J, m.K = 6 + num_parts;
-    const unsigned grid = blocks_for(waves, 4);
-    hipStream_t s = (hipStream_t)stream;
-    switch ((J + 63) / 64) {   // the joints of a lane in registers up to J = 256; beyond, the same arithmetic round by round
-        case 1: return launch<frame_errors_kernel<1>>("frame_errors_kernel", grid, 256, 0, s, m);
-        case 2: return launch<frame_errors_kernel<2>>("frame_errors_kernel", grid, 256, 0, s, m);
-        case 3: return launch<frame_errors_kernel<3>>("frame_errors_kernel", grid, 256, 0, s, m);
-        case 4: return launch<frame_errors_kernel<4>>("frame_errors_kernel", grid, 256, 0, s, m);
-        default: return launch<frame_errors_kernel<0>>("frame_errors_kernel", grid, 256, 0, s, m);
-    }
+    return by_joint_slots(J, [&](auto slots) { return launch<frame_errors_kernel<decltype(slots)::value>>("frame_errors_kernel", grid, 256, 0, (hipStream_t)stream, m); });
 }
 
 int pafuse_frame_errors_reduce(const double* err, const int32_t* cnt, int32_t T, int32_t N, int32_t K, double* sums,
@@ -2282,12 +2281,12 @@ int pafuse_frame_errors_reduce(const double* err, const int32_t* cnt, int32_t T,
     if (!err || !cnt || !sums || !counts) return fail(PAFUSE_E_ARG, "frame_errors_reduce: null pointer");
     if (T < 1 || N < 1) return fail(PAFUSE_E_ARG, "frame_errors_reduce: bad size (T=%d N=%d)", T, N);
     if (K < 7 || K > 6 + PAFUSE_MAX_PARTS) return fail(PAFUSE_E_SHAPE, "frame_errors_reduce: K = %d outside 7 .. %d (6 + num_parts)", K, 6 + PAFUSE_MAX_PARTS);
-    const int64_t waves = (int64_t)T * K;   // one wave per (t, k), four per workgroup
-    if ((waves + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "frame_errors_reduce: grid out of range");
+    unsigned grid;
+    if (int rc = wave_grid("frame_errors_reduce", (int64_t)T * K, grid)) return rc;   // one wave per (t, k)
     StreamDevice on_stream_device(stream);
     FrameErrorsReduceParams m{};
     m.err = err, m.cnt = cnt, m.sums = sums, m.counts = counts, m.T = T, m.N = N, m.K = K;
-    return launch<frame_errors_reduce_kernel>("frame_errors_reduce_kernel", blocks_for(waves, 4), 256, 0, (hipStream_t)stream, m);
+    return launch<frame_errors_reduce_kernel>("frame_errors_reduce_kernel", grid, 256, 0, (hipStream_t)stream, m);
 }
 
 int pafuse_procrustes_errors(const float* pred, const float* gt, const float* x2d, const float* traj, const float* cam,

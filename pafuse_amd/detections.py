@@ -39,7 +39,9 @@ This module is test infrastructure and the documentation of the arithmetic.  The
 """
 import numpy as np
 
-OBSERVED, FILLED, HELD, UNFILLED = 0, 1, 2, 3
+from .trajectory import LINE, MEAN, NONE, local_line      # the smoother's filter: x2d [N,J,2] has its frames on axis 0 already
+
+OBSERVED, FILLED, HELD, UNFILLED = 0, LINE, MEAN, NONE
 STATUS_NAMES = ("observed", "filled", "held", "unfilled")
 DROPPED_XY = (-1.0, -1.0)      # what a planted dropout holds: about what pixel (0, 0) normalises to on the H3WB cameras
 
@@ -67,40 +69,6 @@ def check_anchor(anchor, J):
         raise ValueError(f"anchor[{j}] = {int(a[j])} is out of range, the joint itself or an anchored joint (one anchor level only): "
                          f"the repair would treat joint {j} as unanchored")
     return a.astype(np.int32)
-
-
-def _fill(y, part, w64, r):
-    """the smoother's sums for every (n, k): y [N,K,2] fp64, part [N,K] bool, w64 [N,K] fp64 ->
-    (value [N,K,2] fp64 before its rounding, code [N,K]: FILLED, HELD or UNFILLED)"""
-    N, K = part.shape
-    S0, S1, S2 = np.zeros((N, K)), np.zeros((N, K)), np.zeros((N, K))
-    Q0, Q1 = np.zeros((N, K, 2)), np.zeros((N, K, 2))
-    cnt = np.zeros((N, K), dtype=np.int64)
-    n = np.arange(N)
-    span = np.float64((r + 1) * (r + 1))
-    for d in range(-r, r + 1):                                        # ascending m = n + d
-        m = n + d
-        inside = (m >= 0) & (m < N)
-        mc = np.clip(m, 0, N - 1)
-        take = part[mc] & inside[:, None]
-        q = np.float64(d * d) / span
-        h = 1.0 - q
-        g = h * h
-        om = g * w64[mc]
-        omd = om * np.float64(d)
-        S0 = S0 + np.where(take, om, 0.0)
-        S1 = S1 + np.where(take, omd, 0.0)
-        S2 = S2 + np.where(take, omd * np.float64(d), 0.0)
-        Q0 = Q0 + np.where(take[..., None], om[..., None] * y[mc], 0.0)
-        Q1 = Q1 + np.where(take[..., None], omd[..., None] * y[mc], 0.0)
-        cnt = cnt + take
-    D = S0 * S2 - S1 * S1
-    line = (cnt >= 2) & np.isfinite(D) & (D > 0)
-    val_line = (S2[..., None] * Q0 - S1[..., None] * Q1) / D[..., None]
-    val_mean = Q0 / S0[..., None]
-    value = np.where(line[..., None], val_line, val_mean)
-    code = np.where(line, FILLED, np.where(S0 > 0, HELD, UNFILLED)).astype(np.uint8)
-    return value, code
 
 
 def repair(x2d, conf, anchor=None, radius=13, threshold=0.0):
@@ -134,14 +102,14 @@ def repair(x2d, conf, anchor=None, radius=13, threshold=0.0):
             status[:, cols] = st
 
         j0 = np.nonzero(~lvl1)[0]
-        value, code = _fill(x64[:, j0], observed[:, j0], w64[:, j0], r)
+        value, code = local_line(x64[:, j0], observed[:, j0], w64[:, j0], r)
         settle(j0, value.astype(np.float32), code, np.ones((N, j0.size), dtype=bool))
         j1 = np.nonzero(lvl1)[0]
         if j1.size:
             a = np.asarray(anchor).astype(np.int64)[j1]
             base = out[:, a].astype(np.float64)                          # level 0's finished output
             able = status[:, a] != UNFILLED
-            value, code = _fill(x64[:, j1] - base, observed[:, j1] & able, w64[:, j1], r)
+            value, code = local_line(x64[:, j1] - base, observed[:, j1] & able, w64[:, j1], r)
             settle(j1, (base + value).astype(np.float32), code, able)
     conf_out = np.where(status == OBSERVED, conf, np.float32(0)).astype(np.float32)
     return out, conf_out, status

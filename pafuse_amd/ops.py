@@ -1343,6 +1343,22 @@ def finish_frames(N, T, J, frame=None, spread=None, want=None):
 TRAJECTORY_OUTPUTS = ("traj", "wsum", "resid")
 
 
+def _frame_pose_operands(who, pose, x2d, cam, conf):
+    """pose [T,N,J,3] beside its detections x2d [N,J,2], cam [>= 4] and conf [N,J] or None, as fit_trajectory and focal_sums take them"""
+    _need(isinstance(pose, torch.Tensor) and pose.dim() == 4 and pose.shape[-1] == 3, f"{who}: pose must be [T,N,J,3]")
+    T, N, J = (int(v) for v in pose.shape[:3])
+    _need(T > 0 and N > 0 and J > 0, f"{who}: T, N, J > 0")
+    _need(x2d is not None and cam is not None, f"{who}: x2d and cam are needed")
+    _need(tuple(x2d.shape) == (N, J, 2) and cam.dim() == 1 and cam.numel() >= 4 and (conf is None or tuple(conf.shape) == (N, J)),
+          f"{who}: x2d [N,J,2], cam [>= 4] and conf [N,J] must match pose [T,N,J,3]")
+    _need_tensors(who, [pose, x2d, cam] + ([] if conf is None else [conf]), ())
+    return T, N, J
+
+
+def _need_radius(who, radius):
+    _need(not isinstance(radius, bool) and int(radius) == radius and 1 <= int(radius) <= 64, f"{who}: radius must be an integer in 1 .. 64, got {radius!r}")
+
+
 def fit_trajectory(pose, x2d, cam, conf=None, want=TRAJECTORY_OUTPUTS):
     """pafuse_frames_root_fit: pose [T,N,J,3] the finished whole-body, root-relative pose of every (t, frame) (finish_frames'
     "mean" or "pick", or stitched clips), x2d [N,J,2] screen-normalised detections, cam [>= 4] (fx fy cx cy first), conf
@@ -1353,13 +1369,7 @@ def fit_trajectory(pose, x2d, cam, conf=None, want=TRAJECTORY_OUTPUTS):
     lib = _lib.load()
     want = tuple(want)
     _need(all(k in TRAJECTORY_OUTPUTS for k in want) and "traj" in want, f'fit_trajectory: want holds "traj" and any of wsum, resid - got {want}')
-    _need(isinstance(pose, torch.Tensor) and pose.dim() == 4 and pose.shape[-1] == 3, "fit_trajectory: pose must be [T,N,J,3]")
-    T, N, J = (int(v) for v in pose.shape[:3])
-    _need(T > 0 and N > 0 and J > 0, "fit_trajectory: T, N, J > 0")
-    _need(x2d is not None and cam is not None, "fit_trajectory: x2d and cam are needed")
-    _need(tuple(x2d.shape) == (N, J, 2) and cam.dim() == 1 and cam.numel() >= 4 and (conf is None or tuple(conf.shape) == (N, J)),
-          "fit_trajectory: x2d [N,J,2], cam [>= 4] and conf [N,J] must match pose [T,N,J,3]")
-    _need_tensors("fit_trajectory", [pose, x2d, cam] + ([] if conf is None else [conf]), ())
+    T, N, J = _frame_pose_operands("fit_trajectory", pose, x2d, cam, conf)
     dev = pose.device
     out = {k: torch.empty((T, N, 3) if k == "traj" else (T, N), device=dev, dtype=torch.float32) for k in want}
     ptr = lambda k: out[k].data_ptr() if k in out else None
@@ -1378,8 +1388,7 @@ def smooth_trajectory(traj, weight, radius, out=None):
     _need(isinstance(traj, torch.Tensor) and traj.dim() == 3 and traj.shape[-1] == 3, "smooth_trajectory: traj must be [T,N,3]")
     T, N = int(traj.shape[0]), int(traj.shape[1])
     _need(T > 0 and N > 0, "smooth_trajectory: T, N > 0")
-    _need(not isinstance(radius, bool) and int(radius) == radius and 1 <= int(radius) <= 64,
-          f"smooth_trajectory: radius must be an integer in 1 .. 64, got {radius!r}")
+    _need_radius("smooth_trajectory", radius)
     _need(weight is None or tuple(weight.shape) == (T, N), "smooth_trajectory: weight must be [T,N]")
     if out is None:
         out = torch.empty_like(traj)
@@ -1437,8 +1446,7 @@ def repair_detections(x2d, conf, anchor=None, radius=13, threshold=0.0, want=("x
     N, J = int(x2d.shape[0]), int(x2d.shape[1])
     _need(N > 0 and J > 0, "repair_detections: N, J > 0")
     _need(isinstance(conf, torch.Tensor) and tuple(conf.shape) == (N, J), "repair_detections: conf must be [N,J]")
-    _need(not isinstance(radius, bool) and int(radius) == radius and 1 <= int(radius) <= 64,
-          f"repair_detections: radius must be an integer in 1 .. 64, got {radius!r}")
+    _need_radius("repair_detections", radius)
     threshold = float(threshold)
     _need(threshold == threshold and 0.0 <= threshold < float("inf"), f"repair_detections: threshold must be finite and >= 0, got {threshold!r}")
     table = None if anchor is None else repair_anchor_table(anchor, J)      # refused here, before anything touches the device
@@ -1466,13 +1474,7 @@ def focal_sums(pose, x2d, cam, conf=None):
     zeros for a frame that takes no part (pafuse_amd.focal states the arithmetic).  States of several videos of one camera
     concatenate along N."""
     lib = _lib.load()
-    _need(isinstance(pose, torch.Tensor) and pose.dim() == 4 and pose.shape[-1] == 3, "focal_sums: pose must be [T,N,J,3]")
-    T, N, J = (int(v) for v in pose.shape[:3])
-    _need(T > 0 and N > 0 and J > 0, "focal_sums: T, N, J > 0")
-    _need(x2d is not None and cam is not None, "focal_sums: x2d and cam are needed")
-    _need(tuple(x2d.shape) == (N, J, 2) and cam.dim() == 1 and cam.numel() >= 4 and (conf is None or tuple(conf.shape) == (N, J)),
-          "focal_sums: x2d [N,J,2], cam [>= 4] and conf [N,J] must match pose [T,N,J,3]")
-    _need_tensors("focal_sums", [pose, x2d, cam] + ([] if conf is None else [conf]), ())
+    T, N, J = _frame_pose_operands("focal_sums", pose, x2d, cam, conf)
     out = torch.empty(T, N, 4, device=pose.device, dtype=torch.float64)
     with torch.cuda.device(pose.device):
         _lib.check(lib.pafuse_frames_focal_sums(pose.data_ptr(), x2d.data_ptr(), None if conf is None else conf.data_ptr(),

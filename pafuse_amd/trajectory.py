@@ -80,6 +80,44 @@ def fit_frames(pose, x2d, conf, cam):
     return traj, wsum, resid
 
 
+LINE, MEAN, NONE = 1, 2, 3     # what local_line found at a frame (the status codes 1, 2, 3 of pafuse_amd.detections)
+
+
+def local_line(y, part, w64, r):
+    """THE filter above, on any number of tracks and components at once, the frames on axis 0: y [N,...,C] fp64, part [N,...]
+    bool (the frames that take part), w64 [N,...] fp64 ->
+    (value [N,...,C] fp64 before its rounding - the line's where code is LINE, else Q0/S0 - and code [N,...] uint8)"""
+    N = part.shape[0]
+    S0, S1, S2 = np.zeros(part.shape), np.zeros(part.shape), np.zeros(part.shape)
+    Q0, Q1 = np.zeros(y.shape), np.zeros(y.shape)
+    cnt = np.zeros(part.shape, dtype=np.int64)
+    n = np.arange(N)
+    span = np.float64((r + 1) * (r + 1))
+    for d in range(-r, r + 1):                                        # ascending m = n + d
+        m = n + d
+        inside = (m >= 0) & (m < N)
+        mc = np.clip(m, 0, N - 1)
+        take = part[mc] & inside.reshape((N,) + (1,) * (part.ndim - 1))
+        q = np.float64(d * d) / span
+        h = 1.0 - q
+        g = h * h
+        om = g * w64[mc]
+        omd = om * np.float64(d)
+        S0 = S0 + np.where(take, om, 0.0)
+        S1 = S1 + np.where(take, omd, 0.0)
+        S2 = S2 + np.where(take, omd * np.float64(d), 0.0)
+        Q0 = Q0 + np.where(take[..., None], om[..., None] * y[mc], 0.0)
+        Q1 = Q1 + np.where(take[..., None], omd[..., None] * y[mc], 0.0)
+        cnt = cnt + take
+    D = S0 * S2 - S1 * S1
+    line = (cnt >= 2) & np.isfinite(D) & (D > 0)
+    val_line = (S2[..., None] * Q0 - S1[..., None] * Q1) / D[..., None]
+    val_mean = Q0 / S0[..., None]
+    value = np.where(line[..., None], val_line, val_mean)
+    code = np.where(line, LINE, np.where(S0 > 0, MEAN, NONE)).astype(np.uint8)
+    return value, code
+
+
 def smooth(traj, weight, radius):
     """traj [T,N,3] fp32, weight [T,N] fp32 or None, radius 1 .. 64 -> [T,N,3] fp32: what pafuse_trajectory_smooth writes,
     one rounded operation after the other."""
@@ -92,32 +130,7 @@ def smooth(traj, weight, radius):
     assert traj.shape == (T, N, 3) and wt.shape == (T, N)
     with np.errstate(all="ignore"):
         part = (wt > 0) & np.isfinite(traj).all(axis=-1)              # [T,N]; False for a NaN weight
-        y = traj.astype(np.float64)
-        w64 = wt.astype(np.float64)
-        S0, S1, S2 = np.zeros((T, N)), np.zeros((T, N)), np.zeros((T, N))
-        Q0, Q1 = np.zeros((T, N, 3)), np.zeros((T, N, 3))
-        cnt = np.zeros((T, N), dtype=np.int64)
-        n = np.arange(N)
-        span = np.float64((r + 1) * (r + 1))
-        for d in range(-r, r + 1):                                    # ascending m = n + d
-            m = n + d
-            inside = (m >= 0) & (m < N)
-            mc = np.clip(m, 0, N - 1)
-            take = part[:, mc] & inside[None]
-            q = np.float64(d * d) / span
-            h = 1.0 - q
-            g = h * h
-            om = g * w64[:, mc]
-            omd = om * np.float64(d)
-            S0 = S0 + np.where(take, om, 0.0)
-            S1 = S1 + np.where(take, omd, 0.0)
-            S2 = S2 + np.where(take, omd * np.float64(d), 0.0)
-            Q0 = Q0 + np.where(take[..., None], om[..., None] * y[:, mc], 0.0)
-            Q1 = Q1 + np.where(take[..., None], omd[..., None] * y[:, mc], 0.0)
-            cnt = cnt + take
-        D = S0 * S2 - S1 * S1
-        line = (cnt >= 2) & np.isfinite(D) & (D > 0)
-        val_line = ((S2[..., None] * Q0 - S1[..., None] * Q1) / D[..., None]).astype(np.float32)
-        val_mean = (Q0 / S0[..., None]).astype(np.float32)
-        out = np.where(line[..., None], val_line, np.where((S0 > 0)[..., None], val_mean, np.float32(np.nan)))
-    return out.astype(np.float32)
+        frames_first = lambda a: np.moveaxis(a, 1, 0)                 # local_line walks axis 0; elementwise, so no bit moves
+        value, code = local_line(frames_first(traj.astype(np.float64)), frames_first(part), frames_first(wt.astype(np.float64)), r)
+        out = np.where((code != NONE)[..., None], value.astype(np.float32), np.float32(np.nan))
+    return np.ascontiguousarray(frames_first(out), dtype=np.float32)

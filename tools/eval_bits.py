@@ -12,6 +12,12 @@ set.  The Python API is all the tool touches: the same file runs against any tre
             weight (64 and 6 behind a full chunk: the fit kernel re-reads its state between chunks)
   empty     the hostile shards with an empty shard (P_r = 0) in first and in middle position
   frames    N=40 video frames, windows of F=27 at stride 5, folded in batches of 1 and of 3, finished, root trajectory
+  frame_kernels  root fit, focal sums and frame errors at J = 5, 65, 134, 200, 300 (every joint-slot form), N=7, T=2, with NaN
+            joints, zero, negative and NaN weights, a NaN part root and frames with fewer than 4 valid joints; focal solve on
+            states of N = 1, 65, 130
+  line_filters   the smoother at (N, r) = (1, 1), (9, 4), (70, 64) and the repair at (J, N, r) = (5, 9, 3), (65, 9, 64),
+            (134, 70, 13), the last on the whole-body anchors with planted dropouts, an unfillable run and a lost anchor
+All inputs are drawn on the CPU from seeded generators: two trees see the same bytes.
 """
 import argparse
 import hashlib
@@ -195,6 +201,77 @@ class Run:
                 self.put(f"frames.batch{batch}.trajectory.{name}", fit)
         self.put("frames.trajectory.no_conf", ops.fit_trajectory(done["mean"], video_x2d, cam))
 
+    def frame_kernels(self):
+        """the wave-per-(t, frame) kernels at every joint-slot form (J <= 64, 128, 192, 256 and beyond), N = 7, T = 2"""
+        torch, ops = self.torch, self.ops
+        T, N = 2, 7
+        cam = torch.tensor(CAM).cuda()
+        for Jn in (5, 65, 134, 200, 300):
+            g = torch.Generator().manual_seed(1000 + Jn)
+            gt = torch.randn(N, Jn, 3, generator=g) * 0.3
+            pose = gt[None] + torch.randn(T, N, Jn, 3, generator=g) * 0.05
+            x2d = torch.rand(N, Jn, 2, generator=g) * 2 - 1
+            conf = torch.rand(N, Jn, generator=g)
+            traj = torch.randn(T, N, 3, generator=g) * 0.1 + torch.tensor([0.0, 0.0, 4.0])
+            gt_root = torch.randn(N, 3, generator=g) * 0.1 + torch.tensor([0.0, 0.0, 4.0])
+            part = torch.arange(Jn, dtype=torch.int32) % PARTS        # part roots: joints 0 .. 3
+            pbroot = part.clone()
+            conf[conf < 0.2] = 0
+            conf[1, 0], conf[2, Jn - 1], conf[3, Jn // 2] = -0.5, float("nan"), 0.0
+            pose[0, 1, Jn - 1, 1] = float("nan")                     # NaN joints: one component, a whole joint
+            pose[1, 2, Jn // 2] = float("nan")
+            pose[:, 4, 1] = float("nan")                             # a NaN part root
+            pose[0, 5, 3:] = float("nan")                            # a frame with fewer than 4 valid joints
+            conf[6, 2:] = 0                                          # and one by its weights
+            traj[1, 3] = float("nan")
+            gt[2, 0, 0] = float("nan")
+            pose, gt, x2d, conf, traj, gt_root, part, pbroot = (v.contiguous().cuda() for v in (pose, gt, x2d, conf, traj, gt_root, part, pbroot))
+            for tag, c in (("conf", conf), ("no_conf", None)):
+                self.put(f"frame_kernels.J{Jn}.fit_trajectory.{tag}", ops.fit_trajectory(pose, x2d, cam, conf=c))
+                self.put(f"frame_kernels.J{Jn}.focal_sums.{tag}", ops.focal_sums(pose, x2d, cam, conf=c))
+            self.put(f"frame_kernels.J{Jn}.frame_errors.rooted", ops.frame_errors(pose, gt, pbroot, part, PARTS, traj=traj, gt_root=gt_root, per_frame=True))
+            self.put(f"frame_kernels.J{Jn}.frame_errors.plain", ops.frame_errors(pose, gt, pbroot, part, PARTS, per_frame=True))
+        for Nn in (1, 65, 130):
+            g = torch.Generator().manual_seed(2000 + Nn)
+            state = torch.rand(3, Nn, 4, generator=g, dtype=torch.float64) + 0.5
+            state[..., 3] = 1.0
+            state[torch.rand(3, Nn, generator=g) < 0.3] = 0.0        # frames that take no part
+            state[2] = 0.0                                           # a t without any frame
+            self.put(f"frame_kernels.focal_solve.N{Nn}", ops.focal_solve(state.cuda(), cam))
+
+    def line_filters(self):
+        """the smoother and the repair: both outcomes of the filter (line, mean) and none"""
+        torch, ops = self.torch, self.ops
+        from pafuse_amd import detections
+        for Nn, r in ((1, 1), (9, 4), (70, 64)):
+            g = torch.Generator().manual_seed(3000 + Nn)
+            traj = torch.randn(2, Nn, 3, generator=g)
+            weight = torch.rand(2, Nn, generator=g)
+            traj[torch.rand(2, Nn, generator=g) < 0.3] = float("nan")
+            weight[torch.rand(2, Nn, generator=g) < 0.3] = 0
+            if Nn > 1:
+                weight[1, 1:] = 0                                    # one frame left: the mean; t = 1, frame 0 may be NaN: none
+            self.put(f"line_filters.smooth.N{Nn}_r{r}", {"weighted": ops.smooth_trajectory(traj.cuda(), weight.cuda(), r),
+                                                       "plain": ops.smooth_trajectory(traj.cuda(), None, r)})
+        for Jn, Nn, r in ((5, 9, 3), (65, 9, 64), (134, 70, 13)):
+            g = torch.Generator().manual_seed(4000 + Jn)
+            x2d = torch.rand(Nn, Jn, 2, generator=g) * 2 - 1
+            if Jn == J:
+                anchor = detections.repair_anchors(dataset())
+                lost = torch.from_numpy(detections.plant_dropouts(Nn, Jn, 0.2, 10, seed=4000))
+                lost[20:50, 40] = True                               # an unfillable run: nothing within 13 frames of its middle
+                lost[:, int(anchor[100])] = True                     # a lost anchor: what hangs on it cannot be filled
+                conf = torch.rand(Nn, Jn, generator=g) * 0.9 + 0.1
+            else:
+                anchor = [-1, 0, 0, -1, 3] if Jn == 5 else None
+                lost = torch.rand(Nn, Jn, generator=g) < 0.4
+                conf = torch.rand(Nn, Jn, generator=g)
+                conf[0, 0], x2d[1, 1, 0] = float("nan"), float("nan")
+                lost[1:, 2] = True                                   # one frame left: held
+            conf[lost] = 0
+            x2d[lost] = -1.0
+            self.put(f"line_filters.repair.J{Jn}_N{Nn}_r{r}", ops.repair_detections(x2d.cuda(), conf.cuda(), anchor=anchor, radius=r))
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -219,6 +296,8 @@ def main():
     run.unsharded("random", z)
     run.shards("random", z, (64, 6), conf.cuda())
     run.frames()
+    run.frame_kernels()
+    run.line_filters()
     torch.cuda.synchronize()
     doc = json.dumps(run.out, indent=1, sort_keys=True)
     print(doc)
