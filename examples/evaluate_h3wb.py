@@ -17,6 +17,8 @@ the true one per video (H3WB knows its intrinsics: this is how the estimator can
 about RATE of the joints, detections.plant_dropouts - and `--repair [R]` repairs them on the device before the model sees them
 (harness.repair_detections; R in 1 .. 64, default 13); per video the joints per status and detections.repair_error are logged.
 Ground-truth 2-D has no dropouts: without the planting nobody can measure whether the repair helps on H3WB.
+`--path-weight L` (with `--frames --aggregate reproj|reproj_fit`, un-strided) scores the pick made coherent in time: per clip and
+joint one path through the hypotheses instead of every frame's own winner (harness.evaluate_frames(path_weight=...)).
 Without `--data` the synthetic H3WB files of tests/golden/h3wb_synth are used (random weights: numbers are meaningless).
 """
 import argparse
@@ -66,8 +68,16 @@ def main():
     ap.add_argument("--repair", type=int, default=None, nargs="?", const=13, metavar="R",
                     help="with --frames --drop-detections: repair the lost detections on the device along the frames within R "
                          "(1 .. 64, default 13) and log the repair error per video")
+    ap.add_argument("--path-weight", type=float, default=None, metavar="L",
+                    help="with --frames --aggregate reproj or reproj_fit on un-strided clips: the pick coherent in time - per clip and "
+                         "joint one path through the hypotheses, a jump costing L per metre (normalised screen length per metre; "
+                         "about fx / depth makes a jump cost what it projects to); compare the mpjpe and accel columns")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.path_weight is not None and not (a.frames and a.aggregate in ("reproj", "reproj_fit") and a.stride is None
+                                          and a.hypothesis_chunk is None and 0.0 <= a.path_weight < float("inf")):
+        ap.error("--path-weight takes a finite weight >= 0 and needs --frames --aggregate reproj or reproj_fit, without --stride "
+                 "or --hypothesis-chunk")
     drop = None
     if a.drop_detections is not None:
         try:
@@ -115,7 +125,7 @@ def main():
         h3wb.evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, aggregate=a.aggregate, stride=a.stride,
                              trajectory=None if a.trajectory is None else (a.trajectory or True), log=log,
                              hypothesis_chunk=a.hypothesis_chunk, p2=bool(args.ft2d.p2), seam_profile=a.seam_profile,
-                             focal="estimate" if a.estimate_focal else None, repair=a.repair, drop=drop)
+                             focal="estimate" if a.estimate_focal else None, repair=a.repair, drop=drop, path_weight=a.path_weight)
     else:
         h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
                       batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),

@@ -50,6 +50,10 @@ and then the trajectory is NaN.
 image corner - is filled along the frames from the frames within R in which it was found, a face keypoint relative to the nose and
 a hand keypoint relative to its wrist; found keypoints are not touched, and a filled one keeps confidence 0, so the fits above go on
 ignoring it.  It writes test_3d_output_repaired.npy [frames,134] (0 observed, 1 filled, 2 held, 3 unfilled) and prints the counts.
+
+--path-weight L (with --reproj-fit) makes that pick coherent in time (infer_sequence(path_weight=...)): per clip and joint the path
+through the hypotheses that minimises the reprojection error plus L times the distance the joint jumps relative to the mean pose,
+instead of every frame's own winner.  It works per clip - the clip seams stay - and every joint written is still some hypothesis's.
 """
 import argparse
 import json
@@ -114,8 +118,15 @@ def main():
                          "2 held, 3 unfilled) and prints the four counts")
     ap.add_argument("--repair-threshold", type=float, default=0.0, metavar="C",
                     help="with --repair: a keypoint counts as found if its confidence is above C (default 0)")
+    ap.add_argument("--path-weight", type=float, default=None, metavar="L",
+                    help="with --reproj-fit (no --stride, no --hypothesis-chunk): make the pick coherent in time - per clip and joint "
+                         "one path through the hypotheses, a jump costing L per metre (normalised screen length per metre; about "
+                         "2 * FOCAL_PX / width / depth makes a jump cost what it projects to; 0: the per-frame pick)")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.path_weight is not None and (a.reproj_fit is None or a.stride is not None or a.hypothesis_chunk is not None
+                                      or not 0.0 <= a.path_weight < float("inf")):
+        ap.error("--path-weight takes a finite weight >= 0 and needs --reproj-fit without --stride or --hypothesis-chunk")
     if a.repair is not None and not 1 <= a.repair <= 64:
         ap.error("--repair takes a radius in 1 .. 64 frames")
     if not 0.0 <= a.repair_threshold < float("inf"):
@@ -172,7 +183,8 @@ def main():
     if a.reproj_fit is not None:
         cam = pinhole(a.reproj_fit)
         pick = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="reproj_fit",
-                                      cam=cam, conf=conf, hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride)
+                                      cam=cam, conf=conf, hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride,
+                                      path_weight=a.path_weight)
         if a.stride is not None:         # per-frame arrays already
             for k, name in (("pose", "pick"), ("idx", "pick_idx"), ("window", "pick_window"), ("std", "pick_std"), ("cov", "pick_cov")):
                 if k in pick:

@@ -31,6 +31,7 @@
  *   pafuse_hypothesis_partials / _combine  the same from per-shard partial reductions (sharded or chunked P)
  *   pafuse_pose_partials / _combine  the P-Agg / J-Agg aggregates as poses, from shards or chunks of P (no ground truth)
  *   pafuse_pose_partials_fit the same state without a trajectory: the root of every hypothesis fitted from the detections
+ *   pafuse_pose_path         J-Agg coherent in time: per joint a path through the hypotheses of a clip (Viterbi along the frames)
  *   pafuse_spread_partials / _combine  the spread of the hypotheses beside the P-Agg mean: per-joint covariance and std
  *   pafuse_pose_windows_fold / pafuse_spread_windows_fold / pafuse_frames_finish  those states of overlapping windows
  *                            pooled into one pose (and spread) per video frame
@@ -663,6 +664,36 @@ int pafuse_pose_partials_fit(const float *pred, const float *x2d, const float *c
  *   pick_idx  [B,T,F,J] int32 its hypothesis (-1 where none) */
 int pafuse_pose_combine(const void *states, int32_t W, size_t stride_bytes, int32_t B, int32_t T, int32_t F, int32_t J,
                         int32_t P_total, void *merged, float *mean, float *pick, int32_t *pick_idx, void *stream);
+
+/* J-Agg COHERENT IN TIME.  The pick above takes every frame on its own; this one chooses, per line (b, t, j), a path h(f)
+ * through ALL P hypotheses of a clip that minimises
+ *   sum_f u_f(h(f)) + weight * sum_f |off_f(h(f)) - off_f-1(h(f-1))|
+ * by a Viterbi recursion along the frames (pafuse_amd/posepath.py states it operation for operation; fp64, contraction
+ * off, correctly rounded sqrt; after every frame the frame's minimum is subtracted from the running costs and added to the
+ * total).  w = the whole-body joint; off = (double)w - (double)mean (mean NULL: absolute).  A hypothesis is AVAILABLE at a
+ * frame if its offset is finite; a frame is OBSERVED if conf > 0 (NULL: always) and an available hypothesis has a finite
+ * e2 - the fp32 reprojection error of pafuse_pose_partials, under `root`: the shared trajectory [B,F,3], or
+ * (root_per_hypothesis != 0) [B,T,P,F,3], as pafuse_pose_partials_fit writes to tfit.  u is e2 at an observed frame (+inf
+ * where it is not finite) and 0 for every available hypothesis at an unobserved one: the joint crosses a gap by smoothness
+ * alone.  Ties go to the lower hypothesis at every step.  weight == 0: the pick of pafuse_pose_combine wherever that has one.
+ * weight has the unit of normalised screen length per metre; fx / Z is the weight at which a jump costs what it projects to.
+ *   pick     [B,T,F,J,3] the chosen hypothesis's whole-body joint     pick_idx [B,T,F,J] int32 its index
+ *   pick_e2  [B,T,F,J] (NULL: not wanted) its e2, +inf at an unobserved frame
+ *   cost     [B,T,J] double (NULL: not wanted) the cost of the path
+ * A line with a frame at which no hypothesis is available, or without an observed frame, has no path: -1, NaN, +inf and a
+ * NaN cost at all its frames.  Per clip only: nothing crosses a clip seam.  Not a smoother of the pose values: every joint
+ * returned is some hypothesis's joint.
+ * workspace: pafuse_pose_path_workspace_bytes bytes, 8-byte aligned (one back-pointer byte per line, frame and hypothesis:
+ * 1/12 of pred).  One kernel, one wave per line, no atomics, bit-reproducible.  B == 0 launches nothing.
+ * Refused before any HIP call: a null required operand, negative sizes, a short or misaligned workspace, a weight that is
+ * negative or not finite (PAFUSE_E_ARG); P > 256 or F > 256 (PAFUSE_E_SHAPE). */
+size_t pafuse_pose_path_workspace_bytes(int32_t B, int32_t T, int32_t P, int32_t F, int32_t J);
+int pafuse_pose_path(const float *pred /* [B,T,P,F,J,3] */, const float *x2d /* [B,F,J,2] */,
+                     const float *root /* [B,F,3] or [B,T,P,F,3] */, int32_t root_per_hypothesis, const float *cam /* [9] */,
+                     const float *conf /* [B,F,J] or NULL */, const int32_t *conn /* [J] */,
+                     const float *mean /* [B,T,F,J,3] or NULL */, double weight, int32_t B, int32_t T, int32_t P, int32_t F,
+                     int32_t J, float *pick, int32_t *pick_idx, float *pick_e2, double *cost, void *workspace,
+                     size_t workspace_bytes, void *stream);
 
 /* The spread of the hypotheses beside the mean pose, from the same shards: first and second moments of the whole-body
  * joint per (b,t,f,j).  pred [B,T,P_r,F,J,3] holds the part-centred hypotheses [h0, h0 + P_r) of the run, conn int32 [J].

@@ -165,6 +165,9 @@ SIGNATURES = {
     "pafuse_pose_partials": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "pafuse_pose_partials_fit": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pafuse_pose_combine": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t] + [C.c_int32] * 5 + [C.c_void_p] * 5),
+    "pafuse_pose_path_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "pafuse_pose_path": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_double] + [C.c_int32] * 5 +
+                         [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
     "pafuse_spread_partials_bytes": (C.c_size_t, [C.c_int32] * 4),
     "pafuse_spread_partials": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "pafuse_spread_combine": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t] + [C.c_int32] * 4 + [C.c_void_p] * 5),

@@ -3322,6 +3322,187 @@ __global__ void __launch_bounds__(256) pose_fit_partials_kernel(const PoseFitPar
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// J-Agg COHERENT IN TIME: per line (b, t, j) the path h(f) through the P hypotheses of a clip that minimises the
+// reprojection error plus weight * (the distance the joint jumps, relative to the mean pose) - a Viterbi recursion along
+// the frames (statement: pafuse_amd/posepath.py; fp64, contraction pinned OFF, sqrt correctly rounded):
+//   off_f(h) = (double)w - (double)mean_f        w = wb_joint of hypothesis h at frame f (mean null: 0.0)
+//   h available at f: off_f(h) finite;  f observed: conf > 0 (or null) and some available h has a finite e2 (reproj_error)
+//   u_f(h)   = observed ? (available and e2 finite ? (double)e2 : +inf) : (available ? 0 : +inf)
+//   c_f(h)   = u_f(h) + min_h' (c_f-1(h') + weight * sqrt((dx*dx + dy*dy) + dz*dz)),  d = off_f(h) - off_f-1(h'),
+//              the minimum taken in ascending h' under strict < from +inf (back-pointer 0): a NaN never wins
+//   m_f = min_h c_f(h);  c_f -= m_f;  total += m_f
+// and the backtrace from the first minimum (the first exact 0) of the last frame.  A frame without an available hypothesis,
+// or a line without an observed frame, has no path: idx -1, pick NaN, e2 +inf, cost NaN.
+//
+// One wave per line, four lines (adjacent joints, mostly of one (b, t)) per workgroup: wave_item.  Lane l owns hypotheses
+// l, l + 64, ... (R <= 4 of them, in registers).  Per frame a lane forms wb_joint, offset and e2 of its hypotheses; the
+// wave's (c, w) of frame f - 1 sit in LDS, 20 bytes per hypothesis, and the loop over h' reads the same address in every lane
+// (a broadcast: no bank conflict).  The LDS rows are the wave's own (DS operations of a wave complete in order): wave
+// barriers, no workgroup barrier.  m_f is a butterfly (wave_min_f64), the first minimum of the last frame a ballot.  The
+// back-pointers, one byte each, go to the caller's workspace [lines,F,P]: the wave that wrote them reads them back (a
+// workgroup-scope fence in between), one dependent byte load per frame.  No atomics, no scratch; nothing depends on the
+// launch shape.
+// ----------------------------------------------------------------------------------------------------------------
+struct PosePathParams {
+    const float* pred;    // [B,T,P,F,J,3] part-centred predictions, ALL P hypotheses
+    const float* x2d;     // [B,F,J,2]
+    const float* root;    // [B,F,3], or (root_per_h) [B,T,P,F,3]
+    const float* cam;     // [9]
+    const float* conf;    // [B,F,J] or null
+    const int32_t* conn;  // [J]
+    const float* mean;    // [B,T,F,J,3] or null
+    double weight;
+    float* pick;          // [B,T,F,J,3]
+    int32_t* pick_idx;    // [B,T,F,J]
+    float* pick_e2;       // [B,T,F,J] or null
+    double* cost;         // [B,T,J] or null
+    uint8_t* back;        // [B*T*J,F,P] back-pointers (workspace)
+    int B, T, P, F, J, root_per_h;
+};
+
+// after the butterfly every lane of the wave holds the same bits (no NaN among the operands: fmin is then commutative)
+__device__ __forceinline__ double wave_min_f64(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+
+template <int R>
+__global__ void __launch_bounds__(256) pose_path_kernel(const PosePathParams p) {
+    __shared__ double s_c[4][64 * R];
+    __shared__ float s_w[4][3][64 * R];
+    const int lane = wave_lane(), wv = threadIdx.x >> 6;
+    const int64_t line = wave_item();
+    if (line >= (int64_t)p.B * p.T * p.J) return;   // wave-uniform: all 64 lanes of a wave share `line`
+    const int P = p.P, F = p.F, J = p.J;
+    const int j = (int)(line % J);
+    const int64_t bt = line / J;
+    const int b = (int)(bt / p.T);
+    const float* pose0 = p.pred + bt * P * F * J * 3;   // hypothesis h, frame f: + (h * F + f) * J * 3
+    const int64_t hstride = (int64_t)F * J * 3;
+    uint8_t* back = p.back + line * F * P;
+    double* sc = s_c[wv];
+    float *sw0 = s_w[wv][0], *sw1 = s_w[wv][1], *sw2 = s_w[wv][2];
+    const double lam = p.weight, inf = (double)INFINITY;
+    const float qnan = __builtin_nanf("");
+    double c[R], total = 0.0, mprev[3] = {0.0, 0.0, 0.0};
+    uint32_t myobs = 0;            // lane l keeps "observed" of frames l, l + 64, ...: bit f >> 6
+    bool dead = false, any_obs = false;
+    for (int f = 0; f < F; ++f) {
+#pragma clang fp contract(off)
+        const int64_t bf = (int64_t)b * F + f;
+        const float x20 = p.x2d[(bf * J + j) * 2], x21 = p.x2d[(bf * J + j) * 2 + 1];
+        const bool seen = p.conf ? p.conf[bf * J + j] > 0.f : true;
+        double m3[3] = {0.0, 0.0, 0.0};
+        if (p.mean) {
+            const float* mp = p.mean + ((bt * F + f) * J + j) * 3;
+            m3[0] = (double)mp[0], m3[1] = (double)mp[1], m3[2] = (double)mp[2];
+        }
+        float w[R][3];
+        double off[R][3], u[R];
+        bool avail[R], fin[R], any_avail = false, any_fin = false;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int h = r * 64 + lane;
+            avail[r] = fin[r] = false;
+            w[r][0] = w[r][1] = w[r][2] = qnan;
+            off[r][0] = off[r][1] = off[r][2] = 0.0, u[r] = inf;
+            if (h < P) {
+                wb_joint(pose0 + h * hstride + (int64_t)f * J * 3, p.conn, j, w[r]);
+                const float* tr = p.root_per_h ? p.root + ((bt * P + h) * F + f) * 3 : p.root + bf * 3;
+                const float e2 = reproj_error(w[r], tr[0], tr[1], tr[2], x20, x21, p.cam);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) off[r][k] = (double)w[r][k] - m3[k];
+                avail[r] = isfinite(off[r][0]) && isfinite(off[r][1]) && isfinite(off[r][2]);
+                fin[r] = avail[r] && seen && isfinite(e2);
+                u[r] = (double)e2;
+            }
+            any_avail |= avail[r], any_fin |= fin[r];
+        }
+        const bool observed = __ballot(any_fin) != 0;
+        dead |= __ballot(any_avail) == 0;
+        any_obs |= observed;
+        if (observed && lane == (f & 63)) myobs |= 1u << (f >> 6);
+#pragma unroll
+        for (int r = 0; r < R; ++r) u[r] = observed ? (fin[r] ? u[r] : inf) : (avail[r] ? 0.0 : inf);
+        if (f == 0) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) c[r] = u[r];
+        } else {
+            double best[R];
+            int bp[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) best[r] = inf, bp[r] = 0;
+            for (int hp = 0; hp < P; ++hp) {   // the same LDS address in every lane
+                const double cp = sc[hp];
+                const double o0 = (double)sw0[hp] - mprev[0], o1 = (double)sw1[hp] - mprev[1], o2 = (double)sw2[hp] - mprev[2];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double dx = off[r][0] - o0, dy = off[r][1] - o1, dz = off[r][2] - o2;
+                    const double v = cp + lam * sqrt((dx * dx + dy * dy) + dz * dz);
+                    if (v < best[r]) best[r] = v, bp[r] = hp;   // first minimum wins; a NaN (an unavailable h') never does
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                c[r] = u[r] + best[r];
+                if (r * 64 + lane < P) back[(int64_t)f * P + r * 64 + lane] = (uint8_t)bp[r];
+            }
+        }
+        double m = c[0];
+#pragma unroll
+        for (int r = 1; r < R; ++r) m = fmin(m, c[r]);
+        m = wave_min_f64(m);
+        total += m;
+        __builtin_amdgcn_wave_barrier();   // the reads of frame f - 1 come before the writes of frame f
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            c[r] -= m;
+            const int h = r * 64 + lane;
+            if (h < P) sc[h] = c[r], sw0[h] = w[r][0], sw1[h] = w[r][1], sw2[h] = w[r][2];
+        }
+        __builtin_amdgcn_wave_barrier();
+        mprev[0] = m3[0], mprev[1] = m3[1], mprev[2] = m3[2];
+    }
+    const int64_t out0 = bt * F * J + j;   // frame f: + f * J
+    if (dead || !any_obs) {
+        for (int f = lane; f < F; f += 64) {
+            const int64_t e = out0 + (int64_t)f * J;
+            p.pick_idx[e] = -1;
+            p.pick[e * 3 + 0] = qnan, p.pick[e * 3 + 1] = qnan, p.pick[e * 3 + 2] = qnan;
+            if (p.pick_e2) p.pick_e2[e] = INFINITY;
+        }
+        if (p.cost && lane == 0) p.cost[line] = __builtin_nan("");
+        return;
+    }
+    int h = 0;
+#pragma unroll
+    for (int r = R - 1; r >= 0; --r) {   // the first h whose normalised cost is the exact 0
+        const uint64_t zero = __ballot(r * 64 + lane < P && c[r] == 0.0);
+        if (zero) h = r * 64 + __builtin_ctzll(zero);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the back-pointers this wave stored are what it now loads
+    if (p.cost && lane == 0) p.cost[line] = total;
+    for (int f = F - 1; f >= 0; --f) {   // wave-uniform walk: every lane follows the path, lane 0 writes
+        const int hprev = f > 0 ? (int)back[(int64_t)f * P + h] : 0;
+        const int64_t bf = (int64_t)b * F + f, e = out0 + (int64_t)f * J;
+        float w[3];
+        wb_joint(pose0 + h * hstride + (int64_t)f * J * 3, p.conn, j, w);
+        float e2 = INFINITY;
+        if ((__shfl((int)myobs, f & 63) >> (f >> 6)) & 1) {
+            const float* tr = p.root_per_h ? p.root + ((bt * P + h) * F + f) * 3 : p.root + bf * 3;
+            e2 = reproj_error(w, tr[0], tr[1], tr[2], p.x2d[(bf * J + j) * 2], p.x2d[(bf * J + j) * 2 + 1], p.cam);
+        }
+        if (lane == 0) {
+            p.pick_idx[e] = h;
+            p.pick[e * 3 + 0] = w[0], p.pick[e * 3 + 1] = w[1], p.pick[e * 3 + 2] = w[2];
+            if (p.pick_e2) p.pick_e2[e] = e2;
+        }
+        h = hprev;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // The SPREAD of the hypotheses beside the mean pose: first and second moments of the whole-body joint per (b, t, f, j),
 // by the same shard / chunk scheme.  spread_partials_kernel reduces hypotheses [h0, h0 + P_r) to a state whose size does
 // not depend on P, spread_combine_kernel merges W states in ascending-h0 order and / or writes mean, covariance and std.

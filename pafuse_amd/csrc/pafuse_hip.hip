@@ -2001,6 +2001,42 @@ int pafuse_pose_combine(const void* states, int32_t W, size_t stride_bytes, int3
     return launch<pose_combine_kernel>("pose_combine_kernel", blocks_for(n), 256, 0, (hipStream_t)stream, c);
 }
 
+// workspace of pafuse_pose_path: one back-pointer byte per (line, frame, hypothesis), rounded up to 8 bytes
+size_t pafuse_pose_path_workspace_bytes(int32_t B, int32_t T, int32_t P, int32_t F, int32_t J) {
+    if (B < 0 || T <= 0 || P <= 0 || F <= 0 || J <= 0) return 0;
+    return ((size_t)B * T * J * F * P + 7) / 8 * 8;
+}
+
+// J-Agg coherent in time (pose_path_kernel): one wave per line (b, t, j); the argument checks come before the first HIP call
+int pafuse_pose_path(const float* pred, const float* x2d, const float* root, int32_t root_per_hypothesis, const float* cam,
+                     const float* conf, const int32_t* conn, const float* mean, double weight, int32_t B, int32_t T, int32_t P,
+                     int32_t F, int32_t J, float* pick, int32_t* pick_idx, float* pick_e2, double* cost, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    if (B < 0 || T <= 0 || P <= 0 || F <= 0 || J <= 0) return fail(PAFUSE_E_ARG, "pose_path: bad size");
+    if (!std::isfinite(weight) || weight < 0.0) return fail(PAFUSE_E_ARG, "pose_path: weight %g is not finite and >= 0", weight);
+    if (P > 256 || F > 256) return fail(PAFUSE_E_SHAPE, "pose_path: P = %d, F = %d: at most 256 hypotheses and 256 frames", P, F);
+    if (B == 0) return PAFUSE_OK;   // nothing to launch
+    if (!pred || !x2d || !root || !cam || !conn || !pick || !pick_idx)
+        return fail(PAFUSE_E_ARG, "pose_path: pred, x2d, root, cam, conn, pick and pick_idx are needed (conf, mean, pick_e2, cost may be null)");
+    const size_t need = pafuse_pose_path_workspace_bytes(B, T, P, F, J);
+    if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 8)
+        return fail(PAFUSE_E_ARG, "pose_path: the workspace needs %zu bytes, 8-byte aligned", need);
+    if ((uintptr_t)cost % 8) return fail(PAFUSE_E_ARG, "pose_path: cost must be 8-byte aligned");
+    unsigned grid;
+    if (int rc = wave_grid("pose_path", (int64_t)B * T * J, grid)) return rc;   // one wave per (b, t, j)
+    StreamDevice on_stream_device(stream);
+    PosePathParams m{};
+    m.pred = pred, m.x2d = x2d, m.root = root, m.cam = cam, m.conf = conf, m.conn = conn, m.mean = mean, m.weight = weight;
+    m.pick = pick, m.pick_idx = pick_idx, m.pick_e2 = pick_e2, m.cost = cost, m.back = (uint8_t*)workspace;
+    m.B = B, m.T = T, m.P = P, m.F = F, m.J = J, m.root_per_h = root_per_hypothesis ? 1 : 0;
+    switch ((P + 63) / 64) {   // hypotheses per lane
+        case 1: return launch<pose_path_kernel<1>>("pose_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
+        case 2: return launch<pose_path_kernel<2>>("pose_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
+        case 3: return launch<pose_path_kernel<3>>("pose_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
+        default: return launch<pose_path_kernel<4>>("pose_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
+    }
+}
+
 // state of pafuse_spread_partials: double sum[n][3] | double m2[n][6] | double count
 size_t pafuse_spread_partials_bytes(int32_t B, int32_t T, int32_t F, int32_t J) {
     if (B <= 0 || T <= 0 || F <= 0 || J <= 0) return 0;

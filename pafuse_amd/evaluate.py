@@ -545,6 +545,47 @@ def aggregate_poses_sharded(pred_local, h0, num_proposals, dataset, inputs_2d=No
     return out
 
 
+def path_poses(pred_parts, dataset, inputs_2d, cam, weight, traj=None, conf=None, fit=False):
+    """J-Agg coherent in time (ops.pose_path; pafuse_amd.posepath states it): per line (b, t, j) a path through ALL P
+    hypotheses pred_parts [B,T,P,F,J,3] (part-centred, P <= 256, F <= 256) that minimises the reprojection error plus
+    `weight` times the distance the joint jumps relative to the mean pose.  The recursion needs every hypothesis of a clip
+    at once: there is no per-shard state, so callers gather the hypotheses first.
+
+    It runs the existing pose pair first - accumulate_poses on inputs_2d [B,F,J,2], traj [B,F,3] and cam [9], or with
+    fit=True on inputs_2d, cam and conf [B,F,J], which also gives the root of every (hypothesis, frame) - for the mean pose,
+    then the path kernel against that mean.  conf (None: all observed) marks a (frame, joint) whose weight is not > 0 as
+    unobserved: the path crosses it by smoothness alone.  weight >= 0 in normalised screen length per metre (cam[0] / depth:
+    a jump costs what it projects to); 0 gives the per-frame pick.
+
+    -> dict "pick" [B,T,F,J,3], "idx" [B,T,F,J] int32 (NaN / -1 on a line without a path), "mean" [B,T,F,J,3],
+    "cost" [B,T,J] float64, "state" the flat pose state of the P hypotheses whose (e2, idx, sel) hold the path's pick (sum
+    as the pair wrote it) and "shape" = (B,T,F,J): what accumulate_frames folds like any merged state."""
+    from . import ops
+    if fit:
+        if traj is not None:
+            raise ValueError("path_poses: fit=True takes no traj (the root is what it fits)")
+        B, T, P, F = pred_parts.shape[:4]
+        root = torch.empty(B, T, P, F, 3, device=pred_parts.device)
+        state = accumulate_poses(None, pred_parts, 0, dataset, inputs_2d, None, cam, fit=True, conf=conf, tfit=root)
+    else:
+        if traj is None:
+            raise ValueError("path_poses: a trajectory [B,F,3], or fit=True")
+        state = accumulate_poses(None, pred_parts, 0, dataset, inputs_2d, traj, cam)
+    if fit:   # (accumulate_poses checked inputs_2d, cam and conf against pred)
+        pred, _, _, _, _, conn, _ = _operands(pred_parts, None, None, None, None, dataset, "path_poses")
+        x2d, tr, cm = inputs_2d.contiguous().float(), None, cam.reshape(-1)[:9].contiguous().float().to(pred.device)
+    else:
+        pred, _, x2d, tr, cm, conn, _ = _operands(pred_parts, None, inputs_2d, traj, cam, dataset, "path_poses")
+    B, T, F, J = shape = state.shape
+    merged = torch.empty(state.head.numel(), device=pred.device, dtype=torch.float64)
+    mean = ops.combine_poses(state.head.unsqueeze(0), shape, pred.shape[2], merged=merged, want=("mean",))["mean"]
+    cf = None if conf is None else conf.contiguous().float()
+    out = ops.pose_path(pred, conn, x2d, root if fit else tr, cm, weight, conf=cf, mean=mean, want=("pick", "idx", "e2", "cost"))
+    views = ops.pose_views(merged, B, T, F, J)
+    views["e2"].copy_(out["e2"]), views["idx"].copy_(out["idx"]), views["sel"].copy_(out["pick"])
+    return {"pick": out["pick"], "idx": out["idx"], "mean": mean, "cost": out["cost"], "state": merged, "shape": shape}
+
+
 # ------------------------------------------------------------------------------------- spread of the hypotheses
 class SpreadState(_RunningState):
     """The running first and second moments of the hypotheses one rank has seen so far: 72 bytes per (b,t,f,j) and a

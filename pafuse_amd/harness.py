@@ -110,7 +110,7 @@ def repair_detections(seq_2d, conf, dataset=None, anchor=None, radius=13, thresh
 @torch.no_grad()
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
                    hypothesis_chunk=None, spread=None, conf=None, stride=None, trajectory=None, focal=None, repair=None,
-                   repair_threshold=0.0):
+                   repair_threshold=0.0, path_weight=None):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -174,10 +174,23 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     the repaired pair before the flip copy and the cutting: the denoisers, the flip copy, the root fits, the focal estimate and
     the pick all see the same filled detections, and the zeroed confidences keep the filled joints out of every fit.  Results
     that are dicts gain ``"repaired"`` [N,J] uint8, the status of every joint (0 observed, 1 filled, 2 held, 3 unfilled);
-    tensor and tuple results keep their type."""
+    tensor and tuple results keep their type.
+
+    ``path_weight`` (with "reproj" or "reproj_fit"; None: everything above, unchanged, bit for bit) makes the pick COHERENT IN
+    TIME: per joint and clip, instead of the closest reprojection of every frame on its own, the path through the P hypotheses
+    that minimises the reprojection error plus ``path_weight`` times the distance the joint jumps relative to the mean pose
+    (evaluate.path_poses, pafuse_amd.posepath: a Viterbi recursion on the device).  The weight is in normalised screen length
+    per metre - cam[0] / depth is the weight at which a jump costs as much as its own projection; 0.0 returns the per-frame
+    pick.  The return types are those above.  A joint unobserved in a frame (with "reproj_fit": a confidence not > 0) is carried
+    through by smoothness alone and still gets a pick; with "reproj_fit" a joint without a path (idx -1) carries the mean.  The
+    recursion needs all P hypotheses of a clip at once, so ``hypothesis_chunk`` is refused and, under a process group, the
+    hypotheses are gathered as ``aggregate=None`` gathers them; ``stride`` may only be None or F - a path lives inside one clip
+    and crosses neither clip seams nor pooled windows.  It is not a smoother of the pose values: every returned joint is still
+    some hypothesis's joint."""
     smooth = _trajectory_radius(trajectory)
     _focal_mode(focal)
     repair = _repair_radius(repair, repair_threshold)
+    path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, getattr(model, "frames", None))
     if repair is not None and conf is None:
         raise ValueError("repair needs conf [N,J]: a missing detection is one whose confidence is not above repair_threshold")
     if focal is not None and trajectory is None:
@@ -220,25 +233,49 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     dev = next(model.parameters()).device
     if repair is None:
         return _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, trajectory, smooth, focal, dev)
+                               spread, conf, stride, trajectory, smooth, focal, dev, path_weight)
     from .detections import repair_anchors
     fixed = _repair_detections(seq_2d.squeeze(0) if seq_2d.dim() == 4 else seq_2d, conf, repair_anchors(dataset), repair,
                                float(repair_threshold), dev)
     # the callees cut and flip on the host: the repaired pair takes the place of the input, whole, before either
     out = _infer_sequence(model, dataset, fixed["x2d"].cpu(), kps_left, kps_right, batch_size, group, aggregate, cam, traj,
-                          hypothesis_chunk, spread, fixed["conf"].cpu(), stride, trajectory, smooth, focal, dev)
+                          hypothesis_chunk, spread, fixed["conf"].cpu(), stride, trajectory, smooth, focal, dev, path_weight)
     if isinstance(out, dict):
         out["repaired"] = fixed["status"].cpu()
     return out
 
 
+def _path_weight(path_weight, aggregate, hypothesis_chunk, stride, frames):
+    """infer_sequence's / evaluate_frames' `path_weight`: None, or a finite float >= 0 with what it may be combined with"""
+    if path_weight is None:
+        return None
+    if isinstance(path_weight, bool) or not isinstance(path_weight, (int, float)) or not 0 <= path_weight < float("inf"):   # (a NaN fails both)
+        raise ValueError(f"path_weight must be None or a finite number >= 0 (normalised screen length per metre), got {path_weight!r}")
+    if aggregate not in ("reproj", "reproj_fit"):
+        raise ValueError('path_weight belongs to aggregate="reproj" or "reproj_fit": it is the J-Agg pick made coherent in time')
+    if hypothesis_chunk is not None:
+        raise ValueError("path_weight takes no hypothesis_chunk: the recursion needs all P hypotheses of a clip at once")
+    if stride is not None and int(stride) != frames:
+        raise ValueError(f"path_weight takes un-strided clips only (stride None or {frames}): a path crosses no pooled windows")
+    return float(path_weight)
+
+
+def _path_batch(sampler, dataset, x2d, x2d_flip, traj, cam, conf, fit, path_weight, spread=None):
+    """One batch of clips under path_weight: ALL P hypotheses (gathered across the ranks, as aggregate=None gathers them),
+    evaluate.path_poses on them and, with `spread`, their moments -> (path_poses' dict, the SpreadState or None)"""
+    from .evaluate import path_poses
+    pred = sampler(x2d, None, input_2d_flip=x2d_flip)
+    out = path_poses(pred, dataset, x2d, cam, path_weight, traj=None if fit else traj, conf=conf if fit else None, fit=fit)
+    return out, (None if spread is None else accumulate_spread(None, pred, 0, dataset))
+
+
 def _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                    conf, stride, trajectory, smooth, focal, dev):
+                    conf, stride, trajectory, smooth, focal, dev, path_weight=None):
     """infer_sequence behind its argument checks (and behind the repair of the detections, when one was asked for)"""
     fit = aggregate == "reproj_fit"
     if stride is not None:
         return _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                             spread, conf, int(stride), dev, trajectory is not None, smooth, focal)
+                             spread, conf, int(stride), dev, trajectory is not None, smooth, focal, path_weight)
     x2d = cut_clips(seq_2d, model.frames).to(dev)
     x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), model.frames).to(dev)
     sampler = ShardedSampler(model, group)
@@ -267,6 +304,17 @@ def _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, gro
         hi = min(lo + batch_size, x2d.shape[0])
         operands = (x2d[lo:hi], traj[lo:hi], cam) if reproj and not fit else ()
         state = moments = None
+        if path_weight is not None:
+            from . import ops
+            out, moments = _path_batch(sampler, dataset, x2d[lo:hi], x2d_flip[lo:hi], None if fit else traj[lo:hi], cam,
+                                       None if conf is None else conf[lo:hi], fit, path_weight, spread)
+            if moments is not None:
+                out.update(ops.combine_spread(moments.head.unsqueeze(0), moments.shape, want=[k for k in names if k in ("std", "cov")]))
+            if fit:     # a joint without a path carries the mean
+                out["pick"] = torch.where((out["idx"] < 0).unsqueeze(-1), out["mean"], out["pick"])
+            for k in kept:
+                kept[k].append(out[k].cpu())
+            continue
         for pred, h0, _ in sampler.sample_chunks(x2d[lo:hi], None, input_2d_flip=x2d_flip[lo:hi], chunk=hypothesis_chunk):
             if fit:
                 state = accumulate_poses(state, pred, h0, dataset, x2d[lo:hi], None, cam, fit=True,
@@ -298,15 +346,15 @@ def cut_windows(seq, starts, frames=27):
 
 
 def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                  conf, stride, dev, trajectory=False, smooth=None, focal=None):
+                  conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None):
     """infer_sequence(stride=...): sliding windows pooled into one pose per video frame (arguments already checked)"""
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, dev, trajectory, smooth, focal)
+                               spread, conf, stride, dev, trajectory, smooth, focal, path_weight)
     return {k: v.cpu() for k, v in out.items()}
 
 
 def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                         conf, stride, dev, trajectory=False, smooth=None, focal=None):
+                         conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None):
     """_infer_frames with its result left on the device (evaluate_frames scores it there)"""
     from . import ops
     from .windows import window_starts
@@ -332,6 +380,14 @@ def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size
     for lo in range(0, x2d.shape[0], batch_size):
         hi = min(lo + batch_size, x2d.shape[0])
         state = moments = None
+        if path_weight is not None:     # every rank holds all P hypotheses and the same path: nothing to exchange
+            merged, moments = _path_batch(sampler, dataset, x2d[lo:hi], x2d_flip[lo:hi], None if fit else traj[lo:hi], cam,
+                                          None if conf is None or not fit else conf[lo:hi], fit, path_weight, spread)
+            if moments is not None:
+                merged["spread_state"] = torch.empty_like(moments.head)
+                ops.combine_spread(moments.head.unsqueeze(0), moments.shape, merged=merged["spread_state"], want=())
+            frames = accumulate_frames(frames, merged, starts[lo:hi], valid[lo:hi], N, model.num_proposals)
+            continue
         for pred, h0, _ in sampler.sample_chunks(x2d[lo:hi], None, input_2d_flip=x2d_flip[lo:hi], chunk=hypothesis_chunk):
             if fit:
                 state = accumulate_poses(state, pred, h0, dataset, x2d[lo:hi], None, cam, fit=True,
@@ -696,7 +752,7 @@ holds the p2_* keys, each step ends with the four Protocol #2 lines (:511-519): 
 @torch.no_grad()
 def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
                     conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False, focal=None, repair=None,
-                    drop=None, repair_threshold=0.0):
+                    drop=None, repair_threshold=0.0, path_weight=None):
     """One video scored at the level of frames: the frames path of :func:`infer_sequence` - ONE pose per video frame, pooled
     over the windows that cover it - against the ground truth, on the device before anything crosses to the host
     (evaluate.frame_metrics; pafuse_amd.framemetrics states the arithmetic).
@@ -722,7 +778,12 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     ``repair`` (a radius 1 .. 64; needs ``conf`` or ``drop``) then repairs the detections as infer_sequence(repair=...) does,
     before the model sees them.  With either, one more, last element is returned: a dict of CPU tensors ``"x2d"`` [N,J,2] and
     ``"conf"`` [N,J] as the model and the fits saw them, ``"lost"`` [N,J] bool with ``drop`` and ``"status"`` [N,J] uint8 with
-    ``repair`` - what detections.repair_error takes."""
+    ``repair`` - what detections.repair_error takes.
+
+    ``path_weight`` (with "reproj" or "reproj_fit", un-strided clips and no hypothesis_chunk; None: everything above, unchanged)
+    scores the pick made coherent in time, infer_sequence(path_weight=...): per clip and joint one path through the hypotheses.
+    Where the last window overlaps its predecessor the fold's first-minimum rule decides between the two paths, frame by frame.
+    The ``mpjpe`` and ``accel`` columns show what a weight buys."""
     _focal_mode(focal)
     repair = _repair_radius(repair, repair_threshold)
     if drop is not None:
@@ -741,6 +802,7 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     if isinstance(stride, bool) or not isinstance(stride, int) or not 1 <= stride <= frames:
         raise ValueError(f"stride must be None or an integer in 1 .. {frames} (the window length), got {stride!r}")
     smooth = _trajectory_radius(trajectory)
+    path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, frames)
     if cam is None:
         raise ValueError("evaluate_frames needs cam [9] (the intrinsics)")
     if hypothesis_chunk is not None and int(hypothesis_chunk) < 1:
@@ -775,7 +837,7 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     gt_wb = (seq_3d - seq_3d[:, :1]).to(dev)                        # joint 0 at 0, exactly
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam,
                                gt_root if aggregate == "reproj" else None, hypothesis_chunk, None, conf, stride, dev,
-                               trajectory is not None, smooth, focal)
+                               trajectory is not None, smooth, focal, path_weight)
     estimate = {k: out[k].cpu() for k in ("focal", "focal_r2", "focal_frames", "cam")} if focal is not None else None
     m = frame_metrics(out["pose"], gt_wb, dataset, traj=out.get("traj"), gt_root=gt_root.to(dev) if "traj" in out else None,
                       p2=p2, per_frame=per_frame)

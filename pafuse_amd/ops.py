@@ -1129,6 +1129,56 @@ def combine_poses(states, shape, num_proposals, merged=None, want=("mean", "pick
     return out
 
 
+PATH_OUTPUTS = ("pick", "idx", "e2", "cost")
+
+
+def pose_path_workspace_bytes(B, T, P, F, J):
+    """Bytes of the workspace pafuse_pose_path needs (the formula of pafuse_pose_path_workspace_bytes): one back-pointer
+    byte per (b, t, j, f, h), rounded up to a multiple of 8."""
+    return (B * T * J * F * P + 7) // 8 * 8
+
+
+def pose_path(pred, conn, x2d, root, cam, weight, conf=None, mean=None, want=("pick", "idx"), workspace=None):
+    """J-Agg coherent in time (pafuse_pose_path; pafuse_amd.posepath states the arithmetic): pred [B,T,P,F,J,3] ALL P <= 256
+    part-centred hypotheses of clips of F <= 256 frames, conn int32 [J], x2d [B,F,J,2], root [B,F,3] (or [B,F,1,3]) one
+    trajectory or [B,T,P,F,3] a root per hypothesis (tfit of pose_partials_fit), cam [9], weight >= 0 (normalised screen
+    length per metre; 0: the per-frame pick), conf [B,F,J] (None: all observed; not > 0: that frame is unobserved for that
+    joint), mean [B,T,F,J,3] the pose the offsets are taken against (None: absolute) -> dict with the entries of `want`:
+    "pick" [B,T,F,J,3], "idx" [B,T,F,J] int32, "e2" [B,T,F,J], "cost" [B,T,J] float64.  A line without a path: NaN, -1, +inf,
+    NaN.  `workspace`: a uint8 buffer of pose_path_workspace_bytes or more to use instead of a new one."""
+    lib = _lib.load()
+    B, T, P, F, J = _need_pred("pose_path", pred, axis="P")
+    want = tuple(want)
+    _need(all(k in PATH_OUTPUTS for k in want) and want, f"pose_path: want holds some of {PATH_OUTPUTS} - got {want}")
+    _need(T > 0 and P > 0 and F > 0 and J > 0, "pose_path: T, P, F, J > 0")
+    _need(conn.numel() == J and conn.dtype == torch.int32, "pose_path: conn must be int32 [J]")
+    per_h = root.dim() == 5
+    _need(tuple(x2d.shape) == (B, F, J, 2) and cam.numel() == 9 and (conf is None or tuple(conf.shape) == (B, F, J))
+          and (mean is None or tuple(mean.shape) == (B, T, F, J, 3))
+          and (tuple(root.shape) == (B, T, P, F, 3) if per_h else root.numel() == B * F * 3), "pose_path: operands do not match pred")
+    _need_tensors("pose_path", [pred, x2d, root, cam] + [t for t in (conf, mean) if t is not None], (conn,))
+    weight = float(weight)
+    dev = pred.device
+    out = {"pick": torch.empty(B, T, F, J, 3, device=dev), "idx": torch.empty(B, T, F, J, device=dev, dtype=torch.int32)}
+    if "e2" in want:
+        out["e2"] = torch.empty(B, T, F, J, device=dev)
+    if "cost" in want:
+        out["cost"] = torch.empty(B, T, J, device=dev, dtype=torch.float64)
+    need = int(lib.pafuse_pose_path_workspace_bytes(B, T, P, F, J)) if P <= 256 and F <= 256 else 0   # beyond: the library refuses
+    assert need == (pose_path_workspace_bytes(B, T, P, F, J) if P <= 256 and F <= 256 else 0)
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    _need(workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(),
+          f"pose_path: workspace must be a uint8 buffer on {dev}")
+    ptr = lambda t: None if t is None else _data(t)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_pose_path(
+            _data(pred), _data(x2d), _data(root), int(per_h), cam.data_ptr(), ptr(conf), _data(conn), ptr(mean), weight,
+            B, T, P, F, J, _data(out["pick"]), _data(out["idx"]), ptr(out.get("e2")), ptr(out.get("cost")),
+            _data(workspace), workspace.numel(), _stream(pred)))
+    return {k: out[k] for k in want}
+
+
 # ------------------------------------------------------------------------------------- spread of the hypotheses
 SPREAD_STATE_DOUBLES_PER_ELEMENT = 9   # double sum[3] + double m2[6] per (b, t, f, j); one more double, the count, ends the state
 SPREAD_OUTPUTS = {"mean": (3,), "cov": (6,), "std": ()}   # trailing shape of every output of combine_spread behind [B,T,F,J]

@@ -15,6 +15,7 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::procrustes_combine(states, sums, gt, conn, T, num_proposals)   jbest, pagg, jagg, pick from W states   main_h3wb.py:381-395
   pafuse::aggregate_poses(pred, conn, x2d?, traj?, cam?)  P-Agg mean pose, J-Agg pose and its hypothesis index, one shard
   pafuse::aggregate_poses_fit(pred, conn, x2d, cam, conf?)  the same without a trajectory: roots fitted on the device; + tfit
+  pafuse::pose_path(pred, conn, x2d, root, cam, weight, conf?, mean?)   J-Agg coherent in time: per joint a path through the hypotheses
   pafuse::fold_windows(frame!, N, state, shape, starts, valid, w0, num_proposals)   a batch of overlapping windows into the frame state
   pafuse::finish_frames(frame, N, T, J, spread?)          one pose per video frame: mean, pick, idx, window (+ std, cov)
   pafuse::fit_trajectory(pose, x2d, cam, conf?)           the camera-space root of that pose: traj, wsum, resid per (t, frame)
@@ -391,6 +392,24 @@ def _(pred, conn, x2d, cam, conf=None):
     B, T, P, F, J, _ = pred.shape
     return [pred.new_empty(B, T, F, J, 3), pred.new_empty(B, T, F, J, 3), pred.new_empty((B, T, F, J), dtype=torch.int32),
             pred.new_empty(B, T, P, F, 3)]
+
+
+@torch.library.custom_op("pafuse::pose_path", mutates_args=(), device_types="cuda")
+def pose_path(pred: torch.Tensor, conn: torch.Tensor, x2d: torch.Tensor, root: torch.Tensor, cam: torch.Tensor, weight: float,
+              conf: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+    """pafuse_amd.ops.pose_path (J-Agg coherent in time): pred [B,T,P,F,J,3] ALL part-centred hypotheses, x2d [B,F,J,2], root
+    [B,F,3] or [B,T,P,F,3], cam [9], weight >= 0, conf [B,F,J] or None, mean [B,T,F,J,3] or None -> [pick [B,T,F,J,3],
+    idx [B,T,F,J] int32, e2 [B,T,F,J], cost [B,T,J] float64]; a line without a path: NaN, -1, +inf, NaN."""
+    from . import ops
+    m = ops.pose_path(pred, conn, x2d, root, cam, weight, conf=conf, mean=mean, want=ops.PATH_OUTPUTS)
+    return [m[k] for k in ops.PATH_OUTPUTS]
+
+
+@pose_path.register_fake
+def _(pred, conn, x2d, root, cam, weight, conf=None, mean=None):
+    B, T, P, F, J, _ = pred.shape
+    return [pred.new_empty(B, T, F, J, 3), pred.new_empty((B, T, F, J), dtype=torch.int32), pred.new_empty(B, T, F, J),
+            pred.new_empty((B, T, J), dtype=torch.float64)]
 
 
 # ----------------------------------------------------------------------------------- spread of the hypotheses
