@@ -19,6 +19,8 @@ about RATE of the joints, detections.plant_dropouts - and `--repair [R]` repairs
 Ground-truth 2-D has no dropouts: without the planting nobody can measure whether the repair helps on H3WB.
 `--path-weight L` (with `--frames --aggregate reproj|reproj_fit`, un-strided) scores the pick made coherent in time: per clip and
 joint one path through the hypotheses instead of every frame's own winner (harness.evaluate_frames(path_weight=...)).
+`--path-scope video` runs that path along the whole video instead, across clip seams and the pooled windows of `--stride S`
+(the candidates of a frame are the hypotheses of all windows covering it; at most 256, kept on the device for the whole video).
 Without `--data` the synthetic H3WB files of tests/golden/h3wb_synth are used (random weights: numbers are meaningless).
 """
 import argparse
@@ -72,12 +74,17 @@ def main():
                     help="with --frames --aggregate reproj or reproj_fit on un-strided clips: the pick coherent in time - per clip and "
                          "joint one path through the hypotheses, a jump costing L per metre (normalised screen length per metre; "
                          "about fx / depth makes a jump cost what it projects to); compare the mpjpe and accel columns")
+    ap.add_argument("--path-scope", choices=("clip", "video"), default="clip",
+                    help="with --path-weight: 'clip' (default) one path per un-strided clip; 'video' one path along the whole video, "
+                         "across clip seams and the pooled windows of any --stride")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
-    if a.path_weight is not None and not (a.frames and a.aggregate in ("reproj", "reproj_fit") and a.stride is None
+    if a.path_scope == "video" and a.path_weight is None:
+        ap.error("--path-scope video needs --path-weight")
+    if a.path_weight is not None and not (a.frames and a.aggregate in ("reproj", "reproj_fit") and (a.stride is None or a.path_scope == "video")
                                           and a.hypothesis_chunk is None and 0.0 <= a.path_weight < float("inf")):
-        ap.error("--path-weight takes a finite weight >= 0 and needs --frames --aggregate reproj or reproj_fit, without --stride "
-                 "or --hypothesis-chunk")
+        ap.error("--path-weight takes a finite weight >= 0 and needs --frames --aggregate reproj or reproj_fit, without "
+                 "--hypothesis-chunk and (unless --path-scope video) without --stride")
     drop = None
     if a.drop_detections is not None:
         try:
@@ -125,7 +132,8 @@ def main():
         h3wb.evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, aggregate=a.aggregate, stride=a.stride,
                              trajectory=None if a.trajectory is None else (a.trajectory or True), log=log,
                              hypothesis_chunk=a.hypothesis_chunk, p2=bool(args.ft2d.p2), seam_profile=a.seam_profile,
-                             focal="estimate" if a.estimate_focal else None, repair=a.repair, drop=drop, path_weight=a.path_weight)
+                             focal="estimate" if a.estimate_focal else None, repair=a.repair, drop=drop, path_weight=a.path_weight,
+                             path_scope=a.path_scope)
     else:
         h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
                       batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),

@@ -54,6 +54,9 @@ ignoring it.  It writes test_3d_output_repaired.npy [frames,134] (0 observed, 1 
 --path-weight L (with --reproj-fit) makes that pick coherent in time (infer_sequence(path_weight=...)): per clip and joint the path
 through the hypotheses that minimises the reprojection error plus L times the distance the joint jumps relative to the mean pose,
 instead of every frame's own winner.  It works per clip - the clip seams stay - and every joint written is still some hypothesis's.
+--path-scope video runs that path along the whole video instead, across the clip seams and the pooled windows of --stride S: the
+candidates of a frame are the hypotheses of all windows covering it (at most 256; they stay on the device for the whole video).  The
+per-frame files of --stride are written, and test_3d_output_pick_path_cost.npy [steps,134], the cost of every joint's path (NaN: none).
 """
 import argparse
 import json
@@ -122,11 +125,16 @@ def main():
                     help="with --reproj-fit (no --stride, no --hypothesis-chunk): make the pick coherent in time - per clip and joint "
                          "one path through the hypotheses, a jump costing L per metre (normalised screen length per metre; about "
                          "2 * FOCAL_PX / width / depth makes a jump cost what it projects to; 0: the per-frame pick)")
+    ap.add_argument("--path-scope", choices=("clip", "video"), default="clip",
+                    help="with --path-weight: 'clip' (default) one path per clip; 'video' one path along the whole video, across clip "
+                         "seams and the pooled windows of any --stride (per-frame output)")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
-    if a.path_weight is not None and (a.reproj_fit is None or a.stride is not None or a.hypothesis_chunk is not None
+    if a.path_scope == "video" and a.path_weight is None:
+        ap.error("--path-scope video needs --path-weight")
+    if a.path_weight is not None and (a.reproj_fit is None or (a.stride is not None and a.path_scope == "clip") or a.hypothesis_chunk is not None
                                       or not 0.0 <= a.path_weight < float("inf")):
-        ap.error("--path-weight takes a finite weight >= 0 and needs --reproj-fit without --stride or --hypothesis-chunk")
+        ap.error("--path-weight takes a finite weight >= 0 and needs --reproj-fit without --hypothesis-chunk and (unless --path-scope video) without --stride")
     if a.repair is not None and not 1 <= a.repair <= 64:
         ap.error("--repair takes a radius in 1 .. 64 frames")
     if not 0.0 <= a.repair_threshold < float("inf"):
@@ -184,9 +192,11 @@ def main():
         cam = pinhole(a.reproj_fit)
         pick = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="reproj_fit",
                                       cam=cam, conf=conf, hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride,
-                                      path_weight=a.path_weight)
-        if a.stride is not None:         # per-frame arrays already
-            for k, name in (("pose", "pick"), ("idx", "pick_idx"), ("window", "pick_window"), ("std", "pick_std"), ("cov", "pick_cov")):
+                                      path_weight=a.path_weight, path_scope=a.path_scope)
+        per_frame = a.stride is not None or a.path_scope == "video"
+        if per_frame:                    # per-frame arrays already
+            for k, name in (("pose", "pick"), ("idx", "pick_idx"), ("window", "pick_window"), ("std", "pick_std"), ("cov", "pick_cov"),
+                            ("path_cost", "pick_path_cost")):
                 if k in pick:
                     save(f"test_3d_output_{name}.npy", pick[k])
             save("test_3d_output_count.npy", pick["count"])
@@ -195,7 +205,7 @@ def main():
                 np.save(os.path.join(a.out, f"test_3d_output_pick_{k}.npy"),
                         harness.stitch_spread(pick[k], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
             pick = (pick["pose"], pick["idx"])
-        if a.stride is None:
+        if not per_frame:
             np.save(os.path.join(a.out, "test_3d_output_pick.npy"),
                     harness.stitch_poses(pick[0], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
             np.save(os.path.join(a.out, "test_3d_output_pick_idx.npy"),

@@ -32,6 +32,7 @@
  *   pafuse_pose_partials / _combine  the P-Agg / J-Agg aggregates as poses, from shards or chunks of P (no ground truth)
  *   pafuse_pose_partials_fit the same state without a trajectory: the root of every hypothesis fitted from the detections
  *   pafuse_pose_path         J-Agg coherent in time: per joint a path through the hypotheses of a clip (Viterbi along the frames)
+ *   pafuse_frames_path       the same path along a whole VIDEO: the candidates of a frame are the hypotheses of all windows covering it
  *   pafuse_spread_partials / _combine  the spread of the hypotheses beside the P-Agg mean: per-joint covariance and std
  *   pafuse_pose_windows_fold / pafuse_spread_windows_fold / pafuse_frames_finish  those states of overlapping windows
  *                            pooled into one pose (and spread) per video frame
@@ -694,6 +695,49 @@ int pafuse_pose_path(const float *pred /* [B,T,P,F,J,3] */, const float *x2d /* 
                      const float *mean /* [B,T,F,J,3] or NULL */, double weight, int32_t B, int32_t T, int32_t P, int32_t F,
                      int32_t J, float *pick, int32_t *pick_idx, float *pick_e2, double *cost, void *workspace,
                      size_t workspace_bytes, void *stream);
+
+/* THE PATH OF A WHOLE VIDEO.  pafuse_pose_path stops at the clip: every F frames the path starts again from nothing, and
+ * pooled windows (stride < F) cannot be combined with it.  Here the recursion runs along the N frames of the video, and the
+ * candidates at video frame n are the pairs (window, hypothesis) of ALL windows that cover n - window w covers the frames
+ * [starts[w], starts[w] + valid[w]), its local frame f = n - starts[w].  pafuse_amd/posepath.py frames_path states it: the
+ * statement of pafuse_pose_path on the dense [W*P, N] form in which a window that does not cover a frame is unavailable
+ * there; the arithmetic (fp64, contraction off, correctly rounded sqrt, the frame's minimum subtracted after every frame),
+ * availability, observation and the unary cost u are those of pafuse_pose_path, with
+ *   off = (double)w - (double)mean[t,n,j]   mean [T,N,J,3] as pafuse_frames_finish writes it (NULL: absolute offsets)
+ *   e2 under root [N,3] (one trajectory of the video) or (root_per_hypothesis != 0) [W,T,P,F,3] (tfit of the windows)
+ *   x2d [N,J,2] and conf [N,J] (NULL: all observed) per VIDEO frame
+ * Ties go to the lower (window, hypothesis) at every step - the order of pafuse_pose_windows_fold -, so weight == 0 is the
+ * pick, index and window of pafuse_frames_finish wherever that has one.
+ * The windows must be the whole video: starts strictly ascending, starts[0] == 0, starts[w] + valid[w] not descending,
+ * no gap (starts[w+1] <= starts[w] + valid[w]), the last window ending at N, valid in 1 .. F - everything
+ * pafuse_amd.windows.window_starts produces, the shifted last window and the one padded window of a short video included.
+ * starts / valid are passed twice, device and host copies, as pafuse_pose_windows_fold takes them: the checks read the
+ * host copy, the kernel the device copy, and the call neither copies nor synchronises.
+ *   pick     [T,N,J,3] the chosen hypothesis's whole-body joint
+ *   pick_idx [T,N,J] int32 its hypothesis      pick_win [T,N,J] int32 its window (the index within this call)
+ *   pick_e2  [T,N,J] (NULL: not wanted) its e2, +inf at an unobserved frame
+ *   cost     [T,J] double (NULL: not wanted) the cost of the path
+ * A LINE DIES WHOLE: one frame at which no candidate is available, or no observed frame at all, and the line (t, j) has no
+ * path at ANY frame of the video: -1, -1, NaN, +inf and a NaN cost.  Segments that restart are not built.  Not a smoother
+ * of the pose values: every joint returned is some hypothesis's joint.
+ * workspace: pafuse_frames_path_workspace_bytes bytes, 8-byte aligned: one back-pointer byte per (line, frame, slot),
+ * [T*J, N, K] rounded up to 8, K = P * the largest number of windows that cover one frame; it grows with the length of the
+ * video, as pred does.  The function returns 0 for whatever the call would refuse.  One kernel, one wave per line (t, j), no
+ * atomics, bit-reproducible.  N has no limit of its own.
+ * Refused before any HIP call: a null required operand, sizes < 1 (W == 0 too: a video has at least one window), windows
+ * that break a rule above, a weight that is negative or not finite, a short or misaligned workspace (PAFUSE_E_ARG);
+ * K > 256 (PAFUSE_E_SHAPE). */
+size_t pafuse_frames_path_workspace_bytes(int32_t N, int32_t T, int32_t J, int32_t P, int32_t W,
+                                          const int32_t *starts_host, const int32_t *valid_host);
+int pafuse_frames_path(const float *pred /* [W,T,P,F,J,3] */, const float *x2d /* [N,J,2] */,
+                       const float *root /* [N,3] or [W,T,P,F,3] */, int32_t root_per_hypothesis,
+                       const float *cam /* [9] */, const float *conf /* [N,J] or NULL */, const int32_t *conn /* [J] */,
+                       const float *mean /* [T,N,J,3] or NULL */, double weight,
+                       int32_t W, int32_t T, int32_t P, int32_t F, int32_t J, int32_t N,
+                       const int32_t *starts, const int32_t *valid, const int32_t *starts_host, const int32_t *valid_host,
+                       float *pick /* [T,N,J,3] */, int32_t *pick_idx, int32_t *pick_win /* [T,N,J] */,
+                       float *pick_e2 /* [T,N,J] or NULL */, double *cost /* [T,J] or NULL */,
+                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* The spread of the hypotheses beside the mean pose, from the same shards: first and second moments of the whole-body
  * joint per (b,t,f,j).  pred [B,T,P_r,F,J,3] holds the part-centred hypotheses [h0, h0 + P_r) of the run, conn int32 [J].

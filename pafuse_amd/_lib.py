@@ -168,6 +168,9 @@ SIGNATURES = {
     "pafuse_pose_path_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
     "pafuse_pose_path": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_double] + [C.c_int32] * 5 +
                          [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
+    "pafuse_frames_path_workspace_bytes": (C.c_size_t, [C.c_int32] * 5 + [C.c_void_p] * 2),
+    "pafuse_frames_path": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_double] + [C.c_int32] * 6 +
+                           [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p]),
     "pafuse_spread_partials_bytes": (C.c_size_t, [C.c_int32] * 4),
     "pafuse_spread_partials": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "pafuse_spread_combine": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t] + [C.c_int32] * 4 + [C.c_void_p] * 5),

@@ -3503,6 +3503,199 @@ __global__ void __launch_bounds__(256) pose_path_kernel(const PosePathParams p) 
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// THE PATH OF A WHOLE VIDEO: the recursion above along the N frames of a video instead of the F frames of a clip.  At
+// video frame n the candidates are the pairs (window, hypothesis) of ALL windows that cover n - window w covers
+// [starts[w], starts[w] + valid[w]) - so a path crosses clip seams and pooled windows (statement:
+// pafuse_amd/posepath.py frames_path = `path` on the dense [W*P, N] form, a window that does not cover a frame being
+// unavailable there).  The host checked the windows: starts ascend strictly, the ends do not descend, no gap, 0 .. N
+// covered; the covering windows are then a contiguous range [lo_n, hi_n], both ends monotone in n, and
+//   slot s at frame n = the candidate (w, h) = (lo_n + s / P, s % P), local frame f = n - starts[w]     s < K_n = (hi_n - lo_n + 1) * P
+// ascends in (w, h): the order of the dense form, so ties go to the lower (window, hypothesis) - the fold's order.
+// The arithmetic is pose_path_kernel's, operation for operation (fp64, contraction pinned OFF, sqrt correctly rounded):
+//   off_n(s) = (double)w - (double)mean[t,n,j]      w = wb_joint of the slot's hypothesis at its local frame (mean null: 0.0)
+//   s available at n: off_n(s) finite;  n observed: conf[n,j] > 0 (or null) and some available s has a finite e2 (reproj_error)
+//   u_n(s)   = observed ? (available and e2 finite ? (double)e2 : +inf) : (available ? 0 : +inf)
+//   c_n(s)   = u_n(s) + min_s' (c_n-1(s') + weight * sqrt((dx*dx + dy*dy) + dz*dz)),  d = off_n(s) - off_n-1(s'),
+//              s' ascending over the K_n-1 slots of frame n - 1 under strict < from +inf (back-pointer 0): a NaN never wins
+//   m_n = min_s c_n(s);  c_n -= m_n;  total += m_n
+// and the backtrace from the first exact 0 of the last frame.  A frame without an available candidate, or a line without an
+// observed frame, has no path at ANY frame: idx -1, window -1, pick NaN, e2 +inf, cost NaN.
+//
+// One wave per line (t, j), four adjacent joints per workgroup (wave_item).  Lane l owns slots l, l + 64, ... (R <= 4, in
+// registers; K = P * the largest coverage <= 256).  Per frame the window range advances on wave-uniform reads of the device
+// tables; a lane forms wb_joint, offset and e2 of its slots; (c, w) of frame n - 1 sit in the wave's own LDS rows and the
+// s' loop reads the same address in every lane (a broadcast).  Wave barriers, no workgroup barrier.  The back-pointer
+// stored is the PREVIOUS frame's slot, one byte, in the caller's workspace [lines,N,K]; the backtrace recovers lo_n by
+// walking the window pointer back (monotone), nothing else is kept per frame - except "observed", which pick_e2 (when wanted)
+// carries from the forward pass to the backtrace: 0 or +inf, then overwritten with the value.  The wave that wrote both
+// reads them back, a workgroup-scope fence in between.  No atomics, no scratch; nothing depends on the launch shape.
+// Sizes the device tables would lead out of (they are the caller's copy of the checked host tables) are clamped, never followed.
+// ----------------------------------------------------------------------------------------------------------------
+struct FramesPathParams {
+    const float* pred;      // [W,T,P,F,J,3] part-centred predictions, ALL P hypotheses of every window
+    const float* x2d;       // [N,J,2]
+    const float* root;      // [N,3], or (root_per_h) [W,T,P,F,3]
+    const float* cam;       // [9]
+    const float* conf;      // [N,J] or null
+    const int32_t* conn;    // [J]
+    const float* mean;      // [T,N,J,3] or null
+    const int32_t* starts;  // [W] device copies of the window tables
+    const int32_t* valid;   // [W]
+    double weight;
+    float* pick;            // [T,N,J,3]
+    int32_t* pick_idx;      // [T,N,J]
+    int32_t* pick_win;      // [T,N,J]
+    float* pick_e2;         // [T,N,J] or null
+    double* cost;           // [T,J] or null
+    uint8_t* back;          // [T*J,N,K] back-pointers (workspace)
+    int W, T, P, F, J, N, K, root_per_h;
+};
+
+template <int R>
+__global__ void __launch_bounds__(256) frames_path_kernel(const FramesPathParams p) {
+    __shared__ double s_c[4][64 * R];
+    __shared__ float s_w[4][3][64 * R];
+    const int lane = wave_lane(), wv = threadIdx.x >> 6;
+    const int64_t line = wave_item();
+    if (line >= (int64_t)p.T * p.J) return;   // wave-uniform: all 64 lanes of a wave share `line`
+    const int W = p.W, T = p.T, P = p.P, F = p.F, J = p.J, N = p.N, K = p.K;
+    const int j = (int)(line % J), t = (int)(line / J);
+    uint8_t* back = p.back + line * N * K;
+    double* sc = s_c[wv];
+    float *sw0 = s_w[wv][0], *sw1 = s_w[wv][1], *sw2 = s_w[wv][2];
+    const double lam = p.weight, inf = (double)INFINITY;
+    const float qnan = __builtin_nanf("");
+    const int64_t out0 = (int64_t)t * N * J + j;   // frame n: + n * J
+    double c[R], total = 0.0, mprev[3] = {0.0, 0.0, 0.0};
+    bool dead = false, any_obs = false;
+    int lo = 0, hi = 0, kn = 0, kprev = 0;
+    for (int n = 0; n < N; ++n) {
+#pragma clang fp contract(off)
+        while (hi + 1 < W && p.starts[hi + 1] <= n) ++hi;              // wave-uniform
+        while (lo < hi && p.starts[lo] + p.valid[lo] <= n) ++lo;
+        kprev = kn;
+        kn = min((hi - lo + 1) * P, K);
+        const float x20 = p.x2d[((int64_t)n * J + j) * 2], x21 = p.x2d[((int64_t)n * J + j) * 2 + 1];
+        const bool seen = p.conf ? p.conf[(int64_t)n * J + j] > 0.f : true;
+        double m3[3] = {0.0, 0.0, 0.0};
+        if (p.mean) {
+            const float* mp = p.mean + (out0 + (int64_t)n * J) * 3;
+            m3[0] = (double)mp[0], m3[1] = (double)mp[1], m3[2] = (double)mp[2];
+        }
+        float w[R][3];
+        double off[R][3], u[R];
+        bool avail[R], fin[R], any_avail = false, any_fin = false;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int s = r * 64 + lane;
+            avail[r] = fin[r] = false;
+            w[r][0] = w[r][1] = w[r][2] = qnan;
+            off[r][0] = off[r][1] = off[r][2] = 0.0, u[r] = inf;
+            if (s < kn) {
+                const int wl = s / P, h = s - wl * P, win = lo + wl;
+                const int f = n - p.starts[win];
+                if (f >= 0 && f < F) {
+                    const int64_t hyp = (((int64_t)win * T + t) * P + h) * F + f;   // (w, t, h, f)
+                    wb_joint(p.pred + hyp * J * 3, p.conn, j, w[r]);
+                    const float* tr = p.root_per_h ? p.root + hyp * 3 : p.root + (int64_t)n * 3;
+                    const float e2 = reproj_error(w[r], tr[0], tr[1], tr[2], x20, x21, p.cam);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) off[r][k] = (double)w[r][k] - m3[k];
+                    avail[r] = isfinite(off[r][0]) && isfinite(off[r][1]) && isfinite(off[r][2]);
+                    fin[r] = avail[r] && seen && isfinite(e2);
+                    u[r] = (double)e2;
+                }
+            }
+            any_avail |= avail[r], any_fin |= fin[r];
+        }
+        const bool observed = __ballot(any_fin) != 0;
+        dead |= __ballot(any_avail) == 0;
+        any_obs |= observed;
+        if (p.pick_e2 && lane == 0) p.pick_e2[out0 + (int64_t)n * J] = observed ? 0.f : INFINITY;   // for the backtrace
+#pragma unroll
+        for (int r = 0; r < R; ++r) u[r] = observed ? (fin[r] ? u[r] : inf) : (avail[r] ? 0.0 : inf);
+        if (n == 0) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) c[r] = u[r];
+        } else {
+            double best[R];
+            int bp[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) best[r] = inf, bp[r] = 0;
+            const int rounds = (kn + 63) >> 6;     // wave-uniform: a round of slots no candidate of this frame reaches keeps
+            for (int sp = 0; sp < kprev; ++sp) {   // best = +inf, hence c = +inf, without its square roots.  The same LDS address in every lane
+                const double cp = sc[sp];
+                const double o0 = (double)sw0[sp] - mprev[0], o1 = (double)sw1[sp] - mprev[1], o2 = (double)sw2[sp] - mprev[2];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if (r > 0 && r >= rounds) break;   // (kn >= P >= 1: round 0 always runs, and R = 1 has no test)
+                    const double dx = off[r][0] - o0, dy = off[r][1] - o1, dz = off[r][2] - o2;
+                    const double v = cp + lam * sqrt((dx * dx + dy * dy) + dz * dz);
+                    if (v < best[r]) best[r] = v, bp[r] = sp;   // first minimum wins; a NaN (an unavailable s') never does
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                c[r] = u[r] + best[r];
+                if (r * 64 + lane < kn) back[(int64_t)n * K + r * 64 + lane] = (uint8_t)bp[r];
+            }
+        }
+        double m = c[0];
+#pragma unroll
+        for (int r = 1; r < R; ++r) m = fmin(m, c[r]);
+        m = wave_min_f64(m);
+        total += m;
+        __builtin_amdgcn_wave_barrier();   // the reads of frame n - 1 come before the writes of frame n
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            c[r] -= m;
+            const int s = r * 64 + lane;
+            if (s < kn) sc[s] = c[r], sw0[s] = w[r][0], sw1[s] = w[r][1], sw2[s] = w[r][2];
+        }
+        __builtin_amdgcn_wave_barrier();
+        mprev[0] = m3[0], mprev[1] = m3[1], mprev[2] = m3[2];
+    }
+    if (dead || !any_obs) {
+        for (int n = lane; n < N; n += 64) {
+            const int64_t e = out0 + (int64_t)n * J;
+            p.pick_idx[e] = -1, p.pick_win[e] = -1;
+            p.pick[e * 3 + 0] = qnan, p.pick[e * 3 + 1] = qnan, p.pick[e * 3 + 2] = qnan;
+            if (p.pick_e2) p.pick_e2[e] = INFINITY;
+        }
+        if (p.cost && lane == 0) p.cost[line] = __builtin_nan("");
+        return;
+    }
+    int s = 0;
+#pragma unroll
+    for (int r = R - 1; r >= 0; --r) {   // the first slot whose normalised cost is the exact 0
+        const uint64_t zero = __ballot(r * 64 + lane < kn && c[r] == 0.0);
+        if (zero) s = r * 64 + __builtin_ctzll(zero);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the back-pointers and marks this wave stored are what it now loads
+    if (p.cost && lane == 0) p.cost[line] = total;
+    for (int n = N - 1; n >= 0; --n) {   // wave-uniform walk: every lane follows the path, lane 0 writes
+        while (lo > 0 && p.starts[lo - 1] + p.valid[lo - 1] > n) --lo;   // lo_n: the first window that ends behind n
+        const int sprev = n > 0 ? (int)back[(int64_t)n * K + s] : 0;
+        const int wl = s / P, h = s - wl * P, win = min(lo + wl, W - 1);
+        const int f = min(max(n - p.starts[win], 0), F - 1);
+        const int64_t hyp = (((int64_t)win * T + t) * P + h) * F + f, e = out0 + (int64_t)n * J;
+        float w[3];
+        wb_joint(p.pred + hyp * J * 3, p.conn, j, w);
+        float e2 = INFINITY;
+        if (p.pick_e2 && p.pick_e2[e] == 0.f) {   // observed (the forward pass's mark)
+            const float* tr = p.root_per_h ? p.root + hyp * 3 : p.root + (int64_t)n * 3;
+            e2 = reproj_error(w, tr[0], tr[1], tr[2], p.x2d[((int64_t)n * J + j) * 2], p.x2d[((int64_t)n * J + j) * 2 + 1], p.cam);
+        }
+        if (lane == 0) {
+            p.pick_idx[e] = h, p.pick_win[e] = win;
+            p.pick[e * 3 + 0] = w[0], p.pick[e * 3 + 1] = w[1], p.pick[e * 3 + 2] = w[2];
+            if (p.pick_e2) p.pick_e2[e] = e2;
+        }
+        s = sprev;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // The SPREAD of the hypotheses beside the mean pose: first and second moments of the whole-body joint per (b, t, f, j),
 // by the same shard / chunk scheme.  spread_partials_kernel reduces hypotheses [h0, h0 + P_r) to a state whose size does
 // not depend on P, spread_combine_kernel merges W states in ascending-h0 order and / or writes mean, covariance and std.

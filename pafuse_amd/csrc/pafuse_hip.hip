@@ -2037,6 +2037,80 @@ int pafuse_pose_path(const float* pred, const float* x2d, const float* root, int
     }
 }
 
+namespace {
+// What pafuse_frames_path asks of the window table of a video (the HOST copy): starts strictly ascending from 0, ends
+// starts[w] + valid[w] not descending and ending at N, no gap, valid >= 1 (and <= F where F > 0).  -> nullptr and the largest
+// number of windows that cover one frame, or what is wrong.  The windows that cover a frame are then a contiguous range,
+// and the coverage peaks at some window's first frame.
+const char* video_windows(const int32_t* starts, const int32_t* valid, int32_t W, int32_t F, int32_t N, int* cover) {
+    if (W < 1 || N < 1) return "a video has at least one window and one frame";
+    if (starts[0] != 0) return "the first window must start at frame 0";
+    int lo = 0, most = 0;
+    for (int w = 0; w < W; ++w) {
+        if (valid[w] < 1 || (F > 0 && valid[w] > F)) return "valid must lie in 1 .. F";
+        if (starts[w] < 0 || (int64_t)starts[w] + valid[w] > N) return "a window reaches past the N frames";
+        if (w) {
+            if (starts[w] <= starts[w - 1]) return "starts must ascend strictly";
+            if (starts[w] + valid[w] < starts[w - 1] + valid[w - 1]) return "the windows' ends must not descend";
+            if (starts[w] > starts[w - 1] + valid[w - 1]) return "a gap between two windows";
+        }
+        while (starts[lo] + valid[lo] <= starts[w]) ++lo;   // (lo <= w: window w covers its own first frame)
+        most = w - lo + 1 > most ? w - lo + 1 : most;
+    }
+    if (starts[W - 1] + valid[W - 1] != N) return "the last window must end at frame N";
+    *cover = most;
+    return nullptr;
+}
+}  // namespace
+
+// workspace of pafuse_frames_path: one back-pointer byte per (line, frame, slot), K = P * the largest coverage slots per
+// frame, rounded up to 8 bytes; 0 for whatever the call would refuse
+size_t pafuse_frames_path_workspace_bytes(int32_t N, int32_t T, int32_t J, int32_t P, int32_t W, const int32_t* starts_host,
+                                          const int32_t* valid_host) {
+    int cover = 0;
+    if (N <= 0 || T <= 0 || J <= 0 || P <= 0 || W <= 0 || !starts_host || !valid_host) return 0;
+    if (video_windows(starts_host, valid_host, W, 0, N, &cover) || (int64_t)cover * P > 256) return 0;
+    return ((size_t)T * J * N * cover * P + 7) / 8 * 8;
+}
+
+// The path of a whole video (frames_path_kernel): one wave per line (t, j); the argument checks come before the first HIP call
+int pafuse_frames_path(const float* pred, const float* x2d, const float* root, int32_t root_per_hypothesis, const float* cam,
+                       const float* conf, const int32_t* conn, const float* mean, double weight, int32_t W, int32_t T, int32_t P,
+                       int32_t F, int32_t J, int32_t N, const int32_t* starts, const int32_t* valid, const int32_t* starts_host,
+                       const int32_t* valid_host, float* pick, int32_t* pick_idx, int32_t* pick_win, float* pick_e2, double* cost,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (W <= 0 || T <= 0 || P <= 0 || F <= 0 || J <= 0 || N <= 0)
+        return fail(PAFUSE_E_ARG, "frames_path: bad size (a video has at least one window and one frame)");
+    if (!std::isfinite(weight) || weight < 0.0) return fail(PAFUSE_E_ARG, "frames_path: weight %g is not finite and >= 0", weight);
+    if (!pred || !x2d || !root || !cam || !conn || !starts || !valid || !starts_host || !valid_host || !pick || !pick_idx || !pick_win)
+        return fail(PAFUSE_E_ARG, "frames_path: pred, x2d, root, cam, conn, the window tables (device and host), pick, pick_idx and "
+                                  "pick_win are needed (conf, mean, pick_e2, cost may be null)");
+    int cover = 0;
+    if (const char* why = video_windows(starts_host, valid_host, W, F, N, &cover))
+        return fail(PAFUSE_E_ARG, "frames_path: the windows must be the whole video of N = %d frames: %s", N, why);
+    if ((int64_t)cover * P > 256)
+        return fail(PAFUSE_E_SHAPE, "frames_path: %d windows cover one frame with P = %d hypotheses each: at most 256 candidates per frame", cover, P);
+    const int K = cover * P;
+    const size_t need = ((size_t)T * J * N * K + 7) / 8 * 8;
+    if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 8)
+        return fail(PAFUSE_E_ARG, "frames_path: the workspace needs %zu bytes, 8-byte aligned", need);
+    if ((uintptr_t)cost % 8) return fail(PAFUSE_E_ARG, "frames_path: cost must be 8-byte aligned");
+    unsigned grid;
+    if (int rc = wave_grid("frames_path", (int64_t)T * J, grid)) return rc;   // one wave per (t, j)
+    StreamDevice on_stream_device(stream);
+    FramesPathParams m{};
+    m.pred = pred, m.x2d = x2d, m.root = root, m.cam = cam, m.conf = conf, m.conn = conn, m.mean = mean, m.weight = weight;
+    m.starts = starts, m.valid = valid;
+    m.pick = pick, m.pick_idx = pick_idx, m.pick_win = pick_win, m.pick_e2 = pick_e2, m.cost = cost, m.back = (uint8_t*)workspace;
+    m.W = W, m.T = T, m.P = P, m.F = F, m.J = J, m.N = N, m.K = K, m.root_per_h = root_per_hypothesis ? 1 : 0;
+    switch ((K + 63) / 64) {   // slots per lane
+        case 1: return launch<frames_path_kernel<1>>("frames_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
+        case 2: return launch<frames_path_kernel<2>>("frames_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
+        case 3: return launch<frames_path_kernel<3>>("frames_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
+        default: return launch<frames_path_kernel<4>>("frames_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
+    }
+}
+
 // state of pafuse_spread_partials: double sum[n][3] | double m2[n][6] | double count
 size_t pafuse_spread_partials_bytes(int32_t B, int32_t T, int32_t F, int32_t J) {
     if (B <= 0 || T <= 0 || F <= 0 || J <= 0) return 0;

@@ -651,6 +651,50 @@ def accumulate_frames(frames, merged, starts, valid, N, num_proposals):
     return frames
 
 
+def path_frames(pred_windows, dataset, seq_2d, cam, weight, starts, valid, N, frames, traj=None, conf=None, fit=False):
+    """The J-Agg path of a whole VIDEO (ops.frames_path; pafuse_amd.posepath.frames_path states it): per line (t, j) one path
+    along the N video frames whose candidates at frame n are ALL P hypotheses of ALL windows that cover n - it crosses clip
+    seams and pooled windows.  pred_windows [W,T,P,F,J,3] part-centred, the hypotheses of every window of the video, on the
+    device (memory grows with the length of the video: W*T*P*F*J*3*4 bytes, plus one back-pointer byte per (t, j, n,
+    candidate)); starts, valid: the rows of pafuse_amd.windows.window_starts (host integers, the whole video); seq_2d
+    [N,J,2] the detections of the video; cam [9]; `frames` the FrameState already folded from the pose states of the same
+    windows (accumulate_frames): its pooled mean (ops.finish_frames) is what the offsets are taken against.  traj [N,3]
+    the root trajectory of the video, or fit=True (no traj): the root of every (window, hypothesis, frame) as
+    ops.pose_partials_fit fits it (tfit) under the weights conf [N,J].  conf (None: all observed) also marks a (frame,
+    joint) whose weight is not > 0 as unobserved: the path crosses it by smoothness alone.  At most 256 candidates per frame
+    (P times the windows covering one frame).
+    -> dict "pick" [T,N,J,3], "idx" and "window" [T,N,J] int32 (NaN / -1 / -1 at every frame of a line without a path:
+    one frame without an available candidate removes the joint's path for the video), "e2" [T,N,J], "cost" [T,J] float64
+    and "mean" [T,N,J,3]."""
+    from . import ops
+    who = "path_frames"
+    pred, _, _, _, _, conn, _ = _operands(pred_windows, None, None, None, None, dataset, who, name="pred_windows")
+    W, T, P, F, J, _ = pred.shape
+    dev, N = pred.device, int(N)
+    if frames is None or frames.pose is None or (frames.N, frames.T, frames.J) != (N, T, J) or frames.windows != W:
+        raise ValueError(f"{who}: `frames` must hold the folded pose states of the same {W} windows over N = {N} frames")
+    if cam is None or tuple(seq_2d.shape) != (N, J, 2) or (conf is not None and tuple(conf.shape) != (N, J)):
+        raise ValueError(f"{who}: seq_2d [N,J,2] = {(N, J, 2)}, cam [9] and conf [N,J] or None")
+    x2d = seq_2d.to(dev).contiguous().float()
+    cm = torch.as_tensor(cam, dtype=torch.float32).reshape(-1)[:9].contiguous().to(dev)
+    cf = None if conf is None else conf.to(dev).contiguous().float()
+    if fit:
+        if traj is not None:
+            raise ValueError(f"{who}: fit=True takes no traj (the root is what it fits)")
+        first = torch.as_tensor(starts, dtype=torch.long, device=dev)
+        at = (first[:, None] + torch.arange(F, device=dev)[None]).clamp(max=N - 1)     # [W,F]: a short video repeats its last frame
+        root = torch.empty(W, T, P, F, 3, device=dev)
+        ops.pose_partials_fit(pred, conn, 0, x2d[at].contiguous(), cm, conf=None if cf is None else cf[at].contiguous(), tfit=root)
+    else:
+        if traj is None or tuple(traj.shape) != (N, 3):
+            raise ValueError(f"{who}: a trajectory [N,3] with N = {N}, or fit=True")
+        root = traj.to(dev).contiguous().float()
+    mean = ops.finish_frames(N, T, J, frame=frames.pose, want=("mean",))["mean"]
+    out = ops.frames_path(pred, conn, x2d, root, cm, weight, starts, valid, conf=cf, mean=mean, want=ops.FRAMES_PATH_OUTPUTS)
+    out["mean"] = mean
+    return out
+
+
 # ----------------------------------------------------------------- the per-frame pose scored against ground truth
 FRAME_METRICS = ("mpjpe", "mpjve", "accel", "root", "root_vel", "abs_mpjpe")   # ops.FRAME_ERROR_SLOTS; then one slot per part
 

@@ -110,7 +110,7 @@ def repair_detections(seq_2d, conf, dataset=None, anchor=None, radius=13, thresh
 @torch.no_grad()
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
                    hypothesis_chunk=None, spread=None, conf=None, stride=None, trajectory=None, focal=None, repair=None,
-                   repair_threshold=0.0, path_weight=None):
+                   repair_threshold=0.0, path_weight=None, path_scope="clip"):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -186,11 +186,24 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     recursion needs all P hypotheses of a clip at once, so ``hypothesis_chunk`` is refused and, under a process group, the
     hypotheses are gathered as ``aggregate=None`` gathers them; ``stride`` may only be None or F - a path lives inside one clip
     and crosses neither clip seams nor pooled windows.  It is not a smoother of the pose values: every returned joint is still
-    some hypothesis's joint."""
+    some hypothesis's joint.
+
+    ``path_scope="video"`` (with ``path_weight``; the default "clip" is everything above, refusals included) runs that
+    recursion along the N frames of the VIDEO instead (evaluate.path_frames, pafuse_amd.posepath.frames_path): at every frame
+    the candidates are all P hypotheses of ALL windows that cover it, so the path crosses clip seams and pooled windows.  Any
+    ``stride`` is accepted (None means F) and the result is the per-frame dict of ``stride=`` plus ``"path_cost"`` [T,J]
+    (float64; NaN: no path).  The windows are sampled in batches and their pose and spread states folded as without a path
+    weight - ``count``, ``std`` / ``cov`` and the trajectory keys do not change - but the hypotheses of ALL windows are kept
+    on the device until the end of the video: W*T*P*F*J*3*4 bytes for W windows, plus the path kernel's workspace of one
+    byte per (t, j, frame, candidate) - memory grows with the length of the video.  ``pose``, ``idx`` and ``window`` come
+    from the path; with "reproj_fit" a joint with idx -1 carries the pooled mean.  A joint's path dies whole: one frame at
+    which none of its candidates is finite removes it for the video.  Refused: ``hypothesis_chunk``, ``aggregate`` None /
+    "mean", and more than 256 candidates per frame (P times the windows that cover one frame).  Under a process group the
+    hypotheses are gathered as ``aggregate=None`` gathers them."""
     smooth = _trajectory_radius(trajectory)
     _focal_mode(focal)
     repair = _repair_radius(repair, repair_threshold)
-    path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, getattr(model, "frames", None))
+    path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, getattr(model, "frames", None), path_scope)
     if repair is not None and conf is None:
         raise ValueError("repair needs conf [N,J]: a missing detection is one whose confidence is not above repair_threshold")
     if focal is not None and trajectory is None:
@@ -233,21 +246,29 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     dev = next(model.parameters()).device
     if repair is None:
         return _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, trajectory, smooth, focal, dev, path_weight)
+                               spread, conf, stride, trajectory, smooth, focal, dev, path_weight, path_scope)
     from .detections import repair_anchors
     fixed = _repair_detections(seq_2d.squeeze(0) if seq_2d.dim() == 4 else seq_2d, conf, repair_anchors(dataset), repair,
                                float(repair_threshold), dev)
     # the callees cut and flip on the host: the repaired pair takes the place of the input, whole, before either
     out = _infer_sequence(model, dataset, fixed["x2d"].cpu(), kps_left, kps_right, batch_size, group, aggregate, cam, traj,
-                          hypothesis_chunk, spread, fixed["conf"].cpu(), stride, trajectory, smooth, focal, dev, path_weight)
+                          hypothesis_chunk, spread, fixed["conf"].cpu(), stride, trajectory, smooth, focal, dev, path_weight, path_scope)
     if isinstance(out, dict):
         out["repaired"] = fixed["status"].cpu()
     return out
 
 
-def _path_weight(path_weight, aggregate, hypothesis_chunk, stride, frames):
-    """infer_sequence's / evaluate_frames' `path_weight`: None, or a finite float >= 0 with what it may be combined with"""
+PATH_CANDIDATES = 256    # path_scope="video": P times the windows that cover one frame (ops.FRAMES_PATH_MAX_CANDIDATES)
+
+
+def _path_weight(path_weight, aggregate, hypothesis_chunk, stride, frames, scope="clip"):
+    """infer_sequence's / evaluate_frames' `path_weight`: None, or a finite float >= 0 with what it may be combined with;
+    `scope`: "clip" (a path per clip) or "video" (one path along the video, any stride)"""
+    if scope not in ("clip", "video"):
+        raise ValueError(f'path_scope must be "clip" or "video", got {scope!r}')
     if path_weight is None:
+        if scope == "video":
+            raise ValueError('path_scope="video" belongs to a path_weight')
         return None
     if isinstance(path_weight, bool) or not isinstance(path_weight, (int, float)) or not 0 <= path_weight < float("inf"):   # (a NaN fails both)
         raise ValueError(f"path_weight must be None or a finite number >= 0 (normalised screen length per metre), got {path_weight!r}")
@@ -255,7 +276,7 @@ def _path_weight(path_weight, aggregate, hypothesis_chunk, stride, frames):
         raise ValueError('path_weight belongs to aggregate="reproj" or "reproj_fit": it is the J-Agg pick made coherent in time')
     if hypothesis_chunk is not None:
         raise ValueError("path_weight takes no hypothesis_chunk: the recursion needs all P hypotheses of a clip at once")
-    if stride is not None and int(stride) != frames:
+    if scope == "clip" and stride is not None and int(stride) != frames:
         raise ValueError(f"path_weight takes un-strided clips only (stride None or {frames}): a path crosses no pooled windows")
     return float(path_weight)
 
@@ -270,12 +291,14 @@ def _path_batch(sampler, dataset, x2d, x2d_flip, traj, cam, conf, fit, path_weig
 
 
 def _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                    conf, stride, trajectory, smooth, focal, dev, path_weight=None):
+                    conf, stride, trajectory, smooth, focal, dev, path_weight=None, path_scope="clip"):
     """infer_sequence behind its argument checks (and behind the repair of the detections, when one was asked for)"""
     fit = aggregate == "reproj_fit"
+    if stride is None and path_scope == "video":      # one path along the video: per-frame results, the clips of cut_clips
+        stride = model.frames
     if stride is not None:
         return _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                             spread, conf, int(stride), dev, trajectory is not None, smooth, focal, path_weight)
+                             spread, conf, int(stride), dev, trajectory is not None, smooth, focal, path_weight, path_scope)
     x2d = cut_clips(seq_2d, model.frames).to(dev)
     x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), model.frames).to(dev)
     sampler = ShardedSampler(model, group)
@@ -346,23 +369,29 @@ def cut_windows(seq, starts, frames=27):
 
 
 def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                  conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None):
+                  conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip"):
     """infer_sequence(stride=...): sliding windows pooled into one pose per video frame (arguments already checked)"""
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, dev, trajectory, smooth, focal, path_weight)
+                               spread, conf, stride, dev, trajectory, smooth, focal, path_weight, path_scope)
     return {k: v.cpu() for k, v in out.items()}
 
 
 def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                         conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None):
+                         conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip"):
     """_infer_frames with its result left on the device (evaluate_frames scores it there)"""
     from . import ops
-    from .windows import window_starts
+    from .windows import coverage, window_starts
     if seq_2d.dim() == 4:
         seq_2d = seq_2d.squeeze(0)
     N, F = seq_2d.shape[0], model.frames
     starts, valid = window_starts(N, F, stride)
     fit, reproj = aggregate == "reproj_fit", aggregate in ("reproj", "reproj_fit")
+    video = path_weight is not None and path_scope == "video"
+    if video and int(coverage(N, starts, valid).max()) * model.num_proposals > PATH_CANDIDATES:
+        raise ValueError(f'path_scope="video": up to {int(coverage(N, starts, valid).max())} windows cover one frame at stride {stride}, with '
+                         f"{model.num_proposals} hypotheses each: at most {PATH_CANDIDATES} candidates per frame")
+    video_traj = None if traj is None or not video else torch.as_tensor(traj, dtype=torch.float32)
+    kept = []           # path_scope="video": the hypotheses of every window stay on the device until the end of the video
     frame_conf = conf
     x2d = cut_windows(seq_2d, starts, F).to(dev)
     x2d_flip = cut_windows(flip_2d(seq_2d, kps_left, kps_right), starts, F).to(dev)
@@ -380,6 +409,21 @@ def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size
     for lo in range(0, x2d.shape[0], batch_size):
         hi = min(lo + batch_size, x2d.shape[0])
         state = moments = None
+        if video:                       # every rank holds all P hypotheses: the states the default folds, with nothing to exchange
+            pred = sampler(x2d[lo:hi], None, input_2d_flip=x2d_flip[lo:hi])
+            if fit:
+                state = accumulate_poses(None, pred, 0, dataset, x2d[lo:hi], None, cam, fit=True, conf=None if conf is None else conf[lo:hi])
+            else:
+                state = accumulate_poses(None, pred, 0, dataset, x2d[lo:hi], traj[lo:hi], cam)
+            merged = {"state": torch.empty_like(state.head), "shape": state.shape}
+            ops.combine_poses(state.head.unsqueeze(0), state.shape, model.num_proposals, merged=merged["state"], want=(), no_pick_ok=fit)
+            if spread is not None:
+                moments = accumulate_spread(None, pred, 0, dataset)
+                merged["spread_state"] = torch.empty_like(moments.head)
+                ops.combine_spread(moments.head.unsqueeze(0), moments.shape, merged=merged["spread_state"], want=())
+            frames = accumulate_frames(frames, merged, starts[lo:hi], valid[lo:hi], N, model.num_proposals)
+            kept.append(pred)
+            continue
         if path_weight is not None:     # every rank holds all P hypotheses and the same path: nothing to exchange
             merged, moments = _path_batch(sampler, dataset, x2d[lo:hi], x2d_flip[lo:hi], None if fit else traj[lo:hi], cam,
                                           None if conf is None or not fit else conf[lo:hi], fit, path_weight, spread)
@@ -405,6 +449,12 @@ def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size
     want = (("mean", "count") + (("pick", "idx", "window") if reproj else ())
             + (() if spread is None else ("std",) if spread == "std" else ("std", "cov")))
     out = ops.finish_frames(N, frames.T, frames.J, frame=frames.pose, spread=frames.spread, want=want)
+    if video:       # one path along the video through the hypotheses of all windows, against the pooled mean
+        from .evaluate import path_frames
+        path = path_frames(torch.cat(kept), dataset, seq_2d.to(dev), cam, path_weight, starts, valid, N, frames,
+                           traj=None if fit else video_traj.to(dev), conf=None if frame_conf is None or not fit else frame_conf.to(dev), fit=fit)
+        del kept
+        out.update(pick=path["pick"], idx=path["idx"], window=path["window"], path_cost=path["cost"])
     if fit:         # a joint without a pick carries the pooled mean
         out["pick"] = torch.where((out["idx"] < 0).unsqueeze(-1), out["mean"], out["pick"])
     out["pose"] = out.pop("pick") if reproj else out["mean"]
@@ -752,7 +802,7 @@ holds the p2_* keys, each step ends with the four Protocol #2 lines (:511-519): 
 @torch.no_grad()
 def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
                     conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False, focal=None, repair=None,
-                    drop=None, repair_threshold=0.0, path_weight=None):
+                    drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip"):
     """One video scored at the level of frames: the frames path of :func:`infer_sequence` - ONE pose per video frame, pooled
     over the windows that cover it - against the ground truth, on the device before anything crosses to the host
     (evaluate.frame_metrics; pafuse_amd.framemetrics states the arithmetic).
@@ -783,7 +833,10 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     ``path_weight`` (with "reproj" or "reproj_fit", un-strided clips and no hypothesis_chunk; None: everything above, unchanged)
     scores the pick made coherent in time, infer_sequence(path_weight=...): per clip and joint one path through the hypotheses.
     Where the last window overlaps its predecessor the fold's first-minimum rule decides between the two paths, frame by frame.
-    The ``mpjpe`` and ``accel`` columns show what a weight buys."""
+    The ``mpjpe`` and ``accel`` columns show what a weight buys.  ``path_scope="video"`` scores the path along the whole video
+    instead, infer_sequence(path_weight=..., path_scope="video"): any ``stride``, the candidates of a frame being the
+    hypotheses of all windows that cover it, so nothing is left to the fold's rule; the hypotheses of all windows stay on
+    the device until the end of the video, and at most 256 candidates per frame are taken."""
     _focal_mode(focal)
     repair = _repair_radius(repair, repair_threshold)
     if drop is not None:
@@ -802,7 +855,7 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     if isinstance(stride, bool) or not isinstance(stride, int) or not 1 <= stride <= frames:
         raise ValueError(f"stride must be None or an integer in 1 .. {frames} (the window length), got {stride!r}")
     smooth = _trajectory_radius(trajectory)
-    path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, frames)
+    path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, frames, path_scope)
     if cam is None:
         raise ValueError("evaluate_frames needs cam [9] (the intrinsics)")
     if hypothesis_chunk is not None and int(hypothesis_chunk) < 1:
@@ -837,7 +890,7 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     gt_wb = (seq_3d - seq_3d[:, :1]).to(dev)                        # joint 0 at 0, exactly
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam,
                                gt_root if aggregate == "reproj" else None, hypothesis_chunk, None, conf, stride, dev,
-                               trajectory is not None, smooth, focal, path_weight)
+                               trajectory is not None, smooth, focal, path_weight, path_scope)
     estimate = {k: out[k].cpu() for k in ("focal", "focal_r2", "focal_frames", "cam")} if focal is not None else None
     m = frame_metrics(out["pose"], gt_wb, dataset, traj=out.get("traj"), gt_root=gt_root.to(dev) if "traj" in out else None,
                       p2=p2, per_frame=per_frame)

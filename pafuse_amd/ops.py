@@ -1179,6 +1179,93 @@ def pose_path(pred, conn, x2d, root, cam, weight, conf=None, mean=None, want=("p
     return {k: out[k] for k in want}
 
 
+FRAMES_PATH_OUTPUTS = ("pick", "idx", "window", "e2", "cost")
+FRAMES_PATH_MAX_CANDIDATES = 256    # P times the largest number of windows that cover one frame
+
+
+def _video_windows(who, starts, valid, N, F=None):
+    """starts, valid of the windows of a WHOLE video of N frames, as pafuse_frames_path wants them -> (int32 starts, int32
+    valid, the largest number of windows that cover one frame), or None where the library would refuse them"""
+    import numpy as np
+    hs = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1))
+    hv = np.ascontiguousarray(np.asarray(valid, dtype=np.int32).reshape(-1))
+    _need(hs.shape == hv.shape, f"{who}: starts and valid are two vectors of one length")
+    s, e = hs.astype(np.int64), hs.astype(np.int64) + hv
+    if (hs.shape[0] < 1 or int(N) < 1 or s[0] != 0 or e[-1] != int(N) or (hv < 1).any() or (F is not None and (hv > F).any())
+            or (np.diff(s) <= 0).any() or (np.diff(e) < 0).any() or (s[1:] > e[:-1]).any()):
+        return None
+    cover = int(max(w - int(np.searchsorted(e, s[w], side="right")) + 1 for w in range(hs.shape[0])))
+    return hs, hv, cover
+
+
+def frames_path_workspace_bytes(N, T, J, P, starts, valid):
+    """Bytes of the workspace pafuse_frames_path needs (the formula of pafuse_frames_path_workspace_bytes): one back-pointer
+    byte per (t, j, n, slot) with K = P * the largest coverage slots per frame, rounded up to a multiple of 8; 0 for sizes
+    and windows the library refuses (K > 256 among them)."""
+    if min(int(N), int(T), int(J), int(P)) < 1:
+        return 0
+    tables = _video_windows("frames_path_workspace_bytes", starts, valid, N)
+    if tables is None or tables[2] * int(P) > FRAMES_PATH_MAX_CANDIDATES:
+        return 0
+    return (int(T) * int(J) * int(N) * tables[2] * int(P) + 7) // 8 * 8
+
+
+def frames_path(pred, conn, x2d, root, cam, weight, starts, valid, conf=None, mean=None, want=("pick", "idx", "window"),
+                workspace=None):
+    """The J-Agg path of a whole VIDEO (pafuse_frames_path; pafuse_amd.posepath.frames_path states it): pred [W,T,P,F,J,3] ALL
+    part-centred hypotheses of the W windows of one video of N frames, window w covering the frames [starts[w], starts[w] +
+    valid[w]) (host integers, pafuse_amd.windows.window_starts: the whole video, no gap); conn int32 [J], x2d [N,J,2], root
+    [N,3] one trajectory or [W,T,P,F,3] a root per hypothesis (tfit of pose_partials_fit), cam [9], weight >= 0, conf [N,J]
+    (None: all observed), mean [T,N,J,3] the pooled mean the offsets are taken against (finish_frames; None: absolute).  At
+    every frame the candidates are the hypotheses of all windows covering it, at most 256 -> dict with the entries of
+    `want`: "pick" [T,N,J,3], "idx" and "window" [T,N,J] int32, "e2" [T,N,J], "cost" [T,J] float64.  A line without a path:
+    NaN, -1, -1, +inf, NaN at every frame.  `workspace`: a uint8 buffer of frames_path_workspace_bytes or more to use
+    instead of a new one."""
+    lib = _lib.load()
+    W, T, P, F, J = (int(v) for v in _need_pred("frames_path", pred, axis="P"))
+    want = tuple(want)
+    _need(all(k in FRAMES_PATH_OUTPUTS for k in want) and want, f"frames_path: want holds some of {FRAMES_PATH_OUTPUTS} - got {want}")
+    _need(W > 0 and T > 0 and P > 0 and F > 0 and J > 0, "frames_path: W, T, P, F, J > 0 (a video has at least one window)")
+    _need(x2d.dim() == 3 and x2d.shape[0] > 0, "frames_path: x2d must be [N,J,2]")
+    N = int(x2d.shape[0])
+    _need(conn.numel() == J and conn.dtype == torch.int32, "frames_path: conn must be int32 [J]")
+    per_h = root.dim() == 5
+    _need(tuple(x2d.shape) == (N, J, 2) and cam.numel() == 9 and (conf is None or tuple(conf.shape) == (N, J))
+          and (mean is None or tuple(mean.shape) == (T, N, J, 3))
+          and (tuple(root.shape) == (W, T, P, F, 3) if per_h else root.numel() == N * 3), "frames_path: operands do not match pred")
+    _need_tensors("frames_path", [pred, x2d, root, cam] + [t for t in (conf, mean) if t is not None], (conn,))
+    tables = _video_windows("frames_path", starts, valid, N, F)
+    _need(tables is not None and tables[0].shape[0] == W,
+          f"frames_path: starts / valid must be the W = {W} windows of the whole video of N = {N} frames (from 0, no gap, ends ascending, to N)")
+    hs, hv, cover = tables
+    _need(cover * P <= FRAMES_PATH_MAX_CANDIDATES, f"frames_path: {cover} windows cover one frame with P = {P} hypotheses each: "
+          f"at most {FRAMES_PATH_MAX_CANDIDATES} candidates per frame")
+    weight = float(weight)
+    dev = pred.device
+    out = {"pick": torch.empty(T, N, J, 3, device=dev), "idx": torch.empty(T, N, J, device=dev, dtype=torch.int32),
+           "window": torch.empty(T, N, J, device=dev, dtype=torch.int32)}
+    if "e2" in want:
+        out["e2"] = torch.empty(T, N, J, device=dev)
+    if "cost" in want:
+        out["cost"] = torch.empty(T, J, device=dev, dtype=torch.float64)
+    need = int(lib.pafuse_frames_path_workspace_bytes(N, T, J, P, W, hs.ctypes.data, hv.ctypes.data))
+    assert need == frames_path_workspace_bytes(N, T, J, P, hs, hv)
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    _need(workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(),
+          f"frames_path: workspace must be a uint8 buffer on {dev}")
+    import numpy as np
+    dtab = torch.from_numpy(np.stack([hs, hv])).to(dev)     # the device copies the kernel reads
+    ptr = lambda t: None if t is None else _data(t)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_frames_path(
+            _data(pred), _data(x2d), _data(root), int(per_h), cam.data_ptr(), ptr(conf), _data(conn), ptr(mean), weight,
+            W, T, P, F, J, N, dtab[0].data_ptr(), dtab[1].data_ptr(), hs.ctypes.data, hv.ctypes.data,
+            _data(out["pick"]), _data(out["idx"]), _data(out["window"]), ptr(out.get("e2")), ptr(out.get("cost")),
+            _data(workspace), workspace.numel(), _stream(pred)))
+    return {k: out[k] for k in want}
+
+
 # ------------------------------------------------------------------------------------- spread of the hypotheses
 SPREAD_STATE_DOUBLES_PER_ELEMENT = 9   # double sum[3] + double m2[6] per (b, t, f, j); one more double, the count, ends the state
 SPREAD_OUTPUTS = {"mean": (3,), "cov": (6,), "std": ()}   # trailing shape of every output of combine_spread behind [B,T,F,J]

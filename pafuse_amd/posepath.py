@@ -34,8 +34,18 @@ motion is not penalised.
 The weight.  lam has the unit of normalised screen length per metre.  fx / Z (cam[0] over the depth of the subject) is the
 weight at which a jump costs as much as its own projection onto the screen.  The library chooses no default.
 
-What this is not: it works per clip and crosses neither clip seams nor pooled windows, and it is not a smoother of the pose
-values - every returned joint is still some hypothesis's joint.
+What this is not: `path` / `pick` work per clip and cross neither clip seams nor pooled windows, and it is not a smoother of
+the pose values - every returned joint is still some hypothesis's joint.
+
+The path of a whole VIDEO (frames_path_kernel, pafuse_frames_path) is the same statement on more
+candidates: at video frame n the candidates are the pairs (window, hypothesis) of ALL windows that cover n.  Number them
+g = w * P + h and give a window that does not cover a frame NaN offsets - unavailable -: `path` on that dense [W*P, N] array
+(frames_dense) is the wanted recursion along the N frames.  An unavailable candidate never wins under strict <, and ties
+go to the lower (w, h): the order in which the fold of the windows (windows.fold_pose) keeps its candidate, so weight 0 is
+the pooled per-frame pick.  frames_path does that per line (t, j) and takes the offsets against the pooled per-frame mean.
+Its limits: A LINE DIES WHOLE - one frame at which no candidate is available, or a line that is never observed, has no
+path at any frame of the video; segments that restart are not built -, the dense form and the device's workspace grow with
+the length of the video, and it still is no smoother of the pose values.
 
 This module is test infrastructure and the documentation of the arithmetic.  The product path never calls it.
 """
@@ -107,14 +117,18 @@ def path(e2, off, lam):
         back = np.zeros((L, F, P), dtype=np.int64)
         total = np.zeros(L)
         c = u[:, :, 0].copy()
+        some = avail.any(axis=0)                                       # [P,F]: available on any line at all
         for f in range(F):
             if f:
                 best = np.full((L, P), inf)
-                for hp in range(P):
-                    v = c[:, hp, None] + transition(off[:, :, f], off[:, hp, None, f - 1], lam)
-                    better = v < best                                  # strict: the first minimum wins, a NaN never
-                    best = np.where(better, v, best)
-                    back[:, f] = np.where(better, hp, back[:, f])
+                # an h or h' that no line has available gives NaN transitions only, and a NaN never wins: leaving those
+                # columns and rounds out changes no bit (frames_path's dense form is mostly such candidates)
+                cols = np.flatnonzero(some[:, f])
+                for hp in np.flatnonzero(some[:, f - 1]):
+                    v = c[:, hp, None] + transition(off[:, cols, f], off[:, hp, None, f - 1], lam)
+                    better = v < best[:, cols]                         # strict: the first minimum wins, a NaN never
+                    best[:, cols] = np.where(better, v, best[:, cols])
+                    back[:, f, cols] = np.where(better, hp, back[:, f, cols])
                 c = u[:, :, f] + best
             m = np.min(np.where(np.isnan(c), inf, c), axis=1)
             total = total + m
@@ -177,11 +191,71 @@ def path_cost(e2, off, lam, idx):
 
 def brute_force(e2, off, lam):
     """The minimum of path_cost over all P**F paths of one tiny line -> (cost, a path that attains it).  Ties between paths
-    are broken differently from the recursion: compare the costs, not the paths."""
+    are broken differently from the recursion: compare the costs, not the paths.  A path through an unavailable hypothesis
+    costs +inf or NaN and never is the minimum, so only the available ones of every frame are walked (the dense form of
+    frames_path is mostly unavailable candidates)."""
     P, F = np.asarray(e2).shape
     best, arg = np.inf, None
-    for hs in itertools.product(range(P), repeat=F):
+    with np.errstate(all="ignore"):
+        avail = np.isfinite(np.asarray(off).astype(np.float64)).all(axis=-1)
+    for hs in itertools.product(*(np.flatnonzero(avail[:, f]).tolist() for f in range(F))):
         v = path_cost(e2, off, lam, hs)
         if v < best:
             best, arg = v, hs
     return best, arg
+
+
+# --------------------------------------------------------------------------------- the path of a whole video (section 6l)
+def frames_dense(e2, wb, mean, starts, valid, N):
+    """The candidates of a video in dense form.  e2 [W,T,P,F,J] fp32 (gated), wb [W,T,P,F,J,3] fp32: the hypotheses of the W
+    windows of one video, window w covering the frames [starts[w], starts[w] + valid[w]); mean [T,N,J,3] fp32 or None.
+    Candidate g = w * P + h.  -> (e2 [T,J,W*P,N] fp32, off [T,J,W*P,N,3] fp64): off = (double)w - (double)mean[t,n,j] where
+    window w covers frame n, NaN - unavailable - elsewhere (the padding f >= valid[w] of a short video included)."""
+    e2 = np.asarray(e2, dtype=np.float32)
+    wb = np.asarray(wb, dtype=np.float32)
+    W, T, P, F, J = e2.shape
+    N = int(N)
+    assert wb.shape == (W, T, P, F, J, 3) and len(starts) == W and len(valid) == W
+    m = np.zeros((T, N, J, 3)) if mean is None else np.asarray(mean, dtype=np.float32).astype(np.float64)
+    assert m.shape == (T, N, J, 3)
+    de = np.full((T, J, W * P, N), np.nan, dtype=np.float32)
+    do = np.full((T, J, W * P, N, 3), np.nan)
+    for w in range(W):
+        s, v = int(starts[w]), int(valid[w])
+        assert 1 <= v <= F and 0 <= s and s + v <= N
+        de[:, :, w * P:(w + 1) * P, s:s + v] = e2[w, :, :, :v].transpose(0, 3, 1, 2)                      # [T,J,P,v]
+        with np.errstate(all="ignore"):
+            do[:, :, w * P:(w + 1) * P, s:s + v] = (wb[w, :, :, :v].astype(np.float64).transpose(0, 3, 1, 2, 4)
+                                                    - m[:, s:s + v].transpose(0, 2, 1, 3)[:, :, None])    # [T,J,P,v,3]
+    return de, do
+
+
+def frames_path(e2, wb, mean, starts, valid, N, lam):
+    """The path of every line (t, j) of a VIDEO: at frame n the candidates are the pairs (window, hypothesis) of all windows
+    that cover n, and `path` runs on their dense form (frames_dense) along the N frames - an unavailable candidate never
+    wins, ties go to the lower (window, hypothesis).  e2 [W,T,P,F,J] fp32 unary (gated), wb [W,T,P,F,J,3] fp32, mean
+    [T,N,J,3] fp32 as the pooled finish writes it (None: absolute offsets), starts / valid as windows.window_starts gives them.
+    -> dict idx [T,N,J] int32 (the hypothesis), window [T,N,J] int32, pick [T,N,J,3] fp32, e2 [T,N,J] fp32 (+inf at an
+    unobserved frame), cost [T,J] fp64; -1 / -1 / NaN / +inf / NaN on a line without a path - one frame without an
+    available candidate, or no observed frame at all, removes the path of the line at EVERY frame."""
+    e2 = np.asarray(e2, dtype=np.float32)
+    wb = np.asarray(wb, dtype=np.float32)
+    W, T, P, F, J = e2.shape
+    N = int(N)
+    de, do = frames_dense(e2, wb, mean, starts, valid, N)
+    g, cost = path(de, do, lam)                                        # [T,J,N], [T,J]
+    g = np.ascontiguousarray(np.moveaxis(g, 1, 2))                     # [T,N,J]
+    none = g < 0
+    at = np.maximum(g, 0).astype(np.int64)
+    win, idx = at // P, at % P
+    f = np.clip(np.arange(N)[None, :, None] - np.asarray(starts, dtype=np.int64)[win], 0, F - 1)
+    tt, jj = np.arange(T)[:, None, None], np.arange(J)[None, None, :]
+    sel = wb[win, tt, idx, f, jj]                                      # [T,N,J,3]
+    e2_at = e2[win, tt, idx, f, jj]
+    with np.errstate(all="ignore"):
+        fin = np.isfinite(do).all(axis=-1) & np.isfinite(de)           # [T,J,G,N]
+    observed = np.moveaxis(fin.any(axis=2), 1, 2)                      # [T,N,J]
+    e2_at = np.where(observed & ~none, e2_at, np.float32(np.inf)).astype(np.float32)
+    sel = np.where(none[..., None], np.float32(np.nan), sel).astype(np.float32)
+    return {"idx": np.where(none, -1, idx).astype(np.int32), "window": np.where(none, -1, win).astype(np.int32),
+            "pick": sel, "e2": e2_at, "cost": cost}

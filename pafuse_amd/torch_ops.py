@@ -16,6 +16,7 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::aggregate_poses(pred, conn, x2d?, traj?, cam?)  P-Agg mean pose, J-Agg pose and its hypothesis index, one shard
   pafuse::aggregate_poses_fit(pred, conn, x2d, cam, conf?)  the same without a trajectory: roots fitted on the device; + tfit
   pafuse::pose_path(pred, conn, x2d, root, cam, weight, conf?, mean?)   J-Agg coherent in time: per joint a path through the hypotheses
+  pafuse::frames_path(pred, conn, x2d, root, cam, weight, starts, valid, conf?, mean?)   that path along a whole video, across its windows
   pafuse::fold_windows(frame!, N, state, shape, starts, valid, w0, num_proposals)   a batch of overlapping windows into the frame state
   pafuse::finish_frames(frame, N, T, J, spread?)          one pose per video frame: mean, pick, idx, window (+ std, cov)
   pafuse::fit_trajectory(pose, x2d, cam, conf?)           the camera-space root of that pose: traj, wsum, resid per (t, frame)
@@ -410,6 +411,26 @@ def _(pred, conn, x2d, root, cam, weight, conf=None, mean=None):
     B, T, P, F, J, _ = pred.shape
     return [pred.new_empty(B, T, F, J, 3), pred.new_empty((B, T, F, J), dtype=torch.int32), pred.new_empty(B, T, F, J),
             pred.new_empty((B, T, J), dtype=torch.float64)]
+
+
+@torch.library.custom_op("pafuse::frames_path", mutates_args=(), device_types="cuda")
+def frames_path(pred: torch.Tensor, conn: torch.Tensor, x2d: torch.Tensor, root: torch.Tensor, cam: torch.Tensor, weight: float,
+                starts: List[int], valid: List[int], conf: Optional[torch.Tensor] = None,
+                mean: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+    """pafuse_amd.ops.frames_path (the J-Agg path of a whole video): pred [W,T,P,F,J,3] ALL part-centred hypotheses of the W
+    windows, x2d [N,J,2], root [N,3] or [W,T,P,F,3], cam [9], weight >= 0, starts / valid W host integers each (the whole
+    video), conf [N,J] or None, mean [T,N,J,3] or None -> [pick [T,N,J,3], idx [T,N,J] int32, window [T,N,J] int32,
+    e2 [T,N,J], cost [T,J] float64]; a line without a path: NaN, -1, -1, +inf, NaN."""
+    from . import ops
+    m = ops.frames_path(pred, conn, x2d, root, cam, weight, starts, valid, conf=conf, mean=mean, want=ops.FRAMES_PATH_OUTPUTS)
+    return [m[k] for k in ops.FRAMES_PATH_OUTPUTS]
+
+
+@frames_path.register_fake
+def _(pred, conn, x2d, root, cam, weight, starts, valid, conf=None, mean=None):
+    T, J, N = pred.shape[1], pred.shape[4], x2d.shape[0]
+    return [pred.new_empty(T, N, J, 3), pred.new_empty((T, N, J), dtype=torch.int32), pred.new_empty((T, N, J), dtype=torch.int32),
+            pred.new_empty(T, N, J), pred.new_empty((T, J), dtype=torch.float64)]
 
 
 # ----------------------------------------------------------------------------------- spread of the hypotheses
