@@ -21,6 +21,10 @@ Ground-truth 2-D has no dropouts: without the planting nobody can measure whethe
 joint one path through the hypotheses instead of every frame's own winner (harness.evaluate_frames(path_weight=...)).
 `--path-scope video` runs that path along the whole video instead, across clip seams and the pooled windows of `--stride S`
 (the candidates of a frame are the hypotheses of all windows covering it; at most 256, kept on the device for the whole video).
+`--smooth-pose [R]` (with `--frames`; R in 1 .. 64, default 13; `--smooth-pose-floor S` metres, default 0.001) scores the pose
+SMOOTHED along the frames with the covariance of the hypotheses as matrix weight (harness.evaluate_frames(pose_smooth=...)):
+compare the mpjpe and accel columns with a run without it.  What it buys on a real checkpoint has not been measured: this is the
+tool that measures it.  The 1 mm floor is a regulariser (a zero covariance stays solvable), not a tuned value.
 Without `--data` the synthetic H3WB files of tests/golden/h3wb_synth are used (random weights: numbers are meaningless).
 """
 import argparse
@@ -77,8 +81,18 @@ def main():
     ap.add_argument("--path-scope", choices=("clip", "video"), default="clip",
                     help="with --path-weight: 'clip' (default) one path per un-strided clip; 'video' one path along the whole video, "
                          "across clip seams and the pooled windows of any --stride")
+    ap.add_argument("--smooth-pose", type=int, default=None, nargs="?", const=13, metavar="R",
+                    help="with --frames: score the pose smoothed along the frames within R (1 .. 64, default 13), every frame weighted "
+                         "by the inverse covariance of its hypotheses; compare the mpjpe and accel columns")
+    ap.add_argument("--smooth-pose-floor", type=float, default=1e-3, metavar="S",
+                    help="with --smooth-pose: the standard deviation in metres added to every covariance (finite, > 0; default 0.001, "
+                         "a regulariser, not a tuned value)")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.smooth_pose is not None and not (a.frames and 1 <= a.smooth_pose <= 64):
+        ap.error("--smooth-pose takes a radius in 1 .. 64 and needs --frames")
+    if not 0.0 < a.smooth_pose_floor < float("inf"):
+        ap.error("--smooth-pose-floor takes a finite length > 0 in metres")
     if a.path_scope == "video" and a.path_weight is None:
         ap.error("--path-scope video needs --path-weight")
     if a.path_weight is not None and not (a.frames and a.aggregate in ("reproj", "reproj_fit") and (a.stride is None or a.path_scope == "video")
@@ -133,7 +147,7 @@ def main():
                              trajectory=None if a.trajectory is None else (a.trajectory or True), log=log,
                              hypothesis_chunk=a.hypothesis_chunk, p2=bool(args.ft2d.p2), seam_profile=a.seam_profile,
                              focal="estimate" if a.estimate_focal else None, repair=a.repair, drop=drop, path_weight=a.path_weight,
-                             path_scope=a.path_scope)
+                             path_scope=a.path_scope, pose_smooth=a.smooth_pose, pose_smooth_floor=a.smooth_pose_floor)
     else:
         h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
                       batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),

@@ -57,6 +57,16 @@ instead of every frame's own winner.  It works per clip - the clip seams stay - 
 --path-scope video runs that path along the whole video instead, across the clip seams and the pooled windows of --stride S: the
 candidates of a frame are the hypotheses of all windows covering it (at most 256; they stay on the device for the whole video).  The
 per-frame files of --stride are written, and test_3d_output_pick_path_cost.npy [steps,134], the cost of every joint's path (NaN: none).
+
+--smooth-pose [R] (default 13 frames; --smooth-pose-floor S metres, default 0.001; with --aggregate mean, and with --reproj-fit
+under --stride or --path-scope video) smooths the POSE VALUES along the frames on the device, per joint: a local-linear filter of
+radius R in which every frame enters with the inverse covariance of its hypotheses as a matrix weight - a joint the hypotheses
+disagree on along some direction is carried along that direction by its neighbours' line (harness.smooth_poses,
+infer_sequence(pose_smooth=...)).  The files above then hold the smoothed pose - the trajectory is fitted on it - and
+test_3d_output_raw.npy (_pick_raw.npy) what they held, test_3d_output_smooth_code.npy (_pick_smooth_code.npy) [T,frames,134] 1 line,
+2 weighted mean, 3 nothing in reach.  The floor is a regulariser (a zero covariance stays solvable), not a tuned value.  A fixed-radius
+linear smoother: no motion model, no bone lengths; what it buys on real weights has not been measured (evaluate_h3wb.py --frames
+--smooth-pose measures it).
 """
 import argparse
 import json
@@ -128,8 +138,21 @@ def main():
     ap.add_argument("--path-scope", choices=("clip", "video"), default="clip",
                     help="with --path-weight: 'clip' (default) one path per clip; 'video' one path along the whole video, across clip "
                          "seams and the pooled windows of any --stride (per-frame output)")
+    ap.add_argument("--smooth-pose", type=int, default=None, nargs="?", const=13, metavar="R",
+                    help="smooth the pose along the frames on the device within R frames (1 .. 64, default 13), every frame weighted by "
+                         "the inverse covariance of its hypotheses; the unsmoothed pose goes to test_3d_output_raw.npy")
+    ap.add_argument("--smooth-pose-floor", type=float, default=1e-3, metavar="S",
+                    help="with --smooth-pose: the standard deviation in metres added to every covariance (finite, > 0; default 0.001, "
+                         "a regulariser, not a tuned value)")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.smooth_pose is not None and (not 1 <= a.smooth_pose <= 64 or not (
+            a.aggregate == "mean" or (a.reproj_fit is not None and (a.stride is not None or a.path_scope == "video")))):
+        ap.error("--smooth-pose takes a radius in 1 .. 64 frames and needs --aggregate mean, or --reproj-fit with --stride or "
+                 "--path-scope video (one pose per video frame)")
+    if not 0.0 < a.smooth_pose_floor < float("inf"):
+        ap.error("--smooth-pose-floor takes a finite length > 0 in metres")
+    smoothing = {} if a.smooth_pose is None else dict(pose_smooth=a.smooth_pose, pose_smooth_floor=a.smooth_pose_floor)
     if a.path_scope == "video" and a.path_weight is None:
         ap.error("--path-scope video needs --path-weight")
     if a.path_weight is not None and (a.reproj_fit is None or (a.stride is not None and a.path_scope == "clip") or a.hypothesis_chunk is not None
@@ -190,13 +213,14 @@ def main():
     camera = dict(focal="estimate") if a.estimate_focal else dict(cam=None if a.trajectory is None else pinhole(a.trajectory))
     if a.reproj_fit is not None:
         cam = pinhole(a.reproj_fit)
+        per_frame = a.stride is not None or a.path_scope == "video"
         pick = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="reproj_fit",
                                       cam=cam, conf=conf, hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride,
-                                      path_weight=a.path_weight, path_scope=a.path_scope)
-        per_frame = a.stride is not None or a.path_scope == "video"
+                                      path_weight=a.path_weight, path_scope=a.path_scope,
+                                      **(smoothing if per_frame else {}))
         if per_frame:                    # per-frame arrays already
             for k, name in (("pose", "pick"), ("idx", "pick_idx"), ("window", "pick_window"), ("std", "pick_std"), ("cov", "pick_cov"),
-                            ("path_cost", "pick_path_cost")):
+                            ("path_cost", "pick_path_cost"), ("pose_raw", "pick_raw"), ("pose_smooth_code", "pick_smooth_code")):
                 if k in pick:
                     save(f"test_3d_output_{name}.npy", pick[k])
             save("test_3d_output_count.npy", pick["count"])
@@ -216,21 +240,29 @@ def main():
         wanted = {} if a.trajectory is None else dict(conf=conf, trajectory=True if a.smooth_trajectory is None else a.smooth_trajectory,
                                                       **camera)
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
-                                      hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride, **wanted)
-        for k in ("std", "cov", "count"):
+                                      hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride, **wanted, **smoothing)
+        for k, name in (("std", "std"), ("cov", "cov"), ("count", "count"), ("pose_raw", "raw"), ("pose_smooth_code", "smooth_code")):
             if k in pred:
-                save(f"test_3d_output_{k}.npy", pred[k])
+                save(f"test_3d_output_{name}.npy", pred[k])
         poses = pred["pose"]                                                        # [T,frames,134,3]
         traj = pred if a.trajectory is not None else None
     elif a.aggregate == "mean":
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
-                                      hypothesis_chunk=a.hypothesis_chunk, spread=a.spread)
-        if a.spread is not None:
-            for k in ("std", "cov")[:1 if a.spread == "std" else 2]:
+                                      hypothesis_chunk=a.hypothesis_chunk, spread="cov" if a.smooth_pose is not None else a.spread)
+        cov = None
+        if isinstance(pred, dict):
+            if a.smooth_pose is not None:    # consecutive clips: the filter runs on the stitched per-frame arrays
+                cov = harness.stitch_spread(pred["cov"], keypoints.shape[0], model.frames)
+            for k in ("std", "cov")[:0 if a.spread is None else 1 if a.spread == "std" else 2]:
                 np.save(os.path.join(a.out, f"test_3d_output_{k}.npy"),
                         harness.stitch_spread(pred[k], keypoints.shape[0], model.frames).numpy(), allow_pickle=True)
             pred = pred["pose"]
         poses = harness.stitch_poses(pred, keypoints.shape[0], model.frames)        # [T,frames,134,3]
+        if a.smooth_pose is not None:        # before the trajectory: the root is fitted on the smoothed pose
+            smoothed = harness.smooth_poses(poses, cov, radius=a.smooth_pose, floor=a.smooth_pose_floor)
+            save("test_3d_output_raw.npy", smoothed["pose_raw"])
+            save("test_3d_output_smooth_code.npy", smoothed["pose_smooth_code"])
+            poses = smoothed["pose"]
         if a.trajectory is not None:     # consecutive clips: the fit runs on the stitched per-frame array
             traj = harness.fit_trajectory(poses, keypoints, conf=conf, smooth=a.smooth_trajectory, **camera)
     else:

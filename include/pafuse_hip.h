@@ -883,6 +883,39 @@ int pafuse_detections_repair(const float *x2d /* [N,J,2] */, const float *conf /
                              float threshold /* >= 0 */, float *out /* [N,J,2], may not alias x2d */,
                              float *conf_out /* [N,J] or NULL, may not alias conf */, uint8_t *status /* [N,J] */, void *stream);
 
+/* The per-frame pose smoothed along the frames, every frame weighted by the inverse of its hypothesis covariance
+ * (pafuse_amd/posesmooth.py states the arithmetic, operation for operation).  A fixed-radius
+ * local-linear filter per joint: frame m enters with the MATRIX weight W = (Sigma + floor^2*I)^-1, Sigma the covariance of
+ * its hypotheses (pafuse_frames_finish's cov: xx xy xz yy yz zz) - it is trusted in each direction as far as its hypotheses
+ * agree in that direction and otherwise carried by its neighbours' line.  All in fp64 with contraction off.
+ * Row (t, m, j): the cofactors and determinant of Sigma + floor^2*I; the row takes part iff the three components of its pose are
+ * finite, the determinant is finite and the three leading minors are > 0 (a NaN in cov removes the row, as does an indefinite
+ * covariance); W = cofactors / det.
+ * Output (t, n, j): over m = max(0, n - r) .. min(N - 1, n + r) ascending, d = m - n, g the taper of pafuse_trajectory_smooth:
+ *   A0, A1, A2 = sum g*W*(1, d, d*d);   b0, b1 = sum g*W*y*(1, d)
+ *   two rows or more and the 6x6 system [[A2, A1], [A1, A0]] [slope; value] = [b1; b0] factors by LDL^T (no square root, no
+ *   pivot search) with six pivots finite and > 0 and a finite value:  value, the local line at d = 0   (code 1)
+ *   else a row or more and A0 value = b0 factors the same way:  value, the weighted mean             (code 2)
+ *   else NaN                                                                                          (code 3)
+ * rounded once to fp32; a value that is not finite in fp32 is code 3, NaN.  With equal covariances W cancels and the result
+ * is pafuse_trajectory_smooth's filter per joint: constant velocity passes without lag or end-shrinkage.  The matrix weights act
+ * only where the covariance VARIES along the frames.  No motion model, no covariance of the result, no bone-length constraint.
+ *   cov   [T,N,J,6] or NULL: all zeros - every frame weighs the same in every direction
+ *   floor metres, finite and > 0: a regulariser that keeps a zero covariance (one hypothesis, or identical ones) solvable, not
+ *         a tuned value
+ *   out   [T,N,J,3], may not alias pose;   code uint8 [T,N,J] or NULL
+ *   workspace  pafuse_pose_smooth_workspace_bytes(T, N, J) = 48 bytes per (t, n, j), 8-byte aligned, the caller's: the first of
+ *              the two kernels stores W of every row there once, the second walks it (forming W again at every visit instead
+ *              needs no workspace, gives the same bits and measured 1.2 times slower)
+ * Two kernels on the stream, one thread per row and one per (t, n, j); no atomics, no host synchronisation, bit-reproducible.
+ * Refused (PAFUSE_E_ARG) before any HIP call: a null pose or out, T, N or J < 1, radius outside 1 .. 64, a floor that is not
+ * finite and > 0, out == pose, a workspace that is null, too small or not 8-byte aligned, a grid out of range. */
+size_t pafuse_pose_smooth_workspace_bytes(int32_t T, int32_t N, int32_t J); /* 0 if a size is < 1 */
+int pafuse_pose_smooth(const float *pose /* [T,N,J,3] */, const float *cov /* [T,N,J,6] or NULL */, int32_t T, int32_t N,
+                       int32_t J, int32_t radius /* 1..64 */, float floor /* metres, > 0 */,
+                       float *out /* [T,N,J,3], may not alias pose */, uint8_t *code /* [T,N,J] or NULL */,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
 /* The focal length of the video's camera from the finished per-frame pose and its detections, part one: the sums per
  * (t, frame) (pafuse_amd/focal.py states the arithmetic).  Operands as pafuse_frames_root_fit, except
  * that of cam only cx, cy = cam[2:4] and the pixel aspect rho = cam[1]/cam[0] are read: cam and cam with fx, fy doubled give

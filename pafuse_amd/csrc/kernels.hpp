@@ -4129,6 +4129,13 @@ __global__ void __launch_bounds__(256) frames_root_fit_kernel(const FramesRootFi
 // rounds once.  The kinds are the status codes 1, 2, 3 of the repair.
 enum LineKind { LINE_FIT = 1, LINE_MEAN = 2, LINE_NONE = 3 };
 
+// the taper of every filter along the frames at the offset d, span = (r+1)^2: the biweight (1 - d*d/span)^2
+__device__ __forceinline__ double line_taper(int d, double span) {
+#pragma clang fp contract(off)
+    const double q = (double)(d * d) / span, h = 1.0 - q, g = h * h;
+    return g;
+}
+
 template <int C>
 struct LineFilter {
     const double span;
@@ -4139,7 +4146,7 @@ struct LineFilter {
     __device__ __forceinline__ void add(int d, double weight, const double (&y)[C]) {
 #pragma clang fp contract(off)
         const double dd = (double)d;
-        const double q = (double)(d * d) / span, h = 1.0 - q, g = h * h;
+        const double g = line_taper(d, span);
         const double om = g * weight, omd = om * dd;
         S0 += om, S1 += omd, S2 += omd * dd;
 #pragma unroll
@@ -4259,6 +4266,177 @@ __global__ void __launch_bounds__(256) detections_repair_kernel(const Detections
     }
     p.out[e * 2] = vx, p.out[e * 2 + 1] = vy, p.status[e] = (uint8_t)st;
     if (p.conf_out) p.conf_out[e] = 0.f;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// The per-frame pose smoothed along the frames, every frame weighted by the inverse of its hypothesis covariance (DESIGN.md
+// section 6m; statement: pafuse_amd/posesmooth.py, which fixes every operation and its order - this code follows it
+// operation for operation).  Row (t, m, j): Sigma + floor^2*I from the six covariance entries (null: zeros), its cofactors
+// and determinant; the row takes part iff its pose is finite, det is finite and xx, c22, det > 0; W = cofactors / det.
+// Output (t, n, j): over m = max(0, n - r) .. min(N - 1, n + r), d = m - n, with LineFilter's taper g: G = g*W, Gd = G*d,
+// Gdd = Gd*d, z = G*y, zd = z*d added into A0, A1, A2, b0, b1 - 24 fp64 sums - and a count.  LINE_FIT: two rows or more,
+// [[A2, A1], [A1, A0]] [slope; value] = [b1; b0] factors by ldl_solve with six pivots finite and > 0 and a finite value;
+// else LINE_MEAN: a row or more and A0 value = b0 factors; else LINE_NONE, NaN.  Rounded once; not finite in fp32: LINE_NONE.
+//
+// ldl_solve: LDL^T without a square root or a pivot search on the packed lower triangle M[tri(i, j)], i >= j; the last TAIL
+// unknowns are back-substituted.  Every loop has constant bounds and is unrolled, so u, l, w stay in registers.
+// ----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }                          // i >= j
+__device__ __forceinline__ constexpr int sym3(int k, int l) { return k <= l ? k * (5 - k) / 2 + l : l * (5 - l) / 2 + k; }  // xx xy xz yy yz zz
+
+template <int NDIM, int TAIL>
+__device__ __forceinline__ bool ldl_solve(const double (&M)[NDIM * (NDIM + 1) / 2], const double (&b)[NDIM], double (&x)[TAIL]) {
+#pragma clang fp contract(off)
+    double u[NDIM * (NDIM + 1) / 2], l[NDIM * (NDIM + 1) / 2], D[NDIM], w[NDIM], xs[NDIM];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < NDIM; ++j) {
+#pragma unroll
+        for (int i = j; i < NDIM; ++i) {
+            double v = M[tri(i, j)];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v = v - u[tri(i, k)] * l[tri(j, k)];
+            u[tri(i, j)] = v;
+        }
+        D[j] = u[tri(j, j)];
+        ok = ok && isfinite(D[j]) && D[j] > 0.0;
+#pragma unroll
+        for (int i = j + 1; i < NDIM; ++i) l[tri(i, j)] = u[tri(i, j)] / D[j];
+    }
+#pragma unroll
+    for (int i = 0; i < NDIM; ++i) {
+        double v = b[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) v = v - l[tri(i, k)] * w[k];
+        w[i] = v;
+    }
+#pragma unroll
+    for (int i = NDIM - 1; i >= NDIM - TAIL; --i) {
+        double v = w[i] / D[i];
+#pragma unroll
+        for (int k = i + 1; k < NDIM; ++k) v = v - l[tri(k, i)] * xs[k];
+        xs[i] = v;
+    }
+#pragma unroll
+    for (int k = 0; k < TAIL; ++k) x[k] = xs[NDIM - TAIL + k];
+    return ok;
+}
+
+// Two kernels on one stream.  pose_precision_kernel: one thread per row forms W once and stores its six doubles in the caller's
+// workspace; a row that takes no part gets a NaN in W[0] (the W[0] = c00/det of a row that takes part is never NaN: det is
+// finite and > 0 and an infinite c00 would have made det infinite or NaN).  pose_smooth_kernel: one thread per (t, n, j),
+// e = (t*N + n)*J + j with j fastest: at every m the lanes of a wave read adjacent 12-byte pose rows and 48-byte precision
+// rows of one frame, and the m loop is uniform across the wave; the (2r+1)-fold re-reads are cache hits.  (The one-kernel form,
+// which forms W again at every visit and needs no workspace, gave the same bits and was 1.2x slower: DESIGN.md section 6m.)
+// fp64, contraction off, rounded once.  No LDS, no atomics, no barrier, no scratch; nothing depends on the launch shape.
+struct PoseSmoothParams {
+    const float* pose;   // [T,N,J,3]
+    const float* cov;    // [T,N,J,6] xx xy xz yy yz zz, or null: zeros
+    float* out;          // [T,N,J,3]
+    uint8_t* code;       // [T,N,J] or null
+    int T, N, J, radius;
+    float floor;
+    double* precision;   // [T,N,J,6] workspace: W per row, NaN in W[0] where the row takes no part
+};
+
+// the precision W = (Sigma + floor^2 I)^-1 of row em and whether the row takes part
+__device__ __forceinline__ bool pose_row_precision(const PoseSmoothParams& p, int64_t em, double s2, double (&W)[6]) {
+#pragma clang fp contract(off)
+    const float y0 = p.pose[em * 3 + 0], y1 = p.pose[em * 3 + 1], y2 = p.pose[em * 3 + 2];
+    double xx = s2, xy = 0.0, xz = 0.0, yy = s2, yz = 0.0, zz = s2;
+    if (p.cov) {
+        const float* c = p.cov + em * 6;
+        xx = (double)c[0] + s2, xy = (double)c[1], xz = (double)c[2], yy = (double)c[3] + s2, yz = (double)c[4], zz = (double)c[5] + s2;
+    }
+    W[0] = yy * zz - yz * yz;
+    W[1] = xz * yz - xy * zz;
+    W[2] = xy * yz - xz * yy;
+    W[3] = xx * zz - xz * xz;
+    W[4] = xy * xz - xx * yz;
+    W[5] = xx * yy - xy * xy;
+    const double det = (xx * W[0] + xy * W[1]) + xz * W[2];
+    const bool part = isfinite(y0) && isfinite(y1) && isfinite(y2) && isfinite(det) && xx > 0.0 && W[5] > 0.0 && det > 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) W[k] = W[k] / det;
+    return part;
+}
+
+__global__ void __launch_bounds__(256) pose_precision_kernel(const PoseSmoothParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)p.T * p.N * p.J) return;
+    const double s2 = (double)p.floor * (double)p.floor;
+    double W[6];
+    const bool part = pose_row_precision(p, e, s2, W);
+    if (!part) W[0] = __builtin_nan("");
+#pragma unroll
+    for (int k = 0; k < 6; ++k) p.precision[e * 6 + k] = W[k];
+}
+
+__global__ void __launch_bounds__(256) pose_smooth_kernel(const PoseSmoothParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)p.T * p.N * p.J) return;
+    const int J = p.J, r = p.radius, n = (int)((e / J) % p.N);
+    const double span = (double)((r + 1) * (r + 1));
+    double A0[6] = {}, A1[6] = {}, A2[6] = {}, b0[3] = {}, b1[3] = {};
+    int cnt = 0;
+    const int lo = max(0, n - r), hi = min(p.N - 1, n + r);
+    for (int m = lo; m <= hi; ++m) {
+        const int d = m - n;
+        const int64_t em = e + (int64_t)d * J;   // (t, m, j)
+        double W[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) W[k] = p.precision[em * 6 + k];
+        if (W[0] != W[0]) continue;   // the row takes no part
+        const float y0 = p.pose[em * 3 + 0], y1 = p.pose[em * 3 + 1], y2 = p.pose[em * 3 + 2];
+        const double g = line_taper(d, span), dd = (double)d;
+        const double y[3] = {(double)y0, (double)y1, (double)y2};
+        double G[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            G[k] = g * W[k];
+            const double Gd = G[k] * dd;
+            A0[k] += G[k], A1[k] += Gd, A2[k] += Gd * dd;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double z = (G[sym3(k, 0)] * y[0] + G[sym3(k, 1)] * y[1]) + G[sym3(k, 2)] * y[2];
+            b0[k] += z, b1[k] += z * dd;
+        }
+        ++cnt;
+    }
+    double v[3] = {};
+    int kind = LINE_NONE;
+    if (cnt >= 2) {
+        double M[21], rhs[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) {
+                const double a = i < 3 ? A2[sym3(i % 3, j % 3)] : j < 3 ? A1[sym3(i % 3, j % 3)] : A0[sym3(i % 3, j % 3)];
+                M[tri(i, j)] = a;
+            }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) rhs[k] = b1[k], rhs[3 + k] = b0[k];
+        if (ldl_solve<6, 3>(M, rhs, v) && isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2])) kind = LINE_FIT;
+    }
+    if (kind == LINE_NONE && cnt >= 1) {
+        double M[6];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) M[tri(i, j)] = A0[sym3(i, j)];
+        if (ldl_solve<3, 3>(M, b0, v)) kind = LINE_MEAN;
+    }
+    float o[3] = {(float)v[0], (float)v[1], (float)v[2]};
+    if (kind == LINE_NONE || !(isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]))) {
+        kind = LINE_NONE;
+        o[0] = o[1] = o[2] = __builtin_nanf("");
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p.out[e * 3 + k] = o[k];
+    if (p.code) p.code[e] = (uint8_t)kind;
 }
 
 // ----------------------------------------------------------------------------------------------------------------

@@ -2335,6 +2335,33 @@ int pafuse_detections_repair(const float* x2d, const float* conf, const int32_t*
     return PAFUSE_OK;
 }
 
+// the per-frame pose smoothed along the frames with the inverse hypothesis covariance as matrix weight (pose_precision_kernel,
+// then pose_smooth_kernel, on the stream); the argument checks come before the first HIP call
+size_t pafuse_pose_smooth_workspace_bytes(int32_t T, int32_t N, int32_t J) {
+    return T < 1 || N < 1 || J < 1 ? 0 : (size_t)T * (size_t)N * (size_t)J * 6 * sizeof(double);
+}
+
+int pafuse_pose_smooth(const float* pose, const float* cov, int32_t T, int32_t N, int32_t J, int32_t radius, float floor,
+                       float* out, uint8_t* code, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!pose || !out) return fail(PAFUSE_E_ARG, "pose_smooth: pose and out are needed (cov may be null: zeros; code may be null)");
+    if (T < 1 || N < 1 || J < 1) return fail(PAFUSE_E_ARG, "pose_smooth: bad size (T=%d N=%d J=%d)", T, N, J);
+    if (radius < 1 || radius > 64) return fail(PAFUSE_E_ARG, "pose_smooth: radius %d outside 1 .. 64", radius);
+    if (!std::isfinite(floor) || !(floor > 0.f)) return fail(PAFUSE_E_ARG, "pose_smooth: floor %g is not finite and > 0", (double)floor);
+    if (out == pose) return fail(PAFUSE_E_ARG, "pose_smooth: out may not alias pose (every thread reads its neighbours' frames)");
+    const size_t need = pafuse_pose_smooth_workspace_bytes(T, N, J);
+    if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 8)
+        return fail(PAFUSE_E_ARG, "pose_smooth: the workspace must hold %zu bytes, 8-byte aligned (pafuse_pose_smooth_workspace_bytes)", need);
+    const int64_t rows = (int64_t)T * N * J;
+    if ((rows + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "pose_smooth: grid out of range");
+    StreamDevice on_stream_device(stream);
+    PoseSmoothParams m{};
+    m.pose = pose, m.cov = cov, m.out = out, m.code = code, m.T = T, m.N = N, m.J = J, m.radius = radius, m.floor = floor;
+    m.precision = (double*)workspace;
+    const int rc = launch<pose_precision_kernel>("pose_precision_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
+    if (rc != PAFUSE_OK) return rc;
+    return launch<pose_smooth_kernel>("pose_smooth_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
+}
+
 // the focal-length sums of every (t, frame) of the finished pose (frames_focal_sums_kernel) and the estimate from them
 // (focal_solve_kernel): the argument checks come before the first HIP call
 int pafuse_frames_focal_sums(const float* pose, const float* x2d, const float* conf, const float* cam, int32_t T, int32_t N,

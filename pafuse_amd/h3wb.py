@@ -251,7 +251,8 @@ def evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, batc
 
 def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
                     batch_size=2, group=None, log=print, action=None, hypothesis_chunk=None, p2=False, seam_profile=False, focal=None,
-                    repair=None, drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip"):
+                    repair=None, drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None,
+                    pose_smooth_floor=1e-3):
     """The frame-level evaluation of every video, looped like :func:`evaluate`: harness.evaluate_frames per (camera, sequence) -
     one pose per video frame (``aggregate``, ``stride``; None: un-strided clips laid end to end), optionally its fitted
     camera-space root (``trajectory``: True or a smoothing radius) - scored on the device; the sums and counts added over the
@@ -266,7 +267,10 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
     joints per status are logged and, with both, detections.repair_error: the RMS 2-D distance of the filled and of the
     unfilled joints from the detections that were dropped, overall and per part.  ``path_weight`` (with "reproj" / "reproj_fit" on
     un-strided clips) scores the pick made coherent in time (harness.evaluate_frames); ``path_scope="video"`` scores one path along the
-    whole video instead, at any ``stride``.  On synthetic weights the numbers mean nothing."""
+    whole video instead, at any ``stride``.  ``pose_smooth`` (a radius 1 .. 64, ``pose_smooth_floor`` metres) scores the pose
+    smoothed along the frames with the covariance of the hypotheses as matrix weight (harness.evaluate_frames): compare the
+    ``mpjpe`` and ``accel`` lines with a run without it - what the smoother buys on a real checkpoint has not been measured.
+    On synthetic weights the numbers mean nothing."""
     from . import detections, harness
     if drop is not None and (not isinstance(drop, (tuple, list)) or len(drop) != 3):
         raise ValueError(f"drop must be (rate, run, seed), got {drop!r}")
@@ -277,7 +281,8 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
                                       trajectory=trajectory, batch_size=batch_size, group=group,
                                       hypothesis_chunk=hypothesis_chunk, p2=p2, per_frame=seam_profile, focal=focal, repair=repair,
                                       drop=None if drop is None else (drop[0], drop[1], int(drop[2]) + video),
-                                      repair_threshold=repair_threshold, path_weight=path_weight, path_scope=path_scope)
+                                      repair_threshold=repair_threshold, path_weight=path_weight, path_scope=path_scope,
+                                      pose_smooth=pose_smooth, pose_smooth_floor=pose_smooth_floor)
         if repair is not None or drop is not None:
             seen, got = got[-1], got[:-1]
             if "status" in seen:

@@ -110,7 +110,7 @@ def repair_detections(seq_2d, conf, dataset=None, anchor=None, radius=13, thresh
 @torch.no_grad()
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
                    hypothesis_chunk=None, spread=None, conf=None, stride=None, trajectory=None, focal=None, repair=None,
-                   repair_threshold=0.0, path_weight=None, path_scope="clip"):
+                   repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None, pose_smooth_floor=1e-3):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -199,8 +199,33 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     from the path; with "reproj_fit" a joint with idx -1 carries the pooled mean.  A joint's path dies whole: one frame at
     which none of its candidates is finite removes it for the video.  Refused: ``hypothesis_chunk``, ``aggregate`` None /
     "mean", and more than 256 candidates per frame (P times the windows that cover one frame).  Under a process group the
-    hypotheses are gathered as ``aggregate=None`` gathers them."""
+    hypotheses are gathered as ``aggregate=None`` gathers them.
+
+    ``pose_smooth`` (a radius r in 1 .. 64, with ``stride`` and an ``aggregate``; None: everything above, unchanged, bit for bit)
+    SMOOTHS THE POSE VALUES along the frames, per joint, on the device (:func:`smooth_poses`; pafuse_amd.posesmooth states the
+    arithmetic): a local-linear filter of radius r in which every frame enters with the matrix weight (cov + floor^2 I)^-1, cov
+    the covariance of the hypotheses pooled at that (t, frame, joint) - a frame is trusted in each direction as far as its
+    hypotheses agree in that direction and is otherwise carried by its neighbours' line.  The spread state is folded for it
+    even when ``spread`` is None; ``"std"`` / ``"cov"`` appear only when ``spread`` asks for them and are unchanged: they
+    describe the hypotheses (about the pooled mean, also when the pick is what gets smoothed), not the smoothed pose.  The
+    filter runs right behind the finish (or the video path) on the pose that is returned - with "reproj_fit" the mean already
+    filled in where idx is -1 - and EVERYTHING DOWNSTREAM SEES THE SMOOTHED POSE: the root fit, the focal estimate, the
+    trajectory.  ``"pose"`` is the smoothed pose; added keys: ``"pose_raw"`` [T,N,J,3], what "pose" was, and
+    ``"pose_smooth_code"`` [T,N,J] uint8 (1: local line, 2: weighted mean - a single frame in reach, 3: nothing in reach, NaN).
+    ``idx`` / ``window`` still name the pick, but the returned joint is no longer any hypothesis's joint.
+    ``pose_smooth_floor`` (metres, finite and > 0; default 1 mm) is a regulariser - it keeps P = 1, whose covariance is
+    exactly 0, and identical hypotheses solvable - not a tuned value.  A fixed-radius linear smoother: no motion model, no
+    bone-length constraint, no covariance of the result; weights that are constant along the frames cancel.  What it buys on
+    real weights has NOT been measured.  Every rank holds the same frame state and runs the same filter.  Without ``stride``
+    use :func:`smooth_poses` on the stitched poses."""
     smooth = _trajectory_radius(trajectory)
+    pose_smooth = _pose_smooth_radius(pose_smooth, pose_smooth_floor)
+    if pose_smooth is not None:
+        if stride is None:
+            raise ValueError("pose_smooth needs stride (one pose per video frame); for stitched clips call harness.smooth_poses")
+        if aggregate is None:
+            raise ValueError('pose_smooth needs aggregate="mean", "reproj" or "reproj_fit": it smooths the ONE pose per frame')
+        pose_smooth = (pose_smooth, float(pose_smooth_floor))
     _focal_mode(focal)
     repair = _repair_radius(repair, repair_threshold)
     path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, getattr(model, "frames", None), path_scope)
@@ -246,13 +271,14 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     dev = next(model.parameters()).device
     if repair is None:
         return _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, trajectory, smooth, focal, dev, path_weight, path_scope)
+                               spread, conf, stride, trajectory, smooth, focal, dev, path_weight, path_scope, pose_smooth)
     from .detections import repair_anchors
     fixed = _repair_detections(seq_2d.squeeze(0) if seq_2d.dim() == 4 else seq_2d, conf, repair_anchors(dataset), repair,
                                float(repair_threshold), dev)
     # the callees cut and flip on the host: the repaired pair takes the place of the input, whole, before either
     out = _infer_sequence(model, dataset, fixed["x2d"].cpu(), kps_left, kps_right, batch_size, group, aggregate, cam, traj,
-                          hypothesis_chunk, spread, fixed["conf"].cpu(), stride, trajectory, smooth, focal, dev, path_weight, path_scope)
+                          hypothesis_chunk, spread, fixed["conf"].cpu(), stride, trajectory, smooth, focal, dev, path_weight, path_scope,
+                          pose_smooth)
     if isinstance(out, dict):
         out["repaired"] = fixed["status"].cpu()
     return out
@@ -291,14 +317,14 @@ def _path_batch(sampler, dataset, x2d, x2d_flip, traj, cam, conf, fit, path_weig
 
 
 def _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                    conf, stride, trajectory, smooth, focal, dev, path_weight=None, path_scope="clip"):
+                    conf, stride, trajectory, smooth, focal, dev, path_weight=None, path_scope="clip", pose_smooth=None):
     """infer_sequence behind its argument checks (and behind the repair of the detections, when one was asked for)"""
     fit = aggregate == "reproj_fit"
     if stride is None and path_scope == "video":      # one path along the video: per-frame results, the clips of cut_clips
         stride = model.frames
     if stride is not None:
         return _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                             spread, conf, int(stride), dev, trajectory is not None, smooth, focal, path_weight, path_scope)
+                             spread, conf, int(stride), dev, trajectory is not None, smooth, focal, path_weight, path_scope, pose_smooth)
     x2d = cut_clips(seq_2d, model.frames).to(dev)
     x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), model.frames).to(dev)
     sampler = ShardedSampler(model, group)
@@ -369,18 +395,22 @@ def cut_windows(seq, starts, frames=27):
 
 
 def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                  conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip"):
+                  conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip", pose_smooth=None):
     """infer_sequence(stride=...): sliding windows pooled into one pose per video frame (arguments already checked)"""
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, dev, trajectory, smooth, focal, path_weight, path_scope)
+                               spread, conf, stride, dev, trajectory, smooth, focal, path_weight, path_scope, pose_smooth)
     return {k: v.cpu() for k, v in out.items()}
 
 
 def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                         conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip"):
-    """_infer_frames with its result left on the device (evaluate_frames scores it there)"""
+                         conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip",
+                         pose_smooth=None):
+    """_infer_frames with its result left on the device (evaluate_frames scores it there); pose_smooth: None or (radius, floor)"""
     from . import ops
     from .windows import coverage, window_starts
+    asked = spread                  # what the caller wants returned; the pose smoother needs the covariance whatever that is
+    if pose_smooth is not None and spread is None:
+        spread = "cov"
     if seq_2d.dim() == 4:
         seq_2d = seq_2d.squeeze(0)
     N, F = seq_2d.shape[0], model.frames
@@ -447,7 +477,8 @@ def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size
                                          spread_state=moments, merged=True)
         frames = accumulate_frames(frames, merged, starts[lo:hi], valid[lo:hi], N, model.num_proposals)
     want = (("mean", "count") + (("pick", "idx", "window") if reproj else ())
-            + (() if spread is None else ("std",) if spread == "std" else ("std", "cov")))
+            + (() if asked is None else ("std",) if asked == "std" else ("std", "cov"))
+            + (("cov",) if pose_smooth is not None and asked != "cov" else ()))
     out = ops.finish_frames(N, frames.T, frames.J, frame=frames.pose, spread=frames.spread, want=want)
     if video:       # one path along the video through the hypotheses of all windows, against the pooled mean
         from .evaluate import path_frames
@@ -459,6 +490,10 @@ def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size
         out["pick"] = torch.where((out["idx"] < 0).unsqueeze(-1), out["mean"], out["pick"])
     out["pose"] = out.pop("pick") if reproj else out["mean"]
     out.pop("mean", None)
+    if pose_smooth is not None:     # right behind the finish, on the pose that is returned: everything below sees the smoothed pose
+        cov = out["cov"] if asked == "cov" else out.pop("cov")
+        out["pose_raw"] = out["pose"].contiguous()
+        out["pose"], out["pose_smooth_code"] = ops.smooth_poses(out["pose_raw"], cov, pose_smooth[0], floor=pose_smooth[1], want_code=True)
     if trajectory:  # the root of the pose that is returned, on the device before anything crosses to the host
         out.update(_fit_trajectory(out["pose"], seq_2d.to(dev), cam, None if frame_conf is None else frame_conf.to(dev), smooth, focal))
     return out
@@ -471,6 +506,17 @@ def _trajectory_radius(trajectory, name="trajectory"):
     if isinstance(trajectory, bool) or not isinstance(trajectory, int) or not 1 <= trajectory <= 64:
         raise ValueError(f"{name} must be None, True (the per-frame fit) or a smoothing radius in 1 .. 64, got {trajectory!r}")
     return trajectory
+
+
+def _pose_smooth_radius(pose_smooth, floor=1e-3, name="pose_smooth"):
+    """infer_sequence's `pose_smooth` and its floor: None, or an integer radius in 1 .. 64 with a floor that is finite and > 0"""
+    if pose_smooth is None:
+        return None
+    if isinstance(pose_smooth, bool) or not isinstance(pose_smooth, int) or not 1 <= pose_smooth <= 64:
+        raise ValueError(f"{name} must be None or a smoothing radius in 1 .. 64 (frames), got {pose_smooth!r}")
+    if isinstance(floor, bool) or not isinstance(floor, (int, float)) or not 0 < floor < float("inf"):      # (a NaN fails both)
+        raise ValueError(f"{name}_floor must be a finite number > 0 (metres; the default 1e-3 is a regulariser, not a tuned value), got {floor!r}")
+    return pose_smooth
 
 
 def _focal_mode(focal):
@@ -546,6 +592,34 @@ def fit_trajectory(poses, seq_2d, cam=None, conf=None, smooth=None, device="cuda
     cam = _cam9(cam, dev) if focal is not None else torch.as_tensor(cam, dtype=torch.float32).reshape(-1).to(dev)
     out = _fit_trajectory(poses.to(dev), seq_2d.to(dev), cam, None if conf is None else conf.to(dev), smooth, focal)
     return {k: v.cpu() for k, v in out.items()}
+
+
+@torch.no_grad()
+def smooth_poses(poses, cov=None, radius=13, floor=1e-3, device="cuda"):
+    """Per-frame poses smoothed along the frames on the device, the counterpart of :func:`fit_trajectory` for the joints:
+    ``poses`` [T,N,J,3] - an ``infer_sequence(stride=...)["pose"]``, the result of :func:`stitch_poses` or any such array -
+    ``cov`` [T,N,J,6] the covariance of the hypotheses per (t, frame, joint) (``infer_sequence(spread="cov")["cov"]``: xx xy xz
+    yy yz zz; None: every frame weighs the same in every direction, which is :func:`fit_trajectory`'s filter per joint),
+    ``radius`` 1 .. 64 frames, ``floor`` in metres (finite and > 0; the 1 mm default is a regulariser that keeps a zero
+    covariance solvable, not a tuned value).  ops.smooth_poses; pafuse_amd.posesmooth states the arithmetic.  Returns a dict of
+    CPU tensors: ``"pose"`` [T,N,J,3] the smoothed pose, ``"pose_raw"`` the input and ``"pose_smooth_code"`` [T,N,J] uint8
+    (1 line, 2 weighted mean, 3 none: NaN) - the keys ``infer_sequence(pose_smooth=...)`` adds.  A fixed-radius linear
+    smoother without a motion model or a bone-length constraint; what it buys on real weights has not been measured."""
+    from . import ops
+    radius = _pose_smooth_radius(radius, floor, "radius")
+    if radius is None:
+        raise ValueError("radius must be a smoothing radius in 1 .. 64 (frames), got None")
+    poses = torch.as_tensor(poses, dtype=torch.float32)
+    if poses.dim() != 4 or poses.shape[-1] != 3 or 0 in poses.shape:
+        raise ValueError(f"poses must be [T,N,J,3], got {tuple(poses.shape)}")
+    if cov is not None:
+        cov = torch.as_tensor(cov, dtype=torch.float32)
+        if tuple(cov.shape) != (*poses.shape[:3], 6):
+            raise ValueError(f"cov must be [T,N,J,6] = {(*poses.shape[:3], 6)}, got {tuple(cov.shape)}")
+    dev = poses.device if poses.is_cuda else torch.device(device)
+    raw = poses.to(dev).contiguous()
+    pose, code = ops.smooth_poses(raw, None if cov is None else cov.to(dev).contiguous(), radius, floor=float(floor), want_code=True)
+    return {"pose": pose.cpu(), "pose_raw": raw.cpu(), "pose_smooth_code": code.cpu()}
 
 
 @torch.no_grad()
@@ -802,7 +876,7 @@ holds the p2_* keys, each step ends with the four Protocol #2 lines (:511-519): 
 @torch.no_grad()
 def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
                     conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False, focal=None, repair=None,
-                    drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip"):
+                    drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None, pose_smooth_floor=1e-3):
     """One video scored at the level of frames: the frames path of :func:`infer_sequence` - ONE pose per video frame, pooled
     over the windows that cover it - against the ground truth, on the device before anything crosses to the host
     (evaluate.frame_metrics; pafuse_amd.framemetrics states the arithmetic).
@@ -836,8 +910,15 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     The ``mpjpe`` and ``accel`` columns show what a weight buys.  ``path_scope="video"`` scores the path along the whole video
     instead, infer_sequence(path_weight=..., path_scope="video"): any ``stride``, the candidates of a frame being the
     hypotheses of all windows that cover it, so nothing is left to the fold's rule; the hypotheses of all windows stay on
-    the device until the end of the video, and at most 256 candidates per frame are taken."""
+    the device until the end of the video, and at most 256 candidates per frame are taken.
+
+    ``pose_smooth`` (a radius 1 .. 64; None: everything above, unchanged) scores the pose SMOOTHED along the frames with the
+    covariance of the hypotheses as matrix weight, infer_sequence(pose_smooth=..., pose_smooth_floor=...): the ``mpjpe`` and
+    ``accel`` columns show what a radius buys, and the trajectory is fitted on the smoothed pose."""
     _focal_mode(focal)
+    pose_smooth = _pose_smooth_radius(pose_smooth, pose_smooth_floor)
+    if pose_smooth is not None:
+        pose_smooth = (pose_smooth, float(pose_smooth_floor))
     repair = _repair_radius(repair, repair_threshold)
     if drop is not None:
         if (not isinstance(drop, (tuple, list)) or len(drop) != 3 or not 0.0 <= float(drop[0]) <= 1.0
@@ -890,7 +971,7 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     gt_wb = (seq_3d - seq_3d[:, :1]).to(dev)                        # joint 0 at 0, exactly
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam,
                                gt_root if aggregate == "reproj" else None, hypothesis_chunk, None, conf, stride, dev,
-                               trajectory is not None, smooth, focal, path_weight, path_scope)
+                               trajectory is not None, smooth, focal, path_weight, path_scope, pose_smooth)
     estimate = {k: out[k].cpu() for k in ("focal", "focal_r2", "focal_frames", "cam")} if focal is not None else None
     m = frame_metrics(out["pose"], gt_wb, dataset, traj=out.get("traj"), gt_root=gt_root.to(dev) if "traj" in out else None,
                       p2=p2, per_frame=per_frame)

@@ -1540,6 +1540,62 @@ def smooth_trajectory(traj, weight, radius, out=None):
     return out
 
 
+# ------------------------------------------------------------------ the per-frame pose smoothed along the frames
+def _need_floor(who, floor):
+    import struct
+    ok = not isinstance(floor, bool) and isinstance(floor, (int, float))
+    if ok:
+        try:
+            f32 = struct.unpack("f", struct.pack("f", float(floor)))[0]       # what the entry will see
+        except OverflowError:
+            f32 = float("inf")
+        ok = 0.0 < f32 < float("inf")
+    _need(ok, f"{who}: floor must be a number that is finite and > 0 in fp32 (metres), got {floor!r}")
+
+
+def smooth_poses_workspace_bytes(T, N, J):
+    """pafuse_pose_smooth_workspace_bytes: 48 bytes per (t, frame, joint) - the precision of every row, formed once"""
+    return int(_lib.load().pafuse_pose_smooth_workspace_bytes(int(T), int(N), int(J)))
+
+
+def smooth_poses(pose, cov, radius, floor=1e-3, out=None, want_code=False, workspace=None):
+    """pafuse_pose_smooth: pose [T,N,J,3] the finished per-frame pose (NaN: none), cov [T,N,J,6] the covariance of its
+    hypotheses (finish_frames' "cov": xx xy xz yy yz zz) or None (zeros: every frame weighs the same in every direction),
+    radius 1 .. 64, floor in metres -> [T,N,J,3]: per joint the local-linear filter along the frames in which frame m enters
+    with the matrix weight (cov + floor^2 I)^-1 (pafuse_amd.posesmooth states it).  A row with a NaN pose, a NaN or an
+    indefinite covariance takes no part and is filled from its neighbours; a (t, frame, joint) with nothing within `radius` is
+    NaN.  The floor is a regulariser - it keeps a zero covariance (P = 1, identical hypotheses) solvable - not a tuned value.
+    `out`: a [T,N,J,3] tensor to write into that shares no memory with pose.  want_code=True: -> (out, code [T,N,J] uint8:
+    1 line, 2 weighted mean, 3 none).  `workspace`: a flat float64 tensor of smooth_poses_workspace_bytes(T, N, J) bytes or more
+    to reuse (None: allocated here)."""
+    lib = _lib.load()
+    _need(isinstance(pose, torch.Tensor) and pose.dim() == 4 and pose.shape[-1] == 3, "smooth_poses: pose must be [T,N,J,3]")
+    T, N, J = (int(v) for v in pose.shape[:3])
+    _need(T > 0 and N > 0 and J > 0, "smooth_poses: T, N, J > 0")
+    _need_radius("smooth_poses", radius)
+    _need_floor("smooth_poses", floor)
+    _need(cov is None or (isinstance(cov, torch.Tensor) and tuple(cov.shape) == (T, N, J, 6)), "smooth_poses: cov must be [T,N,J,6]")
+    if out is None:
+        out = torch.empty_like(pose)
+    _need(isinstance(out, torch.Tensor) and tuple(out.shape) == (T, N, J, 3), "smooth_poses: out must be [T,N,J,3]")
+    lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
+    _need(hi <= pose.data_ptr() or lo >= pose.data_ptr() + pose.numel() * 4,
+          "smooth_poses: out may not alias pose (every frame is read by its neighbours)")
+    _need_tensors("smooth_poses", [pose, out] + ([] if cov is None else [cov]), ())
+    need = smooth_poses_workspace_bytes(T, N, J)
+    if workspace is None:
+        workspace = torch.empty(need // 8, device=pose.device, dtype=torch.float64)
+    _need(isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == pose.device and workspace.dtype == torch.float64
+          and workspace.dim() == 1 and workspace.is_contiguous() and workspace.numel() * 8 >= need,
+          f"smooth_poses: workspace must be a flat float64 tensor of {need} bytes or more on {pose.device}")
+    code = torch.empty((T, N, J), device=pose.device, dtype=torch.uint8) if want_code else None
+    with torch.cuda.device(pose.device):
+        _lib.check(lib.pafuse_pose_smooth(pose.data_ptr(), None if cov is None else cov.data_ptr(), T, N, J, int(radius), float(floor),
+                                          out.data_ptr(), None if code is None else code.data_ptr(), workspace.data_ptr(),
+                                          workspace.numel() * 8, _stream(pose)))
+    return (out, code) if want_code else out
+
+
 # ------------------------------------------------------------------ missing 2-D detections, repaired before lifting
 REPAIR_OUTPUTS = {"x2d": ((2,), torch.float32), "conf": ((), torch.float32), "status": ((), torch.uint8)}
 _ANCHOR_CACHE_MAX = 16

@@ -21,6 +21,7 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::finish_frames(frame, N, T, J, spread?)          one pose per video frame: mean, pick, idx, window (+ std, cov)
   pafuse::fit_trajectory(pose, x2d, cam, conf?)           the camera-space root of that pose: traj, wsum, resid per (t, frame)
   pafuse::smooth_trajectory(traj, weight?, radius)        a confidence-weighted local-linear filter along the frames
+  pafuse::pose_smooth(pose, cov?, radius, floor)          that pose smoothed along the frames, weighted by the hypothesis covariance
   pafuse::repair_detections(x2d, conf, anchor?, radius, threshold)   missing 2-D detections filled along the frames, per joint
   pafuse::focal_sums(pose, x2d, cam, conf?)               the focal-length sums of that pose: (K, H, G, 1) per (t, frame)
   pafuse::focal_solve(state, cam)                         the focal length from them: focal, r2, frames, cam per t
@@ -508,6 +509,20 @@ def smooth_trajectory(traj: torch.Tensor, weight: Optional[torch.Tensor], radius
 @smooth_trajectory.register_fake
 def _(traj, weight, radius):
     return torch.empty_like(traj)
+
+
+# ------------------------------------------------------------------ the per-frame pose smoothed along the frames
+@torch.library.custom_op("pafuse::pose_smooth", mutates_args=(), device_types="cuda")
+def pose_smooth(pose: torch.Tensor, cov: Optional[torch.Tensor], radius: int, floor: float = 1e-3) -> List[torch.Tensor]:
+    """pafuse_amd.ops.smooth_poses: pose [T,N,J,3], cov [T,N,J,6] or None, radius 1 .. 64, floor > 0 (metres) -> [the smoothed
+    pose [T,N,J,3], code [T,N,J] uint8 (1 line, 2 weighted mean, 3 none)]."""
+    from . import ops
+    return list(ops.smooth_poses(pose, cov, radius, floor=floor, want_code=True))
+
+
+@pose_smooth.register_fake
+def _(pose, cov, radius, floor=1e-3):
+    return [torch.empty_like(pose), pose.new_empty(pose.shape[:3], dtype=torch.uint8)]
 
 
 # ------------------------------------------------------------------ missing 2-D detections, repaired before lifting
