@@ -25,6 +25,12 @@ joint one path through the hypotheses instead of every frame's own winner (harne
 SMOOTHED along the frames with the covariance of the hypotheses as matrix weight (harness.evaluate_frames(pose_smooth=...)):
 compare the mpjpe and accel columns with a run without it.  What it buys on a real checkpoint has not been measured: this is the
 tool that measures it.  The 1 mm floor is a regulariser (a zero covariance stays solvable), not a tuned value.
+`--bone-lengths [video|symmetric]` (with `--frames`; default video; `--bone-iterations K`, default 16, 0 .. 64) scores the pose with its
+BONE LENGTHS HELD CONSTANT along each video (harness.evaluate_frames(bone_lengths=...)): one length per bone from the whole video,
+every frame projected onto them under the covariance of its hypotheses, behind `--smooth-pose` and before the trajectory fit.  The
+mpjpe and accel columns score it; per video the mean bone-length standard deviation before and after and the largest difference of
+the held lengths from the ground truth's are logged.  What it buys on a real checkpoint has not been measured: this is the tool.
+16 sweeps and the 1 mm floor are defaults, not tuned values.
 Without `--data` the synthetic H3WB files of tests/golden/h3wb_synth are used (random weights: numbers are meaningless).
 """
 import argparse
@@ -87,8 +93,16 @@ def main():
     ap.add_argument("--smooth-pose-floor", type=float, default=1e-3, metavar="S",
                     help="with --smooth-pose: the standard deviation in metres added to every covariance (finite, > 0; default 0.001, "
                          "a regulariser, not a tuned value)")
+    ap.add_argument("--bone-lengths", choices=("video", "symmetric"), default=None, nargs="?", const="video",
+                    help="with --frames: score the pose with its bone lengths held constant along each video - one length per bone "
+                         "from the whole video (symmetric: left and right pooled), every frame projected onto them under the covariance "
+                         "of its hypotheses; compare the mpjpe and accel columns")
+    ap.add_argument("--bone-iterations", type=int, default=16, metavar="K",
+                    help="with --bone-lengths: Jacobi sweeps of the projection before the exact snap (0 .. 64; default 16, not a tuned value)")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.bone_lengths is not None and not (a.frames and 0 <= a.bone_iterations <= 64):
+        ap.error("--bone-lengths takes --bone-iterations in 0 .. 64 and needs --frames")
     if a.smooth_pose is not None and not (a.frames and 1 <= a.smooth_pose <= 64):
         ap.error("--smooth-pose takes a radius in 1 .. 64 and needs --frames")
     if not 0.0 < a.smooth_pose_floor < float("inf"):
@@ -147,7 +161,8 @@ def main():
                              trajectory=None if a.trajectory is None else (a.trajectory or True), log=log,
                              hypothesis_chunk=a.hypothesis_chunk, p2=bool(args.ft2d.p2), seam_profile=a.seam_profile,
                              focal="estimate" if a.estimate_focal else None, repair=a.repair, drop=drop, path_weight=a.path_weight,
-                             path_scope=a.path_scope, pose_smooth=a.smooth_pose, pose_smooth_floor=a.smooth_pose_floor)
+                             path_scope=a.path_scope, pose_smooth=a.smooth_pose, pose_smooth_floor=a.smooth_pose_floor,
+                             bone_lengths=a.bone_lengths, bone_iterations=a.bone_iterations)
     else:
         h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
                       batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),

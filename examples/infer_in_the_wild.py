@@ -67,6 +67,17 @@ test_3d_output_raw.npy (_pick_raw.npy) what they held, test_3d_output_smooth_cod
 2 weighted mean, 3 nothing in reach.  The floor is a regulariser (a zero covariance stays solvable), not a tuned value.  A fixed-radius
 linear smoother: no motion model, no bone lengths; what it buys on real weights has not been measured (evaluate_h3wb.py --frames
 --smooth-pose measures it).
+
+--bone-lengths [video|symmetric] (default video; --bone-iterations K, default 16; where --smooth-pose is allowed) holds the BONE
+LENGTHS CONSTANT along the video on the device: one length per bone from the whole video - every frame weighing as far as its
+hypotheses agree along the bone; "symmetric" pools left and right - and every frame moved onto those lengths by K Jacobi sweeps of
+the covariance-weighted projection and an exact top-down snap (harness.constrain_bones, infer_sequence(bone_lengths=...)).  It runs
+behind --smooth-pose and before the trajectory fit.  The files above then hold the constrained pose and test_3d_output_free.npy
+(_pick_free.npy) what they held; test_3d_output_bone_length.npy, _bone_dev.npy [T,134] (metres; NaN: no bone - the root and the
+face points), _bone_frames.npy, _bone_code.npy [T,frames,134] (1 moved with a bone, 0 untouched, 3 a bone was asked but the joint
+had no finite pose or usable covariance) and _bone_resid.npy [T,frames,2] (the largest |length - L| of the frame before and after,
+metres) come with it.  16 sweeps and the 1 mm floor are defaults, not tuned values; the estimated lengths are biased long where the
+noise is comparable to the bone; what it buys on real weights has not been measured (evaluate_h3wb.py --frames --bone-lengths).
 """
 import argparse
 import json
@@ -144,8 +155,18 @@ def main():
     ap.add_argument("--smooth-pose-floor", type=float, default=1e-3, metavar="S",
                     help="with --smooth-pose: the standard deviation in metres added to every covariance (finite, > 0; default 0.001, "
                          "a regulariser, not a tuned value)")
+    ap.add_argument("--bone-lengths", choices=("video", "symmetric"), default=None, nargs="?", const="video",
+                    help="hold the bone lengths constant along the video on the device: one length per bone from the whole video "
+                         "(symmetric: left and right pooled), every frame projected onto them under the covariance of its hypotheses; "
+                         "the unconstrained pose goes to test_3d_output_free.npy")
+    ap.add_argument("--bone-iterations", type=int, default=16, metavar="K",
+                    help="with --bone-lengths: Jacobi sweeps of the projection before the exact snap (0 .. 64; default 16, not a tuned value)")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.bone_lengths is not None and (not 0 <= a.bone_iterations <= 64 or not (
+            a.aggregate == "mean" or (a.reproj_fit is not None and (a.stride is not None or a.path_scope == "video")))):
+        ap.error("--bone-lengths takes --bone-iterations in 0 .. 64 and needs --aggregate mean, or --reproj-fit with --stride or "
+                 "--path-scope video (one pose per video frame)")
     if a.smooth_pose is not None and (not 1 <= a.smooth_pose <= 64 or not (
             a.aggregate == "mean" or (a.reproj_fit is not None and (a.stride is not None or a.path_scope == "video")))):
         ap.error("--smooth-pose takes a radius in 1 .. 64 frames and needs --aggregate mean, or --reproj-fit with --stride or "
@@ -153,6 +174,10 @@ def main():
     if not 0.0 < a.smooth_pose_floor < float("inf"):
         ap.error("--smooth-pose-floor takes a finite length > 0 in metres")
     smoothing = {} if a.smooth_pose is None else dict(pose_smooth=a.smooth_pose, pose_smooth_floor=a.smooth_pose_floor)
+    if a.bone_lengths is not None:       # behind the smoother, before the trajectory
+        smoothing.update(bone_lengths=a.bone_lengths, bone_iterations=a.bone_iterations)
+    BONE_FILES = (("bone_length", "bone_length"), ("bone_dev", "bone_dev"), ("bone_frames", "bone_frames"), ("bone_code", "bone_code"),
+                  ("bone_resid", "bone_resid"))
     if a.path_scope == "video" and a.path_weight is None:
         ap.error("--path-scope video needs --path-weight")
     if a.path_weight is not None and (a.reproj_fit is None or (a.stride is not None and a.path_scope == "clip") or a.hypothesis_chunk is not None
@@ -220,7 +245,8 @@ def main():
                                       **(smoothing if per_frame else {}))
         if per_frame:                    # per-frame arrays already
             for k, name in (("pose", "pick"), ("idx", "pick_idx"), ("window", "pick_window"), ("std", "pick_std"), ("cov", "pick_cov"),
-                            ("path_cost", "pick_path_cost"), ("pose_raw", "pick_raw"), ("pose_smooth_code", "pick_smooth_code")):
+                            ("path_cost", "pick_path_cost"), ("pose_raw", "pick_raw"), ("pose_smooth_code", "pick_smooth_code"),
+                            ("pose_free", "pick_free")) + tuple((k, "pick_" + n) for k, n in BONE_FILES):
                 if k in pick:
                     save(f"test_3d_output_{name}.npy", pick[k])
             save("test_3d_output_count.npy", pick["count"])
@@ -241,17 +267,18 @@ def main():
                                                       **camera)
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
                                       hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride, **wanted, **smoothing)
-        for k, name in (("std", "std"), ("cov", "cov"), ("count", "count"), ("pose_raw", "raw"), ("pose_smooth_code", "smooth_code")):
+        for k, name in (("std", "std"), ("cov", "cov"), ("count", "count"), ("pose_raw", "raw"), ("pose_smooth_code", "smooth_code"),
+                        ("pose_free", "free")) + BONE_FILES:
             if k in pred:
                 save(f"test_3d_output_{name}.npy", pred[k])
         poses = pred["pose"]                                                        # [T,frames,134,3]
         traj = pred if a.trajectory is not None else None
     elif a.aggregate == "mean":
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
-                                      hypothesis_chunk=a.hypothesis_chunk, spread="cov" if a.smooth_pose is not None else a.spread)
+                                      hypothesis_chunk=a.hypothesis_chunk, spread="cov" if smoothing else a.spread)
         cov = None
         if isinstance(pred, dict):
-            if a.smooth_pose is not None:    # consecutive clips: the filter runs on the stitched per-frame arrays
+            if smoothing:                    # consecutive clips: the filters run on the stitched per-frame arrays
                 cov = harness.stitch_spread(pred["cov"], keypoints.shape[0], model.frames)
             for k in ("std", "cov")[:0 if a.spread is None else 1 if a.spread == "std" else 2]:
                 np.save(os.path.join(a.out, f"test_3d_output_{k}.npy"),
@@ -263,6 +290,12 @@ def main():
             save("test_3d_output_raw.npy", smoothed["pose_raw"])
             save("test_3d_output_smooth_code.npy", smoothed["pose_smooth_code"])
             poses = smoothed["pose"]
+        if a.bone_lengths is not None:       # behind the smoother, before the trajectory
+            held = harness.constrain_bones(poses, cov, tables=h3wb.bone_tables(dataset, True, kps_left, kps_right), lengths=a.bone_lengths,
+                                           iterations=a.bone_iterations)
+            for k, name in (("pose_free", "free"),) + BONE_FILES:
+                save(f"test_3d_output_{name}.npy", held[k])
+            poses = held["pose"]
         if a.trajectory is not None:     # consecutive clips: the fit runs on the stitched per-frame array
             traj = harness.fit_trajectory(poses, keypoints, conf=conf, smooth=a.smooth_trajectory, **camera)
     else:

@@ -916,6 +916,59 @@ int pafuse_pose_smooth(const float *pose /* [T,N,J,3] */, const float *cov /* [T
                        float *out /* [T,N,J,3], may not alias pose */, uint8_t *code /* [T,N,J] or NULL */,
                        void *workspace, size_t workspace_bytes, void *stream);
 
+/* Bone lengths held constant along a video (pafuse_amd/bones.py states the arithmetic of both entries, operation for
+ * operation).  All in fp64 with contraction off, rounded once to fp32.
+ *   pose   [T,N,J,3] the per-frame pose, N the frames of the video (NaN: none)
+ *   cov    [T,N,J,6] the covariance of its hypotheses (pafuse_frames_finish's cov: xx xy xz yy yz zz), or NULL: all zeros, bit
+ *          for bit.  A joint's EFFECTIVE covariance is cov + floor^2*I; it is USABLE under the three leading-minor tests of
+ *          pafuse_pose_smooth (a NaN anywhere, or an indefinite matrix, is not)
+ *   parent int32 [J]: the joint that joint j's bone hangs on; an entry outside 0 .. j-1 is READ AS -1, no bone - a parent index
+ *          is smaller than its child's, so no table can make a walk run on (the Python layers refuse such a table)
+ *   floor  metres, finite and > 0: a regulariser that keeps a zero covariance usable, not a tuned value
+ *
+ * pafuse_bone_lengths - one length per bone and step from the whole video.  Bone j (parent p), frame n: d = x_j - x_p, l = |d|,
+ * u = d/l, v = u'E_j u + u'E_p u.  The frame takes part iff the six pose values are finite, l is finite and > 0, both
+ * covariances are usable and v is finite and > 0; its weight is w = 1/v: a frame is trusted as far as its hypotheses agree
+ * ALONG the bone.  S0 = sum w, S1 = sum w*l, S2 = sum (w*l)*l in the order of the per-frame wave kernels (lane i adds frames
+ * i, i + 64, ... ascending, then the butterfly), L = S1/S0, dev = sqrt(max(S2/S0 - L*L, 0)).
+ *   mirror int32 [J] or NULL: the left/right partner of joint j or -1.  Bone j and bone m = mirror[j] (in range, != j, itself a
+ *          bone) POOL their frames - every lane runs on from the lower-indexed bone's frames into the higher's - so partners
+ *          that name each other get the same bits
+ *   length [T,J]: L, NaN where j has no bone or no frame takes part;   dev [T,J] or NULL: the weighted standard deviation of the
+ *          INPUT's bone length, the known diagnostic;   frames int32 [T,J] or NULL: the frames that took part (both bones')
+ * One kernel, one wave per (t, j); no atomics, bit-reproducible.
+ *
+ * pafuse_bone_project - every frame (t, n), on its own, moved onto the lengths length[t, :] by the least Mahalanobis distance.
+ * A joint without a bone (a chain top, such as the root) is PINNED: its E counts as 0 and it never moves.  Bone j is ACTIVE in
+ * a frame iff it has a parent, length[t,j] is finite and > 0, both ends are finite and both covariances usable.
+ * `iterations` Jacobi sweeps from y = pose.  Phase A, per active bone: d = y_j - y_p, l, u; g_c = E_j u, g_p = E_p u,
+ * s = u'g_c + u'g_p (the bone skips the sweep unless l and s are finite and > 0); lam = (l - L)/s, a_j = g_c*lam, b_j = g_p*lam -
+ * the exact minimiser of dc'E_c^-1 dc + dp'E_p^-1 dp under the linearised constraint.  Phase B, per joint that is not pinned:
+ * n_j = [own bone active] + its active child bones (fixed per frame); y_j += (-a_j + sum of b_k over the children k
+ * ascending)/n_j - the averaging keeps Jacobi stable at a wrist with six bones.  snap = 1: afterwards every joint whose bone is
+ * active walks up while the bone is active and adds, leaf to root, (y_c - y_p)*(L_c/l_c) (the unscaled difference where l_c is
+ * not finite or not > 0) to the y of the joint the walk ends at: the lengths become exact up to the fp32 rounding.
+ *   length [T,J] fp32: an INPUT - pafuse_bone_lengths' or the caller's own (a calibration, another video), symmetric or not
+ *   out    [T,N,J,3], may not alias pose.  A joint with n_j = 0 keeps the input's bits; no NaN is created; iterations = 0 with
+ *          snap = 0 returns the input, bit for bit
+ *   code   uint8 [T,N,J] or NULL: 1 the joint is part of an active bone; 0 untouched; 3 untouched although a bone was asked of
+ *          it (its own bone or a child's has a length) - a pose that is not finite or an unusable covariance made it impossible
+ *   resid  [T,N,2] or NULL: (before, after) the largest |l - L| over the frame's active bones in metres, before on pose, after
+ *          ON THE FP32 VALUES RETURNED; NaN: no active bone.  Jacobi converges slowly: `after` without snap shows an unconverged
+ *          frame, `before` stays visible behind the snap
+ * One kernel, one wave per (t, n), the frame in LDS; no atomics, no workspace, bit-reproducible.
+ * Both refuse (PAFUSE_E_ARG) before any HIP call: a null pose, parent, length (or out), T, N or J < 1, J > 256, iterations
+ * outside 0 .. 64, snap not 0 or 1, a floor that is not finite and > 0, out == pose, a grid out of range. */
+int pafuse_bone_lengths(const float *pose /* [T,N,J,3] */, const float *cov /* [T,N,J,6] or NULL */,
+                        const int32_t *parent /* [J] */, const int32_t *mirror /* [J] or NULL */,
+                        int32_t T, int32_t N, int32_t J, float floor,
+                        float *length /* [T,J] */, float *dev /* [T,J] or NULL */, int32_t *frames /* [T,J] or NULL */, void *stream);
+int pafuse_bone_project(const float *pose, const float *cov /* or NULL */, const int32_t *parent,
+                        const float *length /* [T,J] */, int32_t T, int32_t N, int32_t J,
+                        int32_t iterations /* 0..64 */, int32_t snap /* 0|1 */, float floor,
+                        float *out /* [T,N,J,3], may not alias pose */, uint8_t *code /* or NULL */,
+                        float *resid /* [T,N,2] or NULL */, void *stream);
+
 /* The focal length of the video's camera from the finished per-frame pose and its detections, part one: the sums per
  * (t, frame) (pafuse_amd/focal.py states the arithmetic).  Operands as pafuse_frames_root_fit, except
  * that of cam only cx, cy = cam[2:4] and the pixel aspect rho = cam[1]/cam[0] are read: cam and cam with fx, fy doubled give

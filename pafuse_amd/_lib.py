@@ -188,6 +188,8 @@ SIGNATURES = {
     "pafuse_detections_repair": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_float] + [C.c_void_p] * 4),
     "pafuse_pose_smooth_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "pafuse_pose_smooth": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 4 + [C.c_float] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "pafuse_bone_lengths": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float] + [C.c_void_p] * 4),
+    "pafuse_bone_project": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_float] + [C.c_void_p] * 4),
     "pafuse_frames_focal_sums": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p] * 2),
     "pafuse_focal_solve": (C.c_int, [C.c_void_p] + [C.c_int32] * 2 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
     "pafuse_frame_errors": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p] * 3),

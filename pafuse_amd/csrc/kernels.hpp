@@ -4339,23 +4339,31 @@ struct PoseSmoothParams {
     double* precision;   // [T,N,J,6] workspace: W per row, NaN in W[0] where the row takes no part
 };
 
+// The effective covariance E = Sigma + floor^2*I of six packed entries c (xx xy xz yy yz zz; null: zeros), its cofactors C and
+// determinant, and whether it is USABLE: det finite and the three leading minors > 0 (a NaN anywhere fails them).  The one
+// statement of that test: the pose smoother and the bone kernels below share it.
+__device__ __forceinline__ bool cov_usable(const float* c, double s2, double (&E)[6], double (&C)[6], double& det) {
+#pragma clang fp contract(off)
+    double xx = s2, xy = 0.0, xz = 0.0, yy = s2, yz = 0.0, zz = s2;
+    if (c) xx = (double)c[0] + s2, xy = (double)c[1], xz = (double)c[2], yy = (double)c[3] + s2, yz = (double)c[4], zz = (double)c[5] + s2;
+    E[0] = xx, E[1] = xy, E[2] = xz, E[3] = yy, E[4] = yz, E[5] = zz;
+    C[0] = yy * zz - yz * yz;
+    C[1] = xz * yz - xy * zz;
+    C[2] = xy * yz - xz * yy;
+    C[3] = xx * zz - xz * xz;
+    C[4] = xy * xz - xx * yz;
+    C[5] = xx * yy - xy * xy;
+    det = (xx * C[0] + xy * C[1]) + xz * C[2];
+    return isfinite(det) && xx > 0.0 && C[5] > 0.0 && det > 0.0;
+}
+
 // the precision W = (Sigma + floor^2 I)^-1 of row em and whether the row takes part
 __device__ __forceinline__ bool pose_row_precision(const PoseSmoothParams& p, int64_t em, double s2, double (&W)[6]) {
 #pragma clang fp contract(off)
     const float y0 = p.pose[em * 3 + 0], y1 = p.pose[em * 3 + 1], y2 = p.pose[em * 3 + 2];
-    double xx = s2, xy = 0.0, xz = 0.0, yy = s2, yz = 0.0, zz = s2;
-    if (p.cov) {
-        const float* c = p.cov + em * 6;
-        xx = (double)c[0] + s2, xy = (double)c[1], xz = (double)c[2], yy = (double)c[3] + s2, yz = (double)c[4], zz = (double)c[5] + s2;
-    }
-    W[0] = yy * zz - yz * yz;
-    W[1] = xz * yz - xy * zz;
-    W[2] = xy * yz - xz * yy;
-    W[3] = xx * zz - xz * xz;
-    W[4] = xy * xz - xx * yz;
-    W[5] = xx * yy - xy * xy;
-    const double det = (xx * W[0] + xy * W[1]) + xz * W[2];
-    const bool part = isfinite(y0) && isfinite(y1) && isfinite(y2) && isfinite(det) && xx > 0.0 && W[5] > 0.0 && det > 0.0;
+    double E[6], det;
+    const bool usable = cov_usable(p.cov ? p.cov + em * 6 : nullptr, s2, E, W, det);
+    const bool part = isfinite(y0) && isfinite(y1) && isfinite(y2) && usable;
 #pragma unroll
     for (int k = 0; k < 6; ++k) W[k] = W[k] / det;
     return part;
@@ -4437,6 +4445,372 @@ __global__ void __launch_bounds__(256) pose_smooth_kernel(const PoseSmoothParams
 #pragma unroll
     for (int k = 0; k < 3; ++k) p.out[e * 3 + k] = o[k];
     if (p.code) p.code[e] = (uint8_t)kind;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// Bone lengths held constant along a video (statement: pafuse_amd/bones.py, which fixes every operation
+// and its order - this code follows it operation for operation).  fp64, contraction off, sqrt and divide correctly rounded.
+//
+// Tables: parent[j] outside 0 .. j-1 is read as -1, no bone (bone_parent) - a parent index is smaller than its child's, so no
+// walk below can run on or leave the table, whatever the caller's array holds.
+//
+// bone_lengths_kernel: one wave per (t, bone j), four per workgroup (wave_item); lane l walks frames l, l + 64, ... ascending.
+// Per frame d = x_j - x_p, l = |d|, u = d/l, v = u'E_j u + u'E_p u with the effective covariances (cov_usable); the frame
+// takes part iff the six pose values are finite, l is finite and > 0, both covariances are usable and v is finite and > 0;
+// w = 1/v; S0 += w, S1 += w*l, S2 += (w*l)*l and a count, then wave_sums.  With a mirror table bone j and bone m = mirror[j]
+// (in range, != j, itself a bone) pool their frames: every lane runs on from the lower-indexed bone's frames into the
+// higher's before the butterfly, so partners that name each other write the same bits.  L = S1/S0, dev = sqrt(max(S2/S0 - L*L,
+// 0)); no bone or no frame: NaN, NaN, 0.  No LDS, no atomics, no scratch.
+// ----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int bone_parent(const int32_t* parent, int j) {
+    const int p = parent[j];
+    return p >= 0 && p < j ? p : -1;
+}
+
+// g = E*u for the packed symmetric E, and u.g
+__device__ __forceinline__ void sym3_mul(const double (&E)[6], const double (&u)[3], double (&g)[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) g[k] = (E[sym3(k, 0)] * u[0] + E[sym3(k, 1)] * u[1]) + E[sym3(k, 2)] * u[2];
+}
+__device__ __forceinline__ double dot3(const double (&u)[3], const double (&g)[3]) {
+#pragma clang fp contract(off)
+    return (u[0] * g[0] + u[1] * g[1]) + u[2] * g[2];
+}
+
+struct BoneLengthsParams {
+    const float* pose;       // [T,N,J,3]
+    const float* cov;        // [T,N,J,6] or null: zeros
+    const int32_t* parent;   // [J]
+    const int32_t* mirror;   // [J] or null
+    float* length;           // [T,J]
+    float* dev;              // [T,J] or null
+    int32_t* frames;         // [T,J] or null
+    int T, N, J;
+    float floor;
+};
+
+// the frames of bone (j, pj) of step t that this lane owns, added to its running sums
+__device__ __forceinline__ void bone_frames_add(const BoneLengthsParams& p, int t, int j, int pj, double s2, double (&s)[3], int (&c)[1]) {
+#pragma clang fp contract(off)
+    for (int n = wave_lane(); n < p.N; n += 64) {
+        const int64_t row = ((int64_t)t * p.N + n) * p.J;
+        const float* xc = p.pose + (row + j) * 3;
+        const float* xp = p.pose + (row + pj) * 3;
+        const float c0 = xc[0], c1 = xc[1], c2 = xc[2], p0 = xp[0], p1 = xp[1], p2 = xp[2];
+        double Ec[6], Ep[6], C[6], det;
+        const bool uc = cov_usable(p.cov ? p.cov + (row + j) * 6 : nullptr, s2, Ec, C, det);
+        const bool up = cov_usable(p.cov ? p.cov + (row + pj) * 6 : nullptr, s2, Ep, C, det);
+        const double d[3] = {(double)c0 - (double)p0, (double)c1 - (double)p1, (double)c2 - (double)p2};
+        const double l = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        const double u[3] = {d[0] / l, d[1] / l, d[2] / l};
+        double gc[3], gp[3];
+        sym3_mul(Ec, u, gc);
+        sym3_mul(Ep, u, gp);
+        const double v = dot3(u, gc) + dot3(u, gp);
+        const bool part = isfinite(c0) && isfinite(c1) && isfinite(c2) && isfinite(p0) && isfinite(p1) && isfinite(p2) && isfinite(l) &&
+                          l > 0.0 && uc && up && isfinite(v) && v > 0.0;
+        if (!part) continue;
+        const double w = 1.0 / v, wl = w * l;
+        s[0] += w, s[1] += wl, s[2] += wl * l;
+        ++c[0];
+    }
+}
+
+__global__ void __launch_bounds__(256) bone_lengths_kernel(const BoneLengthsParams p) {
+#pragma clang fp contract(off)
+    const int lane = wave_lane();
+    const int64_t item = wave_item();
+    if (item >= (int64_t)p.T * p.J) return;   // wave-uniform
+    const int j = (int)(item % p.J), t = (int)(item / p.J);
+    const double s2 = (double)p.floor * (double)p.floor;
+    double s[3] = {0.0, 0.0, 0.0};
+    int c[1] = {0};
+    const int pj = bone_parent(p.parent, j);
+    if (pj >= 0) {
+        int m = p.mirror ? p.mirror[j] : -1;
+        if (m < 0 || m >= p.J || m == j || bone_parent(p.parent, m) < 0) m = -1;
+        const int lo = m >= 0 && m < j ? m : j;
+        bone_frames_add(p, t, lo, bone_parent(p.parent, lo), s2, s, c);
+        if (m >= 0) {
+            const int hi = m > j ? m : j;
+            bone_frames_add(p, t, hi, bone_parent(p.parent, hi), s2, s, c);
+        }
+    }
+    wave_sums(s, c);
+    if (lane != 0) return;
+    const float qnan = __builtin_nanf("");
+    const double L = s[1] / s[0], var = s[2] / s[0] - L * L;
+    p.length[item] = c[0] ? (float)L : qnan;
+    if (p.dev) p.dev[item] = c[0] ? (float)sqrt(var > 0.0 ? var : 0.0) : qnan;
+    if (p.frames) p.frames[item] = c[0];
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// bone_project_kernel<R>: every frame projected onto the bone lengths of its step, weighted by the hypothesis covariance
+// (statement: bones.project).  One wave per (t, n), four per workgroup (wave_item); lane l owns joints l, l + 64, ... (R slots,
+// J <= 64*R <= 256) and keeps in registers their y, their a-vector, their effective covariance and - re-read once from global
+// memory as fp32, 24 bytes - their parent's covariance, from which the parent's E = cov + floor^2*I is formed at every sweep
+// (one add per diagonal entry, the same bits as the owner's; zeros where the parent is pinned): no covariance in LDS.  In
+// the wave's own LDS region:
+//   s_y    [J][3] double   the current y of every joint (what a child reads of its parent; at the end the returned values)
+//   s_b    [J][3] double   phase A's b-vector of every bone (what a parent adds up); the snap's step vectors afterwards
+//   s_par, s_first, s_next [J] int16   the read table and its child lists as first child / next sibling, filled once by lane
+//                          0 walking k = J-1 down to 1, so every list ascends; any table works without a host copy of it
+//   s_flag [J] uint8       1: pose finite and covariance usable, 2: pinned (no bone), 4: bone active, 8: a length was asked
+// R = 4: 14 080 bytes per wave, 56 320 per workgroup (static, under 64 KB) - two workgroups per CU.  The phases of a sweep are separated by
+// wave_lds_sync: a wave's LDS operations complete in the order it issued them, so all that is needed is that the compiler
+// keeps them in order (fences at wavefront scope, no instruction) and the lanes converged.  No workgroup barrier, no atomics,
+// no scratch; nothing depends on the launch shape.
+// ----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// after the butterfly every lane holds the same bits (no NaN among the operands)
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+struct BoneProjectParams {
+    const float* pose;       // [T,N,J,3]
+    const float* cov;        // [T,N,J,6] or null: zeros
+    const int32_t* parent;   // [J]
+    const float* length;     // [T,J]
+    float* out;              // [T,N,J,3]
+    uint8_t* code;           // [T,N,J] or null
+    float* resid;            // [T,N,2] or null
+    int T, N, J, iterations, snap;
+    float floor;
+};
+
+enum BoneFlag { BONE_OK = 1, BONE_PINNED = 2, BONE_ACTIVE = 4, BONE_ASKED = 8 };
+enum BoneCode { BONE_KEPT = 0, BONE_DONE = 1, BONE_FAILED = 3 };
+
+template <int R>
+__global__ void __launch_bounds__(256) bone_project_kernel(const BoneProjectParams p) {
+#pragma clang fp contract(off)
+    constexpr int S = 64 * R;
+    __shared__ double s_y_all[4][S * 3];
+    __shared__ double s_b_all[4][S * 3];
+    __shared__ int16_t s_par_all[4][S], s_first_all[4][S], s_next_all[4][S];
+    __shared__ uint8_t s_flag_all[4][S];
+    const int lane = wave_lane(), wv = threadIdx.x >> 6;
+    const int64_t item = wave_item();   // (t, n)
+    if (item >= (int64_t)p.T * p.N) return;   // wave-uniform: there is no workgroup barrier below
+    const int J = p.J, t = (int)(item / p.N);
+    double* s_y = s_y_all[wv];
+    double* s_b = s_b_all[wv];
+    int16_t *s_par = s_par_all[wv], *s_first = s_first_all[wv], *s_next = s_next_all[wv];
+    uint8_t* s_flag = s_flag_all[wv];
+    const double s2 = (double)p.floor * (double)p.floor, inf = (double)INFINITY;
+    const int64_t row = item * J;
+
+    // ---- the frame into registers and LDS
+    double y[R][3], a[R][3], E[R][6], L[R];
+    float cp[R][6];   // the parent's covariance as given
+    int par[R], cnt[R];
+    bool own[R], active[R], asked[R];   // own: the slot holds a joint
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int j = r * 64 + lane;
+        own[r] = j < J, active[r] = asked[r] = false, par[r] = -1, cnt[r] = 0, L[r] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) y[r][k] = a[r][k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) E[r][k] = 0.0, cp[r][k] = 0.f;
+        if (!own[r]) continue;
+        const float* x = p.pose + (row + j) * 3;
+        const float x0 = x[0], x1 = x[1], x2 = x[2];
+        float c[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (p.cov) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) c[k] = p.cov[(row + j) * 6 + k];
+        }
+        double Ej[6], C[6], det;
+        const bool usable = cov_usable(c, s2, Ej, C, det);
+        par[r] = bone_parent(p.parent, j);
+        const float len = p.length[(int64_t)t * J + j];
+        asked[r] = par[r] >= 0 && isfinite(len) && len > 0.f;
+        L[r] = (double)len;
+        y[r][0] = (double)x0, y[r][1] = (double)x1, y[r][2] = (double)x2;
+        if (par[r] >= 0) {   // a pinned joint's E stays 0
+#pragma unroll
+            for (int k = 0; k < 6; ++k) E[r][k] = Ej[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s_y[j * 3 + k] = y[r][k], s_b[j * 3 + k] = 0.0;
+        if (asked[r] && p.cov) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) cp[r][k] = p.cov[(row + par[r]) * 6 + k];
+        }
+        s_par[j] = (int16_t)par[r], s_first[j] = -1, s_next[j] = -1;
+        s_flag[j] = (uint8_t)((isfinite(x0) && isfinite(x1) && isfinite(x2) && usable ? BONE_OK : 0) | (par[r] < 0 ? BONE_PINNED : 0) |
+                              (asked[r] ? BONE_ASKED : 0));
+    }
+    wave_lds_sync();
+    if (lane == 0) {   // the child lists: k descending, so every list ascends
+        for (int k = J - 1; k >= 1; --k) {
+            const int pk = s_par[k];
+            if (pk >= 0) s_next[k] = s_first[pk], s_first[pk] = (int16_t)k;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {   // (reads of BONE_OK only: the list walk above does not touch the flags)
+        const int j = r * 64 + lane;
+        active[r] = own[r] && asked[r] && (s_flag[j] & BONE_OK) && (s_flag[par[r]] & BONE_OK);
+    }
+    wave_lds_sync();
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (active[r]) s_flag[r * 64 + lane] |= BONE_ACTIVE;
+    wave_lds_sync();
+    bool wanted[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        wanted[r] = asked[r], cnt[r] = active[r] ? 1 : 0;
+        if (!own[r]) continue;
+        for (int k = s_first[r * 64 + lane]; k >= 0; k = s_next[k]) {
+            const int f = s_flag[k];
+            cnt[r] += (f & BONE_ACTIVE) ? 1 : 0, wanted[r] |= (f & BONE_ASKED) != 0;
+        }
+    }
+
+    // the largest |l - L| over the active bones at the values in s_y; NaN: no active bone
+    auto residual = [&]() -> double {
+        double m = -inf;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (!active[r]) continue;
+            const int j = r * 64 + lane, pj = par[r];
+            const double d0 = s_y[j * 3] - s_y[pj * 3], d1 = s_y[j * 3 + 1] - s_y[pj * 3 + 1], d2 = s_y[j * 3 + 2] - s_y[pj * 3 + 2];
+            const double l = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+            m = fmax(m, isfinite(l) ? fabs(l - L[r]) : inf);
+        }
+        m = wave_max_f64(m);
+        return m == -inf ? __builtin_nan("") : m;
+    };
+    const double before = p.resid ? residual() : 0.0;
+
+    bool pinp[R];   // the parent is pinned: its E is 0
+#pragma unroll
+    for (int r = 0; r < R; ++r) pinp[r] = active[r] && (s_flag[par[r]] & BONE_PINNED) != 0;
+
+    // ---- the Jacobi sweeps
+    for (int it = 0; it < p.iterations; ++it) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {   // phase A
+            if (!own[r]) continue;
+            const int j = r * 64 + lane;
+            double b[3] = {0.0, 0.0, 0.0};
+            a[r][0] = a[r][1] = a[r][2] = 0.0;
+            if (active[r]) {
+                const int pj = par[r];
+                const double d[3] = {y[r][0] - s_y[pj * 3], y[r][1] - s_y[pj * 3 + 1], y[r][2] - s_y[pj * 3 + 2]};
+                const double l = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+                if (isfinite(l) && l > 0.0) {
+                    const double u[3] = {d[0] / l, d[1] / l, d[2] / l};
+                    double Ep[6], gc[3], gp[3];
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) Ep[k] = pinp[r] ? 0.0 : (double)cp[r][k];
+                    if (!pinp[r]) Ep[0] = Ep[0] + s2, Ep[3] = Ep[3] + s2, Ep[5] = Ep[5] + s2;
+                    sym3_mul(E[r], u, gc);
+                    sym3_mul(Ep, u, gp);
+                    const double s = dot3(u, gc) + dot3(u, gp);
+                    if (isfinite(s) && s > 0.0) {
+                        const double lam = (l - L[r]) / s;
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) a[r][k] = gc[k] * lam, b[k] = gp[k] * lam;
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s_b[j * 3 + k] = b[k];
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int r = 0; r < R; ++r) {   // phase B
+            if (!own[r] || cnt[r] == 0 || par[r] < 0) continue;
+            const int j = r * 64 + lane;
+            double D[3] = {0.0, 0.0, 0.0};
+            if (active[r]) D[0] = 0.0 - a[r][0], D[1] = 0.0 - a[r][1], D[2] = 0.0 - a[r][2];
+            for (int k = s_first[j]; k >= 0; k = s_next[k]) {   // ascending; an inactive or skipped bone holds 0.0
+#pragma unroll
+                for (int q = 0; q < 3; ++q) D[q] = D[q] + s_b[k * 3 + q];
+            }
+            const double nj = (double)cnt[r];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                y[r][k] = y[r][k] + D[k] / nj;
+                s_y[j * 3 + k] = y[r][k];
+            }
+        }
+        wave_lds_sync();
+    }
+
+    // ---- the snap: every bone's step vector, then every joint walks up while its bone is active, leaf to root
+    double z[R][3];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) z[r][k] = y[r][k];
+    if (p.snap) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (!active[r]) continue;
+            const int j = r * 64 + lane, pj = par[r];
+            const double d[3] = {y[r][0] - s_y[pj * 3], y[r][1] - s_y[pj * 3 + 1], y[r][2] - s_y[pj * 3 + 2]};
+            const double l = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+            const bool fine = isfinite(l) && l > 0.0;
+            const double ratio = L[r] / l;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s_b[j * 3 + k] = fine ? d[k] * ratio : d[k];
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (!active[r]) continue;
+            double acc[3] = {0.0, 0.0, 0.0};
+            int c = r * 64 + lane;
+            while (s_flag[c] & BONE_ACTIVE) {   // the parent index falls: at most J - 1 steps
+#pragma unroll
+                for (int k = 0; k < 3; ++k) acc[k] = acc[k] + s_b[c * 3 + k];
+                c = s_par[c];
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) z[r][k] = s_y[c * 3 + k] + acc[k];
+        }
+        wave_lds_sync();   // every walk has read s_y before the returned values overwrite it
+    }
+
+    // ---- out, code, and the residual on the fp32 values that are returned
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (!own[r]) continue;
+        const int j = r * 64 + lane;
+        float o[3];
+        if (cnt[r] > 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) o[k] = (float)z[r][k];
+        } else {   // the input's bits
+#pragma unroll
+            for (int k = 0; k < 3; ++k) o[k] = p.pose[(row + j) * 3 + k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            p.out[(row + j) * 3 + k] = o[k];
+            s_y[j * 3 + k] = (double)o[k];
+        }
+        if (p.code) p.code[row + j] = (uint8_t)(cnt[r] > 0 ? BONE_DONE : wanted[r] ? BONE_FAILED : BONE_KEPT);
+    }
+    if (!p.resid) return;
+    wave_lds_sync();
+    const double after = residual();
+    if (lane == 0) p.resid[item * 2] = (float)before, p.resid[item * 2 + 1] = (float)after;
 }
 
 // ----------------------------------------------------------------------------------------------------------------

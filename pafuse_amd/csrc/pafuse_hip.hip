@@ -2362,6 +2362,49 @@ int pafuse_pose_smooth(const float* pose, const float* cov, int32_t T, int32_t N
     return launch<pose_smooth_kernel>("pose_smooth_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
 }
 
+// bone lengths held constant along a video: the weighted length of every bone (bone_lengths_kernel) and every frame projected
+// onto the lengths of its step (bone_project_kernel); one kernel each, the argument checks come before the first HIP call
+int pafuse_bone_lengths(const float* pose, const float* cov, const int32_t* parent, const int32_t* mirror, int32_t T, int32_t N,
+                        int32_t J, float floor, float* length, float* dev, int32_t* frames, void* stream) {
+    if (!pose || !parent || !length)
+        return fail(PAFUSE_E_ARG, "bone_lengths: pose, parent and length are needed (cov, mirror, dev and frames may be null)");
+    if (T < 1 || N < 1 || J < 1) return fail(PAFUSE_E_ARG, "bone_lengths: bad size (T=%d N=%d J=%d)", T, N, J);
+    if (J > 256) return fail(PAFUSE_E_ARG, "bone_lengths: J = %d is more than 256", J);
+    if (!std::isfinite(floor) || !(floor > 0.f)) return fail(PAFUSE_E_ARG, "bone_lengths: floor %g is not finite and > 0", (double)floor);
+    unsigned grid;
+    if (int rc = wave_grid("bone_lengths", (int64_t)T * J, grid)) return rc;   // one wave per (t, j)
+    StreamDevice on_stream_device(stream);
+    BoneLengthsParams m{};
+    m.pose = pose, m.cov = cov, m.parent = parent, m.mirror = mirror, m.length = length, m.dev = dev, m.frames = frames;
+    m.T = T, m.N = N, m.J = J, m.floor = floor;
+    return launch<bone_lengths_kernel>("bone_lengths_kernel", grid, 256, 0, (hipStream_t)stream, m);
+}
+
+int pafuse_bone_project(const float* pose, const float* cov, const int32_t* parent, const float* length, int32_t T, int32_t N,
+                        int32_t J, int32_t iterations, int32_t snap, float floor, float* out, uint8_t* code, float* resid,
+                        void* stream) {
+    if (!pose || !parent || !length || !out)
+        return fail(PAFUSE_E_ARG, "bone_project: pose, parent, length and out are needed (cov, code and resid may be null)");
+    if (T < 1 || N < 1 || J < 1) return fail(PAFUSE_E_ARG, "bone_project: bad size (T=%d N=%d J=%d)", T, N, J);
+    if (J > 256) return fail(PAFUSE_E_ARG, "bone_project: J = %d is more than 256", J);
+    if (iterations < 0 || iterations > 64) return fail(PAFUSE_E_ARG, "bone_project: iterations %d outside 0 .. 64", iterations);
+    if (snap != 0 && snap != 1) return fail(PAFUSE_E_ARG, "bone_project: snap must be 0 or 1, got %d", snap);
+    if (!std::isfinite(floor) || !(floor > 0.f)) return fail(PAFUSE_E_ARG, "bone_project: floor %g is not finite and > 0", (double)floor);
+    if (out == pose) return fail(PAFUSE_E_ARG, "bone_project: out may not alias pose (a joint without an active bone keeps the input's bits)");
+    unsigned grid;
+    if (int rc = wave_grid("bone_project", (int64_t)T * N, grid)) return rc;   // one wave per (t, n)
+    StreamDevice on_stream_device(stream);
+    BoneProjectParams m{};
+    m.pose = pose, m.cov = cov, m.parent = parent, m.length = length, m.out = out, m.code = code, m.resid = resid;
+    m.T = T, m.N = N, m.J = J, m.iterations = iterations, m.snap = snap, m.floor = floor;
+    switch ((J + 63) / 64) {   // joints per lane
+        case 1: return launch<bone_project_kernel<1>>("bone_project_kernel", grid, 256, 0, (hipStream_t)stream, m);
+        case 2: return launch<bone_project_kernel<2>>("bone_project_kernel", grid, 256, 0, (hipStream_t)stream, m);
+        case 3: return launch<bone_project_kernel<3>>("bone_project_kernel", grid, 256, 0, (hipStream_t)stream, m);
+        default: return launch<bone_project_kernel<4>>("bone_project_kernel", grid, 256, 0, (hipStream_t)stream, m);
+    }
+}
+
 // the focal-length sums of every (t, frame) of the finished pose (frames_focal_sums_kernel) and the estimate from them
 // (focal_solve_kernel): the argument checks come before the first HIP call
 int pafuse_frames_focal_sums(const float* pose, const float* x2d, const float* conf, const float* cam, int32_t T, int32_t N,

@@ -73,6 +73,54 @@ def skeleton_parents(n_face, root_added):
     return body + feet + face + hands
 
 
+def bone_tables(dataset_or_n_face=68, root_added=True, left=None, right=None):
+    """-> (parent int32 [J], mirror int32 [J]): the tables of the bone-length constraint (pafuse_amd.bones, DESIGN.md section
+    6n).  ``parent[j]`` is the joint that joint j's bone hangs on, or -1 for no bone - the body's real topology, a list of our
+    own, unlike :func:`skeleton_parents`, which leaves the head points free for drawing: the nose hangs on the root, eyes
+    and ears on the nose, shoulders and hips on the root, elbow on shoulder, wrist on elbow, knee on hip, ankle on knee, the
+    three foot points on their ankle, the hands as :func:`_hand_parents` has them (depth 8 from the root to a fingertip).
+    The face points get -1 and are not touched: carried with the nose they would take on the noise of its correction, and an
+    expression changes their distances anyway.  Every parent index is smaller than its child's - the kernels rely on that.
+    Without the inserted root the nose is the top and shoulders and hips hang as in ``skeleton_parents(n_face, False)``.
+    ``mirror[j]`` is the left/right partner of joint j, or -1: ``left`` / ``right`` paired by position when given, else the
+    ``joints_left()`` / ``joints_right()`` of a dataset that has a ``skeleton()``, else the layout's own pairs (body and feet
+    alternate left, right; the left hand's points mirror the right hand's).  ``dataset_or_n_face``: such a dataset, any object
+    with ``parts_joint_indices["face"]``, or the number of face points."""
+    ds = dataset_or_n_face
+    if isinstance(ds, (int, np.integer)) and not isinstance(ds, bool):
+        n_face = int(ds)
+    elif hasattr(ds, "parts_joint_indices"):
+        n_face = len(ds.parts_joint_indices["face"])
+    else:
+        n_face = len(ds.metadata["face"])
+    if n_face < 0:
+        raise ValueError(f"bone_tables: the number of face points must be >= 0, got {n_face}")
+    s = 1 if root_added else 0
+    head = [-1, 0, 1, 1, 1, 1] if root_added else [-1, 0, 0, 0, 0]               # (root,) nose, eyes, ears
+    limbs = ([0, 0, 6, 7, 8, 9, 0, 0, 12, 13, 14, 15] if root_added              # shoulders, elbows, wrists, hips, knees, ankles
+             else [0, 0, 5, 6, 7, 8, 5, 6, 11, 12, 13, 14])
+    feet = [15 + s] * 3 + [16 + s] * 3
+    lh, rh = 23 + n_face, 44 + n_face                                            # the hands' wrists before the root shift
+    hands = [p + s for p in _hand_parents(lh, 9) + _hand_parents(rh, 10)]
+    parent = np.array(head + limbs + feet + [-1] * n_face + hands, dtype=np.int32)
+    J = len(parent)
+    assert all(-1 <= parent[j] < j for j in range(J))
+    if left is None and right is None and hasattr(ds, "skeleton"):
+        left, right = ds.skeleton().joints_left(), ds.skeleton().joints_right()
+    if left is None and right is None:
+        body = list(range(1, 17, 2))                                             # left eye, ear, shoulder, ... ankle (no root shift)
+        left = [j + s for j in body + [17, 18, 19] + list(range(lh, lh + 21))]
+        right = [j + s for j in [b + 1 for b in body] + [20, 21, 22] + list(range(rh, rh + 21))]
+    if left is None or right is None or len(left) != len(right):
+        raise ValueError("bone_tables: left and right come together and pair by position")
+    mirror = np.full(J, -1, dtype=np.int32)
+    for a, b in zip(left, right):
+        if not (0 <= a < J and 0 <= b < J and a != b):
+            raise ValueError(f"bone_tables: the pair ({a}, {b}) is not two joints of {J}")
+        mirror[a], mirror[b] = b, a
+    return parent, mirror
+
+
 def with_root_joint(arr, hips=(11, 12)):
     """[N,133,c] -> [N,134,c] (float64, like the reference's np.zeros buffer): keypoint 0 = midpoint of the hips."""
     out = np.zeros((arr.shape[0], arr.shape[1] + 1, arr.shape[2]))
@@ -252,7 +300,7 @@ def evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, batc
 def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
                     batch_size=2, group=None, log=print, action=None, hypothesis_chunk=None, p2=False, seam_profile=False, focal=None,
                     repair=None, drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None,
-                    pose_smooth_floor=1e-3):
+                    pose_smooth_floor=1e-3, bone_lengths=None, bone_iterations=16):
     """The frame-level evaluation of every video, looped like :func:`evaluate`: harness.evaluate_frames per (camera, sequence) -
     one pose per video frame (``aggregate``, ``stride``; None: un-strided clips laid end to end), optionally its fitted
     camera-space root (``trajectory``: True or a smoothing radius) - scored on the device; the sums and counts added over the
@@ -270,6 +318,10 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
     whole video instead, at any ``stride``.  ``pose_smooth`` (a radius 1 .. 64, ``pose_smooth_floor`` metres) scores the pose
     smoothed along the frames with the covariance of the hypotheses as matrix weight (harness.evaluate_frames): compare the
     ``mpjpe`` and ``accel`` lines with a run without it - what the smoother buys on a real checkpoint has not been measured.
+    ``bone_lengths`` ("video" or "symmetric"; ``bone_iterations`` Jacobi sweeps) scores the pose with its bone lengths held
+    constant along each video (harness.evaluate_frames): per video the mean bone-length standard deviation of the free and of
+    the constrained pose and the largest difference of the held lengths from the ground truth's are logged - what it buys on
+    a real checkpoint has not been measured either.
     On synthetic weights the numbers mean nothing."""
     from . import detections, harness
     if drop is not None and (not isinstance(drop, (tuple, list)) or len(drop) != 3):
@@ -282,7 +334,14 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
                                       hypothesis_chunk=hypothesis_chunk, p2=p2, per_frame=seam_profile, focal=focal, repair=repair,
                                       drop=None if drop is None else (drop[0], drop[1], int(drop[2]) + video),
                                       repair_threshold=repair_threshold, path_weight=path_weight, path_scope=path_scope,
-                                      pose_smooth=pose_smooth, pose_smooth_floor=pose_smooth_floor)
+                                      pose_smooth=pose_smooth, pose_smooth_floor=pose_smooth_floor, bone_lengths=bone_lengths,
+                                      bone_iterations=bone_iterations)
+        if bone_lengths is not None:
+            held, got = got[-1], got[:-1]
+            gap = (held["bone_length"].double() - held["bone_length_gt"].double()).abs()
+            log("video %d: bone-length std (mm, mean over the bones) free %s -> constrained %s; held lengths vs ground truth: max %.1f mm"
+                % (video, ["%.2f" % v for v in held["bone_dev_free"].tolist()], ["%.2f" % v for v in held["bone_dev"].tolist()],
+                   float(gap[~gap.isnan()].max()) * 1000.0 if bool((~gap.isnan()).any()) else float("nan")))
         if repair is not None or drop is not None:
             seen, got = got[-1], got[:-1]
             if "status" in seen:

@@ -110,7 +110,8 @@ def repair_detections(seq_2d, conf, dataset=None, anchor=None, radius=13, thresh
 @torch.no_grad()
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
                    hypothesis_chunk=None, spread=None, conf=None, stride=None, trajectory=None, focal=None, repair=None,
-                   repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None, pose_smooth_floor=1e-3):
+                   repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None, pose_smooth_floor=1e-3,
+                   bone_lengths=None, bone_iterations=16):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -217,7 +218,28 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     exactly 0, and identical hypotheses solvable - not a tuned value.  A fixed-radius linear smoother: no motion model, no
     bone-length constraint, no covariance of the result; weights that are constant along the frames cancel.  What it buys on
     real weights has NOT been measured.  Every rank holds the same frame state and runs the same filter.  Without ``stride``
-    use :func:`smooth_poses` on the stitched poses."""
+    use :func:`smooth_poses` on the stitched poses.
+
+    ``bone_lengths`` (with ``stride`` and an ``aggregate``; None: everything above, unchanged, bit for bit) HOLDS THE BONE
+    LENGTHS CONSTANT along the video, on the device (:func:`constrain_bones`; pafuse_amd.bones states the arithmetic).
+    "video": one length per bone and step, the mean of its per-frame lengths with every frame weighing as far as its hypotheses
+    agree along the bone; "symmetric": the same with left and right pooled (the ``joints_left()`` / ``joints_right()`` of the dataset's
+    skeleton, else ``kps_left`` / ``kps_right``, paired by position);
+    a tensor [J] or [T,J]: the caller's own lengths in metres (a calibration, another video; NaN: that bone is left alone).
+    Every frame is then moved onto those lengths by ``bone_iterations`` (0 .. 64) Jacobi sweeps of the covariance-weighted
+    projection - both ends of a wrong bone give way by the least Mahalanobis distance under the covariance of the hypotheses
+    pooled at that joint - and an exact top-down snap.  The bones are h3wb.bone_tables': the body's real topology and the
+    hands; the face points hang on nothing and are not touched; the root never moves.  It runs AFTER ``pose_smooth`` (smoothing
+    bends bones, this straightens them) and before the trajectory fit: the root fit, the focal estimate and the metrics see
+    the constrained pose.  ``"pose"`` is the constrained pose; added keys: ``"pose_free"`` [T,N,J,3], what "pose" was (the
+    smoothed pose with ``pose_smooth``), ``"bone_length"`` [T,J] the lengths held, ``"bone_dev"`` [T,J] the weighted standard
+    deviation of the free pose's bone lengths and ``"bone_frames"`` [T,J] int32 the frames they rest on (both of the video,
+    also when the lengths are the caller's), ``"bone_code"`` [T,N,J] uint8 (1 moved with a bone, 0 untouched, 3 untouched
+    although a bone was asked of it: no finite pose or no usable covariance) and ``"bone_resid"`` [T,N,2] the largest
+    |length - L| of every frame before and after, in metres.  ``std`` / ``cov`` stay what they were: the covariance is not
+    updated.  16 sweeps and the 1 mm floor are defaults, not tuned values.  One length per bone per video, no joint-angle
+    limits; the estimated lengths are biased long where the noise is comparable to the bone (pass your own there).  What it
+    buys on real weights has NOT been measured."""
     smooth = _trajectory_radius(trajectory)
     pose_smooth = _pose_smooth_radius(pose_smooth, pose_smooth_floor)
     if pose_smooth is not None:
@@ -226,6 +248,15 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
         if aggregate is None:
             raise ValueError('pose_smooth needs aggregate="mean", "reproj" or "reproj_fit": it smooths the ONE pose per frame')
         pose_smooth = (pose_smooth, float(pose_smooth_floor))
+    bones = _bone_spec(bone_lengths, bone_iterations)
+    if bones is not None:
+        if stride is None:
+            raise ValueError("bone_lengths needs stride (one pose per video frame); for stitched clips call harness.constrain_bones")
+        if aggregate is None:
+            raise ValueError('bone_lengths needs aggregate="mean", "reproj" or "reproj_fit": it constrains the ONE pose per frame')
+        bones["tables"] = _bone_tables(None, dataset, kps_left, kps_right)
+        if not isinstance(bones["lengths"], str) and bones["lengths"].shape[-1] != len(bones["tables"][0]):
+            raise ValueError(f"bone_lengths must be [J] or [T,J] with J = {len(bones['tables'][0])}, got {tuple(bones['lengths'].shape)}")
     _focal_mode(focal)
     repair = _repair_radius(repair, repair_threshold)
     path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, getattr(model, "frames", None), path_scope)
@@ -271,14 +302,14 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     dev = next(model.parameters()).device
     if repair is None:
         return _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, trajectory, smooth, focal, dev, path_weight, path_scope, pose_smooth)
+                               spread, conf, stride, trajectory, smooth, focal, dev, path_weight, path_scope, pose_smooth, bones)
     from .detections import repair_anchors
     fixed = _repair_detections(seq_2d.squeeze(0) if seq_2d.dim() == 4 else seq_2d, conf, repair_anchors(dataset), repair,
                                float(repair_threshold), dev)
     # the callees cut and flip on the host: the repaired pair takes the place of the input, whole, before either
     out = _infer_sequence(model, dataset, fixed["x2d"].cpu(), kps_left, kps_right, batch_size, group, aggregate, cam, traj,
                           hypothesis_chunk, spread, fixed["conf"].cpu(), stride, trajectory, smooth, focal, dev, path_weight, path_scope,
-                          pose_smooth)
+                          pose_smooth, bones)
     if isinstance(out, dict):
         out["repaired"] = fixed["status"].cpu()
     return out
@@ -317,14 +348,15 @@ def _path_batch(sampler, dataset, x2d, x2d_flip, traj, cam, conf, fit, path_weig
 
 
 def _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                    conf, stride, trajectory, smooth, focal, dev, path_weight=None, path_scope="clip", pose_smooth=None):
+                    conf, stride, trajectory, smooth, focal, dev, path_weight=None, path_scope="clip", pose_smooth=None, bones=None):
     """infer_sequence behind its argument checks (and behind the repair of the detections, when one was asked for)"""
     fit = aggregate == "reproj_fit"
     if stride is None and path_scope == "video":      # one path along the video: per-frame results, the clips of cut_clips
         stride = model.frames
     if stride is not None:
         return _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                             spread, conf, int(stride), dev, trajectory is not None, smooth, focal, path_weight, path_scope, pose_smooth)
+                             spread, conf, int(stride), dev, trajectory is not None, smooth, focal, path_weight, path_scope, pose_smooth,
+                             bones)
     x2d = cut_clips(seq_2d, model.frames).to(dev)
     x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), model.frames).to(dev)
     sampler = ShardedSampler(model, group)
@@ -395,21 +427,24 @@ def cut_windows(seq, starts, frames=27):
 
 
 def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                  conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip", pose_smooth=None):
+                  conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip", pose_smooth=None,
+                  bones=None):
     """infer_sequence(stride=...): sliding windows pooled into one pose per video frame (arguments already checked)"""
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, dev, trajectory, smooth, focal, path_weight, path_scope, pose_smooth)
+                               spread, conf, stride, dev, trajectory, smooth, focal, path_weight, path_scope, pose_smooth, bones)
     return {k: v.cpu() for k, v in out.items()}
 
 
 def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
                          conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip",
-                         pose_smooth=None):
-    """_infer_frames with its result left on the device (evaluate_frames scores it there); pose_smooth: None or (radius, floor)"""
+                         pose_smooth=None, bones=None):
+    """_infer_frames with its result left on the device (evaluate_frames scores it there); pose_smooth: None or (radius, floor);
+    bones: None or _bone_spec's dict with its tables"""
     from . import ops
     from .windows import coverage, window_starts
-    asked = spread                  # what the caller wants returned; the pose smoother needs the covariance whatever that is
-    if pose_smooth is not None and spread is None:
+    asked = spread                  # what the caller wants returned; the pose smoother and the bones need the covariance whatever that is
+    needs_cov = pose_smooth is not None or bones is not None
+    if needs_cov and spread is None:
         spread = "cov"
     if seq_2d.dim() == 4:
         seq_2d = seq_2d.squeeze(0)
@@ -478,7 +513,7 @@ def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size
         frames = accumulate_frames(frames, merged, starts[lo:hi], valid[lo:hi], N, model.num_proposals)
     want = (("mean", "count") + (("pick", "idx", "window") if reproj else ())
             + (() if asked is None else ("std",) if asked == "std" else ("std", "cov"))
-            + (("cov",) if pose_smooth is not None and asked != "cov" else ()))
+            + (("cov",) if needs_cov and asked != "cov" else ()))
     out = ops.finish_frames(N, frames.T, frames.J, frame=frames.pose, spread=frames.spread, want=want)
     if video:       # one path along the video through the hypotheses of all windows, against the pooled mean
         from .evaluate import path_frames
@@ -490,10 +525,13 @@ def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size
         out["pick"] = torch.where((out["idx"] < 0).unsqueeze(-1), out["mean"], out["pick"])
     out["pose"] = out.pop("pick") if reproj else out["mean"]
     out.pop("mean", None)
-    if pose_smooth is not None:     # right behind the finish, on the pose that is returned: everything below sees the smoothed pose
+    if needs_cov:
         cov = out["cov"] if asked == "cov" else out.pop("cov")
+    if pose_smooth is not None:     # right behind the finish, on the pose that is returned: everything below sees the smoothed pose
         out["pose_raw"] = out["pose"].contiguous()
         out["pose"], out["pose_smooth_code"] = ops.smooth_poses(out["pose_raw"], cov, pose_smooth[0], floor=pose_smooth[1], want_code=True)
+    if bones is not None:           # smoothing bends bones, this straightens them; the root fit below sees the constrained pose
+        out.update(_constrain_bones(out["pose"].contiguous(), cov, bones))
     if trajectory:  # the root of the pose that is returned, on the device before anything crosses to the host
         out.update(_fit_trajectory(out["pose"], seq_2d.to(dev), cam, None if frame_conf is None else frame_conf.to(dev), smooth, focal))
     return out
@@ -517,6 +555,73 @@ def _pose_smooth_radius(pose_smooth, floor=1e-3, name="pose_smooth"):
     if isinstance(floor, bool) or not isinstance(floor, (int, float)) or not 0 < floor < float("inf"):      # (a NaN fails both)
         raise ValueError(f"{name}_floor must be a finite number > 0 (metres; the default 1e-3 is a regulariser, not a tuned value), got {floor!r}")
     return pose_smooth
+
+
+BONE_FLOOR = 1e-3      # metres: a regulariser that keeps a zero covariance usable, not a tuned value
+
+
+def _bone_spec(bone_lengths, bone_iterations=16, snap=True, floor=BONE_FLOOR):
+    """infer_sequence's `bone_lengths` / `bone_iterations`: None, or {"lengths": "video" | "symmetric" | a float32 CPU tensor
+    [J] or [T,J], "iterations", "snap", "floor"} - refused here, before anything touches the device"""
+    if bone_lengths is None:
+        return None
+    if isinstance(bone_lengths, str):
+        if bone_lengths not in ("video", "symmetric"):
+            raise ValueError(f'bone_lengths must be None, "video", "symmetric" or a tensor [J] or [T,J] of lengths in metres, got {bone_lengths!r}')
+        lengths = bone_lengths
+    else:
+        lengths = torch.as_tensor(bone_lengths, dtype=torch.float32)
+        if lengths.dim() not in (1, 2) or 0 in lengths.shape:
+            raise ValueError(f"bone_lengths must be [J] or [T,J] (metres), got {tuple(lengths.shape)}")
+    if isinstance(bone_iterations, bool) or not isinstance(bone_iterations, int) or not 0 <= bone_iterations <= 64:
+        raise ValueError(f"bone_iterations must be an integer in 0 .. 64 (Jacobi sweeps; the default 16 is not a tuned value), got {bone_iterations!r}")
+    if isinstance(floor, bool) or not isinstance(floor, (int, float)) or not 0 < floor < float("inf"):
+        raise ValueError(f"floor must be a finite number > 0 (metres; the default 1e-3 is a regulariser, not a tuned value), got {floor!r}")
+    return {"lengths": lengths, "iterations": int(bone_iterations), "snap": bool(snap), "floor": float(floor)}
+
+
+def _bone_tables(tables, dataset=None, kps_left=None, kps_right=None, J=None):
+    """-> (parent, mirror) int32 numpy [J], validated on the host (ops.bone_table): `tables` as given - (parent, mirror) with
+    mirror None or absent - or h3wb.bone_tables of the dataset: the joints_left() / joints_right() of its skeleton() where it has one,
+    else kps_left / kps_right, paired by position"""
+    from . import ops
+    from .h3wb import bone_tables
+    if tables is None:
+        if hasattr(dataset, "skeleton"):                              # the dataset's own joints_left() / joints_right()
+            kps_left = kps_right = None
+        parent, mirror = bone_tables(68 if dataset is None else dataset, True, None if kps_left is None else list(kps_left),
+                                     None if kps_right is None else list(kps_right))
+    else:
+        if not isinstance(tables, (tuple, list)) or len(tables) not in (1, 2):
+            raise ValueError("tables must be (parent, mirror) - mirror may be None - as h3wb.bone_tables returns them")
+        parent, mirror = tables[0], tables[1] if len(tables) == 2 else None
+    n = len(parent) if J is None else int(J)
+    parent = ops.bone_table(parent, n)
+    return parent, None if mirror is None else ops.bone_table(mirror, n, mirror=True)
+
+
+def _constrain_bones(free, cov, bones):
+    """the bone keys of infer_sequence on the device: free [T,N,J,3] contiguous, cov [T,N,J,6] or None, bones: _bone_spec's dict
+    with its tables"""
+    from . import ops
+    T, N, J, _ = free.shape
+    parent, mirror = bones["tables"]
+    if len(parent) != J:
+        raise ValueError(f"the bone tables hold {len(parent)} joints, the pose {J}")
+    lengths, floor = bones["lengths"], bones["floor"]
+    video, dev, frames = ops.bone_lengths(free, cov, parent, mirror if isinstance(lengths, str) and lengths == "symmetric" else None,
+                                          floor=floor, want_dev=True, want_frames=True)
+    if isinstance(lengths, str):
+        held = video
+    else:
+        if tuple(lengths.shape) not in ((J,), (T, J)):
+            raise ValueError(f"bone_lengths must be [J] = [{J}] or [T,J] = {(T, J)}, got {tuple(lengths.shape)}")
+        held = lengths.to(free.device)
+        held = (held.unsqueeze(0).expand(T, J) if held.dim() == 1 else held).contiguous()
+    pose, code, resid = ops.project_bones(free, cov, parent, held, iterations=bones["iterations"], snap=bones["snap"], floor=floor,
+                                          want_code=True, want_resid=True)
+    return {"pose": pose, "pose_free": free, "bone_length": held, "bone_dev": dev, "bone_frames": frames, "bone_code": code,
+            "bone_resid": resid}
 
 
 def _focal_mode(focal):
@@ -620,6 +725,47 @@ def smooth_poses(poses, cov=None, radius=13, floor=1e-3, device="cuda"):
     raw = poses.to(dev).contiguous()
     pose, code = ops.smooth_poses(raw, None if cov is None else cov.to(dev).contiguous(), radius, floor=float(floor), want_code=True)
     return {"pose": pose.cpu(), "pose_raw": raw.cpu(), "pose_smooth_code": code.cpu()}
+
+
+@torch.no_grad()
+def constrain_bones(poses, cov=None, tables=None, lengths="video", iterations=16, snap=True, floor=1e-3, device="cuda"):
+    """Bone lengths held constant along a video, for poses a caller already has: ``poses`` [T,N,J,3] - an
+    ``infer_sequence(stride=...)["pose"]``, the result of :func:`stitch_poses` or :func:`smooth_poses`, or any such array of N
+    video frames - ``cov`` [T,N,J,6] the covariance of the hypotheses per (t, frame, joint) (``infer_sequence(spread="cov")``;
+    None: zeros - every joint gives way alike in every direction), ``tables`` (parent, mirror) as h3wb.bone_tables returns
+    them (None: the H3WB tables with the inserted root, 134 joints; every parent index must be smaller than its child's),
+    ``lengths`` "video" (one length per bone and step from the whole video: ops.bone_lengths), "symmetric" (the same with the
+    mirror partners pooled) or a tensor [J] or [T,J] of the caller's own lengths in metres (NaN: that bone is left alone),
+    ``iterations`` 0 .. 64 Jacobi sweeps of the covariance-weighted projection, ``snap`` the exact top-down pass behind them,
+    ``floor`` in metres (finite and > 0).  16 sweeps and the 1 mm floor are defaults, not tuned values.  ops.bone_lengths and
+    ops.project_bones; pafuse_amd.bones states the arithmetic.  Returns a dict of CPU tensors: ``"pose"`` [T,N,J,3] the
+    constrained pose, ``"pose_free"`` the input, ``"bone_length"`` [T,J] the lengths held, ``"bone_dev"`` [T,J] the weighted
+    standard deviation of the input's bone lengths, ``"bone_frames"`` [T,J] int32, ``"bone_code"`` [T,N,J] uint8 (1 moved with a
+    bone, 0 untouched, 3 untouched although a bone was asked of it) and ``"bone_resid"`` [T,N,2] the largest |length - L| of every
+    frame before and after (metres) - the keys ``infer_sequence(bone_lengths=...)`` adds.  Jacobi converges slowly:
+    ``bone_resid`` with ``snap=False`` tells how far.  One length per bone per video, no joint-angle limits, the covariance is
+    not updated; what it buys on real weights has not been measured."""
+    bones = _bone_spec(lengths, iterations, snap, floor)
+    if bones is None:
+        raise ValueError('lengths must be "video", "symmetric" or a tensor [J] or [T,J], got None')
+    if not isinstance(snap, (bool, int)) or snap not in (0, 1):
+        raise ValueError(f"snap must be a bool, got {snap!r}")
+    poses = torch.as_tensor(poses, dtype=torch.float32)
+    if poses.dim() != 4 or poses.shape[-1] != 3 or 0 in poses.shape:
+        raise ValueError(f"poses must be [T,N,J,3], got {tuple(poses.shape)}")
+    T, N, J, _ = poses.shape
+    if cov is not None:
+        cov = torch.as_tensor(cov, dtype=torch.float32)
+        if tuple(cov.shape) != (T, N, J, 6):
+            raise ValueError(f"cov must be [T,N,J,6] = {(T, N, J, 6)}, got {tuple(cov.shape)}")
+    bones["tables"] = _bone_tables(tables, J=None if tables is None else J)
+    if len(bones["tables"][0]) != J:
+        raise ValueError(f"the bone tables hold {len(bones['tables'][0])} joints, the pose {J}")
+    if not isinstance(bones["lengths"], str) and tuple(bones["lengths"].shape) not in ((J,), (T, J)):
+        raise ValueError(f"lengths must be [J] = [{J}] or [T,J] = {(T, J)}, got {tuple(bones['lengths'].shape)}")
+    dev = poses.device if poses.is_cuda else torch.device(device)
+    out = _constrain_bones(poses.to(dev).contiguous(), None if cov is None else cov.to(dev).contiguous(), bones)
+    return {k: v.cpu() for k, v in out.items()}
 
 
 @torch.no_grad()
@@ -876,7 +1022,8 @@ holds the p2_* keys, each step ends with the four Protocol #2 lines (:511-519): 
 @torch.no_grad()
 def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
                     conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False, focal=None, repair=None,
-                    drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None, pose_smooth_floor=1e-3):
+                    drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None, pose_smooth_floor=1e-3,
+                    bone_lengths=None, bone_iterations=16):
     """One video scored at the level of frames: the frames path of :func:`infer_sequence` - ONE pose per video frame, pooled
     over the windows that cover it - against the ground truth, on the device before anything crosses to the host
     (evaluate.frame_metrics; pafuse_amd.framemetrics states the arithmetic).
@@ -914,11 +1061,23 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
 
     ``pose_smooth`` (a radius 1 .. 64; None: everything above, unchanged) scores the pose SMOOTHED along the frames with the
     covariance of the hypotheses as matrix weight, infer_sequence(pose_smooth=..., pose_smooth_floor=...): the ``mpjpe`` and
-    ``accel`` columns show what a radius buys, and the trajectory is fitted on the smoothed pose."""
+    ``accel`` columns show what a radius buys, and the trajectory is fitted on the smoothed pose.
+
+    ``bone_lengths`` ("video", "symmetric" or a tensor [J] or [T,J]; None: everything above, unchanged) and ``bone_iterations``
+    score the pose with its BONE LENGTHS HELD CONSTANT along the video, infer_sequence(bone_lengths=..., bone_iterations=...):
+    the existing ``mpjpe`` / ``accel`` columns score it, the trajectory is fitted on it.  One more, last element is returned, a
+    dict of CPU tensors: ``"bone_length"`` [J] the lengths held at the last step, ``"bone_length_gt"`` [J] the same kernel on
+    the ground truth (a [1,N,J,3] pose without a covariance; NaN: no bone), and ``"bone_dev_free"`` / ``"bone_dev"`` [T]: the
+    mean over the bones of the bone-length standard deviation, in mm, of the free and of the constrained pose."""
     _focal_mode(focal)
     pose_smooth = _pose_smooth_radius(pose_smooth, pose_smooth_floor)
     if pose_smooth is not None:
         pose_smooth = (pose_smooth, float(pose_smooth_floor))
+    bones = _bone_spec(bone_lengths, bone_iterations)
+    if bones is not None:
+        bones["tables"] = _bone_tables(None, dataset, kps_left, kps_right)
+        if not isinstance(bones["lengths"], str) and bones["lengths"].shape[-1] != len(bones["tables"][0]):
+            raise ValueError(f"bone_lengths must be [J] or [T,J] with J = {len(bones['tables'][0])}, got {tuple(bones['lengths'].shape)}")
     repair = _repair_radius(repair, repair_threshold)
     if drop is not None:
         if (not isinstance(drop, (tuple, list)) or len(drop) != 3 or not 0.0 <= float(drop[0]) <= 1.0
@@ -971,13 +1130,23 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     gt_wb = (seq_3d - seq_3d[:, :1]).to(dev)                        # joint 0 at 0, exactly
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam,
                                gt_root if aggregate == "reproj" else None, hypothesis_chunk, None, conf, stride, dev,
-                               trajectory is not None, smooth, focal, path_weight, path_scope, pose_smooth)
+                               trajectory is not None, smooth, focal, path_weight, path_scope, pose_smooth, bones)
     estimate = {k: out[k].cpu() for k in ("focal", "focal_r2", "focal_frames", "cam")} if focal is not None else None
+    held = None
+    if bones is not None:           # the lengths held beside the ground truth's, and what the constraint did to the known diagnostic
+        from . import ops
+        parent, mirror = bones["tables"]
+        mirror = mirror if isinstance(bones["lengths"], str) and bones["lengths"] == "symmetric" else None
+        gt_length = ops.bone_lengths(gt_wb.unsqueeze(0).contiguous(), None, parent, mirror, floor=bones["floor"])
+        _, dev_after = ops.bone_lengths(out["pose"], None, parent, mirror, floor=bones["floor"], want_dev=True)
+        held = {"bone_length": out["bone_length"][-1].cpu(), "bone_length_gt": gt_length[0].cpu(),
+                "bone_dev_free": (out["bone_dev"].double().nanmean(dim=1) * 1000.0).cpu(),
+                "bone_dev": (dev_after.double().nanmean(dim=1) * 1000.0).cpu()}
     m = frame_metrics(out["pose"], gt_wb, dataset, traj=out.get("traj"), gt_root=gt_root.to(dev) if "traj" in out else None,
                       p2=p2, per_frame=per_frame)
     maps = {k: m.pop(k).cpu() for k in ("err", "cnt") if k in m}
     sums, counts = {k: v[0].cpu() for k, v in m.items()}, {k: v[1].cpu() for k, v in m.items()}
-    tail = (() if estimate is None else (estimate,)) + (() if seen is None else (seen,))
+    tail = (() if estimate is None else (estimate,)) + (() if seen is None else (seen,)) + (() if held is None else (held,))
     if per_frame:
         from .evaluate import frame_metric_names
         maps["names"] = frame_metric_names(dataset)

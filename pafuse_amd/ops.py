@@ -1596,6 +1596,114 @@ def smooth_poses(pose, cov, radius, floor=1e-3, out=None, want_code=False, works
     return (out, code) if want_code else out
 
 
+# ------------------------------------------------------------------ bone lengths held constant along a video
+_BONE_CACHE_MAX = 16
+_bone_cache = {}    # (what, the table's bytes, device) -> its int32 device copy
+
+
+def bone_table(table, J, device=None, mirror=False):
+    """A table of the bone kernels, validated on the host: an integer sequence, numpy array or tensor [J].  The parent table
+    (mirror=False): every entry is -1 (no bone) or the index of a joint below the entry's own - the kernels read anything
+    else as -1, here it is a ValueError (pafuse_amd.bones.table).  The mirror table: every entry is -1 or a joint of 0 .. J-1.
+    -> int32 numpy [J]; with `device` its cached int32 copy there."""
+    from . import bones
+    import numpy as np
+    who = "mirror" if mirror else "parent"
+    if isinstance(table, torch.Tensor):
+        _need(not table.dtype.is_floating_point and table.dtype != torch.bool, f"bones: {who} must be an integer table")
+        table = table.detach().cpu().numpy()
+    table = np.asarray(table)
+    _need(table.shape == (int(J),) and table.dtype.kind in "iu", f"bones: {who} must be an integer table [J] = [{int(J)}], got {table.dtype} {table.shape}")
+    if mirror:
+        _need(bool(((table >= -1) & (table < int(J))).all()), f"bones: every mirror entry must be -1 or a joint of 0 .. {int(J) - 1}")
+    else:
+        bones.table(table, int(J), strict=True)
+    table = np.ascontiguousarray(table.astype(np.int32))
+    if device is None:
+        return table
+    key = (who, table.tobytes(), str(device))
+    hit = _bone_cache.get(key)
+    if hit is None:
+        if len(_bone_cache) >= _BONE_CACHE_MAX:
+            _bone_cache.pop(next(iter(_bone_cache)))
+        hit = _bone_cache[key] = torch.from_numpy(table).to(device)
+    return hit
+
+
+def _bone_operands(who, pose, cov):
+    _need(isinstance(pose, torch.Tensor) and pose.dim() == 4 and pose.shape[-1] == 3, f"{who}: pose must be [T,N,J,3]")
+    T, N, J = (int(v) for v in pose.shape[:3])
+    _need(T > 0 and N > 0 and J > 0, f"{who}: T, N, J > 0")
+    _need(J <= 256, f"{who}: J = {J} is more than 256")
+    _need(cov is None or (isinstance(cov, torch.Tensor) and tuple(cov.shape) == (T, N, J, 6)), f"{who}: cov must be [T,N,J,6]")
+    return T, N, J
+
+
+def bone_lengths(pose, cov, parent, mirror=None, floor=1e-3, want_dev=False, want_frames=False):
+    """pafuse_bone_lengths: pose [T,N,J,3] the finished per-frame pose of a video of N frames, cov [T,N,J,6] the covariance of
+    its hypotheses (finish_frames' "cov") or None (zeros), parent [J] the bone table (host integers: -1 or a joint below the
+    entry's own; h3wb.bone_tables), mirror [J] the left/right partners or None, floor in metres -> length [T,J]: per bone the
+    mean of its per-frame lengths, a frame weighing 1 / (u'E_j u + u'E_p u) - as far as its hypotheses agree ALONG the bone;
+    mirror partners pool their frames and get the same bits; NaN where a joint has no bone or no frame takes part
+    (pafuse_amd.bones states it).  want_dev / want_frames: -> (length, dev [T,J] the weighted standard deviation of the input's
+    bone length, frames [T,J] int32 the frames that took part), in that order, those asked for."""
+    lib = _lib.load()
+    T, N, J = _bone_operands("bone_lengths", pose, cov)
+    _need_floor("bone_lengths", floor)
+    par = bone_table(parent, J)                                       # refused on the host, before anything touches the device
+    mir = None if mirror is None else bone_table(mirror, J, mirror=True)
+    _need_tensors("bone_lengths", [pose] + ([] if cov is None else [cov]), ())
+    par = bone_table(par, J, pose.device)
+    mir = None if mir is None else bone_table(mir, J, pose.device, mirror=True)
+    length = torch.empty((T, J), device=pose.device, dtype=torch.float32)
+    dev = torch.empty_like(length) if want_dev else None
+    frames = torch.empty((T, J), device=pose.device, dtype=torch.int32) if want_frames else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(pose.device):
+        _lib.check(lib.pafuse_bone_lengths(pose.data_ptr(), ptr(cov), par.data_ptr(), ptr(mir), T, N, J, float(floor), length.data_ptr(),
+                                           ptr(dev), ptr(frames), _stream(pose)))
+    got = (length,) + ((dev,) if want_dev else ()) + ((frames,) if want_frames else ())
+    return got if len(got) > 1 else length
+
+
+def project_bones(pose, cov, parent, length, iterations=16, snap=True, floor=1e-3, want_code=False, want_resid=False, out=None):
+    """pafuse_bone_project: pose [T,N,J,3], cov [T,N,J,6] or None, parent [J] as in bone_lengths, length [T,J] (or [J]: the same
+    for every step) the lengths to hold - bone_lengths' or the caller's own, NaN: that bone is left alone - -> [T,N,J,3]: every
+    frame moved onto the lengths by `iterations` (0 .. 64) Jacobi sweeps of the covariance-weighted projection - both ends of a
+    wrong bone give way by the least Mahalanobis distance - and, with snap, an exact top-down pass behind them
+    (pafuse_amd.bones states it).  A joint that is part of no active bone keeps the input's bits; a joint without a bone (the
+    root) never moves.  16 sweeps and the 1 mm floor are defaults, not tuned values.  want_code: code [T,N,J] uint8 (1 moved
+    with a bone, 0 untouched, 3 untouched although a bone was asked of it); want_resid: resid [T,N,2] the largest |l - L| of
+    every frame before, and after on the values returned.  `out`: a [T,N,J,3] tensor to write into that shares no memory
+    with pose."""
+    lib = _lib.load()
+    T, N, J = _bone_operands("project_bones", pose, cov)
+    _need(not isinstance(iterations, bool) and isinstance(iterations, int) and 0 <= iterations <= 64,
+          f"project_bones: iterations must be an integer in 0 .. 64, got {iterations!r}")
+    _need(isinstance(snap, (bool, int)) and snap in (0, 1), f"project_bones: snap must be a bool, got {snap!r}")
+    _need_floor("project_bones", floor)
+    _need(isinstance(length, torch.Tensor) and tuple(length.shape) in ((T, J), (J,)), f"project_bones: length must be [T,J] = {(T, J)} (or [J]), got "
+          f"{tuple(length.shape) if isinstance(length, torch.Tensor) else type(length).__name__}")
+    par = bone_table(parent, J)
+    if length.dim() == 1:
+        length = length.unsqueeze(0).expand(T, J).contiguous()
+    if out is None:
+        out = torch.empty_like(pose)
+    _need(isinstance(out, torch.Tensor) and tuple(out.shape) == (T, N, J, 3), "project_bones: out must be [T,N,J,3]")
+    _need_tensors("project_bones", [pose, out, length] + ([] if cov is None else [cov]), ())
+    lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
+    _need(hi <= pose.data_ptr() or lo >= pose.data_ptr() + pose.numel() * 4, "project_bones: out may not alias pose")
+    par = bone_table(par, J, pose.device)
+    code = torch.empty((T, N, J), device=pose.device, dtype=torch.uint8) if want_code else None
+    resid = torch.empty((T, N, 2), device=pose.device, dtype=torch.float32) if want_resid else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(pose.device):
+        _lib.check(lib.pafuse_bone_project(pose.data_ptr(), ptr(cov), par.data_ptr(), length.data_ptr(), T, N, J, int(iterations), int(snap),
+                                           float(floor), out.data_ptr(), ptr(code), ptr(resid), _stream(pose)))
+    got = (out,) + ((code,) if want_code else ()) + ((resid,) if want_resid else ())
+    return got if len(got) > 1 else out
+
+
 # ------------------------------------------------------------------ missing 2-D detections, repaired before lifting
 REPAIR_OUTPUTS = {"x2d": ((2,), torch.float32), "conf": ((), torch.float32), "status": ((), torch.uint8)}
 _ANCHOR_CACHE_MAX = 16

@@ -22,6 +22,8 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::fit_trajectory(pose, x2d, cam, conf?)           the camera-space root of that pose: traj, wsum, resid per (t, frame)
   pafuse::smooth_trajectory(traj, weight?, radius)        a confidence-weighted local-linear filter along the frames
   pafuse::pose_smooth(pose, cov?, radius, floor)          that pose smoothed along the frames, weighted by the hypothesis covariance
+  pafuse::bone_lengths(pose, cov?, parent, mirror?, floor)   one length per bone from the whole video: length, dev, frames
+  pafuse::bone_project(pose, cov?, parent, length, iterations, snap, floor)   every frame moved onto those lengths: out, code, resid
   pafuse::repair_detections(x2d, conf, anchor?, radius, threshold)   missing 2-D detections filled along the frames, per joint
   pafuse::focal_sums(pose, x2d, cam, conf?)               the focal-length sums of that pose: (K, H, G, 1) per (t, frame)
   pafuse::focal_solve(state, cam)                         the focal length from them: focal, r2, frames, cam per t
@@ -523,6 +525,36 @@ def pose_smooth(pose: torch.Tensor, cov: Optional[torch.Tensor], radius: int, fl
 @pose_smooth.register_fake
 def _(pose, cov, radius, floor=1e-3):
     return [torch.empty_like(pose), pose.new_empty(pose.shape[:3], dtype=torch.uint8)]
+
+
+# ------------------------------------------------------------------ bone lengths held constant along a video
+@torch.library.custom_op("pafuse::bone_lengths", mutates_args=(), device_types="cuda")
+def bone_lengths(pose: torch.Tensor, cov: Optional[torch.Tensor], parent: List[int], mirror: Optional[List[int]] = None,
+                 floor: float = 1e-3) -> List[torch.Tensor]:
+    """pafuse_amd.ops.bone_lengths: pose [T,N,J,3], cov [T,N,J,6] or None, parent [J] host integers (-1 or a joint below the
+    entry's own), mirror [J] or None, floor > 0 (metres) -> [length [T,J], dev [T,J], frames [T,J] int32]."""
+    from . import ops
+    return list(ops.bone_lengths(pose, cov, parent, mirror, floor=floor, want_dev=True, want_frames=True))
+
+
+@bone_lengths.register_fake
+def _(pose, cov, parent, mirror=None, floor=1e-3):
+    T, J = pose.shape[0], pose.shape[2]
+    return [pose.new_empty((T, J)), pose.new_empty((T, J)), pose.new_empty((T, J), dtype=torch.int32)]
+
+
+@torch.library.custom_op("pafuse::bone_project", mutates_args=(), device_types="cuda")
+def bone_project(pose: torch.Tensor, cov: Optional[torch.Tensor], parent: List[int], length: torch.Tensor, iterations: int = 16,
+                 snap: bool = True, floor: float = 1e-3) -> List[torch.Tensor]:
+    """pafuse_amd.ops.project_bones: pose [T,N,J,3], cov [T,N,J,6] or None, parent [J] host integers, length [T,J], iterations
+    0 .. 64, snap, floor > 0 (metres) -> [the constrained pose [T,N,J,3], code [T,N,J] uint8, resid [T,N,2]]."""
+    from . import ops
+    return list(ops.project_bones(pose, cov, parent, length, iterations=iterations, snap=snap, floor=floor, want_code=True, want_resid=True))
+
+
+@bone_project.register_fake
+def _(pose, cov, parent, length, iterations=16, snap=True, floor=1e-3):
+    return [torch.empty_like(pose), pose.new_empty(pose.shape[:3], dtype=torch.uint8), pose.new_empty((*pose.shape[:2], 2))]
 
 
 # ------------------------------------------------------------------ missing 2-D detections, repaired before lifting
