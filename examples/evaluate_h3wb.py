@@ -17,6 +17,12 @@ the true one per video (H3WB knows its intrinsics: this is how the estimator can
 about RATE of the joints, detections.plant_dropouts - and `--repair [R]` repairs them on the device before the model sees them
 (harness.repair_detections; R in 1 .. 64, default 13); per video the joints per status and detections.repair_error are logged.
 Ground-truth 2-D has no dropouts: without the planting nobody can measure whether the repair helps on H3WB.
+`--corrupt-detections RATE:RUN:SIZE[:SEED]` and `--swap-detections RATE:RUN[:SEED]` (with `--frames`) plant WRONG detections with
+their confidence kept - runs of RUN frames displaced by SIZE (screen-normalised units) and runs of left/right pairs exchanged,
+detscreen.corrupt - and `--screen [R]` screens the detections on the device before the repair (harness.screen_detections; R in
+1 .. 64, default 13): outliers leave with confidence 0, swaps leave exchanged; per video the detections per status and
+detscreen.screen_error are logged.  With `--repair` the rejected detections are filled.  Whether the screen lowers the 3-D error
+needs a real checkpoint and has not been measured: this is the tool that measures it.
 `--path-weight L` (with `--frames --aggregate reproj|reproj_fit`, un-strided) scores the pick made coherent in time: per clip and
 joint one path through the hypotheses instead of every frame's own winner (harness.evaluate_frames(path_weight=...)).
 `--path-scope video` runs that path along the whole video instead, across clip seams and the pooled windows of `--stride S`
@@ -80,6 +86,16 @@ def main():
     ap.add_argument("--repair", type=int, default=None, nargs="?", const=13, metavar="R",
                     help="with --frames --drop-detections: repair the lost detections on the device along the frames within R "
                          "(1 .. 64, default 13) and log the repair error per video")
+    ap.add_argument("--corrupt-detections", default=None, metavar="RATE:RUN:SIZE[:SEED]",
+                    help="with --frames: plant wrong detections with their confidence kept - runs of RUN frames, about a share RATE of "
+                         "the joints, displaced by SIZE (screen-normalised units), seeded per video with SEED (default 0) + the video's number")
+    ap.add_argument("--swap-detections", default=None, metavar="RATE:RUN[:SEED]",
+                    help="with --frames: exchange left/right pairs of detections, confidences included, in runs of RUN frames at about "
+                         "a share RATE of the pairs")
+    ap.add_argument("--screen", type=int, default=None, nargs="?", const=13, metavar="R",
+                    help="with --frames and a planting: screen the observed detections on the device before the repair - outliers "
+                         "against the leave-one-out line within R (1 .. 64, default 13) rejected, left/right swaps exchanged back - "
+                         "and log the screen error per video")
     ap.add_argument("--path-weight", type=float, default=None, metavar="L",
                     help="with --frames --aggregate reproj or reproj_fit on un-strided clips: the pick coherent in time - per clip and "
                          "joint one path through the hypotheses, a jump costing L per metre (normalised screen length per metre; "
@@ -121,10 +137,25 @@ def main():
             assert len(fields) <= 3 and 0.0 <= drop[0] <= 1.0 and drop[1] >= 1
         except (ValueError, IndexError, AssertionError):
             ap.error("--drop-detections takes RATE:RUN[:SEED], RATE in 0 .. 1 and RUN >= 1 frames")
-    if (drop is not None or a.repair is not None) and not a.frames:
-        ap.error("--drop-detections and --repair need --frames")
-    if a.repair is not None and (drop is None or not 1 <= a.repair <= 64):
-        ap.error("--repair takes a radius in 1 .. 64 and needs --drop-detections (ground-truth 2-D has nothing to repair)")
+    corrupt = swap = None
+    try:
+        if a.corrupt_detections is not None:
+            fields = a.corrupt_detections.split(":")
+            corrupt = (float(fields[0]), int(fields[1]), float(fields[2]), int(fields[3]) if len(fields) > 3 else 0)
+            assert len(fields) <= 4 and 0.0 <= corrupt[0] <= 1.0 and corrupt[1] >= 1 and 0.0 < corrupt[2] < float("inf")
+        if a.swap_detections is not None:
+            fields = a.swap_detections.split(":")
+            swap = (float(fields[0]), int(fields[1]), int(fields[2]) if len(fields) > 2 else 0)
+            assert len(fields) <= 3 and 0.0 <= swap[0] <= 1.0 and swap[1] >= 1
+    except (ValueError, IndexError, AssertionError):
+        ap.error("--corrupt-detections takes RATE:RUN:SIZE[:SEED] and --swap-detections RATE:RUN[:SEED], RATE in 0 .. 1, RUN >= 1 frames, SIZE > 0")
+    planted = drop is not None or corrupt is not None or swap is not None
+    if (planted or a.repair is not None or a.screen is not None) and not a.frames:
+        ap.error("--drop-detections, --corrupt-detections, --swap-detections, --screen and --repair need --frames")
+    if a.screen is not None and (not planted or not 1 <= a.screen <= 64):
+        ap.error("--screen takes a radius in 1 .. 64 and needs a planting (ground-truth 2-D has nothing to screen)")
+    if a.repair is not None and (not (drop is not None or a.screen is not None) or not 1 <= a.repair <= 64):
+        ap.error("--repair takes a radius in 1 .. 64 and needs --drop-detections or --screen (ground-truth 2-D has nothing to repair)")
     if a.estimate_focal and not (a.frames and a.trajectory is not None):
         ap.error("--estimate-focal needs --frames --trajectory")
     args = config.load(a.config or None, a.overrides)
@@ -162,7 +193,7 @@ def main():
                              hypothesis_chunk=a.hypothesis_chunk, p2=bool(args.ft2d.p2), seam_profile=a.seam_profile,
                              focal="estimate" if a.estimate_focal else None, repair=a.repair, drop=drop, path_weight=a.path_weight,
                              path_scope=a.path_scope, pose_smooth=a.smooth_pose, pose_smooth_floor=a.smooth_pose_floor,
-                             bone_lengths=a.bone_lengths, bone_iterations=a.bone_iterations)
+                             bone_lengths=a.bone_lengths, bone_iterations=a.bone_iterations, corrupt=corrupt, swap=swap, screen=a.screen)
     else:
         h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
                       batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),

@@ -51,6 +51,14 @@ image corner - is filled along the frames from the frames within R in which it w
 a hand keypoint relative to its wrist; found keypoints are not touched, and a filled one keeps confidence 0, so the fits above go on
 ignoring it.  It writes test_3d_output_repaired.npy [frames,134] (0 observed, 1 filled, 2 held, 3 unfilled) and prints the counts.
 
+--screen [R] (default 13 frames; --screen-gate G, --screen-floor S) screens the FOUND keypoints first (harness.screen_detections): a
+keypoint the detector reported wrongly with a confidence - a wrist found on a passer-by, a face point on the background - lies
+far from the leave-one-out line through its neighbours within R frames; one farther than G robust scales of its joint gets
+confidence 0, which --repair then fills and every fit ignores, and a left ankle and a right ankle that changed labels are
+exchanged back.  It writes test_3d_output_screened.npy [frames,134] (0 accepted, 1 rejected, 2 swapped, 3 not found) and prints
+the counts.  A fixed-radius linear model, not a tracker: a wrong person held for longer than about R frames is kept.  G = 4 and
+S = 0.005 are defaults, not tuned values.
+
 --path-weight L (with --reproj-fit) makes that pick coherent in time (infer_sequence(path_weight=...)): per clip and joint the path
 through the hypotheses that minimises the reprojection error plus L times the distance the joint jumps relative to the mean pose,
 instead of every frame's own winner.  It works per clip - the clip seams stay - and every joint written is still some hypothesis's.
@@ -141,7 +149,16 @@ def main():
                          "relative to the nose or its wrist; writes test_3d_output_repaired.npy [frames,134] (0 observed, 1 filled, "
                          "2 held, 3 unfilled) and prints the four counts")
     ap.add_argument("--repair-threshold", type=float, default=0.0, metavar="C",
-                    help="with --repair: a keypoint counts as found if its confidence is above C (default 0)")
+                    help="with --repair or --screen: a keypoint counts as found if its confidence is above C (default 0)")
+    ap.add_argument("--screen", type=int, default=None, nargs="?", const=13, metavar="R",
+                    help="screen the found keypoints on the device before the repair: one farther from the leave-one-out line through "
+                         "its neighbours within R frames (1 .. 64, default 13) than --screen-gate robust scales gets confidence 0, and a "
+                         "left/right pair that fits exchanged is exchanged; writes test_3d_output_screened.npy [frames,134] (0 accepted, "
+                         "1 rejected, 2 swapped, 3 not found) and prints the four counts")
+    ap.add_argument("--screen-gate", type=float, default=4.0, metavar="G",
+                    help="with --screen: the width of the gate in scales (finite, > 0; default 4, not a tuned value)")
+    ap.add_argument("--screen-floor", type=float, default=0.005, metavar="S",
+                    help="with --screen: the smallest scale in screen-normalised units (finite, > 0; default 0.005, not a tuned value)")
     ap.add_argument("--path-weight", type=float, default=None, metavar="L",
                     help="with --reproj-fit (no --stride, no --hypothesis-chunk): make the pick coherent in time - per clip and joint "
                          "one path through the hypotheses, a jump costing L per metre (normalised screen length per metre; about "
@@ -187,6 +204,10 @@ def main():
         ap.error("--repair takes a radius in 1 .. 64 frames")
     if not 0.0 <= a.repair_threshold < float("inf"):
         ap.error("--repair-threshold takes a finite confidence >= 0")
+    if a.screen is not None and not 1 <= a.screen <= 64:
+        ap.error("--screen takes a radius in 1 .. 64 frames")
+    if not (0.0 < a.screen_gate < float("inf") and 0.0 < a.screen_floor < float("inf")):
+        ap.error("--screen-gate and --screen-floor take finite values > 0")
     if a.estimate_focal and a.aggregate != "mean":
         ap.error("--estimate-focal needs --aggregate mean (one pose per frame)")
     if a.trajectory is not None and (a.aggregate != "mean" or not (a.trajectory > 0 or a.estimate_focal)):
@@ -226,6 +247,13 @@ def main():
     pixels, conf = harness.load_pifpaf_keypoints(a.keypoints, args.data.num_kps, with_conf=True)
     keypoints = h3wb.normalize_screen_coordinates(pixels[..., :2], w=a.width, h=a.height).astype(np.float32)
     save = lambda name, t: np.save(os.path.join(a.out, name), t.numpy(), allow_pickle=True)
+    if a.screen is not None:             # once, up front and before the repair, as infer_sequence(screen=...) would
+        screened = harness.screen_detections(keypoints, conf, kps_left=kps_left, kps_right=kps_right, radius=a.screen, gate=a.screen_gate,
+                                             floor=a.screen_floor, threshold=a.repair_threshold)
+        keypoints, conf = screened["x2d"].numpy(), screened["conf"].numpy()
+        save("test_3d_output_screened.npy", screened["status"])
+        print("detections accepted %d, rejected %d, swapped %d, not found %d (a rejected one keeps its coordinates and gets confidence 0: "
+              "--repair fills it)" % tuple(screened["counts"].tolist()))
     if a.repair is not None:             # once, up front: every call below sees the repaired pair, as infer_sequence(repair=...) would
         fixed = harness.repair_detections(keypoints, conf, dataset=dataset, radius=a.repair, threshold=a.repair_threshold)
         keypoints, conf = fixed["x2d"].numpy(), fixed["conf"].numpy()

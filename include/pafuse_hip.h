@@ -40,6 +40,8 @@
  *                            detections, and a confidence-weighted local-linear filter along the frames
  *   pafuse_detections_repair missing 2-D detections filled along the frames by that filter, per joint, a hand or face joint
  *                            relative to the joint it hangs on - the input side, before lifting
+ *   pafuse_detections_screen observed detections screened in front of it: outliers against a leave-one-out local line rejected
+ *                            by a robust per-joint scale, left/right swaps exchanged back
  *   pafuse_frames_focal_sums / pafuse_focal_solve  the focal length that fit needs, estimated from the same pose and
  *                            detections: one value per video, with the fraction of the signal it explains
  *   pafuse_frame_errors / pafuse_frame_errors_reduce  that per-frame pose and root scored against ground truth: position,
@@ -882,6 +884,43 @@ int pafuse_detections_repair(const float *x2d /* [N,J,2] */, const float *conf /
                              const int32_t *anchor /* [J] device, or NULL */, int32_t N, int32_t J, int32_t radius /* 1..64 */,
                              float threshold /* >= 0 */, float *out /* [N,J,2], may not alias x2d */,
                              float *conf_out /* [N,J] or NULL, may not alias conf */, uint8_t *status /* [N,J] */, void *stream);
+
+/* OBSERVED 2-D detections screened in front of that repair: outliers rejected, left/right swaps undone, per joint along the
+ * frames (pafuse_amd/detscreen.py states the arithmetic, operation for operation).  observed(n, j) is the
+ * repair's rule.  All in fp64 with contraction off, rounded once where a value is stored.
+ * The partner rule.  mirror [J] names every joint's mirror joint.  Joint j has the partner q = mirror[j] iff 0 <= q < J, q != j
+ * and mirror[q] == j; mirror[q] is read only for an in-range q, so no table causes a read out of bounds; a NULL table has no
+ * pairs; this entry does NOT refuse a table whose entries the rule drops (the Python layers do).
+ * Residual of (n, j) against an accepted set acc: the filter of pafuse_trajectory_smooth, omega = g * conf[m,j], over the frames
+ * m = max(0, n - r) .. min(N - 1, n + r), m != n, with acc[m,j] - leave one out.  The fit exists iff that filter finds a line
+ * (two frames or more, D finite and > 0) and >= support frames took part; e = float(sqrt(dx*dx + dy*dy)) from the line's
+ * value at d = 0; NaN where (n, j) is not observed or has no fit.
+ * acc_0 = observed; for p = 1 .. passes: acc_p = fit ? double(e_p) <= tau_j : acc_{p-1}, e_p against acc_{p-1} (a Jacobi
+ * update; every observed frame is re-tested in every pass, which re-admits the neighbours of a gross outlier).
+ * tau_j = double(gate) * max(1.4826 * double(med_j), double(floor)), med_j the exact lower median of the values of e_1[:, j]
+ * that are not NaN (rank (c - 1) / 2 of c, +inf last; 0 without a value), found by a radix select on the bit patterns.
+ * One more evaluation against acc_passes gives e_self and, for a pair both observed at n, e_cross(n, j): the partner's
+ * detection against j's line.  The pair's frame is swapped iff both are observed, one of them is not accepted, and for both
+ * joints double(e_cross) <= tau and e_cross < e_self.
+ *   out      [N,J,2]  the partner's detection where swapped, else the input's bits
+ *   conf_out [N,J]    the partner's confidence where swapped, 0 where rejected, else the input's bits
+ *   status   [N,J]    0 accepted, 1 rejected, 2 swapped, 3 not observed (every bit kept)
+ *   resid    [N,J]    (NULL: not wanted) e_self, NaN where there is none
+ *   scale    [J]      (NULL: not wanted) float(tau_j)
+ *   workspace         pafuse_detections_screen_workspace_bytes(N, J) bytes (0 for a size < 1), 8-byte aligned
+ * passes + 3 launches on the stream: one thread per (n, j), but the scales, one wave per joint.  No atomics, no host
+ * synchronisation, bit-reproducible.  gate 4, floor 0.005, passes 3 and support 3 are defaults, not tuned values.
+ * Refused (PAFUSE_E_ARG) before any HIP call: a null x2d / conf / out / conf_out / status, N or J < 1, radius outside 1 .. 64,
+ * passes outside 1 .. 8, support outside 2 .. 129, a gate or floor that is not finite and > 0, a threshold that is not finite
+ * or < 0, out == x2d, conf_out == conf, a null, short or misaligned workspace, a grid out of range. */
+size_t pafuse_detections_screen_workspace_bytes(int32_t N, int32_t J);
+int pafuse_detections_screen(const float *x2d /* [N,J,2] */, const float *conf /* [N,J] */,
+                             const int32_t *mirror /* [J] device, or NULL */, int32_t N, int32_t J, int32_t radius /* 1..64 */,
+                             int32_t passes /* 1..8 */, int32_t support /* 2..129 */, float threshold /* >= 0 */,
+                             float gate /* > 0 */, float floor /* > 0 */, float *out /* [N,J,2], may not alias x2d */,
+                             float *conf_out /* [N,J], may not alias conf */, uint8_t *status /* [N,J] */,
+                             float *resid /* [N,J] or NULL */, float *scale /* [J] or NULL */, void *workspace,
+                             size_t workspace_bytes, void *stream);
 
 /* The per-frame pose smoothed along the frames, every frame weighted by the inverse of its hypothesis covariance
  * (pafuse_amd/posesmooth.py states the arithmetic, operation for operation).  A fixed-radius

@@ -186,6 +186,9 @@ SIGNATURES = {
     "pafuse_frames_root_fit": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p] * 4),
     "pafuse_trajectory_smooth": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p] * 2),
     "pafuse_detections_repair": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_float] + [C.c_void_p] * 4),
+    "pafuse_detections_screen_workspace_bytes": (C.c_size_t, [C.c_int32] * 2),
+    "pafuse_detections_screen": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_float] * 3 + [C.c_void_p] * 6 +
+                                 [C.c_size_t, C.c_void_p]),
     "pafuse_pose_smooth_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "pafuse_pose_smooth": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 4 + [C.c_float] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     "pafuse_bone_lengths": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float] + [C.c_void_p] * 4),

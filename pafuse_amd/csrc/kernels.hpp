@@ -4269,6 +4269,192 @@ __global__ void __launch_bounds__(256) detections_repair_kernel(const Detections
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// Observed detections screened in front of the repair: outliers rejected, left/right swaps undone (DESIGN.md section 6o;
+// statement: pafuse_amd/detscreen.py, which fixes every operation and its order - this code follows it operation for
+// operation).  The host runs, on one stream: the residual kernel against acc_0 = observed (e_1), the scale kernel (tau from
+// the median of e_1), the residual kernel once per further pass (it gates its own residual: acc_p) and once more against
+// acc_K (e_self, e_cross), then the finish.  Which set a residual launch reads is its `source`:
+//   SCREEN_OBSERVED  acc_0:  observed(m, j)
+//   SCREEN_FIRST     acc_1:  observed(m, j) and not (e_1[m,j] > tau_j) - an untested frame, e_1 NaN, keeps acc_0; a tested e
+//                            is never NaN - formed on the fly, so pass 1 needs no launch of its own behind the scale kernel
+//   SCREEN_STORED    acc_p:  the bytes the launch before wrote
+// acc is double-buffered: a launch reads p.acc and writes p.acc_next, never one element in both.
+enum ScreenSource { SCREEN_OBSERVED = 0, SCREEN_FIRST = 1, SCREEN_STORED = 2 };
+
+struct DetectionsScreenParams {
+    const float* x2d;        // [N,J,2]
+    const float* conf;       // [N,J]
+    const int32_t* mirror;   // [J] or null
+    const float* e1;         // [N,J] pass 1's residuals (read with SCREEN_FIRST)
+    const double* tau;       // [J]
+    const uint8_t* acc;      // [N,J] (read with SCREEN_STORED)
+    uint8_t* acc_next;       // [N,J] or null: this launch's gated set
+    float* e;                // [N,J] or null: this launch's residual
+    float* e_cross;          // [N,J] or null: the partner's detection against this joint's line
+    const float* e_self;     // finish: [N,J]
+    const float* e_cross_in; // finish: [N,J] or null (no table)
+    float* out;              // finish: [N,J,2]
+    float* conf_out;         // finish: [N,J]
+    uint8_t* status;         // finish: [N,J]
+    float* resid;            // finish: [N,J] or null
+    int N, J, radius, support, source;
+    float threshold;
+};
+
+__device__ __forceinline__ bool detection_observed(float c, float x, float y, float thr) { return c > thr && isfinite(x) && isfinite(y); }
+
+// the partner of joint j by the rule of the statement, -1 without one; mirror[q] is read only for an in-range q
+__device__ __forceinline__ int screen_partner(const int32_t* mirror, int j, int J) {
+    if (!mirror) return -1;
+    const int q = mirror[j];
+    return q >= 0 && q < J && q != j && mirror[q] == j ? q : -1;
+}
+
+// acc_source(m, j), em = m*J + j, given observed(m, j)
+__device__ __forceinline__ bool screen_accepted(const DetectionsScreenParams& p, int64_t em, int j, bool observed) {
+    if (p.source == SCREEN_OBSERVED) return observed;
+    if (p.source == SCREEN_FIRST) return observed && !((double)p.e1[em] > p.tau[j]);
+    return p.acc[em] != 0;
+}
+
+// One thread per (n, j), e = n*J + j with j fastest - the repair's mapping.  An observed (n, j) walks m = max(0, n - r) ..
+// min(N - 1, n + r), m != n, and feeds LineFilter<2> with the accepted frames; the fit exists iff LINE_FIT with >= support
+// frames.  e = float(sqrt(dx*dx + dy*dy)) from the line's value at d = 0, NaN without a fit or an observation; with acc_next:
+// the gate, fit ? double(e) <= tau_j : acc(n, j); with e_cross and a partner observed at n: its detection's distance from the
+// same line.  fp64, contraction off, rounded once.  No LDS, no atomics, no scratch.
+__global__ void __launch_bounds__(256) detections_residual_kernel(const DetectionsScreenParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)p.N * p.J) return;
+    const int J = p.J, j = (int)(e % J), n = (int)(e / J), r = p.radius;
+    const float thr = p.threshold, qnan = __builtin_nanf("");
+    const float c = p.conf[e], x = p.x2d[e * 2], y = p.x2d[e * 2 + 1];
+    float res = qnan, cross = qnan;
+    bool next = false;
+    if (detection_observed(c, x, y, thr)) {
+        LineFilter<2> f(r);
+        const int lo = max(0, n - r), hi = min(p.N - 1, n + r);
+        for (int m = lo; m <= hi; ++m) {
+            if (m == n) continue;
+            const int64_t em = (int64_t)m * J + j;
+            const float cm = p.conf[em], xm = p.x2d[em * 2], ym = p.x2d[em * 2 + 1];
+            if (!screen_accepted(p, em, j, detection_observed(cm, xm, ym, thr))) continue;
+            const double ys[2] = {(double)xm, (double)ym};
+            f.add(m - n, (double)cm, ys);
+        }
+        const bool fit = f.kind() == LINE_FIT && f.cnt >= p.support;
+        next = screen_accepted(p, e, j, true);
+        if (fit) {
+            const double px = f.value(0), py = f.value(1);
+            const double dx = (double)x - px, dy = (double)y - py;
+            res = (float)sqrt(dx * dx + dy * dy);
+            if (p.acc_next) next = (double)res <= p.tau[j];
+            const int q = p.e_cross ? screen_partner(p.mirror, j, J) : -1;
+            if (q >= 0) {
+                const int64_t eq = (int64_t)n * J + q;
+                const float cq = p.conf[eq], xq = p.x2d[eq * 2], yq = p.x2d[eq * 2 + 1];
+                if (detection_observed(cq, xq, yq, thr)) {
+                    const double ux = (double)xq - px, uy = (double)yq - py;
+                    cross = (float)sqrt(ux * ux + uy * uy);
+                }
+            }
+        }
+    }
+    if (p.e) p.e[e] = res;
+    if (p.acc_next) p.acc_next[e] = next ? 1 : 0;
+    if (p.e_cross) p.e_cross[e] = cross;
+}
+
+// The robust scale of every joint: one wave per joint (wave_item), lanes over the frames, the exact lower median of the
+// values of e_1[:, j] that are not NaN by a radix select on their bit patterns - non-negative floats order as unsigned
+// integers, +inf behind every finite value.  c values: the wanted rank is (c - 1) / 2.  From bit 31 down: the candidates
+// that share the prefix found so far and have a 0 at the bit are counted across the wave - every compare is a ballot, its
+// population count a scalar add: integers, no order, no sort, no atomics, no LDS, no barrier - and the half that holds the
+// rank is kept.  tau_j = double(gate) * max(1.4826 * double(med), double(floor)), med = 0 without a value; scale = float(tau).
+struct DetectionsScaleParams {
+    const float* e1;   // [N,J]
+    double* tau;       // [J]
+    float* scale;      // [J] or null
+    int N, J;
+    float gate, floor;
+};
+
+__global__ void __launch_bounds__(256) detections_scale_kernel(const DetectionsScaleParams p) {
+#pragma clang fp contract(off)
+    const int64_t j = wave_item();
+    if (j >= p.J) return;                      // wave-uniform
+    const int lane = wave_lane(), N = p.N, J = p.J;
+    const uint32_t* keys = reinterpret_cast<const uint32_t*>(p.e1) + j;
+    const uint32_t none = 0x7fc00000u;         // a NaN: takes no part
+    // one sweep over the column: how many values pass `test`.  Eight loads (512 frames) are in flight before the first
+    // compare - the loads of a sweep do not depend on each other, only the next bit depends on the sweep's count
+    auto count = [&](auto test) {
+        int total = 0;
+        for (int64_t base = 0; base < N; base += 64 * 8) {   // 64-bit: N may be near 2^31
+            uint32_t k[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int64_t m = base + u * 64 + lane;
+                k[u] = m < N ? keys[m * J] : none;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) total += __popcll(__ballot((k[u] & 0x7fffffffu) <= 0x7f800000u && test(k[u])));
+        }
+        return total;
+    };
+    const int c = count([](uint32_t) { return true; });
+    uint32_t prefix = 0, known = 0;
+    int rank = (c - 1) / 2;
+    if (c > 0) {
+        for (int b = 31; b >= 0; --b) {
+            const uint32_t bit = 1u << b;
+            const int zeros = count([&](uint32_t k) { return (k & known) == prefix && !(k & bit); });
+            if (rank >= zeros) rank -= zeros, prefix |= bit;
+            known |= bit;
+        }
+    }
+    const double med = (double)__uint_as_float(prefix);
+    const double tau = (double)p.gate * fmax(1.4826 * med, (double)p.floor);
+    if (lane == 0) {
+        p.tau[j] = tau;
+        if (p.scale) p.scale[j] = (float)tau;
+    }
+}
+
+// One thread per (n, j): the swap decided from its own and its partner's e_self, e_cross, acc_K and tau - both joints of a
+// pair evaluate the same symmetric expression - and the outputs written.  Not observed: status 3, every bit kept.  Swapped:
+// status 2, the partner's detection and confidence.  Else acc_K false: status 1, confidence 0.  Else status 0, the same bits.
+__global__ void __launch_bounds__(256) detections_screen_finish_kernel(const DetectionsScreenParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)p.N * p.J) return;
+    const int J = p.J, j = (int)(e % J), n = (int)(e / J);
+    const float thr = p.threshold;
+    const float c = p.conf[e], x = p.x2d[e * 2], y = p.x2d[e * 2 + 1];
+    float ox = x, oy = y, oc = c, res = __builtin_nanf("");
+    int st = 3;
+    if (detection_observed(c, x, y, thr)) {
+        const bool acc = screen_accepted(p, e, j, true);
+        res = p.e_self[e];
+        st = acc ? 0 : 1;
+        const int q = p.e_cross_in ? screen_partner(p.mirror, j, J) : -1;
+        if (q >= 0) {
+            const int64_t eq = (int64_t)n * J + q;
+            const float cq = p.conf[eq], xq = p.x2d[eq * 2], yq = p.x2d[eq * 2 + 1];
+            if (detection_observed(cq, xq, yq, thr)) {
+                const bool accq = screen_accepted(p, eq, q, true);
+                const float xs = p.e_cross_in[e], xo = p.e_cross_in[eq], so = p.e_self[eq];
+                const bool ok = (double)xs <= p.tau[j] && xs < res, okq = (double)xo <= p.tau[q] && xo < so;
+                if ((!acc || !accq) && ok && okq) st = 2, ox = xq, oy = yq, oc = cq;
+            }
+        }
+        if (st == 1) oc = 0.f;
+    }
+    p.out[e * 2] = ox, p.out[e * 2 + 1] = oy, p.conf_out[e] = oc, p.status[e] = (uint8_t)st;
+    if (p.resid) p.resid[e] = res;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // The per-frame pose smoothed along the frames, every frame weighted by the inverse of its hypothesis covariance (DESIGN.md
 // section 6m; statement: pafuse_amd/posesmooth.py, which fixes every operation and its order - this code follows it
 // operation for operation).  Row (t, m, j): Sigma + floor^2*I from the six covariance entries (null: zeros), its cofactors

@@ -2335,6 +2335,64 @@ int pafuse_detections_repair(const float* x2d, const float* conf, const int32_t*
     return PAFUSE_OK;
 }
 
+// observed 2-D detections screened in front of the repair (detections_residual_kernel, detections_scale_kernel,
+// detections_screen_finish_kernel): pass 1's residuals, the scales, passes 2 .. K each gating its own residual, the evaluation
+// against acc_K, the finish - passes + 3 launches on the stream; the argument checks come before the first HIP call.
+// Workspace: tau [J] fp64, then e_1, e_self, e_cross [N,J] fp32, then the two acc buffers [N,J] bytes.
+size_t pafuse_detections_screen_workspace_bytes(int32_t N, int32_t J) {
+    return N < 1 || J < 1 ? 0 : (size_t)J * sizeof(double) + (size_t)N * (size_t)J * (3 * sizeof(float) + 2);
+}
+
+int pafuse_detections_screen(const float* x2d, const float* conf, const int32_t* mirror, int32_t N, int32_t J, int32_t radius,
+                             int32_t passes, int32_t support, float threshold, float gate, float floor, float* out, float* conf_out,
+                             uint8_t* status, float* resid, float* scale, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x2d || !conf || !out || !conf_out || !status)
+        return fail(PAFUSE_E_ARG, "detections_screen: x2d, conf, out, conf_out and status are needed (mirror, resid, scale may be null)");
+    if (N < 1 || J < 1) return fail(PAFUSE_E_ARG, "detections_screen: bad size (N=%d J=%d)", N, J);
+    if (radius < 1 || radius > 64) return fail(PAFUSE_E_ARG, "detections_screen: radius %d outside 1 .. 64", radius);
+    if (passes < 1 || passes > 8) return fail(PAFUSE_E_ARG, "detections_screen: passes %d outside 1 .. 8", passes);
+    if (support < 2 || support > 129) return fail(PAFUSE_E_ARG, "detections_screen: support %d outside 2 .. 129", support);
+    if (!std::isfinite(threshold) || threshold < 0.f) return fail(PAFUSE_E_ARG, "detections_screen: threshold %g is not finite and >= 0", (double)threshold);
+    if (!std::isfinite(gate) || !(gate > 0.f)) return fail(PAFUSE_E_ARG, "detections_screen: gate %g is not finite and > 0", (double)gate);
+    if (!std::isfinite(floor) || !(floor > 0.f)) return fail(PAFUSE_E_ARG, "detections_screen: floor %g is not finite and > 0", (double)floor);
+    if (out == x2d) return fail(PAFUSE_E_ARG, "detections_screen: out may not alias x2d (every launch reads the input)");
+    if (conf_out == conf) return fail(PAFUSE_E_ARG, "detections_screen: conf_out may not alias conf (every launch reads the confidences)");
+    const int64_t rows = (int64_t)N * J;      // the grid first: within it the workspace size cannot overflow
+    if ((rows + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "detections_screen: grid out of range");
+    const size_t need = pafuse_detections_screen_workspace_bytes(N, J);
+    if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 8)
+        return fail(PAFUSE_E_ARG, "detections_screen: the workspace must hold %zu bytes, 8-byte aligned (pafuse_detections_screen_workspace_bytes)", need);
+    unsigned waves;
+    if (int rc = wave_grid("detections_screen", J, waves)) return rc;   // one wave per joint
+    StreamDevice on_stream_device(stream);
+    double* tau = (double*)workspace;
+    float* e1 = (float*)(tau + J);
+    float *e_self = e1 + rows, *e_cross = e_self + rows;
+    uint8_t* acc[2] = {(uint8_t*)(e_cross + rows), (uint8_t*)(e_cross + rows) + rows};
+    const unsigned grid = blocks_for(rows);
+    const hipStream_t s = (hipStream_t)stream;
+    DetectionsScreenParams m{};
+    m.x2d = x2d, m.conf = conf, m.mirror = mirror, m.e1 = e1, m.tau = tau;
+    m.N = N, m.J = J, m.radius = radius, m.support = support, m.threshold = threshold;
+    m.source = SCREEN_OBSERVED, m.e = e1;                                  // pass 1: e_1 against acc_0
+    if (int rc = launch<detections_residual_kernel>("detections_residual_kernel", grid, 256, 0, s, m)) return rc;
+    DetectionsScaleParams sc{};
+    sc.e1 = e1, sc.tau = tau, sc.scale = scale, sc.N = N, sc.J = J, sc.gate = gate, sc.floor = floor;
+    if (int rc = launch<detections_scale_kernel>("detections_scale_kernel", waves, 256, 0, s, sc)) return rc;
+    m.e = nullptr, m.source = SCREEN_FIRST;                                // acc_1 is formed from e_1 and tau where it is read
+    for (int pass = 2; pass <= passes; ++pass) {                           // reads acc_{pass-1}, writes acc_pass
+        m.acc_next = acc[pass & 1];
+        if (int rc = launch<detections_residual_kernel>("detections_residual_kernel", grid, 256, 0, s, m)) return rc;
+        m.source = SCREEN_STORED, m.acc = m.acc_next;
+    }
+    m.acc_next = nullptr, m.e = e_self, m.e_cross = mirror ? e_cross : nullptr;   // against acc_K
+    if (int rc = launch<detections_residual_kernel>("detections_residual_kernel", grid, 256, 0, s, m)) return rc;
+    m.e = nullptr, m.e_cross = nullptr;
+    m.e_self = e_self, m.e_cross_in = mirror ? e_cross : nullptr;
+    m.out = out, m.conf_out = conf_out, m.status = status, m.resid = resid;
+    return launch<detections_screen_finish_kernel>("detections_screen_finish_kernel", grid, 256, 0, s, m);
+}
+
 // the per-frame pose smoothed along the frames with the inverse hypothesis covariance as matrix weight (pose_precision_kernel,
 // then pose_smooth_kernel, on the stream); the argument checks come before the first HIP call
 size_t pafuse_pose_smooth_workspace_bytes(int32_t T, int32_t N, int32_t J) {

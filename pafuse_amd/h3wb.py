@@ -300,7 +300,8 @@ def evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, batc
 def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
                     batch_size=2, group=None, log=print, action=None, hypothesis_chunk=None, p2=False, seam_profile=False, focal=None,
                     repair=None, drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None,
-                    pose_smooth_floor=1e-3, bone_lengths=None, bone_iterations=16):
+                    pose_smooth_floor=1e-3, bone_lengths=None, bone_iterations=16, corrupt=None, swap=None, screen=None,
+                    screen_gate=4.0, screen_floor=0.005):
     """The frame-level evaluation of every video, looped like :func:`evaluate`: harness.evaluate_frames per (camera, sequence) -
     one pose per video frame (``aggregate``, ``stride``; None: un-strided clips laid end to end), optionally its fitted
     camera-space root (``trajectory``: True or a smoothing radius) - scored on the device; the sums and counts added over the
@@ -322,10 +323,20 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
     constant along each video (harness.evaluate_frames): per video the mean bone-length standard deviation of the free and of
     the constrained pose and the largest difference of the held lengths from the ground truth's are logged - what it buys on
     a real checkpoint has not been measured either.
+    ``corrupt=(rate, run, size, seed)`` and ``swap=(rate, run, seed)`` plant wrong detections with their confidence kept - displaced
+    runs and exchanged left/right pairs (detscreen.corrupt, seed + the video's number) - and ``screen`` (a radius 1 .. 64;
+    ``screen_gate``, ``screen_floor``) screens the detections on the device before the repair (harness.evaluate_frames); per
+    video the detections per screen status are logged and, with a planting, detscreen.screen_error: the planted outliers and
+    swaps found and missed and the false rejects and swaps, overall and per part.  Whether the screen lowers the 3-D error needs
+    a real checkpoint and has not been measured.
     On synthetic weights the numbers mean nothing."""
-    from . import detections, harness
+    from . import detections, detscreen, harness
     if drop is not None and (not isinstance(drop, (tuple, list)) or len(drop) != 3):
         raise ValueError(f"drop must be (rate, run, seed), got {drop!r}")
+    if corrupt is not None and (not isinstance(corrupt, (tuple, list)) or len(corrupt) != 4):
+        raise ValueError(f"corrupt must be (rate, run, size, seed), got {corrupt!r}")
+    if swap is not None and (not isinstance(swap, (tuple, list)) or len(swap) != 3):
+        raise ValueError(f"swap must be (rate, run, seed), got {swap!r}")
     sums = counts = prof_s = prof_c = None
     for video, (cam, seq_3d, seq_2d) in enumerate(iter_sequences(cams, poses_3d, poses_2d)):
         got = harness.evaluate_frames(model, dataset, seq_2d[0].astype("float32"), seq_3d[0].astype("float32"),
@@ -335,15 +346,32 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
                                       drop=None if drop is None else (drop[0], drop[1], int(drop[2]) + video),
                                       repair_threshold=repair_threshold, path_weight=path_weight, path_scope=path_scope,
                                       pose_smooth=pose_smooth, pose_smooth_floor=pose_smooth_floor, bone_lengths=bone_lengths,
-                                      bone_iterations=bone_iterations)
+                                      bone_iterations=bone_iterations,
+                                      corrupt=None if corrupt is None else (corrupt[0], corrupt[1], corrupt[2], int(corrupt[3]) + video),
+                                      swap=None if swap is None else (swap[0], swap[1], int(swap[2]) + video), screen=screen,
+                                      screen_gate=screen_gate, screen_floor=screen_floor)
         if bone_lengths is not None:
             held, got = got[-1], got[:-1]
             gap = (held["bone_length"].double() - held["bone_length_gt"].double()).abs()
             log("video %d: bone-length std (mm, mean over the bones) free %s -> constrained %s; held lengths vs ground truth: max %.1f mm"
                 % (video, ["%.2f" % v for v in held["bone_dev_free"].tolist()], ["%.2f" % v for v in held["bone_dev"].tolist()],
                    float(gap[~gap.isnan()].max()) * 1000.0 if bool((~gap.isnan()).any()) else float("nan")))
-        if repair is not None or drop is not None:
+        if repair is not None or drop is not None or corrupt is not None or swap is not None or screen is not None:
             seen, got = got[-1], got[:-1]
+            if "screened" in seen:
+                log("video %d : detections accepted %d, rejected %d, swapped %d, not observed %d"
+                    % ((video,) + tuple(detscreen.counts(seen["screened"].numpy()))))
+                if "planted_out" in seen:
+                    err = detscreen.screen_error(seen["screened"].numpy(), seen["planted_out"].numpy(), seen["planted_swap"].numpy(),
+                                                 parts=dataset.parts_joint_indices)
+                    for name, e in [("all", err)] + list(err["parts"].items()):
+                        log("video %d : screen error %s: outliers found %d, missed %d, false rejects %d of %d untouched; "
+                            "swapped detections found %d, missed %d, false swaps %d"
+                            % (video, name, e["out_found"], e["out_missed"], e["false_rejects"], e["untouched"], e["swap_found"],
+                               e["swap_missed"], e["false_swaps"]))
+            elif "planted_out" in seen:
+                log("video %d : %d outliers and %d swapped detections planted, none screened"
+                    % (video, int(seen["planted_out"].sum()), int(seen["planted_swap"].sum())))
             if "status" in seen:
                 log("video %d : detections observed %d, filled %d, held %d, unfilled %d" % ((video,) + tuple(detections.counts(seen["status"].numpy()))))
             if "status" in seen and "lost" in seen:

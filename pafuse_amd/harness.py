@@ -107,11 +107,62 @@ def repair_detections(seq_2d, conf, dataset=None, anchor=None, radius=13, thresh
     return out
 
 
+def _screen_radius(screen, gate=4.0, floor=0.005, name="screen"):
+    """infer_sequence's `screen`, `screen_gate` and `screen_floor`: None -> None, an integer r in 1 .. 64 -> r; gate and floor
+    finite and > 0"""
+    if screen is None:
+        return None
+    if isinstance(screen, bool) or not isinstance(screen, int) or not 1 <= screen <= 64:
+        raise ValueError(f"{name} must be None or a radius in 1 .. 64 (frames), got {screen!r}")
+    for key, v in (("gate", gate), ("floor", floor)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < float(v) < float("inf"):
+            raise ValueError(f"{name}_{key} must be finite and > 0, got {v!r}")
+    return screen
+
+
+def _screen_detections(seq_2d, conf, mirror, radius, gate, floor, threshold, dev, passes=3, support=3):
+    """CPU or device tensors seq_2d [N,J,2], conf [N,J] -> ops.screen_detections' dict on the device"""
+    from . import ops
+    return ops.screen_detections(seq_2d.to(dev).contiguous(), conf.to(dev).contiguous(), mirror=mirror, radius=radius, gate=float(gate),
+                                 floor=float(floor), passes=passes, support=support, threshold=threshold)
+
+
+@torch.no_grad()
+def screen_detections(seq_2d, conf, kps_left=None, kps_right=None, mirror=None, radius=13, gate=4.0, floor=0.005, passes=3,
+                      support=3, threshold=0.0, device="cuda"):
+    """Observed 2-D detections screened on the device, in front of :func:`repair_detections` (pafuse_amd.detscreen;
+    ops.screen_detections): ``seq_2d`` [N,J,2] screen-normalised detections, ``conf`` [N,J] their confidences.  Per joint and
+    along the frames, every observed detection is compared with the leave-one-out local line through its accepted neighbours
+    within ``radius``; one farther from it than ``gate`` robust scales (1.4826 times the median residual of the joint, at least
+    ``floor``) is REJECTED - it leaves with confidence 0, so the repair fills it and every fit ignores it.  All frames are
+    re-tested over ``passes`` passes, which re-admits the neighbours of a gross outlier.  ``kps_left`` / ``kps_right`` (paired by
+    position) or ``mirror`` [J] name the mirror pairs: where one of a pair is rejected and EXCHANGING the two puts both within
+    their gates, the pair leaves exchanged, confidences included - a left/right swap undone.  Returns a dict of CPU tensors:
+    ``"x2d"`` [N,J,2], ``"conf"`` [N,J], ``"status"`` [N,J] uint8 (0 accepted, 1 rejected, 2 swapped, 3 not observed),
+    ``"resid"`` [N,J], ``"scale"`` [J] and ``"counts"`` [4] int64, the detections per status.  gate, floor, passes and support
+    are defaults, not tuned values.  A fixed-radius linear model, not a tracker: a swap or a wrong person held for longer than
+    about ``radius`` frames becomes the track and is kept."""
+    from .detscreen import mirror_table
+    radius = _screen_radius(radius, gate, floor, "radius")
+    if radius is None:
+        raise ValueError("radius must be a radius in 1 .. 64 (frames), got None")
+    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
+    conf = torch.as_tensor(conf, dtype=torch.float32)
+    if seq_2d.dim() != 3 or seq_2d.shape[-1] != 2 or tuple(conf.shape) != tuple(seq_2d.shape[:2]):
+        raise ValueError(f"seq_2d must be [N,J,2] and conf [N,J], got {tuple(seq_2d.shape)} and {tuple(conf.shape)}")
+    if mirror is None and kps_left is not None and kps_right is not None:
+        mirror = mirror_table(kps_left, kps_right, seq_2d.shape[1])
+    dev = seq_2d.device if seq_2d.is_cuda else torch.device(device)
+    out = {k: v.cpu() for k, v in _screen_detections(seq_2d, conf, mirror, radius, gate, floor, float(threshold), dev, passes, support).items()}
+    out["counts"] = torch.bincount(out["status"].reshape(-1).long(), minlength=4)
+    return out
+
+
 @torch.no_grad()
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
                    hypothesis_chunk=None, spread=None, conf=None, stride=None, trajectory=None, focal=None, repair=None,
                    repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None, pose_smooth_floor=1e-3,
-                   bone_lengths=None, bone_iterations=16):
+                   bone_lengths=None, bone_iterations=16, screen=None, screen_gate=4.0, screen_floor=0.005):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -176,6 +227,16 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     the pick all see the same filled detections, and the zeroed confidences keep the filled joints out of every fit.  Results
     that are dicts gain ``"repaired"`` [N,J] uint8, the status of every joint (0 observed, 1 filled, 2 held, 3 unfilled);
     tensor and tuple results keep their type.
+
+    ``screen`` (a radius 1 .. 64; None: everything above, unchanged, bit for bit) SCREENS THE OBSERVED DETECTIONS on the device
+    before even the repair - :func:`screen_detections` with the mirror pairs of ``kps_left`` / ``kps_right``, that radius,
+    ``screen_gate`` and ``screen_floor`` (defaults, not tuned values) and ``repair_threshold``.  It runs on the un-flipped input and
+    needs ``conf`` [N,J], which is then accepted with every ``aggregate``.  An outlier leaves with confidence 0 - the repair
+    fills it, the fits ignore it - and a left/right swap leaves exchanged; the repair, the flip copy and everything behind
+    them see the screened pair.  Results that are dicts gain ``"screened"`` [N,J] uint8 (0 accepted, 1 rejected, 2 swapped, 3
+    not observed); tensor and tuple results keep their type.  Without ``repair`` a rejected detection keeps its wrong
+    coordinates in front of the denoisers: only the fits are protected.  A fixed-radius linear model with one scale per joint
+    per video, no anchor levels, not a tracker; what it buys on real video has NOT been measured.
 
     ``path_weight`` (with "reproj" or "reproj_fit"; None: everything above, unchanged, bit for bit) makes the pick COHERENT IN
     TIME: per joint and clip, instead of the closest reprojection of every frame on its own, the path through the P hypotheses
@@ -262,6 +323,11 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, getattr(model, "frames", None), path_scope)
     if repair is not None and conf is None:
         raise ValueError("repair needs conf [N,J]: a missing detection is one whose confidence is not above repair_threshold")
+    screen = _screen_radius(screen, screen_gate, screen_floor)
+    if screen is not None:
+        _repair_radius(1, repair_threshold)      # the threshold is read by the screen as well
+        if conf is None:
+            raise ValueError("screen needs conf [N,J]: a rejected detection leaves with confidence 0")
     if focal is not None and trajectory is None:
         raise ValueError('focal="estimate" belongs to a trajectory (harness.estimate_focal gives the estimate alone)')
     if trajectory is not None:
@@ -293,25 +359,36 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
             conf = torch.as_tensor(conf, dtype=torch.float32)
             if tuple(conf.shape) != tuple(seq_2d.shape[-3:-1]):
                 raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[-3:-1])}, got {tuple(conf.shape)}")
-    elif conf is not None and trajectory is None and repair is None:
+    elif conf is not None and trajectory is None and repair is None and screen is None:
         raise ValueError('conf belongs to aggregate="reproj_fit"')
     elif conf is not None:
         conf = torch.as_tensor(conf, dtype=torch.float32)
         if tuple(conf.shape) != tuple(seq_2d.shape[-3:-1]):
             raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[-3:-1])}, got {tuple(conf.shape)}")
     dev = next(model.parameters()).device
-    if repair is None:
+    if repair is None and screen is None:
         return _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
                                spread, conf, stride, trajectory, smooth, focal, dev, path_weight, path_scope, pose_smooth, bones)
-    from .detections import repair_anchors
-    fixed = _repair_detections(seq_2d.squeeze(0) if seq_2d.dim() == 4 else seq_2d, conf, repair_anchors(dataset), repair,
-                               float(repair_threshold), dev)
-    # the callees cut and flip on the host: the repaired pair takes the place of the input, whole, before either
-    out = _infer_sequence(model, dataset, fixed["x2d"].cpu(), kps_left, kps_right, batch_size, group, aggregate, cam, traj,
-                          hypothesis_chunk, spread, fixed["conf"].cpu(), stride, trajectory, smooth, focal, dev, path_weight, path_scope,
+    # the callees cut and flip on the host: the screened and repaired pair takes the place of the input, whole, before either
+    seq_2d = seq_2d.squeeze(0) if seq_2d.dim() == 4 else seq_2d
+    screened = fixed = None
+    if screen is not None:
+        from .detscreen import mirror_table
+        screened = _screen_detections(seq_2d, conf, mirror_table(kps_left, kps_right, seq_2d.shape[-2]), screen, screen_gate,
+                                      screen_floor, float(repair_threshold), dev)
+        seq_2d, conf = screened["x2d"], screened["conf"]
+    if repair is not None:
+        from .detections import repair_anchors
+        fixed = _repair_detections(seq_2d, conf, repair_anchors(dataset), repair, float(repair_threshold), dev)
+        seq_2d, conf = fixed["x2d"], fixed["conf"]
+    out = _infer_sequence(model, dataset, seq_2d.cpu(), kps_left, kps_right, batch_size, group, aggregate, cam, traj,
+                          hypothesis_chunk, spread, conf.cpu(), stride, trajectory, smooth, focal, dev, path_weight, path_scope,
                           pose_smooth, bones)
     if isinstance(out, dict):
-        out["repaired"] = fixed["status"].cpu()
+        if screened is not None:
+            out["screened"] = screened["status"].cpu()
+        if fixed is not None:
+            out["repaired"] = fixed["status"].cpu()
     return out
 
 
@@ -1023,7 +1100,7 @@ holds the p2_* keys, each step ends with the four Protocol #2 lines (:511-519): 
 def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
                     conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False, focal=None, repair=None,
                     drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None, pose_smooth_floor=1e-3,
-                    bone_lengths=None, bone_iterations=16):
+                    bone_lengths=None, bone_iterations=16, corrupt=None, swap=None, screen=None, screen_gate=4.0, screen_floor=0.005):
     """One video scored at the level of frames: the frames path of :func:`infer_sequence` - ONE pose per video frame, pooled
     over the windows that cover it - against the ground truth, on the device before anything crosses to the host
     (evaluate.frame_metrics; pafuse_amd.framemetrics states the arithmetic).
@@ -1050,6 +1127,14 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     before the model sees them.  With either, one more, last element is returned: a dict of CPU tensors ``"x2d"`` [N,J,2] and
     ``"conf"`` [N,J] as the model and the fits saw them, ``"lost"`` [N,J] bool with ``drop`` and ``"status"`` [N,J] uint8 with
     ``repair`` - what detections.repair_error takes.
+
+    ``corrupt=(rate, run, size, seed)`` and ``swap=(rate, run, seed)`` (None: everything above, unchanged) plant WRONG detections
+    with their confidence kept, on the clean detections and before any ``drop``: detscreen.corrupt with the mirror pairs of
+    ``kps_left`` / ``kps_right`` - runs of detections displaced by ``size`` (a length or a (lo, hi) range, screen units) and runs
+    of left/right pairs exchanged; ``conf`` None counts as 1.  ``screen`` (a radius 1 .. 64; needs ``conf``, ``corrupt``, ``swap``
+    or ``drop``) then screens the detections as infer_sequence(screen=...) does, before the repair.  The extra dict gains
+    ``"planted_out"`` / ``"planted_swap"`` [N,J] bool with ``corrupt`` or ``swap`` and ``"screened"`` [N,J] uint8 with ``screen`` -
+    what detscreen.screen_error takes - and its ``"x2d"`` / ``"conf"`` are what the model and the fits saw.
 
     ``path_weight`` (with "reproj" or "reproj_fit", un-strided clips and no hypothesis_chunk; None: everything above, unchanged)
     scores the pick made coherent in time, infer_sequence(path_weight=...): per clip and joint one path through the hypotheses.
@@ -1083,8 +1168,18 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
         if (not isinstance(drop, (tuple, list)) or len(drop) != 3 or not 0.0 <= float(drop[0]) <= 1.0
                 or isinstance(drop[1], bool) or int(drop[1]) != drop[1] or int(drop[1]) < 1):
             raise ValueError(f"drop must be (rate in 0 .. 1, run >= 1 frames, seed), got {drop!r}")
-    if repair is not None and conf is None and drop is None:
+    if repair is not None and conf is None and drop is None and corrupt is None and swap is None:
         raise ValueError("repair needs conf [N,J] or drop: a missing detection is one whose confidence is not above repair_threshold")
+    screen = _screen_radius(screen, screen_gate, screen_floor)
+    planting = corrupt is not None or swap is not None
+    for name, spec, k in (("corrupt", corrupt, 4), ("swap", swap, 3)):
+        if spec is not None and (not isinstance(spec, (tuple, list)) or len(spec) != k or not 0.0 <= float(spec[0]) <= 1.0
+                                 or isinstance(spec[1], bool) or int(spec[1]) != spec[1] or int(spec[1]) < 1):
+            raise ValueError(f"{name} must be (rate in 0 .. 1, run >= 1 frames, {'size, ' if k == 4 else ''}seed), got {spec!r}")
+    if screen is not None:
+        _repair_radius(1, repair_threshold)
+        if conf is None and drop is None and not planting:
+            raise ValueError("screen needs conf [N,J], corrupt, swap or drop: a rejected detection leaves with confidence 0")
     if focal is not None and trajectory is None:
         raise ValueError('focal="estimate" belongs to a trajectory')
     if aggregate not in ("mean", "reproj", "reproj_fit"):
@@ -1105,7 +1200,7 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     if seq_2d.dim() != 3 or seq_2d.shape[-1] != 2 or tuple(seq_3d.shape) != (*seq_2d.shape[:2], 3):
         raise ValueError(f"seq_2d must be [N,J,2] and seq_3d [N,J,3], got {tuple(seq_2d.shape)} and {tuple(seq_3d.shape)}")
     if conf is not None:
-        if aggregate != "reproj_fit" and trajectory is None and repair is None and drop is None:
+        if aggregate != "reproj_fit" and trajectory is None and repair is None and drop is None and screen is None and not planting:
             raise ValueError('conf belongs to aggregate="reproj_fit" or a trajectory')
         conf = torch.as_tensor(conf, dtype=torch.float32)
         if tuple(conf.shape) != tuple(seq_2d.shape[:2]):
@@ -1113,12 +1208,25 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     from .evaluate import frame_metrics
     dev = next(model.parameters()).device
     seen = None
+    if planting or screen is not None:
+        from .detscreen import corrupt as plant_wrong, mirror_table
+        mirror = mirror_table(kps_left, kps_right, seq_2d.shape[1])
+    if planting:
+        wrong = plant_wrong(seq_2d.numpy(), torch.ones(seq_2d.shape[:2]).numpy() if conf is None else conf.numpy(), mirror,
+                            outliers=None if corrupt is None else (float(corrupt[0]), int(corrupt[1]), corrupt[2], corrupt[3]),
+                            swaps=None if swap is None else (float(swap[0]), int(swap[1]), swap[2]))
+        seq_2d, conf = torch.from_numpy(wrong["x2d"]), torch.from_numpy(wrong["conf"])
+        seen = {"planted_out": torch.from_numpy(wrong["planted_out"]), "planted_swap": torch.from_numpy(wrong["planted_swap"])}
     if drop is not None:
         from .detections import DROPPED_XY, plant_dropouts
         lost = torch.from_numpy(plant_dropouts(seq_2d.shape[0], seq_2d.shape[1], float(drop[0]), int(drop[1]), drop[2]))
         seq_2d = torch.where(lost.unsqueeze(-1), torch.tensor(DROPPED_XY, dtype=torch.float32), seq_2d)
         conf = torch.where(lost, torch.zeros(()), torch.ones(lost.shape) if conf is None else conf)
-        seen = {"lost": lost}
+        seen = {**(seen or {}), "lost": lost}
+    if screen is not None:
+        screened = _screen_detections(seq_2d, conf, mirror, screen, screen_gate, screen_floor, float(repair_threshold), dev)
+        seq_2d, conf = screened["x2d"].cpu(), screened["conf"].cpu()
+        seen = {**(seen or {}), "screened": screened["status"].cpu()}
     if repair is not None:
         from .detections import repair_anchors
         fixed = _repair_detections(seq_2d, conf, repair_anchors(dataset), repair, float(repair_threshold), dev)

@@ -1765,6 +1765,87 @@ def repair_detections(x2d, conf, anchor=None, radius=13, threshold=0.0, want=("x
     return {k: out[k] for k in want}
 
 
+# ------------------------------------------------------------------ observed 2-D detections, screened before the repair
+SCREEN_OUTPUTS = {"x2d": ("NJ", (2,), torch.float32), "conf": ("NJ", (), torch.float32), "status": ("NJ", (), torch.uint8),
+                  "resid": ("NJ", (), torch.float32), "scale": ("J", (), torch.float32)}
+
+
+def screen_mirror_table(mirror, J, device=None):
+    """The mirror table of screen_detections, validated on the host: an integer sequence, numpy array or tensor [J], every
+    entry negative (no partner) or the index of the joint whose own entry points back.  An entry the partner rule of
+    pafuse_detections_screen would drop silently - out of range, the joint itself, a joint that does not point back - is a
+    ValueError (pafuse_amd.detscreen.check_mirror).  -> int32 numpy [J]; with `device` its cached int32 copy there."""
+    from .detscreen import check_mirror
+    import numpy as np
+    if isinstance(mirror, torch.Tensor):
+        _need(not mirror.dtype.is_floating_point and mirror.dtype != torch.bool, "screen_detections: mirror must be an integer table")
+        mirror = mirror.detach().cpu().numpy()
+    table = check_mirror(np.asarray(mirror), int(J))
+    if device is None:
+        return table
+    key = (b"mirror" + table.tobytes(), str(device))
+    hit = _anchor_cache.get(key)
+    if hit is None:
+        if len(_anchor_cache) >= _ANCHOR_CACHE_MAX:
+            _anchor_cache.pop(next(iter(_anchor_cache)))
+        hit = _anchor_cache[key] = torch.from_numpy(table).to(device)
+    return hit
+
+
+def _need_count(who, name, value, lo, hi):
+    _need(not isinstance(value, bool) and isinstance(value, int) and lo <= value <= hi,
+          f"{who}: {name} must be an integer in {lo} .. {hi}, got {value!r}")
+
+
+def _need_positive(who, name, value):
+    _need(not isinstance(value, bool) and isinstance(value, (int, float)) and 0.0 < float(value) < float("inf"),
+          f"{who}: {name} must be finite and > 0, got {value!r}")
+
+
+def screen_detections(x2d, conf, mirror=None, radius=13, gate=4.0, floor=0.005, passes=3, support=3, threshold=0.0,
+                      want=("x2d", "conf", "status", "resid", "scale")):
+    """pafuse_detections_screen: x2d [N,J,2] screen-normalised detections, conf [N,J] their confidences, mirror [J] (host
+    integers: every joint's mirror joint, negative for none; None: no pairs), radius 1 .. 64 frames, gate > 0 (scales), floor
+    > 0 (the smallest scale, screen units), passes 1 .. 8, support 2 .. 129 (fewest accepted neighbours for a prediction),
+    threshold >= 0 as in repair_detections -> dict with the entries named in `want`: "x2d" [N,J,2] and "conf" [N,J] - a
+    rejected detection with confidence 0, a swapped pair exchanged, everything else the same bits - "status" [N,J] uint8: 0
+    accepted, 1 rejected, 2 swapped, 3 not observed; "resid" [N,J] the distance of every detection from the leave-one-out
+    line through its accepted neighbours (NaN where there is none); "scale" [J] the gate of every joint.
+    pafuse_amd.detscreen states the arithmetic.  gate, floor, passes and support are defaults, not tuned values."""
+    lib = _lib.load()
+    who = "screen_detections"
+    want = tuple(want)
+    _need(all(k in SCREEN_OUTPUTS for k in want), f"{who}: want holds any of {sorted(SCREEN_OUTPUTS)} - got {want}")
+    _need(isinstance(x2d, torch.Tensor) and x2d.dim() == 3 and x2d.shape[-1] == 2, f"{who}: x2d must be [N,J,2]")
+    N, J = int(x2d.shape[0]), int(x2d.shape[1])
+    _need(N > 0 and J > 0, f"{who}: N, J > 0")
+    _need(isinstance(conf, torch.Tensor) and tuple(conf.shape) == (N, J), f"{who}: conf must be [N,J]")
+    _need_radius(who, radius)
+    _need_count(who, "passes", passes, 1, 8)
+    _need_count(who, "support", support, 2, 129)
+    _need_positive(who, "gate", gate)
+    _need_positive(who, "floor", floor)
+    threshold = float(threshold)
+    _need(threshold == threshold and 0.0 <= threshold < float("inf"), f"{who}: threshold must be finite and >= 0, got {threshold!r}")
+    table = None if mirror is None else screen_mirror_table(mirror, J)      # refused here, before anything touches the device
+    _need_tensors(who, [x2d, conf], ())
+    dev = x2d.device
+    if table is not None:
+        table = screen_mirror_table(table, J, dev)
+    made = ("x2d", "conf", "status") + tuple(k for k in ("resid", "scale") if k in want)   # the finish writes the first three
+    out = {k: torch.empty(((N, J) if SCREEN_OUTPUTS[k][0] == "NJ" else (J,)) + SCREEN_OUTPUTS[k][1], device=dev, dtype=SCREEN_OUTPUTS[k][2])
+           for k in made}
+    need = lib.pafuse_detections_screen_workspace_bytes(N, J)
+    work = torch.empty((need + 7) // 8, device=dev, dtype=torch.float64)
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_detections_screen(x2d.data_ptr(), conf.data_ptr(), None if table is None else table.data_ptr(), N, J,
+                                                int(radius), int(passes), int(support), threshold, float(gate), float(floor),
+                                                ptr("x2d"), ptr("conf"), ptr("status"), ptr("resid"), ptr("scale"),
+                                                work.data_ptr(), need, _stream(x2d)))
+    return {k: out[k] for k in want}
+
+
 # ------------------------------------------------------------------ the focal length, estimated from pose and detections
 FOCAL_OUTPUTS =("focal", "r2", "frames", "cam")
 

@@ -25,6 +25,7 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::bone_lengths(pose, cov?, parent, mirror?, floor)   one length per bone from the whole video: length, dev, frames
   pafuse::bone_project(pose, cov?, parent, length, iterations, snap, floor)   every frame moved onto those lengths: out, code, resid
   pafuse::repair_detections(x2d, conf, anchor?, radius, threshold)   missing 2-D detections filled along the frames, per joint
+  pafuse::screen_detections(x2d, conf, mirror?, radius, gate, floor, passes, support, threshold)   observed detections screened first
   pafuse::focal_sums(pose, x2d, cam, conf?)               the focal-length sums of that pose: (K, H, G, 1) per (t, frame)
   pafuse::focal_solve(state, cam)                         the focal length from them: focal, r2, frames, cam per t
   pafuse::frame_errors(pose, gt, pbroot, part, num_parts, traj?, gt_root?)   that pose (and root) scored against ground truth
@@ -571,6 +572,24 @@ def repair_detections(x2d: torch.Tensor, conf: torch.Tensor, anchor: Optional[Li
 @repair_detections.register_fake
 def _(x2d, conf, anchor=None, radius=13, threshold=0.0):
     return [torch.empty_like(x2d), torch.empty_like(conf), conf.new_empty(conf.shape, dtype=torch.uint8)]
+
+
+# ------------------------------------------------------------------ observed 2-D detections, screened before the repair
+@torch.library.custom_op("pafuse::screen_detections", mutates_args=(), device_types="cuda")
+def screen_detections(x2d: torch.Tensor, conf: torch.Tensor, mirror: Optional[List[int]] = None, radius: int = 13, gate: float = 4.0,
+                      floor: float = 0.005, passes: int = 3, support: int = 3, threshold: float = 0.0) -> List[torch.Tensor]:
+    """pafuse_amd.ops.screen_detections: x2d [N,J,2], conf [N,J], mirror J host integers or None ->
+    [x2d [N,J,2] screened, conf [N,J] (0 where rejected), status [N,J] uint8, resid [N,J], scale [J]]."""
+    from . import ops
+    m = ops.screen_detections(x2d, conf, mirror=mirror, radius=radius, gate=gate, floor=floor, passes=passes, support=support,
+                              threshold=threshold)
+    return [m["x2d"], m["conf"], m["status"], m["resid"], m["scale"]]
+
+
+@screen_detections.register_fake
+def _(x2d, conf, mirror=None, radius=13, gate=4.0, floor=0.005, passes=3, support=3, threshold=0.0):
+    return [torch.empty_like(x2d), torch.empty_like(conf), conf.new_empty(conf.shape, dtype=torch.uint8), torch.empty_like(conf),
+            conf.new_empty(conf.shape[1:])]
 
 
 # ------------------------------------------------------------------ the focal length, estimated from pose and detections
