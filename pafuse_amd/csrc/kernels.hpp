@@ -1657,10 +1657,10 @@ __global__ void __launch_bounds__(256, 2) grouped_rowln_kernel(const GroupedGemm
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-// Attention between qkv and proj (common/mixste.py:65-79): one (sequence, head) per group of LP/16 waves, each
-// wave one tile of 16 queries.  S^T = K Q^T on 16x16x4 MFMAs puts the query on the lane and the keys in the
-// accumulator registers, so softmax reduces in registers + two xor-shuffles and the probabilities are already
-// the A operand of P V.
+// Attention between qkv and proj (common/mixste.py:65-79): one (sequence, head) per wave (attn_wave_kernel, up to 80
+// tokens) or per group of LP/16 waves, each wave one tile of 16 queries (attn_kernel, attn_long_kernel).  S^T = K Q^T on
+// 16x16x4 MFMAs puts the query on the lane and the keys in the accumulator registers, so softmax reduces in registers +
+// two xor-shuffles and the probabilities are already the A operand of P V.
 // ----------------------------------------------------------------------------------------------------------------
 struct AttnParams {
     const float* qkv;  // [M, 3C]
@@ -1692,64 +1692,13 @@ __device__ __forceinline__ void attn_item(int64_t i, int64_t nseq, int heads, in
     }
 }
 
-template <int LP, int DP, int NW>
-__global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnParams p) {
-    PAFUSE_XQ_GUARD();
-    constexpr int QT = LP / 16, KT = LP / 16, CT = DP / 16, SD = DP / 16, ITEMS = NW / QT, LDV = DP + 4;
-    constexpr int NTHR = NW * 64, C4 = DP / 4;
-    static_assert(NW % QT == 0, "waves must be a multiple of the query tiles");
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Ks = smem;                     // [ITEMS][LP][LDV]
-    float* Vs = smem + ITEMS * LP * LDV;  // [ITEMS][LP][LDV]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t nitems = p.nseq * p.heads;
-    const int C3 = 3 * p.C;
-
-    // this wave's item and Q fragments first (straight from global: query = 16*qt + l15, dk = 16*s + 4*g .. +3), so
-    // their latency overlaps the K/V staging below
-    const int il = wave / QT, qt = wave % QT;
-    const int64_t item = (int64_t)blockIdx.x * ITEMS + il;
-    const bool mine = item < nitems;
-    int64_t seq = 0;
-    int head = 0;
-    if (mine) attn_item<ITEMS>(item, p.nseq, p.heads, seq, head);
-    const int64_t base = (seq / p.group) * p.group_stride + (seq % p.group) * p.seq_stride;
-    const int l15 = lane & 15, g = lane >> 4;
-    f32x4 qf[SD];
-    {
-        const int q = qt * 16 + l15;
-#pragma unroll
-        for (int s = 0; s < SD; ++s) {
-            qf[s] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (mine && q < p.L && 16 * s + 4 * g < p.d)
-                qf[s] = *reinterpret_cast<const f32x4*>(p.qkv + (base + q * p.tok_stride) * C3 + head * p.d + 16 * s +
-                                                        4 * g);
-        }
-    }
-    // stage K and V of this workgroup's items (zero-padded to LP x DP)
-    for (int sl = 0; sl < ITEMS; ++sl) {
-        const int64_t it2 = (int64_t)blockIdx.x * ITEMS + sl;
-        const bool ok = it2 < nitems;
-        int64_t seq2 = 0;
-        int head2 = 0;
-        if (ok) attn_item<ITEMS>(it2, p.nseq, p.heads, seq2, head2);
-        const int64_t base2 = (seq2 / p.group) * p.group_stride + (seq2 % p.group) * p.seq_stride;
-        for (int idx = tid; idx < LP * C4; idx += NTHR) {
-            const int t = idx / C4, c4 = idx % C4;
-            f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-            if (ok && t < p.L && c4 * 4 < p.d) {
-                const float* src = p.qkv + (base2 + t * p.tok_stride) * C3 + head2 * p.d + c4 * 4;
-                kv = *reinterpret_cast<const f32x4*>(src + p.C);
-                vv = *reinterpret_cast<const f32x4*>(src + 2 * p.C);
-            }
-            *reinterpret_cast<f32x4*>(Ks + (sl * LP + t) * LDV + c4 * 4) = kv;
-            *reinterpret_cast<f32x4*>(Vs + (sl * LP + t) * LDV + c4 * 4) = vv;
-        }
-    }
-    __syncthreads();
-    if (!mine) return;
-    const float* Kb = Ks + il * LP * LDV;
-    const float* Vb = Vs + il * LP * LDV;
+// One tile of 16 queries against the KT key tiles of its item: the arithmetic both forward forms below share, so that they
+// return the same bits.  qf: the tile's Q fragments (query = 16*qt + l15, dk = 16*s + 4*g .. +3); kfrag(kt, s): the K
+// fragment of key 16*kt + l15 in the same lane layout; Vb: the item's V rows in LDS, [16 KT][LDV]; all three zero past
+// L rows / d columns.  Writes the tile's rows of o (or of its H image).
+template <int KT, int SD, int CT, int LDV, class KFrag>
+__device__ __forceinline__ void attn_tile(const AttnParams& p, const f32x4 (&qf)[SD], KFrag&& kfrag, const float* Vb, int qt,
+                                          int64_t base, int head, int l15, int g) {
     // key tiles innermost: KT independent accumulators back to back (a 16x16x4 MFMA has 40 cycles of dependent
     // latency against 32 of issue)
     f32x4 sc[KT];
@@ -1759,8 +1708,7 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnParams p) {
     for (int s = 0; s < SD; ++s) {
         f32x4 kf[KT];
 #pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-            kf[kt] = *reinterpret_cast<const f32x4*>(Kb + (kt * 16 + l15) * LDV + 16 * s + 4 * g);
+        for (int kt = 0; kt < KT; ++kt) kf[kt] = kfrag(kt, s);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -1831,6 +1779,136 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnParams p) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
             if (ct * 16 + 4 * g < p.d) *reinterpret_cast<f32x4*>(orow + ct * 16) = oc[ct];
+    }
+}
+
+// The workgroup form (LP = 144, and <32,32> and <80,48>, where it is the faster one): K and V of the workgroup's one or two items
+// staged into LDS by all its waves, a barrier, one query tile per wave.
+template <int LP, int DP, int NW>
+__global__ void __launch_bounds__(NW * 64) attn_kernel(const AttnParams p) {
+    PAFUSE_XQ_GUARD();
+    constexpr int QT = LP / 16, KT = LP / 16, CT = DP / 16, SD = DP / 16, ITEMS = NW / QT, LDV = DP + 4;
+    constexpr int NTHR = NW * 64, C4 = DP / 4;
+    static_assert(NW % QT == 0, "waves must be a multiple of the query tiles");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* Ks = smem;                     // [ITEMS][LP][LDV]
+    float* Vs = smem + ITEMS * LP * LDV;  // [ITEMS][LP][LDV]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t nitems = p.nseq * p.heads;
+    const int C3 = 3 * p.C;
+
+    // this wave's item and Q fragments first (straight from global: query = 16*qt + l15, dk = 16*s + 4*g .. +3), so
+    // their latency overlaps the K/V staging below
+    const int il = wave / QT, qt = wave % QT;
+    const int64_t item = (int64_t)blockIdx.x * ITEMS + il;
+    const bool mine = item < nitems;
+    int64_t seq = 0;
+    int head = 0;
+    if (mine) attn_item<ITEMS>(item, p.nseq, p.heads, seq, head);
+    const int64_t base = (seq / p.group) * p.group_stride + (seq % p.group) * p.seq_stride;
+    const int l15 = lane & 15, g = lane >> 4;
+    f32x4 qf[SD];
+    {
+        const int q = qt * 16 + l15;
+#pragma unroll
+        for (int s = 0; s < SD; ++s) {
+            qf[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (mine && q < p.L && 16 * s + 4 * g < p.d)
+                qf[s] = *reinterpret_cast<const f32x4*>(p.qkv + (base + q * p.tok_stride) * C3 + head * p.d + 16 * s +
+                                                        4 * g);
+        }
+    }
+    // stage K and V of this workgroup's items (zero-padded to LP x DP)
+    for (int sl = 0; sl < ITEMS; ++sl) {
+        const int64_t it2 = (int64_t)blockIdx.x * ITEMS + sl;
+        const bool ok = it2 < nitems;
+        int64_t seq2 = 0;
+        int head2 = 0;
+        if (ok) attn_item<ITEMS>(it2, p.nseq, p.heads, seq2, head2);
+        const int64_t base2 = (seq2 / p.group) * p.group_stride + (seq2 % p.group) * p.seq_stride;
+        for (int idx = tid; idx < LP * C4; idx += NTHR) {
+            const int t = idx / C4, c4 = idx % C4;
+            f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+            if (ok && t < p.L && c4 * 4 < p.d) {
+                const float* src = p.qkv + (base2 + t * p.tok_stride) * C3 + head2 * p.d + c4 * 4;
+                kv = *reinterpret_cast<const f32x4*>(src + p.C);
+                vv = *reinterpret_cast<const f32x4*>(src + 2 * p.C);
+            }
+            *reinterpret_cast<f32x4*>(Ks + (sl * LP + t) * LDV + c4 * 4) = kv;
+            *reinterpret_cast<f32x4*>(Vs + (sl * LP + t) * LDV + c4 * 4) = vv;
+        }
+    }
+    __syncthreads();
+    if (!mine) return;
+    const float* Kb = Ks + il * LP * LDV;
+    attn_tile<KT, SD, CT, LDV>(
+        p, qf, [&](int kt, int s) { return *reinterpret_cast<const f32x4*>(Kb + (kt * 16 + l15) * LDV + 16 * s + 4 * g); },
+        Vs + il * LP * LDV, qt, base, head, l15, g);
+}
+
+// The wave form (LP <= 80): one (sequence, head) item per wave from its first load to its last store, WPB independent waves
+// per workgroup and no workgroup barrier.  The wave holds every K fragment of its item in registers, read straight from
+// global memory in the lane layout of the Q fragment (KT x SD f32x4: 40 registers at <80,32>); V goes through a slice of
+// LDS that only this wave touches, [LP][DP + 4], so that the write -> read hand-over between its lanes needs no more than
+// the wave's own LDS writes having landed.  The query tiles follow each other in the wave, tile t + 1's Q fragment fetched
+// before tile t is multiplied.  Every load of an item is in flight before its first wait; what hides the latency is the
+// 12 .. 20 such waves a CU holds (LDS: WPB slices per workgroup; registers), each at its own point of that sequence.
+// (registers: as many waves per SIMD as the slices in 160 KB of LDS allow, up to 4 - 3 at LP = 80, whose 40 K registers beside as
+// many of V in flight need the room; without the bound the compiler takes up to 200 and leaves two waves a SIMD)
+constexpr int attn_wave_min_waves(int LP, int DP, int WPB) {
+    const int by_lds = (160 * 1024 / (WPB * LP * (DP + 4) * 4) * WPB + 3) / 4, by_regs = LP == 80 ? 3 : 4;
+    return by_lds < by_regs ? by_lds : by_regs;
+}
+template <int LP, int DP, int WPB>
+__global__ void __launch_bounds__(WPB * 64, attn_wave_min_waves(LP, DP, WPB)) attn_wave_kernel(const AttnParams p) {
+    PAFUSE_XQ_GUARD();
+    constexpr int QT = LP / 16, KT = LP / 16, CT = DP / 16, SD = DP / 16, LDV = DP + 4, C4 = DP / 4, VN = LP * C4 / 64;
+    static_assert(LP * C4 % 64 == 0, "V rows are loaded by whole waves");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
+    const int64_t item = (int64_t)blockIdx.x * WPB + wave;
+    if (item >= p.nseq * p.heads) return;   // (the last workgroup's spare waves: nobody waits for them)
+    int64_t seq;
+    int head;
+    attn_item<WPB>(item, p.nseq, p.heads, seq, head);
+    const int64_t base = (seq / p.group) * p.group_stride + (seq % p.group) * p.seq_stride;
+    const int C3 = 3 * p.C;
+    const float* const qh = p.qkv + head * p.d;   // q of this head in a token's row; k at + C, v at + 2 C
+    float* const Vs = smem + wave * LP * LDV;      // this wave's slice
+
+    // the fragment of 16 tokens (16*t + l15) x DP columns (16*s + 4*g .. +3) of q (off = 0) or k (off = C), zero past L / d
+    auto frag = [&](int t, int off, f32x4(&f)[SD]) {
+        const int tok = t * 16 + l15;
+#pragma unroll
+        for (int s = 0; s < SD; ++s) {
+            f[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (tok < p.L && 16 * s + 4 * g < p.d)
+                f[s] = *reinterpret_cast<const f32x4*>(qh + (base + tok * p.tok_stride) * C3 + off + 16 * s + 4 * g);
+        }
+    };
+    f32x4 qf[2][SD], kf[KT][SD], vv[VN];
+    frag(0, 0, qf[0]);
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) frag(kt, p.C, kf[kt]);
+#pragma unroll
+    for (int i = 0; i < VN; ++i) {   // V in row layout: C4 lanes per token
+        const int t = (lane + 64 * i) / C4, c4 = (lane + 64 * i) % C4;
+        vv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (t < p.L && c4 * 4 < p.d) vv[i] = *reinterpret_cast<const f32x4*>(qh + (base + t * p.tok_stride) * C3 + 2 * p.C + c4 * 4);
+    }
+#pragma unroll
+    for (int i = 0; i < VN; ++i) {
+        const int t = (lane + 64 * i) / C4, c4 = (lane + 64 * i) % C4;
+        *reinterpret_cast<f32x4*>(Vs + t * LDV + c4 * 4) = vv[i];
+    }
+    // the slice is read by other lanes of this wave than wrote it: the wave's LDS writes have landed, and the compiler
+    // keeps the reads below them (the DS operations of a wave complete in order; no other wave touches the slice)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+        if (16 * t >= p.L) break;   // a tile without a query stores nothing
+        if (t + 1 < QT) frag(t + 1, 0, qf[(t + 1) & 1]);
+        attn_tile<KT, SD, CT, LDV>(p, qf[t & 1], [&](int kt, int s) { return kf[kt][s]; }, Vs, t, base, head, l15, g);
     }
 }
 

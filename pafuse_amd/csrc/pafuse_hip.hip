@@ -621,6 +621,18 @@ int launch_attn(const AttnParams& p, hipStream_t s) {
     return launch<attn_kernel<LP, DP, NW>>("attn_kernel", (unsigned)grid, NW * 64, lds, s, p);
 }
 
+// one item per wave, WPB waves per workgroup; WPB slices of [LP][DP + 4] floats: 12 or more waves per CU in 160 KB of LDS
+// (4 x 6.5 KB at <32,48>: six workgroups .. 4 x 11.25 KB at <80,32>: three)
+template <int LP, int DP, int WPB>
+int launch_attn_wave(const AttnParams& p, hipStream_t s) {
+    constexpr size_t lds = (size_t)WPB * LP * (DP + 4) * sizeof(float);
+    static_assert(lds <= 64 * 1024 && (160 * 1024 / lds) * WPB >= 12, "LDS");
+    const int64_t nitems = p.nseq * p.heads;
+    const int64_t grid = (nitems + WPB - 1) / WPB;
+    if (grid > 0x7fffffff) return fail(PAFUSE_E_ARG, "attention grid out of range");
+    return launch<attn_wave_kernel<LP, DP, WPB>>("attn_wave_kernel", (unsigned)grid, WPB * 64, lds, s, p);
+}
+
 template <int DP>
 int launch_attn_long(const AttnParams& p, hipStream_t s) {
     constexpr size_t lds = (size_t)2 * ATTN_LONG_LP * (DP + 4) * sizeof(float);   // 104 KB at DP = 48
@@ -645,13 +657,16 @@ int attention(const AttnParams& p, hipStream_t s) {
     const int lp = p.L <= 32 ? 32 : (p.L <= 48 ? 48 : (p.L <= 80 ? 80 : 144));
     if (lp == 144)  // the single-model variant: one sequence of all 134 keypoints (common/diffusionpose.py:150-153)
         return dp == 32 ? launch_attn<144, 32, 9>(p, s) : launch_attn<144, 48, 9>(p, s);
+    // one item per wave where that form is the faster one alone (profiles/attention_wave_items.json); the workgroup form keeps
+    // <32,32> (the temporal launches of face and hands: 61 against 54 - 58 us, 41 against 38) and <80,48> (161 against 149:
+    // its 16 KB slices leave 9 waves a CU)
     if (dp == 32) {
         if (lp == 32) return launch_attn<32, 32, 4>(p, s);
-        if (lp == 48) return launch_attn<48, 32, 6>(p, s);
-        return launch_attn<80, 32, 5>(p, s);
+        if (lp == 48) return launch_attn_wave<48, 32, 4>(p, s);
+        return launch_attn_wave<80, 32, 4>(p, s);
     }
-    if (lp == 32) return launch_attn<32, 48, 4>(p, s);
-    if (lp == 48) return launch_attn<48, 48, 6>(p, s);
+    if (lp == 32) return launch_attn_wave<32, 48, 4>(p, s);
+    if (lp == 48) return launch_attn_wave<48, 48, 4>(p, s);
     return launch_attn<80, 48, 5>(p, s);
 }
 
