@@ -23,6 +23,12 @@ detscreen.corrupt - and `--screen [R]` screens the detections on the device befo
 1 .. 64, default 13): outliers leave with confidence 0, swaps leave exchanged; per video the detections per status and
 detscreen.screen_error are logged.  With `--repair` the rejected detections are filled.  Whether the screen lowers the 3-D error
 needs a real checkpoint and has not been measured: this is the tool that measures it.
+`--distract-detections PEOPLE[:SEED]` (with `--frames`) plants PEOPLE other people - shifted copies of the subject - and a new order
+of the detections in every frame (tracks.plant_people): without `--track` the first detection of every frame is lifted, as a caller
+that takes `predictions[0]` does - a splice of the subject and the copies; with `--track` the candidates are linked on the device
+and track 0 is lifted (harness.track_people; the defaults, which are not tuned values).  Per video tracks.track_error is logged: the
+frames with the subject's detection, with another person's, with nobody, and the switches.  What the tracker buys in 3-D error on
+H3WB or on real video has not been measured: this is the tool that will measure it once a real checkpoint exists.
 `--path-weight L` (with `--frames --aggregate reproj|reproj_fit`, un-strided) scores the pick made coherent in time: per clip and
 joint one path through the hypotheses instead of every frame's own winner (harness.evaluate_frames(path_weight=...)).
 `--path-scope video` runs that path along the whole video instead, across clip seams and the pooled windows of `--stride S`
@@ -92,6 +98,11 @@ def main():
     ap.add_argument("--swap-detections", default=None, metavar="RATE:RUN[:SEED]",
                     help="with --frames: exchange left/right pairs of detections, confidences included, in runs of RUN frames at about "
                          "a share RATE of the pairs")
+    ap.add_argument("--distract-detections", default=None, metavar="PEOPLE[:SEED]",
+                    help="with --frames: add PEOPLE (1 .. 63) shifted copies of the subject to every frame and shuffle the order of the "
+                         "detections per frame; the first detection of every frame is lifted unless --track")
+    ap.add_argument("--track", action="store_true",
+                    help="with --distract-detections: link the detections along the frames on the device and lift track 0")
     ap.add_argument("--screen", type=int, default=None, nargs="?", const=13, metavar="R",
                     help="with --frames and a planting: screen the observed detections on the device before the repair - outliers "
                          "against the leave-one-out line within R (1 .. 64, default 13) rejected, left/right swaps exchanged back - "
@@ -137,6 +148,18 @@ def main():
             assert len(fields) <= 3 and 0.0 <= drop[0] <= 1.0 and drop[1] >= 1
         except (ValueError, IndexError, AssertionError):
             ap.error("--drop-detections takes RATE:RUN[:SEED], RATE in 0 .. 1 and RUN >= 1 frames")
+    distract = None
+    if a.distract_detections is not None:
+        try:
+            fields = a.distract_detections.split(":")
+            distract = (int(fields[0]), int(fields[1]) if len(fields) > 1 else 0)
+            assert len(fields) <= 2 and 1 <= distract[0] <= 63
+        except (ValueError, IndexError, AssertionError):
+            ap.error("--distract-detections takes PEOPLE[:SEED], PEOPLE in 1 .. 63")
+    if (distract is not None or a.track) and not a.frames:
+        ap.error("--distract-detections and --track need --frames")
+    if a.track and distract is None:
+        ap.error("--track needs --distract-detections (ground-truth 2-D holds one person)")
     corrupt = swap = None
     try:
         if a.corrupt_detections is not None:
@@ -193,7 +216,8 @@ def main():
                              hypothesis_chunk=a.hypothesis_chunk, p2=bool(args.ft2d.p2), seam_profile=a.seam_profile,
                              focal="estimate" if a.estimate_focal else None, repair=a.repair, drop=drop, path_weight=a.path_weight,
                              path_scope=a.path_scope, pose_smooth=a.smooth_pose, pose_smooth_floor=a.smooth_pose_floor,
-                             bone_lengths=a.bone_lengths, bone_iterations=a.bone_iterations, corrupt=corrupt, swap=swap, screen=a.screen)
+                             bone_lengths=a.bone_lengths, bone_iterations=a.bone_iterations, corrupt=corrupt, swap=swap, screen=a.screen,
+                             distract=distract, track=a.track)
     else:
         h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
                       batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),

@@ -86,6 +86,23 @@ face points), _bone_frames.npy, _bone_code.npy [T,frames,134] (1 moved with a bo
 had no finite pose or usable covariance) and _bone_resid.npy [T,frames,2] (the largest |length - L| of the frame before and after,
 metres) come with it.  16 sweeps and the 1 mm floor are defaults, not tuned values; the estimated lengths are biased long where the
 noise is comparable to the bone; what it buys on real weights has not been measured (evaluate_h3wb.py --frames --bone-lengths).
+
+--track follows ONE PERSON through the video instead of taking entry 0 of every frame's "predictions" - OpenPifPaf lists the people
+of a frame in no stable order, so with two people in view entry 0 is a splice of both.  All entries of every frame are linked
+along the frames on the device (harness.load_pifpaf_people, harness.track_people; pafuse_amd/tracks.py states the arithmetic): a
+link costs the distance the person moved in units of their own size, at most --track-gate (default 0.5), may jump --track-gap
+frames (1 .. 8, default 4) at --track-skip (default 0.05) per frame jumped, and a track is the path with the largest summed gain.
+--track lifts track 0, the best-scoring person; --track-seed FRAME:PERSON the person of that detection; --people M (1 .. 64) runs
+everything above once per track, into <out>/person_<m>/.  A frame in which the person was not found enters as OpenPifPaf's own
+"not found" - zeros with confidence 0, which --repair fills.  It writes test_3d_output_track.npy [M,frames] (the entry of
+"predictions" followed, -1 nobody) and prints per track its frames, its score and the frames with nobody.  Without --track the
+script does what it did.  What the tracker does NOT do: the cost is position only, no velocity term - identities can switch where
+two people cross (on a planted video of 200 frames, 3 people and 6 slots shuffled every frame, a tenth of the detections dropped
+and a ghost in a fifth of the frames, a numpy prototype had every frame right in 2 of 4 seeds and switches at the crossings in
+the other two, 163 of 190 frames right in the worst track); extraction is greedy, one track after another, not a joint
+assignment; a person gone for more than --track-gap - 1 frames comes back as a new track; at most 64 entries per frame; the gain
+table takes frames * gap * K * K * 8 bytes; there is no appearance cue; the defaults are not tuned values; nobody has run it on
+real video.
 """
 import argparse
 import json
@@ -104,7 +121,15 @@ from pafuse_amd import config, h3wb, harness  # noqa: E402
 CAMERA_ROTATION = np.array([0.14070565, -0.15007018, -0.7552408, 0.62232804], dtype=np.float32)
 
 
-def main():
+def parse_seed(text):
+    """FRAME:PERSON -> (frame, person), both integers >= 0; None if it is anything else"""
+    parts = text.split(":")
+    if len(parts) != 2 or not all(v.isdigit() for v in parts):
+        return None
+    return int(parts[0]), int(parts[1])
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--keypoints", default="")
     ap.add_argument("--width", type=int, default=1000)
@@ -178,8 +203,30 @@ def main():
                          "the unconstrained pose goes to test_3d_output_free.npy")
     ap.add_argument("--bone-iterations", type=int, default=16, metavar="K",
                     help="with --bone-lengths: Jacobi sweeps of the projection before the exact snap (0 .. 64; default 16, not a tuned value)")
+    ap.add_argument("--track", action="store_true",
+                    help="follow one person through the video on the device instead of taking entry 0 of every frame's predictions: "
+                         "lift track 0, the best-scoring person; writes test_3d_output_track.npy [M,frames]")
+    ap.add_argument("--track-seed", default=None, metavar="FRAME:PERSON",
+                    help="with --track: follow the person of that detection (entry PERSON of frame FRAME) instead of the best-scoring one")
+    ap.add_argument("--people", type=int, default=None, metavar="M",
+                    help="with --track: follow M people (1 .. 64), best first, and run everything once per track, into <out>/person_<m>/")
+    ap.add_argument("--track-gate", type=float, default=0.5, metavar="C",
+                    help="with --track: the farthest a person may move between linked frames, in units of their own size (finite, > 0; "
+                         "default 0.5, not a tuned value)")
+    ap.add_argument("--track-gap", type=int, default=4, metavar="G",
+                    help="with --track: the longest link in frames (1 .. 8; default 4, not a tuned value)")
+    ap.add_argument("--track-skip", type=float, default=0.05, metavar="C",
+                    help="with --track: what every frame a link jumps over costs (finite, >= 0; default 0.05, not a tuned value)")
     ap.add_argument("overrides", nargs="*")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    if (a.track_seed is not None or a.people is not None) and not a.track:
+        ap.error("--track-seed and --people need --track")
+    if a.track_seed is not None and (parse_seed(a.track_seed) is None or a.people not in (None, 1)):
+        ap.error("--track-seed takes FRAME:PERSON, two integers >= 0, and names one person (no --people above 1)")
+    if a.people is not None and not 1 <= a.people <= 64:
+        ap.error("--people takes 1 .. 64 people")
+    if not (0.0 < a.track_gate < float("inf") and 0.0 <= a.track_skip < float("inf") and 1 <= a.track_gap <= 8):
+        ap.error("--track-gate takes a finite value > 0, --track-skip a finite value >= 0 and --track-gap 1 .. 8 frames")
     if a.bone_lengths is not None and (not 0 <= a.bone_iterations <= 64 or not (
             a.aggregate == "mean" or (a.reproj_fit is not None and (a.stride is not None or a.path_scope == "video")))):
         ap.error("--bone-lengths takes --bone-iterations in 0 .. 64 and needs --aggregate mean, or --reproj-fit with --stride or "
@@ -190,11 +237,6 @@ def main():
                  "--path-scope video (one pose per video frame)")
     if not 0.0 < a.smooth_pose_floor < float("inf"):
         ap.error("--smooth-pose-floor takes a finite length > 0 in metres")
-    smoothing = {} if a.smooth_pose is None else dict(pose_smooth=a.smooth_pose, pose_smooth_floor=a.smooth_pose_floor)
-    if a.bone_lengths is not None:       # behind the smoother, before the trajectory
-        smoothing.update(bone_lengths=a.bone_lengths, bone_iterations=a.bone_iterations)
-    BONE_FILES = (("bone_length", "bone_length"), ("bone_dev", "bone_dev"), ("bone_frames", "bone_frames"), ("bone_code", "bone_code"),
-                  ("bone_resid", "bone_resid"))
     if a.path_scope == "video" and a.path_weight is None:
         ap.error("--path-scope video needs --path-weight")
     if a.path_weight is not None and (a.reproj_fit is None or (a.stride is not None and a.path_scope == "clip") or a.hypothesis_chunk is not None
@@ -222,6 +264,36 @@ def main():
         ap.error("--spread needs --aggregate mean")
     if a.hypothesis_chunk is not None and a.aggregate == "none" and a.reproj_fit is None:
         ap.error("--hypothesis-chunk needs --aggregate mean")
+    return a
+
+
+def select_people(a, num_kps):
+    """The detections the rest of the script lifts -> [(pixels [frames,num_kps,2], conf [frames,num_kps], output directory)]:
+    entry 0 of every frame without --track (what the script always did), else one video per track; the track table is
+    written and reported here."""
+    if not a.track:
+        pixels, conf = harness.load_pifpaf_keypoints(a.keypoints, num_kps, with_conf=True)
+        return [(pixels, conf, a.out)]
+    people, pconf = harness.load_pifpaf_people(a.keypoints, num_kps)
+    seed = None if a.track_seed is None else parse_seed(a.track_seed)
+    if seed is not None and not (seed[0] < people.shape[0] and seed[1] < people.shape[1]):
+        raise SystemExit(f"--track-seed {a.track_seed}: the file has {people.shape[0]} frames and at most {people.shape[1]} people per frame")
+    found = harness.track_people(people, pconf, tracks=a.people or 1, seed=seed, gate=a.track_gate, skip=a.track_skip, max_gap=a.track_gap)
+    np.save(os.path.join(a.out, "test_3d_output_track.npy"), found["assign"].numpy(), allow_pickle=True)
+    out = []
+    for m in range(found["assign"].shape[0]):
+        frames, score = int(found["frames"][m]), float(found["score"][m])
+        print(f"track {m}: {frames} frames, score {score:.3f}, {people.shape[0] - frames} frames with nobody (entering as not found)")
+        if frames == 0 and m > 0:
+            continue                     # fewer people than asked for; track 0 is lifted whatever it holds
+        where = a.out if a.people is None else os.path.join(a.out, f"person_{m}")
+        os.makedirs(where, exist_ok=True)
+        out.append((found["x2d"][m].numpy(), found["conf"][m].numpy(), where))
+    return out
+
+
+def main():
+    a = parse_args()
     args = config.load(None, a.overrides)
     os.makedirs(a.out, exist_ok=True)
     ge.build()
@@ -244,7 +316,21 @@ def main():
     if a.noise == "device":
         model.noise, model.noise_seed = "device", a.seed
 
-    pixels, conf = harness.load_pifpaf_keypoints(a.keypoints, args.data.num_kps, with_conf=True)
+    top = a.out
+    for pixels, conf, where in select_people(a, args.data.num_kps):
+        a.out = where
+        lift(a, args, model, dataset, kps_left, kps_right, pixels, conf)
+    a.out = top
+
+
+def lift(a, args, model, dataset, kps_left, kps_right, pixels, conf):
+    """one person's detections (pixels [frames,134,2], conf [frames,134]) -> the files of the docstring, in a.out"""
+    chunk, spread = a.hypothesis_chunk, a.spread             # restored on the way out: the body narrows them for one person
+    smoothing = {} if a.smooth_pose is None else dict(pose_smooth=a.smooth_pose, pose_smooth_floor=a.smooth_pose_floor)
+    if a.bone_lengths is not None:       # behind the smoother, before the trajectory
+        smoothing.update(bone_lengths=a.bone_lengths, bone_iterations=a.bone_iterations)
+    BONE_FILES = (("bone_length", "bone_length"), ("bone_dev", "bone_dev"), ("bone_frames", "bone_frames"), ("bone_code", "bone_code"),
+                  ("bone_resid", "bone_resid"))
     keypoints = h3wb.normalize_screen_coordinates(pixels[..., :2], w=a.width, h=a.height).astype(np.float32)
     save = lambda name, t: np.save(os.path.join(a.out, name), t.numpy(), allow_pickle=True)
     if a.screen is not None:             # once, up front and before the repair, as infer_sequence(screen=...) would
@@ -349,6 +435,7 @@ def main():
         world[..., 2] -= world[..., 2].min()                                        # no trajectory: rebase the height
     np.save(os.path.join(a.out, "test_3d_output_postprocess.npy"), world.numpy(), allow_pickle=True)
     print(f"{keypoints.shape[0]} frames -> poses {tuple(poses.shape)} in {a.out}")
+    a.hypothesis_chunk, a.spread = chunk, spread
 
 
 if __name__ == "__main__":

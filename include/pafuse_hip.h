@@ -42,6 +42,9 @@
  *                            relative to the joint it hangs on - the input side, before lifting
  *   pafuse_detections_screen observed detections screened in front of it: outliers against a leave-one-out local line rejected
  *                            by a robust per-joint scale, left/right swaps exchanged back
+ *   pafuse_tracks_links / _path / _gather  in front of both: the K unordered candidate detections of every frame (all of
+ *                            frame["predictions"], of which in_the_wild/h3wb_diffusion.py:65 takes entry 0) linked along the
+ *                            frames into per-person videos
  *   pafuse_frames_focal_sums / pafuse_focal_solve  the focal length that fit needs, estimated from the same pose and
  *                            detections: one value per video, with the fraction of the signal it explains
  *   pafuse_frame_errors / pafuse_frame_errors_reduce  that per-frame pose and root scored against ground truth: position,
@@ -921,6 +924,48 @@ int pafuse_detections_screen(const float *x2d /* [N,J,2] */, const float *conf /
                              float *conf_out /* [N,J], may not alias conf */, uint8_t *status /* [N,J] */,
                              float *resid /* [N,J] or NULL */, float *scale /* [J] or NULL */, void *workspace,
                              size_t workspace_bytes, void *stream);
+
+/* PEOPLE FOLLOWED THROUGH A VIDEO: x2d [N,K,J,2] and conf [N,K,J], K candidate detections per frame in no stable order (an
+ * all-zero slot is "nobody"), become M per-person rows assign [M,N] and, gathered, M one-person videos for everything above
+ * (pafuse_amd/tracks.py states the arithmetic, operation for operation).  fp64, contraction off, sums
+ * over the joints in the order of pafuse_frames_root_fit.
+ * Nodes.  A joint is observed by the repair's rule; size(n,k) = sqrt((xmax - xmin) * (ymax - ymin)) over the observed joints;
+ * the candidate is present iff >= support joints are observed and size is finite and > 0 (size is NaN where it is absent).
+ * Links.  a = (n - g, ka), b = (n, kb), g = 1 .. G, both present with >= support common observed joints: w = min(conf_a,
+ * conf_b), d = sum(w * sqrt(dx*dx + dy*dy)) / sum(w), cost = d / (0.5 * (size_a + size_b));
+ * gain[n][g-1][ka][kb] = (gate - cost) - skip * (g - 1) iff cost <= gate, else -inf.
+ * Path.  Per round, in ascending n: S[n,b] = max(0.0, max over g ascending, a ascending of S[n-g,a] + gain[n][g-1][a][b]) under
+ * strict > for a node that is present and not used, -inf for every other; the track ends at the first maximum of S in
+ * (n, b) order, its nodes come from the back-pointers and are marked used; a round whose path has fewer than min_frames
+ * nodes ends the extraction: it and all later rounds are -1 everywhere, score NaN, 0 frames.  With a seed only the seed
+ * starts a path and the frames before it are not walked (M must be 1); the half before the seed is the caller's second call
+ * on the frame-reversed video.
+ *   workspace  pafuse_tracks_workspace_bytes(N, K, J, G) bytes (0 for a size out of range), 8-byte aligned, laid out as
+ *              gain [N,G,K,K] fp64 | size [N,K] fp64 | back-pointers [N,K,2] bytes | used flags [N,K] bytes.
+ *              THE GAIN TABLE GROWS AS N*G*K*K*8 BYTES: 41 MB at N = 5 000, G = 4, K = 16; 1.3 GB at K = 64, G = 8.  Pass the
+ *              largest number of people in any frame as K, not 64.
+ *   pafuse_tracks_links   two launches (one wave per candidate, one wave per (n, g, kb)): writes size and every element of gain
+ *   pafuse_tracks_path    one launch of ONE wave, the M rounds inside it; gain / size NULL: those pafuse_tracks_links left in
+ *                         the workspace, else tables from anywhere (8-byte aligned); uses the back-pointers and used flags
+ *   pafuse_tracks_gather  out [M,N,J,2], conf_out [M,N,J]: the bits of candidate assign[m][n]; zeros with confidence 0 where it
+ *                         is -1 (or outside [0, K)) - the detector's own "not found", which pafuse_detections_repair fills
+ * No atomics, no host synchronisation, bit-reproducible.  gate 0.5, skip 0.05, max_gap 4, support 5 and min_frames 5 are
+ * defaults, not tuned values.
+ * Refused (PAFUSE_E_ARG) before any HIP call: a null x2d / conf / assign / score / frames / out / conf_out, N or J < 1, K outside
+ * 1 .. 64, G outside 1 .. 8, M outside 1 .. 64, support outside 1 .. 65535, min_frames < 1, a gate that is not finite and > 0, a
+ * skip or threshold that is not finite or < 0, a seed outside [0,N) x [0,K) (no seed: -1, -1) or with M != 1, a null, short or
+ * misaligned workspace, a misaligned gain or size, a grid out of range. */
+size_t pafuse_tracks_workspace_bytes(int32_t N, int32_t K /* 1..64 */, int32_t J, int32_t G /* 1..8 */);
+int pafuse_tracks_links(const float *x2d /* [N,K,J,2] */, const float *conf /* [N,K,J] */, int32_t N, int32_t K, int32_t J,
+                        int32_t G, int32_t support, float threshold /* >= 0 */, double gate /* > 0 */, double skip /* >= 0 */,
+                        void *workspace, size_t workspace_bytes, void *stream);
+int pafuse_tracks_path(const double *gain /* [N,G,K,K] or NULL */, const double *size /* [N,K] or NULL */, int32_t N, int32_t K,
+                       int32_t G, int32_t M /* 1..64 */, int32_t min_frames, int32_t seed_n, int32_t seed_k,
+                       int32_t *assign /* [M,N] */, double *score /* [M] */, int32_t *frames /* [M] */, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int pafuse_tracks_gather(const float *x2d /* [N,K,J,2] */, const float *conf /* [N,K,J] */, const int32_t *assign /* [M,N] */,
+                         int32_t N, int32_t K, int32_t J, int32_t M, float *out /* [M,N,J,2] */, float *conf_out /* [M,N,J] */,
+                         void *stream);
 
 /* The per-frame pose smoothed along the frames, every frame weighted by the inverse of its hypothesis covariance
  * (pafuse_amd/posesmooth.py states the arithmetic, operation for operation).  A fixed-radius

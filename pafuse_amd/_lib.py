@@ -189,6 +189,10 @@ SIGNATURES = {
     "pafuse_detections_screen_workspace_bytes": (C.c_size_t, [C.c_int32] * 2),
     "pafuse_detections_screen": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_float] * 3 + [C.c_void_p] * 6 +
                                  [C.c_size_t, C.c_void_p]),
+    "pafuse_tracks_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "pafuse_tracks_links": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_float] + [C.c_double] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pafuse_tracks_path": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 7 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "pafuse_tracks_gather": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 3),
     "pafuse_pose_smooth_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "pafuse_pose_smooth": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 4 + [C.c_float] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     "pafuse_bone_lengths": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float] + [C.c_void_p] * 4),

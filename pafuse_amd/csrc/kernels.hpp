@@ -5078,6 +5078,251 @@ __global__ void __launch_bounds__(256) bone_project_kernel(const BoneProjectPara
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// PEOPLE FOLLOWED THROUGH A VIDEO (statement: pafuse_amd/tracks.py): x2d [N,K,J,2] and conf [N,K,J], K
+// candidate detections per frame in no stable order, become M per-person rows assign [M,N].  fp64, contraction off.
+//
+// track_nodes_kernel: one wave per candidate (n, k) on LaneJoints<SLOTS>.  A joint is observed by the repair's rule
+// (detection_observed); min and max of x and y over the observed joints by butterflies, their number by a ballot per round;
+// size = sqrt((xmax - xmin) * (ymax - ymin)), NaN unless >= support joints are observed and size is finite and > 0.
+//
+// track_links_kernel: one wave per (n, g, kb); b = (n, kb) sits in LaneJoints registers, the loop over ka skips an absent
+// a = (n - g, ka) on a wave-uniform branch before any load of its joints.  Over the common observed joints w = min(conf_a,
+// conf_b), num = sum w * sqrt(dx*dx + dy*dy), den = sum w (two wave_sums chains and the count), cost = (num / den) /
+// (0.5 * (size_a + size_b)), gain = (gate - cost) - skip * (g - 1) iff >= support joints are common and cost <= gate, else
+// -inf.  gain [N,G,K,K], kb fastest; every element is written.  No LDS, no atomics, no scratch.
+//
+// track_path_kernel: ONE wave; lane b owns candidate b of the frame at hand.  Per round (track) and frame, in ascending n,
+//   S[n,b] = max(0.0, max over g ascending, a ascending of S[n-g,a] + gain[n,g,a,b])     strict >: a NaN never wins
+// for a node that is present (size not NaN) and not used, -inf for every other; with a seed only the seed starts from 0.0,
+// every other node from -inf, and the frames before the seed's are not walked.  The last 8 rows of S sit in the wave's own
+// LDS ring and are read as broadcasts; beside them the wave keeps, in scalar registers, the ballot of S > -inf of each row,
+// and the loop over a walks the set bits only - a predecessor at -inf cannot win, so its gain is never loaded.  (The gains
+// of frame n + 1 are NOT prefetched: which of them are needed depends on S of frame n; DESIGN.md section 6p has what loading
+// them in batches measured.)  Wave barriers, no workgroup barrier.  Back-pointers (g, a), two bytes per node, go to the caller's workspace; the running first
+// maximum is a max butterfly plus a ballot.  The backtrace is a wave-uniform walk of which lane 0 stores: every frame of
+// assign[m,:] exactly once, and used[n,b] = 1 along the path; a workgroup-scope fence stands between the wave's stores and
+// its loads of the same bytes.  A round whose path has fewer than min_frames nodes ends the extraction: it and all later
+// rounds are -1, score NaN, 0 frames.  The M rounds run inside the one launch.  Plain vector stores only.
+//
+// track_gather_kernel: one thread per (m, n, j): the bits of candidate assign[m,n], zeros with confidence 0 where it is -1.
+// ----------------------------------------------------------------------------------------------------------------
+struct TrackJoint {
+    float x, y, c;
+    bool on;
+};
+
+__device__ __forceinline__ TrackJoint track_joint(const float* x2, const float* cf, int j, int J, float thr) {
+    TrackJoint t{0.f, 0.f, 0.f, false};
+    if (j < J) {
+        t.x = x2[2 * j], t.y = x2[2 * j + 1], t.c = cf[j];
+        t.on = detection_observed(t.c, t.x, t.y, thr);
+    }
+    return t;
+}
+
+struct TrackLinksParams {
+    const float* x2d;     // [N,K,J,2]
+    const float* conf;    // [N,K,J]
+    double* size;         // [N,K]: written by track_nodes_kernel, read by track_links_kernel
+    double* gain;         // [N,G,K,K]
+    double gate, skip;
+    float threshold;
+    int N, K, J, G, support;
+};
+
+template <int SLOTS>
+__global__ void __launch_bounds__(256) track_nodes_kernel(const TrackLinksParams p) {
+#pragma clang fp contract(off)
+    const int lane = wave_lane();
+    const int64_t item = wave_item();   // (n, k)
+    if (item >= (int64_t)p.N * p.K) return;   // wave-uniform
+    const int J = p.J;
+    const float* x2 = p.x2d + item * J * 2;
+    const float* cf = p.conf + item * J;
+    const float thr = p.threshold;
+    const auto load = [&](int j) -> TrackJoint { return track_joint(x2, cf, j, J, thr); };
+    const LaneJoints<SLOTS, decltype(load)> joints(J, load);
+    const double inf = (double)INFINITY;
+    double xlo = inf, ylo = inf, xhi = -inf, yhi = -inf;
+    int cnt = 0;
+    joints.for_each([&](const TrackJoint& t) {
+        if (t.on) xlo = fmin(xlo, (double)t.x), xhi = fmax(xhi, (double)t.x), ylo = fmin(ylo, (double)t.y), yhi = fmax(yhi, (double)t.y);
+        cnt += __builtin_popcountll(__ballot(t.on));
+    });
+    xlo = wave_min_f64(xlo), ylo = wave_min_f64(ylo), xhi = wave_max_f64(xhi), yhi = wave_max_f64(yhi);
+    const double size = sqrt((xhi - xlo) * (yhi - ylo));
+    const bool present = cnt >= p.support && isfinite(size) && size > 0.0;
+    if (lane == 0) p.size[item] = present ? size : __builtin_nan("");
+}
+
+template <int SLOTS>
+__global__ void __launch_bounds__(256) track_links_kernel(const TrackLinksParams p) {
+#pragma clang fp contract(off)
+    const int lane = wave_lane();
+    const int64_t item = wave_item();   // (n, g - 1, kb)
+    const int K = p.K, G = p.G, J = p.J;
+    if (item >= (int64_t)p.N * G * K) return;   // wave-uniform
+    const int kb = (int)(item % K), g = (int)((item / K) % G) + 1, n = (int)(item / ((int64_t)K * G));
+    double* out = p.gain + (item - kb) * K + kb;   // ka: + ka * K
+    const double ninf = -(double)INFINITY;
+    const int na = n - g;
+    const double sb = na >= 0 ? p.size[(int64_t)n * K + kb] : __builtin_nan("");
+    if (!(sb == sb)) {   // no frame n - g, or b is absent: no link ends here
+        for (int ka = lane; ka < K; ka += 64) out[(int64_t)ka * K] = ninf;
+        return;
+    }
+    const float thr = p.threshold;
+    const float* xb = p.x2d + ((int64_t)n * K + kb) * J * 2;
+    const float* cb = p.conf + ((int64_t)n * K + kb) * J;
+    const auto load = [&](int j) -> TrackJoint { return track_joint(xb, cb, j, J, thr); };
+    const LaneJoints<SLOTS, decltype(load)> joints(J, load);
+    const double lag = p.skip * (double)(g - 1);
+    for (int ka = 0; ka < K; ++ka) {
+        const double sa = p.size[(int64_t)na * K + ka];
+        double gain = ninf;
+        if (sa == sa) {   // wave-uniform: an absent a costs no load of its joints
+            const float* xa = p.x2d + ((int64_t)na * K + ka) * J * 2;
+            const float* ca = p.conf + ((int64_t)na * K + ka) * J;
+            double s[2] = {0.0, 0.0};
+            int c[1] = {0};
+            int j = lane;
+            joints.for_each([&](const TrackJoint& b) {
+                const TrackJoint a = track_joint(xa, ca, j, J, thr);
+                j += 64;
+                const bool common = a.on && b.on;
+                const double w = (double)fminf(a.c, b.c);
+                const double dx = (double)b.x - (double)a.x, dy = (double)b.y - (double)a.y;
+                const double term = w * sqrt(dx * dx + dy * dy);
+                s[0] += common ? term : 0.0, s[1] += common ? w : 0.0;   // selects: a joint that is not common feeds 0.0
+                c[0] += common;
+            });
+            wave_sums(s, c);
+            const double cost = (s[0] / s[1]) / (0.5 * (sa + sb));
+            if (c[0] >= p.support && cost <= p.gate) gain = (p.gate - cost) - lag;
+        }
+        if (lane == 0) out[(int64_t)ka * K] = gain;
+    }
+}
+
+constexpr int TRACK_MAX_K = 64;    // one lane per candidate
+constexpr int TRACK_MAX_GAP = 8;   // the rows of the S ring
+
+struct TrackPathParams {
+    const double* gain;   // [N,G,K,K]
+    const double* size;   // [N,K], NaN: absent
+    int32_t* assign;      // [M,N]
+    double* score;        // [M]
+    int32_t* frames;      // [M]
+    uint8_t* back;        // [N,K,2] (workspace): lag g (0: the path starts here) and predecessor a
+    uint8_t* used;        // [N,K] (workspace)
+    int N, K, G, M, min_frames, seed_n, seed_k;   // seed_n < 0: no seed
+};
+
+__global__ void __launch_bounds__(64) track_path_kernel(const TrackPathParams p) {
+    __shared__ double s_S[TRACK_MAX_GAP][64];
+    const int lane = threadIdx.x;
+    const int N = p.N, K = p.K, G = p.G;
+    const double ninf = -(double)INFINITY;
+    const bool seeded = p.seed_n >= 0;
+    const int n0 = seeded ? p.seed_n : 0;
+    for (int64_t i = lane; i < (int64_t)N * K; i += 64) p.used[i] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the flags this wave stored are what it now loads
+    bool done = false;
+    for (int m = 0; m < p.M; ++m) {
+        int32_t* assign = p.assign + (int64_t)m * N;
+        double best = ninf;
+        int endn = -1, endb = 0, count = 0;
+        if (!done) {
+            uint64_t live[TRACK_MAX_GAP] = {};   // live[g - 1]: the candidates of frame n - g with S > -inf (wave-uniform)
+            for (int n = n0; n < N; ++n) {
+                const int64_t node = (int64_t)n * K + lane;
+                bool alive = false;
+                if (lane < K) {
+                    const double sz = p.size[node];
+                    alive = sz == sz && !p.used[node];
+                }
+                double v = !seeded || (n == p.seed_n && lane == p.seed_k) ? 0.0 : ninf;
+                int bg = 0, ba = 0;
+                const int gmax = min(G, n - n0);
+                const double* grow = p.gain + (int64_t)n * G * K * K + (lane < K ? lane : 0);   // (g, a): + ((g - 1) * K + a) * K
+#pragma unroll
+                for (int g = 1; g <= TRACK_MAX_GAP; ++g) {
+                    if (g > gmax) break;
+                    const double* srow = s_S[(n - g) & (TRACK_MAX_GAP - 1)];
+                    for (uint64_t mask = live[g - 1]; mask; mask &= mask - 1) {   // ascending a, the same address in every lane
+                        const int a = __builtin_ctzll(mask);
+                        const double c = srow[a] + grow[((int64_t)(g - 1) * K + a) * K];
+                        if (c > v) v = c, bg = g, ba = a;   // the first maximum wins; a NaN never does
+                    }
+                }
+                const double S = alive ? v : ninf;
+                if (lane < K) p.back[node * 2] = (uint8_t)(alive ? bg : 0), p.back[node * 2 + 1] = (uint8_t)ba;
+                const double mx = wave_max_f64(S);
+                if (mx > best) best = mx, endn = n, endb = __builtin_ctzll(__ballot(S == mx));
+#pragma unroll
+                for (int g = TRACK_MAX_GAP - 1; g >= 1; --g) live[g] = live[g - 1];
+                live[0] = __ballot(S > ninf);
+                __builtin_amdgcn_wave_barrier();   // the reads of the rows n - 1 .. n - G come before the write of row n
+                s_S[n & (TRACK_MAX_GAP - 1)][lane] = S;
+                __builtin_amdgcn_wave_barrier();
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the back-pointers this wave stored are what it now loads
+            if (endn >= 0) {
+                for (int n = endn, b = endb;;) {   // wave-uniform walk
+                    ++count;
+                    const int g = p.back[((int64_t)n * K + b) * 2];
+                    if (g == 0 || g > n - n0) break;
+                    b = p.back[((int64_t)n * K + b) * 2 + 1], n -= g;
+                }
+            }
+            done = count < p.min_frames;
+        }
+        if (done) {
+            for (int n = lane; n < N; n += 64) assign[n] = -1;
+            if (lane == 0) p.score[m] = __builtin_nan(""), p.frames[m] = 0;
+            continue;
+        }
+        int n = N - 1;
+        for (; n > endn; --n)
+            if (lane == 0) assign[n] = -1;
+        for (int b = endb;;) {   // wave-uniform walk: every lane follows the path, lane 0 stores
+            const int g = p.back[((int64_t)n * K + b) * 2];
+            const int a = p.back[((int64_t)n * K + b) * 2 + 1];
+            if (lane == 0) assign[n] = b, p.used[(int64_t)n * K + b] = 1;
+            const int step = g == 0 || g > n - n0 ? n + 1 : g;   // a start: every frame in front of it is empty
+            for (int i = 1; i < step && i <= n; ++i)
+                if (lane == 0) assign[n - i] = -1;
+            if (step > n - n0) break;
+            n -= step, b = a;
+        }
+        if (lane == 0) p.score[m] = best, p.frames[m] = count;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the next round reads the used flags of this one
+    }
+}
+
+struct TrackGatherParams {
+    const float* x2d;       // [N,K,J,2]
+    const float* conf;      // [N,K,J]
+    const int32_t* assign;  // [M,N]
+    float* out;             // [M,N,J,2]
+    float* conf_out;        // [M,N,J]
+    int N, K, J, M;
+};
+
+__global__ void __launch_bounds__(256) track_gather_kernel(const TrackGatherParams p) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;   // (m, n, j)
+    if (e >= (int64_t)p.M * p.N * p.J) return;
+    const int j = (int)(e % p.J);
+    const int64_t mn = e / p.J;
+    const int n = (int)(mn % p.N);
+    const int k = p.assign[mn];
+    const bool on = k >= 0 && k < p.K;   // an index the table would lead out of is "nobody", never followed
+    const int64_t src = ((int64_t)n * p.K + (on ? k : 0)) * p.J + j;
+    p.out[e * 2] = on ? p.x2d[src * 2] : 0.f, p.out[e * 2 + 1] = on ? p.x2d[src * 2 + 1] : 0.f;
+    p.conf_out[e] = on ? p.conf[src] : 0.f;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // The focal length of the video's camera from the per-frame pose and its detections (statement:
 // pafuse_amd/focal.py).  With p = u - cx, q = (v - cy)/rho, rho = cam[1]/cam[0], hx = p*Z, hy = q*Z the pinhole is linear
 // in (1/f; tx, ty, tz/f): X + tx = hx/f + (tz/f)*p, Y + ty = hy/f + (tz/f)*q.  frames_focal_sums_kernel projects the

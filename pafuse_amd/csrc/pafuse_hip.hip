@@ -2408,6 +2408,94 @@ int pafuse_detections_screen(const float* x2d, const float* conf, const int32_t*
     return launch<detections_screen_finish_kernel>("detections_screen_finish_kernel", grid, 256, 0, s, m);
 }
 
+// people followed through a video (track_nodes_kernel, track_links_kernel, track_path_kernel, track_gather_kernel); the
+// argument checks come before the first HIP call.  Workspace: gain [N,G,K,K] fp64, size [N,K] fp64, the back-pointers
+// [N,K,2] bytes, the used flags [N,K] bytes, rounded up to a multiple of 8; J takes no part in the size.
+struct TracksViews {
+    double *gain, *size;
+    uint8_t *back, *used;
+    TracksViews(void* ws, int64_t N, int64_t K, int64_t G) {
+        gain = (double*)ws, size = gain + N * G * K * K;
+        back = (uint8_t*)(size + N * K), used = back + 2 * N * K;
+    }
+};
+
+size_t pafuse_tracks_workspace_bytes(int32_t N, int32_t K, int32_t J, int32_t G) {
+    if (N < 1 || K < 1 || K > TRACK_MAX_K || J < 1 || G < 1 || G > TRACK_MAX_GAP) return 0;
+    const size_t nodes = (size_t)N * (size_t)K;
+    return (nodes * (size_t)G * (size_t)K * sizeof(double) + nodes * (sizeof(double) + 3) + 7) / 8 * 8;
+}
+
+static int tracks_sizes(const char* who, int32_t N, int32_t K, int32_t G, const void* workspace, size_t workspace_bytes) {
+    if (N < 1) return fail(PAFUSE_E_ARG, "%s: bad size (N=%d)", who, N);
+    if (K < 1 || K > TRACK_MAX_K) return fail(PAFUSE_E_ARG, "%s: K %d outside 1 .. %d (pass the largest number of people in any frame)", who, K, TRACK_MAX_K);
+    if (G < 1 || G > TRACK_MAX_GAP) return fail(PAFUSE_E_ARG, "%s: max_gap %d outside 1 .. %d", who, G, TRACK_MAX_GAP);
+    if (((int64_t)N * G * K + 3) / 4 > 0x7fffffff) return fail(PAFUSE_E_ARG, "%s: grid out of range", who);   // the grid first: within it no size overflows
+    const size_t need = pafuse_tracks_workspace_bytes(N, K, 1, G);
+    if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 8)
+        return fail(PAFUSE_E_ARG, "%s: the workspace must hold %zu bytes, 8-byte aligned (pafuse_tracks_workspace_bytes)", who, need);
+    return PAFUSE_OK;
+}
+
+int pafuse_tracks_links(const float* x2d, const float* conf, int32_t N, int32_t K, int32_t J, int32_t G, int32_t support,
+                        float threshold, double gate, double skip, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x2d || !conf) return fail(PAFUSE_E_ARG, "tracks_links: x2d and conf are needed");
+    if (J < 1) return fail(PAFUSE_E_ARG, "tracks_links: bad size (J=%d)", J);
+    if (support < 1 || support > 65535) return fail(PAFUSE_E_ARG, "tracks_links: support %d outside 1 .. 65535", support);
+    if (!std::isfinite(threshold) || threshold < 0.f) return fail(PAFUSE_E_ARG, "tracks_links: threshold %g is not finite and >= 0", (double)threshold);
+    if (!std::isfinite(gate) || !(gate > 0.0)) return fail(PAFUSE_E_ARG, "tracks_links: gate %g is not finite and > 0", gate);
+    if (!std::isfinite(skip) || skip < 0.0) return fail(PAFUSE_E_ARG, "tracks_links: skip %g is not finite and >= 0", skip);
+    if (int rc = tracks_sizes("tracks_links", N, K, G, workspace, workspace_bytes)) return rc;
+    unsigned node_grid, link_grid;
+    if (int rc = wave_grid("tracks_links", (int64_t)N * K, node_grid)) return rc;       // one wave per (n, k)
+    if (int rc = wave_grid("tracks_links", (int64_t)N * G * K, link_grid)) return rc;   // one wave per (n, g, kb)
+    StreamDevice on_stream_device(stream);
+    const TracksViews v(workspace, N, K, G);
+    TrackLinksParams m{};
+    m.x2d = x2d, m.conf = conf, m.size = v.size, m.gain = v.gain, m.gate = gate, m.skip = skip, m.threshold = threshold;
+    m.N = N, m.K = K, m.J = J, m.G = G, m.support = support;
+    return by_joint_slots(J, [&](auto slots) {
+        constexpr int S = decltype(slots)::value;
+        if (int rc = launch<track_nodes_kernel<S>>("track_nodes_kernel", node_grid, 256, 0, (hipStream_t)stream, m)) return rc;
+        return launch<track_links_kernel<S>>("track_links_kernel", link_grid, 256, 0, (hipStream_t)stream, m);
+    });
+}
+
+int pafuse_tracks_path(const double* gain, const double* size, int32_t N, int32_t K, int32_t G, int32_t M, int32_t min_frames,
+                       int32_t seed_n, int32_t seed_k, int32_t* assign, double* score, int32_t* frames, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    if (!assign || !score || !frames) return fail(PAFUSE_E_ARG, "tracks_path: assign, score and frames are needed (gain, size null: the workspace's own)");
+    if (M < 1 || M > 64) return fail(PAFUSE_E_ARG, "tracks_path: tracks %d outside 1 .. 64", M);
+    if (min_frames < 1) return fail(PAFUSE_E_ARG, "tracks_path: min_frames %d is not >= 1", min_frames);
+    if (int rc = tracks_sizes("tracks_path", N, K, G, workspace, workspace_bytes)) return rc;
+    const bool seeded = seed_n >= 0 || seed_k >= 0;
+    if (seeded && !(seed_n >= 0 && seed_n < N && seed_k >= 0 && seed_k < K))
+        return fail(PAFUSE_E_ARG, "tracks_path: seed (%d, %d) outside [0, %d) x [0, %d) (no seed: -1, -1)", seed_n, seed_k, N, K);
+    if (seeded && M != 1) return fail(PAFUSE_E_ARG, "tracks_path: a seed names one person, it goes with tracks = 1 (got %d)", M);
+    if ((uintptr_t)gain % 8 || (uintptr_t)size % 8) return fail(PAFUSE_E_ARG, "tracks_path: gain and size must be 8-byte aligned");
+    StreamDevice on_stream_device(stream);
+    const TracksViews v(workspace, N, K, G);
+    TrackPathParams m{};
+    m.gain = gain ? gain : v.gain, m.size = size ? size : v.size, m.assign = assign, m.score = score, m.frames = frames;
+    m.back = v.back, m.used = v.used;
+    m.N = N, m.K = K, m.G = G, m.M = M, m.min_frames = min_frames, m.seed_n = seeded ? seed_n : -1, m.seed_k = seeded ? seed_k : -1;
+    return launch<track_path_kernel>("track_path_kernel", 1, 64, 0, (hipStream_t)stream, m);
+}
+
+int pafuse_tracks_gather(const float* x2d, const float* conf, const int32_t* assign, int32_t N, int32_t K, int32_t J, int32_t M,
+                         float* out, float* conf_out, void* stream) {
+    if (!x2d || !conf || !assign || !out || !conf_out) return fail(PAFUSE_E_ARG, "tracks_gather: x2d, conf, assign, out and conf_out are needed");
+    if (N < 1 || J < 1) return fail(PAFUSE_E_ARG, "tracks_gather: bad size (N=%d J=%d)", N, J);
+    if (K < 1 || K > TRACK_MAX_K) return fail(PAFUSE_E_ARG, "tracks_gather: K %d outside 1 .. %d", K, TRACK_MAX_K);
+    if (M < 1 || M > 64) return fail(PAFUSE_E_ARG, "tracks_gather: tracks %d outside 1 .. 64", M);
+    const int64_t rows = (int64_t)M * N * J;
+    if ((rows + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "tracks_gather: grid out of range");
+    StreamDevice on_stream_device(stream);
+    TrackGatherParams m{};
+    m.x2d = x2d, m.conf = conf, m.assign = assign, m.out = out, m.conf_out = conf_out, m.N = N, m.K = K, m.J = J, m.M = M;
+    return launch<track_gather_kernel>("track_gather_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
+}
+
 // the per-frame pose smoothed along the frames with the inverse hypothesis covariance as matrix weight (pose_precision_kernel,
 // then pose_smooth_kernel, on the stream); the argument checks come before the first HIP call
 size_t pafuse_pose_smooth_workspace_bytes(int32_t T, int32_t N, int32_t J) {

@@ -301,7 +301,7 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
                     batch_size=2, group=None, log=print, action=None, hypothesis_chunk=None, p2=False, seam_profile=False, focal=None,
                     repair=None, drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None,
                     pose_smooth_floor=1e-3, bone_lengths=None, bone_iterations=16, corrupt=None, swap=None, screen=None,
-                    screen_gate=4.0, screen_floor=0.005):
+                    screen_gate=4.0, screen_floor=0.005, distract=None, track=False):
     """The frame-level evaluation of every video, looped like :func:`evaluate`: harness.evaluate_frames per (camera, sequence) -
     one pose per video frame (``aggregate``, ``stride``; None: un-strided clips laid end to end), optionally its fitted
     camera-space root (``trajectory``: True or a smoothing radius) - scored on the device; the sums and counts added over the
@@ -329,8 +329,15 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
     video the detections per screen status are logged and, with a planting, detscreen.screen_error: the planted outliers and
     swaps found and missed and the false rejects and swaps, overall and per part.  Whether the screen lowers the 3-D error needs
     a real checkpoint and has not been measured.
+    ``distract=(people, seed)`` plants that many other people - shifted copies of the subject - and a new order of the slots in
+    every frame (tracks.plant_people, seed + the video's number); slot 0 is then lifted, what ``predictions[0]`` gives on such a
+    file, or with ``track=True`` (a dict: harness.track_people's parameters) track 0 of the device tracker; per video
+    tracks.track_error of what was lifted is logged.  What the tracker buys in 3-D error needs a real checkpoint and has not
+    been measured.
     On synthetic weights the numbers mean nothing."""
-    from . import detections, detscreen, harness
+    from . import detections, detscreen, harness, tracks
+    if distract is not None and (not isinstance(distract, (tuple, list)) or len(distract) != 2):
+        raise ValueError(f"distract must be (people, seed), got {distract!r}")
     if drop is not None and (not isinstance(drop, (tuple, list)) or len(drop) != 3):
         raise ValueError(f"drop must be (rate, run, seed), got {drop!r}")
     if corrupt is not None and (not isinstance(corrupt, (tuple, list)) or len(corrupt) != 4):
@@ -349,15 +356,20 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
                                       bone_iterations=bone_iterations,
                                       corrupt=None if corrupt is None else (corrupt[0], corrupt[1], corrupt[2], int(corrupt[3]) + video),
                                       swap=None if swap is None else (swap[0], swap[1], int(swap[2]) + video), screen=screen,
-                                      screen_gate=screen_gate, screen_floor=screen_floor)
+                                      screen_gate=screen_gate, screen_floor=screen_floor,
+                                      distract=None if distract is None else (distract[0], int(distract[1]) + video), track=track)
         if bone_lengths is not None:
             held, got = got[-1], got[:-1]
             gap = (held["bone_length"].double() - held["bone_length_gt"].double()).abs()
             log("video %d: bone-length std (mm, mean over the bones) free %s -> constrained %s; held lengths vs ground truth: max %.1f mm"
                 % (video, ["%.2f" % v for v in held["bone_dev_free"].tolist()], ["%.2f" % v for v in held["bone_dev"].tolist()],
                    float(gap[~gap.isnan()].max()) * 1000.0 if bool((~gap.isnan()).any()) else float("nan")))
-        if repair is not None or drop is not None or corrupt is not None or swap is not None or screen is not None:
+        if repair is not None or drop is not None or corrupt is not None or swap is not None or screen is not None or distract is not None:
             seen, got = got[-1], got[:-1]
+            if "tracked" in seen:
+                e = tracks.track_error(seen["tracked"].numpy(), seen["truth_slot"].numpy())
+                log("video %d : %s among %d people: the subject's detection in %d frames, another person's in %d, nobody in %d, %d switches"
+                    % (video, "track 0" if track is not False else "slot 0", int(distract[0]) + 1, e["right"], e["wrong"], e["missed"], e["switches"]))
             if "screened" in seen:
                 log("video %d : detections accepted %d, rejected %d, swapped %d, not observed %d"
                     % ((video,) + tuple(detscreen.counts(seen["screened"].numpy()))))

@@ -896,6 +896,62 @@ def load_pifpaf_keypoints(path, num_kps=134, with_conf=False):
     return (kps, conf) if with_conf else kps
 
 
+def load_pifpaf_people(path, num_kps=134, max_people=None):
+    """OpenPifPaf whole-body detections, one JSON object per line and frame, EVERY person of each frame, in the detector's
+    order - which is not stable from frame to frame: -> (kps float32 [frames, K, num_kps, 2] in pixels, conf float32
+    [frames, K, num_kps]), the root inserted at index 0 as :func:`load_pifpaf_keypoints` does.  K is the largest number of
+    people in any frame, or ``max_people`` if that is smaller (the detector's first entries are kept); a slot a frame does
+    not fill, and every slot of a frame whose ``predictions`` list is empty, is all zeros with confidence 0 - "nobody" to
+    :func:`track_people`."""
+    import json
+    import numpy as np
+    if max_people is not None and (isinstance(max_people, bool) or not isinstance(max_people, int) or max_people < 1):
+        raise ValueError(f"max_people must be None or an integer >= 1, got {max_people!r}")
+    frames = []
+    with open(path) as f:
+        for line in f:
+            if line.strip():
+                frames.append(json.loads(line)["predictions"])
+    K = max([len(people) for people in frames] + [1])
+    if max_people is not None:
+        K = min(K, max_people)
+    kps = np.zeros((len(frames), K, num_kps, 2), dtype=np.float32)
+    conf = np.zeros((len(frames), K, num_kps), dtype=np.float32)
+    for i, people in enumerate(frames):
+        for k, person in enumerate(people[:K]):
+            flat = person["keypoints"]
+            kps[i, k, 1:, 0] = flat[::3]
+            kps[i, k, 1:, 1] = flat[1::3]
+            kps[i, k, :1, :] = (kps[i, k, 12:13, :] + kps[i, k, 13:14, :]) / 2.
+            conf[i, k, 1:] = flat[2::3]
+            conf[i, k, 0] = min(conf[i, k, 12], conf[i, k, 13])
+    return kps, conf
+
+
+@torch.no_grad()
+def track_people(kps, conf, tracks=1, seed=None, gate=0.5, skip=0.05, max_gap=4, support=5, min_frames=5, threshold=0.0,
+                 device="cuda"):
+    """People followed through a video on the device, in front of everything else (pafuse_amd.tracks; ops.track_people):
+    ``kps`` [N,K,J,2] the candidate detections of every frame in no stable order (:func:`load_pifpaf_people`), ``conf``
+    [N,K,J].  Nothing is normalised here: the cost of a link is the distance a person moved in units of their own size, so
+    pixels and screen-normalised coordinates give the same tracks up to rounding.  Returns a dict of CPU tensors: ``"x2d"``
+    [M,N,J,2] and ``"conf"`` [M,N,J], one video per person, best first - ``x2d[m]``, ``conf[m]`` go straight into
+    :func:`screen_detections`, :func:`repair_detections` and :func:`infer_sequence`; a frame without the person is zeros with
+    confidence 0 - ``"assign"`` [M,N] int32 (the candidate followed, -1 nobody), ``"score"`` [M] float64 (NaN: no such track)
+    and ``"frames"`` [M] int32.  ``seed`` = (frame, candidate) follows that detection's person (tracks = 1).  The parameters
+    are defaults, not tuned values.  Position only: identities can switch where two people cross; a person gone for more
+    than ``max_gap - 1`` frames comes back as a new track."""
+    from . import ops
+    kps = torch.as_tensor(kps, dtype=torch.float32)
+    conf = torch.as_tensor(conf, dtype=torch.float32)
+    if kps.dim() != 4 or kps.shape[-1] != 2 or tuple(conf.shape) != tuple(kps.shape[:3]):
+        raise ValueError(f"kps must be [N,K,J,2] and conf [N,K,J], got {tuple(kps.shape)} and {tuple(conf.shape)}")
+    dev = kps.device if kps.is_cuda else torch.device(device)
+    out = ops.track_people(kps.to(dev).contiguous(), conf.to(dev).contiguous(), tracks=tracks, seed=seed, gate=gate, skip=skip,
+                           max_gap=max_gap, support=support, min_frames=min_frames, threshold=threshold)
+    return {k: v.cpu() for k, v in out.items()}
+
+
 def stitch_clips(prediction, total_frames, frames=27):
     """[clips, T, P, frames, J, 3] (clips cut by :func:`cut_clips`) -> [T, P, total_frames, J, 3]: consecutive clips laid
     end to end, the last one contributing only its final `total_frames - frames * (clips - 1)` frames
@@ -1100,7 +1156,8 @@ holds the p2_* keys, each step ends with the four Protocol #2 lines (:511-519): 
 def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, aggregate="mean", stride=None, trajectory=None,
                     conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False, focal=None, repair=None,
                     drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None, pose_smooth_floor=1e-3,
-                    bone_lengths=None, bone_iterations=16, corrupt=None, swap=None, screen=None, screen_gate=4.0, screen_floor=0.005):
+                    bone_lengths=None, bone_iterations=16, corrupt=None, swap=None, screen=None, screen_gate=4.0, screen_floor=0.005,
+                    distract=None, track=False):
     """One video scored at the level of frames: the frames path of :func:`infer_sequence` - ONE pose per video frame, pooled
     over the windows that cover it - against the ground truth, on the device before anything crosses to the host
     (evaluate.frame_metrics; pafuse_amd.framemetrics states the arithmetic).
@@ -1136,6 +1193,14 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     ``"planted_out"`` / ``"planted_swap"`` [N,J] bool with ``corrupt`` or ``swap`` and ``"screened"`` [N,J] uint8 with ``screen`` -
     what detscreen.screen_error takes - and its ``"x2d"`` / ``"conf"`` are what the model and the fits saw.
 
+    ``distract=(people, seed)`` (None: everything above, unchanged) plants OTHER PEOPLE, first of all: tracks.plant_people adds
+    ``people`` shifted copies of the subject and draws a new order of the people + 1 slots in every frame - what a detector's
+    list of a frame with several people looks like; ``conf`` None counts as 1.  With ``track=False`` slot 0 of every frame is
+    lifted - what a caller that takes ``predictions[0]`` lifts: a splice of the subject and the copies; with ``track=True`` (or
+    a dict of :func:`track_people`'s parameters) the candidates are linked on the device and track 0 is lifted.  Everything
+    else (corrupt, swap, drop, screen, repair) then sees that one video.  The extra dict gains ``"tracked"`` [N] int32, the
+    slot lifted in every frame (-1: nobody), and ``"truth_slot"`` [N] int32, the subject's - what tracks.track_error takes.
+
     ``path_weight`` (with "reproj" or "reproj_fit", un-strided clips and no hypothesis_chunk; None: everything above, unchanged)
     scores the pick made coherent in time, infer_sequence(path_weight=...): per clip and joint one path through the hypotheses.
     Where the last window overlaps its predecessor the fold's first-minimum rule decides between the two paths, frame by frame.
@@ -1168,7 +1233,14 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
         if (not isinstance(drop, (tuple, list)) or len(drop) != 3 or not 0.0 <= float(drop[0]) <= 1.0
                 or isinstance(drop[1], bool) or int(drop[1]) != drop[1] or int(drop[1]) < 1):
             raise ValueError(f"drop must be (rate in 0 .. 1, run >= 1 frames, seed), got {drop!r}")
-    if repair is not None and conf is None and drop is None and corrupt is None and swap is None:
+    if distract is not None and (not isinstance(distract, (tuple, list)) or len(distract) != 2 or isinstance(distract[0], bool)
+                                 or int(distract[0]) != distract[0] or not 1 <= int(distract[0]) <= 63):
+        raise ValueError(f"distract must be (people in 1 .. 63, seed), got {distract!r}")
+    if track is not False and distract is None:
+        raise ValueError("track needs distract: ground-truth 2-D holds one person, there is nobody to tell apart")
+    if not isinstance(track, (bool, dict)):
+        raise ValueError(f"track must be False, True or a dict of track_people's parameters, got {track!r}")
+    if repair is not None and conf is None and drop is None and corrupt is None and swap is None and distract is None:
         raise ValueError("repair needs conf [N,J] or drop: a missing detection is one whose confidence is not above repair_threshold")
     screen = _screen_radius(screen, screen_gate, screen_floor)
     planting = corrupt is not None or swap is not None
@@ -1178,7 +1250,7 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
             raise ValueError(f"{name} must be (rate in 0 .. 1, run >= 1 frames, {'size, ' if k == 4 else ''}seed), got {spec!r}")
     if screen is not None:
         _repair_radius(1, repair_threshold)
-        if conf is None and drop is None and not planting:
+        if conf is None and drop is None and not planting and distract is None:
             raise ValueError("screen needs conf [N,J], corrupt, swap or drop: a rejected detection leaves with confidence 0")
     if focal is not None and trajectory is None:
         raise ValueError('focal="estimate" belongs to a trajectory')
@@ -1200,7 +1272,8 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     if seq_2d.dim() != 3 or seq_2d.shape[-1] != 2 or tuple(seq_3d.shape) != (*seq_2d.shape[:2], 3):
         raise ValueError(f"seq_2d must be [N,J,2] and seq_3d [N,J,3], got {tuple(seq_2d.shape)} and {tuple(seq_3d.shape)}")
     if conf is not None:
-        if aggregate != "reproj_fit" and trajectory is None and repair is None and drop is None and screen is None and not planting:
+        if (aggregate != "reproj_fit" and trajectory is None and repair is None and drop is None and screen is None and not planting
+                and distract is None):
             raise ValueError('conf belongs to aggregate="reproj_fit" or a trajectory')
         conf = torch.as_tensor(conf, dtype=torch.float32)
         if tuple(conf.shape) != tuple(seq_2d.shape[:2]):
@@ -1208,6 +1281,17 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     from .evaluate import frame_metrics
     dev = next(model.parameters()).device
     seen = None
+    if distract is not None:
+        from .tracks import plant_people
+        crowd = plant_people(seq_2d.numpy(), torch.ones(seq_2d.shape[:2]).numpy() if conf is None else conf.numpy(), int(distract[0]) + 1,
+                             seed=distract[1])
+        if track is False:
+            tracked = torch.zeros(seq_2d.shape[0], dtype=torch.int32)
+            seq_2d, conf = torch.from_numpy(crowd["x2d"][:, 0].copy()), torch.from_numpy(crowd["conf"][:, 0].copy())
+        else:
+            found = track_people(crowd["x2d"], crowd["conf"], device=dev, **(track if isinstance(track, dict) else {}))
+            tracked, seq_2d, conf = found["assign"][0], found["x2d"][0].contiguous(), found["conf"][0].contiguous()
+        seen = {"tracked": tracked, "truth_slot": torch.from_numpy(crowd["truth"][0])}
     if planting or screen is not None:
         from .detscreen import corrupt as plant_wrong, mirror_table
         mirror = mirror_table(kps_left, kps_right, seq_2d.shape[1])
@@ -1216,7 +1300,7 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
                             outliers=None if corrupt is None else (float(corrupt[0]), int(corrupt[1]), corrupt[2], corrupt[3]),
                             swaps=None if swap is None else (float(swap[0]), int(swap[1]), swap[2]))
         seq_2d, conf = torch.from_numpy(wrong["x2d"]), torch.from_numpy(wrong["conf"])
-        seen = {"planted_out": torch.from_numpy(wrong["planted_out"]), "planted_swap": torch.from_numpy(wrong["planted_swap"])}
+        seen = {**(seen or {}), "planted_out": torch.from_numpy(wrong["planted_out"]), "planted_swap": torch.from_numpy(wrong["planted_swap"])}
     if drop is not None:
         from .detections import DROPPED_XY, plant_dropouts
         lost = torch.from_numpy(plant_dropouts(seq_2d.shape[0], seq_2d.shape[1], float(drop[0]), int(drop[1]), drop[2]))

@@ -1846,6 +1846,102 @@ def screen_detections(x2d, conf, mirror=None, radius=13, gate=4.0, floor=0.005, 
     return {k: out[k] for k in want}
 
 
+# ------------------------------------------------------------------ people followed through a video, in front of all of it
+TRACK_OUTPUTS = ("x2d", "conf", "assign", "score", "frames", "gain", "size")
+
+
+def tracks_views(work, N, K, G):
+    """the float64 workspace of pafuse_tracks_links -> (gain [N,G,K,K], size [N,K]): views, in the layout of include/pafuse_hip.h"""
+    n = N * G * K * K
+    return work[:n].view(N, G, K, K), work[n:n + N * K].view(N, K)
+
+
+def _track_half(lib, x2d, conf, N, K, J, G, M, support, threshold, gate, skip, min_frames, seed):
+    """links + path on one video -> (assign [M,N] int32, score [M] float64, frames [M] int32, the workspace)"""
+    dev = x2d.device
+    need = lib.pafuse_tracks_workspace_bytes(N, K, J, G)
+    _need(need > 0, "track_people: sizes out of range")
+    work = torch.empty(need // 8, device=dev, dtype=torch.float64)
+    assign = torch.empty(M, N, device=dev, dtype=torch.int32)
+    score = torch.empty(M, device=dev, dtype=torch.float64)
+    frames = torch.empty(M, device=dev, dtype=torch.int32)
+    sn, sk = (-1, -1) if seed is None else seed
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_tracks_links(x2d.data_ptr(), conf.data_ptr(), N, K, J, G, support, threshold, gate, skip,
+                                           work.data_ptr(), need, _stream(x2d)))
+        _lib.check(lib.pafuse_tracks_path(None, None, N, K, G, M, min_frames, sn, sk, assign.data_ptr(), score.data_ptr(),
+                                          frames.data_ptr(), work.data_ptr(), need, _stream(x2d)))
+    return assign, score, frames, work
+
+
+def gather_tracks(x2d, conf, assign):
+    """pafuse_tracks_gather: x2d [N,K,J,2], conf [N,K,J], assign [M,N] int32 -> (x2d [M,N,J,2], conf [M,N,J]): the bits of the
+    chosen candidates, zeros with confidence 0 where assign is -1."""
+    lib = _lib.load()
+    who = "gather_tracks"
+    _need(isinstance(x2d, torch.Tensor) and x2d.dim() == 4 and x2d.shape[-1] == 2, f"{who}: x2d must be [N,K,J,2]")
+    N, K, J = (int(v) for v in x2d.shape[:3])
+    _need(N > 0 and J > 0 and 1 <= K <= 64, f"{who}: N, J > 0 and K in 1 .. 64")
+    _need(isinstance(conf, torch.Tensor) and tuple(conf.shape) == (N, K, J), f"{who}: conf must be [N,K,J]")
+    _need(isinstance(assign, torch.Tensor) and assign.dim() == 2 and assign.shape[1] == N and 1 <= assign.shape[0] <= 64,
+          f"{who}: assign must be [M,N], M in 1 .. 64")
+    _need_tensors(who, [x2d, conf], [assign])
+    M = int(assign.shape[0])
+    out = torch.empty(M, N, J, 2, device=x2d.device, dtype=torch.float32)
+    cout = torch.empty(M, N, J, device=x2d.device, dtype=torch.float32)
+    with torch.cuda.device(x2d.device):
+        _lib.check(lib.pafuse_tracks_gather(x2d.data_ptr(), conf.data_ptr(), assign.data_ptr(), N, K, J, M, out.data_ptr(),
+                                            cout.data_ptr(), _stream(x2d)))
+    return out, cout
+
+
+def track_people(x2d, conf, tracks=1, seed=None, gate=0.5, skip=0.05, max_gap=4, support=5, min_frames=5, threshold=0.0,
+                 want=("x2d", "conf", "assign", "score", "frames")):
+    """pafuse_tracks_links + pafuse_tracks_path + pafuse_tracks_gather: x2d [N,K,J,2] screen-normalised candidate detections, K
+    per frame in no stable order (an all-zero slot is nobody; K <= 64: pass the largest number of people in any frame), conf
+    [N,K,J]; tracks 1 .. 64 people to follow, best first; seed (frame, candidate) or None: follow that detection's person
+    (tracks = 1); gate > 0: the farthest a person may move between linked frames, in units of their own size; skip >= 0: what
+    every frame a link jumps over costs; max_gap 1 .. 8: the longest link, in frames; support: fewest observed (common) joints
+    of a candidate (a link); min_frames: the shortest track kept; threshold >= 0 as in repair_detections -> dict with the
+    entries named in `want`: "x2d" [M,N,J,2] and "conf" [M,N,J] the per-person videos (a frame without the person is zeros
+    with confidence 0, which repair_detections fills), "assign" [M,N] int32 the candidate followed (-1: nobody), "score" [M]
+    float64 (NaN: no such track), "frames" [M] int32, "gain" [N,G,K,K] float64 and "size" [N,K] float64 (NaN: absent).
+    pafuse_amd.tracks states the arithmetic.  The gain table takes N*G*K*K*8 bytes.  With a seed the half before it is a
+    second run on the frame-reversed video.  gate, skip, max_gap, support and min_frames are defaults, not tuned values."""
+    from . import tracks as statement
+    lib = _lib.load()
+    who = "track_people"
+    want = tuple(want)
+    _need(all(k in TRACK_OUTPUTS for k in want), f"{who}: want holds any of {sorted(TRACK_OUTPUTS)} - got {want}")
+    _need(isinstance(x2d, torch.Tensor) and x2d.dim() == 4 and x2d.shape[-1] == 2, f"{who}: x2d must be [N,K,J,2]")
+    N, K, J = (int(v) for v in x2d.shape[:3])
+    _need(N > 0 and J > 0, f"{who}: N, J > 0")
+    _need(isinstance(conf, torch.Tensor) and tuple(conf.shape) == (N, K, J), f"{who}: conf must be [N,K,J]")
+    for name, v in (("tracks", tracks), ("max_gap", max_gap), ("support", support), ("min_frames", min_frames)):
+        _need(not isinstance(v, bool) and isinstance(v, int), f"{who}: {name} must be an integer, got {v!r}")
+    gate, skip, threshold = float(gate), float(skip), float(threshold)
+    M, G, support, min_frames, seed = statement.check(N, K, tracks, seed, gate, skip, max_gap, support, min_frames, threshold)
+    _need_tensors(who, [x2d, conf], ())
+    args = (lib, x2d, conf, N, K, J, G, M, support, threshold, gate, skip)
+    if seed is None:
+        assign, score, frames, work = _track_half(*args, min_frames, None)
+    else:   # the half from the seed on, and the half before it on the flipped video; min_frames holds for their union
+        assign, score, frames, work = _track_half(*args, 1, seed)
+        back = _track_half(lib, x2d.flip(0).contiguous(), conf.flip(0).contiguous(), *args[3:], 1, (N - 1 - seed[0], seed[1]))
+        assign = torch.where(assign >= 0, assign, back[0].flip(1)).contiguous()
+        count = frames + back[2] - 1
+        keep = (frames >= 1) & (back[2] >= 1) & (count >= min_frames)
+        assign = torch.where(keep[:, None], assign, torch.full_like(assign, -1))
+        score = torch.where(keep, score + back[1], torch.full_like(score, float("nan")))
+        frames = torch.where(keep, count, torch.zeros_like(count)).to(torch.int32)
+    out = {"assign": assign, "score": score, "frames": frames}
+    if "x2d" in want or "conf" in want:
+        out["x2d"], out["conf"] = gather_tracks(x2d, conf, assign)
+    if "gain" in want or "size" in want:
+        out["gain"], out["size"] = tracks_views(work, N, K, G)
+    return {k: out[k] for k in want}
+
+
 # ------------------------------------------------------------------ the focal length, estimated from pose and detections
 FOCAL_OUTPUTS =("focal", "r2", "frames", "cam")
 

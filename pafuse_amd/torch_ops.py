@@ -26,6 +26,7 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::bone_project(pose, cov?, parent, length, iterations, snap, floor)   every frame moved onto those lengths: out, code, resid
   pafuse::repair_detections(x2d, conf, anchor?, radius, threshold)   missing 2-D detections filled along the frames, per joint
   pafuse::screen_detections(x2d, conf, mirror?, radius, gate, floor, passes, support, threshold)   observed detections screened first
+  pafuse::track_people(x2d, conf, tracks, seed?, gate, skip, max_gap, support, min_frames, threshold)   [N,K] candidates -> per-person videos
   pafuse::focal_sums(pose, x2d, cam, conf?)               the focal-length sums of that pose: (K, H, G, 1) per (t, frame)
   pafuse::focal_solve(state, cam)                         the focal length from them: focal, r2, frames, cam per t
   pafuse::frame_errors(pose, gt, pbroot, part, num_parts, traj?, gt_root?)   that pose (and root) scored against ground truth
@@ -590,6 +591,25 @@ def screen_detections(x2d: torch.Tensor, conf: torch.Tensor, mirror: Optional[Li
 def _(x2d, conf, mirror=None, radius=13, gate=4.0, floor=0.005, passes=3, support=3, threshold=0.0):
     return [torch.empty_like(x2d), torch.empty_like(conf), conf.new_empty(conf.shape, dtype=torch.uint8), torch.empty_like(conf),
             conf.new_empty(conf.shape[1:])]
+
+
+# ------------------------------------------------------------------ people followed through a video: [N,K] candidates -> tracks
+@torch.library.custom_op("pafuse::track_people", mutates_args=(), device_types="cuda")
+def track_people(x2d: torch.Tensor, conf: torch.Tensor, tracks: int = 1, seed: Optional[List[int]] = None, gate: float = 0.5,
+                 skip: float = 0.05, max_gap: int = 4, support: int = 5, min_frames: int = 5, threshold: float = 0.0) -> List[torch.Tensor]:
+    """pafuse_amd.ops.track_people: x2d [N,K,J,2], conf [N,K,J], seed (frame, candidate) or None ->
+    [x2d [M,N,J,2], conf [M,N,J], assign [M,N] int32, score [M] float64, frames [M] int32]."""
+    from . import ops
+    m = ops.track_people(x2d, conf, tracks=tracks, seed=None if seed is None else tuple(seed), gate=gate, skip=skip, max_gap=max_gap,
+                         support=support, min_frames=min_frames, threshold=threshold)
+    return [m["x2d"], m["conf"], m["assign"], m["score"], m["frames"]]
+
+
+@track_people.register_fake
+def _(x2d, conf, tracks=1, seed=None, gate=0.5, skip=0.05, max_gap=4, support=5, min_frames=5, threshold=0.0):
+    N, J = x2d.shape[0], x2d.shape[2]
+    return [x2d.new_empty((tracks, N, J, 2)), conf.new_empty((tracks, N, J)), x2d.new_empty((tracks, N), dtype=torch.int32),
+            x2d.new_empty((tracks,), dtype=torch.float64), x2d.new_empty((tracks,), dtype=torch.int32)]
 
 
 # ------------------------------------------------------------------ the focal length, estimated from pose and detections
