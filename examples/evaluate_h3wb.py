@@ -43,6 +43,12 @@ every frame projected onto them under the covariance of its hypotheses, behind `
 mpjpe and accel columns score it; per video the mean bone-length standard deviation before and after and the largest difference of
 the held lengths from the ground truth's are logged.  What it buys on a real checkpoint has not been measured: this is the tool.
 16 sweeps and the 1 mm floor are defaults, not tuned values.
+`--ground [R]` (with `--frames --trajectory`; R in 1 .. 64, default 3; `--ground-speed V` metres per FRAME, default 0.015) also finds
+the GROUND PLANE of every video from its resting feet, behind the trajectory fit (harness.evaluate_frames(ground=...)), and logs
+per video and step the code (1 plane, 2 line, 3 the body's own up, 0 none), the camera height and the contact points - and, where
+the dataset's camera carries an orientation, the angle between the estimated up and the camera's true up, for the prediction and
+for the same estimator run on the ground-truth 3-D, which needs no checkpoint.  The metrics are not changed by it.  What the
+estimate is worth on a real checkpoint has not been measured: that angle is the tool.  The defaults are not tuned values.
 Without `--data` the synthetic H3WB files of tests/golden/h3wb_synth are used (random weights: numbers are meaningless).
 """
 import argparse
@@ -126,8 +132,16 @@ def main():
                          "of its hypotheses; compare the mpjpe and accel columns")
     ap.add_argument("--bone-iterations", type=int, default=16, metavar="K",
                     help="with --bone-lengths: Jacobi sweeps of the projection before the exact snap (0 .. 64; default 16, not a tuned value)")
+    ap.add_argument("--ground", type=int, default=None, nargs="?", const=3, metavar="R",
+                    help="with --frames --trajectory: find the ground plane of every video from its resting feet (a local line of radius "
+                         "R frames, 1 .. 64, default 3) and log the angle between the estimated and the camera's true up, for the "
+                         "prediction and for the ground-truth 3-D")
+    ap.add_argument("--ground-speed", type=float, default=0.015, metavar="V",
+                    help="with --ground: a foot point slower than V metres per FRAME counts as resting (default 0.015, not a tuned value)")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
+    if a.ground is not None and not (a.frames and a.trajectory is not None and 1 <= a.ground <= 64 and 0.0 < a.ground_speed < float("inf")):
+        ap.error("--ground takes a radius in 1 .. 64, --ground-speed a finite speed > 0, and both need --frames --trajectory")
     if a.bone_lengths is not None and not (a.frames and 0 <= a.bone_iterations <= 64):
         ap.error("--bone-lengths takes --bone-iterations in 0 .. 64 and needs --frames")
     if a.smooth_pose is not None and not (a.frames and 1 <= a.smooth_pose <= 64):
@@ -217,7 +231,9 @@ def main():
                              focal="estimate" if a.estimate_focal else None, repair=a.repair, drop=drop, path_weight=a.path_weight,
                              path_scope=a.path_scope, pose_smooth=a.smooth_pose, pose_smooth_floor=a.smooth_pose_floor,
                              bone_lengths=a.bone_lengths, bone_iterations=a.bone_iterations, corrupt=corrupt, swap=swap, screen=a.screen,
-                             distract=distract, track=a.track)
+                             distract=distract, track=a.track, ground=a.ground, ground_speed=a.ground_speed,
+                             orientations=None if a.ground is None else h3wb.fetch_orientations(
+                                 args.data.subjects_test.split(","), keypoints, dataset, action_filter=action_filter))
     else:
         h3wb.evaluate(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_right,
                       batch_size=args.model.batch_size, log=log, p2=bool(args.ft2d.p2),

@@ -103,6 +103,21 @@ the other two, 163 of 190 frames right in the worst track); extraction is greedy
 assignment; a person gone for more than --track-gap - 1 frames comes back as a new track; at most 64 entries per frame; the gain
 table takes frames * gap * K * K * 8 bytes; there is no appearance cue; the defaults are not tuned values; nobody has run it on
 real video.
+
+--ground [R] (with --trajectory; R the radius of the local line through every foot point, 1 .. 64 frames, default 3) finds WHICH WAY
+IS UP from the video instead of rotating by CAMERA_ROTATION, the quaternion of the reference's demo camera: a toe or heel point that
+moves slower than --ground-speed V metres per FRAME (default 0.015: the frame rate enters here) rests on the ground, and the ground
+is the plane through those points, re-weighted three times, on the device behind the trajectory fit (harness.estimate_ground;
+pafuse_amd/ground.py states the arithmetic).  It writes test_3d_output_world.npy [T,frames,134,3] and _world_traj.npy [T,frames,3]
+(every step in the world of its own plane: z up, the ground at z = 0, x the camera's right levelled), _contact.npy [T,frames,6] (the
+weight of every foot point as a contact) and _ground.json: per step the up direction in camera space, the camera's height, the rms
+of the contacts about the plane, the three eigenvalues of their scatter, the number of contact points and the code - 1 a plane,
+2 a line (a person standing: the plane through it closest to the body's own up), 3 the body's own up alone, 0 nothing (null).
+test_3d_output_postprocess.npy is then the camera-space poses of every step in the world of the LAST step's plane.  Without
+--ground the script does what it did.  What it does NOT do: one plane per video - no stairs, no changing slope, no moving camera; a
+slow foot in the air counts as a contact until the re-weighting drops it; codes 2 and 3 lean on the lifted body's own up and
+inherit its lean; the pose is rotated, not corrected (no foot locking: the contacts and heights are there for a caller to do it);
+world x is the camera's right, not a direction of travel; the defaults are not tuned values; nobody has run it on real video.
 """
 import argparse
 import json
@@ -217,6 +232,12 @@ def parse_args(argv=None):
                     help="with --track: the longest link in frames (1 .. 8; default 4, not a tuned value)")
     ap.add_argument("--track-skip", type=float, default=0.05, metavar="C",
                     help="with --track: what every frame a link jumps over costs (finite, >= 0; default 0.05, not a tuned value)")
+    ap.add_argument("--ground", type=int, default=None, nargs="?", const=3, metavar="R",
+                    help="with --trajectory: find the ground plane from the foot points that rest (a local line of radius R frames, "
+                         "1 .. 64, default 3), write world-space poses, contacts and test_3d_output_ground.json, and build the "
+                         "post-processed poses from it instead of the demo camera's rotation")
+    ap.add_argument("--ground-speed", type=float, default=0.015, metavar="V",
+                    help="with --ground: a foot point slower than V metres per FRAME counts as resting (default 0.015, not a tuned value)")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args(argv)
     if (a.track_seed is not None or a.people is not None) and not a.track:
@@ -256,6 +277,8 @@ def parse_args(argv=None):
         ap.error("--trajectory takes a positive focal length in pixels (or --estimate-focal) and needs --aggregate mean (one pose per frame)")
     if a.smooth_trajectory is not None and (a.trajectory is None or not 1 <= a.smooth_trajectory <= 64):
         ap.error("--smooth-trajectory takes a radius in 1 .. 64 and needs --trajectory")
+    if a.ground is not None and (a.trajectory is None or not 1 <= a.ground <= 64 or not 0.0 < a.ground_speed < float("inf")):
+        ap.error("--ground takes a radius in 1 .. 64 frames, --ground-speed a finite speed > 0 in metres per frame, and both need --trajectory")
     if a.stride is not None and a.aggregate == "none" and a.reproj_fit is None:
         ap.error("--stride needs --aggregate mean or --reproj-fit")
     if a.reproj_fit is not None and not a.reproj_fit > 0:
@@ -379,6 +402,8 @@ def lift(a, args, model, dataset, kps_left, kps_right, pixels, conf):
     if a.aggregate == "mean" and a.stride is not None:
         wanted = {} if a.trajectory is None else dict(conf=conf, trajectory=True if a.smooth_trajectory is None else a.smooth_trajectory,
                                                       **camera)
+        if a.ground is not None:
+            wanted.update(ground=a.ground, ground_speed=a.ground_speed)
         pred = harness.infer_sequence(model, dataset, keypoints, kps_left, kps_right, batch_size=a.batch, aggregate="mean",
                                       hypothesis_chunk=a.hypothesis_chunk, spread=a.spread, stride=a.stride, **wanted, **smoothing)
         for k, name in (("std", "std"), ("cov", "cov"), ("count", "count"), ("pose_raw", "raw"), ("pose_smooth_code", "smooth_code"),
@@ -429,6 +454,25 @@ def lift(a, args, model, dataset, kps_left, kps_right, pixels, conf):
         for k in ("traj", "traj_raw", "traj_resid"):
             if k in traj:
                 save(f"test_3d_output_{k}.npy", traj[k])
+    if traj is not None and a.ground is not None:
+        # inside infer_sequence where it ran (--stride), else on the stitched poses and their fitted roots
+        found = traj if "ground_code" in traj else harness.estimate_ground(poses, traj["traj"], radius=a.ground, speed=a.ground_speed)
+        for k, name in (("pose_world", "world"), ("traj_world", "world_traj"), ("contact", "contact")):
+            save(f"test_3d_output_{name}.npy", found[k])
+        number = lambda v: None if v != v else v                                    # NaN (code 0: no plane) -> null
+        with open(os.path.join(a.out, "test_3d_output_ground.json"), "w") as f:
+            json.dump({"radius": a.ground, "speed_m_per_frame": a.ground_speed,
+                       "up": [[number(float(c)) for c in v] for v in found["up"]],
+                       "camera_height_m": [number(float(v)) for v in found["camera_height"]],
+                       "rms_m": [number(float(v)) for v in found["ground_rms"]],
+                       "eigenvalues_m2": [[number(float(c)) for c in v] for v in found["ground_eig"]],
+                       "points": [int(v) for v in found["ground_points"]],
+                       "code": [int(v) for v in found["ground_code"]]}, f, indent=1)
+        print("ground per step: code", [int(v) for v in found["ground_code"]], "camera height, m:",
+              [None if v != v else round(float(v), 3) for v in found["camera_height"]])
+        # one world for the post-processed file: every step's camera-space poses under the plane of the last, fully denoised step
+        world = harness.frames_to_world(poses, traj["traj"], found["ground_plane"][-1])["pose_world"]
+    elif traj is not None:
         world = harness.camera_to_world(poses + traj["traj"][:, :, None], CAMERA_ROTATION)   # a broadcast add: camera-space poses
     else:
         world = harness.camera_to_world(poses, CAMERA_ROTATION)

@@ -47,6 +47,9 @@
  *                            frames into per-person videos
  *   pafuse_frames_focal_sums / pafuse_focal_solve  the focal length that fit needs, estimated from the same pose and
  *                            detections: one value per video, with the fraction of the signal it explains
+ *   pafuse_foot_contacts / pafuse_ground_sums / pafuse_ground_solve / pafuse_frames_to_world  behind that fit: which way is
+ *                            up - the ground plane through the foot points that do not move, and the poses in world space
+ *                            (in place of the demo camera's fixed rotation, in_the_wild/h3wb_diffusion.py)
  *   pafuse_frame_errors / pafuse_frame_errors_reduce  that per-frame pose and root scored against ground truth: position,
  *                            velocity (mean_velocity_error, common/loss.py:488-497), acceleration, root and part-based errors
  *   pafuse_procrustes_errors the Protocol #2 part of it (ft2d.p2), main_h3wb.py:381-395, common/loss.py:251-458
@@ -1091,6 +1094,64 @@ int pafuse_frames_focal_sums(const float *pose /* [T,N,J,3] whole-body, root-rel
 int pafuse_focal_solve(const double *state /* [T,N,4] */, int32_t T, int32_t N, const float *cam /* [cam_len] */,
                        int32_t cam_len /* 4..9 */, float *focal /* [T] */, float *r2 /* [T] or NULL */,
                        int32_t *frames /* [T] or NULL */, float *cam_out /* [T,cam_len] or NULL */, void *stream);
+
+/* Which way is up: the ground plane of a video from its foot contacts, and the poses in world space (pafuse_amd/ground.py
+ * states every operation and its order).  A foot that is not moving is on the ground, and the ground
+ * is the plane through those points.  fp64, contraction off, every output rounded once; four kernels, no workspace, no
+ * atomics, bit-reproducible.  The chain is foot_contacts, `passes` times (ground_sums, ground_solve), frames_to_world on one
+ * stream: a later pass reads the plane and scale of the one before ON THE DEVICE.  speed 0.015 m/frame, gate 2.5, floor
+ * 0.005 m, spread 0.03 m, radius 3 and 3 passes are the defaults of the Python layer: defaults, not tuned values.
+ *
+ * pafuse_foot_contacts: for every (t, n, k) the camera-space point pose[t,m,points[k]] + traj[t,m] goes through the
+ * local-linear filter of pafuse_trajectory_smooth (weight 1; a frame takes part if its six values are finite).  Only a line
+ * through at least 3 frames counts:
+ *   foot       [T,N,K,3] fp32  the line's value at the frame; NaN without such a line
+ *   foot_speed [T,N,K]   fp32  (NULL: not wanted) v = |the line's slope|, metres per frame; NaN without
+ *   contact    [T,N,K]   fp32  (1 - (v/speed)^2)^2 for v < speed, else 0; 0 without
+ * Refused (PAFUSE_E_ARG) before any HIP call: a null pose / traj / points / foot / contact, T, N or J < 1, K outside 1 .. 16,
+ * radius outside 1 .. 64, a speed that is not finite and > 0, a grid out of range.  points[k] lies in [0, J) (the caller's
+ * promise: it is device memory; a point outside reads nothing and gives NaN, NaN, 0). */
+int pafuse_foot_contacts(const float *pose /* [T,N,J,3] root-relative */, const float *traj /* [T,N,3]; NaN: no root */,
+                         const int32_t *points /* [K] */, int32_t T, int32_t N, int32_t J, int32_t K /* 1..16 */,
+                         int32_t radius /* 1..64 */, double speed /* metres per frame */, float *foot /* [T,N,K,3] */,
+                         float *foot_speed /* [T,N,K] or NULL */, float *contact /* [T,N,K] */, void *stream);
+
+/* The sums of every (t, n) over its K points in ascending order.  A point takes part if contact > 0 and its foot and the
+ * frame's root are finite; its weight is omega = contact * rho: rho = 1 without a plane (plane and scale NULL: the first
+ * pass), else (1 - z*z)^2 for |z| < 1 and 0 beyond, z = (n.p - d)/(gate * scale[t]) with (n, d) = plane[t] (a NaN plane: 0).
+ *   state double [T,N,14]  omega; omega*p (3); (omega*p_a)*p_b (xx xy xz yy yz zz, about the camera origin); omega*(root - p)
+ *                          (3); the number of points with omega > 0.  A frame whose every weight is 0: exactly 14 zeros.
+ *                          States of several videos of one scene concatenate along N.
+ * Refused (PAFUSE_E_ARG) before any HIP call: a null foot / contact / traj / state, plane without scale or the reverse, T or
+ * N < 1, K outside 1 .. 16, a gate that is not finite and > 0, a state / plane / scale that is not 8-byte aligned. */
+int pafuse_ground_sums(const float *foot /* [T,N,K,3] */, const float *contact /* [T,N,K] */, const float *traj /* [T,N,3] */,
+                       const double *plane /* [T,4] or NULL */, const double *scale /* [T]; NULL iff plane is */,
+                       int32_t T, int32_t N, int32_t K, double gate, double *state /* [T,N,14] */, void *stream);
+
+/* The plane per t.  The slots are summed over n as pafuse_focal_solve sums; mu = S/W, C = M/W - mu mu^T; the eigen
+ * decomposition of C is a cyclic Jacobi of 8 fixed sweeps (+ - * / sqrt only), sorted ascending.  With u = sum omega*(root - p):
+ *   code 1 plane  lambda1 >= spread^2 and lambda1 >= 9*max(lambda0, floor^2): n = the eigenvector of lambda0
+ *   code 2 line   else lambda2 >= spread^2: the contacts lie on a line a; n = normalize(u - (u.a) a)   (a person standing)
+ *   code 3 body   else W > 0 and |u| > 0: n = normalize(u)
+ *   code 0 none   NaN in every floating-point output, never a guess
+ * n is signed so that n.u >= 0 (the root is above the feet), d = n.mu, rms = sqrt(n.C n), sigma = max(floor, rms).
+ *   plane double [T,4] (n, d) and scale double [T] (sigma): what the next pafuse_ground_sums and pafuse_frames_to_world read
+ *   up [T,3], camera_height [T] (= -d), rms [T], eig [T,3] fp32, points [T] int32, code [T] uint8: each may be NULL
+ * One wave per t.  Refused (PAFUSE_E_ARG) before any HIP call: a null state / plane / scale, T or N < 1, a floor or spread
+ * that is not finite and > 0, a state / plane / scale that is not 8-byte aligned. */
+int pafuse_ground_solve(const double *state /* [T,N,14] */, int32_t T, int32_t N, double floor /* metres */,
+                        double spread /* metres */, double *plane /* [T,4] */, double *scale /* [T] */, float *up,
+                        float *camera_height, float *rms, float *eig, int32_t *points, uint8_t *code, void *stream);
+
+/* Camera space to world space per t from plane[t]: z = n, x = normalize(e - (e.n) n) with e = (1,0,0), the camera's right
+ * ((0,0,1) if |n_x| > 0.99), y = z cross x; p = pose + traj -> (x.p, y.p, n.p - d): the third component of a joint is its
+ * height above the ground.  NaN in gives NaN out, a NaN plane (code 0) gives NaN.
+ *   pose_world [T,N,J,3] fp32;  traj_world [T,N,3] fp32 (NULL: not wanted) the root traj[t,n] likewise
+ * Refused (PAFUSE_E_ARG) before any HIP call: a null pose / traj / plane / pose_world, T, N or J < 1, a plane that is not
+ * 8-byte aligned, a grid out of range. */
+int pafuse_frames_to_world(const float *pose /* [T,N,J,3] */, const float *traj /* [T,N,3] */, const double *plane /* [T,4] */,
+                           int32_t T, int32_t N, int32_t J, float *pose_world /* [T,N,J,3] */,
+                           float *traj_world /* [T,N,3] or NULL */, void *stream);
 
 /* Frame-level errors of the per-frame pose against ground truth (pafuse_amd/framemetrics.py states the arithmetic):
  * pose [T,N,J,3] and gt [N,J,3] whole-body and root-relative, traj [T,N,3] / gt_root [N,3] the camera-space root (both or

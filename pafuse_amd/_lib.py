@@ -199,6 +199,10 @@ SIGNATURES = {
     "pafuse_bone_project": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_float] + [C.c_void_p] * 4),
     "pafuse_frames_focal_sums": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p] * 2),
     "pafuse_focal_solve": (C.c_int, [C.c_void_p] + [C.c_int32] * 2 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
+    "pafuse_foot_contacts": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_double] + [C.c_void_p] * 4),
+    "pafuse_ground_sums": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_double] + [C.c_void_p] * 2),
+    "pafuse_ground_solve": (C.c_int, [C.c_void_p] + [C.c_int32] * 2 + [C.c_double] * 2 + [C.c_void_p] * 9),
+    "pafuse_frames_to_world": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 3),
     "pafuse_frame_errors": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p] * 3),
     "pafuse_frame_errors_reduce": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p] * 3),
     "pafuse_procrustes_errors": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p] * 6),

@@ -4243,6 +4243,11 @@ struct LineFilter {
         const double D = S0 * S2 - S1 * S1;
         return kind() == LINE_FIT ? (S2 * Q0[k] - S1 * Q1[k]) / D : Q0[k] / S0;
     }
+    __device__ __forceinline__ double slope(int k) const {   // kind() == LINE_FIT: the same line's change per frame at d = 0
+#pragma clang fp contract(off)
+        const double D = S0 * S2 - S1 * S1;
+        return (S0 * Q1[k] - S1 * Q0[k]) / D;
+    }
 };
 
 // trajectory_smooth_kernel: LineFilter<3> on the roots (statement: pafuse_amd/trajectory.py smooth).  One thread per (t, n)
@@ -5588,6 +5593,257 @@ __global__ void __launch_bounds__(256) frame_errors_reduce_kernel(const FrameErr
     for (int n = lane; n < p.N; n += 64) s[0] += p.err[(row0 + n) * p.K + k], c[0] += p.cnt[(row0 + n) * p.K + k];
     wave_sums(s, c);
     if (lane == 0) p.sums[item] = s[0], p.counts[item] = (int64_t)c[0];
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// Which way is up: the ground plane of a video from its foot contacts, and the poses in world space (DESIGN.md section
+// 6q; statement: pafuse_amd/ground.py, which pins every operation below and its order).  A foot that is not moving is on
+// the ground, and the ground is the plane through those points.  fp64, contraction off, plain vector stores, no atomics,
+// no LDS, no scratch.
+//
+// foot_contacts_kernel: one thread per (t, n, k), k fastest, on LineFilter<3> with weight 1.0: the camera-space foot point
+// y[m] = double(pose[t,m,points[k]]) + double(traj[t,m]) over m = max(0, n - r) .. min(N - 1, n + r), a frame taking part if
+// its six values are finite.  A LINE_FIT with >= 3 frames gives foot = value, v = |slope|, contact = (1 - (v/speed)^2)^2 for
+// v < speed, else 0; otherwise NaN, NaN, 0.
+// ground_sums_kernel: one thread per (t, n), its K <= 16 points in ascending order.  omega = contact * rho, rho = 1 without a
+// plane, else the biweight of z = (n.p - d)/(gate*sigma) with plane[t], scale[t] read here: the previous pass's solve wrote
+// them on the same stream.  14 slots: omega, omega*p (3), (omega*p_a)*p_b (6: xx xy xz yy yz zz, about the camera origin),
+// omega*(root - p) (3), the number of points with omega > 0.
+// ground_solve_kernel: one wave per t (wave_item); lane l adds frames l, l + 64, ... ascending, the 14 slots through
+// wave_sums - after the butterfly every lane holds the same bits, so everything behind it is wave-uniform: mu, C, eight cyclic
+// Jacobi sweeps on named scalars (no indexed local arrays: nothing for the compiler to put in scratch), the sort, the code
+// (1 plane, 2 line, 3 body, 0 none), the sign, d, the rms through the moments.  Lane 0 stores.
+// frames_to_world_kernel: one thread per (t, n, j), j fastest: the axes x, y, z = n from plane[t] (every thread derives
+// them again: three dozen flops beside two fp64 square roots, no second launch), p = pose + traj -> (x.p, y.p, n.p - d);
+// the thread of joint 0 also writes the root's.
+// ----------------------------------------------------------------------------------------------------------------
+constexpr int GROUND_SLOTS = 14;
+constexpr int GROUND_MAX_POINTS = 16;
+constexpr int GROUND_MIN_FRAMES = 3;
+constexpr int GROUND_SWEEPS = 8;
+
+__device__ __forceinline__ double ground_dot(double x0, double x1, double x2, double y0, double y1, double y2) {
+#pragma clang fp contract(off)
+    return (x0 * y0 + x1 * y1) + x2 * y2;
+}
+
+struct FootContactsParams {
+    const float* pose;      // [T,N,J,3] root-relative
+    const float* traj;      // [T,N,3] camera-space root (NaN: none)
+    const int32_t* points;  // [K] joints, each in [0, J)
+    float* foot;            // [T,N,K,3]
+    float* foot_speed;      // [T,N,K] or null
+    float* contact;         // [T,N,K]
+    double speed;           // metres per frame
+    int T, N, J, K, radius;
+};
+
+__global__ void __launch_bounds__(256) foot_contacts_kernel(const FootContactsParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)p.T * p.N * p.K) return;
+    const int k = (int)(e % p.K), n = (int)((e / p.K) % p.N), r = p.radius;
+    const int64_t row0 = e / p.K - n;   // (t, 0)
+    const int j = p.points[k];
+    const bool inside = j >= 0 && j < p.J;   // the host refuses such a table; a thread never reads outside the pose
+    LineFilter<3> f(r);
+    const int lo = max(0, n - r), hi = min(p.N - 1, n + r);
+    for (int m = lo; inside && m <= hi; ++m) {
+        const float* w = p.pose + ((row0 + m) * p.J + j) * 3;
+        const float* c = p.traj + (row0 + m) * 3;
+        const float w0 = w[0], w1 = w[1], w2 = w[2], c0 = c[0], c1 = c[1], c2 = c[2];
+        if (!(isfinite(w0) && isfinite(w1) && isfinite(w2) && isfinite(c0) && isfinite(c1) && isfinite(c2))) continue;
+        const double y[3] = {(double)w0 + (double)c0, (double)w1 + (double)c1, (double)w2 + (double)c2};
+        f.add(m - n, 1.0, y);
+    }
+    const bool has = f.kind() == LINE_FIT && f.cnt >= GROUND_MIN_FRAMES;
+    const float qnan = __builtin_nanf("");
+    const double v = frame_norm(f.slope(0), f.slope(1), f.slope(2));
+    const double q = v / p.speed, h = 1.0 - q * q;
+    const double w = has && v < p.speed ? h * h : 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p.foot[e * 3 + a] = has ? (float)f.value(a) : qnan;
+    if (p.foot_speed) p.foot_speed[e] = has ? (float)v : qnan;
+    p.contact[e] = (float)w;
+}
+
+struct GroundSumsParams {
+    const float* foot;     // [T,N,K,3]
+    const float* contact;  // [T,N,K]
+    const float* traj;     // [T,N,3]
+    const double* plane;   // [T,4] of the previous pass, or null (the first)
+    const double* scale;   // [T]; null iff plane is
+    double* state;         // [T,N,14]
+    double gate;
+    int T, N, K;
+};
+
+__global__ void __launch_bounds__(256) ground_sums_kernel(const GroundSumsParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;   // (t, n)
+    if (e >= (int64_t)p.T * p.N) return;
+    const int64_t t = e / p.N;
+    const float r0 = p.traj[e * 3 + 0], r1 = p.traj[e * 3 + 1], r2 = p.traj[e * 3 + 2];
+    const bool root_ok = isfinite(r0) && isfinite(r1) && isfinite(r2);
+    const double root0 = (double)r0, root1 = (double)r1, root2 = (double)r2;
+    double nx = 0.0, ny = 0.0, nz = 0.0, d = 0.0, gs = 1.0;
+    if (p.plane) nx = p.plane[t * 4 + 0], ny = p.plane[t * 4 + 1], nz = p.plane[t * 4 + 2], d = p.plane[t * 4 + 3], gs = p.gate * p.scale[t];
+    double s0 = 0.0, sx = 0.0, sy = 0.0, sz = 0.0, mxx = 0.0, mxy = 0.0, mxz = 0.0, myy = 0.0, myz = 0.0, mzz = 0.0;
+    double ux = 0.0, uy = 0.0, uz = 0.0, cnt = 0.0;
+    for (int k = 0; k < p.K; ++k) {   // ascending
+        const float* fp = p.foot + (e * p.K + k) * 3;
+        const float f0 = fp[0], f1 = fp[1], f2 = fp[2], cf = p.contact[e * p.K + k];
+        if (!(cf > 0.f && isfinite(f0) && isfinite(f1) && isfinite(f2) && root_ok)) continue;
+        const double px = (double)f0, py = (double)f1, pz = (double)f2;
+        double om = (double)cf;
+        if (p.plane) {
+            const double z = (((nx * px + ny * py) + nz * pz) - d) / gs;
+            const double g = 1.0 - z * z;
+            om = om * (fabs(z) < 1.0 ? g * g : 0.0);
+        }
+        if (!(om > 0.0)) continue;
+        const double ox = om * px, oy = om * py, oz = om * pz;
+        s0 += om, sx += ox, sy += oy, sz += oz;
+        mxx += ox * px, mxy += ox * py, mxz += ox * pz, myy += oy * py, myz += oy * pz, mzz += oz * pz;
+        ux += om * (root0 - px), uy += om * (root1 - py), uz += om * (root2 - pz);
+        cnt += 1.0;
+    }
+    double* out = p.state + e * GROUND_SLOTS;
+    out[0] = s0, out[1] = sx, out[2] = sy, out[3] = sz;
+    out[4] = mxx, out[5] = mxy, out[6] = mxz, out[7] = myy, out[8] = myz, out[9] = mzz;
+    out[10] = ux, out[11] = uy, out[12] = uz, out[13] = cnt;
+}
+
+struct GroundSolveParams {
+    const double* state;    // [T,N,14]
+    double* plane;          // [T,4]: n, d
+    double* scale;          // [T]: sigma
+    float* up;              // [T,3] or null
+    float* height;          // [T] or null: -d
+    float* rms;             // [T] or null
+    float* eig;             // [T,3] or null
+    int32_t* points;        // [T] or null
+    uint8_t* code;          // [T] or null
+    double floor, spread;
+    int T, N;
+};
+
+// one rotation of the cyclic Jacobi on the pair (p, q), r the third index: the statement's formulas on named scalars
+__device__ __forceinline__ void ground_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p,
+                                              double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
+#pragma clang fp contract(off)
+    if (apq == 0.0) return;   // wave-uniform: every lane holds the same bits
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));   // theta*theta = inf: t = +-0
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    const double pp = app - t * apq, qq = aqq + t * apq;
+    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+    app = pp, aqq = qq, apq = 0.0, arp = rp, arq = rq;
+    const double a0 = c * v0p - s * v0q, b0 = s * v0p + c * v0q;
+    const double a1 = c * v1p - s * v1q, b1 = s * v1p + c * v1q;
+    const double a2 = c * v2p - s * v2q, b2 = s * v2p + c * v2q;
+    v0p = a0, v0q = b0, v1p = a1, v1q = b1, v2p = a2, v2q = b2;
+}
+
+__device__ __forceinline__ void ground_swap(double& a, double& b) {
+    const double t = a;
+    a = b, b = t;
+}
+
+__global__ void __launch_bounds__(256) ground_solve_kernel(const GroundSolveParams p) {
+#pragma clang fp contract(off)
+    const int lane = wave_lane();
+    const int64_t t = wave_item();
+    if (t >= p.T) return;   // wave-uniform
+    const double* row = p.state + t * p.N * GROUND_SLOTS;
+    double sum[GROUND_SLOTS] = {};
+    for (int n = lane; n < p.N; n += 64) {
+        const double* s = row + (int64_t)n * GROUND_SLOTS;
+#pragma unroll
+        for (int i = 0; i < GROUND_SLOTS; ++i) sum[i] += s[i];
+    }
+    wave_sums(sum);
+    const auto& [W, sx, sy, sz, mxx, mxy, mxz, myy, myz, mzz, ux, uy, uz, cnt] = sum;
+    const double mu0 = sx / W, mu1 = sy / W, mu2 = sz / W;
+    const double c00 = mxx / W - mu0 * mu0, c01 = mxy / W - mu0 * mu1, c02 = mxz / W - mu0 * mu2;
+    const double c11 = myy / W - mu1 * mu1, c12 = myz / W - mu1 * mu2, c22 = mzz / W - mu2 * mu2;
+    double a00 = c00, a01 = c01, a02 = c02, a11 = c11, a12 = c12, a22 = c22;
+    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;   // v[row][column]
+#pragma unroll 1
+    for (int sweep = 0; sweep < GROUND_SWEEPS; ++sweep) {
+        ground_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);   // (0,1), r = 2
+        ground_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);   // (0,2), r = 1
+        ground_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);   // (1,2), r = 0
+    }
+    // ascending, equal eigenvalues keeping their order: (0,1), (1,2), (0,1), each on a strict >; column k of v goes with lambda k
+    double l0 = a00, l1 = a11, l2 = a22;
+    if (l0 > l1) ground_swap(l0, l1), ground_swap(v00, v01), ground_swap(v10, v11), ground_swap(v20, v21);
+    if (l1 > l2) ground_swap(l1, l2), ground_swap(v01, v02), ground_swap(v11, v12), ground_swap(v21, v22);
+    if (l0 > l1) ground_swap(l0, l1), ground_swap(v00, v01), ground_swap(v10, v11), ground_swap(v20, v21);
+    const double floor2 = p.floor * p.floor, spread2 = p.spread * p.spread;
+    const bool is_plane = l1 >= spread2 && l1 >= 9.0 * (l0 > floor2 ? l0 : floor2);
+    const bool is_line = !is_plane && l2 >= spread2;
+    const double ua = ground_dot(ux, uy, uz, v02, v12, v22);   // a = column 2
+    const double w0 = ux - ua * v02, w1 = uy - ua * v12, w2 = uz - ua * v22;
+    const double wn = frame_norm(w0, w1, w2), un = frame_norm(ux, uy, uz);
+    const bool is_body = !is_plane && !is_line && W > 0.0 && un > 0.0;
+    const int code = is_plane ? 1 : is_line ? (wn > 0.0 ? 2 : 0) : is_body ? 3 : 0;
+    double n0 = code == 1 ? v00 : code == 2 ? w0 / wn : ux / un;
+    double n1 = code == 1 ? v10 : code == 2 ? w1 / wn : uy / un;
+    double n2 = code == 1 ? v20 : code == 2 ? w2 / wn : uz / un;
+    if (ground_dot(n0, n1, n2, ux, uy, uz) < 0.0) n0 = -n0, n1 = -n1, n2 = -n2;   // the root is above the feet
+    const double d = ground_dot(n0, n1, n2, mu0, mu1, mu2);
+    const double g0 = (c00 * n0 + c01 * n1) + c02 * n2, g1 = (c01 * n0 + c11 * n1) + c12 * n2, g2 = (c02 * n0 + c12 * n1) + c22 * n2;
+    const double q = ground_dot(n0, n1, n2, g0, g1, g2);
+    const double rms = q > 0.0 ? sqrt(q) : 0.0;
+    const double sigma = rms > p.floor ? rms : p.floor;
+    if (lane != 0) return;
+    const bool ok = code != 0;
+    const double dnan = __builtin_nan("");
+    const float qnan = __builtin_nanf("");
+    p.plane[t * 4 + 0] = ok ? n0 : dnan, p.plane[t * 4 + 1] = ok ? n1 : dnan, p.plane[t * 4 + 2] = ok ? n2 : dnan;
+    p.plane[t * 4 + 3] = ok ? d : dnan;
+    p.scale[t] = ok ? sigma : dnan;
+    if (p.up) p.up[t * 3 + 0] = ok ? (float)n0 : qnan, p.up[t * 3 + 1] = ok ? (float)n1 : qnan, p.up[t * 3 + 2] = ok ? (float)n2 : qnan;
+    if (p.height) p.height[t] = ok ? (float)-d : qnan;
+    if (p.rms) p.rms[t] = ok ? (float)rms : qnan;
+    if (p.eig) p.eig[t * 3 + 0] = ok ? (float)l0 : qnan, p.eig[t * 3 + 1] = ok ? (float)l1 : qnan, p.eig[t * 3 + 2] = ok ? (float)l2 : qnan;
+    if (p.points) p.points[t] = (int32_t)cnt;   // a sum of 0.0 and small whole numbers: exact
+    if (p.code) p.code[t] = (uint8_t)code;
+}
+
+struct FramesToWorldParams {
+    const float* pose;     // [T,N,J,3] root-relative
+    const float* traj;     // [T,N,3]
+    const double* plane;   // [T,4]
+    float* pose_world;     // [T,N,J,3]
+    float* traj_world;     // [T,N,3] or null
+    int T, N, J;
+};
+
+__global__ void __launch_bounds__(256) frames_to_world_kernel(const FramesToWorldParams p) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;   // (t, n, j)
+    if (e >= (int64_t)p.T * p.N * p.J) return;
+    const int j = (int)(e % p.J);
+    const int64_t frame = e / p.J, t = frame / p.N;
+    const double n0 = p.plane[t * 4 + 0], n1 = p.plane[t * 4 + 1], n2 = p.plane[t * 4 + 2], d = p.plane[t * 4 + 3];
+    const bool alt = fabs(n0) > 0.99;   // the camera's right is too close to the normal: its forward axis instead
+    const double e0 = alt ? 0.0 : 1.0, e2 = alt ? 1.0 : 0.0, en = alt ? n2 : n0;
+    const double w0 = e0 - en * n0, w1 = 0.0 - en * n1, w2 = e2 - en * n2;
+    const double wn = frame_norm(w0, w1, w2);
+    const double x0 = w0 / wn, x1 = w1 / wn, x2 = w2 / wn;
+    const double y0 = n1 * x2 - n2 * x1, y1 = n2 * x0 - n0 * x2, y2 = n0 * x1 - n1 * x0;
+    const double r0 = (double)p.traj[frame * 3 + 0], r1 = (double)p.traj[frame * 3 + 1], r2 = (double)p.traj[frame * 3 + 2];
+    const double c0 = (double)p.pose[e * 3 + 0] + r0, c1 = (double)p.pose[e * 3 + 1] + r1, c2 = (double)p.pose[e * 3 + 2] + r2;
+    p.pose_world[e * 3 + 0] = (float)ground_dot(x0, x1, x2, c0, c1, c2);
+    p.pose_world[e * 3 + 1] = (float)ground_dot(y0, y1, y2, c0, c1, c2);
+    p.pose_world[e * 3 + 2] = (float)(ground_dot(n0, n1, n2, c0, c1, c2) - d);
+    if (j == 0 && p.traj_world) {
+        p.traj_world[frame * 3 + 0] = (float)ground_dot(x0, x1, x2, r0, r1, r2);
+        p.traj_world[frame * 3 + 1] = (float)ground_dot(y0, y1, y2, r0, r1, r2);
+        p.traj_world[frame * 3 + 2] = (float)(ground_dot(n0, n1, n2, r0, r1, r2) - d);
+    }
 }
 
 // ----------------------------------------------------------------------------------------------------------------

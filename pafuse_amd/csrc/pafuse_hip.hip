@@ -2597,6 +2597,78 @@ int pafuse_focal_solve(const double* state, int32_t T, int32_t N, const float* c
     return launch<focal_solve_kernel>("focal_solve_kernel", grid, 256, 0, (hipStream_t)stream, m);
 }
 
+// the ground plane of a video from its foot contacts and the poses in world space (foot_contacts_kernel, ground_sums_kernel,
+// ground_solve_kernel, frames_to_world_kernel): one kernel each, the argument checks come before the first HIP call
+static bool ground_positive(double v) { return std::isfinite(v) && v > 0.0; }
+
+int pafuse_foot_contacts(const float* pose, const float* traj, const int32_t* points, int32_t T, int32_t N, int32_t J, int32_t K,
+                         int32_t radius, double speed, float* foot, float* foot_speed, float* contact, void* stream) {
+    if (!pose || !traj || !points || !foot || !contact)
+        return fail(PAFUSE_E_ARG, "foot_contacts: pose, traj, points, foot and contact are needed (foot_speed may be null)");
+    if (T < 1 || N < 1 || J < 1) return fail(PAFUSE_E_ARG, "foot_contacts: bad size (T=%d N=%d J=%d)", T, N, J);
+    if (K < 1 || K > GROUND_MAX_POINTS) return fail(PAFUSE_E_ARG, "foot_contacts: K = %d outside 1 .. %d", K, GROUND_MAX_POINTS);
+    if (radius < 1 || radius > 64) return fail(PAFUSE_E_ARG, "foot_contacts: radius %d outside 1 .. 64", radius);
+    if (!ground_positive(speed)) return fail(PAFUSE_E_ARG, "foot_contacts: speed %g is not finite and > 0 (metres per frame)", speed);
+    const int64_t rows = (int64_t)T * N * K;
+    if ((rows + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "foot_contacts: grid out of range");
+    StreamDevice on_stream_device(stream);
+    FootContactsParams m{};
+    m.pose = pose, m.traj = traj, m.points = points, m.foot = foot, m.foot_speed = foot_speed, m.contact = contact;
+    m.speed = speed, m.T = T, m.N = N, m.J = J, m.K = K, m.radius = radius;
+    return launch<foot_contacts_kernel>("foot_contacts_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
+}
+
+int pafuse_ground_sums(const float* foot, const float* contact, const float* traj, const double* plane, const double* scale,
+                       int32_t T, int32_t N, int32_t K, double gate, double* state, void* stream) {
+    if (!foot || !contact || !traj || !state) return fail(PAFUSE_E_ARG, "ground_sums: foot, contact, traj and state are needed");
+    if ((plane == nullptr) != (scale == nullptr)) return fail(PAFUSE_E_ARG, "ground_sums: plane and scale come together (or neither: the first pass)");
+    if (T < 1 || N < 1) return fail(PAFUSE_E_ARG, "ground_sums: bad size (T=%d N=%d)", T, N);
+    if (K < 1 || K > GROUND_MAX_POINTS) return fail(PAFUSE_E_ARG, "ground_sums: K = %d outside 1 .. %d", K, GROUND_MAX_POINTS);
+    if (!ground_positive(gate)) return fail(PAFUSE_E_ARG, "ground_sums: gate %g is not finite and > 0", gate);
+    if ((uintptr_t)state % 8 || (uintptr_t)plane % 8 || (uintptr_t)scale % 8)
+        return fail(PAFUSE_E_ARG, "ground_sums: state, plane and scale must be 8-byte aligned");
+    const int64_t rows = (int64_t)T * N;
+    if ((rows + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "ground_sums: grid out of range");
+    StreamDevice on_stream_device(stream);
+    GroundSumsParams m{};
+    m.foot = foot, m.contact = contact, m.traj = traj, m.plane = plane, m.scale = scale, m.state = state;
+    m.gate = gate, m.T = T, m.N = N, m.K = K;
+    return launch<ground_sums_kernel>("ground_sums_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
+}
+
+int pafuse_ground_solve(const double* state, int32_t T, int32_t N, double floor, double spread, double* plane, double* scale,
+                        float* up, float* camera_height, float* rms, float* eig, int32_t* points, uint8_t* code, void* stream) {
+    if (!state || !plane || !scale)
+        return fail(PAFUSE_E_ARG, "ground_solve: state, plane and scale are needed (up, camera_height, rms, eig, points, code may be null)");
+    if (T < 1 || N < 1) return fail(PAFUSE_E_ARG, "ground_solve: bad size (T=%d N=%d)", T, N);
+    if (!ground_positive(floor)) return fail(PAFUSE_E_ARG, "ground_solve: floor %g is not finite and > 0 (metres)", floor);
+    if (!ground_positive(spread)) return fail(PAFUSE_E_ARG, "ground_solve: spread %g is not finite and > 0 (metres)", spread);
+    if ((uintptr_t)state % 8 || (uintptr_t)plane % 8 || (uintptr_t)scale % 8)
+        return fail(PAFUSE_E_ARG, "ground_solve: state, plane and scale must be 8-byte aligned");
+    unsigned grid;
+    if (int rc = wave_grid("ground_solve", (int64_t)T, grid)) return rc;   // one wave per t
+    StreamDevice on_stream_device(stream);
+    GroundSolveParams m{};
+    m.state = state, m.plane = plane, m.scale = scale, m.up = up, m.height = camera_height, m.rms = rms, m.eig = eig;
+    m.points = points, m.code = code, m.floor = floor, m.spread = spread, m.T = T, m.N = N;
+    return launch<ground_solve_kernel>("ground_solve_kernel", grid, 256, 0, (hipStream_t)stream, m);
+}
+
+int pafuse_frames_to_world(const float* pose, const float* traj, const double* plane, int32_t T, int32_t N, int32_t J,
+                           float* pose_world, float* traj_world, void* stream) {
+    if (!pose || !traj || !plane || !pose_world)
+        return fail(PAFUSE_E_ARG, "frames_to_world: pose, traj, plane and pose_world are needed (traj_world may be null)");
+    if (T < 1 || N < 1 || J < 1) return fail(PAFUSE_E_ARG, "frames_to_world: bad size (T=%d N=%d J=%d)", T, N, J);
+    if ((uintptr_t)plane % 8) return fail(PAFUSE_E_ARG, "frames_to_world: plane must be 8-byte aligned");
+    const int64_t rows = (int64_t)T * N * J;
+    if ((rows + 255) / 256 > 0x7fffffff) return fail(PAFUSE_E_ARG, "frames_to_world: grid out of range");
+    StreamDevice on_stream_device(stream);
+    FramesToWorldParams m{};
+    m.pose = pose, m.traj = traj, m.plane = plane, m.pose_world = pose_world, m.traj_world = traj_world;
+    m.T = T, m.N = N, m.J = J;
+    return launch<frames_to_world_kernel>("frames_to_world_kernel", blocks_for(rows), 256, 0, (hipStream_t)stream, m);
+}
+
 // the frame-level errors of the per-frame pose against ground truth (frame_errors_kernel) and their sums over the frames
 // (frame_errors_reduce_kernel): the argument checks come before the first HIP call
 static_assert(FRAME_MAX_PARTS == PAFUSE_MAX_PARTS, "frame_errors_kernel keeps one register slot per part");

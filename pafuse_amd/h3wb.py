@@ -121,6 +121,17 @@ def bone_tables(dataset_or_n_face=68, root_added=True, left=None, right=None):
     return parent, mirror
 
 
+def foot_points(dataset_or_root_added=True):
+    """-> int32 [6]: the toe and heel points of both feet, what the ground estimate takes as foot points (pafuse_amd.ground,
+    DESIGN.md section 6q): keypoints 17 .. 22 of the H3WB order (left big toe, small toe, heel; right likewise), 18 .. 23 with
+    the inserted root.  NOT the ankles: they ride about 8 cm above the floor.  ``dataset_or_root_added``: True / False, or a
+    dataset of this package - they all carry the inserted root (134 joints)."""
+    ds = dataset_or_root_added
+    root_added = bool(ds) if isinstance(ds, (bool, np.bool_)) else True
+    s = 1 if root_added else 0
+    return np.arange(17 + s, 23 + s, dtype=np.int32)
+
+
 def with_root_joint(arr, hips=(11, 12)):
     """[N,133,c] -> [N,134,c] (float64, like the reference's np.zeros buffer): keypoint 0 = midpoint of the hips."""
     out = np.zeros((arr.shape[0], arr.shape[1] + 1, arr.shape[2]))
@@ -257,6 +268,36 @@ def fetch(subjects, keypoints, dataset, stride=1, action_filter=None, parse_3d_p
     return (cams or None), (poses_3d or None), poses_2d
 
 
+def fetch_orientations(subjects, keypoints, dataset, action_filter=None):
+    """The camera-to-world quaternion (w, x, y, z) of every video, in the order of :func:`fetch`'s lists; None for a camera
+    that carries no orientation."""
+    out = []
+    for subject in subjects:
+        for action, per_cam in keypoints[subject].items():
+            if action_filter is not None and not any(action.startswith(a) for a in action_filter):
+                continue
+            subject_cams = dataset.cameras().get(subject, [])
+            for i in range(len(per_cam)):
+                q = subject_cams[i].get("orientation") if i < len(subject_cams) else None
+                out.append(None if q is None else np.asarray(q, dtype=np.float64))
+    return out
+
+
+def camera_up(orientation):
+    """the world's up (0, 0, 1) in the camera space of a camera whose camera-to-world rotation is the unit quaternion
+    `orientation` (w, x, y, z): rotated by its inverse (the reference's world_to_camera, common/camera.py)"""
+    import torch
+    from .harness import camera_to_world
+    q = np.asarray(orientation, dtype=np.float64)
+    return camera_to_world(torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64), q * np.array([1.0, -1.0, -1.0, -1.0])).numpy()
+
+
+def up_angle(a, b):
+    """the angle between two directions, degrees (NaN for a NaN direction)"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return float(np.rad2deg(np.arctan2(np.linalg.norm(np.cross(a, b)), np.dot(a, b))))
+
+
 def iter_sequences(cams, poses_3d, poses_2d):
     """One (cam [1,9], seq_3d [1,N,J,3], seq_2d [1,N,J,2]) triple per video, batch axis added, no augmentation."""
     from itertools import zip_longest
@@ -301,7 +342,7 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
                     batch_size=2, group=None, log=print, action=None, hypothesis_chunk=None, p2=False, seam_profile=False, focal=None,
                     repair=None, drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None,
                     pose_smooth_floor=1e-3, bone_lengths=None, bone_iterations=16, corrupt=None, swap=None, screen=None,
-                    screen_gate=4.0, screen_floor=0.005, distract=None, track=False):
+                    screen_gate=4.0, screen_floor=0.005, distract=None, track=False, ground=None, ground_speed=0.015, orientations=None):
     """The frame-level evaluation of every video, looped like :func:`evaluate`: harness.evaluate_frames per (camera, sequence) -
     one pose per video frame (``aggregate``, ``stride``; None: un-strided clips laid end to end), optionally its fitted
     camera-space root (``trajectory``: True or a smoothing radius) - scored on the device; the sums and counts added over the
@@ -334,7 +375,14 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
     file, or with ``track=True`` (a dict: harness.track_people's parameters) track 0 of the device tracker; per video
     tracks.track_error of what was lifted is logged.  What the tracker buys in 3-D error needs a real checkpoint and has not
     been measured.
+    ``ground`` (True or a radius 1 .. 64, with ``trajectory``; ``ground_speed`` metres per frame) also finds the ground plane of
+    every video from its resting feet (harness.evaluate_frames(ground=...)) and logs, per video and step, the code, the camera
+    height and the number of contact points of the prediction, and the same estimator run on the GROUND-TRUTH 3-D (which needs
+    no checkpoint).  ``orientations`` (:func:`fetch_orientations`: one camera-to-world quaternion per video, or None) adds the
+    angle between each estimated up and the camera's true up.  The defaults are not tuned values; what the estimate is worth on
+    a real checkpoint has not been measured - that angle is the tool for it.
     On synthetic weights the numbers mean nothing."""
+    import torch
     from . import detections, detscreen, harness, tracks
     if distract is not None and (not isinstance(distract, (tuple, list)) or len(distract) != 2):
         raise ValueError(f"distract must be (people, seed), got {distract!r}")
@@ -357,7 +405,20 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
                                       corrupt=None if corrupt is None else (corrupt[0], corrupt[1], corrupt[2], int(corrupt[3]) + video),
                                       swap=None if swap is None else (swap[0], swap[1], int(swap[2]) + video), screen=screen,
                                       screen_gate=screen_gate, screen_floor=screen_floor,
-                                      distract=None if distract is None else (distract[0], int(distract[1]) + video), track=track)
+                                      distract=None if distract is None else (distract[0], int(distract[1]) + video), track=track,
+                                      ground=ground, ground_speed=ground_speed)
+        if ground is not None:
+            found, got = got[-1], got[:-1]
+            gt = torch.as_tensor(seq_3d[0].astype("float32"))
+            truth = harness.estimate_ground((gt - gt[:, :1]).unsqueeze(0), gt[:, 0].unsqueeze(0), radius=3 if ground is True else ground,
+                                            speed=ground_speed)
+            true_up = None if orientations is None or orientations[video] is None else camera_up(orientations[video])
+            off = lambda up: "n/a" if true_up is None else "%.3f" % up_angle(up, true_up)
+            for t in range(found["up"].shape[0]):
+                log("video %d step %d : ground code %d, camera height %.3f m, %d contact points, angle to the camera's true up %s deg"
+                    % (video, t, int(found["ground_code"][t]), float(found["camera_height"][t]), int(found["ground_points"][t]), off(found["up"][t])))
+            log("video %d ground truth 3-D : ground code %d, camera height %.3f m, %d contact points, angle to the camera's true up %s deg"
+                % (video, int(truth["ground_code"][0]), float(truth["camera_height"][0]), int(truth["ground_points"][0]), off(truth["up"][0])))
         if bone_lengths is not None:
             held, got = got[-1], got[:-1]
             gap = (held["bone_length"].double() - held["bone_length_gt"].double()).abs()

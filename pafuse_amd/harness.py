@@ -3,6 +3,8 @@
 accumulators - with tensors kept on the HIP device.  SURVEY.md section 8f rows n1/n3 (partial: no dataset files
 or Hydra here; the caller hands in arrays).
 """
+import math
+
 import torch
 
 from .evaluate import (accumulate_frames, accumulate_partials, accumulate_poses, accumulate_spread, aggregate_poses_sharded,
@@ -162,7 +164,8 @@ def screen_detections(seq_2d, conf, kps_left=None, kps_right=None, mirror=None, 
 def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, group=None, aggregate=None, cam=None, traj=None,
                    hypothesis_chunk=None, spread=None, conf=None, stride=None, trajectory=None, focal=None, repair=None,
                    repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None, pose_smooth_floor=1e-3,
-                   bone_lengths=None, bone_iterations=16, screen=None, screen_gate=4.0, screen_floor=0.005):
+                   bone_lengths=None, bone_iterations=16, screen=None, screen_gate=4.0, screen_floor=0.005, ground=None,
+                   ground_speed=0.015, ground_passes=3, ground_gate=2.5, ground_floor=0.005, ground_spread=0.03, ground_points=None):
     """In-the-wild inference for one 2-D keypoint sequence [N,J,2] (already screen-normalised): flip copy, 27-frame
     clips, batched sampling with ``input_3d=None``, whole-body poses (in_the_wild/utils.py:322-376).
     Returns a CPU tensor [clips, T, P, F, J, 3].  The model is taken as it is configured (``model.noise``, ``model.noise_seed``).
@@ -300,7 +303,21 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     |length - L| of every frame before and after, in metres.  ``std`` / ``cov`` stay what they were: the covariance is not
     updated.  16 sweeps and the 1 mm floor are defaults, not tuned values.  One length per bone per video, no joint-angle
     limits; the estimated lengths are biased long where the noise is comparable to the bone (pass your own there).  What it
-    buys on real weights has NOT been measured."""
+    buys on real weights has NOT been measured.
+
+    ``ground`` (with ``trajectory``; None: everything above, unchanged; True: radius 3; or a radius 1 .. 64) finds WHICH WAY IS UP
+    from the video itself, on the device behind the trajectory fit and its smoother - so on the smoothed, bone-constrained
+    pose that is returned (:func:`estimate_ground`; pafuse_amd.ground): a foot point whose local line
+    moves slower than ``ground_speed`` metres per FRAME (the frame rate enters here) rests on the ground, the ground is the
+    plane through those points, re-weighted ``ground_passes`` times; a person standing gives a line, and the plane through it
+    closest to the body's own up.  ``ground_points``: the foot joints (None: h3wb.foot_points, the six toe and heel points of
+    the 134-joint layout).  Added keys (GROUND_KEYS): ``"up"`` [T,3] the unit normal in camera space, ``"camera_height"`` [T]
+    metres, ``"ground_rms"`` [T], ``"ground_eig"`` [T,3], ``"ground_points"`` [T] int32, ``"ground_code"`` [T] uint8 (1 plane, 2
+    line, 3 the body's own up, 0 none: NaN), ``"ground_plane"`` [T,4] float64, ``"foot"`` [T,N,K,3], ``"foot_speed"`` and
+    ``"contact"`` [T,N,K], and ``"pose_world"`` [T,N,J,3] / ``"traj_world"`` [T,N,3]: pose + traj with z up and the ground at
+    z = 0 - the height of a joint is its third component.  One plane per video; the pose is rotated, not corrected (no foot
+    locking); world x is the camera's right, not a direction of travel.  Every default is a default, not a tuned value, and
+    nobody has run it on real video."""
     smooth = _trajectory_radius(trajectory)
     pose_smooth = _pose_smooth_radius(pose_smooth, pose_smooth_floor)
     if pose_smooth is not None:
@@ -319,6 +336,9 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
         if not isinstance(bones["lengths"], str) and bones["lengths"].shape[-1] != len(bones["tables"][0]):
             raise ValueError(f"bone_lengths must be [J] or [T,J] with J = {len(bones['tables'][0])}, got {tuple(bones['lengths'].shape)}")
     _focal_mode(focal)
+    ground = _ground_spec(ground, ground_speed, ground_passes, ground_gate, ground_floor, ground_spread, ground_points)
+    if ground is not None and trajectory is None:
+        raise ValueError("ground needs a trajectory: the ground is found in camera space (harness.estimate_ground takes poses and roots a caller has)")
     repair = _repair_radius(repair, repair_threshold)
     path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, getattr(model, "frames", None), path_scope)
     if repair is not None and conf is None:
@@ -368,7 +388,7 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     dev = next(model.parameters()).device
     if repair is None and screen is None:
         return _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, trajectory, smooth, focal, dev, path_weight, path_scope, pose_smooth, bones)
+                               spread, conf, stride, trajectory, smooth, focal, dev, path_weight, path_scope, pose_smooth, bones, ground)
     # the callees cut and flip on the host: the screened and repaired pair takes the place of the input, whole, before either
     seq_2d = seq_2d.squeeze(0) if seq_2d.dim() == 4 else seq_2d
     screened = fixed = None
@@ -383,7 +403,7 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
         seq_2d, conf = fixed["x2d"], fixed["conf"]
     out = _infer_sequence(model, dataset, seq_2d.cpu(), kps_left, kps_right, batch_size, group, aggregate, cam, traj,
                           hypothesis_chunk, spread, conf.cpu(), stride, trajectory, smooth, focal, dev, path_weight, path_scope,
-                          pose_smooth, bones)
+                          pose_smooth, bones, ground)
     if isinstance(out, dict):
         if screened is not None:
             out["screened"] = screened["status"].cpu()
@@ -425,7 +445,8 @@ def _path_batch(sampler, dataset, x2d, x2d_flip, traj, cam, conf, fit, path_weig
 
 
 def _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                    conf, stride, trajectory, smooth, focal, dev, path_weight=None, path_scope="clip", pose_smooth=None, bones=None):
+                    conf, stride, trajectory, smooth, focal, dev, path_weight=None, path_scope="clip", pose_smooth=None, bones=None,
+                    ground=None):
     """infer_sequence behind its argument checks (and behind the repair of the detections, when one was asked for)"""
     fit = aggregate == "reproj_fit"
     if stride is None and path_scope == "video":      # one path along the video: per-frame results, the clips of cut_clips
@@ -433,7 +454,7 @@ def _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, gro
     if stride is not None:
         return _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
                              spread, conf, int(stride), dev, trajectory is not None, smooth, focal, path_weight, path_scope, pose_smooth,
-                             bones)
+                             bones, ground)
     x2d = cut_clips(seq_2d, model.frames).to(dev)
     x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), model.frames).to(dev)
     sampler = ShardedSampler(model, group)
@@ -505,18 +526,18 @@ def cut_windows(seq, starts, frames=27):
 
 def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
                   conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip", pose_smooth=None,
-                  bones=None):
+                  bones=None, ground=None):
     """infer_sequence(stride=...): sliding windows pooled into one pose per video frame (arguments already checked)"""
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, dev, trajectory, smooth, focal, path_weight, path_scope, pose_smooth, bones)
+                               spread, conf, stride, dev, trajectory, smooth, focal, path_weight, path_scope, pose_smooth, bones, ground)
     return {k: v.cpu() for k, v in out.items()}
 
 
 def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
                          conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip",
-                         pose_smooth=None, bones=None):
+                         pose_smooth=None, bones=None, ground=None):
     """_infer_frames with its result left on the device (evaluate_frames scores it there); pose_smooth: None or (radius, floor);
-    bones: None or _bone_spec's dict with its tables"""
+    bones: None or _bone_spec's dict with its tables; ground: None or _ground_spec's dict"""
     from . import ops
     from .windows import coverage, window_starts
     asked = spread                  # what the caller wants returned; the pose smoother and the bones need the covariance whatever that is
@@ -611,6 +632,8 @@ def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size
         out.update(_constrain_bones(out["pose"].contiguous(), cov, bones))
     if trajectory:  # the root of the pose that is returned, on the device before anything crosses to the host
         out.update(_fit_trajectory(out["pose"], seq_2d.to(dev), cam, None if frame_conf is None else frame_conf.to(dev), smooth, focal))
+    if ground is not None:  # behind the fit and its smoother: the plane through the resting feet of the pose and roots that are returned
+        out.update(_estimate_ground(out["pose"], out["traj"], ground))
     return out
 
 
@@ -869,6 +892,90 @@ def estimate_focal(poses, seq_2d, cam=None, conf=None, device="cuda"):
     dev = poses.device if poses.is_cuda else torch.device(device)
     out = _estimate_focal(poses.to(dev), seq_2d.to(dev), cam.to(dev), None if conf is None else conf.to(dev))
     return {k: v.cpu() for k, v in out.items()}
+
+
+GROUND_KEYS = ("up", "camera_height", "ground_rms", "ground_eig", "ground_points", "ground_code", "ground_plane", "foot", "foot_speed",
+               "contact", "pose_world", "traj_world")
+
+
+def _ground_spec(ground, speed=0.015, passes=3, gate=2.5, floor=0.005, spread=0.03, points=None):
+    """infer_sequence's `ground` and its companions: None -> None, True -> radius 3, an integer r in 1 .. 64 -> r; -> the
+    keyword arguments of ops.estimate_ground (defaults, not tuned values), refused here before anything touches the device"""
+    if ground is None:
+        return None
+    if ground is True:
+        ground = 3
+    if isinstance(ground, bool) or not isinstance(ground, int) or not 1 <= ground <= 64:
+        raise ValueError(f"ground must be None, True (radius 3) or a radius in 1 .. 64 frames, got {ground!r}")
+    for name, v in (("ground_speed", speed), ("ground_gate", gate), ("ground_floor", floor), ("ground_spread", spread)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v > 0):
+            raise ValueError(f"{name} must be a number that is finite and > 0, got {v!r}")
+    if isinstance(passes, bool) or not isinstance(passes, int) or not 1 <= passes <= 8:
+        raise ValueError(f"ground_passes must be an integer in 1 .. 8, got {passes!r}")
+    return dict(points=points, radius=ground, speed=float(speed), passes=passes, gate=float(gate), floor=float(floor), spread=float(spread))
+
+
+def _estimate_ground(pose, traj, spec):
+    """device tensors -> the ground keys of infer_sequence / estimate_ground (GROUND_KEYS), on the device"""
+    from . import ops
+    spec = dict(spec)
+    points = spec.pop("points")
+    if points is None:
+        from .h3wb import foot_points
+        points = foot_points(True)
+        if pose.shape[2] != 134:
+            raise ValueError(f"ground: the default foot points are those of the 134-joint layout, the pose has {pose.shape[2]} joints: pass points")
+    m = ops.estimate_ground(pose.contiguous(), traj.contiguous(), points, want=[k for k in ops.GROUND_OUTPUTS if k != "scale"], **spec)
+    m["ground_plane"] = m.pop("plane")
+    return {k: m[k] for k in GROUND_KEYS}
+
+
+@torch.no_grad()
+def estimate_ground(poses, traj, points=None, radius=3, speed=0.015, passes=3, gate=2.5, floor=0.005, spread=0.03, device="cuda"):
+    """Which way is up, for poses and roots a caller already has: ``poses`` [T,N,J,3] whole-body and root-relative, ``traj``
+    [T,N,3] their camera-space roots (NaN: none) - ``infer_sequence(trajectory=...)``'s "pose" and "traj", or
+    :func:`fit_trajectory`'s - ``points`` the foot joints (None: h3wb.foot_points, the six toe and heel points of the 134-joint
+    layout; not the ankles, which ride above the floor), ``radius`` 1 .. 64 frames of the local line through every foot
+    point, ``speed`` in metres per FRAME below which a foot counts as resting (the frame rate enters here), ``passes`` 1 .. 8
+    re-weightings with ``gate`` times the plane's own rms (at least ``floor`` metres), ``spread`` metres the extent the contacts
+    must have for a plane (or, failing that, a line).  On the device (ops.estimate_ground; pafuse_amd.ground states the
+    arithmetic).  Returns a dict of CPU tensors, the keys ``infer_sequence(ground=...)`` adds (GROUND_KEYS): ``"up"``,
+    ``"camera_height"``, ``"ground_rms"``, ``"ground_eig"``, ``"ground_points"``, ``"ground_code"`` (1 plane, 2 line, 3 the
+    body's own up, 0 none: NaN everywhere), ``"ground_plane"``, ``"foot"``, ``"foot_speed"``, ``"contact"``, ``"pose_world"`` and
+    ``"traj_world"``.  One plane per video: no stairs, no changing slope, no moving camera; a slow foot in the air counts until
+    the re-weighting drops it; codes 2 and 3 lean on the lifted body's own up and inherit its lean; the pose is rotated, not
+    corrected.  Every default is a default, not a tuned value; nobody has run it on real video."""
+    spec = _ground_spec(radius if radius is not True else None, speed, passes, gate, floor, spread, points)
+    if spec is None:
+        raise ValueError(f"radius must be a radius in 1 .. 64 (frames), got {radius!r}")
+    poses = torch.as_tensor(poses, dtype=torch.float32)
+    traj = torch.as_tensor(traj, dtype=torch.float32)
+    if poses.dim() != 4 or poses.shape[-1] != 3 or 0 in poses.shape or tuple(traj.shape) != (*poses.shape[:2], 3):
+        raise ValueError(f"poses must be [T,N,J,3] and traj [T,N,3], got {tuple(poses.shape)} and {tuple(traj.shape)}")
+    dev = poses.device if poses.is_cuda else torch.device(device)
+    out = _estimate_ground(poses.to(dev), traj.to(dev), spec)
+    return {k: v.cpu() for k, v in out.items()}
+
+
+@torch.no_grad()
+def frames_to_world(poses, traj, plane, device="cuda"):
+    """Camera space to world space with a plane a caller has: ``poses`` [T,N,J,3] root-relative, ``traj`` [T,N,3], ``plane`` [T,4]
+    float64 - :func:`estimate_ground`'s "ground_plane" - or [4], ONE plane for every step (its last row, say: the plane of the
+    fully denoised step).  ops.frames_to_world.  Returns a dict of CPU tensors ``"pose_world"`` [T,N,J,3] and ``"traj_world"``
+    [T,N,3]: z up, the ground at z = 0, x the camera's right levelled; NaN in gives NaN out."""
+    from . import ops
+    poses = torch.as_tensor(poses, dtype=torch.float32)
+    traj = torch.as_tensor(traj, dtype=torch.float32)
+    if poses.dim() != 4 or poses.shape[-1] != 3 or 0 in poses.shape or tuple(traj.shape) != (*poses.shape[:2], 3):
+        raise ValueError(f"poses must be [T,N,J,3] and traj [T,N,3], got {tuple(poses.shape)} and {tuple(traj.shape)}")
+    plane = torch.as_tensor(plane, dtype=torch.float64)
+    if tuple(plane.shape) == (4,):
+        plane = plane.expand(poses.shape[0], 4)
+    if tuple(plane.shape) != (poses.shape[0], 4):
+        raise ValueError(f"plane must be [T,4] = {(poses.shape[0], 4)} or [4], got {tuple(plane.shape)}")
+    dev = poses.device if poses.is_cuda else torch.device(device)
+    pose_world, traj_world = ops.frames_to_world(poses.to(dev).contiguous(), traj.to(dev).contiguous(), plane.to(dev).contiguous())
+    return {"pose_world": pose_world.cpu(), "traj_world": traj_world.cpu()}
 
 
 def load_pifpaf_keypoints(path, num_kps=134, with_conf=False):
@@ -1157,7 +1264,7 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
                     conf=None, batch_size=2, group=None, hypothesis_chunk=None, p2=False, per_frame=False, focal=None, repair=None,
                     drop=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None, pose_smooth_floor=1e-3,
                     bone_lengths=None, bone_iterations=16, corrupt=None, swap=None, screen=None, screen_gate=4.0, screen_floor=0.005,
-                    distract=None, track=False):
+                    distract=None, track=False, ground=None, ground_speed=0.015):
     """One video scored at the level of frames: the frames path of :func:`infer_sequence` - ONE pose per video frame, pooled
     over the windows that cover it - against the ground truth, on the device before anything crosses to the host
     (evaluate.frame_metrics; pafuse_amd.framemetrics states the arithmetic).
@@ -1218,8 +1325,15 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     the existing ``mpjpe`` / ``accel`` columns score it, the trajectory is fitted on it.  One more, last element is returned, a
     dict of CPU tensors: ``"bone_length"`` [J] the lengths held at the last step, ``"bone_length_gt"`` [J] the same kernel on
     the ground truth (a [1,N,J,3] pose without a covariance; NaN: no bone), and ``"bone_dev_free"`` / ``"bone_dev"`` [T]: the
-    mean over the bones of the bone-length standard deviation, in mm, of the free and of the constrained pose."""
+    mean over the bones of the bone-length standard deviation, in mm, of the free and of the constrained pose.
+
+    ``ground`` (True, or a radius 1 .. 64; with ``trajectory``; None: everything above, unchanged) and ``ground_speed`` also find
+    the ground plane of the video, infer_sequence(ground=..., ground_speed=...), behind the trajectory fit.  The metrics are not
+    changed by it; one more, last element is returned, a dict of CPU tensors with infer_sequence's ground keys (GROUND_KEYS)."""
     _focal_mode(focal)
+    ground = _ground_spec(ground, ground_speed)
+    if ground is not None and trajectory is None:
+        raise ValueError("ground needs a trajectory: the ground is found in camera space")
     pose_smooth = _pose_smooth_radius(pose_smooth, pose_smooth_floor)
     if pose_smooth is not None:
         pose_smooth = (pose_smooth, float(pose_smooth_floor))
@@ -1322,7 +1436,8 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     gt_wb = (seq_3d - seq_3d[:, :1]).to(dev)                        # joint 0 at 0, exactly
     out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam,
                                gt_root if aggregate == "reproj" else None, hypothesis_chunk, None, conf, stride, dev,
-                               trajectory is not None, smooth, focal, path_weight, path_scope, pose_smooth, bones)
+                               trajectory is not None, smooth, focal, path_weight, path_scope, pose_smooth, bones, ground)
+    found = {k: out[k].cpu() for k in GROUND_KEYS} if ground is not None else None
     estimate = {k: out[k].cpu() for k in ("focal", "focal_r2", "focal_frames", "cam")} if focal is not None else None
     held = None
     if bones is not None:           # the lengths held beside the ground truth's, and what the constraint did to the known diagnostic
@@ -1338,7 +1453,8 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
                       p2=p2, per_frame=per_frame)
     maps = {k: m.pop(k).cpu() for k in ("err", "cnt") if k in m}
     sums, counts = {k: v[0].cpu() for k, v in m.items()}, {k: v[1].cpu() for k, v in m.items()}
-    tail = (() if estimate is None else (estimate,)) + (() if seen is None else (seen,)) + (() if held is None else (held,))
+    tail = ((() if estimate is None else (estimate,)) + (() if seen is None else (seen,)) + (() if held is None else (held,))
+            + (() if found is None else (found,)))
     if per_frame:
         from .evaluate import frame_metric_names
         maps["names"] = frame_metric_names(dataset)

@@ -1990,6 +1990,169 @@ def estimate_focal(pose, x2d, cam, conf=None, want=FOCAL_OUTPUTS):
     return focal_solve(focal_sums(pose, x2d, cam, conf=conf), cam, want=want)
 
 
+# ------------------------------------------------------------------ which way is up: the ground plane from the foot contacts
+GROUND_SLOTS, GROUND_MAX_POINTS = 14, 16
+GROUND_SOLVE_OUTPUTS = ("plane", "scale", "up", "camera_height", "ground_rms", "ground_eig", "ground_points", "ground_code")
+GROUND_OUTPUTS = GROUND_SOLVE_OUTPUTS + ("foot", "foot_speed", "contact", "pose_world", "traj_world")
+_GROUND_CACHE_MAX = 16
+_ground_cache = {}  # (the points' bytes, device) -> their int32 device copy
+
+
+def ground_points(points, J, device=None):
+    """The foot points of the ground estimate, validated on the host: an integer sequence, numpy array or tensor of 1 .. 16
+    joints, each in [0, J) (h3wb.foot_points gives the six toe and heel points) -> int32 numpy [K]; with `device` its cached
+    int32 copy there."""
+    import numpy as np
+    if isinstance(points, torch.Tensor):
+        _need(not points.dtype.is_floating_point and points.dtype != torch.bool, "ground: points must be integers")
+        points = points.detach().cpu().numpy()
+    points = np.asarray(points)
+    _need(points.ndim == 1 and points.dtype.kind in "iu" and 1 <= points.size <= GROUND_MAX_POINTS,
+          f"ground: points must be 1 .. {GROUND_MAX_POINTS} integers, got {points.dtype} {points.shape}")
+    _need(bool(((points >= 0) & (points < int(J))).all()), f"ground: every point must be a joint of 0 .. {int(J) - 1}, got {points.tolist()}")
+    points = np.ascontiguousarray(points.astype(np.int32))
+    if device is None:
+        return points
+    key = (points.tobytes(), str(device))
+    hit = _ground_cache.get(key)
+    if hit is None:
+        if len(_ground_cache) >= _GROUND_CACHE_MAX:
+            _ground_cache.pop(next(iter(_ground_cache)))
+        hit = _ground_cache[key] = torch.from_numpy(points).to(device)
+    return hit
+
+
+def _need_metres(who, name, value):
+    ok = not isinstance(value, bool) and isinstance(value, (int, float)) and math.isfinite(float(value)) and float(value) > 0.0
+    _need(ok, f"{who}: {name} must be a number that is finite and > 0, got {value!r}")
+    return float(value)
+
+
+def _ground_pose_operands(who, pose, traj):
+    _need(isinstance(pose, torch.Tensor) and pose.dim() == 4 and pose.shape[-1] == 3, f"{who}: pose must be [T,N,J,3]")
+    T, N, J = (int(v) for v in pose.shape[:3])
+    _need(T > 0 and N > 0 and J > 0, f"{who}: T, N, J > 0")
+    _need(isinstance(traj, torch.Tensor) and tuple(traj.shape) == (T, N, 3), f"{who}: traj must be [T,N,3] = {(T, N, 3)}")
+    _need_tensors(who, [pose, traj], ())
+    return T, N, J
+
+
+def _need_plane(who, plane, scale, T, dev):
+    _need(isinstance(plane, torch.Tensor) and tuple(plane.shape) == (T, 4) and plane.dtype == torch.float64 and plane.is_cuda
+          and plane.device == dev and plane.is_contiguous(), f"{who}: plane must be a contiguous float64 [T,4] = {(T, 4)} tensor on {dev}")
+    _need(scale is None or (isinstance(scale, torch.Tensor) and tuple(scale.shape) == (T,) and scale.dtype == torch.float64
+                            and scale.device == dev and scale.is_contiguous()), f"{who}: scale must be a contiguous float64 [T] tensor on {dev}")
+
+
+def foot_contacts(pose, traj, points, radius=3, speed=0.015, want_speed=True):
+    """pafuse_foot_contacts: pose [T,N,J,3] root-relative, traj [T,N,3] the camera-space root (NaN: none), points the foot
+    joints (ground_points), radius 1 .. 64 frames, speed in metres per FRAME (finite, > 0) -> dict "foot" [T,N,K,3] the foot
+    points in camera space on their local line (NaN: no line through 3 frames), "contact" [T,N,K] the weight of a foot that
+    is not moving, (1 - (v/speed)^2)^2 below `speed` and 0 from there, and (want_speed) "foot_speed" [T,N,K] v in metres per
+    frame.  pafuse_amd.ground states the arithmetic.  0.015 and 3 are defaults, not tuned values."""
+    lib = _lib.load()
+    T, N, J = _ground_pose_operands("foot_contacts", pose, traj)
+    _need_radius("foot_contacts", radius)
+    speed = _need_metres("foot_contacts", "speed", speed)
+    pts = ground_points(points, J, pose.device)
+    K, dev = int(pts.numel()), pose.device
+    out = {"foot": torch.empty(T, N, K, 3, device=dev), "contact": torch.empty(T, N, K, device=dev)}
+    if want_speed:
+        out["foot_speed"] = torch.empty(T, N, K, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_foot_contacts(pose.data_ptr(), traj.data_ptr(), pts.data_ptr(), T, N, J, K, int(radius), speed,
+                                            out["foot"].data_ptr(), out["foot_speed"].data_ptr() if want_speed else None,
+                                            out["contact"].data_ptr(), _stream(pose)))
+    return out
+
+
+def ground_sums(foot, contact, traj, plane=None, scale=None, gate=2.5, out=None):
+    """pafuse_ground_sums: foot [T,N,K,3], contact [T,N,K] (foot_contacts), traj [T,N,3]; plane [T,4] and scale [T] float64 of
+    the previous pass's ground_solve (read on the device) or both None: the first pass -> state [T,N,14] float64 (`out`: a
+    tensor of that shape to write into).  States of several videos of one scene concatenate along N."""
+    lib = _lib.load()
+    _need(isinstance(foot, torch.Tensor) and foot.dim() == 4 and foot.shape[-1] == 3, "ground_sums: foot must be [T,N,K,3]")
+    T, N, K = (int(v) for v in foot.shape[:3])
+    _need(T > 0 and N > 0 and 1 <= K <= GROUND_MAX_POINTS, f"ground_sums: T, N > 0 and K in 1 .. {GROUND_MAX_POINTS}")
+    _need(isinstance(contact, torch.Tensor) and tuple(contact.shape) == (T, N, K) and isinstance(traj, torch.Tensor)
+          and tuple(traj.shape) == (T, N, 3), "ground_sums: contact [T,N,K] and traj [T,N,3] must match foot [T,N,K,3]")
+    _need((plane is None) == (scale is None), "ground_sums: plane and scale come together (or neither: the first pass)")
+    _need_tensors("ground_sums", [foot, contact, traj], ())
+    gate = _need_metres("ground_sums", "gate", gate)
+    dev = foot.device
+    if plane is not None:
+        _need_plane("ground_sums", plane, scale, T, dev)
+    if out is None:
+        out = torch.empty(T, N, GROUND_SLOTS, device=dev, dtype=torch.float64)
+    _need(tuple(out.shape) == (T, N, GROUND_SLOTS) and out.dtype == torch.float64 and out.device == dev and out.is_contiguous(),
+          f"ground_sums: out must be a contiguous float64 [T,N,{GROUND_SLOTS}] tensor on {dev}")
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_ground_sums(foot.data_ptr(), contact.data_ptr(), traj.data_ptr(), None if plane is None else plane.data_ptr(),
+                                          None if scale is None else scale.data_ptr(), T, N, K, gate, out.data_ptr(), _stream(foot)))
+    return out
+
+
+def ground_solve(state, floor=0.005, spread=0.03, want=GROUND_SOLVE_OUTPUTS):
+    """pafuse_ground_solve: state [T,N,14] float64 (ground_sums; several concatenated along N) -> dict with "plane" [T,4] float64
+    (the unit normal pointing up and d: a point p is n.p - d above the ground), "scale" [T] float64 (what the next pass's
+    ground_sums reads) and those of "up" [T,3], "camera_height" [T] (= -d), "ground_rms" [T], "ground_eig" [T,3] (ascending),
+    "ground_points" [T] int32 and "ground_code" [T] uint8 (1 plane, 2 line: a person standing, 3 body: the lifted body's own up,
+    0 none: NaN everywhere) named in `want`.  floor and spread in metres; 0.005 and 0.03 are defaults, not tuned values."""
+    lib = _lib.load()
+    want = tuple(want)
+    _need(all(k in GROUND_SOLVE_OUTPUTS for k in want), f"ground_solve: want holds any of {GROUND_SOLVE_OUTPUTS} - got {want}")
+    _need(isinstance(state, torch.Tensor) and state.dim() == 3 and state.shape[-1] == GROUND_SLOTS and state.dtype == torch.float64
+          and state.is_cuda and state.is_contiguous(), f"ground_solve: state must be a contiguous float64 [T,N,{GROUND_SLOTS}] tensor on a HIP device")
+    T, N = int(state.shape[0]), int(state.shape[1])
+    _need(T > 0 and N > 0, "ground_solve: T, N > 0")
+    floor, spread = _need_metres("ground_solve", "floor", floor), _need_metres("ground_solve", "spread", spread)
+    dev = state.device
+    f32, f64 = torch.float32, torch.float64
+    shapes = {"plane": ((T, 4), f64), "scale": ((T,), f64), "up": ((T, 3), f32), "camera_height": ((T,), f32), "ground_rms": ((T,), f32),
+              "ground_eig": ((T, 3), f32), "ground_points": ((T,), torch.int32), "ground_code": ((T,), torch.uint8)}
+    out = {k: torch.empty(shapes[k][0], device=dev, dtype=shapes[k][1]) for k in GROUND_SOLVE_OUTPUTS if k in want or k in ("plane", "scale")}
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.pafuse_ground_solve(state.data_ptr(), T, N, floor, spread, ptr("plane"), ptr("scale"), ptr("up"), ptr("camera_height"),
+                                           ptr("ground_rms"), ptr("ground_eig"), ptr("ground_points"), ptr("ground_code"), _stream(state)))
+    return {k: v for k, v in out.items() if k in want}
+
+
+def frames_to_world(pose, traj, plane, want_traj=True):
+    """pafuse_frames_to_world: pose [T,N,J,3] root-relative, traj [T,N,3], plane [T,4] float64 (ground_solve) ->
+    (pose_world [T,N,J,3], traj_world [T,N,3] or None): world space with z up and the ground at z = 0, x the camera's right
+    projected onto the ground.  The height of a joint above the ground is its third component.  NaN in gives NaN out."""
+    lib = _lib.load()
+    T, N, J = _ground_pose_operands("frames_to_world", pose, traj)
+    _need_plane("frames_to_world", plane, None, T, pose.device)
+    pose_world = torch.empty_like(pose)
+    traj_world = torch.empty_like(traj) if want_traj else None
+    with torch.cuda.device(pose.device):
+        _lib.check(lib.pafuse_frames_to_world(pose.data_ptr(), traj.data_ptr(), plane.data_ptr(), T, N, J, pose_world.data_ptr(),
+                                              None if traj_world is None else traj_world.data_ptr(), _stream(pose)))
+    return pose_world, traj_world
+
+
+def estimate_ground(pose, traj, points, radius=3, speed=0.015, passes=3, gate=2.5, floor=0.005, spread=0.03, want=GROUND_OUTPUTS):
+    """The chain on one stream, nothing crossing to the host: foot_contacts, `passes` (1 .. 8) times ground_sums + ground_solve -
+    every later pass re-weighting the contacts with the plane of the one before, read on the device - and frames_to_world
+    when "pose_world" or "traj_world" is wanted: 1 + 2*passes + 1 launches.  -> dict with the entries named in `want`
+    (GROUND_OUTPUTS).  One plane per step t for the whole video.  Every default is a default, not a tuned value."""
+    want = tuple(want)
+    _need(all(k in GROUND_OUTPUTS for k in want), f"estimate_ground: want holds any of {GROUND_OUTPUTS} - got {want}")
+    _need(not isinstance(passes, bool) and int(passes) == passes and 1 <= int(passes) <= 8, f"estimate_ground: passes must be an integer in 1 .. 8, got {passes!r}")
+    feet = foot_contacts(pose, traj, points, radius=radius, speed=speed, want_speed="foot_speed" in want)
+    state, sol = None, {"plane": None, "scale": None}
+    for i in range(int(passes)):
+        last = i == int(passes) - 1
+        state = ground_sums(feet["foot"], feet["contact"], traj, sol["plane"], sol["scale"], gate=gate, out=state)
+        sol = ground_solve(state, floor=floor, spread=spread, want=GROUND_SOLVE_OUTPUTS if last else ("plane", "scale"))
+    out = {**sol, **feet}
+    if "pose_world" in want or "traj_world" in want:
+        out["pose_world"], out["traj_world"] = frames_to_world(pose, traj, sol["plane"], want_traj="traj_world" in want)
+    return {k: out[k] for k in want}
+
+
 # ------------------------------------------------------------------ the per-frame pose scored against ground truth
 FRAME_ERROR_SLOTS = ("mpjpe", "mpjve", "accel", "root", "root_vel", "abs_mpjpe")   # then one slot per part (pafuse_amd.framemetrics)
 

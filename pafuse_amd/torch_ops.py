@@ -29,6 +29,10 @@ there is no fallback), with fake-tensor shape functions so the ops trace under `
   pafuse::track_people(x2d, conf, tracks, seed?, gate, skip, max_gap, support, min_frames, threshold)   [N,K] candidates -> per-person videos
   pafuse::focal_sums(pose, x2d, cam, conf?)               the focal-length sums of that pose: (K, H, G, 1) per (t, frame)
   pafuse::focal_solve(state, cam)                         the focal length from them: focal, r2, frames, cam per t
+  pafuse::foot_contacts(pose, traj, points, radius, speed)   the foot points on their local line and the weight of one that rests
+  pafuse::ground_sums(foot, contact, traj, plane?, scale?, gate) / pafuse::ground_solve(state, floor, spread)   the ground plane per t
+  pafuse::frames_to_world(pose, traj, plane)              pose + traj in world space: z up, the ground at z = 0
+  pafuse::estimate_ground(pose, traj, points, ...)        that chain in one call: the tensors of ops.GROUND_OUTPUTS
   pafuse::frame_errors(pose, gt, pbroot, part, num_parts, traj?, gt_root?)   that pose (and root) scored against ground truth
   pafuse::noise_fill(key, draw, B, P, F, J)               one draw of noise stream v1 as a tensor (DESIGN.md section 6)
 
@@ -638,6 +642,86 @@ def _(state, cam):
     T = state.shape[0]
     return [state.new_empty((T,), dtype=torch.float32), state.new_empty((T,), dtype=torch.float32),
             state.new_empty((T,), dtype=torch.int32), state.new_empty((T, cam.shape[0]), dtype=torch.float32)]
+
+
+# ------------------------------------------------------------------ which way is up: the ground plane from the foot contacts
+def _ground_fake_solve(ref, T):
+    f32, f64 = torch.float32, torch.float64
+    return [ref.new_empty((T, 4), dtype=f64), ref.new_empty((T,), dtype=f64), ref.new_empty((T, 3), dtype=f32),
+            ref.new_empty((T,), dtype=f32), ref.new_empty((T,), dtype=f32), ref.new_empty((T, 3), dtype=f32),
+            ref.new_empty((T,), dtype=torch.int32), ref.new_empty((T,), dtype=torch.uint8)]
+
+
+@torch.library.custom_op("pafuse::foot_contacts", mutates_args=(), device_types="cuda")
+def foot_contacts(pose: torch.Tensor, traj: torch.Tensor, points: List[int], radius: int = 3, speed: float = 0.015) -> List[torch.Tensor]:
+    """pafuse_amd.ops.foot_contacts: pose [T,N,J,3], traj [T,N,3], points K host integers -> [foot [T,N,K,3], foot_speed [T,N,K],
+    contact [T,N,K]]."""
+    from . import ops
+    m = ops.foot_contacts(pose, traj, list(points), radius=radius, speed=speed)
+    return [m["foot"], m["foot_speed"], m["contact"]]
+
+
+@foot_contacts.register_fake
+def _(pose, traj, points, radius=3, speed=0.015):
+    T, N, K = pose.shape[0], pose.shape[1], len(points)
+    return [pose.new_empty((T, N, K, 3)), pose.new_empty((T, N, K)), pose.new_empty((T, N, K))]
+
+
+@torch.library.custom_op("pafuse::ground_sums", mutates_args=(), device_types="cuda")
+def ground_sums(foot: torch.Tensor, contact: torch.Tensor, traj: torch.Tensor, plane: Optional[torch.Tensor] = None,
+                scale: Optional[torch.Tensor] = None, gate: float = 2.5) -> torch.Tensor:
+    """pafuse_amd.ops.ground_sums: foot [T,N,K,3], contact [T,N,K], traj [T,N,3], plane [T,4] / scale [T] float64 or neither ->
+    state [T,N,14] float64."""
+    from . import ops
+    return ops.ground_sums(foot, contact, traj, plane, scale, gate=gate)
+
+
+@ground_sums.register_fake
+def _(foot, contact, traj, plane=None, scale=None, gate=2.5):
+    return foot.new_empty((foot.shape[0], foot.shape[1], 14), dtype=torch.float64)
+
+
+@torch.library.custom_op("pafuse::ground_solve", mutates_args=(), device_types="cuda")
+def ground_solve(state: torch.Tensor, floor: float = 0.005, spread: float = 0.03) -> List[torch.Tensor]:
+    """pafuse_amd.ops.ground_solve: state [T,N,14] float64 -> [plane [T,4] f64, scale [T] f64, up [T,3], camera_height [T],
+    ground_rms [T], ground_eig [T,3], ground_points [T] int32, ground_code [T] uint8]."""
+    from . import ops
+    m = ops.ground_solve(state, floor=floor, spread=spread)
+    return [m[k] for k in ops.GROUND_SOLVE_OUTPUTS]
+
+
+@ground_solve.register_fake
+def _(state, floor=0.005, spread=0.03):
+    return _ground_fake_solve(state, state.shape[0])
+
+
+@torch.library.custom_op("pafuse::frames_to_world", mutates_args=(), device_types="cuda")
+def frames_to_world(pose: torch.Tensor, traj: torch.Tensor, plane: torch.Tensor) -> List[torch.Tensor]:
+    """pafuse_amd.ops.frames_to_world: pose [T,N,J,3], traj [T,N,3], plane [T,4] float64 -> [pose_world [T,N,J,3], traj_world [T,N,3]]."""
+    from . import ops
+    return list(ops.frames_to_world(pose, traj, plane))
+
+
+@frames_to_world.register_fake
+def _(pose, traj, plane):
+    return [torch.empty_like(pose), torch.empty_like(traj)]
+
+
+@torch.library.custom_op("pafuse::estimate_ground", mutates_args=(), device_types="cuda")
+def estimate_ground(pose: torch.Tensor, traj: torch.Tensor, points: List[int], radius: int = 3, speed: float = 0.015, passes: int = 3,
+                    gate: float = 2.5, floor: float = 0.005, spread: float = 0.03) -> List[torch.Tensor]:
+    """pafuse_amd.ops.estimate_ground: the chain -> the tensors of ops.GROUND_OUTPUTS in that order: plane, scale, up, camera_height,
+    ground_rms, ground_eig, ground_points, ground_code, foot, foot_speed, contact, pose_world, traj_world."""
+    from . import ops
+    m = ops.estimate_ground(pose, traj, list(points), radius=radius, speed=speed, passes=passes, gate=gate, floor=floor, spread=spread)
+    return [m[k] for k in ops.GROUND_OUTPUTS]
+
+
+@estimate_ground.register_fake
+def _(pose, traj, points, radius=3, speed=0.015, passes=3, gate=2.5, floor=0.005, spread=0.03):
+    T, N, K = pose.shape[0], pose.shape[1], len(points)
+    return _ground_fake_solve(pose, T) + [pose.new_empty((T, N, K, 3)), pose.new_empty((T, N, K)), pose.new_empty((T, N, K)),
+                                          torch.empty_like(pose), torch.empty_like(traj)]
 
 
 # ------------------------------------------------------------------ the per-frame pose scored against ground truth

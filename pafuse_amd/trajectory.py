@@ -26,7 +26,8 @@ the frames m = max(0, n - r) .. min(N - 1, n + r) are walked in ascending order,
   else:                                      NaN
 
 rounded once to fp32.  A local line, not a local mean: a root moving at constant velocity comes through without lag and
-without shrinking at the ends, and a frame without a fit is filled from its neighbours.
+without shrinking at the ends, and a frame without a fit is filled from its neighbours.  The slope of the same line,
+(S0*Q1 - S1*Q0)/D per component, is local_line_slope's second result: pafuse_amd.ground reads it as a foot's velocity.
 
 This module is test infrastructure and the documentation of the arithmetic.  The product path never calls it.
 """
@@ -83,10 +84,9 @@ def fit_frames(pose, x2d, conf, cam):
 LINE, MEAN, NONE = 1, 2, 3     # what local_line found at a frame (the status codes 1, 2, 3 of pafuse_amd.detections)
 
 
-def local_line(y, part, w64, r):
-    """THE filter above, on any number of tracks and components at once, the frames on axis 0: y [N,...,C] fp64, part [N,...]
-    bool (the frames that take part), w64 [N,...] fp64 ->
-    (value [N,...,C] fp64 before its rounding - the line's where code is LINE, else Q0/S0 - and code [N,...] uint8)"""
+def line_sums(y, part, w64, r):
+    """The sums of THE filter above, on any number of tracks and components at once, the frames on axis 0: y [N,...,C] fp64,
+    part [N,...] bool (the frames that take part), w64 [N,...] fp64 -> (S0, S1, S2 [N,...], Q0, Q1 [N,...,C], cnt [N,...] int64)"""
     N = part.shape[0]
     S0, S1, S2 = np.zeros(part.shape), np.zeros(part.shape), np.zeros(part.shape)
     Q0, Q1 = np.zeros(y.shape), np.zeros(y.shape)
@@ -109,13 +109,34 @@ def local_line(y, part, w64, r):
         Q0 = Q0 + np.where(take[..., None], om[..., None] * y[mc], 0.0)
         Q1 = Q1 + np.where(take[..., None], omd[..., None] * y[mc], 0.0)
         cnt = cnt + take
+    return S0, S1, S2, Q0, Q1, cnt
+
+
+def _line_value(S0, S1, S2, Q0, Q1, cnt):
     D = S0 * S2 - S1 * S1
     line = (cnt >= 2) & np.isfinite(D) & (D > 0)
     val_line = (S2[..., None] * Q0 - S1[..., None] * Q1) / D[..., None]
     val_mean = Q0 / S0[..., None]
     value = np.where(line[..., None], val_line, val_mean)
     code = np.where(line, LINE, np.where(S0 > 0, MEAN, NONE)).astype(np.uint8)
+    return value, code, D
+
+
+def local_line(y, part, w64, r):
+    """THE filter above (line_sums has the operands) -> (value [N,...,C] fp64 before its rounding - the line's where code is
+    LINE, else Q0/S0 - and code [N,...] uint8)"""
+    value, code, _ = _line_value(*line_sums(y, part, w64, r))
     return value, code
+
+
+def local_line_slope(y, part, w64, r):
+    """local_line with the slope of the same line beside its value, (S0*Q1 - S1*Q0)/D per component - the change of y per
+    frame at d = 0, meaningful where code is LINE - and the number of frames in the sums (the foot contacts of
+    pafuse_amd.ground ask for three): -> (value, slope [N,...,C] fp64, code [N,...] uint8, cnt [N,...] int64)"""
+    S0, S1, S2, Q0, Q1, cnt = line_sums(y, part, w64, r)
+    value, code, D = _line_value(S0, S1, S2, Q0, Q1, cnt)
+    slope = (S0[..., None] * Q1 - S1[..., None] * Q0) / D[..., None]
+    return value, slope, code, cnt
 
 
 def smooth(traj, weight, radius):
