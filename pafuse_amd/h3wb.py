@@ -394,21 +394,21 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
         raise ValueError(f"swap must be (rate, run, seed), got {swap!r}")
     sums = counts = prof_s = prof_c = None
     for video, (cam, seq_3d, seq_2d) in enumerate(iter_sequences(cams, poses_3d, poses_2d)):
-        got = harness.evaluate_frames(model, dataset, seq_2d[0].astype("float32"), seq_3d[0].astype("float32"),
-                                      cam[0].astype("float32"), kps_left, kps_right, aggregate=aggregate, stride=stride,
-                                      trajectory=trajectory, batch_size=batch_size, group=group,
-                                      hypothesis_chunk=hypothesis_chunk, p2=p2, per_frame=seam_profile, focal=focal, repair=repair,
-                                      drop=None if drop is None else (drop[0], drop[1], int(drop[2]) + video),
-                                      repair_threshold=repair_threshold, path_weight=path_weight, path_scope=path_scope,
-                                      pose_smooth=pose_smooth, pose_smooth_floor=pose_smooth_floor, bone_lengths=bone_lengths,
-                                      bone_iterations=bone_iterations,
-                                      corrupt=None if corrupt is None else (corrupt[0], corrupt[1], corrupt[2], int(corrupt[3]) + video),
-                                      swap=None if swap is None else (swap[0], swap[1], int(swap[2]) + video), screen=screen,
-                                      screen_gate=screen_gate, screen_floor=screen_floor,
-                                      distract=None if distract is None else (distract[0], int(distract[1]) + video), track=track,
-                                      ground=ground, ground_speed=ground_speed)
-        if ground is not None:
-            found, got = got[-1], got[:-1]
+        got = harness._evaluate_frames(model, dataset, seq_2d[0].astype("float32"), seq_3d[0].astype("float32"),
+                                       cam[0].astype("float32"), kps_left, kps_right, aggregate=aggregate, stride=stride,
+                                       trajectory=trajectory, batch_size=batch_size, group=group,
+                                       hypothesis_chunk=hypothesis_chunk, p2=p2, per_frame=seam_profile, focal=focal, repair=repair,
+                                       drop=None if drop is None else (drop[0], drop[1], int(drop[2]) + video),
+                                       repair_threshold=repair_threshold, path_weight=path_weight, path_scope=path_scope,
+                                       pose_smooth=pose_smooth, pose_smooth_floor=pose_smooth_floor, bone_lengths=bone_lengths,
+                                       bone_iterations=bone_iterations,
+                                       corrupt=None if corrupt is None else (corrupt[0], corrupt[1], corrupt[2], int(corrupt[3]) + video),
+                                       swap=None if swap is None else (swap[0], swap[1], int(swap[2]) + video), screen=screen,
+                                       screen_gate=screen_gate, screen_floor=screen_floor,
+                                       distract=None if distract is None else (distract[0], int(distract[1]) + video), track=track,
+                                       ground=ground, ground_speed=ground_speed)       # named: what an option did not ask for is None
+        found, held, seen, est = got.found, got.held, got.seen, got.estimate
+        if found is not None:
             gt = torch.as_tensor(seq_3d[0].astype("float32"))
             truth = harness.estimate_ground((gt - gt[:, :1]).unsqueeze(0), gt[:, 0].unsqueeze(0), radius=3 if ground is True else ground,
                                             speed=ground_speed)
@@ -419,14 +419,12 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
                     % (video, t, int(found["ground_code"][t]), float(found["camera_height"][t]), int(found["ground_points"][t]), off(found["up"][t])))
             log("video %d ground truth 3-D : ground code %d, camera height %.3f m, %d contact points, angle to the camera's true up %s deg"
                 % (video, int(truth["ground_code"][0]), float(truth["camera_height"][0]), int(truth["ground_points"][0]), off(truth["up"][0])))
-        if bone_lengths is not None:
-            held, got = got[-1], got[:-1]
+        if held is not None:
             gap = (held["bone_length"].double() - held["bone_length_gt"].double()).abs()
             log("video %d: bone-length std (mm, mean over the bones) free %s -> constrained %s; held lengths vs ground truth: max %.1f mm"
                 % (video, ["%.2f" % v for v in held["bone_dev_free"].tolist()], ["%.2f" % v for v in held["bone_dev"].tolist()],
                    float(gap[~gap.isnan()].max()) * 1000.0 if bool((~gap.isnan()).any()) else float("nan")))
-        if repair is not None or drop is not None or corrupt is not None or swap is not None or screen is not None or distract is not None:
-            seen, got = got[-1], got[:-1]
+        if seen is not None:
             if "tracked" in seen:
                 e = tracks.track_error(seen["tracked"].numpy(), seen["truth_slot"].numpy())
                 log("video %d : %s among %d people: the subject's detection in %d frames, another person's in %d, nobody in %d, %d switches"
@@ -455,16 +453,15 @@ def evaluate_frames(model, dataset, cams, poses_3d, poses_2d, kps_left, kps_righ
                         % (video, name, e["filled"], e["n_filled"], e["unfilled"], e["n_unfilled"]))
             elif "lost" in seen:
                 log("video %d : %d detections dropped, none repaired" % (video, int(seen["lost"].sum())))
-        if focal is not None:
-            est = got[-1]
+        if est is not None:
             for t in range(est["focal"].shape[0]):
                 log("video %d step %d : estimated focal length %f (true %f, ratio %f), r2 %f over %d frames"
                     % (video, t, float(est["focal"][t]), float(cam[0][0]), float(est["focal"][t]) / float(cam[0][0]),
                        float(est["focal_r2"][t]), int(est["focal_frames"][t])))
-        sums = got[0] if sums is None else {k: sums[k] + got[0][k] for k in sums}
-        counts = got[1] if counts is None else {k: counts[k] + got[1][k] for k in counts}
+        sums = got.sums if sums is None else {k: sums[k] + got.sums[k] for k in sums}
+        counts = got.counts if counts is None else {k: counts[k] + got.counts[k] for k in counts}
         if seam_profile:       # the sums and the counts of the bins add over videos; the quotient is formed once
-            s, c = harness.seam_bins(got[2]["err"], got[2]["cnt"], model.frames)
+            s, c = harness.seam_bins(got.maps["err"], got.maps["cnt"], model.frames)
             prof_s, prof_c = (s, c) if prof_s is None else (prof_s + s, prof_c + c)
     rep = harness.frame_report(sums, counts)
     for line in harness.format_frame_report(rep, action):

@@ -3,7 +3,9 @@
 accumulators - with tensors kept on the HIP device.  SURVEY.md section 8f rows n1/n3 (partial: no dataset files
 or Hydra here; the caller hands in arrays).
 """
+import dataclasses
 import math
+from typing import NamedTuple
 
 import torch
 
@@ -64,6 +66,56 @@ def wb_pose_from_parts(pose, dataset):
     return out
 
 
+# ------------------------------------------------------- the operand checks the stand-alone wrappers and the chain share
+def _poses_operand(poses, other=None, named=None, dims=slice(0, 2), tail=(3,), empty_ok=False):
+    """poses [T,N,J,3] -> fp32; with `other` its companion, refused as `named`, of shape poses.shape[dims] + tail -> the pair"""
+    poses = torch.as_tensor(poses, dtype=torch.float32)
+    bad = poses.dim() != 4 or poses.shape[-1] != 3 or (not empty_ok and 0 in poses.shape)
+    if named is None:
+        if bad:
+            raise ValueError(f"poses must be [T,N,J,3], got {tuple(poses.shape)}")
+        return poses
+    other = torch.as_tensor(other, dtype=torch.float32)
+    if bad or tuple(other.shape) != (*poses.shape[dims], *tail):
+        raise ValueError(f"poses must be [T,N,J,3] and {named}, got {tuple(poses.shape)} and {tuple(other.shape)}")
+    return poses, other
+
+
+def _cov_operand(cov, poses):
+    """cov [T,N,J,6] beside poses [T,N,J,3], or None -> fp32 or None"""
+    if cov is None:
+        return None
+    cov = torch.as_tensor(cov, dtype=torch.float32)
+    if tuple(cov.shape) != (*poses.shape[:3], 6):
+        raise ValueError(f"cov must be [T,N,J,6] = {(*poses.shape[:3], 6)}, got {tuple(cov.shape)}")
+    return cov
+
+
+def _conf_operand(conf, shape):
+    """conf [N,J] = `shape`, or None -> fp32 or None"""
+    if conf is None:
+        return None
+    conf = torch.as_tensor(conf, dtype=torch.float32)
+    if tuple(conf.shape) != tuple(shape):
+        raise ValueError(f"conf must be [N,J] = {tuple(shape)}, got {tuple(conf.shape)}")
+    return conf
+
+
+def _detections_pair(seq_2d, conf):
+    """seq_2d [N,J,2] and conf [N,J] -> the fp32 pair"""
+    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
+    conf = torch.as_tensor(conf, dtype=torch.float32)
+    if seq_2d.dim() != 3 or seq_2d.shape[-1] != 2 or tuple(conf.shape) != tuple(seq_2d.shape[:2]):
+        raise ValueError(f"seq_2d must be [N,J,2] and conf [N,J], got {tuple(seq_2d.shape)} and {tuple(conf.shape)}")
+    return seq_2d, conf
+
+
+def _run_on(operand, device, run):
+    """run(dev) on the operand's own device when it is on one, else on `device`; its dict of device tensors -> CPU tensors"""
+    dev = operand.device if operand.is_cuda else torch.device(device)
+    return {k: v.cpu() for k, v in run(dev).items()}
+
+
 def _repair_radius(repair, threshold=0.0, name="repair"):
     """infer_sequence's `repair` and `repair_threshold`: None -> None, an integer r in 1 .. 64 -> r; the threshold finite and >= 0"""
     if repair is None:
@@ -75,10 +127,11 @@ def _repair_radius(repair, threshold=0.0, name="repair"):
     return repair
 
 
-def _repair_detections(seq_2d, conf, anchor, radius, threshold, dev):
-    """CPU or device tensors seq_2d [N,J,2], conf [N,J] -> ops.repair_detections' dict on the device"""
+def _repair_detections(seq_2d, conf, dev, **options):
+    """CPU or device tensors seq_2d [N,J,2], conf [N,J] -> ops.repair_detections' dict on the device; options: its anchor, radius
+    and threshold"""
     from . import ops
-    return ops.repair_detections(seq_2d.to(dev).contiguous(), conf.to(dev).contiguous(), anchor=anchor, radius=radius, threshold=threshold)
+    return ops.repair_detections(seq_2d.to(dev).contiguous(), conf.to(dev).contiguous(), **options)
 
 
 @torch.no_grad()
@@ -97,14 +150,10 @@ def repair_detections(seq_2d, conf, dataset=None, anchor=None, radius=13, thresh
     radius = _repair_radius(radius, threshold, "radius")
     if radius is None:
         raise ValueError("radius must be a radius in 1 .. 64 (frames), got None")
-    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
-    conf = torch.as_tensor(conf, dtype=torch.float32)
-    if seq_2d.dim() != 3 or seq_2d.shape[-1] != 2 or tuple(conf.shape) != tuple(seq_2d.shape[:2]):
-        raise ValueError(f"seq_2d must be [N,J,2] and conf [N,J], got {tuple(seq_2d.shape)} and {tuple(conf.shape)}")
+    seq_2d, conf = _detections_pair(seq_2d, conf)
     if anchor is None and dataset is not None:
         anchor = repair_anchors(dataset)
-    dev = seq_2d.device if seq_2d.is_cuda else torch.device(device)
-    out = {k: v.cpu() for k, v in _repair_detections(seq_2d, conf, anchor, radius, float(threshold), dev).items()}
+    out = _run_on(seq_2d, device, lambda dev: _repair_detections(seq_2d, conf, dev, anchor=anchor, radius=radius, threshold=float(threshold)))
     out["counts"] = torch.bincount(out["status"].reshape(-1).long(), minlength=4)
     return out
 
@@ -122,11 +171,11 @@ def _screen_radius(screen, gate=4.0, floor=0.005, name="screen"):
     return screen
 
 
-def _screen_detections(seq_2d, conf, mirror, radius, gate, floor, threshold, dev, passes=3, support=3):
-    """CPU or device tensors seq_2d [N,J,2], conf [N,J] -> ops.screen_detections' dict on the device"""
+def _screen_detections(seq_2d, conf, dev, **options):
+    """CPU or device tensors seq_2d [N,J,2], conf [N,J] -> ops.screen_detections' dict on the device; options: its mirror, radius,
+    gate, floor, passes, support and threshold"""
     from . import ops
-    return ops.screen_detections(seq_2d.to(dev).contiguous(), conf.to(dev).contiguous(), mirror=mirror, radius=radius, gate=float(gate),
-                                 floor=float(floor), passes=passes, support=support, threshold=threshold)
+    return ops.screen_detections(seq_2d.to(dev).contiguous(), conf.to(dev).contiguous(), **options)
 
 
 @torch.no_grad()
@@ -148,14 +197,11 @@ def screen_detections(seq_2d, conf, kps_left=None, kps_right=None, mirror=None, 
     radius = _screen_radius(radius, gate, floor, "radius")
     if radius is None:
         raise ValueError("radius must be a radius in 1 .. 64 (frames), got None")
-    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
-    conf = torch.as_tensor(conf, dtype=torch.float32)
-    if seq_2d.dim() != 3 or seq_2d.shape[-1] != 2 or tuple(conf.shape) != tuple(seq_2d.shape[:2]):
-        raise ValueError(f"seq_2d must be [N,J,2] and conf [N,J], got {tuple(seq_2d.shape)} and {tuple(conf.shape)}")
+    seq_2d, conf = _detections_pair(seq_2d, conf)
     if mirror is None and kps_left is not None and kps_right is not None:
         mirror = mirror_table(kps_left, kps_right, seq_2d.shape[1])
-    dev = seq_2d.device if seq_2d.is_cuda else torch.device(device)
-    out = {k: v.cpu() for k, v in _screen_detections(seq_2d, conf, mirror, radius, gate, floor, float(threshold), dev, passes, support).items()}
+    out = _run_on(seq_2d, device, lambda dev: _screen_detections(seq_2d, conf, dev, mirror=mirror, radius=radius, gate=float(gate), floor=float(floor),
+                                                                 passes=passes, support=support, threshold=float(threshold)))
     out["counts"] = torch.bincount(out["status"].reshape(-1).long(), minlength=4)
     return out
 
@@ -318,6 +364,60 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     z = 0 - the height of a joint is its third component.  One plane per video; the pose is rotated, not corrected (no foot
     locking); world x is the camera's right, not a direction of travel.  Every default is a default, not a tuned value, and
     nobody has run it on real video."""
+    plan = _frame_plan(getattr(model, "frames", None), dataset, kps_left, kps_right, cam=cam, traj=traj, conf=conf, aggregate=aggregate,
+                       stride=stride, hypothesis_chunk=hypothesis_chunk, spread=spread, trajectory=trajectory, focal=focal, repair=repair,
+                       repair_threshold=repair_threshold, path_weight=path_weight, path_scope=path_scope, pose_smooth=pose_smooth,
+                       pose_smooth_floor=pose_smooth_floor, bone_lengths=bone_lengths, bone_iterations=bone_iterations, screen=screen,
+                       screen_gate=screen_gate, screen_floor=screen_floor, ground=ground, ground_speed=ground_speed,
+                       ground_passes=ground_passes, ground_gate=ground_gate, ground_floor=ground_floor, ground_spread=ground_spread,
+                       ground_points=ground_points)
+    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
+    conf = _conf_operand(conf, seq_2d.shape[-3:-1])
+    dev = next(model.parameters()).device
+    # the callees cut and flip on the host: the screened and repaired pair takes the place of the input, whole, before either
+    seq_2d, conf, screened, repaired = _front_end(seq_2d, conf, plan, dataset, kps_left, kps_right, dev)
+    out = _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, plan, cam=cam, traj=traj, conf=conf, batch_size=batch_size,
+                          group=group, dev=dev)
+    if isinstance(out, dict):
+        out.update({k: v for k, v in (("screened", screened), ("repaired", repaired)) if v is not None})
+    return out
+
+
+@dataclasses.dataclass(frozen=True)
+class _FramePlan:
+    """What the per-frame chain does, every option checked (_frame_plan); a switch that is off is None (trajectory: False)"""
+    aggregate: object           # None, "mean", "reproj" or "reproj_fit"
+    stride: object              # None: the clip path; else 1 .. frames, one pose per video frame
+    hypothesis_chunk: object
+    spread: object              # what the caller wants returned: None, "std" or "cov"
+    fold_spread: object         # what is folded: the pose smoother and the bones need the covariance whatever the caller wants
+    path_weight: object
+    path_scope: str
+    trajectory: bool
+    smooth: object              # the radius of the trajectory's smoother
+    focal: object               # None or "estimate"
+    pose_smooth: object         # (radius, floor)
+    bones: object               # _bone_spec's dict with its "tables" (_bone_tables)
+    ground: object              # _ground_spec's dict
+    screen: object              # (radius, gate, floor)
+    repair: object              # the radius
+    threshold: object           # repair_threshold as given (checked when the repair or the screen is on; both read it as a float)
+
+
+def _frame_plan(frames, dataset, kps_left, kps_right, *, cam, traj, conf, aggregate, stride=None, hypothesis_chunk=None, spread=None,
+                trajectory=None, focal=None, repair=None, repair_threshold=0.0, path_weight=None, path_scope="clip", pose_smooth=None,
+                pose_smooth_floor=1e-3, bone_lengths=None, bone_iterations=16, screen=None, screen_gate=4.0, screen_floor=0.005,
+                ground=None, ground_speed=0.015, ground_passes=3, ground_gate=2.5, ground_floor=0.005, ground_spread=0.03,
+                ground_points=None, frames_only=False, conf_made=False):
+    """The plan of infer_sequence / evaluate_frames from their raw options and `frames` = model.frames: every option check and
+    every companion check, before anything touches the model or the device.  cam, traj and conf are only asked whether they
+    are there.  What evaluate_frames does differently: frames_only=True - there is no clip path, so stride None means `frames`, an
+    aggregate and cam are required, traj is its own - and conf_made=True: one of its plantings will make the confidences."""
+    if frames_only:
+        if aggregate not in ("mean", "reproj", "reproj_fit"):
+            raise ValueError(f'aggregate must be "mean", "reproj" or "reproj_fit", got {aggregate!r}')
+        if stride is None:
+            stride = frames
     smooth = _trajectory_radius(trajectory)
     pose_smooth = _pose_smooth_radius(pose_smooth, pose_smooth_floor)
     if pose_smooth is not None:
@@ -338,26 +438,34 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     _focal_mode(focal)
     ground = _ground_spec(ground, ground_speed, ground_passes, ground_gate, ground_floor, ground_spread, ground_points)
     if ground is not None and trajectory is None:
-        raise ValueError("ground needs a trajectory: the ground is found in camera space (harness.estimate_ground takes poses and roots a caller has)")
+        raise ValueError("ground needs a trajectory: the ground is found in camera space"
+                         + ("" if frames_only else " (harness.estimate_ground takes poses and roots a caller has)"))
     repair = _repair_radius(repair, repair_threshold)
-    path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, getattr(model, "frames", None), path_scope)
-    if repair is not None and conf is None:
-        raise ValueError("repair needs conf [N,J]: a missing detection is one whose confidence is not above repair_threshold")
+    if frames_only and (isinstance(stride, bool) or not isinstance(stride, int) or not 1 <= stride <= frames):
+        raise ValueError(f"stride must be None or an integer in 1 .. {frames} (the window length), got {stride!r}")
+    path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, frames, path_scope)
+    if repair is not None and conf is None and not conf_made:
+        raise ValueError("repair needs conf [N,J]" + (" or drop" if frames_only else "") + ": a missing detection is one whose confidence is not above repair_threshold")
     screen = _screen_radius(screen, screen_gate, screen_floor)
     if screen is not None:
         _repair_radius(1, repair_threshold)      # the threshold is read by the screen as well
-        if conf is None:
-            raise ValueError("screen needs conf [N,J]: a rejected detection leaves with confidence 0")
+        if conf is None and not conf_made:
+            raise ValueError("screen needs conf [N,J]" + (", corrupt, swap or drop" if frames_only else "")
+                             + ": a rejected detection leaves with confidence 0")
+        screen = (screen, float(screen_gate), float(screen_floor))
     if focal is not None and trajectory is None:
-        raise ValueError('focal="estimate" belongs to a trajectory (harness.estimate_focal gives the estimate alone)')
+        raise ValueError('focal="estimate" belongs to a trajectory'
+                         + ("" if frames_only else " (harness.estimate_focal gives the estimate alone)"))
+    if frames_only and cam is None:
+        raise ValueError("evaluate_frames needs cam [9] (the intrinsics)")
     if trajectory is not None:
         if stride is None:
             raise ValueError("trajectory needs stride (one pose per video frame); for stitched clips call harness.fit_trajectory")
         if cam is None and focal is None:
             raise ValueError('trajectory needs cam (fx, fy, cx, cy first): the fit takes the intrinsics as known (or focal="estimate")')
-    if stride is not None:
-        if isinstance(stride, bool) or int(stride) != stride or not 1 <= int(stride) <= model.frames:
-            raise ValueError(f"stride must be an integer in 1 .. {model.frames} (the window length), got {stride!r}")
+    if stride is not None and not frames_only:
+        if isinstance(stride, bool) or int(stride) != stride or not 1 <= int(stride) <= frames:
+            raise ValueError(f"stride must be an integer in 1 .. {frames} (the window length), got {stride!r}")
         if aggregate is None:
             raise ValueError('stride needs aggregate="mean", "reproj" or "reproj_fit": the hypotheses per frame would be ragged')
     if aggregate not in (None, "mean", "reproj", "reproj_fit"):
@@ -367,49 +475,39 @@ def infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size=2, gr
     if spread is not None and aggregate is None:
         raise ValueError('spread needs aggregate="mean", "reproj" or "reproj_fit" (it is reduced on the device beside the pose)')
     if hypothesis_chunk is not None and (aggregate is None or int(hypothesis_chunk) < 1):
-        raise ValueError("hypothesis_chunk is a positive count and needs an aggregate")
-    if aggregate == "reproj" and (cam is None or traj is None):
+        raise ValueError("hypothesis_chunk is a positive count" + ("" if frames_only else " and needs an aggregate"))
+    if aggregate == "reproj" and not frames_only and (cam is None or traj is None):
         raise ValueError('aggregate="reproj" needs cam [9] and traj [N,3]')
-    fit = aggregate == "reproj_fit"
-    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
-    if fit:
-        if cam is None or traj is not None:
-            raise ValueError('aggregate="reproj_fit" needs cam [9] and takes no traj (the root is what it fits)')
-        if conf is not None:
-            conf = torch.as_tensor(conf, dtype=torch.float32)
-            if tuple(conf.shape) != tuple(seq_2d.shape[-3:-1]):
-                raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[-3:-1])}, got {tuple(conf.shape)}")
-    elif conf is not None and trajectory is None and repair is None and screen is None:
-        raise ValueError('conf belongs to aggregate="reproj_fit"')
-    elif conf is not None:
-        conf = torch.as_tensor(conf, dtype=torch.float32)
-        if tuple(conf.shape) != tuple(seq_2d.shape[-3:-1]):
-            raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[-3:-1])}, got {tuple(conf.shape)}")
-    dev = next(model.parameters()).device
-    if repair is None and screen is None:
-        return _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, trajectory, smooth, focal, dev, path_weight, path_scope, pose_smooth, bones, ground)
-    # the callees cut and flip on the host: the screened and repaired pair takes the place of the input, whole, before either
+    if aggregate == "reproj_fit" and (cam is None or traj is not None):
+        raise ValueError('aggregate="reproj_fit" needs cam [9] and takes no traj (the root is what it fits)')
+    if conf is not None and aggregate != "reproj_fit" and trajectory is None and repair is None and screen is None and not conf_made:
+        raise ValueError('conf belongs to aggregate="reproj_fit"' + (" or a trajectory" if frames_only else ""))
+    if stride is None and path_scope == "video":      # one path along the video: per-frame results, the clips of cut_clips
+        stride = frames
+    return _FramePlan(aggregate=aggregate, stride=None if stride is None else int(stride), hypothesis_chunk=hypothesis_chunk, spread=spread,
+                      fold_spread="cov" if pose_smooth is not None or bones is not None else spread,
+                      path_weight=path_weight, path_scope=path_scope, trajectory=trajectory is not None, smooth=smooth, focal=focal,
+                      pose_smooth=pose_smooth, bones=bones, ground=ground, screen=screen, repair=repair, threshold=repair_threshold)
+
+
+def _front_end(seq_2d, conf, plan, dataset, kps_left, kps_right, dev):
+    """The detections as the model will see them: screened, then repaired, as the plan asks (both on the device, the pair staying
+    there in between) -> (seq_2d, conf, the screen's status map or None, the repair's or None), all on the CPU"""
+    if plan.screen is None and plan.repair is None:
+        return seq_2d, conf, None, None
     seq_2d = seq_2d.squeeze(0) if seq_2d.dim() == 4 else seq_2d
-    screened = fixed = None
-    if screen is not None:
+    screened = repaired = None
+    if plan.screen is not None:
         from .detscreen import mirror_table
-        screened = _screen_detections(seq_2d, conf, mirror_table(kps_left, kps_right, seq_2d.shape[-2]), screen, screen_gate,
-                                      screen_floor, float(repair_threshold), dev)
-        seq_2d, conf = screened["x2d"], screened["conf"]
-    if repair is not None:
+        radius, gate, floor = plan.screen
+        m = _screen_detections(seq_2d, conf, dev, mirror=mirror_table(kps_left, kps_right, seq_2d.shape[-2]), radius=radius, gate=gate,
+                               floor=floor, threshold=float(plan.threshold))
+        seq_2d, conf, screened = m["x2d"], m["conf"], m["status"].cpu()
+    if plan.repair is not None:
         from .detections import repair_anchors
-        fixed = _repair_detections(seq_2d, conf, repair_anchors(dataset), repair, float(repair_threshold), dev)
-        seq_2d, conf = fixed["x2d"], fixed["conf"]
-    out = _infer_sequence(model, dataset, seq_2d.cpu(), kps_left, kps_right, batch_size, group, aggregate, cam, traj,
-                          hypothesis_chunk, spread, conf.cpu(), stride, trajectory, smooth, focal, dev, path_weight, path_scope,
-                          pose_smooth, bones, ground)
-    if isinstance(out, dict):
-        if screened is not None:
-            out["screened"] = screened["status"].cpu()
-        if fixed is not None:
-            out["repaired"] = fixed["status"].cpu()
-    return out
+        m = _repair_detections(seq_2d, conf, dev, anchor=repair_anchors(dataset), radius=plan.repair, threshold=float(plan.threshold))
+        seq_2d, conf, repaired = m["x2d"], m["conf"], m["status"].cpu()
+    return seq_2d.cpu(), conf.cpu(), screened, repaired
 
 
 PATH_CANDIDATES = 256    # path_scope="video": P times the windows that cover one frame (ops.FRAMES_PATH_MAX_CANDIDATES)
@@ -435,45 +533,78 @@ def _path_weight(path_weight, aggregate, hypothesis_chunk, stride, frames, scope
     return float(path_weight)
 
 
-def _path_batch(sampler, dataset, x2d, x2d_flip, traj, cam, conf, fit, path_weight, spread=None):
-    """One batch of clips under path_weight: ALL P hypotheses (gathered across the ranks, as aggregate=None gathers them),
-    evaluate.path_poses on them and, with `spread`, their moments -> (path_poses' dict, the SpreadState or None)"""
+def _sample_batch(sampler, dataset, plan, x2d, x2d_flip, traj, cam, conf, group, want=None):
+    """One batch of clips or windows sampled under the plan; traj [B,F,3] with "reproj", conf [B,F,J] or None with "reproj_fit",
+    else None.  `want` None (the frames path): the merged states of the batch's hypotheses, what accumulate_frames folds;
+    names (the clip path): the combined outputs of those names.  -> (that dict, the hypotheses themselves with
+    path_scope="video" - they stay on the device until the end of the video - else None)"""
+    from . import ops
     from .evaluate import path_poses
+    merged, spread, P = want is None, plan.fold_spread, sampler.model.num_proposals
+    fit, reproj = plan.aggregate == "reproj_fit", plan.aggregate in ("reproj", "reproj_fit")
+
+    def fold(state, pred, h0):
+        if fit:
+            return accumulate_poses(state, pred, h0, dataset, x2d, None, cam, fit=True, conf=conf)
+        return accumulate_poses(state, pred, h0, dataset, x2d, traj, cam) if reproj else accumulate_poses(state, pred, h0, dataset)
+
+    if plan.path_weight is None:
+        state = moments = None
+        for pred, h0, _ in sampler.sample_chunks(x2d, None, input_2d_flip=x2d_flip, chunk=plan.hypothesis_chunk):
+            if merged or reproj or spread is None:      # the clip path's mean with a spread: the spread state holds the sums
+                state = fold(state, pred, h0)
+            if spread is not None:
+                moments = accumulate_spread(moments, pred, h0, dataset)
+            del pred
+        return aggregate_poses_sharded(None, None, P, dataset, group=group, state=state, want=() if merged else want,
+                                       spread_state=moments, merged=merged), None
+    # a path needs ALL P hypotheses at once (gathered across the ranks, as aggregate=None gathers them): every rank holds them
+    # and the same states, with nothing to exchange
     pred = sampler(x2d, None, input_2d_flip=x2d_flip)
-    out = path_poses(pred, dataset, x2d, cam, path_weight, traj=None if fit else traj, conf=conf if fit else None, fit=fit)
-    return out, (None if spread is None else accumulate_spread(None, pred, 0, dataset))
+    video = plan.path_scope == "video"
+    if video:           # the path comes at the end of the video: here the states the default folds
+        state = fold(None, pred, 0)
+        out = {"state": torch.empty_like(state.head), "shape": state.shape}
+        ops.combine_poses(state.head.unsqueeze(0), state.shape, P, merged=out["state"], want=(), no_pick_ok=fit)
+    else:
+        out = path_poses(pred, dataset, x2d, cam, plan.path_weight, traj=traj, conf=conf, fit=fit)
+    if spread is not None:
+        moments = accumulate_spread(None, pred, 0, dataset)
+        into = torch.empty_like(moments.head) if merged else None
+        out.update(ops.combine_spread(moments.head.unsqueeze(0), moments.shape, merged=into,
+                                      want=() if merged else [k for k in want if k in ("std", "cov")]))
+        if merged:
+            out["spread_state"] = into
+    return out, (pred if video else None)
 
 
-def _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                    conf, stride, trajectory, smooth, focal, dev, path_weight=None, path_scope="clip", pose_smooth=None, bones=None,
-                    ground=None):
-    """infer_sequence behind its argument checks (and behind the repair of the detections, when one was asked for)"""
-    fit = aggregate == "reproj_fit"
-    if stride is None and path_scope == "video":      # one path along the video: per-frame results, the clips of cut_clips
-        stride = model.frames
-    if stride is not None:
-        return _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                             spread, conf, int(stride), dev, trajectory is not None, smooth, focal, path_weight, path_scope, pose_smooth,
-                             bones, ground)
-    x2d = cut_clips(seq_2d, model.frames).to(dev)
-    x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), model.frames).to(dev)
+def _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, plan, *, cam, traj, conf, batch_size, group, dev):
+    """infer_sequence behind its plan and the detection front end: the frames path's result copied to the CPU, or the clip path"""
+    if plan.stride is not None:
+        out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, plan, cam=cam, traj=traj, conf=conf,
+                                   batch_size=batch_size, group=group, dev=dev)
+        return {k: v.cpu() for k, v in out.items()}
+    F, spread = model.frames, plan.spread
+    x2d = cut_clips(seq_2d, F).to(dev)
+    x2d_flip = cut_clips(flip_2d(seq_2d, kps_left, kps_right), F).to(dev)
     sampler = ShardedSampler(model, group)
-    if aggregate is None:
+    if plan.aggregate is None:
         outs = []
         for lo in range(0, x2d.shape[0], batch_size):
             pred = sampler(x2d[lo:lo + batch_size], None, input_2d_flip=x2d_flip[lo:lo + batch_size])
             outs.append(wb_pose_from_parts(pred, dataset).cpu())
         return torch.cat(outs)
-    reproj = aggregate in ("reproj", "reproj_fit")
+    fit, reproj = plan.aggregate == "reproj_fit", plan.aggregate in ("reproj", "reproj_fit")
+    clip_traj = clip_conf = None
     if fit:
         cam = torch.as_tensor(cam, dtype=torch.float32).to(dev)
         if conf is not None:
-            conf = cut_clips(conf.unsqueeze(-1), model.frames).squeeze(-1).to(dev)  # [clips,F,J]
+            clip_conf = cut_clips(conf.unsqueeze(-1), F).squeeze(-1).to(dev)               # [clips,F,J]
     elif reproj:
         traj = torch.as_tensor(traj, dtype=torch.float32)
         if traj.dim() != 2 or tuple(traj.shape) != (seq_2d.shape[-3], 3):
             raise ValueError(f"traj must be [N,3] with N = {seq_2d.shape[-3]} frames, got {tuple(traj.shape)}")
-        traj = cut_clips(traj.unsqueeze(1), model.frames).squeeze(2).to(dev)          # [clips,F,3]
+        clip_traj = cut_clips(traj.unsqueeze(1), F).squeeze(2).to(dev)                      # [clips,F,3]
         cam = torch.as_tensor(cam, dtype=torch.float32).to(dev)
     pose_name = "pick" if reproj else "mean"
     names = ((pose_name,) + (("idx",) if reproj else ()) + (("mean",) if fit else ())
@@ -481,31 +612,9 @@ def _infer_sequence(model, dataset, seq_2d, kps_left, kps_right, batch_size, gro
     kept = {k: [] for k in names if not (fit and k == "mean")}     # with the fit the mean only fills joints without a pick
     for lo in range(0, x2d.shape[0], batch_size):
         hi = min(lo + batch_size, x2d.shape[0])
-        operands = (x2d[lo:hi], traj[lo:hi], cam) if reproj and not fit else ()
-        state = moments = None
-        if path_weight is not None:
-            from . import ops
-            out, moments = _path_batch(sampler, dataset, x2d[lo:hi], x2d_flip[lo:hi], None if fit else traj[lo:hi], cam,
-                                       None if conf is None else conf[lo:hi], fit, path_weight, spread)
-            if moments is not None:
-                out.update(ops.combine_spread(moments.head.unsqueeze(0), moments.shape, want=[k for k in names if k in ("std", "cov")]))
-            if fit:     # a joint without a path carries the mean
-                out["pick"] = torch.where((out["idx"] < 0).unsqueeze(-1), out["mean"], out["pick"])
-            for k in kept:
-                kept[k].append(out[k].cpu())
-            continue
-        for pred, h0, _ in sampler.sample_chunks(x2d[lo:hi], None, input_2d_flip=x2d_flip[lo:hi], chunk=hypothesis_chunk):
-            if fit:
-                state = accumulate_poses(state, pred, h0, dataset, x2d[lo:hi], None, cam, fit=True,
-                                         conf=None if conf is None else conf[lo:hi])
-            elif reproj or spread is None:
-                state = accumulate_poses(state, pred, h0, dataset, *operands)
-            if spread is not None:
-                moments = accumulate_spread(moments, pred, h0, dataset)
-            del pred
-        out = aggregate_poses_sharded(None, None, model.num_proposals, dataset, group=group, state=state, want=names,
-                                      spread_state=moments)
-        if fit:     # a joint without a pick carries the mean (the one combine call wrote both)
+        out, _ = _sample_batch(sampler, dataset, plan, x2d[lo:hi], x2d_flip[lo:hi], None if clip_traj is None else clip_traj[lo:hi], cam,
+                               None if clip_conf is None else clip_conf[lo:hi], group, want=names)
+        if fit:     # a joint without a pick (or a path) carries the mean: the one combine call wrote both
             out["pick"] = torch.where((out["idx"] < 0).unsqueeze(-1), out["mean"], out["pick"])
         for k in kept:
             kept[k].append(out[k].cpu())
@@ -524,116 +633,74 @@ def cut_windows(seq, starts, frames=27):
     return torch.stack([seq[int(s):int(s) + frames] for s in starts])
 
 
-def _infer_frames(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                  conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip", pose_smooth=None,
-                  bones=None, ground=None):
-    """infer_sequence(stride=...): sliding windows pooled into one pose per video frame (arguments already checked)"""
-    out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk,
-                               spread, conf, stride, dev, trajectory, smooth, focal, path_weight, path_scope, pose_smooth, bones, ground)
-    return {k: v.cpu() for k, v in out.items()}
-
-
-def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam, traj, hypothesis_chunk, spread,
-                         conf, stride, dev, trajectory=False, smooth=None, focal=None, path_weight=None, path_scope="clip",
-                         pose_smooth=None, bones=None, ground=None):
-    """_infer_frames with its result left on the device (evaluate_frames scores it there); pose_smooth: None or (radius, floor);
-    bones: None or _bone_spec's dict with its tables; ground: None or _ground_spec's dict"""
+def _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, plan, *, cam, traj, conf, batch_size, group, dev):
+    """infer_sequence(stride=...): sliding windows pooled into one pose per video frame, then the stages behind the finish
+    (_finish_stages) - the result left on the device, where evaluate_frames scores it"""
     from . import ops
     from .windows import coverage, window_starts
-    asked = spread                  # what the caller wants returned; the pose smoother and the bones need the covariance whatever that is
-    needs_cov = pose_smooth is not None or bones is not None
-    if needs_cov and spread is None:
-        spread = "cov"
     if seq_2d.dim() == 4:
         seq_2d = seq_2d.squeeze(0)
-    N, F = seq_2d.shape[0], model.frames
-    starts, valid = window_starts(N, F, stride)
-    fit, reproj = aggregate == "reproj_fit", aggregate in ("reproj", "reproj_fit")
-    video = path_weight is not None and path_scope == "video"
-    if video and int(coverage(N, starts, valid).max()) * model.num_proposals > PATH_CANDIDATES:
-        raise ValueError(f'path_scope="video": up to {int(coverage(N, starts, valid).max())} windows cover one frame at stride {stride}, with '
-                         f"{model.num_proposals} hypotheses each: at most {PATH_CANDIDATES} candidates per frame")
-    video_traj = None if traj is None or not video else torch.as_tensor(traj, dtype=torch.float32)
-    kept = []           # path_scope="video": the hypotheses of every window stay on the device until the end of the video
-    frame_conf = conf
+    N, F, P = seq_2d.shape[0], model.frames, model.num_proposals
+    starts, valid = window_starts(N, F, plan.stride)
+    fit, reproj = plan.aggregate == "reproj_fit", plan.aggregate in ("reproj", "reproj_fit")
+    video = plan.path_weight is not None and plan.path_scope == "video"
+    if video and int(coverage(N, starts, valid).max()) * P > PATH_CANDIDATES:
+        raise ValueError(f'path_scope="video": up to {int(coverage(N, starts, valid).max())} windows cover one frame at stride {plan.stride}, with '
+                         f"{P} hypotheses each: at most {PATH_CANDIDATES} candidates per frame")
     x2d = cut_windows(seq_2d, starts, F).to(dev)
     x2d_flip = cut_windows(flip_2d(seq_2d, kps_left, kps_right), starts, F).to(dev)
-    if reproj or trajectory:
+    if reproj or plan.trajectory:
         cam = _default_cam(dev) if cam is None else torch.as_tensor(cam, dtype=torch.float32).to(dev)
+    win_traj = win_conf = None
     if fit and conf is not None:
-        conf = cut_windows(conf, starts, F).to(dev)                                    # [windows,F,J]
-    elif reproj and not fit:
+        win_conf = cut_windows(conf, starts, F).to(dev)                                # [windows,F,J]
+    if reproj and not fit:
         traj = torch.as_tensor(traj, dtype=torch.float32)
         if traj.dim() != 2 or tuple(traj.shape) != (N, 3):
             raise ValueError(f"traj must be [N,3] with N = {N} frames, got {tuple(traj.shape)}")
-        traj = cut_windows(traj, starts, F).to(dev)                                    # [windows,F,3]
+        win_traj = cut_windows(traj, starts, F).to(dev)                                # [windows,F,3]
     sampler = ShardedSampler(model, group)
-    frames = None
+    frames, kept = None, []     # kept, path_scope="video": the hypotheses of every window stay on the device until the end of the video
     for lo in range(0, x2d.shape[0], batch_size):
         hi = min(lo + batch_size, x2d.shape[0])
-        state = moments = None
-        if video:                       # every rank holds all P hypotheses: the states the default folds, with nothing to exchange
-            pred = sampler(x2d[lo:hi], None, input_2d_flip=x2d_flip[lo:hi])
-            if fit:
-                state = accumulate_poses(None, pred, 0, dataset, x2d[lo:hi], None, cam, fit=True, conf=None if conf is None else conf[lo:hi])
-            else:
-                state = accumulate_poses(None, pred, 0, dataset, x2d[lo:hi], traj[lo:hi], cam)
-            merged = {"state": torch.empty_like(state.head), "shape": state.shape}
-            ops.combine_poses(state.head.unsqueeze(0), state.shape, model.num_proposals, merged=merged["state"], want=(), no_pick_ok=fit)
-            if spread is not None:
-                moments = accumulate_spread(None, pred, 0, dataset)
-                merged["spread_state"] = torch.empty_like(moments.head)
-                ops.combine_spread(moments.head.unsqueeze(0), moments.shape, merged=merged["spread_state"], want=())
-            frames = accumulate_frames(frames, merged, starts[lo:hi], valid[lo:hi], N, model.num_proposals)
+        merged, pred = _sample_batch(sampler, dataset, plan, x2d[lo:hi], x2d_flip[lo:hi], None if win_traj is None else win_traj[lo:hi], cam,
+                                     None if win_conf is None else win_conf[lo:hi], group)
+        frames = accumulate_frames(frames, merged, starts[lo:hi], valid[lo:hi], N, P)
+        if pred is not None:
             kept.append(pred)
-            continue
-        if path_weight is not None:     # every rank holds all P hypotheses and the same path: nothing to exchange
-            merged, moments = _path_batch(sampler, dataset, x2d[lo:hi], x2d_flip[lo:hi], None if fit else traj[lo:hi], cam,
-                                          None if conf is None or not fit else conf[lo:hi], fit, path_weight, spread)
-            if moments is not None:
-                merged["spread_state"] = torch.empty_like(moments.head)
-                ops.combine_spread(moments.head.unsqueeze(0), moments.shape, merged=merged["spread_state"], want=())
-            frames = accumulate_frames(frames, merged, starts[lo:hi], valid[lo:hi], N, model.num_proposals)
-            continue
-        for pred, h0, _ in sampler.sample_chunks(x2d[lo:hi], None, input_2d_flip=x2d_flip[lo:hi], chunk=hypothesis_chunk):
-            if fit:
-                state = accumulate_poses(state, pred, h0, dataset, x2d[lo:hi], None, cam, fit=True,
-                                         conf=None if conf is None else conf[lo:hi])
-            elif reproj:
-                state = accumulate_poses(state, pred, h0, dataset, x2d[lo:hi], traj[lo:hi], cam)
-            else:
-                state = accumulate_poses(state, pred, h0, dataset)
-            if spread is not None:
-                moments = accumulate_spread(moments, pred, h0, dataset)
-            del pred
-        merged = aggregate_poses_sharded(None, None, model.num_proposals, dataset, group=group, state=state, want=(),
-                                         spread_state=moments, merged=True)
-        frames = accumulate_frames(frames, merged, starts[lo:hi], valid[lo:hi], N, model.num_proposals)
+    needs_cov = plan.fold_spread != plan.spread
     want = (("mean", "count") + (("pick", "idx", "window") if reproj else ())
-            + (() if asked is None else ("std",) if asked == "std" else ("std", "cov"))
-            + (("cov",) if needs_cov and asked != "cov" else ()))
+            + (() if plan.spread is None else ("std",) if plan.spread == "std" else ("std", "cov")) + (("cov",) if needs_cov else ()))
     out = ops.finish_frames(N, frames.T, frames.J, frame=frames.pose, spread=frames.spread, want=want)
     if video:       # one path along the video through the hypotheses of all windows, against the pooled mean
         from .evaluate import path_frames
-        path = path_frames(torch.cat(kept), dataset, seq_2d.to(dev), cam, path_weight, starts, valid, N, frames,
-                           traj=None if fit else video_traj.to(dev), conf=None if frame_conf is None or not fit else frame_conf.to(dev), fit=fit)
+        path = path_frames(torch.cat(kept), dataset, seq_2d.to(dev), cam, plan.path_weight, starts, valid, N, frames,
+                           traj=None if fit else traj.to(dev), conf=None if conf is None or not fit else conf.to(dev), fit=fit)
         del kept
         out.update(pick=path["pick"], idx=path["idx"], window=path["window"], path_cost=path["cost"])
-    if fit:         # a joint without a pick carries the pooled mean
+    return _finish_stages(out, plan, seq_2d, cam, conf)
+
+
+def _finish_stages(out, plan, seq_2d, cam, conf):
+    """The stages behind the finish (or the video path) in their order, each on what the one before it returns: out - finish_frames'
+    dict on the device - becomes infer_sequence(stride=...)'s; seq_2d [N,J,2] and conf [N,J] or None on the CPU, cam on the device"""
+    from . import ops
+    dev = out["mean"].device
+    if plan.aggregate == "reproj_fit":      # a joint without a pick carries the pooled mean
         out["pick"] = torch.where((out["idx"] < 0).unsqueeze(-1), out["mean"], out["pick"])
-    out["pose"] = out.pop("pick") if reproj else out["mean"]
+    out["pose"] = out.pop("pick") if "pick" in out else out["mean"]
     out.pop("mean", None)
-    if needs_cov:
-        cov = out["cov"] if asked == "cov" else out.pop("cov")
-    if pose_smooth is not None:     # right behind the finish, on the pose that is returned: everything below sees the smoothed pose
+    if plan.fold_spread == "cov":           # the covariance is returned only when the caller asked for it
+        cov = out["cov"] if plan.spread == "cov" else out.pop("cov")
+    if plan.pose_smooth is not None:        # on the pose that is returned: everything below sees the smoothed pose
         out["pose_raw"] = out["pose"].contiguous()
-        out["pose"], out["pose_smooth_code"] = ops.smooth_poses(out["pose_raw"], cov, pose_smooth[0], floor=pose_smooth[1], want_code=True)
-    if bones is not None:           # smoothing bends bones, this straightens them; the root fit below sees the constrained pose
-        out.update(_constrain_bones(out["pose"].contiguous(), cov, bones))
-    if trajectory:  # the root of the pose that is returned, on the device before anything crosses to the host
-        out.update(_fit_trajectory(out["pose"], seq_2d.to(dev), cam, None if frame_conf is None else frame_conf.to(dev), smooth, focal))
-    if ground is not None:  # behind the fit and its smoother: the plane through the resting feet of the pose and roots that are returned
-        out.update(_estimate_ground(out["pose"], out["traj"], ground))
+        out["pose"], out["pose_smooth_code"] = ops.smooth_poses(out["pose_raw"], cov, plan.pose_smooth[0], floor=plan.pose_smooth[1], want_code=True)
+    if plan.bones is not None:              # smoothing bends bones, this straightens them; the root fit below sees the constrained pose
+        out.update(_constrain_bones(out["pose"].contiguous(), cov, plan.bones))
+    if plan.trajectory:                     # the root of the pose that is returned, on the device before anything crosses to the host
+        out.update(_fit_trajectory(out["pose"], seq_2d.to(dev), cam, None if conf is None else conf.to(dev), smooth=plan.smooth, focal=plan.focal))
+    if plan.ground is not None:             # behind the fit and its smoother: the plane through the resting feet of the pose and roots
+        out.update(_estimate_ground(out["pose"], out["traj"], plan.ground))
     return out
 
 
@@ -752,7 +819,7 @@ def _estimate_focal(pose, x2d, cam, conf):
     return {"focal": m["focal"], "focal_r2": m["r2"], "focal_frames": m["frames"], "cam": m["cam"]}
 
 
-def _fit_trajectory(pose, x2d, cam, conf, smooth, focal=None):
+def _fit_trajectory(pose, x2d, cam, conf, *, smooth, focal=None):
     """device tensors -> the trajectory keys of infer_sequence / fit_trajectory, on the device"""
     from . import ops
     est = {}
@@ -783,20 +850,15 @@ def fit_trajectory(poses, seq_2d, cam=None, conf=None, smooth=None, device="cuda
     if smooth is True:
         raise ValueError("smooth must be None or a smoothing radius in 1 .. 64")
     smooth = _trajectory_radius(smooth, "smooth")
-    poses = torch.as_tensor(poses, dtype=torch.float32)
-    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
     if cam is None and focal is None:
         raise ValueError('fit_trajectory needs cam (fx, fy, cx, cy first), or focal="estimate"')
-    if poses.dim() != 4 or poses.shape[-1] != 3 or tuple(seq_2d.shape) != (*poses.shape[1:3], 2):
-        raise ValueError(f"poses must be [T,N,J,3] and seq_2d [N,J,2], got {tuple(poses.shape)} and {tuple(seq_2d.shape)}")
-    if conf is not None:
-        conf = torch.as_tensor(conf, dtype=torch.float32)
-        if tuple(conf.shape) != tuple(seq_2d.shape[:2]):
-            raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[:2])}, got {tuple(conf.shape)}")
-    dev = poses.device if poses.is_cuda else torch.device(device)
-    cam = _cam9(cam, dev) if focal is not None else torch.as_tensor(cam, dtype=torch.float32).reshape(-1).to(dev)
-    out = _fit_trajectory(poses.to(dev), seq_2d.to(dev), cam, None if conf is None else conf.to(dev), smooth, focal)
-    return {k: v.cpu() for k, v in out.items()}
+    poses, seq_2d = _poses_operand(poses, seq_2d, "seq_2d [N,J,2]", slice(1, 3), (2,), empty_ok=True)
+    conf = _conf_operand(conf, seq_2d.shape[:2])
+
+    def run(dev):
+        cam9 = _cam9(cam, dev) if focal is not None else torch.as_tensor(cam, dtype=torch.float32).reshape(-1).to(dev)
+        return _fit_trajectory(poses.to(dev), seq_2d.to(dev), cam9, None if conf is None else conf.to(dev), smooth=smooth, focal=focal)
+    return _run_on(poses, device, run)
 
 
 @torch.no_grad()
@@ -814,17 +876,14 @@ def smooth_poses(poses, cov=None, radius=13, floor=1e-3, device="cuda"):
     radius = _pose_smooth_radius(radius, floor, "radius")
     if radius is None:
         raise ValueError("radius must be a smoothing radius in 1 .. 64 (frames), got None")
-    poses = torch.as_tensor(poses, dtype=torch.float32)
-    if poses.dim() != 4 or poses.shape[-1] != 3 or 0 in poses.shape:
-        raise ValueError(f"poses must be [T,N,J,3], got {tuple(poses.shape)}")
-    if cov is not None:
-        cov = torch.as_tensor(cov, dtype=torch.float32)
-        if tuple(cov.shape) != (*poses.shape[:3], 6):
-            raise ValueError(f"cov must be [T,N,J,6] = {(*poses.shape[:3], 6)}, got {tuple(cov.shape)}")
-    dev = poses.device if poses.is_cuda else torch.device(device)
-    raw = poses.to(dev).contiguous()
-    pose, code = ops.smooth_poses(raw, None if cov is None else cov.to(dev).contiguous(), radius, floor=float(floor), want_code=True)
-    return {"pose": pose.cpu(), "pose_raw": raw.cpu(), "pose_smooth_code": code.cpu()}
+    poses = _poses_operand(poses)
+    cov = _cov_operand(cov, poses)
+
+    def run(dev):
+        raw = poses.to(dev).contiguous()
+        pose, code = ops.smooth_poses(raw, None if cov is None else cov.to(dev).contiguous(), radius, floor=float(floor), want_code=True)
+        return {"pose": pose, "pose_raw": raw, "pose_smooth_code": code}
+    return _run_on(poses, device, run)
 
 
 @torch.no_grad()
@@ -850,22 +909,15 @@ def constrain_bones(poses, cov=None, tables=None, lengths="video", iterations=16
         raise ValueError('lengths must be "video", "symmetric" or a tensor [J] or [T,J], got None')
     if not isinstance(snap, (bool, int)) or snap not in (0, 1):
         raise ValueError(f"snap must be a bool, got {snap!r}")
-    poses = torch.as_tensor(poses, dtype=torch.float32)
-    if poses.dim() != 4 or poses.shape[-1] != 3 or 0 in poses.shape:
-        raise ValueError(f"poses must be [T,N,J,3], got {tuple(poses.shape)}")
+    poses = _poses_operand(poses)
     T, N, J, _ = poses.shape
-    if cov is not None:
-        cov = torch.as_tensor(cov, dtype=torch.float32)
-        if tuple(cov.shape) != (T, N, J, 6):
-            raise ValueError(f"cov must be [T,N,J,6] = {(T, N, J, 6)}, got {tuple(cov.shape)}")
+    cov = _cov_operand(cov, poses)
     bones["tables"] = _bone_tables(tables, J=None if tables is None else J)
     if len(bones["tables"][0]) != J:
         raise ValueError(f"the bone tables hold {len(bones['tables'][0])} joints, the pose {J}")
     if not isinstance(bones["lengths"], str) and tuple(bones["lengths"].shape) not in ((J,), (T, J)):
         raise ValueError(f"lengths must be [J] = [{J}] or [T,J] = {(T, J)}, got {tuple(bones['lengths'].shape)}")
-    dev = poses.device if poses.is_cuda else torch.device(device)
-    out = _constrain_bones(poses.to(dev).contiguous(), None if cov is None else cov.to(dev).contiguous(), bones)
-    return {k: v.cpu() for k, v in out.items()}
+    return _run_on(poses, device, lambda dev: _constrain_bones(poses.to(dev).contiguous(), None if cov is None else cov.to(dev).contiguous(), bones))
 
 
 @torch.no_grad()
@@ -880,18 +932,10 @@ def estimate_focal(poses, seq_2d, cam=None, conf=None, device="cuda"):
     [T,9] the intrinsics with the estimate in place - what ``fit_trajectory(..., cam=out["cam"][-1])`` takes.  The estimate
     inherits a depth-scale error of the poses one for one; a single frame or a distant person carries little signal, which
     focal_r2 and focal_frames show."""
-    poses = torch.as_tensor(poses, dtype=torch.float32)
-    seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
-    if poses.dim() != 4 or poses.shape[-1] != 3 or tuple(seq_2d.shape) != (*poses.shape[1:3], 2):
-        raise ValueError(f"poses must be [T,N,J,3] and seq_2d [N,J,2], got {tuple(poses.shape)} and {tuple(seq_2d.shape)}")
-    if conf is not None:
-        conf = torch.as_tensor(conf, dtype=torch.float32)
-        if tuple(conf.shape) != tuple(seq_2d.shape[:2]):
-            raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[:2])}, got {tuple(conf.shape)}")
+    poses, seq_2d = _poses_operand(poses, seq_2d, "seq_2d [N,J,2]", slice(1, 3), (2,), empty_ok=True)
+    conf = _conf_operand(conf, seq_2d.shape[:2])
     cam = _cam9(cam, "cpu")                                          # refused here, before anything touches the device
-    dev = poses.device if poses.is_cuda else torch.device(device)
-    out = _estimate_focal(poses.to(dev), seq_2d.to(dev), cam.to(dev), None if conf is None else conf.to(dev))
-    return {k: v.cpu() for k, v in out.items()}
+    return _run_on(poses, device, lambda dev: _estimate_focal(poses.to(dev), seq_2d.to(dev), cam.to(dev), None if conf is None else conf.to(dev)))
 
 
 GROUND_KEYS = ("up", "camera_height", "ground_rms", "ground_eig", "ground_points", "ground_code", "ground_plane", "foot", "foot_speed",
@@ -948,13 +992,8 @@ def estimate_ground(poses, traj, points=None, radius=3, speed=0.015, passes=3, g
     spec = _ground_spec(radius if radius is not True else None, speed, passes, gate, floor, spread, points)
     if spec is None:
         raise ValueError(f"radius must be a radius in 1 .. 64 (frames), got {radius!r}")
-    poses = torch.as_tensor(poses, dtype=torch.float32)
-    traj = torch.as_tensor(traj, dtype=torch.float32)
-    if poses.dim() != 4 or poses.shape[-1] != 3 or 0 in poses.shape or tuple(traj.shape) != (*poses.shape[:2], 3):
-        raise ValueError(f"poses must be [T,N,J,3] and traj [T,N,3], got {tuple(poses.shape)} and {tuple(traj.shape)}")
-    dev = poses.device if poses.is_cuda else torch.device(device)
-    out = _estimate_ground(poses.to(dev), traj.to(dev), spec)
-    return {k: v.cpu() for k, v in out.items()}
+    poses, traj = _poses_operand(poses, traj, "traj [T,N,3]")
+    return _run_on(poses, device, lambda dev: _estimate_ground(poses.to(dev), traj.to(dev), spec))
 
 
 @torch.no_grad()
@@ -964,18 +1003,16 @@ def frames_to_world(poses, traj, plane, device="cuda"):
     fully denoised step).  ops.frames_to_world.  Returns a dict of CPU tensors ``"pose_world"`` [T,N,J,3] and ``"traj_world"``
     [T,N,3]: z up, the ground at z = 0, x the camera's right levelled; NaN in gives NaN out."""
     from . import ops
-    poses = torch.as_tensor(poses, dtype=torch.float32)
-    traj = torch.as_tensor(traj, dtype=torch.float32)
-    if poses.dim() != 4 or poses.shape[-1] != 3 or 0 in poses.shape or tuple(traj.shape) != (*poses.shape[:2], 3):
-        raise ValueError(f"poses must be [T,N,J,3] and traj [T,N,3], got {tuple(poses.shape)} and {tuple(traj.shape)}")
+    poses, traj = _poses_operand(poses, traj, "traj [T,N,3]")
     plane = torch.as_tensor(plane, dtype=torch.float64)
     if tuple(plane.shape) == (4,):
         plane = plane.expand(poses.shape[0], 4)
     if tuple(plane.shape) != (poses.shape[0], 4):
         raise ValueError(f"plane must be [T,4] = {(poses.shape[0], 4)} or [4], got {tuple(plane.shape)}")
-    dev = poses.device if poses.is_cuda else torch.device(device)
-    pose_world, traj_world = ops.frames_to_world(poses.to(dev).contiguous(), traj.to(dev).contiguous(), plane.to(dev).contiguous())
-    return {"pose_world": pose_world.cpu(), "traj_world": traj_world.cpu()}
+    def run(dev):
+        pose_world, traj_world = ops.frames_to_world(poses.to(dev).contiguous(), traj.to(dev).contiguous(), plane.to(dev).contiguous())
+        return {"pose_world": pose_world, "traj_world": traj_world}
+    return _run_on(poses, device, run)
 
 
 def load_pifpaf_keypoints(path, num_kps=134, with_conf=False):
@@ -1053,10 +1090,9 @@ def track_people(kps, conf, tracks=1, seed=None, gate=0.5, skip=0.05, max_gap=4,
     conf = torch.as_tensor(conf, dtype=torch.float32)
     if kps.dim() != 4 or kps.shape[-1] != 2 or tuple(conf.shape) != tuple(kps.shape[:3]):
         raise ValueError(f"kps must be [N,K,J,2] and conf [N,K,J], got {tuple(kps.shape)} and {tuple(conf.shape)}")
-    dev = kps.device if kps.is_cuda else torch.device(device)
-    out = ops.track_people(kps.to(dev).contiguous(), conf.to(dev).contiguous(), tracks=tracks, seed=seed, gate=gate, skip=skip,
-                           max_gap=max_gap, support=support, min_frames=min_frames, threshold=threshold)
-    return {k: v.cpu() for k, v in out.items()}
+    return _run_on(kps, device, lambda dev: ops.track_people(kps.to(dev).contiguous(), conf.to(dev).contiguous(), tracks=tracks, seed=seed,
+                                                             gate=gate, skip=skip, max_gap=max_gap, support=support,
+                                                             min_frames=min_frames, threshold=threshold))
 
 
 def stitch_clips(prediction, total_frames, frames=27):
@@ -1330,19 +1366,31 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
     ``ground`` (True, or a radius 1 .. 64; with ``trajectory``; None: everything above, unchanged) and ``ground_speed`` also find
     the ground plane of the video, infer_sequence(ground=..., ground_speed=...), behind the trajectory fit.  The metrics are not
     changed by it; one more, last element is returned, a dict of CPU tensors with infer_sequence's ground keys (GROUND_KEYS)."""
-    _focal_mode(focal)
-    ground = _ground_spec(ground, ground_speed)
-    if ground is not None and trajectory is None:
-        raise ValueError("ground needs a trajectory: the ground is found in camera space")
-    pose_smooth = _pose_smooth_radius(pose_smooth, pose_smooth_floor)
-    if pose_smooth is not None:
-        pose_smooth = (pose_smooth, float(pose_smooth_floor))
-    bones = _bone_spec(bone_lengths, bone_iterations)
-    if bones is not None:
-        bones["tables"] = _bone_tables(None, dataset, kps_left, kps_right)
-        if not isinstance(bones["lengths"], str) and bones["lengths"].shape[-1] != len(bones["tables"][0]):
-            raise ValueError(f"bone_lengths must be [J] or [T,J] with J = {len(bones['tables'][0])}, got {tuple(bones['lengths'].shape)}")
-    repair = _repair_radius(repair, repair_threshold)
+    got = _evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, aggregate=aggregate, conf=conf, batch_size=batch_size,
+                           group=group, p2=p2, per_frame=per_frame, drop=drop, corrupt=corrupt, swap=swap, distract=distract, track=track,
+                           stride=stride, trajectory=trajectory, hypothesis_chunk=hypothesis_chunk, focal=focal, repair=repair,
+                           repair_threshold=repair_threshold, path_weight=path_weight, path_scope=path_scope, pose_smooth=pose_smooth,
+                           pose_smooth_floor=pose_smooth_floor, bone_lengths=bone_lengths, bone_iterations=bone_iterations, screen=screen,
+                           screen_gate=screen_gate, screen_floor=screen_floor, ground=ground, ground_speed=ground_speed)
+    return tuple(v for v in got if v is not None)      # the documented shape: the optional elements in the fields' order
+
+
+class _FrameScores(NamedTuple):
+    """evaluate_frames' result by name; what the options did not ask for is None"""
+    sums: dict
+    counts: dict
+    maps: object = None         # per_frame=True
+    estimate: object = None     # focal="estimate": the focal keys
+    seen: object = None         # a planting, screen or repair: the detections as the model saw them
+    held: object = None         # bone_lengths: the lengths held beside the ground truth's
+    found: object = None        # ground: GROUND_KEYS
+
+
+@torch.no_grad()
+def _evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, *, aggregate="mean", conf=None, batch_size=2, group=None,
+                     p2=False, per_frame=False, drop=None, corrupt=None, swap=None, distract=None, track=False, **options):
+    """evaluate_frames with its result named (_FrameScores); `options`: the options it shares with infer_sequence, as _frame_plan
+    takes them"""
     if drop is not None:
         if (not isinstance(drop, (tuple, list)) or len(drop) != 3 or not 0.0 <= float(drop[0]) <= 1.0
                 or isinstance(drop[1], bool) or int(drop[1]) != drop[1] or int(drop[1]) < 1):
@@ -1354,44 +1402,18 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
         raise ValueError("track needs distract: ground-truth 2-D holds one person, there is nobody to tell apart")
     if not isinstance(track, (bool, dict)):
         raise ValueError(f"track must be False, True or a dict of track_people's parameters, got {track!r}")
-    if repair is not None and conf is None and drop is None and corrupt is None and swap is None and distract is None:
-        raise ValueError("repair needs conf [N,J] or drop: a missing detection is one whose confidence is not above repair_threshold")
-    screen = _screen_radius(screen, screen_gate, screen_floor)
     planting = corrupt is not None or swap is not None
     for name, spec, k in (("corrupt", corrupt, 4), ("swap", swap, 3)):
         if spec is not None and (not isinstance(spec, (tuple, list)) or len(spec) != k or not 0.0 <= float(spec[0]) <= 1.0
                                  or isinstance(spec[1], bool) or int(spec[1]) != spec[1] or int(spec[1]) < 1):
             raise ValueError(f"{name} must be (rate in 0 .. 1, run >= 1 frames, {'size, ' if k == 4 else ''}seed), got {spec!r}")
-    if screen is not None:
-        _repair_radius(1, repair_threshold)
-        if conf is None and drop is None and not planting and distract is None:
-            raise ValueError("screen needs conf [N,J], corrupt, swap or drop: a rejected detection leaves with confidence 0")
-    if focal is not None and trajectory is None:
-        raise ValueError('focal="estimate" belongs to a trajectory')
-    if aggregate not in ("mean", "reproj", "reproj_fit"):
-        raise ValueError(f'aggregate must be "mean", "reproj" or "reproj_fit", got {aggregate!r}')
-    frames = getattr(model, "frames", None)
-    if stride is None:
-        stride = frames
-    if isinstance(stride, bool) or not isinstance(stride, int) or not 1 <= stride <= frames:
-        raise ValueError(f"stride must be None or an integer in 1 .. {frames} (the window length), got {stride!r}")
-    smooth = _trajectory_radius(trajectory)
-    path_weight = _path_weight(path_weight, aggregate, hypothesis_chunk, stride, frames, path_scope)
-    if cam is None:
-        raise ValueError("evaluate_frames needs cam [9] (the intrinsics)")
-    if hypothesis_chunk is not None and int(hypothesis_chunk) < 1:
-        raise ValueError("hypothesis_chunk is a positive count")
+    plan = _frame_plan(getattr(model, "frames", None), dataset, kps_left, kps_right, cam=cam, traj=None, conf=conf, aggregate=aggregate,
+                       frames_only=True, conf_made=drop is not None or planting or distract is not None, **options)
     seq_2d = torch.as_tensor(seq_2d, dtype=torch.float32)
     seq_3d = torch.as_tensor(seq_3d, dtype=torch.float32)
     if seq_2d.dim() != 3 or seq_2d.shape[-1] != 2 or tuple(seq_3d.shape) != (*seq_2d.shape[:2], 3):
         raise ValueError(f"seq_2d must be [N,J,2] and seq_3d [N,J,3], got {tuple(seq_2d.shape)} and {tuple(seq_3d.shape)}")
-    if conf is not None:
-        if (aggregate != "reproj_fit" and trajectory is None and repair is None and drop is None and screen is None and not planting
-                and distract is None):
-            raise ValueError('conf belongs to aggregate="reproj_fit" or a trajectory')
-        conf = torch.as_tensor(conf, dtype=torch.float32)
-        if tuple(conf.shape) != tuple(seq_2d.shape[:2]):
-            raise ValueError(f"conf must be [N,J] = {tuple(seq_2d.shape[:2])}, got {tuple(conf.shape)}")
+    conf = _conf_operand(conf, seq_2d.shape[:2])
     from .evaluate import frame_metrics
     dev = next(model.parameters()).device
     seen = None
@@ -1406,11 +1428,10 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
             found = track_people(crowd["x2d"], crowd["conf"], device=dev, **(track if isinstance(track, dict) else {}))
             tracked, seq_2d, conf = found["assign"][0], found["x2d"][0].contiguous(), found["conf"][0].contiguous()
         seen = {"tracked": tracked, "truth_slot": torch.from_numpy(crowd["truth"][0])}
-    if planting or screen is not None:
-        from .detscreen import corrupt as plant_wrong, mirror_table
-        mirror = mirror_table(kps_left, kps_right, seq_2d.shape[1])
     if planting:
-        wrong = plant_wrong(seq_2d.numpy(), torch.ones(seq_2d.shape[:2]).numpy() if conf is None else conf.numpy(), mirror,
+        from .detscreen import corrupt as plant_wrong, mirror_table
+        wrong = plant_wrong(seq_2d.numpy(), torch.ones(seq_2d.shape[:2]).numpy() if conf is None else conf.numpy(),
+                            mirror_table(kps_left, kps_right, seq_2d.shape[1]),
                             outliers=None if corrupt is None else (float(corrupt[0]), int(corrupt[1]), corrupt[2], corrupt[3]),
                             swaps=None if swap is None else (float(swap[0]), int(swap[1]), swap[2]))
         seq_2d, conf = torch.from_numpy(wrong["x2d"]), torch.from_numpy(wrong["conf"])
@@ -1421,25 +1442,20 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
         seq_2d = torch.where(lost.unsqueeze(-1), torch.tensor(DROPPED_XY, dtype=torch.float32), seq_2d)
         conf = torch.where(lost, torch.zeros(()), torch.ones(lost.shape) if conf is None else conf)
         seen = {**(seen or {}), "lost": lost}
-    if screen is not None:
-        screened = _screen_detections(seq_2d, conf, mirror, screen, screen_gate, screen_floor, float(repair_threshold), dev)
-        seq_2d, conf = screened["x2d"].cpu(), screened["conf"].cpu()
-        seen = {**(seen or {}), "screened": screened["status"].cpu()}
-    if repair is not None:
-        from .detections import repair_anchors
-        fixed = _repair_detections(seq_2d, conf, repair_anchors(dataset), repair, float(repair_threshold), dev)
-        seq_2d, conf = fixed["x2d"].cpu(), fixed["conf"].cpu()
-        seen = {**(seen or {}), "status": fixed["status"].cpu()}
+    seq_2d, conf, screened, repaired = _front_end(seq_2d, conf, plan, dataset, kps_left, kps_right, dev)
+    if screened is not None:
+        seen = {**(seen or {}), "screened": screened}
+    if repaired is not None:
+        seen = {**(seen or {}), "status": repaired}
     if seen is not None:
         seen.update(x2d=seq_2d, conf=conf)
     gt_root = seq_3d[:, 0].contiguous()                             # [N,3]
     gt_wb = (seq_3d - seq_3d[:, :1]).to(dev)                        # joint 0 at 0, exactly
-    out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, batch_size, group, aggregate, cam,
-                               gt_root if aggregate == "reproj" else None, hypothesis_chunk, None, conf, stride, dev,
-                               trajectory is not None, smooth, focal, path_weight, path_scope, pose_smooth, bones, ground)
-    found = {k: out[k].cpu() for k in GROUND_KEYS} if ground is not None else None
-    estimate = {k: out[k].cpu() for k in ("focal", "focal_r2", "focal_frames", "cam")} if focal is not None else None
-    held = None
+    out = _infer_frames_device(model, dataset, seq_2d, kps_left, kps_right, plan, cam=cam, traj=gt_root if aggregate == "reproj" else None,
+                               conf=conf, batch_size=batch_size, group=group, dev=dev)
+    found = {k: out[k].cpu() for k in GROUND_KEYS} if plan.ground is not None else None
+    estimate = {k: out[k].cpu() for k in ("focal", "focal_r2", "focal_frames", "cam")} if plan.focal is not None else None
+    bones, held = plan.bones, None
     if bones is not None:           # the lengths held beside the ground truth's, and what the constraint did to the known diagnostic
         from . import ops
         parent, mirror = bones["tables"]
@@ -1453,13 +1469,10 @@ def evaluate_frames(model, dataset, seq_2d, seq_3d, cam, kps_left, kps_right, ag
                       p2=p2, per_frame=per_frame)
     maps = {k: m.pop(k).cpu() for k in ("err", "cnt") if k in m}
     sums, counts = {k: v[0].cpu() for k, v in m.items()}, {k: v[1].cpu() for k, v in m.items()}
-    tail = ((() if estimate is None else (estimate,)) + (() if seen is None else (seen,)) + (() if held is None else (held,))
-            + (() if found is None else (found,)))
     if per_frame:
         from .evaluate import frame_metric_names
         maps["names"] = frame_metric_names(dataset)
-        return (sums, counts, maps) + tail
-    return (sums, counts) + tail
+    return _FrameScores(sums, counts, maps if per_frame else None, estimate, seen, held, found)
 
 
 FRAME_UNITS = {"mpjve": "mm/frame", "root_vel": "mm/frame", "accel": "mm/frame^2"}     # every other metric: mm

@@ -1597,8 +1597,28 @@ def smooth_poses(pose, cov, radius, floor=1e-3, out=None, want_code=False, works
 
 
 # ------------------------------------------------------------------ bone lengths held constant along a video
-_BONE_CACHE_MAX = 16
-_bone_cache = {}    # (what, the table's bytes, device) -> its int32 device copy
+_TABLE_CACHE_MAX = 16
+_table_cache = {}   # (tag, the table's bytes, device) -> its int32 device copy; the oldest entry goes first
+
+
+def _index_table(who, table, J, check, device, tag):
+    """An index table of a per-frame kernel, validated on the host: an integer sequence, numpy array or tensor (refused as `who`
+    when its dtype is not an integer's); check(table, J) -> int32 contiguous numpy, or a ValueError.  -> that array; with
+    `device` its int32 copy there, cached under (tag, bytes, device)."""
+    import numpy as np
+    if isinstance(table, torch.Tensor):
+        _need(not table.dtype.is_floating_point and table.dtype != torch.bool, who)
+        table = table.detach().cpu().numpy()
+    table = check(np.asarray(table), int(J))
+    if device is None:
+        return table
+    key = (tag, table.tobytes(), str(device))
+    hit = _table_cache.get(key)
+    if hit is None:
+        if len(_table_cache) >= _TABLE_CACHE_MAX:
+            _table_cache.pop(next(iter(_table_cache)))
+        hit = _table_cache[key] = torch.from_numpy(table).to(device)
+    return hit
 
 
 def bone_table(table, J, device=None, mirror=False):
@@ -1609,25 +1629,15 @@ def bone_table(table, J, device=None, mirror=False):
     from . import bones
     import numpy as np
     who = "mirror" if mirror else "parent"
-    if isinstance(table, torch.Tensor):
-        _need(not table.dtype.is_floating_point and table.dtype != torch.bool, f"bones: {who} must be an integer table")
-        table = table.detach().cpu().numpy()
-    table = np.asarray(table)
-    _need(table.shape == (int(J),) and table.dtype.kind in "iu", f"bones: {who} must be an integer table [J] = [{int(J)}], got {table.dtype} {table.shape}")
-    if mirror:
-        _need(bool(((table >= -1) & (table < int(J))).all()), f"bones: every mirror entry must be -1 or a joint of 0 .. {int(J) - 1}")
-    else:
-        bones.table(table, int(J), strict=True)
-    table = np.ascontiguousarray(table.astype(np.int32))
-    if device is None:
-        return table
-    key = (who, table.tobytes(), str(device))
-    hit = _bone_cache.get(key)
-    if hit is None:
-        if len(_bone_cache) >= _BONE_CACHE_MAX:
-            _bone_cache.pop(next(iter(_bone_cache)))
-        hit = _bone_cache[key] = torch.from_numpy(table).to(device)
-    return hit
+
+    def check(table, J):
+        _need(table.shape == (J,) and table.dtype.kind in "iu", f"bones: {who} must be an integer table [J] = [{J}], got {table.dtype} {table.shape}")
+        if mirror:
+            _need(bool(((table >= -1) & (table < J)).all()), f"bones: every mirror entry must be -1 or a joint of 0 .. {J - 1}")
+        else:
+            bones.table(table, J, strict=True)
+        return np.ascontiguousarray(table.astype(np.int32))
+    return _index_table(f"bones: {who} must be an integer table", table, J, check, device, "bone " + who)
 
 
 def _bone_operands(who, pose, cov):
@@ -1706,8 +1716,6 @@ def project_bones(pose, cov, parent, length, iterations=16, snap=True, floor=1e-
 
 # ------------------------------------------------------------------ missing 2-D detections, repaired before lifting
 REPAIR_OUTPUTS = {"x2d": ((2,), torch.float32), "conf": ((), torch.float32), "status": ((), torch.uint8)}
-_ANCHOR_CACHE_MAX = 16
-_anchor_cache = {}    # (the table's bytes, device) -> its int32 device copy
 
 
 def repair_anchor_table(anchor, J, device=None):
@@ -1716,20 +1724,7 @@ def repair_anchor_table(anchor, J, device=None):
     of pafuse_detections_repair would demote silently - out of range, the joint itself, an anchored joint - is a ValueError
     (pafuse_amd.detections.check_anchor).  -> int32 numpy [J]; with `device` its cached int32 copy there."""
     from .detections import check_anchor
-    import numpy as np
-    if isinstance(anchor, torch.Tensor):
-        _need(not anchor.dtype.is_floating_point and anchor.dtype != torch.bool, "repair_detections: anchor must be an integer table")
-        anchor = anchor.detach().cpu().numpy()
-    table = check_anchor(np.asarray(anchor), int(J))
-    if device is None:
-        return table
-    key = (table.tobytes(), str(device))
-    hit = _anchor_cache.get(key)
-    if hit is None:
-        if len(_anchor_cache) >= _ANCHOR_CACHE_MAX:
-            _anchor_cache.pop(next(iter(_anchor_cache)))
-        hit = _anchor_cache[key] = torch.from_numpy(table).to(device)
-    return hit
+    return _index_table("repair_detections: anchor must be an integer table", anchor, J, check_anchor, device, "anchor")
 
 
 def repair_detections(x2d, conf, anchor=None, radius=13, threshold=0.0, want=("x2d", "conf", "status")):
@@ -1776,20 +1771,7 @@ def screen_mirror_table(mirror, J, device=None):
     pafuse_detections_screen would drop silently - out of range, the joint itself, a joint that does not point back - is a
     ValueError (pafuse_amd.detscreen.check_mirror).  -> int32 numpy [J]; with `device` its cached int32 copy there."""
     from .detscreen import check_mirror
-    import numpy as np
-    if isinstance(mirror, torch.Tensor):
-        _need(not mirror.dtype.is_floating_point and mirror.dtype != torch.bool, "screen_detections: mirror must be an integer table")
-        mirror = mirror.detach().cpu().numpy()
-    table = check_mirror(np.asarray(mirror), int(J))
-    if device is None:
-        return table
-    key = (b"mirror" + table.tobytes(), str(device))
-    hit = _anchor_cache.get(key)
-    if hit is None:
-        if len(_anchor_cache) >= _ANCHOR_CACHE_MAX:
-            _anchor_cache.pop(next(iter(_anchor_cache)))
-        hit = _anchor_cache[key] = torch.from_numpy(table).to(device)
-    return hit
+    return _index_table("screen_detections: mirror must be an integer table", mirror, J, check_mirror, device, "mirror")
 
 
 def _need_count(who, name, value, lo, hi):
@@ -1994,8 +1976,6 @@ def estimate_focal(pose, x2d, cam, conf=None, want=FOCAL_OUTPUTS):
 GROUND_SLOTS, GROUND_MAX_POINTS = 14, 16
 GROUND_SOLVE_OUTPUTS = ("plane", "scale", "up", "camera_height", "ground_rms", "ground_eig", "ground_points", "ground_code")
 GROUND_OUTPUTS = GROUND_SOLVE_OUTPUTS + ("foot", "foot_speed", "contact", "pose_world", "traj_world")
-_GROUND_CACHE_MAX = 16
-_ground_cache = {}  # (the points' bytes, device) -> their int32 device copy
 
 
 def ground_points(points, J, device=None):
@@ -2003,23 +1983,13 @@ def ground_points(points, J, device=None):
     joints, each in [0, J) (h3wb.foot_points gives the six toe and heel points) -> int32 numpy [K]; with `device` its cached
     int32 copy there."""
     import numpy as np
-    if isinstance(points, torch.Tensor):
-        _need(not points.dtype.is_floating_point and points.dtype != torch.bool, "ground: points must be integers")
-        points = points.detach().cpu().numpy()
-    points = np.asarray(points)
-    _need(points.ndim == 1 and points.dtype.kind in "iu" and 1 <= points.size <= GROUND_MAX_POINTS,
-          f"ground: points must be 1 .. {GROUND_MAX_POINTS} integers, got {points.dtype} {points.shape}")
-    _need(bool(((points >= 0) & (points < int(J))).all()), f"ground: every point must be a joint of 0 .. {int(J) - 1}, got {points.tolist()}")
-    points = np.ascontiguousarray(points.astype(np.int32))
-    if device is None:
-        return points
-    key = (points.tobytes(), str(device))
-    hit = _ground_cache.get(key)
-    if hit is None:
-        if len(_ground_cache) >= _GROUND_CACHE_MAX:
-            _ground_cache.pop(next(iter(_ground_cache)))
-        hit = _ground_cache[key] = torch.from_numpy(points).to(device)
-    return hit
+
+    def check(points, J):
+        _need(points.ndim == 1 and points.dtype.kind in "iu" and 1 <= points.size <= GROUND_MAX_POINTS,
+              f"ground: points must be 1 .. {GROUND_MAX_POINTS} integers, got {points.dtype} {points.shape}")
+        _need(bool(((points >= 0) & (points < J)).all()), f"ground: every point must be a joint of 0 .. {J - 1}, got {points.tolist()}")
+        return np.ascontiguousarray(points.astype(np.int32))
+    return _index_table("ground: points must be integers", points, J, check, device, "ground")
 
 
 def _need_metres(who, name, value):

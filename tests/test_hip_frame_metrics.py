@@ -255,3 +255,85 @@ def test_evaluate_frames_end_to_end_and_infer_sequence_is_unchanged():
     assert "root" not in s0 and all(same_bits(s0[k], s1[k]) and torch.equal(c0[k], c1[k]) for k in s0)
     s2, c2 = harness.evaluate_frames(model, ds, seq_2d, seq_3d, cam, gu.SYN_JOINTS_LEFT, gu.SYN_JOINTS_RIGHT, aggregate="reproj", stride=9)
     assert bool(torch.isfinite(s2["mpjpe"]).all()) and bool((c2["mpjpe"] > 0).all())
+
+
+# ------------------------------------------------------------------------------- the whole chain against its own parts
+N_CHAIN, STRIDE_CHAIN = 2 * F27 + 1, 26     # windows at 0, 26 and a last one at N - F = 28 that lies almost wholly over its predecessor
+
+
+def chain_video(seed=97):
+    """-> (seq_2d [N,J,2], seq_3d, conf [N,J], cam): a person drifting across the screen with a little detector noise, a few gross
+    outliers for the screen and a few lost detections (confidence 0) for the repair"""
+    g = torch.Generator().manual_seed(seed)
+    _, seq_3d, cam = sequence(N_CHAIN)
+    t = torch.arange(N_CHAIN, dtype=torch.float32)[:, None, None]
+    seq_2d = (torch.rand(1, 134, 2, generator=g) - 0.5) + t * 0.004 * (torch.rand(1, 134, 2, generator=g) - 0.5)
+    seq_2d = seq_2d + torch.randn(N_CHAIN, 134, 2, generator=g) * 0.002
+    conf = torch.rand(N_CHAIN, 134, generator=g) * 0.5 + 0.5
+    for n, j in ((4, 7), (20, 100), (30, 16), (N_CHAIN - 2, 50)):
+        seq_2d[n, j] += 0.3
+    for n, j in ((0, 3), (10, 22), (11, 22), (26, 40), (27, 40), (N_CHAIN - 1, 120)):
+        seq_2d[n, j], conf[n, j] = 0.0, 0.0
+    return seq_2d.contiguous(), seq_3d, conf.contiguous(), cam
+
+
+def test_the_whole_chain_in_one_call_is_its_stages_one_by_one_and_evaluate_frames_names_its_dicts():
+    """infer_sequence with every stage on against the stand-alone stages run in the chain's order from the same start of the noise
+    stream: screen, repair, the lift with its spread, pose smoothing, bones, the trajectory with the focal estimate, the ground -
+    every key the same bits.  Then evaluate_frames' tail of optional dicts: its order, told by the key sets, and the named
+    internal result under its names."""
+    from __graft_entry__ import make_model
+    from pafuse_amd import h3wb, harness
+    model = make_model(5, 2, depth=2)[0]
+    ds = dataset()
+    left, right = gu.SYN_JOINTS_LEFT, gu.SYN_JOINTS_RIGHT
+    seq_2d, seq_3d, conf, cam = chain_video()
+
+    def restart():
+        model.noise_fn, model.noise, model.noise_seed = None, "device", SEED            # setting the seed restarts the call index
+
+    restart()
+    whole = harness.infer_sequence(model, ds, seq_2d, left, right, batch_size=2, aggregate="reproj_fit", spread="cov", stride=STRIDE_CHAIN,
+                                   cam=cam, conf=conf, screen=3, repair=3, pose_smooth=2, bone_lengths="symmetric", trajectory=3,
+                                   focal="estimate", ground=True)
+    restart()
+    screened = harness.screen_detections(seq_2d, conf, left, right, radius=3)
+    fixed = harness.repair_detections(screened["x2d"], screened["conf"], dataset=ds, radius=3)
+    lifted = harness.infer_sequence(model, ds, fixed["x2d"], left, right, batch_size=2, aggregate="reproj_fit", spread="cov",
+                                    stride=STRIDE_CHAIN, cam=cam, conf=fixed["conf"])
+    smoothed = harness.smooth_poses(lifted["pose"], lifted["cov"], radius=2)
+    held = harness.constrain_bones(smoothed["pose"], lifted["cov"], tables=h3wb.bone_tables(ds, True, left, right), lengths="symmetric")
+    rooted = harness.fit_trajectory(held["pose"], fixed["x2d"], cam=cam, conf=fixed["conf"], smooth=3, focal="estimate")
+    ground = harness.estimate_ground(held["pose"], rooted["traj"], radius=3)
+    parts = {"screened": screened["status"], "repaired": fixed["status"],
+             **{k: lifted[k] for k in ("count", "idx", "window", "std", "cov")},
+             "pose_raw": lifted["pose"], "pose_smooth_code": smoothed["pose_smooth_code"], "pose_free": smoothed["pose"],
+             **{k: held[k] for k in ("pose", "bone_length", "bone_dev", "bone_frames", "bone_code", "bone_resid")},
+             **rooted, **ground}
+    assert set(lifted) == {"pose", "count", "idx", "window", "std", "cov"} and set(ground) == set(harness.GROUND_KEYS)
+    assert set(rooted) == {"traj", "traj_raw", "traj_weight", "traj_resid", "focal", "focal_r2", "focal_frames", "cam"}
+    assert set(whole) == set(parts)
+    for k in sorted(whole):
+        assert not whole[k].is_cuda and same_bits(whole[k], parts[k]), k
+    assert same_bits(smoothed["pose_raw"], lifted["pose"]) and same_bits(held["pose_free"], smoothed["pose"])
+    # the shapes did their work: frames pooled from two windows (0, 26 and the last one at N - F = 28, in two batches), something
+    # rejected, something filled, a pose all the way through
+    P = model.num_proposals
+    assert whole["count"][25:29].tolist() == [P, 2 * P, P, 2 * P] and whole["count"][52:].tolist() == [2 * P, P, P]
+    assert bool((whole["screened"] == 1).any()) and bool((whole["repaired"] == 1).any())
+    assert tuple(whole["pose_world"].shape) == (2, N_CHAIN, 134, 3) and bool(torch.isfinite(whole["pose"]).all())
+
+    options = dict(stride=STRIDE_CHAIN, trajectory=3, focal="estimate", bone_lengths="video", ground=True,
+                   drop=(0.1, 3, 0), repair=3)
+    keys = [{"focal", "focal_r2", "focal_frames", "cam"}, {"x2d", "conf", "lost", "status"},
+            {"bone_length", "bone_length_gt", "bone_dev_free", "bone_dev"}, set(harness.GROUND_KEYS)]
+    restart()
+    public = harness.evaluate_frames(model, ds, seq_2d, seq_3d, cam, left, right, **options)
+    assert isinstance(public, tuple) and len(public) == 2 + 4
+    assert [set(d) for d in public[2:]] == keys                                         # estimate, seen, held, found
+    assert set(public[0]) == set(public[1]) and "abs_mpjpe" in public[0]
+    restart()
+    named = harness._evaluate_frames(model, ds, seq_2d, seq_3d, cam, left, right, **options)
+    assert named.maps is None
+    for got, want in zip(public, (named.sums, named.counts, named.estimate, named.seen, named.held, named.found)):
+        assert set(got) == set(want) and all(same_bits(got[k], want[k]) for k in got)
