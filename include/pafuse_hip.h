@@ -438,7 +438,7 @@ int pafuse_train_sinusoid(const int64_t *t, const float *freqs, float *out, int3
 /* x[S*L,C] <- Block(x) in place for S contiguous sequences of L tokens (Block.forward, eps 1e-6).  operand_bf16: the
  * matrix-product mode of the four linear layers (as pafuse_mixste2_weights.operand_bf16; 2, 3 and 4 need the *_ws images of
  * their scheme, 4 also qkv_hs / qkv_hb). */
-size_t pafuse_block_workspace_bytes(int64_t rows, int32_t C);
+size_t pafuse_block_workspace_bytes(int64_t rows, int32_t C); /* 0 if a size is < 1 */
 int pafuse_block_forward(const pafuse_block_weights *w, float *x, int64_t S, int32_t L, int32_t C, int32_t heads,
                          int32_t operand_bf16, void *workspace, size_t workspace_bytes, void *stream);
 
@@ -457,7 +457,7 @@ int pafuse_mode_supported(int32_t mode, int32_t C, int32_t hidden, int32_t heads
 int pafuse_mixste2_fused_blocks(const pafuse_mixste2_weights *w);
 
 /* MixSTE2.forward, eval: x2d[B,F,J,2], x3d[B,P,F,J,3], t[B] -> out[B,P,F,J,3]. */
-size_t pafuse_mixste2_workspace_bytes(const pafuse_mixste2_weights *w, int32_t B, int32_t P);
+size_t pafuse_mixste2_workspace_bytes(const pafuse_mixste2_weights *w, int32_t B, int32_t P); /* 0 if w is NULL or a size is < 1 */
 int pafuse_mixste2_forward(const pafuse_mixste2_weights *w, const float *x2d, const float *x3d, const int64_t *t,
                            int32_t B, int32_t P, float *out, void *workspace, size_t workspace_bytes, void *stream);
 
@@ -474,7 +474,7 @@ int pafuse_mixste2_forward(const pafuse_mixste2_weights *w, const float *x2d, co
  * queue a v_pk_*_f32 with a high-register src1 select returns wrong lanes on MI355X
  * (profiles/r03_bf16_mfma_concurrency.md).  A build without that flag ignores the aux streams when any part runs a
  * bf16-MFMA mode (operand_bf16 != 0) and pafuse_d3dp_lanes returns 1. */
-size_t pafuse_d3dp_workspace_bytes(const pafuse_d3dp_config *cfg, int32_t B, int32_t P);
+size_t pafuse_d3dp_workspace_bytes(const pafuse_d3dp_config *cfg, int32_t B, int32_t P); /* 0 if cfg is NULL or a size is < 1 */
 int pafuse_d3dp_sample(const pafuse_d3dp_config *cfg, const pafuse_ddim_step *steps, int32_t nsteps,
                        const float *x2d, const float *x2d_flip, const float *noise, int32_t n_draws, int32_t B,
                        int32_t P, float *out, void *workspace, size_t workspace_bytes, void *stream,

@@ -288,6 +288,48 @@ def load(path=None):
     return _lib
 
 
+_workspace_policy = None   # None: torch.empty.  Only workspace_policy() sets it; nothing in the library or the environment does
+
+
+def workspace(nbytes, device, what, dtype=None):
+    """The one place that allocates a byte arena handed to the C ABI as a `workspace`, `saved`, `scratch` or `work` argument:
+    a contiguous 1-D tensor of exactly max(nbytes, 1) bytes (dtype torch.uint8, the default) or that many bytes' worth of
+    torch.float64 (rounded up to whole elements).  `what`: the fixed name of the call site.  With no policy installed this is
+    torch.empty and the content is whatever the allocator hands over - no entry point may depend on it."""
+    import torch
+    dtype = torch.uint8 if dtype is None else dtype
+    if dtype not in (torch.uint8, torch.float64):
+        raise ValueError(f"workspace({what}): dtype torch.uint8 or torch.float64")
+    n = max(int(nbytes), 1)
+    n = n if dtype == torch.uint8 else (n + 7) // 8 * 8
+    if _workspace_policy is None:
+        return torch.empty(n if dtype == torch.uint8 else n // 8, dtype=dtype, device=device)
+    t = _workspace_policy(n, torch.device(device), what, dtype)
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.dim() == 1 and t.is_contiguous() and t.device.type == torch.device(device).type
+            and t.numel() * t.element_size() == n):
+        raise PafuseError(f"workspace policy returned no contiguous {dtype} tensor of {n} bytes for '{what}'")
+    return t
+
+
+class workspace_policy:
+    """Context manager: workspace() asks policy(nbytes, device, what, dtype) -> tensor for every arena while it is entered, and
+    the previous policy (usually none) afterwards, also when the body raises.  A hook for tests that guard or pre-fill the
+    arenas (tests/workspace_policy.py); nothing installs one otherwise."""
+
+    def __init__(self, policy):
+        self.policy = policy
+
+    def __enter__(self):
+        global _workspace_policy
+        self.previous, _workspace_policy = _workspace_policy, self.policy
+        return self.policy
+
+    def __exit__(self, *exc):
+        global _workspace_policy
+        _workspace_policy = self.previous
+        return False
+
+
 def check(rc):
     if rc < 0:
         raise PafuseError(f"pafuse_hip error {rc}: {load().pafuse_last_error().decode()}")

@@ -1369,7 +1369,7 @@ int pafuse_attention(const float* qkv, float* o, int64_t nseq, int32_t L, int32_
     return attention(a, (hipStream_t)stream);
 }
 
-size_t pafuse_block_workspace_bytes(int64_t rows, int32_t C) { return part_buffer_bytes(rows, C, 1, 6); }
+size_t pafuse_block_workspace_bytes(int64_t rows, int32_t C) { return rows <= 0 || C <= 0 ? 0 : part_buffer_bytes(rows, C, 1, 6); }
 
 int pafuse_block_forward(const pafuse_block_weights* w, float* x, int64_t S, int32_t L, int32_t C, int32_t heads,
                          int32_t operand_bf16, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1411,7 +1411,7 @@ int pafuse_time_embed(const pafuse_mixste2_weights* w, const int64_t* t, int32_t
 }
 
 size_t pafuse_mixste2_workspace_bytes(const pafuse_mixste2_weights* w, int32_t B, int32_t P) {
-    if (!w) return 0;
+    if (!w || B <= 0 || P <= 0 || w->frames <= 0 || w->joints <= 0 || w->channels <= 0) return 0;   // (a negative size must not wrap)
     return part_buffer_bytes((int64_t)B * P * w->frames * w->joints, w->channels, B, image_elem_bytes(w->operand_bf16));
 }
 
@@ -1450,7 +1450,7 @@ int pafuse_mixste2_forward(const pafuse_mixste2_weights* w, const float* x2d, co
 }
 
 size_t pafuse_d3dp_workspace_bytes(const pafuse_d3dp_config* cfg, int32_t B, int32_t P) {
-    if (!cfg) return 0;
+    if (!cfg || B <= 0 || P <= 0 || cfg->frames <= 0 || cfg->num_kps <= 0 || cfg->num_parts < 0 || cfg->num_parts > PAFUSE_MAX_PARTS) return 0;
     const int nflip = cfg->flip ? 2 : 1;
     size_t total = align_up((size_t)B * P * cfg->frames * cfg->num_kps * 3 * 4);  // img
     for (int i = 0; i < cfg->num_parts; ++i) {

@@ -474,7 +474,7 @@ class D3DP(nn.Module):
             if g is None:
                 st = {"x2d": x2d.clone(), "x2f": x2f.clone(), "noise": noise.clone(),
                       "out": torch.empty(B, len(steps), P, self.frames, self.num_kps, 3, device=dev),
-                      "ws": torch.empty(nbytes, dtype=torch.uint8, device=dev), "cfg": cfg, "steps": steps}
+                      "ws": _lib.workspace(nbytes, dev, "d3dp_sample_graph"), "cfg": cfg, "steps": steps}
                 cap = torch.cuda.Stream(device=dev)
                 cap.wait_stream(stream)
                 graph = torch.cuda.CUDAGraph()
@@ -493,7 +493,7 @@ class D3DP(nn.Module):
             return st["out"].clone()
 
         out = torch.empty(B, len(steps), P, self.frames, self.num_kps, 3, device=dev, dtype=torch.float32)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(nbytes, dev, "d3dp_sample")
         launch(x2d, x2f, noise, out, ws, stream)
         for t in (ws, noise, x2d, x2f):
             for s in aux:

@@ -221,7 +221,7 @@ class MixSTE2(nn.Module):
         w = self.weights_struct()
         out = torch.empty(B, P, F, J, 3, device=x_3d.device, dtype=torch.float32)
         nbytes = lib.pafuse_mixste2_workspace_bytes(C.byref(w), B, P)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x_3d.device)
+        ws = _lib.workspace(nbytes, x_3d.device, "mixste2_forward")
         stream = torch.cuda.current_stream(x_3d.device).cuda_stream
         _lib.check(lib.pafuse_mixste2_forward(C.byref(w), x_2d.data_ptr(), x_3d.data_ptr(), t.data_ptr(), B, P,
                                               out.data_ptr(), ws.data_ptr(), nbytes, stream))
@@ -325,7 +325,7 @@ class _TrainFunction(torch.autograd.Function):
         nbytes = lib.pafuse_mixste2_train_bytes(C.byref(w), B)
         if nbytes == 0:
             raise _lib.PafuseError("pafuse_mixste2_train_bytes: unsupported configuration")
-        saved = torch.empty(nbytes, dtype=torch.uint8, device=x_3d.device)
+        saved = _lib.workspace(nbytes, x_3d.device, "mixste2_train")
         out = torch.empty(B, F, J, 3, device=x_3d.device, dtype=torch.float32)
         stream = torch.cuda.current_stream(x_3d.device).cuda_stream
         _lib.check(lib.pafuse_mixste2_train_forward(C.byref(w), x_2d.data_ptr(), x_3d.data_ptr(), t.data_ptr(), B,

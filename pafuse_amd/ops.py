@@ -148,7 +148,7 @@ def linear_weight_grad(d_y, x, precision="bf16x3", bias=True):
     dw = torch.zeros(N, K, device=x.device, dtype=torch.float32)
     db = torch.zeros(N, device=x.device, dtype=torch.float32) if bias else None
     nbytes = lib.pafuse_linear_weight_grad_bytes()
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws = _lib.workspace(nbytes, x.device, "linear_weight_grad")
     with torch.cuda.device(x.device):
         _lib.check(lib.pafuse_linear_weight_grad(_ptr(d_y, "d_y"), _ptr(x, "x"), dw.data_ptr(), db.data_ptr() if bias else None, M, N, K,
                                                  PRECISIONS[precision], ws.data_ptr(), nbytes, _stream(x)))
@@ -169,7 +169,7 @@ def _out_buf(out, name, shape, dev, zero=False):
 
 def _unit_workspace(lib, M, N, K, dev):
     nbytes = lib.pafuse_train_unit_bytes(M, N, K)
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
+    return _lib.workspace(nbytes, dev, "train_unit"), nbytes
 
 
 def layer_norm_backward(dy, x, weight, eps, add=None, drop=None, seq_map=(0, 1, 1), scaled=False, branch=False, out=None):
@@ -272,7 +272,8 @@ def gelu_backward(u, dh, db=None, in_place=False):
 
 def _rim_workspace(nbytes, dev):
     """the workspace of a first- / last-layer unit entry, every float a NaN: a partial sum a kernel fails to write shows in the result"""
-    return torch.full((max(nbytes, 1),), 0xFF, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(nbytes, dev, "train_rim")
+    return ws if _lib._workspace_policy is not None else ws.fill_(0xFF)     # (an installed policy decides what the arena holds)
 
 
 def train_head_grad(dout, hn, head_w, out=None):
@@ -363,7 +364,7 @@ def block_forward(block_params, x, heads=8, precision="f32"):
     images = block_images(get, mode, heads)
     fill_block_struct(w, get, images=images, what=lambda key: key.split(".")[-2])
     nbytes = lib.pafuse_block_workspace_bytes(S * L, Cc)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws = _lib.workspace(nbytes, x.device, "block_forward")
     with torch.cuda.device(x.device):
         _lib.check(lib.pafuse_block_forward(C.byref(w), y.data_ptr(), S, L, Cc, heads, mode, ws.data_ptr(),
                                             nbytes, _stream(x)))
@@ -970,7 +971,7 @@ def hypothesis_partials(pred, gt, x2d, traj, cam, conn, pbroot, part, num_parts,
     assert need == partials_bytes(B, T, P_r, F, J, num_parts)
     out = _state_out("hypothesis_partials", out, need, dev)
     wbytes = int(lib.pafuse_hypothesis_partials_workspace_bytes(B, T, P_r, F, J, num_parts))
-    work = torch.empty(max(wbytes // 8, 1), device=dev, dtype=torch.float64)
+    work = _lib.workspace(wbytes, dev, "hypothesis_partials", torch.float64)
     with torch.cuda.device(dev):
         _lib.check(lib.pafuse_hypothesis_partials(
             _data(pred), _data(gt), _data(x2d), _data(traj), _data(cam), _data(conn), _data(pbroot), _data(part), num_parts,
@@ -1167,7 +1168,7 @@ def pose_path(pred, conn, x2d, root, cam, weight, conf=None, mean=None, want=("p
     need = int(lib.pafuse_pose_path_workspace_bytes(B, T, P, F, J)) if P <= 256 and F <= 256 else 0   # beyond: the library refuses
     assert need == (pose_path_workspace_bytes(B, T, P, F, J) if P <= 256 and F <= 256 else 0)
     if workspace is None:
-        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+        workspace = _lib.workspace(need, dev, "pose_path")
     _need(workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(),
           f"pose_path: workspace must be a uint8 buffer on {dev}")
     ptr = lambda t: None if t is None else _data(t)
@@ -1251,7 +1252,7 @@ def frames_path(pred, conn, x2d, root, cam, weight, starts, valid, conf=None, me
     need = int(lib.pafuse_frames_path_workspace_bytes(N, T, J, P, W, hs.ctypes.data, hv.ctypes.data))
     assert need == frames_path_workspace_bytes(N, T, J, P, hs, hv)
     if workspace is None:
-        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+        workspace = _lib.workspace(need, dev, "frames_path")
     _need(workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(),
           f"frames_path: workspace must be a uint8 buffer on {dev}")
     import numpy as np
@@ -1584,7 +1585,7 @@ def smooth_poses(pose, cov, radius, floor=1e-3, out=None, want_code=False, works
     _need_tensors("smooth_poses", [pose, out] + ([] if cov is None else [cov]), ())
     need = smooth_poses_workspace_bytes(T, N, J)
     if workspace is None:
-        workspace = torch.empty(need // 8, device=pose.device, dtype=torch.float64)
+        workspace = _lib.workspace(need, pose.device, "smooth_poses", torch.float64)
     _need(isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == pose.device and workspace.dtype == torch.float64
           and workspace.dim() == 1 and workspace.is_contiguous() and workspace.numel() * 8 >= need,
           f"smooth_poses: workspace must be a flat float64 tensor of {need} bytes or more on {pose.device}")
@@ -1818,7 +1819,7 @@ def screen_detections(x2d, conf, mirror=None, radius=13, gate=4.0, floor=0.005, 
     out = {k: torch.empty(((N, J) if SCREEN_OUTPUTS[k][0] == "NJ" else (J,)) + SCREEN_OUTPUTS[k][1], device=dev, dtype=SCREEN_OUTPUTS[k][2])
            for k in made}
     need = lib.pafuse_detections_screen_workspace_bytes(N, J)
-    work = torch.empty((need + 7) // 8, device=dev, dtype=torch.float64)
+    work = _lib.workspace(need, dev, "screen_detections", torch.float64)
     ptr = lambda k: out[k].data_ptr() if k in out else None
     with torch.cuda.device(dev):
         _lib.check(lib.pafuse_detections_screen(x2d.data_ptr(), conf.data_ptr(), None if table is None else table.data_ptr(), N, J,
@@ -1843,7 +1844,7 @@ def _track_half(lib, x2d, conf, N, K, J, G, M, support, threshold, gate, skip, m
     dev = x2d.device
     need = lib.pafuse_tracks_workspace_bytes(N, K, J, G)
     _need(need > 0, "track_people: sizes out of range")
-    work = torch.empty(need // 8, device=dev, dtype=torch.float64)
+    work = _lib.workspace(need, dev, "track_people", torch.float64)
     assign = torch.empty(M, N, device=dev, dtype=torch.int32)
     score = torch.empty(M, device=dev, dtype=torch.float64)
     frames = torch.empty(M, device=dev, dtype=torch.int32)
@@ -2194,7 +2195,7 @@ def procrustes_partials(pred, gt, x2d, traj, cam, conn, h0, out=None):
     dev = pred.device
     out = _state_out("procrustes_partials", out, procrustes_partials_bytes(B, T, P_r, F, J), dev)
     wbytes = int(lib.pafuse_procrustes_partials_workspace_bytes(B, T, P_r, F, J))
-    work = torch.empty(max(wbytes // 8, 1), device=dev, dtype=torch.float64)
+    work = _lib.workspace(wbytes, dev, "procrustes_partials", torch.float64)
     with torch.cuda.device(dev):
         _lib.check(lib.pafuse_procrustes_partials(
             _data(pred), _data(gt), _data(x2d), _data(traj), _data(cam), _data(conn), B, T, P_r, F, J, int(h0),

@@ -193,7 +193,7 @@ def block(x: torch.Tensor, weights: List[torch.Tensor], heads: int, precision: s
     images = block_images(get, mode, heads, cache=cached)
     fill_block_struct(w, get, images=images)
     nbytes = lib.pafuse_block_workspace_bytes(S * L, Cc)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws = _lib.workspace(nbytes, x.device, "block_forward")
     _lib.check(lib.pafuse_block_forward(C.byref(w), _ptr(y, "x"), S, L, Cc, heads, mode, ws.data_ptr(), nbytes, _stream(x)))
     return y
 
@@ -215,7 +215,7 @@ def mixste_eval(x2d: torch.Tensor, x3d: torch.Tensor, t: torch.Tensor, weights: 
     x2d, x3d, t = x2d.contiguous().float(), x3d.contiguous().float(), t.contiguous().long()
     out = torch.empty(B, P, F, J, 3, device=x3d.device, dtype=torch.float32)
     nbytes = lib.pafuse_mixste2_workspace_bytes(C.byref(w), B, P)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x3d.device)
+    ws = _lib.workspace(nbytes, x3d.device, "mixste2_forward")
     _lib.check(lib.pafuse_mixste2_forward(C.byref(w), _ptr(x2d, "x2d"), _ptr(x3d, "x3d"), t.data_ptr(), B, P,
                                           out.data_ptr(), ws.data_ptr(), nbytes, _stream(x3d)))
     return out
@@ -283,7 +283,7 @@ def ddim_loop(x2d: torch.Tensor, x2d_flip: torch.Tensor, noise: torch.Tensor, we
     noise = noise.contiguous().float()
     out = torch.empty(B, T, P, F, J, 3, device=dev, dtype=torch.float32)
     nbytes = lib.pafuse_d3dp_workspace_bytes(C.byref(cfg), B, P)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(nbytes, dev, "d3dp_sample")
     _lib.check(lib.pafuse_d3dp_sample(C.byref(cfg), steps, T, _ptr(x2d, "x2d"), _ptr(x2f, "x2d_flip"),
                                       _ptr(noise, "noise"), n_draws, B, P, out.data_ptr(), ws.data_ptr(), nbytes,
                                       _stream(noise), None, 0))
