@@ -3400,42 +3400,56 @@ __global__ void __launch_bounds__(256) pose_fit_partials_kernel(const PoseFitPar
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-// J-Agg COHERENT IN TIME: per line (b, t, j) the path h(f) through the P hypotheses of a clip that minimises the
+// THE J-Agg PATH, COHERENT IN TIME: per line the path through the candidates of N consecutive frames that minimises the
 // reprojection error plus weight * (the distance the joint jumps, relative to the mean pose) - a Viterbi recursion along
-// the frames (statement: pafuse_amd/posepath.py; fp64, contraction pinned OFF, sqrt correctly rounded):
-//   off_f(h) = (double)w - (double)mean_f        w = wb_joint of hypothesis h at frame f (mean null: 0.0)
-//   h available at f: off_f(h) finite;  f observed: conf > 0 (or null) and some available h has a finite e2 (reproj_error)
-//   u_f(h)   = observed ? (available and e2 finite ? (double)e2 : +inf) : (available ? 0 : +inf)
-//   c_f(h)   = u_f(h) + min_h' (c_f-1(h') + weight * sqrt((dx*dx + dy*dy) + dz*dz)),  d = off_f(h) - off_f-1(h'),
-//              the minimum taken in ascending h' under strict < from +inf (back-pointer 0): a NaN never wins
-//   m_f = min_h c_f(h);  c_f -= m_f;  total += m_f
-// and the backtrace from the first minimum (the first exact 0) of the last frame.  A frame without an available hypothesis,
-// or a line without an observed frame, has no path: idx -1, pick NaN, e2 +inf, cost NaN.
+// the frames (statement: pafuse_amd/posepath.py).  ONE recursion (path_forward, path_backtrace) behind two kernels that
+// differ only in where the K_n candidates ("slots") of frame n come from:
+//   pose_path_kernel (pafuse_pose_path), line (b, t, j): the P hypotheses of clip b at its frame n; N = F, K_n = K = P.
+//   frames_path_kernel (pafuse_frames_path), line (t, j): the pairs (window, hypothesis) of ALL windows that cover video
+//     frame n - window w covers [starts[w], starts[w] + valid[w]) - so a path crosses clip seams and pooled windows
+//     (posepath.frames_path = `path` on the dense [W*P, N] form, a window that does not cover a frame being unavailable
+//     there).  The host checked the windows: starts ascend strictly, the ends do not descend, no gap, 0 .. N covered; the
+//     covering windows are then a contiguous range [lo_n, hi_n], both ends monotone in n, and
+//       slot s at frame n = the candidate (w, h) = (lo_n + s / P, s % P), local frame f = n - starts[w]     s < K_n = (hi_n - lo_n + 1) * P
+//     ascends in (w, h): the order of the dense form, so ties go to the lower (window, hypothesis) - the fold's order.
+//     A clip call is this with one window per video: the two give the same bits (tests/test_hip_frames_path.py).
+// The arithmetic (fp64, contraction pinned OFF, sqrt correctly rounded):
+//   off_n(s) = (double)w - (double)mean at (line, n)    w = wb_joint of the slot's hypothesis at its local frame (mean null: 0.0)
+//   s available at n: off_n(s) finite;  n observed: conf > 0 (or null) and some available s has a finite e2 (reproj_error)
+//   u_n(s)   = observed ? (available and e2 finite ? (double)e2 : +inf) : (available ? 0 : +inf)
+//   c_n(s)   = u_n(s) + min_s' (c_n-1(s') + weight * sqrt((dx*dx + dy*dy) + dz*dz)),  d = off_n(s) - off_n-1(s'),
+//              s' ascending over the K_n-1 slots of frame n - 1 under strict < from +inf (back-pointer 0): a NaN never wins
+//   m_n = min_s c_n(s);  c_n -= m_n;  total += m_n
+// and the backtrace from the first minimum (the first exact 0) of the last frame.  A frame without an available candidate,
+// or a line without an observed frame, has no path at ANY frame: idx -1, window -1, pick NaN, e2 +inf, cost NaN.
 //
-// One wave per line, four lines (adjacent joints, mostly of one (b, t)) per workgroup: wave_item.  Lane l owns hypotheses
-// l, l + 64, ... (R <= 4 of them, in registers).  Per frame a lane forms wb_joint, offset and e2 of its hypotheses; the
-// wave's (c, w) of frame f - 1 sit in LDS, 20 bytes per hypothesis, and the loop over h' reads the same address in every lane
-// (a broadcast: no bank conflict).  The LDS rows are the wave's own (DS operations of a wave complete in order): wave
-// barriers, no workgroup barrier.  m_f is a butterfly (wave_min_f64), the first minimum of the last frame a ballot.  The
-// back-pointers, one byte each, go to the caller's workspace [lines,F,P]: the wave that wrote them reads them back (a
-// workgroup-scope fence in between), one dependent byte load per frame.  No atomics, no scratch; nothing depends on the
-// launch shape.
+// One wave per line, four lines (adjacent joints, mostly of one (b, t)) per workgroup: wave_item.  Lane l owns slots l,
+// l + 64, ... (R <= 4, in registers; K <= 256).  Per frame a lane forms wb_joint, offset and e2 of its slots; (c, w) of
+// frame n - 1 sit in LDS, 20 bytes per slot, and the s' loop reads the same address in every lane (a broadcast: no bank
+// conflict).  The LDS rows are the wave's own (DS operations of a wave complete in order): wave barriers, no workgroup
+// barrier.  m_n is a butterfly (wave_min_f64), the first minimum of the last frame a ballot.  The back-pointer stored is the
+// PREVIOUS frame's slot, one byte, in the caller's workspace [lines,N,K]: the wave that wrote them reads them back (a
+// workgroup-scope fence in between), one dependent byte load per frame.  Nothing else is kept per frame but "observed",
+// which the candidate source keeps where it can (below).  No atomics, no scratch; nothing depends on the launch shape.
 // ----------------------------------------------------------------------------------------------------------------
-struct PosePathParams {
-    const float* pred;    // [B,T,P,F,J,3] part-centred predictions, ALL P hypotheses
-    const float* x2d;     // [B,F,J,2]
-    const float* root;    // [B,F,3], or (root_per_h) [B,T,P,F,3]
-    const float* cam;     // [9]
-    const float* conf;    // [B,F,J] or null
-    const int32_t* conn;  // [J]
-    const float* mean;    // [B,T,F,J,3] or null
+struct PathParams {
+    const float* pred;      // clip [B,T,P,F,J,3], video [W,T,P,F,J,3]: part-centred predictions, ALL P hypotheses
+    const float* x2d;       // [B,F,J,2] / [N,J,2]
+    const float* root;      // [B,F,3] / [N,3], or (root_per_h) as pred without J: [.,T,P,F,3]
+    const float* cam;       // [9]
+    const float* conf;      // [B,F,J] / [N,J] or null
+    const int32_t* conn;    // [J]
+    const float* mean;      // [B,T,F,J,3] / [T,N,J,3] or null
+    const int32_t* starts;  // video: [W] device copies of the window tables
+    const int32_t* valid;   // video: [W]
     double weight;
-    float* pick;          // [B,T,F,J,3]
-    int32_t* pick_idx;    // [B,T,F,J]
-    float* pick_e2;       // [B,T,F,J] or null
-    double* cost;         // [B,T,J] or null
-    uint8_t* back;        // [B*T*J,F,P] back-pointers (workspace)
-    int B, T, P, F, J, root_per_h;
+    float* pick;            // [B,T,F,J,3] / [T,N,J,3]
+    int32_t* pick_idx;      // [B,T,F,J] / [T,N,J]
+    int32_t* pick_win;      // video: [T,N,J]; clip: null
+    float* pick_e2;         // as pick_idx, or null
+    double* cost;           // [B,T,J] / [T,J] or null
+    uint8_t* back;          // [lines,N,K] back-pointers (workspace)
+    int V, W, T, P, F, J, N, K, root_per_h;   // V clips (video: 1), W windows (clip: 1); clip: N = F, K = P
 };
 
 // after the butterfly every lane of the wave holds the same bits (no NaN among the operands: fmin is then commutative)
@@ -3445,35 +3459,96 @@ __device__ __forceinline__ double wave_min_f64(double v) {
     return v;
 }
 
+// where a line's operands start: frame n is row0 + n of x2d / conf / the shared root and out0 + n * J of mean and the outputs
+struct PathLine {
+    int64_t line, row0, out0;
+    int j;
+};
+
+// The candidates of a clip's line (b, t, j): slot = hypothesis, the same P at every frame.  "Observed" is a bit set in
+// registers - lane l keeps frames l, l + 64, ...: bit n >> 6 -, which is where pafuse_pose_path's F <= 256 comes from.
+struct ClipCandidates {
+    static constexpr bool ragged = false;   // K_n = K at every frame: no round of slots is ever empty
+    int64_t bt;
+    int P, F;
+    uint32_t obs;
+    __device__ int slots(int) { return P; }
+    __device__ bool candidate(int n, int s, int64_t& hyp) const { return hyp = (bt * P + s) * F + n, true; }   // (b, t, h, f)
+    __device__ void mark(int n, int64_t, bool observed) {
+        if (observed && wave_lane() == (n & 63)) obs |= 1u << (n >> 6);
+    }
+    __device__ bool marked(int n, int64_t) const { return (__shfl((int)obs, n & 63) >> (n >> 6)) & 1; }
+    __device__ void back_to(int) {}
+    __device__ void chosen(int n, int s, int64_t& hyp, int& h, int& win) const { h = s, win = 0, candidate(n, s, hyp); }
+};
+
+// The candidates of a video's line (t, j): the window range advances on wave-uniform reads of the device tables.  N has no
+// limit, so "observed" cannot live in registers: pick_e2 (when wanted; otherwise the backtrace forms no e2) carries it from
+// the forward pass to the backtrace as 0 or +inf, then overwritten with the value - stored and loaded by the same wave.
+// The backtrace recovers lo_n by walking the window pointer back (monotone).  Sizes the device tables would lead out of
+// (they are the caller's copy of the checked host tables) are clamped, never followed.
+struct VideoCandidates {
+    static constexpr bool ragged = true;
+    const int32_t *starts, *valid;
+    float* e2;
+    int W, T, P, F, K, t, lo, hi;
+    __device__ int slots(int n) {
+        while (hi + 1 < W && starts[hi + 1] <= n) ++hi;              // wave-uniform
+        while (lo < hi && starts[lo] + valid[lo] <= n) ++lo;
+        return min((hi - lo + 1) * P, K);
+    }
+    __device__ bool candidate(int n, int s, int64_t& hyp) const {
+        const int wl = s / P, h = s - wl * P, win = lo + wl;
+        const int f = n - starts[win];
+        hyp = (((int64_t)win * T + t) * P + h) * F + f;   // (w, t, h, f)
+        return f >= 0 && f < F;
+    }
+    __device__ void mark(int, int64_t e, bool observed) {
+        if (e2 && wave_lane() == 0) e2[e] = observed ? 0.f : INFINITY;
+    }
+    __device__ bool marked(int, int64_t e) const { return e2 && e2[e] == 0.f; }
+    __device__ void back_to(int n) {
+        while (lo > 0 && starts[lo - 1] + valid[lo - 1] > n) --lo;   // lo_n: the first window that ends behind n
+    }
+    __device__ void chosen(int n, int s, int64_t& hyp, int& h, int& win) const {
+        const int wl = s / P;
+        h = s - wl * P, win = min(lo + wl, W - 1);
+        hyp = (((int64_t)win * T + t) * P + h) * F + min(max(n - starts[win], 0), F - 1);
+    }
+};
+
+// what the forward pass leaves to the backtrace: the normalised costs of the last frame's slots
 template <int R>
-__global__ void __launch_bounds__(256) pose_path_kernel(const PosePathParams p) {
+struct PathEnd {
+    double c[R], total;
+    int kn;
+    bool alive;
+};
+
+template <int R, class Candidates>
+__device__ __forceinline__ void path_forward(const PathParams& p, const PathLine& at, Candidates& src, PathEnd<R>& end) {
     __shared__ double s_c[4][64 * R];
     __shared__ float s_w[4][3][64 * R];
     const int lane = wave_lane(), wv = threadIdx.x >> 6;
-    const int64_t line = wave_item();
-    if (line >= (int64_t)p.B * p.T * p.J) return;   // wave-uniform: all 64 lanes of a wave share `line`
-    const int P = p.P, F = p.F, J = p.J;
-    const int j = (int)(line % J);
-    const int64_t bt = line / J;
-    const int b = (int)(bt / p.T);
-    const float* pose0 = p.pred + bt * P * F * J * 3;   // hypothesis h, frame f: + (h * F + f) * J * 3
-    const int64_t hstride = (int64_t)F * J * 3;
-    uint8_t* back = p.back + line * F * P;
+    const int J = p.J, N = p.N, K = p.K, j = at.j;
+    uint8_t* back = p.back + at.line * N * K;
     double* sc = s_c[wv];
     float *sw0 = s_w[wv][0], *sw1 = s_w[wv][1], *sw2 = s_w[wv][2];
     const double lam = p.weight, inf = (double)INFINITY;
     const float qnan = __builtin_nanf("");
     double c[R], total = 0.0, mprev[3] = {0.0, 0.0, 0.0};
-    uint32_t myobs = 0;            // lane l keeps "observed" of frames l, l + 64, ...: bit f >> 6
     bool dead = false, any_obs = false;
-    for (int f = 0; f < F; ++f) {
+    int kn = 0, kprev = 0;
+    for (int n = 0; n < N; ++n) {
 #pragma clang fp contract(off)
-        const int64_t bf = (int64_t)b * F + f;
-        const float x20 = p.x2d[(bf * J + j) * 2], x21 = p.x2d[(bf * J + j) * 2 + 1];
-        const bool seen = p.conf ? p.conf[bf * J + j] > 0.f : true;
+        kprev = kn;
+        kn = src.slots(n);
+        const int64_t row = at.row0 + n, e = at.out0 + (int64_t)n * J;
+        const float x20 = p.x2d[(row * J + j) * 2], x21 = p.x2d[(row * J + j) * 2 + 1];
+        const bool seen = p.conf ? p.conf[row * J + j] > 0.f : true;
         double m3[3] = {0.0, 0.0, 0.0};
         if (p.mean) {
-            const float* mp = p.mean + ((bt * F + f) * J + j) * 3;
+            const float* mp = p.mean + e * 3;
             m3[0] = (double)mp[0], m3[1] = (double)mp[1], m3[2] = (double)mp[2];
         }
         float w[R][3];
@@ -3481,13 +3556,14 @@ __global__ void __launch_bounds__(256) pose_path_kernel(const PosePathParams p) 
         bool avail[R], fin[R], any_avail = false, any_fin = false;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const int h = r * 64 + lane;
+            const int s = r * 64 + lane;
+            int64_t hyp;
             avail[r] = fin[r] = false;
             w[r][0] = w[r][1] = w[r][2] = qnan;
             off[r][0] = off[r][1] = off[r][2] = 0.0, u[r] = inf;
-            if (h < P) {
-                wb_joint(pose0 + h * hstride + (int64_t)f * J * 3, p.conn, j, w[r]);
-                const float* tr = p.root_per_h ? p.root + ((bt * P + h) * F + f) * 3 : p.root + bf * 3;
+            if (s < kn && src.candidate(n, s, hyp)) {
+                wb_joint(p.pred + hyp * J * 3, p.conn, j, w[r]);
+                const float* tr = p.root_per_h ? p.root + hyp * 3 : p.root + row * 3;
                 const float e2 = reproj_error(w[r], tr[0], tr[1], tr[2], x20, x21, p.cam);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) off[r][k] = (double)w[r][k] - m3[k];
@@ -3500,196 +3576,7 @@ __global__ void __launch_bounds__(256) pose_path_kernel(const PosePathParams p) 
         const bool observed = __ballot(any_fin) != 0;
         dead |= __ballot(any_avail) == 0;
         any_obs |= observed;
-        if (observed && lane == (f & 63)) myobs |= 1u << (f >> 6);
-#pragma unroll
-        for (int r = 0; r < R; ++r) u[r] = observed ? (fin[r] ? u[r] : inf) : (avail[r] ? 0.0 : inf);
-        if (f == 0) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) c[r] = u[r];
-        } else {
-            double best[R];
-            int bp[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) best[r] = inf, bp[r] = 0;
-            for (int hp = 0; hp < P; ++hp) {   // the same LDS address in every lane
-                const double cp = sc[hp];
-                const double o0 = (double)sw0[hp] - mprev[0], o1 = (double)sw1[hp] - mprev[1], o2 = (double)sw2[hp] - mprev[2];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const double dx = off[r][0] - o0, dy = off[r][1] - o1, dz = off[r][2] - o2;
-                    const double v = cp + lam * sqrt((dx * dx + dy * dy) + dz * dz);
-                    if (v < best[r]) best[r] = v, bp[r] = hp;   // first minimum wins; a NaN (an unavailable h') never does
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                c[r] = u[r] + best[r];
-                if (r * 64 + lane < P) back[(int64_t)f * P + r * 64 + lane] = (uint8_t)bp[r];
-            }
-        }
-        double m = c[0];
-#pragma unroll
-        for (int r = 1; r < R; ++r) m = fmin(m, c[r]);
-        m = wave_min_f64(m);
-        total += m;
-        __builtin_amdgcn_wave_barrier();   // the reads of frame f - 1 come before the writes of frame f
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            c[r] -= m;
-            const int h = r * 64 + lane;
-            if (h < P) sc[h] = c[r], sw0[h] = w[r][0], sw1[h] = w[r][1], sw2[h] = w[r][2];
-        }
-        __builtin_amdgcn_wave_barrier();
-        mprev[0] = m3[0], mprev[1] = m3[1], mprev[2] = m3[2];
-    }
-    const int64_t out0 = bt * F * J + j;   // frame f: + f * J
-    if (dead || !any_obs) {
-        for (int f = lane; f < F; f += 64) {
-            const int64_t e = out0 + (int64_t)f * J;
-            p.pick_idx[e] = -1;
-            p.pick[e * 3 + 0] = qnan, p.pick[e * 3 + 1] = qnan, p.pick[e * 3 + 2] = qnan;
-            if (p.pick_e2) p.pick_e2[e] = INFINITY;
-        }
-        if (p.cost && lane == 0) p.cost[line] = __builtin_nan("");
-        return;
-    }
-    int h = 0;
-#pragma unroll
-    for (int r = R - 1; r >= 0; --r) {   // the first h whose normalised cost is the exact 0
-        const uint64_t zero = __ballot(r * 64 + lane < P && c[r] == 0.0);
-        if (zero) h = r * 64 + __builtin_ctzll(zero);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the back-pointers this wave stored are what it now loads
-    if (p.cost && lane == 0) p.cost[line] = total;
-    for (int f = F - 1; f >= 0; --f) {   // wave-uniform walk: every lane follows the path, lane 0 writes
-        const int hprev = f > 0 ? (int)back[(int64_t)f * P + h] : 0;
-        const int64_t bf = (int64_t)b * F + f, e = out0 + (int64_t)f * J;
-        float w[3];
-        wb_joint(pose0 + h * hstride + (int64_t)f * J * 3, p.conn, j, w);
-        float e2 = INFINITY;
-        if ((__shfl((int)myobs, f & 63) >> (f >> 6)) & 1) {
-            const float* tr = p.root_per_h ? p.root + ((bt * P + h) * F + f) * 3 : p.root + bf * 3;
-            e2 = reproj_error(w, tr[0], tr[1], tr[2], p.x2d[(bf * J + j) * 2], p.x2d[(bf * J + j) * 2 + 1], p.cam);
-        }
-        if (lane == 0) {
-            p.pick_idx[e] = h;
-            p.pick[e * 3 + 0] = w[0], p.pick[e * 3 + 1] = w[1], p.pick[e * 3 + 2] = w[2];
-            if (p.pick_e2) p.pick_e2[e] = e2;
-        }
-        h = hprev;
-    }
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// THE PATH OF A WHOLE VIDEO: the recursion above along the N frames of a video instead of the F frames of a clip.  At
-// video frame n the candidates are the pairs (window, hypothesis) of ALL windows that cover n - window w covers
-// [starts[w], starts[w] + valid[w]) - so a path crosses clip seams and pooled windows (statement:
-// pafuse_amd/posepath.py frames_path = `path` on the dense [W*P, N] form, a window that does not cover a frame being
-// unavailable there).  The host checked the windows: starts ascend strictly, the ends do not descend, no gap, 0 .. N
-// covered; the covering windows are then a contiguous range [lo_n, hi_n], both ends monotone in n, and
-//   slot s at frame n = the candidate (w, h) = (lo_n + s / P, s % P), local frame f = n - starts[w]     s < K_n = (hi_n - lo_n + 1) * P
-// ascends in (w, h): the order of the dense form, so ties go to the lower (window, hypothesis) - the fold's order.
-// The arithmetic is pose_path_kernel's, operation for operation (fp64, contraction pinned OFF, sqrt correctly rounded):
-//   off_n(s) = (double)w - (double)mean[t,n,j]      w = wb_joint of the slot's hypothesis at its local frame (mean null: 0.0)
-//   s available at n: off_n(s) finite;  n observed: conf[n,j] > 0 (or null) and some available s has a finite e2 (reproj_error)
-//   u_n(s)   = observed ? (available and e2 finite ? (double)e2 : +inf) : (available ? 0 : +inf)
-//   c_n(s)   = u_n(s) + min_s' (c_n-1(s') + weight * sqrt((dx*dx + dy*dy) + dz*dz)),  d = off_n(s) - off_n-1(s'),
-//              s' ascending over the K_n-1 slots of frame n - 1 under strict < from +inf (back-pointer 0): a NaN never wins
-//   m_n = min_s c_n(s);  c_n -= m_n;  total += m_n
-// and the backtrace from the first exact 0 of the last frame.  A frame without an available candidate, or a line without an
-// observed frame, has no path at ANY frame: idx -1, window -1, pick NaN, e2 +inf, cost NaN.
-//
-// One wave per line (t, j), four adjacent joints per workgroup (wave_item).  Lane l owns slots l, l + 64, ... (R <= 4, in
-// registers; K = P * the largest coverage <= 256).  Per frame the window range advances on wave-uniform reads of the device
-// tables; a lane forms wb_joint, offset and e2 of its slots; (c, w) of frame n - 1 sit in the wave's own LDS rows and the
-// s' loop reads the same address in every lane (a broadcast).  Wave barriers, no workgroup barrier.  The back-pointer
-// stored is the PREVIOUS frame's slot, one byte, in the caller's workspace [lines,N,K]; the backtrace recovers lo_n by
-// walking the window pointer back (monotone), nothing else is kept per frame - except "observed", which pick_e2 (when wanted)
-// carries from the forward pass to the backtrace: 0 or +inf, then overwritten with the value.  The wave that wrote both
-// reads them back, a workgroup-scope fence in between.  No atomics, no scratch; nothing depends on the launch shape.
-// Sizes the device tables would lead out of (they are the caller's copy of the checked host tables) are clamped, never followed.
-// ----------------------------------------------------------------------------------------------------------------
-struct FramesPathParams {
-    const float* pred;      // [W,T,P,F,J,3] part-centred predictions, ALL P hypotheses of every window
-    const float* x2d;       // [N,J,2]
-    const float* root;      // [N,3], or (root_per_h) [W,T,P,F,3]
-    const float* cam;       // [9]
-    const float* conf;      // [N,J] or null
-    const int32_t* conn;    // [J]
-    const float* mean;      // [T,N,J,3] or null
-    const int32_t* starts;  // [W] device copies of the window tables
-    const int32_t* valid;   // [W]
-    double weight;
-    float* pick;            // [T,N,J,3]
-    int32_t* pick_idx;      // [T,N,J]
-    int32_t* pick_win;      // [T,N,J]
-    float* pick_e2;         // [T,N,J] or null
-    double* cost;           // [T,J] or null
-    uint8_t* back;          // [T*J,N,K] back-pointers (workspace)
-    int W, T, P, F, J, N, K, root_per_h;
-};
-
-template <int R>
-__global__ void __launch_bounds__(256) frames_path_kernel(const FramesPathParams p) {
-    __shared__ double s_c[4][64 * R];
-    __shared__ float s_w[4][3][64 * R];
-    const int lane = wave_lane(), wv = threadIdx.x >> 6;
-    const int64_t line = wave_item();
-    if (line >= (int64_t)p.T * p.J) return;   // wave-uniform: all 64 lanes of a wave share `line`
-    const int W = p.W, T = p.T, P = p.P, F = p.F, J = p.J, N = p.N, K = p.K;
-    const int j = (int)(line % J), t = (int)(line / J);
-    uint8_t* back = p.back + line * N * K;
-    double* sc = s_c[wv];
-    float *sw0 = s_w[wv][0], *sw1 = s_w[wv][1], *sw2 = s_w[wv][2];
-    const double lam = p.weight, inf = (double)INFINITY;
-    const float qnan = __builtin_nanf("");
-    const int64_t out0 = (int64_t)t * N * J + j;   // frame n: + n * J
-    double c[R], total = 0.0, mprev[3] = {0.0, 0.0, 0.0};
-    bool dead = false, any_obs = false;
-    int lo = 0, hi = 0, kn = 0, kprev = 0;
-    for (int n = 0; n < N; ++n) {
-#pragma clang fp contract(off)
-        while (hi + 1 < W && p.starts[hi + 1] <= n) ++hi;              // wave-uniform
-        while (lo < hi && p.starts[lo] + p.valid[lo] <= n) ++lo;
-        kprev = kn;
-        kn = min((hi - lo + 1) * P, K);
-        const float x20 = p.x2d[((int64_t)n * J + j) * 2], x21 = p.x2d[((int64_t)n * J + j) * 2 + 1];
-        const bool seen = p.conf ? p.conf[(int64_t)n * J + j] > 0.f : true;
-        double m3[3] = {0.0, 0.0, 0.0};
-        if (p.mean) {
-            const float* mp = p.mean + (out0 + (int64_t)n * J) * 3;
-            m3[0] = (double)mp[0], m3[1] = (double)mp[1], m3[2] = (double)mp[2];
-        }
-        float w[R][3];
-        double off[R][3], u[R];
-        bool avail[R], fin[R], any_avail = false, any_fin = false;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int s = r * 64 + lane;
-            avail[r] = fin[r] = false;
-            w[r][0] = w[r][1] = w[r][2] = qnan;
-            off[r][0] = off[r][1] = off[r][2] = 0.0, u[r] = inf;
-            if (s < kn) {
-                const int wl = s / P, h = s - wl * P, win = lo + wl;
-                const int f = n - p.starts[win];
-                if (f >= 0 && f < F) {
-                    const int64_t hyp = (((int64_t)win * T + t) * P + h) * F + f;   // (w, t, h, f)
-                    wb_joint(p.pred + hyp * J * 3, p.conn, j, w[r]);
-                    const float* tr = p.root_per_h ? p.root + hyp * 3 : p.root + (int64_t)n * 3;
-                    const float e2 = reproj_error(w[r], tr[0], tr[1], tr[2], x20, x21, p.cam);
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) off[r][k] = (double)w[r][k] - m3[k];
-                    avail[r] = isfinite(off[r][0]) && isfinite(off[r][1]) && isfinite(off[r][2]);
-                    fin[r] = avail[r] && seen && isfinite(e2);
-                    u[r] = (double)e2;
-                }
-            }
-            any_avail |= avail[r], any_fin |= fin[r];
-        }
-        const bool observed = __ballot(any_fin) != 0;
-        dead |= __ballot(any_avail) == 0;
-        any_obs |= observed;
-        if (p.pick_e2 && lane == 0) p.pick_e2[out0 + (int64_t)n * J] = observed ? 0.f : INFINITY;   // for the backtrace
+        src.mark(n, e, observed);   // for the backtrace
 #pragma unroll
         for (int r = 0; r < R; ++r) u[r] = observed ? (fin[r] ? u[r] : inf) : (avail[r] ? 0.0 : inf);
         if (n == 0) {
@@ -3706,7 +3593,7 @@ __global__ void __launch_bounds__(256) frames_path_kernel(const FramesPathParams
                 const double o0 = (double)sw0[sp] - mprev[0], o1 = (double)sw1[sp] - mprev[1], o2 = (double)sw2[sp] - mprev[2];
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    if (r > 0 && r >= rounds) break;   // (kn >= P >= 1: round 0 always runs, and R = 1 has no test)
+                    if (Candidates::ragged && r > 0 && r >= rounds) break;   // (kn >= P >= 1: round 0 always runs, and R = 1 has no test)
                     const double dx = off[r][0] - o0, dy = off[r][1] - o1, dz = off[r][2] - o2;
                     const double v = cp + lam * sqrt((dx * dx + dy * dy) + dz * dz);
                     if (v < best[r]) best[r] = v, bp[r] = sp;   // first minimum wins; a NaN (an unavailable s') never does
@@ -3733,44 +3620,83 @@ __global__ void __launch_bounds__(256) frames_path_kernel(const FramesPathParams
         __builtin_amdgcn_wave_barrier();
         mprev[0] = m3[0], mprev[1] = m3[1], mprev[2] = m3[2];
     }
-    if (dead || !any_obs) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) end.c[r] = c[r];
+    end.total = total, end.kn = kn, end.alive = !dead && any_obs;
+}
+
+template <int R, class Candidates>
+__device__ __forceinline__ void path_backtrace(const PathParams& p, const PathLine& at, Candidates& src, const PathEnd<R>& end) {
+    const int lane = wave_lane();
+    const int J = p.J, N = p.N, K = p.K, j = at.j;
+    const uint8_t* back = p.back + at.line * N * K;
+    if (!end.alive) {
+        const float qnan = __builtin_nanf("");
         for (int n = lane; n < N; n += 64) {
-            const int64_t e = out0 + (int64_t)n * J;
-            p.pick_idx[e] = -1, p.pick_win[e] = -1;
+            const int64_t e = at.out0 + (int64_t)n * J;
+            p.pick_idx[e] = -1;
+            if (p.pick_win) p.pick_win[e] = -1;
             p.pick[e * 3 + 0] = qnan, p.pick[e * 3 + 1] = qnan, p.pick[e * 3 + 2] = qnan;
             if (p.pick_e2) p.pick_e2[e] = INFINITY;
         }
-        if (p.cost && lane == 0) p.cost[line] = __builtin_nan("");
+        if (p.cost && lane == 0) p.cost[at.line] = __builtin_nan("");
         return;
     }
     int s = 0;
 #pragma unroll
     for (int r = R - 1; r >= 0; --r) {   // the first slot whose normalised cost is the exact 0
-        const uint64_t zero = __ballot(r * 64 + lane < kn && c[r] == 0.0);
+        const uint64_t zero = __ballot(r * 64 + lane < end.kn && end.c[r] == 0.0);
         if (zero) s = r * 64 + __builtin_ctzll(zero);
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the back-pointers and marks this wave stored are what it now loads
-    if (p.cost && lane == 0) p.cost[line] = total;
+    if (p.cost && lane == 0) p.cost[at.line] = end.total;
     for (int n = N - 1; n >= 0; --n) {   // wave-uniform walk: every lane follows the path, lane 0 writes
-        while (lo > 0 && p.starts[lo - 1] + p.valid[lo - 1] > n) --lo;   // lo_n: the first window that ends behind n
+        src.back_to(n);
         const int sprev = n > 0 ? (int)back[(int64_t)n * K + s] : 0;
-        const int wl = s / P, h = s - wl * P, win = min(lo + wl, W - 1);
-        const int f = min(max(n - p.starts[win], 0), F - 1);
-        const int64_t hyp = (((int64_t)win * T + t) * P + h) * F + f, e = out0 + (int64_t)n * J;
+        const int64_t row = at.row0 + n, e = at.out0 + (int64_t)n * J;
+        int64_t hyp;
+        int h, win;
+        src.chosen(n, s, hyp, h, win);
         float w[3];
         wb_joint(p.pred + hyp * J * 3, p.conn, j, w);
         float e2 = INFINITY;
-        if (p.pick_e2 && p.pick_e2[e] == 0.f) {   // observed (the forward pass's mark)
-            const float* tr = p.root_per_h ? p.root + hyp * 3 : p.root + (int64_t)n * 3;
-            e2 = reproj_error(w, tr[0], tr[1], tr[2], p.x2d[((int64_t)n * J + j) * 2], p.x2d[((int64_t)n * J + j) * 2 + 1], p.cam);
+        if (src.marked(n, e)) {   // observed
+            const float* tr = p.root_per_h ? p.root + hyp * 3 : p.root + row * 3;
+            e2 = reproj_error(w, tr[0], tr[1], tr[2], p.x2d[(row * J + j) * 2], p.x2d[(row * J + j) * 2 + 1], p.cam);
         }
         if (lane == 0) {
-            p.pick_idx[e] = h, p.pick_win[e] = win;
+            p.pick_idx[e] = h;
+            if (p.pick_win) p.pick_win[e] = win;
             p.pick[e * 3 + 0] = w[0], p.pick[e * 3 + 1] = w[1], p.pick[e * 3 + 2] = w[2];
             if (p.pick_e2) p.pick_e2[e] = e2;
         }
         s = sprev;
     }
+}
+
+template <int R>
+__global__ void __launch_bounds__(256) pose_path_kernel(const PathParams p) {
+    const int64_t line = wave_item();
+    if (line >= (int64_t)p.V * p.T * p.J) return;   // wave-uniform: all 64 lanes of a wave share `line`
+    const int j = (int)(line % p.J);
+    const int64_t bt = line / p.J, b = bt / p.T;
+    const PathLine at{line, b * p.F, bt * p.F * p.J + j, j};
+    ClipCandidates src{bt, p.P, p.F, 0u};
+    PathEnd<R> end;
+    path_forward<R>(p, at, src, end);
+    path_backtrace<R>(p, at, src, end);
+}
+
+template <int R>
+__global__ void __launch_bounds__(256) frames_path_kernel(const PathParams p) {
+    const int64_t line = wave_item();
+    if (line >= (int64_t)p.T * p.J) return;   // wave-uniform: all 64 lanes of a wave share `line`
+    const int j = (int)(line % p.J), t = (int)(line / p.J);
+    const PathLine at{line, 0, (int64_t)t * p.N * p.J + j, j};
+    VideoCandidates src{p.starts, p.valid, p.pick_e2, p.W, p.T, p.P, p.F, p.K, t, 0, 0};
+    PathEnd<R> end;
+    path_forward<R>(p, at, src, end);
+    path_backtrace<R>(p, at, src, end);
 }
 
 // ----------------------------------------------------------------------------------------------------------------

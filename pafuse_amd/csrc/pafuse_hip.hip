@@ -94,6 +94,18 @@ int by_joint_slots(int J, F&& f) {
     }
 }
 
+// f(std::integral_constant<int, R>) for a kernel whose lanes keep R = 1 .. 4 items each in registers: count <= 256, which
+// the caller has checked
+template <class F>
+int by_lane_slots(int count, F&& f) {
+    switch ((count + 63) / 64) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
+
 // Makes the device of the caller's stream current for the duration of an entry point (kernel launches, events and
 // function attributes go to the CURRENT device): a caller whose tensors live on cuda:1 while cuda:0 is current
 // would otherwise record events on the wrong device.  The legacy null stream belongs to the current device.
@@ -2040,16 +2052,11 @@ int pafuse_pose_path(const float* pred, const float* x2d, const float* root, int
     unsigned grid;
     if (int rc = wave_grid("pose_path", (int64_t)B * T * J, grid)) return rc;   // one wave per (b, t, j)
     StreamDevice on_stream_device(stream);
-    PosePathParams m{};
+    PathParams m{};   // B clips: one window [0, F) each, no tables, no pick_win; slot = hypothesis
     m.pred = pred, m.x2d = x2d, m.root = root, m.cam = cam, m.conf = conf, m.conn = conn, m.mean = mean, m.weight = weight;
     m.pick = pick, m.pick_idx = pick_idx, m.pick_e2 = pick_e2, m.cost = cost, m.back = (uint8_t*)workspace;
-    m.B = B, m.T = T, m.P = P, m.F = F, m.J = J, m.root_per_h = root_per_hypothesis ? 1 : 0;
-    switch ((P + 63) / 64) {   // hypotheses per lane
-        case 1: return launch<pose_path_kernel<1>>("pose_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
-        case 2: return launch<pose_path_kernel<2>>("pose_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
-        case 3: return launch<pose_path_kernel<3>>("pose_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
-        default: return launch<pose_path_kernel<4>>("pose_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
-    }
+    m.V = B, m.W = 1, m.T = T, m.P = P, m.F = F, m.J = J, m.N = F, m.K = P, m.root_per_h = root_per_hypothesis ? 1 : 0;
+    return by_lane_slots(P, [&](auto r) { return launch<pose_path_kernel<decltype(r)::value>>("pose_path_kernel", grid, 256, 0, (hipStream_t)stream, m); });
 }
 
 namespace {
@@ -2113,17 +2120,12 @@ int pafuse_frames_path(const float* pred, const float* x2d, const float* root, i
     unsigned grid;
     if (int rc = wave_grid("frames_path", (int64_t)T * J, grid)) return rc;   // one wave per (t, j)
     StreamDevice on_stream_device(stream);
-    FramesPathParams m{};
+    PathParams m{};   // one video
     m.pred = pred, m.x2d = x2d, m.root = root, m.cam = cam, m.conf = conf, m.conn = conn, m.mean = mean, m.weight = weight;
     m.starts = starts, m.valid = valid;
     m.pick = pick, m.pick_idx = pick_idx, m.pick_win = pick_win, m.pick_e2 = pick_e2, m.cost = cost, m.back = (uint8_t*)workspace;
-    m.W = W, m.T = T, m.P = P, m.F = F, m.J = J, m.N = N, m.K = K, m.root_per_h = root_per_hypothesis ? 1 : 0;
-    switch ((K + 63) / 64) {   // slots per lane
-        case 1: return launch<frames_path_kernel<1>>("frames_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
-        case 2: return launch<frames_path_kernel<2>>("frames_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
-        case 3: return launch<frames_path_kernel<3>>("frames_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
-        default: return launch<frames_path_kernel<4>>("frames_path_kernel", grid, 256, 0, (hipStream_t)stream, m);
-    }
+    m.V = 1, m.W = W, m.T = T, m.P = P, m.F = F, m.J = J, m.N = N, m.K = K, m.root_per_h = root_per_hypothesis ? 1 : 0;
+    return by_lane_slots(K, [&](auto r) { return launch<frames_path_kernel<decltype(r)::value>>("frames_path_kernel", grid, 256, 0, (hipStream_t)stream, m); });
 }
 
 // state of pafuse_spread_partials: double sum[n][3] | double m2[n][6] | double count
@@ -2558,12 +2560,7 @@ int pafuse_bone_project(const float* pose, const float* cov, const int32_t* pare
     BoneProjectParams m{};
     m.pose = pose, m.cov = cov, m.parent = parent, m.length = length, m.out = out, m.code = code, m.resid = resid;
     m.T = T, m.N = N, m.J = J, m.iterations = iterations, m.snap = snap, m.floor = floor;
-    switch ((J + 63) / 64) {   // joints per lane
-        case 1: return launch<bone_project_kernel<1>>("bone_project_kernel", grid, 256, 0, (hipStream_t)stream, m);
-        case 2: return launch<bone_project_kernel<2>>("bone_project_kernel", grid, 256, 0, (hipStream_t)stream, m);
-        case 3: return launch<bone_project_kernel<3>>("bone_project_kernel", grid, 256, 0, (hipStream_t)stream, m);
-        default: return launch<bone_project_kernel<4>>("bone_project_kernel", grid, 256, 0, (hipStream_t)stream, m);
-    }
+    return by_lane_slots(J, [&](auto r) { return launch<bone_project_kernel<decltype(r)::value>>("bone_project_kernel", grid, 256, 0, (hipStream_t)stream, m); });
 }
 
 // the focal-length sums of every (t, frame) of the finished pose (frames_focal_sums_kernel) and the estimate from them

@@ -1133,6 +1133,30 @@ def combine_poses(states, shape, num_proposals, merged=None, want=("mean", "pick
 PATH_OUTPUTS = ("pick", "idx", "e2", "cost")
 
 
+def _path_call(who, names, want):
+    """What pose_path and frames_path share around their own shape checks.  Now: `want` checked against the outputs `names`
+    -> (want, buffers).  Once the shapes are known, buffers(frames, lines, need, workspace, dev) -> (out, workspace, ptr):
+    the outputs by name ("pick" [*frames,3], "idx" and - where named - "window" [*frames] int32 always, "e2" [*frames] and
+    "cost" [*lines] float64 when wanted), the checked workspace (a new one of `need` bytes for None) and the pointer of a
+    tensor that may be None."""
+    want = tuple(want)
+    _need(all(k in names for k in want) and want, f"{who}: want holds some of {names} - got {want}")
+
+    def buffers(frames, lines, need, workspace, dev):
+        out = {"pick": torch.empty(*frames, 3, device=dev)}
+        out.update((k, torch.empty(*frames, device=dev, dtype=torch.int32)) for k in ("idx", "window") if k in names)
+        if "e2" in want:
+            out["e2"] = torch.empty(*frames, device=dev)
+        if "cost" in want:
+            out["cost"] = torch.empty(*lines, device=dev, dtype=torch.float64)
+        if workspace is None:
+            workspace = _lib.workspace(need, dev, who)
+        _need(workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(),
+              f"{who}: workspace must be a uint8 buffer on {dev}")
+        return out, workspace, lambda t: None if t is None else _data(t)
+    return want, buffers
+
+
 def pose_path_workspace_bytes(B, T, P, F, J):
     """Bytes of the workspace pafuse_pose_path needs (the formula of pafuse_pose_path_workspace_bytes): one back-pointer
     byte per (b, t, j, f, h), rounded up to a multiple of 8."""
@@ -1149,8 +1173,7 @@ def pose_path(pred, conn, x2d, root, cam, weight, conf=None, mean=None, want=("p
     NaN.  `workspace`: a uint8 buffer of pose_path_workspace_bytes or more to use instead of a new one."""
     lib = _lib.load()
     B, T, P, F, J = _need_pred("pose_path", pred, axis="P")
-    want = tuple(want)
-    _need(all(k in PATH_OUTPUTS for k in want) and want, f"pose_path: want holds some of {PATH_OUTPUTS} - got {want}")
+    want, buffers = _path_call("pose_path", PATH_OUTPUTS, want)
     _need(T > 0 and P > 0 and F > 0 and J > 0, "pose_path: T, P, F, J > 0")
     _need(conn.numel() == J and conn.dtype == torch.int32, "pose_path: conn must be int32 [J]")
     per_h = root.dim() == 5
@@ -1160,18 +1183,9 @@ def pose_path(pred, conn, x2d, root, cam, weight, conf=None, mean=None, want=("p
     _need_tensors("pose_path", [pred, x2d, root, cam] + [t for t in (conf, mean) if t is not None], (conn,))
     weight = float(weight)
     dev = pred.device
-    out = {"pick": torch.empty(B, T, F, J, 3, device=dev), "idx": torch.empty(B, T, F, J, device=dev, dtype=torch.int32)}
-    if "e2" in want:
-        out["e2"] = torch.empty(B, T, F, J, device=dev)
-    if "cost" in want:
-        out["cost"] = torch.empty(B, T, J, device=dev, dtype=torch.float64)
     need = int(lib.pafuse_pose_path_workspace_bytes(B, T, P, F, J)) if P <= 256 and F <= 256 else 0   # beyond: the library refuses
     assert need == (pose_path_workspace_bytes(B, T, P, F, J) if P <= 256 and F <= 256 else 0)
-    if workspace is None:
-        workspace = _lib.workspace(need, dev, "pose_path")
-    _need(workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(),
-          f"pose_path: workspace must be a uint8 buffer on {dev}")
-    ptr = lambda t: None if t is None else _data(t)
+    out, workspace, ptr = buffers((B, T, F, J), (B, T, J), need, workspace, dev)
     with torch.cuda.device(dev):
         _lib.check(lib.pafuse_pose_path(
             _data(pred), _data(x2d), _data(root), int(per_h), cam.data_ptr(), ptr(conf), _data(conn), ptr(mean), weight,
@@ -1224,8 +1238,7 @@ def frames_path(pred, conn, x2d, root, cam, weight, starts, valid, conf=None, me
     instead of a new one."""
     lib = _lib.load()
     W, T, P, F, J = (int(v) for v in _need_pred("frames_path", pred, axis="P"))
-    want = tuple(want)
-    _need(all(k in FRAMES_PATH_OUTPUTS for k in want) and want, f"frames_path: want holds some of {FRAMES_PATH_OUTPUTS} - got {want}")
+    want, buffers = _path_call("frames_path", FRAMES_PATH_OUTPUTS, want)
     _need(W > 0 and T > 0 and P > 0 and F > 0 and J > 0, "frames_path: W, T, P, F, J > 0 (a video has at least one window)")
     _need(x2d.dim() == 3 and x2d.shape[0] > 0, "frames_path: x2d must be [N,J,2]")
     N = int(x2d.shape[0])
@@ -1243,21 +1256,11 @@ def frames_path(pred, conn, x2d, root, cam, weight, starts, valid, conf=None, me
           f"at most {FRAMES_PATH_MAX_CANDIDATES} candidates per frame")
     weight = float(weight)
     dev = pred.device
-    out = {"pick": torch.empty(T, N, J, 3, device=dev), "idx": torch.empty(T, N, J, device=dev, dtype=torch.int32),
-           "window": torch.empty(T, N, J, device=dev, dtype=torch.int32)}
-    if "e2" in want:
-        out["e2"] = torch.empty(T, N, J, device=dev)
-    if "cost" in want:
-        out["cost"] = torch.empty(T, J, device=dev, dtype=torch.float64)
     need = int(lib.pafuse_frames_path_workspace_bytes(N, T, J, P, W, hs.ctypes.data, hv.ctypes.data))
     assert need == frames_path_workspace_bytes(N, T, J, P, hs, hv)
-    if workspace is None:
-        workspace = _lib.workspace(need, dev, "frames_path")
-    _need(workspace.is_cuda and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(),
-          f"frames_path: workspace must be a uint8 buffer on {dev}")
+    out, workspace, ptr = buffers((T, N, J), (T, J), need, workspace, dev)
     import numpy as np
     dtab = torch.from_numpy(np.stack([hs, hv])).to(dev)     # the device copies the kernel reads
-    ptr = lambda t: None if t is None else _data(t)
     with torch.cuda.device(dev):
         _lib.check(lib.pafuse_frames_path(
             _data(pred), _data(x2d), _data(root), int(per_h), cam.data_ptr(), ptr(conf), _data(conn), ptr(mean), weight,

@@ -1,5 +1,5 @@
 """J-Agg coherent in time - the host statement, in numpy, of what pose_path_kernel (csrc/kernels.hpp,
-pafuse_pose_path) computes.
+pafuse_pose_path) computes: the recursion path_forward / path_backtrace on the candidates of a clip.
 
 J-Agg picks, per joint and per frame, the hypothesis whose reprojection is closest to the detection; every frame on its
 own, so the winner changes on sub-pixel differences of e2 and the joint jumps between hypotheses centimetres apart.  Here
@@ -37,8 +37,8 @@ weight at which a jump costs as much as its own projection onto the screen.  The
 What this is not: `path` / `pick` work per clip and cross neither clip seams nor pooled windows, and it is not a smoother of
 the pose values - every returned joint is still some hypothesis's joint.
 
-The path of a whole VIDEO (frames_path_kernel, pafuse_frames_path) is the same statement on more
-candidates: at video frame n the candidates are the pairs (window, hypothesis) of ALL windows that cover n.  Number them
+The path of a whole VIDEO (frames_path_kernel, pafuse_frames_path: the same device recursion) is the
+same statement on more candidates: at video frame n the candidates are the pairs (window, hypothesis) of ALL windows that cover n.  Number them
 g = w * P + h and give a window that does not cover a frame NaN offsets - unavailable -: `path` on that dense [W*P, N] array
 (frames_dense) is the wanted recursion along the N frames.  An unavailable candidate never wins under strict <, and ties
 go to the lower (w, h): the order in which the fold of the windows (windows.fold_pose) keeps its candidate, so weight 0 is

@@ -163,17 +163,50 @@ def test_small_shapes(shape):
 
 
 def test_one_window_is_pose_path():
+    """One clip call on a batch of B = 2 clips against two video calls of one window each: the same bits per clip in every
+    output, at one and at two slots per lane - the video stride of every operand and the decode of the line (v, t, j)."""
     from pafuse_amd import ops
-    v = Video(2, 5, 3, J, 3, 3, seed=61)
-    assert v.W == 1
-    for kind, gated in (("traj", False), ("fit", True)):
-        got = v.run(kind, 0.5, gated)
-        root = v.z["traj"] if kind == "traj" else v.tfit
-        clip = ops.pose_path(v.pred, v.conn, v.z["x2d"], root, v.cam, 0.5, conf=v.conf_w if gated else None, mean=v.mean[None].contiguous(),
-                             want=ops.PATH_OUTPUTS)
-        assert torch.equal(got["idx"], clip["idx"][0]) and same_bits(got["pick"], clip["pick"][0])      # (NaN on a line without a path)
-        assert torch.equal(got["window"], torch.where(got["idx"] >= 0, 0, -1).int()) and (got["idx"] >= 0).any()
-        assert same_bits(got["e2"], clip["e2"][0]) and same_bits(got["cost"], clip["cost"][0])
+    for P in (5, 65):
+        vs = [Video(2, P, 3, J, 3, 3, seed=61 + b) for b in range(2)]
+        assert all(v.W == 1 for v in vs)
+        batch = lambda pick: torch.cat([pick(v) for v in vs]).contiguous()
+        for kind in ("traj", "fit"):
+            for gated in (False, True):
+                root = batch(lambda v: v.z["traj"] if kind == "traj" else v.tfit)
+                clip = ops.pose_path(batch(lambda v: v.pred), vs[0].conn, batch(lambda v: v.z["x2d"]), root, vs[0].cam, 0.5,
+                                     conf=batch(lambda v: v.conf_w) if gated else None, mean=batch(lambda v: v.mean[None]),
+                                     want=ops.PATH_OUTPUTS)
+                for b, v in enumerate(vs):
+                    got, tag = v.run(kind, 0.5, gated), (P, kind, gated, b)
+                    assert torch.equal(got["idx"], clip["idx"][b]) and same_bits(got["pick"], clip["pick"][b]), tag   # (NaN on a line without a path)
+                    assert torch.equal(got["window"], torch.where(got["idx"] >= 0, 0, -1).int()) and (got["idx"] >= 0).any(), tag
+                    assert same_bits(got["e2"], clip["e2"][b]) and same_bits(got["cost"], clip["cost"][b]), tag
+        assert not torch.equal(vs[0].pred, vs[1].pred) and not torch.equal(clip["idx"][0], clip["idx"][1])   # two clips, not one twice
+
+
+@pytest.mark.parametrize("entry", ["clip", "video"])
+def test_without_e2_the_path_is_the_same(entry):
+    """want without "e2": pick_e2 is null - in the video kernel the observed mark of the forward pass then has nowhere to live
+    and the backtrace forms no e2 - and pick and idx keep the bits of the call that asks for e2 (conf gated, so that there
+    are unobserved frames)."""
+    from pafuse_amd import ops
+    if entry == "clip":                                  # (B,T,P,F) = (2,2,65,3), J = 5
+        g = torch.Generator().manual_seed(91)
+        pred = (torch.randn(2, 2, 65, 3, 5, 3, generator=g) * 0.25).to(DEV)
+        x2d = (torch.rand(2, 3, 5, 2, generator=g) * 2 - 1).to(DEV)
+        traj = torch.randn(2, 3, 3, generator=g) * 0.1
+        traj[..., 2] = 4.0
+        conf = (torch.rand(2, 3, 5, generator=g) >= 0.2).float().to(DEV)
+        conn = torch.tensor(C5, dtype=torch.int32, device=DEV)
+        run = lambda want: ops.pose_path(pred, conn, x2d, traj.to(DEV), sequence(1)[2].to(DEV), 0.5, conf=conf, want=want)
+        names = ops.PATH_OUTPUTS
+    else:
+        v = Video(*SMALL[2], seed=92)
+        run = lambda want: ops.frames_path(v.pred, v.conn, v.x2d, v.traj, v.cam, 0.5, v.starts, v.valid, conf=v.conf, mean=v.mean, want=want)
+        names = ops.FRAMES_PATH_OUTPUTS
+    full, bare = run(names), run(("pick", "idx"))
+    assert set(bare) == {"pick", "idx"} and (full["idx"] >= 0).any() and torch.isinf(full["e2"]).any()
+    assert torch.equal(bare["idx"], full["idx"]) and same_bits(bare["pick"], full["pick"])
 
 
 def test_zero_weight_is_the_pick_of_the_fold(big):

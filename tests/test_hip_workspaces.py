@@ -18,15 +18,16 @@ refusal, with and without a policy, and nothing else.
 THE INDEX-HOLDING WORKSPACES, read kernel by kernel before the first run (pafuse_amd/csrc/kernels.hpp) - every word is written by
 the call before it is read or used as an index; none needed a fix:
 
-  pose_path_kernel    back[line, f, h], one byte.  Forward pass: at every frame f >= 1 lane l stores back[f*P + r*64 + l] for every
-                      h = r*64 + l < P (R = ceil(P / 64) rounds cover P <= 256) - the value bp in [0, P), 0 when no predecessor
-                      wins.  Backtrace: reads back[f*P + h] for f >= 1 only (f == 0 takes 0), h the exact-zero slot of the last frame
-                      (< P) and then the bytes read, all < P.  A dead line returns before the backtrace.  A workgroup fence stands
-                      between the wave's stores and its loads.
-  frames_path_kernel  back[line, n, s], one byte.  Forward: at n >= 1 every slot s < k_n is stored, the value in [0, k_(n-1)).
-                      Backtrace: s < k_(N-1) at the last frame, then back[n*K + s] for n >= 1, which is < k_(n-1): a slot stored at
-                      n - 1 (or frame 0, which is not read).  The "observed" marks the backtrace reads live in the OUTPUT pick_e2,
-                      written for every n in the forward pass before they are read.
+  pose_path_kernel / frames_path_kernel: one recursion, path_forward and path_backtrace, on two candidate sources
+                      back[line, n, s], one byte (the clip kernel: n = f, s = h, k_n = K = P at every frame; the video kernel:
+                      k_n = P * the windows covering n).  Forward pass: at every frame n >= 1 lane l stores
+                      back[n*K + r*64 + l] for every slot s = r*64 + l < k_n (R = ceil(K / 64) rounds cover K <= 256) - the value in
+                      [0, k_(n-1)), 0 when no predecessor wins.  Backtrace: s is the exact-zero slot of the last frame (< k_(N-1)),
+                      then the byte back[n*K + s] for n >= 1 only (n == 0 takes 0), which is < k_(n-1): a slot stored at n - 1 (or of
+                      frame 0, whose row is neither stored nor read).  A dead line returns before the backtrace.  A workgroup fence
+                      stands between the wave's stores and its loads.  The "observed" marks the backtrace reads are not in the arena:
+                      the clip kernel keeps them in registers, the video kernel in the OUTPUT pick_e2 - written for every n in the
+                      forward pass before they are read, and neither written nor read when pick_e2 is null.
   track_nodes_kernel  size[n, k]: every (n, k) stored (NaN: absent) before track_links / track_path read it (stream order).
   track_links_kernel  gain[n, g, ka, kb]: every element stored - the absent branch stores the whole column over its lanes, the
                       other branch stores each ka from lane 0.
